@@ -14,11 +14,16 @@ engine.BatchesInFlight): the launch-bound once-per-batch prefix of step k+1 runs
 does all of its own work inside the timed region and its results are bit for bit the one-stream ones.
 
     python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3 --full   # + roofline, CPU baseline, other engines, RCCL probe (see below)
+    python bench.py --gpus 1 --steps 10 --warmup 3 --dump-outputs DIR     # + the last timed step's mean / var / logit_mean as DIR/*.npy
     python bench.py --gpus 8 --steps 10 --warmup 3          # starts its 8 rank processes itself (fresh children, torch.distributed.run)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port P \\
         bench.py --gpus 8 --steps 10 --warmup 3             # or under a launcher: RANK / LOCAL_RANK / WORLD_SIZE from the env
 
-Prints ONE JSON line (rank 0).  `roofline` is the DOMINANT kernel family of the step (the conv family with the largest
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the --steps steps and prints the headline: `value`, `ms_per_step`
+(wall time of the timed steps / --steps), the per-step completion spread, the engine type and the ECE of the last step.  Everything
+that takes runs of its own is measured only with --full: `roofline`, `cpu_baseline`, `parity` / `value_at_tolerance` and
+`allreduce_us_1rank`.  `roofline` is the DOMINANT kernel family of the step (the conv family with the largest
 share of the step time: conv3x3_pw / conv_igemm_wide / conv3x3_patch / conv_igemm): algorithmic FLOPs (or, where the HBM
 roofline is the tighter one, bytes) per launch / its average launch duration, measured by the library with HIP events on the
 launch stream in a separate profiled step right after the timed region (event records around every launch would perturb
@@ -48,6 +53,7 @@ HBM_PEAK_GBS = 8000.0           # HBM3E, same table
 LAUNCH_BOUND_MS = 1.5           # a rank's step under this is launch-bound: three batches in flight + one hipGraph replay per step (round 6: measured on the
                                 # exit-only ResNet-18 — probe 1.1 ms, +5.5 % — and VGG-19 — 1.2 ms, +4 % —; neutral at the Masksembles config's 2.2 ms)
 MODEL_KW = dict(dropout_exit=True, dropout="block", dropout_p=0.25, out_dim=10)
+DUMP_CAP_BYTES = 64 << 20       # --dump-outputs writes at most this much
 
 # name -> (package class, oracle class, kwargs, batch, T, description).  The default is the configuration BASELINE.json's
 # metric is quoted on; the others are measurement aids for the remaining GPU configs (not the driver's bench line).
@@ -102,9 +108,9 @@ def parse():
                          "5e-4 (models/_engine_mixin.py); on the synthetic bench weights that is f16, and the line says so (config.engine_dtype).  "
                          "f16 / bf16: 16-bit activations and conv weights (bf16 is reported next to f16); "
                          "f16x2 / bf16x3: the split engines (fp32 activations, 16-bit head + tail operands, three MFMAs per K-step: csrc/conv_split.hip)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and the other 16-bit engine")
     ap.add_argument("--no-parity-leg", action="store_true",
-                    help="N = 1: skip the tolerance leg (engine_dtype='auto' on the bench model and on its trained-like twin, and the rate of the engine "
+                    help="--full, N = 1: skip the tolerance leg (engine_dtype='auto' on the bench model and on its trained-like twin, and the rate of the engine "
                          "auto picks there: `parity_engine` / `value_at_tolerance`)")
     ap.add_argument("--cpu-procs", type=int, default=8, help="processes of the multi-process CPU-baseline sample (slices of the batch, 16 threads each; 0 = skip)")
     ap.add_argument("--cpu-worker", default="", help=argparse.SUPPRESS)      # internal: "lo,hi,T,threads" — one slice of the multi-process CPU baseline
@@ -128,10 +134,33 @@ def parse():
                          "than one rank the graph holds the rank's share and the all-reduce + finalize follow the replay eagerly")
     ap.add_argument("--partition", choices=("auto", "samples", "images"), default="auto",
                     help="how a batch x T samples is split over the ranks (sharding.partition): auto = by samples while T > ranks, by images otherwise")
-    ap.add_argument("--no-rccl-probe", action="store_true", help="N = 1: skip the one-rank RCCL probe (allreduce_us_1rank)")
+    ap.add_argument("--no-rccl-probe", action="store_true", help="--full, N = 1: skip the one-rank RCCL probe (allreduce_us_1rank)")
     ap.add_argument("--rccl-probe-only", action="store_true", help="N = 1: run only the one-rank RCCL probe and print its JSON (tests)")
     ap.add_argument("--dump-mean", default="", help="rank 0 writes the final predictive mean [E,B,C] float64 to this .npy (tests)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 writes what the last timed step returned (mean / var / logit_mean, float64 [E,B,C]) as DIR/<name>.npy; "
+                         f"over {DUMP_CAP_BYTES >> 20} MB in all, a fixed seeded sample of the images")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need, each in runs of its own after the timed steps: the per-kernel "
+                         "roofline (a profiled step), at N = 1 the CPU baseline and the other 16-bit engine (--no-cpu-baseline), the tolerance "
+                         "leg (--no-parity-leg) and the one-rank RCCL probe (--no-rccl-probe)")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps >= 1")
+    return a
+
+
+def dump_outputs(path, outs, seed=0):
+    """--dump-outputs: the arrays the timed path returned in its last step, one DIR/<name>.npy each.  Over DUMP_CAP_BYTES in all,
+    the same fixed, seeded sample of the images (axis 1 of [E, B, C]) is written for every array."""
+    os.makedirs(path, exist_ok=True)
+    total = sum(v.nbytes for v in outs.values())
+    keep = None
+    if total > DUMP_CAP_BYTES:
+        B = next(iter(outs.values())).shape[1]
+        keep = np.sort(np.random.default_rng(seed).choice(B, max(1, B * DUMP_CAP_BYTES // total), replace=False))
+    for name, v in outs.items():
+        np.save(os.path.join(path, f"{name}.npy"), v if keep is None else v[:, keep])
 
 
 def _family_match(kernel_name, family):
@@ -687,33 +716,26 @@ def main():
         tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
+    outs = {k: v.cpu().numpy() for k, v in out.items()} if rank == 0 else None      # what the last timed step returned
 
-    # ---- per-kernel profile (rank 0's share of the samples), outside the timed region ----------
-    eng.profile(True)
-    one_batch(eng, Ss[0])
-    torch.cuda.synchronize()
-    prof = eng.profile_read()
-    eng.profile(False)
+    if a.full:
+        # ---- per-kernel profile (rank 0's share of the samples), outside the timed region ----------
+        eng.profile(True)
+        one_batch(eng, Ss[0])
+        torch.cuda.synchronize()
+        prof = eng.profile_read()
+        eng.profile(False)
 
     if rank == 0:
         samples = B * T * a.steps
         value = samples / dt
-        my_T = t_hi - t_lo
-        # conv FLOPs of rank 0's profiled step: prefix convs once + suffix convs x its samples
-        my_B = B if share[0] == "samples" else share[2] - share[1]      # images of rank 0's profiled step
-        conv_flops = 2.0 * my_B * ((eng.prefix_macs) + my_T * (eng.suffix_macs - eng.head_macs - eng.dense_macs))
-        conv_ms, conv_launches = prof.get("conv_igemm", (0.0, 0))
-        conv_flops -= 2.0 * my_B * eng.stem_macs     # the 3-channel stem runs in its own direct kernel
-        achieved = conv_flops / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0
-        alg_launches = int(conv_launches)            # launches actually made (paired convs are one launch)
-        alg_bytes = sum(v["bytes"] for v in eng.conv_families.values())       # what the launches were priced at (lazy-site operands: B images + bits)
-        traffic, traffic_src = (hbm_traffic(a.workload, max(alg_launches, 1))
-                                if (world == 1 and not a.batch and not a.T and not a.chunk) else (None, None))
-        mean = out["mean"].cpu().numpy()
+        mean = outs["mean"]
         for e in pipe.engines:
             e.check_finite()                           # non-finite moment sums in any timed step are an error, not a number
         if a.dump_mean:
             np.save(a.dump_mean, mean)
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, outs)
         labels = synthetic_labels(B, kw["out_dim"], seed=1235).numpy()
         onehot = np.eye(kw["out_dim"])[labels]
         line = {
@@ -743,62 +765,74 @@ def main():
             "ece_note": "synthetic weights on uniform synthetic labels: plumbing (equal to the CPU oracle's at equal T), not calibration",
             "tflops_executed": round(eng.flops_per_batch(B, T) * a.steps / dt / 1e12, 2),
             "tflops_naive_equiv": round(2.0 * (eng.prefix_macs + eng.suffix_macs) * samples / dt / 1e12, 2),
-            "roofline": None,
         }
-        # ---- roofline: the DOMINANT kernel family of the step (largest share of the step time), priced against the roofline
-        # that bounds it: algorithmic FLOPs (or bytes) per launch / its average launch duration, HIP events on the launch
-        # stream.  `all_conv_launches` is the same for every conv launch together, `by_kernel` per family.
-        fam = eng.conv_families
-        # the split engines' kernel issues THREE MFMA instructions per algorithmic product (w_lo.x_hi + w_hi.x_lo + w_hi.x_hi): its MFMA
-        # roofline in algorithmic FLOPs is a third of the dense peak (`achieved` stays algorithmic, `mfma_work_factor` says so)
-        wf = lambda k: 3.0 if k == "conv_split_kernel" else 1.0
-        by_kernel = {k: {"launches": int(v["launches"]), "avg_launch_ms": round(v["ms"] / v["launches"], 4),
-                         "achieved": round(v["flops"] / (v["ms"] * 1e-3) / 1e12, 1),
-                         "mfma_work_factor": wf(k), "peak_algorithmic_tflops": round(MFMA_PEAK_TFLOPS / wf(k), 1),
-                         "frac": round(wf(k) * v["flops"] / (v["ms"] * 1e-3) / 1e12 / MFMA_PEAK_TFLOPS, 4),
-                         "hbm_gbs_algorithmic": round(v["bytes"] / (v["ms"] * 1e-3) / 1e9, 1),
-                         "hbm_frac": round(v["bytes"] / (v["ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                         "flop_per_byte": round(v["flops"] / max(v["bytes"], 1.0), 1),
-                         "algorithmic_flops_per_launch": round(v["flops"] / v["launches"]),
-                         "algorithmic_bytes_per_launch": round(v["bytes"] / v["launches"]),
-                         "bound": "mfma" if wf(k) * v["flops"] / MFMA_PEAK_TFLOPS / 1e12 >= v["bytes"] / HBM_PEAK_GBS / 1e9 else "hbm",
-                         **(pmc_sq(a.workload, k) if traffic is not None else {})}
-                     for k, v in fam.items()}
-        dom = max(fam, key=lambda k: fam[k]["ms"]) if fam else None
-        if dom is not None:
-            d = by_kernel[dom]
-            dom_traffic, _ = (hbm_traffic(a.workload, max(alg_launches, 1), dom) if traffic is not None else (None, None))
-            hbm_bound = d["bound"] == "hbm"
-            # the same family in the committed rocprofv3 summary of this command: its kernel's name as rocprof prints it, and the
-            # roofline fraction its average duration gives (the live HIP-event `frac` of THIS box beside it: boxes differ by 2-3 %)
-            rp = rocprof_family(a.workload, dom, d["launches"]) if (world == 1 and not a.batch and not a.T and not a.chunk and a.dtype == "f16") else None
-            per_launch = d["algorithmic_bytes_per_launch"] / 1e9 if hbm_bound else d["mfma_work_factor"] * d["algorithmic_flops_per_launch"] / 1e12
-            line["roofline"] = {
-                "bound": d["bound"], "kernel": rp[0] if rp else dom, "kernel_family": dom,
-                "frac_rocprof": None if rp is None else round(per_launch / (rp[1] * 1e-3) / (HBM_PEAK_GBS if hbm_bound else MFMA_PEAK_TFLOPS), 4),
-                "avg_launch_ms_rocprof": None if rp is None else round(rp[1], 4), "rocprof_source": None if rp is None else rp[3],
-                "dominant_by": "hip_event_ms (the conv family with the most device time in the profiled step; "
-                                                                   "quote whole_step.frac when comparing rounds)",
-                "rocprof_top_symbol": rocprof_top_symbol(a.workload) if rp else None,
-                "achieved": d["hbm_gbs_algorithmic"] if hbm_bound else d["achieved"],
-                "peak": HBM_PEAK_GBS if hbm_bound else d["peak_algorithmic_tflops"], "unit": "GB/s" if hbm_bound else "TFLOP/s",
-                "frac": d["hbm_frac"] if hbm_bound else d["frac"],
-                "traffic": None if dom_traffic is None else round(dom_traffic),
-                "traffic_unit": "fabric bytes per launch = L2 misses, Infinity-Cache hits included (PMC FETCH_SIZE x2 + WRITE_SIZE): an upper bound of the HBM bytes", "traffic_source": traffic_src,
-                "algorithmic_flops_per_launch": d["algorithmic_flops_per_launch"],
-                "algorithmic_bytes_per_launch": d["algorithmic_bytes_per_launch"],
-                "launches": d["launches"], "avg_launch_ms": d["avg_launch_ms"],
-                "share_of_step_ms": round(fam[dom]["ms"], 3),
-                "all_conv_launches": {"achieved": round(achieved, 2), "unit": "TFLOP/s", "frac": round(achieved / MFMA_PEAK_TFLOPS, 4),
-                                      "launches": int(conv_launches), "avg_launch_ms": round(conv_ms / max(conv_launches, 1), 4),
-                                      "traffic": None if traffic is None else round(traffic),
-                                      "algorithmic_bytes_per_launch": round(alg_bytes / max(alg_launches, 1)),
-                                      "algorithmic_flops_per_launch": round(conv_flops / max(conv_launches, 1))},
-                "whole_step": {"achieved": line["tflops_executed"], "unit": "TFLOP/s",
-                               "frac": round(line["tflops_executed"] / MFMA_PEAK_TFLOPS, 4)},
-                "by_kernel": by_kernel,
-                "profile_ms": {k: round(v[0], 3) for k, v in prof.items()}}
-        if not a.no_cpu_baseline and world == 1:        # the CPU baseline is reported at N=1 only
+        if a.full:
+            my_T = t_hi - t_lo
+            # conv FLOPs of rank 0's profiled step: prefix convs once + suffix convs x its samples
+            my_B = B if share[0] == "samples" else share[2] - share[1]      # images of rank 0's profiled step
+            conv_flops = 2.0 * my_B * ((eng.prefix_macs) + my_T * (eng.suffix_macs - eng.head_macs - eng.dense_macs))
+            conv_ms, conv_launches = prof.get("conv_igemm", (0.0, 0))
+            conv_flops -= 2.0 * my_B * eng.stem_macs     # the 3-channel stem runs in its own direct kernel
+            achieved = conv_flops / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0
+            alg_launches = int(conv_launches)            # launches actually made (paired convs are one launch)
+            alg_bytes = sum(v["bytes"] for v in eng.conv_families.values())       # what the launches were priced at (lazy-site operands: B images + bits)
+            traffic, traffic_src = (hbm_traffic(a.workload, max(alg_launches, 1))
+                                    if (world == 1 and not a.batch and not a.T and not a.chunk) else (None, None))
+            line["roofline"] = None
+            # ---- roofline: the DOMINANT kernel family of the step (largest share of the step time), priced against the roofline
+            # that bounds it: algorithmic FLOPs (or bytes) per launch / its average launch duration, HIP events on the launch
+            # stream.  `all_conv_launches` is the same for every conv launch together, `by_kernel` per family.
+            fam = eng.conv_families
+            # the split engines' kernel issues THREE MFMA instructions per algorithmic product (w_lo.x_hi + w_hi.x_lo + w_hi.x_hi): its MFMA
+            # roofline in algorithmic FLOPs is a third of the dense peak (`achieved` stays algorithmic, `mfma_work_factor` says so)
+            wf = lambda k: 3.0 if k == "conv_split_kernel" else 1.0
+            by_kernel = {k: {"launches": int(v["launches"]), "avg_launch_ms": round(v["ms"] / v["launches"], 4),
+                             "achieved": round(v["flops"] / (v["ms"] * 1e-3) / 1e12, 1),
+                             "mfma_work_factor": wf(k), "peak_algorithmic_tflops": round(MFMA_PEAK_TFLOPS / wf(k), 1),
+                             "frac": round(wf(k) * v["flops"] / (v["ms"] * 1e-3) / 1e12 / MFMA_PEAK_TFLOPS, 4),
+                             "hbm_gbs_algorithmic": round(v["bytes"] / (v["ms"] * 1e-3) / 1e9, 1),
+                             "hbm_frac": round(v["bytes"] / (v["ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                             "flop_per_byte": round(v["flops"] / max(v["bytes"], 1.0), 1),
+                             "algorithmic_flops_per_launch": round(v["flops"] / v["launches"]),
+                             "algorithmic_bytes_per_launch": round(v["bytes"] / v["launches"]),
+                             "bound": "mfma" if wf(k) * v["flops"] / MFMA_PEAK_TFLOPS / 1e12 >= v["bytes"] / HBM_PEAK_GBS / 1e9 else "hbm",
+                             **(pmc_sq(a.workload, k) if traffic is not None else {})}
+                         for k, v in fam.items()}
+            dom = max(fam, key=lambda k: fam[k]["ms"]) if fam else None
+            if dom is not None:
+                d = by_kernel[dom]
+                dom_traffic, _ = (hbm_traffic(a.workload, max(alg_launches, 1), dom) if traffic is not None else (None, None))
+                hbm_bound = d["bound"] == "hbm"
+                # the same family in the committed rocprofv3 summary of this command: its kernel's name as rocprof prints it, and the
+                # roofline fraction its average duration gives (the live HIP-event `frac` of THIS box beside it: boxes differ by 2-3 %)
+                rp = rocprof_family(a.workload, dom, d["launches"]) if (world == 1 and not a.batch and not a.T and not a.chunk and a.dtype == "f16") else None
+                per_launch = d["algorithmic_bytes_per_launch"] / 1e9 if hbm_bound else d["mfma_work_factor"] * d["algorithmic_flops_per_launch"] / 1e12
+                line["roofline"] = {
+                    "bound": d["bound"], "kernel": rp[0] if rp else dom, "kernel_family": dom,
+                    "frac_rocprof": None if rp is None else round(per_launch / (rp[1] * 1e-3) / (HBM_PEAK_GBS if hbm_bound else MFMA_PEAK_TFLOPS), 4),
+                    "avg_launch_ms_rocprof": None if rp is None else round(rp[1], 4), "rocprof_source": None if rp is None else rp[3],
+                    "dominant_by": "hip_event_ms (the conv family with the most device time in the profiled step; "
+                                                                       "quote whole_step.frac when comparing rounds)",
+                    "rocprof_top_symbol": rocprof_top_symbol(a.workload) if rp else None,
+                    "achieved": d["hbm_gbs_algorithmic"] if hbm_bound else d["achieved"],
+                    "peak": HBM_PEAK_GBS if hbm_bound else d["peak_algorithmic_tflops"], "unit": "GB/s" if hbm_bound else "TFLOP/s",
+                    "frac": d["hbm_frac"] if hbm_bound else d["frac"],
+                    "traffic": None if dom_traffic is None else round(dom_traffic),
+                    "traffic_unit": "fabric bytes per launch = L2 misses, Infinity-Cache hits included (PMC FETCH_SIZE x2 + WRITE_SIZE): an upper bound of the HBM bytes", "traffic_source": traffic_src,
+                    "algorithmic_flops_per_launch": d["algorithmic_flops_per_launch"],
+                    "algorithmic_bytes_per_launch": d["algorithmic_bytes_per_launch"],
+                    "launches": d["launches"], "avg_launch_ms": d["avg_launch_ms"],
+                    "share_of_step_ms": round(fam[dom]["ms"], 3),
+                    "all_conv_launches": {"achieved": round(achieved, 2), "unit": "TFLOP/s", "frac": round(achieved / MFMA_PEAK_TFLOPS, 4),
+                                          "launches": int(conv_launches), "avg_launch_ms": round(conv_ms / max(conv_launches, 1), 4),
+                                          "traffic": None if traffic is None else round(traffic),
+                                          "algorithmic_bytes_per_launch": round(alg_bytes / max(alg_launches, 1)),
+                                          "algorithmic_flops_per_launch": round(conv_flops / max(conv_launches, 1))},
+                    "whole_step": {"achieved": line["tflops_executed"], "unit": "TFLOP/s",
+                                   "frac": round(line["tflops_executed"] / MFMA_PEAK_TFLOPS, 4)},
+                    "by_kernel": by_kernel,
+                    "profile_ms": {k: round(v[0], 3) for k, v in prof.items()}}
+        if a.full and not a.no_cpu_baseline and world == 1:        # the CPU baseline is reported at N=1 only
             cpu_val, threads, cpu_mean, sweep = cpu_baseline(wl, B, a.cpu_T, a.seed)
             gpu_same = eng.predict(x, a.cpu_T, seed=a.seed)["mean"].cpu().numpy()
             other = "bf16" if a.dtype == "f16" else "f16"          # the other 16-bit instantiation (split engines: plain fp16) on the same inputs / masks
@@ -823,11 +857,11 @@ def main():
                 "max_abs_mean_diff_gpu_vs_cpu": float(np.abs(gpu_same - cpu_mean).max()),
                 f"max_abs_mean_diff_gpu_{other}_vs_cpu": float(np.abs(gpu_other - cpu_mean).max()),
             }
-        if world == 1 and not a.no_parity_leg and a.dtype == "f16":
+        if a.full and world == 1 and not a.no_parity_leg and a.dtype == "f16":
             line["parity"] = tolerance_leg(model, dev, x, B, T, a.seed, max(3, a.steps // 2), rec=auto_rec)
             line["parity_engine"] = line["parity"].get("parity_engine")
             line["value_at_tolerance"] = line["parity"].get("value_at_tolerance")
-        if world == 1 and not a.no_rccl_probe:       # after everything timed: RCCL executed once on this GPU (SURVEY 8.5, round-4 review item 5)
+        if a.full and world == 1 and not a.no_rccl_probe:       # after everything timed: RCCL executed once on this GPU (SURVEY 8.5, round-4 review item 5)
             line["allreduce_us_1rank"] = rccl_probe_in_a_child(a)
         print(json.dumps(line), flush=True)
     if dist is not None:

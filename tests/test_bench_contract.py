@@ -1,5 +1,5 @@
 """bench.py prints ONE JSON line with the fields the driver reads (metric/value/unit/n_gpus/steps/warmup/ms_per_step/
-higher_is_better/scaling/vs_baseline/dtype/data/config) plus `roofline` and, at N=1, `cpu_baseline`."""
+higher_is_better/scaling/vs_baseline/dtype/data/config) plus, with --full, `roofline` and, at N=1, `cpu_baseline`."""
 import json
 import os
 import subprocess
@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.mark.gpu
 def test_bench_prints_the_contract_line():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--cpu-T", "1"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--full", "--cpu-T", "1"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.strip().split("\n") if ln.startswith("{")]
@@ -54,6 +54,33 @@ def test_bench_prints_the_contract_line():
     assert d["parity_engine"] == "f16x2" and 0.2 < d["value_at_tolerance"] / d["value"] < 0.45
     top = rf.get("rocprof_top_symbol")
     assert top is None or (top["name"].startswith("conv") and 0 < top["share_of_kernel_time"] < 1)
+
+
+@pytest.mark.gpu
+def test_plain_bench_is_lean_and_dumps_its_outputs(tmp_path):
+    """A plain run (no --full) carries the headline only, and --dump-outputs writes what the last timed step returned: mean / var /
+    logit_mean, float64 [E, B, C], the mean equal to --dump-mean's.  The inputs are seeded: two runs write the same arrays."""
+    import numpy as np
+    runs = []
+    for i in range(2):
+        out = tmp_path / f"out{i}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", str(out), "--dump-mean", str(tmp_path / f"m{i}.npy")],
+                           capture_output=True, text=True, timeout=900, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.strip().split("\n") if ln.startswith("{")]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "MCD-samples/s" and d["higher_is_better"] is True and d["dtype"] == "f16"
+        assert abs(d["value"] - 250 * 100 / (d["ms_per_step"] * 1e-3)) / d["value"] < 0.01
+        assert not {"roofline", "cpu_baseline", "parity", "value_at_tolerance", "allreduce_us_1rank"} & set(d)
+        assert sorted(os.listdir(out)) == ["logit_mean.npy", "mean.npy", "var.npy"]
+        arrs = {f[:-len(".npy")]: np.load(out / f) for f in os.listdir(out)}
+        assert all(v.dtype == np.float64 and v.shape == (4, 250, 10) for v in arrs.values())
+        assert np.array_equal(arrs["mean"], np.load(tmp_path / f"m{i}.npy"))
+        np.testing.assert_allclose(arrs["mean"].sum(-1), 1.0, atol=1e-6)
+        runs.append(arrs)
+    assert all(np.array_equal(runs[0][k], runs[1][k]) for k in runs[0])
 
 
 @pytest.mark.gpu

@@ -81,26 +81,34 @@ def test_state_dict_route(tmp_path):
     assert state_checksum(a.state_dict()) == state_checksum(b.state_dict())
 
 
-REF = "/root/reference/Software_Artifact/software"
-
-
-@pytest.mark.skipif(not __import__("os").path.isdir(REF), reason="reference checkout not present (build container only)")
 def test_real_reference_pickle_round_trip(tmp_path):
-    """A pickle written by the reference's own classes (in a subprocess, so its `models`/`utils`
-    modules never enter this process) loads as this package's classes with identical state."""
-    import subprocess
-    path = tmp_path / "final_model_ref"
-    code = (
-        "import sys, torch, numpy as np; sys.dont_write_bytecode=True; sys.path.insert(0, %r)\n"
-        "from models.resnet18.resnet18 import ResNet18MCEarlyExit\n"
-        "torch.manual_seed(0); np.random.seed(0)\n"
-        "m = ResNet18MCEarlyExit(dropout_exit=True, dropout='block', mask_type='mask', num_masks=4, out_dim=10)\n"
-        "torch.save(m, %r)\n" % (REF, str(path)))
-    subprocess.run([sys.executable, "-c", code], check=True, env={"PYTHONDONTWRITEBYTECODE": "1", "PATH": "/usr/bin:/bin"})
-    m = checkpoint.load_model(str(path))
-    assert type(m) is bres.ResNet18MCEarlyExit and type(m.layer1[1]) is butils.Masksembles2D
+    """A pickle written by the reference's own classes loads as this package's classes with identical state.
+    tests/golden/reference_pickle.npz (tools/gen_golden.py) holds that archive's object graph verbatim and each tensor storage as
+    the sha256 of its bytes; the storages are refilled from this package's model built under the same seeds, matched by digest, so
+    the archive loaded here is byte for byte the reference's."""
+    import hashlib
+    import zipfile
+    from tests.helpers import load_golden
+    g = load_golden("reference_pickle.npz")
     torch.manual_seed(0)
     np.random.seed(0)
     want = bres.ResNet18MCEarlyExit(dropout_exit=True, dropout="block", mask_type="mask", num_masks=4, out_dim=10)
+    assert state_checksum(want.state_dict()) == str(g["state_sha256"])
+    by_digest = {}
+    for t in want.state_dict().values():
+        raw = torch.empty(0, dtype=torch.uint8).set_(t.untyped_storage()).numpy().tobytes()
+        by_digest[hashlib.sha256(raw).hexdigest()] = raw
+    missing = [k for k, h in zip(g["storage_keys"], g["storage_sha256"]) if h not in by_digest]
+    assert not missing, f"storages of the reference's pickle with no byte-equal tensor in this package's model: {missing}"
+    prefix = str(g["archive"])
+    path = tmp_path / prefix
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_STORED) as z:
+        z.writestr(f"{prefix}/data.pkl", g["data_pkl"].tobytes())
+        for name, value in zip(g["record_names"], g["record_values"]):
+            z.writestr(f"{prefix}/{name}", str(value))
+        for key, h in zip(g["storage_keys"], g["storage_sha256"]):
+            z.writestr(f"{prefix}/data/{key}", by_digest[h])
+    m = checkpoint.load_model(str(path))
+    assert type(m) is bres.ResNet18MCEarlyExit and type(m.layer1[1]) is butils.Masksembles2D
     assert state_checksum(m.state_dict()) == state_checksum(want.state_dict())
     assert m.layer1[1].cnt == 0 and m.dropout == "block"

@@ -340,6 +340,33 @@ def gen_philox():
     np.savez_compressed(os.path.join(OUT, "philox_masks.npz"), cases=np.array(cases, dtype=object), allow_pickle=True)
 
 
+def gen_reference_pickle():
+    """A whole-module pickle written by the reference's own ResNet18MCEarlyExit (torch.save, as its training loop saves final_model_*):
+    the archive's object graph (data.pkl) and small records verbatim, each tensor storage only as the sha256 of its bytes (the storages
+    are 60 MB; tests/test_checkpoint.py refills them from this package's model built under the same seeds and checks every digest)."""
+    import tempfile
+    import zipfile
+    torch.manual_seed(0)
+    np.random.seed(0)
+    m = ResNet18MCEarlyExit(dropout_exit=True, dropout="block", mask_type="mask", num_masks=4, out_dim=10)
+    with tempfile.TemporaryDirectory() as d:
+        path = os.path.join(d, "final_model_ref")
+        torch.save(m, path)
+        z = zipfile.ZipFile(path)
+        names = z.namelist()
+        prefix = names[0].split("/")[0]
+        rel = [n[len(prefix) + 1:] for n in names]
+        storages = [r for r in rel if r.startswith("data/")]
+        records = [r for r in rel if r != "data.pkl" and not r.startswith("data/")]
+        np.savez_compressed(os.path.join(OUT, "reference_pickle.npz"),
+                            archive=np.array(prefix), data_pkl=np.frombuffer(z.read(f"{prefix}/data.pkl"), dtype=np.uint8),
+                            record_names=np.array(records), record_values=np.array([z.read(f"{prefix}/{r}").decode() for r in records]),
+                            storage_keys=np.array([s[len("data/"):] for s in storages]),
+                            storage_sha256=np.array([hashlib.sha256(z.read(f"{prefix}/{s}")).hexdigest() for s in storages]),
+                            state_sha256=np.array(state_checksum(m.state_dict())))
+    print("reference_pickle ok")
+
+
 def converter_cnn():
     """The small sequential CNN of the converter fixtures (shared with tests/helpers.py by construction order)."""
     from torch import nn
@@ -492,6 +519,9 @@ if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "converter_vgg":
         gen_converter_vgg()
         sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "reference_pickle":
+        gen_reference_pickle()
+        sys.exit(0)
     gen_converter()
     gen_converter_resnet()
     gen_converter_vgg()
@@ -504,3 +534,4 @@ if __name__ == "__main__":
     gen_confidence_exiting()
     gen_resnet()
     gen_vgg()
+    gen_reference_pickle()
