@@ -96,6 +96,7 @@ struct bmi_engine_s {
     size_t head_off = 0, head_part_bytes = 0;   // float64 partial sums of a head launch's 32-sample groups (joined in group order), one region per exit
     // bmi_forward_mcd_samples: per-sample logits out, Masksembles masks walked with a stride
     float* logits_out = nullptr;         // (run time) [t_count][E][batch][C] of the current call, or null
+    double* sh_out = nullptr;            // (run time) bmi_forward_mcd_entropy: [E][batch] sums of the per-sample entropies, or null
     bool no_moments = false;             // (run time) the heads write per-sample logits only
     int logits_t_begin = 0, logits_batch = 0;
     int mask_stride = 1, mask_t_begin = 0;    // (run time) mask_permuted: a site's mask of sample t is row (t - mask_t_begin) % M of its PERMUTED table
@@ -761,7 +762,8 @@ int bmi_plan(bmi_handle h, int32_t max_batch, int32_t chunk_samples, size_t* wor
     }
     off += sk_bytes;
     h->head_off = off;
-    h->head_part_bytes = align_up((size_t)((chunk_samples + 31) / 32) * 3 * max_batch * h->out_dim * sizeof(double), 256);
+    // [groups][3][B][C] moment partials + [groups][B] entropy partials (bmi_forward_mcd_entropy)
+    h->head_part_bytes = align_up((size_t)((chunk_samples + 31) / 32) * max_batch * (3 * h->out_dim + 1) * sizeof(double), 256);
     off += h->head_part_bytes * (size_t)h->n_exits;      // one region per exit: the heads of a batched launch (launch_head_fused_multi) run concurrently
     h->perm.clear();
     for (const std::vector<OpInfo>* ops : {&h->prefix, &h->suffix})
@@ -883,6 +885,7 @@ HeadArgs make_head_args(bmi_engine_s* e, const OpInfo& op, char* ws, int N, int 
     const size_t eo = (size_t)d.out * B * e->out_dim;
     a.S1 = S1 + eo; a.S2 = S2 + eo; a.SL = SL + eo;
     if (e->no_moments) a.S1 = a.S2 = a.SL = nullptr;
+    if (e->sh_out && !e->no_moments) a.SH = e->sh_out + (size_t)d.out * B;     // this exit's [batch] row of the entropy sums
     a.part = (double*)(ws + e->head_off + (size_t)d.out * e->head_part_bytes);     // this exit's own region
     if (e->logits_out) {            // per-sample logits of this exit: [t - t_begin][E][batch][C]
         const size_t plane = (size_t)e->logits_batch * e->out_dim;
@@ -1278,6 +1281,17 @@ int bmi_forward_mcd_images(bmi_handle h, const float* x_nchw, int32_t batch, int
     return rc;
 }
 
+int bmi_forward_mcd_entropy(bmi_handle h, const float* x_nchw, int32_t batch, int32_t image_offset, int32_t t_begin,
+                            int32_t t_count, uint64_t seed, int32_t mask_cnt0, double* S1, double* S2, double* SL, double* SH,
+                            void* workspace, size_t workspace_bytes, bmi_stream stream) {
+    if (!h || !SH) return BMI_ERR_INVALID;
+    h->sh_out = SH;
+    const int rc = bmi_forward_mcd_images(h, x_nchw, batch, image_offset, t_begin, t_count, seed, mask_cnt0, S1, S2, SL, workspace,
+                                          workspace_bytes, stream);
+    h->sh_out = nullptr;
+    return rc;
+}
+
 int bmi_forward_mcd(bmi_handle h, const float* x_nchw, int32_t batch, int32_t t_begin, int32_t t_count, uint64_t seed,
                     int32_t mask_cnt0, double* S1, double* S2, double* SL, void* workspace, size_t workspace_bytes,
                     bmi_stream stream) {
@@ -1403,6 +1417,15 @@ int bmi_finalize_checked(int64_t n, int32_t t_total, const double* S1, const dou
                          double* var, double* logit_mean, int32_t* nonfinite, bmi_stream stream) {
     if (!S1 || !S2 || !SL || !mean || !var || !logit_mean || !nonfinite) return BMI_ERR_INVALID;
     return launch_finalize(n, t_total, S1, S2, SL, mean, var, logit_mean, nonfinite, (hipStream_t)stream);
+}
+
+int bmi_finalize_uncertainty(int32_t n_exits, int32_t batch, int32_t out_dim, int32_t t_total, const double* S1, const double* SH,
+                             double* pred_entropy, double* exp_entropy, double* mutual_info, int32_t* nonfinite, bmi_stream stream) {
+    if (!S1 || !SH || !pred_entropy || !exp_entropy || !mutual_info || n_exits < 1 || batch < 1 || out_dim < 1 || t_total < 1)
+        return BMI_ERR_INVALID;
+    if ((int64_t)n_exits * batch > INT32_MAX) return BMI_ERR_UNSUPPORTED;
+    return launch_finalize_uncertainty(n_exits * batch, out_dim, t_total, S1, SH, pred_entropy, exp_entropy, mutual_info, nonfinite,
+                                       (hipStream_t)stream);
 }
 
 int bmi_profile_enable(bmi_handle h, int32_t enable) {

@@ -42,7 +42,9 @@ typedef _Float16 half8_h __attribute__((ext_vector_type(8)));
 // softmax reads), the feature chunk is 256 deep (32 KB) and a wave stages its [32 classes][32 k] weight blocks in 4.5 KB of
 // its own (8 lanes per 128-byte row segment instead of one 2 KB row per lane): 66 KB of LDS, two workgroups per CU.
 // The kernel body, shared by the one-head launch and the batched one (head_fused_multi_kernel: blockIdx.z = which head of the pack).
-template <int RT, int KIND, bool CSPLIT>
+// ENT: the per-sample entropies into a.SH as well (bmi_forward_mcd_entropy) — a template parameter, not a runtime branch: as a branch
+// it moved the register counts of the default instantiations, which must stay what they were.
+template <int RT, int KIND, bool CSPLIT, bool ENT>
 __device__ __forceinline__ void head_body(const HeadArgs& a) {
     static_assert(!CSPLIT || (RT >= 3 && RT <= 4), "class split: one wave per class tile");
     constexpr int KC = CSPLIT ? 256 : HEAD_KC;                 // K chunk held in LDS (floats per sample)
@@ -310,6 +312,20 @@ __device__ __forceinline__ void head_body(const HeadArgs& a) {
                     const int c = 32 * i + (e & 3) + 8 * (e >> 2) + 4 * hh;
                     if (c < C) pb_p[c * 33 + r] = pb_p[c * 33 + r] / sum;      // same quotient the per-sample path stored
                 }
+            if constexpr (ENT) {
+                // the sample's entropy in log-softmax form, H = log(sum) - sum_c p_c (l_c - mx): no log of an underflowed p, so peaky
+                // logits give no NaN; from this lane's own LDS entries, parked in the padding column 32 of pb_p (row r = sample r)
+                float dot = 0.f;
+#pragma unroll
+                for (int i = 0; i < RT; ++i)
+#pragma unroll
+                    for (int e = 0; e < 16; ++e) {
+                        const int c = 32 * i + (e & 3) + 8 * (e >> 2) + 4 * hh;
+                        if (c < C) dot += pb_p[c * 33 + r] * (pb_l[c * 33 + r] - mx);
+                    }
+                dot += __shfl_xor(dot, 32);
+                if (hh == 0) pb_p[r * 33 + 32] = logf(sum) - dot;
+            }
         }
         __syncthreads();
         // ---- moments: 32 lanes = the group's 32 samples of one class; float64 wavefront-shuffle butterfly; two classes per
@@ -346,13 +362,24 @@ __device__ __forceinline__ void head_body(const HeadArgs& a) {
                     }
                 }
             }
+            if (ENT && wave == 0) {
+                // the group's 32 per-sample entropies, float64 butterfly as above; written the three ways S1 is
+                double h = live ? (double)pb_p[ts * 33 + 32] : 0.0;
+#pragma unroll
+                for (int m = 16; m >= 1; m >>= 1) h += __shfl_xor(h, m);
+                if (lane == 0) {
+                    if (a.part) a.part[(size_t)((a.tc + 31) / 32) * 3 * a.B * C + (size_t)g * a.B + b] = h;
+                    else if (gridDim.y == 1) a.SH[b] += h;
+                    else unsafeAtomicAdd(a.SH + b, h);
+                }
+            }
         }
     }
 }
 
-template <int RT, int KIND, bool CSPLIT = false>
+template <int RT, int KIND, bool CSPLIT = false, bool ENT = false>
 __global__ __launch_bounds__(256, CSPLIT ? 2 : 1) void head_fused_kernel(HeadArgs a) {
-    head_body<RT, KIND, CSPLIT>(a);
+    head_body<RT, KIND, CSPLIT, ENT>(a);
 }
 
 // Several exit heads in ONE launch (round 6): with exit-only dropout — the configuration every run of the paper uses,
@@ -361,17 +388,18 @@ __global__ __launch_bounds__(256, CSPLIT ? 2 : 1) void head_fused_kernel(HeadArg
 // runs the one-head body on its head's arguments (same arithmetic, same bits; tests/test_full_batch.py).  The heads of a pack agree in
 // everything the template parameters and the grid depend on (class tiles, input kind, images, samples); launch_head_fused_multi checks.
 struct HeadArgsPack { HeadArgs a[BMI_HEAD_PACK_MAX]; };
-template <int RT, int KIND, bool CSPLIT = false>
+template <int RT, int KIND, bool CSPLIT = false, bool ENT = false>
 __global__ __launch_bounds__(256, CSPLIT ? 2 : 1) void head_fused_multi_kernel(HeadArgsPack p) {
-    head_body<RT, KIND, CSPLIT>(p.a[blockIdx.z]);
+    head_body<RT, KIND, CSPLIT, ENT>(p.a[blockIdx.z]);
 }
 
 // Joins the per-group partial sums of an image in GROUP ORDER into the caller's accumulators: with hardware float64 atomics the
 // groups met in whatever order the workgroups finished, and the last bit of the sums of more than 64 samples changed from run to
 // run (round-2 verdict); an ordered "last arriver adds all" reduction inside the head kernel needed agent-scope fences that doubled
 // it.  This is one more launch of B x C threads per exit and chunk (~3 us), only when a launch carries more than 32 samples.
+// SH (or null): the [groups][B] entropy plane behind the moment planes joins the same way, by the thread of class 0 of each image.
 __global__ __launch_bounds__(256) void head_join_kernel(const double* __restrict__ part, int groups, int B, int C, const int* imap, int Bc,
-                                                        double* S1, double* S2, double* SL) {
+                                                        double* S1, double* S2, double* SL, double* SH) {
     const int rows = imap ? Bc : B;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= rows * C) return;
@@ -384,9 +412,18 @@ __global__ __launch_bounds__(256) void head_join_kernel(const double* __restrict
         s1 += pp[0]; s2 += pp[plane]; sl += pp[2 * plane];
     }
     S1[o] += s1; S2[o] += s2; SL[o] += sl;
+    if (SH && c == 0) {
+        const double* ph = part + (size_t)groups * 3 * plane + b;
+        double sh = 0.0;
+        for (int g = 0; g < groups; ++g) sh += ph[(size_t)g * B];
+        SH[b] += sh;
+    }
 }
 
-struct HeadJoinPack { const double* part[BMI_HEAD_PACK_MAX]; double *S1[BMI_HEAD_PACK_MAX], *S2[BMI_HEAD_PACK_MAX], *SL[BMI_HEAD_PACK_MAX]; };
+struct HeadJoinPack {
+    const double* part[BMI_HEAD_PACK_MAX];
+    double *S1[BMI_HEAD_PACK_MAX], *S2[BMI_HEAD_PACK_MAX], *SL[BMI_HEAD_PACK_MAX], *SH[BMI_HEAD_PACK_MAX];
+};
 __global__ __launch_bounds__(256) void head_join_multi_kernel(HeadJoinPack p, int groups, int B, int C) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= B * C) return;
@@ -398,20 +435,28 @@ __global__ __launch_bounds__(256) void head_join_multi_kernel(HeadJoinPack p, in
         s1 += pp[0]; s2 += pp[plane]; sl += pp[2 * plane];
     }
     p.S1[z][o] += s1; p.S2[z][o] += s2; p.SL[z][o] += sl;
+    if (p.SH[z] && i % C == 0) {
+        const int b = i / C;
+        const double* ph = p.part[z] + (size_t)groups * 3 * plane + b;
+        double sh = 0.0;
+        for (int g = 0; g < groups; ++g) sh += ph[(size_t)g * B];
+        p.SH[z][b] += sh;
+    }
 }
 
 template <int RT>
 static void launch_rt_multi(const HeadArgsPack& p, int n, hipStream_t s) {
     const HeadArgs& a = p.a[0];
     const dim3 grid((unsigned)a.B, (unsigned)((a.tc + 31) / 32), (unsigned)n), block(256);
-#define HEAD_LAUNCH_M(CS)                                                                                                 \
+#define HEAD_LAUNCH_ME(CS, EN)                                                                                            \
     switch (a.in_kind) {                                                                                                  \
-        case 1: hipLaunchKernelGGL((head_fused_multi_kernel<RT, 1, CS>), grid, block, 0, s, p); break;                    \
-        case 2: hipLaunchKernelGGL((head_fused_multi_kernel<RT, 2, CS>), grid, block, 0, s, p); break;                    \
-        case 3: hipLaunchKernelGGL((head_fused_multi_kernel<RT, 3, CS>), grid, block, 0, s, p); break;                    \
-        case 4: hipLaunchKernelGGL((head_fused_multi_kernel<RT, 4, CS>), grid, block, 0, s, p); break;                    \
-        default: hipLaunchKernelGGL((head_fused_multi_kernel<RT, 0, CS>), grid, block, 0, s, p); break;                   \
+        case 1: hipLaunchKernelGGL((head_fused_multi_kernel<RT, 1, CS, EN>), grid, block, 0, s, p); break;                \
+        case 2: hipLaunchKernelGGL((head_fused_multi_kernel<RT, 2, CS, EN>), grid, block, 0, s, p); break;                \
+        case 3: hipLaunchKernelGGL((head_fused_multi_kernel<RT, 3, CS, EN>), grid, block, 0, s, p); break;                \
+        case 4: hipLaunchKernelGGL((head_fused_multi_kernel<RT, 4, CS, EN>), grid, block, 0, s, p); break;                \
+        default: hipLaunchKernelGGL((head_fused_multi_kernel<RT, 0, CS, EN>), grid, block, 0, s, p); break;               \
     }
+#define HEAD_LAUNCH_M(CS) if (a.SH) { HEAD_LAUNCH_ME(CS, true) } else { HEAD_LAUNCH_ME(CS, false) }
     if constexpr (RT >= 3) {
         static const int csplit = [] { const char* v = std::getenv("BMI_HEAD_CSPLIT"); return v ? std::atoi(v) : 1; }();
         if (csplit) {
@@ -421,19 +466,21 @@ static void launch_rt_multi(const HeadArgsPack& p, int n, hipStream_t s) {
     }
     HEAD_LAUNCH_M(false)
 #undef HEAD_LAUNCH_M
+#undef HEAD_LAUNCH_ME
 }
 
 template <int RT>
 static void launch_rt(const HeadArgs& a, hipStream_t s) {
     const dim3 grid((unsigned)(a.imap ? a.Bc : a.B), (unsigned)((a.tc + 31) / 32)), block(256);
-#define HEAD_LAUNCH(CS)                                                                                                   \
+#define HEAD_LAUNCH_E(CS, EN)                                                                                             \
     switch (a.in_kind) {                                                                                                  \
-        case 1: hipLaunchKernelGGL((head_fused_kernel<RT, 1, CS>), grid, block, 0, s, a); break;                          \
-        case 2: hipLaunchKernelGGL((head_fused_kernel<RT, 2, CS>), grid, block, 0, s, a); break;                          \
-        case 3: hipLaunchKernelGGL((head_fused_kernel<RT, 3, CS>), grid, block, 0, s, a); break;                          \
-        case 4: hipLaunchKernelGGL((head_fused_kernel<RT, 4, CS>), grid, block, 0, s, a); break;                          \
-        default: hipLaunchKernelGGL((head_fused_kernel<RT, 0, CS>), grid, block, 0, s, a); break;                         \
+        case 1: hipLaunchKernelGGL((head_fused_kernel<RT, 1, CS, EN>), grid, block, 0, s, a); break;                      \
+        case 2: hipLaunchKernelGGL((head_fused_kernel<RT, 2, CS, EN>), grid, block, 0, s, a); break;                      \
+        case 3: hipLaunchKernelGGL((head_fused_kernel<RT, 3, CS, EN>), grid, block, 0, s, a); break;                      \
+        case 4: hipLaunchKernelGGL((head_fused_kernel<RT, 4, CS, EN>), grid, block, 0, s, a); break;                      \
+        default: hipLaunchKernelGGL((head_fused_kernel<RT, 0, CS, EN>), grid, block, 0, s, a); break;                     \
     }
+#define HEAD_LAUNCH(CS) if (a.SH) { HEAD_LAUNCH_E(CS, true) } else { HEAD_LAUNCH_E(CS, false) }
     if constexpr (RT >= 3) {
         static const int csplit = [] { const char* v = std::getenv("BMI_HEAD_CSPLIT"); return v ? std::atoi(v) : 1; }();
         if (csplit) {
@@ -443,13 +490,15 @@ static void launch_rt(const HeadArgs& a, hipStream_t s) {
     }
     HEAD_LAUNCH(false)
 #undef HEAD_LAUNCH
+#undef HEAD_LAUNCH_E
 }
 
 static int head_prepare(HeadArgs& a) {
     const int groups = (a.tc + 31) / 32;
     if (groups <= 1) a.part = nullptr;             // one group per image: the workgroup adds into S1 / S2 / SL itself
     if (!a.in || !a.w || !a.bias) return BMI_ERR_INVALID;
-    if (!a.S1 || !a.S2 || !a.SL) { if (!a.logits) return BMI_ERR_INVALID; a.S1 = a.S2 = a.SL = nullptr; a.part = nullptr; }     // logits only
+    if (!a.S1 || !a.S2 || !a.SL) { if (!a.logits) return BMI_ERR_INVALID; a.S1 = a.S2 = a.SL = a.SH = nullptr; a.part = nullptr; }     // logits only
+    if (a.SH && a.imap) return BMI_ERR_UNSUPPORTED;      // (the entropy plane is per image of the full batch: no dynamic early exit)
     if (a.B <= 0 || a.tc <= 0 || a.in_mod <= 0 || a.HW <= 0 || a.C <= 0 || a.in_kind < 0 || a.in_kind > 4) return BMI_ERR_INVALID;
     if (a.in_mod != a.B && a.in_mod != a.B * a.tc) return BMI_ERR_INVALID;
     if (a.imap && (a.Bc <= 0 || a.Bc > a.B)) return BMI_ERR_INVALID;
@@ -473,7 +522,7 @@ int launch_head_fused(const HeadArgs& a_in, hipStream_t s) {
     if (a.part) {
         const int n = (a.imap ? a.Bc : a.B) * a.C;
         hipLaunchKernelGGL(head_join_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a.part, groups, a.B, a.C, a.imap, a.Bc, a.S1,
-                           a.S2, a.SL);
+                           a.S2, a.SL, a.SH);
         BMI_CHECK_LAUNCH();
     }
     return BMI_OK;
@@ -491,7 +540,7 @@ int launch_head_fused_multi(const HeadArgs* list, int n, hipStream_t s) {
         if (rcp != BMI_OK) return rcp;
         const HeadArgs &x = p.a[i], &y = p.a[0];
         if (x.imap || x.C != y.C || x.in_kind != y.in_kind || x.B != y.B || x.tc != y.tc || (x.part != nullptr) != (y.part != nullptr) ||
-            (x.S1 != nullptr) != (y.S1 != nullptr))
+            (x.S1 != nullptr) != (y.S1 != nullptr) || (x.SH != nullptr) != (y.SH != nullptr))
             return BMI_ERR_UNSUPPORTED;
         for (int j = 0; j < i; ++j)
             if (x.part && x.part == p.a[j].part) return BMI_ERR_INVALID;
@@ -509,7 +558,7 @@ int launch_head_fused_multi(const HeadArgs* list, int n, hipStream_t s) {
         HeadJoinPack j;
         for (int i = 0; i < BMI_HEAD_PACK_MAX; ++i) {
             const HeadArgs& x = p.a[i < n ? i : 0];
-            j.part[i] = x.part; j.S1[i] = x.S1; j.S2[i] = x.S2; j.SL[i] = x.SL;
+            j.part[i] = x.part; j.S1[i] = x.S1; j.S2[i] = x.S2; j.SL[i] = x.SL; j.SH[i] = x.SH;
         }
         const int groups = (a.tc + 31) / 32, m = a.B * a.C;
         hipLaunchKernelGGL(head_join_multi_kernel, dim3((unsigned)((m + 255) / 256), (unsigned)n), dim3(256), 0, s, j, groups, a.B, a.C);

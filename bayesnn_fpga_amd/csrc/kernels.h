@@ -117,7 +117,9 @@ struct HeadArgs {   // fused exit head (head_fused.hip)
     float* logits;        // per-sample logits out: sample tl of this launch, class c of image b -> logits[tl * logits_tstride + b * C + c]; or null
     size_t logits_tstride;
     double* part;         // scratch [ceil(tc / 32)][3][B][C] for the per-group partial sums of a launch with more than 32 samples, or
-                          // null (hardware atomics then: the single-kernel entry point)
+                          // null (hardware atomics then: the single-kernel entry point); with SH, [ceil(tc / 32)][B] entropy sums behind it
+    double* SH;           // this exit's [B] accumulator of per-sample softmax entropies in nats (bmi_forward_mcd_entropy), or null: off
+                          // (last: the layout the kernels read stays what it was)
 };
 int launch_head_fused(const HeadArgs& a, hipStream_t s);
 #define BMI_HEAD_PACK_MAX 8
@@ -153,6 +155,9 @@ int launch_mask_permute(const float* src, float* dst, int m, int c, int cnt0, in
 int launch_expand_rows(const int* active, int bc, int batch, int tc, int* rows, hipStream_t s);   // rows[tl*bc + i] = tl*batch + active[i]
 int launch_finalize(int64_t n, int t_total, const double* S1, const double* S2, const double* SL, double* mean,
                     double* var, double* lm, int* nonfinite, hipStream_t s);
+// per (exit, image): predictive entropy of S1 / T, expected entropy SH / T, their difference (bmi_finalize_uncertainty)
+int launch_finalize_uncertainty(int n_rows, int C, int t_total, const double* S1, const double* SH, double* pred, double* expd,
+                                double* mi, int* nonfinite, hipStream_t s);
 int launch_philox_mask(uint8_t* keep, int64_t n, uint64_t seed, int site, int t, float p, hipStream_t s);
 // planar_w > 0: the bits in the lazy site's planar layout (rows of planar_w pixels; 2-bit sites, c % 64 == 0)
 int launch_mask_bits(uint8_t* bits, int n, int hw, int c, const SiteArgs& site, int batch, int t0, hipStream_t s, int planar_w = 0);

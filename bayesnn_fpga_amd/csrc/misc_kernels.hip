@@ -669,6 +669,48 @@ int launch_finalize(int64_t n, int t_total, const double* S1, const double* S2, 
 }
 
 // ---------------------------------------------------------------------------------------------
+// One wave per (exit, image) row: lanes walk the classes of the mean m = S1 / T, -sum m log m (0 log 0 = 0) meets by float64
+// wavefront shuffle; expected entropy SH / T; mutual information = their difference, clamped at 0 (a NaN stays a NaN).
+__global__ __launch_bounds__(256) void finalize_uncertainty_kernel(int rows, int C, double inv_t, const double* S1, const double* SH,
+                                                                   double* pred, double* expd, double* mi, int* nonfinite) {
+    const int row = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6), lane = threadIdx.x & 63;
+    if (row >= rows) return;                       // (wave-uniform)
+    const double* s1 = S1 + (size_t)row * C;
+    double h = 0.0;
+    int bad = 0;
+    for (int c = lane; c < C; c += 64) {
+        const double v = s1[c];
+        const double m = v * inv_t;
+        if (m > 0.0) h -= m * log(m);
+        bad += !__builtin_isfinite(v);
+        if (!__builtin_isfinite(v)) h = v - v;    // NaN: the row's entropy is not a number either (m > 0 is false for NaN)
+    }
+    const double sh = SH[row];
+    if (lane == 0) bad += !__builtin_isfinite(sh);
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        h += __shfl_xor(h, m);
+        bad += __shfl_xor(bad, m);
+    }
+    if (lane == 0) {
+        const double e = sh * inv_t, d = h - e;
+        pred[row] = h;
+        expd[row] = e;
+        mi[row] = d > 0 ? d : (d == d ? 0.0 : d);
+        if (nonfinite && bad) atomicAdd(nonfinite, bad);
+    }
+}
+
+int launch_finalize_uncertainty(int n_rows, int C, int t_total, const double* S1, const double* SH, double* pred, double* expd,
+                                double* mi, int* nonfinite, hipStream_t s) {
+    if (n_rows <= 0 || C <= 0 || t_total <= 0) return BMI_ERR_INVALID;
+    const dim3 grid((unsigned)((n_rows + 3) / 4)), block(256);
+    hipLaunchKernelGGL(finalize_uncertainty_kernel, grid, block, 0, s, n_rows, C, 1.0 / t_total, S1, SH, pred, expd, mi, nonfinite);
+    BMI_CHECK_LAUNCH();
+    return BMI_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
 __global__ void philox_mask_kernel(uint8_t* keep, long n, SiteArgs s, int t) {
     const long g = (long)blockIdx.x * blockDim.x + threadIdx.x;     // one 8-element group per thread
     if (g * 8 >= n) return;

@@ -501,6 +501,51 @@ class MCDEngine(CompiledGraph):
         self.accumulate(x, S, t_begin, T, seed, cnt0)
         return self.finalize(S, T)
 
+    # ---- uncertainty decomposition (bmi_forward_mcd_entropy / bmi_finalize_uncertainty) ------------------------------------------
+    def new_uncertainty_sums(self, batch):
+        """Zeroed float64 accumulators of ``accumulate_uncertainty``: S [3, E, B, C] (``new_moments``' S1 / S2 / SL) and H [E, B] (the sums
+        of the per-sample entropies), views of ONE allocation (``S._base``) so that a sharded caller all-reduces both in one call."""
+        from .sharding import new_uncertainty_sums
+        return new_uncertainty_sums(self.n_exits, batch, self.out_dim, self.device)
+
+    def accumulate_uncertainty(self, x, S, H, t_begin, t_count, seed=0, cnt0=0, image_offset=0):
+        """``accumulate`` (the same bits in S) that also adds every sample's softmax entropy into H [E, B]: computed in the fused head where
+        the per-sample softmax exists, so nothing per-sample reaches memory (``forward_samples`` would write [T, E, B, C] logits)."""
+        x = self._check_x(x)
+        B = x.shape[0]
+        if tuple(S.shape) != (3, self.n_exits, B, self.out_dim) or S.dtype != torch.float64 or not S.is_contiguous():
+            raise ValueError("moment buffer must be contiguous float64 [3, E, B, C]")
+        if tuple(H.shape) != (self.n_exits, B) or H.dtype != torch.float64 or not H.is_contiguous():
+            raise ValueError("entropy buffer must be contiguous float64 [E, B]")
+        with torch.cuda.device(self.device):
+            rc = self.lib.bmi_forward_mcd_entropy(self.handle, x.data_ptr(), B, int(image_offset), int(t_begin), int(t_count),
+                                                  int(seed) & 0xFFFFFFFFFFFFFFFF, int(cnt0), S[0].data_ptr(), S[1].data_ptr(), S[2].data_ptr(),
+                                                  H.data_ptr(), self.workspace.data_ptr(), self.workspace_bytes, self._stream())
+        _lib.check(rc, "bmi_forward_mcd_entropy")
+        return S, H
+
+    def finalize_uncertainty(self, S, H, t_total):
+        """``finalize``'s dict plus, float64 [E, B] each: ``pred_entropy`` H[mean] (total uncertainty), ``exp_entropy`` E_t H[p_t]
+        (aleatoric) and ``mutual_info`` their difference clamped at 0 (epistemic, "BALD").  Non-finite inputs count into the engine's
+        counter like finalize's (``check_finite``)."""
+        r = self.finalize(S, t_total)
+        E, B, Cd = S.shape[1], S.shape[2], S.shape[3]
+        if tuple(H.shape) != (E, B) or H.dtype != torch.float64 or not H.is_contiguous():
+            raise ValueError("entropy buffer must be contiguous float64 [E, B]")
+        out = torch.empty(3, E, B, dtype=torch.float64, device=S.device)
+        with torch.cuda.device(self.device):
+            rc = self.lib.bmi_finalize_uncertainty(E, B, Cd, int(t_total), S[0].data_ptr(), H.data_ptr(), out[0].data_ptr(), out[1].data_ptr(),
+                                                   out[2].data_ptr(), self._nonfinite.data_ptr(), self._stream())
+        _lib.check(rc, "bmi_finalize_uncertainty")
+        r.update(pred_entropy=out[0], exp_entropy=out[1], mutual_info=out[2])
+        return r
+
+    def predict_uncertainty(self, x, T, seed=0, t_begin=0, cnt0=0):
+        """``predict`` plus the uncertainty decomposition of ``finalize_uncertainty``."""
+        S, H = self.new_uncertainty_sums(x.shape[0])
+        self.accumulate_uncertainty(x, S, H, t_begin, T, seed, cnt0)
+        return self.finalize_uncertainty(S, H, T)
+
     def predict_with_exit(self, x, T, threshold, seed=0, cnt0=0, first_exit=1):
         """Confidence-threshold early exiting on the device (bmi_forward_mcd_exit): an image leaves after the first exit
         e >= ``first_exit`` whose T-mean confidence exceeds ``threshold`` (the reference's ``confidence_exiting`` rule,

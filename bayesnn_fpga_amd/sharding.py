@@ -128,3 +128,61 @@ def predict_sharded(engine, x, T, seed=0, cnt0=0, group=None):
     S = engine.new_moments(x.shape[0])
     accumulate_partitioned(engine, x, S, T, seed, cnt0, group)
     return engine.finalize(S, T)
+
+
+def new_uncertainty_sums(n_exits, batch, out_dim, device=None):
+    """S [3, E, B, C] and H [E, B], zeroed float64 views of ONE allocation (``S._base``: what ``accumulate_partitioned_uncertainty``
+    all-reduces)."""
+    n = 3 * n_exits * batch * out_dim
+    buf = torch.zeros(n + n_exits * batch, dtype=torch.float64, device=device)
+    return buf[:n].view(3, n_exits, batch, out_dim), buf[n:].view(n_exits, batch)
+
+
+def _packed(S, H):
+    buf = S._base
+    if buf is None or H._base is not buf or buf.numel() != S.numel() + H.numel() or not buf.is_contiguous():
+        raise ValueError("S and H must be the two views of one buffer (new_uncertainty_sums)")
+    return buf
+
+
+def accumulate_share_uncertainty(engine, x, S, H, T, seed=0, cnt0=0, rank=0, world=1, kind=None):
+    """``accumulate_share`` with the entropy sums H [E, B] beside S (``engine.accumulate_uncertainty``): the same partition, the same
+    engine-owned staging buffer for an image share; no collective."""
+    B = x.shape[0]
+    kind = share_kind(engine, T, B, world, kind)
+    _, lo, hi = partition(T, B, rank, world, kind)
+    if kind == "samples":
+        if hi > lo:
+            engine.accumulate_uncertainty(x, S, H, lo, hi - lo, seed, cnt0)
+        return S, H
+    if hi > lo:
+        cache = engine.__dict__.setdefault("_share_unc_parts", {})
+        key = (S.shape[1], hi - lo, S.shape[3])
+        part = cache.get(key)
+        if part is None:
+            part = cache[key] = new_uncertainty_sums(S.shape[1], hi - lo, S.shape[3], S.device)      # first call of this share shape only
+        else:
+            _packed(*part).zero_()
+        engine.accumulate_uncertainty(x[lo:hi], part[0], part[1], 0, T, seed, cnt0, image_offset=lo)
+        S[:, :, lo:hi].add_(part[0])
+        H[:, lo:hi].add_(part[1])
+    return S, H
+
+
+def accumulate_partitioned_uncertainty(engine, x, S, H, T, seed=0, cnt0=0, group=None, kind=None):
+    """This rank's share of batch ``x`` x T samples ADDED into S / H (``accumulate_share_uncertainty``), then ONE all-reduce (sum) of the
+    buffer they are views of."""
+    import torch.distributed as dist
+    rank, world = _rank_world(group)
+    buf = _packed(S, H)
+    accumulate_share_uncertainty(engine, x, S, H, T, seed, cnt0, rank, world, kind)
+    if world > 1:
+        dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=group)
+    return S, H
+
+
+def predict_sharded_uncertainty(engine, x, T, seed=0, cnt0=0, group=None):
+    """``predict_sharded`` with the uncertainty decomposition (``MCDEngine.finalize_uncertainty``)."""
+    S, H = engine.new_uncertainty_sums(x.shape[0])
+    accumulate_partitioned_uncertainty(engine, x, S, H, T, seed, cnt0, group)
+    return engine.finalize_uncertainty(S, H, T)

@@ -1,2 +1,3 @@
 from .evaluate import MultiExitAccuracy, evaluate  # noqa: F401
 from .results_analyzer import FullAnalysis  # noqa: F401
+from .uncertainty import UncertaintyAnalysis, average_predictive_entropy  # noqa: F401

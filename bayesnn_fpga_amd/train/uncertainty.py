@@ -1,0 +1,124 @@
+"""Uncertainty decomposition over a loader: the predictive entropy the paper's hardware evaluation reports as aPE (average predictive
+entropy, Hardware_Artifact/bayes_hw/metric_utils.py:3-6, computed on random-noise inputs at hls4ml_pred.py:86-119 from
+data_utils.py:73-88), and its split into the expected entropy (aleatoric) and the mutual information (epistemic, "BALD") per exit.
+
+The per-sample entropies are summed on the device inside the fused exit head (``MCDEngine.accumulate_uncertainty``); nothing per-sample
+reaches memory.  The T-mean probabilities are ``FullAnalysis``'s ``preds`` for the same seed: the walk keeps its per-batch bookkeeping.
+"""
+import numpy as np
+
+from .results_analyzer import exit_ensembles, get_device
+
+
+def average_predictive_entropy(p):
+    """The reference's aPE of probabilities ``p`` [N, C] (metric_utils.entropy): -sum(log(p + 1e-8) * p) / N."""
+    p = np.asarray(p)
+    batch_size = p.shape[0]
+    return -np.sum(np.log(p + 1e-8) * p) / batch_size
+
+
+def entropy_rows(p):
+    """-sum_c p log p over the last axis, float64, 0 log 0 = 0 (the device's bmi_finalize_uncertainty on the host)."""
+    p = np.asarray(p, dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        t = np.where(p > 0, p * np.log(np.where(p > 0, p, 1.0)), 0.0)
+    return -t.sum(axis=-1)
+
+
+def decompose_logits(logits):
+    """The decomposition of per-pass logits [T, ..., C] in float64 on the host (what the device computes from its own per-sample
+    logits): dict(mean [..., C], pred_entropy, exp_entropy, mutual_info [...]), entropies in nats, mutual_info clamped at 0."""
+    z = np.asarray(logits, dtype=np.float64)
+    z = z - z.max(axis=-1, keepdims=True)
+    lse = np.log(np.exp(z).sum(axis=-1, keepdims=True))
+    p = np.exp(z - lse)
+    exp_entropy = (lse[..., 0] - (p * z).sum(axis=-1)).mean(axis=0)
+    mean = p.mean(axis=0)
+    pred_entropy = entropy_rows(mean)
+    return dict(mean=mean, pred_entropy=pred_entropy, exp_entropy=exp_entropy, mutual_info=np.maximum(pred_entropy - exp_entropy, 0.0))
+
+
+class UncertaintyAnalysis:
+    """One walk of ``loader`` (batches ``(x, y, ...)``) with ``mc_passes`` stochastic passes per batch.
+
+    Batch k runs under seed ``seed + k`` with the model's current Masksembles counter, and the counters advance by ``mc_passes``
+    afterwards: the bookkeeping of ``FullAnalysis._batch_call``, so ``mean`` equals ``FullAnalysis(model, loader, mc_dropout=True,
+    mc_passes=T, seed=seed).preds``.  The engine is the model's (``engine_dtype="auto"`` applies).  Under an initialised
+    ``torch.distributed`` with more than one rank every rank walks the same loader and each batch is partitioned like ``FullAnalysis``'s
+    (``sharding.predict_sharded_uncertainty``: one all-reduce per batch); every rank ends with the full arrays, rank 0 writes them.
+
+    Per exit, float64: ``mean`` [E, N, C], ``pred_entropy`` / ``exp_entropy`` / ``mutual_info`` [E, N]; ``ape`` [E] (the reference's
+    aPE of the T-mean probabilities), ``mean_mi`` [E], ``mean_exp_entropy`` [E]; ``ensemble_pred_entropy`` [E, N] and ``ensemble_ape``
+    [E]: the same for the reference's cumulative exit ensembles (the mean of exits 0..e; their mutual information would need
+    per-sample ensemble probabilities and is not computed)."""
+
+    def __init__(self, model, loader, gpu=0, mc_passes=10, seed=0, group=None):
+        self.model = model
+        self.loader = loader
+        self.device = get_device(gpu)
+        self.mc_passes = int(mc_passes)
+        self.seed = seed
+        self.group = group
+        self._run()
+
+    def _ranks(self):
+        from ..sharding import _rank_world
+        return _rank_world(self.group)
+
+    def is_writer(self):
+        return self._ranks()[0] == 0
+
+    def _engine(self, b_x):
+        dtype = self.model.resolve_engine_dtype(self.device, None, calib=b_x, samples=self.mc_passes)
+        if self._ranks()[1] > 1:          # (collective: every rank builds its engine on the same first batch)
+            import torch.distributed as dist
+            dtype = self.model.agree_engine_dtype(self.device, dtype, self.group or dist.group.WORLD)
+        want = max(b_x.shape[0], int(getattr(self.loader, "batch_size", 0) or 0))
+        return self.model.engine(self.device, max_batch=want, dtype=dtype)
+
+    def _run(self):
+        from ..sharding import predict_sharded_uncertainty
+        world = self._ranks()[1]
+        parts, labels, eng = [], [], None
+        for k, batch in enumerate(self.loader):
+            b_x = batch[0].to(self.device)
+            if eng is None:
+                eng = self._engine(b_x)
+            ml = self.model.mask_layers()
+            T, seed, cnt0 = self.mc_passes, self.seed + k, (ml[0].cnt if ml else 0)
+            self.model.advance(T)
+            if world > 1:
+                r = predict_sharded_uncertainty(eng, b_x, T, seed, cnt0, group=self.group)
+            else:
+                r = eng.predict_uncertainty(b_x, T, seed, cnt0=cnt0)
+            parts.append({n: r[n].cpu().numpy() for n in ("mean", "pred_entropy", "exp_entropy", "mutual_info")})
+            eng.check_finite()
+            labels.append(np.asarray(batch[1]).astype(np.int64))
+        if not parts:
+            raise ValueError("empty loader")
+        self.mean = np.concatenate([p["mean"] for p in parts], axis=1)
+        self.pred_entropy = np.concatenate([p["pred_entropy"] for p in parts], axis=1)
+        self.exp_entropy = np.concatenate([p["exp_entropy"] for p in parts], axis=1)
+        self.mutual_info = np.concatenate([p["mutual_info"] for p in parts], axis=1)
+        self.labels = np.concatenate(labels)
+        self.ape = np.array([average_predictive_entropy(m) for m in self.mean])
+        self.mean_mi = self.mutual_info.mean(axis=1)
+        self.mean_exp_entropy = self.exp_entropy.mean(axis=1)
+        ens = exit_ensembles(self.mean)
+        self.ensemble_pred_entropy = entropy_rows(ens)
+        self.ensemble_ape = np.array([average_predictive_entropy(m) for m in ens])
+
+    def summary(self):
+        """Per exit: dict(ape, mean_mi, mean_exp_entropy, ensemble_ape)."""
+        return [dict(ape=float(self.ape[e]), mean_mi=float(self.mean_mi[e]), mean_exp_entropy=float(self.mean_exp_entropy[e]),
+                     ensemble_ape=float(self.ensemble_ape[e])) for e in range(len(self.ape))]
+
+    def save(self, experiment_id):
+        """``test_uncertainty_<experiment_id>.npz`` (rank 0 of a sharded walk only); returns the file name, or None on the other ranks."""
+        if not self.is_writer():
+            return None
+        name = f"test_uncertainty_{experiment_id}.npz"
+        np.savez(name, mean=self.mean, pred_entropy=self.pred_entropy, exp_entropy=self.exp_entropy, mutual_info=self.mutual_info,
+                 labels=self.labels, ape=self.ape, mean_mi=self.mean_mi, mean_exp_entropy=self.mean_exp_entropy,
+                 ensemble_pred_entropy=self.ensemble_pred_entropy, ensemble_ape=self.ensemble_ape)
+        return name

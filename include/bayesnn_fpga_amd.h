@@ -320,6 +320,20 @@ int bmi_forward_mcd_samples(bmi_handle h, const float* x_nchw, int32_t batch, in
                             int32_t mask_cnt0, int32_t mask_stride, float* logits, double* S1, double* S2, double* SL, void* workspace,
                             size_t workspace_bytes, bmi_stream stream);
 
+/* Uncertainty decomposition of the folded path: bmi_forward_mcd_images (same arguments, same S1 / S2 / SL, the same bits in them), and
+ * the fused head also ADDS the softmax entropy of every sample it evaluates into the float64 [E][batch] buffer SH:
+ *     SH[e][b] += sum_t H(softmax(logits_t[e][b])),   H(p) = -sum_c p_c log p_c in nats,
+ * computed per sample where the softmax is (never stored) in log-softmax form, log(sum) - sum_c p_c (l_c - max): no log of an underflowed
+ * probability.  Per-sample values do not depend on the chunking; the float64 sums join in group order like S1's.  SH of a share
+ * (image_offset) covers rows 0 .. batch-1 of that share.  With bmi_finalize_uncertainty it gives the expected entropy E_t H[p_t] (the
+ * aleatoric part) and the mutual information H[p_mean] - E_t H[p_t] (the epistemic part, "BALD") that MC dropout and Masksembles exist to
+ * produce; the paper's hardware evaluation reports the predictive entropy H[p_mean] of random-noise inputs as aPE
+ * (Hardware_Artifact/bayes_hw/metric_utils.py:3-6, used at hls4ml_pred.py:86-119 on the inputs of data_utils.py:73-88).
+ * No allocation and no synchronisation: captures into a hipGraph like bmi_forward_mcd. */
+int bmi_forward_mcd_entropy(bmi_handle h, const float* x_nchw, int32_t batch, int32_t image_offset, int32_t t_begin,
+                            int32_t t_count, uint64_t seed, int32_t mask_cnt0, double* S1, double* S2, double* SL, double* SH,
+                            void* workspace, size_t workspace_bytes, bmi_stream stream);
+
 /* Confidence-threshold early exiting ON the device — what the reference only models after the fact
  * (FullAnalysis.confidence_exiting / is_confident / flop_saver, SA/train/results_analyzer.py:606-630, :638-677, :725-733):
  * runs samples 0 .. t_count-1 of the batch stage by stage; after the head of exit e (first_exit <= e < n_exits-1; the
@@ -343,6 +357,13 @@ int bmi_finalize(int64_t n, int32_t t_total, const double* S1, const double* S2,
  * reference's np.average (SA/train/results_analyzer.py:247-248) unnoticed.  No synchronisation: read the counter with the results. */
 int bmi_finalize_checked(int64_t n, int32_t t_total, const double* S1, const double* S2, const double* SL, double* mean,
                          double* var, double* logit_mean, int32_t* nonfinite, bmi_stream stream);
+
+/* Per (exit, image), float64 [E][batch] each, from the S1 [E][batch][C] and SH [E][batch] sums of t_total samples
+ * (bmi_forward_mcd_entropy): m = S1 / T, pred_entropy = -sum_c m_c log m_c (0 log 0 = 0; the reference's entropy() adds 1e-8
+ * inside the log instead), exp_entropy = SH / T, mutual_info = max(pred_entropy - exp_entropy, 0).  nonfinite (NULL: not counted) as
+ * in bmi_finalize_checked: ADDS the number of non-finite S1 / SH inputs. */
+int bmi_finalize_uncertainty(int32_t n_exits, int32_t batch, int32_t out_dim, int32_t t_total, const double* S1, const double* SH,
+                             double* pred_entropy, double* exp_entropy, double* mutual_info, int32_t* nonfinite, bmi_stream stream);
 
 /* Per-op-kind HIP-event timing of bmi_forward_mcd (off by default; adds two event records per
  * launch).  bmi_profile_read synchronises the recorded events and resets the accumulators. */
