@@ -92,15 +92,7 @@ struct bmi_engine_s {
     int max_batch = 0, chunk = 0;
     size_t ws_bytes = 0, exit_off = 0;   // exit_off: 2 active-image lists + a counter (dynamic early exit)
     size_t splitk_off = 0;               // fp32 partial sums of the split-K prefix convs
-    int image_offset = 0;                // batch index of the current call's image 0 (bmi_forward_mcd_images), else 0
     size_t head_off = 0, head_part_bytes = 0;   // float64 partial sums of a head launch's 32-sample groups (joined in group order), one region per exit
-    // bmi_forward_mcd_samples: per-sample logits out, Masksembles masks walked with a stride
-    float* logits_out = nullptr;         // (run time) [t_count][E][batch][C] of the current call, or null
-    double* sh_out = nullptr;            // (run time) bmi_forward_mcd_entropy: [E][batch] sums of the per-sample entropies, or null
-    bool no_moments = false;             // (run time) the heads write per-sample logits only
-    int logits_t_begin = 0, logits_batch = 0;
-    int mask_stride = 1, mask_t_begin = 0;    // (run time) mask_permuted: a site's mask of sample t is row (t - mask_t_begin) % M of its PERMUTED table
-    bool mask_permuted = false;
     std::vector<std::pair<const float*, size_t>> perm;   // (bmi_plan) Masksembles tables (device pointer of the site) -> workspace offset of the permuted copy
     // profiling
     bool profiling = false;
@@ -851,16 +843,47 @@ struct ProfScope {
     }
 };
 
+// One forward call: built on the stack by each bmi_forward_* entry point; nothing a call does is kept in the handle.
+struct Pass {
+    const float* x;
+    char* ws;
+    hipStream_t stream;
+    int B;                            // the call's batch
+    uint64_t seed;
+    int cnt0;
+    int b0 = 0;                       // batch index of the call's image 0 (bmi_forward_mcd_images / _entropy), else 0
+    double *S1 = nullptr, *S2 = nullptr, *SL = nullptr;   // [E][B][C] moment sums, or null: the heads write per-sample logits only
+    double* SH = nullptr;             // bmi_forward_mcd_entropy: [E][B] sums of the per-sample entropies, or null
+    float* logits = nullptr;          // bmi_forward_mcd_samples: [t - logits_t_begin][E][B][C] per-sample logits, or null
+    int logits_t_begin = 0;
+    bool permuted = false;            // bmi_forward_mcd_samples: a site's mask of sample t is row (t - mask_t_begin) % M of its PERMUTED table
+    int mask_t_begin = 0;
+};
+
+// A site's arguments in this pass.  Masksembles masks walked with a stride (bmi_forward_mcd_samples): the kernels index row (cnt0 + t) % M
+// of a site's table; the call has gathered table'[r] = table[(mask_cnt0 + r stride) % M] into the workspace, and cnt0' = -t_begin mod M
+// makes that row (t - t_begin) % M — no kernel knows about the stride
+SiteArgs pass_site(const bmi_engine_s* e, const Pass& p, const bmi_site* site, uint64_t elem_off = 0) {
+    SiteArgs sa = resolve_site(site, p.seed, p.cnt0, elem_off);
+    if (sa.kind == BMI_SITE_MASKSEMBLE && p.permuted)
+        for (const auto& pr : e->perm)
+            if (pr.first == sa.masks) {
+                sa.masks = (const float*)(p.ws + pr.second);
+                sa.cnt0 = (sa.num_masks - p.mask_t_begin % sa.num_masks) % sa.num_masks;
+                break;
+            }
+    return sa;
+}
+
 // The arguments of one exit head's launch (head_fused.hip).
-HeadArgs make_head_args(bmi_engine_s* e, const OpInfo& op, char* ws, int N, int B, int t0, uint64_t seed, int cnt0, double* S1, double* S2, double* SL,
-                        const int* imap, int Bc) {
+HeadArgs make_head_args(bmi_engine_s* e, const Pass& p, const OpInfo& op, int N, int t0, const int* imap, int Bc) {
     const bmi_op_desc& d = op.d;
     const TensorInfo& tin = e->tensors[d.in];
-    const int b0 = e->image_offset;
+    const int B = p.B;
     const int n_rows = imap ? (N / Bc) * B : N;
     HeadArgs a;
     std::memset(&a, 0, sizeof(a));
-    a.in = ws + tin.offset;
+    a.in = p.ws + tin.offset;
     a.in_kind = (e->split && !tin.dense_out) ? 2 + e->split        // the split engines' pair32 tensors
                 : (tin.f32 || tin.pooled_now) ? 1 : (e->bf16 ? 2 : 0);      // pooled_now: fp32 means [row][K] written by the conv
     a.in_mod = tin.stoch ? n_rows : B;
@@ -868,28 +891,19 @@ HeadArgs make_head_args(bmi_engine_s* e, const OpInfo& op, char* ws, int N, int 
     a.HW = tin.pooled_now ? 1 : tin.h * tin.w; a.K = tin.c; a.B = B; a.t0 = t0; a.tc = imap ? N / Bc : N / B;
     a.w = (const float*)d.weight; a.bias = d.bias; a.C = e->out_dim;
     const bool on_logits = d.site_pos == BMI_SITE_POS_INNER;
-    const uint64_t soff = (uint64_t)b0 * (uint64_t)tin.c;          // (site_off of run_op: [B, K] features, elementwise and per-channel draws alike)
-    SiteArgs sf = resolve_site(on_logits ? nullptr : &d.site, seed, cnt0, soff);
-    SiteArgs sl = resolve_site(on_logits ? &d.site : nullptr, seed, cnt0);
-    for (SiteArgs* sa : {&sf, &sl})                                 // Masksembles tables walked with a stride (bmi_forward_mcd_samples): see run_op
-        if (sa->kind == BMI_SITE_MASKSEMBLE && e->mask_permuted)
-            for (const auto& pr : e->perm)
-                if (pr.first == sa->masks) {
-                    sa->masks = (const float*)(ws + pr.second);
-                    sa->cnt0 = (sa->num_masks - e->mask_t_begin % sa->num_masks) % sa->num_masks;
-                    break;
-                }
-    a.site = sf;
-    a.site_logits = sl;
-    a.b0 = b0;
-    const size_t eo = (size_t)d.out * B * e->out_dim;
-    a.S1 = S1 + eo; a.S2 = S2 + eo; a.SL = SL + eo;
-    if (e->no_moments) a.S1 = a.S2 = a.SL = nullptr;
-    if (e->sh_out && !e->no_moments) a.SH = e->sh_out + (size_t)d.out * B;     // this exit's [batch] row of the entropy sums
-    a.part = (double*)(ws + e->head_off + (size_t)d.out * e->head_part_bytes);     // this exit's own region
-    if (e->logits_out) {            // per-sample logits of this exit: [t - t_begin][E][batch][C]
-        const size_t plane = (size_t)e->logits_batch * e->out_dim;
-        a.logits = e->logits_out + ((size_t)(t0 - e->logits_t_begin) * e->n_exits + d.out) * plane;
+    const uint64_t soff = (uint64_t)p.b0 * (uint64_t)tin.c;          // (site_off of run_op: [B, K] features, elementwise and per-channel draws alike)
+    a.site = pass_site(e, p, on_logits ? nullptr : &d.site, soff);
+    a.site_logits = pass_site(e, p, on_logits ? &d.site : nullptr);
+    a.b0 = p.b0;
+    if (p.S1) {
+        const size_t eo = (size_t)d.out * B * e->out_dim;
+        a.S1 = p.S1 + eo; a.S2 = p.S2 + eo; a.SL = p.SL + eo;
+        if (p.SH) a.SH = p.SH + (size_t)d.out * B;     // this exit's [batch] row of the entropy sums
+    }
+    a.part = (double*)(p.ws + e->head_off + (size_t)d.out * e->head_part_bytes);     // this exit's own region
+    if (p.logits) {            // per-sample logits of this exit: [t - t_begin][E][batch][C]
+        const size_t plane = (size_t)B * e->out_dim;
+        a.logits = p.logits + ((size_t)(t0 - p.logits_t_begin) * e->n_exits + d.out) * plane;
         a.logits_tstride = (size_t)e->n_exits * plane;
     }
     return a;
@@ -897,31 +911,18 @@ HeadArgs make_head_args(bmi_engine_s* e, const OpInfo& op, char* ws, int N, int 
 
 // imap / rows / Bc: dynamic early exit: N = samples * Bc compact images of the B-image batch; imap = the Bc active images
 // (heads), rows = the N-entry row table (ConvArgs::imap); null = all images
-int run_op(bmi_engine_s* e, const OpInfo& op, const float* x, char* ws, int N, int B, int t0, uint64_t seed, int cnt0,
-           double* S1, double* S2, double* SL, hipStream_t s, const int* imap = nullptr, int Bc = 0, const int* rows = nullptr) {
+int run_op(bmi_engine_s* e, const Pass& p, const OpInfo& op, int N, int t0, const int* imap = nullptr, int Bc = 0, const int* rows = nullptr) {
     const bmi_op_desc& d = op.d;
     const TensorInfo& tin = e->tensors[d.in];
+    char* const ws = p.ws;
+    const int B = p.B;
+    const hipStream_t s = p.stream;
     // image-partitioned launch (bmi_forward_mcd_images): element index of image 0 in the index space of a site on a tensor with
     // `per_image` elements per image (elementwise) / `channels` (per-(image, channel) draws)
-    const int b0 = e->image_offset;
     auto site_off = [&](const bmi_site& st, size_t per_image, size_t channels) -> uint64_t {
-        return (uint64_t)b0 * (st.kind == BMI_SITE_CHANNEL ? channels : per_image);
+        return (uint64_t)p.b0 * (st.kind == BMI_SITE_CHANNEL ? channels : per_image);
     };
     const int n_rows = imap ? (N / Bc) * B : N;     // rows of a stochastic tensor (original folded layout)
-    // Masksembles masks walked with a stride (bmi_forward_mcd_samples): the kernels index row (cnt0 + t) % M of a site's table; the
-    // call has gathered table'[r] = table[(mask_cnt0 + r stride) % M] into the workspace, and cnt0' = -t_begin mod M makes that row
-    // (t - t_begin) % M — no kernel knows about the stride
-    auto resolve_site = [&](const bmi_site* site, uint64_t sd, int c0, uint64_t elem_off = 0) {
-        SiteArgs sa = ::resolve_site(site, sd, c0, elem_off);
-        if (sa.kind == BMI_SITE_MASKSEMBLE && e->mask_permuted)
-            for (const auto& pr : e->perm)
-                if (pr.first == sa.masks) {
-                    sa.masks = (const float*)(ws + pr.second);
-                    sa.cnt0 = (sa.num_masks - e->mask_t_begin % sa.num_masks) % sa.num_masks;
-                    break;
-                }
-        return sa;
-    };
     if (imap && d.kind != BMI_OP_CONV && d.kind != BMI_OP_HEAD) return BMI_ERR_UNSUPPORTED;
     if (imap && e->f32 && !e->split) return BMI_ERR_UNSUPPORTED;      // (the exact engine: parity only)
     // a lazy site's tensor (see bmi_create) is written now if this op cannot apply the mask itself
@@ -943,7 +944,7 @@ int run_op(bmi_engine_s* e, const OpInfo& op, const float* x, char* ws, int N, i
     prof.r.out = d.out; prof.r.images = N;
     switch (d.kind) {
         case BMI_OP_STEM:
-            return launch_stem_conv(x, (const float*)d.weight, d.scale, d.bias, (_Float16*)(ws + e->tensors[d.out].offset), N,
+            return launch_stem_conv(p.x, (const float*)d.weight, d.scale, d.bias, (_Float16*)(ws + e->tensors[d.out].offset), N,
                                     tin.c, tin.h, tin.w, op.cout, d.ksize, d.stride, d.pad, d.relu, e->dtype, s);     // (F32: fp32 out; F16X2 / BF16X3: pair32 out)
         case BMI_OP_CONV: {
             ConvArgs a;
@@ -969,7 +970,7 @@ int run_op(bmi_engine_s* e, const OpInfo& op, const float* x, char* ws, int N, i
             a.ksize = d.ksize; a.stride = d.stride; a.pad = d.pad; a.relu = d.relu;
             a.M = N * op.ho * op.wo;
             a.B = B; a.t0 = t0;
-            a.site = resolve_site(&d.site, seed, cnt0, site_off(d.site, (size_t)op.ho * op.wo * op.cout, (size_t)op.cout));
+            a.site = pass_site(e, p, &d.site, site_off(d.site, (size_t)op.ho * op.wo * op.cout, (size_t)op.cout));
             if (d.site_pos == BMI_SITE_POS_INNER && d.site.kind != BMI_SITE_NONE) { a.site_inner = 1; a.bias_post = d.bias_post; }
             a.out_mul = op.out_mul;
             if (d.in2 >= 0) {
@@ -1037,7 +1038,7 @@ int run_op(bmi_engine_s* e, const OpInfo& op, const float* x, char* ws, int N, i
                 b.H = op.ho; b.W = op.wo; b.Cin = op.cout; b.Ho = op.ho; b.Wo = op.wo; b.Cout = op.seam_cout;
                 b.ksize = 1; b.stride = 1; b.pad = 0; b.relu = op.seam_d.relu;
                 b.M = a.M; b.B = B; b.t0 = t0;
-                b.site = resolve_site(nullptr, seed, cnt0, 0);
+                b.site = pass_site(e, p, nullptr);
                 b.out_mul = 1.f;
                 const double flops_b = 2.0 * N * op.ho * op.wo * (double)op.seam_cout * op.cout;
                 const double bytes_b = 2.0 * N * op.ho * op.wo * (double)op.seam_cout + 2.0 * (double)op.seam_cout * op.cout;   // (its input never leaves the chip)
@@ -1140,7 +1141,6 @@ int run_op(bmi_engine_s* e, const OpInfo& op, const float* x, char* ws, int N, i
                 prof.tag(BMI_CONV_FAMILY_IGEMM, flops, bytes);
                 return launch_conv_igemm(a, s);
             }
-            e->tensors[d.out].pooled_now = false;
             if (opt_conv_pool() == 1 && op.pool_pw_ok) {      // ("conv_pool" = 2: conv3x3_s2's only)
                 ConvArgs q = a;
                 q.pool = (float*)q.out;
@@ -1168,7 +1168,7 @@ int run_op(bmi_engine_s* e, const OpInfo& op, const float* x, char* ws, int N, i
         }
         case OP_MASKBITS:
             return launch_mask_bits((uint8_t*)(ws + e->tensors[d.out].offset), N, tin.h * tin.w, tin.c,
-                                    resolve_site(&d.site, seed, cnt0, site_off(d.site, (size_t)tin.h * tin.w * tin.c, (size_t)tin.c)), B, t0, s);
+                                    pass_site(e, p, &d.site, site_off(d.site, (size_t)tin.h * tin.w * tin.c, (size_t)tin.c)), B, t0, s);
         case BMI_OP_MASK: {
             EltArgs a;
             std::memset(&a, 0, sizeof(a));
@@ -1176,7 +1176,7 @@ int run_op(bmi_engine_s* e, const OpInfo& op, const float* x, char* ws, int N, i
             a.in = (const _Float16*)(ws + tin.offset);
             a.out = ws + e->tensors[d.out].offset;
             a.N = N; a.in_mod = tin.stoch ? N : B; a.HW = tin.h * tin.w; a.C = tin.c; a.B = B; a.t0 = t0;
-            a.site = resolve_site(&d.site, seed, cnt0, site_off(d.site, (size_t)tin.h * tin.w * tin.c, (size_t)tin.c));
+            a.site = pass_site(e, p, &d.site, site_off(d.site, (size_t)tin.h * tin.w * tin.c, (size_t)tin.c));
             if (d.site_pos == BMI_SITE_POS_INNER) { a.bias_post = d.bias_post; a.relu = d.relu; }
             a.pair = e->split;                                     // the split engines: pair32 tensors in and out
             if (e->f32) return launch_mask_apply_f32(a, s);
@@ -1206,10 +1206,10 @@ int run_op(bmi_engine_s* e, const OpInfo& op, const float* x, char* ws, int N, i
             // input: fp32 (a dense layer's output; any tensor of the exact engine), the engine's 16-bit type, or pair32 (kinds 3 | 4)
             return launch_dense_f32(ws + tin.offset, (e->split && !tin.dense_out) ? 2 + e->split : (tin.f32 ? 1 : (e->bf16 ? 2 : 0)), (const float*)d.weight, d.bias,
                                     (float*)(ws + e->tensors[d.out].offset), N, tin.stoch ? N : B, tin.c, op.cout, d.relu,
-                                    resolve_site(&d.site, seed, cnt0, site_off(d.site, (size_t)op.cout, (size_t)op.cout)), B, t0, s);
+                                    pass_site(e, p, &d.site, site_off(d.site, (size_t)op.cout, (size_t)op.cout)), B, t0, s);
         case BMI_OP_HEAD:
             // pool + site + Linear + softmax + the chunk's moment sums in one launch (head_fused.hip)
-            return launch_head_fused(make_head_args(e, op, ws, N, B, t0, seed, cnt0, S1, S2, SL, imap, Bc), s);
+            return launch_head_fused(make_head_args(e, p, op, N, t0, imap, Bc), s);
     }
     return BMI_ERR_INVALID;
 }
@@ -1217,8 +1217,8 @@ int run_op(bmi_engine_s* e, const OpInfo& op, const float* x, char* ws, int N, i
 // One chunk of the suffix.  Consecutive exit heads run as ONE launch ("head_batch"; launch_head_fused_multi): with exit-only dropout — what
 // every run of the paper uses, Software_Artifact/script_figs/journal_script.sh:10-63 — the suffix is nothing but the heads, each a launch of
 // mostly fixed latency; the same arithmetic per head, the same bits.
-int run_suffix(bmi_engine_s* e, const float* x, char* ws, int N, int B, int t0, uint64_t seed, int cnt0, double* S1, double* S2, double* SL,
-               hipStream_t s) {
+int run_suffix(bmi_engine_s* e, const Pass& p, int N, int t0) {
+    const hipStream_t s = p.stream;
     const std::vector<OpInfo>& ops = e->suffix;
     for (size_t i = 0; i < ops.size();) {
         size_t j = i;
@@ -1226,7 +1226,7 @@ int run_suffix(bmi_engine_s* e, const float* x, char* ws, int N, int B, int t0, 
             while (j < ops.size() && j - i < BMI_HEAD_PACK_MAX && ops[j].d.kind == BMI_OP_HEAD && !e->tensors[ops[j].d.in].lazy_pending) ++j;
         if (j - i >= 2) {
             HeadArgs list[BMI_HEAD_PACK_MAX];
-            for (size_t k = i; k < j; ++k) list[k - i] = make_head_args(e, ops[k], ws, N, B, t0, seed, cnt0, S1, S2, SL, nullptr, 0);
+            for (size_t k = i; k < j; ++k) list[k - i] = make_head_args(e, p, ops[k], N, t0, nullptr, 0);
             int rc;
             {
                 ProfScope prof(e, BMI_OP_HEAD, s);
@@ -1240,11 +1240,41 @@ int run_suffix(bmi_engine_s* e, const float* x, char* ws, int N, int B, int t0, 
                 e->recs.pop_back();
             }
         }
-        const int rc = run_op(e, ops[i], x, ws, N, B, t0, seed, cnt0, S1, S2, SL, s);
+        const int rc = run_op(e, p, ops[i], N, t0);
         if (rc != BMI_OK) return rc;
         ++i;
     }
     return BMI_OK;
+}
+
+// The folded path: the prefix once, then samples t_begin .. t_begin+t_count-1 through the suffix, `chunk` at a time.
+int forward_folded(bmi_engine_s* e, const Pass& p, int t_begin, int t_count) {
+    BmiOptionScope opt_scope(&e->opts);
+    for (const OpInfo& op : e->prefix) {
+        const int rc = run_op(e, p, op, p.B, 0);
+        if (rc != BMI_OK) return rc;
+    }
+    for (int t0 = t_begin; t0 < t_begin + t_count; t0 += e->chunk) {
+        const int tc = std::min(e->chunk, t_begin + t_count - t0);
+        const int rc = run_suffix(e, p, tc * p.B, t0);
+        if (rc != BMI_OK) return rc;
+    }
+    return BMI_OK;
+}
+
+// bmi_forward_mcd, _images and _entropy (SH: null but for _entropy): their argument checks, then the folded path.
+int forward_moments(bmi_handle h, const float* x_nchw, int32_t batch, int32_t image_offset, int32_t t_begin, int32_t t_count, uint64_t seed,
+                    int32_t mask_cnt0, double* S1, double* S2, double* SL, double* SH, void* workspace, size_t workspace_bytes, bmi_stream stream) {
+    const int rco = bmi_image_offset_ok(h, image_offset);      // (a null handle: BMI_ERR_INVALID; image 0 always passes)
+    if (rco != BMI_OK) return rco;
+    if (!x_nchw || !S1 || !S2 || !SL || !workspace) return BMI_ERR_INVALID;
+    if (batch < 1 || t_count < 1 || t_begin < 0 || mask_cnt0 < 0) return BMI_ERR_INVALID;
+    if (h->max_batch == 0 || batch > h->max_batch) return BMI_ERR_INVALID;
+    if (workspace_bytes < h->ws_bytes) return BMI_ERR_NOMEM;
+    Pass p{x_nchw, (char*)workspace, (hipStream_t)stream, batch, seed, mask_cnt0};
+    p.b0 = image_offset;
+    p.S1 = S1; p.S2 = S2; p.SL = SL; p.SH = SH;
+    return forward_folded(h, p, t_begin, t_count);
 }
 
 }  // namespace
@@ -1270,49 +1300,25 @@ int bmi_image_offset_ok(bmi_handle h, int32_t image_offset) {
     return BMI_OK;
 }
 
+int bmi_forward_mcd(bmi_handle h, const float* x_nchw, int32_t batch, int32_t t_begin, int32_t t_count, uint64_t seed,
+                    int32_t mask_cnt0, double* S1, double* S2, double* SL, void* workspace, size_t workspace_bytes,
+                    bmi_stream stream) {
+    return forward_moments(h, x_nchw, batch, 0, t_begin, t_count, seed, mask_cnt0, S1, S2, SL, nullptr, workspace, workspace_bytes, stream);
+}
+
 int bmi_forward_mcd_images(bmi_handle h, const float* x_nchw, int32_t batch, int32_t image_offset, int32_t t_begin,
                            int32_t t_count, uint64_t seed, int32_t mask_cnt0, double* S1, double* S2, double* SL,
                            void* workspace, size_t workspace_bytes, bmi_stream stream) {
-    const int rco = bmi_image_offset_ok(h, image_offset);
-    if (rco != BMI_OK) return rco;
-    h->image_offset = image_offset;
-    const int rc = bmi_forward_mcd(h, x_nchw, batch, t_begin, t_count, seed, mask_cnt0, S1, S2, SL, workspace, workspace_bytes, stream);
-    h->image_offset = 0;
-    return rc;
+    return forward_moments(h, x_nchw, batch, image_offset, t_begin, t_count, seed, mask_cnt0, S1, S2, SL, nullptr, workspace,
+                           workspace_bytes, stream);
 }
 
 int bmi_forward_mcd_entropy(bmi_handle h, const float* x_nchw, int32_t batch, int32_t image_offset, int32_t t_begin,
                             int32_t t_count, uint64_t seed, int32_t mask_cnt0, double* S1, double* S2, double* SL, double* SH,
                             void* workspace, size_t workspace_bytes, bmi_stream stream) {
     if (!h || !SH) return BMI_ERR_INVALID;
-    h->sh_out = SH;
-    const int rc = bmi_forward_mcd_images(h, x_nchw, batch, image_offset, t_begin, t_count, seed, mask_cnt0, S1, S2, SL, workspace,
-                                          workspace_bytes, stream);
-    h->sh_out = nullptr;
-    return rc;
-}
-
-int bmi_forward_mcd(bmi_handle h, const float* x_nchw, int32_t batch, int32_t t_begin, int32_t t_count, uint64_t seed,
-                    int32_t mask_cnt0, double* S1, double* S2, double* SL, void* workspace, size_t workspace_bytes,
-                    bmi_stream stream) {
-    if (!h || !x_nchw || !S1 || !S2 || !SL || !workspace) return BMI_ERR_INVALID;
-    BmiOptionScope opt_scope(&h->opts);
-    if (batch < 1 || t_count < 1 || t_begin < 0 || mask_cnt0 < 0) return BMI_ERR_INVALID;
-    if (h->max_batch == 0 || batch > h->max_batch) return BMI_ERR_INVALID;
-    if (workspace_bytes < h->ws_bytes) return BMI_ERR_NOMEM;
-    hipStream_t s = (hipStream_t)stream;
-    char* ws = (char*)workspace;
-    for (const OpInfo& op : h->prefix) {
-        const int rc = run_op(h, op, x_nchw, ws, batch, batch, 0, seed, mask_cnt0, S1, S2, SL, s);
-        if (rc != BMI_OK) return rc;
-    }
-    for (int t0 = t_begin; t0 < t_begin + t_count; t0 += h->chunk) {
-        const int tc = std::min(h->chunk, t_begin + t_count - t0);
-        const int N = tc * batch;
-        const int rc = run_suffix(h, x_nchw, ws, N, batch, t0, seed, mask_cnt0, S1, S2, SL, s);
-        if (rc != BMI_OK) return rc;
-    }
-    return BMI_OK;
+    return forward_moments(h, x_nchw, batch, image_offset, t_begin, t_count, seed, mask_cnt0, S1, S2, SL, SH, workspace,
+                           workspace_bytes, stream);
 }
 
 int bmi_forward_mcd_samples(bmi_handle h, const float* x_nchw, int32_t batch, int32_t t_begin, int32_t t_count, uint64_t seed,
@@ -1323,7 +1329,10 @@ int bmi_forward_mcd_samples(bmi_handle h, const float* x_nchw, int32_t batch, in
     if ((S1 || S2 || SL) && !(S1 && S2 && SL)) return BMI_ERR_INVALID;
     if (h->max_batch == 0 || batch < 1 || batch > h->max_batch) return BMI_ERR_INVALID;
     if (workspace_bytes < h->ws_bytes) return BMI_ERR_NOMEM;
-    int cnt0 = mask_cnt0;
+    if (!x_nchw || t_count < 1) return BMI_ERR_INVALID;
+    Pass p{x_nchw, (char*)workspace, (hipStream_t)stream, batch, seed, mask_cnt0};
+    p.S1 = S1; p.S2 = S2; p.SL = SL;                  // (all null: per-sample logits only)
+    p.logits = logits; p.logits_t_begin = t_begin;
     if ((mask_stride != 1 || t_begin != 0) && !h->perm.empty()) {
         // gather every Masksembles table in the order this call walks it: table'[r] = table[(mask_cnt0 + r * stride) % M]
         // (stride 1 from t_begin > 0 too: the kernels index (cnt0 + t) mod M with the GLOBAL sample index t, which would rotate the walk by t_begin —
@@ -1335,25 +1344,17 @@ int bmi_forward_mcd_samples(bmi_handle h, const float* x_nchw, int32_t batch, in
                 for (auto& pr : h->perm)
                     if (pr.first == st.masks) {
                         const int width = op.d.kind == BMI_OP_HEAD ? h->tensors[op.d.in].c : op.cout;
-                        const int rc = launch_mask_permute(st.masks, (float*)((char*)workspace + pr.second), st.num_masks, width, mask_cnt0, mask_stride,
-                                                           (hipStream_t)stream);
+                        const int rc = launch_mask_permute(st.masks, (float*)(p.ws + pr.second), st.num_masks, width, mask_cnt0, mask_stride,
+                                                           p.stream);
                         if (rc != BMI_OK) return rc;
                         break;
                     }
             }
-        h->mask_stride = mask_stride;
-        h->mask_permuted = true;
-        h->mask_t_begin = t_begin;
-        cnt0 = 0;
+        p.permuted = true;
+        p.mask_t_begin = t_begin;
+        p.cnt0 = 0;
     }
-    h->logits_out = logits; h->logits_t_begin = t_begin; h->logits_batch = batch;
-    static double dummy;          // (bmi_forward_mcd's argument check; the head never dereferences S* when S1 is the dummy: see run_op)
-    const bool moments = S1 != nullptr;
-    h->no_moments = !moments;
-    const int rc = bmi_forward_mcd(h, x_nchw, batch, t_begin, t_count, seed, cnt0, moments ? S1 : &dummy, moments ? S2 : &dummy, moments ? SL : &dummy,
-                                   workspace, workspace_bytes, stream);
-    h->logits_out = nullptr; h->mask_stride = 1; h->mask_t_begin = 0; h->mask_permuted = false; h->no_moments = false;
-    return rc;
+    return forward_folded(h, p, t_begin, t_count);
 }
 
 int bmi_forward_mcd_exit(bmi_handle h, const float* x_nchw, int32_t batch, int32_t t_count, uint64_t seed, int32_t mask_cnt0,
@@ -1365,8 +1366,10 @@ int bmi_forward_mcd_exit(bmi_handle h, const float* x_nchw, int32_t batch, int32
     if (h->max_batch == 0 || batch > h->max_batch) return BMI_ERR_INVALID;
     if (t_count > h->chunk || (h->f32 && !h->split)) return BMI_ERR_UNSUPPORTED;     // an exit's decision needs ALL samples of the stage in the workspace
     if (workspace_bytes < h->ws_bytes) return BMI_ERR_NOMEM;
-    hipStream_t s = (hipStream_t)stream;
-    char* ws = (char*)workspace;
+    Pass p{x_nchw, (char*)workspace, (hipStream_t)stream, batch, seed, mask_cnt0};
+    p.S1 = S1; p.S2 = S2; p.SL = SL;
+    const hipStream_t s = p.stream;
+    char* const ws = p.ws;
     int* lists[2] = {(int*)(ws + h->exit_off), (int*)(ws + h->exit_off) + h->max_batch};
     int* count_dev = (int*)(ws + h->exit_off) + 2 * h->max_batch;
     int* rows_dev = count_dev + 64;
@@ -1375,14 +1378,14 @@ int bmi_forward_mcd_exit(bmi_handle h, const float* x_nchw, int32_t batch, int32
     if (rc != BMI_OK) return rc;
     for (int x = 0; x < h->n_exits; ++x) active_after[x] = 0;
     for (const OpInfo& op : h->prefix) {
-        rc = run_op(h, op, x_nchw, ws, batch, batch, 0, seed, mask_cnt0, S1, S2, SL, s);
+        rc = run_op(h, p, op, batch, 0);
         if (rc != BMI_OK) return rc;
     }
     const int* imap = nullptr;     // null: every image is still active
     const int* rows = nullptr;
     int bc = batch, cur = 0;
     for (const OpInfo& op : h->suffix) {
-        rc = run_op(h, op, x_nchw, ws, t_count * bc, batch, 0, seed, mask_cnt0, S1, S2, SL, s, imap, bc, rows);
+        rc = run_op(h, p, op, t_count * bc, 0, imap, bc, rows);
         if (rc != BMI_OK) return rc;
         if (op.d.kind != BMI_OP_HEAD) continue;
         const int e = op.d.out;

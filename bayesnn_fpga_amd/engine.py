@@ -441,16 +441,23 @@ class MCDEngine(CompiledGraph):
         """Adds samples t_begin .. t_begin+t_count-1 of batch ``x`` into the moment buffer ``S``.
         ``image_offset``: ``x`` (and ``S``) are images image_offset.. of a larger batch — the masks are drawn at the images'
         indices in the whole batch (bmi_forward_mcd_images: one rank's share of a batch partitioned by images)."""
+        self._forward(x, S, None, t_begin, t_count, seed, cnt0, image_offset)
+        return S
+
+    def _forward(self, x, S, H, t_begin, t_count, seed, cnt0, image_offset):
+        """``accumulate`` (H None: bmi_forward_mcd_images) and ``accumulate_uncertainty`` (bmi_forward_mcd_entropy)."""
         x = self._check_x(x)
         B = x.shape[0]
         if tuple(S.shape) != (3, self.n_exits, B, self.out_dim) or S.dtype != torch.float64 or not S.is_contiguous():
             raise ValueError("moment buffer must be contiguous float64 [3, E, B, C]")
+        if H is not None and (tuple(H.shape) != (self.n_exits, B) or H.dtype != torch.float64 or not H.is_contiguous()):
+            raise ValueError("entropy buffer must be contiguous float64 [E, B]")
+        name = "bmi_forward_mcd_images" if H is None else "bmi_forward_mcd_entropy"
         with torch.cuda.device(self.device):
-            rc = self.lib.bmi_forward_mcd_images(self.handle, x.data_ptr(), B, int(image_offset), int(t_begin), int(t_count),
-                                                 int(seed) & 0xFFFFFFFFFFFFFFFF, int(cnt0), S[0].data_ptr(), S[1].data_ptr(),
-                                                 S[2].data_ptr(), self.workspace.data_ptr(), self.workspace_bytes, self._stream())
-        _lib.check(rc, "bmi_forward_mcd_images")
-        return S
+            rc = getattr(self.lib, name)(self.handle, x.data_ptr(), B, int(image_offset), int(t_begin), int(t_count),
+                                         int(seed) & 0xFFFFFFFFFFFFFFFF, int(cnt0), S[0].data_ptr(), S[1].data_ptr(), S[2].data_ptr(),
+                                         *(() if H is None else (H.data_ptr(),)), self.workspace.data_ptr(), self.workspace_bytes, self._stream())
+        _lib.check(rc, name)
 
     def image_offset_ok(self, image_offset):
         """Whether a share of a batch that starts at image ``image_offset`` can be run by ``accumulate(..., image_offset=)``
@@ -511,17 +518,7 @@ class MCDEngine(CompiledGraph):
     def accumulate_uncertainty(self, x, S, H, t_begin, t_count, seed=0, cnt0=0, image_offset=0):
         """``accumulate`` (the same bits in S) that also adds every sample's softmax entropy into H [E, B]: computed in the fused head where
         the per-sample softmax exists, so nothing per-sample reaches memory (``forward_samples`` would write [T, E, B, C] logits)."""
-        x = self._check_x(x)
-        B = x.shape[0]
-        if tuple(S.shape) != (3, self.n_exits, B, self.out_dim) or S.dtype != torch.float64 or not S.is_contiguous():
-            raise ValueError("moment buffer must be contiguous float64 [3, E, B, C]")
-        if tuple(H.shape) != (self.n_exits, B) or H.dtype != torch.float64 or not H.is_contiguous():
-            raise ValueError("entropy buffer must be contiguous float64 [E, B]")
-        with torch.cuda.device(self.device):
-            rc = self.lib.bmi_forward_mcd_entropy(self.handle, x.data_ptr(), B, int(image_offset), int(t_begin), int(t_count),
-                                                  int(seed) & 0xFFFFFFFFFFFFFFFF, int(cnt0), S[0].data_ptr(), S[1].data_ptr(), S[2].data_ptr(),
-                                                  H.data_ptr(), self.workspace.data_ptr(), self.workspace_bytes, self._stream())
-        _lib.check(rc, "bmi_forward_mcd_entropy")
+        self._forward(x, S, H, t_begin, t_count, seed, cnt0, image_offset)
         return S, H
 
     def finalize_uncertainty(self, S, H, t_total):

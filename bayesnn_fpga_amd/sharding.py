@@ -82,44 +82,59 @@ def share_kind(engine, T, B, world, kind=None):
                      "whole Philox call of every site (bmi_image_offset_ok)")
 
 
-def accumulate_share(engine, x, S, T, seed=0, cnt0=0, rank=0, world=1, kind=None):
+def accumulate_share(engine, x, S, T, seed=0, cnt0=0, rank=0, world=1, kind=None, H=None):
     """Rank ``rank``'s share of batch ``x`` x T samples ADDED into the moment buffer ``S`` [3, E, B, C]; NO collective (what a
     hipGraph of a rank's step captures: ``BatchesInFlight.predict_graphed``).  ``partition`` decides (``share_kind``): by samples
     while T > world size; by images when T <= world — the rank runs ``engine.accumulate(x[lo:hi], ..., image_offset=lo)``, masks
     drawn at the images' indices in the whole batch (bmi_forward_mcd_images), into its rows of S (the other ranks' rows stay zero
     until the all-reduce) — unless some rank's share cannot start where the split puts it: then by samples after all
     (``kind=None``), or a ValueError on every rank (explicit ``kind="images"``).  Nothing is allocated here: the share's
-    [3, E, hi - lo, C] staging buffer belongs to the engine."""
+    [3, E, hi - lo, C] staging buffer belongs to the engine.  ``H``: the entropy sums [E, B] beside S (``new_uncertainty_sums``), added
+    into as well (``engine.accumulate_uncertainty``); returns (S, H) then."""
     B = x.shape[0]
     kind = share_kind(engine, T, B, world, kind)
     _, lo, hi = partition(T, B, rank, world, kind)
-    if kind == "samples":
-        if hi > lo:
-            engine.accumulate(x, S, lo, hi - lo, seed, cnt0)
-        return S
-    if hi > lo:
-        cache = engine.__dict__.setdefault("_share_parts", {})
-        key = (S.shape[1], hi - lo, S.shape[3])
-        part = cache.get(key)
-        if part is None:
-            part = cache[key] = S.new_zeros(3, S.shape[1], hi - lo, S.shape[3])      # first call of this share shape only
+    out = S if H is None else (S, H)
+
+    def run(x, S, H, t_begin, t_count, image_offset):
+        if H is None:
+            engine.accumulate(x, S, t_begin, t_count, seed, cnt0, image_offset=image_offset)
         else:
-            part.zero_()
-        engine.accumulate(x[lo:hi], part, 0, T, seed, cnt0, image_offset=lo)
-        S[:, :, lo:hi].add_(part)
-    return S
+            engine.accumulate_uncertainty(x, S, H, t_begin, t_count, seed, cnt0, image_offset=image_offset)
+
+    if hi <= lo:
+        return out
+    if kind == "samples":
+        run(x, S, H, lo, hi - lo, 0)
+        return out
+    cache = engine.__dict__.setdefault("_share_parts", {})
+    key = (H is not None, S.shape[1], hi - lo, S.shape[3])
+    part = cache.get(key)
+    if part is None:                # first call of this share shape only
+        part = cache[key] = (S.new_zeros(3, S.shape[1], hi - lo, S.shape[3]), None) if H is None else \
+            new_uncertainty_sums(S.shape[1], hi - lo, S.shape[3], S.device)
+    else:
+        (part[0] if H is None else _packed(*part)).zero_()
+    run(x[lo:hi], *part, 0, T, lo)
+    S[:, :, lo:hi].add_(part[0])
+    if H is not None:
+        H[:, lo:hi].add_(part[1])
+    return out
 
 
-def accumulate_partitioned(engine, x, S, T, seed=0, cnt0=0, group=None, kind=None, always_reduce=False):
+def accumulate_partitioned(engine, x, S, T, seed=0, cnt0=0, group=None, kind=None, always_reduce=False, H=None):
     """This rank's share of batch ``x`` x T samples ADDED into the moment buffer ``S`` [3, E, B, C] (``accumulate_share``), then ONE
     all-reduce (sum) over the group.  ``always_reduce``: issue the collective in a group of ONE rank too (a sum over one rank: the same
-    bits) — how a 1-GPU box exercises RCCL on exactly the streams and buffers the N-GPU path uses (bench.py's ``allreduce_us_1rank``)."""
+    bits) — how a 1-GPU box exercises RCCL on exactly the streams and buffers the N-GPU path uses (bench.py's ``allreduce_us_1rank``).
+    ``H``: the entropy sums beside S, views of one buffer (``new_uncertainty_sums``): that buffer is what the all-reduce sums; returns
+    (S, H) then."""
     import torch.distributed as dist
     rank, world = _rank_world(group)
-    accumulate_share(engine, x, S, T, seed, cnt0, rank, world, kind)
+    buf = S if H is None else _packed(S, H)
+    out = accumulate_share(engine, x, S, T, seed, cnt0, rank, world, kind, H=H)
     if world > 1 or (always_reduce and dist.is_available() and dist.is_initialized()):
-        dist.all_reduce(S, op=dist.ReduceOp.SUM, group=group)
-    return S
+        dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=group)
+    return out
 
 
 def predict_sharded(engine, x, T, seed=0, cnt0=0, group=None):
@@ -131,7 +146,7 @@ def predict_sharded(engine, x, T, seed=0, cnt0=0, group=None):
 
 
 def new_uncertainty_sums(n_exits, batch, out_dim, device=None):
-    """S [3, E, B, C] and H [E, B], zeroed float64 views of ONE allocation (``S._base``: what ``accumulate_partitioned_uncertainty``
+    """S [3, E, B, C] and H [E, B], zeroed float64 views of ONE allocation (``S._base``: what ``accumulate_partitioned(..., H=H)``
     all-reduces)."""
     n = 3 * n_exits * batch * out_dim
     buf = torch.zeros(n + n_exits * batch, dtype=torch.float64, device=device)
@@ -145,44 +160,13 @@ def _packed(S, H):
     return buf
 
 
-def accumulate_share_uncertainty(engine, x, S, H, T, seed=0, cnt0=0, rank=0, world=1, kind=None):
-    """``accumulate_share`` with the entropy sums H [E, B] beside S (``engine.accumulate_uncertainty``): the same partition, the same
-    engine-owned staging buffer for an image share; no collective."""
-    B = x.shape[0]
-    kind = share_kind(engine, T, B, world, kind)
-    _, lo, hi = partition(T, B, rank, world, kind)
-    if kind == "samples":
-        if hi > lo:
-            engine.accumulate_uncertainty(x, S, H, lo, hi - lo, seed, cnt0)
-        return S, H
-    if hi > lo:
-        cache = engine.__dict__.setdefault("_share_unc_parts", {})
-        key = (S.shape[1], hi - lo, S.shape[3])
-        part = cache.get(key)
-        if part is None:
-            part = cache[key] = new_uncertainty_sums(S.shape[1], hi - lo, S.shape[3], S.device)      # first call of this share shape only
-        else:
-            _packed(*part).zero_()
-        engine.accumulate_uncertainty(x[lo:hi], part[0], part[1], 0, T, seed, cnt0, image_offset=lo)
-        S[:, :, lo:hi].add_(part[0])
-        H[:, lo:hi].add_(part[1])
-    return S, H
-
-
 def accumulate_partitioned_uncertainty(engine, x, S, H, T, seed=0, cnt0=0, group=None, kind=None):
-    """This rank's share of batch ``x`` x T samples ADDED into S / H (``accumulate_share_uncertainty``), then ONE all-reduce (sum) of the
-    buffer they are views of."""
-    import torch.distributed as dist
-    rank, world = _rank_world(group)
-    buf = _packed(S, H)
-    accumulate_share_uncertainty(engine, x, S, H, T, seed, cnt0, rank, world, kind)
-    if world > 1:
-        dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=group)
-    return S, H
+    """``accumulate_partitioned`` with the entropy sums H [E, B] beside S."""
+    return accumulate_partitioned(engine, x, S, T, seed, cnt0, group, kind, H=H)
 
 
 def predict_sharded_uncertainty(engine, x, T, seed=0, cnt0=0, group=None):
     """``predict_sharded`` with the uncertainty decomposition (``MCDEngine.finalize_uncertainty``)."""
     S, H = engine.new_uncertainty_sums(x.shape[0])
-    accumulate_partitioned_uncertainty(engine, x, S, H, T, seed, cnt0, group)
+    accumulate_partitioned(engine, x, S, T, seed, cnt0, group, H=H)
     return engine.finalize_uncertainty(S, H, T)

@@ -233,3 +233,52 @@ def test_a_live_engine_keeps_its_options_whatever_the_process_defaults_become():
     assert torch.equal(ra["mean"], rb["mean"])
     with pytest.raises(_lib.BmiError):
         b.set_option("no_such_switch", 1)
+
+
+def test_forward_entry_points_check_arguments_before_any_launch():
+    """Every forward entry point validates its arguments, in a fixed order, before it touches the GPU: one bad argument per row, the
+    return code it gets (-22 invalid, -12 workspace too small, -95 unsupported).  The graph lives on the CPU, so a row that got as far
+    as a launch would fail with a HIP error instead."""
+    from bayesnn_fpga_amd.models import extra as bx
+    cg = CompiledGraph(build_seeded(bx.VGG11MC, dict(num_bayes_layer=3)), "cpu", 8, 2)
+    lib, h, ws_ok, E = _lib.lib(), cg.handle, cg.workspace_bytes, cg.n_exits
+    buf = np.zeros(64, dtype=np.float64)                  # a non-null address; no row gets far enough to use it
+    p = buf.ctypes.data
+    act = (C.c_int32 * E)()
+
+    def mcd(h=h, x=p, batch=8, t_begin=0, t_count=2, cnt0=0, S1=p, S2=p, SL=p, ws=p, nbytes=ws_ok):
+        return lib.bmi_forward_mcd(h, x, batch, t_begin, t_count, 7, cnt0, S1, S2, SL, ws, nbytes, None)
+
+    def images(h=h, x=p, batch=8, off=0, t_begin=0, t_count=2, cnt0=0, S1=p, ws=p, nbytes=ws_ok):
+        return lib.bmi_forward_mcd_images(h, x, batch, off, t_begin, t_count, 7, cnt0, S1, p, p, ws, nbytes, None)
+
+    def entropy(h=h, x=p, batch=8, off=0, t_count=2, S1=p, SH=p, ws=p, nbytes=ws_ok):
+        return lib.bmi_forward_mcd_entropy(h, x, batch, off, 0, t_count, 7, 0, S1, p, p, SH, ws, nbytes, None)
+
+    def samples(h=h, x=p, batch=8, t_begin=0, t_count=2, cnt0=0, stride=1, logits=p, S=(p, p, p), ws=p, nbytes=ws_ok):
+        return lib.bmi_forward_mcd_samples(h, x, batch, t_begin, t_count, 7, cnt0, stride, logits, *S, ws, nbytes, None)
+
+    def exit_(h=h, x=p, batch=8, t_count=2, cnt0=0, first=0, S1=p, eoi=p, act=act, ws=p, nbytes=ws_ok):
+        return lib.bmi_forward_mcd_exit(h, x, batch, t_count, 7, cnt0, 0.5, first, S1, p, p, eoi, act, ws, nbytes, None)
+
+    small = ws_ok - 1
+    rows = [
+        (mcd(h=None), -22), (mcd(x=None), -22), (mcd(S1=None), -22), (mcd(S2=None), -22), (mcd(SL=None), -22), (mcd(ws=None), -22),
+        (mcd(batch=0), -22), (mcd(t_count=0), -22), (mcd(t_begin=-1), -22), (mcd(cnt0=-1), -22), (mcd(batch=9), -22),
+        (mcd(batch=9, nbytes=small), -22), (mcd(t_count=0, nbytes=small), -22), (mcd(nbytes=small), -12),
+        (images(h=None), -22), (images(off=-1), -22), (images(off=-1, nbytes=small), -22), (images(off=4, x=None), -22), (images(off=4, S1=None), -22), (images(off=4, batch=9, nbytes=small), -22),
+        (images(off=4, t_count=0), -22), (images(off=4, t_begin=-1), -22), (images(off=4, cnt0=-1), -22), (images(off=4, nbytes=small), -12),
+        (entropy(h=None), -22), (entropy(SH=None), -22), (entropy(SH=None, nbytes=small), -22), (entropy(off=-1), -22),
+        (entropy(off=-1, nbytes=small), -22), (entropy(S1=None), -22), (entropy(x=None, nbytes=small), -22), (entropy(ws=None), -22),
+        (entropy(batch=9), -22), (entropy(t_count=0), -22), (entropy(nbytes=small), -12), (entropy(off=4, nbytes=small), -12),
+        (samples(h=None), -22), (samples(logits=None), -22), (samples(ws=None), -22), (samples(stride=0), -22), (samples(t_begin=-1), -22),
+        (samples(cnt0=-1), -22), (samples(S=(p, None, None)), -22), (samples(S=(None, p, p)), -22), (samples(batch=0), -22),
+        (samples(batch=9), -22), (samples(batch=9, nbytes=small), -22), (samples(nbytes=small), -12),
+        (samples(S=(None, None, None), nbytes=small), -12), (samples(x=None, nbytes=small), -12), (samples(t_count=0, nbytes=small), -12),
+        (samples(x=None), -22), (samples(x=None, S=(None, None, None)), -22), (samples(t_count=0), -22),
+        (exit_(h=None), -22), (exit_(x=None), -22), (exit_(S1=None), -22), (exit_(eoi=None), -22), (exit_(act=None), -22),
+        (exit_(ws=None), -22), (exit_(batch=0), -22), (exit_(t_count=0), -22), (exit_(cnt0=-1), -22), (exit_(first=-1), -22),
+        (exit_(batch=9), -22), (exit_(batch=9, t_count=3), -22), (exit_(t_count=3), -95), (exit_(t_count=3, nbytes=small), -95),
+        (exit_(nbytes=small), -12),
+    ]
+    assert [rc for rc, _ in rows] == [want for _, want in rows]
