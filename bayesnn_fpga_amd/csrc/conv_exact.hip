@@ -118,7 +118,8 @@ int launch_conv_exact(const ConvArgs& a, hipStream_t s) {
 // stand-alone site on an fp32 tensor (mask_apply_kernel's arithmetic: MCDropout / Masksembles2D on a stage output, or the
 // mask + BN shift + ReLU half of a deterministic conv with an inner site)
 // PAIR = 0: fp32 tensors; 1 | 2: pair32 tensors (conv_epilogue.h) of fp16 | bf16 halves — the split engines
-template <int PAIR>
+// ROWS (adaptive sampling, a.rows): launch image i is folded row a.rows[i] of both tensors and of the Philox index space
+template <int PAIR, bool ROWS = false>
 __global__ __launch_bounds__(256) void mask_apply_f32_kernel(EltArgs a) {
     const float* const in = (const float*)a.in;
     float* const out = (float*)a.out;
@@ -127,8 +128,9 @@ __global__ __launch_bounds__(256) void mask_apply_f32_kernel(EltArgs a) {
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
         const int c8 = (int)(i % cg) * 8;
         const long pix = i / cg;
-        const int n = (int)(pix / a.HW);
-        const int p = (int)(pix - (long)n * a.HW);
+        const int nc = (int)(pix / a.HW);
+        const int p = (int)(pix - (long)nc * a.HW);
+        const int n = ROWS ? a.rows[nc] : nc;
         const int tl = n / a.B, b = n - tl * a.B;
         const int t = a.t0 + tl;
         float v[8];
@@ -219,6 +221,15 @@ __global__ __launch_bounds__(256) void mask_apply_pair_lb1_kernel(EltArgs a) {
 int launch_mask_apply_f32(const EltArgs& a, hipStream_t s) {
     if (a.C % 8 != 0 || (a.pair && a.C % 32 != 0)) return BMI_ERR_UNSUPPORTED;
     if (a.N <= 0 || a.in_mod <= 0 || a.B <= 0) return BMI_ERR_INVALID;
+    if (a.rows) {      // a row table: the per-item kernel (the same value per element as the shared-Philox form below)
+        long blocks = ((long)a.N * a.HW * (a.C >> 3) + 255) / 256;
+        if (blocks > 256 * 16) blocks = 256 * 16;
+        if (a.pair == 1) hipLaunchKernelGGL((mask_apply_f32_kernel<1, true>), dim3((unsigned)blocks), dim3(256), 0, s, a);
+        else if (a.pair == 2) hipLaunchKernelGGL((mask_apply_f32_kernel<2, true>), dim3((unsigned)blocks), dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((mask_apply_f32_kernel<0, true>), dim3((unsigned)blocks), dim3(256), 0, s, a);
+        BMI_CHECK_LAUNCH();
+        return BMI_OK;
+    }
     if (a.pair && a.site.kind == BMI_SITE_ELEMENTWISE && a.site.log2_bits == 1 && !a.bias_post && !a.relu && a.N % a.B == 0 && a.in_mod == a.B &&
         ((long)a.B * a.HW * (a.C >> 3)) % 512 == 0 && a.site.elem_off % 64 == 0) {
         const long waves = ((long)a.B * a.HW * (a.C >> 3)) / 512;
@@ -235,14 +246,16 @@ int launch_mask_apply_f32(const EltArgs& a, hipStream_t s) {
     }
     long blocks = ((long)a.N * a.HW * (a.C >> 3) + 255) / 256;
     if (blocks > 256 * 16) blocks = 256 * 16;
-    if (a.pair == 1) hipLaunchKernelGGL(mask_apply_f32_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, s, a);
-    else if (a.pair == 2) hipLaunchKernelGGL(mask_apply_f32_kernel<2>, dim3((unsigned)blocks), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(mask_apply_f32_kernel<0>, dim3((unsigned)blocks), dim3(256), 0, s, a);
+    if (a.pair == 1) hipLaunchKernelGGL((mask_apply_f32_kernel<1>), dim3((unsigned)blocks), dim3(256), 0, s, a);
+    else if (a.pair == 2) hipLaunchKernelGGL((mask_apply_f32_kernel<2>), dim3((unsigned)blocks), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((mask_apply_f32_kernel<0>), dim3((unsigned)blocks), dim3(256), 0, s, a);
     BMI_CHECK_LAUNCH();
     return BMI_OK;
 }
 
-__global__ __launch_bounds__(256) void maxpool2_f32_kernel(const float* in, float* out, int N, int H, int W, int C) {
+// ROWS (here and in the pair32 form): launch image i is folded row rows[i] of both tensors (adaptive sampling)
+template <bool ROWS = false>
+__global__ __launch_bounds__(256) void maxpool2_f32_kernel(const float* in, float* out, int N, int H, int W, int C, const int* rows) {
     const int cg = C >> 2, Ho = H >> 1, Wo = W >> 1;
     const long total = (long)N * Ho * Wo * cg;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
@@ -250,7 +263,7 @@ __global__ __launch_bounds__(256) void maxpool2_f32_kernel(const float* in, floa
         long q = i / cg;
         const int ox = (int)(q % Wo); q /= Wo;
         const int oy = (int)(q % Ho);
-        const int n = (int)(q / Ho);
+        const int n = ROWS ? rows[q / Ho] : (int)(q / Ho);
         const float* p = in + (((size_t)n * H + 2 * oy) * W + 2 * ox) * C + c4;
         const f32x4_x a0 = *(const f32x4_x*)p, a1 = *(const f32x4_x*)(p + C);
         const f32x4_x a2 = *(const f32x4_x*)(p + (size_t)W * C), a3 = *(const f32x4_x*)(p + (size_t)W * C + C);
@@ -262,8 +275,8 @@ __global__ __launch_bounds__(256) void maxpool2_f32_kernel(const float* in, floa
 }
 
 // pair32 tensors: the maximum of the four decoded values, re-encoded (it IS one of the four pairs' value, so the encoding is exact again)
-template <bool BF>
-__global__ __launch_bounds__(256) void maxpool2_pair_kernel(const _Float16* in, _Float16* out, int N, int H, int W, int C) {
+template <bool BF, bool ROWS = false>
+__global__ __launch_bounds__(256) void maxpool2_pair_kernel(const _Float16* in, _Float16* out, int N, int H, int W, int C, const int* rows) {
     const int cg = C >> 3, Ho = H >> 1, Wo = W >> 1;
     const long total = (long)N * Ho * Wo * cg;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
@@ -271,7 +284,7 @@ __global__ __launch_bounds__(256) void maxpool2_pair_kernel(const _Float16* in, 
         long q = i / cg;
         const int ox = (int)(q % Wo); q /= Wo;
         const int oy = (int)(q % Ho);
-        const int n = (int)(q / Ho);
+        const int n = ROWS ? rows[q / Ho] : (int)(q / Ho);
         const size_t p00 = ((size_t)n * H + 2 * oy) * W + 2 * ox;
         float a0[8], a1[8], a2[8], a3[8], o[8];
         pair_decode<BF, 8>(in + pair32_off(p00, C, c8), a0);
@@ -284,15 +297,22 @@ __global__ __launch_bounds__(256) void maxpool2_pair_kernel(const _Float16* in, 
     }
 }
 
-int launch_maxpool2_f32(const float* in, float* out, int n, int h, int w, int c, hipStream_t s, int pair) {
+int launch_maxpool2_f32(const float* in, float* out, int n, int h, int w, int c, hipStream_t s, int pair, const int* rows) {
     if (c % 4 != 0 || (h & 1) || (w & 1) || (pair && c % 32 != 0)) return BMI_ERR_UNSUPPORTED;
     const long total = (long)n * (h / 2) * (w / 2) * (c / (pair ? 8 : 4));
     long blocks = (total + 255) / 256;
     if (blocks > 256 * 16) blocks = 256 * 16;
     if (blocks <= 0) return BMI_ERR_INVALID;
-    if (pair == 1) hipLaunchKernelGGL(maxpool2_pair_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, (const _Float16*)in, (_Float16*)out, n, h, w, c);
-    else if (pair == 2) hipLaunchKernelGGL(maxpool2_pair_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, (const _Float16*)in, (_Float16*)out, n, h, w, c);
-    else hipLaunchKernelGGL(maxpool2_f32_kernel, dim3((unsigned)blocks), dim3(256), 0, s, in, out, n, h, w, c);
+    const dim3 g((unsigned)blocks), b(256);
+    const _Float16* in16 = (const _Float16*)in;
+    _Float16* out16 = (_Float16*)out;
+    if (rows) {
+        if (pair == 1) hipLaunchKernelGGL((maxpool2_pair_kernel<false, true>), g, b, 0, s, in16, out16, n, h, w, c, rows);
+        else if (pair == 2) hipLaunchKernelGGL((maxpool2_pair_kernel<true, true>), g, b, 0, s, in16, out16, n, h, w, c, rows);
+        else hipLaunchKernelGGL((maxpool2_f32_kernel<true>), g, b, 0, s, in, out, n, h, w, c, rows);
+    } else if (pair == 1) hipLaunchKernelGGL((maxpool2_pair_kernel<false>), g, b, 0, s, in16, out16, n, h, w, c, rows);
+    else if (pair == 2) hipLaunchKernelGGL((maxpool2_pair_kernel<true>), g, b, 0, s, in16, out16, n, h, w, c, rows);
+    else hipLaunchKernelGGL((maxpool2_f32_kernel<false>), g, b, 0, s, in, out, n, h, w, c, rows);
     BMI_CHECK_LAUNCH();
     return BMI_OK;
 }

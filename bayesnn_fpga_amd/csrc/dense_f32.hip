@@ -26,18 +26,21 @@ typedef _Float16 half8_d __attribute__((ext_vector_type(8)));
 #define DN_TF 64
 #define DN_TS 128
 
-template <typename TIN, bool BF>
+// ROWS (adaptive sampling, here and in dense_split_kernel): launch row i is folded row rows[i] of the input / output tensors and of the
+// Philox index space; every row's dot product is the same whatever rows share its tile.
+template <typename TIN, bool BF, bool ROWS = false>
 __global__ __launch_bounds__(256) void dense_f32_kernel(const TIN* __restrict__ in, const float* __restrict__ w,
                                                         const float* __restrict__ bias, float* __restrict__ out, int N,
-                                                        int in_mod, int K, int Cout, int relu, SiteArgs site, int B, int t0) {
+                                                        int in_mod, int K, int Cout, int relu, SiteArgs site, int B, int t0,
+                                                        const int* __restrict__ rows) {
     constexpr int RT = DN_TF / 32;
     __shared__ __attribute__((aligned(16))) float Wt[DN_TF * DN_ROW];
     __shared__ __attribute__((aligned(16))) float It[DN_TS * DN_ROW];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31, hh = lane >> 5;
     const int n0 = blockIdx.x * DN_TS, c0 = blockIdx.y * DN_TF;
-    const int n = n0 + wave * 32 + r;
-    const bool valid = n < N;
+    const int nc = n0 + wave * 32 + r;
+    const bool valid = nc < N;
 
     f32x16 acc[RT];
 #pragma unroll
@@ -62,13 +65,13 @@ __global__ __launch_bounds__(256) void dense_f32_kernel(const TIN* __restrict__ 
         if constexpr (sizeof(TIN) == 2) {                                                                          \
             _Pragma("unroll") for (int i = 0; i < 2; ++i) {                                                        \
                 const int f = tid + 256 * i, row = f >> 2, k8 = f & 3;                                             \
-                const int nn = n0 + row < N ? n0 + row : 0;                                                        \
+                const int nn = n0 + row < N ? (ROWS ? rows[n0 + row] : n0 + row) : 0;                                                        \
                 xh[i] = *(const half8_d*)(in + (size_t)(nn % in_mod) * K + (K0) + 8 * k8);                         \
             }                                                                                                      \
         } else {                                                                                                   \
             _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                        \
                 const int f = tid + 256 * i, row = f >> 3, kq = f & 7;                                             \
-                const int nn = n0 + row < N ? n0 + row : 0;                                                        \
+                const int nn = n0 + row < N ? (ROWS ? rows[n0 + row] : n0 + row) : 0;                                                        \
                 xf[i] = *(const f32x4_d*)((const float*)in + (size_t)(nn % in_mod) * K + (K0) + 4 * kq);           \
             }                                                                                                      \
         }                                                                                                          \
@@ -118,6 +121,7 @@ __global__ __launch_bounds__(256) void dense_f32_kernel(const TIN* __restrict__ 
     }
 #undef DN_FETCH
     if (!valid) return;
+    const int n = ROWS ? rows[nc] : nc;
     const int tl = n / B, bimg = n - tl * B;
     const uint32_t t = (uint32_t)(t0 + tl);
     const float* mrow = site.kind == BMI_SITE_MASKSEMBLE ? site.masks + (size_t)((site.cnt0 + (int)t) % site.num_masks) * Cout : nullptr;
@@ -157,10 +161,11 @@ __global__ __launch_bounds__(256) void dense_f32_kernel(const TIN* __restrict__ 
 typedef _Float16 half4_d __attribute__((ext_vector_type(4)));
 
 // XKIND: 0 fp16 input (its own head), 1 fp32, 3 | 4 a pair32 tensor of the split engines (fp16 | bf16 halves: decoded while it is fetched)
-template <int XKIND>
+template <int XKIND, bool ROWS = false>
 __global__ __launch_bounds__(256) void dense_split_kernel(const void* __restrict__ in_, const float* __restrict__ w,
                                                           const float* __restrict__ bias, float* __restrict__ out, int N,
-                                                          int in_mod, int K, int Cout, int relu, SiteArgs site, int B, int t0) {
+                                                          int in_mod, int K, int Cout, int relu, SiteArgs site, int B, int t0,
+                                                          const int* __restrict__ rows) {
     constexpr bool XF32 = XKIND != 0;
     __shared__ __attribute__((aligned(16))) _Float16 Wh[DN_TF * 32], Wl[DN_TF * 32], Xh[DN_TS * 32], Xl[XF32 ? DN_TS * 32 : 8];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -183,7 +188,7 @@ __global__ __launch_bounds__(256) void dense_split_kernel(const void* __restrict
         if constexpr (XF32) {                                                                                      \
             _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                        \
                 const int f = tid + 256 * i, row = f >> 3, q4 = f & 7;                                             \
-                const int nn = n0 + row < N ? n0 + row : 0;                                                        \
+                const int nn = n0 + row < N ? (ROWS ? rows[n0 + row] : n0 + row) : 0;                                                        \
                 if constexpr (XKIND >= 3) {                                                                        \
                     float d_[4];                                                                                   \
                     pair_decode<XKIND == 4, 4>((const _Float16*)in_ + pair32_off((size_t)(nn % in_mod), K, (K0) + 4 * q4), d_); \
@@ -194,7 +199,7 @@ __global__ __launch_bounds__(256) void dense_split_kernel(const void* __restrict
         } else {                                                                                                   \
             _Pragma("unroll") for (int i = 0; i < 2; ++i) {                                                        \
                 const int f = tid + 256 * i, row = f >> 2, k8 = f & 3;                                             \
-                const int nn = n0 + row < N ? n0 + row : 0;                                                        \
+                const int nn = n0 + row < N ? (ROWS ? rows[n0 + row] : n0 + row) : 0;                                                        \
                 xh[i] = *(const half8_d*)((const _Float16*)in_ + (size_t)(nn % in_mod) * K + (K0) + 8 * k8);       \
             }                                                                                                      \
         }                                                                                                          \
@@ -260,8 +265,9 @@ __global__ __launch_bounds__(256) void dense_split_kernel(const void* __restrict
     // lane = sample l16 of tile j, registers = 4 consecutive features 16*i + 4*kq ..
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-        const int n = n0 + wave * 32 + 16 * j + l16;
-        if (n >= N) continue;
+        const int nc = n0 + wave * 32 + 16 * j + l16;
+        if (nc >= N) continue;
+        const int n = ROWS ? rows[nc] : nc;
         const int tl = n / B, bimg = n - tl * B;
         const uint32_t t = (uint32_t)(t0 + tl);
         const float* mrow = site.kind == BMI_SITE_MASKSEMBLE ? site.masks + (size_t)((site.cnt0 + (int)t) % site.num_masks) * Cout : nullptr;
@@ -289,23 +295,32 @@ __global__ __launch_bounds__(256) void dense_split_kernel(const void* __restrict
 }
 
 int launch_dense_f32(const void* in, int in_kind, const float* w, const float* bias, float* out, int n, int in_mod, int k,
-                     int cout, int relu, const SiteArgs& site, int batch, int t0, hipStream_t s) {
+                     int cout, int relu, const SiteArgs& site, int batch, int t0, hipStream_t s, const int* rows) {
     if (n <= 0 || in_mod <= 0 || batch <= 0) return BMI_ERR_INVALID;
     if (k % DN_KC != 0 || cout % DN_TF != 0) return BMI_ERR_UNSUPPORTED;
     const dim3 grid((n + DN_TS - 1) / DN_TS, cout / DN_TF), block(256);
-    if ((!opt_dense_exact() && in_kind != 2) || in_kind >= 3) {     // (pair32 inputs: the split form always)
-        if (in_kind == 1) hipLaunchKernelGGL((dense_split_kernel<1>), grid, block, 0, s, in, w, bias, out, n, in_mod, k, cout, relu, site, batch, t0);
-        else if (in_kind == 0) hipLaunchKernelGGL((dense_split_kernel<0>), grid, block, 0, s, in, w, bias, out, n, in_mod, k, cout, relu, site, batch, t0);
-        else if (in_kind == 3) hipLaunchKernelGGL((dense_split_kernel<3>), grid, block, 0, s, in, w, bias, out, n, in_mod, k, cout, relu, site, batch, t0);
-        else if (in_kind == 4) hipLaunchKernelGGL((dense_split_kernel<4>), grid, block, 0, s, in, w, bias, out, n, in_mod, k, cout, relu, site, batch, t0);
-        else return BMI_ERR_INVALID;
-        BMI_CHECK_LAUNCH();
-        return BMI_OK;
+#define DN_SPLIT(X_)                                                                                                                     \
+    {                                                                                                                                    \
+        if (rows) hipLaunchKernelGGL((dense_split_kernel<X_, true>), grid, block, 0, s, in, w, bias, out, n, in_mod, k, cout, relu, site, batch, t0, rows); \
+        else hipLaunchKernelGGL((dense_split_kernel<X_>), grid, block, 0, s, in, w, bias, out, n, in_mod, k, cout, relu, site, batch, t0, rows);           \
     }
-    if (in_kind == 1) hipLaunchKernelGGL((dense_f32_kernel<float, false>), grid, block, 0, s, (const float*)in, w, bias, out, n, in_mod, k, cout, relu, site, batch, t0);
-    else if (in_kind == 2) hipLaunchKernelGGL((dense_f32_kernel<_Float16, true>), grid, block, 0, s, (const _Float16*)in, w, bias, out, n, in_mod, k, cout, relu, site, batch, t0);
-    else if (in_kind == 0) hipLaunchKernelGGL((dense_f32_kernel<_Float16, false>), grid, block, 0, s, (const _Float16*)in, w, bias, out, n, in_mod, k, cout, relu, site, batch, t0);
+#define DN_EXACT(T_, BF_)                                                                                                                \
+    {                                                                                                                                    \
+        if (rows) hipLaunchKernelGGL((dense_f32_kernel<T_, BF_, true>), grid, block, 0, s, (const T_*)in, w, bias, out, n, in_mod, k, cout, relu, site, batch, t0, rows); \
+        else hipLaunchKernelGGL((dense_f32_kernel<T_, BF_>), grid, block, 0, s, (const T_*)in, w, bias, out, n, in_mod, k, cout, relu, site, batch, t0, rows);           \
+    }
+    if ((!opt_dense_exact() && in_kind != 2) || in_kind >= 3) {     // (pair32 inputs: the split form always)
+        if (in_kind == 1) DN_SPLIT(1)
+        else if (in_kind == 0) DN_SPLIT(0)
+        else if (in_kind == 3) DN_SPLIT(3)
+        else if (in_kind == 4) DN_SPLIT(4)
+        else return BMI_ERR_INVALID;
+    } else if (in_kind == 1) DN_EXACT(float, false)
+    else if (in_kind == 2) DN_EXACT(_Float16, true)
+    else if (in_kind == 0) DN_EXACT(_Float16, false)
     else return BMI_ERR_INVALID;
+#undef DN_SPLIT
+#undef DN_EXACT
     BMI_CHECK_LAUNCH();
     return BMI_OK;
 }

@@ -909,8 +909,8 @@ HeadArgs make_head_args(bmi_engine_s* e, const Pass& p, const OpInfo& op, int N,
     return a;
 }
 
-// imap / rows / Bc: dynamic early exit: N = samples * Bc compact images of the B-image batch; imap = the Bc active images
-// (heads), rows = the N-entry row table (ConvArgs::imap); null = all images
+// imap / rows / Bc: dynamic early exit and adaptive sampling: N = samples * Bc compact images of the B-image batch; imap = the Bc
+// active images (heads), rows = the N-entry row table (ConvArgs::imap, EltArgs::rows, the maxpool / dense launchers); null = all images
 int run_op(bmi_engine_s* e, const Pass& p, const OpInfo& op, int N, int t0, const int* imap = nullptr, int Bc = 0, const int* rows = nullptr) {
     const bmi_op_desc& d = op.d;
     const TensorInfo& tin = e->tensors[d.in];
@@ -923,7 +923,8 @@ int run_op(bmi_engine_s* e, const Pass& p, const OpInfo& op, int N, int t0, cons
         return (uint64_t)p.b0 * (st.kind == BMI_SITE_CHANNEL ? channels : per_image);
     };
     const int n_rows = imap ? (N / Bc) * B : N;     // rows of a stochastic tensor (original folded layout)
-    if (imap && d.kind != BMI_OP_CONV && d.kind != BMI_OP_HEAD) return BMI_ERR_UNSUPPORTED;
+    if (imap && d.kind != BMI_OP_CONV && d.kind != BMI_OP_HEAD && d.kind != BMI_OP_MASK && d.kind != BMI_OP_MAXPOOL && d.kind != BMI_OP_DENSE)
+        return BMI_ERR_UNSUPPORTED;      // (OP_MASKBITS: its conv_igemm readers have no row-table form)
     if (imap && e->f32 && !e->split) return BMI_ERR_UNSUPPORTED;      // (the exact engine: parity only)
     // a lazy site's tensor (see bmi_create) is written now if this op cannot apply the mask itself
     auto pending = [&](int id) { return id >= 0 && e->tensors[id].lazy_pending; };
@@ -1175,14 +1176,17 @@ int run_op(bmi_engine_s* e, const Pass& p, const OpInfo& op, int N, int t0, cons
             a.bf16 = e->bf16;
             a.in = (const _Float16*)(ws + tin.offset);
             a.out = ws + e->tensors[d.out].offset;
-            a.N = N; a.in_mod = tin.stoch ? N : B; a.HW = tin.h * tin.w; a.C = tin.c; a.B = B; a.t0 = t0;
+            a.N = N; a.in_mod = tin.stoch ? n_rows : B; a.HW = tin.h * tin.w; a.C = tin.c; a.B = B; a.t0 = t0;
+            a.rows = rows;
             a.site = pass_site(e, p, &d.site, site_off(d.site, (size_t)tin.h * tin.w * tin.c, (size_t)tin.c));
             if (d.site_pos == BMI_SITE_POS_INNER) { a.bias_post = d.bias_post; a.relu = d.relu; }
             a.pair = e->split;                                     // the split engines: pair32 tensors in and out
             if (e->f32) return launch_mask_apply_f32(a, s);
             TensorInfo& to = e->tensors[d.out];
             to.lazy_pending = false;
-            if (to.lazy_bits >= 0 && opt_mask_lazy() && !tin.stoch && N % B == 0) {
+            // under a row table a lazy site is materialised (its own workspace range, the lazy path's fallback): its stride-2 reader,
+            // conv3x3_s2 with keep bits, has no row-table form
+            if (to.lazy_bits >= 0 && opt_mask_lazy() && !tin.stoch && N % B == 0 && !rows) {
                 const bool planar = to.lazy_planar_plan && opt_lazy_planar();
                 to.lazy_planar_now = planar;
                 const int rcb = launch_mask_bits((uint8_t*)(ws + e->tensors[to.lazy_bits].offset), N, tin.h * tin.w, tin.c, a.site, B, t0, s, planar ? tin.w : 0);
@@ -1199,14 +1203,14 @@ int run_op(bmi_engine_s* e, const Pass& p, const OpInfo& op, int N, int t0, cons
             return launch_mask_apply(a, s);
         }
         case BMI_OP_MAXPOOL:
-            if (e->f32) return launch_maxpool2_f32((const float*)(ws + tin.offset), (float*)(ws + e->tensors[d.out].offset), N, tin.h, tin.w, tin.c, s, e->split);
+            if (e->f32) return launch_maxpool2_f32((const float*)(ws + tin.offset), (float*)(ws + e->tensors[d.out].offset), N, tin.h, tin.w, tin.c, s, e->split, rows);
             return launch_maxpool2((const _Float16*)(ws + tin.offset), (_Float16*)(ws + e->tensors[d.out].offset), N, tin.h,
-                                   tin.w, tin.c, e->bf16, s);
+                                   tin.w, tin.c, e->bf16, s, rows);
         case BMI_OP_DENSE:
             // input: fp32 (a dense layer's output; any tensor of the exact engine), the engine's 16-bit type, or pair32 (kinds 3 | 4)
             return launch_dense_f32(ws + tin.offset, (e->split && !tin.dense_out) ? 2 + e->split : (tin.f32 ? 1 : (e->bf16 ? 2 : 0)), (const float*)d.weight, d.bias,
-                                    (float*)(ws + e->tensors[d.out].offset), N, tin.stoch ? N : B, tin.c, op.cout, d.relu,
-                                    pass_site(e, p, &d.site, site_off(d.site, (size_t)op.cout, (size_t)op.cout)), B, t0, s);
+                                    (float*)(ws + e->tensors[d.out].offset), N, tin.stoch ? n_rows : B, tin.c, op.cout, d.relu,
+                                    pass_site(e, p, &d.site, site_off(d.site, (size_t)op.cout, (size_t)op.cout)), B, t0, s, rows);
         case BMI_OP_HEAD:
             // pool + site + Linear + softmax + the chunk's moment sums in one launch (head_fused.hip)
             return launch_head_fused(make_head_args(e, p, op, N, t0, imap, Bc), s);
@@ -1216,13 +1220,14 @@ int run_op(bmi_engine_s* e, const Pass& p, const OpInfo& op, int N, int t0, cons
 
 // One chunk of the suffix.  Consecutive exit heads run as ONE launch ("head_batch"; launch_head_fused_multi): with exit-only dropout — what
 // every run of the paper uses, Software_Artifact/script_figs/journal_script.sh:10-63 — the suffix is nothing but the heads, each a launch of
-// mostly fixed latency; the same arithmetic per head, the same bits.
-int run_suffix(bmi_engine_s* e, const Pass& p, int N, int t0) {
+// mostly fixed latency; the same arithmetic per head, the same bits.  Under a row table (imap / rows / Bc as in run_op: adaptive sampling)
+// the heads run one by one.
+int run_suffix(bmi_engine_s* e, const Pass& p, int N, int t0, const int* imap = nullptr, int Bc = 0, const int* rows = nullptr) {
     const hipStream_t s = p.stream;
     const std::vector<OpInfo>& ops = e->suffix;
     for (size_t i = 0; i < ops.size();) {
         size_t j = i;
-        if (opt_head_batch())
+        if (opt_head_batch() && !imap)
             while (j < ops.size() && j - i < BMI_HEAD_PACK_MAX && ops[j].d.kind == BMI_OP_HEAD && !e->tensors[ops[j].d.in].lazy_pending) ++j;
         if (j - i >= 2) {
             HeadArgs list[BMI_HEAD_PACK_MAX];
@@ -1240,7 +1245,7 @@ int run_suffix(bmi_engine_s* e, const Pass& p, int N, int t0) {
                 e->recs.pop_back();
             }
         }
-        const int rc = run_op(e, p, ops[i], N, t0);
+        const int rc = run_op(e, p, ops[i], N, t0, imap, Bc, rows);
         if (rc != BMI_OK) return rc;
         ++i;
     }
@@ -1365,6 +1370,12 @@ int bmi_forward_mcd_exit(bmi_handle h, const float* x_nchw, int32_t batch, int32
     if (batch < 1 || t_count < 1 || mask_cnt0 < 0 || first_exit < 0) return BMI_ERR_INVALID;
     if (h->max_batch == 0 || batch > h->max_batch) return BMI_ERR_INVALID;
     if (t_count > h->chunk || (h->f32 && !h->split)) return BMI_ERR_UNSUPPORTED;     // an exit's decision needs ALL samples of the stage in the workspace
+    const int last = h->n_exits - 1;
+    bool compacted = false;        // MASK / MAXPOOL / DENSE ops behind the first tested exit: not this entry point's contract
+    for (const OpInfo& op : h->suffix) {
+        if (compacted && (op.d.kind == BMI_OP_MASK || op.d.kind == BMI_OP_MAXPOOL || op.d.kind == BMI_OP_DENSE)) return BMI_ERR_UNSUPPORTED;
+        compacted = compacted || (op.d.kind == BMI_OP_HEAD && op.d.out >= first_exit && op.d.out < last);
+    }
     if (workspace_bytes < h->ws_bytes) return BMI_ERR_NOMEM;
     Pass p{x_nchw, (char*)workspace, (hipStream_t)stream, batch, seed, mask_cnt0};
     p.S1 = S1; p.S2 = S2; p.SL = SL;
@@ -1373,7 +1384,6 @@ int bmi_forward_mcd_exit(bmi_handle h, const float* x_nchw, int32_t batch, int32
     int* lists[2] = {(int*)(ws + h->exit_off), (int*)(ws + h->exit_off) + h->max_batch};
     int* count_dev = (int*)(ws + h->exit_off) + 2 * h->max_batch;
     int* rows_dev = count_dev + 64;
-    const int last = h->n_exits - 1;
     int rc = launch_fill_int(exit_of_image, batch, last, s);
     if (rc != BMI_OK) return rc;
     for (int x = 0; x < h->n_exits; ++x) active_after[x] = 0;
@@ -1408,6 +1418,77 @@ int bmi_forward_mcd_exit(bmi_handle h, const float* x_nchw, int32_t batch, int32
         rows = rows_dev;
     }
     return BMI_OK;
+}
+
+int bmi_forward_mcd_adaptive(bmi_handle h, const float* x_nchw, int32_t batch, int32_t image_offset, int32_t t_max,
+                             int32_t t_step, uint64_t seed, int32_t mask_cnt0, int32_t rule, double threshold,
+                             int32_t test_exit, double* S1, double* S2, double* SL, double* SH, int32_t* t_used,
+                             uint8_t* converged, int32_t* active_after_step, void* workspace, size_t workspace_bytes,
+                             bmi_stream stream) {
+    const int rco = bmi_image_offset_ok(h, image_offset);      // (a null handle: BMI_ERR_INVALID)
+    if (rco != BMI_OK) return rco;
+    BmiOptionScope opt_scope(&h->opts);
+    if (!x_nchw || !S1 || !S2 || !SL || !t_used || !active_after_step || !workspace) return BMI_ERR_INVALID;
+    if (batch < 1 || t_max < 1 || t_step < 1 || mask_cnt0 < 0) return BMI_ERR_INVALID;
+    if (rule != BMI_STOP_SEM && rule != BMI_STOP_MARGIN) return BMI_ERR_INVALID;
+    if (test_exit < 0 || test_exit >= h->n_exits) return BMI_ERR_INVALID;
+    if (h->max_batch == 0 || batch > h->max_batch) return BMI_ERR_INVALID;
+    if (t_step > h->chunk || (h->f32 && !h->split)) return BMI_ERR_UNSUPPORTED;     // (a step is one suffix chunk: the row table holds chunk x max_batch)
+    for (const OpInfo& op : h->suffix)
+        if (op.d.kind == OP_MASKBITS) return BMI_ERR_UNSUPPORTED;
+    if (workspace_bytes < h->ws_bytes) return BMI_ERR_NOMEM;
+    Pass p{x_nchw, (char*)workspace, (hipStream_t)stream, batch, seed, mask_cnt0};
+    p.b0 = image_offset;
+    p.S1 = S1; p.S2 = S2; p.SL = SL; p.SH = SH;
+    const hipStream_t s = p.stream;
+    // the exit region of the workspace (bmi_plan): two active-image lists, a counter, the row table
+    int* lists[2] = {(int*)(p.ws + h->exit_off), (int*)(p.ws + h->exit_off) + h->max_batch};
+    int* count_dev = (int*)(p.ws + h->exit_off) + 2 * h->max_batch;
+    int* rows_dev = count_dev + 64;
+    const size_t eo = (size_t)test_exit * batch * h->out_dim;
+    const int n_steps = (t_max + t_step - 1) / t_step;
+    for (int k = 0; k < n_steps; ++k) active_after_step[k] = 0;
+    int rc;
+    for (const OpInfo& op : h->prefix) {
+        rc = run_op(h, p, op, batch, 0);
+        if (rc != BMI_OK) return rc;
+    }
+    const int* imap = nullptr;     // null: every image is still active — the step runs bmi_forward_mcd's kernels
+    const int* rows = nullptr;
+    int bc = batch, cur = 0;
+    for (int k = 0, t0 = 0; k < n_steps; ++k, t0 += t_step) {
+        const int tc = std::min(t_step, t_max - t0);
+        rc = run_suffix(h, p, tc * bc, t0, imap, bc, rows);
+        if (rc != BMI_OK) return rc;
+        // the stop rule over the still-active images, on the device; the host only learns how many go on
+        rc = launch_adaptive_decide(S1 + eo, S2 + eo, h->out_dim, t0 + tc, rule, threshold, imap, bc, lists[cur], count_dev, t_used, s);
+        if (rc != BMI_OK) return rc;
+        int n_active = 0;
+        if (hipMemcpyAsync(&n_active, count_dev, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+            return BMI_ERR_HIP;
+        active_after_step[k] = n_active;
+        if (n_active == 0 || k + 1 == n_steps) break;
+        if (n_active == batch) continue;           // nobody has retired yet: the next step runs on the full grids too
+        imap = lists[cur];
+        bc = n_active;
+        cur ^= 1;
+        rc = launch_expand_rows(imap, bc, batch, std::min(t_step, t_max - t0 - t_step), rows_dev, s);   // compact image -> tensor row
+        if (rc != BMI_OK) return rc;
+        rows = rows_dev;
+    }
+    return converged ? launch_adaptive_converged(S1 + eo, S2 + eo, h->out_dim, rule, threshold, batch, t_used, converged, s) : BMI_OK;
+}
+
+int bmi_finalize_per_image(int32_t n_exits, int32_t batch, int32_t out_dim, const int32_t* t_used, const double* S1,
+                           const double* S2, const double* SL, const double* SH, double* mean, double* var,
+                           double* logit_mean, double* pred_entropy, double* exp_entropy, double* mutual_info,
+                           int32_t* nonfinite, bmi_stream stream) {
+    if (!t_used || !S1 || !S2 || !SL || !mean || !var || !logit_mean || n_exits < 1 || batch < 1 || out_dim < 1) return BMI_ERR_INVALID;
+    const bool any_unc = SH || pred_entropy || exp_entropy || mutual_info;
+    if (any_unc && !(SH && pred_entropy && exp_entropy && mutual_info)) return BMI_ERR_INVALID;
+    if ((int64_t)n_exits * batch > INT32_MAX) return BMI_ERR_UNSUPPORTED;
+    return launch_finalize_per_image(n_exits, batch, out_dim, t_used, S1, S2, SL, SH, mean, var, logit_mean, pred_entropy, exp_entropy,
+                                     mutual_info, nonfinite, (hipStream_t)stream);
 }
 
 int bmi_finalize(int64_t n, int32_t t_total, const double* S1, const double* S2, const double* SL, double* mean,

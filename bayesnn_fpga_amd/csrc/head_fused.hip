@@ -498,7 +498,6 @@ static int head_prepare(HeadArgs& a) {
     if (groups <= 1) a.part = nullptr;             // one group per image: the workgroup adds into S1 / S2 / SL itself
     if (!a.in || !a.w || !a.bias) return BMI_ERR_INVALID;
     if (!a.S1 || !a.S2 || !a.SL) { if (!a.logits) return BMI_ERR_INVALID; a.S1 = a.S2 = a.SL = a.SH = nullptr; a.part = nullptr; }     // logits only
-    if (a.SH && a.imap) return BMI_ERR_UNSUPPORTED;      // (the entropy plane is per image of the full batch: no dynamic early exit)
     if (a.B <= 0 || a.tc <= 0 || a.in_mod <= 0 || a.HW <= 0 || a.C <= 0 || a.in_kind < 0 || a.in_kind > 4) return BMI_ERR_INVALID;
     if (a.in_mod != a.B && a.in_mod != a.B * a.tc) return BMI_ERR_INVALID;
     if (a.imap && (a.Bc <= 0 || a.Bc > a.B)) return BMI_ERR_INVALID;

@@ -96,6 +96,8 @@ struct EltArgs {  // MASK op
     const float* bias_post;  // MASK with an inner site: out = relu?(x * mask + bias_post[c]); or null
     int relu;
     int tchunk;              // (set by the launcher) samples per work item of mask_apply_lb1_kernel
+    const int* rows;         // adaptive sampling: launch image i is folded row rows[i] of `in` / `out` and of the Philox index space
+                             // (N compact images; in_mod as for the full folded batch), or null (identity)
 };
 
 struct HeadArgs {   // fused exit head (head_fused.hip)
@@ -141,15 +143,28 @@ int launch_conv_exact(const ConvArgs& a, hipStream_t s);
 int launch_conv_split(const ConvArgs& a, int bf16, hipStream_t s);
 bool conv_takes_split_kernel(int cin, int cout);
 int launch_mask_apply_f32(const EltArgs& a, hipStream_t s);
-int launch_maxpool2_f32(const float* in, float* out, int n, int h, int w, int c, hipStream_t s, int pair = 0);   // pair: 1 | 2 = pair32 tensors (fp16 | bf16)
+// rows (maxpool, dense; EltArgs::rows for the mask): adaptive sampling's row table — launch image i is folded row rows[i] of the
+// tensors and of the Philox index space — or null
+int launch_maxpool2_f32(const float* in, float* out, int n, int h, int w, int c, hipStream_t s, int pair = 0, const int* rows = nullptr);   // pair: 1 | 2 = pair32 tensors (fp16 | bf16)
 int launch_mask_apply(const EltArgs& a, hipStream_t s);
-int launch_maxpool2(const _Float16* in, _Float16* out, int n, int h, int w, int c, int bf16, hipStream_t s);
+int launch_maxpool2(const _Float16* in, _Float16* out, int n, int h, int w, int c, int bf16, hipStream_t s, const int* rows = nullptr);
 // hidden dense layer, fp32 weights [cout][k] / accumulate / output; `in` 16-bit (in_kind 0: fp16, 2: bf16) or fp32 (1) [n or in_mod][k]
 int launch_dense_f32(const void* in, int in_kind, const float* w, const float* bias, float* out, int n, int in_mod, int k,
-                     int cout, int relu, const SiteArgs& site, int batch, int t0, hipStream_t s);
+                     int cout, int relu, const SiteArgs& site, int batch, int t0, hipStream_t s, const int* rows = nullptr);
 int launch_exit_decide(const double* S1e, int C, int t_total, double thr, const int* in, int bc, int* out, int* count,
                        int* exit_of, int e, hipStream_t s);
 int launch_fill_int(int* p, int n, int v, hipStream_t s);
+// adaptive sampling's stop rule (BMI_STOP_*) at one exit, S1e / S2e = its [batch][C] sums: every image of the active list `in` (null:
+// 0 .. bc-1) gets t_used[b] = t; the ones that pass retire, the others go to `out` in order, their number to *count
+int launch_adaptive_decide(const double* S1e, const double* S2e, int C, int t, int rule, double thr, const int* in, int bc, int* out,
+                           int* count, int* t_used, hipStream_t s);
+// converged[b] = the rule at t_used[b], b < batch
+int launch_adaptive_converged(const double* S1e, const double* S2e, int C, int rule, double thr, int batch, const int* t_used,
+                              uint8_t* converged, hipStream_t s);
+// launch_finalize (with a nonfinite count when not null) and, when SH is not null, launch_finalize_uncertainty, dividing row (exit, b) by t_used[b]
+int launch_finalize_per_image(int n_exits, int batch, int C, const int* t_used, const double* S1, const double* S2, const double* SL,
+                              const double* SH, double* mean, double* var, double* lm, double* pred, double* expd, double* mi, int* nonfinite,
+                              hipStream_t s);
 // dst[r][c] = src[(cnt0 + r * stride) % m][c], r < m (a Masksembles table in the order a strided walk visits it)
 int launch_mask_permute(const float* src, float* dst, int m, int c, int cnt0, int stride, hipStream_t s);
 int launch_expand_rows(const int* active, int bc, int batch, int tc, int* rows, hipStream_t s);   // rows[tl*bc + i] = tl*batch + active[i]

@@ -28,15 +28,17 @@ __device__ __forceinline__ void site_mask8(const SiteArgs& s, float v[8], uint64
 }
 
 // ---------------------------------------------------------------------------------------------
-template <bool BF>
+// ROWS (adaptive sampling, a.rows): launch image i is folded row a.rows[i] of the input / output tensors and of the Philox index space
+template <bool BF, bool ROWS = false>
 __global__ __launch_bounds__(256) void mask_apply_kernel(EltArgs a) {
     const int cg = a.C >> 3;  // 8-channel groups per pixel
     const long total = (long)a.N * a.HW * cg;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
         const int c8 = (int)(i % cg) * 8;
         const long pix = i / cg;  // n*HW + p
-        const int n = (int)(pix / a.HW);
-        const int p = (int)(pix - (long)n * a.HW);
+        const int nc = (int)(pix / a.HW);
+        const int p = (int)(pix - (long)nc * a.HW);
+        const int n = ROWS ? a.rows[nc] : nc;
         const int tl = n / a.B, b = n - tl * a.B;
         const int t = a.t0 + tl;
         const half8 x = *(const half8*)(a.in + ((size_t)(n % a.in_mod) * a.HW + p) * a.C + c8);
@@ -197,6 +199,12 @@ int launch_mask_apply(const EltArgs& a, hipStream_t s) {
     const long total = (long)a.N * a.HW * (a.C >> 3);
     long blocks = (total + 255) / 256;
     if (blocks > 256 * 16) blocks = 256 * 16;
+    if (a.rows) {      // a row table: the per-item kernel (the same value per element as the shared-Philox forms below)
+        if (a.bf16) hipLaunchKernelGGL((mask_apply_kernel<true, true>), dim3((unsigned)blocks), dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((mask_apply_kernel<false, true>), dim3((unsigned)blocks), dim3(256), 0, s, a);
+        BMI_CHECK_LAUNCH();
+        return BMI_OK;
+    }
     static const int share = [] { const char* v = std::getenv("BMI_MASK_SHARE"); return v ? std::atoi(v) : 1; }();
     const int lb = a.site.log2_bits;
     const long sample_elems = (long)a.B * a.HW * a.C;
@@ -399,8 +407,9 @@ int launch_mask_bits(uint8_t* bits, int n, int hw, int c, const SiteArgs& site, 
 }
 
 // ---------------------------------------------------------------------------------------------
-template <bool BF>
-__global__ __launch_bounds__(256) void maxpool2_kernel(const _Float16* in, _Float16* out, int N, int H, int W, int C) {
+// ROWS: launch image i is folded row rows[i] of both tensors (adaptive sampling)
+template <bool BF, bool ROWS = false>
+__global__ __launch_bounds__(256) void maxpool2_kernel(const _Float16* in, _Float16* out, int N, int H, int W, int C, const int* rows) {
     const int cg = C >> 3, Ho = H >> 1, Wo = W >> 1;
     const long total = (long)N * Ho * Wo * cg;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
@@ -408,7 +417,7 @@ __global__ __launch_bounds__(256) void maxpool2_kernel(const _Float16* in, _Floa
         long q = i / cg;
         const int ox = (int)(q % Wo); q /= Wo;
         const int oy = (int)(q % Ho);
-        const int n = (int)(q / Ho);
+        const int n = ROWS ? rows[q / Ho] : (int)(q / Ho);
         const _Float16* p = in + (((size_t)n * H + 2 * oy) * W + 2 * ox) * C + c8;
         const half8 a0 = *(const half8*)p, a1 = *(const half8*)(p + C);
         const half8 a2 = *(const half8*)(p + (size_t)W * C), a3 = *(const half8*)(p + (size_t)W * C + C);
@@ -422,14 +431,18 @@ __global__ __launch_bounds__(256) void maxpool2_kernel(const _Float16* in, _Floa
     }
 }
 
-int launch_maxpool2(const _Float16* in, _Float16* out, int n, int h, int w, int c, int bf16, hipStream_t s) {
+int launch_maxpool2(const _Float16* in, _Float16* out, int n, int h, int w, int c, int bf16, hipStream_t s, const int* rows) {
     if (c % 8 != 0 || (h & 1) || (w & 1)) return BMI_ERR_UNSUPPORTED;
     const long total = (long)n * (h / 2) * (w / 2) * (c / 8);
     long blocks = (total + 255) / 256;
     if (blocks > 256 * 16) blocks = 256 * 16;
     if (blocks <= 0) return BMI_ERR_INVALID;
-    if (bf16) hipLaunchKernelGGL(maxpool2_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, in, out, n, h, w, c);
-    else hipLaunchKernelGGL(maxpool2_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, in, out, n, h, w, c);
+    const dim3 g((unsigned)blocks), b(256);
+    if (rows) {
+        if (bf16) hipLaunchKernelGGL((maxpool2_kernel<true, true>), g, b, 0, s, in, out, n, h, w, c, rows);
+        else hipLaunchKernelGGL((maxpool2_kernel<false, true>), g, b, 0, s, in, out, n, h, w, c, rows);
+    } else if (bf16) hipLaunchKernelGGL((maxpool2_kernel<true>), g, b, 0, s, in, out, n, h, w, c, rows);
+    else hipLaunchKernelGGL((maxpool2_kernel<false>), g, b, 0, s, in, out, n, h, w, c, rows);
     BMI_CHECK_LAUNCH();
     return BMI_OK;
 }
@@ -610,6 +623,94 @@ int launch_expand_rows(const int* active, int bc, int batch, int tc, int* rows, 
     return BMI_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Adaptive sampling (bmi_forward_mcd_adaptive): the stop rule of one image on its running sums at the tested exit, float64, as the
+// header states it (m = S1 / t, v = max(S2 / t - m^2, 0); no contraction into fma: a numpy re-derivation gets the same statistic).
+__device__ bool adaptive_stop(const double* __restrict__ s1, const double* __restrict__ s2, int C, double t, int rule, double thr) {
+#pragma clang fp contract(off)
+    if (rule == BMI_STOP_SEM) {
+        double stat = 0.0;
+        for (int c = 0; c < C; ++c) {
+            const double m = s1[c] / t, v = fmax(s2[c] / t - m * m, 0.0);
+            stat = fmax(stat, sqrt(v / t));
+        }
+        return stat <= thr;
+    }
+    int c1 = 0;
+    for (int c = 1; c < C; ++c)
+        if (s1[c] / t > s1[c1] / t) c1 = c;
+    int c2 = -1;
+    for (int c = 0; c < C; ++c)
+        if (c != c1 && (c2 < 0 || s1[c] / t > s1[c2] / t)) c2 = c;
+    if (c2 < 0) return true;                        // (one class: nothing to separate it from)
+    const double m1 = s1[c1] / t, m2 = s1[c2] / t;
+    const double v1 = fmax(s2[c1] / t - m1 * m1, 0.0), v2 = fmax(s2[c2] / t - m2 * m2, 0.0);
+    const double d = m1 - m2, den = sqrt((v1 + v2) / t);
+    const double stat = den > 0.0 ? d / den : (d > 0.0 ? __builtin_huge_val() : 0.0);
+    return stat >= thr;
+}
+
+// DECIDE: among the `bc` active images (list `in`, identity when null), every one gets t_used[b] = t; those whose rule holds retire, the
+// others are written, order preserved, to `out` (`in` != `out`) and counted (exit_decide_kernel's compaction).  FINAL: converged[b] = the
+// rule at t_used[b], for images 0 .. bc-1.  S1e / S2e: the tested exit's [batch][C] sums.
+template <bool FINAL>
+__global__ __launch_bounds__(256) void adaptive_decide_kernel(const double* __restrict__ S1e, const double* __restrict__ S2e, int C, int t,
+                                                              int rule, double thr, const int* __restrict__ in, int bc, int* __restrict__ out,
+                                                              int* __restrict__ count, int* __restrict__ t_used, uint8_t* __restrict__ converged) {
+    __shared__ int scan[256];
+    __shared__ int base_s;
+    const int tid = threadIdx.x;
+    if (FINAL) {
+        for (int b = (int)(blockIdx.x * blockDim.x) + tid; b < bc; b += (int)(gridDim.x * blockDim.x))
+            converged[b] = adaptive_stop(S1e + (size_t)b * C, S2e + (size_t)b * C, C, (double)t_used[b], rule, thr) ? 1 : 0;
+        return;
+    }
+    if (tid == 0) base_s = 0;
+    __syncthreads();
+    for (int base = 0; base < bc; base += 256) {
+        const int i = base + tid;
+        int keep = 0, b = -1;
+        if (i < bc) {
+            b = in ? in[i] : i;
+            t_used[b] = t;
+            keep = adaptive_stop(S1e + (size_t)b * C, S2e + (size_t)b * C, C, (double)t, rule, thr) ? 0 : 1;
+        }
+        scan[tid] = keep;
+        __syncthreads();
+        for (int off = 1; off < 256; off <<= 1) {
+            const int v = tid >= off ? scan[tid - off] : 0;
+            __syncthreads();
+            scan[tid] += v;
+            __syncthreads();
+        }
+        if (keep) out[base_s + scan[tid] - 1] = b;
+        __syncthreads();
+        if (tid == 255) base_s += scan[255];
+        __syncthreads();
+    }
+    if (tid == 0) *count = base_s;
+}
+
+int launch_adaptive_decide(const double* S1e, const double* S2e, int C, int t, int rule, double thr, const int* in, int bc, int* out,
+                           int* count, int* t_used, hipStream_t s) {
+    if (!S1e || !S2e || !out || !count || !t_used || bc <= 0 || C <= 0 || t <= 0 || in == out) return BMI_ERR_INVALID;
+    if (rule != BMI_STOP_SEM && rule != BMI_STOP_MARGIN) return BMI_ERR_INVALID;
+    hipLaunchKernelGGL((adaptive_decide_kernel<false>), dim3(1), dim3(256), 0, s, S1e, S2e, C, t, rule, thr, in, bc, out, count, t_used,
+                       (uint8_t*)nullptr);
+    BMI_CHECK_LAUNCH();
+    return BMI_OK;
+}
+
+int launch_adaptive_converged(const double* S1e, const double* S2e, int C, int rule, double thr, int batch, const int* t_used,
+                              uint8_t* converged, hipStream_t s) {
+    if (!S1e || !S2e || !t_used || !converged || batch <= 0 || C <= 0) return BMI_ERR_INVALID;
+    if (rule != BMI_STOP_SEM && rule != BMI_STOP_MARGIN) return BMI_ERR_INVALID;
+    hipLaunchKernelGGL((adaptive_decide_kernel<true>), dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, s, S1e, S2e, C, 0, rule, thr,
+                       (const int*)nullptr, batch, (int*)nullptr, (int*)nullptr, (int*)t_used, converged);
+    BMI_CHECK_LAUNCH();
+    return BMI_OK;
+}
+
 __global__ void fill_int_kernel(int* p, int n, int v) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) p[i] = v;
@@ -638,12 +739,14 @@ int launch_fill_int(int* p, int n, int v, hipStream_t s) {
 
 // CHECK: also counts the elements whose sums are not finite (an fp16 activation that saturated at 65 504 turns into inf, then NaN in the
 // softmax) into *nonfinite — one ballot per wavefront, one atomic per wavefront that saw any.
-template <bool CHECK>
+// PER_IMAGE (bmi_finalize_per_image): element i = (exit, image b, class) of [E][batch][C] divides by t_used[b] instead of one T.
+template <bool CHECK, bool PER_IMAGE = false>
 __global__ void finalize_kernel(long n, double inv_t, const double* S1, const double* S2, const double* SL, double* mean,
-                                double* var, double* lm, int* nonfinite) {
+                                double* var, double* lm, int* nonfinite, const int* t_used, int batch, int C) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     bool bad = false;
     if (i < n) {
+        if (PER_IMAGE) inv_t = 1.0 / t_used[(i / C) % batch];
         const double s1 = S1[i], s2 = S2[i], sl = SL[i];
         const double m = s1 * inv_t;
         const double v = s2 * inv_t - m * m;
@@ -662,8 +765,10 @@ int launch_finalize(int64_t n, int t_total, const double* S1, const double* S2, 
                     double* var, double* lm, int* nonfinite, hipStream_t s) {
     if (n <= 0 || t_total <= 0) return BMI_ERR_INVALID;
     const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-    if (nonfinite) hipLaunchKernelGGL(finalize_kernel<true>, grid, block, 0, s, (long)n, 1.0 / t_total, S1, S2, SL, mean, var, lm, nonfinite);
-    else hipLaunchKernelGGL(finalize_kernel<false>, grid, block, 0, s, (long)n, 1.0 / t_total, S1, S2, SL, mean, var, lm, nonfinite);
+    if (nonfinite) hipLaunchKernelGGL((finalize_kernel<true>), grid, block, 0, s, (long)n, 1.0 / t_total, S1, S2, SL, mean, var, lm, nonfinite,
+                                      (const int*)nullptr, 1, 1);
+    else hipLaunchKernelGGL((finalize_kernel<false>), grid, block, 0, s, (long)n, 1.0 / t_total, S1, S2, SL, mean, var, lm, nonfinite,
+                            (const int*)nullptr, 1, 1);
     BMI_CHECK_LAUNCH();
     return BMI_OK;
 }
@@ -671,10 +776,14 @@ int launch_finalize(int64_t n, int t_total, const double* S1, const double* S2, 
 // ---------------------------------------------------------------------------------------------
 // One wave per (exit, image) row: lanes walk the classes of the mean m = S1 / T, -sum m log m (0 log 0 = 0) meets by float64
 // wavefront shuffle; expected entropy SH / T; mutual information = their difference, clamped at 0 (a NaN stays a NaN).
+// PER_IMAGE: row (exit, image b) divides by t_used[b].
+template <bool PER_IMAGE = false>
 __global__ __launch_bounds__(256) void finalize_uncertainty_kernel(int rows, int C, double inv_t, const double* S1, const double* SH,
-                                                                   double* pred, double* expd, double* mi, int* nonfinite) {
+                                                                   double* pred, double* expd, double* mi, int* nonfinite, const int* t_used,
+                                                                   int batch) {
     const int row = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6), lane = threadIdx.x & 63;
     if (row >= rows) return;                       // (wave-uniform)
+    if (PER_IMAGE) inv_t = 1.0 / t_used[row % batch];
     const double* s1 = S1 + (size_t)row * C;
     double h = 0.0;
     int bad = 0;
@@ -705,7 +814,25 @@ int launch_finalize_uncertainty(int n_rows, int C, int t_total, const double* S1
                                 double* mi, int* nonfinite, hipStream_t s) {
     if (n_rows <= 0 || C <= 0 || t_total <= 0) return BMI_ERR_INVALID;
     const dim3 grid((unsigned)((n_rows + 3) / 4)), block(256);
-    hipLaunchKernelGGL(finalize_uncertainty_kernel, grid, block, 0, s, n_rows, C, 1.0 / t_total, S1, SH, pred, expd, mi, nonfinite);
+    hipLaunchKernelGGL((finalize_uncertainty_kernel<false>), grid, block, 0, s, n_rows, C, 1.0 / t_total, S1, SH, pred, expd, mi, nonfinite,
+                       (const int*)nullptr, 1);
+    BMI_CHECK_LAUNCH();
+    return BMI_OK;
+}
+
+int launch_finalize_per_image(int n_exits, int batch, int C, const int* t_used, const double* S1, const double* S2, const double* SL,
+                              const double* SH, double* mean, double* var, double* lm, double* pred, double* expd, double* mi, int* nonfinite,
+                              hipStream_t s) {
+    if (n_exits <= 0 || batch <= 0 || C <= 0 || !t_used) return BMI_ERR_INVALID;
+    const long n = (long)n_exits * batch * C;
+    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    if (nonfinite) hipLaunchKernelGGL((finalize_kernel<true, true>), grid, block, 0, s, n, 1.0, S1, S2, SL, mean, var, lm, nonfinite, t_used, batch, C);
+    else hipLaunchKernelGGL((finalize_kernel<false, true>), grid, block, 0, s, n, 1.0, S1, S2, SL, mean, var, lm, nonfinite, t_used, batch, C);
+    BMI_CHECK_LAUNCH();
+    if (!SH) return BMI_OK;
+    const int rows = n_exits * batch;
+    hipLaunchKernelGGL((finalize_uncertainty_kernel<true>), dim3((unsigned)((rows + 3) / 4)), block, 0, s, rows, C, 1.0, S1, SH, pred, expd, mi,
+                       nonfinite, t_used, batch);
     BMI_CHECK_LAUNCH();
     return BMI_OK;
 }

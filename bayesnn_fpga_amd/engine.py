@@ -24,6 +24,11 @@ from .utils import Masksembles1D, Masksembles2D
 
 DEFAULT_CHUNK_IMAGES = 25600      # image-samples folded into one suffix launch (tuned on MI355X)
 DEFAULT_CHUNK_SAMPLES_MAX = 128   # ... but never more than this many samples (the workspace is sized for a full chunk)
+DEFAULT_ADAPTIVE_T_STEP = 25      # samples per step of predict_adaptive (never more than the planned chunk): a smaller step stops images
+                                  # sooner but runs smaller launches and one more host sync per step.  Headline model, B = 250, T_max = 100,
+                                  # SEM threshold at the median of the first step's (tools/adaptive_bench.py, MI355X): t_step 10 / 20 / 25 /
+                                  # 50 -> 10.5 / 10.1 / 10.4 / 11.6 ms per batch (fixed T = 100: 22.1 ms); 20 and 25 are within noise, 25
+                                  # splits T = 100 into four steps
 
 
 def _is_site(m):
@@ -566,6 +571,80 @@ class MCDEngine(CompiledGraph):
         r["exit_layer"] = exit_layer
         r["active_after"] = [int(v) for v in active]
         r["best_preds"] = r["mean"][exit_layer.long(), torch.arange(B, device=self.device)]
+        return r
+
+    def accumulate_adaptive(self, x, S, T_max, threshold, rule="sem", t_step=None, test_exit=-1, seed=0, cnt0=0, H=None, image_offset=0):
+        """The sampling half of ``predict_adaptive`` (bmi_forward_mcd_adaptive) into the ZEROED sums S [3, E, B, C] (and H [E, B]:
+        ``new_uncertainty_sums``): on return image b's rows hold exactly its first t_used[b] samples.  Returns (t_used int32 [B],
+        converged uint8 [B], active_after_step host list)."""
+        x = self._check_x(x)
+        B = x.shape[0]
+        if rule not in _lib.STOP_RULES:
+            raise ValueError(f"rule must be one of {sorted(_lib.STOP_RULES)}, got {rule!r}")
+        if t_step is None:
+            t_step = min(DEFAULT_ADAPTIVE_T_STEP, self.chunk_samples)
+        T_max, t_step, test_exit = int(T_max), int(t_step), int(test_exit)
+        if T_max < 1:
+            raise ValueError(f"T_max must be >= 1, got {T_max}")
+        if not 1 <= t_step <= self.chunk_samples:
+            raise ValueError(f"t_step must be in [1, {self.chunk_samples}] (the engine's planned chunk), got {t_step}")
+        if test_exit < 0:
+            test_exit += self.n_exits
+        if not 0 <= test_exit < self.n_exits:
+            raise ValueError(f"test_exit out of range for {self.n_exits} exits")
+        if tuple(S.shape) != (3, self.n_exits, B, self.out_dim) or S.dtype != torch.float64 or not S.is_contiguous():
+            raise ValueError("moment buffer must be contiguous float64 [3, E, B, C]")
+        if H is not None and (tuple(H.shape) != (self.n_exits, B) or H.dtype != torch.float64 or not H.is_contiguous()):
+            raise ValueError("entropy buffer must be contiguous float64 [E, B]")
+        t_used = torch.empty(B, dtype=torch.int32, device=self.device)
+        converged = torch.empty(B, dtype=torch.uint8, device=self.device)
+        active = (C.c_int32 * (-(-T_max // t_step)))()
+        with torch.cuda.device(self.device):
+            rc = self.lib.bmi_forward_mcd_adaptive(self.handle, x.data_ptr(), B, int(image_offset), T_max, t_step, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                                   int(cnt0), _lib.STOP_RULES[rule], float(threshold), test_exit, S[0].data_ptr(), S[1].data_ptr(),
+                                                   S[2].data_ptr(), None if H is None else H.data_ptr(), t_used.data_ptr(), converged.data_ptr(),
+                                                   active, self.workspace.data_ptr(), self.workspace_bytes, self._stream())
+        _lib.check(rc, "bmi_forward_mcd_adaptive")
+        return t_used, converged, [int(v) for v in active]
+
+    def predict_adaptive(self, x, T_max, threshold, rule="sem", t_step=None, test_exit=-1, seed=0, cnt0=0, uncertainty=False,
+                         image_offset=0):
+        """Adaptive Monte-Carlo sampling on the device (bmi_forward_mcd_adaptive): samples run in steps of ``t_step`` (default
+        DEFAULT_ADAPTIVE_T_STEP, at most the planned chunk) up to ``T_max``; after each step an image whose running estimate at exit
+        ``test_exit`` passes the stop rule retires, and the later steps run on the images still active only.  Rules: ``"sem"`` — the
+        largest standard error of the mean softmax, max_c sqrt(var_c / t), is at most ``threshold``; ``"margin"`` —
+        (m_top1 - m_top2) / sqrt((var_top1 + var_top2) / t) is at least ``threshold``.  Every sample keeps its global index, so image b's
+        result is ``predict(T=t_used[b])``'s for that image.  Returns dict(mean / var / logit_mean [E,B,C] float64, t_used int32 [B] and
+        converged bool [B] on the device, active_after_step: host list of the images still active after each step); with
+        ``uncertainty``, also pred_entropy / exp_entropy / mutual_info [E,B] as in ``finalize_uncertainty``.  Synchronises once per step."""
+        B = x.shape[0]
+        S, H = self.new_uncertainty_sums(B) if uncertainty else (self.new_moments(B), None)
+        t_used, converged, active = self.accumulate_adaptive(x, S, T_max, threshold, rule, t_step, test_exit, seed, cnt0, H, image_offset)
+        r = self.finalize_per_image(S, t_used, H)
+        r.update(t_used=t_used, converged=converged.bool(), active_after_step=active)
+        return r
+
+    def finalize_per_image(self, S, t_used, H=None):
+        """``finalize`` (and, with H, ``finalize_uncertainty``) with image b's sums divided by its own sample count t_used[b]
+        (bmi_finalize_per_image; device int32 [B], every entry >= 1)."""
+        E, B, Cd = S.shape[1], S.shape[2], S.shape[3]
+        if S.dtype != torch.float64 or not S.is_contiguous():
+            raise ValueError("moment buffer must be contiguous float64 [3, E, B, C]")
+        if tuple(t_used.shape) != (B,) or t_used.dtype != torch.int32 or t_used.device != S.device:
+            raise ValueError("t_used must be int32 [B] on the moment buffer's device")
+        if H is not None and (tuple(H.shape) != (E, B) or H.dtype != torch.float64 or not H.is_contiguous()):
+            raise ValueError("entropy buffer must be contiguous float64 [E, B]")
+        out = torch.empty_like(S)
+        unc = None if H is None else torch.empty(3, E, B, dtype=torch.float64, device=S.device)
+        ptr = (lambda i: None) if unc is None else (lambda i: unc[i].data_ptr())
+        with torch.cuda.device(self.device):
+            rc = self.lib.bmi_finalize_per_image(E, B, Cd, t_used.contiguous().data_ptr(), S[0].data_ptr(), S[1].data_ptr(), S[2].data_ptr(),
+                                                 None if H is None else H.data_ptr(), out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(),
+                                                 ptr(0), ptr(1), ptr(2), self._nonfinite.data_ptr(), self._stream())
+        _lib.check(rc, "bmi_finalize_per_image")
+        r = dict(mean=out[0], var=out[1], logit_mean=out[2])
+        if unc is not None:
+            r.update(pred_entropy=unc[0], exp_entropy=unc[1], mutual_info=unc[2])
         return r
 
     def forward_once(self, x, seed=0, t=0, cnt0=0):

@@ -349,6 +349,42 @@ int bmi_forward_mcd_exit(bmi_handle h, const float* x_nchw, int32_t batch, int32
                          double threshold, int32_t first_exit, double* S1, double* S2, double* SL, int32_t* exit_of_image,
                          int32_t* active_after, void* workspace, size_t workspace_bytes, bmi_stream stream);
 
+/* Adaptive (sequential) Monte-Carlo sampling with a per-image stopping rule, on the folded path.  The prefix runs once; samples
+ * then run in steps of t_step (<= the planned chunk) up to t_max.  After each step the stop rule is tested at exit test_exit on
+ * the running sums of every still-active image; images that pass retire with t_used[b] = the samples they got, and later steps
+ * cover only the images still active: compact grids, original tensor rows, original mask element indices — so every sample keeps
+ * its global index t (Philox counter, Masksembles row (mask_cnt0 + t) mod M) and image b's sums are those of bmi_forward_mcd
+ * truncated at t_used[b].  A step in which no image has retired yet runs exactly bmi_forward_mcd's kernels.
+ * Rules, float64, with t = samples so far, m = S1/t, v = max(S2/t - m^2, 0), both at test_exit:
+ *   BMI_STOP_SEM    (0): stat = max_c sqrt(v_c / t);                                          stop when stat <= threshold
+ *   BMI_STOP_MARGIN (1): c1 = argmax m (lowest index on ties), c2 = argmax over c != c1;
+ *                        stat = (m_c1 - m_c2) / sqrt((v_c1 + v_c2) / t), +inf when the denominator is 0 and the margin > 0,
+ *                        0 when both are 0;                                                    stop when stat >= threshold
+ * S1 / S2 / SL [E][batch][C] (and SH [E][batch] when not NULL: per-sample entropies as in bmi_forward_mcd_entropy) must be ZERO on
+ * entry; on return every exit's rows of image b hold exactly its first t_used[b] samples.  t_used (device int32 [batch]) is
+ * required; converged (device uint8 [batch], NULL: not written) = whether the rule holds at t_used[b] (an image at t_max may or may
+ * not pass).  active_after_step (host, [ceil(t_max / t_step)]) = images still active after each step (0 after the last step that
+ * ran).  image_offset as in bmi_forward_mcd_images.  Synchronises the stream once per step (the host sizes the next step's
+ * grids), so it cannot be graph-captured.  A first MC site that is lazy in the full run is materialised in steps that carry a row
+ * table.  BMI_ERR_INVALID: a NULL required pointer, batch / t_max < 1, t_step < 1, mask_cnt0 < 0, an unknown rule, test_exit
+ * outside [0, E), batch > max_batch; BMI_ERR_UNSUPPORTED: t_step > the planned chunk, the exact engine (BMI_DTYPE_F32), keep-bit
+ * consumers (BMI_MASK_BITS=1) in the suffix. */
+#define BMI_STOP_SEM 0
+#define BMI_STOP_MARGIN 1
+int bmi_forward_mcd_adaptive(bmi_handle h, const float* x_nchw, int32_t batch, int32_t image_offset, int32_t t_max,
+                             int32_t t_step, uint64_t seed, int32_t mask_cnt0, int32_t rule, double threshold,
+                             int32_t test_exit, double* S1, double* S2, double* SL, double* SH, int32_t* t_used,
+                             uint8_t* converged, int32_t* active_after_step, void* workspace, size_t workspace_bytes,
+                             bmi_stream stream);
+
+/* bmi_finalize_checked and bmi_finalize_uncertainty with a per-image sample count t_used[b] (device int32 [batch], every entry >= 1)
+ * in place of t_total: mean / var / logit_mean [E][batch][C]; pred_entropy / exp_entropy / mutual_info [E][batch] when SH and
+ * the three outputs are all non-NULL (all NULL: skipped).  nonfinite (NULL: not counted) as in bmi_finalize_checked. */
+int bmi_finalize_per_image(int32_t n_exits, int32_t batch, int32_t out_dim, const int32_t* t_used, const double* S1,
+                           const double* S2, const double* SL, const double* SH, double* mean, double* var,
+                           double* logit_mean, double* pred_entropy, double* exp_entropy, double* mutual_info,
+                           int32_t* nonfinite, bmi_stream stream);
+
 /* mean = S1/T, var = S2/T - mean^2 (clamped at 0), logit_mean = SL/T; n = E*B*C. */
 int bmi_finalize(int64_t n, int32_t t_total, const double* S1, const double* S2, const double* SL, double* mean,
                  double* var, double* logit_mean, bmi_stream stream);

@@ -1,0 +1,144 @@
+"""Fixed-T against adaptive Monte-Carlo sampling on the headline workload (ResNet-18 multi-exit, block + exit MC dropout, B = 250):
+``predict(T=100)`` against ``predict_adaptive(T_max=100)`` at a few SEM thresholds, on the synthetic bench model and on its trained-like twin
+(every classifier x 24, as bench.py's tolerance leg builds it), same process, alternating.  Prints one JSON line per measurement:
+median wall time per batch, mean t_used, active_after_step and the largest |mean - mean at T = 100| over every exit, image and class.
+Also: the cost of steps with no retirement against the same samples inside bmi_forward_mcd, a t_step sweep, and the device time of the
+first site's MASK launches with and without a row table (bmi_profile_launches).
+
+    python tools/adaptive_bench.py [--reps 5] [--quantiles 0.25,0.5,0.75] [--t-steps 10,20,25,50] [--dtype f16]
+
+The thresholds are the given quantiles of every image's SEM statistic after the first step (t = t_step) at the last exit, per model: a
+fixed threshold that suits one set of weights retires nobody on the other.
+"""
+import argparse
+import copy
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from bayesnn_fpga_amd.models.resnet18.resnet18 import ResNet18MCEarlyExit  # noqa: E402
+from bayesnn_fpga_amd.synthetic import synthetic_images, synthetic_weights_  # noqa: E402
+
+HEAD_NAMES = ("ex1linear", "ex2linear", "ex3linear", "linear")
+KW = dict(dropout_exit=True, dropout="block", dropout_p=0.25, out_dim=10)
+
+
+def timed(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    r = fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3, r
+
+
+def mask_split(eng, fn, full_images):
+    """Device ms and image-samples of the MASK-slot launches of one call, split into full-grid launches and row-table launches."""
+    eng.profile(True)
+    try:
+        eng.profile_read()
+        fn()
+        torch.cuda.synchronize()
+        eng.profile_read()
+        launches = eng.profile_launches()
+    finally:
+        eng.profile(False)
+    out = {"full": [0.0, 0], "rows": [0.0, 0]}
+    for l in launches:
+        if l["kind"] != "mask":
+            continue
+        k = "full" if l["images"] == full_images else "rows"
+        out[k][0] += l["ms"]
+        out[k][1] += l["images"]
+    return {k: dict(ms=round(v[0], 4), images=v[1], us_per_1k_images=round(1e3 * v[0] / max(v[1], 1) * 1e3, 3)) for k, v in out.items()}
+
+
+def leg(name, model, dev, x, a):
+    B, T = x.shape[0], a.T
+    eng = model.engine(dev, max_batch=B, dtype=a.dtype)
+    t_step = min(a.t_step, eng.chunk_samples)
+    S = eng.new_moments(B)
+    eng.accumulate(x, S, 0, t_step, a.seed)
+    m = S[0, -1] / t_step
+    sem = ((S[1, -1] / t_step - m * m).clamp_min(0) / t_step).sqrt().max(-1).values
+    thresholds = [float(torch.quantile(sem, float(q))) for q in a.quantiles.split(",")]
+    ref = eng.predict(x, T, seed=a.seed)["mean"]
+    for _ in range(2):                                               # warm-up of every path
+        eng.predict(x, T, seed=a.seed)
+        for thr in thresholds:
+            eng.predict_adaptive(x, T, thr, t_step=t_step, seed=a.seed)
+    times = {"fixed": []}
+    res = {}
+    for _ in range(a.reps):                                          # alternating, same process
+        times["fixed"].append(timed(lambda: eng.predict(x, T, seed=a.seed))[0])
+        for thr in thresholds:
+            ms, r = timed(lambda: eng.predict_adaptive(x, T, thr, t_step=t_step, seed=a.seed))
+            times.setdefault(thr, []).append(ms)
+            res[thr] = r
+    fixed = float(np.median(times["fixed"]))
+    print(json.dumps(dict(model=name, what="fixed", T=T, B=B, dtype=a.dtype, ms=round(fixed, 3))))
+    for thr in thresholds:
+        r = res[thr]
+        ms = float(np.median(times[thr]))
+        print(json.dumps(dict(model=name, what="adaptive", rule="sem", threshold=thr, t_step=t_step, ms=round(ms, 3),
+                              vs_fixed=round(ms / fixed, 3), mean_t_used=round(float(r["t_used"].float().mean()), 2),
+                              work_fraction=round(float(r["t_used"].float().mean()) / T, 3), active_after_step=r["active_after_step"],
+                              max_abs_dmean_vs_T_tested_exit=float((r["mean"][-1] - ref[-1]).abs().max()),
+                              max_abs_dmean_vs_T_any_exit=float((r["mean"] - ref).abs().max()))))
+    # steps with no retirement (threshold -1: the SEM is never <= -1) against the same samples inside bmi_forward_mcd
+    for steps in (1, T // t_step):
+        Tn = steps * t_step
+        tf, ta = [], []
+        for _ in range(a.reps):
+            tf.append(timed(lambda: eng.predict(x, Tn, seed=a.seed))[0])
+            ta.append(timed(lambda: eng.predict_adaptive(x, Tn, -1.0, t_step=t_step, seed=a.seed))[0])
+        print(json.dumps(dict(model=name, what="no_retirement", steps=steps, samples=Tn, fixed_ms=round(float(np.median(tf)), 3),
+                              adaptive_ms=round(float(np.median(ta)), 3),
+                              per_step_overhead_ms=round((float(np.median(ta)) - float(np.median(tf))) / steps, 3))))
+    return eng, t_step, thresholds
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=250)
+    ap.add_argument("--T", type=int, default=100)
+    ap.add_argument("--t-step", type=int, default=25)
+    ap.add_argument("--t-steps", default="10,20,25,50")
+    ap.add_argument("--quantiles", default="0.25,0.5,0.75")
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--seed", type=int, default=3)
+    ap.add_argument("--dtype", default="f16")
+    a = ap.parse_args()
+    dev = torch.device("cuda:0")
+    torch.manual_seed(0)
+    model = synthetic_weights_(ResNet18MCEarlyExit(**KW), 0).to(dev).eval()
+    x = synthetic_images(a.batch, seed=1234).to(dev)
+    twin = copy.deepcopy(model)
+    with torch.no_grad():
+        for n in HEAD_NAMES:
+            getattr(twin, n).weight.mul_(24.0)
+    twin.invalidate_engine()
+    for name, m in (("synthetic", model), ("trained_like_twin", twin)):
+        eng, t_step, thresholds = leg(name, m, dev, x, a)
+        if name == "synthetic":
+            thr = thresholds[len(thresholds) // 2]
+            print(json.dumps(dict(model=name, what="mask_launches", threshold=thr, t_step=t_step,
+                                  **mask_split(eng, lambda: eng.predict_adaptive(x, a.T, thr, t_step=t_step, seed=a.seed), a.batch * t_step))))
+            for ts in (int(v) for v in a.t_steps.split(",")):
+                ts = min(ts, eng.chunk_samples)
+                ms = []
+                for _ in range(a.reps):
+                    t, r = timed(lambda: eng.predict_adaptive(x, a.T, thr, t_step=ts, seed=a.seed))
+                    ms.append(t)
+                print(json.dumps(dict(model=name, what="t_step_sweep", threshold=thr, t_step=ts, ms=round(float(np.median(ms)), 3),
+                                      mean_t_used=round(float(r["t_used"].float().mean()), 2), active_after_step=r["active_after_step"])))
+        m.invalidate_engine()
+
+
+if __name__ == "__main__":
+    main()
