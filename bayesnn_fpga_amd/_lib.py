@@ -17,6 +17,12 @@ DTYPES = {"f16": DTYPE_F16, "bf16": DTYPE_BF16, "f32": DTYPE_F32, "f16x2": DTYPE
 FP32_ACT_DTYPES = ("f32", "f16x2", "bf16x3")      # engines that keep fp32 activations in the workspace
 OP_STEM, OP_CONV, OP_MASK, OP_HEAD, OP_MAXPOOL, OP_DENSE = 1, 2, 3, 4, 5, 6
 STOP_RULES = {"sem": 0, "margin": 1}      # BMI_STOP_* of bmi_forward_mcd_adaptive
+EXIT_RULES = {"confidence": 0, "margin": 1}      # BMI_EXIT_* of bmi_forward_mcd_exit_staged
+
+
+class ExitRule(C.Structure):
+    _fields_ = [("criterion", C.c_int32), ("ensemble", C.c_int32), ("threshold", C.c_double), ("first_exit", C.c_int32)]
+
 PROFILE_SLOTS = 8
 CONV_FAMILY_KERNELS = ("conv3x3_patch_kernel", "conv_igemm_wide_kernel", "conv_igemm_kernel", "conv3x3_pw_kernel", "conv1x1_stream_kernel",
                        "conv3x3_s2_kernel", "conv_split_kernel", "conv1x1_seam_kernel")
@@ -79,6 +85,11 @@ _PROTOS = {
     "bmi_forward_mcd_exit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_uint64, C.c_int32, C.c_double, C.c_int32,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p, C.c_size_t,
                                        C.c_void_p]),
+    "bmi_forward_mcd_exit_staged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_uint64, C.c_int32, C.POINTER(ExitRule)] +
+                                    [C.c_void_p] * 5 + [C.POINTER(C.c_int32), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "bmi_query_op_stages": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32] + [C.POINTER(C.c_int32)] * 4),
+    "bmi_query_exit_stages": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                        C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     "bmi_forward_mcd_adaptive": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_int32,
                                            C.c_int32, C.c_double, C.c_int32] + [C.c_void_p] * 6 + [C.POINTER(C.c_int32), C.c_void_p,
                                                                                                    C.c_size_t, C.c_void_p]),

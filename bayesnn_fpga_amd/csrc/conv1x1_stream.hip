@@ -264,14 +264,13 @@ bool conv_takes_stream_kernel(int ksize, int stride, int pad, int cin, int cout)
     return ksize == 1 && pad == 0 && (stride == 1 || stride == 2) && cin % 64 == 0 && cin <= STREAM_MAX_CIN && cout % SBC == 0;
 }
 
-// BMI_ERR_UNSUPPORTED -> the caller goes on to conv_igemm_wide / conv_igemm.
-int launch_conv1x1_stream(const ConvArgs& a_in, hipStream_t s) {
-    if (!opt_conv_stream() || a_in.wgt_b || a_in.in2 || a_in.imap || (a_in.in_bits && a_in.lazy_planar)) return BMI_ERR_UNSUPPORTED;
+// Whether this kernel takes the launch `a_in` (row tables aside): BMI_OK with its epilogue kind and pixel tile, else the launcher's code.
+static int stream_select(const ConvArgs& a_in, int* epi_out, int* sbp_out) {
+    if (!opt_conv_stream() || a_in.wgt_b || a_in.in2 || (a_in.in_bits && a_in.lazy_planar)) return BMI_ERR_UNSUPPORTED;
     if (a_in.in_bits && (a_in.out_mul != 1.f || (size_t)a_in.N * a_in.H * a_in.W * (a_in.Cin >> 3) >= 0x7fffffffull)) return BMI_ERR_UNSUPPORTED;
     if (!conv_takes_stream_kernel(a_in.ksize, a_in.stride, a_in.pad, a_in.Cin, a_in.Cout)) return BMI_ERR_UNSUPPORTED;
     if (a_in.N <= 0 || a_in.M <= 0 || a_in.in_mod <= 0 || a_in.B <= 0 || (a_in.res && a_in.res_mod <= 0)) return BMI_ERR_INVALID;
-    ConvArgs a = a_in;
-    a.xcd_split = xcd_split_for(a.Cout / SBC, (size_t)a.Cout * a.Cin * 2);
+    const ConvArgs& a = a_in;
     const int SBP = (opt_conv_stream() == 3 && !a_in.in_bits) ? 256 : 128;   // 3: the 256-pixel tile (A/B)
     const long tiles = (((long)a.M + SBP - 1) / SBP) * (a.Cout / SBC);
     if (tiles > 0x7fffffffL) return BMI_ERR_INVALID;
@@ -294,6 +293,25 @@ int launch_conv1x1_stream(const ConvArgs& a_in, hipStream_t s) {
     // Where the wide kernel cannot go (Cout % 256 != 0: the 256 -> 128 / 64 -> 128 reduce and downsample convs) the alternative is the
     // per-tap conv_igemm, and this kernel wins plain launches too: 256 -> 128 on 32x32 2723 -> 2310 us, 64 -> 128 stride 2 455 -> 312 us.
     if (epi == BMI_EPI_PLAIN && a.Cout % 256 == 0 && opt_conv_stream() != 2 && !a.in_bits) return BMI_ERR_UNSUPPORTED;   // (keep bits: the wide kernel has no place to apply them)
+    *epi_out = epi;
+    *sbp_out = SBP;
+    return BMI_OK;
+}
+
+bool conv1x1_stream_takes(const ConvArgs& a) {
+    int epi = 0, sbp = 0;
+    return stream_select(a, &epi, &sbp) == BMI_OK;
+}
+
+// BMI_ERR_UNSUPPORTED -> the caller goes on to conv_igemm_wide / conv_igemm.  No row-table form: a launch with one is declined.
+int launch_conv1x1_stream(const ConvArgs& a_in, hipStream_t s) {
+    if (a_in.imap) return BMI_ERR_UNSUPPORTED;
+    int epi = 0, SBP = 0;
+    const int rc = stream_select(a_in, &epi, &SBP);
+    if (rc != BMI_OK) return rc;
+    ConvArgs a = a_in;
+    a.xcd_split = xcd_split_for(a.Cout / SBC, (size_t)a.Cout * a.Cin * 2);
+    const long tiles = (((long)a.M + SBP - 1) / SBP) * (a.Cout / SBC);
     // keep bits on a deterministic input: the samples of one activation tile back to back on one XCD (lazy_tile_map)
     a.lazy_order = a.in_bits && opt_lazy_order() && a.N % a.in_mod == 0 && (a.Ho * a.Wo) % SBP == 0 && a.in_mod < a.N;
     const dim3 grid((unsigned)(a.lazy_order ? lazy_tile_grid(tiles) : tiles)), block(256);

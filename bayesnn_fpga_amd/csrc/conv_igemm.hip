@@ -299,7 +299,8 @@ static int launch_cfg(const ConvArgs& a_in, hipStream_t s) {
 }
 
 // out = fp16(relu?(bn(sum over the splits, in split order))): the plain epilogue's arithmetic on the added partial sums.
-template <bool BF>
+// IMAP (early exit by stages): the partial sums are those of the launch's compact pixels; the result goes to the tensor row a.imap[n].
+template <bool BF, bool IMAP = false>
 __global__ __launch_bounds__(256) void splitk_finish_kernel(ConvArgs a) {
     const long total = (long)a.M * (a.Cout >> 2);
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
@@ -319,7 +320,12 @@ __global__ __launch_bounds__(256) void splitk_finish_kernel(ConvArgs a) {
             if (a.relu) x = fmaxf(x, 0.f);
             o[e] = a16_from_f32<BF>(x);
         }
-        *(half4*)(a.out + (size_t)m * a.Cout + c4) = o;
+        size_t mo = (size_t)m;
+        if constexpr (IMAP) {
+            const int HoWo = a.Ho * a.Wo, n = (int)(m / HoWo);
+            mo = (size_t)map_image<true>(a, n) * HoWo + (size_t)(m - (long)n * HoWo);
+        }
+        *(half4*)(a.out + mo * a.Cout + c4) = o;
     }
 }
 
@@ -328,7 +334,10 @@ int launch_splitk_finish(const ConvArgs& a, hipStream_t s) {
     const long total = (long)a.M * (a.Cout >> 2);
     long blocks = (total + 255) / 256;
     if (blocks > 256 * 8) blocks = 256 * 8;
-    if (a.bf16) hipLaunchKernelGGL(splitk_finish_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, a);
+    if (a.imap) {
+        if (a.bf16) hipLaunchKernelGGL((splitk_finish_kernel<true, true>), dim3((unsigned)blocks), dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((splitk_finish_kernel<false, true>), dim3((unsigned)blocks), dim3(256), 0, s, a);
+    } else if (a.bf16) hipLaunchKernelGGL(splitk_finish_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, a);
     else hipLaunchKernelGGL(splitk_finish_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, a);
     BMI_CHECK_LAUNCH();
     return BMI_OK;
@@ -341,12 +350,17 @@ int launch_conv_igemm(const ConvArgs& a, hipStream_t s) {
     if ((size_t)a.H * a.W * a.Cin >= 0x7fffffffull) return BMI_ERR_UNSUPPORTED;   // 31-bit in-image element offsets
     static const int big = [] { const char* v = std::getenv("BMI_IGEMM_BP256"); return v ? std::atoi(v) : 1; }();
     if (a.partial) {   // split-K: 128 x 128 tiles, nsplit workgroups per tile, then the finishing pass
-        if (a.nsplit < 2 || a.nsplit > a.ksize * a.ksize * (a.Cin / BK) || !conv_epilogue_is_plain(a) || a.Cout % 128 != 0 || a.in_bits || a.imap)
+        if (a.nsplit < 2 || a.nsplit > a.ksize * a.ksize * (a.Cin / BK) || !conv_epilogue_is_plain(a) || a.Cout % 128 != 0 || a.in_bits)
             return BMI_ERR_INVALID;
         const long tiles = (((long)a.M + 127) / 128) * (a.Cout / 128);
         if (tiles > 0x7fffffffL) return BMI_ERR_INVALID;
         const dim3 grid((unsigned)tiles, (unsigned)a.nsplit), block(256);
-        if (a.bf16) hipLaunchKernelGGL((conv_igemm_kernel<128, 128, 2, 2, true, false, true, true, false, true>), grid, block, 0, s, a);
+        // (a row table: the same K ranges and the same per-range partial sums for the launch's compact pixels; the finishing pass writes
+        //  through the table)
+        if (a.imap) {
+            if (a.bf16) hipLaunchKernelGGL((conv_igemm_kernel<128, 128, 2, 2, true, false, true, true, true, true>), grid, block, 0, s, a);
+            else hipLaunchKernelGGL((conv_igemm_kernel<128, 128, 2, 2, true, false, true, false, true, true>), grid, block, 0, s, a);
+        } else if (a.bf16) hipLaunchKernelGGL((conv_igemm_kernel<128, 128, 2, 2, true, false, true, true, false, true>), grid, block, 0, s, a);
         else hipLaunchKernelGGL((conv_igemm_kernel<128, 128, 2, 2, true, false, true, false, false, true>), grid, block, 0, s, a);
         BMI_CHECK_LAUNCH();
         return launch_splitk_finish(a, s);

@@ -535,7 +535,8 @@ __global__ __launch_bounds__(512) void conv_split_kernel(ConvArgs a) {
 }
 
 // out (pair32) = encode(relu?(bn(sum over the splits, in split order))): conv_split's epilogue arithmetic on the added partial sums
-template <bool BF>
+// IMAP (early exit by stages): the partial sums are those of the launch's compact pixels; the result goes to the tensor row a.imap[n].
+template <bool BF, bool IMAP = false>
 __global__ __launch_bounds__(256) void splitk_finish_pair_kernel(ConvArgs a) {
     const long total = (long)a.M * (a.Cout >> 3);
     const int HoWo = a.Ho * a.Wo;
@@ -556,7 +557,12 @@ __global__ __launch_bounds__(256) void splitk_finish_pair_kernel(ConvArgs a) {
         epilogue_quad_f32sb(a, a.scale, a.bias, p, zero, false, va, c8);
         epilogue_quad_f32sb(a, a.scale, a.bias, p, zero, false, vb, c8 + 4);
         const float v8[8] = {va[0], va[1], va[2], va[3], vb[0], vb[1], vb[2], vb[3]};
-        pair_encode<BF, 8>(a.out + pair32_off((size_t)m, a.Cout, c8), v8);
+        size_t mo = (size_t)m;
+        if constexpr (IMAP) {
+            const int n = (int)(m / HoWo);
+            mo = (size_t)map_image<true>(a, n) * HoWo + (size_t)(m - (long)n * HoWo);
+        }
+        pair_encode<BF, 8>(a.out + pair32_off(mo, a.Cout, c8), v8);
     }
     (void)HoWo;
 }
@@ -600,7 +606,8 @@ static int launch_split_t(const ConvArgs& a, hipStream_t s) {
         const long total = (long)a.M * (a.Cout >> 3);
         long fb = (total + 255) / 256;
         if (fb > 256 * 8) fb = 256 * 8;
-        hipLaunchKernelGGL(splitk_finish_pair_kernel<BF>, dim3((unsigned)fb), dim3(256), 0, s, a);
+        if (a.imap) hipLaunchKernelGGL((splitk_finish_pair_kernel<BF, true>), dim3((unsigned)fb), dim3(256), 0, s, a);
+        else hipLaunchKernelGGL(splitk_finish_pair_kernel<BF>, dim3((unsigned)fb), dim3(256), 0, s, a);
         BMI_CHECK_LAUNCH();
     }
     return BMI_OK;
@@ -611,7 +618,7 @@ bool conv_takes_split_kernel(int cin, int cout) { return cin % 32 == 0 && cout %
 // a.in / a.res / a.out: pair32 tensors (conv_epilogue.h); a.wgt: 16-bit [2][Cout][k*k*Cin] head / tail planes
 int launch_conv_split(const ConvArgs& a, int bf16, hipStream_t s) {
     if (!conv_takes_split_kernel(a.Cin, a.Cout)) return BMI_ERR_UNSUPPORTED;
-    if (a.in_bits || a.in2_bits || a.pool || a.pool_b || (a.imap && a.partial)) return BMI_ERR_UNSUPPORTED;
+    if (a.in_bits || a.in2_bits || a.pool || a.pool_b) return BMI_ERR_UNSUPPORTED;
     // fused 1x1 shortcut: in2 a pair32 tensor of Cin2 channels read at stride2 (no padding), wgt2 the planes [2][Cout][Cin2]
     if (a.in2 && (!a.wgt2 || a.wgt_b || a.Cin2 % 32 != 0 || a.Cin2 <= 0 || a.stride2 < 1 || a.in2_mod <= 0 || (a.Ho - 1) * a.stride2 >= a.H2 ||
                   (a.Wo - 1) * a.stride2 >= a.W2))

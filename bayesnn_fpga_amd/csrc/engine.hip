@@ -40,6 +40,7 @@ struct TensorInfo {
     EltArgs lazy_call;          // (run time) the mask launch that materialises it on demand
     int first = -1, last = -1;  // suffix op indices (stochastic tensors only)
     size_t offset = 0;          // byte offset in the workspace
+    size_t bytes = 0;           // (bmi_plan) its workspace range (stochastic tensors)
 };
 
 #define OP_MASKBITS 100   // internal: a MASK op rewritten to emit keep bits for its conv_igemm consumers
@@ -60,6 +61,8 @@ struct OpInfo {
     bool has_seam = false;  // CONV (1x1 expand + residual + ReLU of a Bottleneck): the NEXT op, a plain 1x1 conv that reads this conv's output (conv1 of the
     bmi_op_desc seam_d;     // following Bottleneck), rides in this launch when conv1x1_seam takes it (else the two launches, in order)
     int seam_cout = 0;
+    int64_t macs = 0;       // MACs per image (per sample in the suffix), a pair / seam partner's included
+    int xstage = 0;         // (bmi_plan) the smallest exit index of any head downstream of this op's outputs (staged early exit)
 };
 
 struct ProfRec {
@@ -94,6 +97,7 @@ struct bmi_engine_s {
     size_t splitk_off = 0;               // fp32 partial sums of the split-K prefix convs
     size_t head_off = 0, head_part_bytes = 0;   // float64 partial sums of a head launch's 32-sample groups (joined in group order), one region per exit
     std::vector<std::pair<const float*, size_t>> perm;   // (bmi_plan) Masksembles tables (device pointer of the site) -> workspace offset of the permuted copy
+    std::vector<char> staged_ok;         // (bmi_plan) per first_exit: the staged suffix order keeps every shared workspace range's live ranges apart
     // profiling
     bool profiling = false;
     double fam_ms[BMI_CONV_FAMILIES] = {0}, fam_flops[BMI_CONV_FAMILIES] = {0}, fam_bytes[BMI_CONV_FAMILIES] = {0};
@@ -246,6 +250,91 @@ int xcd_split_for(int n_ctiles, size_t weight_bytes) {
     return cs;
 }
 
+// Staged early exit (bmi_forward_mcd_exit_staged).  The stage of an op is the smallest exit index of any head downstream of its outputs,
+// transitively; a tensor no head reads counts as the last exit's.  If op A feeds op B, every head downstream of B is also downstream of
+// A, so stage(A) <= stage(B): a stable sort by stage keeps the engine's topological order.  A pair- or seam-fused op takes the smaller
+// stage of its two members (the walk takes the minimum over both outputs) and runs whole there: splitting it would change the kernel
+// family and so the bits.
+int op_stage(const OpInfo& op, int first_exit) { return std::max(0, op.xstage - first_exit); }
+
+// A prefix op behind a decision runs on the active images through a row table where its full-run kernel has that form; otherwise it
+// runs over the whole batch (never in another kernel family: that would change the bits).  Decided under the options of the call.
+// No row table: the stem, and the 1x1 convs that conv1x1_stream takes at the planned batch.
+bool prefix_row_form(const bmi_engine_s* h, const OpInfo& op) {
+    const bmi_op_desc& d = op.d;
+    if (d.kind == BMI_OP_STEM) return false;
+    if (d.kind != BMI_OP_CONV || h->f32 || d.ksize != 1 || op.has_pair || op.nsplit > 1 || d.in2 >= 0) return true;
+    const TensorInfo& tin = h->tensors[d.in];
+    ConvArgs a;          // the selection-relevant arguments of run_op's full-run launch (the pointers only need to be present)
+    std::memset(&a, 0, sizeof(a));
+    a.bf16 = h->bf16;
+    a.N = a.n_ref = a.B = a.in_mod = h->max_batch;
+    a.H = tin.h; a.W = tin.w; a.Cin = tin.c;
+    a.Ho = op.ho; a.Wo = op.wo; a.Cout = op.cout;
+    a.ksize = d.ksize; a.stride = d.stride; a.pad = d.pad; a.relu = d.relu;
+    a.M = a.N * op.ho * op.wo;
+    a.scale = d.scale; a.bias = d.bias;
+    a.out_mul = op.out_mul;
+    a.site = resolve_site(nullptr, 0, 0, 0);
+    if (d.residual >= 0) { a.res = (const _Float16*)(uintptr_t)256; a.res_mod = h->max_batch; }
+    return !conv1x1_stream_takes(a);
+}
+
+void plan_exit_stages(bmi_engine_s* h) {
+    const int E = h->n_exits;
+    std::vector<int> tmin(h->tensors.size(), E - 1);
+    for (std::vector<OpInfo>* ops : {&h->suffix, &h->prefix})
+        for (size_t i = ops->size(); i-- > 0;) {
+            OpInfo& op = (*ops)[i];
+            const bmi_op_desc& d = op.d;
+            int st = d.kind == BMI_OP_HEAD ? d.out : tmin[d.out];
+            if (op.has_pair) st = std::min(st, tmin[op.pair_d.out]);
+            if (op.has_seam) st = std::min(st, tmin[op.seam_d.out]);
+            op.xstage = st;
+            auto feed = [&](int id) { if (id >= 0) tmin[id] = std::min(tmin[id], st); };
+            feed(d.in);
+            if (d.kind == BMI_OP_CONV) { feed(d.residual); feed(d.in2); }
+            feed(op.bits_tensor);
+        }
+    // The suffix tensors share workspace ranges by live range in the engine's order: per first_exit, the staged order must keep
+    // every two tensors that share bytes live at disjoint times (where the engine's order does)
+    const int n = (int)h->suffix.size(), nt = (int)h->tensors.size();
+    h->staged_ok.assign(E, 0);
+    for (int fe = 0; fe < E; ++fe) {
+        std::vector<int> order(n);
+        for (int k = 0; k < n; ++k) order[k] = k;
+        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return op_stage(h->suffix[a], fe) < op_stage(h->suffix[b], fe); });
+        std::vector<int> first(nt, -1), last(nt, -1);
+        for (int k = 0; k < n; ++k) {
+            const OpInfo& op = h->suffix[order[k]];
+            const bmi_op_desc& d = op.d;
+            auto touch = [&](int id) {
+                if (id < 0 || !h->tensors[id].stoch) return;
+                if (first[id] < 0) first[id] = k;
+                last[id] = k;
+            };
+            touch(d.in);
+            if (d.kind == BMI_OP_CONV) { touch(d.in2); touch(d.residual); }
+            touch(op.bits_tensor);
+            if (d.kind != BMI_OP_HEAD) touch(d.out);
+            if (op.has_pair) touch(op.pair_d.out);
+            if (op.has_seam) touch(op.seam_d.out);
+        }
+        for (int id = 0; id < nt; ++id)
+            if (h->tensors[id].lazy_bits >= 0) { first[h->tensors[id].lazy_bits] = first[id]; last[h->tensors[id].lazy_bits] = last[id]; }
+        bool ok = true;
+        for (int a = 1; a < nt && ok; ++a)
+            for (int b = a + 1; b < nt && ok; ++b) {
+                const TensorInfo &ta = h->tensors[a], &tb = h->tensors[b];
+                if (!ta.stoch || !tb.stoch || ta.first < 0 || tb.first < 0 || ta.bytes == 0 || tb.bytes == 0) continue;
+                if (ta.offset >= tb.offset + tb.bytes || tb.offset >= ta.offset + ta.bytes) continue;   // no shared bytes
+                if (!(ta.last < tb.first || tb.last < ta.first)) continue;                              // (shared by design in the engine's order)
+                ok = last[a] < first[b] || last[b] < first[a];
+            }
+        h->staged_ok[fe] = ok;
+    }
+}
+
 extern "C" {
 
 int bmi_version(void) { return BMI_VERSION; }
@@ -354,6 +443,7 @@ int bmi_create(const bmi_model_desc* desc, bmi_handle* out) {
                     conv.d.bias_post = nullptr;
                     if (inner) conv.d.relu = 0;   // the prefix keeps conv*scale+bias; mask, BN shift and ReLU follow in the MASK op
                     conv.stoch = false;
+                    conv.macs = macs;
                     e->prefix.push_back(conv);
                     e->prefix_macs += macs;
                     OpInfo m;
@@ -372,6 +462,7 @@ int bmi_create(const bmi_model_desc* desc, bmi_handle* out) {
                 } else {
                     op.stoch = in_st || d.site.kind != BMI_SITE_NONE;
                     e->tensors[d.out].stoch = op.stoch;
+                    op.macs = macs;
                     (op.stoch ? e->suffix : e->prefix).push_back(op);
                     (op.stoch ? e->suffix_macs : e->prefix_macs) += macs;
                 }
@@ -422,6 +513,7 @@ int bmi_create(const bmi_model_desc* desc, bmi_handle* out) {
                 e->tensors[d.out].stoch = op.stoch;
                 e->tensors[d.out].f32 = true;
                 e->tensors[d.out].dense_out = true;
+                op.macs = (int64_t)tin.c * to.c;
                 (op.stoch ? e->suffix : e->prefix).push_back(op);
                 (op.stoch ? e->suffix_macs : e->prefix_macs) += (int64_t)tin.c * to.c;
                 written[d.out] = 1;
@@ -438,6 +530,7 @@ int bmi_create(const bmi_model_desc* desc, bmi_handle* out) {
                 exit_seen[d.out] = 1;
                 op.stoch = true;  // heads always run per sample (they emit per-sample softmax)
                 op.cout = desc->out_dim;
+                op.macs = (int64_t)tin.c * desc->out_dim;
                 e->suffix.push_back(op);
                 e->suffix_macs += (int64_t)tin.c * desc->out_dim;
                 break;
@@ -518,6 +611,7 @@ int bmi_create(const bmi_model_desc* desc, bmi_handle* out) {
                     ops[i].has_pair = true;
                     ops[i].pair_d = Bo.d;
                     ops[i].pair_cout = Bo.cout;
+                    ops[i].macs += Bo.macs;
                     ops.erase(ops.begin() + (long)j);
                     break;
                 }
@@ -543,6 +637,7 @@ int bmi_create(const bmi_model_desc* desc, bmi_handle* out) {
         A.has_seam = true;
         A.seam_d = Bo.d;
         A.seam_cout = Bo.cout;
+        A.macs += Bo.macs;
         e->suffix.erase(e->suffix.begin() + (long)i + 1);
     }
     // ReLU + global average pool fused into the producing conv: a plain 3x3 stride-2 conv whose 4x4 output map feeds ONE exit head and
@@ -716,6 +811,7 @@ int bmi_plan(bmi_handle h, int32_t max_batch, int32_t chunk_samples, size_t* wor
             pos = std::max(pos, b.off + b.size);
         }
         t.offset = st_base + pos;
+        t.bytes = size;
         live.push_back({pos, size, t.last});
         st_peak = std::max(st_peak, pos + size);
     }
@@ -789,6 +885,7 @@ int bmi_plan(bmi_handle h, int32_t max_batch, int32_t chunk_samples, size_t* wor
             if (opt_conv_s2() == 0) t.lazy_planar_plan = false;
         }
     }
+    plan_exit_stages(h);
     *workspace_bytes = off;
     return BMI_OK;
 }
@@ -812,6 +909,63 @@ int bmi_query(bmi_handle h, int64_t* prefix_macs, int64_t* suffix_macs, int32_t*
     if (suffix_macs) *suffix_macs = h->suffix_macs;
     if (n_prefix_ops) *n_prefix_ops = (int32_t)h->prefix.size();
     if (n_suffix_ops) *n_suffix_ops = (int32_t)h->suffix.size();
+    return BMI_OK;
+}
+
+int bmi_query_op_stages(bmi_handle h, int32_t first_exit, int32_t capacity, int32_t* count, int32_t* out, int32_t* stage, int32_t* whole_batch) {
+    if (!h || !count || capacity < 0 || h->max_batch == 0 || first_exit < 0 || first_exit >= h->n_exits) return BMI_ERR_INVALID;
+    BmiOptionScope opt_scope(&h->opts);
+    int n = 0;
+    for (const std::vector<OpInfo>* ops : {&h->prefix, &h->suffix})
+        for (const OpInfo& op : *ops) {
+            if (op.d.kind == OP_MASKBITS) continue;
+            const int k = op_stage(op, first_exit);
+            const int wb = (ops == &h->prefix && k > 0 && !prefix_row_form(h, op)) ? 1 : 0;
+            const int outs[3] = {op.d.kind == BMI_OP_HEAD ? -1 - op.d.out : op.d.out, op.has_pair ? op.pair_d.out : -1, op.has_seam ? op.seam_d.out : -1};
+            for (int j = 0; j < 3; ++j) {
+                if (j > 0 && outs[j] < 0) continue;
+                if (n < capacity) {
+                    if (out) out[n] = outs[j];
+                    if (stage) stage[n] = k;
+                    if (whole_batch) whole_batch[n] = wb;
+                }
+                ++n;
+            }
+        }
+    *count = n;
+    return capacity > 0 && capacity < n ? BMI_ERR_INVALID : BMI_OK;
+}
+
+int bmi_query_exit_stages(bmi_handle h, int32_t first_exit, int32_t capacity, int32_t* n_stages, int64_t* prefix_macs, int64_t* suffix_macs,
+                          int32_t* n_ops, int64_t* whole_batch_macs, int32_t* n_whole_batch_ops) {
+    if (!h || !n_stages || capacity < 0) return BMI_ERR_INVALID;
+    if (h->max_batch == 0 || first_exit < 0 || first_exit >= h->n_exits) return BMI_ERR_INVALID;
+    BmiOptionScope opt_scope(&h->opts);
+    const int ns = h->n_exits - first_exit;
+    *n_stages = ns;
+    if (capacity == 0) return BMI_OK;
+    if (capacity < ns) return BMI_ERR_INVALID;
+    for (int k = 0; k < ns; ++k) {
+        if (prefix_macs) prefix_macs[k] = 0;
+        if (suffix_macs) suffix_macs[k] = 0;
+        if (n_ops) n_ops[k] = 0;
+        if (whole_batch_macs) whole_batch_macs[k] = 0;
+        if (n_whole_batch_ops) n_whole_batch_ops[k] = 0;
+    }
+    for (const OpInfo& op : h->prefix) {
+        const int k = op_stage(op, first_exit);
+        if (prefix_macs) prefix_macs[k] += op.macs;
+        if (n_ops) n_ops[k] += 1;
+        if (k > 0 && !prefix_row_form(h, op)) {        // behind a decision but over the whole batch
+            if (whole_batch_macs) whole_batch_macs[k] += op.macs;
+            if (n_whole_batch_ops) n_whole_batch_ops[k] += 1;
+        }
+    }
+    for (const OpInfo& op : h->suffix) {
+        const int k = op_stage(op, first_exit);
+        if (suffix_macs) suffix_macs[k] += op.macs;
+        if (n_ops) n_ops[k] += 1;
+    }
     return BMI_OK;
 }
 
@@ -1136,7 +1290,7 @@ int run_op(bmi_engine_s* e, const Pass& p, const OpInfo& op, int N, int t0, cons
                 if (rcm != BMI_OK) return rcm;
             }
             e->tensors[d.out].pooled_now = false;
-            if (op.nsplit > 1 && !op.stoch && !rows) {
+            if (op.nsplit > 1 && !op.stoch) {        // (under a row table too: conv_igemm's split-K form writes through it)
                 a.partial = (float*)(ws + e->splitk_off);
                 a.nsplit = op.nsplit;
                 prof.tag(BMI_CONV_FAMILY_IGEMM, flops, bytes);
@@ -1222,20 +1376,21 @@ int run_op(bmi_engine_s* e, const Pass& p, const OpInfo& op, int N, int t0, cons
 // every run of the paper uses, Software_Artifact/script_figs/journal_script.sh:10-63 — the suffix is nothing but the heads, each a launch of
 // mostly fixed latency; the same arithmetic per head, the same bits.  Under a row table (imap / rows / Bc as in run_op: adaptive sampling)
 // the heads run one by one.
-int run_suffix(bmi_engine_s* e, const Pass& p, int N, int t0, const int* imap = nullptr, int Bc = 0, const int* rows = nullptr) {
+// (run_suffix_ops: the same over ops op_at(0 .. n-1), a stage of bmi_forward_mcd_exit_staged)
+template <class OpAt>
+int run_suffix_ops(bmi_engine_s* e, const Pass& p, size_t n, OpAt op_at, int N, int t0, const int* imap, int Bc, const int* rows) {
     const hipStream_t s = p.stream;
-    const std::vector<OpInfo>& ops = e->suffix;
-    for (size_t i = 0; i < ops.size();) {
+    for (size_t i = 0; i < n;) {
         size_t j = i;
         if (opt_head_batch() && !imap)
-            while (j < ops.size() && j - i < BMI_HEAD_PACK_MAX && ops[j].d.kind == BMI_OP_HEAD && !e->tensors[ops[j].d.in].lazy_pending) ++j;
+            while (j < n && j - i < BMI_HEAD_PACK_MAX && op_at(j).d.kind == BMI_OP_HEAD && !e->tensors[op_at(j).d.in].lazy_pending) ++j;
         if (j - i >= 2) {
             HeadArgs list[BMI_HEAD_PACK_MAX];
-            for (size_t k = i; k < j; ++k) list[k - i] = make_head_args(e, p, ops[k], N, t0, nullptr, 0);
+            for (size_t k = i; k < j; ++k) list[k - i] = make_head_args(e, p, op_at(k), N, t0, nullptr, 0);
             int rc;
             {
                 ProfScope prof(e, BMI_OP_HEAD, s);
-                prof.r.out = ops[i].d.out; prof.r.images = N;
+                prof.r.out = op_at(i).d.out; prof.r.images = N;
                 rc = launch_head_fused_multi(list, (int)(j - i), s);
             }
             if (rc == BMI_OK) { i = j; continue; }
@@ -1245,11 +1400,16 @@ int run_suffix(bmi_engine_s* e, const Pass& p, int N, int t0, const int* imap = 
                 e->recs.pop_back();
             }
         }
-        const int rc = run_op(e, p, ops[i], N, t0, imap, Bc, rows);
+        const int rc = run_op(e, p, op_at(i), N, t0, imap, Bc, rows);
         if (rc != BMI_OK) return rc;
         ++i;
     }
     return BMI_OK;
+}
+
+int run_suffix(bmi_engine_s* e, const Pass& p, int N, int t0, const int* imap = nullptr, int Bc = 0, const int* rows = nullptr) {
+    const std::vector<OpInfo>& ops = e->suffix;
+    return run_suffix_ops(e, p, ops.size(), [&](size_t i) -> const OpInfo& { return ops[i]; }, N, t0, imap, Bc, rows);
 }
 
 // The folded path: the prefix once, then samples t_begin .. t_begin+t_count-1 through the suffix, `chunk` at a time.
@@ -1414,6 +1574,69 @@ int bmi_forward_mcd_exit(bmi_handle h, const float* x_nchw, int32_t batch, int32
         bc = n_active;
         cur ^= 1;
         rc = launch_expand_rows(imap, bc, batch, t_count, rows_dev, s);     // compact image -> tensor row, for the conv kernels
+        if (rc != BMI_OK) return rc;
+        rows = rows_dev;
+    }
+    return BMI_OK;
+}
+
+int bmi_forward_mcd_exit_staged(bmi_handle h, const float* x_nchw, int32_t batch, int32_t t_count, uint64_t seed, int32_t mask_cnt0,
+                                const bmi_exit_rule* rule, double* S1, double* S2, double* SL, double* SH, int32_t* exit_of_image,
+                                int32_t* active_after, void* workspace, size_t workspace_bytes, bmi_stream stream) {
+    if (!h || !x_nchw || !rule || !S1 || !S2 || !SL || !workspace || !exit_of_image || !active_after) return BMI_ERR_INVALID;
+    BmiOptionScope opt_scope(&h->opts);
+    if (rule->criterion != BMI_EXIT_CONFIDENCE && rule->criterion != BMI_EXIT_MARGIN) return BMI_ERR_INVALID;
+    if ((rule->ensemble != 0 && rule->ensemble != 1) || rule->threshold != rule->threshold) return BMI_ERR_INVALID;
+    if (rule->first_exit < 0 || rule->first_exit >= h->n_exits) return BMI_ERR_INVALID;
+    if (batch < 1 || t_count < 1 || mask_cnt0 < 0) return BMI_ERR_INVALID;
+    if (h->max_batch == 0 || batch > h->max_batch) return BMI_ERR_INVALID;
+    if (t_count > h->chunk || (h->f32 && !h->split)) return BMI_ERR_UNSUPPORTED;     // a decision needs ALL samples of its stage in the workspace
+    const int fe = rule->first_exit, last = h->n_exits - 1;
+    for (const OpInfo& op : h->suffix)
+        if (op.d.kind == OP_MASKBITS && op_stage(op, fe) > 0) return BMI_ERR_UNSUPPORTED;     // (its conv_igemm readers have no row-table form)
+    if (!h->staged_ok[fe]) return BMI_ERR_UNSUPPORTED;
+    if (workspace_bytes < h->ws_bytes) return BMI_ERR_NOMEM;
+    Pass p{x_nchw, (char*)workspace, (hipStream_t)stream, batch, seed, mask_cnt0};
+    p.S1 = S1; p.S2 = S2; p.SL = SL; p.SH = SH;
+    const hipStream_t s = p.stream;
+    int* lists[2] = {(int*)(p.ws + h->exit_off), (int*)(p.ws + h->exit_off) + h->max_batch};
+    int* count_dev = (int*)(p.ws + h->exit_off) + 2 * h->max_batch;
+    int* rows_dev = count_dev + 64;
+    int rc = launch_fill_int(exit_of_image, batch, last, s);
+    if (rc != BMI_OK) return rc;
+    for (int x = 0; x < h->n_exits; ++x) active_after[x] = 0;
+    const int* act = nullptr;      // null: every image is still active (stage 0: bmi_forward_mcd's launches)
+    const int* rows = nullptr;
+    int bc = batch, cur = 0;
+    std::vector<const OpInfo*> stage_ops;
+    for (int k = 0; fe + k <= last; ++k) {
+        // the stage's prefix ops once per active image (rows = the active list); those without a row-table form over the whole batch
+        for (const OpInfo& op : h->prefix) {
+            if (op_stage(op, fe) != k) continue;
+            rc = (act && prefix_row_form(h, op)) ? run_op(h, p, op, bc, 0, act, bc, act) : run_op(h, p, op, batch, 0);
+            if (rc != BMI_OK) return rc;
+        }
+        stage_ops.clear();
+        for (const OpInfo& op : h->suffix)
+            if (op_stage(op, fe) == k) stage_ops.push_back(&op);
+        rc = run_suffix_ops(h, p, stage_ops.size(), [&](size_t i) -> const OpInfo& { return *stage_ops[i]; }, t_count * bc, 0, act, bc, rows);
+        if (rc != BMI_OK) return rc;
+        const int e = fe + k;          // the exit tested after this stage (none after the last)
+        for (const OpInfo* op : stage_ops)
+            if (op->d.kind == BMI_OP_HEAD && (op->d.out != e || e == last)) active_after[op->d.out] = bc;
+        if (e == last) break;
+        rc = launch_exit_rule_decide(S1, batch, h->out_dim, t_count, rule->threshold, rule->criterion == BMI_EXIT_MARGIN, rule->ensemble, act, bc,
+                                     lists[cur], count_dev, exit_of_image, e, s);
+        if (rc != BMI_OK) return rc;
+        int n_active = 0;
+        if (hipMemcpyAsync(&n_active, count_dev, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+            return BMI_ERR_HIP;
+        active_after[e] = n_active;
+        if (n_active == 0) return BMI_OK;                    // every image has left: the later stages do not run at all
+        act = lists[cur];
+        bc = n_active;
+        cur ^= 1;
+        rc = launch_expand_rows(act, bc, batch, t_count, rows_dev, s);     // compact image -> tensor row of the suffix launches
         if (rc != BMI_OK) return rc;
         rows = rows_dev;
     }

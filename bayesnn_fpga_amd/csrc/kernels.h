@@ -167,6 +167,9 @@ int launch_finalize_per_image(int n_exits, int batch, int C, const int* t_used, 
                               hipStream_t s);
 // dst[r][c] = src[(cnt0 + r * stride) % m][c], r < m (a Masksembles table in the order a strided walk visits it)
 int launch_mask_permute(const float* src, float* dst, int m, int c, int cnt0, int stride, hipStream_t s);
+// bmi_forward_mcd_exit_staged: the bmi_exit_rule test at exit e on S1 [E][B][C] of t_total samples (margin: BMI_EXIT_MARGIN; ensemble: exits 0..e)
+int launch_exit_rule_decide(const double* S1, int B, int C, int t_total, double thr, int margin, int ensemble, const int* in, int bc, int* out,
+                            int* count, int* exit_of, int e, hipStream_t s);
 int launch_expand_rows(const int* active, int bc, int batch, int tc, int* rows, hipStream_t s);   // rows[tl*bc + i] = tl*batch + active[i]
 int launch_finalize(int64_t n, int t_total, const double* S1, const double* S2, const double* SL, double* mean,
                     double* var, double* lm, int* nonfinite, hipStream_t s);
@@ -181,6 +184,7 @@ int launch_scale_copy(const _Float16* in, _Float16* out, long n, float scale, in
 int launch_splitk_finish(const ConvArgs& a, hipStream_t s);   // after a split-K conv_igemm launch
 int launch_conv1x1_seam(const ConvArgs& a, const ConvArgs& b, hipStream_t s);   // conv1x1_seam.hip: a = expand conv (+ residual), b = the reduce conv that reads a.out
 bool conv_takes_seam_kernel(int cmid, int cw, int cn);
+bool conv1x1_stream_takes(const ConvArgs& a);   // whether launch_conv1x1_stream takes `a` (a row table aside): it has no row-table form
 int launch_conv1x1_stream(const ConvArgs& a, hipStream_t s);
 bool conv_takes_patch_kernel(int ksize, int stride, int pad, int cin, int cout, int ho, int wo);
 

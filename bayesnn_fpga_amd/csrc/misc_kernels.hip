@@ -608,6 +608,68 @@ int launch_exit_decide(const double* S1e, int C, int t_total, double thr, const 
     return BMI_OK;
 }
 
+// Staged early exit (bmi_forward_mcd_exit_staged): the same compaction with the rule of bmi_exit_rule, float64 as the header states
+// it: p_c = S1[e][b][c] / t (ensemble: the exits 0..e's p_c summed in exit order, / (e + 1)); confidence = max_c p_c, margin = top-1
+// minus top-2 (0 on a tie).  No contraction into fma: a numpy restatement gets the same statistic.
+__device__ double exit_rule_stat(const double* __restrict__ S1, int B, int C, int b, int e, double t, int margin, int ensemble) {
+#pragma clang fp contract(off)
+    double m1 = -1.0, m2 = -1.0;
+    for (int c = 0; c < C; ++c) {
+        double p;
+        if (ensemble) {
+            double acc = 0.0;
+            for (int x = 0; x <= e; ++x) acc = acc + S1[((size_t)x * B + b) * C + c] / t;
+            p = acc / (double)(e + 1);
+        } else {
+            p = S1[((size_t)e * B + b) * C + c] / t;
+        }
+        if (p > m1) { m2 = m1; m1 = p; }
+        else if (p > m2) m2 = p;
+    }
+    return margin ? m1 - (C > 1 ? m2 : 0.0) : m1;
+}
+
+__global__ __launch_bounds__(256) void exit_rule_decide_kernel(const double* __restrict__ S1, int B, int C, double t, double thr, int margin,
+                                                               int ensemble, const int* __restrict__ in, int bc, int* __restrict__ out,
+                                                               int* __restrict__ count, int* __restrict__ exit_of, int e) {
+    __shared__ int scan[256];
+    __shared__ int base_s;
+    const int tid = threadIdx.x;
+    if (tid == 0) base_s = 0;
+    __syncthreads();
+    for (int base = 0; base < bc; base += 256) {
+        const int i = base + tid;
+        int keep = 0, b = -1;
+        if (i < bc) {
+            b = in ? in[i] : i;
+            if (exit_rule_stat(S1, B, C, b, e, t, margin, ensemble) > thr) exit_of[b] = e;
+            else keep = 1;
+        }
+        scan[tid] = keep;
+        __syncthreads();
+        for (int off = 1; off < 256; off <<= 1) {
+            const int v = tid >= off ? scan[tid - off] : 0;
+            __syncthreads();
+            scan[tid] += v;
+            __syncthreads();
+        }
+        if (keep) out[base_s + scan[tid] - 1] = b;
+        __syncthreads();
+        if (tid == 255) base_s += scan[255];
+        __syncthreads();
+    }
+    if (tid == 0) *count = base_s;
+}
+
+int launch_exit_rule_decide(const double* S1, int B, int C, int t_total, double thr, int margin, int ensemble, const int* in, int bc, int* out,
+                            int* count, int* exit_of, int e, hipStream_t s) {
+    if (!S1 || !out || !count || !exit_of || bc <= 0 || bc > B || C <= 0 || t_total <= 0 || e < 0 || in == out) return BMI_ERR_INVALID;
+    hipLaunchKernelGGL(exit_rule_decide_kernel, dim3(1), dim3(256), 0, s, S1, B, C, (double)t_total, thr, margin, ensemble, in, bc, out, count,
+                       exit_of, e);
+    BMI_CHECK_LAUNCH();
+    return BMI_OK;
+}
+
 __global__ void expand_rows_kernel(const int* __restrict__ active, int bc, int batch, int total, int* __restrict__ rows) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= total) return;

@@ -349,6 +349,35 @@ class CompiledGraph:
         self.head_macs = sum(t[o["in_"]][2] * self.out_dim for o in self.graph.ops if o["kind"] == _lib.OP_HEAD)
         self.dense_macs = sum(t[o["in_"]][2] * t[o["out"]][2] for o in self.graph.ops if o["kind"] == _lib.OP_DENSE)
 
+    def exit_stages(self, first_exit=1):
+        """The stage plan of ``MCDEngine.predict_early_exit`` (bmi_query_exit_stages, host only): a list with one dict per decision stage,
+        stage 0 holding every op up to exit ``first_exit``: prefix_macs (per image), suffix_macs (per image and sample), n_ops, and the
+        prefix ops of the stage that run over the whole batch because their kernel has no row-table form (whole_batch_macs per image, also
+        counted in prefix_macs; n_whole_batch_ops)."""
+        first_exit = int(first_exit)
+        if not 0 <= first_exit < self.n_exits:
+            raise ValueError(f"first_exit must be in [0, {self.n_exits})")
+        n = C.c_int32(0)
+        _lib.check(self.lib.bmi_query_exit_stages(self.handle, first_exit, 0, C.byref(n), None, None, None, None, None), "bmi_query_exit_stages")
+        k = n.value
+        pm, sm, wm = (C.c_int64 * k)(), (C.c_int64 * k)(), (C.c_int64 * k)()
+        no, nw = (C.c_int32 * k)(), (C.c_int32 * k)()
+        _lib.check(self.lib.bmi_query_exit_stages(self.handle, first_exit, k, C.byref(n), pm, sm, no, wm, nw), "bmi_query_exit_stages")
+        return [dict(prefix_macs=pm[i], suffix_macs=sm[i], n_ops=no[i], whole_batch_macs=wm[i], n_whole_batch_ops=nw[i]) for i in range(k)]
+
+    def op_stages(self, first_exit=1):
+        """The stage plan per op (bmi_query_op_stages): a list of (out, stage, whole_batch) in the engine's order, one entry per output of
+        every op (a pair- or seam-fused op lists both); ``out`` is the tensor id, or -1 - the exit index for a head."""
+        first_exit = int(first_exit)
+        if not 0 <= first_exit < self.n_exits:
+            raise ValueError(f"first_exit must be in [0, {self.n_exits})")
+        n = C.c_int32(0)
+        _lib.check(self.lib.bmi_query_op_stages(self.handle, first_exit, 0, C.byref(n), None, None, None), "bmi_query_op_stages")
+        k = n.value
+        out, st, wb = (C.c_int32 * k)(), (C.c_int32 * k)(), (C.c_int32 * k)()
+        _lib.check(self.lib.bmi_query_op_stages(self.handle, first_exit, k, C.byref(n), out, st, wb), "bmi_query_op_stages")
+        return [(out[i], st[i], bool(wb[i])) for i in range(k)]
+
     def _make_desc(self):
         g = self.graph
         tarr = (_lib.TensorDesc * len(g.tensors))(*[_lib.TensorDesc(*t) for t in g.tensors])
@@ -571,6 +600,70 @@ class MCDEngine(CompiledGraph):
         r["exit_layer"] = exit_layer
         r["active_after"] = [int(v) for v in active]
         r["best_preds"] = r["mean"][exit_layer.long(), torch.arange(B, device=self.device)]
+        return r
+
+    def accumulate_early_exit(self, x, S, T, threshold, seed=0, cnt0=0, first_exit=1, rule="confidence", ensemble=False, H=None):
+        """The sampling half of ``predict_early_exit`` (bmi_forward_mcd_exit_staged) into the ZEROED sums S [3, E, B, C] (and H [E, B]:
+        ``new_uncertainty_sums``): every row it computes equals ``accumulate``'s over samples 0 .. T-1 bit for bit, rows of exits an image
+        never reached stay zero.  Returns (exit_layer int32 [B] on the device, active_after host list [E])."""
+        x = self._check_x(x)
+        B = x.shape[0]
+        if rule not in _lib.EXIT_RULES:
+            raise ValueError(f"rule must be one of {sorted(_lib.EXIT_RULES)}, got {rule!r}")
+        T, first_exit = int(T), int(first_exit)
+        if not 1 <= T <= self.chunk_samples:
+            raise ValueError(f"early exiting needs all T={T} samples in one chunk (engine planned for {self.chunk_samples})")
+        if not 0 <= first_exit < self.n_exits:
+            raise ValueError(f"first_exit must be in [0, {self.n_exits})")
+        if tuple(S.shape) != (3, self.n_exits, B, self.out_dim) or S.dtype != torch.float64 or not S.is_contiguous():
+            raise ValueError("moment buffer must be contiguous float64 [3, E, B, C]")
+        if H is not None and (tuple(H.shape) != (self.n_exits, B) or H.dtype != torch.float64 or not H.is_contiguous()):
+            raise ValueError("entropy buffer must be contiguous float64 [E, B]")
+        exit_layer = torch.empty(B, dtype=torch.int32, device=self.device)
+        active = (C.c_int32 * self.n_exits)()
+        r_c = _lib.ExitRule(_lib.EXIT_RULES[rule], int(bool(ensemble)), float(threshold), first_exit)
+        with torch.cuda.device(self.device):
+            rc = self.lib.bmi_forward_mcd_exit_staged(self.handle, x.data_ptr(), B, T, int(seed) & 0xFFFFFFFFFFFFFFFF, int(cnt0), C.byref(r_c),
+                                                      S[0].data_ptr(), S[1].data_ptr(), S[2].data_ptr(), None if H is None else H.data_ptr(),
+                                                      exit_layer.data_ptr(), active, self.workspace.data_ptr(), self.workspace_bytes, self._stream())
+        _lib.check(rc, "bmi_forward_mcd_exit_staged")
+        return exit_layer, [int(v) for v in active]
+
+    def predict_early_exit(self, x, T, threshold, seed=0, cnt0=0, first_exit=1, rule="confidence", ensemble=False, uncertainty=False):
+        """Early exiting by stages on the device (bmi_forward_mcd_exit_staged): unlike ``predict_with_exit`` the later stages skip the
+        deterministic trunk too, so with exit-only dropout an image that leaves at exit 1 never runs layer3 / layer4.  After exit e >=
+        ``first_exit`` an image leaves when its statistic exceeds ``threshold``: ``rule="confidence"`` max_c p_c (the reference's
+        is_confident), ``"margin"`` top-1 minus top-2 (confident(diff=True)); p = the T-mean softmax of exit e, or with ``ensemble`` the mean
+        of exits 0..e (the reference's exit ensembles).  Every computed row equals ``predict``'s bit for bit.  Returns
+        ``predict_with_exit``'s dict (``best_preds``: the ensemble mean at the exit taken when ``ensemble``), plus ``macs_done`` (MACs the
+        stages ran: per stage, images that ran it x (prefix MACs + T x suffix MACs), ops without a row-table form at the whole batch) and
+        ``macs_full`` (``predict``'s); with ``uncertainty``, also pred_entropy / exp_entropy / mutual_info [E,B] of the computed rows as in
+        ``finalize_uncertainty``.  Synchronises once per decision."""
+        if rule not in _lib.EXIT_RULES:
+            raise ValueError(f"rule must be one of {sorted(_lib.EXIT_RULES)}, got {rule!r}")
+        if not 1 <= int(T) <= self.chunk_samples:
+            raise ValueError(f"early exiting needs all T={T} samples in one chunk (engine planned for {self.chunk_samples})")
+        B, T, first_exit = x.shape[0], int(T), int(first_exit)
+        stages = self.exit_stages(first_exit)
+        S, H = self.new_uncertainty_sums(B) if uncertainty else (self.new_moments(B), None)
+        exit_layer, active = self.accumulate_early_exit(x, S, T, threshold, seed, cnt0, first_exit, rule, ensemble, H)
+        r = self.finalize(S, T) if H is None else self.finalize_uncertainty(S, H, T)
+        r["exit_layer"] = exit_layer
+        r["active_after"] = active
+        idx = torch.arange(B, device=self.device)
+        p = r["mean"]
+        if ensemble:          # the mean of exits 0..e, summed in exit order
+            p = p.cumsum(0) / torch.arange(1, self.n_exits + 1, dtype=torch.float64, device=self.device).view(-1, 1, 1)
+        r["best_preds"] = p[exit_layer.long(), idx]
+        # images that ran stage k: all for stage 0, then those still active after exit first_exit + k - 1's test
+        ran = [B] + [active[first_exit + k - 1] for k in range(1, len(stages))]
+        done = 0
+        for k, st in enumerate(stages):
+            if ran[k] == 0:
+                break
+            done += ran[k] * (st["prefix_macs"] - st["whole_batch_macs"] + T * st["suffix_macs"]) + B * st["whole_batch_macs"]
+        r["macs_done"] = done
+        r["macs_full"] = B * (self.prefix_macs + T * self.suffix_macs)
         return r
 
     def accumulate_adaptive(self, x, S, T_max, threshold, rule="sem", t_step=None, test_exit=-1, seed=0, cnt0=0, H=None, image_offset=0):

@@ -377,6 +377,52 @@ int bmi_forward_mcd_adaptive(bmi_handle h, const float* x_nchw, int32_t batch, i
                              uint8_t* converged, int32_t* active_after_step, void* workspace, size_t workspace_bytes,
                              bmi_stream stream);
 
+/* Early exit by stages that also skips the deterministic trunk (the paper's exit-only dropout: every trunk and exit-branch conv is in
+ * the once-per-batch prefix).  Every op, prefix and suffix, has a stage: the smallest exit index of any head downstream of its outputs
+ * (a pair- or seam-fused op: the smaller of its two members'); stages <= rule->first_exit fold into stage 0.  Stage 0 runs on the whole
+ * batch exactly as bmi_forward_mcd would; after stage k the rule is tested at exit e = first_exit + k (e < n_exits-1) on the device, and
+ * stage k+1 runs on the images still active only: its prefix ops once over the Bc active images (one row-table entry per image), its
+ * suffix ops over t_count x Bc rows.  Tensors keep their original rows and masks their original element indices, and a launch under a
+ * row table takes the full run's kernel, so every row that is computed equals bmi_forward_mcd's (same seed, mask_cnt0) bit for bit:
+ * S1 / S2 / SL, and SH when not NULL (as bmi_forward_mcd_entropy).  Split-K launches (conv_igemm, conv_split) and the pooled epilogues run
+ * compacted; a prefix op whose full-run kernel has no row-table form (a 1x1 conv that conv1x1_stream takes at the planned batch) runs
+ * over the whole batch, and bmi_query_exit_stages reports those ops.
+ * The rule, float64 on the active images' sums at exit e, p_c = S1[e][b][c] / t_count, or with ensemble = 1
+ * p_c = (sum_{e'=0..e} S1[e'][b][c] / t_count) / (e + 1), summed in exit order (the reference's exit ensembles):
+ *   BMI_EXIT_CONFIDENCE (0): stat = max_c p_c          (is_confident)
+ *   BMI_EXIT_MARGIN     (1): stat = p_(1) - p_(2)      (top-1 minus top-2: confident(diff=True))
+ * an image leaves when stat > threshold: exit_of_image[b] = e (device int32 [batch]); images that never leave get n_exits-1.
+ * S1 / S2 / SL [E][batch][C] (and SH [E][batch]) must be ZERO on entry; rows of exits an image never reached stay zero.
+ * active_after[e] (host, [n_exits]) = images still active after exit e's test (exits before first_exit and the last: the images that
+ * ran it; 0 for exits nobody reached).  Synchronises the stream once per decision (the host sizes the next stage's grids), so it cannot
+ * be graph-captured.  BMI_ERR_INVALID: a NULL required pointer, an unknown criterion, ensemble not 0 / 1, a NaN threshold, first_exit
+ * outside [0, E), batch / t_count < 1, mask_cnt0 < 0, batch > max_batch; BMI_ERR_UNSUPPORTED: t_count > the planned chunk, the exact
+ * engine (BMI_DTYPE_F32), keep-bit consumers (BMI_MASK_BITS=1) behind a decision, a staged suffix order that the workspace packing
+ * cannot hold (never seen on the bundled models). */
+#define BMI_EXIT_CONFIDENCE 0
+#define BMI_EXIT_MARGIN 1
+typedef struct bmi_exit_rule {
+    int32_t criterion;   /* BMI_EXIT_* */
+    int32_t ensemble;    /* 1: the mean of exits 0..e decides */
+    double threshold;
+    int32_t first_exit;  /* the first exit tested */
+} bmi_exit_rule;
+int bmi_forward_mcd_exit_staged(bmi_handle h, const float* x_nchw, int32_t batch, int32_t t_count, uint64_t seed, int32_t mask_cnt0,
+                                const bmi_exit_rule* rule, double* S1, double* S2, double* SL, double* SH, int32_t* exit_of_image,
+                                int32_t* active_after, void* workspace, size_t workspace_bytes, bmi_stream stream);
+
+/* The stage plan of bmi_forward_mcd_exit_staged for first_exit (host only; needs bmi_plan).  *n_stages = n_exits - first_exit; with
+ * capacity 0 only that is written, else capacity must be >= it.  Per stage k (each array NULL: not written): prefix_macs[k] (MACs per
+ * image), suffix_macs[k] (per image and sample), n_ops[k] (prefix + suffix ops), and of those the prefix ops that run over the whole
+ * batch because their kernel has no row-table form: whole_batch_macs[k] (per image, also counted in prefix_macs[k]) and
+ * n_whole_batch_ops[k] (0 in stage 0).  Summed over the stages the MACs equal bmi_query's. */
+int bmi_query_exit_stages(bmi_handle h, int32_t first_exit, int32_t capacity, int32_t* n_stages, int64_t* prefix_macs, int64_t* suffix_macs,
+                          int32_t* n_ops, int64_t* whole_batch_macs, int32_t* n_whole_batch_ops);
+/* The same plan per op (host only): one entry per output of every op (a pair- or seam-fused op lists both outputs), in the engine's
+ * order: out[i] = the tensor id (a head: -1 - its exit index), stage[i] its stage for first_exit, whole_batch[i] = 1 for a prefix op
+ * behind a decision without a row-table form.  *count = the number of entries; capacity 0 writes only that, else capacity must be >= it. */
+int bmi_query_op_stages(bmi_handle h, int32_t first_exit, int32_t capacity, int32_t* count, int32_t* out, int32_t* stage, int32_t* whole_batch);
+
 /* bmi_finalize_checked and bmi_finalize_uncertainty with a per-image sample count t_used[b] (device int32 [batch], every entry >= 1)
  * in place of t_total: mean / var / logit_mean [E][batch][C]; pred_entropy / exp_entropy / mutual_info [E][batch] when SH and
  * the three outputs are all non-NULL (all NULL: skipped).  nonfinite (NULL: not counted) as in bmi_finalize_checked. */

@@ -1,0 +1,100 @@
+"""Full ``predict`` against early exit by stages (``predict_early_exit``), same process, alternating, on the exit workloads: ResNet-18
+exit-only dropout (C = 100, T = 10), VGG-19 exit-only (C = 100, T = 10) and the headline ResNet-18 block + exit (T = 20), at B = 250 and,
+where the engine plans it, B = 1024.  Thresholds: the confidence statistic's quantiles at exit 1 on the full run, so that about 25 / 50 / 75 %
+of the images leave there.  Prints one JSON line per measurement: median ms of both calls, exit histogram, macs_done / macs_full, and per
+stage the images each launch carried (bmi_profile_launches).
+
+    python tools/exit_bench.py [--reps 7] [--batches 250,1024] [--leave 0.25,0.5,0.75] [--dtype f16]
+"""
+import argparse
+import collections
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from bayesnn_fpga_amd.models.resnet18.resnet18 import ResNet18MCEarlyExit  # noqa: E402
+from bayesnn_fpga_amd.models.vgg19.vgg19 import VGG19MCEarlyExit  # noqa: E402
+from bayesnn_fpga_amd.synthetic import synthetic_images, synthetic_weights_  # noqa: E402
+
+EXIT_ONLY = dict(dropout_exit=True, dropout=None, dropout_p=0.25, out_dim=100)
+WORKLOADS = {
+    "resnet18_exit_only": (ResNet18MCEarlyExit, EXIT_ONLY, 10),
+    "vgg19_me": (VGG19MCEarlyExit, EXIT_ONLY, 10),
+    "resnet18_me": (ResNet18MCEarlyExit, dict(dropout_exit=True, dropout="block", dropout_p=0.25, out_dim=10), 20),
+}
+
+
+def median_ms(fn, reps):
+    out = []
+    for _ in range(reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        out.append((time.perf_counter() - t0) * 1e3)
+    return float(np.median(out))
+
+
+def launch_images(eng, fn):
+    """Counter of the images carried by each launch of one call."""
+    eng.profile(True)
+    try:
+        eng.profile_read()
+        fn()
+        torch.cuda.synchronize()
+        eng.profile_read()
+        launches = eng.profile_launches()
+    finally:
+        eng.profile(False)
+    return dict(sorted(collections.Counter(ln["images"] for ln in launches).items()))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--batches", default="250,1024")
+    ap.add_argument("--leave", default="0.25,0.5,0.75")
+    ap.add_argument("--dtype", default="f16")
+    ap.add_argument("--workloads", default=",".join(WORKLOADS))
+    a = ap.parse_args()
+    dev = torch.device("cuda:0")
+    for name in a.workloads.split(","):
+        cls, kw, T = WORKLOADS[name]
+        for B in (int(b) for b in a.batches.split(",")):
+            torch.manual_seed(0)
+            m = synthetic_weights_(cls(**kw), 0).to(dev).eval()
+            try:
+                eng = m.engine(dev, max_batch=B, chunk_samples=T, dtype=a.dtype)
+            except Exception as ex:      # (an engine the planner refuses at this batch)
+                print(json.dumps(dict(workload=name, B=B, skipped=str(ex))), flush=True)
+                continue
+            x = synthetic_images(B, seed=1).to(dev)
+            full = eng.predict(x, T, seed=3)
+            conf1 = full["mean"][1].max(-1).values.cpu().numpy()
+            for frac in (float(f) for f in a.leave.split(",")):
+                thr = float(np.quantile(conf1, 1.0 - frac))
+                ee = lambda: eng.predict_early_exit(x, T, thr, seed=3)       # noqa: E731
+                pr = lambda: eng.predict(x, T, seed=3)                      # noqa: E731
+                ee(), pr()
+                ms_full, ms_exit = [], []
+                for _ in range(a.reps):           # alternating
+                    ms_full.append(median_ms(pr, 1))
+                    ms_exit.append(median_ms(ee, 1))
+                r = ee()
+                hist = np.bincount(r["exit_layer"].cpu().numpy(), minlength=eng.n_exits).tolist()
+                print(json.dumps(dict(workload=name, dtype=a.dtype, B=B, T=T, leave_at_exit1=frac, threshold=round(thr, 6), exit_hist=hist,
+                                      active_after=r["active_after"], ms_predict=round(float(np.median(ms_full)), 4),
+                                      ms_early_exit=round(float(np.median(ms_exit)), 4), macs_ratio=round(r["macs_done"] / r["macs_full"], 4),
+                                      launch_images=launch_images(eng, ee))), flush=True)
+            del eng, m
+            torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main()
