@@ -98,6 +98,11 @@ _PROTOS = {
                                C.c_void_p, C.c_void_p]),
     "bmi_finalize_checked": (C.c_int, [C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bmi_engine_set_temperature": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int32]),
+    "bmi_engine_get_temperature": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int32]),
+    "bmi_nll_temperature_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "bmi_nll_temperature_grid": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                           C.c_void_p, C.c_size_t, C.c_void_p]),
     "bmi_profile_enable": (C.c_int, [C.c_void_p, C.c_int32]),
     "bmi_profile_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "bmi_philox_mask": (C.c_int, [C.c_void_p, C.c_int64, C.c_uint64, C.c_int32, C.c_int32, C.c_float, C.c_void_p]),

@@ -12,6 +12,7 @@
 // Activation buffers live in ONE caller-owned workspace; the suffix tensors are packed by live range (first-fit): 7 GB of
 // the 288 GB for the bench's 25 500-image-sample chunk (large chunks won every A/B, so activations do round-trip HBM).
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <new>
@@ -97,6 +98,8 @@ struct bmi_engine_s {
     size_t splitk_off = 0;               // fp32 partial sums of the split-K prefix convs
     size_t head_off = 0, head_part_bytes = 0;   // float64 partial sums of a head launch's 32-sample groups (joined in group order), one region per exit
     std::vector<std::pair<const float*, size_t>> perm;   // (bmi_plan) Masksembles tables (device pointer of the site) -> workspace offset of the permuted copy
+    std::vector<float> tau;              // bmi_engine_set_temperature: the temperatures as given ([n_exits]; empty: never set = ones)
+    std::vector<float> inv_tau;          // float32(1 / (double)tau[e]) per exit, what the heads multiply by; EMPTY when off (never set, or all ones)
     std::vector<char> staged_ok;         // (bmi_plan) per first_exit: the staged suffix order keeps every shared workspace range's live ranges apart
     // profiling
     bool profiling = false;
@@ -769,6 +772,32 @@ int bmi_engine_set_option(bmi_handle h, const char* name, int32_t value) {
     return set_named_option(h->opts, name, value);
 }
 
+// One temperature per exit (host pointer), or NULL: off.  All ones is off too — the heads then run the untempered instantiations, and the
+// outputs are the bits of an engine that never had a temperature.  Read at launch time: captured graphs keep what was set at capture.
+int bmi_engine_set_temperature(bmi_handle h, const float* tau, int32_t n_exits) {
+    if (!h) return BMI_ERR_INVALID;
+    if (!tau) { h->tau.clear(); h->inv_tau.clear(); return BMI_OK; }
+    if (n_exits != h->n_exits) return BMI_ERR_INVALID;
+    bool ones = true;
+    for (int i = 0; i < n_exits; ++i) {
+        if (!(tau[i] > 0.f) || !std::isfinite(tau[i])) return BMI_ERR_INVALID;
+        const float inv = (float)(1.0 / (double)tau[i]);
+        if (!(inv > 0.f) || !std::isfinite(inv)) return BMI_ERR_INVALID;      // 1 / tau leaves the float32 range
+        ones = ones && tau[i] == 1.f;
+    }
+    h->tau.assign(tau, tau + n_exits);
+    h->inv_tau.clear();
+    if (!ones)
+        for (int i = 0; i < n_exits; ++i) h->inv_tau.push_back((float)(1.0 / (double)tau[i]));
+    return BMI_OK;
+}
+
+int bmi_engine_get_temperature(bmi_handle h, float* tau, int32_t capacity) {
+    if (!h || !tau || capacity < h->n_exits) return BMI_ERR_INVALID;
+    for (int i = 0; i < h->n_exits; ++i) tau[i] = h->tau.empty() ? 1.f : h->tau[i];
+    return BMI_OK;
+}
+
 int bmi_destroy(bmi_handle h) {
     if (!h) return BMI_ERR_INVALID;
     for (auto& r : h->recs) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
@@ -1049,6 +1078,7 @@ HeadArgs make_head_args(bmi_engine_s* e, const Pass& p, const OpInfo& op, int N,
     a.site = pass_site(e, p, on_logits ? nullptr : &d.site, soff);
     a.site_logits = pass_site(e, p, on_logits ? &d.site : nullptr);
     a.b0 = p.b0;
+    a.inv_tau = e->inv_tau.empty() ? 0.f : e->inv_tau[d.out];       // 0: the untempered instantiations
     if (p.S1) {
         const size_t eo = (size_t)d.out * B * e->out_dim;
         a.S1 = p.S1 + eo; a.S2 = p.S2 + eo; a.SL = p.SL + eo;
@@ -1733,6 +1763,18 @@ int bmi_finalize_uncertainty(int32_t n_exits, int32_t batch, int32_t out_dim, in
     if ((int64_t)n_exits * batch > INT32_MAX) return BMI_ERR_UNSUPPORTED;
     return launch_finalize_uncertainty(n_exits * batch, out_dim, t_total, S1, SH, pred_entropy, exp_entropy, mutual_info, nonfinite,
                                        (hipStream_t)stream);
+}
+
+size_t bmi_nll_temperature_scratch_bytes(int32_t E, int32_t B, int32_t G) {
+    if (E < 1 || B < 1 || G < 1) return 0;
+    return (size_t)E * G * B * sizeof(double);
+}
+
+int bmi_nll_temperature_grid(const float* logits, int32_t T, int32_t E, int32_t B, int32_t C, const int32_t* labels, const float* tau_grid,
+                             int32_t G, double* nll, void* scratch, size_t scratch_bytes, bmi_stream stream) {
+    if (!logits || !labels || !tau_grid || !nll || !scratch || T < 1 || E < 1 || B < 1 || C < 1 || G < 1) return BMI_ERR_INVALID;
+    if (scratch_bytes < bmi_nll_temperature_scratch_bytes(E, B, G)) return BMI_ERR_NOMEM;
+    return launch_nll_temperature_grid(logits, T, E, B, C, labels, tau_grid, G, nll, (double*)scratch, (hipStream_t)stream);
 }
 
 int bmi_profile_enable(bmi_handle h, int32_t enable) {

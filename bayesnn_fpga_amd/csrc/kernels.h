@@ -122,6 +122,8 @@ struct HeadArgs {   // fused exit head (head_fused.hip)
                           // null (hardware atomics then: the single-kernel entry point); with SH, [ceil(tc / 32)][B] entropy sums behind it
     double* SH;           // this exit's [B] accumulator of per-sample softmax entropies in nats (bmi_forward_mcd_entropy), or null: off
                           // (last: the layout the kernels read stays what it was)
+    float inv_tau;        // temperature scaling (bmi_engine_set_temperature): float32(1 / tau) of this exit — softmax, S1, S2 and SH are those of
+                          // z = logit * inv_tau, SL and `logits` stay the raw logit — or 0: off, the untempered instantiations (appended as SH was)
 };
 int launch_head_fused(const HeadArgs& a, hipStream_t s);
 #define BMI_HEAD_PACK_MAX 8
@@ -176,6 +178,10 @@ int launch_finalize(int64_t n, int t_total, const double* S1, const double* S2, 
 // per (exit, image): predictive entropy of S1 / T, expected entropy SH / T, their difference (bmi_finalize_uncertainty)
 int launch_finalize_uncertainty(int n_rows, int C, int t_total, const double* S1, const double* SH, double* pred, double* expd,
                                 double* mi, int* nonfinite, hipStream_t s);
+// calibration.hip (bmi_nll_temperature_grid): nll [E][G] += the NLL of the T-mean tempered softmax of logits [T][E][B][C] at tau_grid [E][G];
+// scratch: [E][G][B] float64 per-image terms
+int launch_nll_temperature_grid(const float* logits, int T, int E, int B, int C, const int* labels, const float* tau_grid, int G, double* nll,
+                                double* scratch, hipStream_t s);
 int launch_philox_mask(uint8_t* keep, int64_t n, uint64_t seed, int site, int t, float p, hipStream_t s);
 // planar_w > 0: the bits in the lazy site's planar layout (rows of planar_w pixels; 2-bit sites, c % 64 == 0)
 int launch_mask_bits(uint8_t* bits, int n, int hw, int c, const SiteArgs& site, int batch, int t0, hipStream_t s, int planar_w = 0);

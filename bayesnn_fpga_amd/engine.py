@@ -300,6 +300,23 @@ def model_exits(model):
     return 4 if getattr(model, "multi_exit", True) else 1
 
 
+def check_temperature(tau, n_exits):
+    """``tau`` as a plain list of ``n_exits`` Python floats, or None (off): a scalar stands for every exit; raises ValueError for a wrong
+    count, a non-finite or a non-positive entry, or one whose float32 value (what the device is given) is not finite and positive."""
+    if tau is None:
+        return None
+    raw = np.asarray(tau.detach().cpu() if isinstance(tau, torch.Tensor) else tau, dtype=np.float64)
+    vals = np.repeat(raw.reshape(-1), n_exits) if raw.ndim == 0 else raw.reshape(-1)
+    if vals.size != n_exits:
+        raise ValueError(f"temperature: expected one value per exit ({n_exits}), got {vals.size}")
+    with np.errstate(over="ignore", divide="ignore"):
+        f32 = vals.astype(np.float32)
+        inv = (1.0 / f32.astype(np.float64)).astype(np.float32)
+    if not (np.all(np.isfinite(vals)) and np.all(vals > 0) and np.all(np.isfinite(f32)) and np.all(f32 > 0) and np.all(np.isfinite(inv)) and np.all(inv > 0)):
+        raise ValueError(f"temperature: every entry must be finite and > 0 (in float32, and its reciprocal too), got {vals.tolist()}")
+    return [float(v) for v in vals]
+
+
 def build_graph(model, device, dtype="f16"):
     g = GraphBuilder(device, dtype)
     fam = getattr(model, "family", None)
@@ -348,6 +365,30 @@ class CompiledGraph:
         self.stem_macs = sum(t[o["out"]][0] * t[o["out"]][1] * t[o["out"]][2] * 27 for o in self.graph.ops if o["kind"] == _lib.OP_STEM)
         self.head_macs = sum(t[o["in_"]][2] * self.out_dim for o in self.graph.ops if o["kind"] == _lib.OP_HEAD)
         self.dense_macs = sum(t[o["in_"]][2] * t[o["out"]][2] for o in self.graph.ops if o["kind"] == _lib.OP_DENSE)
+        # per-exit temperature scaling: a model that carries one (EngineModelMixin.set_exit_temperature, train/calibration.py) hands it to
+        # every engine built from it — model.engine(), BatchesInFlight, FullAnalysis, evaluate's pipes, the sharded walks, the "auto" calibration
+        self.set_temperature(getattr(model, "exit_temperature", None))
+
+    def set_temperature(self, tau):
+        """One softmax temperature per exit (bmi_engine_set_temperature; host only): a scalar (every exit) or ``n_exits`` values, finite and
+        > 0; ``None`` — or all ones — is off.  From the next launch on, every path through the fused head (predict, accumulate,
+        predict_uncertainty, predict_with_exit, predict_early_exit, predict_adaptive, the moment sums of the sharded walks) computes softmax,
+        mean, var and the entropies of ``logit * float32(1 / tau_e)``; ``logit_mean``, ``forward_once`` and ``forward_samples`` stay the raw
+        logits and do not depend on it.  Off, the engine launches the untempered kernels: the bits of an engine that never had one.  A hipGraph
+        captured earlier keeps the temperature it was captured with (``BatchesInFlight.set_temperature`` discards them)."""
+        tau = check_temperature(tau, self.n_exits)
+        if tau is None:
+            rc = self.lib.bmi_engine_set_temperature(self.handle, None, 0)
+        else:
+            rc = self.lib.bmi_engine_set_temperature(self.handle, (C.c_float * self.n_exits)(*tau), self.n_exits)
+        _lib.check(rc, "bmi_engine_set_temperature")
+
+    @property
+    def temperature(self):
+        """The temperatures in force, a list of ``n_exits`` floats (ones when off)."""
+        buf = (C.c_float * self.n_exits)()
+        _lib.check(self.lib.bmi_engine_get_temperature(self.handle, buf, self.n_exits), "bmi_engine_get_temperature")
+        return [float(v) for v in buf]
 
     def exit_stages(self, first_exit=1):
         """The stage plan of ``MCDEngine.predict_early_exit`` (bmi_query_exit_stages, host only): a list with one dict per decision stage,
@@ -764,6 +805,36 @@ class MCDEngine(CompiledGraph):
         _lib.check(rc, "bmi_forward_mcd_samples")
         return out
 
+    def nll_grid(self, logits, labels, tau_grid, out=None):
+        """The objective of a temperature fit on the device (bmi_nll_temperature_grid): ``logits`` fp32 [T, E, B, C] (``forward_samples``),
+        ``labels`` int [B] in [0, C) (the CALLER checks the range: ``train.calibration`` does, on the host), ``tau_grid`` [E, G] candidate
+        temperatures.  ADDS, per exit and candidate, sum_b -log mean_t softmax(l_tb / tau)[y_b] into ``out`` (float64 [E, G], zeros when None)
+        and returns it: a walk over a loader accumulates.  float64 throughout, log-sum-exp form, the same bits on every run;
+        ``train.calibration.nll_grid_numpy`` is its host restatement.  Independent of the temperature set on this engine."""
+        T, E, B, Cd = logits.shape
+        if logits.dtype != torch.float32 or not logits.is_contiguous() or logits.device != self.device:
+            raise ValueError(f"logits must be contiguous float32 [T, E, B, C] on {self.device}")
+        if tuple(labels.shape) != (B,):
+            raise ValueError(f"labels must be [B] = [{B}]")
+        labels = labels.to(device=self.device, dtype=torch.int32).contiguous()
+        tau_grid = torch.as_tensor(tau_grid, dtype=torch.float32).to(self.device).contiguous()
+        if tau_grid.dim() != 2 or tau_grid.shape[0] != E:
+            raise ValueError(f"tau_grid must be [E, G] with E = {E}")
+        G = tau_grid.shape[1]
+        if out is None:
+            out = torch.zeros(E, G, dtype=torch.float64, device=self.device)
+        elif tuple(out.shape) != (E, G) or out.dtype != torch.float64 or not out.is_contiguous() or out.device != self.device:
+            raise ValueError("out must be contiguous float64 [E, G] on the engine's device")
+        need = int(self.lib.bmi_nll_temperature_scratch_bytes(E, B, G))
+        scratch = self.__dict__.get("_nll_scratch")
+        if scratch is None or scratch.numel() < need:
+            scratch = self.__dict__["_nll_scratch"] = torch.empty(need, dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = self.lib.bmi_nll_temperature_grid(logits.data_ptr(), T, E, B, Cd, labels.data_ptr(), tau_grid.data_ptr(), G, out.data_ptr(),
+                                                   scratch.data_ptr(), scratch.numel(), self._stream())
+        _lib.check(rc, "bmi_nll_temperature_grid")
+        return out
+
     def read_tensor(self, tensor_id, batch, samples=1):
         """A copy of graph tensor ``tensor_id`` as it sits in the workspace after a forward (bmi_tensor_info): fp32
         [samples * batch or batch, h, w, c].  For per-layer traces (tools/layer_trace.py): plan the engine under
@@ -915,6 +986,16 @@ class BatchesInFlight:
             if hasattr(self, attr):
                 delattr(self, attr)
         return self
+
+    def set_temperature(self, tau):
+        """``MCDEngine.set_temperature`` on every engine of the pipe; the captured hipGraphs are discarded (after a synchronize): a captured
+        launch carries its kernel arguments and its instantiation, so a replay would run under the temperature it was captured with."""
+        self.synchronize()
+        for e in self.engines:
+            e.set_temperature(tau)
+        for attr in ("_graphs", "_gstreams"):
+            if hasattr(self, attr):
+                delattr(self, attr)
 
     def step(self, x, T, seed=0, cnt0=0, group=None, kind=None, shard=False):
         """One batch step on the next slot — a hipGraph replay (``use_graph``) or eager — with the work partitioned over ``group`` when

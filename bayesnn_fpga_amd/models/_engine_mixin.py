@@ -24,6 +24,7 @@ class EngineModelMixin:
     engine_dtype = "auto"     # "auto" | "f16" | "bf16" | "f16x2" | "bf16x3" | "f32": the default of engine() / model(x) / FullAnalysis / evaluate
     auto_candidates = AUTO_CANDIDATES
     auto_tol = AUTO_TOL
+    exit_temperature = None   # per-exit softmax temperatures (a plain list of floats: survives torch.save(model)), or None: off — set_exit_temperature
 
     def _init_engine_state(self):
         self.mc_seed = 0      # Philox key of the Monte-Carlo stream (csrc/philox.h)
@@ -57,6 +58,16 @@ class EngineModelMixin:
         """After in-place weight updates (an optimizer step, ``p.data.copy_``) the compiled engines, the folded evaluation's pipes and the
         auto engine choice are stale: call this before the next ``model(x)`` / ``FullAnalysis`` / ``evaluate`` (``.to()`` / ``load_state_dict``
         do it themselves; ``train()`` does not — the converter's wrapper uses the training flag to mean "one pass" — so a training loop must)."""
+        self._drop_engines()
+
+    def set_exit_temperature(self, tau):
+        """Per-exit temperature scaling of everything the engines compute from this model's softmax (``MCDEngine.set_temperature``: mean, var,
+        the entropies, the early-exit and adaptive-sampling decisions; never the logits): ``tau`` = one value per exit (or a scalar for all),
+        finite and > 0, or None = off; ``train.calibration.TemperatureScaling`` fits it on a validation split.  Stored on the model as a plain
+        list, and treated like a weight change: compiled engines, pipes with their captured graphs and the ``engine_dtype="auto"`` decision
+        were all made under the other softmax and are dropped — the next use rebuilds them (and re-decides "auto") under this one."""
+        from ..engine import check_temperature, model_exits
+        self.exit_temperature = check_temperature(tau, model_exits(self))
         self._drop_engines()
 
     def __getstate__(self):

@@ -1,0 +1,222 @@
+"""Per-exit temperature scaling: the host restatements, the deterministic search and the loader-level fit.
+
+Temperature scaling is the one-scalar-per-classifier post-hoc calibration (Guo et al. 2017; the subject of the Mix-n-Match code the
+reference's ECE evaluator comes from, SA/train/results_analyzer.py:53): exit e's probabilities become ``softmax(logits / tau_e)``.  With
+Monte-Carlo sampling the prediction is the T-mean of the per-sample softmax, which is NOT a function of the untempered mean — the
+temperature has to act where the per-sample softmax exists, inside the fused exit head (``MCDEngine.set_temperature``) — and the objective
+of the fit is the NLL of that mean,
+
+    nll(tau) = sum_b -log( (1/T) sum_t softmax(l_tb / tau)[y_b] ),
+
+evaluated on the device for a grid of candidates per exit in one launch (``MCDEngine.nll_grid``, bmi_nll_temperature_grid).  The reference
+has no temperature scaling; it saves the validation predictions (``save_validation``) this step is fitted on.
+
+* ``nll_grid_numpy``  — float64 restatement of the device objective (what host users and the tests call).
+* ``temper_logits``   — mean / var of the tempered per-sample softmax, the restatement of what the head computes under a temperature.
+* ``zoom_search``     — the deterministic per-exit search, all exits evaluated in the same launch.
+* ``TemperatureScaling`` — walks a labelled loader once, keeps the split's raw logits on the device, searches, applies, saves.
+"""
+import numpy as np
+import torch
+
+from .results_analyzer import get_device
+
+
+def _inv32(tau):
+    """float32(1 / float64(float32 tau)): the factor the exit heads multiply by."""
+    return (1.0 / np.asarray(tau, dtype=np.float32).astype(np.float64)).astype(np.float32)
+
+
+def nll_grid_numpy(logits, labels, tau_grid):
+    """float64 [E, G]: sum_b -log mean_t softmax(l_tb / tau_eg)[y_b] for ``logits`` [T, E, B, C], ``labels`` [B], ``tau_grid`` [E, G] (taken
+    as float32, like the device's).  bmi_nll_temperature_grid's arithmetic step by step, in log-sum-exp form (no clip; finite for any
+    finite logits):  z = float64(l) * (1.0 / float64(tau));  a_t = (z_y - max_c z) - log sum_c exp(z_c - max_c z);
+    term_b = -(logsumexp_t a_t - log T)."""
+    logits = np.asarray(logits)
+    T, E, B, C = logits.shape
+    labels = np.asarray(labels).astype(np.int64).reshape(B)
+    if labels.min() < 0 or labels.max() >= C:
+        raise ValueError(f"labels must lie in [0, {C})")
+    inv = 1.0 / np.asarray(tau_grid, dtype=np.float32).astype(np.float64)
+    if inv.ndim != 2 or inv.shape[0] != E:
+        raise ValueError(f"tau_grid must be [E, G] with E = {E}")
+    out = np.zeros(inv.shape)
+    idx = np.arange(B)
+    for e in range(E):
+        l = logits[:, e].astype(np.float64)                      # [T, B, C]
+        for g in range(inv.shape[1]):
+            z = l * inv[e, g]
+            zmax = z.max(-1)
+            a = (z[:, idx, labels] - zmax) - np.log(np.exp(z - zmax[..., None]).sum(-1))       # [T, B]
+            am = a.max(0)
+            lse = am + np.log(np.exp(a - am).sum(0))
+            out[e, g] = np.sum(-(lse - np.log(float(T))))
+    return out
+
+
+def temper_logits(logits, tau):
+    """(mean, var), float64 [E, B, C]: over the T samples of ``logits`` [T, E, B, C], the mean and the variance (ddof = 0) of
+    softmax(float32(l * inv_e)), inv_e = float32(1 / tau_e) — the fp32 product the exit head forms, the softmax in float64.  ``tau``: one
+    value per exit or a scalar."""
+    logits = np.asarray(logits)
+    E = logits.shape[1]
+    inv = np.broadcast_to(_inv32(tau).reshape(-1), (E,))
+    z = (logits.astype(np.float32) * inv.reshape(1, E, 1, 1)).astype(np.float64)
+    z -= z.max(-1, keepdims=True)
+    p = np.exp(z)
+    p /= p.sum(-1, keepdims=True)
+    return p.mean(0), p.var(0)
+
+
+def _log_grid(lo, hi, n):
+    """n log-spaced float32-representable points on [lo, hi] whose first and last are lo and hi THEMSELVES (exp(log(20)) is
+    19.999999999999996, and at_bound compares for equality)."""
+    if n < 2 or hi <= lo:
+        return np.full(max(n, 1), lo)
+    g = np.exp(np.linspace(np.log(lo), np.log(hi), n)).astype(np.float32).astype(np.float64)
+    g[0], g[-1] = lo, hi
+    return np.clip(g, lo, hi)
+
+
+def zoom_search(eval_fn, n_exits, bracket=(0.05, 20.0), grid=33, rtol=1e-4, max_rounds=8):
+    """Deterministic one-dimensional search per exit, every exit evaluated in the same call: ``eval_fn(tau [E, G] float64) -> nll [E, G]``.
+
+    Round one evaluates a log-spaced grid of ``grid`` points over the bracket plus tau = 1 exactly; each later round puts a log-spaced
+    grid on [left neighbour, right neighbour] of the best point so far (neighbours among everything evaluated for that exit, clamped at the
+    bracket).  An exit stops when hi / lo - 1 <= rtol, the search when every exit has or after ``max_rounds``.  Returned is the argmin over
+    EVERYTHING evaluated, so nll_after <= nll_before (the value at tau = 1) holds by construction.  Candidates are float32-representable
+    (what the device evaluates and what an engine stores), the bracket's ends included: the ends are rounded to float32 once, and
+    ``at_bound[e]`` says the returned point is one of them — the optimum lies outside the bracket, or the split does not determine it.
+
+    The search finds the basin of the coarse grid's minimum; the objective is NOT guaranteed unimodal in tau (a mixture over samples),
+    and a narrower basin between two coarse points is not seen.  Non-finite objective values count as +inf.
+
+    Returns dict(tau [E], nll_after [E], nll_before [E], at_bound bool [E], rounds)."""
+    E, G = int(n_exits), int(grid)
+    if G < 3:
+        raise ValueError("grid must have at least 3 points")
+    b_lo, b_hi = float(np.float32(bracket[0])), float(np.float32(bracket[1]))
+    if not (0 < b_lo < b_hi and np.isfinite(b_hi)):
+        raise ValueError(f"bracket must be 0 < lo < hi, got {bracket}")
+    taus = [np.empty(0) for _ in range(E)]
+    nlls = [np.empty(0) for _ in range(E)]
+    lo, hi = np.full(E, b_lo), np.full(E, b_hi)
+    nll_before = None
+    rounds = 0
+    while rounds < max_rounds:
+        cand = np.stack([_log_grid(lo[e], hi[e], G) for e in range(E)])
+        if rounds == 0:
+            cand = np.concatenate([cand, np.ones((E, 1))], axis=1)
+        val = np.asarray(eval_fn(cand), dtype=np.float64).reshape(cand.shape)
+        val = np.where(np.isfinite(val), val, np.inf)
+        rounds += 1
+        if nll_before is None:
+            nll_before = val[:, -1].copy()
+        done = True
+        for e in range(E):
+            t, v = np.concatenate([taus[e], cand[e]]), np.concatenate([nlls[e], val[e]])
+            order = np.argsort(t, kind="stable")
+            t, v = t[order], v[order]
+            keep = np.concatenate([[True], t[1:] != t[:-1]])      # a tau evaluated twice gave the same value twice
+            taus[e], nlls[e] = t[keep], v[keep]
+            i = int(np.argmin(nlls[e]))
+            lo[e] = min(max(taus[e][max(i - 1, 0)], b_lo), b_hi)
+            hi[e] = max(min(taus[e][min(i + 1, len(taus[e]) - 1)], b_hi), b_lo)
+            done = done and (hi[e] / lo[e] - 1.0 <= rtol)
+        if done:
+            break
+    best = [int(np.argmin(nlls[e])) for e in range(E)]
+    tau = np.array([taus[e][best[e]] for e in range(E)])
+    return dict(tau=tau, nll_after=np.array([nlls[e][best[e]] for e in range(E)]), nll_before=nll_before,
+                at_bound=np.array([t == b_lo or t == b_hi for t in tau]), rounds=rounds)
+
+
+class TemperatureScaling:
+    """Fits one temperature per exit on a labelled (validation) loader.
+
+        ts = TemperatureScaling(model, val_loader, gpu=0, mc_passes=10)
+        ts.fit()            # dict(tau, nll_before, nll_after, at_bound, rounds, n)
+        ts.apply()          # model.set_exit_temperature(tau): every engine built from the model from now on runs under it
+
+    ``fit`` walks the loader ONCE — batch k under the Philox seed ``seed + k`` and the Masksembles counter FullAnalysis' walk would use
+    (the layers' current ``cnt``, advanced by ``mc_passes`` per batch; the model's own state is left where it was) — and keeps the RAW
+    per-sample logits of the whole split on the device: N x T x E x C x 4 bytes (160 MB for the paper's 10 000 x 10 x 4 x 100).  Beyond
+    ``max_logit_bytes`` it raises ValueError (recomputing the logits per search round is out of scope).  The search is ``zoom_search``
+    with one ``MCDEngine.nll_grid`` launch per batch and round.  Raw logits do not depend on a temperature already set on the model, so a
+    fit can be repeated."""
+
+    def __init__(self, model, val_loader, gpu=0, mc_passes=10, seed=0, max_logit_bytes=1 << 30):
+        self.model, self.loader, self.gpu = model, val_loader, gpu
+        self.mc_passes, self.seed, self.max_logit_bytes = int(mc_passes), int(seed), int(max_logit_bytes)
+        self.device = get_device(gpu)
+        self.result = None
+
+    def _n_images(self):
+        loader = self.loader
+        if getattr(loader, "sampler", None) is not None and hasattr(loader.sampler, "__len__"):
+            return len(loader.sampler)
+        if hasattr(loader, "dataset"):
+            return len(loader.dataset)
+        return sum(len(b[1]) for b in loader)
+
+    def collect(self):
+        """The walk: [(logits fp32 [T, E, B, C], labels int32 [B])] per loader batch, on the device."""
+        from ..engine import model_exits
+        model, T = self.model, self.mc_passes
+        model.eval()
+        E, C = model_exits(model), int(model.out_dim)
+        need = self._n_images() * T * E * C * 4
+        if need > self.max_logit_bytes:
+            raise ValueError(f"the split's per-sample logits take {need} bytes (N x T x E x C x 4 = {self._n_images()} x {T} x {E} x {C} x 4), "
+                             f"more than max_logit_bytes = {self.max_logit_bytes}")
+        ml = model.mask_layers()
+        cnt, held, batches = (ml[0].cnt if ml else 0), 0, []
+        for k, (x, y) in enumerate(self.loader):
+            y = torch.as_tensor(y).reshape(-1).to("cpu", torch.int64)
+            if y.numel() != x.shape[0] or int(y.min()) < 0 or int(y.max()) >= C:
+                raise ValueError(f"batch {k}: labels must be one per image and lie in [0, {C})")
+            held += x.shape[0] * T * E * C * 4
+            if held > self.max_logit_bytes:            # (a loader that yields more than it announced)
+                raise ValueError(f"the split's per-sample logits exceed max_logit_bytes = {self.max_logit_bytes} ({held} bytes after batch {k})")
+            x = x.to(self.device, non_blocking=True)
+            eng = model.engine(self.device, max_batch=x.shape[0], calib=x)
+            cnt0 = (cnt + k * T) % ml[0].n if ml else 0
+            batches.append((eng.forward_samples(x, T, seed=self.seed + k, cnt0=cnt0), y.to(self.device, torch.int32)))
+        if not batches:
+            raise ValueError("the loader yielded no batch")
+        self._engine = eng
+        return batches
+
+    def fit(self, **search):
+        """Walk + search (keyword arguments go to ``zoom_search``).  Returns — and keeps in ``self.result`` — dict(tau, nll_before, nll_after,
+        at_bound [E] each, rounds, n)."""
+        from ..engine import model_exits
+        batches = self.collect()
+        eng, E = self._engine, model_exits(self.model)
+
+        def eval_fn(tau):
+            out = None
+            grid = torch.from_numpy(np.ascontiguousarray(tau, dtype=np.float32)).to(self.device)
+            for logits, y in batches:
+                out = eng.nll_grid(logits, y, grid, out=out)
+            return out.cpu().numpy()
+
+        r = zoom_search(eval_fn, E, **search)
+        r["n"] = int(sum(y.numel() for _, y in batches))
+        self.result = r
+        return r
+
+    def apply(self):
+        """``model.set_exit_temperature(tau)`` with the fitted temperatures."""
+        if self.result is None:
+            raise RuntimeError("fit() first")
+        self.model.set_exit_temperature([float(t) for t in self.result["tau"]])
+        return self.model.exit_temperature
+
+    def save(self, experiment_id):
+        """Writes ``temperature_<id>.npz`` (tau, nll_before, nll_after, at_bound, rounds, n) and returns its name."""
+        if self.result is None:
+            raise RuntimeError("fit() first")
+        name = f"temperature_{experiment_id}.npz"
+        np.savez(name, **{k: np.asarray(v) for k, v in self.result.items()})
+        return name

@@ -447,6 +447,31 @@ int bmi_finalize_checked(int64_t n, int32_t t_total, const double* S1, const dou
 int bmi_finalize_uncertainty(int32_t n_exits, int32_t batch, int32_t out_dim, int32_t t_total, const double* S1, const double* SH,
                              double* pred_entropy, double* exp_entropy, double* mutual_info, int32_t* nonfinite, bmi_stream stream);
 
+/* Temperature scaling, one scalar per exit (host only, no HIP call).  tau: host [n_exits], every entry finite and > 0, or NULL = off;
+ * all ones is off as well.  The heads multiply by inv_e = float32(1.0 / (double)tau_e): behind the bias and a site on the logits, in
+ * front of the running max, every sample's logits become z = l * inv_e in fp32; the softmax, S1, S2 and the per-sample entropy (SH) are
+ * those of z.  SL and the per-sample logits of bmi_forward_mcd_samples stay the RAW l — the logit mean does not depend on tau, and a
+ * fit that reads per-sample logits never depends on the temperature currently set.  Every bmi_forward_mcd* entry point honours it (the
+ * decision kernels of _exit / _exit_staged / _adaptive read the tempered sums); bmi_head_fused does not.  Off, the launches are the
+ * untempered kernels and every output keeps its bits.  The value is read at launch: a captured hipGraph keeps what was set at capture.
+ * BMI_ERR_INVALID: wrong count, a non-finite or non-positive entry, capacity < n_exits.  get returns ones when nothing was set. */
+int bmi_engine_set_temperature(bmi_handle h, const float* tau, int32_t n_exits);
+int bmi_engine_get_temperature(bmi_handle h, float* tau, int32_t capacity);
+
+/* The objective of a temperature fit on per-sample logits, for G candidate temperatures per exit in one launch.  logits: device fp32
+ * [T][E][B][C] (bmi_forward_mcd_samples' layout), labels: device int32 [B], every entry in [0, C) (the CALLER checks: an out-of-range
+ * label is not read but makes that image's term meaningless), tau_grid: device fp32 [E][G], every entry finite and > 0; nll: device
+ * float64 [E][G], ADDED TO (a walk over a loader accumulates).  All in float64, no fused multiply-add in the statistic:
+ *     z_tc = (double)l_tebc * (1.0 / (double)tau_eg),   a_t = z_{t,y_b} - max_c z_tc - log sum_c exp(z_tc - max_c z_tc),
+ *     nll[e][g] += sum_b -( logsumexp_t a_t - log T )
+ * — the negative log-likelihood of the T-mean softmax at temperature tau_eg, in log-sum-exp form: no clip (the reference's NLL clips
+ * at 1e-256, SA/train/results_analyzer.py:497-505), finite for any finite logits.  Bit-reproducible: the per-image terms go to
+ * `scratch` ([E][G][B] float64, bmi_nll_temperature_scratch_bytes) and a second kernel sums them over the images in a fixed order; no
+ * floating-point atomics.  BMI_ERR_NOMEM: scratch too small.  No allocation, no synchronisation. */
+size_t bmi_nll_temperature_scratch_bytes(int32_t E, int32_t B, int32_t G);
+int bmi_nll_temperature_grid(const float* logits, int32_t T, int32_t E, int32_t B, int32_t C, const int32_t* labels, const float* tau_grid,
+                             int32_t G, double* nll, void* scratch, size_t scratch_bytes, bmi_stream stream);
+
 /* Per-op-kind HIP-event timing of bmi_forward_mcd (off by default; adds two event records per
  * launch).  bmi_profile_read synchronises the recorded events and resets the accumulators. */
 int bmi_profile_enable(bmi_handle h, int32_t enable);
