@@ -1442,16 +1442,30 @@ int run_suffix(bmi_engine_s* e, const Pass& p, int N, int t0, const int* imap = 
     return run_suffix_ops(e, p, ops.size(), [&](size_t i) -> const OpInfo& { return ops[i]; }, N, t0, imap, Bc, rows);
 }
 
+// bmi_forward_mcd_ensemble: the exit-ensemble sums of the call and the caller's scratch, one chunk of per-sample logits [chunk][E][B][C]
+struct EnsembleSums {
+    double *Q1, *Q2, *QH;
+    float* scratch;
+};
+
 // The folded path: the prefix once, then samples t_begin .. t_begin+t_count-1 through the suffix, `chunk` at a time.
-int forward_folded(bmi_engine_s* e, const Pass& p, int t_begin, int t_count) {
+// ens: every chunk's heads also write their logits into ens->scratch (a runtime branch of the same kernels: S1 / S2 / SL / SH keep their
+// bits), and one launch of ensemble.hip behind them adds the chunk's samples, in sample order, to the ensemble sums.
+int forward_folded(bmi_engine_s* e, const Pass& p, int t_begin, int t_count, const EnsembleSums* ens = nullptr) {
     BmiOptionScope opt_scope(&e->opts);
     for (const OpInfo& op : e->prefix) {
         const int rc = run_op(e, p, op, p.B, 0);
         if (rc != BMI_OK) return rc;
     }
+    Pass pc = p;
     for (int t0 = t_begin; t0 < t_begin + t_count; t0 += e->chunk) {
         const int tc = std::min(e->chunk, t_begin + t_count - t0);
-        const int rc = run_suffix(e, p, tc * p.B, t0);
+        if (ens) { pc.logits = ens->scratch; pc.logits_t_begin = t0; }
+        int rc = run_suffix(e, pc, tc * p.B, t0);
+        if (rc != BMI_OK) return rc;
+        if (!ens) continue;
+        rc = launch_ensemble_moments(ens->scratch, tc, e->n_exits, p.B, e->out_dim, e->inv_tau.empty() ? nullptr : e->inv_tau.data(), ens->Q1,
+                                     ens->Q2, ens->QH, p.stream);
         if (rc != BMI_OK) return rc;
     }
     return BMI_OK;
@@ -1459,7 +1473,8 @@ int forward_folded(bmi_engine_s* e, const Pass& p, int t_begin, int t_count) {
 
 // bmi_forward_mcd, _images and _entropy (SH: null but for _entropy): their argument checks, then the folded path.
 int forward_moments(bmi_handle h, const float* x_nchw, int32_t batch, int32_t image_offset, int32_t t_begin, int32_t t_count, uint64_t seed,
-                    int32_t mask_cnt0, double* S1, double* S2, double* SL, double* SH, void* workspace, size_t workspace_bytes, bmi_stream stream) {
+                    int32_t mask_cnt0, double* S1, double* S2, double* SL, double* SH, void* workspace, size_t workspace_bytes, bmi_stream stream,
+                    const EnsembleSums* ens = nullptr) {
     const int rco = bmi_image_offset_ok(h, image_offset);      // (a null handle: BMI_ERR_INVALID; image 0 always passes)
     if (rco != BMI_OK) return rco;
     if (!x_nchw || !S1 || !S2 || !SL || !workspace) return BMI_ERR_INVALID;
@@ -1469,7 +1484,7 @@ int forward_moments(bmi_handle h, const float* x_nchw, int32_t batch, int32_t im
     Pass p{x_nchw, (char*)workspace, (hipStream_t)stream, batch, seed, mask_cnt0};
     p.b0 = image_offset;
     p.S1 = S1; p.S2 = S2; p.SL = SL; p.SH = SH;
-    return forward_folded(h, p, t_begin, t_count);
+    return forward_folded(h, p, t_begin, t_count, ens);
 }
 
 }  // namespace
@@ -1514,6 +1529,23 @@ int bmi_forward_mcd_entropy(bmi_handle h, const float* x_nchw, int32_t batch, in
     if (!h || !SH) return BMI_ERR_INVALID;
     return forward_moments(h, x_nchw, batch, image_offset, t_begin, t_count, seed, mask_cnt0, S1, S2, SL, SH, workspace,
                            workspace_bytes, stream);
+}
+
+size_t bmi_ensemble_scratch_bytes(bmi_handle h, int32_t batch) {
+    if (!h || h->max_batch == 0 || batch < 1 || batch > h->max_batch) return 0;
+    return (size_t)h->chunk * h->n_exits * batch * h->out_dim * sizeof(float);
+}
+
+int bmi_forward_mcd_ensemble(bmi_handle h, const float* x_nchw, int32_t batch, int32_t image_offset, int32_t t_begin, int32_t t_count,
+                             uint64_t seed, int32_t mask_cnt0, double* S1, double* S2, double* SL, double* SH, double* Q1, double* Q2,
+                             double* QH, void* scratch, size_t scratch_bytes, void* workspace, size_t workspace_bytes, bmi_stream stream) {
+    if (!h || !SH || !Q1 || !Q2 || !QH || !scratch) return BMI_ERR_INVALID;
+    if (!ensemble_takes(h->n_exits, h->out_dim)) return BMI_ERR_UNSUPPORTED;
+    if (h->max_batch == 0 || batch < 1 || batch > h->max_batch) return BMI_ERR_INVALID;
+    if (scratch_bytes < bmi_ensemble_scratch_bytes(h, batch)) return BMI_ERR_NOMEM;
+    const EnsembleSums ens{Q1, Q2, QH, (float*)scratch};
+    return forward_moments(h, x_nchw, batch, image_offset, t_begin, t_count, seed, mask_cnt0, S1, S2, SL, SH, workspace, workspace_bytes, stream,
+                           &ens);
 }
 
 int bmi_forward_mcd_samples(bmi_handle h, const float* x_nchw, int32_t batch, int32_t t_begin, int32_t t_count, uint64_t seed,
@@ -1763,6 +1795,31 @@ int bmi_finalize_uncertainty(int32_t n_exits, int32_t batch, int32_t out_dim, in
     if ((int64_t)n_exits * batch > INT32_MAX) return BMI_ERR_UNSUPPORTED;
     return launch_finalize_uncertainty(n_exits * batch, out_dim, t_total, S1, SH, pred_entropy, exp_entropy, mutual_info, nonfinite,
                                        (hipStream_t)stream);
+}
+
+int bmi_finalize_ensemble(int32_t n_exits, int32_t batch, int32_t out_dim, int32_t t_total, const double* Q1, const double* Q2, const double* QH,
+                          double* ens_mean, double* ens_var, double* pred_entropy, double* exp_entropy, double* mutual_info, int32_t* nonfinite,
+                          bmi_stream stream) {
+    if (!Q1 || !Q2 || !QH || !ens_mean || !ens_var || !pred_entropy || !exp_entropy || !mutual_info || n_exits < 1 || batch < 1 || out_dim < 1 ||
+        t_total < 1)
+        return BMI_ERR_INVALID;
+    if ((int64_t)n_exits * batch > INT32_MAX) return BMI_ERR_UNSUPPORTED;
+    return launch_finalize_ensemble(n_exits * batch, out_dim, t_total, Q1, Q2, QH, ens_mean, ens_var, pred_entropy, exp_entropy, mutual_info,
+                                    nonfinite, (hipStream_t)stream);
+}
+
+int bmi_ensemble_moments(const float* logits, int32_t T, int32_t E, int32_t B, int32_t C, const float* tau, double* Q1, double* Q2, double* QH,
+                         bmi_stream stream) {
+    if (!logits || !Q1 || !Q2 || !QH || T < 1 || E < 1 || B < 1 || C < 1) return BMI_ERR_INVALID;
+    if (!ensemble_takes(E, C)) return BMI_ERR_UNSUPPORTED;
+    float inv[BMI_ENS_MAX_EXITS];
+    if (tau)
+        for (int e = 0; e < E; ++e) {
+            if (!(tau[e] > 0.f) || !std::isfinite(tau[e])) return BMI_ERR_INVALID;
+            inv[e] = (float)(1.0 / (double)tau[e]);       // (bmi_engine_set_temperature's rounding)
+            if (!(inv[e] > 0.f) || !std::isfinite(inv[e])) return BMI_ERR_INVALID;
+        }
+    return launch_ensemble_moments(logits, T, E, B, C, tau ? inv : nullptr, Q1, Q2, QH, (hipStream_t)stream);
 }
 
 size_t bmi_nll_temperature_scratch_bytes(int32_t E, int32_t B, int32_t G) {

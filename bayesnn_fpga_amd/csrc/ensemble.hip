@@ -1,0 +1,175 @@
+// The exit ensemble as a predictor of its own (bmi_ensemble_moments, bmi_forward_mcd_ensemble, bmi_finalize_ensemble): the reference's
+// cumulative mean of the exits' softmax outputs, formed PER STOCHASTIC PASS (SA/train/loss/base_classes.py:41,54,58: `ensemble +=
+// softmax(logits)` inside one forward) and then treated like any other Monte-Carlo predictor.  On per-sample logits [t][E][B][C]
+// (bmi_forward_mcd_samples' layout), all in float64 and without fused multiply-adds:
+//     z_te = (double) fl32(l_te * inv_e)             inv_e = float32(1 / tau_e), the ONE rounded fp32 product of the tempered head (1: off)
+//     p_te = softmax_c(z_te)                         max-subtracted
+//     q_te = (p_t0 + ... + p_te) / (e + 1)           summed in exit order, divided once
+//     Q1[e][b][c] += q      Q2[e][b][c] += q * q      QH[e][b] += -sum_c q log q   (0 log 0 = 0, class order)
+// The exits of one pass share the trunk's dropout draw, so the second moment of q holds cross-exit terms that no per-exit sum contains:
+// it has to be formed per sample (train/uncertainty.py: decompose_ensemble_logits is the host restatement).
+//
+//   workgroup = one image, 256 threads; the samples of the launch go through LDS in chunks of TS samples (what fits), in sample order.
+//   phase A     a group of L = min(64, pow2 >= C) lanes per softmax row (sample, exit): running max in fp32 (the logits ARE fp32), the
+//               float64 exponentials to LDS ([row][C | 1]: an odd stride, lanes of phase C walk different rows at one class), their sum
+//               by shuffle butterfly inside the group — a fixed tree, the same for every row wherever the row sits in a launch.
+//   phase B     a thread per (sample, class) walks the exits: p = exp / sum, running sum, q = sum / (e + 1) over the exponential in
+//               place, q log q beside it.
+//   phase C     a thread per row adds its q log q in class order; then a thread per (exit, class) LOADS the running Q1 / Q2, adds the
+//               chunk's samples in sample order and stores them, a thread per exit does the same for QH.  No floating-point atomics, and
+//               the sums are the same bits however the samples were split into launches: every launch continues the one running sum.
+#include <algorithm>
+#include <cmath>
+
+#include "kernels.h"
+
+#define ENS_THREADS 256
+#define ENS_SLAB 3456            // float64 entries of each of the two staged arrays (27 KB each)
+#define ENS_ROWS 512             // (sample, exit) rows per staged chunk, at most
+
+struct EnsTau { float inv[BMI_ENS_MAX_EXITS]; };
+
+__global__ __launch_bounds__(ENS_THREADS) void ensemble_moments_kernel(const float* __restrict__ logits, int T, int E, int B, int C, int CS, int TS,
+                                                                       int L, EnsTau tau, double* __restrict__ Q1, double* __restrict__ Q2,
+                                                                       double* __restrict__ QH) {
+#pragma clang fp contract(off)
+    __shared__ double pq[ENS_SLAB];                      // [row][CS], row = tl * E + e: exp(z - max), then q
+    __shared__ double ql[ENS_SLAB];                      // q log q
+    __shared__ double row_sum[ENS_ROWS], row_h[ENS_ROWS];
+    __shared__ float inv_s[BMI_ENS_MAX_EXITS];
+    const int tid = threadIdx.x;
+    const int b = blockIdx.x;
+    const int lane = tid & (L - 1), grp = tid / L, ngrp = ENS_THREADS / L;
+    if (tid < E) inv_s[tid] = tau.inv[tid];
+    for (int t0 = 0; t0 < T; t0 += TS) {
+        const int tn = min(TS, T - t0);
+        const int rows = tn * E;                         // <= ENS_ROWS, rows * CS <= ENS_SLAB (the launcher's TS)
+        __syncthreads();                                 // the previous chunk's readers are done (first chunk: inv_s is written)
+        for (int r0 = 0; r0 < rows; r0 += ngrp) {        // (every lane walks every step: the shuffles below need whole groups)
+            const int r = r0 + grp;
+            const bool live = r < rows;
+            const int tl = live ? r / E : 0, e = live ? r - tl * E : 0;
+            const float* src = logits + (((size_t)(t0 + tl) * E + e) * B + b) * C;
+            const float inv = inv_s[e];
+            float mx = -INFINITY;
+            if (live)
+                for (int c = lane; c < C; c += L) mx = fmaxf(mx, src[c] * inv);
+            for (int m = L >> 1; m >= 1; m >>= 1) mx = fmaxf(mx, __shfl_xor(mx, m));
+            double s = 0.0;
+            if (live)
+                for (int c = lane; c < C; c += L) {
+                    const double ex = exp((double)(src[c] * inv) - (double)mx);
+                    pq[r * CS + c] = ex;
+                    s += ex;
+                }
+            for (int m = L >> 1; m >= 1; m >>= 1) s += __shfl_xor(s, m);
+            if (live && lane == 0) row_sum[r] = s;
+        }
+        __syncthreads();
+        for (int i = tid; i < tn * C; i += ENS_THREADS) {
+            const int tl = i / C, c = i - tl * C;
+            double acc = 0.0;
+            for (int e = 0; e < E; ++e) {
+                const int r = tl * E + e;
+                acc += pq[r * CS + c] / row_sum[r];
+                const double q = acc / (double)(e + 1);
+                pq[r * CS + c] = q;
+                ql[r * CS + c] = q > 0.0 ? q * log(q) : (q == q ? 0.0 : q);      // (a NaN stays a NaN)
+            }
+        }
+        __syncthreads();
+        for (int r = tid; r < rows; r += ENS_THREADS) {
+            const double* row = ql + r * CS;
+            double h = 0.0;
+            for (int c = 0; c < C; ++c) h += row[c];
+            row_h[r] = -h;
+        }
+        __syncthreads();
+        for (int i = tid; i < E * C + E; i += ENS_THREADS) {
+            if (i < E * C) {
+                const int e = i / C, c = i - e * C;
+                const size_t o = ((size_t)e * B + b) * C + c;
+                double s1 = Q1[o], s2 = Q2[o];
+                for (int tl = 0; tl < tn; ++tl) {
+                    const double q = pq[(tl * E + e) * CS + c];
+                    s1 += q;
+                    s2 += q * q;
+                }
+                Q1[o] = s1;
+                Q2[o] = s2;
+            } else {
+                const int e = i - E * C;
+                double sh = QH[(size_t)e * B + b];
+                for (int tl = 0; tl < tn; ++tl) sh += row_h[tl * E + e];
+                QH[(size_t)e * B + b] = sh;
+            }
+        }
+    }
+}
+
+bool ensemble_takes(int E, int C) {
+    return E >= 1 && C >= 1 && E <= BMI_ENS_MAX_EXITS && C <= BMI_ENS_MAX_CLASSES && E * (C | 1) <= ENS_SLAB;
+}
+
+int launch_ensemble_moments(const float* logits, int T, int E, int B, int C, const float* inv_tau, double* Q1, double* Q2, double* QH,
+                            hipStream_t s) {
+    if (T < 1 || B < 1) return BMI_ERR_INVALID;
+    if (!ensemble_takes(E, C)) return BMI_ERR_UNSUPPORTED;
+    const int CS = C | 1;                                // odd row stride
+    const int TS = std::min(ENS_SLAB / (E * CS), ENS_ROWS / E);      // >= 1 (ensemble_takes)
+    int L = 1;
+    while (L < C && L < 64) L <<= 1;
+    EnsTau tau;
+    for (int e = 0; e < BMI_ENS_MAX_EXITS; ++e) tau.inv[e] = (inv_tau && e < E) ? inv_tau[e] : 1.f;
+    hipLaunchKernelGGL(ensemble_moments_kernel, dim3((unsigned)B), dim3(ENS_THREADS), 0, s, logits, T, E, B, C, CS, TS, L, tau, Q1, Q2, QH);
+    BMI_CHECK_LAUNCH();
+    return BMI_OK;
+}
+
+// One wave per (exit, image) row: mean = Q1 / T, var = max(Q2 / T - mean^2, 0) (ddof 0, a NaN stays a NaN), the entropy of the mean by
+// float64 wavefront shuffle like finalize_uncertainty_kernel, expected entropy QH / T, mutual information clamped at 0.
+__global__ __launch_bounds__(256) void finalize_ensemble_kernel(int rows, int C, double t, const double* __restrict__ Q1,
+                                                                const double* __restrict__ Q2, const double* __restrict__ QH,
+                                                                double* __restrict__ mean, double* __restrict__ var, double* __restrict__ pred,
+                                                                double* __restrict__ expd, double* __restrict__ mi, int* nonfinite) {
+#pragma clang fp contract(off)
+    const int row = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6), lane = threadIdx.x & 63;
+    if (row >= rows) return;                       // (wave-uniform)
+    double h = 0.0;
+    int bad = 0;
+    for (int c = lane; c < C; c += 64) {
+        const size_t o = (size_t)row * C + c;
+        const double s1 = Q1[o], s2 = Q2[o];
+        const double m = s1 / t;
+        const double v = s2 / t - m * m;
+        mean[o] = m;
+        var[o] = v > 0 ? v : (v == v ? 0 : v);
+        if (m > 0.0) h -= m * log(m);
+        const bool nf = !(__builtin_isfinite(s1) && __builtin_isfinite(s2));
+        bad += nf;
+        if (!__builtin_isfinite(s1)) h = s1 - s1;   // NaN: the row's entropy is not a number either
+    }
+    const double sh = QH[row];
+    if (lane == 0) bad += !__builtin_isfinite(sh);
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        h += __shfl_xor(h, m);
+        bad += __shfl_xor(bad, m);
+    }
+    if (lane == 0) {
+        const double e = sh / t, d = h - e;
+        pred[row] = h;
+        expd[row] = e;
+        mi[row] = d > 0 ? d : (d == d ? 0.0 : d);
+        if (nonfinite && bad) atomicAdd(nonfinite, bad);
+    }
+}
+
+int launch_finalize_ensemble(int n_rows, int C, int t_total, const double* Q1, const double* Q2, const double* QH, double* mean, double* var,
+                             double* pred, double* expd, double* mi, int* nonfinite, hipStream_t s) {
+    if (n_rows <= 0 || C <= 0 || t_total <= 0) return BMI_ERR_INVALID;
+    hipLaunchKernelGGL(finalize_ensemble_kernel, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, s, n_rows, C, (double)t_total, Q1, Q2, QH, mean,
+                       var, pred, expd, mi, nonfinite);
+    BMI_CHECK_LAUNCH();
+    return BMI_OK;
+}

@@ -182,6 +182,16 @@ int launch_finalize_uncertainty(int n_rows, int C, int t_total, const double* S1
 // scratch: [E][G][B] float64 per-image terms
 int launch_nll_temperature_grid(const float* logits, int T, int E, int B, int C, const int* labels, const float* tau_grid, int G, double* nll,
                                 double* scratch, hipStream_t s);
+// ensemble.hip (bmi_ensemble_moments): Q1 / Q2 [E][B][C] and QH [E][B] += the moments and the entropy of the per-sample exit ensembles
+// q_te = mean_{i<=e} softmax(fl32(l_ti * inv_tau[i])) of logits [T][E][B][C], in sample order onto the running sums; inv_tau: host [E] or null
+#define BMI_ENS_MAX_EXITS 32
+#define BMI_ENS_MAX_CLASSES 128
+bool ensemble_takes(int E, int C);
+int launch_ensemble_moments(const float* logits, int T, int E, int B, int C, const float* inv_tau, double* Q1, double* Q2, double* QH,
+                            hipStream_t s);
+// per (exit, image): mean / var of Q1 / Q2, the entropy of the mean, QH / T and their difference (bmi_finalize_ensemble)
+int launch_finalize_ensemble(int n_rows, int C, int t_total, const double* Q1, const double* Q2, const double* QH, double* mean, double* var,
+                             double* pred, double* expd, double* mi, int* nonfinite, hipStream_t s);
 int launch_philox_mask(uint8_t* keep, int64_t n, uint64_t seed, int site, int t, float p, hipStream_t s);
 // planar_w > 0: the bits in the lazy site's planar layout (rows of planar_w pixels; 2-bit sites, c % 64 == 0)
 int launch_mask_bits(uint8_t* bits, int n, int hw, int c, const SiteArgs& site, int batch, int t0, hipStream_t s, int planar_w = 0);

@@ -495,6 +495,10 @@ class MCDEngine(CompiledGraph):
         # (BatchesInFlight.predict_graphed) would otherwise allocate it from the graph's private pool and re-zero it on every replay
         self._nonfinite = torch.zeros(1, dtype=torch.int32, device=device)
 
+    def close(self):
+        self.__dict__.pop("_ens_scratch", None)      # (accumulate_ensemble's chunk of per-sample logits)
+        super().close()
+
     # ---- the path ------------------------------------------------------------------------------
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
@@ -617,6 +621,102 @@ class MCDEngine(CompiledGraph):
         S, H = self.new_uncertainty_sums(x.shape[0])
         self.accumulate_uncertainty(x, S, H, t_begin, T, seed, cnt0)
         return self.finalize_uncertainty(S, H, T)
+
+    # ---- the exit ensemble as a predictor (bmi_forward_mcd_ensemble / bmi_finalize_ensemble / bmi_ensemble_moments) -----------------
+    def new_ensemble_sums(self, batch):
+        """Zeroed float64 accumulators of ``accumulate_ensemble``: S [3, E, B, C] and H [E, B] (``new_uncertainty_sums``), Q [2, E, B, C]
+        (the sums of the per-sample exit ensembles q and of q^2) and QH [E, B] (the sums of their entropies) — views of ONE allocation
+        (``S._base``), so that a sharded caller all-reduces all four in one call: every one of them is additive over samples."""
+        E, Cd = self.n_exits, self.out_dim
+        ns, nh, nq = 3 * E * batch * Cd, E * batch, 2 * E * batch * Cd
+        buf = torch.zeros(ns + nh + nq + nh, dtype=torch.float64, device=self.device)
+        return (buf[:ns].view(3, E, batch, Cd), buf[ns:ns + nh].view(E, batch), buf[ns + nh:ns + nh + nq].view(2, E, batch, Cd),
+                buf[ns + nh + nq:].view(E, batch))
+
+    def _ensemble_scratch(self, batch):
+        """One chunk of per-sample logits (bmi_ensemble_scratch_bytes), allocated once per engine — for ``max_batch`` — on first use."""
+        need = int(self.lib.bmi_ensemble_scratch_bytes(self.handle, int(batch)))
+        scratch = self.__dict__.get("_ens_scratch")
+        if scratch is None:
+            full = int(self.lib.bmi_ensemble_scratch_bytes(self.handle, self.max_batch))
+            scratch = self.__dict__["_ens_scratch"] = torch.empty(max(full, need, 1), dtype=torch.uint8, device=self.device)
+        return scratch, need
+
+    def accumulate_ensemble(self, x, S, H, Q, QH, t_begin, t_count, seed=0, cnt0=0, image_offset=0):
+        """``accumulate_uncertainty`` (the same bits in S and H) that also adds, per sample, the exit ensembles q_e = mean of the softmax
+        outputs of exits 0..e of THAT sample into Q[0], their squares into Q[1] and their entropies into QH: the heads of a chunk leave
+        their logits in the engine's scratch and one kernel behind them (csrc/ensemble.hip) adds the chunk in sample order onto the
+        running sums — the same bits however the samples are split into calls.  The members are the tempered distributions when a
+        temperature is set (``set_temperature``)."""
+        x = self._check_x(x)
+        B = x.shape[0]
+        E, Cd = self.n_exits, self.out_dim
+        for buf, shape, what in ((S, (3, E, B, Cd), "moment buffer S"), (H, (E, B), "entropy buffer H"), (Q, (2, E, B, Cd), "ensemble buffer Q"),
+                                 (QH, (E, B), "ensemble entropy buffer QH")):
+            if tuple(buf.shape) != shape or buf.dtype != torch.float64 or not buf.is_contiguous() or buf.device != self.device:
+                raise ValueError(f"{what} must be contiguous float64 {list(shape)} on {self.device}")
+        scratch, need = self._ensemble_scratch(B)
+        with torch.cuda.device(self.device):
+            rc = self.lib.bmi_forward_mcd_ensemble(self.handle, x.data_ptr(), B, int(image_offset), int(t_begin), int(t_count),
+                                                   int(seed) & 0xFFFFFFFFFFFFFFFF, int(cnt0), S[0].data_ptr(), S[1].data_ptr(), S[2].data_ptr(),
+                                                   H.data_ptr(), Q[0].data_ptr(), Q[1].data_ptr(), QH.data_ptr(), scratch.data_ptr(),
+                                                   scratch.numel(), self.workspace.data_ptr(), self.workspace_bytes, self._stream())
+        _lib.check(rc, "bmi_forward_mcd_ensemble")
+        return S, H, Q, QH
+
+    def _finalize_ensemble_sums(self, Q, QH, t_total):
+        _, E, B, Cd = Q.shape
+        if Q.shape[0] != 2 or tuple(QH.shape) != (E, B) or Q.dtype != torch.float64 or QH.dtype != torch.float64 or \
+                not Q.is_contiguous() or not QH.is_contiguous():
+            raise ValueError("ensemble buffers must be contiguous float64 Q [2, E, B, C] and QH [E, B]")
+        mv = torch.empty(2, E, B, Cd, dtype=torch.float64, device=Q.device)
+        ent = torch.empty(3, E, B, dtype=torch.float64, device=Q.device)
+        with torch.cuda.device(self.device):
+            rc = self.lib.bmi_finalize_ensemble(E, B, Cd, int(t_total), Q[0].data_ptr(), Q[1].data_ptr(), QH.data_ptr(), mv[0].data_ptr(),
+                                                mv[1].data_ptr(), ent[0].data_ptr(), ent[1].data_ptr(), ent[2].data_ptr(),
+                                                self._nonfinite.data_ptr(), self._stream())
+        _lib.check(rc, "bmi_finalize_ensemble")
+        return dict(ens_mean=mv[0], ens_var=mv[1], ens_pred_entropy=ent[0], ens_exp_entropy=ent[1], ens_mutual_info=ent[2])
+
+    def finalize_ensemble(self, S, H, Q, QH, t_total):
+        """``finalize_uncertainty``'s dict plus the read-out of the exit ensembles, float64: ``ens_mean`` and ``ens_var`` (ddof 0) [E, B, C],
+        ``ens_pred_entropy`` H[ens_mean], ``ens_exp_entropy`` E_t H[q_t] and ``ens_mutual_info`` (clamped at 0) [E, B]; row 0 is exit 0
+        itself.  Non-finite sums count into the engine's counter (``check_finite``)."""
+        r = self.finalize_uncertainty(S, H, t_total)
+        r.update(self._finalize_ensemble_sums(Q, QH, t_total))
+        return r
+
+    def predict_ensemble(self, x, T, seed=0, t_begin=0, cnt0=0):
+        """``predict_uncertainty`` plus the five ``ens_*`` entries of ``finalize_ensemble``."""
+        S, H, Q, QH = self.new_ensemble_sums(x.shape[0])
+        self.accumulate_ensemble(x, S, H, Q, QH, t_begin, T, seed, cnt0)
+        return self.finalize_ensemble(S, H, Q, QH, T)
+
+    def ensemble_moments(self, logits, tau=None, out=None, t_before=0):
+        """The exit-ensemble read-out of per-sample logits the caller holds (bmi_ensemble_moments + bmi_finalize_ensemble): ``logits`` fp32
+        [T, E, B, C] on the engine's device (``forward_samples``), ``tau`` None, a scalar or E temperatures (independent of the one set on
+        this engine).  Returns the five ``ens_*`` entries of ``finalize_ensemble`` plus the sums ``Q`` [2, E, B, C] and ``QH`` [E, B];
+        ``out=(Q, QH)`` ADDS into the sums of earlier calls that held ``t_before`` samples — the same bits as one call on all of them —
+        and the results describe all ``t_before + T``.  ``train.uncertainty.decompose_ensemble_logits`` is the host restatement."""
+        if logits.dim() != 4 or logits.dtype != torch.float32 or not logits.is_contiguous() or logits.device != self.device:
+            raise ValueError(f"logits must be contiguous float32 [T, E, B, C] on {self.device}")
+        T, E, B, Cd = logits.shape
+        tau = check_temperature(tau, E)
+        if out is None:
+            Q = torch.zeros(2, E, B, Cd, dtype=torch.float64, device=self.device)
+            QH = torch.zeros(E, B, dtype=torch.float64, device=self.device)
+        else:
+            Q, QH = out
+            if tuple(Q.shape) != (2, E, B, Cd) or tuple(QH.shape) != (E, B) or Q.dtype != torch.float64 or QH.dtype != torch.float64 or \
+                    not Q.is_contiguous() or not QH.is_contiguous() or Q.device != self.device or QH.device != self.device:
+                raise ValueError("out must be contiguous float64 (Q [2, E, B, C], QH [E, B]) on the engine's device")
+        with torch.cuda.device(self.device):
+            rc = self.lib.bmi_ensemble_moments(logits.data_ptr(), T, E, B, Cd, None if tau is None else (C.c_float * E)(*tau), Q[0].data_ptr(),
+                                               Q[1].data_ptr(), QH.data_ptr(), self._stream())
+        _lib.check(rc, "bmi_ensemble_moments")
+        r = self._finalize_ensemble_sums(Q, QH, int(t_before) + T)
+        r.update(Q=Q, QH=QH)
+        return r
 
     def predict_with_exit(self, x, T, threshold, seed=0, cnt0=0, first_exit=1):
         """Confidence-threshold early exiting on the device (bmi_forward_mcd_exit): an image leaves after the first exit

@@ -38,6 +38,48 @@ def decompose_logits(logits):
     return dict(mean=mean, pred_entropy=pred_entropy, exp_entropy=exp_entropy, mutual_info=np.maximum(pred_entropy - exp_entropy, 0.0))
 
 
+def decompose_ensemble_logits(logits, tau=None):
+    """The exit ensembles as predictors, from per-pass logits [T, E, B, C] (``MCDEngine.forward_samples``), float64 on the host: the
+    definition csrc/ensemble.hip implements on the device (``MCDEngine.predict_ensemble`` / ``ensemble_moments``).  Per pass t the members
+    are p_te = softmax(z_te), z = the fp32 logit, or with ``tau`` (a scalar or E temperatures) the tempered head's ONE rounded fp32 product
+    float32(l) * float32(1 / tau_e); the ensemble of exits 0..e is q_te = (p_t0 + ... + p_te) / (e + 1) — the reference's per-pass
+    ``ensemble += softmax(logits)`` (train/loss/base_classes.py:41,54,58).  Returns dict(mean, var [E, B, C] — var with ddof 0, clamped at
+    0 —, pred_entropy H[mean], exp_entropy E_t H[q_t], mutual_info [E, B] — clamped at 0), entropies in nats.  Row 0 is exit 0 itself.
+    The exits of one pass share the trunk's draw: ``var`` is NOT sum_i var_i / (e + 1)^2."""
+    l = np.asarray(logits, dtype=np.float32)
+    if l.ndim != 4:
+        raise ValueError("logits must be [T, E, B, C]")
+    T, E = l.shape[:2]
+    if tau is not None:
+        t32 = np.asarray(tau, dtype=np.float64).astype(np.float32)
+        t32 = np.repeat(t32.reshape(-1), E) if t32.ndim == 0 else t32.reshape(-1)
+        if t32.size != E:
+            raise ValueError(f"tau: expected one value per exit ({E}), got {t32.size}")
+        inv = (1.0 / t32.astype(np.float64)).astype(np.float32)
+        l = (l * inv[None, :, None, None]).astype(np.float32)
+    z = l.astype(np.float64)
+    z = z - z.max(axis=-1, keepdims=True)
+    ex = np.exp(z)
+    p = ex / ex.sum(axis=-1, keepdims=True)
+    q1 = np.zeros(l.shape[1:], dtype=np.float64)
+    q2 = np.zeros(l.shape[1:], dtype=np.float64)
+    qh = np.zeros(l.shape[1:3], dtype=np.float64)
+    for t in range(T):                          # in sample order onto the running sums, like the device
+        acc = np.zeros(l.shape[2:], dtype=np.float64)
+        for e in range(E):
+            acc = acc + p[t, e]
+            q = acc / (e + 1)
+            q1[e] += q
+            q2[e] += q * q
+            qh[e] += entropy_rows(q)
+    mean = q1 / T
+    var = np.maximum(q2 / T - mean * mean, 0.0)
+    pred_entropy = entropy_rows(mean)
+    exp_entropy = qh / T
+    return dict(mean=mean, var=var, pred_entropy=pred_entropy, exp_entropy=exp_entropy,
+                mutual_info=np.maximum(pred_entropy - exp_entropy, 0.0))
+
+
 class UncertaintyAnalysis:
     """One walk of ``loader`` (batches ``(x, y, ...)``) with ``mc_passes`` stochastic passes per batch.
 
@@ -49,10 +91,16 @@ class UncertaintyAnalysis:
 
     Per exit, float64: ``mean`` [E, N, C], ``pred_entropy`` / ``exp_entropy`` / ``mutual_info`` [E, N]; ``ape`` [E] (the reference's
     aPE of the T-mean probabilities), ``mean_mi`` [E], ``mean_exp_entropy`` [E]; ``ensemble_pred_entropy`` [E, N] and ``ensemble_ape``
-    [E]: the same for the reference's cumulative exit ensembles (the mean of exits 0..e; their mutual information would need
-    per-sample ensemble probabilities and is not computed)."""
+    [E]: the same for the reference's cumulative exit ensembles (the mean of exits 0..e).
 
-    def __init__(self, model, loader, gpu=0, mc_passes=10, seed=0, group=None):
+    ``ensemble=True``: the walk treats every exit ensemble as a predictor of its own (``MCDEngine.predict_ensemble``: the per-sample
+    ensembles are accumulated on the device) and also fills ``ensemble_var`` [E, N, C], ``ensemble_exp_entropy`` and
+    ``ensemble_mutual_info`` [E, N], ``ensemble_mean_mi`` [E]; ``summary()`` and ``save()`` gain those keys.  ``ensemble_pred_entropy`` is then the
+    device's entropy of the float64 ensemble mean (within 1e-5 of the default walk's, whose members are the heads' fp32 softmax), so that
+    ensemble_mutual_info = ensemble_pred_entropy - ensemble_exp_entropy; everything else keeps its numbers.  Not under a sharded walk (more than one rank): NotImplementedError."""
+
+    def __init__(self, model, loader, gpu=0, mc_passes=10, seed=0, group=None, ensemble=False):
+        self.ensemble = bool(ensemble)
         self.model = model
         self.loader = loader
         self.device = get_device(gpu)
@@ -79,6 +127,12 @@ class UncertaintyAnalysis:
     def _run(self):
         from ..sharding import predict_sharded_uncertainty
         world = self._ranks()[1]
+        if self.ensemble and world > 1:
+            raise NotImplementedError("UncertaintyAnalysis(ensemble=True) under a sharded walk: the ensemble sums are not part of "
+                                      "sharding.accumulate_partitioned's all-reduce")
+        names = ("mean", "pred_entropy", "exp_entropy", "mutual_info")
+        if self.ensemble:
+            names += ("ens_var", "ens_pred_entropy", "ens_exp_entropy", "ens_mutual_info")
         parts, labels, eng = [], [], None
         for k, batch in enumerate(self.loader):
             b_x = batch[0].to(self.device)
@@ -89,9 +143,11 @@ class UncertaintyAnalysis:
             self.model.advance(T)
             if world > 1:
                 r = predict_sharded_uncertainty(eng, b_x, T, seed, cnt0, group=self.group)
+            elif self.ensemble:
+                r = eng.predict_ensemble(b_x, T, seed, cnt0=cnt0)
             else:
                 r = eng.predict_uncertainty(b_x, T, seed, cnt0=cnt0)
-            parts.append({n: r[n].cpu().numpy() for n in ("mean", "pred_entropy", "exp_entropy", "mutual_info")})
+            parts.append({n: r[n].cpu().numpy() for n in names})
             eng.check_finite()
             labels.append(np.asarray(batch[1]).astype(np.int64))
         if not parts:
@@ -107,18 +163,33 @@ class UncertaintyAnalysis:
         ens = exit_ensembles(self.mean)
         self.ensemble_pred_entropy = entropy_rows(ens)
         self.ensemble_ape = np.array([average_predictive_entropy(m) for m in ens])
+        if self.ensemble:
+            # the device's H[ens_mean] (float64 softmax members; the line above: the heads' fp32 ones): ensemble_mutual_info is ITS difference
+            self.ensemble_pred_entropy = np.concatenate([p["ens_pred_entropy"] for p in parts], axis=1)
+            self.ensemble_var = np.concatenate([p["ens_var"] for p in parts], axis=1)
+            self.ensemble_exp_entropy = np.concatenate([p["ens_exp_entropy"] for p in parts], axis=1)
+            self.ensemble_mutual_info = np.concatenate([p["ens_mutual_info"] for p in parts], axis=1)
+            self.ensemble_mean_mi = self.ensemble_mutual_info.mean(axis=1)
 
     def summary(self):
-        """Per exit: dict(ape, mean_mi, mean_exp_entropy, ensemble_ape)."""
-        return [dict(ape=float(self.ape[e]), mean_mi=float(self.mean_mi[e]), mean_exp_entropy=float(self.mean_exp_entropy[e]),
-                     ensemble_ape=float(self.ensemble_ape[e])) for e in range(len(self.ape))]
+        """Per exit: dict(ape, mean_mi, mean_exp_entropy, ensemble_ape), and ensemble_mean_mi of an ``ensemble=True`` walk."""
+        out = [dict(ape=float(self.ape[e]), mean_mi=float(self.mean_mi[e]), mean_exp_entropy=float(self.mean_exp_entropy[e]),
+                    ensemble_ape=float(self.ensemble_ape[e])) for e in range(len(self.ape))]
+        if self.ensemble:
+            for e, d in enumerate(out):
+                d["ensemble_mean_mi"] = float(self.ensemble_mean_mi[e])
+        return out
 
     def save(self, experiment_id):
         """``test_uncertainty_<experiment_id>.npz`` (rank 0 of a sharded walk only); returns the file name, or None on the other ranks."""
         if not self.is_writer():
             return None
         name = f"test_uncertainty_{experiment_id}.npz"
+        extra = {}
+        if self.ensemble:
+            extra = dict(ensemble_var=self.ensemble_var, ensemble_exp_entropy=self.ensemble_exp_entropy,
+                         ensemble_mutual_info=self.ensemble_mutual_info, ensemble_mean_mi=self.ensemble_mean_mi)
         np.savez(name, mean=self.mean, pred_entropy=self.pred_entropy, exp_entropy=self.exp_entropy, mutual_info=self.mutual_info,
                  labels=self.labels, ape=self.ape, mean_mi=self.mean_mi, mean_exp_entropy=self.mean_exp_entropy,
-                 ensemble_pred_entropy=self.ensemble_pred_entropy, ensemble_ape=self.ensemble_ape)
+                 ensemble_pred_entropy=self.ensemble_pred_entropy, ensemble_ape=self.ensemble_ape, **extra)
         return name

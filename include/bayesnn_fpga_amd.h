@@ -334,6 +334,45 @@ int bmi_forward_mcd_entropy(bmi_handle h, const float* x_nchw, int32_t batch, in
                             int32_t t_count, uint64_t seed, int32_t mask_cnt0, double* S1, double* S2, double* SL, double* SH,
                             void* workspace, size_t workspace_bytes, bmi_stream stream);
 
+/* The exit ensemble as a predictor of its own.  What the paper ships is the mean of the softmax outputs of exits 0..e; the reference forms
+ * it from the T-mean probabilities (FullAnalysis._get_output, SA/train/results_analyzer.py:260-269: `ensemble_output_sm`) and per
+ * stochastic pass (_MultiExitAccuracy._metrics, SA/train/loss/base_classes.py:41,54,58: `ensemble += softmax(logits)` inside one forward).
+ * Its variance and its mutual information need the PER-SAMPLE ensemble: the exits of one pass share the trunk's dropout draw, so
+ * E_t[q q] holds cross-exit terms that S1 / S2 do not.  Per sample t, exit e, image b, class c, in float64 from the fp32 per-sample
+ * logits l of the fused head (the plane bmi_forward_mcd_samples writes), without fused multiply-adds:
+ *     z_te = (double) fl32(l_te * inv_e)        inv_e = float32(1 / tau_e) (bmi_engine_set_temperature), the head's own z; 1 when off
+ *     p_te = softmax_c(z_te)                    max-subtracted
+ *     q_te = (p_t0 + ... + p_te) / (e + 1)      summed in exit order, divided once
+ *     Q1[e][b][c] += q     Q2[e][b][c] += q * q     QH[e][b] += -sum_c q log q   (0 log 0 = 0, class order)
+ * Row e = 0 is exit 0 itself.  For every (e, b, c) the samples of a call are added IN SAMPLE ORDER ONTO THE RUNNING SUM (load, add, store;
+ * no floating-point atomics): the sums are the same bits however the samples were split into chunks, launches or calls.
+ *
+ * bmi_forward_mcd_ensemble: bmi_forward_mcd_entropy with the same arguments and the same bits in S1 / S2 / SL / SH; per planned chunk the
+ * heads also write their logits into `scratch` (device, bmi_ensemble_scratch_bytes(h, batch) = planned chunk x E x batch x C x 4 bytes;
+ * 0 for a handle that is not planned or a batch it does not take) and one launch of ensemble.hip follows the chunk's heads.  Q1 / Q2
+ * [E][batch][C] and QH [E][batch] are device float64, ADDED TO like S1; rows 0 .. batch-1 of a share (image_offset).  The planned
+ * workspace is that of every other entry point.  BMI_ERR_NOMEM: scratch too small; BMI_ERR_UNSUPPORTED: more than 32 exits, more than
+ * 128 classes or n_exits * (C | 1) > 3456.  No allocation and no synchronisation: captures into a hipGraph like bmi_forward_mcd.  The
+ * fixed-T path only: adaptive sampling and early exit decide on sums that exist already. */
+size_t bmi_ensemble_scratch_bytes(bmi_handle h, int32_t batch);
+int bmi_forward_mcd_ensemble(bmi_handle h, const float* x_nchw, int32_t batch, int32_t image_offset, int32_t t_begin, int32_t t_count,
+                             uint64_t seed, int32_t mask_cnt0, double* S1, double* S2, double* SL, double* SH, double* Q1, double* Q2,
+                             double* QH, void* scratch, size_t scratch_bytes, void* workspace, size_t workspace_bytes, bmi_stream stream);
+
+/* The same sums from a caller's per-sample logits: device fp32 [T][E][B][C] (bmi_forward_mcd_samples' layout), tau: HOST [E], every entry
+ * finite and > 0 (rounded like bmi_engine_set_temperature: inv_e = float32(1.0 / (double)tau_e)), or NULL = ones.  Q1 / Q2 / QH are ADDED
+ * TO; two calls on the halves of T leave the bits of one call.  BMI_ERR_UNSUPPORTED (never a wrong number) for a shape the kernel does
+ * not take: E > 32, C > 128 or E * (C | 1) > 3456. */
+int bmi_ensemble_moments(const float* logits, int32_t T, int32_t E, int32_t B, int32_t C, const float* tau, double* Q1, double* Q2, double* QH,
+                         bmi_stream stream);
+
+/* Per (exit, image) from the sums of t_total samples, float64: ens_mean = Q1 / T and ens_var = max(Q2 / T - ens_mean^2, 0) (ddof 0 like
+ * bmi_finalize's var), [E][batch][C]; pred_entropy = H[ens_mean], exp_entropy = QH / T, mutual_info = max(pred - exp, 0), [E][batch]
+ * (0 log 0 = 0).  nonfinite (NULL: not counted) as in bmi_finalize_checked: ADDS the number of non-finite Q1 / Q2 / QH inputs. */
+int bmi_finalize_ensemble(int32_t n_exits, int32_t batch, int32_t out_dim, int32_t t_total, const double* Q1, const double* Q2, const double* QH,
+                          double* ens_mean, double* ens_var, double* pred_entropy, double* exp_entropy, double* mutual_info, int32_t* nonfinite,
+                          bmi_stream stream);
+
 /* Confidence-threshold early exiting ON the device — what the reference only models after the fact
  * (FullAnalysis.confidence_exiting / is_confident / flop_saver, SA/train/results_analyzer.py:606-630, :638-677, :725-733):
  * runs samples 0 .. t_count-1 of the batch stage by stage; after the head of exit e (first_exit <= e < n_exits-1; the
