@@ -36,6 +36,37 @@
 //                RAW  in interval 4T+3 every wave waits (counted vmcnt) until only the DMA issued in step T and the patch
 //                     piece of step T-1 are in flight, i.e. until the weights of step T+1 have landed, before the barrier that
 //                     ends 4T+3; first reads of step T+1 in 4T+4.  At tap 8 the count (2) also retires the whole next sub-patch.
+//
+// The pad-skip form of the 4x4 maps ("pw_pad_skip" = 1, the default; PwGeomSkip, SKIP = true in both kernels; 8x8 maps keep the above).
+// On a 4x4 map 44 of the 16 x 9 (output position, tap) pairs read nothing but the zero-padding ring (30.6 %).  With a 4 x 4 block of ONE
+// image as the MFMA pixel tile every tile has a live pixel for every tap and all of that is DMA'd, read and multiplied.  Here:
+//   tile order = the workgroup tile is still 16 images x 16 positions x 256 channels and a wave still owns 64 channels x 8 pixel tiles,
+//                but tile pixel p = 128 wp + 16 j + n: column l16 of pixel tile j is IMAGE n = l16 and j selects ONE output position,
+//                (y, x) = (j >> 1, 2 (j & 1) + ((y + wp) & 1)): the two pixel waves split the map as a checkerboard, wave wp owns the
+//                positions with (y + x) & 1 == wp.  For tap (ky, kx) tile (y, x) is ALL padding exactly when y + ky - 1 or x + kx - 1
+//                leaves 0..3; taps and j are compile-time, so a dead tile is a ds_read_b128 and four MFMAs that are not emitted.  Live
+//                tiles per wave and tap: centre 8 / 8, the four edge taps 6 / 6, the four corner taps 5 / 4; the waves meet at a barrier
+//                every phase, so the slower one counts: 8 + 4 * 6 + 4 * 5 = 52 tile-steps per chunk instead of 72 (a split by rows would give
+//                60).  A step's live tiles are spread over its two phases in tile order (4 + 4, 3 + 3, 3 + 2, 2 + 2).  Which tiles are dead
+//                depends on wp: the chunk loop exists once per pixel wave behind a wave-uniform branch (the same barriers on both sides).
+//   K order    = unchanged — chunk-major, taps 0..8 inside, 32 channels per MFMA; a product with an all-zero pixel fragment leaves its
+//                accumulator as it was, so every output keeps its bits (tests/test_pw_pad_skip.py).
+//   LDS        = 3 weight stages as above + 2 sub-patches [input cell 0..15][image 0..15][4 chunks of 16 B]: 16 KB instead of 48 KB, only
+//                real cells (no ring, no pitch cells); the 16-byte chunk c of image n is stored at position c ^ 2 ((n >> 3) & 1): a lane
+//                group of ds_read_b128 reads chunk kq of images 0-3 and 12-15 and chunk kq ^ 1 of images 4-11 of one cell — 16 distinct
+//                16-byte slots.  A tap shift is a whole cell: an immediate offset of 1024 B from ONE per-lane address.  The permutation
+//                again sits in the per-lane DMA source: piece q = tid + 512 i -> cell q >> 6, image (q >> 2) & 15, position q & 3; the
+//                images of a ragged last tile lie beyond the buffer descriptor (persistent kernel) or read the zero page.
+//   DMA / waits= ITER_P = 2 pieces per thread and sub-patch instead of 6, issued in phase 0 of taps 1 and 2 of the chunk before.  The
+//                windows are the ones above with that count: at the end of step `tap` a wave leaves in flight the weight DMA issued in
+//                this step (WROWS = 2 instructions) plus the pieces of this step and the step before — vmcnt(2) at taps 0, 4..8,
+//                vmcnt(3) at taps 1 and 3, vmcnt(4) at tap 2; a last chunk vmcnt(2), from tap 7 on vmcnt(0).  WAR: sub-patch (c + 1) & 1 was
+//                last read in step 9c - 1, its refill starts in step 9c + 1; RAW: the count of tap 4 allows no piece in flight any more, both
+//                have landed five steps before the first read in step 9 (c + 1).
+//   epilogues  = everything keyed to the tile-pixel order goes through PwGeomSkip::p_img / p_oy / p_ox: the fused shortcut's pixel rows,
+//                the direct stores, the residual runs, the Philox keep-bit index (image and position) and the row table of the dynamic-exit
+//                form.  The pooled tail of the persistent kernel sums an image's 16 positions — 8 registers in each pixel wave — through
+//                LDS in the order of the DPP tree it replaces; the pooled per-tile launches (dynamic exit) keep the 4 x 4-block tiles.
 // Reference semantics: BasicBlock.forward SA/models/resnet18/resnet18.py:32-48 (conv2 of every block, conv1 of the
 // stride-1 blocks).
 #include <cstdlib>
@@ -78,10 +109,51 @@ struct PwGeom {
     __host__ __device__ static constexpr int cell_delta(int j) { return (j / BI) * PH * PWP + 4 * ((j % BI) / BR) * PWP + 4 * ((j % BI) % BR); }
 };
 
-template <int TW, int EPI, bool BF, bool IMAP, bool POOL = false>
+// The pad-skip geometry of the 4x4 maps ("pw_pad_skip", see the header comment): the same 16 images x 16 positions x 256 channels per
+// workgroup, tile pixel p = 128 wp + 16 j + image.  Pixel tile j of pixel wave wp is the output position (y, x) = (j >> 1,
+// 2 (j & 1) + ((y + wp) & 1)): wave wp owns the eight positions with (y + x) & 1 == wp.
+struct PwGeomSkip {
+    static constexpr int CT = 256, TH = 4, PX = 256, IMGS = 16;
+    static constexpr int PH = 4, PW = 4, PWP = 4;                 // no ring, no pitch cells
+    static constexpr int CELLS = 16;                              // input cells of a map; one cell = [16 images][64 B] = 1 KB
+    static constexpr int ITER_P = CELLS * IMGS * 4 / 512;         // 16-byte pieces per thread and sub-patch: 2
+    static constexpr int PBUF = ITER_P * 512 * 16;                // 16 KB
+    static constexpr int WROWS = CT / 128;
+    static constexpr int WST = CT * 64;
+    static constexpr int NST = 3;
+    static constexpr int MAIN = NST * WST + 2 * PBUF;             // 80 KB
+    static constexpr int SHORT = 2 * (WST + PX * 64);
+    static constexpr int NEED = MAIN > SHORT ? MAIN : SHORT;
+    static constexpr int LDS_BYTES = NEED > 2 * BMI_EPILOGUE_LDS_BYTES ? NEED : 2 * BMI_EPILOGUE_LDS_BYTES;
+    __host__ __device__ static constexpr int t_y(int j) { return j >> 1; }
+    __host__ __device__ static constexpr int t_x(int wp, int j) { return 2 * (j & 1) + (((j >> 1) + wp) & 1); }
+    __host__ __device__ static constexpr int p_img(int p) { return p & 15; }
+    __host__ __device__ static constexpr int p_oy(int p) { return t_y((p >> 4) & 7); }
+    __host__ __device__ static constexpr int p_ox(int p) { return t_x(p >> 7, (p >> 4) & 7); }
+    // tap (ky, kx) of tile (wp, j) reads input cell (y + ky - 1, x + kx - 1) of all 16 images — or nothing but padding
+    __host__ __device__ static constexpr bool valid(int wp, int j, int tap) {
+        const int iy = t_y(j) + tap / 3 - 1, ix = t_x(wp, j) + tap % 3 - 1;
+        return iy >= 0 && iy < 4 && ix >= 0 && ix < 4;
+    }
+    __host__ __device__ static constexpr int cell(int wp, int j, int tap) { return (t_y(j) + tap / 3 - 1) * 4 + t_x(wp, j) + tap % 3 - 1; }
+    // the live tiles of a K-step are split evenly over its two phases (8: 4 + 4, 6: 3 + 3, 5: 3 + 2, 4: 2 + 2) in tile order
+    __host__ __device__ static constexpr int phase(int wp, int j, int tap) {
+        int n = 0, r = 0;
+        for (int t = 0; t < 8; ++t) {
+            if (valid(wp, t, tap)) { ++n; if (t < j) ++r; }
+        }
+        return r < (n + 1) / 2 ? 0 : 1;
+    }
+    __host__ __device__ static constexpr bool live(int wp, int j, int tap, int kk) { return valid(wp, j, tap) && phase(wp, j, tap) == kk; }
+};
+template <int TW, bool SKIP> struct PwGeomSel { using type = PwGeom<TW>; };
+template <> struct PwGeomSel<4, true> { using type = PwGeomSkip; };
+
+template <int TW, int EPI, bool BF, bool IMAP, bool POOL = false, bool SKIP = false>
 __global__ __launch_bounds__(512, 1) void conv3x3_pw_kernel(ConvArgs a) {
     static_assert(!POOL || (TW == 4 && EPI == BMI_EPI_LITE), "pooled output: 4x4 maps, the lite epilogue");
-    using G = PwGeom<TW>;
+    static_assert(!SKIP || (TW == 4 && !POOL), "pad-skip: 4x4 maps; the pooled per-tile form keeps the 4 x 4-block tiles (its DPP row is one image)");
+    using G = typename PwGeomSel<TW, SKIP>::type;
     constexpr int CT = G::CT, TH = G::TH, IMGS = G::IMGS, PH = G::PH, PW = G::PW, PWP = G::PWP;
     constexpr int TJ = 4, TI = 4, TP = 8;
     typedef float accv __attribute__((ext_vector_type(4)));
@@ -132,13 +204,20 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pw_kernel(ConvArgs a) {
 #pragma unroll
     for (int i = 0; i < G::ITER_P; ++i) {
         const int q = tid + 512 * i;
-        const int cell = q >> 2, pos = q & 3;
-        const int rowc = cell / PWP, x = cell - rowc * PWP;
-        const int img = rowc / PH, y = rowc - img * PH;
-        const int n = n0 + img;
-        const int iy = y - 1, ix = x - 1;
-        const bool ok = cell < G::CELLS && x < PW && n < a.N && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
-        psrc[i] = ok ? (int)((((size_t)(map_image<IMAP>(a, n) % a.in_mod) * a.H + iy) * a.W + ix) * a.Cin + (pos ^ ((y & 1) << 1)) * 8) : -1;
+        if constexpr (SKIP) {
+            // pad-skip: piece q -> input cell q >> 6, image (q >> 2) & 15, position q & 3 holds chunk pos ^ 2 ((image >> 3) & 1)
+            const int cell = q >> 6, img = (q >> 2) & 15, pos = q & 3;
+            const int n = n0 + img;
+            psrc[i] = n < a.N ? (int)((((size_t)(map_image<IMAP>(a, n) % a.in_mod) * a.H + (cell >> 2)) * a.W + (cell & 3)) * a.Cin + (pos ^ (((img >> 3) & 1) << 1)) * 8) : -1;
+        } else {
+            const int cell = q >> 2, pos = q & 3;
+            const int rowc = cell / PWP, x = cell - rowc * PWP;
+            const int img = rowc / PH, y = rowc - img * PH;
+            const int n = n0 + img;
+            const int iy = y - 1, ix = x - 1;
+            const bool ok = cell < G::CELLS && x < PW && n < a.N && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
+            psrc[i] = ok ? (int)((((size_t)(map_image<IMAP>(a, n) % a.in_mod) * a.H + iy) * a.W + ix) * a.Cin + (pos ^ ((y & 1) << 1)) * 8) : -1;
+        }
     }
 #define ISSUE_P(I, C0, PB)                                                                                   \
     GLDS16(psrc[I] >= 0 ? a.in + (size_t)(unsigned)psrc[I] + (C0) : (const _Float16*)g_zero_page_pw,       \
@@ -155,11 +234,16 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pw_kernel(ConvArgs a) {
     // Pixel fragments: cell of (wave's first block) + compile-time cell_delta(j) + this lane's cell inside the 4 x 4 block; the
     // chunk position kq ^ 2 (y & 1) depends on the lane's row in the block and on the tap's ky only (block origins are multiples
     // of 4) — so a fragment read is ONE ds_read_b128 with an immediate offset from one of three per-lane addresses.
-    const int wave_cell = (G::p_img(pbase) * PH + G::p_oy(pbase)) * PWP + G::p_ox(pbase);
     int boff[3];
+    if constexpr (SKIP) {
+        // pad-skip: lane (l16, kq) reads chunk kq of image l16 of a cell; the cell itself is an immediate offset (PW_STEP_S)
+        boff[0] = boff[1] = boff[2] = l16 * 64 + ((kq ^ (((l16 >> 3) & 1) << 1)) << 4);
+    } else {
+        const int wave_cell = (G::p_img(pbase) * PH + G::p_oy(pbase)) * PWP + G::p_ox(pbase);
 #pragma unroll
-    for (int ky = 0; ky < 3; ++ky)
-        boff[ky] = (wave_cell + (l16 >> 2) * PWP + (l16 & 3)) * 64 + ((kq ^ ((((l16 >> 2) + ky) & 1) << 1)) << 4);
+        for (int ky = 0; ky < 3; ++ky)
+            boff[ky] = (wave_cell + (l16 >> 2) * PWP + (l16 & 3)) * 64 + ((kq ^ ((((l16 >> 2) + ky) & 1) << 1)) << 4);
+    }
 
     accv acc[TI][TP];
 #pragma unroll
@@ -226,18 +310,66 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pw_kernel(ConvArgs a) {
         }                                                                                                      \
     }
 
+    // The pad-skip K-step of pixel wave WP (compile-time: which tiles are dead depends on the wave's positions): the same two phases, DMA
+    // issue and waits; a phase reads and multiplies only the tiles that are live in it (PwGeomSkip::live) — a dead tile is a ds_read_b128
+    // and four MFMAs that are not there.  Every accumulator still receives its products in the same K order.
+#define PW_STEP_S(TAP, WP)                                                                                     \
+    {                                                                                                          \
+        const char* ws_ = wst + ((TAP) % 3) * G::WST + a_off + a_byte;                                         \
+        const char* pb_ = pb + boff[0];                                                                        \
+        _Pragma("unroll") for (int kk = 0; kk < 2; ++kk) {                                                     \
+            if (kk == 0) {                                                                                     \
+                _Pragma("unroll") for (int i = 0; i < TI; ++i) af[i] = *(const half8*)(ws_ + i * 16 * 64);     \
+            }                                                                                                  \
+            _Pragma("unroll") for (int j = 0; j < TP; ++j)                                                     \
+                if (PwGeomSkip::live(WP, j, TAP, kk)) bfs[j] = *(const half8*)(pb_ + PwGeomSkip::cell(WP, j, TAP) * 1024); \
+            if (kk == 0) {                                                                                     \
+                if ((TAP) < 7) { ISSUE_W(((TAP) + 2) * a.Cin + c32, ((TAP) + 2) % 3); }                        \
+                else if (!last) { ISSUE_W(((TAP) - 7) * a.Cin + c32 + 32, ((TAP) + 2) % 3); }                  \
+                if ((TAP) >= 1 && (TAP) <= G::ITER_P && !last) { ISSUE_P((TAP) >= 1 && (TAP) <= G::ITER_P ? (TAP) - 1 : 0, c32 + 32, nb); } \
+            }                                                                                                  \
+            if (kk == 1 && g == 1) END_OF_STEP_WAIT(TAP);                                                      \
+            RAW_BARRIER();                                                                                     \
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                 \
+            __builtin_amdgcn_s_setprio(1);                                                                     \
+            _Pragma("unroll") for (int i = 0; i < TI; ++i)                                                     \
+                _Pragma("unroll") for (int j = 0; j < TP; ++j)                                                 \
+                    if (PwGeomSkip::live(WP, j, TAP, kk)) acc[i][j] = mfma_16x16x32<BF>(af[i], bfs[j], acc[i][j]); \
+            __builtin_amdgcn_s_setprio(0);                                                                     \
+            if (kk == 1 && g == 0) END_OF_STEP_WAIT(TAP);                                                      \
+            RAW_BARRIER();                                                                                     \
+        }                                                                                                      \
+    }
+#define PW_CHUNKS_S(WP)                                                                                        \
+    for (int chunk = 0; chunk < nC; ++chunk) {                                                                 \
+        const bool last = chunk + 1 == nC;                                                                     \
+        const int c32 = chunk * 32;                                                                            \
+        const int nb = (chunk + 1) & 1;                                                                        \
+        const char* pb = pbuf + (chunk & 1) * G::PBUF;                                                         \
+        PW_STEP_S(0, WP) PW_STEP_S(1, WP) PW_STEP_S(2, WP) PW_STEP_S(3, WP) PW_STEP_S(4, WP)                   \
+        PW_STEP_S(5, WP) PW_STEP_S(6, WP) PW_STEP_S(7, WP) PW_STEP_S(8, WP)                                    \
+    }
+
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     RAW_BARRIER();                      // weight stages 0, 1 and sub-patch 0 have landed
     if (g == 1) RAW_BARRIER();          // stagger
-    half8 af[TI], bf[4];
-    for (int chunk = 0; chunk < nC; ++chunk) {
-        const bool last = chunk + 1 == nC;
-        const int c32 = chunk * 32;
-        const int nb = (chunk + 1) & 1;
-        const char* pb = pbuf + (chunk & 1) * G::PBUF;
-        PW_STEP(0) PW_STEP(1) PW_STEP(2) PW_STEP(3) PW_STEP(4) PW_STEP(5) PW_STEP(6) PW_STEP(7) PW_STEP(8)
+    half8 af[TI];
+    if constexpr (SKIP) {
+        half8 bfs[TP];
+        if (wp == 0) { PW_CHUNKS_S(0) } else { PW_CHUNKS_S(1) }     // (wave-uniform: both sides take the same barriers)
+    } else {
+        half8 bf[4];
+        for (int chunk = 0; chunk < nC; ++chunk) {
+            const bool last = chunk + 1 == nC;
+            const int c32 = chunk * 32;
+            const int nb = (chunk + 1) & 1;
+            const char* pb = pbuf + (chunk & 1) * G::PBUF;
+            PW_STEP(0) PW_STEP(1) PW_STEP(2) PW_STEP(3) PW_STEP(4) PW_STEP(5) PW_STEP(6) PW_STEP(7) PW_STEP(8)
+        }
     }
     if (g == 0) RAW_BARRIER();          // re-align the two groups before the epilogue reuses the LDS
+#undef PW_CHUNKS_S
+#undef PW_STEP_S
 #undef PW_STEP
 #undef END_OF_STEP_WAIT
 #undef WAIT_VM
@@ -560,9 +692,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 // across the tile boundary (vmcnt(16)).  Why: per-tile fixed cost of conv3x3_pw from its own K = 2304 / 4608 rates (1308 / 1422 TFLOP/s, corrected
 // for the last partial round of tiles): 14-21 K-steps' worth per tile, of which the prologue's HBM round trip and the workgroup hand-over are
 // what a persistent walk removes.  Same K order, same arithmetic, same bits as conv3x3_pw_kernel<TW, PLAIN>.
-template <int TW>
+template <class G_>
 struct PwpGeom {
-    using G = PwGeom<TW>;
+    using G = G_;
     static constexpr int WST = G::WST, PBUF = G::PBUF;
     __host__ __device__ static constexpr int w_off(int st) { return st < 2 ? st * WST : 2 * WST + PBUF; }
     __host__ __device__ static constexpr int p_off(int b) { return b == 0 ? 2 * WST : 3 * WST + PBUF; }
@@ -586,13 +718,14 @@ struct PwpGeom {
 // its three barriers are gone and these launches can take the persistent walk.  Same arithmetic in the same order as epilogue_lite: the same bits.
 // POOLP (4x4 maps, ConvArgs::pool): the tail feeds nothing but an exit head — instead of the map, fp32 means over it ([row][Cout]) of relu(.): a pixel
 // tile is one image, its 16 pixels the 16 lanes of a DPP row (epilogue_lite's POOL: the same four adds in the same order).
-template <int TW, bool BF, bool SHORTCUT, int EPIK = BMI_EPI_PLAIN, bool POOLP = false>
+template <int TW, bool BF, bool SHORTCUT, int EPIK = BMI_EPI_PLAIN, bool POOLP = false, bool SKIP = false>
 __global__ __launch_bounds__(512, 1) void conv3x3_pwp_kernel(ConvArgs a, int n_tiles) {
     static_assert(!POOLP || (TW == 4 && EPIK != BMI_EPI_PLAIN), "pooled output: the 4x4 maps' BasicBlock tails");
+    static_assert(!SKIP || TW == 4, "pad-skip: 4x4 maps");
     static_assert(EPIK == BMI_EPI_PLAIN || (PWP_DIRECT && !SHORTCUT && (EPIK == BMI_EPI_LITE_RES || EPIK == BMI_EPI_LITE_RES_MC || EPIK == BMI_EPI_LITE_RES_MSK)),
                   "epilogue kind");
-    using G = PwGeom<TW>;
-    using L = PwpGeom<TW>;
+    using G = typename PwGeomSel<TW, SKIP>::type;
+    using L = PwpGeom<G>;
     constexpr int CT = G::CT, TH = G::TH, IMGS = G::IMGS, PH = G::PH, PW = G::PW, PWP = G::PWP;
     constexpr int TI = 4, TP = 8;
     typedef float accv __attribute__((ext_vector_type(4)));
@@ -636,12 +769,19 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pwp_kernel(ConvArgs a, int n_t
 #pragma unroll
     for (int i = 0; i < G::ITER_P; ++i) {
         const int q = tid + 512 * i;
-        const int cell = q >> 2, pos = q & 3;
-        const int rowc = cell / PWP, x = cell - rowc * PWP;
-        const int img = rowc / PH, y = rowc - img * PH;
-        const int iy = y - 1, ix = x - 1;
-        const bool ok = cell < G::CELLS && x < PW && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
-        pre[i] = ok ? 2u * ((unsigned)img * HWC + (unsigned)((iy * a.W + ix) * a.Cin + ((pos ^ ((y & 1) << 1)) << 3))) : OOB;
+        if constexpr (SKIP) {
+            // pad-skip: piece q -> input cell q >> 6, image (q >> 2) & 15, position q & 3 holds chunk pos ^ 2 ((image >> 3) & 1); every piece is a
+            // real cell, only the images of a last tile beyond N lie outside the descriptor
+            const int cell = q >> 6, img = (q >> 2) & 15, pos = q & 3;
+            pre[i] = 2u * ((unsigned)img * HWC + (unsigned)(((cell >> 2) * a.W + (cell & 3)) * a.Cin + ((pos ^ (((img >> 3) & 1) << 1)) << 3)));
+        } else {
+            const int cell = q >> 2, pos = q & 3;
+            const int rowc = cell / PWP, x = cell - rowc * PWP;
+            const int img = rowc / PH, y = rowc - img * PH;
+            const int iy = y - 1, ix = x - 1;
+            const bool ok = cell < G::CELLS && x < PW && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
+            pre[i] = ok ? 2u * ((unsigned)img * HWC + (unsigned)((iy * a.W + ix) * a.Cin + ((pos ^ ((y & 1) << 1)) << 3))) : OOB;
+        }
     }
     __amdgpu_buffer_rsrc_t rs_w, rs_wn, rs_in;
 #define BLDS16(RSRC, VOFF, SOFF, LDSPTR) \
@@ -667,11 +807,15 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pwp_kernel(ConvArgs a, int n_t
 #define A_TILE(I) (PWP_DIRECT ? (32 * ((I) >> 1) + 4 * ((I) & 1)) * 64 : (I) * 16 * 64)
     const int pbase = wp * 128;
     const int a_byte = (kq ^ (((l16 >> 2) & 1) << 1)) << 4;
-    const int wave_cell = (G::p_img(pbase) * PH + G::p_oy(pbase)) * PWP + G::p_ox(pbase);
     int boff[3];
+    if constexpr (SKIP) {
+        boff[0] = boff[1] = boff[2] = l16 * 64 + ((kq ^ (((l16 >> 3) & 1) << 1)) << 4);      // chunk kq of image l16 inside a cell (PWP_STEP_S)
+    } else {
+        const int wave_cell = (G::p_img(pbase) * PH + G::p_oy(pbase)) * PWP + G::p_ox(pbase);
 #pragma unroll
-    for (int ky = 0; ky < 3; ++ky)
-        boff[ky] = (wave_cell + (l16 >> 2) * PWP + (l16 & 3)) * 64 + ((kq ^ ((((l16 >> 2) + ky) & 1) << 1)) << 4);
+        for (int ky = 0; ky < 3; ++ky)
+            boff[ky] = (wave_cell + (l16 >> 2) * PWP + (l16 & 3)) * 64 + ((kq ^ ((((l16 >> 2) + ky) & 1) << 1)) << 4);
+    }
 
 #define RAW_BARRIER()                                  \
     {                                                  \
@@ -728,6 +872,56 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pwp_kernel(ConvArgs a, int n_t
         }                                                                                                      \
     }
 
+    // conv3x3_pw's pad-skip K-step (PW_STEP_S) with this kernel's prefetch targets
+#define PWP_STEP_S(TAP, WP)                                                                                    \
+    {                                                                                                          \
+        const char* ws_ = smem + L::w_off((TAP) % 3) + a_off + a_byte;                                         \
+        const char* pb_ = pb + boff[0];                                                                        \
+        _Pragma("unroll") for (int kk = 0; kk < 2; ++kk) {                                                     \
+            if (kk == 0) {                                                                                     \
+                _Pragma("unroll") for (int i = 0; i < TI; ++i) af[i] = *(const half8*)(ws_ + A_TILE(i));       \
+            }                                                                                                  \
+            _Pragma("unroll") for (int j = 0; j < TP; ++j)                                                     \
+                if (PwGeomSkip::live(WP, j, TAP, kk)) bfs[j] = *(const half8*)(pb_ + PwGeomSkip::cell(WP, j, TAP) * 1024); \
+            if (kk == 0) {                                                                                     \
+                if ((TAP) < 7) { ISSUE_W(rs_w, ((TAP) + 2) * a.Cin + c32, ((TAP) + 2) % 3); }                  \
+                else if (!last) {                                                                              \
+                    if (tile_last) { ISSUE_W(rs_wn, ((TAP) - 7) * a.Cin, ((TAP) + 2) % 3); }                   \
+                    else { ISSUE_W(rs_w, ((TAP) - 7) * a.Cin + c32 + 32, ((TAP) + 2) % 3); }                   \
+                }                                                                                              \
+                if ((TAP) >= 1 && (TAP) <= G::ITER_P && !last) {                                               \
+                    constexpr int i_ = (TAP) >= 1 && (TAP) <= G::ITER_P ? (TAP) - 1 : 0;                       \
+                    ISSUE_P(i_, nx_k, nb);                                                                     \
+                }                                                                                              \
+            }                                                                                                  \
+            if (kk == 1 && g == 1) END_OF_STEP_WAIT(TAP);                                                      \
+            RAW_BARRIER();                                                                                     \
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                 \
+            __builtin_amdgcn_s_setprio(1);                                                                     \
+            _Pragma("unroll") for (int i = 0; i < TI; ++i)                                                     \
+                _Pragma("unroll") for (int j = 0; j < TP; ++j)                                                 \
+                    if (PwGeomSkip::live(WP, j, TAP, kk)) acc[i][j] = mfma_16x16x32<BF>(af[i], bfs[j], acc[i][j]); \
+            __builtin_amdgcn_s_setprio(0);                                                                     \
+            if (kk == 1 && g == 0) END_OF_STEP_WAIT(TAP);                                                      \
+            RAW_BARRIER();                                                                                     \
+        }                                                                                                      \
+    }
+#define PWP_CHUNK_HEAD()                                                                                       \
+        const bool tile_last = chunk + 1 == nC;                                                                \
+        const bool last = tile_last && !more;                                                                  \
+        const int c32 = chunk * 32;                                                                            \
+        const int nb = (chunk + 1) & 1;                                                                        \
+        const char* pb = smem + L::p_off(chunk & 1);                                                           \
+        const int nx_k = tile_last ? 0 : c32 + 32;                                                             \
+        /* the last chunk of a tile issues no piece of its own tile any more: the input descriptor becomes the next tile's here */ \
+        if (tile_last && more) { TILE_RSRC_IN(n0n) }
+#define PWP_CHUNKS_S(WP)                                                                                       \
+    for (int chunk = 0; chunk < nC; ++chunk) {                                                                 \
+        PWP_CHUNK_HEAD()                                                                                       \
+        PWP_STEP_S(0, WP) PWP_STEP_S(1, WP) PWP_STEP_S(2, WP) PWP_STEP_S(3, WP) PWP_STEP_S(4, WP)              \
+        PWP_STEP_S(5, WP) PWP_STEP_S(6, WP) PWP_STEP_S(7, WP) PWP_STEP_S(8, WP)                                \
+    }
+
     int vb = blockIdx.x;
     int ptile, ctile;
     xcd_tile_map(vb, n_ptiles, n_ctiles, ptile, ctile, a.xcd_split);
@@ -764,17 +958,16 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pwp_kernel(ConvArgs a, int n_t
         else asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
         RAW_BARRIER();
         if (g == 1) RAW_BARRIER();          // stagger
-        half8 af[TI], bf[4];
-        for (int chunk = 0; chunk < nC; ++chunk) {
-            const bool tile_last = chunk + 1 == nC;
-            const bool last = tile_last && !more;
-            const int c32 = chunk * 32;
-            const int nb = (chunk + 1) & 1;
-            const char* pb = smem + L::p_off(chunk & 1);
-            const int nx_k = tile_last ? 0 : c32 + 32;
-            // the last chunk of a tile issues no piece of its own tile any more: the input descriptor becomes the next tile's here
-            if (tile_last && more) { TILE_RSRC_IN(n0n) }
-            PWP_STEP(0) PWP_STEP(1) PWP_STEP(2) PWP_STEP(3) PWP_STEP(4) PWP_STEP(5) PWP_STEP(6) PWP_STEP(7) PWP_STEP(8)
+        half8 af[TI];
+        if constexpr (SKIP) {
+            half8 bfs[TP];
+            if (wp == 0) { PWP_CHUNKS_S(0) } else { PWP_CHUNKS_S(1) }     // (wave-uniform: both sides take the same barriers)
+        } else {
+            half8 bf[4];
+            for (int chunk = 0; chunk < nC; ++chunk) {
+                PWP_CHUNK_HEAD()
+                PWP_STEP(0) PWP_STEP(1) PWP_STEP(2) PWP_STEP(3) PWP_STEP(4) PWP_STEP(5) PWP_STEP(6) PWP_STEP(7) PWP_STEP(8)
+            }
         }
         if (g == 0) RAW_BARRIER();          // re-align the two groups: every wave is past its last fragment reads
 
@@ -863,6 +1056,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pwp_kernel(ConvArgs a, int n_t
                     sc[ii] = *(const f32x4_e*)(bn_scale + chw + 32 * h + 4 * ii);
                     bi[ii] = *(const f32x4_e*)(bn_bias + chw + 32 * h + 4 * ii);
                 }
+                [[maybe_unused]] float xs[POOLP && SKIP ? TP : 1][8];   // pad-skip pooled tail: relu(.) of this lane's 8 channels at its 8 positions
 #pragma unroll
                 for (int j = 0; j < TP; ++j) {
                     uint32_t fields = 0u;
@@ -884,7 +1078,9 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pwp_kernel(ConvArgs a, int n_t
                             if constexpr (MC) v = ((fields >> (2 * (4 * ii + e))) & 3u) >= a.site.thresh ? v * a.site.scale : 0.f;
                             if constexpr (MSKS) { const float mk = a.site.masks[mrow[j] + 32 * h + 4 * ii + e]; v = mk == 0.f ? 0.f : v * mk; }
                             asm("" : "+v"(v));                                  // keep the fp32 product (epilogue_lite): rounded once
-                            if constexpr (POOLP) {
+                            if constexpr (POOLP && SKIP) {
+                                xs[j][4 * ii + e] = fmaxf(v, 0.f);             // (the head's ReLU); summed over the map below
+                            } else if constexpr (POOLP) {
                                 float x = fmaxf(v, 0.f);                       // (the head's ReLU)
                                 x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0xB1, 0xF, 0xF, true));    // lane ^ 1
                                 x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x4E, 0xF, 0xF, true));    // lane ^ 2
@@ -897,13 +1093,73 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pwp_kernel(ConvArgs a, int n_t
                         }
                     const int p = pbase + 16 * j + l16;
                     const int nimg = n0 + G::p_img(p);
-                    if constexpr (POOLP) {
+                    if constexpr (POOLP && SKIP) {
+                        // (below, once per h)
+                    } else if constexpr (POOLP) {
                         if (l16 == 0 && nimg < a.N) {
                             *(f32x4_e*)(a.pool + (size_t)nimg * a.Cout + chw + 32 * h) = pv[0];
                             *(f32x4_e*)(a.pool + (size_t)nimg * a.Cout + chw + 32 * h + 4) = pv[1];
                         }
                     } else if (nimg < a.N) {
                         *(half8_e*)(a.out + ((size_t)poff[j] << 3) + 32 * h) = o;
+                    }
+                }
+                if constexpr (POOLP && SKIP) {
+                    // An image's 16 positions are the 8 tile registers of this lane and of the same lane of the partner wave (wp ^ 1).  The sum keeps the
+                    // order of the DPP tree of the 4 x 4-block form — map row y: (p0 + p1) + (p2 + p3), then (r0 + r1) + (r3 + r2) — through the 64 KB
+                    // beside the prefetched stages: wave wp sends its rows 2 (1 - wp), 2 (1 - wp) + 1 and sums rows 2 wp, 2 wp + 1 (a pair p0 + p1 / p2 + p3 is one
+                    // value of each wave; float addition commutes); pixel wave 1 then sends r3 + r2 and pixel wave 0 stores.  Slot of wave w: 8 KB,
+                    // [tile 0..3][quad 0..1][lane] float4 (lane-linear ds_write_b128 / ds_read_b128).
+                    char* const X = smem + L::E_OFF;
+                    char* const mine_x = X + wave * 8192 + lane * 16;
+                    char* const theirs_x = X + (wave ^ 1) * 8192 + lane * 16;
+#pragma unroll
+                    for (int jj = 0; jj < 4; ++jj)
+#pragma unroll
+                        for (int q = 0; q < 2; ++q) {
+                            f32x4_e t;
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) t[e] = wp ? xs[jj][4 * q + e] : xs[4 + jj][4 * q + e];
+                            *(f32x4_e*)(mine_x + (jj * 2 + q) * 1024) = t;
+                        }
+                    lds_barrier();
+                    float rs[2][8];                                       // the two row sums of this wave
+#pragma unroll
+                    for (int r = 0; r < 2; ++r)
+#pragma unroll
+                        for (int q = 0; q < 2; ++q) {
+                            const f32x4_e t0 = *(const f32x4_e*)(theirs_x + ((2 * r) * 2 + q) * 1024), t1 = *(const f32x4_e*)(theirs_x + ((2 * r + 1) * 2 + q) * 1024);
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) {
+                                const float o0 = wp ? xs[4 + 2 * r][4 * q + e] : xs[2 * r][4 * q + e], o1 = wp ? xs[4 + 2 * r + 1][4 * q + e] : xs[2 * r + 1][4 * q + e];
+                                const float s01 = o0 + t0[e], s23 = o1 + t1[e];
+                                rs[r][4 * q + e] = s01 + s23;
+                            }
+                        }
+                    float half_sum[8];
+#pragma unroll
+                    for (int c = 0; c < 8; ++c) half_sum[c] = rs[0][c] + rs[1][c];          // r0 + r1 | r2 + r3
+                    lds_barrier();                                        // every wave has read its partner's slot
+                    if (wp) {
+#pragma unroll
+                        for (int q = 0; q < 2; ++q) {
+                            f32x4_e t;
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) t[e] = half_sum[4 * q + e];
+                            *(f32x4_e*)(theirs_x + q * 1024) = t;
+                        }
+                    }
+                    lds_barrier();
+                    if (!wp) {
+                        const int nimg = n0 + l16;
+#pragma unroll
+                        for (int q = 0; q < 2; ++q) {
+                            const f32x4_e t = *(const f32x4_e*)(mine_x + q * 1024);
+                            f32x4_e pv;
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) pv[e] = (half_sum[4 * q + e] + t[e]) * (1.f / 16.f);
+                            if (nimg < a.N) *(f32x4_e*)(a.pool + (size_t)nimg * a.Cout + chw + 32 * h + 4 * q) = pv;
+                        }
                     }
                 }
             }
@@ -992,6 +1248,9 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pwp_kernel(ConvArgs a, int n_t
         vb = nvb; ch0 = ch0n; n0 = n0n;
         TILE_RSRC_W(rs_w, ch0);
     }
+#undef PWP_CHUNKS_S
+#undef PWP_CHUNK_HEAD
+#undef PWP_STEP_S
 #undef PWP_STEP
 #undef END_OF_STEP_WAIT
 #undef WAIT_VM
@@ -1010,7 +1269,8 @@ bool conv_takes_pw_kernel(int ksize, int stride, int pad, int cin, int cout, int
     return ksize == 3 && stride == 1 && pad == 1 && cin % 64 == 0 && cout % 256 == 0 && ho == wo && (ho == 8 || ho == 4);
 }
 
-template <int TW>
+// SK: the pad-skip form of the 4x4 maps ("pw_pad_skip"; the pooled per-tile launches keep the 4 x 4-block tiles)
+template <int TW, bool SK>
 static int launch_pw(const ConvArgs& a_in, hipStream_t s) {
     ConvArgs a = a_in;
     a.xcd_split = xcd_split_for(a.Cout / 256, (size_t)a.Cout * 9 * a.Cin * 2);
@@ -1032,8 +1292,8 @@ static int launch_pw(const ConvArgs& a_in, hipStream_t s) {
                     return cu > 0 ? cu : 256;
                 }();
                 const dim3 pgrid((unsigned)(tiles < n_cu_p ? tiles : n_cu_p));
-                if (a.bf16) hipLaunchKernelGGL((conv3x3_pwp_kernel<4, true, false, BMI_EPI_LITE_RES, true>), pgrid, block, 0, s, a, (int)tiles);
-                else hipLaunchKernelGGL((conv3x3_pwp_kernel<4, false, false, BMI_EPI_LITE_RES, true>), pgrid, block, 0, s, a, (int)tiles);
+                if (a.bf16) hipLaunchKernelGGL((conv3x3_pwp_kernel<4, true, false, BMI_EPI_LITE_RES, true, SK>), pgrid, block, 0, s, a, (int)tiles);
+                else hipLaunchKernelGGL((conv3x3_pwp_kernel<4, false, false, BMI_EPI_LITE_RES, true, SK>), pgrid, block, 0, s, a, (int)tiles);
                 BMI_CHECK_LAUNCH();
                 return BMI_OK;
             }
@@ -1058,11 +1318,11 @@ static int launch_pw(const ConvArgs& a_in, hipStream_t s) {
         }();
         const dim3 pgrid((unsigned)(tiles < n_cu ? tiles : n_cu));
         if (a.in2) {
-            if (a.bf16) hipLaunchKernelGGL((conv3x3_pwp_kernel<TW, true, true>), pgrid, block, 0, s, a, (int)tiles);
-            else hipLaunchKernelGGL((conv3x3_pwp_kernel<TW, false, true>), pgrid, block, 0, s, a, (int)tiles);
+            if (a.bf16) hipLaunchKernelGGL((conv3x3_pwp_kernel<TW, true, true, BMI_EPI_PLAIN, false, SK>), pgrid, block, 0, s, a, (int)tiles);
+            else hipLaunchKernelGGL((conv3x3_pwp_kernel<TW, false, true, BMI_EPI_PLAIN, false, SK>), pgrid, block, 0, s, a, (int)tiles);
         } else {
-            if (a.bf16) hipLaunchKernelGGL((conv3x3_pwp_kernel<TW, true, false>), pgrid, block, 0, s, a, (int)tiles);
-            else hipLaunchKernelGGL((conv3x3_pwp_kernel<TW, false, false>), pgrid, block, 0, s, a, (int)tiles);
+            if (a.bf16) hipLaunchKernelGGL((conv3x3_pwp_kernel<TW, true, false, BMI_EPI_PLAIN, false, SK>), pgrid, block, 0, s, a, (int)tiles);
+            else hipLaunchKernelGGL((conv3x3_pwp_kernel<TW, false, false, BMI_EPI_PLAIN, false, SK>), pgrid, block, 0, s, a, (int)tiles);
         }
         BMI_CHECK_LAUNCH();
         return BMI_OK;
@@ -1084,37 +1344,37 @@ static int launch_pw(const ConvArgs& a_in, hipStream_t s) {
         }();
         const dim3 pgrid((unsigned)(tiles < n_cu ? tiles : n_cu));
         if (epi_fine == BMI_EPI_LITE_RES) {
-            if (a.bf16) hipLaunchKernelGGL((conv3x3_pwp_kernel<TW, true, false, BMI_EPI_LITE_RES>), pgrid, block, 0, s, a, (int)tiles);
-            else hipLaunchKernelGGL((conv3x3_pwp_kernel<TW, false, false, BMI_EPI_LITE_RES>), pgrid, block, 0, s, a, (int)tiles);
+            if (a.bf16) hipLaunchKernelGGL((conv3x3_pwp_kernel<TW, true, false, BMI_EPI_LITE_RES, false, SK>), pgrid, block, 0, s, a, (int)tiles);
+            else hipLaunchKernelGGL((conv3x3_pwp_kernel<TW, false, false, BMI_EPI_LITE_RES, false, SK>), pgrid, block, 0, s, a, (int)tiles);
         } else if (epi_fine == BMI_EPI_LITE_RES_MSK) {
-            if (a.bf16) hipLaunchKernelGGL((conv3x3_pwp_kernel<TW, true, false, BMI_EPI_LITE_RES_MSK>), pgrid, block, 0, s, a, (int)tiles);
-            else hipLaunchKernelGGL((conv3x3_pwp_kernel<TW, false, false, BMI_EPI_LITE_RES_MSK>), pgrid, block, 0, s, a, (int)tiles);
+            if (a.bf16) hipLaunchKernelGGL((conv3x3_pwp_kernel<TW, true, false, BMI_EPI_LITE_RES_MSK, false, SK>), pgrid, block, 0, s, a, (int)tiles);
+            else hipLaunchKernelGGL((conv3x3_pwp_kernel<TW, false, false, BMI_EPI_LITE_RES_MSK, false, SK>), pgrid, block, 0, s, a, (int)tiles);
         } else {
-            if (a.bf16) hipLaunchKernelGGL((conv3x3_pwp_kernel<TW, true, false, BMI_EPI_LITE_RES_MC>), pgrid, block, 0, s, a, (int)tiles);
-            else hipLaunchKernelGGL((conv3x3_pwp_kernel<TW, false, false, BMI_EPI_LITE_RES_MC>), pgrid, block, 0, s, a, (int)tiles);
+            if (a.bf16) hipLaunchKernelGGL((conv3x3_pwp_kernel<TW, true, false, BMI_EPI_LITE_RES_MC, false, SK>), pgrid, block, 0, s, a, (int)tiles);
+            else hipLaunchKernelGGL((conv3x3_pwp_kernel<TW, false, false, BMI_EPI_LITE_RES_MC, false, SK>), pgrid, block, 0, s, a, (int)tiles);
         }
         BMI_CHECK_LAUNCH();
         return BMI_OK;
     }
     if (epi_fine == BMI_EPI_LITE_RES || epi_fine == BMI_EPI_LITE_RES_MC || epi_fine == BMI_EPI_LITE_RES_MSK) {
         if (epi_fine == BMI_EPI_LITE_RES) {
-            if (a.bf16) hipLaunchKernelGGL((conv3x3_pw_kernel<TW, BMI_EPI_LITE_RES, true, false>), grid, block, 0, s, a);
-            else hipLaunchKernelGGL((conv3x3_pw_kernel<TW, BMI_EPI_LITE_RES, false, false>), grid, block, 0, s, a);
+            if (a.bf16) hipLaunchKernelGGL((conv3x3_pw_kernel<TW, BMI_EPI_LITE_RES, true, false, false, SK>), grid, block, 0, s, a);
+            else hipLaunchKernelGGL((conv3x3_pw_kernel<TW, BMI_EPI_LITE_RES, false, false, false, SK>), grid, block, 0, s, a);
         } else if (epi_fine == BMI_EPI_LITE_RES_MSK) {
-            if (a.bf16) hipLaunchKernelGGL((conv3x3_pw_kernel<TW, BMI_EPI_LITE_RES_MSK, true, false>), grid, block, 0, s, a);
-            else hipLaunchKernelGGL((conv3x3_pw_kernel<TW, BMI_EPI_LITE_RES_MSK, false, false>), grid, block, 0, s, a);
+            if (a.bf16) hipLaunchKernelGGL((conv3x3_pw_kernel<TW, BMI_EPI_LITE_RES_MSK, true, false, false, SK>), grid, block, 0, s, a);
+            else hipLaunchKernelGGL((conv3x3_pw_kernel<TW, BMI_EPI_LITE_RES_MSK, false, false, false, SK>), grid, block, 0, s, a);
         } else {
-            if (a.bf16) hipLaunchKernelGGL((conv3x3_pw_kernel<TW, BMI_EPI_LITE_RES_MC, true, false>), grid, block, 0, s, a);
-            else hipLaunchKernelGGL((conv3x3_pw_kernel<TW, BMI_EPI_LITE_RES_MC, false, false>), grid, block, 0, s, a);
+            if (a.bf16) hipLaunchKernelGGL((conv3x3_pw_kernel<TW, BMI_EPI_LITE_RES_MC, true, false, false, SK>), grid, block, 0, s, a);
+            else hipLaunchKernelGGL((conv3x3_pw_kernel<TW, BMI_EPI_LITE_RES_MC, false, false, false, SK>), grid, block, 0, s, a);
         }
         BMI_CHECK_LAUNCH();
         return BMI_OK;
     }
 #define PW_LAUNCH_BF(BF_, IMAP_)                                                                                                    \
     {                                                                                                                               \
-        if (epi == BMI_EPI_PLAIN) hipLaunchKernelGGL((conv3x3_pw_kernel<TW, BMI_EPI_PLAIN, BF_, IMAP_>), grid, block, 0, s, a);     \
-        else if (epi == BMI_EPI_LITE) hipLaunchKernelGGL((conv3x3_pw_kernel<TW, BMI_EPI_LITE, BF_, IMAP_>), grid, block, 0, s, a);  \
-        else hipLaunchKernelGGL((conv3x3_pw_kernel<TW, BMI_EPI_GENERAL, BF_, IMAP_>), grid, block, 0, s, a);                        \
+        if (epi == BMI_EPI_PLAIN) hipLaunchKernelGGL((conv3x3_pw_kernel<TW, BMI_EPI_PLAIN, BF_, IMAP_, false, SK>), grid, block, 0, s, a);     \
+        else if (epi == BMI_EPI_LITE) hipLaunchKernelGGL((conv3x3_pw_kernel<TW, BMI_EPI_LITE, BF_, IMAP_, false, SK>), grid, block, 0, s, a);  \
+        else hipLaunchKernelGGL((conv3x3_pw_kernel<TW, BMI_EPI_GENERAL, BF_, IMAP_, false, SK>), grid, block, 0, s, a);                        \
     }
 #define PW_LAUNCH(IMAP_) \
     if (a.bf16) PW_LAUNCH_BF(true, IMAP_) else PW_LAUNCH_BF(false, IMAP_)
@@ -1148,5 +1408,6 @@ int launch_conv3x3_pw(const ConvArgs& a, hipStream_t s) {
     if (a.N <= 0 || a.in_mod <= 0 || a.B <= 0 || (a.res && a.res_mod <= 0)) return BMI_ERR_INVALID;
     if ((size_t)a.in_mod * a.H * a.W * a.Cin >= 0x7fffffffull) return BMI_ERR_UNSUPPORTED;   // 31-bit DMA source offsets
     if (a.in2 && (size_t)a.in2_mod * a.H2 * a.W2 * a.Cin2 >= 0x7fffffffull) return BMI_ERR_UNSUPPORTED;
-    return a.Ho == 8 ? launch_pw<8>(a, s) : launch_pw<4>(a, s);
+    if (a.Ho == 8) return launch_pw<8, false>(a, s);
+    return opt_pw_pad_skip() ? launch_pw<4, true>(a, s) : launch_pw<4, false>(a, s);
 }

@@ -4,7 +4,7 @@ bmi_set_option sets — the comparison the CDNA guide asks for (rule 24: separat
 
     python tools/step_ab.py --workload resnet18_me --rounds 7 --steps 3 \
         --ab "mfma_shape_patch=32+mfma_shape_wide=32,mfma_shape_patch=16+mfma_shape_wide=16"
-Prints per variant the median / min ms per step and the per-family conv time of one profiled step.
+Prints per variant the median / min / max ms per step over the rounds and the per-family conv time of one profiled step.
 """
 import argparse
 import os
@@ -88,7 +88,7 @@ def main():
         eng.profile(False)
         t = sorted(times[v])
         fam = "  ".join(f"{k.replace('_kernel', '')} {d['ms']:.2f} ms {d['flops'] / d['ms'] / 1e9:.0f} TF/s" for k, d in eng.conv_families.items())
-        print(f"{v:60s} median {t[len(t) // 2]:8.3f} ms/step  min {t[0]:8.3f}   {B * T / t[len(t) // 2] * 1e3:10.0f} samples/s   | {fam} | "
+        print(f"{v:60s} median {t[len(t) // 2]:8.3f} ms/step  min {t[0]:8.3f}  max {t[-1]:8.3f}   {B * T / t[len(t) // 2] * 1e3:10.0f} samples/s   | {fam} | "
               + " ".join(f"{k} {v2[0]:.2f}" for k, v2 in prof.items() if k != "conv_igemm"))
 
 
