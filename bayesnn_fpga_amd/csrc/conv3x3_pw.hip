@@ -67,9 +67,26 @@
 //                the direct stores, the residual runs, the Philox keep-bit index (image and position) and the row table of the dynamic-exit
 //                form.  The pooled tail of the persistent kernel sums an image's 16 positions — 8 registers in each pixel wave — through
 //                LDS in the order of the DPP tree it replaces; the pooled per-tile launches (dynamic exit) keep the 4 x 4-block tiles.
+// The pad-skip form of the 8x8 maps ("pw_pad_skip8" = 1, the default; PwGeomSkip8 / PwSkip8Q, conv3x3_pwp_kernel<8, .., SKIP = true> only — the per-tile,
+// four-wave and row-table launches keep the 4 x 4-block tiles).  92 of the 64 x 9 (position, tap) pairs of an 8x8 map read the ring (16.0 %).
+//   tile       = 16 images x ONE 4x4 quadrant x 256 channels, pixel order and checkerboard split as above inside the quadrant; a launch has 4 x
+//                ceil(N / 16) pixel tiles instead of ceil(N / 4).  A quadrant touches two edges of the map: corner tap 5 / 4 live tiles per wave, the
+//                four taps next to it 6 / 6, the other four 8 / 8 — 61 tile-steps per chunk instead of 72 (−15.3 %), mirrored per quadrant.
+//   code       = which tiles are dead depends on the quadrant kind and on wp.  The walk over the tiles is instantiated once per kind (a generic
+//                lambda, QK compile-time) and a persistent workgroup walks tiles of ONE kind only: grid % 32 == 0 -> kind (block >> 3) & 3, so that
+//                the four quadrants of a group of 16 images run on one XCD at about the same time.  Per-lane values are computed inside the walk
+//                from a lane index the compiler cannot trace (else it hoists them above the branch and spills them across it).
+//   LDS        = sub-patch [cell 0..24][image 0..15][4 x 16 B]: the quadrant's 5 x 5 REAL input cells (its 16 + the halo towards the centre, never
+//                the ring), 25 KB of a 32 KB buffer, the same chunk swizzle; a tap shift is an immediate offset of whole cells.  4 DMA pieces per
+//                thread: piece i of wave w is cell w + 8 i (wave-uniform: its offset goes into the instruction's scalar offset, one per-lane offset
+//                serves all four; cells 25..31 lie outside the descriptor); the descriptor starts at the sub-patch's cell (0, 0).  Counted waits:
+//                END_OF_STEP_WAIT with ITER_P = 4, the windows of the 4 x 4-block 8x8 form.
+//   epilogues  = PwGeomSkip8::p_img / p_oy / p_ox + the quadrant's origin; the residual row offsets are one per-lane value (the image) + a
+//                wave-uniform one per tile.  Same K order, same bits (tests/test_pw_pad_skip8.py).
 // Reference semantics: BasicBlock.forward SA/models/resnet18/resnet18.py:32-48 (conv2 of every block, conv1 of the
 // stride-1 blocks).
 #include <cstdlib>
+#include <type_traits>
 
 #include "conv_epilogue.h"
 #include "kernels.h"
@@ -146,8 +163,78 @@ struct PwGeomSkip {
     }
     __host__ __device__ static constexpr bool live(int wp, int j, int tap, int kk) { return valid(wp, j, tap) && phase(wp, j, tap) == kk; }
 };
+
+// The pad-skip geometry of the 8x8 maps ("pw_pad_skip8", persistent kernel only): a workgroup tile is 16 images x ONE 4x4 quadrant of the map
+// x 256 channels, tile pixel p = 128 wp + 16 j + image with PwGeomSkip's positions inside the quadrant.  Quadrant qk = 2 qy + qx covers the
+// outputs (4 qy + y, 4 qx + x); its sub-patch holds the 5 x 5 REAL input cells it reads — rows 0..4 (qy = 0) or 3..7 (qy = 1), columns
+// likewise: the quadrant's own 16 cells plus the halo towards the map's centre, never the ring — as [cell 0..24][image 0..15][4 x 16 B].
+// A persistent workgroup walks tiles of ONE quadrant kind (conv3x3_pwp_kernel: the kind is compile-time in its walk).
+struct PwGeomSkip8 {
+    static constexpr int CT = 256, TH = 8, PX = 256, IMGS = 16;
+    static constexpr int PH = 5, PW = 5, PWP = 5;                 // the real cells of a quadrant's sub-patch
+    static constexpr int CELLS = 25;                              // one cell = [16 images][64 B] = 1 KB
+    static constexpr int ITER_P = (CELLS * IMGS * 4 + 511) / 512; // 16-byte pieces per thread and sub-patch: 4 (pieces 1600..2047 lie beyond the descriptor)
+    static constexpr int PBUF = ITER_P * 512 * 16;                // 32 KB, 25 KB of it read
+    static constexpr int WROWS = CT / 128;
+    static constexpr int WST = CT * 64;
+    static constexpr int NST = 3;
+    static constexpr int MAIN = NST * WST + 2 * PBUF;             // 112 KB
+    static constexpr int SHORT = 2 * (WST + PX * 64);
+    static constexpr int NEED = MAIN > SHORT ? MAIN : SHORT;
+    static constexpr int LDS_BYTES = NEED > 2 * BMI_EPILOGUE_LDS_BYTES ? NEED : 2 * BMI_EPILOGUE_LDS_BYTES;
+    __host__ __device__ static constexpr int p_img(int p) { return p & 15; }
+    __host__ __device__ static constexpr int p_oy(int p) { return PwGeomSkip::p_oy(p); }     // inside the quadrant: + oy0(qk)
+    __host__ __device__ static constexpr int p_ox(int p) { return PwGeomSkip::p_ox(p); }     //                      + ox0(qk)
+    __host__ __device__ static constexpr int oy0(int qk) { return 4 * (qk >> 1); }
+    __host__ __device__ static constexpr int ox0(int qk) { return 4 * (qk & 1); }
+    __host__ __device__ static constexpr int cy0(int qk) { return (qk >> 1) ? 3 : 0; }       // map row / column of sub-patch cell (0, 0)
+    __host__ __device__ static constexpr int cx0(int qk) { return (qk & 1) ? 3 : 0; }
+};
+// which tiles of quadrant QK are live for a tap, and the sub-patch cell they read (PwGeomSkip's interface)
+template <int QK>
+struct PwSkip8Q {
+    __host__ __device__ static constexpr int iy(int j, int tap) { return PwGeomSkip8::oy0(QK) + PwGeomSkip::t_y(j) + tap / 3 - 1; }
+    __host__ __device__ static constexpr int ix(int wp, int j, int tap) { return PwGeomSkip8::ox0(QK) + PwGeomSkip::t_x(wp, j) + tap % 3 - 1; }
+    __host__ __device__ static constexpr bool valid(int wp, int j, int tap) { return iy(j, tap) >= 0 && iy(j, tap) < 8 && ix(wp, j, tap) >= 0 && ix(wp, j, tap) < 8; }
+    __host__ __device__ static constexpr int cell(int wp, int j, int tap) { return (iy(j, tap) - PwGeomSkip8::cy0(QK)) * 5 + ix(wp, j, tap) - PwGeomSkip8::cx0(QK); }
+    __host__ __device__ static constexpr int phase(int wp, int j, int tap) {
+        int n = 0, r = 0;
+        for (int t = 0; t < 8; ++t) {
+            if (valid(wp, t, tap)) { ++n; if (t < j) ++r; }
+        }
+        return r < (n + 1) / 2 ? 0 : 1;
+    }
+    __host__ __device__ static constexpr bool live(int wp, int j, int tap, int kk) { return valid(wp, j, tap) && phase(wp, j, tap) == kk; }
+};
+// every live tile reads one of the 25 cells; per 32-channel chunk the slower pixel wave runs 61 tile-steps instead of 72
+constexpr bool pw_skip8_geometry_ok() {
+    int steps = 0;
+    for (int tap = 0; tap < 9; ++tap) {
+        int n[2] = {0, 0};
+        for (int wp = 0; wp < 2; ++wp)
+            for (int j = 0; j < 8; ++j) {
+                if (!PwSkip8Q<0>::valid(wp, j, tap)) continue;
+                ++n[wp];
+                const int c = PwSkip8Q<0>::cell(wp, j, tap);
+                if (c < 0 || c >= 25) return false;
+            }
+        steps += n[0] > n[1] ? n[0] : n[1];
+    }
+    for (int tap = 0; tap < 9; ++tap)
+        for (int wp = 0; wp < 2; ++wp)
+            for (int j = 0; j < 8; ++j) {
+                if (PwSkip8Q<1>::valid(wp, j, tap) && (PwSkip8Q<1>::cell(wp, j, tap) < 0 || PwSkip8Q<1>::cell(wp, j, tap) >= 25)) return false;
+                if (PwSkip8Q<2>::valid(wp, j, tap) && (PwSkip8Q<2>::cell(wp, j, tap) < 0 || PwSkip8Q<2>::cell(wp, j, tap) >= 25)) return false;
+                if (PwSkip8Q<3>::valid(wp, j, tap) && (PwSkip8Q<3>::cell(wp, j, tap) < 0 || PwSkip8Q<3>::cell(wp, j, tap) >= 25)) return false;
+            }
+    return steps == 61;
+}
+static_assert(pw_skip8_geometry_ok(), "pad-skip 8x8: cells inside the sub-patch, 61 tile-steps per chunk");
+template <bool SK8, int QK> struct PwSkipSel { using type = PwGeomSkip; };
+template <int QK> struct PwSkipSel<true, QK> { using type = PwSkip8Q<QK>; };
 template <int TW, bool SKIP> struct PwGeomSel { using type = PwGeom<TW>; };
 template <> struct PwGeomSel<4, true> { using type = PwGeomSkip; };
+template <> struct PwGeomSel<8, true> { using type = PwGeomSkip8; };
 
 template <int TW, int EPI, bool BF, bool IMAP, bool POOL = false, bool SKIP = false>
 __global__ __launch_bounds__(512, 1) void conv3x3_pw_kernel(ConvArgs a) {
@@ -721,25 +808,24 @@ struct PwpGeom {
 template <int TW, bool BF, bool SHORTCUT, int EPIK = BMI_EPI_PLAIN, bool POOLP = false, bool SKIP = false>
 __global__ __launch_bounds__(512, 1) void conv3x3_pwp_kernel(ConvArgs a, int n_tiles) {
     static_assert(!POOLP || (TW == 4 && EPIK != BMI_EPI_PLAIN), "pooled output: the 4x4 maps' BasicBlock tails");
-    static_assert(!SKIP || TW == 4, "pad-skip: 4x4 maps");
+    static_assert(!SKIP || TW == 4 || TW == 8, "pad-skip: 4x4 maps, 8x8 maps by quadrants");
     static_assert(EPIK == BMI_EPI_PLAIN || (PWP_DIRECT && !SHORTCUT && (EPIK == BMI_EPI_LITE_RES || EPIK == BMI_EPI_LITE_RES_MC || EPIK == BMI_EPI_LITE_RES_MSK)),
                   "epilogue kind");
     using G = typename PwGeomSel<TW, SKIP>::type;
     using L = PwpGeom<G>;
     constexpr int CT = G::CT, TH = G::TH, IMGS = G::IMGS, PH = G::PH, PW = G::PW, PWP = G::PWP;
     constexpr int TI = 4, TP = 8;
+    constexpr bool SK8 = SKIP && TW == 8;                        // quadrant tiles (PwGeomSkip8): a pixel tile index is (group of 16 images, quadrant)
     typedef float accv __attribute__((ext_vector_type(4)));
     __shared__ __attribute__((aligned(16))) char smem[L::LDS_BYTES];
     float* const bn_scale = (float*)(smem + L::BN_OFF);
     float* const bn_bias = bn_scale + 512;
 
     const int tid = threadIdx.x;
-    const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int l16 = lane & 15, kq = lane >> 4;
     const int g = wave >> 2, wc = (wave >> 1) & 1, wp = wave & 1;
     const int n_ctiles = a.Cout / CT;
-    const int n_ptiles = (a.N + IMGS - 1) / IMGS;
+    const int n_ptiles = (a.N + IMGS - 1) / IMGS;                // (quadrant tiles: of ONE quadrant kind)
     const int Ktot = 9 * a.Cin;
     const int nC = a.Cin / 32;                                   // even (launcher: Cin % 64 == 0)
 
@@ -749,14 +835,36 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pwp_kernel(ConvArgs a, int n_t
     }
     __syncthreads();   // (no LDS-DMA in flight yet)
 
+    // This workgroup's tiles: vb0, vb0 + vstride, .. below n_walk.  Quadrant tiles: the grid is a multiple of 4 (launcher) and a quarter of it walks
+    // each quadrant kind's n_tiles / 4 tiles.  A grid that is a multiple of 32: kind = (block >> 3) & 3, so the four quadrants of a group of 16
+    // images run on ONE XCD (block % 8) at about the same time and the halo re-reads meet in its L2; otherwise kind = block & 3.
+    const bool x32 = (gridDim.x & 31) == 0;
+    const int wg_kind = !SK8 ? 0 : x32 ? ((int)blockIdx.x >> 3) & 3 : (int)blockIdx.x & 3;
+    const int vb0 = !SK8 ? (int)blockIdx.x : x32 ? (((int)blockIdx.x >> 5) << 3) + ((int)blockIdx.x & 7) : (int)blockIdx.x >> 2;
+    const int vstride = SK8 ? (int)gridDim.x >> 2 : (int)gridDim.x;
+    const int n_walk = SK8 ? n_tiles >> 2 : n_tiles;
+    // The walk over the tiles.  Quadrant tiles: QKC carries the quadrant kind of THIS workgroup's tiles as a compile-time value — which tiles are
+    // dead depends on the quadrant (which edges of the map it touches) and on wp, so the walk is instantiated once per kind, each with its two
+    // chunk loops, and a workgroup runs one of them (otherwise QK = 0, one instantiation).  Every per-lane value is computed inside: nothing but the
+    // thread index lives across the branch.
+    auto walk = [&](auto QKC) __attribute__((always_inline)) {
+    constexpr int QK = decltype(QKC)::value;
+    using GS = typename PwSkipSel<SK8, QK>::type;                // live tiles and their cells: PwGeomSkip (4x4 maps) or PwSkip8Q<QK>
+    // (the per-lane indices again, from a lane index the compiler cannot trace: otherwise it hoists the four instantiations' common per-lane values
+    //  above the branch and keeps them live — spilled — across all of it; like this no VGPR lives across the branch)
+    int lane;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane));
+    const int tid = wave * 64 + lane, l16 = lane & 15, kq = lane >> 4;
+
     // Every DMA is a buffer_load ... lds through a per-tile buffer descriptor (wave-uniform, SGPRs) with a 32-bit per-lane byte offset that
     // is computed ONCE per kernel (conv3x3_s2's scheme: with per-tile 64-bit sources the persistent loop spilled 30-60 VGPRs): what a piece
     // reads is the same for every tile up to the tile's first image, and a lane whose offset lies beyond the descriptor loads ZEROS — the
     // padding ring, the cells of the pitch, the images of a last tile beyond N.
     // weights: piece q = tid + 512 i -> row (tid >> 2) + 128 i of the channel tile, position tid & 3 holds chunk pos ^ 2 ((row >> 2) & 1)
-    unsigned woff[G::WROWS];
+    // (quadrant tiles: rows 128 apart hold the same chunk position, so the second piece is the first + 128 rows in the scalar offset — one VGPR)
+    unsigned woff[SK8 ? 1 : G::WROWS];
 #pragma unroll
-    for (int i = 0; i < G::WROWS; ++i) {
+    for (int i = 0; i < (SK8 ? 1 : G::WROWS); ++i) {
         const int row = (tid >> 2) + 128 * i;
         // (PWP_DIRECT: a fragment's 16 lanes read rows 8 a + b + const, a = 0..3, b = 0..3: the chunk position alternates with row >> 3)
         woff[i] = 2u * ((unsigned)row * Ktot + (((tid & 3) ^ (((row >> (PWP_DIRECT ? 3 : 2)) & 1) << 1)) << 3));
@@ -765,11 +873,17 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pwp_kernel(ConvArgs a, int n_t
     const unsigned HWC = (unsigned)a.H * a.W * a.Cin;
     constexpr unsigned OOB = 0xfffffff0u;
     // sub-patch: piece q = tid + 512 i -> cell q >> 2, position q & 3 holds chunk pos ^ 2 (y & 1): byte offset relative to the tile's image 0
-    unsigned pre[G::ITER_P];
+    // (quadrant tiles: the same piece -> (cell, image, position) map on the 5 x 5 cells of the quadrant's sub-patch.  The cell, wave + 8 i, is
+    //  wave-uniform: its offset relative to cell (0, 0) — the descriptor's base, TILE_RSRC_IN — travels in the scalar offset (ISSUE_P) and one per-lane
+    //  offset (image, chunk position) serves the four pieces; the pieces of cells 25..31 lie outside every descriptor)
+    unsigned pre[SK8 ? 1 : G::ITER_P];
 #pragma unroll
-    for (int i = 0; i < G::ITER_P; ++i) {
+    for (int i = 0; i < (SK8 ? 1 : G::ITER_P); ++i) {
         const int q = tid + 512 * i;
-        if constexpr (SKIP) {
+        if constexpr (SK8) {
+            const int img = (q >> 2) & 15, pos = q & 3;
+            pre[i] = 2u * ((unsigned)img * HWC + (unsigned)((pos ^ (((img >> 3) & 1) << 1)) << 3));
+        } else if constexpr (SKIP) {
             // pad-skip: piece q -> input cell q >> 6, image (q >> 2) & 15, position q & 3 holds chunk pos ^ 2 ((image >> 3) & 1); every piece is a
             // real cell, only the images of a last tile beyond N lie outside the descriptor
             const int cell = q >> 6, img = (q >> 2) & 15, pos = q & 3;
@@ -790,15 +904,25 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pwp_kernel(ConvArgs a, int n_t
     {                                                                                              \
         const unsigned so_ = __builtin_amdgcn_readfirstlane(2u * (unsigned)(KOFF));                \
         _Pragma("unroll") for (int i = 0; i < G::WROWS; ++i)                                       \
-            BLDS16(RS, woff[i], so_, smem + L::w_off(ST) + (i * 512 + wave * 64) * 16);            \
+            BLDS16(RS, woff[SK8 ? 0 : i], SK8 ? so_ + (unsigned)i * 256u * (unsigned)Ktot : so_, smem + L::w_off(ST) + (i * 512 + wave * 64) * 16); \
     }
-#define ISSUE_P(I, C0, PB) \
-    BLDS16(rs_in, pre[I], __builtin_amdgcn_readfirstlane(2u * (unsigned)(C0)), smem + L::p_off(PB) + ((I) * 512 + wave * 64) * 16)
+#define ISSUE_P(I, C0, PB)                                                                                                             \
+    {                                                                                                                                  \
+        if constexpr (SK8) {                                                                                                           \
+            const int cell_ = wave + 8 * (I);                                                                                          \
+            BLDS16(rs_in, cell_ < G::CELLS ? pre[0] : OOB, __builtin_amdgcn_readfirstlane(2u * (unsigned)((C0) + ((cell_ / 5) * a.W + cell_ % 5) * a.Cin)), \
+                   smem + L::p_off(PB) + ((I) * 512 + wave * 64) * 16);                                                                \
+        } else {                                                                                                                       \
+            BLDS16(rs_in, pre[SK8 ? 0 : (I)], __builtin_amdgcn_readfirstlane(2u * (unsigned)(C0)), smem + L::p_off(PB) + ((I) * 512 + wave * 64) * 16); \
+        }                                                                                                                              \
+    }
 #define TILE_RSRC_W(RS, CH0) RS = __builtin_amdgcn_make_buffer_rsrc((void*)(a.wgt + (size_t)(CH0) * Ktot), 0, wbytes, 0x00020000)
+    // (quadrant tiles: the descriptor starts at cell (0, 0) of quadrant QK's sub-patch in the tile's first image and ends with its last image)
 #define TILE_RSRC_IN(N0)                                                                                                      \
     {                                                                                                                         \
         const int nimg_ = a.N - (N0) < IMGS ? a.N - (N0) : IMGS;                                                              \
-        rs_in = __builtin_amdgcn_make_buffer_rsrc((void*)(a.in + (size_t)(N0) * HWC), 0, 2u * (unsigned)nimg_ * HWC, 0x00020000); \
+        const unsigned qo_ = SK8 ? (unsigned)((PwGeomSkip8::cy0(QK) * a.W + PwGeomSkip8::cx0(QK)) * a.Cin) : 0u;              \
+        rs_in = __builtin_amdgcn_make_buffer_rsrc((void*)(a.in + (size_t)(N0) * HWC + qo_), 0, 2u * ((unsigned)nimg_ * HWC - qo_), 0x00020000); \
     }
 
     // ---- per-lane fragment geometry (tile-independent) ----
@@ -872,8 +996,9 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pwp_kernel(ConvArgs a, int n_t
         }                                                                                                      \
     }
 
-    // conv3x3_pw's pad-skip K-step (PW_STEP_S) with this kernel's prefetch targets
-#define PWP_STEP_S(TAP, WP)                                                                                    \
+    // conv3x3_pw's pad-skip K-step (PW_STEP_S) with this kernel's prefetch targets; GS: which tiles are live and the cell they read —
+    // PwGeomSkip (4x4 maps) or PwSkip8Q<quadrant> (8x8 maps)
+#define PWP_STEP_S(TAP, WP, GS)                                                                                   \
     {                                                                                                          \
         const char* ws_ = smem + L::w_off((TAP) % 3) + a_off + a_byte;                                         \
         const char* pb_ = pb + boff[0];                                                                        \
@@ -882,7 +1007,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pwp_kernel(ConvArgs a, int n_t
                 _Pragma("unroll") for (int i = 0; i < TI; ++i) af[i] = *(const half8*)(ws_ + A_TILE(i));       \
             }                                                                                                  \
             _Pragma("unroll") for (int j = 0; j < TP; ++j)                                                     \
-                if (PwGeomSkip::live(WP, j, TAP, kk)) bfs[j] = *(const half8*)(pb_ + PwGeomSkip::cell(WP, j, TAP) * 1024); \
+                if (GS::live(WP, j, TAP, kk)) bfs[j] = *(const half8*)(pb_ + GS::cell(WP, j, TAP) * 1024); \
             if (kk == 0) {                                                                                     \
                 if ((TAP) < 7) { ISSUE_W(rs_w, ((TAP) + 2) * a.Cin + c32, ((TAP) + 2) % 3); }                  \
                 else if (!last) {                                                                              \
@@ -900,7 +1025,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pwp_kernel(ConvArgs a, int n_t
             __builtin_amdgcn_s_setprio(1);                                                                     \
             _Pragma("unroll") for (int i = 0; i < TI; ++i)                                                     \
                 _Pragma("unroll") for (int j = 0; j < TP; ++j)                                                 \
-                    if (PwGeomSkip::live(WP, j, TAP, kk)) acc[i][j] = mfma_16x16x32<BF>(af[i], bfs[j], acc[i][j]); \
+                    if (GS::live(WP, j, TAP, kk)) acc[i][j] = mfma_16x16x32<BF>(af[i], bfs[j], acc[i][j]); \
             __builtin_amdgcn_s_setprio(0);                                                                     \
             if (kk == 1 && g == 0) END_OF_STEP_WAIT(TAP);                                                      \
             RAW_BARRIER();                                                                                     \
@@ -915,17 +1040,23 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pwp_kernel(ConvArgs a, int n_t
         const int nx_k = tile_last ? 0 : c32 + 32;                                                             \
         /* the last chunk of a tile issues no piece of its own tile any more: the input descriptor becomes the next tile's here */ \
         if (tile_last && more) { TILE_RSRC_IN(n0n) }
-#define PWP_CHUNKS_S(WP)                                                                                       \
+#define PWP_CHUNKS_S(WP, GS)                                                                                   \
     for (int chunk = 0; chunk < nC; ++chunk) {                                                                 \
         PWP_CHUNK_HEAD()                                                                                       \
-        PWP_STEP_S(0, WP) PWP_STEP_S(1, WP) PWP_STEP_S(2, WP) PWP_STEP_S(3, WP) PWP_STEP_S(4, WP)              \
-        PWP_STEP_S(5, WP) PWP_STEP_S(6, WP) PWP_STEP_S(7, WP) PWP_STEP_S(8, WP)                                \
+        PWP_STEP_S(0, WP, GS) PWP_STEP_S(1, WP, GS) PWP_STEP_S(2, WP, GS) PWP_STEP_S(3, WP, GS) PWP_STEP_S(4, WP, GS) \
+        PWP_STEP_S(5, WP, GS) PWP_STEP_S(6, WP, GS) PWP_STEP_S(7, WP, GS) PWP_STEP_S(8, WP, GS)                \
+    }
+    // tile index -> channel tile and first image
+#define PWP_TILE(VB, CH0, N0)                                                                                  \
+    {                                                                                                          \
+        int pt_, ct_;                                                                                          \
+        xcd_tile_map(VB, n_ptiles, n_ctiles, pt_, ct_, a.xcd_split);                                           \
+        CH0 = ct_ * CT; N0 = pt_ * IMGS;                                                                       \
     }
 
-    int vb = blockIdx.x;
-    int ptile, ctile;
-    xcd_tile_map(vb, n_ptiles, n_ctiles, ptile, ctile, a.xcd_split);
-    int ch0 = ctile * CT, n0 = ptile * IMGS;
+    int vb = vb0;
+    int ch0, n0;
+    PWP_TILE(vb, ch0, n0)
     TILE_RSRC_W(rs_w, ch0);
     TILE_RSRC_W(rs_wn, ch0);          // (descriptors are rebuilt, never copied: the opaque type has no host-side copy and the host pass drops the kernel)
     TILE_RSRC_IN(n0)
@@ -936,15 +1067,17 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pwp_kernel(ConvArgs a, int n_t
     __builtin_amdgcn_sched_barrier(0);
     bool stores16 = false;
     while (true) {
-        const int nvb = vb + (int)gridDim.x;
-        const bool more = nvb < n_tiles;
+        const int nvb = vb + vstride;
+        const bool more = nvb < n_walk;
         int ch0n = 0, n0n = 0;
         if (more) {
-            int pt, ct;
-            xcd_tile_map(nvb, n_ptiles, n_ctiles, pt, ct, a.xcd_split);
-            ch0n = ct * CT; n0n = pt * IMGS;
+            PWP_TILE(nvb, ch0n, n0n)
             TILE_RSRC_W(rs_wn, ch0n);
         }
+        // output coordinates of the tile's pixels: G::p_oy / p_ox, inside the quadrant for the quadrant tiles
+        constexpr int oy0 = SK8 ? PwGeomSkip8::oy0(QK) : 0, ox0 = SK8 ? PwGeomSkip8::ox0(QK) : 0;
+#define P_OY(P) (G::p_oy(P) + oy0)
+#define P_OX(P) (G::p_ox(P) + ox0)
         accv acc[TI][TP];
 #pragma unroll
         for (int i = 0; i < TI; ++i)
@@ -961,7 +1094,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pwp_kernel(ConvArgs a, int n_t
         half8 af[TI];
         if constexpr (SKIP) {
             half8 bfs[TP];
-            if (wp == 0) { PWP_CHUNKS_S(0) } else { PWP_CHUNKS_S(1) }     // (wave-uniform: both sides take the same barriers)
+            if (wp == 0) { PWP_CHUNKS_S(0, GS) } else { PWP_CHUNKS_S(1, GS) }     // (wave-uniform: both sides take the same barriers)
         } else {
             half8 bf[4];
             for (int chunk = 0; chunk < nC; ++chunk) {
@@ -983,8 +1116,8 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pwp_kernel(ConvArgs a, int n_t
             for (int i = 0; i < XROWS; ++i) {
                 const int row = (tid >> 2) + 128 * i;
                 const int n = n0 + G::p_img(row);
-                x2off[i] = n < a.N ? (int)((((size_t)(n % a.in2_mod) * a.H2 + (size_t)G::p_oy(row) * a.stride2) * a.W2 +
-                                            (size_t)G::p_ox(row) * a.stride2) * a.Cin2 + lg)
+                x2off[i] = n < a.N ? (int)((((size_t)(n % a.in2_mod) * a.H2 + (size_t)P_OY(row) * a.stride2) * a.W2 +
+                                            (size_t)P_OX(row) * a.stride2) * a.Cin2 + lg)
                                    : -1;
             }
 #define ISSUE_S(C2, ST)                                                                                        \
@@ -1022,19 +1155,26 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pwp_kernel(ConvArgs a, int n_t
             const int chw = ch0 + 128 * g + wc * 64 + 8 * kq;
             // the residual runs of this lane: run h of pixel tile j = 8 channels at chw + 32 h (rows beyond the tensor read row 0, never stored)
             half8_e rres[2][TP];
-            unsigned poff[TP];                                    // element offset of the pixel's row / 8 (< 2^32: launcher)
+            // element offset of the pixel's row / 8 (< 2^32: launcher).  Quadrant tiles: the image is the lane's and the position the tile's, so it is ONE
+            // per-lane value + a wave-uniform one per tile (Cout % 256 == 0: the same row), added where a load or a store needs it — the eight
+            // registers do not fit beside the accumulators, the residual and the Philox words
+            unsigned poff[SK8 ? 1 : TP];
+#define POFF(J, BASE) (SK8 ? (BASE) + (unsigned)(((P_OY(pbase + 16 * (J)) * TW + P_OX(pbase + 16 * (J))) * a.Cout) >> 3) : poff[SK8 ? 0 : (J)])
             int mrow[MSKS ? TP : 1];                              // Masksembles: element offset of this lane's multipliers in the mask table
+            if constexpr (SK8) poff[0] = (unsigned)(((size_t)(n0 + l16 < a.N ? n0 + l16 : 0) * (TH * TW) * a.Cout + chw) >> 3);
 #pragma unroll
             for (int j = 0; j < TP; ++j) {
                 const int p = pbase + 16 * j + l16;
                 const int n = n0 + G::p_img(p);
-                poff[j] = (unsigned)((((size_t)(n < a.N ? n : 0) * (TH * TW) + G::p_oy(p) * TW + G::p_ox(p)) * a.Cout + chw) >> 3);
+                if constexpr (!SK8) poff[j] = (unsigned)((((size_t)(n < a.N ? n : 0) * (TH * TW) + P_OY(p) * TW + P_OX(p)) * a.Cout + chw) >> 3);
                 if constexpr (MSKS) mrow[j] = ((a.site.cnt0 + a.t0 + n / a.B) % a.site.num_masks) * a.Cout + chw;     // Masksembles2D: mask (cnt0 + t) mod M
             }
 #pragma unroll
             for (int h = 0; h < 2; ++h)
 #pragma unroll
-                for (int j = 0; j < TP; ++j) rres[h][j] = *(const half8_e*)(a.res + ((size_t)poff[j] << 3) + 32 * h);
+                for (int j = 0; j < TP; ++j) rres[h][j] = *(const half8_e*)(a.res + ((size_t)POFF(j, poff[0]) << 3) + 32 * h);
+            unsigned poff_st = poff[0];                           // (quadrant tiles: the stores add their offsets again instead of keeping the loads' sums)
+            if constexpr (SK8) asm volatile("" : "+v"(poff_st));
             // the site's Philox calls while the residual is in flight: one call = the 64 channels of (pixel, wave); this lane draws the calls of
             // its own pixel column for the tiles j = kq and kq + 4, the four lanes of a column exchange words (epilogue_lite's distribution)
             philox4 mine[TP / 4];
@@ -1044,7 +1184,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pwp_kernel(ConvArgs a, int n_t
                     const int p = pbase + 16 * (kq + 4 * r) + l16;
                     const int n = n0 + G::p_img(p);
                     const int tl = n / a.B;
-                    const uint64_t e0 = (uint64_t)((n - tl * a.B) * (TH * TW) + G::p_oy(p) * TW + G::p_ox(p)) * a.Cout + ch0 + 128 * g + wc * 64;
+                    const uint64_t e0 = (uint64_t)((n - tl * a.B) * (TH * TW) + P_OY(p) * TW + P_OX(p)) * a.Cout + ch0 + 128 * g + wc * 64;
                     mine[r] = philox_site_call(a.site, e0, (uint32_t)(a.t0 + tl));
                 }
             }
@@ -1101,7 +1241,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pwp_kernel(ConvArgs a, int n_t
                             *(f32x4_e*)(a.pool + (size_t)nimg * a.Cout + chw + 32 * h + 4) = pv[1];
                         }
                     } else if (nimg < a.N) {
-                        *(half8_e*)(a.out + ((size_t)poff[j] << 3) + 32 * h) = o;
+                        *(half8_e*)(a.out + ((size_t)POFF(j, poff_st) << 3) + 32 * h) = o;
                     }
                 }
                 if constexpr (POOLP && SKIP) {
@@ -1178,7 +1318,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pwp_kernel(ConvArgs a, int n_t
             for (int j = 0; j < TP; ++j) {
                 const int p = pbase + 16 * j + l16;
                 const int n = n0 + G::p_img(p);
-                _Float16* const dst = a.out + ((size_t)n * (TH * TW) + G::p_oy(p) * TW + G::p_ox(p)) * a.Cout + chw;
+                _Float16* const dst = a.out + ((size_t)n * (TH * TW) + P_OY(p) * TW + P_OX(p)) * a.Cout + chw;
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
                     half8_e o;
@@ -1237,7 +1377,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pwp_kernel(ConvArgs a, int n_t
                         if (n >= a.N) continue;
                         half8_e v = o8[it];
                         if (it & 1) v = __builtin_shufflevector(v, v, 4, 5, 6, 7, 0, 1, 2, 3);
-                        *(half8_e*)(a.out + ((size_t)n * (TH * TW) + G::p_oy(p) * TW + G::p_ox(p)) * a.Cout + chl + 8 * k) = v;
+                        *(half8_e*)(a.out + ((size_t)n * (TH * TW) + P_OY(p) * TW + P_OX(p)) * a.Cout + chl + 8 * k) = v;
                     }
                 }
             }
@@ -1247,7 +1387,22 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pwp_kernel(ConvArgs a, int n_t
         if (!more) break;
         vb = nvb; ch0 = ch0n; n0 = n0n;
         TILE_RSRC_W(rs_w, ch0);
+#undef POFF
+#undef P_OY
+#undef P_OX
     }
+    };
+    if constexpr (SK8) {
+        switch (wg_kind) {
+            case 0: walk(std::integral_constant<int, 0>{}); break;
+            case 1: walk(std::integral_constant<int, 1>{}); break;
+            case 2: walk(std::integral_constant<int, 2>{}); break;
+            default: walk(std::integral_constant<int, 3>{}); break;
+        }
+    } else {
+        walk(std::integral_constant<int, 0>{});
+    }
+#undef PWP_TILE
 #undef PWP_CHUNKS_S
 #undef PWP_CHUNK_HEAD
 #undef PWP_STEP_S
@@ -1269,13 +1424,19 @@ bool conv_takes_pw_kernel(int ksize, int stride, int pad, int cin, int cout, int
     return ksize == 3 && stride == 1 && pad == 1 && cin % 64 == 0 && cout % 256 == 0 && ho == wo && (ho == 8 || ho == 4);
 }
 
-// SK: the pad-skip form of the 4x4 maps ("pw_pad_skip"; the pooled per-tile launches keep the 4 x 4-block tiles)
-template <int TW, bool SK>
+// SK: the pad-skip form — of the 4x4 maps ("pw_pad_skip"; the pooled per-tile launches keep the 4 x 4-block tiles), or of the 8x8 maps
+// ("pw_pad_skip8": quadrant tiles in the persistent kernel; the per-tile, four-wave and row-table launches keep the 4 x 4-block tiles)
+template <int TW, bool SK_>
 static int launch_pw(const ConvArgs& a_in, hipStream_t s) {
+    constexpr bool SK = SK_ && TW == 4;                          // the per-tile kernel
+    constexpr bool SKP = SK_;                                    // the persistent kernel
     ConvArgs a = a_in;
     a.xcd_split = xcd_split_for(a.Cout / 256, (size_t)a.Cout * 9 * a.Cin * 2);
     const long tiles = (long)((a.N + PwGeom<TW>::IMGS - 1) / PwGeom<TW>::IMGS) * (a.Cout / 256);
-    if (tiles <= 0 || tiles > 0x7fffffffL) return BMI_ERR_INVALID;
+    // (a quadrant tile is 16 images x a quarter of the map: as many tiles up to the ragged last group)
+    const long ptiles = SKP && TW == 8 ? 4L * ((a.N + 15) / 16) * (a.Cout / 256) : tiles;
+    constexpr size_t PIMGS = SKP ? 16 : PwGeom<TW>::IMGS;        // images a persistent tile's input descriptor spans
+    if (tiles <= 0 || tiles > 0x7fffffffL || ptiles > 0x7fffffffL) return BMI_ERR_INVALID;
     const dim3 grid((unsigned)tiles), block(512);
     const int epi = opt_epilogue_lite() ? conv_epilogue_kind(a, 16) : (conv_epilogue_is_plain(a) ? BMI_EPI_PLAIN : BMI_EPI_GENERAL);
     const int epi_fine = opt_epilogue_lite() && !a.imap && opt_conv_pw() < 3 ? conv_epilogue_kind_launch(a, 16) : epi;   // (the specialised lite forms: same bits)
@@ -1309,20 +1470,20 @@ static int launch_pw(const ConvArgs& a_in, hipStream_t s) {
         }
     }
     if (opt_pw_persist() && opt_conv_pw() < 3 && epi == BMI_EPI_PLAIN && !a.imap && a.Cin % 64 == 0 && a.Cout <= 512 && (!a.in2 || a.Cin2 % 32 == 0) &&
-        a.in_mod >= a.N /* a tile's images are consecutive tensor rows */ && (size_t)a.H * a.W * a.Cin * PwGeom<TW>::IMGS * 2 < 0xfffffff0ull) {
+        a.in_mod >= a.N /* a tile's images are consecutive tensor rows */ && (size_t)a.H * a.W * a.Cin * PIMGS * 2 < 0xfffffff0ull) {
         // the persistent form (conv3x3_pwp): one workgroup per CU walks the tiles; the same bits
         static const int n_cu = [] {
             int dev = 0, cu = 0;
             if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cu = 0;
             return cu > 0 ? cu : 256;
         }();
-        const dim3 pgrid((unsigned)(tiles < n_cu ? tiles : n_cu));
+        const dim3 pgrid((unsigned)(ptiles < n_cu ? ptiles : SKP && TW == 8 ? n_cu & ~3 : n_cu));   // (quadrant tiles: a quarter of the grid per quadrant kind)
         if (a.in2) {
-            if (a.bf16) hipLaunchKernelGGL((conv3x3_pwp_kernel<TW, true, true, BMI_EPI_PLAIN, false, SK>), pgrid, block, 0, s, a, (int)tiles);
-            else hipLaunchKernelGGL((conv3x3_pwp_kernel<TW, false, true, BMI_EPI_PLAIN, false, SK>), pgrid, block, 0, s, a, (int)tiles);
+            if (a.bf16) hipLaunchKernelGGL((conv3x3_pwp_kernel<TW, true, true, BMI_EPI_PLAIN, false, SKP>), pgrid, block, 0, s, a, (int)ptiles);
+            else hipLaunchKernelGGL((conv3x3_pwp_kernel<TW, false, true, BMI_EPI_PLAIN, false, SKP>), pgrid, block, 0, s, a, (int)ptiles);
         } else {
-            if (a.bf16) hipLaunchKernelGGL((conv3x3_pwp_kernel<TW, true, false, BMI_EPI_PLAIN, false, SK>), pgrid, block, 0, s, a, (int)tiles);
-            else hipLaunchKernelGGL((conv3x3_pwp_kernel<TW, false, false, BMI_EPI_PLAIN, false, SK>), pgrid, block, 0, s, a, (int)tiles);
+            if (a.bf16) hipLaunchKernelGGL((conv3x3_pwp_kernel<TW, true, false, BMI_EPI_PLAIN, false, SKP>), pgrid, block, 0, s, a, (int)ptiles);
+            else hipLaunchKernelGGL((conv3x3_pwp_kernel<TW, false, false, BMI_EPI_PLAIN, false, SKP>), pgrid, block, 0, s, a, (int)ptiles);
         }
         BMI_CHECK_LAUNCH();
         return BMI_OK;
@@ -1335,23 +1496,23 @@ static int launch_pw(const ConvArgs& a_in, hipStream_t s) {
         return BMI_OK;
     }
     if (PWP_DIRECT && opt_pw_persist() && opt_conv_pw() < 3 && (epi_fine == BMI_EPI_LITE_RES || epi_fine == BMI_EPI_LITE_RES_MC || epi_fine == BMI_EPI_LITE_RES_MSK) && !a.in2 && a.Cin % 64 == 0 &&
-        a.Cout <= 512 && a.in_mod >= a.N && (size_t)a.H * a.W * a.Cin * PwGeom<TW>::IMGS * 2 < 0xfffffff0ull && (size_t)a.N * a.Ho * a.Wo * a.Cout < (8ull << 32)) {
+        a.Cout <= 512 && a.in_mod >= a.N && (size_t)a.H * a.W * a.Cin * PIMGS * 2 < 0xfffffff0ull && (size_t)a.N * a.Ho * a.Wo * a.Cout < (8ull << 32)) {
         // the BasicBlock tails on the persistent walk, finished straight from the registers (conv3x3_pwp_kernel<.., EPIK>): the same bits
         static const int n_cu = [] {
             int dev = 0, cu = 0;
             if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cu = 0;
             return cu > 0 ? cu : 256;
         }();
-        const dim3 pgrid((unsigned)(tiles < n_cu ? tiles : n_cu));
+        const dim3 pgrid((unsigned)(ptiles < n_cu ? ptiles : SKP && TW == 8 ? n_cu & ~3 : n_cu));   // (quadrant tiles: a quarter of the grid per quadrant kind)
         if (epi_fine == BMI_EPI_LITE_RES) {
-            if (a.bf16) hipLaunchKernelGGL((conv3x3_pwp_kernel<TW, true, false, BMI_EPI_LITE_RES, false, SK>), pgrid, block, 0, s, a, (int)tiles);
-            else hipLaunchKernelGGL((conv3x3_pwp_kernel<TW, false, false, BMI_EPI_LITE_RES, false, SK>), pgrid, block, 0, s, a, (int)tiles);
+            if (a.bf16) hipLaunchKernelGGL((conv3x3_pwp_kernel<TW, true, false, BMI_EPI_LITE_RES, false, SKP>), pgrid, block, 0, s, a, (int)ptiles);
+            else hipLaunchKernelGGL((conv3x3_pwp_kernel<TW, false, false, BMI_EPI_LITE_RES, false, SKP>), pgrid, block, 0, s, a, (int)ptiles);
         } else if (epi_fine == BMI_EPI_LITE_RES_MSK) {
-            if (a.bf16) hipLaunchKernelGGL((conv3x3_pwp_kernel<TW, true, false, BMI_EPI_LITE_RES_MSK, false, SK>), pgrid, block, 0, s, a, (int)tiles);
-            else hipLaunchKernelGGL((conv3x3_pwp_kernel<TW, false, false, BMI_EPI_LITE_RES_MSK, false, SK>), pgrid, block, 0, s, a, (int)tiles);
+            if (a.bf16) hipLaunchKernelGGL((conv3x3_pwp_kernel<TW, true, false, BMI_EPI_LITE_RES_MSK, false, SKP>), pgrid, block, 0, s, a, (int)ptiles);
+            else hipLaunchKernelGGL((conv3x3_pwp_kernel<TW, false, false, BMI_EPI_LITE_RES_MSK, false, SKP>), pgrid, block, 0, s, a, (int)ptiles);
         } else {
-            if (a.bf16) hipLaunchKernelGGL((conv3x3_pwp_kernel<TW, true, false, BMI_EPI_LITE_RES_MC, false, SK>), pgrid, block, 0, s, a, (int)tiles);
-            else hipLaunchKernelGGL((conv3x3_pwp_kernel<TW, false, false, BMI_EPI_LITE_RES_MC, false, SK>), pgrid, block, 0, s, a, (int)tiles);
+            if (a.bf16) hipLaunchKernelGGL((conv3x3_pwp_kernel<TW, true, false, BMI_EPI_LITE_RES_MC, false, SKP>), pgrid, block, 0, s, a, (int)ptiles);
+            else hipLaunchKernelGGL((conv3x3_pwp_kernel<TW, false, false, BMI_EPI_LITE_RES_MC, false, SKP>), pgrid, block, 0, s, a, (int)ptiles);
         }
         BMI_CHECK_LAUNCH();
         return BMI_OK;
@@ -1408,6 +1569,6 @@ int launch_conv3x3_pw(const ConvArgs& a, hipStream_t s) {
     if (a.N <= 0 || a.in_mod <= 0 || a.B <= 0 || (a.res && a.res_mod <= 0)) return BMI_ERR_INVALID;
     if ((size_t)a.in_mod * a.H * a.W * a.Cin >= 0x7fffffffull) return BMI_ERR_UNSUPPORTED;   // 31-bit DMA source offsets
     if (a.in2 && (size_t)a.in2_mod * a.H2 * a.W2 * a.Cin2 >= 0x7fffffffull) return BMI_ERR_UNSUPPORTED;
-    if (a.Ho == 8) return launch_pw<8, false>(a, s);
+    if (a.Ho == 8) return opt_pw_pad_skip8() ? launch_pw<8, true>(a, s) : launch_pw<8, false>(a, s);
     return opt_pw_pad_skip() ? launch_pw<4, true>(a, s) : launch_pw<4, false>(a, s);
 }

@@ -214,6 +214,9 @@ const char* bmi_error_string(int code);
  *   "pw_pad_skip"                           0 | 1: conv3x3_pw on 4x4 maps takes an MFMA pixel tile to be ONE output position across the tile's 16 images,
  *                                           so a (position, tap) pair that reads the zero-padding ring is a whole tile that is neither fetched, read
  *                                           nor multiplied (1, default), or a 4 x 4 block of one image with the ring in LDS (0); the same bits either way
+ *   "pw_pad_skip8"                          0 | 1: the same on 8x8 maps, persistent conv3x3_pw launches only: a workgroup tile is 16 images x one 4x4
+ *                                           quadrant of the map, its sub-patch the quadrant's 5 x 5 real input cells (1, default), or four whole
+ *                                           images in 4 x 4 blocks with the ring in LDS (0); the same bits either way
  *   "lazy_planar"                           0 | 1: a lazy site whose readers are all stride-2 consumers (conv3x3_s2 on 32x32 maps, the fused 1x1
  *                                           stride-2 shortcut of conv3x3_patch) stores its scaled copy and keep bits as 32-channel planes with
  *                                           the even columns of a row in front of the odd ones — what such a reader DMAs is then contiguous,
