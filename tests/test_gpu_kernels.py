@@ -225,6 +225,7 @@ def _head_ref(x_nhwk, in_mod, B, tc, t0, seed, w, b, out_dim, site, site_logits,
     (10, 2048, 16, 5, None, "f16", True),                # ResNet-50 final head: K in four LDS chunks; deterministic input (in_mod = B)
     (100, 256, 4, 33, "channel", "bf16", False),         # bf16 bits, 2x2 maps, K < one chunk
     (10, 96, 1, 2, "logits", "f16", False),              # dropout on the LOGITS (converter/pytorch rule); K = 96: 7-chunk swizzle
+    (10, 128, 6, 3, "elementwise", "f16", False),        # a non-square map: HW = 6 (2x3)
 ])
 def test_head_fused(out_dim, K, HW, tc, site_kind, in_kind, det):
     """bmi_head_fused = pool + site + Linear + softmax + float64 moment sums in one launch, against a float64 reference;
@@ -235,7 +236,7 @@ def test_head_fused(out_dim, K, HW, tc, site_kind, in_kind, det):
     in_mod = B if det else N
     g = _gen(8)
     h = int(HW ** 0.5)
-    x = torch.randn(in_mod, h, h, K, generator=g)
+    x = torch.randn(in_mod, h, HW // h, K, generator=g)
     tdt = dict(f16=torch.float16, bf16=torch.bfloat16, f32=torch.float32)[in_kind]
     xd = x.to(tdt).to(DEV)
     w = torch.zeros((out_dim + 31) // 32 * 32, K)
