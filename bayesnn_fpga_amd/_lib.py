@@ -18,6 +18,7 @@ FP32_ACT_DTYPES = ("f32", "f16x2", "bf16x3")      # engines that keep fp32 activ
 OP_STEM, OP_CONV, OP_MASK, OP_HEAD, OP_MAXPOOL, OP_DENSE = 1, 2, 3, 4, 5, 6
 STOP_RULES = {"sem": 0, "margin": 1}      # BMI_STOP_* of bmi_forward_mcd_adaptive
 EXIT_RULES = {"confidence": 0, "margin": 1}      # BMI_EXIT_* of bmi_forward_mcd_exit_staged
+STOP_ON = {"exit": 0, "ensemble": 1}      # BMI_STOP_ON_* of bmi_forward_mcd_adaptive_ensemble
 
 
 class ExitRule(C.Structure):
@@ -29,7 +30,7 @@ CONV_FAMILY_KERNELS = ("conv3x3_patch_kernel", "conv_igemm_wide_kernel", "conv_i
 ABI_VERSION = 600             # BMI_VERSION of include/bayesnn_fpga_amd.h this binding was written against
 CONV_FAMILIES = len(CONV_FAMILY_KERNELS)     # BMI_CONV_FAMILIES
 PROFILE_NAMES = {OP_STEM: "stem", OP_CONV: "conv_igemm", OP_MASK: "mask", OP_HEAD: "head", OP_MAXPOOL: "maxpool",
-                 OP_DENSE: "dense"}
+                 OP_DENSE: "dense", 7: "ensemble"}      # 7: BMI_PROFILE_ENSEMBLE (the row-table entry points' ensemble.hip launches)
 
 
 class Site(C.Structure):
@@ -98,6 +99,13 @@ _PROTOS = {
     "bmi_forward_mcd_adaptive": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_int32,
                                            C.c_int32, C.c_double, C.c_int32] + [C.c_void_p] * 6 + [C.POINTER(C.c_int32), C.c_void_p,
                                                                                                    C.c_size_t, C.c_void_p]),
+    "bmi_forward_mcd_adaptive_ensemble": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_int32,
+                                                    C.c_int32, C.c_double, C.c_int32, C.c_int32] + [C.c_void_p] * 8 + [C.c_size_t] +
+                                          [C.c_void_p] * 2 + [C.POINTER(C.c_int32), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "bmi_forward_mcd_exit_staged_ensemble": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_uint64, C.c_int32, C.POINTER(ExitRule)] +
+                                             [C.c_void_p] * 8 + [C.c_size_t, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p, C.c_size_t,
+                                                                 C.c_void_p]),
+    "bmi_finalize_ensemble_per_image": (C.c_int, [C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 11),
     "bmi_finalize_per_image": (C.c_int, [C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 13),
     "bmi_finalize": (C.c_int, [C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                C.c_void_p, C.c_void_p]),

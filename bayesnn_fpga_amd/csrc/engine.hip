@@ -1644,9 +1644,12 @@ int bmi_forward_mcd_exit(bmi_handle h, const float* x_nchw, int32_t batch, int32
     return BMI_OK;
 }
 
-int bmi_forward_mcd_exit_staged(bmi_handle h, const float* x_nchw, int32_t batch, int32_t t_count, uint64_t seed, int32_t mask_cnt0,
-                                const bmi_exit_rule* rule, double* S1, double* S2, double* SL, double* SH, int32_t* exit_of_image,
-                                int32_t* active_after, void* workspace, size_t workspace_bytes, bmi_stream stream) {
+// bmi_forward_mcd_exit_staged (ens null) and bmi_forward_mcd_exit_staged_ensemble: with ens every stage's heads also leave their logits in
+// the one [t_count][E][batch][C] scratch (active images only), and ONE launch of ensemble.hip behind the last stage that ran adds, for
+// every image, the exits it reached (n_e[b] = exit_of_image[b] + 1) to the ensemble sums
+static int exit_staged(bmi_handle h, const float* x_nchw, int32_t batch, int32_t t_count, uint64_t seed, int32_t mask_cnt0,
+                       const bmi_exit_rule* rule, double* S1, double* S2, double* SL, double* SH, int32_t* exit_of_image, int32_t* active_after,
+                       void* workspace, size_t workspace_bytes, bmi_stream stream, const EnsembleSums* ens) {
     if (!h || !x_nchw || !rule || !S1 || !S2 || !SL || !workspace || !exit_of_image || !active_after) return BMI_ERR_INVALID;
     BmiOptionScope opt_scope(&h->opts);
     if (rule->criterion != BMI_EXIT_CONFIDENCE && rule->criterion != BMI_EXIT_MARGIN) return BMI_ERR_INVALID;
@@ -1662,6 +1665,7 @@ int bmi_forward_mcd_exit_staged(bmi_handle h, const float* x_nchw, int32_t batch
     if (workspace_bytes < h->ws_bytes) return BMI_ERR_NOMEM;
     Pass p{x_nchw, (char*)workspace, (hipStream_t)stream, batch, seed, mask_cnt0};
     p.S1 = S1; p.S2 = S2; p.SL = SL; p.SH = SH;
+    if (ens) { p.logits = ens->scratch; p.logits_t_begin = 0; }
     const hipStream_t s = p.stream;
     int* lists[2] = {(int*)(p.ws + h->exit_off), (int*)(p.ws + h->exit_off) + h->max_batch};
     int* count_dev = (int*)(p.ws + h->exit_off) + 2 * h->max_batch;
@@ -1669,6 +1673,16 @@ int bmi_forward_mcd_exit_staged(bmi_handle h, const float* x_nchw, int32_t batch
     int rc = launch_fill_int(exit_of_image, batch, last, s);
     if (rc != BMI_OK) return rc;
     for (int x = 0; x < h->n_exits; ++x) active_after[x] = 0;
+    // the ensemble read-out behind the last stage that ran: exit_of_image is final and both image lists are dead (n_e takes the first)
+    auto ensemble_readout = [&]() -> int {
+        if (!ens) return BMI_OK;
+        ProfScope prof(h, BMI_PROFILE_ENSEMBLE, s);
+        prof.r.images = t_count * batch;
+        const int rce = launch_exit_counts(exit_of_image, batch, lists[0], s);
+        if (rce != BMI_OK) return rce;
+        return launch_ensemble_moments(ens->scratch, t_count, h->n_exits, batch, h->out_dim, h->inv_tau.empty() ? nullptr : h->inv_tau.data(),
+                                       ens->Q1, ens->Q2, ens->QH, s, nullptr, 0, lists[0]);
+    };
     const int* act = nullptr;      // null: every image is still active (stage 0: bmi_forward_mcd's launches)
     const int* rows = nullptr;
     int bc = batch, cur = 0;
@@ -1696,7 +1710,7 @@ int bmi_forward_mcd_exit_staged(bmi_handle h, const float* x_nchw, int32_t batch
         if (hipMemcpyAsync(&n_active, count_dev, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
             return BMI_ERR_HIP;
         active_after[e] = n_active;
-        if (n_active == 0) return BMI_OK;                    // every image has left: the later stages do not run at all
+        if (n_active == 0) return ensemble_readout();        // every image has left: the later stages do not run at all
         act = lists[cur];
         bc = n_active;
         cur ^= 1;
@@ -1704,14 +1718,37 @@ int bmi_forward_mcd_exit_staged(bmi_handle h, const float* x_nchw, int32_t batch
         if (rc != BMI_OK) return rc;
         rows = rows_dev;
     }
-    return BMI_OK;
+    return ensemble_readout();
 }
 
-int bmi_forward_mcd_adaptive(bmi_handle h, const float* x_nchw, int32_t batch, int32_t image_offset, int32_t t_max,
-                             int32_t t_step, uint64_t seed, int32_t mask_cnt0, int32_t rule, double threshold,
-                             int32_t test_exit, double* S1, double* S2, double* SL, double* SH, int32_t* t_used,
-                             uint8_t* converged, int32_t* active_after_step, void* workspace, size_t workspace_bytes,
-                             bmi_stream stream) {
+int bmi_forward_mcd_exit_staged(bmi_handle h, const float* x_nchw, int32_t batch, int32_t t_count, uint64_t seed, int32_t mask_cnt0,
+                                const bmi_exit_rule* rule, double* S1, double* S2, double* SL, double* SH, int32_t* exit_of_image,
+                                int32_t* active_after, void* workspace, size_t workspace_bytes, bmi_stream stream) {
+    return exit_staged(h, x_nchw, batch, t_count, seed, mask_cnt0, rule, S1, S2, SL, SH, exit_of_image, active_after, workspace, workspace_bytes,
+                       stream, nullptr);
+}
+
+int bmi_forward_mcd_exit_staged_ensemble(bmi_handle h, const float* x_nchw, int32_t batch, int32_t t_count, uint64_t seed, int32_t mask_cnt0,
+                                         const bmi_exit_rule* rule, double* S1, double* S2, double* SL, double* SH, double* Q1, double* Q2,
+                                         double* QH, void* scratch, size_t scratch_bytes, int32_t* exit_of_image, int32_t* active_after,
+                                         void* workspace, size_t workspace_bytes, bmi_stream stream) {
+    if (!h || !Q1 || !Q2 || !QH || !scratch) return BMI_ERR_INVALID;
+    if (!ensemble_takes(h->n_exits, h->out_dim)) return BMI_ERR_UNSUPPORTED;
+    if (h->max_batch == 0 || batch < 1 || batch > h->max_batch) return BMI_ERR_INVALID;
+    if (scratch_bytes < bmi_ensemble_scratch_bytes(h, batch)) return BMI_ERR_NOMEM;
+    const EnsembleSums ens{Q1, Q2, QH, (float*)scratch};
+    return exit_staged(h, x_nchw, batch, t_count, seed, mask_cnt0, rule, S1, S2, SL, SH, exit_of_image, active_after, workspace, workspace_bytes,
+                       stream, &ens);
+}
+
+// bmi_forward_mcd_adaptive (ens null) and bmi_forward_mcd_adaptive_ensemble: with ens every step's heads also leave their logits in the
+// scratch (one step of [t_step][E][batch][C]) and one launch of ensemble.hip behind them adds the step's samples of the images that ran it
+// to the ensemble sums — the full form while nobody has retired, the image-list form afterwards; stop_on = BMI_STOP_ON_ENSEMBLE: the rule
+// reads Q1 / Q2 at row test_exit in place of S1 / S2
+static int adaptive(bmi_handle h, const float* x_nchw, int32_t batch, int32_t image_offset, int32_t t_max, int32_t t_step, uint64_t seed,
+                    int32_t mask_cnt0, int32_t rule, double threshold, int32_t test_exit, double* S1, double* S2, double* SL, double* SH,
+                    int32_t* t_used, uint8_t* converged, int32_t* active_after_step, void* workspace, size_t workspace_bytes, bmi_stream stream,
+                    const EnsembleSums* ens, int stop_on) {
     const int rco = bmi_image_offset_ok(h, image_offset);      // (a null handle: BMI_ERR_INVALID)
     if (rco != BMI_OK) return rco;
     BmiOptionScope opt_scope(&h->opts);
@@ -1733,6 +1770,8 @@ int bmi_forward_mcd_adaptive(bmi_handle h, const float* x_nchw, int32_t batch, i
     int* count_dev = (int*)(p.ws + h->exit_off) + 2 * h->max_batch;
     int* rows_dev = count_dev + 64;
     const size_t eo = (size_t)test_exit * batch * h->out_dim;
+    const double* const R1 = (stop_on == BMI_STOP_ON_ENSEMBLE ? ens->Q1 : S1) + eo;      // the [batch][C] sums the rule reads
+    const double* const R2 = (stop_on == BMI_STOP_ON_ENSEMBLE ? ens->Q2 : S2) + eo;
     const int n_steps = (t_max + t_step - 1) / t_step;
     for (int k = 0; k < n_steps; ++k) active_after_step[k] = 0;
     int rc;
@@ -1745,10 +1784,18 @@ int bmi_forward_mcd_adaptive(bmi_handle h, const float* x_nchw, int32_t batch, i
     int bc = batch, cur = 0;
     for (int k = 0, t0 = 0; k < n_steps; ++k, t0 += t_step) {
         const int tc = std::min(t_step, t_max - t0);
+        if (ens) { p.logits = ens->scratch; p.logits_t_begin = t0; }
         rc = run_suffix(h, p, tc * bc, t0, imap, bc, rows);
         if (rc != BMI_OK) return rc;
+        if (ens) {
+            ProfScope prof(h, BMI_PROFILE_ENSEMBLE, s);
+            prof.r.images = tc * bc;
+            rc = launch_ensemble_moments(ens->scratch, tc, h->n_exits, batch, h->out_dim, h->inv_tau.empty() ? nullptr : h->inv_tau.data(), ens->Q1,
+                                         ens->Q2, ens->QH, s, imap, bc);
+            if (rc != BMI_OK) return rc;
+        }
         // the stop rule over the still-active images, on the device; the host only learns how many go on
-        rc = launch_adaptive_decide(S1 + eo, S2 + eo, h->out_dim, t0 + tc, rule, threshold, imap, bc, lists[cur], count_dev, t_used, s);
+        rc = launch_adaptive_decide(R1, R2, h->out_dim, t0 + tc, rule, threshold, imap, bc, lists[cur], count_dev, t_used, s);
         if (rc != BMI_OK) return rc;
         int n_active = 0;
         if (hipMemcpyAsync(&n_active, count_dev, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
@@ -1763,7 +1810,31 @@ int bmi_forward_mcd_adaptive(bmi_handle h, const float* x_nchw, int32_t batch, i
         if (rc != BMI_OK) return rc;
         rows = rows_dev;
     }
-    return converged ? launch_adaptive_converged(S1 + eo, S2 + eo, h->out_dim, rule, threshold, batch, t_used, converged, s) : BMI_OK;
+    return converged ? launch_adaptive_converged(R1, R2, h->out_dim, rule, threshold, batch, t_used, converged, s) : BMI_OK;
+}
+
+int bmi_forward_mcd_adaptive(bmi_handle h, const float* x_nchw, int32_t batch, int32_t image_offset, int32_t t_max,
+                             int32_t t_step, uint64_t seed, int32_t mask_cnt0, int32_t rule, double threshold,
+                             int32_t test_exit, double* S1, double* S2, double* SL, double* SH, int32_t* t_used,
+                             uint8_t* converged, int32_t* active_after_step, void* workspace, size_t workspace_bytes,
+                             bmi_stream stream) {
+    return adaptive(h, x_nchw, batch, image_offset, t_max, t_step, seed, mask_cnt0, rule, threshold, test_exit, S1, S2, SL, SH, t_used, converged,
+                    active_after_step, workspace, workspace_bytes, stream, nullptr, BMI_STOP_ON_EXIT);
+}
+
+int bmi_forward_mcd_adaptive_ensemble(bmi_handle h, const float* x_nchw, int32_t batch, int32_t image_offset, int32_t t_max, int32_t t_step,
+                                      uint64_t seed, int32_t mask_cnt0, int32_t rule, double threshold, int32_t test_exit, int32_t stop_on,
+                                      double* S1, double* S2, double* SL, double* SH, double* Q1, double* Q2, double* QH, void* scratch,
+                                      size_t scratch_bytes, int32_t* t_used, uint8_t* converged, int32_t* active_after_step, void* workspace,
+                                      size_t workspace_bytes, bmi_stream stream) {
+    if (!h || !Q1 || !Q2 || !QH || !scratch) return BMI_ERR_INVALID;
+    if (stop_on != BMI_STOP_ON_EXIT && stop_on != BMI_STOP_ON_ENSEMBLE) return BMI_ERR_INVALID;
+    if (!ensemble_takes(h->n_exits, h->out_dim)) return BMI_ERR_UNSUPPORTED;
+    if (h->max_batch == 0 || batch < 1 || batch > h->max_batch) return BMI_ERR_INVALID;
+    if (scratch_bytes < bmi_ensemble_scratch_bytes(h, batch)) return BMI_ERR_NOMEM;
+    const EnsembleSums ens{Q1, Q2, QH, (float*)scratch};
+    return adaptive(h, x_nchw, batch, image_offset, t_max, t_step, seed, mask_cnt0, rule, threshold, test_exit, S1, S2, SL, SH, t_used, converged,
+                    active_after_step, workspace, workspace_bytes, stream, &ens, stop_on);
 }
 
 int bmi_finalize_per_image(int32_t n_exits, int32_t batch, int32_t out_dim, const int32_t* t_used, const double* S1,
@@ -1808,6 +1879,17 @@ int bmi_finalize_ensemble(int32_t n_exits, int32_t batch, int32_t out_dim, int32
     if ((int64_t)n_exits * batch > INT32_MAX) return BMI_ERR_UNSUPPORTED;
     return launch_finalize_ensemble(n_exits * batch, out_dim, t_total, Q1, Q2, QH, ens_mean, ens_var, pred_entropy, exp_entropy, mutual_info,
                                     nonfinite, (hipStream_t)stream);
+}
+
+int bmi_finalize_ensemble_per_image(int32_t n_exits, int32_t batch, int32_t out_dim, const int32_t* t_used, const double* Q1, const double* Q2,
+                                    const double* QH, double* ens_mean, double* ens_var, double* pred_entropy, double* exp_entropy,
+                                    double* mutual_info, int32_t* nonfinite, bmi_stream stream) {
+    if (!t_used || !Q1 || !Q2 || !QH || !ens_mean || !ens_var || !pred_entropy || !exp_entropy || !mutual_info || n_exits < 1 || batch < 1 ||
+        out_dim < 1)
+        return BMI_ERR_INVALID;
+    if ((int64_t)n_exits * batch > INT32_MAX) return BMI_ERR_UNSUPPORTED;
+    return launch_finalize_ensemble_per_image(n_exits, batch, out_dim, t_used, Q1, Q2, QH, ens_mean, ens_var, pred_entropy, exp_entropy,
+                                              mutual_info, nonfinite, (hipStream_t)stream);
 }
 
 int bmi_ensemble_moments(const float* logits, int32_t T, int32_t E, int32_t B, int32_t C, const float* tau, double* Q1, double* Q2, double* QH,

@@ -29,16 +29,24 @@
 
 struct EnsTau { float inv[BMI_ENS_MAX_EXITS]; };
 
-__global__ __launch_bounds__(ENS_THREADS) void ensemble_moments_kernel(const float* __restrict__ logits, int T, int E, int B, int C, int CS, int TS,
-                                                                       int L, EnsTau tau, double* __restrict__ Q1, double* __restrict__ Q2,
-                                                                       double* __restrict__ QH) {
+// ROWS (bmi_forward_mcd_adaptive_ensemble, bmi_forward_mcd_exit_staged_ensemble): workgroup i works on image b = list[i] of the B-image
+// batch (list null: b = i) and on its first n_e[b] exits only (n_e null: all E) — the running exit sum is cut there, so the rows
+// e < n_e[b] are the full form's bits; `logits` and the sums keep the ORIGINAL image index, rows of other images and of later exits are
+// neither read nor written.  Both lookups are the same for the whole workgroup.  Not ROWS: the code as it was.
+template <bool ROWS>
+__global__ __launch_bounds__(ENS_THREADS) void ensemble_moments_kernel(const float* __restrict__ logits, int T, int E_all, int B, int C, int CS,
+                                                                       int TS, int L, EnsTau tau, double* __restrict__ Q1,
+                                                                       double* __restrict__ Q2, double* __restrict__ QH,
+                                                                       const int* __restrict__ list, const int* __restrict__ n_e) {
 #pragma clang fp contract(off)
     __shared__ double pq[ENS_SLAB];                      // [row][CS], row = tl * E + e: exp(z - max), then q
     __shared__ double ql[ENS_SLAB];                      // q log q
     __shared__ double row_sum[ENS_ROWS], row_h[ENS_ROWS];
     __shared__ float inv_s[BMI_ENS_MAX_EXITS];
     const int tid = threadIdx.x;
-    const int b = blockIdx.x;
+    const int b = (ROWS && list) ? list[blockIdx.x] : (int)blockIdx.x;
+    const int E = (ROWS && n_e) ? min(n_e[b], E_all) : E_all;       // the exits of THIS image (rows of the chunk: [tl][E])
+    if (ROWS && (E < 1 || (unsigned)b >= (unsigned)B)) return;       // (the whole workgroup)
     const int lane = tid & (L - 1), grp = tid / L, ngrp = ENS_THREADS / L;
     if (tid < E) inv_s[tid] = tau.inv[tid];
     for (int t0 = 0; t0 < T; t0 += TS) {
@@ -49,7 +57,7 @@ __global__ __launch_bounds__(ENS_THREADS) void ensemble_moments_kernel(const flo
             const int r = r0 + grp;
             const bool live = r < rows;
             const int tl = live ? r / E : 0, e = live ? r - tl * E : 0;
-            const float* src = logits + (((size_t)(t0 + tl) * E + e) * B + b) * C;
+            const float* src = logits + (((size_t)(t0 + tl) * E_all + e) * B + b) * C;
             const float inv = inv_s[e];
             float mx = -INFINITY;
             if (live)
@@ -112,8 +120,8 @@ bool ensemble_takes(int E, int C) {
 }
 
 int launch_ensemble_moments(const float* logits, int T, int E, int B, int C, const float* inv_tau, double* Q1, double* Q2, double* QH,
-                            hipStream_t s) {
-    if (T < 1 || B < 1) return BMI_ERR_INVALID;
+                            hipStream_t s, const int* list, int Bc, const int* n_e) {
+    if (T < 1 || B < 1 || (list && (Bc < 1 || Bc > B))) return BMI_ERR_INVALID;
     if (!ensemble_takes(E, C)) return BMI_ERR_UNSUPPORTED;
     const int CS = C | 1;                                // odd row stride
     const int TS = std::min(ENS_SLAB / (E * CS), ENS_ROWS / E);      // >= 1 (ensemble_takes)
@@ -121,20 +129,42 @@ int launch_ensemble_moments(const float* logits, int T, int E, int B, int C, con
     while (L < C && L < 64) L <<= 1;
     EnsTau tau;
     for (int e = 0; e < BMI_ENS_MAX_EXITS; ++e) tau.inv[e] = (inv_tau && e < E) ? inv_tau[e] : 1.f;
-    hipLaunchKernelGGL(ensemble_moments_kernel, dim3((unsigned)B), dim3(ENS_THREADS), 0, s, logits, T, E, B, C, CS, TS, L, tau, Q1, Q2, QH);
+    if (list || n_e)
+        hipLaunchKernelGGL((ensemble_moments_kernel<true>), dim3((unsigned)(list ? Bc : B)), dim3(ENS_THREADS), 0, s, logits, T, E, B, C, CS, TS, L,
+                           tau, Q1, Q2, QH, list, n_e);
+    else
+        hipLaunchKernelGGL((ensemble_moments_kernel<false>), dim3((unsigned)B), dim3(ENS_THREADS), 0, s, logits, T, E, B, C, CS, TS, L, tau, Q1, Q2,
+                           QH, (const int*)nullptr, (const int*)nullptr);
+    BMI_CHECK_LAUNCH();
+    return BMI_OK;
+}
+
+// n_e[b] = exit_of[b] + 1: the exits image b ran under bmi_forward_mcd_exit_staged, the per-image exit count of the launch above
+__global__ void exit_counts_kernel(const int* __restrict__ exit_of, int n, int* __restrict__ n_e) {
+    const int b = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (b < n) n_e[b] = exit_of[b] + 1;
+}
+
+int launch_exit_counts(const int* exit_of, int n, int* n_e, hipStream_t s) {
+    if (!exit_of || !n_e || n < 1) return BMI_ERR_INVALID;
+    hipLaunchKernelGGL(exit_counts_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, exit_of, n, n_e);
     BMI_CHECK_LAUNCH();
     return BMI_OK;
 }
 
 // One wave per (exit, image) row: mean = Q1 / T, var = max(Q2 / T - mean^2, 0) (ddof 0, a NaN stays a NaN), the entropy of the mean by
 // float64 wavefront shuffle like finalize_uncertainty_kernel, expected entropy QH / T, mutual information clamped at 0.
+// PER_IMAGE (bmi_finalize_ensemble_per_image): row (exit, image b) divides by t_used[b].
+template <bool PER_IMAGE = false>
 __global__ __launch_bounds__(256) void finalize_ensemble_kernel(int rows, int C, double t, const double* __restrict__ Q1,
                                                                 const double* __restrict__ Q2, const double* __restrict__ QH,
                                                                 double* __restrict__ mean, double* __restrict__ var, double* __restrict__ pred,
-                                                                double* __restrict__ expd, double* __restrict__ mi, int* nonfinite) {
+                                                                double* __restrict__ expd, double* __restrict__ mi, int* nonfinite,
+                                                                const int* __restrict__ t_used, int batch) {
 #pragma clang fp contract(off)
     const int row = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6), lane = threadIdx.x & 63;
     if (row >= rows) return;                       // (wave-uniform)
+    if (PER_IMAGE) t = (double)t_used[row % batch];
     double h = 0.0;
     int bad = 0;
     for (int c = lane; c < C; c += 64) {
@@ -168,8 +198,18 @@ __global__ __launch_bounds__(256) void finalize_ensemble_kernel(int rows, int C,
 int launch_finalize_ensemble(int n_rows, int C, int t_total, const double* Q1, const double* Q2, const double* QH, double* mean, double* var,
                              double* pred, double* expd, double* mi, int* nonfinite, hipStream_t s) {
     if (n_rows <= 0 || C <= 0 || t_total <= 0) return BMI_ERR_INVALID;
-    hipLaunchKernelGGL(finalize_ensemble_kernel, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, s, n_rows, C, (double)t_total, Q1, Q2, QH, mean,
-                       var, pred, expd, mi, nonfinite);
+    hipLaunchKernelGGL((finalize_ensemble_kernel<false>), dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, s, n_rows, C, (double)t_total, Q1, Q2,
+                       QH, mean, var, pred, expd, mi, nonfinite, (const int*)nullptr, 1);
+    BMI_CHECK_LAUNCH();
+    return BMI_OK;
+}
+
+int launch_finalize_ensemble_per_image(int n_exits, int batch, int C, const int* t_used, const double* Q1, const double* Q2, const double* QH,
+                                       double* mean, double* var, double* pred, double* expd, double* mi, int* nonfinite, hipStream_t s) {
+    if (n_exits <= 0 || batch <= 0 || C <= 0 || !t_used) return BMI_ERR_INVALID;
+    const int n_rows = n_exits * batch;
+    hipLaunchKernelGGL((finalize_ensemble_kernel<true>), dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, s, n_rows, C, 1.0, Q1, Q2, QH, mean, var,
+                       pred, expd, mi, nonfinite, t_used, batch);
     BMI_CHECK_LAUNCH();
     return BMI_OK;
 }

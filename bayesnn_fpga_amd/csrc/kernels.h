@@ -187,11 +187,17 @@ int launch_nll_temperature_grid(const float* logits, int T, int E, int B, int C,
 #define BMI_ENS_MAX_EXITS 32
 #define BMI_ENS_MAX_CLASSES 128
 bool ensemble_takes(int E, int C);
+// list / Bc / n_e (device int32, each null: not used): the launch covers the Bc images list[0 .. Bc-1] of the batch only, and of image b only
+// its first n_e[b] exits; every row that is computed holds the plain launch's bits, the other rows are neither read nor written
 int launch_ensemble_moments(const float* logits, int T, int E, int B, int C, const float* inv_tau, double* Q1, double* Q2, double* QH,
-                            hipStream_t s);
+                            hipStream_t s, const int* list = nullptr, int Bc = 0, const int* n_e = nullptr);
+int launch_exit_counts(const int* exit_of, int n, int* n_e, hipStream_t s);      // n_e[b] = exit_of[b] + 1 (staged exit: the exits image b ran)
 // per (exit, image): mean / var of Q1 / Q2, the entropy of the mean, QH / T and their difference (bmi_finalize_ensemble)
 int launch_finalize_ensemble(int n_rows, int C, int t_total, const double* Q1, const double* Q2, const double* QH, double* mean, double* var,
                              double* pred, double* expd, double* mi, int* nonfinite, hipStream_t s);
+// the same with row (exit, image b) divided by t_used[b] (bmi_finalize_ensemble_per_image)
+int launch_finalize_ensemble_per_image(int n_exits, int batch, int C, const int* t_used, const double* Q1, const double* Q2, const double* QH,
+                                       double* mean, double* var, double* pred, double* expd, double* mi, int* nonfinite, hipStream_t s);
 int launch_philox_mask(uint8_t* keep, int64_t n, uint64_t seed, int site, int t, float p, hipStream_t s);
 // planar_w > 0: the bits in the lazy site's planar layout (rows of planar_w pixels; 2-bit sites, c % 64 == 0)
 int launch_mask_bits(uint8_t* bits, int n, int hw, int c, const SiteArgs& site, int batch, int t0, hipStream_t s, int planar_w = 0);

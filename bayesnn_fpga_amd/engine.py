@@ -300,6 +300,14 @@ def model_exits(model):
     return 4 if getattr(model, "multi_exit", True) else 1
 
 
+def check_stop_on(stop_on, ensemble):
+    """``stop_on`` of accumulate_adaptive / predict_adaptive: "exit" or "ensemble", the latter only with ``ensemble=True`` (host only)."""
+    if stop_on not in _lib.STOP_ON:
+        raise ValueError(f"stop_on must be one of {sorted(_lib.STOP_ON)}, got {stop_on!r}")
+    if stop_on == "ensemble" and not ensemble:
+        raise ValueError('stop_on="ensemble" needs ensemble=True: the rule reads the exit-ensemble sums')
+
+
 def check_temperature(tau, n_exits):
     """``tau`` as a plain list of ``n_exits`` Python floats, or None (off): a scalar stands for every exit; raises ValueError for a wrong
     count, a non-finite or a non-positive entry, or one whose float32 value (what the device is given) is not finite and positive."""
@@ -678,6 +686,34 @@ class MCDEngine(CompiledGraph):
         _lib.check(rc, "bmi_finalize_ensemble")
         return dict(ens_mean=mv[0], ens_var=mv[1], ens_pred_entropy=ent[0], ens_exp_entropy=ent[1], ens_mutual_info=ent[2])
 
+    def finalize_ensemble_per_image(self, Q, QH, t_used):
+        """The five ``ens_*`` entries of ``finalize_ensemble`` with image b's sums divided by its own sample count t_used[b]
+        (bmi_finalize_ensemble_per_image; device int32 [B], every entry >= 1): the read-out of ``accumulate_adaptive(ensemble=True)``."""
+        if Q.dim() != 4 or Q.shape[0] != 2:
+            raise ValueError("ensemble buffers must be contiguous float64 Q [2, E, B, C] and QH [E, B]")
+        _, E, B, Cd = Q.shape
+        if tuple(QH.shape) != (E, B) or Q.dtype != torch.float64 or QH.dtype != torch.float64 or not Q.is_contiguous() or \
+                not QH.is_contiguous():
+            raise ValueError("ensemble buffers must be contiguous float64 Q [2, E, B, C] and QH [E, B]")
+        if tuple(t_used.shape) != (B,) or t_used.dtype != torch.int32 or t_used.device != Q.device:
+            raise ValueError("t_used must be int32 [B] on the ensemble buffers' device")
+        mv = torch.empty(2, E, B, Cd, dtype=torch.float64, device=Q.device)
+        ent = torch.empty(3, E, B, dtype=torch.float64, device=Q.device)
+        with torch.cuda.device(self.device):
+            rc = self.lib.bmi_finalize_ensemble_per_image(E, B, Cd, t_used.contiguous().data_ptr(), Q[0].data_ptr(), Q[1].data_ptr(),
+                                                          QH.data_ptr(), mv[0].data_ptr(), mv[1].data_ptr(), ent[0].data_ptr(),
+                                                          ent[1].data_ptr(), ent[2].data_ptr(), self._nonfinite.data_ptr(), self._stream())
+        _lib.check(rc, "bmi_finalize_ensemble_per_image")
+        return dict(ens_mean=mv[0], ens_var=mv[1], ens_pred_entropy=ent[0], ens_exp_entropy=ent[1], ens_mutual_info=ent[2])
+
+    def _check_ensemble_sums(self, B, H, Q, QH):
+        """The buffers an ensemble read-out under a row table needs beside S: H, Q and QH of ``new_ensemble_sums``."""
+        E, Cd = self.n_exits, self.out_dim
+        for buf, shape, what in ((H, (E, B), "entropy buffer H"), (Q, (2, E, B, Cd), "ensemble buffer Q"),
+                                 (QH, (E, B), "ensemble entropy buffer QH")):
+            if buf is None or tuple(buf.shape) != shape or buf.dtype != torch.float64 or not buf.is_contiguous() or buf.device != self.device:
+                raise ValueError(f"{what} must be contiguous float64 {list(shape)} on {self.device}")
+
     def finalize_ensemble(self, S, H, Q, QH, t_total):
         """``finalize_uncertainty``'s dict plus the read-out of the exit ensembles, float64: ``ens_mean`` and ``ens_var`` (ddof 0) [E, B, C],
         ``ens_pred_entropy`` H[ens_mean], ``ens_exp_entropy`` E_t H[q_t] and ``ens_mutual_info`` (clamped at 0) [E, B]; row 0 is exit 0
@@ -743,10 +779,13 @@ class MCDEngine(CompiledGraph):
         r["best_preds"] = r["mean"][exit_layer.long(), torch.arange(B, device=self.device)]
         return r
 
-    def accumulate_early_exit(self, x, S, T, threshold, seed=0, cnt0=0, first_exit=1, rule="confidence", ensemble=False, H=None):
+    def accumulate_early_exit(self, x, S, T, threshold, seed=0, cnt0=0, first_exit=1, rule="confidence", ensemble=False, H=None, Q=None,
+                              QH=None):
         """The sampling half of ``predict_early_exit`` (bmi_forward_mcd_exit_staged) into the ZEROED sums S [3, E, B, C] (and H [E, B]:
         ``new_uncertainty_sums``): every row it computes equals ``accumulate``'s over samples 0 .. T-1 bit for bit, rows of exits an image
-        never reached stay zero.  Returns (exit_layer int32 [B] on the device, active_after host list [E])."""
+        never reached stay zero.  With ``Q`` and ``QH`` (and H; all ZEROED: ``new_ensemble_sums``) the exit-ensemble sums of the exits every
+        image reached as well (bmi_forward_mcd_exit_staged_ensemble): rows e <= exit_layer[b] are ``accumulate_ensemble``'s bits, the others
+        stay zero; the rule is not changed.  Returns (exit_layer int32 [B] on the device, active_after host list [E])."""
         x = self._check_x(x)
         B = x.shape[0]
         if rule not in _lib.EXIT_RULES:
@@ -760,9 +799,22 @@ class MCDEngine(CompiledGraph):
             raise ValueError("moment buffer must be contiguous float64 [3, E, B, C]")
         if H is not None and (tuple(H.shape) != (self.n_exits, B) or H.dtype != torch.float64 or not H.is_contiguous()):
             raise ValueError("entropy buffer must be contiguous float64 [E, B]")
+        if (Q is None) != (QH is None):
+            raise ValueError("the ensemble read-out needs both Q and QH (new_ensemble_sums)")
+        if Q is not None:
+            self._check_ensemble_sums(B, H, Q, QH)
         exit_layer = torch.empty(B, dtype=torch.int32, device=self.device)
         active = (C.c_int32 * self.n_exits)()
         r_c = _lib.ExitRule(_lib.EXIT_RULES[rule], int(bool(ensemble)), float(threshold), first_exit)
+        if Q is not None:
+            scratch, _ = self._ensemble_scratch(B)
+            with torch.cuda.device(self.device):
+                rc = self.lib.bmi_forward_mcd_exit_staged_ensemble(
+                    self.handle, x.data_ptr(), B, T, int(seed) & 0xFFFFFFFFFFFFFFFF, int(cnt0), C.byref(r_c), S[0].data_ptr(), S[1].data_ptr(),
+                    S[2].data_ptr(), H.data_ptr(), Q[0].data_ptr(), Q[1].data_ptr(), QH.data_ptr(), scratch.data_ptr(), scratch.numel(),
+                    exit_layer.data_ptr(), active, self.workspace.data_ptr(), self.workspace_bytes, self._stream())
+            _lib.check(rc, "bmi_forward_mcd_exit_staged_ensemble")
+            return exit_layer, [int(v) for v in active]
         with torch.cuda.device(self.device):
             rc = self.lib.bmi_forward_mcd_exit_staged(self.handle, x.data_ptr(), B, T, int(seed) & 0xFFFFFFFFFFFFFFFF, int(cnt0), C.byref(r_c),
                                                       S[0].data_ptr(), S[1].data_ptr(), S[2].data_ptr(), None if H is None else H.data_ptr(),
@@ -770,7 +822,8 @@ class MCDEngine(CompiledGraph):
         _lib.check(rc, "bmi_forward_mcd_exit_staged")
         return exit_layer, [int(v) for v in active]
 
-    def predict_early_exit(self, x, T, threshold, seed=0, cnt0=0, first_exit=1, rule="confidence", ensemble=False, uncertainty=False):
+    def predict_early_exit(self, x, T, threshold, seed=0, cnt0=0, first_exit=1, rule="confidence", ensemble=False, uncertainty=False,
+                           ensemble_readout=False):
         """Early exiting by stages on the device (bmi_forward_mcd_exit_staged): unlike ``predict_with_exit`` the later stages skip the
         deterministic trunk too, so with exit-only dropout an image that leaves at exit 1 never runs layer3 / layer4.  After exit e >=
         ``first_exit`` an image leaves when its statistic exceeds ``threshold``: ``rule="confidence"`` max_c p_c (the reference's
@@ -779,19 +832,30 @@ class MCDEngine(CompiledGraph):
         ``predict_with_exit``'s dict (``best_preds``: the ensemble mean at the exit taken when ``ensemble``), plus ``macs_done`` (MACs the
         stages ran: per stage, images that ran it x (prefix MACs + T x suffix MACs), ops without a row-table form at the whole batch) and
         ``macs_full`` (``predict``'s); with ``uncertainty``, also pred_entropy / exp_entropy / mutual_info [E,B] of the computed rows as in
-        ``finalize_uncertainty``.  Synchronises once per decision."""
+        ``finalize_uncertainty``.  With ``ensemble_readout`` (``ensemble`` keeps its meaning: it selects the rule), also the entropies
+        above and the five ``ens_*`` entries of ``finalize_ensemble`` over ``T`` — the per-sample exit ensembles, from one kernel launch
+        behind the last stage that ran; rows of exits an image never reached are meaningless — and ``best_ens``: dict(mean, var [B, C],
+        pred_entropy, exp_entropy, mutual_info [B]) of the ensemble of exits 0..exit_layer[b].  Synchronises once per decision."""
         if rule not in _lib.EXIT_RULES:
             raise ValueError(f"rule must be one of {sorted(_lib.EXIT_RULES)}, got {rule!r}")
         if not 1 <= int(T) <= self.chunk_samples:
             raise ValueError(f"early exiting needs all T={T} samples in one chunk (engine planned for {self.chunk_samples})")
         B, T, first_exit = x.shape[0], int(T), int(first_exit)
         stages = self.exit_stages(first_exit)
-        S, H = self.new_uncertainty_sums(B) if uncertainty else (self.new_moments(B), None)
-        exit_layer, active = self.accumulate_early_exit(x, S, T, threshold, seed, cnt0, first_exit, rule, ensemble, H)
+        Q = QH = None
+        if ensemble_readout:
+            S, H, Q, QH = self.new_ensemble_sums(B)
+        else:
+            S, H = self.new_uncertainty_sums(B) if uncertainty else (self.new_moments(B), None)
+        exit_layer, active = self.accumulate_early_exit(x, S, T, threshold, seed, cnt0, first_exit, rule, ensemble, H, Q, QH)
         r = self.finalize(S, T) if H is None else self.finalize_uncertainty(S, H, T)
         r["exit_layer"] = exit_layer
         r["active_after"] = active
         idx = torch.arange(B, device=self.device)
+        if ensemble_readout:
+            r.update(self._finalize_ensemble_sums(Q, QH, T))
+            at = exit_layer.long()
+            r["best_ens"] = {k: r["ens_" + k][at, idx] for k in ("mean", "var", "pred_entropy", "exp_entropy", "mutual_info")}
         p = r["mean"]
         if ensemble:          # the mean of exits 0..e, summed in exit order
             p = p.cumsum(0) / torch.arange(1, self.n_exits + 1, dtype=torch.float64, device=self.device).view(-1, 1, 1)
@@ -807,10 +871,14 @@ class MCDEngine(CompiledGraph):
         r["macs_full"] = B * (self.prefix_macs + T * self.suffix_macs)
         return r
 
-    def accumulate_adaptive(self, x, S, T_max, threshold, rule="sem", t_step=None, test_exit=-1, seed=0, cnt0=0, H=None, image_offset=0):
+    def accumulate_adaptive(self, x, S, T_max, threshold, rule="sem", t_step=None, test_exit=-1, seed=0, cnt0=0, H=None, image_offset=0,
+                            ensemble=False, stop_on="exit", Q=None, QH=None):
         """The sampling half of ``predict_adaptive`` (bmi_forward_mcd_adaptive) into the ZEROED sums S [3, E, B, C] (and H [E, B]:
-        ``new_uncertainty_sums``): on return image b's rows hold exactly its first t_used[b] samples.  Returns (t_used int32 [B],
-        converged uint8 [B], active_after_step host list)."""
+        ``new_uncertainty_sums``): on return image b's rows hold exactly its first t_used[b] samples.  With ``ensemble`` also into the
+        ZEROED exit-ensemble sums ``Q`` [2, E, B, C] and ``QH`` [E, B] (``new_ensemble_sums``; H is required then), truncated the same way
+        (bmi_forward_mcd_adaptive_ensemble); ``stop_on="ensemble"`` makes the rule read the ensemble of exits 0..test_exit (Q) in place of
+        exit test_exit's own sums.  Returns (t_used int32 [B], converged uint8 [B], active_after_step host list)."""
+        check_stop_on(stop_on, ensemble)
         x = self._check_x(x)
         B = x.shape[0]
         if rule not in _lib.STOP_RULES:
@@ -830,9 +898,23 @@ class MCDEngine(CompiledGraph):
             raise ValueError("moment buffer must be contiguous float64 [3, E, B, C]")
         if H is not None and (tuple(H.shape) != (self.n_exits, B) or H.dtype != torch.float64 or not H.is_contiguous()):
             raise ValueError("entropy buffer must be contiguous float64 [E, B]")
+        if ensemble:
+            self._check_ensemble_sums(B, H, Q, QH)
+        elif Q is not None or QH is not None:
+            raise ValueError("Q / QH are the sums of ensemble=True")
         t_used = torch.empty(B, dtype=torch.int32, device=self.device)
         converged = torch.empty(B, dtype=torch.uint8, device=self.device)
         active = (C.c_int32 * (-(-T_max // t_step)))()
+        if ensemble:
+            scratch, _ = self._ensemble_scratch(B)
+            with torch.cuda.device(self.device):
+                rc = self.lib.bmi_forward_mcd_adaptive_ensemble(
+                    self.handle, x.data_ptr(), B, int(image_offset), T_max, t_step, int(seed) & 0xFFFFFFFFFFFFFFFF, int(cnt0),
+                    _lib.STOP_RULES[rule], float(threshold), test_exit, _lib.STOP_ON[stop_on], S[0].data_ptr(), S[1].data_ptr(), S[2].data_ptr(),
+                    H.data_ptr(), Q[0].data_ptr(), Q[1].data_ptr(), QH.data_ptr(), scratch.data_ptr(), scratch.numel(), t_used.data_ptr(),
+                    converged.data_ptr(), active, self.workspace.data_ptr(), self.workspace_bytes, self._stream())
+            _lib.check(rc, "bmi_forward_mcd_adaptive_ensemble")
+            return t_used, converged, [int(v) for v in active]
         with torch.cuda.device(self.device):
             rc = self.lib.bmi_forward_mcd_adaptive(self.handle, x.data_ptr(), B, int(image_offset), T_max, t_step, int(seed) & 0xFFFFFFFFFFFFFFFF,
                                                    int(cnt0), _lib.STOP_RULES[rule], float(threshold), test_exit, S[0].data_ptr(), S[1].data_ptr(),
@@ -842,7 +924,7 @@ class MCDEngine(CompiledGraph):
         return t_used, converged, [int(v) for v in active]
 
     def predict_adaptive(self, x, T_max, threshold, rule="sem", t_step=None, test_exit=-1, seed=0, cnt0=0, uncertainty=False,
-                         image_offset=0):
+                         image_offset=0, ensemble=False, stop_on="exit"):
         """Adaptive Monte-Carlo sampling on the device (bmi_forward_mcd_adaptive): samples run in steps of ``t_step`` (default
         DEFAULT_ADAPTIVE_T_STEP, at most the planned chunk) up to ``T_max``; after each step an image whose running estimate at exit
         ``test_exit`` passes the stop rule retires, and the later steps run on the images still active only.  Rules: ``"sem"`` — the
@@ -850,11 +932,24 @@ class MCDEngine(CompiledGraph):
         (m_top1 - m_top2) / sqrt((var_top1 + var_top2) / t) is at least ``threshold``.  Every sample keeps its global index, so image b's
         result is ``predict(T=t_used[b])``'s for that image.  Returns dict(mean / var / logit_mean [E,B,C] float64, t_used int32 [B] and
         converged bool [B] on the device, active_after_step: host list of the images still active after each step); with
-        ``uncertainty``, also pred_entropy / exp_entropy / mutual_info [E,B] as in ``finalize_uncertainty``.  Synchronises once per step."""
+        ``uncertainty``, also pred_entropy / exp_entropy / mutual_info [E,B] as in ``finalize_uncertainty``.  With ``ensemble``, those
+        entropies and the exit-ensemble read-out as well: the five ``ens_*`` entries of ``finalize_ensemble``, each image's divided by its own
+        t_used[b], plus the sums ``Q`` [2, E, B, C] and ``QH`` [E, B] — image b's are ``predict_ensemble(T=t_used[b])``'s; and
+        ``stop_on="ensemble"`` (needs ``ensemble``) tests the rule on the ensemble of exits 0..test_exit, the predictor a caller of the
+        ensemble uses, instead of on exit test_exit alone.  Synchronises once per step."""
+        check_stop_on(stop_on, ensemble)
         B = x.shape[0]
-        S, H = self.new_uncertainty_sums(B) if uncertainty else (self.new_moments(B), None)
-        t_used, converged, active = self.accumulate_adaptive(x, S, T_max, threshold, rule, t_step, test_exit, seed, cnt0, H, image_offset)
+        Q = QH = None
+        if ensemble:
+            S, H, Q, QH = self.new_ensemble_sums(B)
+        else:
+            S, H = self.new_uncertainty_sums(B) if uncertainty else (self.new_moments(B), None)
+        t_used, converged, active = self.accumulate_adaptive(x, S, T_max, threshold, rule, t_step, test_exit, seed, cnt0, H, image_offset,
+                                                             ensemble, stop_on, Q, QH)
         r = self.finalize_per_image(S, t_used, H)
+        if ensemble:
+            r.update(self.finalize_ensemble_per_image(Q, QH, t_used))
+            r.update(Q=Q, QH=QH)
         r.update(t_used=t_used, converged=converged.bool(), active_after_step=active)
         return r
 

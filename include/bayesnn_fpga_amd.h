@@ -168,6 +168,7 @@ typedef struct bmi_model_desc {
 
 /* per-op-kind device time, filled by bmi_profile_read */
 #define BMI_PROFILE_SLOTS 8 /* index = BMI_OP_* (the exit heads' slot includes the moment sums) */
+#define BMI_PROFILE_ENSEMBLE 7 /* the ensemble.hip launches of bmi_forward_mcd_adaptive_ensemble / bmi_forward_mcd_exit_staged_ensemble */
 
 int bmi_version(void);
 const char* bmi_error_string(int code);
@@ -358,8 +359,8 @@ int bmi_forward_mcd_entropy(bmi_handle h, const float* x_nchw, int32_t batch, in
  * 0 for a handle that is not planned or a batch it does not take) and one launch of ensemble.hip follows the chunk's heads.  Q1 / Q2
  * [E][batch][C] and QH [E][batch] are device float64, ADDED TO like S1; rows 0 .. batch-1 of a share (image_offset).  The planned
  * workspace is that of every other entry point.  BMI_ERR_NOMEM: scratch too small; BMI_ERR_UNSUPPORTED: more than 32 exits, more than
- * 128 classes or n_exits * (C | 1) > 3456.  No allocation and no synchronisation: captures into a hipGraph like bmi_forward_mcd.  The
- * fixed-T path only: adaptive sampling and early exit decide on sums that exist already. */
+ * 128 classes or n_exits * (C | 1) > 3456.  No allocation and no synchronisation: captures into a hipGraph like bmi_forward_mcd.  Under
+ * adaptive sampling and staged early exit: bmi_forward_mcd_adaptive_ensemble and bmi_forward_mcd_exit_staged_ensemble below. */
 size_t bmi_ensemble_scratch_bytes(bmi_handle h, int32_t batch);
 int bmi_forward_mcd_ensemble(bmi_handle h, const float* x_nchw, int32_t batch, int32_t image_offset, int32_t t_begin, int32_t t_count,
                              uint64_t seed, int32_t mask_cnt0, double* S1, double* S2, double* SL, double* SH, double* Q1, double* Q2,
@@ -378,6 +379,13 @@ int bmi_ensemble_moments(const float* logits, int32_t T, int32_t E, int32_t B, i
 int bmi_finalize_ensemble(int32_t n_exits, int32_t batch, int32_t out_dim, int32_t t_total, const double* Q1, const double* Q2, const double* QH,
                           double* ens_mean, double* ens_var, double* pred_entropy, double* exp_entropy, double* mutual_info, int32_t* nonfinite,
                           bmi_stream stream);
+
+/* bmi_finalize_ensemble with a per-image sample count t_used[b] (device int32 [batch], every entry >= 1) in place of t_total, as
+ * bmi_finalize_per_image is to bmi_finalize_checked / bmi_finalize_uncertainty: row (e, b) of every output divides by t_used[b] (the sums of
+ * bmi_forward_mcd_adaptive_ensemble). */
+int bmi_finalize_ensemble_per_image(int32_t n_exits, int32_t batch, int32_t out_dim, const int32_t* t_used, const double* Q1, const double* Q2,
+                                    const double* QH, double* ens_mean, double* ens_var, double* pred_entropy, double* exp_entropy,
+                                    double* mutual_info, int32_t* nonfinite, bmi_stream stream);
 
 /* Confidence-threshold early exiting ON the device — what the reference only models after the fact
  * (FullAnalysis.confidence_exiting / is_confident / flop_saver, SA/train/results_analyzer.py:606-630, :638-677, :725-733):
@@ -422,6 +430,31 @@ int bmi_forward_mcd_adaptive(bmi_handle h, const float* x_nchw, int32_t batch, i
                              uint8_t* converged, int32_t* active_after_step, void* workspace, size_t workspace_bytes,
                              bmi_stream stream);
 
+/* Adaptive sampling that also keeps the exit-ensemble sums, and can stop on them.  The ensemble is the predictor the paper ships — the
+ * reference forms it from the T-mean probabilities (FullAnalysis._get_output, SA/train/results_analyzer.py:260-269: `ensemble_output_sm`)
+ * and per stochastic pass (_MultiExitAccuracy._metrics, SA/train/loss/base_classes.py:41,54,58) — and its standard error holds cross-exit
+ * covariance that no per-exit sum contains.  bmi_forward_mcd_adaptive with the same arguments plus stop_on, Q1 / Q2 [E][batch][C],
+ * QH [E][batch] (device float64, ZERO on entry like S1) and the scratch of bmi_forward_mcd_ensemble (bmi_ensemble_scratch_bytes(h, batch):
+ * one step of [t_step][E][batch][C] logits fits, t_step <= the planned chunk).  Per step the heads also write their logits into
+ * `scratch` — at the ORIGINAL image row under a row table; rows of retired images are stale and never read — and one launch of
+ * ensemble.hip follows them: over every image while none has retired, over the list of active images afterwards (same arithmetic per
+ * row, one running sum per (exit, image, class) continued in sample order).  The decision follows that launch.
+ *   BMI_STOP_ON_EXIT     (0): the rule reads S1 / S2 at test_exit: t_used, converged, active_after_step, S1 / S2 / SL / SH are
+ *                             bmi_forward_mcd_adaptive's bits.
+ *   BMI_STOP_ON_ENSEMBLE (1): the SAME rule (BMI_STOP_SEM / BMI_STOP_MARGIN, float64) reads Q1 / Q2 at row test_exit: the sums of the
+ *                             ensemble of exits 0..test_exit (row 0 is exit 0 itself).
+ * On return image b's rows of Q1 / Q2 / QH, like those of S1, hold exactly its first t_used[b] samples: bmi_forward_mcd_ensemble's bits
+ * truncated there (bmi_finalize_ensemble_per_image reads them out).  Errors: bmi_forward_mcd_adaptive's, BMI_ERR_INVALID for a NULL Q1 /
+ * Q2 / QH / scratch or an unknown stop_on, BMI_ERR_NOMEM for a scratch too small, BMI_ERR_UNSUPPORTED for a shape ensemble.hip does not
+ * take (bmi_forward_mcd_ensemble's list); in every error case nothing is written.  Synchronises once per step. */
+#define BMI_STOP_ON_EXIT 0
+#define BMI_STOP_ON_ENSEMBLE 1
+int bmi_forward_mcd_adaptive_ensemble(bmi_handle h, const float* x_nchw, int32_t batch, int32_t image_offset, int32_t t_max, int32_t t_step,
+                                      uint64_t seed, int32_t mask_cnt0, int32_t rule, double threshold, int32_t test_exit, int32_t stop_on,
+                                      double* S1, double* S2, double* SL, double* SH, double* Q1, double* Q2, double* QH, void* scratch,
+                                      size_t scratch_bytes, int32_t* t_used, uint8_t* converged, int32_t* active_after_step, void* workspace,
+                                      size_t workspace_bytes, bmi_stream stream);
+
 /* Early exit by stages that also skips the deterministic trunk (the paper's exit-only dropout: every trunk and exit-branch conv is in
  * the once-per-batch prefix).  Every op, prefix and suffix, has a stage: the smallest exit index of any head downstream of its outputs
  * (a pair- or seam-fused op: the smaller of its two members'); stages <= rule->first_exit fold into stage 0.  Stage 0 runs on the whole
@@ -455,6 +488,22 @@ typedef struct bmi_exit_rule {
 int bmi_forward_mcd_exit_staged(bmi_handle h, const float* x_nchw, int32_t batch, int32_t t_count, uint64_t seed, int32_t mask_cnt0,
                                 const bmi_exit_rule* rule, double* S1, double* S2, double* SL, double* SH, int32_t* exit_of_image,
                                 int32_t* active_after, void* workspace, size_t workspace_bytes, bmi_stream stream);
+
+/* Staged early exit that also keeps the exit-ensemble sums of the exits every image reached (the per-pass ensemble of
+ * _MultiExitAccuracy._metrics, SA/train/loss/base_classes.py:41,54,58; FullAnalysis._get_output, SA/train/results_analyzer.py:260-269).
+ * bmi_forward_mcd_exit_staged with the same arguments — the rule is NOT changed: its ensemble = 1 stays the mean of the T-means — plus
+ * Q1 / Q2 [E][batch][C], QH [E][batch] (device float64, ZERO on entry) and the scratch of bmi_forward_mcd_ensemble
+ * (bmi_ensemble_scratch_bytes(h, batch); t_count <= the planned chunk).  Every stage's heads also write their logits into the one
+ * [t_count][E][batch][C] scratch, active images only; behind the last stage that ran — also when every image has left early — ONE launch
+ * of ensemble.hip walks all images with n_e[b] = exit_of_image[b] + 1 exits each: the running exit sum is cut there, so rows
+ * e <= exit_of_image[b] of Q1 / Q2 / QH are bmi_forward_mcd_ensemble's (samples 0 .. t_count-1) bit for bit, and rows of exits an image
+ * never reached stay zero, like S1's.  S1 / S2 / SL / SH, exit_of_image and active_after are bmi_forward_mcd_exit_staged's bits.
+ * Errors: bmi_forward_mcd_exit_staged's, BMI_ERR_INVALID for a NULL Q1 / Q2 / QH / scratch, BMI_ERR_NOMEM for a scratch too small,
+ * BMI_ERR_UNSUPPORTED for a shape ensemble.hip does not take; in every error case nothing is written. */
+int bmi_forward_mcd_exit_staged_ensemble(bmi_handle h, const float* x_nchw, int32_t batch, int32_t t_count, uint64_t seed, int32_t mask_cnt0,
+                                         const bmi_exit_rule* rule, double* S1, double* S2, double* SL, double* SH, double* Q1, double* Q2,
+                                         double* QH, void* scratch, size_t scratch_bytes, int32_t* exit_of_image, int32_t* active_after,
+                                         void* workspace, size_t workspace_bytes, bmi_stream stream);
 
 /* The stage plan of bmi_forward_mcd_exit_staged for first_exit (host only; needs bmi_plan).  *n_stages = n_exits - first_exit; with
  * capacity 0 only that is written, else capacity must be >= it.  Per stage k (each array NULL: not written): prefix_macs[k] (MACs per

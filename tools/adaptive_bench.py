@@ -5,7 +5,12 @@ median wall time per batch, mean t_used, active_after_step and the largest |mean
 Also: the cost of steps with no retirement against the same samples inside bmi_forward_mcd, a t_step sweep, and the device time of the
 first site's MASK launches with and without a row table (bmi_profile_launches).
 
-    python tools/adaptive_bench.py [--reps 5] [--quantiles 0.25,0.5,0.75] [--t-steps 10,20,25,50] [--dtype f16]
+    python tools/adaptive_bench.py [--reps 5] [--quantiles 0.25,0.5,0.75] [--t-steps 10,20,25,50] [--dtype f16] [--ensemble]
+
+--ensemble: per threshold also ``predict_adaptive(ensemble=True)`` (the exit-ensemble sums under the row table), alternating with the plain
+call: its wall time with ``stop_on="exit"`` (the same steps: what the read-out costs) and with ``stop_on="ensemble"`` (the rule on the
+ensemble of all exits at the SAME threshold), the mean t_used of both, and the device time of the ensemble.hip launches per step
+(bmi_profile_launches, full-grid steps and image-list steps apart).
 
 The thresholds are the given quantiles of every image's SEM statistic after the first step (t = t_step) at the last exit, per model: a
 fixed threshold that suits one set of weights retires nobody on the other.
@@ -56,6 +61,52 @@ def mask_split(eng, fn, full_images):
         out[k][0] += l["ms"]
         out[k][1] += l["images"]
     return {k: dict(ms=round(v[0], 4), images=v[1], us_per_1k_images=round(1e3 * v[0] / max(v[1], 1) * 1e3, 3)) for k, v in out.items()}
+
+
+def ensemble_split(eng, fn, full_images):
+    """Device ms of the ensemble.hip launches of one call: full-grid steps and image-list steps apart, per launch (= per step)."""
+    eng.profile(True)
+    try:
+        eng.profile_read()
+        fn()
+        torch.cuda.synchronize()
+        eng.profile_read()
+        launches = [l for l in eng.profile_launches() if l["kind"] == "ensemble"]
+    finally:
+        eng.profile(False)
+    out = {}
+    for k, sel in (("full", lambda l: l["images"] == full_images), ("list", lambda l: l["images"] != full_images)):
+        ms = [l["ms"] for l in launches if sel(l)]
+        out[k] = dict(launches=len(ms), ms_per_step=round(float(np.mean(ms)), 4) if ms else None,
+                      images=[l["images"] for l in launches if sel(l)])
+    return out
+
+
+def ensemble_leg(name, eng, x, a, t_step, thresholds):
+    """predict_adaptive against predict_adaptive(ensemble=True), stop_on "exit" and "ensemble", alternating, at the leg's thresholds."""
+    T = a.T
+    calls = {
+        "plain": lambda thr: eng.predict_adaptive(x, T, thr, t_step=t_step, seed=a.seed, uncertainty=True),
+        "ensemble_stop_on_exit": lambda thr: eng.predict_adaptive(x, T, thr, t_step=t_step, seed=a.seed, ensemble=True),
+        "ensemble_stop_on_ensemble": lambda thr: eng.predict_adaptive(x, T, thr, t_step=t_step, seed=a.seed, ensemble=True, stop_on="ensemble"),
+    }
+    for thr in thresholds:
+        for fn in calls.values():
+            fn(thr)                                                  # warm-up (the scratch is allocated here)
+        times, res = {k: [] for k in calls}, {}
+        for _ in range(a.reps):                                      # alternating, same process
+            for k, fn in calls.items():
+                ms, res[k] = timed(lambda: fn(thr))
+                times[k].append(ms)
+        med = {k: float(np.median(v)) for k, v in times.items()}
+        steps = sum(1 for n in [x.shape[0]] + res["plain"]["active_after_step"][:-1] if n)
+        prof = ensemble_split(eng, lambda: calls["ensemble_stop_on_exit"](thr), x.shape[0] * t_step)
+        print(json.dumps(dict(model=name, what="adaptive_ensemble", rule="sem", threshold=thr, t_step=t_step, steps_run=steps,
+                              ms={k: round(v, 3) for k, v in med.items()},
+                              readout_ms_per_step=round((med["ensemble_stop_on_exit"] - med["plain"]) / max(steps, 1), 4),
+                              ensemble_kernel=prof,
+                              mean_t_used={k: round(float(r["t_used"].float().mean()), 2) for k, r in res.items()},
+                              active_after_step={k: r["active_after_step"] for k, r in res.items()})), flush=True)
 
 
 def leg(name, model, dev, x, a):
@@ -113,6 +164,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--seed", type=int, default=3)
     ap.add_argument("--dtype", default="f16")
+    ap.add_argument("--ensemble", action="store_true", help="also measure predict_adaptive(ensemble=True) at the same thresholds")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
@@ -125,6 +177,8 @@ def main():
     twin.invalidate_engine()
     for name, m in (("synthetic", model), ("trained_like_twin", twin)):
         eng, t_step, thresholds = leg(name, m, dev, x, a)
+        if a.ensemble:
+            ensemble_leg(name, eng, x, a, t_step, thresholds)
         if name == "synthetic":
             thr = thresholds[len(thresholds) // 2]
             print(json.dumps(dict(model=name, what="mask_launches", threshold=thr, t_step=t_step,

@@ -4,7 +4,11 @@ where the engine plans it, B = 1024.  Thresholds: the confidence statistic's qua
 of the images leave there.  Prints one JSON line per measurement: median ms of both calls, exit histogram, macs_done / macs_full, and per
 stage the images each launch carried (bmi_profile_launches).
 
-    python tools/exit_bench.py [--reps 7] [--batches 250,1024] [--leave 0.25,0.5,0.75] [--dtype f16]
+    python tools/exit_bench.py [--reps 7] [--batches 250,1024] [--leave 0.25,0.5,0.75] [--dtype f16] [--ensemble]
+
+--ensemble: also ``predict_early_exit(ensemble_readout=True)`` (the exit-ensemble sums of the exits every image reached: the heads leave
+their logits in the scratch, one ensemble.hip launch behind the last stage that ran), alternating with the two other calls: its median ms,
+the difference per stage that ran, and the device time of that one launch (bmi_profile_launches).
 """
 import argparse
 import collections
@@ -55,6 +59,20 @@ def launch_images(eng, fn):
     return dict(sorted(collections.Counter(ln["images"] for ln in launches).items()))
 
 
+def ensemble_launch_ms(eng, fn):
+    """Device ms of the ensemble.hip launch of one call (the exit-count fill included)."""
+    eng.profile(True)
+    try:
+        eng.profile_read()
+        fn()
+        torch.cuda.synchronize()
+        eng.profile_read()
+        ms = [ln["ms"] for ln in eng.profile_launches() if ln["kind"] == "ensemble"]
+    finally:
+        eng.profile(False)
+    return round(float(sum(ms)), 4), len(ms)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=7)
@@ -62,6 +80,7 @@ def main():
     ap.add_argument("--leave", default="0.25,0.5,0.75")
     ap.add_argument("--dtype", default="f16")
     ap.add_argument("--workloads", default=",".join(WORKLOADS))
+    ap.add_argument("--ensemble", action="store_true", help="also measure predict_early_exit(ensemble_readout=True)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     for name in a.workloads.split(","):
@@ -81,17 +100,32 @@ def main():
                 thr = float(np.quantile(conf1, 1.0 - frac))
                 ee = lambda: eng.predict_early_exit(x, T, thr, seed=3)       # noqa: E731
                 pr = lambda: eng.predict(x, T, seed=3)                      # noqa: E731
+                eu = lambda: eng.predict_early_exit(x, T, thr, seed=3, uncertainty=True)            # noqa: E731
+                er = lambda: eng.predict_early_exit(x, T, thr, seed=3, ensemble_readout=True)       # noqa: E731
                 ee(), pr()
-                ms_full, ms_exit = [], []
+                if a.ensemble:
+                    eu(), er()
+                ms_full, ms_exit, ms_unc, ms_read = [], [], [], []
                 for _ in range(a.reps):           # alternating
                     ms_full.append(median_ms(pr, 1))
                     ms_exit.append(median_ms(ee, 1))
+                    if a.ensemble:
+                        ms_unc.append(median_ms(eu, 1))
+                        ms_read.append(median_ms(er, 1))
                 r = ee()
+                extra = {}
+                if a.ensemble:
+                    stages = 1 + sum(1 for n in r["active_after"][1:-1] if n)
+                    k_ms, k_n = ensemble_launch_ms(eng, er)
+                    extra = dict(ms_early_exit_uncertainty=round(float(np.median(ms_unc)), 4),
+                                 ms_early_exit_readout=round(float(np.median(ms_read)), 4), stages_run=stages,
+                                 readout_ms_per_stage=round((float(np.median(ms_read)) - float(np.median(ms_unc))) / stages, 4),
+                                 ensemble_launches=k_n, ensemble_launch_ms=k_ms)
                 hist = np.bincount(r["exit_layer"].cpu().numpy(), minlength=eng.n_exits).tolist()
                 print(json.dumps(dict(workload=name, dtype=a.dtype, B=B, T=T, leave_at_exit1=frac, threshold=round(thr, 6), exit_hist=hist,
                                       active_after=r["active_after"], ms_predict=round(float(np.median(ms_full)), 4),
                                       ms_early_exit=round(float(np.median(ms_exit)), 4), macs_ratio=round(r["macs_done"] / r["macs_full"], 4),
-                                      launch_images=launch_images(eng, ee))), flush=True)
+                                      launch_images=launch_images(eng, ee), **extra)), flush=True)
             del eng, m
             torch.cuda.empty_cache()
 
