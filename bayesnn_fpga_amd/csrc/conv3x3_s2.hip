@@ -37,6 +37,44 @@
 //                registers: S2_DIRECT; formerly two rounds of 128 pixels per channel half through the 64 KB the C / D pieces and W2 occupy).
 //   pair mode  = as conv_igemm_wide: channel tiles >= split use the second conv's weights / BN / output tensor.
 //   epilogue   = plain (BN + ReLU) only: every stride-2 conv of the path.  Anything else stays with conv_igemm_wide.
+//
+// The pad-skip form of the 8x8 -> 4x4 class ("s2_pad_skip" = 1, the default; conv3x3_s2_skip_kernel = the body with SKIP = true; TW == 4, 256-channel
+// tiles, fp16 / bf16, single and pair launches, direct and pooled epilogue; row-table launches keep the 4 x 4 blocks).  Output row 0 with ky = 0 and
+// output column 0 with kx = 0 read only padding: 23 of the 16 x 9 (position, tap) pairs (16.0 %).  With a 4 x 4 block of ONE image as the MFMA pixel
+// tile every tile has a live pixel for every tap.  Here:
+//   tile order = conv3x3_pw's pad-skip order (PwGeomSkip): tile pixel p = 128 wp + 16 j + image, pixel tile j of pixel wave wp is the output position
+//                (oy, ox) = (j >> 1, 2 (j & 1) + ((oy + wp) & 1)).  Step S (tap (ky, kx) = s2_tap(S)) of a tile is dead exactly when (ky == 0 && oy == 0)
+//                || (kx == 0 && ox == 0): a ds_read_b128 and four MFMAs that are not emitted.  Live tiles per wave: tap (0,0) 5 / 4, taps (0,1) (0,2)
+//                (1,0) (2,0) 6 / 6, the other four 8 / 8 — the slower wave runs 61 tile-steps per chunk instead of 72 (−15.3 %), 121 of 144 pairs are
+//                live (static_asserts below S2Skip).  A step's live tiles go to its two phases in tile order (4 + 4, 3 + 3, 3 + 2, 2 + 2).  Which tiles
+//                are dead depends on wp: the chunk loop exists once per pixel wave behind a wave-uniform branch, the same barriers on both sides.  The
+//                live sets enter the step as constexpr bit masks: as calls on the unrolled tile index they outlived the inliner in two of the
+//                eighteen step bodies — real calls, around MFMAs that ignore EXEC.
+//   LDS        = S2Geom untouched: plane sizes, cell0, A_PAD, NPT, pstep, wait_n, the weight stages and everything schedule_ok() checks.  Only the
+//                numbering of the cells INSIDE a plane changes: local cell (y * cols(pl) + x) * 16 + img, the image fastest, instead of
+//                (img * rows + y) * cols + x — a pixel fragment (16 images of one cell) is 1 KB contiguous.  The padding cells (plane row 0 of the
+//                odd-row planes, column 0 of the odd-column planes) keep their slots, their DMA lanes still read beyond the descriptor, and no live
+//                tile reads them (S2Skip::cells_ok).  Chunk c of image n sits at position c ^ 2 ((n >> 3) & 1) (conv3x3_pw's): a ds_read_b128 lane
+//                group reads images 0-3 and 12-15 at chunk kq and images 4-11 at kq ^ 1, 16 distinct 16-byte slots.  A tap shift and a tile's position
+//                are whole cells: compile-time multiples of 1 KB (at most 24 KB) on ONE per-lane offset per plane, boff[pl] (P_OFF + a plane offset does
+//                not fit the 16-bit immediate of ds_read).  The images of a ragged last tile lie beyond the per-tile buffer descriptor, as before.
+//   K order    = unchanged — chunk-major, steps A A A A B B C C D, 32 channels per MFMA; a product with an all-zero pixel fragment leaves an fp32
+//                accumulator as it was, so every output keeps its bits (tests/test_s2_pad_skip.py).
+//   epilogues  = direct stores: lane (l16, kq) of tile j is image n0 + l16 at (oy, ox), predicated on n < N.  Pooled: an image's 16 positions are 8
+//                tile registers in each of the two pixel waves; they are summed through the staging area at E_OFF in the order of the DPP tree of the
+//                4 x 4-block form — per map row (p0 + p1) + (p2 + p3), then (r0 + r1) + (r2 + r3), then * 1/16 (conv3x3_pw's persistent pooled tail):
+//                the fp32 results are bit-equal.
+//   hazards    = 1. tile-start wait: a wave may leave in flight only the stores it issued BEHIND the next tile's prefetch DMAs.  Per WAVE (vmcnt counts
+//                   instructions, whatever the EXEC mask): direct 16, pooled 4 in pixel wave 0 (2 halves x 2 float4) and none in pixel wave 1 — so
+//                   vmcnt(16) / vmcnt(4) / vmcnt(0); a ragged tile (lanes beyond N skip their stores: a branch may skip the instruction) drains with
+//                   vmcnt(0) as before.
+//                2. s_barrier is workgroup-wide: the pooled exchange takes three barriers per 32-channel half = six per tile; in a mixed pair tile the
+//                   channel group that stores plainly executes six barriers behind its stores.
+//                3. the exchange area (E_OFF .. + 64 KB: the own-period pieces, padding, the last weight stage) is written by the next tile from its
+//                   step 0 on (SETUP_TILE issues stages 0 / 1 and the A / B pieces only): the pooled tail ends with lgkmcnt(0), before the tile-start
+//                   barrier.
+//                4. registers: two step bodies per step.  242 VGPRs, no scratch, no VGPR spill, LDS as the 4 x 4-block form (tools/kernel_resources.py,
+//                   tests/test_build_resources.py); the per-lane values (boff[], a_off) do not depend on wp, so nothing was hoisted across the branch.
 #include <cstdlib>
 
 #include "conv_epilogue.h"
@@ -258,10 +296,55 @@ __host__ __device__ constexpr int s2_tap(int s) {
     return t[s];
 }
 
-template <int TW, bool BF, bool IMAP, bool MSK = false, int CT_ = 256>
-__global__ __launch_bounds__(512, 1) void conv3x3_s2_kernel(ConvArgs a, int n_tiles) {
+// The pad-skip tile order of the 8x8 -> 4x4 class ("s2_pad_skip", see the header comment): tile pixel p = 128 wp + 16 j + image, pixel tile j of
+// pixel wave wp is the output position (oy, ox) = (j >> 1, 2 (j & 1) + ((oy + wp) & 1)) — conv3x3_pw's checkerboard (PwGeomSkip).  Step S
+// (tap (ky, kx) = s2_tap(S)) of tile (wp, j) reads plane cell (oy + dy, ox + dx) of all 16 images, or — ky == 0 in output row 0, kx == 0 in
+// output column 0 — nothing but the padding row / column of its plane.
+struct S2Skip {
+    __host__ __device__ static constexpr int t_y(int j) { return j >> 1; }
+    __host__ __device__ static constexpr int t_x(int wp, int j) { return 2 * (j & 1) + (((j >> 1) + wp) & 1); }
+    __host__ __device__ static constexpr bool valid(int wp, int j, int S) {
+        return !((s2_tap(S) / 3 == 0 && t_y(j) == 0) || (s2_tap(S) % 3 == 0 && t_x(wp, j) == 0));
+    }
+    // cell (position) of the plane that the tile reads in step S: a multiple of 1 KB on the per-lane fragment address
+    __host__ __device__ static constexpr int cell(int wp, int j, int S) {
+        return (t_y(j) + s2_dy(S)) * (4 + ((s2_plane(S) & 1) ? 0 : 1)) + t_x(wp, j) + s2_dx(S);
+    }
+    __host__ __device__ static constexpr int count(int wp, int S) { int n = 0; for (int t = 0; t < 8; ++t) n += valid(wp, t, S) ? 1 : 0; return n; }
+    // the live tiles of a K-step are split over its two phases in tile order (8: 4 + 4, 6: 3 + 3, 5: 3 + 2, 4: 2 + 2), as PwGeomSkip::phase
+    __host__ __device__ static constexpr int phase(int wp, int j, int S) {
+        int r = 0;
+        for (int t = 0; t < j; ++t) r += valid(wp, t, S) ? 1 : 0;
+        return r < (count(wp, S) + 1) / 2 ? 0 : 1;
+    }
+    __host__ __device__ static constexpr bool live(int wp, int j, int S, int kk) { return valid(wp, j, S) && phase(wp, j, S) == kk; }
+    // bit j: tile j is live in phase kk of step S.  (The kernel takes the masks as constexpr values: left as calls with the unrolled tile index
+    // for an argument, the two bodies of nine steps exhaust the inliner and real calls stay behind — around MFMAs, which ignore EXEC.)
+    __host__ __device__ static constexpr unsigned mask(int wp, int S, int kk) { unsigned m = 0; for (int j = 0; j < 8; ++j) m |= live(wp, j, S, kk) ? 1u << j : 0u; return m; }
+    __host__ __device__ static constexpr int sum(int wp) { int n = 0; for (int s = 0; s < 9; ++s) n += count(wp, s); return n; }
+    __host__ __device__ static constexpr int slower() { int n = 0; for (int s = 0; s < 9; ++s) n += count(0, s) > count(1, s) ? count(0, s) : count(1, s); return n; }
+    __host__ __device__ static constexpr bool cells_ok() {       // no live tile reads a padding cell or leaves its plane
+        for (int wp = 0; wp < 2; ++wp)
+            for (int j = 0; j < 8; ++j)
+                for (int s = 0; s < 9; ++s) {
+                    const int pl = s2_plane(s), y = t_y(j) + s2_dy(s), x = t_x(wp, j) + s2_dx(s);
+                    const bool pad = (pl < 2 && y == 0) || ((pl == 0 || pl == 2) && x == 0);
+                    if (valid(wp, j, s) == pad) return false;
+                    if (y >= S2Geom<4>::rows(pl) || x >= S2Geom<4>::cols(pl) || cell(wp, j, s) != y * S2Geom<4>::cols(pl) + x) return false;
+                }
+        return true;
+    }
+};
+static_assert(S2Skip::slower() == 61 && S2Skip::sum(0) + S2Skip::sum(1) == 121, "pad-skip: 61 of 72 tile-steps per chunk on the slower pixel wave, 121 of 144 live (position, tap) pairs");
+static_assert(S2Skip::count(0, 0) == 5 && S2Skip::count(1, 0) == 4 && S2Skip::count(0, 8) == 8 && S2Skip::count(1, 4) == 6, "pad-skip: live tiles per tap");
+static_assert(S2Skip::cells_ok(), "pad-skip: a tile is dead exactly when it reads the padding row / column of its plane");
+
+// (the kernel's body: SKIP = the pad-skip form; the two entry points are below)
+template <int TW, bool BF, bool IMAP, bool MSK, int CT_, bool SKIP>
+__device__ __forceinline__ void conv3x3_s2_body(const ConvArgs& a, int n_tiles) {
     using G = S2Geom<TW, (TW == 4 ? 3 : S2_NST_BIG), MSK, CT_>;
     static_assert(!MSK || (TW == 16 && !IMAP), "masked input: one image per tile, the ordinary form");
+    static_assert(!SKIP || (TW == 4 && CT_ == 256 && !IMAP && !MSK && S2_DIRECT && !S2_WSPLIT && !S2_RELAX0), "pad-skip: the 8x8 -> 4x4 class without a row table");
     constexpr int CT = G::CT, IMGS = G::IMGS, NPT = G::NPT, PRO = G::PRO, NST = G::NST;
     constexpr bool HALF = CT == 128;
     constexpr int TI = 4, TP = HALF ? 4 : 8, JB = TP / 2;        // JB pixel blocks per phase of a K-step
@@ -318,6 +401,8 @@ __global__ __launch_bounds__(512, 1) void conv3x3_s2_kernel(ConvArgs a, int n_ti
     for (int pl = 0; pl < 4; ++pl) {
         const int wave_cell = G::cell0(pl) + (G::p_img(pbase) * G::rows(pl) + G::p_oy(pbase)) * G::cols(pl) + G::p_ox(pbase);
         boff[pl] = G::P_OFF + (wave_cell + by * G::cols(pl) + bx) * 64 + ((kq ^ ((by & 1) << 1)) << 4);
+        // pad-skip: lane l16 is IMAGE l16 of the cell the tile reads; the cell (tile position + tap shift) is an immediate multiple of 1 KB
+        if constexpr (SKIP) boff[pl] = G::P_OFF + (G::cell0(pl) + l16) * 64 + ((kq ^ (((l16 >> 3) & 1) << 1)) << 4);
     }
 
     // ---- per-thread DMA sources ----
@@ -341,13 +426,15 @@ __global__ __launch_bounds__(512, 1) void conv3x3_s2_kernel(ConvArgs a, int n_ti
         const int pyl = pl < 2 ? 1 : 0, pxl = (pl == 0 || pl == 2) ? 1 : 0;
         const int RQ = (TW + pyl) * (TW + pxl), Q = TW + pxl;
         const int lc = cell - (pl == 0 ? 0 : (pl == 1 ? G::cell0(1) : (pl == 2 ? G::cell0(2) : G::cell0(3))));
-        const int img = lc / RQ, rm = lc - img * RQ;
+        // (pad-skip: the cells of a plane are numbered (y * cols + x) * 16 + img, the image fastest: a pixel fragment = 16 images of one cell = 1 KB)
+        const int img = SKIP ? (lc & 15) : lc / RQ, rm = SKIP ? (lc >> 4) : lc - img * RQ;
         const int y = rm / Q, x = rm - y * Q;
         const int iy = 2 * y - pyl, ix = 2 * x - pxl;
+        const int sw = SKIP ? ((img >> 3) & 1) : (y & 1);        // chunk swizzle: pos ^ 2 sw
         const bool ok = lc < IMGS * RQ && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
         // (masked input in the lazy site's planar layout, kernels.h lazy_planar_off: a plane row's cells are contiguous 64-byte runs)
-        const unsigned inoff = (MSK && a.lazy_planar) ? (unsigned)((iy * a.W + (ix & 1) * (a.W >> 1) + (ix >> 1)) * 32 + ((pos ^ ((y & 1) << 1)) << 3))
-                                                      : (unsigned)((iy * a.W + ix) * a.Cin + ((pos ^ ((y & 1) << 1)) << 3));
+        const unsigned inoff = (MSK && a.lazy_planar) ? (unsigned)((iy * a.W + (ix & 1) * (a.W >> 1) + (ix >> 1)) * 32 + ((pos ^ (sw << 1)) << 3))
+                                                      : (unsigned)((iy * a.W + ix) * a.Cin + ((pos ^ (sw << 1)) << 3));
         pre[k] = !ok ? OOB : (IMAP ? ((unsigned)img << 24) | inoff : 2u * ((unsigned)img * HWC + inoff));
     }
     // IMAP: tensor row of each image of a tile (-1 beyond N), two tables: the epilogue of tile i reads table i & 1 while the
@@ -619,6 +706,55 @@ __global__ __launch_bounds__(512, 1) void conv3x3_s2_kernel(ConvArgs a, int n_ti
         }                                                                                                      \
     }
 
+    // The pad-skip K-step (S2_STEP without the masked-input parts): a phase reads and multiplies only the tiles that are live in it
+    // (S2Skip::live, compile-time per pixel wave WP) — a dead tile is a ds_read_b128 and four MFMAs that are not emitted.  DMA issue, waits
+    // and barriers are S2_STEP's.
+#define S2_STEP_S(S, WP)                                                                                       \
+    {                                                                                                          \
+        constexpr int pl_ = s2_plane(S), sn_ = (S) + NST - 1;                                                  \
+        constexpr int st_r_ = (S) % 3, st_w_ = ((S) + 2) % 3;                                                  \
+        constexpr unsigned live_[2] = {S2Skip::mask(WP, S, 0), S2Skip::mask(WP, S, 1)};                        \
+        constexpr int cols_ = G::cols(pl_), shift_ = s2_dy(S) * cols_ + s2_dx(S);       /* cell of tile j: its position + the tap shift */ \
+        static_assert(S2Skip::cell(WP, 5, S) == (5 >> 1) * cols_ + 2 * (5 & 1) + (((5 >> 1) + (WP)) & 1) + shift_, "cell"); \
+        const char* ws_ = smem + G::wstage_off(st_r_) + a_off;                                                 \
+        const char* pb_ = smem + boff[pl_];                                                                    \
+        _Pragma("unroll") for (int kk = 0; kk < 2; ++kk) {                                                     \
+            if (kk == 0) {                                                                                     \
+                _Pragma("unroll") for (int i = 0; i < TI; ++i) af[i] = *(const half8*)(ws_ + A_TILE(i));       \
+            }                                                                                                  \
+            _Pragma("unroll") for (int j = 0; j < TP; ++j)                                                     \
+                if ((live_[kk] >> j) & 1u) bfs[j] = *(const half8*)(pb_ + ((j >> 1) * cols_ + 2 * (j & 1) + (((j >> 1) + (WP)) & 1) + shift_) * 1024); \
+            if (kk == 0) {                                                                                     \
+                if (sn_ <= 8) { ISSUE_W(s2_tap(sn_ <= 8 ? sn_ : 0) * a.Cin + c32, st_w_); }                    \
+                else if (!last) { ISSUE_W(s2_tap(sn_ > 8 ? sn_ - 9 : 0) * a.Cin + c32 + 32, st_w_); }          \
+            }                                                                                                  \
+            if (kk == S2_PIECE_PHASE) {                                                                        \
+                _Pragma("unroll") for (int k = 0; k < NPT; ++k)                                                \
+                    if (G::pstep(k) == (S)) {                                                                  \
+                        if (k >= PRO) { ISSUE_P(k, c32); }                                                     \
+                        else if (!last) { ISSUE_P(k, c32 + 32); }                                              \
+                    }                                                                                          \
+            }                                                                                                  \
+            if (kk == 1 && g == 1) END_OF_STEP_WAIT(S);                                                        \
+            RAW_BARRIER();                                                                                     \
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                 \
+            __builtin_amdgcn_s_setprio(1);                                                                     \
+            _Pragma("unroll") for (int i = 0; i < TI; ++i)                                                     \
+                _Pragma("unroll") for (int j = 0; j < TP; ++j)                                                 \
+                    if ((live_[kk] >> j) & 1u) acc[i][j] = mfma_16x16x32<BF>(af[i], bfs[j], acc[i][j]);        \
+            __builtin_amdgcn_s_setprio(0);                                                                     \
+            if (kk == 1 && g == 0) END_OF_STEP_WAIT(S);                                                        \
+            RAW_BARRIER();                                                                                     \
+        }                                                                                                      \
+    }
+#define S2_CHUNKS_S(WP)                                                                                        \
+    for (int chunk = 0; chunk < nC; ++chunk) {                                                                 \
+        const bool last = chunk + 1 == nC;                                                                     \
+        const int c32 = chunk * 32;                                                                            \
+        S2_STEP_S(0, WP) S2_STEP_S(1, WP) S2_STEP_S(2, WP) S2_STEP_S(3, WP) S2_STEP_S(4, WP)                   \
+        S2_STEP_S(5, WP) S2_STEP_S(6, WP) S2_STEP_S(7, WP) S2_STEP_S(8, WP)                                    \
+    }
+
     // The walk: tile positions blockIdx.x, + gridDim.x, ... through xcd_tile_map — or, reading a deterministic input through keep bits
     // (MSK, ConvArgs::lazy_order), the sample-minor numbering id = (b T + t) n_ct + ct dealt per XCD: XCD x (workgroups = x mod 8, J of
     // them) owns the contiguous ids [x L, (x + 1) L) and its workgroup j takes x L + j, + J, ...: at any moment the XCD's workgroups read
@@ -637,6 +773,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_s2_kernel(ConvArgs a, int n_ti
     SETUP_TILE(vb);
     constexpr int NSTORES = HALF ? 8 : 16;                 // output stores per thread of a full tile
     bool stores16 = false;                                 // the tile before this one issued exactly NSTORES stores per thread
+    [[maybe_unused]] bool pooled_prev = false;             // pad-skip: ... and this wave's channel half was pooled (4 stores in pixel wave 0, none in pixel wave 1)
     while (vb < v_end) {
         const int cur_ch0 = ch0, cur_n0 = n0, cur_tsel = tsel;
         accv acc[TI][TP];
@@ -651,6 +788,10 @@ __global__ __launch_bounds__(512, 1) void conv3x3_s2_kernel(ConvArgs a, int n_ti
         // issued BEHIND them (vmcnt retires in order): a full tile leaves them in flight, a ragged one (some stores skipped:
         // the count is not known) and the dynamic-exit form drain everything.
         if (IMAP || !stores16 || S2_DRAIN_STORES) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        else if (SKIP && pooled_prev) {                    // (wave-uniform: the count is per wave)
+            if (wp) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+        }
         else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NSTORES) : "memory");
         if constexpr (MSK) {                               // the A / B pieces of chunk 0 (issued by SETUP_TILE)
 #pragma unroll
@@ -659,11 +800,17 @@ __global__ __launch_bounds__(512, 1) void conv3x3_s2_kernel(ConvArgs a, int n_ti
         }
         RAW_BARRIER();
         if (g == 1) RAW_BARRIER();                         // stagger
-        half8 af[TI], bf[4];
-        for (int chunk = 0; chunk < nC; ++chunk) {
-            const bool last = chunk + 1 == nC;
-            const int c32 = chunk * 32;
-            S2_STEP(0) S2_STEP(1) S2_STEP(2) S2_STEP(3) S2_STEP(4) S2_STEP(5) S2_STEP(6) S2_STEP(7) S2_STEP(8)
+        half8 af[TI];
+        if constexpr (SKIP) {
+            half8 bfs[TP];
+            if (wp == 0) { S2_CHUNKS_S(0) } else { S2_CHUNKS_S(1) }      // (wave-uniform: both sides take the same barriers)
+        } else {
+            half8 bf[4];
+            for (int chunk = 0; chunk < nC; ++chunk) {
+                const bool last = chunk + 1 == nC;
+                const int c32 = chunk * 32;
+                S2_STEP(0) S2_STEP(1) S2_STEP(2) S2_STEP(3) S2_STEP(4) S2_STEP(5) S2_STEP(6) S2_STEP(7) S2_STEP(8)
+            }
         }
         if (g == 0) RAW_BARRIER();                         // both groups aligned: every wave is done with the stages and the patch
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -672,6 +819,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_s2_kernel(ConvArgs a, int n_ti
         const int nvb = vb + v_step;
         if (nvb < v_end) SETUP_TILE(nvb);
 
+        [[maybe_unused]] bool pooled_now = false;
         // ---- epilogue of the current tile: BN + ReLU on the accumulators, fp16 straight from the registers (S2_DIRECT) or through LDS, 32 KB per
         //      channel half, two rounds of 128 pixels (conv_igemm_wide_persist's, with this kernel's tile-pixel order) ----
         if (S2_ABL_NOEPI) {
@@ -694,7 +842,87 @@ __global__ __launch_bounds__(512, 1) void conv3x3_s2_kernel(ConvArgs a, int n_ti
             }
             const int k = tl & 15;
             float* const poolp = TW == 4 ? ((a.wgt_b && chl >= split) ? a.pool_b : a.pool) : nullptr;     // wave-uniform (per channel half)
-            if (poolp) {
+            if constexpr (SKIP) pooled_now = poolp != nullptr;
+            if (SKIP && poolp) {
+                if constexpr (SKIP) {
+                // Pad-skip: an image's 16 positions are the 8 tile registers of this lane and of the same lane of the partner wave (wp ^ 1).  The sum
+                // keeps the order of the DPP tree below — map row y: (p0 + p1) + (p2 + p3), then (r0 + r1) + (r3 + r2), then * 1/16 — through the staging
+                // area at E_OFF, which nothing of the next tile touches before its step 0 (conv3x3_pw's persistent pooled tail): wave wp sends the tiles
+                // of rows 2 (1 - wp), 2 (1 - wp) + 1 and sums rows 2 wp, 2 wp + 1 (a pair p0 + p1 / p2 + p3 is one value of each wave; float addition
+                // commutes); pixel wave 1 then sends r2 + r3 and pixel wave 0 stores.  Slot of wave w: 8 KB, [tile 0..3][quad 0..1][lane] float4.
+                // Three barriers per 32-channel half h: a channel group that stores plainly (mixed pair) takes the same six below.
+                char* const X = smem + G::E_OFF;
+                char* const mine_x = X + wave * 8192 + lane * 16;
+                char* const theirs_x = X + (wave ^ 1) * 8192 + lane * 16;
+                const int chw = chl + wc * 64 + 8 * kq;
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    f32x4_e sc[2], bi[2];
+#pragma unroll
+                    for (int ii = 0; ii < 2; ++ii) {
+                        sc[ii] = *(const f32x4_e*)(bn_scale + chw + 32 * h + 4 * ii);
+                        bi[ii] = *(const f32x4_e*)(bn_bias + chw + 32 * h + 4 * ii);
+                    }
+                    float xs[TP][8];                                      // relu(bn(.)) of this lane's 8 channels at its 8 positions
+#pragma unroll
+                    for (int j = 0; j < TP; ++j)
+#pragma unroll
+                        for (int ii = 0; ii < 2; ++ii)
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) xs[j][4 * ii + e] = fmaxf(__builtin_fmaf(acc[2 * h + ii][j][e], sc[ii][e], bi[ii][e]), 0.f);
+#pragma unroll
+                    for (int jj = 0; jj < 4; ++jj)
+#pragma unroll
+                        for (int q = 0; q < 2; ++q) {
+                            f32x4_e t;
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) t[e] = wp ? xs[jj][4 * q + e] : xs[4 + jj][4 * q + e];
+                            *(f32x4_e*)(mine_x + (jj * 2 + q) * 1024) = t;
+                        }
+                    lds_barrier();
+                    float rs[2][8];                                       // the two row sums of this wave
+#pragma unroll
+                    for (int r = 0; r < 2; ++r)
+#pragma unroll
+                        for (int q = 0; q < 2; ++q) {
+                            const f32x4_e t0 = *(const f32x4_e*)(theirs_x + ((2 * r) * 2 + q) * 1024), t1 = *(const f32x4_e*)(theirs_x + ((2 * r + 1) * 2 + q) * 1024);
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) {
+                                const float o0 = wp ? xs[4 + 2 * r][4 * q + e] : xs[2 * r][4 * q + e], o1 = wp ? xs[4 + 2 * r + 1][4 * q + e] : xs[2 * r + 1][4 * q + e];
+                                const float s01 = o0 + t0[e], s23 = o1 + t1[e];
+                                rs[r][4 * q + e] = s01 + s23;
+                            }
+                        }
+                    float half_sum[8];
+#pragma unroll
+                    for (int c = 0; c < 8; ++c) half_sum[c] = rs[0][c] + rs[1][c];          // r0 + r1 | r2 + r3
+                    lds_barrier();                                        // every wave has read its partner's slot
+                    if (wp) {
+#pragma unroll
+                        for (int q = 0; q < 2; ++q) {
+                            f32x4_e t;
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) t[e] = half_sum[4 * q + e];
+                            *(f32x4_e*)(theirs_x + q * 1024) = t;
+                        }
+                    }
+                    lds_barrier();
+                    if (!wp) {
+                        const int n = cur_n0 + l16;
+#pragma unroll
+                        for (int q = 0; q < 2; ++q) {
+                            const f32x4_e t = *(const f32x4_e*)(mine_x + q * 1024);
+                            f32x4_e pv;
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) pv[e] = (half_sum[4 * q + e] + t[e]) * (1.f / 16.f);
+                            if (n < a.N) *(f32x4_e*)(poolp + (size_t)n * oc + chg + wc * 64 + 8 * kq + 32 * h + 4 * q) = pv;
+                        }
+                    }
+                }
+                // (the next tile's own-period pieces overwrite the staging area from its step 0: every exchange read is complete before the tile-start barrier)
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                }
+            } else if (poolp) {
                 // ReLU + global average pool fused (the conv feeds an exit head only): a wave's pixel tile j is image wp * 8 + j of
                 // the tile, its 16 pixels the 16 lanes of a DPP row — four v_add_f32 with DPP (quad xor 1, xor 2, half mirror, row
                 // mirror) leave the sum in every lane; lane 0 of each row stores 4 consecutive channels as fp32.  Nothing goes
@@ -736,10 +964,12 @@ __global__ __launch_bounds__(512, 1) void conv3x3_s2_kernel(ConvArgs a, int n_ti
 #pragma unroll
                 for (int j = 0; j < TP; ++j) {
                     const int p = pbase + 16 * j + l16;
-                    int n = cur_n0 + G::p_img(p);
+                    // (pad-skip: lane l16 of tile j is image l16 at the tile's position)
+                    int n = cur_n0 + (SKIP ? l16 : G::p_img(p));
+                    const int opos = SKIP ? S2Skip::t_y(j) * TW + S2Skip::t_x(wp, j) : G::p_oy(p) * TW + G::p_ox(p);
                     if constexpr (IMAP) n = row_tabs[cur_tsel * 16 + G::p_img(p)];      // tensor row, -1 beyond N
                     else if (n >= a.N) n = -1;
-                    _Float16* const dst = outp + ((size_t)(n < 0 ? 0 : n) * (TW * TW) + G::p_oy(p) * TW + G::p_ox(p)) * oc + chg + cw;
+                    _Float16* const dst = outp + ((size_t)(n < 0 ? 0 : n) * (TW * TW) + opos) * oc + chg + cw;
 #pragma unroll
                     for (int h = 0; h < 2; ++h) {
                         half8_e o;
@@ -752,6 +982,14 @@ __global__ __launch_bounds__(512, 1) void conv3x3_s2_kernel(ConvArgs a, int n_ti
                                 o[4 * ii + e] = a16_from_f32<BF>(v);
                             }
                         if (n >= 0 && !S2_ABL_NOSTORE) *(half8_e*)(dst + 32 * h) = o;
+                    }
+                }
+                if constexpr (SKIP) {
+                    // mixed pair: the other channel group of this workgroup pools through LDS — s_barrier is workgroup-wide: its six barriers
+                    const float* const pool_o = (a.wgt_b && cur_ch0 + 128 * (1 - g) >= split) ? a.pool_b : a.pool;
+                    if (pool_o) {
+#pragma unroll
+                        for (int b = 0; b < 6; ++b) lds_barrier();
                     }
                 }
             } else
@@ -809,9 +1047,12 @@ __global__ __launch_bounds__(512, 1) void conv3x3_s2_kernel(ConvArgs a, int n_ti
                 }
             }
         }
+        if constexpr (SKIP) pooled_prev = pooled_now;
         stores16 = cur_n0 + IMGS <= a.N;              // (a pooled half issues 32 stores: vmcnt(16) then waits for half of them, never for less)
         vb = nvb;
     }
+#undef S2_CHUNKS_S
+#undef S2_STEP_S
 #undef S2_STEP
 #undef END_OF_STEP_WAIT
 #undef WAIT_VM
@@ -826,6 +1067,17 @@ __global__ __launch_bounds__(512, 1) void conv3x3_s2_kernel(ConvArgs a, int n_ti
 #undef ISSUE_W
 #undef ISSUE_W_HALF
 #undef A_TILE
+}
+
+template <int TW, bool BF, bool IMAP, bool MSK = false, int CT_ = 256>
+__global__ __launch_bounds__(512, 1) void conv3x3_s2_kernel(ConvArgs a, int n_tiles) {
+    conv3x3_s2_body<TW, BF, IMAP, MSK, CT_, false>(a, n_tiles);
+}
+
+// the pad-skip form of the 8x8 -> 4x4 class ("s2_pad_skip")
+template <bool BF>
+__global__ __launch_bounds__(512, 1) void conv3x3_s2_skip_kernel(ConvArgs a, int n_tiles) {
+    conv3x3_s2_body<4, BF, false, false, 256, true>(a, n_tiles);
 }
 
 
@@ -866,6 +1118,15 @@ static int launch_s2(const ConvArgs& a, int n_cu, hipStream_t s) {
         }
     }
 #define S2_LAUNCH(BF_, IMAP_) hipLaunchKernelGGL((conv3x3_s2_kernel<TW, BF_, IMAP_>), grid, block, 0, s, a, (int)tiles)
+    if constexpr (TW == 4) {
+        // pad-skip form ("s2_pad_skip"): by shape and options only, never by N; row-table launches keep the 4 x 4-block tiles
+        if (opt_s2_pad_skip() && !a.imap && !a.in_bits) {
+            if (a.bf16) hipLaunchKernelGGL((conv3x3_s2_skip_kernel<true>), grid, block, 0, s, a, (int)tiles);
+            else hipLaunchKernelGGL((conv3x3_s2_skip_kernel<false>), grid, block, 0, s, a, (int)tiles);
+            BMI_CHECK_LAUNCH();
+            return BMI_OK;
+        }
+    }
     if (a.in_bits) {
         if constexpr (TW == 16) {
             ConvArgs al = a;

@@ -208,6 +208,7 @@ static int set_named_option(BmiOptions& o, const char* name, int32_t value) {
         {"pw_persist", &BmiOptions::pw_persist, 0, 1},
         {"pw_pad_skip", &BmiOptions::pw_pad_skip, 0, 1},
         {"pw_pad_skip8", &BmiOptions::pw_pad_skip8, 0, 1},
+        {"s2_pad_skip", &BmiOptions::s2_pad_skip, 0, 1},
         {"lazy_planar", &BmiOptions::lazy_planar, 0, 1},
         {"ws_no_reuse", &BmiOptions::ws_no_reuse, 0, 1},                 // read by bmi_plan
         {"wide_persist_min_x10", &BmiOptions::wide_persist_min, 10, 1000},

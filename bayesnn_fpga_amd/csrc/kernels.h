@@ -235,6 +235,7 @@ struct BmiOptions {
     int pw_persist = 1;          // 1: plain-epilogue launches of conv3x3_pw run in its persistent form (conv3x3_pwp_kernel), 0: never
     int pw_pad_skip = 1;         // 1: conv3x3_pw on 4x4 maps in the pad-skip form (MFMA pixel tile = one output position across 16 images: padding taps are never read or multiplied), 0: the 4 x 4-block tiles
     int pw_pad_skip8 = 1;        // 1: the persistent conv3x3_pw launches on 8x8 maps take 16 images x one 4x4 quadrant as the workgroup tile in the pad-skip form (PwGeomSkip8), 0: the 4 x 4-block tiles
+    int s2_pad_skip = 1;         // 1: conv3x3_s2 on 8x8 -> 4x4 maps in the pad-skip form (MFMA pixel tile = one output position across the tile's 16 images: the (position, tap) pairs that read only padding are never read or multiplied), 0: the 4 x 4-block tiles; row-table launches always the latter
     int lazy_planar = 1;         // 1: lazy sites whose readers are all stride-2 consumers store their scaled copy + bits in the planar layout
     int ws_no_reuse = 0;         // bmi_plan: every suffix tensor keeps its own workspace range (per-layer traces)
     int conv_patch64 = 1;        // 1: 64 -> 64-class 3x3 stride-1 convs on 32-wide maps run in conv3x3_patch's 64-channel tile, 0: conv_igemm
@@ -257,7 +258,7 @@ struct BmiOptionScope {
 BMI_OPT(mfma_shape_patch) BMI_OPT(mfma_shape_wide) BMI_OPT(unit_dtype) BMI_OPT(wide_persist_min) BMI_OPT(conv_pw) BMI_OPT(conv_wide)
 BMI_OPT(mask_lazy) BMI_OPT(conv_pool) BMI_OPT(conv_s2) BMI_OPT(split_shx) BMI_OPT(split_tile) BMI_OPT(conv_seam) BMI_OPT(conv_stream)
 BMI_OPT(splitk) BMI_OPT(dense_exact) BMI_OPT(lazy_order) BMI_OPT(epilogue_lite) BMI_OPT(xcd_split) BMI_OPT(pw_persist) BMI_OPT(lazy_planar)
-BMI_OPT(pw_pad_skip) BMI_OPT(pw_pad_skip8) BMI_OPT(ws_no_reuse) BMI_OPT(head_batch) BMI_OPT(conv_patch64) BMI_OPT(splitk_tiles) BMI_OPT(pair_prefix) BMI_OPT(patch_direct)
+BMI_OPT(pw_pad_skip) BMI_OPT(pw_pad_skip8) BMI_OPT(s2_pad_skip) BMI_OPT(ws_no_reuse) BMI_OPT(head_batch) BMI_OPT(conv_patch64) BMI_OPT(splitk_tiles) BMI_OPT(pair_prefix) BMI_OPT(patch_direct)
 #undef BMI_OPT
 int xcd_split_for(int n_ctiles, size_t weight_bytes);
 

@@ -218,6 +218,11 @@ const char* bmi_error_string(int code);
  *   "pw_pad_skip8"                          0 | 1: the same on 8x8 maps, persistent conv3x3_pw launches only: a workgroup tile is 16 images x one 4x4
  *                                           quadrant of the map, its sub-patch the quadrant's 5 x 5 real input cells (1, default), or four whole
  *                                           images in 4 x 4 blocks with the ring in LDS (0); the same bits either way
+ *   "s2_pad_skip"                           0 | 1: the same for conv3x3_s2 on 8x8 -> 4x4 maps (plain, pair and pooled launches; row-table launches keep
+ *                                           the 4 x 4 blocks): the parity planes keep their size and refill schedule, a plane's cells are stored
+ *                                           position-major with the image fastest, and the 23 of 144 (position, tap) pairs that read only the
+ *                                           padding row / column are never read or multiplied (1, default), or 4 x 4 blocks of one image (0); the
+ *                                           same bits either way
  *   "lazy_planar"                           0 | 1: a lazy site whose readers are all stride-2 consumers (conv3x3_s2 on 32x32 maps, the fused 1x1
  *                                           stride-2 shortcut of conv3x3_patch) stores its scaled copy and keep bits as 32-channel planes with
  *                                           the even columns of a row in front of the odd ones — what such a reader DMAs is then contiguous,
