@@ -91,7 +91,7 @@ struct PatchGeom {
 // the 8 KB weight stage is read by every wave, and the launch finishes in the per-quad epilogue (conv_epilogue.h: epilogue_quad — every site kind,
 // residual, ReLU; no LDS): same K order per accumulator as the 128-channel tile.  No fused shortcut (a 64-channel block has no downsample path).
 // DIRECT (round 6; the 16x16 class, 16x16x32 MFMAs, plain epilogue and the two BasicBlock tails): the epilogue runs on the accumulator registers and
-// stores straight to HBM — what conv3x3_pw's persistent kernel does since round 4 (PWP_DIRECT).  The MFMA rows of a wave's four channel tiles are a
+// stores straight to HBM — what conv3x3_pw's persistent kernel does since round 4.  The MFMA rows of a wave's four channel tiles are a
 // PERMUTATION of its 64 channels — LDS weight row 16 i + r holds channel 32 (i >> 1) + 8 (r >> 2) + 4 (i & 1) + (r & 3), applied where the weight DMA picks
 // its source row, so nothing on the LDS side moves — and a lane's sixteen accumulators of a pixel are two runs of 8 consecutive channels (8 q + 0..7 and
 // 32 + 8 q + 0..7, q = lane >> 4): two 16-byte stores per pixel tile (the four lanes of a pixel write 64 contiguous bytes), the residual as two 16-byte loads,

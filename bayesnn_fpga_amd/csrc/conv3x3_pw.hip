@@ -276,13 +276,6 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pw_kernel(ConvArgs a) {
         _Pragma("unroll") for (int i = 0; i < G::WROWS; ++i)                                     \
             GLDS16(wsrc[i] + (KOFF), wst + (ST) * G::WST + (i * 512 + wave * 64) * 16);          \
     }
-#define ISSUE_W_HALF(KOFF, ST, I) GLDS16(wsrc[I] + (KOFF), wst + (ST) * G::WST + ((I) * 512 + wave * 64) * 16)
-#ifndef PW_ABL_HALFREADS
-#define PW_ABL_HALFREADS 0   // timing probe (wrong results): every second pixel-fragment read is skipped (8 instead of 12 reads per 32 MFMAs)
-#endif
-#ifndef PW_WSPLIT
-#define PW_WSPLIT 0          // 1: a wave's two weight DMA instructions of a K-step go out in the two phases (one each)
-#endif
     ISSUE_W(0, 0);
     __builtin_amdgcn_sched_barrier(0);
     // sub-patch: piece q = tid + 512 i -> cell q >> 2, position q & 3 holds chunk pos ^ 2 (y & 1); element offset of its
@@ -371,18 +364,12 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pw_kernel(ConvArgs a) {
                 _Pragma("unroll") for (int i = 0; i < TI; ++i) af[i] = *(const half8*)(ws_ + i * 16 * 64);     \
             }                                                                                                  \
             _Pragma("unroll") for (int j = 0; j < 4; ++j)                                                      \
-                if (!PW_ABL_HALFREADS || !(j & 1)) bf[j] = *(const half8*)(pb_ + boff[ky_] + G::cell_delta(4 * kk + j) * 64); \
-                else bf[j] = bf[j - 1];                                                                        \
-            if (kk == 0 && !PW_WSPLIT) {                                                                       \
+                bf[j] = *(const half8*)(pb_ + boff[ky_] + G::cell_delta(4 * kk + j) * 64);                     \
+            if (kk == 0) {                                                                                     \
                 /* weights of the step after next: (tap + 2) of this chunk, or taps 0 / 1 of the next one */   \
                 if ((TAP) < 7) { ISSUE_W(((TAP) + 2) * a.Cin + c32, ((TAP) + 2) % 3); }                        \
                 else if (!last) { ISSUE_W(((TAP) - 7) * a.Cin + c32 + 32, ((TAP) + 2) % 3); }                  \
                 if ((TAP) >= 1 && (TAP) <= G::ITER_P && !last) { ISSUE_P((TAP) - 1, c32 + 32, nb); }           \
-            }                                                                                                  \
-            if (PW_WSPLIT) {                                                                                   \
-                if ((TAP) < 7) { ISSUE_W_HALF(((TAP) + 2) * a.Cin + c32, ((TAP) + 2) % 3, kk); }               \
-                else if (!last) { ISSUE_W_HALF(((TAP) - 7) * a.Cin + c32 + 32, ((TAP) + 2) % 3, kk); }         \
-                if (kk == 1 && (TAP) >= 1 && (TAP) <= G::ITER_P && !last) { ISSUE_P((TAP) - 1, c32 + 32, nb); } \
             }                                                                                                  \
             if (kk == 1 && g == 1) END_OF_STEP_WAIT(TAP);      /* interval 4T+3, group 1: LOAD part */         \
             RAW_BARRIER();                                                                                     \
@@ -461,7 +448,6 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pw_kernel(ConvArgs a) {
 #undef END_OF_STEP_WAIT
 #undef WAIT_VM
 #undef ISSUE_W
-#undef ISSUE_W_HALF
 #undef ISSUE_P
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 
@@ -774,8 +760,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 // that would prefetch "the next chunk" — the weight stages of steps 0 / 1 (issued at taps 7 / 8) and the pieces of sub-patch 0 (taps
 // 1..ITER_P) — fetch the NEXT TILE's instead, with the unchanged counted-vmcnt schedule; Cin % 64 == 0 makes the last chunk odd, so what it
 // prefetches lands in stages 0 / 1 and sub-patch buffer 0.  The LDS map [W0 | W1 | P0 | W2 | P1 | pad] keeps those three outside the
-// 64 KB [W2 | P1 | pad] the shortcut's K-steps work in (and the epilogue did before PWP_DIRECT: conv3x3_s2's two rounds of 128 pixels per channel
-// half; BN comes from an LDS table — a global load there would wait for every DMA in flight).  A full tile leaves its 16 output stores per thread in flight
+// 64 KB [W2 | P1 | pad] the shortcut's K-steps and the pad-skip pooled exchange work in (BN comes from an LDS table — a global load in the
+// epilogue would wait for every DMA in flight).  A full tile leaves its 16 output stores per thread in flight
 // across the tile boundary (vmcnt(16)).  Why: per-tile fixed cost of conv3x3_pw from its own K = 2304 / 4608 rates (1308 / 1422 TFLOP/s, corrected
 // for the last partial round of tiles): 14-21 K-steps' worth per tile, of which the prologue's HBM round trip and the workgroup hand-over are
 // what a persistent walk removes.  Same K order, same arithmetic, same bits as conv3x3_pw_kernel<TW, PLAIN>.
@@ -793,13 +779,11 @@ struct PwpGeom {
     static_assert(LDS_BYTES <= 160 * 1024, "LDS");
 };
 
-#ifndef PWP_DIRECT
-#define PWP_DIRECT 1      // the MFMA rows of a wave's four channel tiles are a PERMUTATION of its 64 channels — row r of tile i is channel
-                          // 32 (i >> 1) + 8 (r >> 2) + 4 (i & 1) + (r & 3) — so that a lane's accumulators are, per pixel, two runs of 8 consecutive
-                          // channels: the epilogue stores them straight from the registers (two 16-byte stores per pixel tile; the four lanes of a
-                          // pixel write 64 contiguous bytes per store) with no trip through LDS and no barrier.  0: conv3x3_s2's epilogue through LDS
-#endif
-// EPIK: BMI_EPI_PLAIN, or (PWP_DIRECT only) BMI_EPI_LITE_RES / BMI_EPI_LITE_RES_MC — the BasicBlock tails (residual whose rows are the output's rows,
+// The MFMA rows of a wave's four channel tiles are a PERMUTATION of its 64 channels — row r of tile i is channel
+// 32 (i >> 1) + 8 (r >> 2) + 4 (i & 1) + (r & 3) — so that a lane's accumulators are, per pixel, two runs of 8 consecutive channels: the epilogue
+// stores them straight from the registers (two 16-byte stores per pixel tile; the four lanes of a pixel write 64 contiguous bytes per store) with
+// no trip through LDS and no barrier.
+// EPIK: BMI_EPI_PLAIN, or BMI_EPI_LITE_RES / BMI_EPI_LITE_RES_MC — the BasicBlock tails (residual whose rows are the output's rows,
 // ReLU, optionally the 2-bit elementwise site) finished straight from the registers too: a lane fetches the two 16-byte residual runs of each of its
 // pixel tiles itself (the four lanes of a pixel read 64 contiguous bytes per instruction), so the lite epilogue's residual DMA, its 2 x 64 KB of LDS and
 // its three barriers are gone and these launches can take the persistent walk.  Same arithmetic in the same order as epilogue_lite: the same bits.
@@ -809,7 +793,7 @@ template <int TW, bool BF, bool SHORTCUT, int EPIK = BMI_EPI_PLAIN, bool POOLP =
 __global__ __launch_bounds__(512, 1) void conv3x3_pwp_kernel(ConvArgs a, int n_tiles) {
     static_assert(!POOLP || (TW == 4 && EPIK != BMI_EPI_PLAIN), "pooled output: the 4x4 maps' BasicBlock tails");
     static_assert(!SKIP || TW == 4 || TW == 8, "pad-skip: 4x4 maps, 8x8 maps by quadrants");
-    static_assert(EPIK == BMI_EPI_PLAIN || (PWP_DIRECT && !SHORTCUT && (EPIK == BMI_EPI_LITE_RES || EPIK == BMI_EPI_LITE_RES_MC || EPIK == BMI_EPI_LITE_RES_MSK)),
+    static_assert(EPIK == BMI_EPI_PLAIN || (!SHORTCUT && (EPIK == BMI_EPI_LITE_RES || EPIK == BMI_EPI_LITE_RES_MC || EPIK == BMI_EPI_LITE_RES_MSK)),
                   "epilogue kind");
     using G = typename PwGeomSel<TW, SKIP>::type;
     using L = PwpGeom<G>;
@@ -866,8 +850,8 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pwp_kernel(ConvArgs a, int n_t
 #pragma unroll
     for (int i = 0; i < (SK8 ? 1 : G::WROWS); ++i) {
         const int row = (tid >> 2) + 128 * i;
-        // (PWP_DIRECT: a fragment's 16 lanes read rows 8 a + b + const, a = 0..3, b = 0..3: the chunk position alternates with row >> 3)
-        woff[i] = 2u * ((unsigned)row * Ktot + (((tid & 3) ^ (((row >> (PWP_DIRECT ? 3 : 2)) & 1) << 1)) << 3));
+        // (a fragment's 16 lanes read rows 8 a + b + const, a = 0..3, b = 0..3: the chunk position alternates with row >> 3)
+        woff[i] = 2u * ((unsigned)row * Ktot + (((tid & 3) ^ (((row >> 3) & 1) << 1)) << 3));
     }
     const unsigned wbytes = 2u * (unsigned)CT * Ktot;
     const unsigned HWC = (unsigned)a.H * a.W * a.Cin;
@@ -926,9 +910,9 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pwp_kernel(ConvArgs a, int n_t
     }
 
     // ---- per-lane fragment geometry (tile-independent) ----
-    const int a_off = (g * 128 + wc * 64 + (PWP_DIRECT ? 8 * (l16 >> 2) + (l16 & 3) : l16)) * 64;
+    const int a_off = (g * 128 + wc * 64 + (8 * (l16 >> 2) + (l16 & 3))) * 64;      // (the inner parentheses shape the instruction order: keep)
     // byte offset of channel tile i's row of this lane relative to a_off
-#define A_TILE(I) (PWP_DIRECT ? (32 * ((I) >> 1) + 4 * ((I) & 1)) * 64 : (I) * 16 * 64)
+#define A_TILE(I) ((32 * ((I) >> 1) + 4 * ((I) & 1)) * 64)
     const int pbase = wp * 128;
     const int a_byte = (kq ^ (((l16 >> 2) & 1) << 1)) << 4;
     int boff[3];
@@ -1110,7 +1094,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pwp_kernel(ConvArgs a, int n_t
             constexpr int XROWS = G::PX / 128, SST = G::WST + G::PX * 64;
             char* const sbase = smem + L::E_OFF;
             const int lg = ((tid & 3) ^ (((tid >> 4) & 1) << 1)) * 8;                                  // pixel rows: chunk position alternates with row >> 2
-            const int lgw = PWP_DIRECT ? ((tid & 3) ^ (((tid >> 5) & 1) << 1)) * 8 : lg;               // weight rows (PWP_DIRECT): with row >> 3
+            const int lgw = ((tid & 3) ^ (((tid >> 5) & 1) << 1)) * 8;                                 // weight rows: with row >> 3
             int x2off[XROWS];
 #pragma unroll
             for (int i = 0; i < XROWS; ++i) {
@@ -1303,7 +1287,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pwp_kernel(ConvArgs a, int n_t
                     }
                 }
             }
-        } else if constexpr (PWP_DIRECT) {
+        } else {
             // ---- epilogue straight from the registers: lane (kq, l16) holds, for pixel tile j, channels 8 kq .. + 7 (tiles 0, 1) and
             //      32 + 8 kq .. + 7 (tiles 2, 3) of the wave's 64 channels of pixel pbase + 16 j + l16 ----
             const int chw = ch0 + 128 * g + wc * 64 + 8 * kq;
@@ -1333,55 +1317,6 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pwp_kernel(ConvArgs a, int n_t
                     if (n < a.N) *(half8_e*)(dst + 32 * h) = o;
                 }
             }
-        } else {
-            char* const E = smem + L::E_OFF + g * 32768;
-            int tl = tid & 255;
-            asm volatile("" : "+v"(tl));
-            const int chl = ch0 + 128 * g;
-            const int k = tl & 15;
-#pragma unroll
-            for (int rr = 0; rr < 2; ++rr) {
-                if (rr) lds_barrier();
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const int c4 = chl + wc * 64 + 16 * i + 4 * kq;
-                    const f32x4_e sc = *(const f32x4_e*)(bn_scale + c4), bi = *(const f32x4_e*)(bn_bias + c4);
-                    const int cq = wc * 8 + 2 * i + (kq >> 1);
-#pragma unroll
-                    for (int jj = 0; jj < 4; ++jj) {
-                        const int p = wp * 64 + jj * 16 + l16;
-                        half4 o;
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            float v = acc[i][4 * rr + jj][e] * sc[e] + bi[e];
-                            if (a.relu) v = fmaxf(v, 0.f);
-                            o[e] = a16_from_f32<BF>(v);
-                        }
-                        *(half4*)(E + p * 256 + ((cq ^ l16) << 4) + (((kq ^ jj) & 1) << 3)) = o;
-                    }
-                }
-                lds_barrier();
-#pragma unroll
-                for (int hb = 0; hb < 2; ++hb) {
-                    half8_e o8[4];
-#pragma unroll
-                    for (int it = 0; it < 4; ++it) {
-                        const int pl = (tl >> 4) + 16 * (4 * hb + it);
-                        o8[it] = *(const half8_e*)(E + pl * 256 + ((k ^ (pl & 15)) << 4));
-                    }
-#pragma unroll
-                    for (int it = 0; it < 4; ++it) {
-                        const int pl = (tl >> 4) + 16 * (4 * hb + it);
-                        const int p = (pl >> 6) * 128 + rr * 64 + (pl & 63);
-                        const int n = n0 + G::p_img(p);
-                        if (n >= a.N) continue;
-                        half8_e v = o8[it];
-                        if (it & 1) v = __builtin_shufflevector(v, v, 4, 5, 6, 7, 0, 1, 2, 3);
-                        *(half8_e*)(a.out + ((size_t)n * (TH * TW) + P_OY(p) * TW + P_OX(p)) * a.Cout + chl + 8 * k) = v;
-                    }
-                }
-            }
-            lds_barrier();      // the staging area (W2 | P1) is free again for the next tile's K-steps
         }
         stores16 = !POOLP && n0 + IMGS <= a.N;          // (a pooled tail: lane 0 of a row stores 32 quads, the others nothing: the next tile drains)
         if (!more) break;
@@ -1443,7 +1378,7 @@ static int launch_pw(const ConvArgs& a_in, hipStream_t s) {
     if (a.pool) {   // fp32 means over the 4x4 map instead of the map (the conv feeds one exit head only): the lite epilogue on the registers
         if constexpr (TW == 4) {
             if (epi == BMI_EPI_GENERAL) return BMI_ERR_UNSUPPORTED;
-            if (PWP_DIRECT && opt_pw_persist() && opt_conv_pw() < 3 && opt_epilogue_lite() == 1 && epi == BMI_EPI_LITE && a.res && a.res_mod >= a.N && a.relu &&
+            if (opt_pw_persist() && opt_conv_pw() < 3 && opt_epilogue_lite() == 1 && epi == BMI_EPI_LITE && a.res && a.res_mod >= a.N && a.relu &&
                 a.site.kind == BMI_SITE_NONE && !a.imap && !a.in2 && a.Cin % 64 == 0 && a.Cout <= 512 && a.in_mod >= a.N &&
                 (size_t)a.H * a.W * a.Cin * PwGeom<4>::IMGS * 2 < 0xfffffff0ull && (size_t)a.N * a.Ho * a.Wo * a.Cout < (8ull << 32)) {
                 // the pooled BasicBlock tail on the persistent walk (conv3x3_pwp_kernel<4, .., LITE_RES, POOLP>): the same bits
@@ -1495,7 +1430,7 @@ static int launch_pw(const ConvArgs& a_in, hipStream_t s) {
         BMI_CHECK_LAUNCH();
         return BMI_OK;
     }
-    if (PWP_DIRECT && opt_pw_persist() && opt_conv_pw() < 3 && (epi_fine == BMI_EPI_LITE_RES || epi_fine == BMI_EPI_LITE_RES_MC || epi_fine == BMI_EPI_LITE_RES_MSK) && !a.in2 && a.Cin % 64 == 0 &&
+    if (opt_pw_persist() && opt_conv_pw() < 3 && (epi_fine == BMI_EPI_LITE_RES || epi_fine == BMI_EPI_LITE_RES_MC || epi_fine == BMI_EPI_LITE_RES_MSK) && !a.in2 && a.Cin % 64 == 0 &&
         a.Cout <= 512 && a.in_mod >= a.N && (size_t)a.H * a.W * a.Cin * PIMGS * 2 < 0xfffffff0ull && (size_t)a.N * a.Ho * a.Wo * a.Cout < (8ull << 32)) {
         // the BasicBlock tails on the persistent walk, finished straight from the registers (conv3x3_pwp_kernel<.., EPIK>): the same bits
         static const int n_cu = [] {

@@ -20,7 +20,7 @@
 //   tile       = IMGS whole output maps (256 pixels: 1 map of 16x16, 4 of 8x8, 16 of 4x4) x 256 output channels
 //   waves      = 2 channel halves (g) x [2 (channels) x 2 (pixels)], wave tile 64 ch x 128 px = 4 x 8 tiles of v_mfma_f32_16x16x32;
 //                the 16 pixels of an MFMA tile are a 4 x 4 block of output pixels (conv3x3_pw's tile-pixel order)
-//   LDS        = [W0 | W1 (| W2) | patch pieces | (pad) | last stage] + BN table: three or four weight stages [256 ch][32 k] (64-byte rows), the patch as
+//   LDS        = [W0 | W1 | patch pieces | (pad) | last stage] + BN table: three weight stages [256 ch][32 k] (64-byte rows), the patch as
 //                NPT pieces of 128 cells x 64 B (piece = one DMA instruction per thread), planes back to back with plane A
 //                padded to whole pieces.  132-152 KB: one 512-thread workgroup per CU.
 //   64-B rows  = four rows share a 256-byte bank window.  ds_read_b128 is served in four lane groups {0-3, 12-15, 20-27},
@@ -34,7 +34,7 @@
 //                immediates (the 9 steps of a chunk are unrolled).  Per step at most two patch pieces ride along.
 //   persistent = one workgroup per CU walks the tiles; the next tile's weight stages 0 / 1 and its plane A / B pieces are
 //                issued when the main loop ends and land while the epilogue runs (BN + ReLU on the accumulators, fp16 straight from the
-//                registers: S2_DIRECT; formerly two rounds of 128 pixels per channel half through the 64 KB the C / D pieces and W2 occupy).
+//                registers).
 //   pair mode  = as conv_igemm_wide: channel tiles >= split use the second conv's weights / BN / output tensor.
 //   epilogue   = plain (BN + ReLU) only: every stride-2 conv of the path.  Anything else stays with conv_igemm_wide.
 //
@@ -82,99 +82,30 @@
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 
-#ifndef S2_DIRECT
-#define S2_DIRECT 1          // conv3x3_pwp's PWP_DIRECT: the MFMA rows of a wave's four channel tiles are a permutation of its 64 channels (row r of tile i =
-                             // channel 32 (i >> 1) + 8 (r >> 2) + 4 (i & 1) + (r & 3)), so a lane holds two runs of 8 consecutive channels per pixel and the
-                             // epilogue stores them straight from the registers — no trip through LDS, no barrier.  0: the two rounds through LDS
-#endif
-#ifndef S2_RELAX0
-#define S2_RELAX0 0          // 1: the previous tile's 16 output stores may stay in flight through step 0 of the next tile (see END_OF_STEP_WAIT).
-                             // Built and measured in round 4 (same-box A/B on the five stride-2 classes, bit-identical): neutral (+-0.5 %): off
-#endif
-#ifndef S2_DRAIN_STORES
-#define S2_DRAIN_STORES 0    // 1 (diagnostic): every tile starts with vmcnt(0)
-#endif
-#ifndef S2_WSPLIT
-#define S2_WSPLIT 0          // 1: a wave issues its two weight DMA instructions of a K-step in the two phases (one each) instead of both in phase 0
-#endif
-#ifndef S2_STORE_SC1
-#define S2_STORE_SC1 0       // 1: the output tile leaves with write-through stores that do not stay in the XCD's L2 (sc1, inline asm).  A 32-channel
-                             // chunk is half (a quarter) of an input pixel's 128-byte lines, whose other half is asked for 9 K-steps later, and
-                             // the 128 KB of output per tile push those lines out of the 4 MB L2 in between: with sc1 stores rocprofv3 FETCH_SIZE
-                             // over the six stride-2 launches of the headline step went 16.3 -> 14.3 GB (conv_igemm_wide: 17.9) at UNCHANGED
-                             // wall time (the re-fetches are Infinity-Cache hits; profiles/experiments/r3_s2_sc1_stores.log).  OFF: hipcc does
-                             // not model an asm store (cdna_hip_programming.md 5.7 item 1); the first build without the trailing s_nop failed
-                             // every model parity test, and with it one build still gave ONE image of one dynamic-exit test a 1e-6 deviation
-                             // that a recompile with an unrelated edit removed — a data-register hazard that depends on instruction
-                             // placement is not worth a counter that does not show up in the time.
-#endif
-#ifndef S2_PIECE_PHASE
-#define S2_PIECE_PHASE 1     // phase of a K-step whose LOAD part issues the step's patch pieces (phase 0 carries 8 fragment reads and
-                             // the 2 weight DMAs, phase 1 only 4 reads)
-#endif
-#ifndef S2_NST_BIG
-#define S2_NST_BIG 3         // weight stages on the 32x32 / 16x16 input maps (3 | 4: four measured 1-2 % slower, below; the 8x8 maps have LDS for 3)
-#endif
-
-// Timing probes (tools/ab_build.py name:-DS2_ABL_...=1; wrong results by construction, never in the product build): which part of a
-// tile's life the time goes to.
-#ifndef S2_ABL_NOPATCH
-#define S2_ABL_NOPATCH 0     // no patch DMA (the main loop reads whatever is in LDS)
-#endif
-#ifndef S2_ABL_NOSTORE
-#define S2_ABL_NOSTORE 0     // the epilogue runs but stores nothing
-#endif
-#ifndef S2_ABL_HALFREADS
-#define S2_ABL_HALFREADS 0   // every second pixel-fragment read is skipped (8 instead of 12 reads per 32 MFMAs)
-#endif
-#ifndef S2_ABL_NOBITS
-#define S2_ABL_NOBITS 0      // masked-input form: no keep-bit DMA (the masking reads whatever the slots hold)
-#endif
-#ifndef S2_ABL_NORMW
-#define S2_ABL_NORMW 0       // masked-input form: the pieces are not masked in LDS
-#endif
-#ifndef S2_MASK_PHASE
-#define S2_MASK_PHASE 0      // masked-input form: phase of a K-step whose LOAD part masks the pieces that are due
-#endif
-#ifndef S2_BITS_GROUP
-#define S2_BITS_GROUP 0      // 1: ONE keep-bit DMA serves four pieces (the four lanes of a cell fetch the dwords of four different pieces): three
-                             // bit DMAs per chunk instead of ten.  Measured SLOWER (2.21 -> 2.37 ms on the headline's pair launch): the per-lane
-                             // choice among four piece offsets costs 7 VGPRs the kernel does not have, and two of the spilled values are
-                             // reloaded inside the main loop (a scratch load in front of a DMA is a vmcnt wait for everything in flight)
-#endif
-#ifndef S2_MASK_LUT
-#define S2_MASK_LUT 1        // 1: the four dword masks of a keep byte come from a 256-entry table in LDS (one ds_read_b128) instead of 16 vector
-                             // instructions; with S2_MASK_ATOMIC the pair launch of the headline 2.245 -> 2.18 ms (r3_lazy_site.log)
-#endif
-#ifndef S2_MASK_ATOMIC
-#define S2_MASK_ATOMIC 1     // 1: the dropped elements are cleared by two ds_and_b64 (the LDS unit reads, ANDs and writes) instead of
-                             // ds_read_b128 / v_and / ds_write_b128 through the registers
-#endif
-#ifndef S2_ABL_NOEPI
-#define S2_ABL_NOEPI 0       // no epilogue at all (one accumulator element per lane is stored so the MFMAs stay live)
-#endif
+// The MFMA rows of a wave's four channel tiles are a permutation of its 64 channels (conv3x3_pwp's: row r of tile i = channel
+// 32 (i >> 1) + 8 (r >> 2) + 4 (i & 1) + (r & 3)), so a lane holds two runs of 8 consecutive channels per pixel and the epilogue stores them
+// straight from the registers — no trip through LDS, no barrier.
+// Output stores that bypass the XCD's L2 (sc1, an inline-asm store hipcc does not model) cut rocprofv3 FETCH_SIZE by 12 % at unchanged wall time and were not kept
+// (profiles/experiments/r3_s2_sc1_stores.log).
 
 // TW = OUTPUT map size (TW x TW; the input map is 2 TW x 2 TW): 16, 8 or 4.
-// NST = weight stages: the weights of K-step T + NST - 1 are issued in step T.  vmcnt retires in order, so waiting for the NEXT
+// NST = 3 weight stages: the weights of K-step T + NST - 1 are issued in step T.  vmcnt retires in order, so waiting for the NEXT
 // step's weights also waits for every patch piece issued before them: a piece issued in step s must have landed by the end of
-// step s + NST - 1 whether its plane is needed by then or not.  With 3 stages that is 2 K-steps (~1.4 us) for an HBM round
-// trip.  Timing probes (profiles/experiments/r3_s2_ablation.log) showed the 32x32 / 16x16 classes 15-20 % faster WITHOUT the
-// patch DMA, which suggested that window; a fourth stage (one more K-step, built and kept behind -DS2_NST_BIG=4) measured
-// 1-2 % SLOWER on all three classes (same-box A/B, r3_s2_stages_phase.log): the window is not what they wait for.
+// step s + NST - 1 whether its plane is needed by then or not: 2 K-steps (~1.4 us) for an HBM round trip.  A fourth stage (one more
+// K-step) measured 1-2 % slower on all three classes (profiles/experiments/r3_s2_stages_phase.log): the window is not what they wait for.
 // MSK = masked input (ConvArgs::in_bits): the patch is DMA'd from the deterministic (pre-scaled) tensor, a piece's keep bits ride
 // along as one more DMA (a dword per lane into a 2 KB slot), and the thread that issued a piece clears the dropped elements of
 // ITS 16 bytes in LDS one K-step after the piece has landed — a piece is readable one step later than without the mask.
 // CT_ = channels per tile: 256, or 128 (round 4, 16x16 output maps only: ResNet-50's Cout = 128 stride-2 convs).  With 128 the two wave groups
 // split the tile's PIXELS (output rows 0-7 / 8-15) instead of its channels: a wave tile is 64 ch x 64 px (4 x 4 MFMA tiles), both groups read the
 // same 8 KB weight stage, a K-step's two phases take two pixel blocks each (8 MFMAs per phase instead of 16; the barrier schedule, the patch and
-// its refill windows are the same), and a group's 128 ch x 128 px are ONE round of the epilogue.
-template <int TW, int NST_ = (TW == 4 ? 3 : S2_NST_BIG), bool MSK_ = false, int CT_ = 256>
+// its refill windows are the same).
+template <int TW, bool MSK_ = false, int CT_ = 256>
 struct S2Geom {
     static_assert(CT_ == 256 || (CT_ == 128 && TW == 16), "128-channel tiles: the 16x16 output maps");
-    static constexpr int NST = NST_;
+    static constexpr int NST = 3;
     static constexpr bool MSK = MSK_;
     static constexpr int LAND = NST + (MSK ? 1 : 0);              // a piece issued in step s is readable from step s + LAND on
-    static_assert(NST == 3 || NST == 4, "weight stages");
     static constexpr int BN_MAX = TW == 4 ? 1024 : 512;           // channels of the launch (both convs of a pair): the BN table
     static constexpr int CT = CT_, PX = 256, IMGS = PX / (TW * TW);
     static constexpr int WPI = CT / 128;                          // weight DMA instructions per thread and K-step
@@ -200,11 +131,11 @@ struct S2Geom {
     static constexpr int PRO = count_hi_le(1);                    // ... planes A / B only: loaded ahead (prologue, next chunk)
     static constexpr int NB = PRO - NA;
     static constexpr int NOWN = NPT - PRO;                        // pieces with C / D cells: loaded in their own chunk's period
-    // K-step (0..8 of a chunk's period) in which piece k is issued.  A pieces (next chunk): steps 5, 6 (step 5 with four
-    // stages: they must have landed NST - 1 steps later, before step 0); B pieces (next chunk): steps 7, 8; own-period pieces:
+    // K-step (0..8 of a chunk's period) in which piece k is issued.  A pieces (next chunk): steps 5, 6 (masked input: all in
+    // step 5: they must be readable LAND = 4 steps later, in step 0); B pieces (next chunk): steps 7, 8; own-period pieces:
     // one per step from step 0.
     __host__ __device__ static constexpr int pstep(int k) {
-        return k < NA ? (NST == 3 && !MSK ? 5 + (2 * k) / NA : 5) : (k < PRO ? 7 + (2 * (k - NA)) / NB : k - PRO);
+        return k < NA ? (!MSK ? 5 + (2 * k) / NA : 5) : (k < PRO ? 7 + (2 * (k - NA)) / NB : k - PRO);
     }
     __host__ __device__ static constexpr int pieces_at(int s) { int n = 0; for (int k = 0; k < NPT; ++k) n += pstep(k) == s ? 1 : 0; return n; }
     // Validity of that schedule (see the hazard notes in the kernel): a plane last read in step L may be overwritten from
@@ -226,15 +157,9 @@ struct S2Geom {
     static_assert(schedule_ok(), "patch refill schedule violates a WAR / RAW window");
     // DMA instructions of step s of a chunk (`last`: the tile's last chunk — no next-chunk pieces, no weights beyond the tile)
     __host__ __device__ static constexpr bool w_issued(int s, bool last) { return s + NST - 1 <= 8 || !last; }
-    // keep-bit DMAs (MSK).  Grouped: pieces 0-3 (A, A, A, B: next chunk) at step 5, pieces 4 (B, next chunk) + 9 (own) at step 4, pieces 5-8
-    // (own) at step 0 — each with its group's earliest piece, so a piece's bits land no later than the piece.
-    __host__ __device__ static constexpr int grp(int k) { return k < 4 ? 0 : (k == 4 || k == 9 ? 1 : 2); }
-    __host__ __device__ static constexpr int gidx(int k) { return k < 4 ? k : (k == 4 ? 0 : (k == 9 ? 1 : k - 5)); }
-    __host__ __device__ static constexpr int bits_at(int s, bool last) {
-        if (!MSK || S2_ABL_NOBITS) return 0;
-        if (!S2_BITS_GROUP) return (s <= 4 || !last) ? pieces_at(s) : 0;
-        return (s == 0 || s == 4) ? 1 : ((s == 5 && !last) ? 1 : 0);
-    }
+    // keep-bit DMAs (MSK): one per piece, issued with it.  (One DMA for the bits of four pieces — three per chunk instead of ten — measured
+    // slower, 2.21 -> 2.37 ms on the headline's pair launch: profiles/HISTORY.md.)
+    __host__ __device__ static constexpr int bits_at(int s, bool last) { return MSK && (s <= 4 || !last) ? pieces_at(s) : 0; }
     __host__ __device__ static constexpr int p_issued(int s, bool last) { return ((s <= 4 || !last) ? pieces_at(s) : 0) + bits_at(s, last); }
     // What may still be in flight when step S ends: everything issued BEHIND the weights of step S + 1 (which were issued first
     // thing in step S - (NST - 2)): that step's pieces, then weights + pieces of the steps up to S.  (Steps before 0 are the
@@ -253,8 +178,8 @@ struct S2Geom {
     }
     static constexpr int WST = CT * 64;                           // one weight stage (32-deep K-step)
     static constexpr int PIECE = 512 * 16;
-    static constexpr int P_OFF = (NST - 1) * WST;                 // [W0 | W1 (| W2) | pieces ... | (pad) | last stage | BN]
-    static constexpr int E_OFF = P_OFF + PRO * PIECE;             // epilogue staging: the own-period pieces, padding, the last stage
+    static constexpr int P_OFF = (NST - 1) * WST;                 // [W0 | W1 | pieces ... | (pad) | last stage | BN]
+    static constexpr int E_OFF = P_OFF + PRO * PIECE;             // pooled-exchange staging: the own-period pieces, padding, the last stage
     static constexpr int E_BYTES = 65536;
     static constexpr int END_PIECES = P_OFF + NPT * PIECE;
     static constexpr int WL_OFF = (END_PIECES + WST > E_OFF + E_BYTES ? END_PIECES : E_OFF + E_BYTES - WST);
@@ -268,11 +193,13 @@ struct S2Geom {
             if (pstep(k) + 3 == S || pstep(k) + 3 == S + 9) return k;
         return -1;
     }
-    static constexpr int NSLOT = MSK ? (S2_BITS_GROUP ? 3 : 6) : 0;
-    __host__ __device__ static constexpr int slot(int k) { return S2_BITS_GROUP ? grp(k) : (k >= PRO ? k - PRO : (k < NA ? (k < 2 ? k : 5) : 2 + (k - NA))); }
+    static constexpr int NSLOT = MSK ? 6 : 0;
+    __host__ __device__ static constexpr int slot(int k) { return k >= PRO ? k - PRO : (k < NA ? (k < 2 ? k : 5) : 2 + (k - NA)); }
     static_assert(!MSK || (NA == 3 && NB == 2 && NOWN == 5 && NPT == 10), "keep-bit slot plan");
+    // MSK: the four dword masks of a keep byte come from a 256-entry table (one ds_read_b128 instead of 16 vector instructions; with the
+    // ds_and_b64 clear the pair launch of the headline 2.245 -> 2.18 ms, profiles/experiments/r3_lazy_site.log)
     static constexpr int LUT_OFF = BITS_OFF + NSLOT * 2048;
-    static constexpr int LDS_BYTES = LUT_OFF + (MSK && S2_MASK_LUT ? 4096 : 0);
+    static constexpr int LDS_BYTES = LUT_OFF + (MSK ? 4096 : 0);
     static_assert(BN_OFF - E_OFF >= E_BYTES, "epilogue staging area");
     static_assert(LDS_BYTES <= 160 * 1024, "LDS");
     __host__ __device__ static constexpr int wstage_off(int st) { return st == NST - 1 ? WL_OFF : st * WST; }
@@ -342,12 +269,14 @@ static_assert(S2Skip::cells_ok(), "pad-skip: a tile is dead exactly when it read
 // (the kernel's body: SKIP = the pad-skip form; the two entry points are below)
 template <int TW, bool BF, bool IMAP, bool MSK, int CT_, bool SKIP>
 __device__ __forceinline__ void conv3x3_s2_body(const ConvArgs& a, int n_tiles) {
-    using G = S2Geom<TW, (TW == 4 ? 3 : S2_NST_BIG), MSK, CT_>;
+    using G = S2Geom<TW, MSK, CT_>;
     static_assert(!MSK || (TW == 16 && !IMAP), "masked input: one image per tile, the ordinary form");
-    static_assert(!SKIP || (TW == 4 && CT_ == 256 && !IMAP && !MSK && S2_DIRECT && !S2_WSPLIT && !S2_RELAX0), "pad-skip: the 8x8 -> 4x4 class without a row table");
+    static_assert(!SKIP || (TW == 4 && CT_ == 256 && !IMAP && !MSK), "pad-skip: the 8x8 -> 4x4 class without a row table");
     constexpr int CT = G::CT, IMGS = G::IMGS, NPT = G::NPT, PRO = G::PRO, NST = G::NST;
     constexpr bool HALF = CT == 128;
     constexpr int TI = 4, TP = HALF ? 4 : 8, JB = TP / 2;        // JB pixel blocks per phase of a K-step
+    constexpr int PIECE_PHASE = 1;     // phase of a K-step whose LOAD part issues the step's patch pieces (phase 0 carries 8 fragment reads and
+                                       // the 2 weight DMAs, phase 1 only 4 reads)
     typedef float accv __attribute__((ext_vector_type(4)));
     __shared__ __attribute__((aligned(16))) char smem[G::LDS_BYTES];
     char* const pbuf = smem + G::P_OFF;
@@ -375,7 +304,7 @@ __device__ __forceinline__ void conv3x3_s2_body(const ConvArgs& a, int n_tiles) 
         bn_scale[c] = (sp ? sp[cc] : 1.f) * a.out_mul;
         bn_bias[c] = bp ? bp[cc] : 0.f;
     }
-    if constexpr (MSK && S2_MASK_LUT) {
+    if constexpr (MSK) {
         if (tid < 256) {
             typedef unsigned int u32x4_l __attribute__((ext_vector_type(4)));
             u32x4_l m;
@@ -388,9 +317,10 @@ __device__ __forceinline__ void conv3x3_s2_body(const ConvArgs& a, int n_tiles) 
 
     // ---- per-lane fragment geometry (tile-independent) ----
     // weights: row (g*128 + wc*64 + l16 + 16 i), chunk kq at position kq ^ 2 ((row >> 2) & 1) = kq ^ 2 ((l16 >> 2) & 1)
-    const int a_off = ((HALF ? 0 : g * 128) + wc * 64 + (S2_DIRECT ? 8 * (l16 >> 2) + (l16 & 3) : l16)) * 64 + ((kq ^ (((l16 >> 2) & 1) << 1)) << 4);
+    // (the parentheses around the lane's row are conv3x3_pw's, where they shape the instruction order: keep)
+    const int a_off = ((HALF ? 0 : g * 128) + wc * 64 + (8 * (l16 >> 2) + (l16 & 3))) * 64 + ((kq ^ (((l16 >> 2) & 1) << 1)) << 4);
     // byte offset of channel tile i's row of this lane relative to a_off
-#define A_TILE(I) (S2_DIRECT ? (32 * ((I) >> 1) + 4 * ((I) & 1)) * 64 : (I) * 16 * 64)
+#define A_TILE(I) ((32 * ((I) >> 1) + 4 * ((I) & 1)) * 64)
     // pixels: lane (by, bx) = (l16 >> 2, l16 & 3) of each 4 x 4 block; plane row parity of the cell = (by + dy) & 1
     const int by = l16 >> 2, bx = l16 & 3;
     const int pbase = HALF ? (g * 2 + wp) * 64 : wp * 128;        // first tile pixel of this wave
@@ -443,8 +373,8 @@ __device__ __forceinline__ void conv3x3_s2_body(const ConvArgs& a, int n_tiles) 
     int tsel = 0;
     // weights: piece q = tid + 512 i -> row (tid >> 2) + 128 i, position tid & 3 holds chunk (tid & 3) ^ 2 ((row >> 2) & 1);
     // one descriptor per 128-row half of the channel tile (a pair's second conv has its own weight tensor)
-    // (S2_DIRECT: a fragment's 16 lanes read rows 8 a + b + const: the chunk position alternates with row >> 3 instead of row >> 2)
-    const unsigned woff = 2u * ((unsigned)(tid >> 2) * Ktot + (((tid & 3) ^ (((tid >> (S2_DIRECT ? 5 : 4)) & 1) << 1)) << 3));
+    // (the MFMA row permutation: a fragment's 16 lanes read rows 8 a + b + const, so the chunk position alternates with row >> 3 instead of row >> 2)
+    const unsigned woff = 2u * ((unsigned)(tid >> 2) * Ktot + (((tid & 3) ^ (((tid >> 5) & 1) << 1)) << 3));
     const unsigned wbytes = 2u * 128u * Ktot;
     // element offset of channel chunk C0 (a multiple of 32) = C0 * cmul: 1 in NHWC, H * W in the planar layout (one 32-channel plane per chunk)
     const unsigned cmul = (MSK && a.lazy_planar) ? (unsigned)(a.H * a.W) : 1u;
@@ -456,16 +386,11 @@ __device__ __forceinline__ void conv3x3_s2_body(const ConvArgs& a, int n_tiles) 
     // offsets stay loop-invariant, one VGPR each, and nothing is added per DMA)
 #define BLDS16(RSRC, VOFF, SOFF, LDSPTR) \
     __builtin_amdgcn_raw_ptr_buffer_load_lds((RSRC), (__attribute__((address_space(3))) void*)(LDSPTR), 16, (VOFF), (SOFF), 0, 0)
-#define ISSUE_W_HALF(KOFF, ST, I)                                                                            \
-    {                                                                                                        \
-        const unsigned so_ = __builtin_amdgcn_readfirstlane(2u * (unsigned)(KOFF));                          \
-        if ((I) == 0) BLDS16(rs_w0, woff, so_, smem + G::wstage_off(ST) + (0 * 512 + wave * 64) * 16);       \
-        else BLDS16(rs_w1, woff, so_, smem + G::wstage_off(ST) + (1 * 512 + wave * 64) * 16);                \
-    }
 #define ISSUE_W(KOFF, ST)                                                                                    \
     {                                                                                                        \
-        ISSUE_W_HALF(KOFF, ST, 0);                                                                           \
-        if (!HALF) ISSUE_W_HALF(KOFF, ST, 1);                                                                \
+        const unsigned so_ = __builtin_amdgcn_readfirstlane(2u * (unsigned)(KOFF));                          \
+        BLDS16(rs_w0, woff, so_, smem + G::wstage_off(ST) + (0 * 512 + wave * 64) * 16);                     \
+        if (!HALF) BLDS16(rs_w1, woff, so_, smem + G::wstage_off(ST) + (1 * 512 + wave * 64) * 16);          \
     }
 #define ISSUE_P(K, C0)                                                                                       \
     {                                                                                                        \
@@ -474,8 +399,8 @@ __device__ __forceinline__ void conv3x3_s2_body(const ConvArgs& a, int n_tiles) 
             const int row_ = row_tabs[tsel * 16 + ((pre[K] >> 24) & 15)];                                    \
             o_ = (pre[K] == OOB || row_ < 0) ? OOB : 2u * ((unsigned)row_ * HWC + (pre[K] & 0xffffffu));     \
         }                                                                                                    \
-        if (!S2_ABL_NOPATCH) BLDS16(rs_in, o_, __builtin_amdgcn_readfirstlane(2u * (unsigned)(C0) * cmul), pbuf + ((K) * 512 + wave * 64) * 16); \
-        if constexpr (MSK && !S2_ABL_NOBITS && !S2_BITS_GROUP) {                                             \
+        BLDS16(rs_in, o_, __builtin_amdgcn_readfirstlane(2u * (unsigned)(C0) * cmul), pbuf + ((K) * 512 + wave * 64) * 16); \
+        if constexpr (MSK) {                                                                                 \
             /* the cell's 32 keep bits of this chunk (the dword that holds this piece's byte); beyond the descriptor: zeros */ \
             /* (derived from pre[K] at every issue: as loop invariants the ten offsets are spilled, and a scratch reload in */ \
             /*  front of a DMA is a vmcnt wait for everything in flight)                                                    */ \
@@ -485,59 +410,32 @@ __device__ __forceinline__ void conv3x3_s2_body(const ConvArgs& a, int n_tiles) 
                                                      4, (bo_ >> 4) & ~3u, __builtin_amdgcn_readfirstlane(((unsigned)(C0) * cmul) >> 3), 0, 0); \
         }                                                                                                    \
     }
-    // Grouped keep-bit DMA: lane (cell, pos) fetches the dword of piece PA / PB / PC / PD (pos 0..3; -1: none) of ITS cell row; CB = channel
-    // offset of the group's chunk (bytes of bits: / 8), ADD0 = extra bytes for pos 0 (the one piece of the mixed group that carries the
-    // next chunk).  The four lanes of a cell are lanes of one wave: the wave's vmcnt wait covers what its neighbours fetched.
-#define ISSUE_BITS(GRP, PA, PB, PC, PD, CB, ADD0)                                                            \
-    if constexpr (MSK && !S2_ABL_NOBITS && S2_BITS_GROUP) {                                                  \
-        int p4_ = tid & 3;                                                                                   \
-        asm volatile("" : "+v"(p4_));                                                                        \
-        unsigned bo_ = p4_ == 0 ? pre[PA] : (p4_ == 1 ? pre[PB] : ((PC) >= 0 ? (p4_ == 2 ? pre[(PC) < 0 ? 0 : (PC)] : pre[(PD) < 0 ? 0 : (PD)]) : OOB)); \
-        bo_ = ((bo_ >> 4) & ~3u) + (p4_ == 0 ? (unsigned)(ADD0) : 0u);                                       \
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_bits, (__attribute__((address_space(3))) void*)(smem + G::BITS_OFF + (GRP) * 2048 + wave * 256), \
-                                                 4, bo_, __builtin_amdgcn_readfirstlane(((unsigned)(CB) * cmul) >> 3), 0, 0); \
-    }
     // The thread that issued piece K clears the dropped elements of its 16 bytes: byte (logical chunk) of the slot's dword -> four
     // dword masks.  Own DMA only: the thread's counted vmcnt wait is all it needs; the barriers of the step publish the result.
     typedef unsigned int u32x4_m __attribute__((ext_vector_type(4)));
-#define MASK_LOAD(K, W, V)                                                                                   \
-    if (!S2_ABL_NORMW) {                                                                                     \
-        int t4_ = S2_BITS_GROUP ? ((tid & ~3) + G::gidx(K)) * 4 : tid * 4;                                   \
+#define MASK_LOAD(K, W)                                                                                      \
+    {                                                                                                        \
+        int t4_ = tid * 4;                                                                                   \
         asm volatile("" : "+v"(t4_));                                                                        \
         W = *(const unsigned*)(smem + G::BITS_OFF + G::slot(K) * 2048 + t4_);                                /* the dword of this piece's cell */ \
-        if (!S2_MASK_ATOMIC) V = *(const u32x4_m*)(pbuf + ((K) * 512 + tid) * 16);                           \
     }
-#define MASK_STORE(K, W, V)                                                                                  \
-    if (!S2_ABL_NORMW) {                                                                                     \
+    // (two ds_and_b64: the LDS unit reads, ANDs and writes — no round trip through the registers)
+#define MASK_STORE(K, W)                                                                                     \
+    {                                                                                                        \
         unsigned sh_ = pre[K];                                                                               \
         asm volatile("" : "+v"(sh_));                                                                        \
         const int b_ = (int)((W) >> ((sh_ >> 1) & 24u));                                                     \
-        u32x4_m v_ = V, m_;                                                                                  \
-        if (S2_MASK_LUT) {                                                                                   \
-            m_ = *(const u32x4_m*)(smem + G::LUT_OFF + ((b_ & 0xff) << 4));                                  \
-            v_ &= m_;                                                                                        \
-        } else {                                                                                             \
-            _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) {                                               \
-                const unsigned lo_ = (unsigned)__builtin_amdgcn_sbfe(b_, 2 * i_, 1), hi_ = (unsigned)__builtin_amdgcn_sbfe(b_, 2 * i_ + 1, 1); \
-                m_[i_] = (lo_ & 0xffffu) | (hi_ & 0xffff0000u);                                              \
-                v_[i_] &= m_[i_];                                                                            \
-            }                                                                                                \
-        }                                                                                                    \
-        if (S2_MASK_ATOMIC) {                                                                                \
-            typedef __attribute__((address_space(3))) unsigned long long lds_u64;                            \
-            lds_u64* const q_ = (lds_u64*)(pbuf + ((K) * 512 + tid) * 16);                                   \
-            __atomic_fetch_and(q_, ((unsigned long long)m_[1] << 32) | m_[0], __ATOMIC_RELAXED);             \
-            __atomic_fetch_and(q_ + 1, ((unsigned long long)m_[3] << 32) | m_[2], __ATOMIC_RELAXED);         \
-        } else {                                                                                             \
-            *(u32x4_m*)(pbuf + ((K) * 512 + tid) * 16) = v_;                                                 \
-        }                                                                                                    \
+        const u32x4_m m_ = *(const u32x4_m*)(smem + G::LUT_OFF + ((b_ & 0xff) << 4));                        \
+        typedef __attribute__((address_space(3))) unsigned long long lds_u64;                                \
+        lds_u64* const q_ = (lds_u64*)(pbuf + ((K) * 512 + tid) * 16);                                       \
+        __atomic_fetch_and(q_, ((unsigned long long)m_[1] << 32) | m_[0], __ATOMIC_RELAXED);                 \
+        __atomic_fetch_and(q_ + 1, ((unsigned long long)m_[3] << 32) | m_[2], __ATOMIC_RELAXED);             \
     }
 #define MASK_P(K)                                                                                            \
     {                                                                                                        \
         unsigned mw_;                                                                                        \
-        u32x4_m mv_;                                                                                         \
-        MASK_LOAD(K, mw_, mv_);                                                                              \
-        MASK_STORE(K, mw_, mv_);                                                                             \
+        MASK_LOAD(K, mw_);                                                                                   \
+        MASK_STORE(K, mw_);                                                                                  \
     }
     // piece whose masking is due in step S of a period (issued three steps earlier), -1: none.  (Step 8: the A pieces, all three
     // issued in step 5: the first one takes the early-load slot, the others follow serially.)
@@ -578,10 +476,7 @@ __device__ __forceinline__ void conv3x3_s2_body(const ConvArgs& a, int n_tiles) 
             __syncthreads();   /* (drains W(0) too: the dynamic-exit path only) */                           \
         }                                                                                                    \
         _Pragma("unroll") for (int k = 0; k < PRO; ++k) ISSUE_P(k, 0);                                       \
-        ISSUE_BITS(0, 0, 1, 2, 3, 0, 0);                                                                     \
-        ISSUE_BITS(1, 4, 9, -1, -1, 0, 0);                                                                   \
         ISSUE_W(s2_tap(1) * a.Cin, 1);                                                                       \
-        if constexpr (NST == 4) ISSUE_W(s2_tap(2) * a.Cin, 2);                                               \
         __builtin_amdgcn_sched_barrier(0);                                                                   \
     }
 
@@ -598,13 +493,11 @@ __device__ __forceinline__ void conv3x3_s2_body(const ConvArgs& a, int n_tiles) 
     // issued this step) and the patch pieces issued this step and the step before; everything older — in particular the next
     // step's weights and every piece issued two or more steps ago — has landed.  In the last chunk no next-chunk piece (steps
     // 5-8) and no weights beyond the tile's last step (steps 7, 8) are issued.
-    // (Step 0 of a tile that follows a full tile, round 4: everything step 1 reads — weight stage 1, the A / B pieces — was issued BEFORE the
-    //  previous tile's 16 output stores and has landed at the tile's start; only this step's own DMAs are younger than the stores, which may
-    //  therefore stay in flight one step longer.)
+    // (Letting the previous tile's output stores stay in flight through step 0 of the next tile was built and measured neutral, +-0.5 %, in
+    //  round 4: the tile-start wait below drains them.)
 #define END_OF_STEP_WAIT(S)                                                                                    \
     {                                                                                                          \
-        if (S2_RELAX0 && (S) == 0 && chunk == 0 && stores16 && !IMAP && !S2_DRAIN_STORES) { WAIT_VM(NSTORES + G::wait_n(0, false)); } \
-        else if (!last) { WAIT_VM(G::wait_n(S, false)); }                                                      \
+        if (!last) { WAIT_VM(G::wait_n(S, false)); }                                                           \
         else { WAIT_VM(G::wait_n(S, true)); }                                                                  \
     }
     // One K-step = step S of the chunk's period (one tap x this chunk's 32 channels).  Two phases (LOAD part, barrier, MFMA part,
@@ -616,9 +509,8 @@ __device__ __forceinline__ void conv3x3_s2_body(const ConvArgs& a, int n_tiles) 
 #define S2_STEP(S)                                                                                             \
     {                                                                                                          \
         constexpr int pl_ = s2_plane(S), dy_ = s2_dy(S), dx_ = s2_dx(S), sn_ = (S) + NST - 1;                  \
-        /* stage read by this step / filled for step S + NST - 1: compile-time with three stages (9 steps per chunk), */ \
-        /* (chunk + S) & 3 with four (9 = 1 mod 4) */                                                          \
-        const int st_r_ = NST == 3 ? (S) % 3 : ((chunk + (S)) & 3), st_w_ = NST == 3 ? ((S) + 2) % 3 : ((chunk + (S) + 3) & 3); \
+        /* stage read by this step / filled for step S + NST - 1: compile-time (9 steps per chunk: the index repeats) */ \
+        constexpr int st_r_ = (S) % 3, st_w_ = ((S) + 2) % 3;                                                  \
         const char* ws_ = smem + G::wstage_off(st_r_) + a_off;                                                 \
         const char* pb_ = smem + (dy_ * G::cols(pl_) + dx_) * 64 + (boff[pl_] ^ (dy_ << 5));                   \
         /* MSK: pieces issued three steps ago have landed (this thread's wait at the end of the previous step).  The first due */ \
@@ -628,78 +520,39 @@ __device__ __forceinline__ void conv3x3_s2_body(const ConvArgs& a, int n_tiles) 
         constexpr int due0_ = G::first_due(S);                                                                 \
         const bool due_on_ = MSK && due0_ >= 0 && (due0_ >= PRO ? true : (G::pstep(due0_ < 0 ? 0 : due0_) + 3 == (S) ? !last : chunk > 0)); \
         unsigned mw0_ = 0;                                                                                     \
-        u32x4_m mv0_ = {0u, 0u, 0u, 0u};                                                                       \
         _Pragma("unroll") for (int kk = 0; kk < 2; ++kk) {                                                     \
-            if constexpr (MSK && due0_ >= 0) { if (kk == S2_MASK_PHASE && due_on_) { MASK_LOAD(due0_ < 0 ? 0 : due0_, mw0_, mv0_); } } \
+            if constexpr (MSK && due0_ >= 0) { if (kk == 0 && due_on_) { MASK_LOAD(due0_ < 0 ? 0 : due0_, mw0_); } } \
             if (kk == 0) {                                                                                     \
                 _Pragma("unroll") for (int i = 0; i < TI; ++i) af[i] = *(const half8*)(ws_ + A_TILE(i));       \
             }                                                                                                  \
             _Pragma("unroll") for (int j = 0; j < JB; ++j)                                                     \
-                if (!S2_ABL_HALFREADS || !(j & 1)) bf[j] = *(const half8*)(pb_ + G::cell_delta(pl_, JB * kk + j) * 64); \
-                else bf[j] = bf[j - 1];                                                                        \
+                bf[j] = *(const half8*)(pb_ + G::cell_delta(pl_, JB * kk + j) * 64);                           \
             if constexpr (MSK && due0_ >= 0) {                                                                 \
-                if (kk == S2_MASK_PHASE) {                                                                     \
-                    if (due_on_) { MASK_STORE(due0_ < 0 ? 0 : due0_, mw0_, mv0_); }                            \
+                if (kk == 0) {                                                                                 \
+                    if (due_on_) { MASK_STORE(due0_ < 0 ? 0 : due0_, mw0_); }                                  \
                     _Pragma("unroll") for (int k = 0; k < NPT; ++k)                                            \
                         if (k != due0_ && MASK_DUE(S, k)) { if (due_on_) { MASK_P(k); } }                      \
-                    /* (phase 1: the masked piece may be read in the next interval — the write has to be complete at the barrier) */ \
-                    if (S2_MASK_PHASE == 1 && due_on_) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      \
                 }                                                                                              \
             }                                                                                                  \
-            if (kk == 0 || S2_WSPLIT) {                                                                        \
-                /* weights of step S + NST - 1: of this chunk, or of the first steps of the next one (S2_WSPLIT: the two */ \
-                /* DMA instructions of a wave in the two phases of the step) */                                \
-                if (!S2_WSPLIT) {                                                                              \
-                    if (sn_ <= 8) { ISSUE_W(s2_tap(sn_ <= 8 ? sn_ : 0) * a.Cin + c32, st_w_); }                \
-                    else if (!last) { ISSUE_W(s2_tap(sn_ > 8 ? sn_ - 9 : 0) * a.Cin + c32 + 32, st_w_); }      \
-                } else {                                                                                       \
-                    if (sn_ <= 8) { ISSUE_W_HALF(s2_tap(sn_ <= 8 ? sn_ : 0) * a.Cin + c32, st_w_, kk); }       \
-                    else if (!last) { ISSUE_W_HALF(s2_tap(sn_ > 8 ? sn_ - 9 : 0) * a.Cin + c32 + 32, st_w_, kk); } \
-                }                                                                                              \
+            if (kk == 0) {                                                                                     \
+                /* weights of step S + NST - 1: of this chunk, or of the first steps of the next one */        \
+                if (sn_ <= 8) { ISSUE_W(s2_tap(sn_ <= 8 ? sn_ : 0) * a.Cin + c32, st_w_); }                    \
+                else if (!last) { ISSUE_W(s2_tap(sn_ > 8 ? sn_ - 9 : 0) * a.Cin + c32 + 32, st_w_); }          \
             }                                                                                                  \
-            if (kk == S2_PIECE_PHASE) {                                                                        \
+            if (kk == PIECE_PHASE) {                                                                           \
                 _Pragma("unroll") for (int k = 0; k < NPT; ++k)                                                \
                     if (G::pstep(k) == (S)) {                                                                  \
                         if (k >= PRO) { ISSUE_P(k, c32); }                                                     \
                         else if (!last) { ISSUE_P(k, c32 + 32); }                                              \
                     }                                                                                          \
-                if ((S) == 0) { ISSUE_BITS(2, 5, 6, 7, 8, c32, 0); }                                           \
-                if ((S) == 4) { ISSUE_BITS(1, 4, 9, -1, -1, c32, 4); }                                         \
-                if ((S) == 5) { if (!last) { ISSUE_BITS(0, 0, 1, 2, 3, c32 + 32, 0); } }                       \
             }                                                                                                  \
-            /* (S2_MASK_PHASE 2: the masking of phase 0's MFMA part wrote LDS behind nothing but this phase's four fragment */ \
-            /*  reads — LDS operations of a wave complete in order: with at most four outstanding the write is done) */ \
-            if (MSK && S2_MASK_PHASE == 2 && kk == 1) asm volatile("s_waitcnt lgkmcnt(4)" ::: "memory");       \
             if (kk == 1 && g == 1) END_OF_STEP_WAIT(S);        /* interval 4T+3, group 1: LOAD part */         \
             RAW_BARRIER();                                                                                     \
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                 \
             __builtin_amdgcn_s_setprio(1);                                                                     \
-            if constexpr (MSK && S2_MASK_PHASE == 2 && due0_ >= 0) {                                           \
-                if (kk == 0) {                                                                                 \
-                    /* the piece's read-modify-write BETWEEN the MFMAs: its LDS round trip and its 20 vector instructions */ \
-                    /* ride in the matrix pipe's shadow instead of stretching a LOAD part */                    \
-                    _Pragma("unroll") for (int j = 0; j < 4; ++j) acc[0][j] = mfma_16x16x32<BF>(af[0], bf[j], acc[0][j]); \
-                    __builtin_amdgcn_sched_barrier(0);                                                         \
-                    if (due_on_) { MASK_LOAD(due0_ < 0 ? 0 : due0_, mw0_, mv0_); }                             \
-                    __builtin_amdgcn_sched_barrier(0);                                                         \
-                    _Pragma("unroll") for (int i = 1; i < 3; ++i)                                              \
-                        _Pragma("unroll") for (int j = 0; j < 4; ++j) acc[i][j] = mfma_16x16x32<BF>(af[i], bf[j], acc[i][j]); \
-                    __builtin_amdgcn_sched_barrier(0);                                                         \
-                    if (due_on_) { MASK_STORE(due0_ < 0 ? 0 : due0_, mw0_, mv0_); }                            \
-                    _Pragma("unroll") for (int k = 0; k < NPT; ++k)                                            \
-                        if (k != due0_ && MASK_DUE(S, k)) { if (due_on_) { MASK_P(k); } }                      \
-                    __builtin_amdgcn_sched_barrier(0);                                                         \
-                    _Pragma("unroll") for (int j = 0; j < 4; ++j) acc[3][j] = mfma_16x16x32<BF>(af[3], bf[j], acc[3][j]); \
-                } else {                                                                                       \
-                    _Pragma("unroll") for (int i = 0; i < TI; ++i)                                             \
-                        _Pragma("unroll") for (int j = 0; j < JB; ++j)                                         \
-                            acc[i][JB * kk + j] = mfma_16x16x32<BF>(af[i], bf[j], acc[i][JB * kk + j]);        \
-                }                                                                                              \
-            } else {                                                                                           \
-                _Pragma("unroll") for (int i = 0; i < TI; ++i)                                                 \
-                    _Pragma("unroll") for (int j = 0; j < JB; ++j)                                             \
-                        acc[i][JB * kk + j] = mfma_16x16x32<BF>(af[i], bf[j], acc[i][JB * kk + j]);            \
-            }                                                                                                  \
+            _Pragma("unroll") for (int i = 0; i < TI; ++i)                                                     \
+                _Pragma("unroll") for (int j = 0; j < JB; ++j)                                                 \
+                    acc[i][JB * kk + j] = mfma_16x16x32<BF>(af[i], bf[j], acc[i][JB * kk + j]);                \
             __builtin_amdgcn_s_setprio(0);                                                                     \
             if (kk == 1 && g == 0) END_OF_STEP_WAIT(S);        /* interval 4T+3, group 0: MFMA part */         \
             RAW_BARRIER();                                                                                     \
@@ -728,7 +581,7 @@ __device__ __forceinline__ void conv3x3_s2_body(const ConvArgs& a, int n_tiles) 
                 if (sn_ <= 8) { ISSUE_W(s2_tap(sn_ <= 8 ? sn_ : 0) * a.Cin + c32, st_w_); }                    \
                 else if (!last) { ISSUE_W(s2_tap(sn_ > 8 ? sn_ - 9 : 0) * a.Cin + c32 + 32, st_w_); }          \
             }                                                                                                  \
-            if (kk == S2_PIECE_PHASE) {                                                                        \
+            if (kk == PIECE_PHASE) {                                                                           \
                 _Pragma("unroll") for (int k = 0; k < NPT; ++k)                                                \
                     if (G::pstep(k) == (S)) {                                                                  \
                         if (k >= PRO) { ISSUE_P(k, c32); }                                                     \
@@ -787,7 +640,7 @@ __device__ __forceinline__ void conv3x3_s2_body(const ConvArgs& a, int n_tiles) 
         // weight stages 0, 1 and the A / B pieces of chunk 0 have landed.  The previous tile's 16 output stores per thread were
         // issued BEHIND them (vmcnt retires in order): a full tile leaves them in flight, a ragged one (some stores skipped:
         // the count is not known) and the dynamic-exit form drain everything.
-        if (IMAP || !stores16 || S2_DRAIN_STORES) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (IMAP || !stores16) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         else if (SKIP && pooled_prev) {                    // (wave-uniform: the count is per wave)
             if (wp) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
@@ -820,230 +673,164 @@ __device__ __forceinline__ void conv3x3_s2_body(const ConvArgs& a, int n_tiles) 
         if (nvb < v_end) SETUP_TILE(nvb);
 
         [[maybe_unused]] bool pooled_now = false;
-        // ---- epilogue of the current tile: BN + ReLU on the accumulators, fp16 straight from the registers (S2_DIRECT) or through LDS, 32 KB per
-        //      channel half, two rounds of 128 pixels (conv_igemm_wide_persist's, with this kernel's tile-pixel order) ----
-        if (S2_ABL_NOEPI) {
-            float sum_ = 0.f;
+        // ---- epilogue of the current tile: BN + ReLU on the accumulators, fp16 straight from the registers ----
+        int tl = tid & 255;
+        asm volatile("" : "+v"(tl));                        // (unused: kept only because it shapes register allocation — without it the SGPR-spill VGPR moves)
+        const int chl = cur_ch0 + (HALF ? 0 : 128 * g);    // launch-wide channel of this group's channel 0 (BN table index)
+        _Float16* outp = a.out;
+        int oc = a.Cout, chg = chl;
+        if (a.wgt_b) {
+            if (chl >= split) { outp = a.out_b; oc = a.Cout - split; chg = chl - split; }
+            else oc = split;
+        }
+        float* const poolp = TW == 4 ? ((a.wgt_b && chl >= split) ? a.pool_b : a.pool) : nullptr;     // wave-uniform (per channel half)
+        if constexpr (SKIP) pooled_now = poolp != nullptr;
+        if (SKIP && poolp) {
+            if constexpr (SKIP) {
+            // Pad-skip: an image's 16 positions are the 8 tile registers of this lane and of the same lane of the partner wave (wp ^ 1).  The sum
+            // keeps the order of the DPP tree below — map row y: (p0 + p1) + (p2 + p3), then (r0 + r1) + (r3 + r2), then * 1/16 — through the staging
+            // area at E_OFF, which nothing of the next tile touches before its step 0 (conv3x3_pw's persistent pooled tail): wave wp sends the tiles
+            // of rows 2 (1 - wp), 2 (1 - wp) + 1 and sums rows 2 wp, 2 wp + 1 (a pair p0 + p1 / p2 + p3 is one value of each wave; float addition
+            // commutes); pixel wave 1 then sends r2 + r3 and pixel wave 0 stores.  Slot of wave w: 8 KB, [tile 0..3][quad 0..1][lane] float4.
+            // Three barriers per 32-channel half h: a channel group that stores plainly (mixed pair) takes the same six below.
+            char* const X = smem + G::E_OFF;
+            char* const mine_x = X + wave * 8192 + lane * 16;
+            char* const theirs_x = X + (wave ^ 1) * 8192 + lane * 16;
+            const int chw = chl + wc * 64 + 8 * kq;
 #pragma unroll
-            for (int i = 0; i < TI; ++i)
+            for (int h = 0; h < 2; ++h) {
+                f32x4_e sc[2], bi[2];
 #pragma unroll
-                for (int j = 0; j < TP; ++j) sum_ += acc[i][j][0] + acc[i][j][1] + acc[i][j][2] + acc[i][j][3];
-            if (sum_ == 12345.678f) a.out[tid] = (_Float16)sum_;
-        } else {
-            char* const E = smem + G::E_OFF + g * 32768;
-            int tl = tid & 255;
-            asm volatile("" : "+v"(tl));                    // (per tile: hoisted out of the tile loop, what derives from it is spilled)
-            const int chl = cur_ch0 + (HALF ? 0 : 128 * g);    // launch-wide channel of this group's channel 0 (BN table index)
-            _Float16* outp = a.out;
-            int oc = a.Cout, chg = chl;
-            if (a.wgt_b) {
-                if (chl >= split) { outp = a.out_b; oc = a.Cout - split; chg = chl - split; }
-                else oc = split;
-            }
-            const int k = tl & 15;
-            float* const poolp = TW == 4 ? ((a.wgt_b && chl >= split) ? a.pool_b : a.pool) : nullptr;     // wave-uniform (per channel half)
-            if constexpr (SKIP) pooled_now = poolp != nullptr;
-            if (SKIP && poolp) {
-                if constexpr (SKIP) {
-                // Pad-skip: an image's 16 positions are the 8 tile registers of this lane and of the same lane of the partner wave (wp ^ 1).  The sum
-                // keeps the order of the DPP tree below — map row y: (p0 + p1) + (p2 + p3), then (r0 + r1) + (r3 + r2), then * 1/16 — through the staging
-                // area at E_OFF, which nothing of the next tile touches before its step 0 (conv3x3_pw's persistent pooled tail): wave wp sends the tiles
-                // of rows 2 (1 - wp), 2 (1 - wp) + 1 and sums rows 2 wp, 2 wp + 1 (a pair p0 + p1 / p2 + p3 is one value of each wave; float addition
-                // commutes); pixel wave 1 then sends r2 + r3 and pixel wave 0 stores.  Slot of wave w: 8 KB, [tile 0..3][quad 0..1][lane] float4.
-                // Three barriers per 32-channel half h: a channel group that stores plainly (mixed pair) takes the same six below.
-                char* const X = smem + G::E_OFF;
-                char* const mine_x = X + wave * 8192 + lane * 16;
-                char* const theirs_x = X + (wave ^ 1) * 8192 + lane * 16;
-                const int chw = chl + wc * 64 + 8 * kq;
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    f32x4_e sc[2], bi[2];
-#pragma unroll
-                    for (int ii = 0; ii < 2; ++ii) {
-                        sc[ii] = *(const f32x4_e*)(bn_scale + chw + 32 * h + 4 * ii);
-                        bi[ii] = *(const f32x4_e*)(bn_bias + chw + 32 * h + 4 * ii);
-                    }
-                    float xs[TP][8];                                      // relu(bn(.)) of this lane's 8 channels at its 8 positions
-#pragma unroll
-                    for (int j = 0; j < TP; ++j)
-#pragma unroll
-                        for (int ii = 0; ii < 2; ++ii)
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) xs[j][4 * ii + e] = fmaxf(__builtin_fmaf(acc[2 * h + ii][j][e], sc[ii][e], bi[ii][e]), 0.f);
-#pragma unroll
-                    for (int jj = 0; jj < 4; ++jj)
-#pragma unroll
-                        for (int q = 0; q < 2; ++q) {
-                            f32x4_e t;
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) t[e] = wp ? xs[jj][4 * q + e] : xs[4 + jj][4 * q + e];
-                            *(f32x4_e*)(mine_x + (jj * 2 + q) * 1024) = t;
-                        }
-                    lds_barrier();
-                    float rs[2][8];                                       // the two row sums of this wave
-#pragma unroll
-                    for (int r = 0; r < 2; ++r)
-#pragma unroll
-                        for (int q = 0; q < 2; ++q) {
-                            const f32x4_e t0 = *(const f32x4_e*)(theirs_x + ((2 * r) * 2 + q) * 1024), t1 = *(const f32x4_e*)(theirs_x + ((2 * r + 1) * 2 + q) * 1024);
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) {
-                                const float o0 = wp ? xs[4 + 2 * r][4 * q + e] : xs[2 * r][4 * q + e], o1 = wp ? xs[4 + 2 * r + 1][4 * q + e] : xs[2 * r + 1][4 * q + e];
-                                const float s01 = o0 + t0[e], s23 = o1 + t1[e];
-                                rs[r][4 * q + e] = s01 + s23;
-                            }
-                        }
-                    float half_sum[8];
-#pragma unroll
-                    for (int c = 0; c < 8; ++c) half_sum[c] = rs[0][c] + rs[1][c];          // r0 + r1 | r2 + r3
-                    lds_barrier();                                        // every wave has read its partner's slot
-                    if (wp) {
-#pragma unroll
-                        for (int q = 0; q < 2; ++q) {
-                            f32x4_e t;
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) t[e] = half_sum[4 * q + e];
-                            *(f32x4_e*)(theirs_x + q * 1024) = t;
-                        }
-                    }
-                    lds_barrier();
-                    if (!wp) {
-                        const int n = cur_n0 + l16;
-#pragma unroll
-                        for (int q = 0; q < 2; ++q) {
-                            const f32x4_e t = *(const f32x4_e*)(mine_x + q * 1024);
-                            f32x4_e pv;
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) pv[e] = (half_sum[4 * q + e] + t[e]) * (1.f / 16.f);
-                            if (n < a.N) *(f32x4_e*)(poolp + (size_t)n * oc + chg + wc * 64 + 8 * kq + 32 * h + 4 * q) = pv;
-                        }
-                    }
+                for (int ii = 0; ii < 2; ++ii) {
+                    sc[ii] = *(const f32x4_e*)(bn_scale + chw + 32 * h + 4 * ii);
+                    bi[ii] = *(const f32x4_e*)(bn_bias + chw + 32 * h + 4 * ii);
                 }
-                // (the next tile's own-period pieces overwrite the staging area from its step 0: every exchange read is complete before the tile-start barrier)
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                }
-            } else if (poolp) {
-                // ReLU + global average pool fused (the conv feeds an exit head only): a wave's pixel tile j is image wp * 8 + j of
-                // the tile, its 16 pixels the 16 lanes of a DPP row — four v_add_f32 with DPP (quad xor 1, xor 2, half mirror, row
-                // mirror) leave the sum in every lane; lane 0 of each row stores 4 consecutive channels as fp32.  Nothing goes
-                // through LDS; the three barriers keep step with a channel half that takes the ordinary path.
+                float xs[TP][8];                                      // relu(bn(.)) of this lane's 8 channels at its 8 positions
 #pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const int cw = S2_DIRECT ? 32 * (i >> 1) + 8 * kq + 4 * (i & 1) : 16 * i + 4 * kq;      // this lane's 4 channels of tile i
-                    const int c4 = chl + wc * 64 + cw;
-                    const f32x4_e sc = *(const f32x4_e*)(bn_scale + c4), bi = *(const f32x4_e*)(bn_bias + c4);
+                for (int j = 0; j < TP; ++j)
 #pragma unroll
-                    for (int j = 0; j < TP; ++j) {
-                        f32x4_e v;
+                    for (int ii = 0; ii < 2; ++ii)
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) xs[j][4 * ii + e] = fmaxf(__builtin_fmaf(acc[2 * h + ii][j][e], sc[ii][e], bi[ii][e]), 0.f);
+#pragma unroll
+                for (int jj = 0; jj < 4; ++jj)
+#pragma unroll
+                    for (int q = 0; q < 2; ++q) {
+                        f32x4_e t;
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) t[e] = wp ? xs[jj][4 * q + e] : xs[4 + jj][4 * q + e];
+                        *(f32x4_e*)(mine_x + (jj * 2 + q) * 1024) = t;
+                    }
+                lds_barrier();
+                float rs[2][8];                                       // the two row sums of this wave
+#pragma unroll
+                for (int r = 0; r < 2; ++r)
+#pragma unroll
+                    for (int q = 0; q < 2; ++q) {
+                        const f32x4_e t0 = *(const f32x4_e*)(theirs_x + ((2 * r) * 2 + q) * 1024), t1 = *(const f32x4_e*)(theirs_x + ((2 * r + 1) * 2 + q) * 1024);
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
-                            float x = fmaxf(__builtin_fmaf(acc[i][j][e], sc[e], bi[e]), 0.f);     // (explicitly fused: the same bits in every instantiation)
-                            x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0xB1, 0xF, 0xF, true));    // lane ^ 1
-                            x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x4E, 0xF, 0xF, true));    // lane ^ 2
-                            x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x141, 0xF, 0xF, true));   // 7 - lane (half row)
-                            x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x140, 0xF, 0xF, true));   // 15 - lane (row)
-                            v[e] = x * (1.f / 16.f);
+                            const float o0 = wp ? xs[4 + 2 * r][4 * q + e] : xs[2 * r][4 * q + e], o1 = wp ? xs[4 + 2 * r + 1][4 * q + e] : xs[2 * r + 1][4 * q + e];
+                            const float s01 = o0 + t0[e], s23 = o1 + t1[e];
+                            rs[r][4 * q + e] = s01 + s23;
                         }
-                        int n = cur_n0 + wp * 8 + j;
-                        if constexpr (IMAP) n = row_tabs[cur_tsel * 16 + wp * 8 + j];
-                        else if (n >= a.N) n = -1;
-                        if (l16 == 0 && n >= 0) *(f32x4_e*)(poolp + (size_t)n * oc + chg + wc * 64 + cw) = v;
                     }
-                }
-                if (!S2_DIRECT) { lds_barrier(); lds_barrier(); lds_barrier(); }
-            } else if constexpr (S2_DIRECT) {
-                // straight from the registers: lane (kq, l16) holds, for pixel tile j, channels 8 kq .. + 7 (tiles 0, 1) and 32 + 8 kq .. + 7
-                // (tiles 2, 3) of the wave's 64 channels of tile pixel pbase + 16 j + l16; the four lanes of a pixel write 64 contiguous bytes
-                const int cw = wc * 64 + 8 * kq;
-                f32x4_e sc[4], bi[4];
+                float half_sum[8];
 #pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    sc[i] = *(const f32x4_e*)(bn_scale + chl + cw + 32 * (i >> 1) + 4 * (i & 1));
-                    bi[i] = *(const f32x4_e*)(bn_bias + chl + cw + 32 * (i >> 1) + 4 * (i & 1));
-                }
+                for (int c = 0; c < 8; ++c) half_sum[c] = rs[0][c] + rs[1][c];          // r0 + r1 | r2 + r3
+                lds_barrier();                                        // every wave has read its partner's slot
+                if (wp) {
 #pragma unroll
-                for (int j = 0; j < TP; ++j) {
-                    const int p = pbase + 16 * j + l16;
-                    // (pad-skip: lane l16 of tile j is image l16 at the tile's position)
-                    int n = cur_n0 + (SKIP ? l16 : G::p_img(p));
-                    const int opos = SKIP ? S2Skip::t_y(j) * TW + S2Skip::t_x(wp, j) : G::p_oy(p) * TW + G::p_ox(p);
-                    if constexpr (IMAP) n = row_tabs[cur_tsel * 16 + G::p_img(p)];      // tensor row, -1 beyond N
-                    else if (n >= a.N) n = -1;
-                    _Float16* const dst = outp + ((size_t)(n < 0 ? 0 : n) * (TW * TW) + opos) * oc + chg + cw;
+                    for (int q = 0; q < 2; ++q) {
+                        f32x4_e t;
 #pragma unroll
-                    for (int h = 0; h < 2; ++h) {
-                        half8_e o;
-#pragma unroll
-                        for (int ii = 0; ii < 2; ++ii)
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) {
-                                float v = acc[2 * h + ii][j][e] * sc[2 * h + ii][e] + bi[2 * h + ii][e];
-                                if (a.relu) v = fmaxf(v, 0.f);
-                                o[4 * ii + e] = a16_from_f32<BF>(v);
-                            }
-                        if (n >= 0 && !S2_ABL_NOSTORE) *(half8_e*)(dst + 32 * h) = o;
-                    }
-                }
-                if constexpr (SKIP) {
-                    // mixed pair: the other channel group of this workgroup pools through LDS — s_barrier is workgroup-wide: its six barriers
-                    const float* const pool_o = (a.wgt_b && cur_ch0 + 128 * (1 - g) >= split) ? a.pool_b : a.pool;
-                    if (pool_o) {
-#pragma unroll
-                        for (int b = 0; b < 6; ++b) lds_barrier();
-                    }
-                }
-            } else
-#pragma unroll
-            for (int rr = 0; rr < (HALF ? 1 : 2); ++rr) {   // (128-channel tiles: a group's 128 ch x 128 px are one round)
-                if (rr) lds_barrier();                      // round 0's reads are done
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const int c4 = chl + wc * 64 + 16 * i + 4 * kq;
-                    const f32x4_e sc = *(const f32x4_e*)(bn_scale + c4), bi = *(const f32x4_e*)(bn_bias + c4);
-                    const int cq = wc * 8 + 2 * i + (kq >> 1);
-#pragma unroll
-                    for (int jj = 0; jj < 4; ++jj) {
-                        const int p = wp * 64 + jj * 16 + l16;                   // pixel inside the round
-                        half4 o;
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            float v = acc[i][4 * rr + jj][e] * sc[e] + bi[e];
-                            if (a.relu) v = fmaxf(v, 0.f);
-                            o[e] = a16_from_f32<BF>(v);
-                        }
-                        *(half4*)(E + p * 256 + ((cq ^ l16) << 4) + (((kq ^ jj) & 1) << 3)) = o;
+                        for (int e = 0; e < 4; ++e) t[e] = half_sum[4 * q + e];
+                        *(f32x4_e*)(theirs_x + q * 1024) = t;
                     }
                 }
                 lds_barrier();
+                if (!wp) {
+                    const int n = cur_n0 + l16;
 #pragma unroll
-                for (int hb = 0; hb < 2; ++hb) {            // (two batches of four: the next tile's DMA sources stay in registers)
-                    half8_e o8[4];
+                    for (int q = 0; q < 2; ++q) {
+                        const f32x4_e t = *(const f32x4_e*)(mine_x + q * 1024);
+                        f32x4_e pv;
 #pragma unroll
-                    for (int it = 0; it < 4; ++it) {
-                        const int pl = (tl >> 4) + 16 * (4 * hb + it);
-                        o8[it] = *(const half8_e*)(E + pl * 256 + ((k ^ (pl & 15)) << 4));
+                        for (int e = 0; e < 4; ++e) pv[e] = (half_sum[4 * q + e] + t[e]) * (1.f / 16.f);
+                        if (n < a.N) *(f32x4_e*)(poolp + (size_t)n * oc + chg + wc * 64 + 8 * kq + 32 * h + 4 * q) = pv;
                     }
+                }
+            }
+            // (the next tile's own-period pieces overwrite the staging area from its step 0: every exchange read is complete before the tile-start barrier)
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            }
+        } else if (poolp) {
+            // ReLU + global average pool fused (the conv feeds an exit head only): a wave's pixel tile j is image wp * 8 + j of
+            // the tile, its 16 pixels the 16 lanes of a DPP row — four v_add_f32 with DPP (quad xor 1, xor 2, half mirror, row
+            // mirror) leave the sum in every lane; lane 0 of each row stores 4 consecutive channels as fp32.  Nothing goes
+            // through LDS.
 #pragma unroll
-                    for (int it = 0; it < 4; ++it) {
-                        const int pl = (tl >> 4) + 16 * (4 * hb + it);
-                        const int p = HALF ? g * 128 + pl : (pl >> 6) * 128 + rr * 64 + (pl & 63);     // tile pixel
-                        int n = cur_n0 + G::p_img(p);
-                        if constexpr (IMAP) n = row_tabs[cur_tsel * 16 + G::p_img(p)];      // tensor row, -1 beyond N
-                        else if (n >= a.N) n = -1;
-                        if (n < 0 || S2_ABL_NOSTORE) continue;
-                        half8_e v = o8[it];
-                        if (it & 1) v = __builtin_shufflevector(v, v, 4, 5, 6, 7, 0, 1, 2, 3);
-                        _Float16* dst_ = outp + ((size_t)n * (TW * TW) + G::p_oy(p) * TW + G::p_ox(p)) * oc + chg + 8 * k;
-                        if (S2_STORE_SC1) {
-                            typedef unsigned int u32x4_ __attribute__((ext_vector_type(4)));
-                            // (hipcc does not model an asm store: without the trailing s_nop its next instruction may overwrite the data
-                            // registers before the store has read them — cdna_hip_programming.md §5.7 item 1; the first build without it
-                            // failed every model-level parity test)
-                            asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(dst_), "v"(__builtin_bit_cast(u32x4_, v)) : "memory");
-                        } else {
-                            *(half8_e*)dst_ = v;
+            for (int i = 0; i < 4; ++i) {
+                const int cw = 32 * (i >> 1) + 8 * kq + 4 * (i & 1);      // this lane's 4 channels of tile i
+                const int c4 = chl + wc * 64 + cw;
+                const f32x4_e sc = *(const f32x4_e*)(bn_scale + c4), bi = *(const f32x4_e*)(bn_bias + c4);
+#pragma unroll
+                for (int j = 0; j < TP; ++j) {
+                    f32x4_e v;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        float x = fmaxf(__builtin_fmaf(acc[i][j][e], sc[e], bi[e]), 0.f);     // (explicitly fused: the same bits in every instantiation)
+                        x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0xB1, 0xF, 0xF, true));    // lane ^ 1
+                        x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x4E, 0xF, 0xF, true));    // lane ^ 2
+                        x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x141, 0xF, 0xF, true));   // 7 - lane (half row)
+                        x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x140, 0xF, 0xF, true));   // 15 - lane (row)
+                        v[e] = x * (1.f / 16.f);
+                    }
+                    int n = cur_n0 + wp * 8 + j;
+                    if constexpr (IMAP) n = row_tabs[cur_tsel * 16 + wp * 8 + j];
+                    else if (n >= a.N) n = -1;
+                    if (l16 == 0 && n >= 0) *(f32x4_e*)(poolp + (size_t)n * oc + chg + wc * 64 + cw) = v;
+                }
+            }
+        } else {
+            // straight from the registers: lane (kq, l16) holds, for pixel tile j, channels 8 kq .. + 7 (tiles 0, 1) and 32 + 8 kq .. + 7
+            // (tiles 2, 3) of the wave's 64 channels of tile pixel pbase + 16 j + l16; the four lanes of a pixel write 64 contiguous bytes
+            const int cw = wc * 64 + 8 * kq;
+            f32x4_e sc[4], bi[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                sc[i] = *(const f32x4_e*)(bn_scale + chl + cw + 32 * (i >> 1) + 4 * (i & 1));
+                bi[i] = *(const f32x4_e*)(bn_bias + chl + cw + 32 * (i >> 1) + 4 * (i & 1));
+            }
+#pragma unroll
+            for (int j = 0; j < TP; ++j) {
+                const int p = pbase + 16 * j + l16;
+                // (pad-skip: lane l16 of tile j is image l16 at the tile's position)
+                int n = cur_n0 + (SKIP ? l16 : G::p_img(p));
+                const int opos = SKIP ? S2Skip::t_y(j) * TW + S2Skip::t_x(wp, j) : G::p_oy(p) * TW + G::p_ox(p);
+                if constexpr (IMAP) n = row_tabs[cur_tsel * 16 + G::p_img(p)];      // tensor row, -1 beyond N
+                else if (n >= a.N) n = -1;
+                _Float16* const dst = outp + ((size_t)(n < 0 ? 0 : n) * (TW * TW) + opos) * oc + chg + cw;
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    half8_e o;
+#pragma unroll
+                    for (int ii = 0; ii < 2; ++ii)
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            float v = acc[2 * h + ii][j][e] * sc[2 * h + ii][e] + bi[2 * h + ii][e];
+                            if (a.relu) v = fmaxf(v, 0.f);
+                            o[4 * ii + e] = a16_from_f32<BF>(v);
                         }
-                    }
+                    if (n >= 0) *(half8_e*)(dst + 32 * h) = o;
+                }
+            }
+            if constexpr (SKIP) {
+                // mixed pair: the other channel group of this workgroup pools through LDS — s_barrier is workgroup-wide: its six barriers
+                const float* const pool_o = (a.wgt_b && cur_ch0 + 128 * (1 - g) >= split) ? a.pool_b : a.pool;
+                if (pool_o) {
+#pragma unroll
+                    for (int b = 0; b < 6; ++b) lds_barrier();
                 }
             }
         }
@@ -1058,14 +845,12 @@ __device__ __forceinline__ void conv3x3_s2_body(const ConvArgs& a, int n_tiles) 
 #undef WAIT_VM
 #undef RAW_BARRIER
 #undef SETUP_TILE
-#undef ISSUE_BITS
 #undef MASK_DUE
 #undef MASK_P
 #undef MASK_STORE
 #undef MASK_LOAD
 #undef ISSUE_P
 #undef ISSUE_W
-#undef ISSUE_W_HALF
 #undef A_TILE
 }
 

@@ -39,7 +39,7 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(ConvArgs a) {
     constexpr int TILE = (BC + BP) * 128;
     constexpr int MAIN_BYTES = (DBUF ? 2 : 1) * TILE;
     constexpr int LDS_BYTES = (BC == 128 && MAIN_BYTES < BMI_EPILOGUE_LDS_BYTES) ? BMI_EPILOGUE_LDS_BYTES : MAIN_BYTES;
-    // XMASK: keep byte -> the four dword masks of its 8 halves, a 256-entry table behind the tiles (conv3x3_s2's S2_MASK_LUT: one
+    // XMASK: keep byte -> the four dword masks of its 8 halves, a 256-entry table behind the tiles (conv3x3_s2's masked-input table: one
     // ds_read_b128 instead of ~20 vector instructions per staged row — this kernel's masked form was issue-bound, see GLOAD)
     __shared__ __attribute__((aligned(16))) char smem[LDS_BYTES + (XMASK ? 4096 : 0)];
     if constexpr (XMASK) {
