@@ -19,6 +19,7 @@ OP_STEM, OP_CONV, OP_MASK, OP_HEAD, OP_MAXPOOL, OP_DENSE = 1, 2, 3, 4, 5, 6
 STOP_RULES = {"sem": 0, "margin": 1}      # BMI_STOP_* of bmi_forward_mcd_adaptive
 EXIT_RULES = {"confidence": 0, "margin": 1}      # BMI_EXIT_* of bmi_forward_mcd_exit_staged
 STOP_ON = {"exit": 0, "ensemble": 1}      # BMI_STOP_ON_* of bmi_forward_mcd_adaptive_ensemble
+NLL_ENS_SLAB, NLL_ENS_ROWS = 9216, 192      # BMI_NLL_ENS_* of bmi_nll_ensemble_temperature_grid: floats / rows a workgroup stages per chunk
 
 
 class ExitRule(C.Structure):
@@ -116,6 +117,9 @@ _PROTOS = {
     "bmi_nll_temperature_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "bmi_nll_temperature_grid": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                            C.c_void_p, C.c_size_t, C.c_void_p]),
+    "bmi_nll_ensemble_temperature_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "bmi_nll_ensemble_temperature_grid": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint32,
+                                                    C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "bmi_profile_enable": (C.c_int, [C.c_void_p, C.c_int32]),
     "bmi_profile_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "bmi_philox_mask": (C.c_int, [C.c_void_p, C.c_int64, C.c_uint64, C.c_int32, C.c_int32, C.c_float, C.c_void_p]),

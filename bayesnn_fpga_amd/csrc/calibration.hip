@@ -16,6 +16,33 @@
 //   the sum over images: the per-image terms go to a scratch [E][G][B]; nll_sum_kernel adds them in a fixed order (one wavefront per
 //               (exit, candidate): lane j takes images j, j + 64, .. in order, then a shuffle butterfly) — no floating-point atomics,
 //               the same bits on every run, the way head_join_kernel joins the sample groups of the exit heads.
+//
+// The objective of a JOINT fit of the exit ensembles (bmi_nll_ensemble_temperature_grid, ens_nll_terms_kernel below): row e is the NLL
+// of the mean over exits 0..e and over the T samples of the tempered softmax — the row ensemble.hip forms, as a likelihood —
+//     a[t][i][b] as a_t above at tau_i(g),  L[i][b] = logsumexp_t a[t][i][b],  R[0] = L[0],  R[e] = logaddexp(R[e-1], L[e]),
+//     nll[e][g] += sum_b -( R[e][b] - log(T * (e + 1)) ),      logaddexp(x, y) = m + log(exp(x - m) + exp(y - m)),  m = max(x, y)
+// where tau_i(g) is the candidate tau_cand[g] for the exits in vary_mask and the current tau[i] for the others
+// (train/calibration.py: ensemble_nll_grid_numpy).
+//
+//   workgroup = a run of IMG consecutive images x ALL E exits x a slice of at most ENS_GS candidates, 256 threads.  The run's logits are
+//               staged once, slab row = (sample, exit, image) with the same odd stride; row max and label logit once per row.
+//   a           ONE list of work items per chunk: (row) for the exits outside the mask — their a does not depend on the candidate and
+//               is computed once per row and workgroup — and (candidate, row) for the exits in the mask.  A candidate of a coordinate
+//               step costs C exponentials per (image, sample), not E * C; G = 33 candidates of a step at E = 4 cost 6 * 3C + 33C = 51C
+//               against the 132C of a per-exit grid launch on the same logits.
+//   join        one thread per (candidate, image) walks the exits in order: the log-sum-exp over the samples in sample order, then
+//               logaddexp onto the running R, and writes the image's term of every row e.  Rows below the lowest varied exit come
+//               from the same values by the same operations for every candidate: they hold the same bits.
+//   chunks      T * E rows that do not fit run one image per workgroup in chunks of TC samples; the running (max, sum) of every
+//               (candidate, exit) is carried in LDS from chunk to chunk.
+//   limits      the slab stays at NLL_SLAB's 36 KB and a chunk at ENS_ROWS = 192 rows, ENS_GS = 6: with row_max / row_lab (1.5 KB), a of the
+//               fixed rows (1.5 KB), a of (candidate, row) (9 KB) and the chunk state (3 KB) a workgroup holds 51 KB of LDS, so THREE
+//               workgroups (12 wavefronts) share a CU's 160 KB — the kernel is bound by the latency of serial float64 exponentials,
+//               which resident wavefronts hide.  The paper's shape (E = 4, C = 100, T = 10: 40 rows of 101 floats per image) fits two
+//               images either way; a third would need a 48 KB slab and drop the CU to two workgroups.  E = 5, C = 100 fits 18
+//               (image, sample) rows: T = 10 runs one image per workgroup, unchunked.  The balanced slice (G = 33: six slices of 6, 6, 6,
+//               6, 6, 3) makes 750 workgroups of the paper's batch of 250, one resident wave of the chip's 768 slots.
+//   the sum over images is nll_sum_kernel's, on the same [E][G][B] scratch.
 #include <cmath>
 
 #include "kernels.h"
@@ -109,6 +136,117 @@ int launch_nll_temperature_grid(const float* logits, int T, int E, int B, int C,
     if (E > 65535 || gz > 65535 || (int64_t)E * G > INT32_MAX) return BMI_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(nll_terms_kernel, dim3(gx, (unsigned)E, gz), dim3(NLL_THREADS), 0, s, logits, T, E, B, C, CS, IMG, TC, labels, tau_grid, G,
                        scratch);
+    BMI_CHECK_LAUNCH();
+    hipLaunchKernelGGL(nll_sum_kernel, dim3((unsigned)(E * G)), dim3(64), 0, s, scratch, B, nll);
+    BMI_CHECK_LAUNCH();
+    return BMI_OK;
+}
+
+#define ENS_SLAB BMI_NLL_ENS_SLAB      // floats of staged logits (36 KB, NLL_SLAB's)
+#define ENS_ROWS BMI_NLL_ENS_ROWS      // (sample, exit, image) rows per staged chunk, at most
+#define ENS_GS 6                       // candidates per workgroup, at most
+#define ENS_MAX_EXITS 32               // vary_mask is 32 bits
+
+__global__ __launch_bounds__(NLL_THREADS) void ens_nll_terms_kernel(const float* __restrict__ logits, int T, int E, int B, int C, int CS, int IMG,
+                                                                    int TC, const int* __restrict__ labels, const float* __restrict__ tau,
+                                                                    unsigned vary_mask, const float* __restrict__ tau_cand, int G, int GSL,
+                                                                    double* __restrict__ terms) {
+#pragma clang fp contract(off)
+    __shared__ float slab[ENS_SLAB];                     // [row][CS]: row = (tl * E + i) * imgs + bi
+    __shared__ float row_max[ENS_ROWS], row_lab[ENS_ROWS];
+    __shared__ double a_f[ENS_ROWS];                     // a of (row), exits outside the mask
+    __shared__ double a_v[ENS_GS][ENS_ROWS];             // a of (candidate, row), exits in the mask
+    __shared__ double st_m[ENS_GS][ENS_MAX_EXITS], st_s[ENS_GS][ENS_MAX_EXITS];      // several sample chunks (IMG == 1): the running max / sum
+    __shared__ int ex_of[ENS_MAX_EXITS];                 // the exits outside the mask in order, then the exits in the mask in order
+    const int tid = threadIdx.x;
+    const int b0 = blockIdx.x * IMG;
+    const int imgs = min(IMG, B - b0);
+    const int g0 = blockIdx.y * GSL;
+    const int gs = min(GSL, G - g0);
+    const int nv = __popc(vary_mask), nf = E - nv;
+    if (tid < E) {
+        const int below = __popc(vary_mask & ((1u << tid) - 1u));            // varied exits below this one
+        ex_of[(vary_mask >> tid & 1u) ? nf + below : tid - below] = tid;
+    }
+    for (int t0 = 0; t0 < T; t0 += TC) {
+        const int tcn = min(TC, T - t0);
+        const int np = imgs * tcn;                       // (image, sample) pairs; rows = np * E <= ENS_ROWS, rows * CS <= ENS_SLAB (the launcher's IMG / TC)
+        const int rows = np * E;
+        __syncthreads();                                 // the previous chunk's readers are done (and ex_of is written)
+        for (int idx = tid; idx < rows * C; idx += NLL_THREADS) {
+            const int r = idx / C, c = idx - r * C;
+            const int ti = r / imgs, bi = r - ti * imgs; // ti = tl * E + i
+            slab[r * CS + c] = logits[((size_t)t0 * E + ti) * B * C + (size_t)(b0 + bi) * C + c];
+        }
+        __syncthreads();
+        if (tid < rows) {
+            const float* row = slab + tid * CS;
+            float mx = row[0];
+            for (int c = 1; c < C; ++c) mx = fmaxf(mx, row[c]);
+            const int y = labels[b0 + tid % imgs];
+            row_max[tid] = mx;
+            row_lab[tid] = (y >= 0 && y < C) ? row[y] : NAN;      // (the callers check their labels: never an out-of-range read)
+        }
+        __syncthreads();
+        const int n_fixed = np * nf, n_var = np * nv;
+        for (int it = tid; it < n_fixed + gs * n_var; it += NLL_THREADS) {
+            int gl = -1, k = it;
+            if (it >= n_fixed) { gl = (it - n_fixed) / n_var; k = n_fixed + (it - n_fixed) - gl * n_var; }
+            const int i = ex_of[k / np], p = k % np;     // p = tl * imgs + bi
+            const int tl = p / imgs, bi = p - tl * imgs;
+            const int r = (tl * E + i) * imgs + bi;
+            const double inv = 1.0 / (double)(gl < 0 ? tau[i] : tau_cand[g0 + gl]);
+            const double zmax = (double)row_max[r] * inv;
+            const float* row = slab + r * CS;
+            double s = 0.0;
+            for (int c = 0; c < C; ++c) s += exp((double)row[c] * inv - zmax);
+            const double a = ((double)row_lab[r] * inv - zmax) - log(s);
+            if (gl < 0) a_f[r] = a;
+            else a_v[gl][r] = a;
+        }
+        __syncthreads();
+        // thread (candidate, image): per exit the log-sum-exp over the samples in sample order, then the exits in order
+        for (int it = tid; it < gs * imgs; it += NLL_THREADS) {
+            const int gl = it / imgs, bi = it - gl * imgs;
+            const bool last = t0 + tcn >= T;
+            double R = 0.0;
+            for (int i = 0; i < E; ++i) {
+                const double* a = ((vary_mask >> i & 1u) ? a_v[gl] : a_f) + i * imgs + bi;       // sample tl at a[tl * E * imgs]
+                const int step = E * imgs;
+                double m = -INFINITY, s = 0.0;
+                if (t0 > 0) { m = st_m[gl][i]; s = st_s[gl][i]; }              // (more than one chunk: imgs == 1, it == gl)
+                double cm = a[0];
+                for (int tl = 1; tl < tcn; ++tl) cm = fmax(cm, a[tl * step]);
+                const double nm = fmax(m, cm);
+                s = s * exp(m - nm);
+                for (int tl = 0; tl < tcn; ++tl) s += exp(a[tl * step] - nm);
+                m = nm;
+                if (last) {
+                    const double L = m + log(s);
+                    if (i == 0) R = L;
+                    else {
+                        const double mx = fmax(R, L);
+                        R = mx + log(exp(R - mx) + exp(L - mx));
+                    }
+                    terms[((size_t)i * G + g0 + gl) * B + b0 + bi] = -(R - log((double)T * (double)(i + 1)));
+                } else { st_m[gl][i] = m; st_s[gl][i] = s; }
+            }
+        }
+    }
+}
+
+int launch_nll_ensemble_temperature_grid(const float* logits, int T, int E, int B, int C, const int* labels, const float* tau, unsigned vary_mask,
+                                         const float* tau_cand, int G, double* nll, double* scratch, hipStream_t s) {
+    const int CS = C | 1;                                // odd row stride
+    if (E > ENS_MAX_EXITS || (int64_t)E * CS > ENS_SLAB) return BMI_ERR_UNSUPPORTED;
+    const int per_t = min(ENS_ROWS, ENS_SLAB / CS) / E;  // samples of one image (E rows each) a chunk can stage, >= 1
+    const int TC = min(T, per_t);
+    const int IMG = T <= per_t ? min(per_t / T, B) : 1;
+    const int slices = (G + ENS_GS - 1) / ENS_GS, GSL = (G + slices - 1) / slices;      // balanced: G = 7 runs as 4 + 3, not 6 + 1
+    const unsigned gx = (unsigned)((B + IMG - 1) / IMG), gy = (unsigned)((G + GSL - 1) / GSL);
+    if (gy > 65535 || (int64_t)E * G > INT32_MAX) return BMI_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(ens_nll_terms_kernel, dim3(gx, gy), dim3(NLL_THREADS), 0, s, logits, T, E, B, C, CS, IMG, TC, labels, tau, vary_mask, tau_cand,
+                       G, GSL, scratch);
     BMI_CHECK_LAUNCH();
     hipLaunchKernelGGL(nll_sum_kernel, dim3((unsigned)(E * G)), dim3(64), 0, s, scratch, B, nll);
     BMI_CHECK_LAUNCH();

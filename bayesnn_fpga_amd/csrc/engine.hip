@@ -1919,6 +1919,18 @@ int bmi_nll_temperature_grid(const float* logits, int32_t T, int32_t E, int32_t 
     return launch_nll_temperature_grid(logits, T, E, B, C, labels, tau_grid, G, nll, (double*)scratch, (hipStream_t)stream);
 }
 
+size_t bmi_nll_ensemble_temperature_scratch_bytes(int32_t E, int32_t B, int32_t G) { return bmi_nll_temperature_scratch_bytes(E, B, G); }
+
+int bmi_nll_ensemble_temperature_grid(const float* logits, int32_t T, int32_t E, int32_t B, int32_t C, const int32_t* labels, const float* tau,
+                                      uint32_t vary_mask, const float* tau_cand, int32_t G, double* nll, void* scratch, size_t scratch_bytes,
+                                      bmi_stream stream) {
+    if (!logits || !labels || !tau || !tau_cand || !nll || !scratch || T < 1 || E < 1 || B < 1 || C < 1 || G < 1) return BMI_ERR_INVALID;
+    if (E < 32 && (vary_mask >> E) != 0) return BMI_ERR_INVALID;
+    if (E > 32) return BMI_ERR_UNSUPPORTED;
+    if (scratch_bytes < bmi_nll_ensemble_temperature_scratch_bytes(E, B, G)) return BMI_ERR_NOMEM;
+    return launch_nll_ensemble_temperature_grid(logits, T, E, B, C, labels, tau, vary_mask, tau_cand, G, nll, (double*)scratch, (hipStream_t)stream);
+}
+
 int bmi_profile_enable(bmi_handle h, int32_t enable) {
     if (!h) return BMI_ERR_INVALID;
     h->profiling = enable != 0;

@@ -182,6 +182,11 @@ int launch_finalize_uncertainty(int n_rows, int C, int t_total, const double* S1
 // scratch: [E][G][B] float64 per-image terms
 int launch_nll_temperature_grid(const float* logits, int T, int E, int B, int C, const int* labels, const float* tau_grid, int G, double* nll,
                                 double* scratch, hipStream_t s);
+// calibration.hip (bmi_nll_ensemble_temperature_grid): nll [E][G] += row e = the NLL of the mean over exits 0..e and the T samples of the
+// tempered softmax, exit i at tau_cand[g] when bit i of vary_mask is set and at tau[i] otherwise; scratch: [E][G][B] float64 per-image terms.
+// BMI_ERR_UNSUPPORTED (nothing launched): E > 32, or E rows of C | 1 floats beyond BMI_NLL_ENS_SLAB
+int launch_nll_ensemble_temperature_grid(const float* logits, int T, int E, int B, int C, const int* labels, const float* tau, unsigned vary_mask,
+                                         const float* tau_cand, int G, double* nll, double* scratch, hipStream_t s);
 // ensemble.hip (bmi_ensemble_moments): Q1 / Q2 [E][B][C] and QH [E][B] += the moments and the entropy of the per-sample exit ensembles
 // q_te = mean_{i<=e} softmax(fl32(l_ti * inv_tau[i])) of logits [T][E][B][C], in sample order onto the running sums; inv_tau: host [E] or null
 #define BMI_ENS_MAX_EXITS 32

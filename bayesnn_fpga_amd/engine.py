@@ -325,6 +325,18 @@ def check_temperature(tau, n_exits):
     return [float(v) for v in vals]
 
 
+def vary_mask(vary, n_exits):
+    """``vary`` of ensemble_nll_grid (an exit index, an iterable of indices, or None) as the bit mask bmi_nll_ensemble_temperature_grid
+    takes; raises ValueError for an index outside [0, n_exits)."""
+    idx = [] if vary is None else [int(vary)] if np.ndim(vary) == 0 else [int(i) for i in vary]
+    if any(i < 0 or i >= n_exits for i in idx):
+        raise ValueError(f"vary: exit indices must lie in [0, {n_exits}), got {idx}")
+    mask = 0
+    for i in idx:
+        mask |= 1 << i
+    return mask
+
+
 def build_graph(model, device, dtype="f16"):
     g = GraphBuilder(device, dtype)
     fam = getattr(model, "family", None)
@@ -1028,6 +1040,41 @@ class MCDEngine(CompiledGraph):
             rc = self.lib.bmi_nll_temperature_grid(logits.data_ptr(), T, E, B, Cd, labels.data_ptr(), tau_grid.data_ptr(), G, out.data_ptr(),
                                                    scratch.data_ptr(), scratch.numel(), self._stream())
         _lib.check(rc, "bmi_nll_temperature_grid")
+        return out
+
+    def ensemble_nll_grid(self, logits, labels, tau, vary, cand, out=None):
+        """The objective of a joint temperature fit of the exit ensembles on the device (bmi_nll_ensemble_temperature_grid): ``logits`` /
+        ``labels`` as ``nll_grid``'s, ``tau`` the current temperatures (one per exit, a scalar for all, None for ones), ``vary`` the exits
+        that take the candidate instead (an exit index, an iterable of indices, or None), ``cand`` [G] candidate temperatures.  ADDS, per
+        row e and candidate, the NLL of the mean over exits 0..e and the T samples of the tempered softmax into ``out`` (float64 [E, G],
+        zeros when None) and returns it.  One index is a coordinate step, every index one shared temperature, None with G = 1 evaluates
+        ``tau``.  float64 throughout, the same bits on every run; ``train.calibration.ensemble_nll_grid_numpy`` is its host restatement.
+        Independent of the temperature set on this engine."""
+        T, E, B, Cd = logits.shape
+        if logits.dtype != torch.float32 or not logits.is_contiguous() or logits.device != self.device:
+            raise ValueError(f"logits must be contiguous float32 [T, E, B, C] on {self.device}")
+        if tuple(labels.shape) != (B,):
+            raise ValueError(f"labels must be [B] = [{B}]")
+        labels = labels.to(device=self.device, dtype=torch.int32).contiguous()
+        tau = check_temperature(1.0 if tau is None else tau, E)
+        mask = vary_mask(vary, E)
+        tau = torch.tensor(tau, dtype=torch.float32).to(self.device)
+        cand = torch.as_tensor(cand, dtype=torch.float32).to(self.device).contiguous()
+        if cand.dim() != 1 or cand.numel() < 1:
+            raise ValueError("cand must be [G], G >= 1")
+        G = cand.numel()
+        if out is None:
+            out = torch.zeros(E, G, dtype=torch.float64, device=self.device)
+        elif tuple(out.shape) != (E, G) or out.dtype != torch.float64 or not out.is_contiguous() or out.device != self.device:
+            raise ValueError("out must be contiguous float64 [E, G] on the engine's device")
+        need = int(self.lib.bmi_nll_ensemble_temperature_scratch_bytes(E, B, G))
+        scratch = self.__dict__.get("_nll_scratch")
+        if scratch is None or scratch.numel() < need:
+            scratch = self.__dict__["_nll_scratch"] = torch.empty(need, dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = self.lib.bmi_nll_ensemble_temperature_grid(logits.data_ptr(), T, E, B, Cd, labels.data_ptr(), tau.data_ptr(), mask, cand.data_ptr(),
+                                                            G, out.data_ptr(), scratch.data_ptr(), scratch.numel(), self._stream())
+        _lib.check(rc, "bmi_nll_ensemble_temperature_grid")
         return out
 
     def read_tensor(self, tensor_id, batch, samples=1):

@@ -15,6 +15,18 @@ has no temperature scaling; it saves the validation predictions (``save_validati
 * ``temper_logits``   — mean / var of the tempered per-sample softmax, the restatement of what the head computes under a temperature.
 * ``zoom_search``     — the deterministic per-exit search, all exits evaluated in the same launch.
 * ``TemperatureScaling`` — walks a labelled loader once, keeps the split's raw logits on the device, searches, applies, saves.
+
+Members calibrated one by one do not give a calibrated mean.  The exit ensemble (``predict_ensemble``: per sample the mean of exits
+0..e) is formed from the tempered members, and the JOINT fit minimises the ensemble's own NLL,
+
+    nll_e(tau) = sum_b -log( 1 / (T (e + 1)) sum_{i <= e} sum_t softmax(l_tib / tau_i)[y_b] ),
+
+evaluated on the device for a grid of candidates of one coordinate (or of one shared temperature) in one launch
+(``MCDEngine.ensemble_nll_grid``, bmi_nll_ensemble_temperature_grid).
+
+* ``ensemble_nll_grid_numpy`` — float64 restatement of that objective.
+* ``coordinate_search``  — coordinate descent (``zoom_search`` per coordinate) or one shared temperature, on row ``target``.
+* ``EnsembleTemperatureScaling`` — the loader-level joint fit, on the same walk as ``TemperatureScaling``.
 """
 import numpy as np
 import torch
@@ -54,6 +66,57 @@ def nll_grid_numpy(logits, labels, tau_grid):
     return out
 
 
+def _vary_list(vary, n_exits):
+    idx = [] if vary is None else [int(vary)] if np.ndim(vary) == 0 else [int(i) for i in vary]
+    if any(i < 0 or i >= n_exits for i in idx):
+        raise ValueError(f"vary: exit indices must lie in [0, {n_exits}), got {idx}")
+    return idx
+
+
+def ensemble_nll_grid_numpy(logits, labels, tau, vary, cand):
+    """float64 [E, G]: row e is sum_b -log of the mean over exits 0..e and the T samples of softmax(l / tau_i(g))[y_b], for ``logits``
+    [T, E, B, C], ``labels`` [B], ``tau`` [E] (or a scalar), ``vary`` (an exit index, an iterable of indices, or None) and ``cand`` [G],
+    temperatures taken as float32 like the device's: tau_i(g) = cand[g] for the exits in ``vary``, tau[i] for the others.
+    bmi_nll_ensemble_temperature_grid's arithmetic step by step (no clip; finite for any finite logits):
+    z = float64(l) * (1.0 / float64(tau_i(g)));  a_ti = (z_y - max_c z) - log sum_c exp(z_c - max_c z);  L_i = logsumexp_t a_ti;
+    R_0 = L_0, R_e = m + log(exp(R_{e-1} - m) + exp(L_e - m)) with m = max(R_{e-1}, L_e);  term_e = -(R_e - log(T (e + 1)))."""
+    logits = np.asarray(logits)
+    T, E, B, C = logits.shape
+    labels = np.asarray(labels).astype(np.int64).reshape(B)
+    if labels.min() < 0 or labels.max() >= C:
+        raise ValueError(f"labels must lie in [0, {C})")
+    tau = np.asarray(tau, dtype=np.float32).reshape(-1)
+    tau = np.repeat(tau, E) if tau.size == 1 else tau
+    if tau.size != E:
+        raise ValueError(f"tau must hold one value per exit ({E})")
+    cand = np.asarray(cand, dtype=np.float32).reshape(-1)
+    varied = set(_vary_list(vary, E))
+    inv_tau, inv_cand = 1.0 / tau.astype(np.float64), 1.0 / cand.astype(np.float64)
+    idx = np.arange(B)
+
+    def lse_samples(l, inv):                                     # L [B] of one exit at one temperature
+        z = l * inv
+        zmax = z.max(-1)
+        a = (z[:, idx, labels] - zmax) - np.log(np.exp(z - zmax[..., None]).sum(-1))       # [T, B]
+        am = a.max(0)
+        return am + np.log(np.exp(a - am).sum(0))
+
+    ls = [logits[:, i].astype(np.float64) for i in range(E)]
+    fixed = {i: lse_samples(ls[i], inv_tau[i]) for i in range(E) if i not in varied}
+    out = np.zeros((E, cand.size))
+    for g in range(cand.size):
+        R = None
+        for e in range(E):
+            L = lse_samples(ls[e], inv_cand[g]) if e in varied else fixed[e]
+            if R is None:
+                R = L
+            else:
+                m = np.maximum(R, L)
+                R = m + np.log(np.exp(R - m) + np.exp(L - m))
+            out[e, g] = np.sum(-(R - np.log(float(T) * float(e + 1))))
+    return out
+
+
 def temper_logits(logits, tau):
     """(mean, var), float64 [E, B, C]: over the T samples of ``logits`` [T, E, B, C], the mean and the variance (ddof = 0) of
     softmax(float32(l * inv_e)), inv_e = float32(1 / tau_e) — the fp32 product the exit head forms, the softmax in float64.  ``tau``: one
@@ -78,7 +141,7 @@ def _log_grid(lo, hi, n):
     return np.clip(g, lo, hi)
 
 
-def zoom_search(eval_fn, n_exits, bracket=(0.05, 20.0), grid=33, rtol=1e-4, max_rounds=8):
+def zoom_search(eval_fn, n_exits, bracket=(0.05, 20.0), grid=33, rtol=1e-4, max_rounds=8, include=None):
     """Deterministic one-dimensional search per exit, every exit evaluated in the same call: ``eval_fn(tau [E, G] float64) -> nll [E, G]``.
 
     Round one evaluates a log-spaced grid of ``grid`` points over the bracket plus tau = 1 exactly; each later round puts a log-spaced
@@ -87,6 +150,9 @@ def zoom_search(eval_fn, n_exits, bracket=(0.05, 20.0), grid=33, rtol=1e-4, max_
     EVERYTHING evaluated, so nll_after <= nll_before (the value at tau = 1) holds by construction.  Candidates are float32-representable
     (what the device evaluates and what an engine stores), the bracket's ends included: the ends are rounded to float32 once, and
     ``at_bound[e]`` says the returned point is one of them — the optimum lies outside the bracket, or the split does not determine it.
+
+    ``include`` ([E] or a scalar, None: off) is appended to the candidates of EVERY round, as given (the caller's current point: the
+    argmin is then never worse than it) — it is not clamped to the bracket, and ``nll_before`` stays the value at tau = 1.
 
     The search finds the basin of the coarse grid's minimum; the objective is NOT guaranteed unimodal in tau (a mixture over samples),
     and a narrower basin between two coarse points is not seen.  Non-finite objective values count as +inf.
@@ -103,8 +169,11 @@ def zoom_search(eval_fn, n_exits, bracket=(0.05, 20.0), grid=33, rtol=1e-4, max_
     lo, hi = np.full(E, b_lo), np.full(E, b_hi)
     nll_before = None
     rounds = 0
+    extra = None if include is None else np.broadcast_to(np.asarray(include, dtype=np.float64).reshape(-1, 1), (E, 1))
     while rounds < max_rounds:
         cand = np.stack([_log_grid(lo[e], hi[e], G) for e in range(E)])
+        if extra is not None:
+            cand = np.concatenate([cand, extra], axis=1)
         if rounds == 0:
             cand = np.concatenate([cand, np.ones((E, 1))], axis=1)
         val = np.asarray(eval_fn(cand), dtype=np.float64).reshape(cand.shape)
@@ -129,6 +198,62 @@ def zoom_search(eval_fn, n_exits, bracket=(0.05, 20.0), grid=33, rtol=1e-4, max_
     tau = np.array([taus[e][best[e]] for e in range(E)])
     return dict(tau=tau, nll_after=np.array([nlls[e][best[e]] for e in range(E)]), nll_before=nll_before,
                 at_bound=np.array([t == b_lo or t == b_hi for t in tau]), rounds=rounds)
+
+
+def coordinate_search(eval_fn, n_exits, target, init, mode="vector", sweep_rtol=1e-7, max_sweeps=50, **zoom):
+    """Deterministic search of the temperatures of exits 0..``target`` on row ``target`` of the ensemble objective:
+    ``eval_fn(tau [E] float64, vary, cand [G] float64) -> nll [E, G]`` (``ensemble_nll_grid_numpy``'s signature behind the logits).
+
+    ``mode="vector"``: sweeps over the coordinates 0..target, each step a ``zoom_search`` (keyword arguments ``zoom``) over that one
+    exit's temperature with the others held; the coordinate's current value is among the candidates of every round
+    (``zoom_search(include=)``), so no step increases the objective.  The search stops when a whole sweep improves row ``target`` by at
+    most ``sweep_rtol`` relative (``stopped_by_rule``), or after ``max_sweeps``.  ``mode="shared"``: ONE ``zoom_search`` with every exit
+    0..target in the mask — one temperature for the ensemble's members (``sweeps`` = 1, ``stopped_by_rule`` = True; the members' common ``init`` value is
+    the included candidate, and where they differ in ``init`` nothing is, so only a uniform start bounds the result by ``nll_init``).  Exits above
+    ``target`` are not members of row ``target``: they keep their ``init`` value.  ``init``: [E] or a scalar, float32-representable
+    values are kept as they are (others are rounded to float32 once).
+
+    Returns dict(tau [E], nll_init [E], nll_after [E] (every row at ``init`` / at ``tau``), trace (row ``target`` after each sweep),
+    sweeps, at_bound bool [E] (a searched coordinate ended on an end of the bracket), stopped_by_rule)."""
+    E = int(n_exits)
+    target = int(target) + (E if int(target) < 0 else 0)
+    if not 0 <= target < E:
+        raise ValueError(f"target must be an exit index of {E} exits, got {target}")
+    if mode not in ("vector", "shared"):
+        raise ValueError(f'mode must be "vector" or "shared", got {mode!r}')
+    tau = np.asarray(init, dtype=np.float64).reshape(-1).astype(np.float32).astype(np.float64)
+    tau = np.repeat(tau, E) if tau.size == 1 else tau.copy()
+    if tau.size != E or not (np.all(np.isfinite(tau)) and np.all(tau > 0)):
+        raise ValueError(f"init must hold one finite temperature > 0 per exit ({E}), got {tau.tolist()}")
+    at_bound = np.zeros(E, dtype=bool)
+
+    def rows(t):
+        return np.asarray(eval_fn(t, None, t[:1]), dtype=np.float64).reshape(E, 1)[:, 0]
+
+    def step(vary, current):
+        z = zoom_search(lambda c: np.asarray(eval_fn(tau, vary, c[0]), dtype=np.float64)[target][None], 1, include=current, **zoom)
+        return z["tau"][0], z["nll_after"][0], bool(z["at_bound"][0])
+
+    nll_init = rows(tau)
+    trace, sweeps, stopped = [], 0, False
+    if mode == "shared":
+        members = list(range(target + 1))
+        same = bool(np.all(tau[members] == tau[0]))
+        t, v, b = step(members, tau[0] if same else None)
+        tau[members], at_bound[members] = t, b
+        trace, sweeps, stopped = [float(v)], 1, True
+    else:
+        prev = float(nll_init[target])
+        while sweeps < int(max_sweeps):
+            for i in range(target + 1):
+                tau[i], v, at_bound[i] = step(i, tau[i])
+            sweeps += 1
+            trace.append(float(v))
+            if prev - v <= sweep_rtol * abs(prev):
+                stopped = True
+                break
+            prev = float(v)
+    return dict(tau=tau, nll_init=nll_init, nll_after=rows(tau), trace=np.array(trace), sweeps=sweeps, at_bound=at_bound, stopped_by_rule=stopped)
 
 
 class TemperatureScaling:
@@ -218,5 +343,63 @@ class TemperatureScaling:
         if self.result is None:
             raise RuntimeError("fit() first")
         name = f"temperature_{experiment_id}.npz"
+        np.savez(name, **{k: np.asarray(v) for k, v in self.result.items()})
+        return name
+
+
+class EnsembleTemperatureScaling(TemperatureScaling):
+    """Fits the exits' temperatures JOINTLY, to the NLL of the exit ensemble they end up in (row ``target``: the mean of exits 0..target).
+
+        ets = EnsembleTemperatureScaling(model, val_loader, gpu=0, mc_passes=10)
+        ets.fit()           # dict(tau, nll_init, nll_after, trace, sweeps, at_bound, stopped_by_rule, tau_init, nll_ones, nll_per_exit, n)
+        ets.apply()         # model.set_exit_temperature(tau): predict_ensemble and the adaptive / staged read-outs follow
+
+    The walk (``collect``), its seeds, the Masksembles counter and the ``max_logit_bytes`` budget are ``TemperatureScaling``'s; the search
+    is ``coordinate_search`` with one ``MCDEngine.ensemble_nll_grid`` launch per batch and round."""
+
+    def fit(self, target=-1, mode="vector", init="per_exit", **search):
+        """Walk + search (keyword arguments go to ``coordinate_search`` and on to ``zoom_search``).  ``init``: "per_exit" (the parent's fit
+        of every exit to its own NLL, on the same logits), "ones", or an array [E].  Returns — and keeps in ``self.result`` —
+        ``coordinate_search``'s dict plus ``tau_init`` (the start of the search), ``nll_ones`` [E] (the ensemble rows at tau = 1), ``nll_per_exit`` [E] (the ensemble rows at the
+        per-exit fit, where that fit was run) and ``n``."""
+        from ..engine import model_exits
+        batches = self.collect()
+        eng, E = self._engine, model_exits(self.model)
+
+        def eval_fn(tau, vary, cand):
+            out = None
+            cand = torch.from_numpy(np.ascontiguousarray(cand, dtype=np.float32)).to(self.device)
+            for logits, y in batches:
+                out = eng.ensemble_nll_grid(logits, y, tau, vary, cand, out=out)
+            return out.cpu().numpy()
+
+        extra = {}
+        if isinstance(init, str):
+            if init == "per_exit":
+                def per_exit_fn(tau):
+                    out = None
+                    grid = torch.from_numpy(np.ascontiguousarray(tau, dtype=np.float32)).to(self.device)
+                    for logits, y in batches:
+                        out = eng.nll_grid(logits, y, grid, out=out)
+                    return out.cpu().numpy()
+                init = zoom_search(per_exit_fn, E)["tau"]
+                extra["nll_per_exit"] = eval_fn(init, None, np.ones(1))[:, 0]
+            elif init == "ones":
+                init = np.ones(E)
+            else:
+                raise ValueError(f'init must be "per_exit", "ones" or an array, got {init!r}')
+        r = coordinate_search(eval_fn, E, target, init, mode=mode, **search)
+        r["tau_init"] = np.asarray(init, dtype=np.float64).reshape(-1)
+        r["nll_ones"] = eval_fn(np.ones(E), None, np.ones(1))[:, 0]
+        r.update(extra)
+        r["n"] = int(sum(y.numel() for _, y in batches))
+        self.result = r
+        return r
+
+    def save(self, experiment_id):
+        """Writes ``ensemble_temperature_<id>.npz`` (the result dict) and returns its name."""
+        if self.result is None:
+            raise RuntimeError("fit() first")
+        name = f"ensemble_temperature_{experiment_id}.npz"
         np.savez(name, **{k: np.asarray(v) for k, v in self.result.items()})
         return name

@@ -571,6 +571,36 @@ size_t bmi_nll_temperature_scratch_bytes(int32_t E, int32_t B, int32_t G);
 int bmi_nll_temperature_grid(const float* logits, int32_t T, int32_t E, int32_t B, int32_t C, const int32_t* labels, const float* tau_grid,
                              int32_t G, double* nll, void* scratch, size_t scratch_bytes, bmi_stream stream);
 
+/* The objective of a JOINT temperature fit of the exit ensembles on per-sample logits: row e is the NLL of the mean over exits 0..e and
+ * over the T samples of the tempered softmax (the row bmi_forward_mcd_ensemble forms, as a likelihood), for G candidate temperatures
+ * in one launch.  logits / labels as bmi_nll_temperature_grid's; tau: device fp32 [E], the current temperature vector; vary_mask: bit i
+ * set = exit i takes the candidate; tau_cand: device fp32 [G]; every temperature finite and > 0:
+ *     tau_i(g) = bit i of vary_mask ? tau_cand[g] : tau[i]
+ * — one bit is a coordinate step, all E bits one shared "ensemble temperature", no bit with G = 1 evaluates the vector tau.  nll: device
+ * float64 [E][G], ADDED TO; ALL E rows are written for every candidate (the rows below the lowest varied exit hold the same bits for
+ * every g).  All in float64, no fused multiply-add in the statistic, y = labels[b]:
+ *     z_c        = (double)l[t][i][b][c] * (1.0 / (double)tau_i(g))
+ *     a[t][i][b] = (z_y - max_c z) - log sum_c exp(z_c - max_c z)
+ *     L[i][b]    = logsumexp_t a[t][i][b]
+ *     R[0][b]    = L[0][b],   R[e][b] = logaddexp(R[e-1][b], L[e][b])        (m + log(exp(x - m) + exp(y - m)), m = max(x, y))
+ *     nll[e][g] += sum_b -( R[e][b] - log(T * (e + 1)) )
+ * — the float64 product bmi_nll_temperature_grid uses, not the heads' fp32 product, so a fit never depends on the temperature set on an
+ * engine; log-sum-exp form, no clip, finite for any finite logits.  The logits of a run of (image, sample) rows, all E exits, are
+ * staged once; an exit outside the mask costs C exponentials per row, an exit in the mask C per (candidate, row): a candidate of a
+ * coordinate step costs C per row, not E * C.  Bit-reproducible: per-image terms go to `scratch` ([E][G][B] float64,
+ * bmi_nll_ensemble_temperature_scratch_bytes = E * G * B * 8, 0 for a count below 1) and are summed over the images in a fixed order;
+ * no floating-point atomics.  No allocation, no synchronisation.  A sample count whose T * E rows exceed
+ * min(BMI_NLL_ENS_ROWS, BMI_NLL_ENS_SLAB / (C | 1)) runs in chunks of samples.
+ * BMI_ERR_INVALID (decided before any HIP call): a null pointer, a count below 1, a mask bit at or above E.  BMI_ERR_UNSUPPORTED: E > 32,
+ * or one sample's E rows do not fit the staging buffer, E * (C | 1) > BMI_NLL_ENS_SLAB.  BMI_ERR_NOMEM: scratch too small.  An error
+ * writes nothing. */
+#define BMI_NLL_ENS_SLAB 9216 /* floats of staged logits per workgroup */
+#define BMI_NLL_ENS_ROWS 192  /* (sample, exit, image) rows per staged chunk, at most */
+size_t bmi_nll_ensemble_temperature_scratch_bytes(int32_t E, int32_t B, int32_t G);
+int bmi_nll_ensemble_temperature_grid(const float* logits, int32_t T, int32_t E, int32_t B, int32_t C, const int32_t* labels, const float* tau,
+                                      uint32_t vary_mask, const float* tau_cand, int32_t G, double* nll, void* scratch, size_t scratch_bytes,
+                                      bmi_stream stream);
+
 /* Per-op-kind HIP-event timing of bmi_forward_mcd (off by default; adds two event records per
  * launch).  bmi_profile_read synchronises the recorded events and resets the accumulators. */
 int bmi_profile_enable(bmi_handle h, int32_t enable);
