@@ -85,6 +85,8 @@ _PROTOS = {
     "bmi_forward_mcd_ensemble": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_int32] +
                                  [C.c_void_p] * 8 + [C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
     "bmi_ensemble_moments": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float)] + [C.c_void_p] * 4),
+    "bmi_ensemble_moments_weighted": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float)] + [C.c_void_p] * 5),
+    "bmi_engine_set_ensemble_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
     "bmi_finalize_ensemble": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 10),
     "bmi_finalize_uncertainty": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 7),
     "bmi_forward_mcd_samples": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_int32, C.c_int32, C.c_void_p,

@@ -100,6 +100,7 @@ struct bmi_engine_s {
     std::vector<std::pair<const float*, size_t>> perm;   // (bmi_plan) Masksembles tables (device pointer of the site) -> workspace offset of the permuted copy
     std::vector<float> tau;              // bmi_engine_set_temperature: the temperatures as given ([n_exits]; empty: never set = ones)
     std::vector<float> inv_tau;          // float32(1 / (double)tau[e]) per exit, what the heads multiply by; EMPTY when off (never set, or all ones)
+    const double* ens_w = nullptr;       // bmi_engine_set_ensemble_weights: the caller's DEVICE [n_exits][n_exits] float64 (not owned), null: the equal-weight mean
     std::vector<char> staged_ok;         // (bmi_plan) per first_exit: the staged suffix order keeps every shared workspace range's live ranges apart
     // profiling
     bool profiling = false;
@@ -795,6 +796,16 @@ int bmi_engine_set_temperature(bmi_handle h, const float* tau, int32_t n_exits) 
     return BMI_OK;
 }
 
+// The weights of the exit ensembles (caller-owned device buffer, used as given), or NULL: off — the launches are then the unweighted
+// instantiations and every output keeps its bits.  Read at launch time: captured graphs keep what was set at capture.
+int bmi_engine_set_ensemble_weights(bmi_handle h, const double* W_device, int32_t n_exits) {
+    if (!h) return BMI_ERR_INVALID;
+    if (!W_device) { h->ens_w = nullptr; return BMI_OK; }
+    if (n_exits != h->n_exits) return BMI_ERR_INVALID;
+    h->ens_w = W_device;
+    return BMI_OK;
+}
+
 int bmi_engine_get_temperature(bmi_handle h, float* tau, int32_t capacity) {
     if (!h || !tau || capacity < h->n_exits) return BMI_ERR_INVALID;
     for (int i = 0; i < h->n_exits; ++i) tau[i] = h->tau.empty() ? 1.f : h->tau[i];
@@ -1468,7 +1479,7 @@ int forward_folded(bmi_engine_s* e, const Pass& p, int t_begin, int t_count, con
         if (rc != BMI_OK) return rc;
         if (!ens) continue;
         rc = launch_ensemble_moments(ens->scratch, tc, e->n_exits, p.B, e->out_dim, e->inv_tau.empty() ? nullptr : e->inv_tau.data(), ens->Q1,
-                                     ens->Q2, ens->QH, p.stream);
+                                     ens->Q2, ens->QH, p.stream, nullptr, 0, nullptr, e->ens_w);
         if (rc != BMI_OK) return rc;
     }
     return BMI_OK;
@@ -1682,7 +1693,7 @@ static int exit_staged(bmi_handle h, const float* x_nchw, int32_t batch, int32_t
         const int rce = launch_exit_counts(exit_of_image, batch, lists[0], s);
         if (rce != BMI_OK) return rce;
         return launch_ensemble_moments(ens->scratch, t_count, h->n_exits, batch, h->out_dim, h->inv_tau.empty() ? nullptr : h->inv_tau.data(),
-                                       ens->Q1, ens->Q2, ens->QH, s, nullptr, 0, lists[0]);
+                                       ens->Q1, ens->Q2, ens->QH, s, nullptr, 0, lists[0], h->ens_w);
     };
     const int* act = nullptr;      // null: every image is still active (stage 0: bmi_forward_mcd's launches)
     const int* rows = nullptr;
@@ -1705,7 +1716,7 @@ static int exit_staged(bmi_handle h, const float* x_nchw, int32_t batch, int32_t
             if (op->d.kind == BMI_OP_HEAD && (op->d.out != e || e == last)) active_after[op->d.out] = bc;
         if (e == last) break;
         rc = launch_exit_rule_decide(S1, batch, h->out_dim, t_count, rule->threshold, rule->criterion == BMI_EXIT_MARGIN, rule->ensemble, act, bc,
-                                     lists[cur], count_dev, exit_of_image, e, s);
+                                     lists[cur], count_dev, exit_of_image, e, s, h->ens_w, h->n_exits);
         if (rc != BMI_OK) return rc;
         int n_active = 0;
         if (hipMemcpyAsync(&n_active, count_dev, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
@@ -1792,7 +1803,7 @@ static int adaptive(bmi_handle h, const float* x_nchw, int32_t batch, int32_t im
             ProfScope prof(h, BMI_PROFILE_ENSEMBLE, s);
             prof.r.images = tc * bc;
             rc = launch_ensemble_moments(ens->scratch, tc, h->n_exits, batch, h->out_dim, h->inv_tau.empty() ? nullptr : h->inv_tau.data(), ens->Q1,
-                                         ens->Q2, ens->QH, s, imap, bc);
+                                         ens->Q2, ens->QH, s, imap, bc, nullptr, h->ens_w);
             if (rc != BMI_OK) return rc;
         }
         // the stop rule over the still-active images, on the device; the host only learns how many go on
@@ -1893,8 +1904,8 @@ int bmi_finalize_ensemble_per_image(int32_t n_exits, int32_t batch, int32_t out_
                                               mutual_info, nonfinite, (hipStream_t)stream);
 }
 
-int bmi_ensemble_moments(const float* logits, int32_t T, int32_t E, int32_t B, int32_t C, const float* tau, double* Q1, double* Q2, double* QH,
-                         bmi_stream stream) {
+static int ensemble_moments_entry(const float* logits, int32_t T, int32_t E, int32_t B, int32_t C, const float* tau, const double* W, double* Q1,
+                                  double* Q2, double* QH, bmi_stream stream) {
     if (!logits || !Q1 || !Q2 || !QH || T < 1 || E < 1 || B < 1 || C < 1) return BMI_ERR_INVALID;
     if (!ensemble_takes(E, C)) return BMI_ERR_UNSUPPORTED;
     float inv[BMI_ENS_MAX_EXITS];
@@ -1904,7 +1915,18 @@ int bmi_ensemble_moments(const float* logits, int32_t T, int32_t E, int32_t B, i
             inv[e] = (float)(1.0 / (double)tau[e]);       // (bmi_engine_set_temperature's rounding)
             if (!(inv[e] > 0.f) || !std::isfinite(inv[e])) return BMI_ERR_INVALID;
         }
-    return launch_ensemble_moments(logits, T, E, B, C, tau ? inv : nullptr, Q1, Q2, QH, (hipStream_t)stream);
+    return launch_ensemble_moments(logits, T, E, B, C, tau ? inv : nullptr, Q1, Q2, QH, (hipStream_t)stream, nullptr, 0, nullptr, W);
+}
+
+int bmi_ensemble_moments(const float* logits, int32_t T, int32_t E, int32_t B, int32_t C, const float* tau, double* Q1, double* Q2, double* QH,
+                         bmi_stream stream) {
+    return ensemble_moments_entry(logits, T, E, B, C, tau, nullptr, Q1, Q2, QH, stream);
+}
+
+int bmi_ensemble_moments_weighted(const float* logits, int32_t T, int32_t E, int32_t B, int32_t C, const float* tau, const double* W_device,
+                                  double* Q1, double* Q2, double* QH, bmi_stream stream) {
+    if (!W_device) return BMI_ERR_INVALID;
+    return ensemble_moments_entry(logits, T, E, B, C, tau, W_device, Q1, Q2, QH, stream);
 }
 
 size_t bmi_nll_temperature_scratch_bytes(int32_t E, int32_t B, int32_t G) {

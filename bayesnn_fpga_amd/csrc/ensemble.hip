@@ -33,11 +33,17 @@ struct EnsTau { float inv[BMI_ENS_MAX_EXITS]; };
 // batch (list null: b = i) and on its first n_e[b] exits only (n_e null: all E) — the running exit sum is cut there, so the rows
 // e < n_e[b] are the full form's bits; `logits` and the sums keep the ORIGINAL image index, rows of other images and of later exits are
 // neither read nor written.  Both lookups are the same for the whole workgroup.  Not ROWS: the code as it was.
-template <bool ROWS>
+// WEIGHTED (bmi_engine_set_ensemble_weights, bmi_ensemble_moments_weighted): q_te = ((W[e][0] p_t0 + W[e][1] p_t1) + ...) + W[e][e] p_te,
+// W device float64 [E_all][E_all] row-major, used as given (no renormalisation): every product rounded, added in exit order from 0.0.
+// Phase B first turns the rows of pq into p in place, then forms q_e for e DESCENDING: row e reads the rows i <= e, which are still p.
+// e and i are the same for the whole wave, so a weight is one scalar load (the 63.6 KB of LDS leave no room for a [32][32] table); under
+// ROWS only the rows e < n_e[b] of W are read.  Not WEIGHTED: the code as it was, W is never read.
+template <bool ROWS, bool WEIGHTED>
 __global__ __launch_bounds__(ENS_THREADS) void ensemble_moments_kernel(const float* __restrict__ logits, int T, int E_all, int B, int C, int CS,
                                                                        int TS, int L, EnsTau tau, double* __restrict__ Q1,
                                                                        double* __restrict__ Q2, double* __restrict__ QH,
-                                                                       const int* __restrict__ list, const int* __restrict__ n_e) {
+                                                                       const int* __restrict__ list, const int* __restrict__ n_e,
+                                                                       const double* __restrict__ W) {
 #pragma clang fp contract(off)
     __shared__ double pq[ENS_SLAB];                      // [row][CS], row = tl * E + e: exp(z - max), then q
     __shared__ double ql[ENS_SLAB];                      // q log q
@@ -76,6 +82,18 @@ __global__ __launch_bounds__(ENS_THREADS) void ensemble_moments_kernel(const flo
         __syncthreads();
         for (int i = tid; i < tn * C; i += ENS_THREADS) {
             const int tl = i / C, c = i - tl * C;
+            if (WEIGHTED) {
+                double* col = pq + tl * E * CS + c;          // this thread's (sample, class) column: element e at col[e * CS]
+                for (int e = 0; e < E; ++e) col[e * CS] = col[e * CS] / row_sum[tl * E + e];
+                for (int e = E - 1; e >= 0; --e) {
+                    const double* w = W + (size_t)e * E_all;
+                    double q = 0.0;
+                    for (int x = 0; x <= e; ++x) q = q + w[x] * col[x * CS];
+                    col[e * CS] = q;
+                    ql[(tl * E + e) * CS + c] = q > 0.0 ? q * log(q) : (q == q ? 0.0 : q);
+                }
+                continue;
+            }
             double acc = 0.0;
             for (int e = 0; e < E; ++e) {
                 const int r = tl * E + e;
@@ -119,8 +137,15 @@ bool ensemble_takes(int E, int C) {
     return E >= 1 && C >= 1 && E <= BMI_ENS_MAX_EXITS && C <= BMI_ENS_MAX_CLASSES && E * (C | 1) <= ENS_SLAB;
 }
 
+template <bool ROWS, bool WEIGHTED>
+static void launch_ens(unsigned grid, hipStream_t s, const float* logits, int T, int E, int B, int C, int CS, int TS, int L, const EnsTau& tau,
+                       double* Q1, double* Q2, double* QH, const int* list, const int* n_e, const double* W) {
+    hipLaunchKernelGGL((ensemble_moments_kernel<ROWS, WEIGHTED>), dim3(grid), dim3(ENS_THREADS), 0, s, logits, T, E, B, C, CS, TS, L, tau, Q1, Q2,
+                       QH, list, n_e, W);
+}
+
 int launch_ensemble_moments(const float* logits, int T, int E, int B, int C, const float* inv_tau, double* Q1, double* Q2, double* QH,
-                            hipStream_t s, const int* list, int Bc, const int* n_e) {
+                            hipStream_t s, const int* list, int Bc, const int* n_e, const double* W) {
     if (T < 1 || B < 1 || (list && (Bc < 1 || Bc > B))) return BMI_ERR_INVALID;
     if (!ensemble_takes(E, C)) return BMI_ERR_UNSUPPORTED;
     const int CS = C | 1;                                // odd row stride
@@ -129,12 +154,12 @@ int launch_ensemble_moments(const float* logits, int T, int E, int B, int C, con
     while (L < C && L < 64) L <<= 1;
     EnsTau tau;
     for (int e = 0; e < BMI_ENS_MAX_EXITS; ++e) tau.inv[e] = (inv_tau && e < E) ? inv_tau[e] : 1.f;
-    if (list || n_e)
-        hipLaunchKernelGGL((ensemble_moments_kernel<true>), dim3((unsigned)(list ? Bc : B)), dim3(ENS_THREADS), 0, s, logits, T, E, B, C, CS, TS, L,
-                           tau, Q1, Q2, QH, list, n_e);
-    else
-        hipLaunchKernelGGL((ensemble_moments_kernel<false>), dim3((unsigned)B), dim3(ENS_THREADS), 0, s, logits, T, E, B, C, CS, TS, L, tau, Q1, Q2,
-                           QH, (const int*)nullptr, (const int*)nullptr);
+    const bool rows = list || n_e;
+    const unsigned grid = (unsigned)(list ? Bc : B);
+    if (rows && W) launch_ens<true, true>(grid, s, logits, T, E, B, C, CS, TS, L, tau, Q1, Q2, QH, list, n_e, W);
+    else if (rows) launch_ens<true, false>(grid, s, logits, T, E, B, C, CS, TS, L, tau, Q1, Q2, QH, list, n_e, nullptr);
+    else if (W) launch_ens<false, true>(grid, s, logits, T, E, B, C, CS, TS, L, tau, Q1, Q2, QH, nullptr, nullptr, W);
+    else launch_ens<false, false>(grid, s, logits, T, E, B, C, CS, TS, L, tau, Q1, Q2, QH, nullptr, nullptr, nullptr);
     BMI_CHECK_LAUNCH();
     return BMI_OK;
 }

@@ -169,9 +169,10 @@ int launch_finalize_per_image(int n_exits, int batch, int C, const int* t_used, 
                               hipStream_t s);
 // dst[r][c] = src[(cnt0 + r * stride) % m][c], r < m (a Masksembles table in the order a strided walk visits it)
 int launch_mask_permute(const float* src, float* dst, int m, int c, int cnt0, int stride, hipStream_t s);
-// bmi_forward_mcd_exit_staged: the bmi_exit_rule test at exit e on S1 [E][B][C] of t_total samples (margin: BMI_EXIT_MARGIN; ensemble: exits 0..e)
+// bmi_forward_mcd_exit_staged: the bmi_exit_rule test at exit e on S1 [E][B][C] of t_total samples (margin: BMI_EXIT_MARGIN; ensemble: exits 0..e,
+// weighted by row e of W — device float64, n_exits doubles per row — when W is not null: bmi_engine_set_ensemble_weights)
 int launch_exit_rule_decide(const double* S1, int B, int C, int t_total, double thr, int margin, int ensemble, const int* in, int bc, int* out,
-                            int* count, int* exit_of, int e, hipStream_t s);
+                            int* count, int* exit_of, int e, hipStream_t s, const double* W = nullptr, int n_exits = 0);
 int launch_expand_rows(const int* active, int bc, int batch, int tc, int* rows, hipStream_t s);   // rows[tl*bc + i] = tl*batch + active[i]
 int launch_finalize(int64_t n, int t_total, const double* S1, const double* S2, const double* SL, double* mean,
                     double* var, double* lm, int* nonfinite, hipStream_t s);
@@ -194,8 +195,10 @@ int launch_nll_ensemble_temperature_grid(const float* logits, int T, int E, int 
 bool ensemble_takes(int E, int C);
 // list / Bc / n_e (device int32, each null: not used): the launch covers the Bc images list[0 .. Bc-1] of the batch only, and of image b only
 // its first n_e[b] exits; every row that is computed holds the plain launch's bits, the other rows are neither read nor written
+// W (device float64 [E][E] row-major, null: the equal-weight mean above): q_te = sum_{i<=e} W[e][i] p_ti in exit order, the weights as given;
+// of image b only the rows e < n_e[b] of W are read (bmi_engine_set_ensemble_weights, bmi_ensemble_moments_weighted)
 int launch_ensemble_moments(const float* logits, int T, int E, int B, int C, const float* inv_tau, double* Q1, double* Q2, double* QH,
-                            hipStream_t s, const int* list = nullptr, int Bc = 0, const int* n_e = nullptr);
+                            hipStream_t s, const int* list = nullptr, int Bc = 0, const int* n_e = nullptr, const double* W = nullptr);
 int launch_exit_counts(const int* exit_of, int n, int* n_e, hipStream_t s);      // n_e[b] = exit_of[b] + 1 (staged exit: the exits image b ran)
 // per (exit, image): mean / var of Q1 / Q2, the entropy of the mean, QH / T and their difference (bmi_finalize_ensemble)
 int launch_finalize_ensemble(int n_rows, int C, int t_total, const double* Q1, const double* Q2, const double* QH, double* mean, double* var,

@@ -610,13 +610,19 @@ int launch_exit_decide(const double* S1e, int C, int t_total, double thr, const 
 
 // Staged early exit (bmi_forward_mcd_exit_staged): the same compaction with the rule of bmi_exit_rule, float64 as the header states
 // it: p_c = S1[e][b][c] / t (ensemble: the exits 0..e's p_c summed in exit order, / (e + 1)); confidence = max_c p_c, margin = top-1
-// minus top-2 (0 on a tie).  No contraction into fma: a numpy restatement gets the same statistic.
-__device__ double exit_rule_stat(const double* __restrict__ S1, int B, int C, int b, int e, double t, int margin, int ensemble) {
+// minus top-2 (0 on a tie).  No contraction into fma: a numpy restatement gets the same statistic.  w (ensemble only; row e of the weights
+// of bmi_engine_set_ensemble_weights, null: the equal mean, the expression as it was): p_c = sum_{x<=e} w[x] * (S1[x][b][c] / t), each
+// product rounded, added in exit order from 0.0.
+__device__ double exit_rule_stat(const double* __restrict__ S1, int B, int C, int b, int e, double t, int margin, int ensemble,
+                                 const double* __restrict__ w) {
 #pragma clang fp contract(off)
     double m1 = -1.0, m2 = -1.0;
     for (int c = 0; c < C; ++c) {
         double p;
-        if (ensemble) {
+        if (ensemble && w) {
+            p = 0.0;
+            for (int x = 0; x <= e; ++x) p = p + w[x] * (S1[((size_t)x * B + b) * C + c] / t);
+        } else if (ensemble) {
             double acc = 0.0;
             for (int x = 0; x <= e; ++x) acc = acc + S1[((size_t)x * B + b) * C + c] / t;
             p = acc / (double)(e + 1);
@@ -631,7 +637,8 @@ __device__ double exit_rule_stat(const double* __restrict__ S1, int B, int C, in
 
 __global__ __launch_bounds__(256) void exit_rule_decide_kernel(const double* __restrict__ S1, int B, int C, double t, double thr, int margin,
                                                                int ensemble, const int* __restrict__ in, int bc, int* __restrict__ out,
-                                                               int* __restrict__ count, int* __restrict__ exit_of, int e) {
+                                                               int* __restrict__ count, int* __restrict__ exit_of, int e,
+                                                               const double* __restrict__ w) {
     __shared__ int scan[256];
     __shared__ int base_s;
     const int tid = threadIdx.x;
@@ -642,7 +649,7 @@ __global__ __launch_bounds__(256) void exit_rule_decide_kernel(const double* __r
         int keep = 0, b = -1;
         if (i < bc) {
             b = in ? in[i] : i;
-            if (exit_rule_stat(S1, B, C, b, e, t, margin, ensemble) > thr) exit_of[b] = e;
+            if (exit_rule_stat(S1, B, C, b, e, t, margin, ensemble, w) > thr) exit_of[b] = e;
             else keep = 1;
         }
         scan[tid] = keep;
@@ -662,10 +669,11 @@ __global__ __launch_bounds__(256) void exit_rule_decide_kernel(const double* __r
 }
 
 int launch_exit_rule_decide(const double* S1, int B, int C, int t_total, double thr, int margin, int ensemble, const int* in, int bc, int* out,
-                            int* count, int* exit_of, int e, hipStream_t s) {
+                            int* count, int* exit_of, int e, hipStream_t s, const double* W, int n_exits) {
     if (!S1 || !out || !count || !exit_of || bc <= 0 || bc > B || C <= 0 || t_total <= 0 || e < 0 || in == out) return BMI_ERR_INVALID;
+    if (W && e >= n_exits) return BMI_ERR_INVALID;
     hipLaunchKernelGGL(exit_rule_decide_kernel, dim3(1), dim3(256), 0, s, S1, B, C, (double)t_total, thr, margin, ensemble, in, bc, out, count,
-                       exit_of, e);
+                       exit_of, e, (W && ensemble) ? W + (size_t)e * n_exits : (const double*)nullptr);
     BMI_CHECK_LAUNCH();
     return BMI_OK;
 }

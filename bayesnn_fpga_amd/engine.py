@@ -325,6 +325,37 @@ def check_temperature(tau, n_exits):
     return [float(v) for v in vals]
 
 
+def check_ensemble_weights(w, n_exits):
+    """The weights of the exit ensembles as a float64 array [E, E] (row e: the weights of the ensemble of exits 0..e), or None (off: the
+    equal-weight mean).  ``w``: None, an [E] vector — one non-negative weight per exit, expanded as W[e][i] = w_i / fsum(w[:e+1]), every
+    prefix sum > 0 — or an [E, E] matrix.  Raises ValueError for any other shape, a negative or non-finite entry, a nonzero entry above the
+    diagonal, or a row whose (exactly rounded) sum is further than 1e-12 from 1.  Host only."""
+    if w is None:
+        return None
+    import math
+    E = int(n_exits)
+    raw = np.array(w.detach().cpu().numpy() if isinstance(w, torch.Tensor) else w, dtype=np.float64)
+    if not np.all(np.isfinite(raw)) or np.any(raw < 0):
+        raise ValueError("ensemble weights: every entry must be finite and >= 0")
+    if raw.shape == (E,):
+        W = np.zeros((E, E), dtype=np.float64)
+        for e in range(E):
+            tot = math.fsum(raw[:e + 1])
+            if not tot > 0:
+                raise ValueError(f"ensemble weights: the weights of exits 0..{e} sum to {tot}, every prefix sum must be > 0")
+            W[e, :e + 1] = raw[:e + 1] / tot
+    elif raw.shape == (E, E):
+        W = np.ascontiguousarray(raw)
+    else:
+        raise ValueError(f"ensemble weights: expected [{E}] or [{E}, {E}] for {E} exits, got {list(raw.shape)}")
+    if np.any(np.triu(W, 1) != 0):
+        raise ValueError("ensemble weights: W[e][i] must be 0 for i > e (the ensemble of exits 0..e has no later member)")
+    sums = [math.fsum(row) for row in W]
+    if not all(abs(v - 1.0) <= 1e-12 for v in sums):
+        raise ValueError(f"ensemble weights: every row must sum to 1 within 1e-12, got {sums}")
+    return W
+
+
 def vary_mask(vary, n_exits):
     """``vary`` of ensemble_nll_grid (an exit index, an iterable of indices, or None) as the bit mask bmi_nll_ensemble_temperature_grid
     takes; raises ValueError for an index outside [0, n_exits)."""
@@ -514,10 +545,35 @@ class MCDEngine(CompiledGraph):
         # the non-finite counter of bmi_finalize_checked: allocated HERE, never lazily — a first finalize() inside a hipGraph capture
         # (BatchesInFlight.predict_graphed) would otherwise allocate it from the graph's private pool and re-zero it on every replay
         self._nonfinite = torch.zeros(1, dtype=torch.int32, device=device)
+        # weighted exit ensembles: like the temperature, a model that carries weights (EngineModelMixin.set_exit_ensemble_weights,
+        # train/calibration.py: EnsembleWeights) hands them to every engine built from it
+        self._ens_w_keep = []
+        self.set_ensemble_weights(getattr(model, "exit_ensemble_weights", None))
+
+    ensemble_weights = None       # float64 [E, E] on the host, or None: the equal-weight mean (set_ensemble_weights)
 
     def close(self):
         self.__dict__.pop("_ens_scratch", None)      # (accumulate_ensemble's chunk of per-sample logits)
-        super().close()
+        super().close()                              # (the handle goes first: nothing reads the weight buffers any more)
+        self.__dict__.pop("_ens_w_keep", None)
+
+    def set_ensemble_weights(self, w):
+        """The weights of the exit ensembles (bmi_engine_set_ensemble_weights): ``w`` as ``check_ensemble_weights`` takes it — None (off),
+        an [E] vector or an [E, E] matrix.  From the next launch on every consumer of the ensemble is the WEIGHTED one's, q_te = sum_{i<=e}
+        W[e][i] p_ti per sample in exit order: ``predict_ensemble`` / ``accumulate_ensemble``, ``predict_adaptive(ensemble=True)`` with its
+        ``stop_on="ensemble"`` rule, ``predict_early_exit``'s ``ensemble=True`` rule, ``ensemble_readout`` and ``best_preds``.  mean, var and
+        the per-exit entropies never depend on it; ``predict_with_exit`` (the older entry) has no ensemble rule.  Off, the engine launches the
+        unweighted kernels: the bits of an engine that never had weights.  The matrix lives in a small device buffer the engine keeps; a
+        hipGraph captured earlier keeps the weights it was captured with (``model.set_exit_ensemble_weights`` drops the pipes that hold such graphs)."""
+        W = check_ensemble_weights(w, self.n_exits)
+        if W is None:
+            rc = self.lib.bmi_engine_set_ensemble_weights(self.handle, None, 0)
+        else:
+            buf = torch.from_numpy(W).to(self.device)
+            self._ens_w_keep.append(buf)             # never freed before close(): a captured launch may still hold an earlier pointer
+            rc = self.lib.bmi_engine_set_ensemble_weights(self.handle, C.c_void_p(buf.data_ptr()), self.n_exits)
+        _lib.check(rc, "bmi_engine_set_ensemble_weights")
+        self.ensemble_weights = W
 
     # ---- the path ------------------------------------------------------------------------------
     def _stream(self):
@@ -740,16 +796,19 @@ class MCDEngine(CompiledGraph):
         self.accumulate_ensemble(x, S, H, Q, QH, t_begin, T, seed, cnt0)
         return self.finalize_ensemble(S, H, Q, QH, T)
 
-    def ensemble_moments(self, logits, tau=None, out=None, t_before=0):
+    def ensemble_moments(self, logits, tau=None, out=None, t_before=0, weights=None):
         """The exit-ensemble read-out of per-sample logits the caller holds (bmi_ensemble_moments + bmi_finalize_ensemble): ``logits`` fp32
         [T, E, B, C] on the engine's device (``forward_samples``), ``tau`` None, a scalar or E temperatures (independent of the one set on
         this engine).  Returns the five ``ens_*`` entries of ``finalize_ensemble`` plus the sums ``Q`` [2, E, B, C] and ``QH`` [E, B];
         ``out=(Q, QH)`` ADDS into the sums of earlier calls that held ``t_before`` samples — the same bits as one call on all of them —
-        and the results describe all ``t_before + T``.  ``train.uncertainty.decompose_ensemble_logits`` is the host restatement."""
+        and the results describe all ``t_before + T``.  ``weights`` (``check_ensemble_weights``: None, [E] or [E, E]; independent of the ones
+        set on this engine): the weighted ensembles, bmi_ensemble_moments_weighted.  ``train.uncertainty.decompose_ensemble_logits`` is the
+        host restatement."""
         if logits.dim() != 4 or logits.dtype != torch.float32 or not logits.is_contiguous() or logits.device != self.device:
             raise ValueError(f"logits must be contiguous float32 [T, E, B, C] on {self.device}")
         T, E, B, Cd = logits.shape
         tau = check_temperature(tau, E)
+        W = check_ensemble_weights(weights, E)
         if out is None:
             Q = torch.zeros(2, E, B, Cd, dtype=torch.float64, device=self.device)
             QH = torch.zeros(E, B, dtype=torch.float64, device=self.device)
@@ -758,10 +817,16 @@ class MCDEngine(CompiledGraph):
             if tuple(Q.shape) != (2, E, B, Cd) or tuple(QH.shape) != (E, B) or Q.dtype != torch.float64 or QH.dtype != torch.float64 or \
                     not Q.is_contiguous() or not QH.is_contiguous() or Q.device != self.device or QH.device != self.device:
                 raise ValueError("out must be contiguous float64 (Q [2, E, B, C], QH [E, B]) on the engine's device")
+        tau_c = None if tau is None else (C.c_float * E)(*tau)
         with torch.cuda.device(self.device):
-            rc = self.lib.bmi_ensemble_moments(logits.data_ptr(), T, E, B, Cd, None if tau is None else (C.c_float * E)(*tau), Q[0].data_ptr(),
-                                               Q[1].data_ptr(), QH.data_ptr(), self._stream())
-        _lib.check(rc, "bmi_ensemble_moments")
+            if W is None:
+                rc = self.lib.bmi_ensemble_moments(logits.data_ptr(), T, E, B, Cd, tau_c, Q[0].data_ptr(), Q[1].data_ptr(), QH.data_ptr(),
+                                                   self._stream())
+            else:
+                w_dev = torch.from_numpy(W).to(self.device)      # (freed in stream order behind the launch that reads it)
+                rc = self.lib.bmi_ensemble_moments_weighted(logits.data_ptr(), T, E, B, Cd, tau_c, w_dev.data_ptr(), Q[0].data_ptr(),
+                                                            Q[1].data_ptr(), QH.data_ptr(), self._stream())
+        _lib.check(rc, "bmi_ensemble_moments" if W is None else "bmi_ensemble_moments_weighted")
         r = self._finalize_ensemble_sums(Q, QH, int(t_before) + T)
         r.update(Q=Q, QH=QH)
         return r
@@ -869,7 +934,15 @@ class MCDEngine(CompiledGraph):
             at = exit_layer.long()
             r["best_ens"] = {k: r["ens_" + k][at, idx] for k in ("mean", "var", "pred_entropy", "exp_entropy", "mutual_info")}
         p = r["mean"]
-        if ensemble:          # the mean of exits 0..e, summed in exit order
+        if ensemble and self.ensemble_weights is not None:      # the weighted mean of exits 0..e, in exit order (the rule's p)
+            W, rows = self.ensemble_weights, []
+            for e in range(self.n_exits):
+                acc = torch.zeros_like(p[0])
+                for i in range(e + 1):
+                    acc = acc + float(W[e, i]) * p[i]
+                rows.append(acc)
+            p = torch.stack(rows)
+        elif ensemble:        # the mean of exits 0..e, summed in exit order
             p = p.cumsum(0) / torch.arange(1, self.n_exits + 1, dtype=torch.float64, device=self.device).view(-1, 1, 1)
         r["best_preds"] = p[exit_layer.long(), idx]
         # images that ran stage k: all for stage 0, then those still active after exit first_exit + k - 1's test

@@ -25,6 +25,7 @@ class EngineModelMixin:
     auto_candidates = AUTO_CANDIDATES
     auto_tol = AUTO_TOL
     exit_temperature = None   # per-exit softmax temperatures (a plain list of floats: survives torch.save(model)), or None: off — set_exit_temperature
+    exit_ensemble_weights = None   # the weights of the exit ensembles (a plain float64 array [E, E]: survives torch.save(model)), or None: the equal mean — set_exit_ensemble_weights
 
     def _init_engine_state(self):
         self.mc_seed = 0      # Philox key of the Monte-Carlo stream (csrc/philox.h)
@@ -68,6 +69,18 @@ class EngineModelMixin:
         were all made under the other softmax and are dropped — the next use rebuilds them (and re-decides "auto") under this one."""
         from ..engine import check_temperature, model_exits
         self.exit_temperature = check_temperature(tau, model_exits(self))
+        self._drop_engines()
+
+    def set_exit_ensemble_weights(self, w):
+        """The weights of the exit ensembles of everything the engines compute from this model (``MCDEngine.set_ensemble_weights``: the
+        ensemble read-out of ``predict_ensemble``, of adaptive sampling and of staged early exit, and the two decisions that read the ensemble;
+        never the per-exit results): ``w`` = None (off: the equal-weight mean), one weight per exit (expanded to W[e][i] = w_i / sum(w[:e+1]))
+        or an [E, E] matrix of rows that sum to 1; ``train.calibration.EnsembleWeights`` fits it on a validation split.  Stored on the
+        model as a plain float64 array, and treated like ``set_exit_temperature``: compiled engines and pipes with their captured graphs
+        hold the other instantiation and are dropped — the next use rebuilds them under these weights.  ``FullAnalysis``'s
+        ``ensemble_preds`` and ``evaluate()`` keep the reference's equal mean: they are the reference's file formats."""
+        from ..engine import check_ensemble_weights, model_exits
+        self.exit_ensemble_weights = check_ensemble_weights(w, model_exits(self))
         self._drop_engines()
 
     def __getstate__(self):

@@ -27,6 +27,21 @@ evaluated on the device for a grid of candidates of one coordinate (or of one sh
 * ``ensemble_nll_grid_numpy`` — float64 restatement of that objective.
 * ``coordinate_search``  — coordinate descent (``zoom_search`` per coordinate) or one shared temperature, on row ``target``.
 * ``EnsembleTemperatureScaling`` — the loader-level joint fit, on the same walk as ``TemperatureScaling``.
+
+Equal weights are the wrong prior where the early exits are much weaker than the late ones.  The WEIGHTED exit ensemble is
+q_te = sum_{i<=e} W[e][i] p_ti (``MCDEngine.set_ensemble_weights``); its T-mean is sum_i W[e][i] mean_i, so the likelihood of a weight row
+depends only on the table A[i][n] = mean_t p_{t,i,n}(y_n) — the label's entry of the T-mean softmax ``predict`` already returns — and
+
+    nll_e(w) = sum_n -log( sum_{i<=e} w_i A[i][n] )
+
+is convex in w: EM on the [E, N] table is exact and monotone, runs on the host, and keeps no per-sample logits (no ``max_logit_bytes``).
+
+* ``mixture_weights_em`` — the EM iteration for one row.
+* ``EnsembleWeights``    — the loader-level fit: the walk of ``TemperatureScaling``, the table gathered on the device, EM per row.
+
+THE ORDER: fit the temperatures first (``TemperatureScaling`` or ``EnsembleTemperatureScaling``), ``apply()`` them, then fit the weights AT
+those temperatures — the members are then fixed and the problem is convex.  The joint temperature fit's objective stays the equal-weight
+ensemble's; a joint fit of weights and temperatures is not built.
 """
 import numpy as np
 import torch
@@ -401,5 +416,130 @@ class EnsembleTemperatureScaling(TemperatureScaling):
         if self.result is None:
             raise RuntimeError("fit() first")
         name = f"ensemble_temperature_{experiment_id}.npz"
+        np.savez(name, **{k: np.asarray(v) for k, v in self.result.items()})
+        return name
+
+
+# ---- the weights of the exit ensembles -----------------------------------------------------------------------------------------------
+_MIX_FLOOR = 1e-300      # a sample whose label has probability 0 under every member: its mixture is floored here, the NLL stays finite
+
+
+def _mixture(A, w):
+    """max(sum_i w_i A_i, 1e-300) [N], the members added in order (no BLAS: the same bits for the same table wherever it lies in memory)."""
+    mix = np.zeros(A.shape[1], dtype=np.float64)
+    for i in range(A.shape[0]):
+        mix = mix + w[i] * A[i]
+    return np.maximum(mix, _MIX_FLOOR)
+
+
+def mixture_nll(A, w):
+    """sum_n -log(max(w @ A, 1e-300)) for a table ``A`` [k, N] of member likelihoods and weights ``w`` [k], float64."""
+    return float(-np.log(_mixture(np.asarray(A, dtype=np.float64), np.asarray(w, dtype=np.float64))).sum())
+
+
+def mixture_weights_em(A, rtol=1e-12, max_iter=100000):
+    """The maximum-likelihood weights of a mixture with FIXED members: ``A`` [k, N], A[i][n] >= 0 the likelihood of sample n under member
+    i.  Starts uniform and iterates  w <- w * mean_n(A / (w @ A))  (the EM step; the NLL is convex in w, every step lowers it and keeps
+    sum(w) = 1 — renormalised by the exactly rounded sum against drift) until a step gains <= rtol * |NLL|; a step that would RAISE the
+    NLL (rounding, at the optimum) is not taken.  Returns dict(w [k], nll, nll_uniform, trace — the NLL after every accepted step, first
+    entry the uniform start: non-increasing —, iterations, converged).  One member returns w = [1.]."""
+    import math
+    A = np.ascontiguousarray(A, dtype=np.float64)
+    if A.ndim != 2 or A.shape[0] < 1 or A.shape[1] < 1:
+        raise ValueError("A must be [k, N] with k >= 1 members and N >= 1 samples")
+    if not np.all(np.isfinite(A)) or np.any(A < 0):
+        raise ValueError("A: every likelihood must be finite and >= 0")
+    k = A.shape[0]
+    w = np.full(k, 1.0 / k)
+    mix = _mixture(A, w)
+    nll = float(-np.log(mix).sum())
+    trace, converged, it = [nll], False, 0
+    for it in range(1, int(max_iter) + 1):
+        w_new = w * (A / mix).mean(axis=1)
+        w_new = w_new / math.fsum(w_new)
+        mix_new = _mixture(A, w_new)
+        nll_new = float(-np.log(mix_new).sum())
+        gain = nll - nll_new
+        if gain >= 0:
+            w, mix, nll = w_new, mix_new, nll_new
+            trace.append(nll)
+        if gain <= rtol * abs(nll):
+            converged = True
+            break
+    return dict(w=w, nll=nll, nll_uniform=trace[0], trace=np.array(trace), iterations=it, converged=converged)
+
+
+class EnsembleWeights:
+    """Fits the weights of the exit ensembles on a labelled (validation) loader, by maximum likelihood per row.
+
+        ew = EnsembleWeights(model, val_loader, gpu=0, mc_passes=10)
+        ew.fit()            # dict(weights [E, E], nll_uniform, nll_after, nll_per_exit [E] each, iterations, converged, n)
+        ew.apply()          # model.set_exit_ensemble_weights(W): predict_ensemble, the adaptive / staged read-outs and decisions follow
+
+    The walk is ``TemperatureScaling``'s — batch k under the Philox seed ``seed + k`` and the Masksembles counter FullAnalysis' walk would
+    use, the model's own state left where it was — but it keeps only A[e][n] = mean[e, n, y_n], the label's entry of ``predict``'s T-mean
+    softmax, gathered on the device: E x N float64, no per-sample logits and no ``max_logit_bytes``.  The members are as tempered by the
+    temperature currently set on the model: fit and ``apply()`` the temperatures FIRST, then the weights at those temperatures.  Row e
+    of the result is ``mixture_weights_em`` on rows 0..e of the table (row 0 is [1.])."""
+
+    def __init__(self, model, val_loader, gpu=0, mc_passes=10, seed=0):
+        self.model, self.loader, self.gpu = model, val_loader, gpu
+        self.mc_passes, self.seed = int(mc_passes), int(seed)
+        self.device = get_device(gpu)
+        self.result = None
+
+    def _engine_for(self, x):
+        return self.model.engine(self.device, max_batch=x.shape[0], calib=x)
+
+    def collect(self):
+        """The walk: the table A [E, N] float64 (host) of the label's T-mean probability per exit and image."""
+        model, T = self.model, self.mc_passes
+        model.eval()
+        C = int(model.out_dim)
+        ml = model.mask_layers()
+        cnt, cols = (ml[0].cnt if ml else 0), []
+        for k, (x, y) in enumerate(self.loader):
+            y = torch.as_tensor(y).reshape(-1).to("cpu", torch.int64)
+            if y.numel() != x.shape[0] or int(y.min()) < 0 or int(y.max()) >= C:
+                raise ValueError(f"batch {k}: labels must be one per image and lie in [0, {C})")
+            x = x.to(self.device, non_blocking=True)
+            eng = self._engine_for(x)
+            cnt0 = (cnt + k * T) % ml[0].n if ml else 0
+            mean = eng.predict(x, T, seed=self.seed + k, cnt0=cnt0)["mean"]              # [E, B, C] float64
+            idx = y.to(mean.device).view(1, -1, 1).expand(mean.shape[0], -1, 1)
+            cols.append(mean.gather(2, idx).squeeze(2).cpu().numpy())
+            eng.check_finite()
+        if not cols:
+            raise ValueError("the loader yielded no batch")
+        return np.concatenate(cols, axis=1)
+
+    def fit(self, **em):
+        """Walk + EM per row (keyword arguments go to ``mixture_weights_em``).  Returns — and keeps in ``self.result`` — dict(weights [E, E],
+        nll_uniform / nll_after [E]: the ensemble rows' NLL at equal weights and at the fit, nll_per_exit [E]: every exit alone,
+        iterations, converged [E], n)."""
+        A = self.table = self.collect()
+        E = A.shape[0]
+        W = np.zeros((E, E), dtype=np.float64)
+        rows = [mixture_weights_em(A[:e + 1], **em) for e in range(E)]
+        for e, r in enumerate(rows):
+            W[e, :e + 1] = r["w"]
+        self.result = dict(weights=W, nll_uniform=np.array([r["nll_uniform"] for r in rows]), nll_after=np.array([r["nll"] for r in rows]),
+                           nll_per_exit=np.array([mixture_nll(A[e:e + 1], [1.0]) for e in range(E)]),
+                           iterations=np.array([r["iterations"] for r in rows]), converged=np.array([r["converged"] for r in rows]),
+                           n=int(A.shape[1]))
+        return self.result
+
+    def apply(self):
+        """``model.set_exit_ensemble_weights(W)`` with the fitted matrix."""
+        if self.result is None:
+            raise RuntimeError("fit() first")
+        self.model.set_exit_ensemble_weights(self.result["weights"])
+        return self.model.exit_ensemble_weights
+
+    def save(self, experiment_id):
+        """Writes ``ensemble_weights_<id>.npz`` (the result dict) and returns its name."""
+        if self.result is None:
+            raise RuntimeError("fit() first")
+        name = f"ensemble_weights_{experiment_id}.npz"
         np.savez(name, **{k: np.asarray(v) for k, v in self.result.items()})
         return name

@@ -38,14 +38,28 @@ def decompose_logits(logits):
     return dict(mean=mean, pred_entropy=pred_entropy, exp_entropy=exp_entropy, mutual_info=np.maximum(pred_entropy - exp_entropy, 0.0))
 
 
-def decompose_ensemble_logits(logits, tau=None):
+def weighted_exit_ensembles(per_exit, W):
+    """Row e = sum_{i<=e} W[e][i] * per_exit[i] for ``per_exit`` [E, ...] and weights ``W`` [E, E], float64: every product rounded, added in
+    exit order from 0.0 (the order of csrc/ensemble.hip and of the staged exit rule)."""
+    a = np.asarray(per_exit, dtype=np.float64)
+    W = np.asarray(W, dtype=np.float64)
+    out = np.zeros_like(a)
+    for e in range(a.shape[0]):
+        for i in range(e + 1):
+            out[e] = out[e] + W[e, i] * a[i]
+    return out
+
+
+def decompose_ensemble_logits(logits, tau=None, weights=None):
     """The exit ensembles as predictors, from per-pass logits [T, E, B, C] (``MCDEngine.forward_samples``), float64 on the host: the
     definition csrc/ensemble.hip implements on the device (``MCDEngine.predict_ensemble`` / ``ensemble_moments``).  Per pass t the members
     are p_te = softmax(z_te), z = the fp32 logit, or with ``tau`` (a scalar or E temperatures) the tempered head's ONE rounded fp32 product
     float32(l) * float32(1 / tau_e); the ensemble of exits 0..e is q_te = (p_t0 + ... + p_te) / (e + 1) — the reference's per-pass
     ``ensemble += softmax(logits)`` (train/loss/base_classes.py:41,54,58).  Returns dict(mean, var [E, B, C] — var with ddof 0, clamped at
     0 —, pred_entropy H[mean], exp_entropy E_t H[q_t], mutual_info [E, B] — clamped at 0), entropies in nats.  Row 0 is exit 0 itself.
-    The exits of one pass share the trunk's draw: ``var`` is NOT sum_i var_i / (e + 1)^2."""
+    The exits of one pass share the trunk's draw: ``var`` is NOT sum_i var_i / (e + 1)^2.  ``weights`` (None, [E] or [E, E]:
+    ``engine.check_ensemble_weights``): the weighted ensembles q_te = ((W[e][0] p_t0 + W[e][1] p_t1) + ...) + W[e][e] p_te — every product
+    rounded, added in exit order from 0.0, no renormalisation — in place of the equal mean; everything behind q is the same."""
     l = np.asarray(logits, dtype=np.float32)
     if l.ndim != 4:
         raise ValueError("logits must be [T, E, B, C]")
@@ -57,6 +71,10 @@ def decompose_ensemble_logits(logits, tau=None):
             raise ValueError(f"tau: expected one value per exit ({E}), got {t32.size}")
         inv = (1.0 / t32.astype(np.float64)).astype(np.float32)
         l = (l * inv[None, :, None, None]).astype(np.float32)
+    W = None
+    if weights is not None:
+        from ..engine import check_ensemble_weights
+        W = check_ensemble_weights(weights, E)
     z = l.astype(np.float64)
     z = z - z.max(axis=-1, keepdims=True)
     ex = np.exp(z)
@@ -66,9 +84,10 @@ def decompose_ensemble_logits(logits, tau=None):
     qh = np.zeros(l.shape[1:3], dtype=np.float64)
     for t in range(T):                          # in sample order onto the running sums, like the device
         acc = np.zeros(l.shape[2:], dtype=np.float64)
+        qw = None if W is None else weighted_exit_ensembles(p[t], W)
         for e in range(E):
             acc = acc + p[t, e]
-            q = acc / (e + 1)
+            q = acc / (e + 1) if W is None else qw[e]
             q1[e] += q
             q2[e] += q * q
             qh[e] += entropy_rows(q)
@@ -97,7 +116,9 @@ class UncertaintyAnalysis:
     ensembles are accumulated on the device) and also fills ``ensemble_var`` [E, N, C], ``ensemble_exp_entropy`` and
     ``ensemble_mutual_info`` [E, N], ``ensemble_mean_mi`` [E]; ``summary()`` and ``save()`` gain those keys.  ``ensemble_pred_entropy`` is then the
     device's entropy of the float64 ensemble mean (within 1e-5 of the default walk's, whose members are the heads' fp32 softmax), so that
-    ensemble_mutual_info = ensemble_pred_entropy - ensemble_exp_entropy; everything else keeps its numbers.  Not under a sharded walk (more than one rank): NotImplementedError."""
+    ensemble_mutual_info = ensemble_pred_entropy - ensemble_exp_entropy; everything else keeps its numbers.  Not under a sharded walk (more than one rank): NotImplementedError.
+    On a model that carries ensemble weights (``set_exit_ensemble_weights``) the ``ensemble=True`` walk describes the WEIGHTED ensembles —
+    the five device arrays through the engine, ``ensemble_ape`` from the weighted mean of ``mean``; the default walk keeps the equal mean."""
 
     def __init__(self, model, loader, gpu=0, mc_passes=10, seed=0, group=None, ensemble=False):
         self.ensemble = bool(ensemble)
@@ -160,7 +181,8 @@ class UncertaintyAnalysis:
         self.ape = np.array([average_predictive_entropy(m) for m in self.mean])
         self.mean_mi = self.mutual_info.mean(axis=1)
         self.mean_exp_entropy = self.exp_entropy.mean(axis=1)
-        ens = exit_ensembles(self.mean)
+        W = getattr(self.model, "exit_ensemble_weights", None) if self.ensemble else None
+        ens = exit_ensembles(self.mean) if W is None else weighted_exit_ensembles(self.mean, W)
         self.ensemble_pred_entropy = entropy_rows(ens)
         self.ensemble_ape = np.array([average_predictive_entropy(m) for m in ens])
         if self.ensemble:

@@ -378,6 +378,11 @@ int bmi_forward_mcd_ensemble(bmi_handle h, const float* x_nchw, int32_t batch, i
 int bmi_ensemble_moments(const float* logits, int32_t T, int32_t E, int32_t B, int32_t C, const float* tau, double* Q1, double* Q2, double* QH,
                          bmi_stream stream);
 
+/* bmi_ensemble_moments of the WEIGHTED exit ensembles (bmi_engine_set_ensemble_weights states the arithmetic): W_device is device
+ * float64 [E][E], row-major, used as given.  BMI_ERR_INVALID for a NULL W_device as well. */
+int bmi_ensemble_moments_weighted(const float* logits, int32_t T, int32_t E, int32_t B, int32_t C, const float* tau, const double* W_device,
+                                  double* Q1, double* Q2, double* QH, bmi_stream stream);
+
 /* Per (exit, image) from the sums of t_total samples, float64: ens_mean = Q1 / T and ens_var = max(Q2 / T - ens_mean^2, 0) (ddof 0 like
  * bmi_finalize's var), [E][batch][C]; pred_entropy = H[ens_mean], exp_entropy = QH / T, mutual_info = max(pred - exp, 0), [E][batch]
  * (0 log 0 = 0).  nonfinite (NULL: not counted) as in bmi_finalize_checked: ADDS the number of non-finite Q1 / Q2 / QH inputs. */
@@ -600,6 +605,20 @@ size_t bmi_nll_ensemble_temperature_scratch_bytes(int32_t E, int32_t B, int32_t 
 int bmi_nll_ensemble_temperature_grid(const float* logits, int32_t T, int32_t E, int32_t B, int32_t C, const int32_t* labels, const float* tau,
                                       uint32_t vary_mask, const float* tau_cand, int32_t G, double* nll, void* scratch, size_t scratch_bytes,
                                       bmi_stream stream);
+
+/* Weighted exit ensembles.  W_device: DEVICE float64 [n_exits][n_exits], row-major, owned by the caller and alive for as long as it is
+ * set; row e is the weight vector of the ensemble of exits 0..e (W[e][i] >= 0, W[e][i] == 0 for i > e, every row sums to 1).  NULL: off.
+ * The contents are used AS GIVEN — no check and no renormalisation on the device; validating them is the caller's job (the Python layer
+ * does).  With weights set, per sample, in float64 without fused multiply-adds, p_te the tempered softmax of bmi_forward_mcd_ensemble:
+ *     q_te = ((W[e][0] * p_t0 + W[e][1] * p_t1) + ...) + W[e][e] * p_te         every product rounded, added in exit order from 0.0
+ * and Q1 / Q2 / QH are accumulated from q exactly as before: bmi_forward_mcd_ensemble, bmi_forward_mcd_adaptive_ensemble (so
+ * BMI_STOP_ON_ENSEMBLE decides on the weighted ensemble) and bmi_forward_mcd_exit_staged_ensemble all read it; an image with n exits
+ * reads rows e < n of W only.  The rule of bmi_forward_mcd_exit_staged with ensemble = 1 becomes
+ *     p_c = sum_{i<=e} W[e][i] * (S1[i][b][c] / t_count)                        in exit order, from 0.0
+ * (bmi_forward_mcd_exit, the older entry, keeps the equal mean).  S1 / S2 / SL / SH never depend on it.  Off, the launches are the
+ * unweighted kernels and every output keeps its bits.  The pointer is read at launch: a captured hipGraph keeps what was set at capture.
+ * BMI_ERR_INVALID: a NULL handle, n_exits other than the engine's.  bmi_finalize_ensemble* need no change: they read the sums. */
+int bmi_engine_set_ensemble_weights(bmi_handle h, const double* W_device, int32_t n_exits);
 
 /* Per-op-kind HIP-event timing of bmi_forward_mcd (off by default; adds two event records per
  * launch).  bmi_profile_read synchronises the recorded events and resets the accumulators. */
