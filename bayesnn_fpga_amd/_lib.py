@@ -19,6 +19,7 @@ OP_STEM, OP_CONV, OP_MASK, OP_HEAD, OP_MAXPOOL, OP_DENSE = 1, 2, 3, 4, 5, 6
 STOP_RULES = {"sem": 0, "margin": 1}      # BMI_STOP_* of bmi_forward_mcd_adaptive
 EXIT_RULES = {"confidence": 0, "margin": 1}      # BMI_EXIT_* of bmi_forward_mcd_exit_staged
 STOP_ON = {"exit": 0, "ensemble": 1}      # BMI_STOP_ON_* of bmi_forward_mcd_adaptive_ensemble
+NLL_VEC_SLAB, NLL_VEC_ROWS = 3456, 64       # bmi_nll_vector_scaling_grad stages min(NLL_VEC_ROWS, NLL_VEC_SLAB // (C | 1)) samples per chunk
 NLL_ENS_SLAB, NLL_ENS_ROWS = 9216, 192      # BMI_NLL_ENS_* of bmi_nll_ensemble_temperature_grid: floats / rows a workgroup stages per chunk
 
 
@@ -87,6 +88,10 @@ _PROTOS = {
     "bmi_ensemble_moments": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float)] + [C.c_void_p] * 4),
     "bmi_ensemble_moments_weighted": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float)] + [C.c_void_p] * 5),
     "bmi_engine_set_ensemble_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
+    "bmi_engine_set_vector_scaling": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
+    "bmi_ensemble_moments_vector": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 7),
+    "bmi_nll_vector_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "bmi_nll_vector_scaling_grad": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 7 + [C.c_size_t, C.c_void_p]),
     "bmi_finalize_ensemble": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 10),
     "bmi_finalize_uncertainty": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 7),
     "bmi_forward_mcd_samples": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_int32, C.c_int32, C.c_void_p,

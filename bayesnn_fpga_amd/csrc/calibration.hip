@@ -252,3 +252,140 @@ int launch_nll_ensemble_temperature_grid(const float* logits, int T, int E, int 
     BMI_CHECK_LAUNCH();
     return BMI_OK;
 }
+
+// Value and gradient of a per-exit VECTOR-SCALING fit (bmi_nll_vector_scaling_grad): with z_tc = (double)l_tc * a_c + b_c (two rounded float64
+// operations; a, b float64 [E][C] — the optimiser's smooth objective, the fp32 rounding of the head happens once, when a result is applied),
+//     m_t = max_c z_tc,  s_t = sum_c exp(z_tc - m_t),  A_t = (z_ty - m_t) - log s_t,  nll_b = -( logsumexp_t A_t - log T ),
+//     r_t = exp(A_t - M) / S  (M = max_t A_t, S = sum_t exp(A_t - M)),   p_tc = exp(z_tc - m_t) / s_t,
+//     d nll_b / d b_c = sum_t r_t (p_tc - [c == y]),      d nll_b / d a_c = sum_t r_t (p_tc - [c == y]) l_tc
+// (train/calibration.py: nll_vector_numpy).  float64 throughout, no fused multiply-adds, no floating-point atomics.
+//
+//   workgroup = one image x one exit, 256 threads; the samples go through LDS in chunks of TC rows ([row][C | 1] floats, odd stride, and the
+//               float64 exponentials beside them), in sample order.
+//   pass 1      a group of L = min(64, pow2 >= C) lanes per row: max of z, the exponentials to LDS, their sum by shuffle butterfly (a fixed
+//               tree), A_t.
+//   join        one thread: the chunk's max of A, the running (M, S) of the log-sum-exp over samples moved onto the new max, the weights
+//               w_t = exp(A_t - M) of the chunk — the state ens_nll_terms_kernel carries, so T is not bounded by what a chunk stages.
+//   pass 2      thread c owns class c: its two running sums (registers, carried from chunk to chunk, rescaled by exp(M_old - M_new) with
+//               S) take the chunk's samples in sample order; divided by S once, at the end.
+//   terms       [E][B][2C + 1] float64: the image's nll, then C entries of d / d a, then C of d / d b; nll_vec_sum_kernel adds them over the
+//               images in nll_sum_kernel's fixed order INTO the outputs, so a fit accumulates over loader batches in call order.
+#define NLLV_SLAB 3456           // staged logits (floats, 13.5 KB) and exponentials (float64, 27 KB) per chunk
+#define NLLV_ROWS 64             // samples per staged chunk, at most: the kernel's staging limit is min(NLLV_ROWS, NLLV_SLAB / (C | 1))
+#define NLLV_MAX_C 256           // thread c owns class c
+
+__global__ __launch_bounds__(NLL_THREADS) void nll_vec_terms_kernel(const float* __restrict__ logits, int T, int E, int B, int C, int CS, int TC,
+                                                                    int L, const int* __restrict__ labels, const double* __restrict__ scale,
+                                                                    const double* __restrict__ bias, double* __restrict__ terms) {
+#pragma clang fp contract(off)
+    __shared__ float slab[NLLV_SLAB];                    // [tl][CS] raw logits
+    __shared__ double pe[NLLV_SLAB];                     // [tl][CS] exp(z - m_t)
+    __shared__ double a_s[NLLV_MAX_C], b_s[NLLV_MAX_C];
+    __shared__ double row_s[NLLV_ROWS], row_a[NLLV_ROWS], wt[NLLV_ROWS];
+    __shared__ double st[3];                             // running M, S and the chunk's rescale factor exp(M_old - M_new)
+    const int tid = threadIdx.x;
+    const int b = blockIdx.x, e = blockIdx.y;
+    const int lane = tid & (L - 1), grp = tid / L, ngrp = NLL_THREADS / L;
+    const int y = labels[b];
+    const bool y_ok = y >= 0 && y < C;                   // (the callers check their labels: never an out-of-range read)
+    if (tid < C) { a_s[tid] = scale[(size_t)e * C + tid]; b_s[tid] = bias[(size_t)e * C + tid]; }
+    if (tid == 0) { st[0] = -INFINITY; st[1] = 0.0; st[2] = 0.0; }
+    double ga = 0.0, gb = 0.0;                           // thread c < C: the unnormalised sums of class c
+    for (int t0 = 0; t0 < T; t0 += TC) {
+        const int tcn = min(TC, T - t0);                 // <= NLLV_ROWS, tcn * CS <= NLLV_SLAB (the launcher's TC)
+        __syncthreads();                                 // the previous chunk's readers are done (first chunk: a_s / b_s / st are written)
+        for (int i = tid; i < tcn * C; i += NLL_THREADS) {
+            const int tl = i / C, c = i - tl * C;
+            slab[tl * CS + c] = logits[(((size_t)(t0 + tl) * E + e) * B + b) * C + c];
+        }
+        __syncthreads();
+        for (int r0 = 0; r0 < tcn; r0 += ngrp) {         // (every lane walks every step: the shuffles below need whole groups)
+            const int r = r0 + grp;
+            const bool live = r < tcn;
+            const float* row = slab + (live ? r : 0) * CS;
+            double mx = -INFINITY;
+            if (live)
+                for (int c = lane; c < C; c += L) mx = fmax(mx, (double)row[c] * a_s[c] + b_s[c]);
+            for (int m = L >> 1; m >= 1; m >>= 1) mx = fmax(mx, __shfl_xor(mx, m));
+            double s = 0.0;
+            if (live)
+                for (int c = lane; c < C; c += L) {
+                    const double ex = exp(((double)row[c] * a_s[c] + b_s[c]) - mx);
+                    pe[r * CS + c] = ex;
+                    s += ex;
+                }
+            for (int m = L >> 1; m >= 1; m >>= 1) s += __shfl_xor(s, m);
+            if (live && lane == 0) {
+                row_s[r] = s;
+                row_a[r] = y_ok ? (((double)row[y] * a_s[y] + b_s[y]) - mx) - log(s) : (double)NAN;
+            }
+        }
+        __syncthreads();
+        if (tid == 0) {
+            double cm = row_a[0];
+            for (int tl = 1; tl < tcn; ++tl) cm = fmax(cm, row_a[tl]);
+            const double m = st[0], nm = fmax(m, cm);
+            const double f = exp(m - nm);                // first chunk: exp(-inf) = 0 against sums that are 0
+            double s = st[1] * f;
+            for (int tl = 0; tl < tcn; ++tl) {
+                const double w = exp(row_a[tl] - nm);
+                wt[tl] = w;
+                s += w;
+            }
+            st[0] = nm; st[1] = s; st[2] = f;
+        }
+        __syncthreads();
+        if (tid < C) {
+            const double f = st[2];
+            ga = ga * f;
+            gb = gb * f;
+            const double hot = tid == y ? 1.0 : 0.0;
+            for (int tl = 0; tl < tcn; ++tl) {
+                const double d = wt[tl] * (pe[tl * CS + tid] / row_s[tl] - hot);
+                gb += d;
+                ga += d * (double)slab[tl * CS + tid];
+            }
+        }
+    }
+    __syncthreads();
+    double* const out = terms + ((size_t)e * B + b) * (size_t)(2 * C + 1);
+    const double S = st[1];
+    if (tid == 0) out[0] = -((st[0] + log(S)) - log((double)T));
+    if (tid < C) { out[1 + tid] = ga / S; out[1 + C + tid] = gb / S; }
+}
+
+// nll[e] / grad_scale[e][c] / grad_bias[e][c] += sum_b terms[e][b][k], one wavefront per (e, k), in nll_sum_kernel's fixed order
+__global__ __launch_bounds__(64) void nll_vec_sum_kernel(const double* __restrict__ terms, int B, int C, double* __restrict__ nll,
+                                                         double* __restrict__ grad_scale, double* __restrict__ grad_bias) {
+    const int lane = threadIdx.x, k = blockIdx.x, e = blockIdx.y;
+    const size_t row = (size_t)(2 * C + 1);
+    const double* t = terms + (size_t)e * B * row + k;
+    double s = 0.0;
+    for (int b = lane; b < B; b += 64) s += t[(size_t)b * row];
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m);
+    if (lane == 0) {
+        if (k == 0) nll[e] += s;
+        else if (k <= C) grad_scale[(size_t)e * C + k - 1] += s;
+        else grad_bias[(size_t)e * C + k - 1 - C] += s;
+    }
+}
+
+bool nll_vector_takes(int E, int B, int C) {
+    return E >= 1 && B >= 1 && C >= 1 && C <= NLLV_MAX_C && E <= 65535 && 2 * C + 1 <= 65535;
+}
+
+int launch_nll_vector_scaling_grad(const float* logits, int T, int E, int B, int C, const int* labels, const double* scale, const double* bias,
+                                   double* nll, double* grad_scale, double* grad_bias, double* scratch, hipStream_t s) {
+    if (!nll_vector_takes(E, B, C)) return BMI_ERR_UNSUPPORTED;
+    const int CS = C | 1;                                // odd row stride
+    const int TC = min(T, min(NLLV_ROWS, NLLV_SLAB / CS));           // >= 1: CS <= 257
+    int L = 1;
+    while (L < C && L < 64) L <<= 1;
+    hipLaunchKernelGGL(nll_vec_terms_kernel, dim3((unsigned)B, (unsigned)E), dim3(NLL_THREADS), 0, s, logits, T, E, B, C, CS, TC, L, labels, scale,
+                       bias, scratch);
+    BMI_CHECK_LAUNCH();
+    hipLaunchKernelGGL(nll_vec_sum_kernel, dim3((unsigned)(2 * C + 1), (unsigned)E), dim3(64), 0, s, scratch, B, C, nll, grad_scale, grad_bias);
+    BMI_CHECK_LAUNCH();
+    return BMI_OK;
+}

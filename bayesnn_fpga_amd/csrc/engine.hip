@@ -100,6 +100,8 @@ struct bmi_engine_s {
     std::vector<std::pair<const float*, size_t>> perm;   // (bmi_plan) Masksembles tables (device pointer of the site) -> workspace offset of the permuted copy
     std::vector<float> tau;              // bmi_engine_set_temperature: the temperatures as given ([n_exits]; empty: never set = ones)
     std::vector<float> inv_tau;          // float32(1 / (double)tau[e]) per exit, what the heads multiply by; EMPTY when off (never set, or all ones)
+    const float* vec_scale = nullptr;    // bmi_engine_set_vector_scaling: the caller's DEVICE fp32 [n_exits][out_dim] scales and biases (not owned), null: off;
+    const float* vec_bias = nullptr;     // never together with a non-unit temperature (inv_tau is empty while these are set)
     const double* ens_w = nullptr;       // bmi_engine_set_ensemble_weights: the caller's DEVICE [n_exits][n_exits] float64 (not owned), null: the equal-weight mean
     std::vector<char> staged_ok;         // (bmi_plan) per first_exit: the staged suffix order keeps every shared workspace range's live ranges apart
     // profiling
@@ -789,6 +791,7 @@ int bmi_engine_set_temperature(bmi_handle h, const float* tau, int32_t n_exits) 
         if (!(inv > 0.f) || !std::isfinite(inv)) return BMI_ERR_INVALID;      // 1 / tau leaves the float32 range
         ones = ones && tau[i] == 1.f;
     }
+    if (!ones && h->vec_scale) return BMI_ERR_INVALID;     // one calibration map at a time: clear the vector scaling first
     h->tau.assign(tau, tau + n_exits);
     h->inv_tau.clear();
     if (!ones)
@@ -803,6 +806,19 @@ int bmi_engine_set_ensemble_weights(bmi_handle h, const double* W_device, int32_
     if (!W_device) { h->ens_w = nullptr; return BMI_OK; }
     if (n_exits != h->n_exits) return BMI_ERR_INVALID;
     h->ens_w = W_device;
+    return BMI_OK;
+}
+
+// Per-class scale and bias of every exit (caller-owned device arrays, used as given), or scale_device NULL: off — the heads and the ensemble
+// launches are then the instantiations they were and every output keeps its bits.  Read at launch time: captured graphs keep what was set
+// at capture.  Refused while a temperature other than all ones is in force (and bmi_engine_set_temperature refuses one while this is set).
+int bmi_engine_set_vector_scaling(bmi_handle h, const float* scale_device, const float* bias_device, int32_t n_exits, int32_t out_dim) {
+    if (!h) return BMI_ERR_INVALID;
+    if (!scale_device) { h->vec_scale = h->vec_bias = nullptr; return BMI_OK; }
+    if (!bias_device || n_exits != h->n_exits || out_dim != h->out_dim) return BMI_ERR_INVALID;
+    if (!h->inv_tau.empty()) return BMI_ERR_INVALID;
+    h->vec_scale = scale_device;
+    h->vec_bias = bias_device;
     return BMI_OK;
 }
 
@@ -1093,6 +1109,10 @@ HeadArgs make_head_args(bmi_engine_s* e, const Pass& p, const OpInfo& op, int N,
     a.site_logits = pass_site(e, p, on_logits ? &d.site : nullptr);
     a.b0 = p.b0;
     a.inv_tau = e->inv_tau.empty() ? 0.f : e->inv_tau[d.out];       // 0: the untempered instantiations
+    if (e->vec_scale) {                                             // this exit's [C] rows
+        a.vec_scale = e->vec_scale + (size_t)d.out * e->out_dim;
+        a.vec_bias = e->vec_bias + (size_t)d.out * e->out_dim;
+    }
     if (p.S1) {
         const size_t eo = (size_t)d.out * B * e->out_dim;
         a.S1 = p.S1 + eo; a.S2 = p.S2 + eo; a.SL = p.SL + eo;
@@ -1479,7 +1499,7 @@ int forward_folded(bmi_engine_s* e, const Pass& p, int t_begin, int t_count, con
         if (rc != BMI_OK) return rc;
         if (!ens) continue;
         rc = launch_ensemble_moments(ens->scratch, tc, e->n_exits, p.B, e->out_dim, e->inv_tau.empty() ? nullptr : e->inv_tau.data(), ens->Q1,
-                                     ens->Q2, ens->QH, p.stream, nullptr, 0, nullptr, e->ens_w);
+                                     ens->Q2, ens->QH, p.stream, nullptr, 0, nullptr, e->ens_w, e->vec_scale, e->vec_bias);
         if (rc != BMI_OK) return rc;
     }
     return BMI_OK;
@@ -1693,7 +1713,7 @@ static int exit_staged(bmi_handle h, const float* x_nchw, int32_t batch, int32_t
         const int rce = launch_exit_counts(exit_of_image, batch, lists[0], s);
         if (rce != BMI_OK) return rce;
         return launch_ensemble_moments(ens->scratch, t_count, h->n_exits, batch, h->out_dim, h->inv_tau.empty() ? nullptr : h->inv_tau.data(),
-                                       ens->Q1, ens->Q2, ens->QH, s, nullptr, 0, lists[0], h->ens_w);
+                                       ens->Q1, ens->Q2, ens->QH, s, nullptr, 0, lists[0], h->ens_w, h->vec_scale, h->vec_bias);
     };
     const int* act = nullptr;      // null: every image is still active (stage 0: bmi_forward_mcd's launches)
     const int* rows = nullptr;
@@ -1803,7 +1823,7 @@ static int adaptive(bmi_handle h, const float* x_nchw, int32_t batch, int32_t im
             ProfScope prof(h, BMI_PROFILE_ENSEMBLE, s);
             prof.r.images = tc * bc;
             rc = launch_ensemble_moments(ens->scratch, tc, h->n_exits, batch, h->out_dim, h->inv_tau.empty() ? nullptr : h->inv_tau.data(), ens->Q1,
-                                         ens->Q2, ens->QH, s, imap, bc, nullptr, h->ens_w);
+                                         ens->Q2, ens->QH, s, imap, bc, nullptr, h->ens_w, h->vec_scale, h->vec_bias);
             if (rc != BMI_OK) return rc;
         }
         // the stop rule over the still-active images, on the device; the host only learns how many go on
@@ -1927,6 +1947,29 @@ int bmi_ensemble_moments_weighted(const float* logits, int32_t T, int32_t E, int
                                   double* Q1, double* Q2, double* QH, bmi_stream stream) {
     if (!W_device) return BMI_ERR_INVALID;
     return ensemble_moments_entry(logits, T, E, B, C, tau, W_device, Q1, Q2, QH, stream);
+}
+
+int bmi_ensemble_moments_vector(const float* logits, int32_t T, int32_t E, int32_t B, int32_t C, const float* scale_device, const float* bias_device,
+                                const double* W_device, double* Q1, double* Q2, double* QH, bmi_stream stream) {
+    if (!logits || !scale_device || !bias_device || !Q1 || !Q2 || !QH || T < 1 || E < 1 || B < 1 || C < 1) return BMI_ERR_INVALID;
+    if (!ensemble_takes(E, C)) return BMI_ERR_UNSUPPORTED;
+    return launch_ensemble_moments(logits, T, E, B, C, nullptr, Q1, Q2, QH, (hipStream_t)stream, nullptr, 0, nullptr, W_device, scale_device,
+                                   bias_device);
+}
+
+size_t bmi_nll_vector_scratch_bytes(int32_t E, int32_t B, int32_t C) {
+    if (E < 1 || B < 1 || C < 1) return 0;
+    return (size_t)E * B * (2 * (size_t)C + 1) * sizeof(double);
+}
+
+int bmi_nll_vector_scaling_grad(const float* logits, int32_t T, int32_t E, int32_t B, int32_t C, const int32_t* labels, const double* scale,
+                                const double* bias, double* nll, double* grad_scale, double* grad_bias, void* scratch, size_t scratch_bytes,
+                                bmi_stream stream) {
+    if (!logits || !labels || !scale || !bias || !nll || !grad_scale || !grad_bias || !scratch || T < 1 || E < 1 || B < 1 || C < 1)
+        return BMI_ERR_INVALID;
+    if (!nll_vector_takes(E, B, C)) return BMI_ERR_UNSUPPORTED;
+    if (scratch_bytes < bmi_nll_vector_scratch_bytes(E, B, C)) return BMI_ERR_NOMEM;
+    return launch_nll_vector_scaling_grad(logits, T, E, B, C, labels, scale, bias, nll, grad_scale, grad_bias, (double*)scratch, (hipStream_t)stream);
 }
 
 size_t bmi_nll_temperature_scratch_bytes(int32_t E, int32_t B, int32_t G) {

@@ -38,12 +38,15 @@ struct EnsTau { float inv[BMI_ENS_MAX_EXITS]; };
 // Phase B first turns the rows of pq into p in place, then forms q_e for e DESCENDING: row e reads the rows i <= e, which are still p.
 // e and i are the same for the whole wave, so a weight is one scalar load (the 63.6 KB of LDS leave no room for a [32][32] table); under
 // ROWS only the rows e < n_e[b] of W are read.  Not WEIGHTED: the code as it was, W is never read.
-template <bool ROWS, bool WEIGHTED>
-__global__ __launch_bounds__(ENS_THREADS) void ensemble_moments_kernel(const float* __restrict__ logits, int T, int E_all, int B, int C, int CS,
-                                                                       int TS, int L, EnsTau tau, double* __restrict__ Q1,
-                                                                       double* __restrict__ Q2, double* __restrict__ QH,
-                                                                       const int* __restrict__ list, const int* __restrict__ n_e,
-                                                                       const double* __restrict__ W) {
+// VEC (bmi_engine_set_vector_scaling, bmi_ensemble_moments_vector): z_te,c = (double) fl32(fl32(l * vs[e][c]) + vb[e][c]), the vector-scaled head's
+// own number (two rounded fp32 operations: plain operators under this body's `fp contract(off)`), in place of fl32(l * inv_e); vs / vb are device fp32 [E_all][C], read where they are used (the static LDS is full: 3.2 KB at
+// E = 4, C = 100 are cache hits after the first row).  Not VEC: the code as it was, vs / vb are never read.
+// The body of both kernels below: the vector form is a kernel of its own name and arguments, so that the four older ones keep theirs.
+template <bool ROWS, bool WEIGHTED, bool VEC>
+__device__ __forceinline__ void ensemble_moments_body(const float* __restrict__ logits, int T, int E_all, int B, int C, int CS, int TS, int L,
+                                                      const EnsTau& tau, double* __restrict__ Q1, double* __restrict__ Q2, double* __restrict__ QH,
+                                                      const int* __restrict__ list, const int* __restrict__ n_e, const double* __restrict__ W,
+                                                      const float* __restrict__ vs, const float* __restrict__ vb) {
 #pragma clang fp contract(off)
     __shared__ double pq[ENS_SLAB];                      // [row][CS], row = tl * E + e: exp(z - max), then q
     __shared__ double ql[ENS_SLAB];                      // q log q
@@ -54,7 +57,7 @@ __global__ __launch_bounds__(ENS_THREADS) void ensemble_moments_kernel(const flo
     const int E = (ROWS && n_e) ? min(n_e[b], E_all) : E_all;       // the exits of THIS image (rows of the chunk: [tl][E])
     if (ROWS && (E < 1 || (unsigned)b >= (unsigned)B)) return;       // (the whole workgroup)
     const int lane = tid & (L - 1), grp = tid / L, ngrp = ENS_THREADS / L;
-    if (tid < E) inv_s[tid] = tau.inv[tid];
+    if (!VEC && tid < E) inv_s[tid] = tau.inv[tid];
     for (int t0 = 0; t0 < T; t0 += TS) {
         const int tn = min(TS, T - t0);
         const int rows = tn * E;                         // <= ENS_ROWS, rows * CS <= ENS_SLAB (the launcher's TS)
@@ -64,15 +67,17 @@ __global__ __launch_bounds__(ENS_THREADS) void ensemble_moments_kernel(const flo
             const bool live = r < rows;
             const int tl = live ? r / E : 0, e = live ? r - tl * E : 0;
             const float* src = logits + (((size_t)(t0 + tl) * E_all + e) * B + b) * C;
-            const float inv = inv_s[e];
+            const float inv = VEC ? 1.f : inv_s[e];
+            const float* const sc = VEC ? vs + (size_t)e * C : nullptr;
+            const float* const bi = VEC ? vb + (size_t)e * C : nullptr;
             float mx = -INFINITY;
             if (live)
-                for (int c = lane; c < C; c += L) mx = fmaxf(mx, src[c] * inv);
+                for (int c = lane; c < C; c += L) mx = fmaxf(mx, VEC ? (src[c] * sc[c] + bi[c]) : src[c] * inv);
             for (int m = L >> 1; m >= 1; m >>= 1) mx = fmaxf(mx, __shfl_xor(mx, m));
             double s = 0.0;
             if (live)
                 for (int c = lane; c < C; c += L) {
-                    const double ex = exp((double)(src[c] * inv) - (double)mx);
+                    const double ex = exp((double)(VEC ? (src[c] * sc[c] + bi[c]) : src[c] * inv) - (double)mx);
                     pq[r * CS + c] = ex;
                     s += ex;
                 }
@@ -133,6 +138,25 @@ __global__ __launch_bounds__(ENS_THREADS) void ensemble_moments_kernel(const flo
     }
 }
 
+template <bool ROWS, bool WEIGHTED>
+__global__ __launch_bounds__(ENS_THREADS) void ensemble_moments_kernel(const float* __restrict__ logits, int T, int E_all, int B, int C, int CS,
+                                                                       int TS, int L, EnsTau tau, double* __restrict__ Q1,
+                                                                       double* __restrict__ Q2, double* __restrict__ QH,
+                                                                       const int* __restrict__ list, const int* __restrict__ n_e,
+                                                                       const double* __restrict__ W) {
+    ensemble_moments_body<ROWS, WEIGHTED, false>(logits, T, E_all, B, C, CS, TS, L, tau, Q1, Q2, QH, list, n_e, W, nullptr, nullptr);
+}
+
+template <bool ROWS, bool WEIGHTED>
+__global__ __launch_bounds__(ENS_THREADS) void ensemble_moments_vec_kernel(const float* __restrict__ logits, int T, int E_all, int B, int C, int CS,
+                                                                           int TS, int L, const float* __restrict__ vs,
+                                                                           const float* __restrict__ vb, double* __restrict__ Q1,
+                                                                           double* __restrict__ Q2, double* __restrict__ QH,
+                                                                           const int* __restrict__ list, const int* __restrict__ n_e,
+                                                                           const double* __restrict__ W) {
+    ensemble_moments_body<ROWS, WEIGHTED, true>(logits, T, E_all, B, C, CS, TS, L, EnsTau{}, Q1, Q2, QH, list, n_e, W, vs, vb);
+}
+
 bool ensemble_takes(int E, int C) {
     return E >= 1 && C >= 1 && E <= BMI_ENS_MAX_EXITS && C <= BMI_ENS_MAX_CLASSES && E * (C | 1) <= ENS_SLAB;
 }
@@ -144,9 +168,18 @@ static void launch_ens(unsigned grid, hipStream_t s, const float* logits, int T,
                        QH, list, n_e, W);
 }
 
+template <bool ROWS, bool WEIGHTED>
+static void launch_ens_vec(unsigned grid, hipStream_t s, const float* logits, int T, int E, int B, int C, int CS, int TS, int L, const float* vs,
+                           const float* vb, double* Q1, double* Q2, double* QH, const int* list, const int* n_e, const double* W) {
+    hipLaunchKernelGGL((ensemble_moments_vec_kernel<ROWS, WEIGHTED>), dim3(grid), dim3(ENS_THREADS), 0, s, logits, T, E, B, C, CS, TS, L, vs, vb, Q1,
+                       Q2, QH, list, n_e, W);
+}
+
 int launch_ensemble_moments(const float* logits, int T, int E, int B, int C, const float* inv_tau, double* Q1, double* Q2, double* QH,
-                            hipStream_t s, const int* list, int Bc, const int* n_e, const double* W) {
+                            hipStream_t s, const int* list, int Bc, const int* n_e, const double* W, const float* vec_scale,
+                            const float* vec_bias) {
     if (T < 1 || B < 1 || (list && (Bc < 1 || Bc > B))) return BMI_ERR_INVALID;
+    if ((vec_scale != nullptr) != (vec_bias != nullptr) || (vec_scale && inv_tau)) return BMI_ERR_INVALID;
     if (!ensemble_takes(E, C)) return BMI_ERR_UNSUPPORTED;
     const int CS = C | 1;                                // odd row stride
     const int TS = std::min(ENS_SLAB / (E * CS), ENS_ROWS / E);      // >= 1 (ensemble_takes)
@@ -156,6 +189,14 @@ int launch_ensemble_moments(const float* logits, int T, int E, int B, int C, con
     for (int e = 0; e < BMI_ENS_MAX_EXITS; ++e) tau.inv[e] = (inv_tau && e < E) ? inv_tau[e] : 1.f;
     const bool rows = list || n_e;
     const unsigned grid = (unsigned)(list ? Bc : B);
+    if (vec_scale) {
+        if (rows && W) launch_ens_vec<true, true>(grid, s, logits, T, E, B, C, CS, TS, L, vec_scale, vec_bias, Q1, Q2, QH, list, n_e, W);
+        else if (rows) launch_ens_vec<true, false>(grid, s, logits, T, E, B, C, CS, TS, L, vec_scale, vec_bias, Q1, Q2, QH, list, n_e, nullptr);
+        else if (W) launch_ens_vec<false, true>(grid, s, logits, T, E, B, C, CS, TS, L, vec_scale, vec_bias, Q1, Q2, QH, nullptr, nullptr, W);
+        else launch_ens_vec<false, false>(grid, s, logits, T, E, B, C, CS, TS, L, vec_scale, vec_bias, Q1, Q2, QH, nullptr, nullptr, nullptr);
+        BMI_CHECK_LAUNCH();
+        return BMI_OK;
+    }
     if (rows && W) launch_ens<true, true>(grid, s, logits, T, E, B, C, CS, TS, L, tau, Q1, Q2, QH, list, n_e, W);
     else if (rows) launch_ens<true, false>(grid, s, logits, T, E, B, C, CS, TS, L, tau, Q1, Q2, QH, list, n_e, nullptr);
     else if (W) launch_ens<false, true>(grid, s, logits, T, E, B, C, CS, TS, L, tau, Q1, Q2, QH, nullptr, nullptr, W);

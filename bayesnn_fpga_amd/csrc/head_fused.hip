@@ -25,6 +25,9 @@
 // the tempered instantiations (HeadArgs::inv_tau != 0): head_fused_temp.hip
 void launch_head_rt_temp(const HeadArgs& a, hipStream_t s);
 void launch_head_rt_multi_temp(const HeadArgsPack& p, int n, hipStream_t s);
+// the vector-scaling instantiations (HeadArgs::vec_scale != null): head_fused_vec.hip
+void launch_head_rt_vec(const HeadArgs& a, hipStream_t s);
+void launch_head_rt_multi_vec(const HeadArgsPack& p, int n, hipStream_t s);
 
 // Joins the per-group partial sums of an image in GROUP ORDER into the caller's accumulators: with hardware float64 atomics the
 // groups met in whatever order the workgroups finished, and the last bit of the sums of more than 64 samples changed from run to
@@ -87,6 +90,7 @@ static int head_prepare(HeadArgs& a) {
     if (a.in_mod != a.B && a.in_mod != a.B * a.tc) return BMI_ERR_INVALID;
     if (a.imap && (a.Bc <= 0 || a.Bc > a.B)) return BMI_ERR_INVALID;
     if (!(a.inv_tau >= 0.f) || a.inv_tau > 3.0e38f) return BMI_ERR_INVALID;       // 0: off; else a finite positive 1 / tau
+    if ((a.vec_scale != nullptr) != (a.vec_bias != nullptr) || (a.vec_scale && a.inv_tau != 0.f)) return BMI_ERR_INVALID;   // one calibration map at a time
     if (a.K % 32 != 0 || a.C > 128) return BMI_ERR_UNSUPPORTED;
     if (a.site_logits.kind != BMI_SITE_NONE && a.site_logits.kind != BMI_SITE_ELEMENTWISE) return BMI_ERR_UNSUPPORTED;
     return BMI_OK;
@@ -97,13 +101,14 @@ int launch_head_fused(const HeadArgs& a_in, hipStream_t s) {
     const int groups = (a.tc + 31) / 32;
     const int rcp = head_prepare(a);
     if (rcp != BMI_OK) return rcp;
-    if (a.inv_tau != 0.f) launch_head_rt_temp(a, s);
+    if (a.vec_scale) launch_head_rt_vec(a, s);
+    else if (a.inv_tau != 0.f) launch_head_rt_temp(a, s);
     else
         switch ((a.C + 31) / 32) {
-            case 1: launch_rt<1, false>(a, s); break;
-            case 2: launch_rt<2, false>(a, s); break;
-            case 3: launch_rt<3, false>(a, s); break;
-            default: launch_rt<4, false>(a, s); break;
+            case 1: launch_rt<1, 0>(a, s); break;
+            case 2: launch_rt<2, 0>(a, s); break;
+            case 3: launch_rt<3, 0>(a, s); break;
+            default: launch_rt<4, 0>(a, s); break;
         }
     BMI_CHECK_LAUNCH();
     if (a.part) {
@@ -127,20 +132,22 @@ int launch_head_fused_multi(const HeadArgs* list, int n, hipStream_t s) {
         if (rcp != BMI_OK) return rcp;
         const HeadArgs &x = p.a[i], &y = p.a[0];
         if (x.imap || x.C != y.C || x.in_kind != y.in_kind || x.B != y.B || x.tc != y.tc || (x.part != nullptr) != (y.part != nullptr) ||
-            (x.S1 != nullptr) != (y.S1 != nullptr) || (x.SH != nullptr) != (y.SH != nullptr) || (x.inv_tau != 0.f) != (y.inv_tau != 0.f))
+            (x.S1 != nullptr) != (y.S1 != nullptr) || (x.SH != nullptr) != (y.SH != nullptr) || (x.inv_tau != 0.f) != (y.inv_tau != 0.f) ||
+            (x.vec_scale != nullptr) != (y.vec_scale != nullptr))
             return BMI_ERR_UNSUPPORTED;
         for (int j = 0; j < i; ++j)
             if (x.part && x.part == p.a[j].part) return BMI_ERR_INVALID;
     }
     for (int i = n; i < BMI_HEAD_PACK_MAX; ++i) p.a[i] = p.a[0];
     const HeadArgs& a = p.a[0];
-    if (a.inv_tau != 0.f) launch_head_rt_multi_temp(p, n, s);
+    if (a.vec_scale) launch_head_rt_multi_vec(p, n, s);
+    else if (a.inv_tau != 0.f) launch_head_rt_multi_temp(p, n, s);
     else
         switch ((a.C + 31) / 32) {
-            case 1: launch_rt_multi<1, false>(p, n, s); break;
-            case 2: launch_rt_multi<2, false>(p, n, s); break;
-            case 3: launch_rt_multi<3, false>(p, n, s); break;
-            default: launch_rt_multi<4, false>(p, n, s); break;
+            case 1: launch_rt_multi<1, 0>(p, n, s); break;
+            case 2: launch_rt_multi<2, 0>(p, n, s); break;
+            case 3: launch_rt_multi<3, 0>(p, n, s); break;
+            default: launch_rt_multi<4, 0>(p, n, s); break;
         }
     BMI_CHECK_LAUNCH();
     if (a.part) {

@@ -1,6 +1,7 @@
 // The exit head's kernel body, its two kernel templates and their launch switches (head_fused.hip has the description): shared by
 // head_fused.hip, which instantiates the untempered kernels (TEMP = false — the instantiations, registers and bits of an engine without a
-// temperature), and head_fused_temp.hip, which instantiates the tempered ones in a translation unit of its own (they compile side by side).
+// temperature), head_fused_temp.hip, which instantiates the tempered ones in a translation unit of its own (they compile side by side), and
+// head_fused_vec.hip, which does the same for the vector-scaling kernels.
 #pragma once
 #include <cstdlib>
 
@@ -29,7 +30,25 @@ typedef _Float16 half8_h __attribute__((ext_vector_type(8)));
 // TEMP: temperature scaling (HeadArgs::inv_tau != 0, bmi_engine_set_temperature), a template parameter for the same reason: behind the bias
 // and the logits site every logit is multiplied in fp32, z = l * inv_tau; the running max, the softmax, S1 / S2 and the entropy are those
 // of z, while SL and the per-sample logits output stay the raw l (pb_l keeps l; z lives in the accumulator registers only).
-template <int RT, int KIND, bool CSPLIT, bool ENT, bool TEMP>
+// z = fl32(fl32(l * a) + b), both operations rounded: spelled with plain operators under `fp contract(off)` — this toolchain's __fmul_rn /
+// __fadd_rn are plain operators in a header compiled under the default contraction mode, so a product written with them can still be fused
+// into the sum behind it (or into the subtraction of the max); operations that do not carry the contract flag cannot.
+// head_scale: the tempered head's one rounded product, for the same reason (written with __fmul_rn it was fused into the subtraction of the max).
+__device__ __forceinline__ float head_scale(float l, float inv) {
+#pragma clang fp contract(off)
+    return l * inv;
+}
+__device__ __forceinline__ float head_scale_bias(float l, float a, float b) {
+#pragma clang fp contract(off)
+    const float prod = l * a;
+    return prod + b;
+}
+
+// TEMP == 2: vector scaling (HeadArgs::vec_scale != null, bmi_engine_set_vector_scaling) — at the same place z_c = fl32(fl32(l_c * a_c) + b_c)
+// with this exit's per-class scale a and bias b, two rounded fp32 operations; everything behind it is the tempered code on z (the max is
+// taken over z: the map is not monotone across classes).  The coefficients are read through L1 where they are used: wave 0 only, once
+// per workgroup, 2 * 16 * RT loads that die at once (held across the K loop they would cost that many registers).
+template <int RT, int KIND, bool CSPLIT, bool ENT, int TEMP>
 __device__ __forceinline__ void head_body(const HeadArgs& a) {
     static_assert(!CSPLIT || (RT >= 3 && RT <= 4), "class split: one wave per class tile");
     constexpr int KC = CSPLIT ? 256 : HEAD_KC;                 // K chunk held in LDS (floats per sample)
@@ -270,7 +289,23 @@ __device__ __forceinline__ void head_body(const HeadArgs& a) {
                         if (c < C) acc[i][e] = pb_l[c * 33 + r];
                     }
             }
-            if constexpr (TEMP) {
+            if constexpr (TEMP == 2) {
+                // as the tempered pass below, with a product and a sum per logit: both rounded, never one fused multiply-add, and never
+                // fused into the subtraction of the max either (head_scale_bias)
+                const float* const vs = a.vec_scale;
+                const float* const vb = a.vec_bias;
+#pragma unroll
+                for (int i = 0; i < RT; ++i)
+#pragma unroll
+                    for (int e = 0; e < 16; ++e) {
+                        const int c = 32 * i + (e & 3) + 8 * (e >> 2) + 4 * hh;
+                        if (c < C) {
+                            pb_l[c * 33 + r] = acc[i][e];
+                            acc[i][e] = head_scale_bias(acc[i][e], vs[c], vb[c]);
+                        }
+                    }
+            }
+            if constexpr (TEMP == 1) {
                 // the raw logits go to pb_l now (the pass below stores them otherwise); one rounded fp32 product per logit — never
                 // contracted into the subtraction of the max, so that z is the number a host restatement computes
                 const float inv = a.inv_tau;
@@ -280,7 +315,7 @@ __device__ __forceinline__ void head_body(const HeadArgs& a) {
                     for (int e = 0; e < 16; ++e) {
                         const int c = 32 * i + (e & 3) + 8 * (e >> 2) + 4 * hh;
                         if (c < C) pb_l[c * 33 + r] = acc[i][e];
-                        acc[i][e] = __fmul_rn(acc[i][e], inv);
+                        acc[i][e] = head_scale(acc[i][e], inv);
                     }
             }
             float mx = -INFINITY;
@@ -300,7 +335,7 @@ __device__ __forceinline__ void head_body(const HeadArgs& a) {
                     const int c = 32 * i + (e & 3) + 8 * (e >> 2) + 4 * hh;
                     const float ex = c < C ? expf(acc[i][e] - mx) : 0.f;
                     sum += ex;
-                    if constexpr (TEMP) {
+                    if constexpr (TEMP != 0) {
                         if (c < C) pb_p[c * 33 + r] = ex;
                     } else {
                         if (c < C) { pb_l[c * 33 + r] = acc[i][e]; pb_p[c * 33 + r] = ex; }
@@ -323,7 +358,7 @@ __device__ __forceinline__ void head_body(const HeadArgs& a) {
 #pragma unroll
                     for (int e = 0; e < 16; ++e) {
                         const int c = 32 * i + (e & 3) + 8 * (e >> 2) + 4 * hh;
-                        if constexpr (TEMP) {                      // z_c - max z: pb_l holds the raw logit, the register the tempered one
+                        if constexpr (TEMP != 0) {                 // z_c - max z: pb_l holds the raw logit, the register the tempered one
                             if (c < C) dot += pb_p[c * 33 + r] * (acc[i][e] - mx);
                         } else {
                             if (c < C) dot += pb_p[c * 33 + r] * (pb_l[c * 33 + r] - mx);
@@ -385,7 +420,12 @@ __device__ __forceinline__ void head_body(const HeadArgs& a) {
 
 template <int RT, int KIND, bool CSPLIT = false, bool ENT = false, bool TEMP = false>
 __global__ __launch_bounds__(256, CSPLIT ? 2 : 1) void head_fused_kernel(HeadArgs a) {
-    head_body<RT, KIND, CSPLIT, ENT, TEMP>(a);
+    head_body<RT, KIND, CSPLIT, ENT, TEMP ? 1 : 0>(a);
+}
+// the vector-scaling twin (head_fused_vec.hip): a kernel of its own name, so that the two above keep theirs
+template <int RT, int KIND, bool CSPLIT = false, bool ENT = false>
+__global__ __launch_bounds__(256, CSPLIT ? 2 : 1) void head_fused_vec_kernel(HeadArgs a) {
+    head_body<RT, KIND, CSPLIT, ENT, 2>(a);
 }
 
 // Several exit heads in ONE launch (round 6): with exit-only dropout — the configuration every run of the paper uses,
@@ -396,21 +436,37 @@ __global__ __launch_bounds__(256, CSPLIT ? 2 : 1) void head_fused_kernel(HeadArg
 struct HeadArgsPack { HeadArgs a[BMI_HEAD_PACK_MAX]; };
 template <int RT, int KIND, bool CSPLIT = false, bool ENT = false, bool TEMP = false>
 __global__ __launch_bounds__(256, CSPLIT ? 2 : 1) void head_fused_multi_kernel(HeadArgsPack p) {
-    head_body<RT, KIND, CSPLIT, ENT, TEMP>(p.a[blockIdx.z]);
+    head_body<RT, KIND, CSPLIT, ENT, TEMP ? 1 : 0>(p.a[blockIdx.z]);
+}
+template <int RT, int KIND, bool CSPLIT = false, bool ENT = false>
+__global__ __launch_bounds__(256, CSPLIT ? 2 : 1) void head_fused_multi_vec_kernel(HeadArgsPack p) {
+    head_body<RT, KIND, CSPLIT, ENT, 2>(p.a[blockIdx.z]);     // every head of the pack carries its own exit's coefficient rows
 }
 
-// The launch switches of one class-tile count; TP = the TEMP argument of every kernel they name (one value per translation unit).
-template <int RT, bool TP>
+// TP: 0 untempered, 1 scalar temperature, 2 vector scaling — the kernel of one (class tiles, input kind, class split, entropy) form
+template <int RT, int KIND, bool CS, bool EN, int TP>
+static constexpr auto head_kernel_of() {
+    if constexpr (TP == 2) return &head_fused_vec_kernel<RT, KIND, CS, EN>;
+    else return &head_fused_kernel<RT, KIND, CS, EN, TP == 1>;
+}
+template <int RT, int KIND, bool CS, bool EN, int TP>
+static constexpr auto head_multi_kernel_of() {
+    if constexpr (TP == 2) return &head_fused_multi_vec_kernel<RT, KIND, CS, EN>;
+    else return &head_fused_multi_kernel<RT, KIND, CS, EN, TP == 1>;
+}
+
+// The launch switches of one class-tile count; TP = the scaling state of every kernel they name (one value per translation unit).
+template <int RT, int TP>
 static void launch_rt_multi(const HeadArgsPack& p, int n, hipStream_t s) {
     const HeadArgs& a = p.a[0];
     const dim3 grid((unsigned)a.B, (unsigned)((a.tc + 31) / 32), (unsigned)n), block(256);
 #define HEAD_LAUNCH_ME(CS, EN)                                                                                            \
     switch (a.in_kind) {                                                                                                  \
-        case 1: hipLaunchKernelGGL((head_fused_multi_kernel<RT, 1, CS, EN, TP>), grid, block, 0, s, p); break;            \
-        case 2: hipLaunchKernelGGL((head_fused_multi_kernel<RT, 2, CS, EN, TP>), grid, block, 0, s, p); break;            \
-        case 3: hipLaunchKernelGGL((head_fused_multi_kernel<RT, 3, CS, EN, TP>), grid, block, 0, s, p); break;            \
-        case 4: hipLaunchKernelGGL((head_fused_multi_kernel<RT, 4, CS, EN, TP>), grid, block, 0, s, p); break;            \
-        default: hipLaunchKernelGGL((head_fused_multi_kernel<RT, 0, CS, EN, TP>), grid, block, 0, s, p); break;           \
+        case 1: hipLaunchKernelGGL((head_multi_kernel_of<RT, 1, CS, EN, TP>()), grid, block, 0, s, p); break;            \
+        case 2: hipLaunchKernelGGL((head_multi_kernel_of<RT, 2, CS, EN, TP>()), grid, block, 0, s, p); break;            \
+        case 3: hipLaunchKernelGGL((head_multi_kernel_of<RT, 3, CS, EN, TP>()), grid, block, 0, s, p); break;            \
+        case 4: hipLaunchKernelGGL((head_multi_kernel_of<RT, 4, CS, EN, TP>()), grid, block, 0, s, p); break;            \
+        default: hipLaunchKernelGGL((head_multi_kernel_of<RT, 0, CS, EN, TP>()), grid, block, 0, s, p); break;           \
     }
 #define HEAD_LAUNCH_M(CS) if (a.SH) { HEAD_LAUNCH_ME(CS, true) } else { HEAD_LAUNCH_ME(CS, false) }
     if constexpr (RT >= 3) {
@@ -425,16 +481,16 @@ static void launch_rt_multi(const HeadArgsPack& p, int n, hipStream_t s) {
 #undef HEAD_LAUNCH_ME
 }
 
-template <int RT, bool TP>
+template <int RT, int TP>
 static void launch_rt(const HeadArgs& a, hipStream_t s) {
     const dim3 grid((unsigned)(a.imap ? a.Bc : a.B), (unsigned)((a.tc + 31) / 32)), block(256);
 #define HEAD_LAUNCH_E(CS, EN)                                                                                             \
     switch (a.in_kind) {                                                                                                  \
-        case 1: hipLaunchKernelGGL((head_fused_kernel<RT, 1, CS, EN, TP>), grid, block, 0, s, a); break;                  \
-        case 2: hipLaunchKernelGGL((head_fused_kernel<RT, 2, CS, EN, TP>), grid, block, 0, s, a); break;                  \
-        case 3: hipLaunchKernelGGL((head_fused_kernel<RT, 3, CS, EN, TP>), grid, block, 0, s, a); break;                  \
-        case 4: hipLaunchKernelGGL((head_fused_kernel<RT, 4, CS, EN, TP>), grid, block, 0, s, a); break;                  \
-        default: hipLaunchKernelGGL((head_fused_kernel<RT, 0, CS, EN, TP>), grid, block, 0, s, a); break;                 \
+        case 1: hipLaunchKernelGGL((head_kernel_of<RT, 1, CS, EN, TP>()), grid, block, 0, s, a); break;                  \
+        case 2: hipLaunchKernelGGL((head_kernel_of<RT, 2, CS, EN, TP>()), grid, block, 0, s, a); break;                  \
+        case 3: hipLaunchKernelGGL((head_kernel_of<RT, 3, CS, EN, TP>()), grid, block, 0, s, a); break;                  \
+        case 4: hipLaunchKernelGGL((head_kernel_of<RT, 4, CS, EN, TP>()), grid, block, 0, s, a); break;                  \
+        default: hipLaunchKernelGGL((head_kernel_of<RT, 0, CS, EN, TP>()), grid, block, 0, s, a); break;                 \
     }
 #define HEAD_LAUNCH(CS) if (a.SH) { HEAD_LAUNCH_E(CS, true) } else { HEAD_LAUNCH_E(CS, false) }
     if constexpr (RT >= 3) {

@@ -4,18 +4,18 @@
 
 void launch_head_rt_temp(const HeadArgs& a, hipStream_t s) {
     switch ((a.C + 31) / 32) {
-        case 1: launch_rt<1, true>(a, s); break;
-        case 2: launch_rt<2, true>(a, s); break;
-        case 3: launch_rt<3, true>(a, s); break;
-        default: launch_rt<4, true>(a, s); break;
+        case 1: launch_rt<1, 1>(a, s); break;
+        case 2: launch_rt<2, 1>(a, s); break;
+        case 3: launch_rt<3, 1>(a, s); break;
+        default: launch_rt<4, 1>(a, s); break;
     }
 }
 
 void launch_head_rt_multi_temp(const HeadArgsPack& p, int n, hipStream_t s) {
     switch ((p.a[0].C + 31) / 32) {
-        case 1: launch_rt_multi<1, true>(p, n, s); break;
-        case 2: launch_rt_multi<2, true>(p, n, s); break;
-        case 3: launch_rt_multi<3, true>(p, n, s); break;
-        default: launch_rt_multi<4, true>(p, n, s); break;
+        case 1: launch_rt_multi<1, 1>(p, n, s); break;
+        case 2: launch_rt_multi<2, 1>(p, n, s); break;
+        case 3: launch_rt_multi<3, 1>(p, n, s); break;
+        default: launch_rt_multi<4, 1>(p, n, s); break;
     }
 }

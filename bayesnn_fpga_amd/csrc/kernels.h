@@ -124,6 +124,8 @@ struct HeadArgs {   // fused exit head (head_fused.hip)
                           // (last: the layout the kernels read stays what it was)
     float inv_tau;        // temperature scaling (bmi_engine_set_temperature): float32(1 / tau) of this exit — softmax, S1, S2 and SH are those of
                           // z = logit * inv_tau, SL and `logits` stay the raw logit — or 0: off, the untempered instantiations (appended as SH was)
+    const float* vec_scale; // vector scaling (bmi_engine_set_vector_scaling): this exit's device fp32 [C] rows — z_c = fl32(fl32(logit_c * vec_scale[c]) +
+    const float* vec_bias;  // vec_bias[c]) in place of the tempered z — or null: off (both or neither; never with inv_tau != 0; appended as inv_tau was)
 };
 int launch_head_fused(const HeadArgs& a, hipStream_t s);
 #define BMI_HEAD_PACK_MAX 8
@@ -188,6 +190,12 @@ int launch_nll_temperature_grid(const float* logits, int T, int E, int B, int C,
 // BMI_ERR_UNSUPPORTED (nothing launched): E > 32, or E rows of C | 1 floats beyond BMI_NLL_ENS_SLAB
 int launch_nll_ensemble_temperature_grid(const float* logits, int T, int E, int B, int C, const int* labels, const float* tau, unsigned vary_mask,
                                          const float* tau_cand, int G, double* nll, double* scratch, hipStream_t s);
+// calibration.hip (bmi_nll_vector_scaling_grad): nll [E], grad_scale / grad_bias [E][C] += value and gradient of the per-exit NLL of the T-mean
+// softmax of z = (double)l * scale[e][c] + bias[e][c] (device float64 [E][C]); scratch: [E][B][2C + 1] float64 per-image terms.
+// BMI_ERR_UNSUPPORTED (nothing launched) for the shapes nll_vector_takes refuses (C > 256, grid limits)
+bool nll_vector_takes(int E, int B, int C);
+int launch_nll_vector_scaling_grad(const float* logits, int T, int E, int B, int C, const int* labels, const double* scale, const double* bias,
+                                   double* nll, double* grad_scale, double* grad_bias, double* scratch, hipStream_t s);
 // ensemble.hip (bmi_ensemble_moments): Q1 / Q2 [E][B][C] and QH [E][B] += the moments and the entropy of the per-sample exit ensembles
 // q_te = mean_{i<=e} softmax(fl32(l_ti * inv_tau[i])) of logits [T][E][B][C], in sample order onto the running sums; inv_tau: host [E] or null
 #define BMI_ENS_MAX_EXITS 32
@@ -197,8 +205,11 @@ bool ensemble_takes(int E, int C);
 // its first n_e[b] exits; every row that is computed holds the plain launch's bits, the other rows are neither read nor written
 // W (device float64 [E][E] row-major, null: the equal-weight mean above): q_te = sum_{i<=e} W[e][i] p_ti in exit order, the weights as given;
 // of image b only the rows e < n_e[b] of W are read (bmi_engine_set_ensemble_weights, bmi_ensemble_moments_weighted)
+// vec_scale / vec_bias (device fp32 [E][C], both or neither, inv_tau null then): z = fl32(fl32(l * vec_scale[e][c]) + vec_bias[e][c]) in place
+// of the tempered product (bmi_engine_set_vector_scaling, bmi_ensemble_moments_vector)
 int launch_ensemble_moments(const float* logits, int T, int E, int B, int C, const float* inv_tau, double* Q1, double* Q2, double* QH,
-                            hipStream_t s, const int* list = nullptr, int Bc = 0, const int* n_e = nullptr, const double* W = nullptr);
+                            hipStream_t s, const int* list = nullptr, int Bc = 0, const int* n_e = nullptr, const double* W = nullptr,
+                            const float* vec_scale = nullptr, const float* vec_bias = nullptr);
 int launch_exit_counts(const int* exit_of, int n, int* n_e, hipStream_t s);      // n_e[b] = exit_of[b] + 1 (staged exit: the exits image b ran)
 // per (exit, image): mean / var of Q1 / Q2, the entropy of the mean, QH / T and their difference (bmi_finalize_ensemble)
 int launch_finalize_ensemble(int n_rows, int C, int t_total, const double* Q1, const double* Q2, const double* QH, double* mean, double* var,

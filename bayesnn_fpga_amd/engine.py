@@ -356,6 +356,33 @@ def check_ensemble_weights(w, n_exits):
     return W
 
 
+def check_vector_scaling(scale, bias, n_exits, out_dim):
+    """Vector scaling as two C-contiguous float32 arrays [E, C] (scale, bias), or (None, None) when ``scale`` is None (off).  ``scale`` / ``bias``:
+    [E, C], or [C] for every exit; ``bias`` None = zeros.  Raises ValueError for any other shape, for a bias without a scale and for a value
+    that is not finite (in float32, what the device is given).  No sign constraint.  Host only."""
+    if scale is None:
+        if bias is not None:
+            raise ValueError("vector scaling: a bias needs a scale")
+        return None, None
+    E, Cd = int(n_exits), int(out_dim)
+    out = []
+    for name, v in (("scale", scale), ("bias", bias)):
+        if v is None:
+            out.append(np.zeros((E, Cd), dtype=np.float32))
+            continue
+        raw = np.asarray(v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v, dtype=np.float64)
+        if raw.shape == (Cd,):
+            raw = np.broadcast_to(raw, (E, Cd))
+        elif raw.shape != (E, Cd):
+            raise ValueError(f"vector scaling: {name} must be [{E}, {Cd}] or [{Cd}] for {E} exits of {Cd} classes, got {list(raw.shape)}")
+        with np.errstate(over="ignore"):
+            f32 = np.ascontiguousarray(raw, dtype=np.float32)
+        if not (np.all(np.isfinite(raw)) and np.all(np.isfinite(f32))):
+            raise ValueError(f"vector scaling: every {name} value must be finite (in float32 too)")
+        out.append(f32)
+    return out[0], out[1]
+
+
 def vary_mask(vary, n_exits):
     """``vary`` of ensemble_nll_grid (an exit index, an iterable of indices, or None) as the bit mask bmi_nll_ensemble_temperature_grid
     takes; raises ValueError for an index outside [0, n_exits)."""
@@ -549,13 +576,55 @@ class MCDEngine(CompiledGraph):
         # train/calibration.py: EnsembleWeights) hands them to every engine built from it
         self._ens_w_keep = []
         self.set_ensemble_weights(getattr(model, "exit_ensemble_weights", None))
+        # vector scaling: a model that carries one (EngineModelMixin.set_exit_vector_scaling, train/calibration.py: VectorScaling) — never
+        # together with a temperature — hands it to every engine built from it
+        self._vec_keep = []
+        vs = getattr(model, "exit_vector_scaling", None)
+        if vs is not None:
+            self.set_vector_scaling(*vs)
 
     ensemble_weights = None       # float64 [E, E] on the host, or None: the equal-weight mean (set_ensemble_weights)
+    _vector_scaling = None        # (scale, bias) float32 [E, C] on the host, or None: off (set_vector_scaling)
 
     def close(self):
         self.__dict__.pop("_ens_scratch", None)      # (accumulate_ensemble's chunk of per-sample logits)
         super().close()                              # (the handle goes first: nothing reads the weight buffers any more)
         self.__dict__.pop("_ens_w_keep", None)
+        self.__dict__.pop("_vec_keep", None)
+
+    def set_vector_scaling(self, scale, bias=None):
+        """Per-class scale and bias of every exit's logits (bmi_engine_set_vector_scaling; Guo et al. 2017): ``scale`` / ``bias`` as
+        ``check_vector_scaling`` takes them — [E, C], or [C] for every exit, ``bias`` None = zeros — or ``scale`` None: off.  From the next
+        launch on every path through the fused head and the exit-ensemble launches computes softmax, mean, var, the entropies and the decisions
+        of ``z_c = float32(float32(logit_c * scale[e][c]) + bias[e][c])``; ``logit_mean``, ``forward_once`` and ``forward_samples`` stay the raw
+        logits, as under a temperature.  Off, the engine launches the kernels it did: the bits of an engine that never had one.  Mutually
+        exclusive with a temperature: ValueError while one (other than all ones) is set — ``set_temperature(None)`` first.  The arrays live
+        in device buffers the engine keeps; a hipGraph captured earlier keeps what it was captured with
+        (``BatchesInFlight.set_vector_scaling`` discards them)."""
+        a, b = check_vector_scaling(scale, bias, self.n_exits, self.out_dim)
+        if a is None:
+            rc = self.lib.bmi_engine_set_vector_scaling(self.handle, None, None, 0, 0)
+        else:
+            if any(t != 1.0 for t in self.temperature):
+                raise ValueError("vector scaling: a temperature is set on this engine (set_temperature(None) first: one calibration map at a time)")
+            bufs = (torch.from_numpy(a).to(self.device), torch.from_numpy(b).to(self.device))
+            self._vec_keep.append(bufs)              # never freed before close(): a captured launch may still hold an earlier pointer
+            rc = self.lib.bmi_engine_set_vector_scaling(self.handle, C.c_void_p(bufs[0].data_ptr()), C.c_void_p(bufs[1].data_ptr()), self.n_exits,
+                                                        self.out_dim)
+        _lib.check(rc, "bmi_engine_set_vector_scaling")
+        self._vector_scaling = None if a is None else (a, b)
+
+    @property
+    def vector_scaling(self):
+        """The vector scaling in force: (scale, bias), float32 [E, C] host arrays, or None when off."""
+        return self._vector_scaling
+
+    def set_temperature(self, tau):
+        tau = check_temperature(tau, self.n_exits)
+        if self._vector_scaling is not None and tau is not None and any(t != 1.0 for t in tau):
+            raise ValueError("temperature: a vector scaling is set on this engine (set_vector_scaling(None) first: one calibration map at a time)")
+        super().set_temperature(tau)
+    set_temperature.__doc__ = CompiledGraph.set_temperature.__doc__
 
     def set_ensemble_weights(self, w):
         """The weights of the exit ensembles (bmi_engine_set_ensemble_weights): ``w`` as ``check_ensemble_weights`` takes it — None (off),
@@ -796,19 +865,23 @@ class MCDEngine(CompiledGraph):
         self.accumulate_ensemble(x, S, H, Q, QH, t_begin, T, seed, cnt0)
         return self.finalize_ensemble(S, H, Q, QH, T)
 
-    def ensemble_moments(self, logits, tau=None, out=None, t_before=0, weights=None):
+    def ensemble_moments(self, logits, tau=None, out=None, t_before=0, weights=None, scale=None, bias=None):
         """The exit-ensemble read-out of per-sample logits the caller holds (bmi_ensemble_moments + bmi_finalize_ensemble): ``logits`` fp32
         [T, E, B, C] on the engine's device (``forward_samples``), ``tau`` None, a scalar or E temperatures (independent of the one set on
         this engine).  Returns the five ``ens_*`` entries of ``finalize_ensemble`` plus the sums ``Q`` [2, E, B, C] and ``QH`` [E, B];
         ``out=(Q, QH)`` ADDS into the sums of earlier calls that held ``t_before`` samples — the same bits as one call on all of them —
         and the results describe all ``t_before + T``.  ``weights`` (``check_ensemble_weights``: None, [E] or [E, E]; independent of the ones
-        set on this engine): the weighted ensembles, bmi_ensemble_moments_weighted.  ``train.uncertainty.decompose_ensemble_logits`` is the
-        host restatement."""
+        set on this engine): the weighted ensembles, bmi_ensemble_moments_weighted.  ``scale`` / ``bias`` (``check_vector_scaling``; not together
+        with ``tau``): the members under a vector scaling, bmi_ensemble_moments_vector, with or without ``weights``.
+        ``train.uncertainty.decompose_ensemble_logits`` is the host restatement."""
         if logits.dim() != 4 or logits.dtype != torch.float32 or not logits.is_contiguous() or logits.device != self.device:
             raise ValueError(f"logits must be contiguous float32 [T, E, B, C] on {self.device}")
         T, E, B, Cd = logits.shape
         tau = check_temperature(tau, E)
         W = check_ensemble_weights(weights, E)
+        va, vb = check_vector_scaling(scale, bias, E, Cd)
+        if va is not None and tau is not None:
+            raise ValueError("ensemble_moments: tau and scale / bias are mutually exclusive")
         if out is None:
             Q = torch.zeros(2, E, B, Cd, dtype=torch.float64, device=self.device)
             QH = torch.zeros(E, B, dtype=torch.float64, device=self.device)
@@ -818,6 +891,17 @@ class MCDEngine(CompiledGraph):
                     not Q.is_contiguous() or not QH.is_contiguous() or Q.device != self.device or QH.device != self.device:
                 raise ValueError("out must be contiguous float64 (Q [2, E, B, C], QH [E, B]) on the engine's device")
         tau_c = None if tau is None else (C.c_float * E)(*tau)
+        if va is not None:
+            with torch.cuda.device(self.device):
+                a_dev, b_dev = torch.from_numpy(va).to(self.device), torch.from_numpy(vb).to(self.device)      # (freed in stream order behind the launch)
+                w_dev = None if W is None else torch.from_numpy(W).to(self.device)
+                rc = self.lib.bmi_ensemble_moments_vector(logits.data_ptr(), T, E, B, Cd, a_dev.data_ptr(), b_dev.data_ptr(),
+                                                          None if w_dev is None else w_dev.data_ptr(), Q[0].data_ptr(), Q[1].data_ptr(),
+                                                          QH.data_ptr(), self._stream())
+            _lib.check(rc, "bmi_ensemble_moments_vector")
+            r = self._finalize_ensemble_sums(Q, QH, int(t_before) + T)
+            r.update(Q=Q, QH=QH)
+            return r
         with torch.cuda.device(self.device):
             if W is None:
                 rc = self.lib.bmi_ensemble_moments(logits.data_ptr(), T, E, B, Cd, tau_c, Q[0].data_ptr(), Q[1].data_ptr(), QH.data_ptr(),
@@ -1115,6 +1199,41 @@ class MCDEngine(CompiledGraph):
         _lib.check(rc, "bmi_nll_temperature_grid")
         return out
 
+    def nll_vector_grad(self, logits, labels, scale, bias, out=None):
+        """Value and gradient of a vector-scaling fit on the device (bmi_nll_vector_scaling_grad): ``logits`` / ``labels`` as ``nll_grid``'s,
+        ``scale`` / ``bias`` float64 [E, C] (arrays or tensors; taken as float64: the optimiser's point, not the head's float32).  ADDS, per
+        exit, sum_b -log mean_t softmax(l_tb * scale + bias)[y_b] and its gradients into ``out`` = (nll [E], g_scale [E, C], g_bias [E, C]),
+        device float64 (zeros when None), and returns the triple: a walk over a loader accumulates.  float64 throughout, the same bits on
+        every run; ``train.calibration.nll_vector_numpy`` is its host restatement.  Independent of what is set on this engine."""
+        T, E, B, Cd = logits.shape
+        if logits.dtype != torch.float32 or not logits.is_contiguous() or logits.device != self.device:
+            raise ValueError(f"logits must be contiguous float32 [T, E, B, C] on {self.device}")
+        if tuple(labels.shape) != (B,):
+            raise ValueError(f"labels must be [B] = [{B}]")
+        labels = labels.to(device=self.device, dtype=torch.int32).contiguous()
+        scale = torch.as_tensor(scale, dtype=torch.float64).to(self.device).contiguous()
+        bias = torch.as_tensor(bias, dtype=torch.float64).to(self.device).contiguous()
+        if tuple(scale.shape) != (E, Cd) or tuple(bias.shape) != (E, Cd):
+            raise ValueError(f"scale and bias must be [E, C] = [{E}, {Cd}]")
+        if out is None:
+            out = (torch.zeros(E, dtype=torch.float64, device=self.device), torch.zeros(E, Cd, dtype=torch.float64, device=self.device),
+                   torch.zeros(E, Cd, dtype=torch.float64, device=self.device))
+        else:
+            shapes = ((E,), (E, Cd), (E, Cd))
+            if len(out) != 3 or any(tuple(o.shape) != sh or o.dtype != torch.float64 or not o.is_contiguous() or o.device != self.device
+                                    for o, sh in zip(out, shapes)):
+                raise ValueError("out must be contiguous float64 (nll [E], g_scale [E, C], g_bias [E, C]) on the engine's device")
+        need = int(self.lib.bmi_nll_vector_scratch_bytes(E, B, Cd))
+        scratch = self.__dict__.get("_nll_scratch")
+        if scratch is None or scratch.numel() < need:
+            scratch = self.__dict__["_nll_scratch"] = torch.empty(need, dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = self.lib.bmi_nll_vector_scaling_grad(logits.data_ptr(), T, E, B, Cd, labels.data_ptr(), scale.data_ptr(), bias.data_ptr(),
+                                                      out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), scratch.data_ptr(),
+                                                      scratch.numel(), self._stream())
+        _lib.check(rc, "bmi_nll_vector_scaling_grad")
+        return out
+
     def ensemble_nll_grid(self, logits, labels, tau, vary, cand, out=None):
         """The objective of a joint temperature fit of the exit ensembles on the device (bmi_nll_ensemble_temperature_grid): ``logits`` /
         ``labels`` as ``nll_grid``'s, ``tau`` the current temperatures (one per exit, a scalar for all, None for ones), ``vary`` the exits
@@ -1308,6 +1427,16 @@ class BatchesInFlight:
         self.synchronize()
         for e in self.engines:
             e.set_temperature(tau)
+        for attr in ("_graphs", "_gstreams"):
+            if hasattr(self, attr):
+                delattr(self, attr)
+
+    def set_vector_scaling(self, scale, bias=None):
+        """``MCDEngine.set_vector_scaling`` on every engine of the pipe; the captured hipGraphs are discarded (after a synchronize), like
+        ``set_temperature``'s: a replay would run the instantiation and the pointers it was captured with."""
+        self.synchronize()
+        for e in self.engines:
+            e.set_vector_scaling(scale, bias)
         for attr in ("_graphs", "_gstreams"):
             if hasattr(self, attr):
                 delattr(self, attr)

@@ -25,6 +25,7 @@ class EngineModelMixin:
     auto_candidates = AUTO_CANDIDATES
     auto_tol = AUTO_TOL
     exit_temperature = None   # per-exit softmax temperatures (a plain list of floats: survives torch.save(model)), or None: off — set_exit_temperature
+    exit_vector_scaling = None   # per-exit vector scaling (a pair of plain float32 arrays [E, C], scale and bias: survives torch.save(model)), or None: off — set_exit_vector_scaling; never together with exit_temperature
     exit_ensemble_weights = None   # the weights of the exit ensembles (a plain float64 array [E, E]: survives torch.save(model)), or None: the equal mean — set_exit_ensemble_weights
 
     def _init_engine_state(self):
@@ -68,7 +69,24 @@ class EngineModelMixin:
         list, and treated like a weight change: compiled engines, pipes with their captured graphs and the ``engine_dtype="auto"`` decision
         were all made under the other softmax and are dropped — the next use rebuilds them (and re-decides "auto") under this one."""
         from ..engine import check_temperature, model_exits
-        self.exit_temperature = check_temperature(tau, model_exits(self))
+        tau = check_temperature(tau, model_exits(self))
+        if tau is not None and self.exit_vector_scaling is not None:
+            raise ValueError("set_exit_temperature: a vector scaling is set (set_exit_vector_scaling(None) first: one calibration map at a time)")
+        self.exit_temperature = tau
+        self._drop_engines()
+
+    def set_exit_vector_scaling(self, scale, bias=None):
+        """Per-exit vector scaling of everything the engines compute from this model's softmax (``MCDEngine.set_vector_scaling``: z_c = l_c *
+        scale[e][c] + bias[e][c] in the head's fp32; mean, var, the entropies, the exit ensembles and the decisions; never the logits):
+        ``scale`` / ``bias`` [E, C], or [C] for every exit, ``bias`` None = zeros, every value finite; ``scale`` None = off;
+        ``train.calibration.VectorScaling`` fits it on a validation split.  Stored on the model as two plain float32 arrays and treated like
+        ``set_exit_temperature``: compiled engines, pipes and the "auto" decision are dropped.  Mutually exclusive with a temperature:
+        ValueError while ``exit_temperature`` is set — ``set_exit_temperature(None)`` first."""
+        from ..engine import check_vector_scaling, model_exits
+        a, b = check_vector_scaling(scale, bias, model_exits(self), int(self.out_dim))
+        if a is not None and self.exit_temperature is not None:
+            raise ValueError("set_exit_vector_scaling: a temperature is set (set_exit_temperature(None) first: one calibration map at a time)")
+        self.exit_vector_scaling = None if a is None else (a, b)
         self._drop_engines()
 
     def set_exit_ensemble_weights(self, w):

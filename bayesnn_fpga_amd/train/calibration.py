@@ -39,9 +39,23 @@ is convex in w: EM on the [E, N] table is exact and monotone, runs on the host, 
 * ``mixture_weights_em`` — the EM iteration for one row.
 * ``EnsembleWeights``    — the loader-level fit: the walk of ``TemperatureScaling``, the table gathered on the device, EM per row.
 
-THE ORDER: fit the temperatures first (``TemperatureScaling`` or ``EnsembleTemperatureScaling``), ``apply()`` them, then fit the weights AT
-those temperatures — the members are then fixed and the problem is convex.  The joint temperature fit's objective stays the equal-weight
-ensemble's; a joint fit of weights and temperatures is not built.
+One scalar per exit cannot correct class-wise miscalibration.  VECTOR SCALING (Guo et al. 2017) gives every exit a per-class scale and
+bias, z_c = a_c * l_c + b_c (``MCDEngine.set_vector_scaling``: two rounded fp32 operations inside the fused head, in place of the
+temperature's product; the two are mutually exclusive), fitted on the same objective with z in place of l / tau,
+
+    nll_e(a, b) = sum_n -log( (1/T) sum_t softmax(a * l_tn + b)[y_n] ),
+
+whose value and gradient come from the device in one call for all exits (``MCDEngine.nll_vector_grad``, bmi_nll_vector_scaling_grad).
+
+* ``scale_logits``     — mean / var of the scaled per-sample softmax, the restatement of what the head computes under a vector scaling.
+* ``nll_vector_numpy`` — float64 restatement of the device objective, value and both gradients.
+* ``lbfgs_minimize``   — a small deterministic L-BFGS with Armijo backtracking, the exits as independent problems in the same evaluations.
+* ``VectorScaling``    — the loader-level fit, on the same walk as ``TemperatureScaling``, started at the scalar fit.
+
+THE ORDER: fit the temperatures (``TemperatureScaling`` or ``EnsembleTemperatureScaling``) OR the vector scaling (``VectorScaling``) first,
+``apply()``, then fit the weights AT those members — they are then fixed and the problem is convex (``EnsembleWeights`` reads ``predict``'s
+means, so it needs no change: weights fitted after ``VectorScaling.apply()`` are fitted at the scaled members).  The joint temperature
+fit's objective stays the equal-weight ensemble's; a joint fit of weights and temperatures, or of weights and a vector scaling, is not built.
 """
 import numpy as np
 import torch
@@ -144,6 +158,139 @@ def temper_logits(logits, tau):
     p = np.exp(z)
     p /= p.sum(-1, keepdims=True)
     return p.mean(0), p.var(0)
+
+
+def scale_logits(logits, scale, bias=None):
+    """(mean, var), float64 [E, B, C]: over the T samples of ``logits`` [T, E, B, C], the mean and the variance (ddof = 0) of
+    softmax(float32(float32(l * scale) + bias)) — the two rounded fp32 operations the exit head forms under a vector scaling, the softmax in
+    float64 like ``temper_logits``.  ``scale`` / ``bias``: [E, C], or [C] for every exit; ``bias`` None = zeros."""
+    from ..engine import check_vector_scaling
+    logits = np.asarray(logits)
+    E, C = logits.shape[1], logits.shape[3]
+    a, b = check_vector_scaling(scale, bias, E, C)
+    z = (logits.astype(np.float32) * a[None, :, None, :]).astype(np.float32)
+    z = (z + b[None, :, None, :]).astype(np.float32).astype(np.float64)
+    z -= z.max(-1, keepdims=True)
+    p = np.exp(z)
+    p /= p.sum(-1, keepdims=True)
+    return p.mean(0), p.var(0)
+
+
+def nll_vector_numpy(logits, labels, scale, bias):
+    """(nll [E], g_scale [E, C], g_bias [E, C]), float64: value and gradient of sum_b -log mean_t softmax(l_tb * scale_e + bias_e)[y_b] for
+    ``logits`` [T, E, B, C], ``labels`` [B], ``scale`` / ``bias`` [E, C] taken as float64.  bmi_nll_vector_scaling_grad's arithmetic in
+    log-sum-exp form:  z = float64(l) * a + b;  A_t = (z_y - max_c z) - log sum_c exp(z_c - max_c z);  term_b = -(logsumexp_t A_t - log T);
+    r_t = exp(A_t) / sum_t' exp(A_t'),  p_t = softmax(z_t):  d term / d b_c = sum_t r_t (p_tc - [c == y]),  d term / d a_c the same with a
+    factor l_tc.  sum_c g_bias = 0 identically."""
+    logits = np.asarray(logits)
+    T, E, B, C = logits.shape
+    labels = np.asarray(labels).astype(np.int64).reshape(B)
+    if labels.min() < 0 or labels.max() >= C:
+        raise ValueError(f"labels must lie in [0, {C})")
+    a = np.asarray(scale, dtype=np.float64)
+    b = np.asarray(bias, dtype=np.float64)
+    if a.shape != (E, C) or b.shape != (E, C):
+        raise ValueError(f"scale and bias must be [E, C] = [{E}, {C}]")
+    idx = np.arange(B)
+    hot = np.zeros((B, C))
+    hot[idx, labels] = 1.0
+    nll, ga, gb = np.zeros(E), np.zeros((E, C)), np.zeros((E, C))
+    for e in range(E):
+        l = logits[:, e].astype(np.float64)                      # [T, B, C]
+        z = l * a[e] + b[e]
+        zmax = z.max(-1)
+        ex = np.exp(z - zmax[..., None])
+        s = ex.sum(-1)
+        A = (z[:, idx, labels] - zmax) - np.log(s)               # [T, B]
+        am = A.max(0)
+        w = np.exp(A - am)
+        S = w.sum(0)
+        nll[e] = np.sum(-((am + np.log(S)) - np.log(float(T))))
+        d = (w / S)[..., None] * (ex / s[..., None] - hot)        # [T, B, C]
+        gb[e] = d.sum((0, 1))
+        ga[e] = (d * l).sum((0, 1))
+    return nll, ga, gb
+
+
+def lbfgs_minimize(fun, x0, max_iter=100, gtol=1e-6, history=10, c1=1e-4, max_backtracks=30):
+    """A small deterministic L-BFGS for P independent problems evaluated together: ``fun(x [P, D] float64) -> (f [P], g [P, D])``, every
+    call evaluates all P problems (a problem that is not moving is evaluated where it stands).  Per problem: the two-loop recursion over
+    the last ``history`` pairs (pairs with s.y <= 0 are skipped; a direction that is not a descent direction restarts from -g), then Armijo
+    backtracking from step 1 (first iteration: 1 / max(1, |g|_inf)) by halving — a step is accepted only when f_new <= f + c1 t g.d, so
+    every accepted iterate lowers the objective; non-finite values count as rejected.  A problem stops when |g|_inf <= ``gtol``
+    (``converged``) or when ``max_backtracks`` halvings find no decrease (the step is below what float64 resolves: not ``converged``
+    unless the gradient test holds); the run after ``max_iter`` iterations.
+
+    Returns dict(x [P, D], f [P], g [P, D], iterations [P], converged bool [P], trace (list of f [P] after each iteration, trace[0] the
+    start), n_eval)."""
+    x = np.array(x0, dtype=np.float64)
+    if x.ndim != 2:
+        raise ValueError("x0 must be [P, D]")
+    P = x.shape[0]
+    f, g = fun(x)
+    f, g = np.array(f, dtype=np.float64).reshape(P), np.array(g, dtype=np.float64).reshape(x.shape)
+    n_eval = 1
+    S, Y = [[] for _ in range(P)], [[] for _ in range(P)]
+    active = np.array([np.isfinite(f[p]) and np.max(np.abs(g[p])) > gtol for p in range(P)])
+    converged = np.array([np.isfinite(f[p]) and np.max(np.abs(g[p])) <= gtol for p in range(P)])
+    iterations = np.zeros(P, dtype=np.int64)
+    trace = [f.copy()]
+    for it in range(int(max_iter)):
+        if not active.any():
+            break
+        d, gd, t = np.zeros_like(x), np.zeros(P), np.zeros(P)
+        for p in np.flatnonzero(active):
+            q = g[p].copy()
+            alphas = []
+            for s_, y_ in zip(reversed(S[p]), reversed(Y[p])):
+                al = s_.dot(q) / y_.dot(s_)
+                alphas.append(al)
+                q -= al * y_
+            if S[p]:
+                q *= S[p][-1].dot(Y[p][-1]) / Y[p][-1].dot(Y[p][-1])
+            for (s_, y_), al in zip(zip(S[p], Y[p]), reversed(alphas)):
+                q += (al - y_.dot(q) / y_.dot(s_)) * s_
+            d[p], gd[p] = -q, -q.dot(g[p])
+            if not gd[p] < 0:
+                S[p], Y[p] = [], []
+                d[p], gd[p] = -g[p], -g[p].dot(g[p])
+            t[p] = 1.0 if S[p] else 1.0 / max(1.0, float(np.max(np.abs(g[p]))))
+        searching = active.copy()
+        x_new, f_new, g_new = x.copy(), f.copy(), g.copy()
+        for _ in range(int(max_backtracks)):
+            trial = x.copy()
+            for p in np.flatnonzero(searching):
+                trial[p] = x[p] + t[p] * d[p]
+            ft, gt = fun(trial)
+            ft, gt = np.asarray(ft, dtype=np.float64).reshape(P), np.asarray(gt, dtype=np.float64).reshape(x.shape)
+            n_eval += 1
+            for p in np.flatnonzero(searching):
+                if np.isfinite(ft[p]) and np.all(np.isfinite(gt[p])) and ft[p] <= f[p] + c1 * t[p] * gd[p]:
+                    x_new[p], f_new[p], g_new[p] = trial[p], ft[p], gt[p]
+                    searching[p] = False
+                else:
+                    t[p] *= 0.5
+            if not searching.any():
+                break
+        for p in np.flatnonzero(active):
+            if searching[p]:                                     # no decrease found: this problem ends where it stands
+                active[p] = False
+                continue
+            s_, y_ = x_new[p] - x[p], g_new[p] - g[p]
+            if s_.dot(y_) > 1e-12 * np.sqrt(s_.dot(s_) * y_.dot(y_)):
+                S[p].append(s_)
+                Y[p].append(y_)
+                if len(S[p]) > history:
+                    S[p].pop(0)
+                    Y[p].pop(0)
+            iterations[p] += 1
+        x, f, g = x_new, f_new, g_new
+        trace.append(f.copy())
+        for p in range(P):
+            if np.max(np.abs(g[p])) <= gtol:
+                converged[p] = True
+                active[p] = False
+    return dict(x=x, f=f, g=g, iterations=iterations, converged=converged, trace=trace, n_eval=n_eval)
 
 
 def _log_grid(lo, hi, n):
@@ -358,6 +505,76 @@ class TemperatureScaling:
         if self.result is None:
             raise RuntimeError("fit() first")
         name = f"temperature_{experiment_id}.npz"
+        np.savez(name, **{k: np.asarray(v) for k, v in self.result.items()})
+        return name
+
+
+class VectorScaling(TemperatureScaling):
+    """Fits a per-class scale and bias per exit (vector scaling) on a labelled (validation) loader.
+
+        vs = VectorScaling(model, val_loader, gpu=0, mc_passes=10)
+        vs.fit()            # dict(scale, bias, nll_start, nll_after, grad_norm, iterations, converged, n)
+        vs.apply()          # model.set_exit_temperature(None); model.set_exit_vector_scaling(scale, bias)
+
+    The walk and the ``max_logit_bytes`` rule are ``TemperatureScaling``'s.  The search starts at the scalar fit of the same logits — a =
+    1 / tau_e for every class, b = 0, tau from ``zoom_search`` — and runs ``lbfgs_minimize`` on the 2C parameters of every exit, all exits
+    in the same ``MCDEngine.nll_vector_grad`` launches (one per batch and evaluation), in float64.  The result is rounded to float32 once
+    and ``nll_after`` is evaluated once more at the ROUNDED parameters — what the head will run; should that rounding not keep the
+    start's value (a fit that did not move), the rounded start is returned.  sum_c of the bias gradient is 0, so the bias stays in the
+    zero-sum gauge it starts in.  Raw logits depend on neither a temperature nor a vector scaling set on the model: a fit can be repeated."""
+
+    def fit(self, max_iter=50, gtol=1e-5, history=10, **search):
+        """Walk + scalar search (keyword arguments ``search`` go to ``zoom_search``) + L-BFGS.  Returns — and keeps in ``self.result`` —
+        dict(scale, bias float32 [E, C]; nll_start (the scalar fit's NLL), nll_after, grad_norm (|g|_inf at the optimiser's last point),
+        iterations, converged [E] each; tau [E] (the scalar fit); n)."""
+        from ..engine import model_exits
+        batches = self.collect()
+        eng, E, C = self._engine, model_exits(self.model), int(self.model.out_dim)
+
+        def eval_tau(tau):
+            out = None
+            grid = torch.from_numpy(np.ascontiguousarray(tau, dtype=np.float32)).to(self.device)
+            for logits, y in batches:
+                out = eng.nll_grid(logits, y, grid, out=out)
+            return out.cpu().numpy()
+
+        def eval_vec(x):
+            a = torch.from_numpy(np.ascontiguousarray(x[:, :C])).to(self.device)
+            b = torch.from_numpy(np.ascontiguousarray(x[:, C:])).to(self.device)
+            out = None
+            for logits, y in batches:
+                out = eng.nll_vector_grad(logits, y, a, b, out=out)
+            return out[0].cpu().numpy(), np.concatenate([out[1].cpu().numpy(), out[2].cpu().numpy()], axis=1)
+
+        z = zoom_search(eval_tau, E, **search)
+        inv = 1.0 / np.asarray(z["tau"], dtype=np.float32).astype(np.float64)
+        x0 = np.concatenate([np.repeat(inv[:, None], C, axis=1), np.zeros((E, C))], axis=1)
+        r = lbfgs_minimize(eval_vec, x0, max_iter=max_iter, gtol=gtol, history=history)
+        x32 = r["x"].astype(np.float32)
+        x032 = x0.astype(np.float32)
+        nll_after = eval_vec(x32.astype(np.float64))[0]
+        nll_x0 = eval_vec(x032.astype(np.float64))[0]
+        keep = nll_after <= nll_x0                               # (a fit that moved: always)
+        x32 = np.where(keep[:, None], x32, x032)
+        nll_after = np.where(keep, nll_after, nll_x0)
+        self.result = dict(scale=np.ascontiguousarray(x32[:, :C]), bias=np.ascontiguousarray(x32[:, C:]), nll_start=z["nll_after"], nll_after=nll_after,
+                           grad_norm=np.max(np.abs(r["g"]), axis=1), iterations=r["iterations"], converged=r["converged"],
+                           tau=np.asarray(z["tau"]), n=int(sum(y.numel() for _, y in batches)))
+        return self.result
+
+    def apply(self):
+        """Clears the model's temperature and sets the fitted scaling: ``model.set_exit_vector_scaling(scale, bias)``."""
+        if self.result is None:
+            raise RuntimeError("fit() first")
+        self.model.set_exit_temperature(None)
+        self.model.set_exit_vector_scaling(self.result["scale"], self.result["bias"])
+        return self.model.exit_vector_scaling
+
+    def save(self, experiment_id):
+        """Writes ``vector_scaling_<id>.npz`` (every entry of the result) and returns its name."""
+        if self.result is None:
+            raise RuntimeError("fit() first")
+        name = f"vector_scaling_{experiment_id}.npz"
         np.savez(name, **{k: np.asarray(v) for k, v in self.result.items()})
         return name
 

@@ -50,7 +50,7 @@ def weighted_exit_ensembles(per_exit, W):
     return out
 
 
-def decompose_ensemble_logits(logits, tau=None, weights=None):
+def decompose_ensemble_logits(logits, tau=None, weights=None, scale=None, bias=None):
     """The exit ensembles as predictors, from per-pass logits [T, E, B, C] (``MCDEngine.forward_samples``), float64 on the host: the
     definition csrc/ensemble.hip implements on the device (``MCDEngine.predict_ensemble`` / ``ensemble_moments``).  Per pass t the members
     are p_te = softmax(z_te), z = the fp32 logit, or with ``tau`` (a scalar or E temperatures) the tempered head's ONE rounded fp32 product
@@ -59,7 +59,9 @@ def decompose_ensemble_logits(logits, tau=None, weights=None):
     0 —, pred_entropy H[mean], exp_entropy E_t H[q_t], mutual_info [E, B] — clamped at 0), entropies in nats.  Row 0 is exit 0 itself.
     The exits of one pass share the trunk's draw: ``var`` is NOT sum_i var_i / (e + 1)^2.  ``weights`` (None, [E] or [E, E]:
     ``engine.check_ensemble_weights``): the weighted ensembles q_te = ((W[e][0] p_t0 + W[e][1] p_t1) + ...) + W[e][e] p_te — every product
-    rounded, added in exit order from 0.0, no renormalisation — in place of the equal mean; everything behind q is the same."""
+    rounded, added in exit order from 0.0, no renormalisation — in place of the equal mean; everything behind q is the same.  ``scale`` /
+    ``bias`` (``engine.check_vector_scaling``: [E, C] or [C], bias None = zeros; not together with ``tau``): the members under a vector
+    scaling, z = float32(float32(l * scale) + bias), the vector-scaled head's two rounded fp32 operations."""
     l = np.asarray(logits, dtype=np.float32)
     if l.ndim != 4:
         raise ValueError("logits must be [T, E, B, C]")
@@ -71,6 +73,12 @@ def decompose_ensemble_logits(logits, tau=None, weights=None):
             raise ValueError(f"tau: expected one value per exit ({E}), got {t32.size}")
         inv = (1.0 / t32.astype(np.float64)).astype(np.float32)
         l = (l * inv[None, :, None, None]).astype(np.float32)
+    if scale is not None:
+        if tau is not None:
+            raise ValueError("tau and scale / bias are mutually exclusive")
+        from ..engine import check_vector_scaling
+        va, vb = check_vector_scaling(scale, bias, E, l.shape[3])
+        l = ((l * va[None, :, None, :]).astype(np.float32) + vb[None, :, None, :]).astype(np.float32)
     W = None
     if weights is not None:
         from ..engine import check_ensemble_weights

@@ -620,6 +620,48 @@ int bmi_nll_ensemble_temperature_grid(const float* logits, int32_t T, int32_t E,
  * BMI_ERR_INVALID: a NULL handle, n_exits other than the engine's.  bmi_finalize_ensemble* need no change: they read the sums. */
 int bmi_engine_set_ensemble_weights(bmi_handle h, const double* W_device, int32_t n_exits);
 
+/* Vector scaling (Guo et al. 2017): a per-class scale and bias per exit in place of the one scalar of bmi_engine_set_temperature.
+ * scale_device / bias_device: DEVICE fp32 [n_exits][out_dim], owned by the caller and alive for as long as they are set; every value
+ * finite, no sign constraint (used AS GIVEN: validating them is the caller's job, the Python layer does).  scale_device NULL: off.  At the
+ * place the temperature acts — behind the classifier bias and a site on the logits, in front of the running max — every sample's logits
+ * become
+ *     z_c = fl32( fl32(l_c * scale[e][c]) + bias[e][c] )                         two rounded fp32 operations, never one fused multiply-add
+ * and the max, the softmax, S1, S2 and the per-sample entropy (SH) are those of z.  SL and the per-sample logits of
+ * bmi_forward_mcd_samples stay the RAW l, as under a temperature.  Every bmi_forward_mcd* entry point honours it, the ensemble launches
+ * of the *_ensemble entry points included (their z is the number above, in place of fl32(l * inv_e)); the decision kernels read the
+ * scaled sums; bmi_head_fused does not.  Off, the launches are the kernels they were and every output keeps its bits.  The pointers are
+ * read at launch: a captured hipGraph keeps what was set at capture.
+ * Temperature and vector scaling are mutually exclusive; clearing one is how to switch.  BMI_ERR_INVALID: a NULL handle, a NULL
+ * bias_device with a scale, n_exits / out_dim other than the engine's, or a temperature other than all ones in force; and
+ * bmi_engine_set_temperature returns BMI_ERR_INVALID for a temperature other than all ones while a vector scaling is set. */
+int bmi_engine_set_vector_scaling(bmi_handle h, const float* scale_device, const float* bias_device, int32_t n_exits, int32_t out_dim);
+
+/* bmi_ensemble_moments_weighted with tau replaced by the two device arrays of bmi_engine_set_vector_scaling (fp32 [E][C]):
+ *     z_te,c = (double) fl32( fl32(l * scale[e][c]) + bias[e][c] )
+ * and everything behind it unchanged.  W_device may be NULL (the equal-weight mean).  BMI_ERR_INVALID: a null pointer otherwise, a count
+ * below 1; BMI_ERR_UNSUPPORTED as bmi_ensemble_moments. */
+int bmi_ensemble_moments_vector(const float* logits, int32_t T, int32_t E, int32_t B, int32_t C, const float* scale_device, const float* bias_device,
+                                const double* W_device, double* Q1, double* Q2, double* QH, bmi_stream stream);
+
+/* Value and gradient of a vector-scaling fit on per-sample logits, all E exits in one call.  logits / labels as
+ * bmi_nll_temperature_grid's; scale / bias: device float64 [E][C]; nll: device float64 [E], grad_scale / grad_bias: device float64
+ * [E][C], all three ADDED TO (a walk over a loader accumulates in call order).  All in float64, no fused multiply-add, y = labels[b]:
+ *     z_tc = (double)l_tebc * scale[e][c] + bias[e][c]                              (the optimiser's smooth objective: the fp32 rounding of
+ *                                                                                    the head happens once, when a result is applied)
+ *     A_t  = (z_ty - max_c z_tc) - log sum_c exp(z_tc - max_c z_tc),    nll[e] += sum_b -( logsumexp_t A_t - log T )
+ *     p_tc = softmax_c(z_t),   r_t = exp(A_t) / sum_t' exp(A_t')
+ *     grad_bias[e][c]  += sum_b sum_t r_t (p_tc - [c == y])
+ *     grad_scale[e][c] += sum_b sum_t r_t (p_tc - [c == y]) * l_tebc
+ * One workgroup per (image, exit) stages min(64, 3456 / (C | 1)) samples at a time; a larger T runs in chunks of samples with the running
+ * log-sum-exp state carried.  Bit-reproducible: per-image terms go to `scratch` ([E][B][2C + 1] float64,
+ * bmi_nll_vector_scratch_bytes, 0 for a count below 1) and a second kernel sums them over the images in a fixed order; no floating-point
+ * atomics.  No allocation, no synchronisation.  BMI_ERR_INVALID (decided before any HIP call): a null pointer, a count below 1.
+ * BMI_ERR_UNSUPPORTED: C > 256 or E > 65535.  BMI_ERR_NOMEM: scratch too small.  An error writes nothing. */
+size_t bmi_nll_vector_scratch_bytes(int32_t E, int32_t B, int32_t C);
+int bmi_nll_vector_scaling_grad(const float* logits, int32_t T, int32_t E, int32_t B, int32_t C, const int32_t* labels, const double* scale,
+                                const double* bias, double* nll, double* grad_scale, double* grad_bias, void* scratch, size_t scratch_bytes,
+                                bmi_stream stream);
+
 /* Per-op-kind HIP-event timing of bmi_forward_mcd (off by default; adds two event records per
  * launch).  bmi_profile_read synchronises the recorded events and resets the accumulators. */
 int bmi_profile_enable(bmi_handle h, int32_t enable);
