@@ -94,22 +94,57 @@ struct bmi_engine_s {
     int64_t prefix_macs = 0, suffix_macs = 0;
     // plan
     int max_batch = 0, chunk = 0;
-    size_t ws_bytes = 0, exit_off = 0;   // exit_off: 2 active-image lists + a counter (dynamic early exit)
+    size_t ws_bytes = 0, exit_off = 0;   // exit_off: ActiveImages' region (dynamic early exit, adaptive sampling)
     size_t splitk_off = 0;               // fp32 partial sums of the split-K prefix convs
     size_t head_off = 0, head_part_bytes = 0;   // float64 partial sums of a head launch's 32-sample groups (joined in group order), one region per exit
     std::vector<std::pair<const float*, size_t>> perm;   // (bmi_plan) Masksembles tables (device pointer of the site) -> workspace offset of the permuted copy
     std::vector<float> tau;              // bmi_engine_set_temperature: the temperatures as given ([n_exits]; empty: never set = ones)
-    std::vector<float> inv_tau;          // float32(1 / (double)tau[e]) per exit, what the heads multiply by; EMPTY when off (never set, or all ones)
-    const float* vec_scale = nullptr;    // bmi_engine_set_vector_scaling: the caller's DEVICE fp32 [n_exits][out_dim] scales and biases (not owned), null: off;
-    const float* vec_bias = nullptr;     // never together with a non-unit temperature (inv_tau is empty while these are set)
-    const double* ens_w = nullptr;       // bmi_engine_set_ensemble_weights: the caller's DEVICE [n_exits][n_exits] float64 (not owned), null: the equal-weight mean
-    std::vector<char> staged_ok;         // (bmi_plan) per first_exit: the staged suffix order keeps every shared workspace range's live ranges apart
+    Calibration cal;                     // the calibration map in force (kernels.h): written by the three setters below, read by make_head_args and ensemble_add
+    std::vector<char> staged_ok;        // (bmi_plan) per first_exit: the staged suffix order keeps every shared workspace range's live ranges apart
     // profiling
     bool profiling = false;
     double fam_ms[BMI_CONV_FAMILIES] = {0}, fam_flops[BMI_CONV_FAMILIES] = {0}, fam_bytes[BMI_CONV_FAMILIES] = {0};
     int64_t fam_launches[BMI_CONV_FAMILIES] = {0};
     std::vector<ProfRec> recs, last;   // last: the launches of the most recent bmi_profile_read (bmi_profile_launches)
     std::vector<hipEvent_t> pool;
+};
+
+// The active images of a dynamic call (bmi_forward_mcd_exit, _exit_staged, _adaptive) and the exit region of the workspace they live in: from
+// exit_off, in ints, two image lists of max_batch entries, a decide kernel's counter (64 ints), the row table of max_batch x chunk entries.
+// act / rows / bc: run_op's imap / rows / Bc of the call's next launches (act null: every image is active).  A decide kernel reads act and
+// writes the images that go on to next(), their number to count_dev.
+struct ActiveImages {
+    static size_t counter_at(size_t max_batch) { return 2 * max_batch; }
+    static size_t rows_at(size_t max_batch) { return counter_at(max_batch) + 64; }
+    static size_t ints(size_t max_batch, size_t rows) { return rows_at(max_batch) + rows; }
+    int* lists[2];
+    int *count_dev, *rows_dev;
+    const int batch;
+    const hipStream_t s;
+    const int* act = nullptr;
+    const int* rows = nullptr;
+    int bc;
+    int cur = 0;                    // the free list: not the one act points into
+    ActiveImages(const bmi_engine_s* h, char* ws, int batch_, hipStream_t s_) : batch(batch_), s(s_), bc(batch_) {
+        int* const base = (int*)(ws + h->exit_off);
+        lists[0] = base; lists[1] = base + h->max_batch;
+        count_dev = base + counter_at(h->max_batch);
+        rows_dev = base + rows_at(h->max_batch);
+    }
+    int* next() const { return lists[cur]; }
+    // Behind a decide kernel: how many images go on (the host's only look at the decision: one copy, one synchronise) ...
+    int read_count(int* n_active) const {
+        const bool ok = hipMemcpyAsync(n_active, count_dev, sizeof(int), hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+        return ok ? BMI_OK : BMI_ERR_HIP;
+    }
+    // ... and, where the caller goes on: the list just written becomes the active one, the row table (compact image -> tensor row) is expanded
+    int take(int n_active, int tc_next) {
+        act = lists[cur];
+        bc = n_active;
+        cur ^= 1;
+        rows = rows_dev;
+        return launch_expand_rows(act, bc, batch, tc_next, rows_dev, s);
+    }
 };
 
 SiteArgs resolve_site(const bmi_site* site, uint64_t seed, int mask_cnt0, uint64_t elem_off) {
@@ -274,7 +309,7 @@ bool prefix_row_form(const bmi_engine_s* h, const OpInfo& op) {
     if (d.kind == BMI_OP_STEM) return false;
     if (d.kind != BMI_OP_CONV || h->f32 || d.ksize != 1 || op.has_pair || op.nsplit > 1 || d.in2 >= 0) return true;
     const TensorInfo& tin = h->tensors[d.in];
-    ConvArgs a;          // the selection-relevant arguments of run_op's full-run launch (the pointers only need to be present)
+    ConvArgs a;          // the selection-relevant arguments of conv_base_args for the full-run launch (the pointers only need to be present)
     std::memset(&a, 0, sizeof(a));
     a.bf16 = h->bf16;
     a.N = a.n_ref = a.B = a.in_mod = h->max_batch;
@@ -632,7 +667,7 @@ int bmi_create(const bmi_model_desc* desc, bmi_handle* out) {
         if (enable && opt_pair_prefix() && !e->f32) merge(e->prefix, true);
     }
     // Seam fusion (Bottleneck nets): conv3 + BN + residual + ReLU of block k followed at once by conv1 + BN + ReLU of block k+1 on its output:
-    // one conv1x1_seam launch produces both tensors and the wide one is not read back (conv1x1_seam.hip).  Decided per launch in run_op.
+    // one conv1x1_seam launch produces both tensors and the wide one is not read back (conv1x1_seam.hip).  Decided per launch in run_conv.
     for (size_t i = 0; !e->f32 && opt_conv_seam() && i + 1 < e->suffix.size(); ++i) {
         OpInfo& A = e->suffix[i];
         const OpInfo& Bo = e->suffix[i + 1];
@@ -651,7 +686,7 @@ int bmi_create(const bmi_model_desc* desc, bmi_handle* out) {
     }
     // ReLU + global average pool fused into the producing conv: a plain 3x3 stride-2 conv whose 4x4 output map feeds ONE exit head and
     // nothing else (ex1conv3 / ex2conv2 / ex3conv1 of the ResNets: relu -> avg_pool2d(4) -> Linear, resnet18.py:309-314, :320-325,
-    // :331-335) may write fp32 means [row][Cout] instead of the map when conv3x3_s2 takes the launch (decided per launch: run_op).
+    // :331-335) may write fp32 means [row][Cout] instead of the map when conv3x3_s2 takes the launch (decided per launch: run_conv).
     for (std::vector<OpInfo>* ops : {&e->prefix, &e->suffix}) {
         auto readers = [&](int id, int* heads) {
             int n = 0;
@@ -712,7 +747,7 @@ int bmi_create(const bmi_model_desc* desc, bmi_handle* out) {
     // mask itself — conv3x3_s2 on 32x32 maps (clears the dropped elements of its patch pieces in LDS), conv3x3_patch for the input of
     // a fused shortcut on 16x16 maps — the op writes the keep bits (1/16 of the bytes) and ONE scaled copy of the B images
     // instead; kept x 1/(1-p) rounded to fp16 and ANDed with the bits is what the MASK op itself stores, so the result is bit for
-    // bit the materialised one.  Decided per launch (run_op): a consumer whose kernel does not take the launch makes the
+    // bit the materialised one.  Decided per launch (run_op, run_conv): a consumer whose kernel does not take the launch makes the
     // MASK op's own launch happen first ("mask_lazy" = 0: always).
     for (size_t mi = 0; mi < e->suffix.size() && !e->f32; ++mi) {
         const bmi_op_desc md = e->suffix[mi].d;
@@ -782,7 +817,7 @@ int bmi_engine_set_option(bmi_handle h, const char* name, int32_t value) {
 // outputs are the bits of an engine that never had a temperature.  Read at launch time: captured graphs keep what was set at capture.
 int bmi_engine_set_temperature(bmi_handle h, const float* tau, int32_t n_exits) {
     if (!h) return BMI_ERR_INVALID;
-    if (!tau) { h->tau.clear(); h->inv_tau.clear(); return BMI_OK; }
+    if (!tau) { h->tau.clear(); h->cal.inv_tau.clear(); return BMI_OK; }
     if (n_exits != h->n_exits) return BMI_ERR_INVALID;
     bool ones = true;
     for (int i = 0; i < n_exits; ++i) {
@@ -791,11 +826,11 @@ int bmi_engine_set_temperature(bmi_handle h, const float* tau, int32_t n_exits) 
         if (!(inv > 0.f) || !std::isfinite(inv)) return BMI_ERR_INVALID;      // 1 / tau leaves the float32 range
         ones = ones && tau[i] == 1.f;
     }
-    if (!ones && h->vec_scale) return BMI_ERR_INVALID;     // one calibration map at a time: clear the vector scaling first
+    if (!ones && h->cal.vec_scale) return BMI_ERR_INVALID;     // one calibration map at a time: clear the vector scaling first
     h->tau.assign(tau, tau + n_exits);
-    h->inv_tau.clear();
+    h->cal.inv_tau.clear();
     if (!ones)
-        for (int i = 0; i < n_exits; ++i) h->inv_tau.push_back((float)(1.0 / (double)tau[i]));
+        for (int i = 0; i < n_exits; ++i) h->cal.inv_tau.push_back((float)(1.0 / (double)tau[i]));
     return BMI_OK;
 }
 
@@ -803,9 +838,9 @@ int bmi_engine_set_temperature(bmi_handle h, const float* tau, int32_t n_exits) 
 // instantiations and every output keeps its bits.  Read at launch time: captured graphs keep what was set at capture.
 int bmi_engine_set_ensemble_weights(bmi_handle h, const double* W_device, int32_t n_exits) {
     if (!h) return BMI_ERR_INVALID;
-    if (!W_device) { h->ens_w = nullptr; return BMI_OK; }
+    if (!W_device) { h->cal.ens_w = nullptr; return BMI_OK; }
     if (n_exits != h->n_exits) return BMI_ERR_INVALID;
-    h->ens_w = W_device;
+    h->cal.ens_w = W_device;
     return BMI_OK;
 }
 
@@ -814,11 +849,11 @@ int bmi_engine_set_ensemble_weights(bmi_handle h, const double* W_device, int32_
 // at capture.  Refused while a temperature other than all ones is in force (and bmi_engine_set_temperature refuses one while this is set).
 int bmi_engine_set_vector_scaling(bmi_handle h, const float* scale_device, const float* bias_device, int32_t n_exits, int32_t out_dim) {
     if (!h) return BMI_ERR_INVALID;
-    if (!scale_device) { h->vec_scale = h->vec_bias = nullptr; return BMI_OK; }
+    if (!scale_device) { h->cal.vec_scale = h->cal.vec_bias = nullptr; return BMI_OK; }
     if (!bias_device || n_exits != h->n_exits || out_dim != h->out_dim) return BMI_ERR_INVALID;
-    if (!h->inv_tau.empty()) return BMI_ERR_INVALID;
-    h->vec_scale = scale_device;
-    h->vec_bias = bias_device;
+    if (!h->cal.inv_tau.empty()) return BMI_ERR_INVALID;
+    h->cal.vec_scale = scale_device;
+    h->cal.vec_bias = bias_device;
     return BMI_OK;
 }
 
@@ -876,7 +911,7 @@ int bmi_plan(bmi_handle h, int32_t max_batch, int32_t chunk_samples, size_t* wor
     }
     off = st_base + st_peak;
     h->exit_off = off;
-    off += align_up((2 * (size_t)max_batch + 64 + NS) * sizeof(int), 256);   // two image lists, a counter, the row table
+    off += align_up(ActiveImages::ints(max_batch, NS) * sizeof(int), 256);
     // Split-K for the skinny deterministic 3x3 convs (VGG's 512 -> 512 convs on 2x2 maps: 250 images are 1000 pixels = 32 tiles
     // of 128 x 128 on 256 CUs, 65 us at 73 TFLOP/s): one workgroup per (tile, tap), fp32 partial sums, a finishing pass.
     // Decided here from the shape and the planned batch only.
@@ -928,7 +963,7 @@ int bmi_plan(bmi_handle h, int32_t max_batch, int32_t chunk_samples, size_t* wor
     h->max_batch = max_batch;
     h->chunk = chunk_samples;
     // A lazy site keeps its PLANAR layout only while every stride-2 reader's launch passes conv3x3_s2's minimum-grid rule at the planned
-    // full chunk (n_ref = max_batch x chunk: what the launcher looks at; 256 CUs): a reader that declines makes run_op materialise the
+    // full chunk (n_ref = max_batch x chunk: what the launcher looks at; 256 CUs): a reader that declines makes run_conv materialise the
     // tensor — correct either way, but the planar bits + copy would then have been written for nothing (and conv_igemm / conv1x1_stream
     // refuse a planar operand).  Small engines (tests, T = 1 mirrors) therefore plan NHWC lazy sites.
     for (TensorInfo& t : h->tensors) {
@@ -1104,14 +1139,14 @@ HeadArgs make_head_args(bmi_engine_s* e, const Pass& p, const OpInfo& op, int N,
     a.HW = tin.pooled_now ? 1 : tin.h * tin.w; a.K = tin.c; a.B = B; a.t0 = t0; a.tc = imap ? N / Bc : N / B;
     a.w = (const float*)d.weight; a.bias = d.bias; a.C = e->out_dim;
     const bool on_logits = d.site_pos == BMI_SITE_POS_INNER;
-    const uint64_t soff = (uint64_t)p.b0 * (uint64_t)tin.c;          // (site_off of run_op: [B, K] features, elementwise and per-channel draws alike)
+    const uint64_t soff = (uint64_t)p.b0 * (uint64_t)tin.c;          // (as site_off: [B, K] features, elementwise and per-channel draws alike)
     a.site = pass_site(e, p, on_logits ? nullptr : &d.site, soff);
     a.site_logits = pass_site(e, p, on_logits ? &d.site : nullptr);
     a.b0 = p.b0;
-    a.inv_tau = e->inv_tau.empty() ? 0.f : e->inv_tau[d.out];       // 0: the untempered instantiations
-    if (e->vec_scale) {                                             // this exit's [C] rows
-        a.vec_scale = e->vec_scale + (size_t)d.out * e->out_dim;
-        a.vec_bias = e->vec_bias + (size_t)d.out * e->out_dim;
+    a.inv_tau = e->cal.inv_tau.empty() ? 0.f : e->cal.inv_tau[d.out];       // 0: the untempered instantiations
+    if (e->cal.vec_scale) {                                                 // this exit's [C] rows
+        a.vec_scale = e->cal.vec_scale + (size_t)d.out * e->out_dim;
+        a.vec_bias = e->cal.vec_bias + (size_t)d.out * e->out_dim;
     }
     if (p.S1) {
         const size_t eo = (size_t)d.out * B * e->out_dim;
@@ -1127,6 +1162,282 @@ HeadArgs make_head_args(bmi_engine_s* e, const Pass& p, const OpInfo& op, int N,
     return a;
 }
 
+// image-partitioned launch (bmi_forward_mcd_images): element index of image 0 in the index space of a site on a tensor with
+// `per_image` elements per image (elementwise) / `channels` (per-(image, channel) draws)
+uint64_t site_off(const Pass& p, const bmi_site& st, size_t per_image, size_t channels) {
+    return (uint64_t)p.b0 * (st.kind == BMI_SITE_CHANNEL ? channels : per_image);
+}
+
+// a lazy site's tensor (see bmi_create) is written when an op that reads it cannot apply the mask itself
+bool pending(const bmi_engine_s* e, int id) { return id >= 0 && e->tensors[id].lazy_pending; }
+int materialise(bmi_engine_s* e, int id, hipStream_t s) {
+    if (!pending(e, id)) return BMI_OK;
+    e->tensors[id].lazy_pending = false;
+    return launch_mask_apply(e->tensors[id].lazy_call, s);
+}
+
+// The arguments of op's own conv launch (N / t0 / Bc / rows as in run_op; n_rows: the rows of a stochastic tensor): what run_conv starts from
+ConvArgs conv_base_args(const bmi_engine_s* e, const Pass& p, const OpInfo& op, int N, int t0, int Bc, const int* rows, int n_rows) {
+    const bmi_op_desc& d = op.d;
+    const TensorInfo& tin = e->tensors[d.in];
+    char* const ws = p.ws;
+    const int B = p.B;
+    ConvArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.bf16 = e->bf16;
+    a.in = (const _Float16*)(ws + tin.offset);
+    a.wgt = (const _Float16*)d.weight;
+    a.scale = d.scale; a.bias = d.bias;
+    a.out = (_Float16*)(ws + e->tensors[d.out].offset);
+    a.N = N;
+    // kernel selection looks at the PLANNED batch (x the planned chunk for suffix launches), never at this call's batch or sample
+    // count: a t-shard, a partial chunk, an image share (bmi_forward_mcd_images) and a loader's smaller last batch all run the
+    // kernels — and get the bits — of the full batch
+    a.n_ref = (tin.stoch || (d.residual >= 0 && e->tensors[d.residual].stoch) || op.stoch) ? e->max_batch * e->chunk : e->max_batch;
+    a.imap = rows; a.Bc = Bc;
+    a.in_mod = tin.stoch ? n_rows : B;
+    if (d.residual >= 0) {
+        a.res = (const _Float16*)(ws + e->tensors[d.residual].offset);
+        a.res_mod = e->tensors[d.residual].stoch ? n_rows : B;
+    }
+    a.H = tin.h; a.W = tin.w; a.Cin = tin.c;
+    a.Ho = op.ho; a.Wo = op.wo; a.Cout = op.cout;
+    a.ksize = d.ksize; a.stride = d.stride; a.pad = d.pad; a.relu = d.relu;
+    a.M = N * op.ho * op.wo;
+    a.B = B; a.t0 = t0;
+    a.site = pass_site(e, p, &d.site, site_off(p, d.site, (size_t)op.ho * op.wo * op.cout, (size_t)op.cout));
+    if (d.site_pos == BMI_SITE_POS_INNER && d.site.kind != BMI_SITE_NONE) { a.site_inner = 1; a.bias_post = d.bias_post; }
+    a.out_mul = op.out_mul;
+    if (d.in2 >= 0) {
+        const TensorInfo& t2 = e->tensors[d.in2];
+        a.in2 = (const _Float16*)(ws + t2.offset);
+        a.wgt2 = (const _Float16*)d.weight2;
+        a.in2_mod = t2.stoch ? n_rows : B;
+        a.H2 = t2.h; a.W2 = t2.w; a.Cin2 = t2.c; a.stride2 = t2.h / op.ho;
+    }
+    if (op.bits_tensor >= 0) a.in_bits = (const uint8_t*)(ws + e->tensors[op.bits_tensor].offset);
+    return a;
+}
+
+// Pair mode: base arguments `a` with the second conv on the same input riding in the launch (the 256-channel tile) ...
+ConvArgs conv_pair_args(const bmi_engine_s* e, const Pass& p, const OpInfo& op, const ConvArgs& a) {
+    ConvArgs q = a;
+    q.wgt_b = (const _Float16*)op.pair_d.weight;
+    q.scale_b = op.pair_d.scale; q.bias_b = op.pair_d.bias;
+    q.out_b = (_Float16*)(p.ws + e->tensors[op.pair_d.out].offset);
+    q.split = op.cout;
+    q.Cout = op.cout + op.pair_cout;
+    return q;
+}
+
+// ... and that second conv as a plain launch of its own, where no kernel takes the pair
+ConvArgs conv_pair_second_args(const bmi_engine_s* e, const Pass& p, const OpInfo& op, const ConvArgs& a) {
+    ConvArgs q = a;
+    q.wgt = (const _Float16*)op.pair_d.weight;
+    q.scale = op.pair_d.scale; q.bias = op.pair_d.bias;
+    q.out = (_Float16*)(p.ws + e->tensors[op.pair_d.out].offset);
+    q.Cout = op.pair_cout;
+    return q;
+}
+
+// The next Bottleneck's reduce conv on the output of `a` (op.has_seam): the second conv of a conv1x1_seam launch, or a plain launch behind a's
+ConvArgs conv_seam_second_args(const bmi_engine_s* e, const Pass& p, const OpInfo& op, const ConvArgs& a, int n_rows) {
+    ConvArgs b;
+    std::memset(&b, 0, sizeof(b));
+    b.bf16 = e->bf16;
+    b.in = a.out;
+    b.wgt = (const _Float16*)op.seam_d.weight;
+    b.scale = op.seam_d.scale; b.bias = op.seam_d.bias;
+    b.out = (_Float16*)(p.ws + e->tensors[op.seam_d.out].offset);
+    b.N = a.N; b.n_ref = a.n_ref; b.imap = a.imap; b.Bc = a.Bc; b.in_mod = n_rows;
+    b.H = op.ho; b.W = op.wo; b.Cin = op.cout; b.Ho = op.ho; b.Wo = op.wo; b.Cout = op.seam_cout;
+    b.ksize = 1; b.stride = 1; b.pad = 0; b.relu = op.seam_d.relu;
+    b.M = a.M; b.B = a.B; b.t0 = a.t0;
+    b.site = pass_site(e, p, nullptr);
+    b.out_mul = 1.f;
+    return b;
+}
+
+// A pending lazy site's tensor as an operand (in, res or in2): the scaled deterministic copy (B images) and the keep bits of the folded batch
+// that stand in for it, and whether the two are stored in the planar layout
+struct LazyOperand { const _Float16* scaled; const uint8_t* bits; bool planar; };
+LazyOperand lazy_operand(const bmi_engine_s* e, const Pass& p, int id) {
+    const TensorInfo& t = e->tensors[id];
+    return {(const _Float16*)(p.ws + e->tensors[t.lazy_scaled].offset), (const uint8_t*)(p.ws + e->tensors[t.lazy_bits].offset), t.lazy_planar_now};
+}
+
+// The profile's cost model of a conv launch at `elem` bytes per element (2: fp16 / bf16, 4: pair32).  A pair partner widens Cout, a fused 1x1
+// shortcut lengthens K.  Algorithmic bytes: every operand once (a deterministic one counts its B images), the output once, the weights once.
+double operand_bytes(const bmi_engine_s* e, int id, int N, int B, double elem) {
+    const TensorInfo& t = e->tensors[id];
+    return elem * (t.stoch ? N : B) * t.h * t.w * t.c;
+}
+struct ConvCost { double flops, bytes; };
+ConvCost conv_cost(const bmi_engine_s* e, const OpInfo& op, int N, int B, double elem) {
+    const bmi_op_desc& d = op.d;
+    const double cout = op.cout + (op.has_pair ? op.pair_cout : 0);
+    const double k_len = (double)d.ksize * d.ksize * e->tensors[d.in].c + (d.in2 >= 0 ? e->tensors[d.in2].c : 0);
+    const double pixels = (double)N * op.ho * op.wo;
+    ConvCost c;
+    c.flops = 2.0 * pixels * cout * k_len;
+    c.bytes = operand_bytes(e, d.in, N, B, elem) + elem * pixels * cout + elem * cout * k_len;
+    if (d.residual >= 0) c.bytes += operand_bytes(e, d.residual, N, B, elem);
+    if (d.in2 >= 0) c.bytes += operand_bytes(e, d.in2, N, B, elem);
+    return c;
+}
+// an operand read through a lazy site counts what such a launch actually has to move: the B scaled images + the folded batch's keep bits
+double lazy_saving(const bmi_engine_s* e, int id, int N, int B) {
+    const TensorInfo& t = e->tensors[id];
+    return operand_bytes(e, id, N, B, 2.0) - (2.0 * B + N / 8.0) * t.h * t.w * t.c;
+}
+
+// A CONV op of run_op (its arguments; prof: the op's record).  The launch forms are tried in this order, each falling through to the next
+// on BMI_ERR_UNSUPPORTED: the order is the policy.
+int run_conv(bmi_engine_s* e, const Pass& p, const OpInfo& op, int N, int t0, int Bc, const int* rows, int n_rows, ProfScope& prof) {
+    const bmi_op_desc& d = op.d;
+    const int B = p.B;
+    const hipStream_t s = p.stream;
+    ConvArgs a = conv_base_args(e, p, op, N, t0, Bc, rows, n_rows);
+    if (e->f32) {   // the exact / split engines: one generic kernel each (a.in / a.res / a.out hold fp32)
+        if (!e->split) { prof.tag(-1, 0, 0); return launch_conv_exact(a, s); }
+        const ConvCost c4 = conv_cost(e, op, N, B, 4.0);
+        prof.tag(BMI_CONV_FAMILY_SPLIT, c4.flops, c4.bytes);
+        if (op.nsplit > 1 && !op.stoch) {       // split-K (bmi_plan): raw fp32 partial sums per K range, then the finishing pass
+            a.partial = (float*)(p.ws + e->splitk_off);
+            a.nsplit = op.nsplit;
+        }
+        if (op.has_pair) {
+            const int rcp = launch_conv_split(conv_pair_args(e, p, op, a), e->split == 2, s);
+            if (rcp != BMI_ERR_UNSUPPORTED) return rcp;
+            const int rc1 = launch_conv_split(a, e->split == 2, s);          // not taken: two launches
+            return rc1 != BMI_OK ? rc1 : launch_conv_split(conv_pair_second_args(e, p, op, a), e->split == 2, s);
+        }
+        return launch_conv_split(a, e->split == 2, s);
+    }
+    const ConvCost c2 = conv_cost(e, op, N, B, 2.0);
+    const double flops = c2.flops, bytes = c2.bytes;
+    if (op.has_seam) {
+        // the next Bottleneck's reduce conv on this conv's output: one conv1x1_seam launch, or the two launches in order
+        const ConvArgs b = conv_seam_second_args(e, p, op, a, n_rows);
+        const double flops_b = 2.0 * N * op.ho * op.wo * (double)op.seam_cout * op.cout;
+        const double bytes_b = 2.0 * N * op.ho * op.wo * (double)op.seam_cout + 2.0 * (double)op.seam_cout * op.cout;   // (its input never leaves the chip)
+        const int rcs = launch_conv1x1_seam(a, b, s);
+        if (rcs != BMI_ERR_UNSUPPORTED) {
+            prof.tag(BMI_CONV_FAMILY_SEAM, flops + flops_b, bytes + bytes_b);
+            return rcs;
+        }
+        int fam = -1;
+        const int rc1 = launch_conv(a, s, &fam);
+        prof.tag(fam, flops + flops_b, bytes + bytes_b + 2.0 * N * op.ho * op.wo * (double)op.cout);
+        return rc1 != BMI_OK ? rc1 : launch_conv(b, s);
+    }
+    if (op.has_pair) {
+        const ConvArgs pr = conv_pair_args(e, p, op, a);
+        e->tensors[d.out].pooled_now = e->tensors[op.pair_d.out].pooled_now = false;
+        if (pending(e, d.in)) {      // lazy site on the input: conv3x3_s2 clears the dropped elements in LDS, or the tensor is written now
+            ConvArgs m = pr;
+            const LazyOperand v = lazy_operand(e, p, d.in);
+            m.in = v.scaled; m.in_mod = B; m.in_bits = v.bits; m.lazy_planar = v.planar;
+            const int rcl = launch_conv3x3_s2(m, s);
+            prof.tag(BMI_CONV_FAMILY_S2, flops, bytes - lazy_saving(e, d.in, N, B));
+            if (rcl != BMI_ERR_UNSUPPORTED) return rcl;
+            const int rcm = materialise(e, d.in, s);
+            if (rcm != BMI_OK) return rcm;
+        }
+        if (opt_conv_pool() && (op.pool_ok || op.pair_pool_ok)) {
+            ConvArgs q = pr;         // the pooled means take the place of the map in the workspace (16 x 4 B <= 16 x 16 x 2 B per channel)
+            if (op.pool_ok) q.pool = (float*)q.out;
+            if (op.pair_pool_ok) q.pool_b = (float*)q.out_b;
+            const int rcp = launch_conv3x3_s2(q, s);
+            prof.tag(BMI_CONV_FAMILY_S2, flops, bytes);
+            if (rcp != BMI_ERR_UNSUPPORTED) {
+                e->tensors[d.out].pooled_now = op.pool_ok;
+                e->tensors[op.pair_d.out].pooled_now = op.pair_pool_ok;
+                return rcp;
+            }
+        }
+        int rc = launch_conv3x3_s2(pr, s);
+        prof.tag(BMI_CONV_FAMILY_S2, flops, bytes);
+        if (rc != BMI_ERR_UNSUPPORTED) return rc;
+        rc = launch_conv_igemm_wide(pr, s);
+        prof.tag(BMI_CONV_FAMILY_WIDE, flops, bytes);
+        if (rc != BMI_ERR_UNSUPPORTED) return rc;
+        int fam = -1;
+        const int rc2 = launch_conv(a, s, &fam);          // not taken after all: two plain launches
+        prof.tag(fam, flops, bytes);
+        return rc2 != BMI_OK ? rc2 : launch_conv(conv_pair_second_args(e, p, op, a), s);
+    }
+    if (pending(e, d.residual)) {    // (run_op's res_lazy_ok) the residual through its keep bits: conv3x3_patch's 64-channel tile — with the input too
+        ConvArgs m = a;              //  when it is the same pending tensor or another one
+        const LazyOperand r = lazy_operand(e, p, d.residual);
+        m.res = r.scaled; m.res_mod = B; m.res_bits = r.bits; m.lazy_planar = r.planar;
+        if (pending(e, d.in)) {
+            const LazyOperand v = lazy_operand(e, p, d.in);
+            m.in = v.scaled; m.in_mod = B; m.in_bits = v.bits; m.lazy_planar = v.planar || r.planar;
+        }
+        const int rcl = launch_conv3x3_patch(m, s);
+        prof.tag(BMI_CONV_FAMILY_PATCH, flops, bytes - lazy_saving(e, d.residual, N, B) - (pending(e, d.in) ? lazy_saving(e, d.in, N, B) : 0.0));
+        if (rcl != BMI_ERR_UNSUPPORTED) return rcl;
+        const int rcm = materialise(e, d.residual, s);
+        if (rcm != BMI_OK) return rcm;
+    }
+    if (pending(e, d.in)) {          // whichever kernel of the chain applies keep bits: conv1x1_stream, conv3x3_s2, conv_igemm
+        ConvArgs m = a;
+        const LazyOperand v = lazy_operand(e, p, d.in);
+        m.in = v.scaled; m.in_mod = B; m.in_bits = v.bits; m.lazy_planar = v.planar;
+        int faml = -1;
+        const int rcl = launch_conv(m, s, &faml);
+        prof.tag(faml, flops, bytes - lazy_saving(e, d.in, N, B));
+        if (rcl != BMI_ERR_UNSUPPORTED) return rcl;
+        const int rcm = materialise(e, d.in, s);
+        if (rcm != BMI_OK) return rcm;
+    }
+    if (pending(e, d.in2)) {         // ... on the input of a fused shortcut: conv3x3_patch on 16x16 maps
+        int rcl = BMI_ERR_UNSUPPORTED;
+        if (op.ho == 16 && op.wo == 16) {
+            ConvArgs m = a;
+            const LazyOperand v = lazy_operand(e, p, d.in2);
+            m.in2 = v.scaled; m.in2_mod = B; m.in2_bits = v.bits; m.lazy_planar = v.planar;
+            rcl = launch_conv3x3_patch(m, s);
+            prof.tag(BMI_CONV_FAMILY_PATCH, flops, bytes - lazy_saving(e, d.in2, N, B));
+        }
+        if (rcl != BMI_ERR_UNSUPPORTED) return rcl;
+        const int rcm = materialise(e, d.in2, s);
+        if (rcm != BMI_OK) return rcm;
+    }
+    e->tensors[d.out].pooled_now = false;
+    if (op.nsplit > 1 && !op.stoch) {        // (under a row table too: conv_igemm's split-K form writes through it)
+        a.partial = (float*)(p.ws + e->splitk_off);
+        a.nsplit = op.nsplit;
+        prof.tag(BMI_CONV_FAMILY_IGEMM, flops, bytes);
+        return launch_conv_igemm(a, s);
+    }
+    if (opt_conv_pool() == 1 && op.pool_pw_ok) {      // ("conv_pool" = 2: conv3x3_s2's only)
+        ConvArgs q = a;
+        q.pool = (float*)q.out;
+        const int rcp = launch_conv3x3_pw(q, s);
+        if (rcp != BMI_ERR_UNSUPPORTED) {
+            prof.tag(BMI_CONV_FAMILY_PW, flops, bytes);
+            e->tensors[d.out].pooled_now = true;
+            return rcp;
+        }
+    }
+    if (opt_conv_pool() && op.pool_ok) {
+        ConvArgs q = a;
+        q.pool = (float*)q.out;
+        const int rcp = launch_conv3x3_s2(q, s);
+        if (rcp != BMI_ERR_UNSUPPORTED) {
+            prof.tag(BMI_CONV_FAMILY_S2, flops, bytes);
+            e->tensors[d.out].pooled_now = true;
+            return rcp;
+        }
+    }
+    int fam = -1;
+    const int rcc = launch_conv(a, s, &fam);
+    prof.tag(fam, flops, bytes);
+    return rcc;
+}
+
 // imap / rows / Bc: dynamic early exit and adaptive sampling: N = samples * Bc compact images of the B-image batch; imap = the Bc
 // active images (heads), rows = the N-entry row table (ConvArgs::imap, EltArgs::rows, the maxpool / dense launchers); null = all images
 int run_op(bmi_engine_s* e, const Pass& p, const OpInfo& op, int N, int t0, const int* imap = nullptr, int Bc = 0, const int* rows = nullptr) {
@@ -1135,28 +1446,17 @@ int run_op(bmi_engine_s* e, const Pass& p, const OpInfo& op, int N, int t0, cons
     char* const ws = p.ws;
     const int B = p.B;
     const hipStream_t s = p.stream;
-    // image-partitioned launch (bmi_forward_mcd_images): element index of image 0 in the index space of a site on a tensor with
-    // `per_image` elements per image (elementwise) / `channels` (per-(image, channel) draws)
-    auto site_off = [&](const bmi_site& st, size_t per_image, size_t channels) -> uint64_t {
-        return (uint64_t)p.b0 * (st.kind == BMI_SITE_CHANNEL ? channels : per_image);
-    };
     const int n_rows = imap ? (N / Bc) * B : N;     // rows of a stochastic tensor (original folded layout)
     if (imap && d.kind != BMI_OP_CONV && d.kind != BMI_OP_HEAD && d.kind != BMI_OP_MASK && d.kind != BMI_OP_MAXPOOL && d.kind != BMI_OP_DENSE)
         return BMI_ERR_UNSUPPORTED;      // (OP_MASKBITS: its conv_igemm readers have no row-table form)
     if (imap && e->f32 && !e->split) return BMI_ERR_UNSUPPORTED;      // (the exact engine: parity only)
-    // a lazy site's tensor (see bmi_create) is written now if this op cannot apply the mask itself
-    auto pending = [&](int id) { return id >= 0 && e->tensors[id].lazy_pending; };
-    auto materialise = [&](int id) -> int {
-        if (!pending(id)) return BMI_OK;
-        e->tensors[id].lazy_pending = false;
-        return launch_mask_apply(e->tensors[id].lazy_call, s);
-    };
-    // (a pending RESIDUAL stays pending only for conv3x3_patch's 64-channel tile, which masks it where it is added: tried first in the CONV case below)
-    const bool res_lazy_ok = d.kind == BMI_OP_CONV && pending(d.residual) && !op.has_pair && d.in2 < 0 && d.ksize == 3 && d.stride == 1 && d.pad == 1 &&
+    // a pending lazy operand is written now if this op cannot apply the mask itself
+    // (a pending RESIDUAL stays pending only for conv3x3_patch's 64-channel tile, which masks it where it is added: tried first in run_conv)
+    const bool res_lazy_ok = d.kind == BMI_OP_CONV && pending(e, d.residual) && !op.has_pair && d.in2 < 0 && d.ksize == 3 && d.stride == 1 && d.pad == 1 &&
                              op.cout % 64 == 0 && op.cout % 128 != 0 && op.wo == 32 && op.ho % 8 == 0 && opt_conv_patch64() && !imap;
-    if (d.kind != BMI_OP_CONV || (pending(d.residual) && !res_lazy_ok) || (pending(d.in) && pending(d.in2))) {
-        int rcm = materialise(d.in);
-        if (rcm == BMI_OK && d.kind == BMI_OP_CONV) { rcm = materialise(d.residual); if (rcm == BMI_OK) rcm = materialise(d.in2); }
+    if (d.kind != BMI_OP_CONV || (pending(e, d.residual) && !res_lazy_ok) || (pending(e, d.in) && pending(e, d.in2))) {
+        int rcm = materialise(e, d.in, s);
+        if (rcm == BMI_OK && d.kind == BMI_OP_CONV) { rcm = materialise(e, d.residual, s); if (rcm == BMI_OK) rcm = materialise(e, d.in2, s); }
         if (rcm != BMI_OK) return rcm;
     }
     ProfScope prof(e, d.kind == OP_MASKBITS ? BMI_OP_MASK : d.kind, s);
@@ -1165,229 +1465,11 @@ int run_op(bmi_engine_s* e, const Pass& p, const OpInfo& op, int N, int t0, cons
         case BMI_OP_STEM:
             return launch_stem_conv(p.x, (const float*)d.weight, d.scale, d.bias, (_Float16*)(ws + e->tensors[d.out].offset), N,
                                     tin.c, tin.h, tin.w, op.cout, d.ksize, d.stride, d.pad, d.relu, e->dtype, s);     // (F32: fp32 out; F16X2 / BF16X3: pair32 out)
-        case BMI_OP_CONV: {
-            ConvArgs a;
-            std::memset(&a, 0, sizeof(a));
-            a.bf16 = e->bf16;
-            a.in = (const _Float16*)(ws + tin.offset);
-            a.wgt = (const _Float16*)d.weight;
-            a.scale = d.scale; a.bias = d.bias;
-            a.out = (_Float16*)(ws + e->tensors[d.out].offset);
-            a.N = N;
-            // kernel selection looks at the PLANNED batch (x the planned chunk for suffix launches), never at this call's batch or sample
-            // count: a t-shard, a partial chunk, an image share (bmi_forward_mcd_images) and a loader's smaller last batch all run the
-            // kernels — and get the bits — of the full batch
-            a.n_ref = (tin.stoch || (d.residual >= 0 && e->tensors[d.residual].stoch) || op.stoch) ? e->max_batch * e->chunk : e->max_batch;
-            a.imap = rows; a.Bc = Bc;
-            a.in_mod = tin.stoch ? n_rows : B;
-            if (d.residual >= 0) {
-                a.res = (const _Float16*)(ws + e->tensors[d.residual].offset);
-                a.res_mod = e->tensors[d.residual].stoch ? n_rows : B;
-            }
-            a.H = tin.h; a.W = tin.w; a.Cin = tin.c;
-            a.Ho = op.ho; a.Wo = op.wo; a.Cout = op.cout;
-            a.ksize = d.ksize; a.stride = d.stride; a.pad = d.pad; a.relu = d.relu;
-            a.M = N * op.ho * op.wo;
-            a.B = B; a.t0 = t0;
-            a.site = pass_site(e, p, &d.site, site_off(d.site, (size_t)op.ho * op.wo * op.cout, (size_t)op.cout));
-            if (d.site_pos == BMI_SITE_POS_INNER && d.site.kind != BMI_SITE_NONE) { a.site_inner = 1; a.bias_post = d.bias_post; }
-            a.out_mul = op.out_mul;
-            if (d.in2 >= 0) {
-                const TensorInfo& t2 = e->tensors[d.in2];
-                a.in2 = (const _Float16*)(ws + t2.offset);
-                a.wgt2 = (const _Float16*)d.weight2;
-                a.in2_mod = t2.stoch ? n_rows : B;
-                a.H2 = t2.h; a.W2 = t2.w; a.Cin2 = t2.c; a.stride2 = t2.h / op.ho;
-            }
-            if (op.bits_tensor >= 0) a.in_bits = (const uint8_t*)(ws + e->tensors[op.bits_tensor].offset);
-            auto lazy_in = [&](ConvArgs& m) {   // the input as (scaled deterministic tensor, keep bits)
-                m.in = (const _Float16*)(ws + e->tensors[tin.lazy_scaled].offset);
-                m.in_mod = B;
-                m.in_bits = (const uint8_t*)(ws + e->tensors[tin.lazy_bits].offset);
-                m.lazy_planar = tin.lazy_planar_now;
-            };
-            if (e->f32) {   // the exact / split engines: one generic kernel each (a.in / a.res / a.out hold fp32)
-                if (!e->split) { prof.tag(-1, 0, 0); return launch_conv_exact(a, s); }
-                const int cout_l = op.cout + (op.has_pair ? op.pair_cout : 0);      // pair mode: two convs on this input in one launch (the 256-channel tile)
-                const int cin2_l = d.in2 >= 0 ? e->tensors[d.in2].c : 0;            // fused 1x1 shortcut: extra K-steps
-                const double fl = 2.0 * N * op.ho * op.wo * (double)cout_l * (d.ksize * d.ksize * tin.c + cin2_l);
-                auto tb = [&](int id) { const TensorInfo& t = e->tensors[id]; return 4.0 * (t.stoch ? N : B) * t.h * t.w * t.c; };
-                prof.tag(BMI_CONV_FAMILY_SPLIT, fl, tb(d.in) + 4.0 * N * op.ho * op.wo * (double)cout_l + 4.0 * (double)cout_l * (d.ksize * d.ksize * tin.c + cin2_l) +
-                                                    (d.residual >= 0 ? tb(d.residual) : 0.0) + (d.in2 >= 0 ? tb(d.in2) : 0.0));
-                if (op.nsplit > 1 && !op.stoch) {       // split-K (bmi_plan): raw fp32 partial sums per K range, then the finishing pass
-                    a.partial = (float*)(ws + e->splitk_off);
-                    a.nsplit = op.nsplit;
-                }
-                if (op.has_pair) {
-                    ConvArgs p = a;
-                    p.wgt_b = (const _Float16*)op.pair_d.weight;
-                    p.scale_b = op.pair_d.scale; p.bias_b = op.pair_d.bias;
-                    p.out_b = (_Float16*)(ws + e->tensors[op.pair_d.out].offset);
-                    p.split = op.cout;
-                    p.Cout = cout_l;
-                    const int rcp = launch_conv_split(p, e->split == 2, s);
-                    if (rcp != BMI_ERR_UNSUPPORTED) return rcp;
-                    ConvArgs q = a;          // not taken: two launches
-                    q.wgt = p.wgt_b; q.scale = p.scale_b; q.bias = p.bias_b; q.out = p.out_b; q.Cout = op.pair_cout;
-                    const int rc1 = launch_conv_split(a, e->split == 2, s);
-                    return rc1 != BMI_OK ? rc1 : launch_conv_split(q, e->split == 2, s);
-                }
-                return launch_conv_split(a, e->split == 2, s);
-            }
-            double flops = 2.0 * N * op.ho * op.wo * (double)(op.cout + (op.has_pair ? op.pair_cout : 0)) * d.ksize * d.ksize * tin.c;
-            if (d.in2 >= 0) flops += 2.0 * N * op.ho * op.wo * (double)op.cout * e->tensors[d.in2].c;
-            // algorithmic bytes: every operand tensor once (a deterministic operand counts its B images), weights once; an operand read
-            // through a lazy site (the B scaled images + the folded batch's keep bits) counts what such a launch actually has to move
-            auto tbytes = [&](int id) { const TensorInfo& t = e->tensors[id]; return 2.0 * (t.stoch ? N : B) * t.h * t.w * t.c; };
-            auto lazy_saving = [&](int id) { const TensorInfo& t = e->tensors[id]; return tbytes(id) - (2.0 * B + N / 8.0) * t.h * t.w * t.c; };
-            double bytes = tbytes(d.in) + 2.0 * N * op.ho * op.wo * (double)(op.cout + (op.has_pair ? op.pair_cout : 0)) +
-                           2.0 * (double)(op.cout + (op.has_pair ? op.pair_cout : 0)) * d.ksize * d.ksize * tin.c;
-            if (d.residual >= 0) bytes += tbytes(d.residual);
-            if (d.in2 >= 0) bytes += tbytes(d.in2) + 2.0 * op.cout * e->tensors[d.in2].c;
-            if (op.has_seam) {
-                // the next Bottleneck's reduce conv on this conv's output: one conv1x1_seam launch, or the two launches in order
-                ConvArgs b;
-                std::memset(&b, 0, sizeof(b));
-                b.bf16 = e->bf16;
-                b.in = a.out;
-                b.wgt = (const _Float16*)op.seam_d.weight;
-                b.scale = op.seam_d.scale; b.bias = op.seam_d.bias;
-                b.out = (_Float16*)(ws + e->tensors[op.seam_d.out].offset);
-                b.N = N; b.n_ref = a.n_ref; b.imap = rows; b.Bc = Bc; b.in_mod = n_rows;
-                b.H = op.ho; b.W = op.wo; b.Cin = op.cout; b.Ho = op.ho; b.Wo = op.wo; b.Cout = op.seam_cout;
-                b.ksize = 1; b.stride = 1; b.pad = 0; b.relu = op.seam_d.relu;
-                b.M = a.M; b.B = B; b.t0 = t0;
-                b.site = pass_site(e, p, nullptr);
-                b.out_mul = 1.f;
-                const double flops_b = 2.0 * N * op.ho * op.wo * (double)op.seam_cout * op.cout;
-                const double bytes_b = 2.0 * N * op.ho * op.wo * (double)op.seam_cout + 2.0 * (double)op.seam_cout * op.cout;   // (its input never leaves the chip)
-                const int rcs = launch_conv1x1_seam(a, b, s);
-                if (rcs != BMI_ERR_UNSUPPORTED) {
-                    prof.tag(BMI_CONV_FAMILY_SEAM, flops + flops_b, bytes + bytes_b);
-                    return rcs;
-                }
-                int fam = -1;
-                const int rc1 = launch_conv(a, s, &fam);
-                prof.tag(fam, flops + flops_b, bytes + bytes_b + 2.0 * N * op.ho * op.wo * (double)op.cout);
-                return rc1 != BMI_OK ? rc1 : launch_conv(b, s);
-            }
-            if (op.has_pair) {
-                ConvArgs p = a;
-                p.wgt_b = (const _Float16*)op.pair_d.weight;
-                p.scale_b = op.pair_d.scale; p.bias_b = op.pair_d.bias;
-                p.out_b = (_Float16*)(ws + e->tensors[op.pair_d.out].offset);
-                p.split = op.cout;
-                p.Cout = op.cout + op.pair_cout;
-                e->tensors[d.out].pooled_now = e->tensors[op.pair_d.out].pooled_now = false;
-                if (pending(d.in)) {         // lazy site on the input: conv3x3_s2 clears the dropped elements in LDS, or the tensor is written now
-                    ConvArgs m = p;
-                    lazy_in(m);
-                    const int rcl = launch_conv3x3_s2(m, s);
-                    prof.tag(BMI_CONV_FAMILY_S2, flops, bytes - lazy_saving(d.in));
-                    if (rcl != BMI_ERR_UNSUPPORTED) return rcl;
-                    const int rcm = materialise(d.in);
-                    if (rcm != BMI_OK) return rcm;
-                }
-                if (opt_conv_pool() && (op.pool_ok || op.pair_pool_ok)) {
-                    ConvArgs q = p;          // the pooled means take the place of the map in the workspace (16 x 4 B <= 16 x 16 x 2 B per channel)
-                    if (op.pool_ok) q.pool = (float*)q.out;
-                    if (op.pair_pool_ok) q.pool_b = (float*)q.out_b;
-                    const int rcp = launch_conv3x3_s2(q, s);
-                    prof.tag(BMI_CONV_FAMILY_S2, flops, bytes);
-                    if (rcp != BMI_ERR_UNSUPPORTED) {
-                        e->tensors[d.out].pooled_now = op.pool_ok;
-                        e->tensors[op.pair_d.out].pooled_now = op.pair_pool_ok;
-                        return rcp;
-                    }
-                }
-                int rc = launch_conv3x3_s2(p, s);
-                prof.tag(BMI_CONV_FAMILY_S2, flops, bytes);
-                if (rc != BMI_ERR_UNSUPPORTED) return rc;
-                rc = launch_conv_igemm_wide(p, s);
-                prof.tag(BMI_CONV_FAMILY_WIDE, flops, bytes);
-                if (rc != BMI_ERR_UNSUPPORTED) return rc;
-                ConvArgs q = a;          // not taken after all: two plain launches
-                q.wgt = p.wgt_b; q.scale = p.scale_b; q.bias = p.bias_b; q.out = p.out_b; q.Cout = op.pair_cout;
-                int fam = -1;
-                const int rc2 = launch_conv(a, s, &fam);
-                prof.tag(fam, flops, bytes);
-                return rc2 != BMI_OK ? rc2 : launch_conv(q, s);
-            }
-            if (pending(d.residual)) {       // (res_lazy_ok) the residual through its keep bits: conv3x3_patch's 64-channel tile — with the input too when it is the
-                ConvArgs m = a;              //  same pending tensor or another one
-                const TensorInfo& tr = e->tensors[d.residual];
-                m.res = (const _Float16*)(ws + e->tensors[tr.lazy_scaled].offset);
-                m.res_mod = B;
-                m.res_bits = (const uint8_t*)(ws + e->tensors[tr.lazy_bits].offset);
-                m.lazy_planar = tr.lazy_planar_now;
-                if (pending(d.in)) { lazy_in(m); m.lazy_planar = m.lazy_planar || tr.lazy_planar_now; }
-                const int rcl = launch_conv3x3_patch(m, s);
-                prof.tag(BMI_CONV_FAMILY_PATCH, flops, bytes - lazy_saving(d.residual) - (pending(d.in) ? lazy_saving(d.in) : 0.0));
-                if (rcl != BMI_ERR_UNSUPPORTED) return rcl;
-                const int rcm = materialise(d.residual);
-                if (rcm != BMI_OK) return rcm;
-            }
-            if (pending(d.in)) {             // whichever kernel of the chain applies keep bits: conv1x1_stream, conv3x3_s2, conv_igemm
-                ConvArgs m = a;
-                lazy_in(m);
-                int faml = -1;
-                const int rcl = launch_conv(m, s, &faml);
-                prof.tag(faml, flops, bytes - lazy_saving(d.in));
-                if (rcl != BMI_ERR_UNSUPPORTED) return rcl;
-                const int rcm = materialise(d.in);
-                if (rcm != BMI_OK) return rcm;
-            }
-            if (pending(d.in2)) {            // ... on the input of a fused shortcut: conv3x3_patch on 16x16 maps
-                int rcl = BMI_ERR_UNSUPPORTED;
-                if (op.ho == 16 && op.wo == 16) {
-                    const TensorInfo& t2 = e->tensors[d.in2];
-                    ConvArgs m = a;
-                    m.in2 = (const _Float16*)(ws + e->tensors[t2.lazy_scaled].offset);
-                    m.in2_mod = B;
-                    m.in2_bits = (const uint8_t*)(ws + e->tensors[t2.lazy_bits].offset);
-                    m.lazy_planar = t2.lazy_planar_now;
-                    rcl = launch_conv3x3_patch(m, s);
-                    prof.tag(BMI_CONV_FAMILY_PATCH, flops, bytes - lazy_saving(d.in2));
-                }
-                if (rcl != BMI_ERR_UNSUPPORTED) return rcl;
-                const int rcm = materialise(d.in2);
-                if (rcm != BMI_OK) return rcm;
-            }
-            e->tensors[d.out].pooled_now = false;
-            if (op.nsplit > 1 && !op.stoch) {        // (under a row table too: conv_igemm's split-K form writes through it)
-                a.partial = (float*)(ws + e->splitk_off);
-                a.nsplit = op.nsplit;
-                prof.tag(BMI_CONV_FAMILY_IGEMM, flops, bytes);
-                return launch_conv_igemm(a, s);
-            }
-            if (opt_conv_pool() == 1 && op.pool_pw_ok) {      // ("conv_pool" = 2: conv3x3_s2's only)
-                ConvArgs q = a;
-                q.pool = (float*)q.out;
-                const int rcp = launch_conv3x3_pw(q, s);
-                if (rcp != BMI_ERR_UNSUPPORTED) {
-                    prof.tag(BMI_CONV_FAMILY_PW, flops, bytes);
-                    e->tensors[d.out].pooled_now = true;
-                    return rcp;
-                }
-            }
-            if (opt_conv_pool() && op.pool_ok) {
-                ConvArgs q = a;
-                q.pool = (float*)q.out;
-                const int rcp = launch_conv3x3_s2(q, s);
-                if (rcp != BMI_ERR_UNSUPPORTED) {
-                    prof.tag(BMI_CONV_FAMILY_S2, flops, bytes);
-                    e->tensors[d.out].pooled_now = true;
-                    return rcp;
-                }
-            }
-            int fam = -1;
-            const int rcc = launch_conv(a, s, &fam);
-            prof.tag(fam, flops, bytes);
-            return rcc;
-        }
+        case BMI_OP_CONV:
+            return run_conv(e, p, op, N, t0, Bc, rows, n_rows, prof);
         case OP_MASKBITS:
             return launch_mask_bits((uint8_t*)(ws + e->tensors[d.out].offset), N, tin.h * tin.w, tin.c,
-                                    pass_site(e, p, &d.site, site_off(d.site, (size_t)tin.h * tin.w * tin.c, (size_t)tin.c)), B, t0, s);
+                                    pass_site(e, p, &d.site, site_off(p, d.site, (size_t)tin.h * tin.w * tin.c, (size_t)tin.c)), B, t0, s);
         case BMI_OP_MASK: {
             EltArgs a;
             std::memset(&a, 0, sizeof(a));
@@ -1396,7 +1478,7 @@ int run_op(bmi_engine_s* e, const Pass& p, const OpInfo& op, int N, int t0, cons
             a.out = ws + e->tensors[d.out].offset;
             a.N = N; a.in_mod = tin.stoch ? n_rows : B; a.HW = tin.h * tin.w; a.C = tin.c; a.B = B; a.t0 = t0;
             a.rows = rows;
-            a.site = pass_site(e, p, &d.site, site_off(d.site, (size_t)tin.h * tin.w * tin.c, (size_t)tin.c));
+            a.site = pass_site(e, p, &d.site, site_off(p, d.site, (size_t)tin.h * tin.w * tin.c, (size_t)tin.c));
             if (d.site_pos == BMI_SITE_POS_INNER) { a.bias_post = d.bias_post; a.relu = d.relu; }
             a.pair = e->split;                                     // the split engines: pair32 tensors in and out
             if (e->f32) return launch_mask_apply_f32(a, s);
@@ -1428,7 +1510,7 @@ int run_op(bmi_engine_s* e, const Pass& p, const OpInfo& op, int N, int t0, cons
             // input: fp32 (a dense layer's output; any tensor of the exact engine), the engine's 16-bit type, or pair32 (kinds 3 | 4)
             return launch_dense_f32(ws + tin.offset, (e->split && !tin.dense_out) ? 2 + e->split : (tin.f32 ? 1 : (e->bf16 ? 2 : 0)), (const float*)d.weight, d.bias,
                                     (float*)(ws + e->tensors[d.out].offset), N, tin.stoch ? n_rows : B, tin.c, op.cout, d.relu,
-                                    pass_site(e, p, &d.site, site_off(d.site, (size_t)op.cout, (size_t)op.cout)), B, t0, s, rows);
+                                    pass_site(e, p, &d.site, site_off(p, d.site, (size_t)op.cout, (size_t)op.cout)), B, t0, s, rows);
         case BMI_OP_HEAD:
             // pool + site + Linear + softmax + the chunk's moment sums in one launch (head_fused.hip)
             return launch_head_fused(make_head_args(e, p, op, N, t0, imap, Bc), s);
@@ -1482,6 +1564,21 @@ struct EnsembleSums {
     float* scratch;
 };
 
+// The argument check the three *_ensemble entry points share, in front of their own entry point's checks
+int ensemble_args_ok(bmi_handle h, int32_t batch, const double* Q1, const double* Q2, const double* QH, const void* scratch, size_t scratch_bytes) {
+    if (!h || !Q1 || !Q2 || !QH || !scratch) return BMI_ERR_INVALID;
+    if (!ensemble_takes(h->n_exits, h->out_dim)) return BMI_ERR_UNSUPPORTED;
+    if (h->max_batch == 0 || batch < 1 || batch > h->max_batch) return BMI_ERR_INVALID;
+    if (scratch_bytes < bmi_ensemble_scratch_bytes(h, batch)) return BMI_ERR_NOMEM;
+    return BMI_OK;
+}
+
+// Adds the tc samples of per-sample logits in ens.scratch ([tc][E][B][C]) to the ensemble sums, under the handle's calibration: the one
+// launch_ensemble_moments call of the engine.  rows: the images (and of each its exits) the launch covers, default: all.
+int ensemble_add(const bmi_engine_s* e, const EnsembleSums& ens, int tc, int B, hipStream_t s, const EnsRows& rows = EnsRows()) {
+    return launch_ensemble_moments(ens.scratch, tc, e->n_exits, B, e->out_dim, e->cal, rows, ens.Q1, ens.Q2, ens.QH, s);
+}
+
 // The folded path: the prefix once, then samples t_begin .. t_begin+t_count-1 through the suffix, `chunk` at a time.
 // ens: every chunk's heads also write their logits into ens->scratch (a runtime branch of the same kernels: S1 / S2 / SL / SH keep their
 // bits), and one launch of ensemble.hip behind them adds the chunk's samples, in sample order, to the ensemble sums.
@@ -1498,8 +1595,9 @@ int forward_folded(bmi_engine_s* e, const Pass& p, int t_begin, int t_count, con
         int rc = run_suffix(e, pc, tc * p.B, t0);
         if (rc != BMI_OK) return rc;
         if (!ens) continue;
-        rc = launch_ensemble_moments(ens->scratch, tc, e->n_exits, p.B, e->out_dim, e->inv_tau.empty() ? nullptr : e->inv_tau.data(), ens->Q1,
-                                     ens->Q2, ens->QH, p.stream, nullptr, 0, nullptr, e->ens_w, e->vec_scale, e->vec_bias);
+        // (no BMI_PROFILE_ENSEMBLE record here, unlike the staged and adaptive paths: the profile tables of this path never had one, and
+        //  adding it is a change of what profile_launches() returns, not a refactoring)
+        rc = ensemble_add(e, *ens, tc, p.B, p.stream);
         if (rc != BMI_OK) return rc;
     }
     return BMI_OK;
@@ -1573,10 +1671,9 @@ size_t bmi_ensemble_scratch_bytes(bmi_handle h, int32_t batch) {
 int bmi_forward_mcd_ensemble(bmi_handle h, const float* x_nchw, int32_t batch, int32_t image_offset, int32_t t_begin, int32_t t_count,
                              uint64_t seed, int32_t mask_cnt0, double* S1, double* S2, double* SL, double* SH, double* Q1, double* Q2,
                              double* QH, void* scratch, size_t scratch_bytes, void* workspace, size_t workspace_bytes, bmi_stream stream) {
-    if (!h || !SH || !Q1 || !Q2 || !QH || !scratch) return BMI_ERR_INVALID;
-    if (!ensemble_takes(h->n_exits, h->out_dim)) return BMI_ERR_UNSUPPORTED;
-    if (h->max_batch == 0 || batch < 1 || batch > h->max_batch) return BMI_ERR_INVALID;
-    if (scratch_bytes < bmi_ensemble_scratch_bytes(h, batch)) return BMI_ERR_NOMEM;
+    if (!h || !SH) return BMI_ERR_INVALID;
+    const int rce = ensemble_args_ok(h, batch, Q1, Q2, QH, scratch, scratch_bytes);
+    if (rce != BMI_OK) return rce;
     const EnsembleSums ens{Q1, Q2, QH, (float*)scratch};
     return forward_moments(h, x_nchw, batch, image_offset, t_begin, t_count, seed, mask_cnt0, S1, S2, SL, SH, workspace, workspace_bytes, stream,
                            &ens);
@@ -1636,10 +1733,7 @@ int bmi_forward_mcd_exit(bmi_handle h, const float* x_nchw, int32_t batch, int32
     Pass p{x_nchw, (char*)workspace, (hipStream_t)stream, batch, seed, mask_cnt0};
     p.S1 = S1; p.S2 = S2; p.SL = SL;
     const hipStream_t s = p.stream;
-    char* const ws = p.ws;
-    int* lists[2] = {(int*)(ws + h->exit_off), (int*)(ws + h->exit_off) + h->max_batch};
-    int* count_dev = (int*)(ws + h->exit_off) + 2 * h->max_batch;
-    int* rows_dev = count_dev + 64;
+    ActiveImages on(h, p.ws, batch, s);
     int rc = launch_fill_int(exit_of_image, batch, last, s);
     if (rc != BMI_OK) return rc;
     for (int x = 0; x < h->n_exits; ++x) active_after[x] = 0;
@@ -1647,31 +1741,23 @@ int bmi_forward_mcd_exit(bmi_handle h, const float* x_nchw, int32_t batch, int32
         rc = run_op(h, p, op, batch, 0);
         if (rc != BMI_OK) return rc;
     }
-    const int* imap = nullptr;     // null: every image is still active
-    const int* rows = nullptr;
-    int bc = batch, cur = 0;
     for (const OpInfo& op : h->suffix) {
-        rc = run_op(h, p, op, t_count * bc, 0, imap, bc, rows);
+        rc = run_op(h, p, op, t_count * on.bc, 0, on.act, on.bc, on.rows);
         if (rc != BMI_OK) return rc;
         if (op.d.kind != BMI_OP_HEAD) continue;
         const int e = op.d.out;
-        if (e < first_exit || e >= last) { active_after[e] = bc; continue; }
+        if (e < first_exit || e >= last) { active_after[e] = on.bc; continue; }
         // confidence test of exit e over the still-active images, on the device; the host only learns how many go on
-        rc = launch_exit_decide(S1 + (size_t)e * batch * h->out_dim, h->out_dim, t_count, threshold, imap, bc, lists[cur], count_dev,
+        rc = launch_exit_decide(S1 + (size_t)e * batch * h->out_dim, h->out_dim, t_count, threshold, on.act, on.bc, on.next(), on.count_dev,
                                 exit_of_image, e, s);
         if (rc != BMI_OK) return rc;
         int n_active = 0;
-        if (hipMemcpyAsync(&n_active, count_dev, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess)
-            return BMI_ERR_HIP;
+        rc = on.read_count(&n_active);
+        if (rc != BMI_OK) return rc;
         active_after[e] = n_active;
         if (n_active == 0) return BMI_OK;                    // every image has left: the later stages do not run at all
-        imap = lists[cur];
-        bc = n_active;
-        cur ^= 1;
-        rc = launch_expand_rows(imap, bc, batch, t_count, rows_dev, s);     // compact image -> tensor row, for the conv kernels
+        rc = on.take(n_active, t_count);
         if (rc != BMI_OK) return rc;
-        rows = rows_dev;
     }
     return BMI_OK;
 }
@@ -1699,9 +1785,7 @@ static int exit_staged(bmi_handle h, const float* x_nchw, int32_t batch, int32_t
     p.S1 = S1; p.S2 = S2; p.SL = SL; p.SH = SH;
     if (ens) { p.logits = ens->scratch; p.logits_t_begin = 0; }
     const hipStream_t s = p.stream;
-    int* lists[2] = {(int*)(p.ws + h->exit_off), (int*)(p.ws + h->exit_off) + h->max_batch};
-    int* count_dev = (int*)(p.ws + h->exit_off) + 2 * h->max_batch;
-    int* rows_dev = count_dev + 64;
+    ActiveImages on(h, p.ws, batch, s);
     int rc = launch_fill_int(exit_of_image, batch, last, s);
     if (rc != BMI_OK) return rc;
     for (int x = 0; x < h->n_exits; ++x) active_after[x] = 0;
@@ -1710,45 +1794,38 @@ static int exit_staged(bmi_handle h, const float* x_nchw, int32_t batch, int32_t
         if (!ens) return BMI_OK;
         ProfScope prof(h, BMI_PROFILE_ENSEMBLE, s);
         prof.r.images = t_count * batch;
-        const int rce = launch_exit_counts(exit_of_image, batch, lists[0], s);
+        int* const n_e = on.lists[0];
+        const int rce = launch_exit_counts(exit_of_image, batch, n_e, s);
         if (rce != BMI_OK) return rce;
-        return launch_ensemble_moments(ens->scratch, t_count, h->n_exits, batch, h->out_dim, h->inv_tau.empty() ? nullptr : h->inv_tau.data(),
-                                       ens->Q1, ens->Q2, ens->QH, s, nullptr, 0, lists[0], h->ens_w, h->vec_scale, h->vec_bias);
+        return ensemble_add(h, *ens, t_count, batch, s, EnsRows{nullptr, 0, n_e});
     };
-    const int* act = nullptr;      // null: every image is still active (stage 0: bmi_forward_mcd's launches)
-    const int* rows = nullptr;
-    int bc = batch, cur = 0;
     std::vector<const OpInfo*> stage_ops;
     for (int k = 0; fe + k <= last; ++k) {
         // the stage's prefix ops once per active image (rows = the active list); those without a row-table form over the whole batch
         for (const OpInfo& op : h->prefix) {
             if (op_stage(op, fe) != k) continue;
-            rc = (act && prefix_row_form(h, op)) ? run_op(h, p, op, bc, 0, act, bc, act) : run_op(h, p, op, batch, 0);
+            rc = (on.act && prefix_row_form(h, op)) ? run_op(h, p, op, on.bc, 0, on.act, on.bc, on.act) : run_op(h, p, op, batch, 0);
             if (rc != BMI_OK) return rc;
         }
         stage_ops.clear();
         for (const OpInfo& op : h->suffix)
             if (op_stage(op, fe) == k) stage_ops.push_back(&op);
-        rc = run_suffix_ops(h, p, stage_ops.size(), [&](size_t i) -> const OpInfo& { return *stage_ops[i]; }, t_count * bc, 0, act, bc, rows);
+        rc = run_suffix_ops(h, p, stage_ops.size(), [&](size_t i) -> const OpInfo& { return *stage_ops[i]; }, t_count * on.bc, 0, on.act, on.bc, on.rows);
         if (rc != BMI_OK) return rc;
         const int e = fe + k;          // the exit tested after this stage (none after the last)
         for (const OpInfo* op : stage_ops)
-            if (op->d.kind == BMI_OP_HEAD && (op->d.out != e || e == last)) active_after[op->d.out] = bc;
+            if (op->d.kind == BMI_OP_HEAD && (op->d.out != e || e == last)) active_after[op->d.out] = on.bc;
         if (e == last) break;
-        rc = launch_exit_rule_decide(S1, batch, h->out_dim, t_count, rule->threshold, rule->criterion == BMI_EXIT_MARGIN, rule->ensemble, act, bc,
-                                     lists[cur], count_dev, exit_of_image, e, s, h->ens_w, h->n_exits);
+        rc = launch_exit_rule_decide(S1, batch, h->out_dim, t_count, rule->threshold, rule->criterion == BMI_EXIT_MARGIN, rule->ensemble, on.act, on.bc,
+                                     on.next(), on.count_dev, exit_of_image, e, s, h->cal.ens_w, h->n_exits);
         if (rc != BMI_OK) return rc;
         int n_active = 0;
-        if (hipMemcpyAsync(&n_active, count_dev, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-            return BMI_ERR_HIP;
+        rc = on.read_count(&n_active);
+        if (rc != BMI_OK) return rc;
         active_after[e] = n_active;
         if (n_active == 0) return ensemble_readout();        // every image has left: the later stages do not run at all
-        act = lists[cur];
-        bc = n_active;
-        cur ^= 1;
-        rc = launch_expand_rows(act, bc, batch, t_count, rows_dev, s);     // compact image -> tensor row of the suffix launches
+        rc = on.take(n_active, t_count);
         if (rc != BMI_OK) return rc;
-        rows = rows_dev;
     }
     return ensemble_readout();
 }
@@ -1764,10 +1841,8 @@ int bmi_forward_mcd_exit_staged_ensemble(bmi_handle h, const float* x_nchw, int3
                                          const bmi_exit_rule* rule, double* S1, double* S2, double* SL, double* SH, double* Q1, double* Q2,
                                          double* QH, void* scratch, size_t scratch_bytes, int32_t* exit_of_image, int32_t* active_after,
                                          void* workspace, size_t workspace_bytes, bmi_stream stream) {
-    if (!h || !Q1 || !Q2 || !QH || !scratch) return BMI_ERR_INVALID;
-    if (!ensemble_takes(h->n_exits, h->out_dim)) return BMI_ERR_UNSUPPORTED;
-    if (h->max_batch == 0 || batch < 1 || batch > h->max_batch) return BMI_ERR_INVALID;
-    if (scratch_bytes < bmi_ensemble_scratch_bytes(h, batch)) return BMI_ERR_NOMEM;
+    const int rce = ensemble_args_ok(h, batch, Q1, Q2, QH, scratch, scratch_bytes);
+    if (rce != BMI_OK) return rce;
     const EnsembleSums ens{Q1, Q2, QH, (float*)scratch};
     return exit_staged(h, x_nchw, batch, t_count, seed, mask_cnt0, rule, S1, S2, SL, SH, exit_of_image, active_after, workspace, workspace_bytes,
                        stream, &ens);
@@ -1797,10 +1872,7 @@ static int adaptive(bmi_handle h, const float* x_nchw, int32_t batch, int32_t im
     p.b0 = image_offset;
     p.S1 = S1; p.S2 = S2; p.SL = SL; p.SH = SH;
     const hipStream_t s = p.stream;
-    // the exit region of the workspace (bmi_plan): two active-image lists, a counter, the row table
-    int* lists[2] = {(int*)(p.ws + h->exit_off), (int*)(p.ws + h->exit_off) + h->max_batch};
-    int* count_dev = (int*)(p.ws + h->exit_off) + 2 * h->max_batch;
-    int* rows_dev = count_dev + 64;
+    ActiveImages on(h, p.ws, batch, s);      // act null: every image is still active — the step runs bmi_forward_mcd's kernels
     const size_t eo = (size_t)test_exit * batch * h->out_dim;
     const double* const R1 = (stop_on == BMI_STOP_ON_ENSEMBLE ? ens->Q1 : S1) + eo;      // the [batch][C] sums the rule reads
     const double* const R2 = (stop_on == BMI_STOP_ON_ENSEMBLE ? ens->Q2 : S2) + eo;
@@ -1811,36 +1883,28 @@ static int adaptive(bmi_handle h, const float* x_nchw, int32_t batch, int32_t im
         rc = run_op(h, p, op, batch, 0);
         if (rc != BMI_OK) return rc;
     }
-    const int* imap = nullptr;     // null: every image is still active — the step runs bmi_forward_mcd's kernels
-    const int* rows = nullptr;
-    int bc = batch, cur = 0;
     for (int k = 0, t0 = 0; k < n_steps; ++k, t0 += t_step) {
         const int tc = std::min(t_step, t_max - t0);
         if (ens) { p.logits = ens->scratch; p.logits_t_begin = t0; }
-        rc = run_suffix(h, p, tc * bc, t0, imap, bc, rows);
+        rc = run_suffix(h, p, tc * on.bc, t0, on.act, on.bc, on.rows);
         if (rc != BMI_OK) return rc;
         if (ens) {
             ProfScope prof(h, BMI_PROFILE_ENSEMBLE, s);
-            prof.r.images = tc * bc;
-            rc = launch_ensemble_moments(ens->scratch, tc, h->n_exits, batch, h->out_dim, h->inv_tau.empty() ? nullptr : h->inv_tau.data(), ens->Q1,
-                                         ens->Q2, ens->QH, s, imap, bc, nullptr, h->ens_w, h->vec_scale, h->vec_bias);
+            prof.r.images = tc * on.bc;
+            rc = ensemble_add(h, *ens, tc, batch, s, EnsRows{on.act, on.bc, nullptr});
             if (rc != BMI_OK) return rc;
         }
         // the stop rule over the still-active images, on the device; the host only learns how many go on
-        rc = launch_adaptive_decide(R1, R2, h->out_dim, t0 + tc, rule, threshold, imap, bc, lists[cur], count_dev, t_used, s);
+        rc = launch_adaptive_decide(R1, R2, h->out_dim, t0 + tc, rule, threshold, on.act, on.bc, on.next(), on.count_dev, t_used, s);
         if (rc != BMI_OK) return rc;
         int n_active = 0;
-        if (hipMemcpyAsync(&n_active, count_dev, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-            return BMI_ERR_HIP;
+        rc = on.read_count(&n_active);
+        if (rc != BMI_OK) return rc;
         active_after_step[k] = n_active;
         if (n_active == 0 || k + 1 == n_steps) break;
         if (n_active == batch) continue;           // nobody has retired yet: the next step runs on the full grids too
-        imap = lists[cur];
-        bc = n_active;
-        cur ^= 1;
-        rc = launch_expand_rows(imap, bc, batch, std::min(t_step, t_max - t0 - t_step), rows_dev, s);   // compact image -> tensor row
+        rc = on.take(n_active, std::min(t_step, t_max - t0 - t_step));
         if (rc != BMI_OK) return rc;
-        rows = rows_dev;
     }
     return converged ? launch_adaptive_converged(R1, R2, h->out_dim, rule, threshold, batch, t_used, converged, s) : BMI_OK;
 }
@@ -1859,11 +1923,9 @@ int bmi_forward_mcd_adaptive_ensemble(bmi_handle h, const float* x_nchw, int32_t
                                       double* S1, double* S2, double* SL, double* SH, double* Q1, double* Q2, double* QH, void* scratch,
                                       size_t scratch_bytes, int32_t* t_used, uint8_t* converged, int32_t* active_after_step, void* workspace,
                                       size_t workspace_bytes, bmi_stream stream) {
-    if (!h || !Q1 || !Q2 || !QH || !scratch) return BMI_ERR_INVALID;
-    if (stop_on != BMI_STOP_ON_EXIT && stop_on != BMI_STOP_ON_ENSEMBLE) return BMI_ERR_INVALID;
-    if (!ensemble_takes(h->n_exits, h->out_dim)) return BMI_ERR_UNSUPPORTED;
-    if (h->max_batch == 0 || batch < 1 || batch > h->max_batch) return BMI_ERR_INVALID;
-    if (scratch_bytes < bmi_ensemble_scratch_bytes(h, batch)) return BMI_ERR_NOMEM;
+    if (stop_on != BMI_STOP_ON_EXIT && stop_on != BMI_STOP_ON_ENSEMBLE) return BMI_ERR_INVALID;      // (BMI_ERR_INVALID like the null checks next)
+    const int rce = ensemble_args_ok(h, batch, Q1, Q2, QH, scratch, scratch_bytes);
+    if (rce != BMI_OK) return rce;
     const EnsembleSums ens{Q1, Q2, QH, (float*)scratch};
     return adaptive(h, x_nchw, batch, image_offset, t_max, t_step, seed, mask_cnt0, rule, threshold, test_exit, S1, S2, SL, SH, t_used, converged,
                     active_after_step, workspace, workspace_bytes, stream, &ens, stop_on);
@@ -1924,37 +1986,40 @@ int bmi_finalize_ensemble_per_image(int32_t n_exits, int32_t batch, int32_t out_
                                               mutual_info, nonfinite, (hipStream_t)stream);
 }
 
-static int ensemble_moments_entry(const float* logits, int32_t T, int32_t E, int32_t B, int32_t C, const float* tau, const double* W, double* Q1,
+// bmi_ensemble_moments, _weighted and _vector: cal holds what the entry point was given beside tau (the weights, the vector scaling)
+static int ensemble_moments_entry(const float* logits, int32_t T, int32_t E, int32_t B, int32_t C, const float* tau, Calibration cal, double* Q1,
                                   double* Q2, double* QH, bmi_stream stream) {
     if (!logits || !Q1 || !Q2 || !QH || T < 1 || E < 1 || B < 1 || C < 1) return BMI_ERR_INVALID;
     if (!ensemble_takes(E, C)) return BMI_ERR_UNSUPPORTED;
-    float inv[BMI_ENS_MAX_EXITS];
     if (tau)
         for (int e = 0; e < E; ++e) {
             if (!(tau[e] > 0.f) || !std::isfinite(tau[e])) return BMI_ERR_INVALID;
-            inv[e] = (float)(1.0 / (double)tau[e]);       // (bmi_engine_set_temperature's rounding)
-            if (!(inv[e] > 0.f) || !std::isfinite(inv[e])) return BMI_ERR_INVALID;
+            const float inv = (float)(1.0 / (double)tau[e]);       // (bmi_engine_set_temperature's rounding)
+            if (!(inv > 0.f) || !std::isfinite(inv)) return BMI_ERR_INVALID;
+            cal.inv_tau.push_back(inv);
         }
-    return launch_ensemble_moments(logits, T, E, B, C, tau ? inv : nullptr, Q1, Q2, QH, (hipStream_t)stream, nullptr, 0, nullptr, W);
+    return launch_ensemble_moments(logits, T, E, B, C, cal, EnsRows(), Q1, Q2, QH, (hipStream_t)stream);
 }
 
 int bmi_ensemble_moments(const float* logits, int32_t T, int32_t E, int32_t B, int32_t C, const float* tau, double* Q1, double* Q2, double* QH,
                          bmi_stream stream) {
-    return ensemble_moments_entry(logits, T, E, B, C, tau, nullptr, Q1, Q2, QH, stream);
+    return ensemble_moments_entry(logits, T, E, B, C, tau, Calibration(), Q1, Q2, QH, stream);
 }
 
 int bmi_ensemble_moments_weighted(const float* logits, int32_t T, int32_t E, int32_t B, int32_t C, const float* tau, const double* W_device,
                                   double* Q1, double* Q2, double* QH, bmi_stream stream) {
     if (!W_device) return BMI_ERR_INVALID;
-    return ensemble_moments_entry(logits, T, E, B, C, tau, W_device, Q1, Q2, QH, stream);
+    Calibration cal;
+    cal.ens_w = W_device;
+    return ensemble_moments_entry(logits, T, E, B, C, tau, cal, Q1, Q2, QH, stream);
 }
 
 int bmi_ensemble_moments_vector(const float* logits, int32_t T, int32_t E, int32_t B, int32_t C, const float* scale_device, const float* bias_device,
                                 const double* W_device, double* Q1, double* Q2, double* QH, bmi_stream stream) {
-    if (!logits || !scale_device || !bias_device || !Q1 || !Q2 || !QH || T < 1 || E < 1 || B < 1 || C < 1) return BMI_ERR_INVALID;
-    if (!ensemble_takes(E, C)) return BMI_ERR_UNSUPPORTED;
-    return launch_ensemble_moments(logits, T, E, B, C, nullptr, Q1, Q2, QH, (hipStream_t)stream, nullptr, 0, nullptr, W_device, scale_device,
-                                   bias_device);
+    if (!scale_device || !bias_device) return BMI_ERR_INVALID;
+    Calibration cal;
+    cal.vec_scale = scale_device; cal.vec_bias = bias_device; cal.ens_w = W_device;
+    return ensemble_moments_entry(logits, T, E, B, C, nullptr, cal, Q1, Q2, QH, stream);
 }
 
 size_t bmi_nll_vector_scratch_bytes(int32_t E, int32_t B, int32_t C) {

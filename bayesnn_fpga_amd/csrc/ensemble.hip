@@ -161,46 +161,42 @@ bool ensemble_takes(int E, int C) {
     return E >= 1 && C >= 1 && E <= BMI_ENS_MAX_EXITS && C <= BMI_ENS_MAX_CLASSES && E * (C | 1) <= ENS_SLAB;
 }
 
-template <bool ROWS, bool WEIGHTED>
-static void launch_ens(unsigned grid, hipStream_t s, const float* logits, int T, int E, int B, int C, int CS, int TS, int L, const EnsTau& tau,
-                       double* Q1, double* Q2, double* QH, const int* list, const int* n_e, const double* W) {
-    hipLaunchKernelGGL((ensemble_moments_kernel<ROWS, WEIGHTED>), dim3(grid), dim3(ENS_THREADS), 0, s, logits, T, E, B, C, CS, TS, L, tau, Q1, Q2,
-                       QH, list, n_e, W);
+// One of the eight kernels: the vector form (VEC) takes the two coefficient arrays where the tempered form takes the table of inverses
+template <bool VEC, bool ROWS, bool WEIGHTED>
+static void launch_ens(unsigned grid, hipStream_t s, const float* logits, int T, int E, int B, int C, int CS, int TS, int L, const Calibration& cal,
+                       const EnsTau& tau, const EnsRows& rows, double* Q1, double* Q2, double* QH) {
+    if constexpr (VEC)
+        hipLaunchKernelGGL((ensemble_moments_vec_kernel<ROWS, WEIGHTED>), dim3(grid), dim3(ENS_THREADS), 0, s, logits, T, E, B, C, CS, TS, L,
+                           cal.vec_scale, cal.vec_bias, Q1, Q2, QH, rows.list, rows.n_e, cal.ens_w);
+    else
+        hipLaunchKernelGGL((ensemble_moments_kernel<ROWS, WEIGHTED>), dim3(grid), dim3(ENS_THREADS), 0, s, logits, T, E, B, C, CS, TS, L, tau, Q1, Q2,
+                           QH, rows.list, rows.n_e, cal.ens_w);
 }
 
-template <bool ROWS, bool WEIGHTED>
-static void launch_ens_vec(unsigned grid, hipStream_t s, const float* logits, int T, int E, int B, int C, int CS, int TS, int L, const float* vs,
-                           const float* vb, double* Q1, double* Q2, double* QH, const int* list, const int* n_e, const double* W) {
-    hipLaunchKernelGGL((ensemble_moments_vec_kernel<ROWS, WEIGHTED>), dim3(grid), dim3(ENS_THREADS), 0, s, logits, T, E, B, C, CS, TS, L, vs, vb, Q1,
-                       Q2, QH, list, n_e, W);
+// The one dispatch over (ROWS, WEIGHTED), for either form
+template <bool VEC, class... Args>
+static void dispatch_ens(bool by_rows, bool weighted, const Args&... args) {
+    if (by_rows && weighted) launch_ens<VEC, true, true>(args...);
+    else if (by_rows) launch_ens<VEC, true, false>(args...);
+    else if (weighted) launch_ens<VEC, false, true>(args...);
+    else launch_ens<VEC, false, false>(args...);
 }
 
-int launch_ensemble_moments(const float* logits, int T, int E, int B, int C, const float* inv_tau, double* Q1, double* Q2, double* QH,
-                            hipStream_t s, const int* list, int Bc, const int* n_e, const double* W, const float* vec_scale,
-                            const float* vec_bias) {
-    if (T < 1 || B < 1 || (list && (Bc < 1 || Bc > B))) return BMI_ERR_INVALID;
-    if ((vec_scale != nullptr) != (vec_bias != nullptr) || (vec_scale && inv_tau)) return BMI_ERR_INVALID;
+int launch_ensemble_moments(const float* logits, int T, int E, int B, int C, const Calibration& cal, const EnsRows& rows, double* Q1, double* Q2,
+                            double* QH, hipStream_t s) {
+    if (T < 1 || B < 1 || (rows.list && (rows.Bc < 1 || rows.Bc > B))) return BMI_ERR_INVALID;
+    if ((cal.vec_scale != nullptr) != (cal.vec_bias != nullptr) || (cal.vec_scale && !cal.inv_tau.empty())) return BMI_ERR_INVALID;
     if (!ensemble_takes(E, C)) return BMI_ERR_UNSUPPORTED;
     const int CS = C | 1;                                // odd row stride
     const int TS = std::min(ENS_SLAB / (E * CS), ENS_ROWS / E);      // >= 1 (ensemble_takes)
     int L = 1;
     while (L < C && L < 64) L <<= 1;
     EnsTau tau;
-    for (int e = 0; e < BMI_ENS_MAX_EXITS; ++e) tau.inv[e] = (inv_tau && e < E) ? inv_tau[e] : 1.f;
-    const bool rows = list || n_e;
-    const unsigned grid = (unsigned)(list ? Bc : B);
-    if (vec_scale) {
-        if (rows && W) launch_ens_vec<true, true>(grid, s, logits, T, E, B, C, CS, TS, L, vec_scale, vec_bias, Q1, Q2, QH, list, n_e, W);
-        else if (rows) launch_ens_vec<true, false>(grid, s, logits, T, E, B, C, CS, TS, L, vec_scale, vec_bias, Q1, Q2, QH, list, n_e, nullptr);
-        else if (W) launch_ens_vec<false, true>(grid, s, logits, T, E, B, C, CS, TS, L, vec_scale, vec_bias, Q1, Q2, QH, nullptr, nullptr, W);
-        else launch_ens_vec<false, false>(grid, s, logits, T, E, B, C, CS, TS, L, vec_scale, vec_bias, Q1, Q2, QH, nullptr, nullptr, nullptr);
-        BMI_CHECK_LAUNCH();
-        return BMI_OK;
-    }
-    if (rows && W) launch_ens<true, true>(grid, s, logits, T, E, B, C, CS, TS, L, tau, Q1, Q2, QH, list, n_e, W);
-    else if (rows) launch_ens<true, false>(grid, s, logits, T, E, B, C, CS, TS, L, tau, Q1, Q2, QH, list, n_e, nullptr);
-    else if (W) launch_ens<false, true>(grid, s, logits, T, E, B, C, CS, TS, L, tau, Q1, Q2, QH, nullptr, nullptr, W);
-    else launch_ens<false, false>(grid, s, logits, T, E, B, C, CS, TS, L, tau, Q1, Q2, QH, nullptr, nullptr, nullptr);
+    for (int e = 0; e < BMI_ENS_MAX_EXITS; ++e) tau.inv[e] = e < E && e < (int)cal.inv_tau.size() ? cal.inv_tau[e] : 1.f;
+    const bool by_rows = rows.list || rows.n_e, weighted = cal.ens_w != nullptr;
+    const unsigned grid = (unsigned)(rows.list ? rows.Bc : B);
+    if (cal.vec_scale) dispatch_ens<true>(by_rows, weighted, grid, s, logits, T, E, B, C, CS, TS, L, cal, tau, rows, Q1, Q2, QH);
+    else dispatch_ens<false>(by_rows, weighted, grid, s, logits, T, E, B, C, CS, TS, L, cal, tau, rows, Q1, Q2, QH);
     BMI_CHECK_LAUNCH();
     return BMI_OK;
 }

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <vector>
+
 #include "../../include/bayesnn_fpga_amd.h"
 #include "philox.h"
 
@@ -197,19 +199,32 @@ bool nll_vector_takes(int E, int B, int C);
 int launch_nll_vector_scaling_grad(const float* logits, int T, int E, int B, int C, const int* labels, const double* scale, const double* bias,
                                    double* nll, double* grad_scale, double* grad_bias, double* scratch, hipStream_t s);
 // ensemble.hip (bmi_ensemble_moments): Q1 / Q2 [E][B][C] and QH [E][B] += the moments and the entropy of the per-sample exit ensembles
-// q_te = mean_{i<=e} softmax(fl32(l_ti * inv_tau[i])) of logits [T][E][B][C], in sample order onto the running sums; inv_tau: host [E] or null
+// q_te = mean_{i<=e} softmax(fl32(l_ti * inv_tau[i])) of logits [T][E][B][C], in sample order onto the running sums
 #define BMI_ENS_MAX_EXITS 32
 #define BMI_ENS_MAX_CLASSES 128
 bool ensemble_takes(int E, int C);
-// list / Bc / n_e (device int32, each null: not used): the launch covers the Bc images list[0 .. Bc-1] of the batch only, and of image b only
-// its first n_e[b] exits; every row that is computed holds the plain launch's bits, the other rows are neither read nor written
-// W (device float64 [E][E] row-major, null: the equal-weight mean above): q_te = sum_{i<=e} W[e][i] p_ti in exit order, the weights as given;
-// of image b only the rows e < n_e[b] of W are read (bmi_engine_set_ensemble_weights, bmi_ensemble_moments_weighted)
-// vec_scale / vec_bias (device fp32 [E][C], both or neither, inv_tau null then): z = fl32(fl32(l * vec_scale[e][c]) + vec_bias[e][c]) in place
-// of the tempered product (bmi_engine_set_vector_scaling, bmi_ensemble_moments_vector)
-int launch_ensemble_moments(const float* logits, int T, int E, int B, int C, const float* inv_tau, double* Q1, double* Q2, double* QH,
-                            hipStream_t s, const int* list = nullptr, int Bc = 0, const int* n_e = nullptr, const double* W = nullptr,
-                            const float* vec_scale = nullptr, const float* vec_bias = nullptr);
+// Calibration: the calibration map in force and the ensemble weights — ONE host-side record (no kernel receives it): the engine handle keeps
+// one (written by bmi_engine_set_temperature / _vector_scaling / _ensemble_weights, read by the head and ensemble launches), the single-kernel
+// entry points build one from their arguments.
+//   inv_tau    host [E]: float32(1 / (double)tau[e]), what the heads and the ensemble members multiply by; EMPTY: off (never set, or all ones)
+//   vec_scale / vec_bias   the caller's DEVICE fp32 [E][C] (not owned; both or neither), null: off; never together with a non-empty inv_tau:
+//              z = fl32(fl32(l * vec_scale[e][c]) + vec_bias[e][c]) in place of the tempered product
+//   ens_w      the caller's DEVICE float64 [E][E] row-major (not owned), null: the equal-weight mean above; q_te = sum_{i<=e} W[e][i] p_ti in
+//              exit order, the weights as given; of image b only the rows e < n_e[b] are read
+struct Calibration {
+    std::vector<float> inv_tau;
+    const float *vec_scale = nullptr, *vec_bias = nullptr;
+    const double* ens_w = nullptr;
+};
+// EnsRows (device int32, each null: not used): the launch covers the Bc images list[0 .. Bc-1] of the batch only, and of image b only its first
+// n_e[b] exits; every row that is computed holds the plain launch's bits, the other rows are neither read nor written
+struct EnsRows {
+    const int* list = nullptr;
+    int Bc = 0;
+    const int* n_e = nullptr;
+};
+int launch_ensemble_moments(const float* logits, int T, int E, int B, int C, const Calibration& cal, const EnsRows& rows, double* Q1, double* Q2,
+                            double* QH, hipStream_t s);
 int launch_exit_counts(const int* exit_of, int n, int* n_e, hipStream_t s);      // n_e[b] = exit_of[b] + 1 (staged exit: the exits image b ran)
 // per (exit, image): mean / var of Q1 / Q2, the entropy of the mean, QH / T and their difference (bmi_finalize_ensemble)
 int launch_finalize_ensemble(int n_rows, int C, int t_total, const double* Q1, const double* Q2, const double* QH, double* mean, double* var,

@@ -395,6 +395,18 @@ def vary_mask(vary, n_exits):
     return mask
 
 
+def check_buffer(t, shape, dtype, device, name):
+    """The one validation of a buffer whose pointer goes to the C ABI: ``t`` is a contiguous tensor of ``dtype`` and ``shape`` (None: any
+    extent in that dimension) on ``device``; ``name`` is what the message calls it.  ValueError otherwise; returns ``t``."""
+    ok = isinstance(t, torch.Tensor) and t.dim() == len(shape) and all(w is None or w == g for w, g in zip(shape, t.shape)) and \
+        t.dtype == dtype and t.is_contiguous() and t.device == device
+    if not ok:
+        want = [("*" if w is None else w) for w in shape]
+        got = f"{t.dtype} {list(t.shape)} on {t.device}{'' if t.is_contiguous() else ', not contiguous'}" if isinstance(t, torch.Tensor) else repr(t)
+        raise ValueError(f"{name} must be a contiguous {dtype} tensor {want} on {device}, got {got}")
+    return t
+
+
 def build_graph(model, device, dtype="f16"):
     g = GraphBuilder(device, dtype)
     fam = getattr(model, "family", None)
@@ -668,14 +680,27 @@ class MCDEngine(CompiledGraph):
         self._forward(x, S, None, t_begin, t_count, seed, cnt0, image_offset)
         return S
 
+    def _check_sums(self, B, S, H, Q=None, QH=None, ensemble=False):
+        """The float64 sums of a batch of B images a forward call adds into: S [3, E, B, C] (``new_moments``) and, where given, H [E, B]
+        (``new_uncertainty_sums``), Q [2, E, B, C] and QH [E, B] (``new_ensemble_sums``); ``ensemble``: the call needs all four."""
+        E, Cd = self.n_exits, self.out_dim
+        for buf, shape, name, needed in ((S, (3, E, B, Cd), "moment buffer S", True), (H, (E, B), "entropy buffer H", ensemble),
+                                         (Q, (2, E, B, Cd), "ensemble buffer Q", ensemble), (QH, (E, B), "ensemble entropy buffer QH", ensemble)):
+            if needed or buf is not None:
+                check_buffer(buf, shape, torch.float64, self.device, name)
+
+    def _scratch(self, name, need):
+        """The engine's byte buffer ``name`` on the device, grown on demand to ``need`` bytes (never shrunk)."""
+        buf = self.__dict__.get(name)
+        if buf is None or buf.numel() < need:
+            buf = self.__dict__[name] = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return buf
+
     def _forward(self, x, S, H, t_begin, t_count, seed, cnt0, image_offset):
         """``accumulate`` (H None: bmi_forward_mcd_images) and ``accumulate_uncertainty`` (bmi_forward_mcd_entropy)."""
         x = self._check_x(x)
         B = x.shape[0]
-        if tuple(S.shape) != (3, self.n_exits, B, self.out_dim) or S.dtype != torch.float64 or not S.is_contiguous():
-            raise ValueError("moment buffer must be contiguous float64 [3, E, B, C]")
-        if H is not None and (tuple(H.shape) != (self.n_exits, B) or H.dtype != torch.float64 or not H.is_contiguous()):
-            raise ValueError("entropy buffer must be contiguous float64 [E, B]")
+        self._check_sums(B, S, H)
         name = "bmi_forward_mcd_images" if H is None else "bmi_forward_mcd_entropy"
         with torch.cuda.device(self.device):
             rc = getattr(self.lib, name)(self.handle, x.data_ptr(), B, int(image_offset), int(t_begin), int(t_count),
@@ -751,8 +776,7 @@ class MCDEngine(CompiledGraph):
         counter like finalize's (``check_finite``)."""
         r = self.finalize(S, t_total)
         E, B, Cd = S.shape[1], S.shape[2], S.shape[3]
-        if tuple(H.shape) != (E, B) or H.dtype != torch.float64 or not H.is_contiguous():
-            raise ValueError("entropy buffer must be contiguous float64 [E, B]")
+        check_buffer(H, (E, B), torch.float64, self.device, "entropy buffer H")
         out = torch.empty(3, E, B, dtype=torch.float64, device=S.device)
         with torch.cuda.device(self.device):
             rc = self.lib.bmi_finalize_uncertainty(E, B, Cd, int(t_total), S[0].data_ptr(), H.data_ptr(), out[0].data_ptr(), out[1].data_ptr(),
@@ -778,14 +802,11 @@ class MCDEngine(CompiledGraph):
         return (buf[:ns].view(3, E, batch, Cd), buf[ns:ns + nh].view(E, batch), buf[ns + nh:ns + nh + nq].view(2, E, batch, Cd),
                 buf[ns + nh + nq:].view(E, batch))
 
-    def _ensemble_scratch(self, batch):
+    def _ensemble_scratch(self):
         """One chunk of per-sample logits (bmi_ensemble_scratch_bytes), allocated once per engine — for ``max_batch`` — on first use."""
-        need = int(self.lib.bmi_ensemble_scratch_bytes(self.handle, int(batch)))
-        scratch = self.__dict__.get("_ens_scratch")
-        if scratch is None:
-            full = int(self.lib.bmi_ensemble_scratch_bytes(self.handle, self.max_batch))
-            scratch = self.__dict__["_ens_scratch"] = torch.empty(max(full, need, 1), dtype=torch.uint8, device=self.device)
-        return scratch, need
+        if "_ens_scratch" not in self.__dict__:
+            self._scratch("_ens_scratch", max(int(self.lib.bmi_ensemble_scratch_bytes(self.handle, self.max_batch)), 1))
+        return self.__dict__["_ens_scratch"]
 
     def accumulate_ensemble(self, x, S, H, Q, QH, t_begin, t_count, seed=0, cnt0=0, image_offset=0):
         """``accumulate_uncertainty`` (the same bits in S and H) that also adds, per sample, the exit ensembles q_e = mean of the softmax
@@ -795,12 +816,8 @@ class MCDEngine(CompiledGraph):
         temperature is set (``set_temperature``)."""
         x = self._check_x(x)
         B = x.shape[0]
-        E, Cd = self.n_exits, self.out_dim
-        for buf, shape, what in ((S, (3, E, B, Cd), "moment buffer S"), (H, (E, B), "entropy buffer H"), (Q, (2, E, B, Cd), "ensemble buffer Q"),
-                                 (QH, (E, B), "ensemble entropy buffer QH")):
-            if tuple(buf.shape) != shape or buf.dtype != torch.float64 or not buf.is_contiguous() or buf.device != self.device:
-                raise ValueError(f"{what} must be contiguous float64 {list(shape)} on {self.device}")
-        scratch, need = self._ensemble_scratch(B)
+        self._check_sums(B, S, H, Q, QH, ensemble=True)
+        scratch = self._ensemble_scratch()
         with torch.cuda.device(self.device):
             rc = self.lib.bmi_forward_mcd_ensemble(self.handle, x.data_ptr(), B, int(image_offset), int(t_begin), int(t_count),
                                                    int(seed) & 0xFFFFFFFFFFFFFFFF, int(cnt0), S[0].data_ptr(), S[1].data_ptr(), S[2].data_ptr(),
@@ -809,47 +826,28 @@ class MCDEngine(CompiledGraph):
         _lib.check(rc, "bmi_forward_mcd_ensemble")
         return S, H, Q, QH
 
-    def _finalize_ensemble_sums(self, Q, QH, t_total):
+    def _finalize_ensemble_sums(self, Q, QH, t_total, t_used=None):
+        """The five ``ens_*`` entries of ``finalize_ensemble`` from the sums Q [2, E, B, C] and QH [E, B]: divided by ``t_total``
+        (bmi_finalize_ensemble), or image b's by t_used[b] when ``t_used`` is given (bmi_finalize_ensemble_per_image)."""
+        check_buffer(Q, (2, None, None, None), torch.float64, self.device, "ensemble buffer Q")
         _, E, B, Cd = Q.shape
-        if Q.shape[0] != 2 or tuple(QH.shape) != (E, B) or Q.dtype != torch.float64 or QH.dtype != torch.float64 or \
-                not Q.is_contiguous() or not QH.is_contiguous():
-            raise ValueError("ensemble buffers must be contiguous float64 Q [2, E, B, C] and QH [E, B]")
-        mv = torch.empty(2, E, B, Cd, dtype=torch.float64, device=Q.device)
-        ent = torch.empty(3, E, B, dtype=torch.float64, device=Q.device)
+        check_buffer(QH, (E, B), torch.float64, self.device, "ensemble entropy buffer QH")
+        if t_used is not None:
+            check_buffer(t_used, (B,), torch.int32, self.device, "t_used")
+        name = "bmi_finalize_ensemble" if t_used is None else "bmi_finalize_ensemble_per_image"
+        count = int(t_total) if t_used is None else t_used.data_ptr()
+        mv = torch.empty(2, E, B, Cd, dtype=torch.float64, device=self.device)
+        ent = torch.empty(3, E, B, dtype=torch.float64, device=self.device)
         with torch.cuda.device(self.device):
-            rc = self.lib.bmi_finalize_ensemble(E, B, Cd, int(t_total), Q[0].data_ptr(), Q[1].data_ptr(), QH.data_ptr(), mv[0].data_ptr(),
-                                                mv[1].data_ptr(), ent[0].data_ptr(), ent[1].data_ptr(), ent[2].data_ptr(),
-                                                self._nonfinite.data_ptr(), self._stream())
-        _lib.check(rc, "bmi_finalize_ensemble")
+            rc = getattr(self.lib, name)(E, B, Cd, count, Q[0].data_ptr(), Q[1].data_ptr(), QH.data_ptr(), mv[0].data_ptr(), mv[1].data_ptr(),
+                                         ent[0].data_ptr(), ent[1].data_ptr(), ent[2].data_ptr(), self._nonfinite.data_ptr(), self._stream())
+        _lib.check(rc, name)
         return dict(ens_mean=mv[0], ens_var=mv[1], ens_pred_entropy=ent[0], ens_exp_entropy=ent[1], ens_mutual_info=ent[2])
 
     def finalize_ensemble_per_image(self, Q, QH, t_used):
         """The five ``ens_*`` entries of ``finalize_ensemble`` with image b's sums divided by its own sample count t_used[b]
         (bmi_finalize_ensemble_per_image; device int32 [B], every entry >= 1): the read-out of ``accumulate_adaptive(ensemble=True)``."""
-        if Q.dim() != 4 or Q.shape[0] != 2:
-            raise ValueError("ensemble buffers must be contiguous float64 Q [2, E, B, C] and QH [E, B]")
-        _, E, B, Cd = Q.shape
-        if tuple(QH.shape) != (E, B) or Q.dtype != torch.float64 or QH.dtype != torch.float64 or not Q.is_contiguous() or \
-                not QH.is_contiguous():
-            raise ValueError("ensemble buffers must be contiguous float64 Q [2, E, B, C] and QH [E, B]")
-        if tuple(t_used.shape) != (B,) or t_used.dtype != torch.int32 or t_used.device != Q.device:
-            raise ValueError("t_used must be int32 [B] on the ensemble buffers' device")
-        mv = torch.empty(2, E, B, Cd, dtype=torch.float64, device=Q.device)
-        ent = torch.empty(3, E, B, dtype=torch.float64, device=Q.device)
-        with torch.cuda.device(self.device):
-            rc = self.lib.bmi_finalize_ensemble_per_image(E, B, Cd, t_used.contiguous().data_ptr(), Q[0].data_ptr(), Q[1].data_ptr(),
-                                                          QH.data_ptr(), mv[0].data_ptr(), mv[1].data_ptr(), ent[0].data_ptr(),
-                                                          ent[1].data_ptr(), ent[2].data_ptr(), self._nonfinite.data_ptr(), self._stream())
-        _lib.check(rc, "bmi_finalize_ensemble_per_image")
-        return dict(ens_mean=mv[0], ens_var=mv[1], ens_pred_entropy=ent[0], ens_exp_entropy=ent[1], ens_mutual_info=ent[2])
-
-    def _check_ensemble_sums(self, B, H, Q, QH):
-        """The buffers an ensemble read-out under a row table needs beside S: H, Q and QH of ``new_ensemble_sums``."""
-        E, Cd = self.n_exits, self.out_dim
-        for buf, shape, what in ((H, (E, B), "entropy buffer H"), (Q, (2, E, B, Cd), "ensemble buffer Q"),
-                                 (QH, (E, B), "ensemble entropy buffer QH")):
-            if buf is None or tuple(buf.shape) != shape or buf.dtype != torch.float64 or not buf.is_contiguous() or buf.device != self.device:
-                raise ValueError(f"{what} must be contiguous float64 {list(shape)} on {self.device}")
+        return self._finalize_ensemble_sums(Q, QH, None, t_used)
 
     def finalize_ensemble(self, S, H, Q, QH, t_total):
         """``finalize_uncertainty``'s dict plus the read-out of the exit ensembles, float64: ``ens_mean`` and ``ens_var`` (ddof 0) [E, B, C],
@@ -874,9 +872,7 @@ class MCDEngine(CompiledGraph):
         set on this engine): the weighted ensembles, bmi_ensemble_moments_weighted.  ``scale`` / ``bias`` (``check_vector_scaling``; not together
         with ``tau``): the members under a vector scaling, bmi_ensemble_moments_vector, with or without ``weights``.
         ``train.uncertainty.decompose_ensemble_logits`` is the host restatement."""
-        if logits.dim() != 4 or logits.dtype != torch.float32 or not logits.is_contiguous() or logits.device != self.device:
-            raise ValueError(f"logits must be contiguous float32 [T, E, B, C] on {self.device}")
-        T, E, B, Cd = logits.shape
+        T, E, B, Cd = check_buffer(logits, (None,) * 4, torch.float32, self.device, "logits [T, E, B, C]").shape
         tau = check_temperature(tau, E)
         W = check_ensemble_weights(weights, E)
         va, vb = check_vector_scaling(scale, bias, E, Cd)
@@ -887,30 +883,21 @@ class MCDEngine(CompiledGraph):
             QH = torch.zeros(E, B, dtype=torch.float64, device=self.device)
         else:
             Q, QH = out
-            if tuple(Q.shape) != (2, E, B, Cd) or tuple(QH.shape) != (E, B) or Q.dtype != torch.float64 or QH.dtype != torch.float64 or \
-                    not Q.is_contiguous() or not QH.is_contiguous() or Q.device != self.device or QH.device != self.device:
-                raise ValueError("out must be contiguous float64 (Q [2, E, B, C], QH [E, B]) on the engine's device")
+            check_buffer(Q, (2, E, B, Cd), torch.float64, self.device, "out[0] (Q)")
+            check_buffer(QH, (E, B), torch.float64, self.device, "out[1] (QH)")
         tau_c = None if tau is None else (C.c_float * E)(*tau)
-        if va is not None:
-            with torch.cuda.device(self.device):
-                a_dev, b_dev = torch.from_numpy(va).to(self.device), torch.from_numpy(vb).to(self.device)      # (freed in stream order behind the launch)
-                w_dev = None if W is None else torch.from_numpy(W).to(self.device)
-                rc = self.lib.bmi_ensemble_moments_vector(logits.data_ptr(), T, E, B, Cd, a_dev.data_ptr(), b_dev.data_ptr(),
-                                                          None if w_dev is None else w_dev.data_ptr(), Q[0].data_ptr(), Q[1].data_ptr(),
-                                                          QH.data_ptr(), self._stream())
-            _lib.check(rc, "bmi_ensemble_moments_vector")
-            r = self._finalize_ensemble_sums(Q, QH, int(t_before) + T)
-            r.update(Q=Q, QH=QH)
-            return r
         with torch.cuda.device(self.device):
-            if W is None:
-                rc = self.lib.bmi_ensemble_moments(logits.data_ptr(), T, E, B, Cd, tau_c, Q[0].data_ptr(), Q[1].data_ptr(), QH.data_ptr(),
-                                                   self._stream())
+            # the device copies stay alive until the launch is queued, and are freed in stream order behind it
+            a_dev, b_dev, w_dev = (None if a is None else torch.from_numpy(a).to(self.device) for a in (va, vb, W))
+            ptr = lambda t: None if t is None else t.data_ptr()
+            if va is not None:
+                name, cal = "bmi_ensemble_moments_vector", (ptr(a_dev), ptr(b_dev), ptr(w_dev))
+            elif W is not None:
+                name, cal = "bmi_ensemble_moments_weighted", (tau_c, ptr(w_dev))
             else:
-                w_dev = torch.from_numpy(W).to(self.device)      # (freed in stream order behind the launch that reads it)
-                rc = self.lib.bmi_ensemble_moments_weighted(logits.data_ptr(), T, E, B, Cd, tau_c, w_dev.data_ptr(), Q[0].data_ptr(),
-                                                            Q[1].data_ptr(), QH.data_ptr(), self._stream())
-        _lib.check(rc, "bmi_ensemble_moments" if W is None else "bmi_ensemble_moments_weighted")
+                name, cal = "bmi_ensemble_moments", (tau_c,)
+            rc = getattr(self.lib, name)(logits.data_ptr(), T, E, B, Cd, *cal, Q[0].data_ptr(), Q[1].data_ptr(), QH.data_ptr(), self._stream())
+        _lib.check(rc, name)
         r = self._finalize_ensemble_sums(Q, QH, int(t_before) + T)
         r.update(Q=Q, QH=QH)
         return r
@@ -956,31 +943,20 @@ class MCDEngine(CompiledGraph):
             raise ValueError(f"early exiting needs all T={T} samples in one chunk (engine planned for {self.chunk_samples})")
         if not 0 <= first_exit < self.n_exits:
             raise ValueError(f"first_exit must be in [0, {self.n_exits})")
-        if tuple(S.shape) != (3, self.n_exits, B, self.out_dim) or S.dtype != torch.float64 or not S.is_contiguous():
-            raise ValueError("moment buffer must be contiguous float64 [3, E, B, C]")
-        if H is not None and (tuple(H.shape) != (self.n_exits, B) or H.dtype != torch.float64 or not H.is_contiguous()):
-            raise ValueError("entropy buffer must be contiguous float64 [E, B]")
         if (Q is None) != (QH is None):
             raise ValueError("the ensemble read-out needs both Q and QH (new_ensemble_sums)")
-        if Q is not None:
-            self._check_ensemble_sums(B, H, Q, QH)
+        self._check_sums(B, S, H, Q, QH, ensemble=Q is not None)
         exit_layer = torch.empty(B, dtype=torch.int32, device=self.device)
         active = (C.c_int32 * self.n_exits)()
         r_c = _lib.ExitRule(_lib.EXIT_RULES[rule], int(bool(ensemble)), float(threshold), first_exit)
-        if Q is not None:
-            scratch, _ = self._ensemble_scratch(B)
-            with torch.cuda.device(self.device):
-                rc = self.lib.bmi_forward_mcd_exit_staged_ensemble(
-                    self.handle, x.data_ptr(), B, T, int(seed) & 0xFFFFFFFFFFFFFFFF, int(cnt0), C.byref(r_c), S[0].data_ptr(), S[1].data_ptr(),
-                    S[2].data_ptr(), H.data_ptr(), Q[0].data_ptr(), Q[1].data_ptr(), QH.data_ptr(), scratch.data_ptr(), scratch.numel(),
-                    exit_layer.data_ptr(), active, self.workspace.data_ptr(), self.workspace_bytes, self._stream())
-            _lib.check(rc, "bmi_forward_mcd_exit_staged_ensemble")
-            return exit_layer, [int(v) for v in active]
+        name = "bmi_forward_mcd_exit_staged" if Q is None else "bmi_forward_mcd_exit_staged_ensemble"
+        scratch = None if Q is None else self._ensemble_scratch()
+        ens = () if Q is None else (Q[0].data_ptr(), Q[1].data_ptr(), QH.data_ptr(), scratch.data_ptr(), scratch.numel())
         with torch.cuda.device(self.device):
-            rc = self.lib.bmi_forward_mcd_exit_staged(self.handle, x.data_ptr(), B, T, int(seed) & 0xFFFFFFFFFFFFFFFF, int(cnt0), C.byref(r_c),
-                                                      S[0].data_ptr(), S[1].data_ptr(), S[2].data_ptr(), None if H is None else H.data_ptr(),
-                                                      exit_layer.data_ptr(), active, self.workspace.data_ptr(), self.workspace_bytes, self._stream())
-        _lib.check(rc, "bmi_forward_mcd_exit_staged")
+            rc = getattr(self.lib, name)(self.handle, x.data_ptr(), B, T, int(seed) & 0xFFFFFFFFFFFFFFFF, int(cnt0), C.byref(r_c), S[0].data_ptr(),
+                                         S[1].data_ptr(), S[2].data_ptr(), None if H is None else H.data_ptr(), *ens, exit_layer.data_ptr(), active,
+                                         self.workspace.data_ptr(), self.workspace_bytes, self._stream())
+        _lib.check(rc, name)
         return exit_layer, [int(v) for v in active]
 
     def predict_early_exit(self, x, T, threshold, seed=0, cnt0=0, first_exit=1, rule="confidence", ensemble=False, uncertainty=False,
@@ -1063,33 +1039,22 @@ class MCDEngine(CompiledGraph):
             test_exit += self.n_exits
         if not 0 <= test_exit < self.n_exits:
             raise ValueError(f"test_exit out of range for {self.n_exits} exits")
-        if tuple(S.shape) != (3, self.n_exits, B, self.out_dim) or S.dtype != torch.float64 or not S.is_contiguous():
-            raise ValueError("moment buffer must be contiguous float64 [3, E, B, C]")
-        if H is not None and (tuple(H.shape) != (self.n_exits, B) or H.dtype != torch.float64 or not H.is_contiguous()):
-            raise ValueError("entropy buffer must be contiguous float64 [E, B]")
-        if ensemble:
-            self._check_ensemble_sums(B, H, Q, QH)
-        elif Q is not None or QH is not None:
+        if not ensemble and (Q is not None or QH is not None):
             raise ValueError("Q / QH are the sums of ensemble=True")
+        self._check_sums(B, S, H, Q, QH, ensemble=ensemble)
         t_used = torch.empty(B, dtype=torch.int32, device=self.device)
         converged = torch.empty(B, dtype=torch.uint8, device=self.device)
         active = (C.c_int32 * (-(-T_max // t_step)))()
-        if ensemble:
-            scratch, _ = self._ensemble_scratch(B)
-            with torch.cuda.device(self.device):
-                rc = self.lib.bmi_forward_mcd_adaptive_ensemble(
-                    self.handle, x.data_ptr(), B, int(image_offset), T_max, t_step, int(seed) & 0xFFFFFFFFFFFFFFFF, int(cnt0),
-                    _lib.STOP_RULES[rule], float(threshold), test_exit, _lib.STOP_ON[stop_on], S[0].data_ptr(), S[1].data_ptr(), S[2].data_ptr(),
-                    H.data_ptr(), Q[0].data_ptr(), Q[1].data_ptr(), QH.data_ptr(), scratch.data_ptr(), scratch.numel(), t_used.data_ptr(),
-                    converged.data_ptr(), active, self.workspace.data_ptr(), self.workspace_bytes, self._stream())
-            _lib.check(rc, "bmi_forward_mcd_adaptive_ensemble")
-            return t_used, converged, [int(v) for v in active]
+        name = "bmi_forward_mcd_adaptive_ensemble" if ensemble else "bmi_forward_mcd_adaptive"
+        scratch = self._ensemble_scratch() if ensemble else None
+        stop = (_lib.STOP_ON[stop_on],) if ensemble else ()
+        ens = (Q[0].data_ptr(), Q[1].data_ptr(), QH.data_ptr(), scratch.data_ptr(), scratch.numel()) if ensemble else ()
         with torch.cuda.device(self.device):
-            rc = self.lib.bmi_forward_mcd_adaptive(self.handle, x.data_ptr(), B, int(image_offset), T_max, t_step, int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                                   int(cnt0), _lib.STOP_RULES[rule], float(threshold), test_exit, S[0].data_ptr(), S[1].data_ptr(),
-                                                   S[2].data_ptr(), None if H is None else H.data_ptr(), t_used.data_ptr(), converged.data_ptr(),
-                                                   active, self.workspace.data_ptr(), self.workspace_bytes, self._stream())
-        _lib.check(rc, "bmi_forward_mcd_adaptive")
+            rc = getattr(self.lib, name)(self.handle, x.data_ptr(), B, int(image_offset), T_max, t_step, int(seed) & 0xFFFFFFFFFFFFFFFF, int(cnt0),
+                                         _lib.STOP_RULES[rule], float(threshold), test_exit, *stop, S[0].data_ptr(), S[1].data_ptr(), S[2].data_ptr(),
+                                         None if H is None else H.data_ptr(), *ens, t_used.data_ptr(), converged.data_ptr(), active,
+                                         self.workspace.data_ptr(), self.workspace_bytes, self._stream())
+        _lib.check(rc, name)
         return t_used, converged, [int(v) for v in active]
 
     def predict_adaptive(self, x, T_max, threshold, rule="sem", t_step=None, test_exit=-1, seed=0, cnt0=0, uncertainty=False,
@@ -1125,18 +1090,15 @@ class MCDEngine(CompiledGraph):
     def finalize_per_image(self, S, t_used, H=None):
         """``finalize`` (and, with H, ``finalize_uncertainty``) with image b's sums divided by its own sample count t_used[b]
         (bmi_finalize_per_image; device int32 [B], every entry >= 1)."""
-        E, B, Cd = S.shape[1], S.shape[2], S.shape[3]
-        if S.dtype != torch.float64 or not S.is_contiguous():
-            raise ValueError("moment buffer must be contiguous float64 [3, E, B, C]")
-        if tuple(t_used.shape) != (B,) or t_used.dtype != torch.int32 or t_used.device != S.device:
-            raise ValueError("t_used must be int32 [B] on the moment buffer's device")
-        if H is not None and (tuple(H.shape) != (E, B) or H.dtype != torch.float64 or not H.is_contiguous()):
-            raise ValueError("entropy buffer must be contiguous float64 [E, B]")
+        _, E, B, Cd = check_buffer(S, (3, None, None, None), torch.float64, self.device, "moment buffer S").shape
+        check_buffer(t_used, (B,), torch.int32, self.device, "t_used")
+        if H is not None:
+            check_buffer(H, (E, B), torch.float64, self.device, "entropy buffer H")
         out = torch.empty_like(S)
         unc = None if H is None else torch.empty(3, E, B, dtype=torch.float64, device=S.device)
         ptr = (lambda i: None) if unc is None else (lambda i: unc[i].data_ptr())
         with torch.cuda.device(self.device):
-            rc = self.lib.bmi_finalize_per_image(E, B, Cd, t_used.contiguous().data_ptr(), S[0].data_ptr(), S[1].data_ptr(), S[2].data_ptr(),
+            rc = self.lib.bmi_finalize_per_image(E, B, Cd, t_used.data_ptr(), S[0].data_ptr(), S[1].data_ptr(), S[2].data_ptr(),
                                                  None if H is None else H.data_ptr(), out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(),
                                                  ptr(0), ptr(1), ptr(2), self._nonfinite.data_ptr(), self._stream())
         _lib.check(rc, "bmi_finalize_per_image")
@@ -1160,8 +1122,8 @@ class MCDEngine(CompiledGraph):
         B = x.shape[0]
         if out is None:
             out = torch.empty(T, self.n_exits, B, self.out_dim, dtype=torch.float32, device=self.device)
-        elif tuple(out.shape) != (T, self.n_exits, B, self.out_dim) or out.dtype != torch.float32 or not out.is_contiguous():
-            raise ValueError("out must be contiguous float32 [T, E, B, C]")
+        else:
+            check_buffer(out, (T, self.n_exits, B, self.out_dim), torch.float32, self.device, "out [T, E, B, C]")
         with torch.cuda.device(self.device):
             rc = self.lib.bmi_forward_mcd_samples(self.handle, x.data_ptr(), B, int(t_begin), int(T), int(seed) & 0xFFFFFFFFFFFFFFFF, int(cnt0),
                                                   int(mask_stride), out.data_ptr(), None, None, None, self.workspace.data_ptr(), self.workspace_bytes,
@@ -1169,30 +1131,32 @@ class MCDEngine(CompiledGraph):
         _lib.check(rc, "bmi_forward_mcd_samples")
         return out
 
+    def _sums_out(self, out, shape, name):
+        """``out`` checked, or zeros when None: the float64 device sums an objective below ADDS into."""
+        if out is None:
+            return torch.zeros(*shape, dtype=torch.float64, device=self.device)
+        return check_buffer(out, shape, torch.float64, self.device, name)
+
+    def _nll_args(self, logits, labels):
+        """What the three objectives below start from: (T, E, B, C) of the checked ``logits`` fp32 [T, E, B, C], and ``labels`` [B] as a
+        device int32 tensor."""
+        T, E, B, Cd = check_buffer(logits, (None,) * 4, torch.float32, self.device, "logits [T, E, B, C]").shape
+        # (labels may come from the host in any integer type: converted first, so of the check below only the shape can fail)
+        labels = check_buffer(labels.to(device=self.device, dtype=torch.int32).contiguous(), (B,), torch.int32, self.device, "labels [B]")
+        return T, E, B, Cd, labels
+
     def nll_grid(self, logits, labels, tau_grid, out=None):
         """The objective of a temperature fit on the device (bmi_nll_temperature_grid): ``logits`` fp32 [T, E, B, C] (``forward_samples``),
         ``labels`` int [B] in [0, C) (the CALLER checks the range: ``train.calibration`` does, on the host), ``tau_grid`` [E, G] candidate
         temperatures.  ADDS, per exit and candidate, sum_b -log mean_t softmax(l_tb / tau)[y_b] into ``out`` (float64 [E, G], zeros when None)
         and returns it: a walk over a loader accumulates.  float64 throughout, log-sum-exp form, the same bits on every run;
         ``train.calibration.nll_grid_numpy`` is its host restatement.  Independent of the temperature set on this engine."""
-        T, E, B, Cd = logits.shape
-        if logits.dtype != torch.float32 or not logits.is_contiguous() or logits.device != self.device:
-            raise ValueError(f"logits must be contiguous float32 [T, E, B, C] on {self.device}")
-        if tuple(labels.shape) != (B,):
-            raise ValueError(f"labels must be [B] = [{B}]")
-        labels = labels.to(device=self.device, dtype=torch.int32).contiguous()
-        tau_grid = torch.as_tensor(tau_grid, dtype=torch.float32).to(self.device).contiguous()
-        if tau_grid.dim() != 2 or tau_grid.shape[0] != E:
-            raise ValueError(f"tau_grid must be [E, G] with E = {E}")
+        T, E, B, Cd, labels = self._nll_args(logits, labels)
+        tau_grid = check_buffer(torch.as_tensor(tau_grid, dtype=torch.float32).to(self.device).contiguous(), (E, None), torch.float32, self.device,
+                                "tau_grid [E, G]")
         G = tau_grid.shape[1]
-        if out is None:
-            out = torch.zeros(E, G, dtype=torch.float64, device=self.device)
-        elif tuple(out.shape) != (E, G) or out.dtype != torch.float64 or not out.is_contiguous() or out.device != self.device:
-            raise ValueError("out must be contiguous float64 [E, G] on the engine's device")
-        need = int(self.lib.bmi_nll_temperature_scratch_bytes(E, B, G))
-        scratch = self.__dict__.get("_nll_scratch")
-        if scratch is None or scratch.numel() < need:
-            scratch = self.__dict__["_nll_scratch"] = torch.empty(need, dtype=torch.uint8, device=self.device)
+        out = self._sums_out(out, (E, G), "out [E, G]")
+        scratch = self._scratch("_nll_scratch", int(self.lib.bmi_nll_temperature_scratch_bytes(E, B, G)))
         with torch.cuda.device(self.device):
             rc = self.lib.bmi_nll_temperature_grid(logits.data_ptr(), T, E, B, Cd, labels.data_ptr(), tau_grid.data_ptr(), G, out.data_ptr(),
                                                    scratch.data_ptr(), scratch.numel(), self._stream())
@@ -1205,28 +1169,18 @@ class MCDEngine(CompiledGraph):
         exit, sum_b -log mean_t softmax(l_tb * scale + bias)[y_b] and its gradients into ``out`` = (nll [E], g_scale [E, C], g_bias [E, C]),
         device float64 (zeros when None), and returns the triple: a walk over a loader accumulates.  float64 throughout, the same bits on
         every run; ``train.calibration.nll_vector_numpy`` is its host restatement.  Independent of what is set on this engine."""
-        T, E, B, Cd = logits.shape
-        if logits.dtype != torch.float32 or not logits.is_contiguous() or logits.device != self.device:
-            raise ValueError(f"logits must be contiguous float32 [T, E, B, C] on {self.device}")
-        if tuple(labels.shape) != (B,):
-            raise ValueError(f"labels must be [B] = [{B}]")
-        labels = labels.to(device=self.device, dtype=torch.int32).contiguous()
-        scale = torch.as_tensor(scale, dtype=torch.float64).to(self.device).contiguous()
-        bias = torch.as_tensor(bias, dtype=torch.float64).to(self.device).contiguous()
-        if tuple(scale.shape) != (E, Cd) or tuple(bias.shape) != (E, Cd):
-            raise ValueError(f"scale and bias must be [E, C] = [{E}, {Cd}]")
+        T, E, B, Cd, labels = self._nll_args(logits, labels)
+        scale = check_buffer(torch.as_tensor(scale, dtype=torch.float64).to(self.device).contiguous(), (E, Cd), torch.float64, self.device, "scale [E, C]")
+        bias = check_buffer(torch.as_tensor(bias, dtype=torch.float64).to(self.device).contiguous(), (E, Cd), torch.float64, self.device, "bias [E, C]")
+        shapes = ((E,), (E, Cd), (E, Cd))
         if out is None:
-            out = (torch.zeros(E, dtype=torch.float64, device=self.device), torch.zeros(E, Cd, dtype=torch.float64, device=self.device),
-                   torch.zeros(E, Cd, dtype=torch.float64, device=self.device))
+            out = tuple(torch.zeros(*shape, dtype=torch.float64, device=self.device) for shape in shapes)
+        elif len(out) != 3:
+            raise ValueError("out must be (nll [E], g_scale [E, C], g_bias [E, C])")
         else:
-            shapes = ((E,), (E, Cd), (E, Cd))
-            if len(out) != 3 or any(tuple(o.shape) != sh or o.dtype != torch.float64 or not o.is_contiguous() or o.device != self.device
-                                    for o, sh in zip(out, shapes)):
-                raise ValueError("out must be contiguous float64 (nll [E], g_scale [E, C], g_bias [E, C]) on the engine's device")
-        need = int(self.lib.bmi_nll_vector_scratch_bytes(E, B, Cd))
-        scratch = self.__dict__.get("_nll_scratch")
-        if scratch is None or scratch.numel() < need:
-            scratch = self.__dict__["_nll_scratch"] = torch.empty(need, dtype=torch.uint8, device=self.device)
+            for o, shape, name in zip(out, shapes, ("out[0] (nll [E])", "out[1] (g_scale [E, C])", "out[2] (g_bias [E, C])")):
+                check_buffer(o, shape, torch.float64, self.device, name)
+        scratch = self._scratch("_nll_scratch", int(self.lib.bmi_nll_vector_scratch_bytes(E, B, Cd)))
         with torch.cuda.device(self.device):
             rc = self.lib.bmi_nll_vector_scaling_grad(logits.data_ptr(), T, E, B, Cd, labels.data_ptr(), scale.data_ptr(), bias.data_ptr(),
                                                       out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), scratch.data_ptr(),
@@ -1242,27 +1196,16 @@ class MCDEngine(CompiledGraph):
         zeros when None) and returns it.  One index is a coordinate step, every index one shared temperature, None with G = 1 evaluates
         ``tau``.  float64 throughout, the same bits on every run; ``train.calibration.ensemble_nll_grid_numpy`` is its host restatement.
         Independent of the temperature set on this engine."""
-        T, E, B, Cd = logits.shape
-        if logits.dtype != torch.float32 or not logits.is_contiguous() or logits.device != self.device:
-            raise ValueError(f"logits must be contiguous float32 [T, E, B, C] on {self.device}")
-        if tuple(labels.shape) != (B,):
-            raise ValueError(f"labels must be [B] = [{B}]")
-        labels = labels.to(device=self.device, dtype=torch.int32).contiguous()
+        T, E, B, Cd, labels = self._nll_args(logits, labels)
         tau = check_temperature(1.0 if tau is None else tau, E)
         mask = vary_mask(vary, E)
         tau = torch.tensor(tau, dtype=torch.float32).to(self.device)
-        cand = torch.as_tensor(cand, dtype=torch.float32).to(self.device).contiguous()
-        if cand.dim() != 1 or cand.numel() < 1:
+        cand = check_buffer(torch.as_tensor(cand, dtype=torch.float32).to(self.device).contiguous(), (None,), torch.float32, self.device, "cand [G]")
+        if cand.numel() < 1:
             raise ValueError("cand must be [G], G >= 1")
         G = cand.numel()
-        if out is None:
-            out = torch.zeros(E, G, dtype=torch.float64, device=self.device)
-        elif tuple(out.shape) != (E, G) or out.dtype != torch.float64 or not out.is_contiguous() or out.device != self.device:
-            raise ValueError("out must be contiguous float64 [E, G] on the engine's device")
-        need = int(self.lib.bmi_nll_ensemble_temperature_scratch_bytes(E, B, G))
-        scratch = self.__dict__.get("_nll_scratch")
-        if scratch is None or scratch.numel() < need:
-            scratch = self.__dict__["_nll_scratch"] = torch.empty(need, dtype=torch.uint8, device=self.device)
+        out = self._sums_out(out, (E, G), "out [E, G]")
+        scratch = self._scratch("_nll_scratch", int(self.lib.bmi_nll_ensemble_temperature_scratch_bytes(E, B, G)))
         with torch.cuda.device(self.device):
             rc = self.lib.bmi_nll_ensemble_temperature_grid(logits.data_ptr(), T, E, B, Cd, labels.data_ptr(), tau.data_ptr(), mask, cand.data_ptr(),
                                                             G, out.data_ptr(), scratch.data_ptr(), scratch.numel(), self._stream())

@@ -282,3 +282,28 @@ def test_forward_entry_points_check_arguments_before_any_launch():
         (exit_(nbytes=small), -12),
     ]
     assert [rc for rc, _ in rows] == [want for _, want in rows]
+
+
+def test_check_buffer_rejects_what_the_c_abi_must_not_see():
+    """``engine.check_buffer`` is what every MCDEngine method puts in front of a caller's buffer: it passes the tensor it was asked for and
+    raises ValueError, naming the buffer, for another device, dtype, layout or shape (None in the shape: any extent)."""
+    from bayesnn_fpga_amd.engine import check_buffer
+    cpu, meta = torch.device("cpu"), torch.device("meta")
+    S = torch.zeros(3, 4, 8, 10, dtype=torch.float64)
+    assert check_buffer(S, (3, 4, 8, 10), torch.float64, cpu, "S") is S
+    assert check_buffer(S, (3, None, None, None), torch.float64, cpu, "S") is S
+    on_meta = torch.empty(3, 4, 8, 10, dtype=torch.float64, device=meta)
+    assert check_buffer(on_meta, (3, 4, 8, 10), torch.float64, meta, "S") is on_meta
+    rejected = {
+        "wrong device": (on_meta, (3, 4, 8, 10), torch.float64, cpu),
+        "wrong device (the other way)": (S, (3, 4, 8, 10), torch.float64, meta),
+        "wrong dtype": (S.float(), (3, 4, 8, 10), torch.float64, cpu),
+        "not contiguous": (torch.zeros(3, 4, 10, 8, dtype=torch.float64).transpose(2, 3), (3, 4, 8, 10), torch.float64, cpu),
+        "wrong extent": (S, (3, 4, 9, 10), torch.float64, cpu),
+        "wrong rank": (S, (3, 4, 80), torch.float64, cpu),
+        "wrong rank under wildcards": (S[0], (None,) * 4, torch.float64, cpu),
+        "not a tensor": (None, (3, 4, 8, 10), torch.float64, cpu),
+    }
+    for what, (t, shape, dtype, device) in rejected.items():
+        with pytest.raises(ValueError, match="buffer S"):       # (a case that is accepted: `what` names it in the traceback)
+            check_buffer(t, shape, dtype, device, "buffer S")
