@@ -15,6 +15,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <vector>
 
@@ -294,6 +295,31 @@ int xcd_split_for(int n_ctiles, size_t weight_bytes) {
     return cs;
 }
 
+// Every tensor an op touches, with its role: f(id, role), once per operand (a tensor the op touches in two roles comes twice).  This is the
+// one place that lists the operand roles; the graph passes and the plans below filter on them.  in2 and residual are a CONV's: the other
+// kinds do not read the fields (add_conv refuses a STEM's residual; nothing validates a STEM's in2).  A HEAD's `out` is an exit index,
+// not a tensor, and is not reported.
+enum TensorRole {
+    ROLE_IN = 1, ROLE_IN2 = 2, ROLE_RESIDUAL = 4, ROLE_BITS = 8, ROLE_OUT = 16, ROLE_PAIR_OUT = 32, ROLE_SEAM_OUT = 64,
+    ROLE_READS = ROLE_IN | ROLE_IN2 | ROLE_RESIDUAL | ROLE_BITS
+};
+template <class F> void for_each_tensor(const OpInfo& op, F&& f) {
+    const bmi_op_desc& d = op.d;
+    f(d.in, ROLE_IN);
+    if (d.kind == BMI_OP_CONV && d.in2 >= 0) f(d.in2, ROLE_IN2);
+    if (d.kind == BMI_OP_CONV && d.residual >= 0) f(d.residual, ROLE_RESIDUAL);
+    if (op.bits_tensor >= 0) f(op.bits_tensor, ROLE_BITS);
+    if (d.kind != BMI_OP_HEAD) f(d.out, ROLE_OUT);
+    if (op.has_pair) f(op.pair_d.out, ROLE_PAIR_OUT);
+    if (op.has_seam) f(op.seam_d.out, ROLE_SEAM_OUT);
+}
+// The roles (ORed) in which op touches tensor id, 0 if it does not; it reads the tensor where roles_of(op, id) & ROLE_READS
+int roles_of(const OpInfo& op, int id) {
+    int r = 0;
+    for_each_tensor(op, [&](int t, int role) { if (t == id) r |= role; });
+    return r;
+}
+
 // Staged early exit (bmi_forward_mcd_exit_staged).  The stage of an op is the smallest exit index of any head downstream of its outputs,
 // transitively; a tensor no head reads counts as the last exit's.  If op A feeds op B, every head downstream of B is also downstream of
 // A, so stage(A) <= stage(B): a stable sort by stage keeps the engine's topological order.  A pair- or seam-fused op takes the smaller
@@ -335,10 +361,7 @@ void plan_exit_stages(bmi_engine_s* h) {
             if (op.has_pair) st = std::min(st, tmin[op.pair_d.out]);
             if (op.has_seam) st = std::min(st, tmin[op.seam_d.out]);
             op.xstage = st;
-            auto feed = [&](int id) { if (id >= 0) tmin[id] = std::min(tmin[id], st); };
-            feed(d.in);
-            if (d.kind == BMI_OP_CONV) { feed(d.residual); feed(d.in2); }
-            feed(op.bits_tensor);
+            for_each_tensor(op, [&](int id, int role) { if (role & ROLE_READS) tmin[id] = std::min(tmin[id], st); });
         }
     // The suffix tensors share workspace ranges by live range in the engine's order: per first_exit, the staged order must keep
     // every two tensors that share bytes live at disjoint times (where the engine's order does)
@@ -349,21 +372,12 @@ void plan_exit_stages(bmi_engine_s* h) {
         for (int k = 0; k < n; ++k) order[k] = k;
         std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return op_stage(h->suffix[a], fe) < op_stage(h->suffix[b], fe); });
         std::vector<int> first(nt, -1), last(nt, -1);
-        for (int k = 0; k < n; ++k) {
-            const OpInfo& op = h->suffix[order[k]];
-            const bmi_op_desc& d = op.d;
-            auto touch = [&](int id) {
-                if (id < 0 || !h->tensors[id].stoch) return;
+        for (int k = 0; k < n; ++k)
+            for_each_tensor(h->suffix[order[k]], [&](int id, int) {
+                if (!h->tensors[id].stoch) return;
                 if (first[id] < 0) first[id] = k;
                 last[id] = k;
-            };
-            touch(d.in);
-            if (d.kind == BMI_OP_CONV) { touch(d.in2); touch(d.residual); }
-            touch(op.bits_tensor);
-            if (d.kind != BMI_OP_HEAD) touch(d.out);
-            if (op.has_pair) touch(op.pair_d.out);
-            if (op.has_seam) touch(op.seam_d.out);
-        }
+            });
         for (int id = 0; id < nt; ++id)
             if (h->tensors[id].lazy_bits >= 0) { first[h->tensors[id].lazy_bits] = first[id]; last[h->tensors[id].lazy_bits] = last[id]; }
         bool ok = true;
@@ -378,6 +392,545 @@ void plan_exit_stages(bmi_engine_s* h) {
         h->staged_ok[fe] = ok;
     }
 }
+
+namespace {
+
+// ---- bmi_create: the descriptor's ops, one at a time, then the graph passes in the order bmi_create calls them ----------------------------
+
+// A validated op goes to the suffix (per sample) or to the once-per-batch prefix, its MACs to that side's count
+void place_op(bmi_engine_s* e, const OpInfo& op) {
+    (op.stoch ? e->suffix : e->prefix).push_back(op);
+    (op.stoch ? e->suffix_macs : e->prefix_macs) += op.macs;
+}
+
+// The tensor an op writes: one of the descriptor's (not the network input), written by no earlier op
+bool fresh_out(const std::vector<char>& written, int id) { return id > 0 && id < (int)written.size() && !written[id]; }
+
+int add_conv(bmi_engine_s* e, std::vector<char>& written, OpInfo op, const TensorInfo& tin) {
+    const bmi_op_desc& d = op.d;
+    auto tensor_ok = [&](int id) { return id >= 0 && id < (int)written.size(); };
+    bool in_st = tin.stoch;
+    if (!fresh_out(written, d.out) || !d.weight || d.ksize < 1 || d.stride < 1 || d.pad < 0) return BMI_ERR_INVALID;
+    if ((d.kind == BMI_OP_STEM) != (d.in == 0)) return BMI_ERR_INVALID;
+    if (d.site_pos != BMI_SITE_POS_OUTER && d.site_pos != BMI_SITE_POS_INNER) return BMI_ERR_INVALID;
+    const bool inner = d.site_pos == BMI_SITE_POS_INNER && d.site.kind != BMI_SITE_NONE;
+    if (inner && (d.in2 >= 0 || d.site.kind == BMI_SITE_MASKSEMBLE)) return BMI_ERR_UNSUPPORTED;
+    const TensorInfo to = e->tensors[d.out];  // by value: the split below grows the vector
+    op.ho = (tin.h + 2 * d.pad - d.ksize) / d.stride + 1;
+    op.wo = (tin.w + 2 * d.pad - d.ksize) / d.stride + 1;
+    op.cout = to.c;
+    if (op.ho != to.h || op.wo != to.w) return BMI_ERR_INVALID;
+    if (d.kind == BMI_OP_CONV && !e->f32 && (tin.c % 64 != 0 || to.c % 64 != 0)) return BMI_ERR_UNSUPPORTED;
+    // the engines with fp32 activations: one generic kernel each (conv_exact / conv_split), 32-deep K-steps, 64-channel tiles
+    if (d.kind == BMI_OP_CONV && e->f32 && (tin.c % 32 != 0 || to.c % 64 != 0)) return BMI_ERR_UNSUPPORTED;
+    if (d.kind == BMI_OP_STEM && (to.c % 8 != 0 || to.c * d.ksize * d.ksize * tin.c > 4096 || d.residual >= 0)) return BMI_ERR_UNSUPPORTED;
+    if (d.residual >= 0) {
+        if (!tensor_ok(d.residual) || !written[d.residual] || d.residual == 0) return BMI_ERR_INVALID;
+        const TensorInfo& tr = e->tensors[d.residual];
+        if (tr.h != to.h || tr.w != to.w || tr.c != to.c) return BMI_ERR_INVALID;
+        in_st = in_st || tr.stoch;
+    }
+    int64_t macs = (int64_t)op.ho * op.wo * op.cout * d.ksize * d.ksize * tin.c;
+    if (d.kind == BMI_OP_CONV && d.in2 >= 0 && e->f32 && !e->split) return BMI_ERR_UNSUPPORTED;   // a speed feature (BN scales folded into the weights): never in the exact engine
+    if (d.kind == BMI_OP_CONV && d.in2 >= 0) {
+        if (!tensor_ok(d.in2) || !written[d.in2] || d.in2 == 0 || !d.weight2 || (d.scale && !e->split)) return BMI_ERR_INVALID;   // (split engines: the host's per-channel power-of-two lift comes back as `scale`)
+        const TensorInfo& t2 = e->tensors[d.in2];
+        if (t2.h % op.ho != 0 || t2.h / op.ho != t2.w / op.wo || t2.w % op.wo != 0) return BMI_ERR_UNSUPPORTED;
+        // fp16 / bf16: conv3x3_patch / conv3x3_pw carry the shortcut; the split engines: extra K-steps of conv_split (any conv geometry)
+        if (e->split ? t2.c % 32 != 0
+                     : (d.ksize != 3 || d.stride != 1 || d.pad != 1 || t2.c % 64 != 0 || !conv_takes_patch_kernel(3, 1, 1, tin.c, op.cout, op.ho, op.wo)))
+            return BMI_ERR_UNSUPPORTED;
+        in_st = in_st || t2.stoch;
+        macs += (int64_t)op.ho * op.wo * op.cout * t2.c;
+    }
+    op.macs = macs;
+    if (!in_st && d.site.kind != BMI_SITE_NONE) {
+        // deterministic conv feeding a site: keep the conv in the once-per-batch prefix
+        // and apply the site while expanding to the folded sample batch.
+        if (inner && d.residual >= 0) return BMI_ERR_UNSUPPORTED;
+        TensorInfo tmp = to;
+        tmp.stoch = false;
+        e->tensors.push_back(tmp);
+        const int tmp_id = (int)e->tensors.size() - 1;
+        OpInfo conv = op;
+        conv.d.out = tmp_id;
+        conv.d.site.kind = BMI_SITE_NONE;
+        conv.d.site_pos = BMI_SITE_POS_OUTER;
+        conv.d.bias_post = nullptr;
+        if (inner) conv.d.relu = 0;   // the prefix keeps conv*scale+bias; mask, BN shift and ReLU follow in the MASK op
+        conv.stoch = false;
+        place_op(e, conv);
+        OpInfo m;
+        std::memset(&m.d, 0, sizeof(m.d));
+        m.d.kind = BMI_OP_MASK;
+        m.d.in = tmp_id;
+        m.d.out = d.out;
+        m.d.residual = -1;
+        m.d.in2 = -1;
+        m.d.site = d.site;
+        if (inner) { m.d.bias_post = d.bias_post; m.d.relu = d.relu; m.d.site_pos = BMI_SITE_POS_INNER; }
+        m.stoch = true;
+        m.ho = to.h; m.wo = to.w; m.cout = to.c;
+        place_op(e, m);
+        e->tensors[d.out].stoch = true;
+    } else {
+        op.stoch = in_st || d.site.kind != BMI_SITE_NONE;
+        e->tensors[d.out].stoch = op.stoch;
+        place_op(e, op);
+    }
+    written[d.out] = 1;
+    return BMI_OK;
+}
+
+int add_mask(bmi_engine_s* e, std::vector<char>& written, OpInfo op, const TensorInfo& tin) {
+    const bmi_op_desc& d = op.d;
+    if (!fresh_out(written, d.out) || d.in == 0 || d.site.kind == BMI_SITE_NONE || d.site_pos != BMI_SITE_POS_OUTER) return BMI_ERR_INVALID;
+    op.d.bias_post = nullptr;
+    op.d.relu = 0;
+    const TensorInfo& to = e->tensors[d.out];
+    if (to.h != tin.h || to.w != tin.w || to.c != tin.c) return BMI_ERR_INVALID;
+    if (tin.c % 8 != 0) return BMI_ERR_UNSUPPORTED;
+    op.stoch = true;
+    op.ho = to.h; op.wo = to.w; op.cout = to.c;
+    e->tensors[d.out].stoch = true;
+    place_op(e, op);
+    written[d.out] = 1;
+    return BMI_OK;
+}
+
+int add_maxpool(bmi_engine_s* e, std::vector<char>& written, OpInfo op, const TensorInfo& tin) {
+    const bmi_op_desc& d = op.d;
+    if (!fresh_out(written, d.out) || d.in == 0) return BMI_ERR_INVALID;
+    const TensorInfo& to = e->tensors[d.out];
+    if (to.h * 2 != tin.h || to.w * 2 != tin.w || to.c != tin.c) return BMI_ERR_INVALID;
+    if (tin.c % 8 != 0) return BMI_ERR_UNSUPPORTED;
+    op.stoch = tin.stoch;
+    op.ho = to.h; op.wo = to.w; op.cout = to.c;
+    e->tensors[d.out].stoch = tin.stoch;
+    place_op(e, op);
+    written[d.out] = 1;
+    return BMI_OK;
+}
+
+int add_dense(bmi_engine_s* e, std::vector<char>& written, OpInfo op, const TensorInfo& tin) {
+    const bmi_op_desc& d = op.d;
+    if (!fresh_out(written, d.out) || d.in == 0 || !d.weight || !d.bias || d.site_pos != BMI_SITE_POS_OUTER) return BMI_ERR_INVALID;
+    const TensorInfo& to = e->tensors[d.out];
+    if (tin.h != 1 || tin.w != 1 || to.h != 1 || to.w != 1) return BMI_ERR_INVALID;
+    if (tin.c % 32 != 0 || to.c % 64 != 0) return BMI_ERR_UNSUPPORTED;
+    op.d.residual = -1; op.d.in2 = -1;
+    // a site makes the layer per-sample even on a deterministic input (the layer is tiny: no conv + MASK split)
+    op.stoch = tin.stoch || d.site.kind != BMI_SITE_NONE;
+    op.ho = 1; op.wo = 1; op.cout = to.c;
+    e->tensors[d.out].stoch = op.stoch;
+    e->tensors[d.out].f32 = true;
+    e->tensors[d.out].dense_out = true;
+    op.macs = (int64_t)tin.c * to.c;
+    place_op(e, op);
+    written[d.out] = 1;
+    return BMI_OK;
+}
+
+int add_head(bmi_engine_s* e, std::vector<char>& exit_seen, OpInfo op, const TensorInfo& tin) {
+    const bmi_op_desc& d = op.d;
+    if (d.in == 0 || d.out < 0 || d.out >= e->n_exits || exit_seen[d.out] || !d.weight || !d.bias) return BMI_ERR_INVALID;
+    if (tin.c % 32 != 0) return BMI_ERR_UNSUPPORTED;   // head_fused splits K over 4 waves x 2 lane halves x float4
+    if (d.site_pos == BMI_SITE_POS_INNER && d.site.kind != BMI_SITE_NONE && d.site.kind != BMI_SITE_ELEMENTWISE)
+        return BMI_ERR_UNSUPPORTED;   // dropout on the logits is elementwise (F.dropout after nn.Linear)
+    exit_seen[d.out] = 1;
+    op.stoch = true;  // heads always run per sample (they emit per-sample softmax)
+    op.cout = e->out_dim;
+    op.macs = (int64_t)tin.c * e->out_dim;
+    place_op(e, op);
+    return BMI_OK;
+}
+
+// One op of the descriptor: validation, ho / wo / cout / macs, and its place in the prefix or the suffix (a deterministic conv that
+// carries a site becomes a prefix conv and a suffix MASK op: add_conv)
+int add_op(bmi_engine_s* e, std::vector<char>& written, std::vector<char>& exit_seen, const bmi_op_desc& desc_op) {
+    OpInfo op;
+    op.d = desc_op;
+    const bmi_op_desc& d = op.d;
+    if (d.in < 0 || d.in >= (int)written.size() || !written[d.in] || !site_ok(d.site)) return BMI_ERR_INVALID;
+    const TensorInfo tin = e->tensors[d.in];
+    if (tin.f32 && !e->f32 && d.kind != BMI_OP_DENSE && d.kind != BMI_OP_HEAD) return BMI_ERR_UNSUPPORTED;
+    switch (d.kind) {
+        case BMI_OP_STEM:
+        case BMI_OP_CONV: return add_conv(e, written, op, tin);
+        case BMI_OP_MASK: return add_mask(e, written, op, tin);
+        case BMI_OP_MAXPOOL: return add_maxpool(e, written, op, tin);
+        case BMI_OP_DENSE: return add_dense(e, written, op, tin);
+        case BMI_OP_HEAD: return add_head(e, exit_seen, op, tin);
+        default: return BMI_ERR_INVALID;
+    }
+}
+
+// The descriptor into the handle: the dtype, the tensors, every op through add_op, every exit with its head
+int read_graph(bmi_engine_s* e, const bmi_model_desc* desc) {
+    e->n_exits = desc->n_exits;
+    e->out_dim = desc->out_dim;
+    e->bf16 = desc->dtype == BMI_DTYPE_BF16;
+    e->split = desc->dtype == BMI_DTYPE_F16X2 ? 1 : (desc->dtype == BMI_DTYPE_BF16X3 ? 2 : 0);
+    e->f32 = desc->dtype == BMI_DTYPE_F32 || e->split;
+    e->dtype = desc->dtype;
+    e->tensors.resize(desc->n_tensors);
+    for (int i = 0; i < desc->n_tensors; ++i) {
+        const bmi_tensor_desc& t = desc->tensors[i];
+        if (t.h < 1 || t.w < 1 || t.c < 1) return BMI_ERR_INVALID;
+        e->tensors[i].h = t.h; e->tensors[i].w = t.w; e->tensors[i].c = t.c;
+        e->tensors[i].f32 = e->f32 && i > 0;   // the exact engine keeps every activation in fp32
+    }
+    std::vector<char> written(desc->n_tensors, 0);
+    written[0] = 1;  // network input
+    std::vector<char> exit_seen(desc->n_exits, 0);
+    for (int k = 0; k < desc->n_ops; ++k) {
+        const int rc = add_op(e, written, exit_seen, desc->ops[k]);
+        if (rc != BMI_OK) return rc;
+    }
+    for (int x = 0; x < desc->n_exits; ++x)
+        if (!exit_seen[x]) return BMI_ERR_INVALID;
+    return BMI_OK;
+}
+
+// Input-side dropout: an elementwise site that expands a deterministic tensor and is consumed only
+// as the input of convs that stage their input through registers (conv_igemm) is not materialised:
+// the MASK op emits keep bits (16x fewer bytes), the consumers read the deterministic tensor (L2 /
+// Infinity Cache resident, B images) and zero the dropped elements while staging; 1/(1-p) is
+// folded into their BN scale.  Same-box A/B on the headline config: HBM traffic of the site drops
+// 16x but the step time is unchanged (-0.47 ms in the mask kernel, +0.5 ms in the three consumers),
+// so it is OFF by default; BMI_MASK_BITS=1 enables it (covered by the parity tests).
+void rewrite_mask_bits(bmi_engine_s* e) {
+    const char* env = std::getenv("BMI_MASK_BITS");
+    const bool enable = env && std::atoi(env) == 1 && !e->f32;
+    for (size_t mi = 0; enable && mi < e->suffix.size(); ++mi) {
+        OpInfo& m = e->suffix[mi];
+        if (m.d.kind != BMI_OP_MASK || m.d.site.kind != BMI_SITE_ELEMENTWISE || e->tensors[m.d.in].stoch) continue;
+        if (m.d.site_pos == BMI_SITE_POS_INNER) continue;   // carries a BN shift / ReLU: must be materialised
+        if (m.d.site.p >= 1.f || e->tensors[m.d.in].c % 8 != 0) continue;
+        bool ok = true;
+        int uses = 0;
+        for (const OpInfo& c : e->suffix) {
+            if (&c == &m) continue;
+            const int as = roles_of(c, m.d.out) & (ROLE_IN | ROLE_RESIDUAL);      // (this pass has only ever looked at these two roles)
+            if (!as) continue;
+            ++uses;
+            const TensorInfo& ti = e->tensors[m.d.out];
+            if ((as & ROLE_RESIDUAL) || c.d.kind != BMI_OP_CONV ||
+                conv_takes_patch_kernel(c.d.ksize, c.d.stride, c.d.pad, ti.c, c.cout, c.ho, c.wo))
+                ok = false;
+        }
+        if (!ok || uses == 0) continue;
+        m.d.kind = OP_MASKBITS;
+        e->tensors[m.d.out].bits = true;
+        for (OpInfo& c : e->suffix)
+            if (&c != &m && c.d.kind == BMI_OP_CONV && c.d.in == m.d.out) {
+                c.bits_tensor = m.d.out;
+                c.d.in = m.d.in;
+                c.out_mul = bmi_drop_scale(m.d.site.p);
+            }
+    }
+}
+
+// Pair fusion: two suffix convs that read the same tensor with the same geometry and a plain BN(+ReLU) epilogue
+// (layerN.0.conv1 and the first conv of the exit head in front of it, resnet18.py:306/:318/:329 vs :280-299)
+// run as ONE conv_igemm_wide launch: the input tile is fetched once for both and a 128-channel conv still fills
+// the kernel's 256-channel tile.  The later conv moves up to the earlier one's position (it depends on nothing
+// in between).  BMI_CONV_PAIR=0 keeps them separate (A/B, tests).
+void fuse_pairs(bmi_engine_s* e) {
+    const char* env = std::getenv("BMI_CONV_PAIR");
+    const bool enable = (!env || std::atoi(env) != 0) && (!e->f32 || e->split);      // (the exact engine's kernel has no pair mode)
+    auto plain = [&](const OpInfo& c) {
+        return c.d.kind == BMI_OP_CONV && !c.has_pair && c.d.residual < 0 && c.d.in2 < 0 && c.d.site.kind == BMI_SITE_NONE &&
+               c.bits_tensor < 0 && c.out_mul == 1.f && c.d.scale && c.d.bias;
+    };
+    auto merge = [&](std::vector<OpInfo>& ops, bool prefix) {
+        for (size_t i = 0; i < ops.size(); ++i) {
+            if (!plain(ops[i])) continue;
+            const OpInfo A = ops[i];
+            const TensorInfo& ti = e->tensors[A.d.in];
+            // (prefix: a conv with 256+ input channels may get a split-K launch from bmi_plan on a small batch — VGG's exit convs, 37 -> 22 us —
+            //  which a pair launch does not have: those stay single.  Measured: VGG-11 on f16x2 15.0 -> 14.4 M with every prefix pair merged)
+            if (prefix && ti.c >= 256) continue;
+            if (conv_takes_patch_kernel(A.d.ksize, A.d.stride, A.d.pad, ti.c, A.cout, A.ho, A.wo)) continue;
+            for (size_t j = i + 1; j < ops.size(); ++j) {
+                const OpInfo& Bo = ops[j];
+                if (!plain(Bo) || Bo.d.in != A.d.in || Bo.d.ksize != A.d.ksize || Bo.d.stride != A.d.stride ||
+                    Bo.d.pad != A.d.pad || Bo.d.relu != A.d.relu)
+                    continue;
+                if (A.cout % 128 != 0 || !conv_takes_wide_kernel(ti.c, A.cout + Bo.cout)) continue;
+                if (e->split && Bo.cout % 128 != 0) continue;
+                ops[i].has_pair = true;
+                ops[i].pair_d = Bo.d;
+                ops[i].pair_cout = Bo.cout;
+                ops[i].macs += Bo.macs;
+                ops.erase(ops.begin() + (long)j);
+                break;
+            }
+        }
+    };
+    if (enable) merge(e->suffix, false);
+    // "pair_prefix" (round 6): the same for the once-per-batch prefix — with exit-only dropout the whole network is prefix and the pairs are
+    // there: the paper's configuration 3.60-3.63 M -> 3.70-3.77 M MCD-samples/s, same box (profiles/experiments/r6_exit_only_variants.txt).
+    if (enable && opt_pair_prefix() && !e->f32) merge(e->prefix, true);
+}
+
+// Seam fusion (Bottleneck nets): conv3 + BN + residual + ReLU of block k followed at once by conv1 + BN + ReLU of block k+1 on its output:
+// one conv1x1_seam launch produces both tensors and the wide one is not read back (conv1x1_seam.hip).  Decided per launch in run_conv.
+void fuse_seams(bmi_engine_s* e) {
+    for (size_t i = 0; !e->f32 && opt_conv_seam() && i + 1 < e->suffix.size(); ++i) {
+        OpInfo& A = e->suffix[i];
+        const OpInfo& Bo = e->suffix[i + 1];
+        auto one = [&](const OpInfo& c) {
+            return c.d.kind == BMI_OP_CONV && c.stoch && !c.has_pair && c.d.in2 < 0 && c.d.site.kind == BMI_SITE_NONE && c.bits_tensor < 0 && c.out_mul == 1.f &&
+                   c.d.ksize == 1 && c.d.stride == 1 && c.d.pad == 0 && c.d.scale && c.d.bias;
+        };
+        if (!one(A) || !one(Bo) || A.d.residual < 0 || !A.d.relu || Bo.d.residual >= 0 || Bo.d.in != A.d.out) continue;
+        if (!e->tensors[A.d.in].stoch || !e->tensors[A.d.residual].stoch) continue;
+        if (!conv_takes_seam_kernel(e->tensors[A.d.in].c, A.cout, Bo.cout)) continue;
+        A.has_seam = true;
+        A.seam_d = Bo.d;
+        A.seam_cout = Bo.cout;
+        A.macs += Bo.macs;
+        e->suffix.erase(e->suffix.begin() + (long)i + 1);
+    }
+}
+
+// The reads of tensor id over the whole graph, one per role (an op that reads it as input and residual counts twice); *heads: the
+// HEAD ops among the readers
+int count_readers(const bmi_engine_s* e, int id, int* heads) {
+    int n = 0;
+    *heads = 0;
+    for (const std::vector<OpInfo>* ops : {&e->prefix, &e->suffix})
+        for (const OpInfo& c : *ops) {
+            for_each_tensor(c, [&](int t, int role) {
+                if (t != id || !(role & ROLE_READS)) return;
+                ++n;
+                if (c.d.kind == BMI_OP_HEAD) ++*heads;
+            });
+            // Left as it was: this count has always taken a STEM for a CONV.  A STEM's residual is refused by add_conv, but nothing
+            // validates its in2 (no kernel reads it), so for_each_tensor does not report it and the count still adds it here.
+            if (c.d.kind == BMI_OP_STEM && c.d.in2 == id) ++n;
+        }
+    return n;
+}
+
+// ReLU + global average pool fused into the producing conv: a plain 3x3 stride-2 conv whose 4x4 output map feeds ONE exit head and
+// nothing else (ex1conv3 / ex2conv2 / ex3conv1 of the ResNets: relu -> avg_pool2d(4) -> Linear, resnet18.py:309-314, :320-325,
+// :331-335) may write fp32 means [row][Cout] instead of the map when conv3x3_s2 takes the launch (decided per launch: run_conv).
+void mark_pooled_tails(bmi_engine_s* e) {
+    for (std::vector<OpInfo>* ops : {&e->prefix, &e->suffix})
+        for (OpInfo& c : *ops) {
+            if (c.d.kind != BMI_OP_CONV || e->f32) continue;
+            auto eligible = [&](const bmi_op_desc& d, int cout) {
+                const TensorInfo& to = e->tensors[d.out];
+                int heads = 0;
+                return d.ksize == 3 && d.stride == 2 && d.pad == 1 && to.h == 4 && to.w == 4 && d.residual < 0 && d.in2 < 0 &&
+                       d.site.kind == BMI_SITE_NONE && cout % 128 == 0 && count_readers(e, d.out, &heads) == 1 && heads == 1;
+            };
+            // ... and the last conv of the net (layer4[1].conv2: stride 1, with its residual) in front of the final head: conv3x3_pw's
+            // lite epilogue does the same on its registers
+            auto eligible_pw = [&](const bmi_op_desc& d, int cout) {
+                const TensorInfo& to = e->tensors[d.out];
+                int heads = 0;
+                return d.ksize == 3 && d.stride == 1 && d.pad == 1 && to.h == 4 && to.w == 4 && d.in2 < 0 && d.relu &&
+                       (d.site.kind == BMI_SITE_NONE || d.site_pos != BMI_SITE_POS_INNER) && cout % 256 == 0 && !c.has_pair &&
+                       count_readers(e, d.out, &heads) == 1 && heads == 1;
+            };
+            c.pool_pw_ok = c.bits_tensor < 0 && eligible_pw(c.d, c.cout);
+            c.pool_ok = c.bits_tensor < 0 && eligible(c.d, c.cout);
+            c.pair_pool_ok = c.has_pair && eligible(c.pair_d, c.pair_cout);
+        }
+}
+
+// live ranges of the stochastic tensors over the suffix
+void compute_live_ranges(bmi_engine_s* e) {
+    for (int k = 0; k < (int)e->suffix.size(); ++k)
+        for_each_tensor(e->suffix[k], [&](int id, int) {
+            TensorInfo& t = e->tensors[id];
+            if (!t.stoch) return;
+            if (t.first < 0) t.first = k;
+            t.last = k;
+        });
+}
+
+// Lazy sites.  The first elementwise site of a "block"-dropout ResNet expands the once-per-batch prefix (B images) to the folded
+// batch: 3.3 GB written by the MASK op and read back by its consumers on the headline config.  Where a consumer can apply the
+// mask itself — conv3x3_s2 on 32x32 maps (clears the dropped elements of its patch pieces in LDS), conv3x3_patch for the input of
+// a fused shortcut on 16x16 maps — the op writes the keep bits (1/16 of the bytes) and ONE scaled copy of the B images
+// instead; kept x 1/(1-p) rounded to fp16 and ANDed with the bits is what the MASK op itself stores, so the result is bit for
+// bit the materialised one.  Decided per launch (run_op, run_conv): a consumer whose kernel does not take the launch makes the
+// MASK op's own launch happen first ("mask_lazy" = 0: always).
+void plan_lazy_sites(bmi_engine_s* e) {
+    for (size_t mi = 0; mi < e->suffix.size() && !e->f32; ++mi) {
+        const bmi_op_desc md = e->suffix[mi].d;
+        if (md.kind != BMI_OP_MASK || md.site.kind != BMI_SITE_ELEMENTWISE || md.site_pos == BMI_SITE_POS_INNER || md.site.p >= 1.f) continue;
+        const TensorInfo ti = e->tensors[md.in];
+        if (ti.stoch || ti.c % 32 != 0) continue;
+        // every reader must be able to apply the bits itself (else the tensor is written anyway and the bits are extra work):
+        //   conv3x3_s2 on 32x32 maps (also as a pair launch); conv3x3_patch for the input of a fused shortcut on 16x16 maps;
+        //   1x1 convs (conv1x1_stream clears the elements in LDS, conv_igemm while staging) and the 3x3 stride-2 convs that run in
+        //   conv_igemm anyway (ResNet-50's first site: 256 -> 128 k3s2, 256 -> 128 k1, 256 -> 512 k1s2).  A 3x3 stride-1 reader would
+        //   lose its patch kernel to the per-tap one: not lazy.
+        int readers = 0;
+        bool all = true, all_s2 = true;
+        for (const OpInfo& c : e->suffix) {
+            const int as = roles_of(c, md.out) & ROLE_READS;      // how c reads the masked tensor
+            if (!as || &c == &e->suffix[mi]) continue;
+            ++readers;
+            bool ok = false;
+            // (round 6) conv3x3_patch's 64-channel tile — 3x3 stride-1 convs with Cout % 128 == 64 on 32-wide maps: the BasicBlocks behind the stem, which is
+            // where the first "layer" site sits — clears the dropped elements of its input patch in LDS and of a residual where it is added
+            auto p64 = [&](const OpInfo& q) {
+                const TensorInfo& qi = e->tensors[q.d.in];
+                return opt_conv_patch64() && q.d.kind == BMI_OP_CONV && !q.has_pair && q.d.in2 < 0 && q.d.ksize == 3 && q.d.stride == 1 && q.d.pad == 1 &&
+                       qi.c % 64 == 0 && q.cout % 64 == 0 && q.cout % 128 != 0 && q.wo == 32 && q.ho % 8 == 0 && q.bits_tensor < 0;
+            };
+            if (p64(c) && !(as & ROLE_IN2)) {
+                // as the input (any epilogue), and / or as the residual (the register-form epilogue: no site or the 2-bit elementwise one, outer)
+                const bool res_ok = !(as & ROLE_RESIDUAL) ||
+                                    (c.d.site_pos != BMI_SITE_POS_INNER && (c.d.site.kind == BMI_SITE_NONE ||
+                                                                            (c.d.site.kind == BMI_SITE_ELEMENTWISE && bmi_site_log2_bits(c.d.site.p) == 1 && c.d.site.p < 1.f)));
+                if (res_ok) { all = all && true; all_s2 = false; continue; }
+            }
+            if (c.d.kind == BMI_OP_CONV && !(as & ROLE_RESIDUAL) && c.bits_tensor < 0) {
+                if (as & ROLE_IN2) { ok = !(as & ROLE_IN) && c.ho == 16 && c.wo == 16; all_s2 = all_s2 && ti.h == 2 * c.ho && ti.w == 2 * c.wo; }
+                else if (c.d.in2 < 0) {
+                    const bool s2 = ti.h == 32 && ti.w == 32 && c.d.residual < 0 && c.d.site.kind == BMI_SITE_NONE &&
+                                    conv_takes_s2_kernel(c.d.ksize, c.d.stride, c.d.pad, ti.c, c.cout + (c.has_pair ? c.pair_cout : 0), ti.h, ti.w, c.ho, c.wo);
+                    const bool igemm = !c.has_pair && ti.c % 64 == 0 && c.cout % 64 == 0 &&
+                                       (c.d.ksize == 1 || (c.d.ksize == 3 && c.d.stride == 2));
+                    ok = s2 || igemm;
+                    all_s2 = all_s2 && s2;
+                }
+            }
+            all = all && ok;
+        }
+        if (!all || readers == 0) continue;
+        TensorInfo tb = ti, tsc = ti;
+        tb.stoch = true; tb.bits = true; tb.first = e->tensors[md.out].first; tb.last = e->tensors[md.out].last;
+        tsc.stoch = false; tsc.first = tsc.last = -1;
+        e->tensors.push_back(tb);
+        e->tensors.push_back(tsc);
+        e->tensors[md.out].lazy_bits = (int)e->tensors.size() - 2;
+        e->tensors[md.out].lazy_scaled = (int)e->tensors.size() - 1;
+        e->tensors[md.out].lazy_planar = all_s2 && ti.c % 64 == 0 && ti.w >= 2 && (ti.w & (ti.w - 1)) == 0 && ((ti.h * ti.w) & (ti.h * ti.w - 1)) == 0 &&
+                                         bmi_site_log2_bits(md.site.p) == 1;
+    }
+}
+
+// ---- bmi_plan: the workspace, region by region in the order bmi_plan calls them (each returns where the next region starts) ----------------
+
+// The deterministic tensors (one copy per image of the batch), from offset 0
+size_t place_deterministic_tensors(bmi_engine_s* h, size_t B) {
+    size_t off = 0;
+    for (size_t i = 1; i < h->tensors.size(); ++i) {
+        TensorInfo& t = h->tensors[i];
+        if (t.stoch) continue;
+        t.offset = off;
+        off += align_up(B * t.h * t.w * t.c * (t.f32 ? 4 : 2), 256);
+    }
+    return off;
+}
+
+// first-fit packing of the suffix tensors by live range ("ws_no_reuse": no range is given out twice)
+size_t pack_suffix_tensors(bmi_engine_s* h, size_t NS, size_t st_base) {
+    struct Blk { size_t off, size; int last; };
+    std::vector<Blk> live;
+    std::vector<int> order;
+    for (size_t i = 1; i < h->tensors.size(); ++i)
+        if (h->tensors[i].stoch && h->tensors[i].first >= 0) order.push_back((int)i);
+    std::sort(order.begin(), order.end(), [&](int a, int b) { return h->tensors[a].first < h->tensors[b].first; });
+    size_t st_peak = 0;
+    h->no_reuse = opt_ws_no_reuse() != 0;
+    for (int id : order) {
+        TensorInfo& t = h->tensors[id];
+        if (!h->no_reuse) live.erase(std::remove_if(live.begin(), live.end(), [&](const Blk& b) { return b.last < t.first; }), live.end());
+        std::sort(live.begin(), live.end(), [](const Blk& a, const Blk& b) { return a.off < b.off; });
+        const size_t size = align_up(t.bits ? NS * t.h * t.w * t.c / 8 : NS * t.h * t.w * t.c * (t.f32 ? 4 : 2), 256);
+        size_t pos = 0;
+        for (const Blk& b : live) {
+            if (pos + size <= b.off) break;
+            pos = std::max(pos, b.off + b.size);
+        }
+        t.offset = st_base + pos;
+        t.bytes = size;
+        live.push_back({pos, size, t.last});
+        st_peak = std::max(st_peak, pos + size);
+    }
+    return st_base + st_peak;
+}
+
+// Split-K for the skinny deterministic 3x3 convs (VGG's 512 -> 512 convs on 2x2 maps: 250 images are 1000 pixels = 32 tiles
+// of 128 x 128 on 256 CUs, 65 us at 73 TFLOP/s): one workgroup per (tile, tap), fp32 partial sums, a finishing pass.
+// Decided here from the shape and the planned batch only.  Returns the bytes of the partial sums (the largest op's).
+size_t plan_splitk(bmi_engine_s* h, size_t B) {
+    size_t sk_bytes = 0;
+    for (OpInfo& op : h->prefix) {
+        op.nsplit = 0;
+        const bmi_op_desc& d = op.d;
+        if (d.kind != BMI_OP_CONV || (h->f32 && !h->split) || !opt_splitk() || d.ksize != 3 || d.residual >= 0 || d.in2 >= 0 || d.site.kind != BMI_SITE_NONE ||
+            op.has_pair || op.bits_tensor >= 0 || op.cout % 128 != 0)
+            continue;
+        const TensorInfo& ti = h->tensors[d.in];
+        const size_t M = B * op.ho * op.wo;
+        if (h->split) {
+            // the split engines (conv_split: 256-pixel tiles, 64-channel tiles on small grids): enough contiguous K ranges per tile for two
+            // workgroups per CU (256 CUs), nine at most, four at least (three ranges of a 252-workgroup launch measured slower: 85 -> 110 us);
+            // 72 K-steps (Cin = 256) or more
+            const size_t blocks = (M + 255) / 256 * (op.cout / 64);
+            const int ns = (int)std::min<size_t>(9, (512 + blocks - 1) / blocks);
+            if (ti.c < 256 || ns < 4) continue;
+            op.nsplit = ns;
+            sk_bytes = std::max(sk_bytes, align_up((size_t)op.nsplit * M * op.cout * sizeof(float), 256));
+            continue;
+        }
+        const size_t tiles = (M + 127) / 128 * (op.cout / 128);
+        if (ti.c % 64 != 0 || ti.c < 256 || tiles > (size_t)opt_splitk_tiles()) continue;      // stride 1 or 2 (VGG-19's 256 -> 512 exit convs: 37 -> 22 us); at
+                                                                       // Cin = 128 (18 K-steps) the split measured slower: 23 -> 28 us
+        op.nsplit = 9;
+        sk_bytes = std::max(sk_bytes, align_up((size_t)op.nsplit * M * op.cout * sizeof(float), 256));
+    }
+    return sk_bytes;
+}
+
+// The permuted copies of the Masksembles tables, one per distinct table of the graph
+size_t place_mask_tables(bmi_engine_s* h, size_t off) {
+    h->perm.clear();
+    for (const std::vector<OpInfo>* ops : {&h->prefix, &h->suffix})
+        for (const OpInfo& op : *ops) {
+            const bmi_site& st = op.d.site;
+            if (st.kind != BMI_SITE_MASKSEMBLE) continue;
+            bool seen = false;
+            for (const auto& pr : h->perm) seen = seen || pr.first == st.masks;
+            if (seen) continue;
+            const int width = op.d.kind == BMI_OP_HEAD ? h->tensors[op.d.in].c : op.cout;       // a site's table is [M][channels of its tensor]
+            h->perm.push_back({st.masks, off});
+            off += align_up((size_t)st.num_masks * width * sizeof(float), 256);
+        }
+    return off;
+}
+
+// A lazy site keeps its PLANAR layout only while every stride-2 reader's launch passes conv3x3_s2's minimum-grid rule at the planned
+// full chunk (n_ref = max_batch x chunk: what the launcher looks at; 256 CUs): a reader that declines makes run_conv materialise the
+// tensor — correct either way, but the planar bits + copy would then have been written for nothing (and conv_igemm / conv1x1_stream
+// refuse a planar operand).  Small engines (tests, T = 1 mirrors) therefore plan NHWC lazy sites.
+void plan_lazy_layout(bmi_engine_s* h, size_t NS) {
+    for (TensorInfo& t : h->tensors) {
+        t.lazy_planar_plan = t.lazy_planar;
+        if (!t.lazy_planar) continue;
+        const int id = (int)(&t - h->tensors.data());
+        for (const OpInfo& c : h->suffix) {
+            if (c.d.kind != BMI_OP_CONV || c.d.in != id || c.d.in2 >= 0) continue;       // (the fused-shortcut reader is conv3x3_patch: no grid rule on the operand)
+            const int cout = c.cout + (c.has_pair ? c.pair_cout : 0);
+            const long imgs = std::max(1, 256 / (c.ho * c.wo));
+            const long tiles = ((long)NS + imgs - 1) / imgs * (cout / (cout % 256 ? 128 : 256));
+            if (opt_conv_s2() != 2 && tiles < 3 * 256 / 4) t.lazy_planar_plan = false;
+            if (opt_conv_s2() == 0) t.lazy_planar_plan = false;
+        }
+    }
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -401,410 +954,19 @@ int bmi_create(const bmi_model_desc* desc, bmi_handle* out) {
     if (desc->n_exits < 1 || desc->out_dim < 1) return BMI_ERR_INVALID;
     if (desc->out_dim > 128) return BMI_ERR_UNSUPPORTED;
     if (desc->dtype < BMI_DTYPE_F16 || desc->dtype > BMI_DTYPE_BF16X3) return BMI_ERR_INVALID;
-    bmi_engine_s* e = new (std::nothrow) bmi_engine_s();
+    std::unique_ptr<bmi_engine_s> e(new (std::nothrow) bmi_engine_s());
     if (!e) return BMI_ERR_NOMEM;
     e->opts = bmi_default_options();
     BmiOptionScope opt_scope(&e->opts);
-    e->n_exits = desc->n_exits;
-    e->out_dim = desc->out_dim;
-    e->bf16 = desc->dtype == BMI_DTYPE_BF16;
-    e->split = desc->dtype == BMI_DTYPE_F16X2 ? 1 : (desc->dtype == BMI_DTYPE_BF16X3 ? 2 : 0);
-    e->f32 = desc->dtype == BMI_DTYPE_F32 || e->split;
-    e->dtype = desc->dtype;
-    e->tensors.resize(desc->n_tensors);
-    for (int i = 0; i < desc->n_tensors; ++i) {
-        const bmi_tensor_desc& t = desc->tensors[i];
-        if (t.h < 1 || t.w < 1 || t.c < 1) { delete e; return BMI_ERR_INVALID; }
-        e->tensors[i].h = t.h; e->tensors[i].w = t.w; e->tensors[i].c = t.c;
-        e->tensors[i].f32 = e->f32 && i > 0;   // the exact engine keeps every activation in fp32
-    }
-    std::vector<char> written(desc->n_tensors, 0);
-    written[0] = 1;  // network input
-    std::vector<char> exit_seen(desc->n_exits, 0);
-    int rc = BMI_OK;
-    for (int k = 0; k < desc->n_ops && rc == BMI_OK; ++k) {
-        OpInfo op;
-        op.d = desc->ops[k];
-        const bmi_op_desc& d = op.d;
-        auto tensor_ok = [&](int id) { return id >= 0 && id < desc->n_tensors; };
-        if (!tensor_ok(d.in) || !written[d.in] || !site_ok(d.site)) { rc = BMI_ERR_INVALID; break; }
-        const TensorInfo tin = e->tensors[d.in];
-        bool in_st = tin.stoch;
-        if (tin.f32 && !e->f32 && d.kind != BMI_OP_DENSE && d.kind != BMI_OP_HEAD) { rc = BMI_ERR_UNSUPPORTED; break; }
-        switch (d.kind) {
-            case BMI_OP_STEM:
-            case BMI_OP_CONV: {
-                if (!tensor_ok(d.out) || d.out == 0 || written[d.out] || !d.weight || d.ksize < 1 || d.stride < 1 || d.pad < 0) {
-                    rc = BMI_ERR_INVALID; break;
-                }
-                if ((d.kind == BMI_OP_STEM) != (d.in == 0)) { rc = BMI_ERR_INVALID; break; }
-                if (d.site_pos != BMI_SITE_POS_OUTER && d.site_pos != BMI_SITE_POS_INNER) { rc = BMI_ERR_INVALID; break; }
-                const bool inner = d.site_pos == BMI_SITE_POS_INNER && d.site.kind != BMI_SITE_NONE;
-                if (inner && (d.in2 >= 0 || d.site.kind == BMI_SITE_MASKSEMBLE)) { rc = BMI_ERR_UNSUPPORTED; break; }
-                const TensorInfo to = e->tensors[d.out];  // by value: the split below grows the vector
-                op.ho = (tin.h + 2 * d.pad - d.ksize) / d.stride + 1;
-                op.wo = (tin.w + 2 * d.pad - d.ksize) / d.stride + 1;
-                op.cout = to.c;
-                if (op.ho != to.h || op.wo != to.w) { rc = BMI_ERR_INVALID; break; }
-                if (d.kind == BMI_OP_CONV && !e->f32 && (tin.c % 64 != 0 || to.c % 64 != 0)) { rc = BMI_ERR_UNSUPPORTED; break; }
-                // the engines with fp32 activations: one generic kernel each (conv_exact / conv_split), 32-deep K-steps, 64-channel tiles
-                if (d.kind == BMI_OP_CONV && e->f32 && (tin.c % 32 != 0 || to.c % 64 != 0)) { rc = BMI_ERR_UNSUPPORTED; break; }
-                if (d.kind == BMI_OP_STEM && (to.c % 8 != 0 || to.c * d.ksize * d.ksize * tin.c > 4096 || d.residual >= 0)) {
-                    rc = BMI_ERR_UNSUPPORTED; break;
-                }
-                if (d.residual >= 0) {
-                    if (!tensor_ok(d.residual) || !written[d.residual] || d.residual == 0) { rc = BMI_ERR_INVALID; break; }
-                    const TensorInfo& tr = e->tensors[d.residual];
-                    if (tr.h != to.h || tr.w != to.w || tr.c != to.c) { rc = BMI_ERR_INVALID; break; }
-                    in_st = in_st || tr.stoch;
-                }
-                int64_t macs = (int64_t)op.ho * op.wo * op.cout * d.ksize * d.ksize * tin.c;
-                if (d.kind == BMI_OP_CONV && d.in2 >= 0 && e->f32 && !e->split) { rc = BMI_ERR_UNSUPPORTED; break; }   // a speed feature (BN scales folded into the weights): never in the exact engine
-                if (d.kind == BMI_OP_CONV && d.in2 >= 0) {
-                    if (!tensor_ok(d.in2) || !written[d.in2] || d.in2 == 0 || !d.weight2 || (d.scale && !e->split)) { rc = BMI_ERR_INVALID; break; }   // (split engines: the host's per-channel power-of-two lift comes back as `scale`)
-                    const TensorInfo& t2 = e->tensors[d.in2];
-                    if (t2.h % op.ho != 0 || t2.h / op.ho != t2.w / op.wo || t2.w % op.wo != 0) { rc = BMI_ERR_UNSUPPORTED; break; }
-                    // fp16 / bf16: conv3x3_patch / conv3x3_pw carry the shortcut; the split engines: extra K-steps of conv_split (any conv geometry)
-                    if (e->split ? t2.c % 32 != 0
-                                 : (d.ksize != 3 || d.stride != 1 || d.pad != 1 || t2.c % 64 != 0 || !conv_takes_patch_kernel(3, 1, 1, tin.c, op.cout, op.ho, op.wo))) {
-                        rc = BMI_ERR_UNSUPPORTED; break;
-                    }
-                    in_st = in_st || t2.stoch;
-                    macs += (int64_t)op.ho * op.wo * op.cout * t2.c;
-                }
-                if (!in_st && d.site.kind != BMI_SITE_NONE) {
-                    // deterministic conv feeding a site: keep the conv in the once-per-batch prefix
-                    // and apply the site while expanding to the folded sample batch.
-                    if (inner && d.residual >= 0) { rc = BMI_ERR_UNSUPPORTED; break; }
-                    TensorInfo tmp = to;
-                    tmp.stoch = false;
-                    e->tensors.push_back(tmp);
-                    const int tmp_id = (int)e->tensors.size() - 1;
-                    OpInfo conv = op;
-                    conv.d.out = tmp_id;
-                    conv.d.site.kind = BMI_SITE_NONE;
-                    conv.d.site_pos = BMI_SITE_POS_OUTER;
-                    conv.d.bias_post = nullptr;
-                    if (inner) conv.d.relu = 0;   // the prefix keeps conv*scale+bias; mask, BN shift and ReLU follow in the MASK op
-                    conv.stoch = false;
-                    conv.macs = macs;
-                    e->prefix.push_back(conv);
-                    e->prefix_macs += macs;
-                    OpInfo m;
-                    std::memset(&m.d, 0, sizeof(m.d));
-                    m.d.kind = BMI_OP_MASK;
-                    m.d.in = tmp_id;
-                    m.d.out = d.out;
-                    m.d.residual = -1;
-                    m.d.in2 = -1;
-                    m.d.site = d.site;
-                    if (inner) { m.d.bias_post = d.bias_post; m.d.relu = d.relu; m.d.site_pos = BMI_SITE_POS_INNER; }
-                    m.stoch = true;
-                    m.ho = to.h; m.wo = to.w; m.cout = to.c;
-                    e->suffix.push_back(m);
-                    e->tensors[d.out].stoch = true;
-                } else {
-                    op.stoch = in_st || d.site.kind != BMI_SITE_NONE;
-                    e->tensors[d.out].stoch = op.stoch;
-                    op.macs = macs;
-                    (op.stoch ? e->suffix : e->prefix).push_back(op);
-                    (op.stoch ? e->suffix_macs : e->prefix_macs) += macs;
-                }
-                written[d.out] = 1;
-                break;
-            }
-            case BMI_OP_MASK: {
-                if (!tensor_ok(d.out) || d.out == 0 || written[d.out] || d.in == 0 || d.site.kind == BMI_SITE_NONE ||
-                    d.site_pos != BMI_SITE_POS_OUTER) {
-                    rc = BMI_ERR_INVALID; break;
-                }
-                op.d.bias_post = nullptr;
-                op.d.relu = 0;
-                const TensorInfo& to = e->tensors[d.out];
-                if (to.h != tin.h || to.w != tin.w || to.c != tin.c) { rc = BMI_ERR_INVALID; break; }
-                if (tin.c % 8 != 0) { rc = BMI_ERR_UNSUPPORTED; break; }
-                op.stoch = true;
-                op.ho = to.h; op.wo = to.w; op.cout = to.c;
-                e->tensors[d.out].stoch = true;
-                e->suffix.push_back(op);
-                written[d.out] = 1;
-                break;
-            }
-            case BMI_OP_MAXPOOL: {
-                if (!tensor_ok(d.out) || d.out == 0 || written[d.out] || d.in == 0) { rc = BMI_ERR_INVALID; break; }
-                const TensorInfo& to = e->tensors[d.out];
-                if (to.h * 2 != tin.h || to.w * 2 != tin.w || to.c != tin.c) { rc = BMI_ERR_INVALID; break; }
-                if (tin.c % 8 != 0) { rc = BMI_ERR_UNSUPPORTED; break; }
-                op.stoch = in_st;
-                op.ho = to.h; op.wo = to.w; op.cout = to.c;
-                e->tensors[d.out].stoch = in_st;
-                (in_st ? e->suffix : e->prefix).push_back(op);
-                written[d.out] = 1;
-                break;
-            }
-            case BMI_OP_DENSE: {
-                if (!tensor_ok(d.out) || d.out == 0 || written[d.out] || d.in == 0 || !d.weight || !d.bias ||
-                    d.site_pos != BMI_SITE_POS_OUTER) {
-                    rc = BMI_ERR_INVALID; break;
-                }
-                const TensorInfo& to = e->tensors[d.out];
-                if (tin.h != 1 || tin.w != 1 || to.h != 1 || to.w != 1) { rc = BMI_ERR_INVALID; break; }
-                if (tin.c % 32 != 0 || to.c % 64 != 0) { rc = BMI_ERR_UNSUPPORTED; break; }
-                op.d.residual = -1; op.d.in2 = -1;
-                // a site makes the layer per-sample even on a deterministic input (the layer is tiny: no conv + MASK split)
-                op.stoch = in_st || d.site.kind != BMI_SITE_NONE;
-                op.ho = 1; op.wo = 1; op.cout = to.c;
-                e->tensors[d.out].stoch = op.stoch;
-                e->tensors[d.out].f32 = true;
-                e->tensors[d.out].dense_out = true;
-                op.macs = (int64_t)tin.c * to.c;
-                (op.stoch ? e->suffix : e->prefix).push_back(op);
-                (op.stoch ? e->suffix_macs : e->prefix_macs) += (int64_t)tin.c * to.c;
-                written[d.out] = 1;
-                break;
-            }
-            case BMI_OP_HEAD: {
-                if (d.in == 0 || d.out < 0 || d.out >= desc->n_exits || exit_seen[d.out] || !d.weight || !d.bias) {
-                    rc = BMI_ERR_INVALID; break;
-                }
-                if (tin.c % 32 != 0) { rc = BMI_ERR_UNSUPPORTED; break; }   // head_fused splits K over 4 waves x 2 lane halves x float4
-                if (d.site_pos == BMI_SITE_POS_INNER && d.site.kind != BMI_SITE_NONE && d.site.kind != BMI_SITE_ELEMENTWISE) {
-                    rc = BMI_ERR_UNSUPPORTED; break;   // dropout on the logits is elementwise (F.dropout after nn.Linear)
-                }
-                exit_seen[d.out] = 1;
-                op.stoch = true;  // heads always run per sample (they emit per-sample softmax)
-                op.cout = desc->out_dim;
-                op.macs = (int64_t)tin.c * desc->out_dim;
-                e->suffix.push_back(op);
-                e->suffix_macs += (int64_t)tin.c * desc->out_dim;
-                break;
-            }
-            default: rc = BMI_ERR_INVALID;
-        }
-    }
-    if (rc == BMI_OK)
-        for (int x = 0; x < desc->n_exits; ++x)
-            if (!exit_seen[x]) rc = BMI_ERR_INVALID;
-    if (rc != BMI_OK) { delete e; return rc; }
-    // Input-side dropout: an elementwise site that expands a deterministic tensor and is consumed only
-    // as the input of convs that stage their input through registers (conv_igemm) is not materialised:
-    // the MASK op emits keep bits (16x fewer bytes), the consumers read the deterministic tensor (L2 /
-    // Infinity Cache resident, B images) and zero the dropped elements while staging; 1/(1-p) is
-    // folded into their BN scale.  Same-box A/B on the headline config: HBM traffic of the site drops
-    // 16x but the step time is unchanged (-0.47 ms in the mask kernel, +0.5 ms in the three consumers),
-    // so it is OFF by default; BMI_MASK_BITS=1 enables it (covered by the parity tests).
-    {
-        const char* env = std::getenv("BMI_MASK_BITS");
-        const bool enable = env && std::atoi(env) == 1 && !e->f32;
-        for (size_t mi = 0; enable && mi < e->suffix.size(); ++mi) {
-            OpInfo& m = e->suffix[mi];
-            if (m.d.kind != BMI_OP_MASK || m.d.site.kind != BMI_SITE_ELEMENTWISE || e->tensors[m.d.in].stoch) continue;
-            if (m.d.site_pos == BMI_SITE_POS_INNER) continue;   // carries a BN shift / ReLU: must be materialised
-            if (m.d.site.p >= 1.f || e->tensors[m.d.in].c % 8 != 0) continue;
-            bool ok = true;
-            int uses = 0;
-            for (const OpInfo& c : e->suffix) {
-                if (&c == &m) continue;
-                const bool as_in = c.d.in == m.d.out, as_res = c.d.kind == BMI_OP_CONV && c.d.residual == m.d.out;
-                if (!as_in && !as_res) continue;
-                ++uses;
-                const TensorInfo& ti = e->tensors[m.d.out];
-                if (as_res || c.d.kind != BMI_OP_CONV ||
-                    conv_takes_patch_kernel(c.d.ksize, c.d.stride, c.d.pad, ti.c, c.cout, c.ho, c.wo))
-                    ok = false;
-            }
-            if (!ok || uses == 0) continue;
-            m.d.kind = OP_MASKBITS;
-            e->tensors[m.d.out].bits = true;
-            for (OpInfo& c : e->suffix)
-                if (&c != &m && c.d.kind == BMI_OP_CONV && c.d.in == m.d.out) {
-                    c.bits_tensor = m.d.out;
-                    c.d.in = m.d.in;
-                    c.out_mul = bmi_drop_scale(m.d.site.p);
-                }
-        }
-    }
-    // Pair fusion: two suffix convs that read the same tensor with the same geometry and a plain BN(+ReLU) epilogue
-    // (layerN.0.conv1 and the first conv of the exit head in front of it, resnet18.py:306/:318/:329 vs :280-299)
-    // run as ONE conv_igemm_wide launch: the input tile is fetched once for both and a 128-channel conv still fills
-    // the kernel's 256-channel tile.  The later conv moves up to the earlier one's position (it depends on nothing
-    // in between).  BMI_CONV_PAIR=0 keeps them separate (A/B, tests).
-    {
-        const char* env = std::getenv("BMI_CONV_PAIR");
-        const bool enable = (!env || std::atoi(env) != 0) && (!e->f32 || e->split);      // (the exact engine's kernel has no pair mode)
-        auto plain = [&](const OpInfo& c) {
-            return c.d.kind == BMI_OP_CONV && !c.has_pair && c.d.residual < 0 && c.d.in2 < 0 && c.d.site.kind == BMI_SITE_NONE &&
-                   c.bits_tensor < 0 && c.out_mul == 1.f && c.d.scale && c.d.bias;
-        };
-        auto merge = [&](std::vector<OpInfo>& ops, bool prefix) {
-            for (size_t i = 0; i < ops.size(); ++i) {
-                if (!plain(ops[i])) continue;
-                const OpInfo A = ops[i];
-                const TensorInfo& ti = e->tensors[A.d.in];
-                // (prefix: a conv with 256+ input channels may get a split-K launch from bmi_plan on a small batch — VGG's exit convs, 37 -> 22 us —
-                //  which a pair launch does not have: those stay single.  Measured: VGG-11 on f16x2 15.0 -> 14.4 M with every prefix pair merged)
-                if (prefix && ti.c >= 256) continue;
-                if (conv_takes_patch_kernel(A.d.ksize, A.d.stride, A.d.pad, ti.c, A.cout, A.ho, A.wo)) continue;
-                for (size_t j = i + 1; j < ops.size(); ++j) {
-                    const OpInfo& Bo = ops[j];
-                    if (!plain(Bo) || Bo.d.in != A.d.in || Bo.d.ksize != A.d.ksize || Bo.d.stride != A.d.stride ||
-                        Bo.d.pad != A.d.pad || Bo.d.relu != A.d.relu)
-                        continue;
-                    if (A.cout % 128 != 0 || !conv_takes_wide_kernel(ti.c, A.cout + Bo.cout)) continue;
-                    if (e->split && Bo.cout % 128 != 0) continue;
-                    ops[i].has_pair = true;
-                    ops[i].pair_d = Bo.d;
-                    ops[i].pair_cout = Bo.cout;
-                    ops[i].macs += Bo.macs;
-                    ops.erase(ops.begin() + (long)j);
-                    break;
-                }
-            }
-        };
-        if (enable) merge(e->suffix, false);
-        // "pair_prefix" (round 6): the same for the once-per-batch prefix — with exit-only dropout the whole network is prefix and the pairs are
-        // there: the paper's configuration 3.60-3.63 M -> 3.70-3.77 M MCD-samples/s, same box (profiles/experiments/r6_exit_only_variants.txt).
-        if (enable && opt_pair_prefix() && !e->f32) merge(e->prefix, true);
-    }
-    // Seam fusion (Bottleneck nets): conv3 + BN + residual + ReLU of block k followed at once by conv1 + BN + ReLU of block k+1 on its output:
-    // one conv1x1_seam launch produces both tensors and the wide one is not read back (conv1x1_seam.hip).  Decided per launch in run_conv.
-    for (size_t i = 0; !e->f32 && opt_conv_seam() && i + 1 < e->suffix.size(); ++i) {
-        OpInfo& A = e->suffix[i];
-        const OpInfo& Bo = e->suffix[i + 1];
-        auto one = [&](const OpInfo& c) {
-            return c.d.kind == BMI_OP_CONV && c.stoch && !c.has_pair && c.d.in2 < 0 && c.d.site.kind == BMI_SITE_NONE && c.bits_tensor < 0 && c.out_mul == 1.f &&
-                   c.d.ksize == 1 && c.d.stride == 1 && c.d.pad == 0 && c.d.scale && c.d.bias;
-        };
-        if (!one(A) || !one(Bo) || A.d.residual < 0 || !A.d.relu || Bo.d.residual >= 0 || Bo.d.in != A.d.out) continue;
-        if (!e->tensors[A.d.in].stoch || !e->tensors[A.d.residual].stoch) continue;
-        if (!conv_takes_seam_kernel(e->tensors[A.d.in].c, A.cout, Bo.cout)) continue;
-        A.has_seam = true;
-        A.seam_d = Bo.d;
-        A.seam_cout = Bo.cout;
-        A.macs += Bo.macs;
-        e->suffix.erase(e->suffix.begin() + (long)i + 1);
-    }
-    // ReLU + global average pool fused into the producing conv: a plain 3x3 stride-2 conv whose 4x4 output map feeds ONE exit head and
-    // nothing else (ex1conv3 / ex2conv2 / ex3conv1 of the ResNets: relu -> avg_pool2d(4) -> Linear, resnet18.py:309-314, :320-325,
-    // :331-335) may write fp32 means [row][Cout] instead of the map when conv3x3_s2 takes the launch (decided per launch: run_conv).
-    for (std::vector<OpInfo>* ops : {&e->prefix, &e->suffix}) {
-        auto readers = [&](int id, int* heads) {
-            int n = 0;
-            *heads = 0;
-            for (const std::vector<OpInfo>* o2 : {&e->prefix, &e->suffix})
-                for (const OpInfo& c : *o2) {
-                    const bmi_op_desc& d = c.d;
-                    const bool conv = d.kind == BMI_OP_CONV || d.kind == BMI_OP_STEM;
-                    if (d.in == id) { ++n; if (d.kind == BMI_OP_HEAD) ++*heads; }
-                    if (conv && d.residual == id) ++n;
-                    if (conv && d.in2 == id) ++n;
-                    if (c.bits_tensor == id) ++n;
-                }
-            return n;
-        };
-        for (OpInfo& c : *ops) {
-            if (c.d.kind != BMI_OP_CONV || e->f32) continue;
-            auto eligible = [&](const bmi_op_desc& d, int cout) {
-                const TensorInfo& to = e->tensors[d.out];
-                int heads = 0;
-                return d.ksize == 3 && d.stride == 2 && d.pad == 1 && to.h == 4 && to.w == 4 && d.residual < 0 && d.in2 < 0 &&
-                       d.site.kind == BMI_SITE_NONE && cout % 128 == 0 && readers(d.out, &heads) == 1 && heads == 1;
-            };
-            // ... and the last conv of the net (layer4[1].conv2: stride 1, with its residual) in front of the final head: conv3x3_pw's
-            // lite epilogue does the same on its registers
-            auto eligible_pw = [&](const bmi_op_desc& d, int cout) {
-                const TensorInfo& to = e->tensors[d.out];
-                int heads = 0;
-                return d.ksize == 3 && d.stride == 1 && d.pad == 1 && to.h == 4 && to.w == 4 && d.in2 < 0 && d.relu &&
-                       (d.site.kind == BMI_SITE_NONE || d.site_pos != BMI_SITE_POS_INNER) && cout % 256 == 0 && !c.has_pair &&
-                       readers(d.out, &heads) == 1 && heads == 1;
-            };
-            c.pool_pw_ok = c.bits_tensor < 0 && eligible_pw(c.d, c.cout);
-            c.pool_ok = c.bits_tensor < 0 && eligible(c.d, c.cout);
-            c.pair_pool_ok = c.has_pair && eligible(c.pair_d, c.pair_cout);
-        }
-    }
-    // live ranges of the stochastic tensors over the suffix
-    for (int k = 0; k < (int)e->suffix.size(); ++k) {
-        const bmi_op_desc& d = e->suffix[k].d;
-        auto touch = [&](int id) {
-            if (id < 0) return;
-            TensorInfo& t = e->tensors[id];
-            if (!t.stoch) return;
-            if (t.first < 0) t.first = k;
-            t.last = k;
-        };
-        touch(d.in);
-        if (d.kind == BMI_OP_CONV) touch(d.in2);
-        touch(e->suffix[k].bits_tensor);
-        if (d.kind == BMI_OP_CONV) touch(d.residual);
-        if (d.kind != BMI_OP_HEAD) touch(d.out);
-        if (e->suffix[k].has_pair) touch(e->suffix[k].pair_d.out);
-        if (e->suffix[k].has_seam) touch(e->suffix[k].seam_d.out);
-    }
-    // Lazy sites.  The first elementwise site of a "block"-dropout ResNet expands the once-per-batch prefix (B images) to the folded
-    // batch: 3.3 GB written by the MASK op and read back by its consumers on the headline config.  Where a consumer can apply the
-    // mask itself — conv3x3_s2 on 32x32 maps (clears the dropped elements of its patch pieces in LDS), conv3x3_patch for the input of
-    // a fused shortcut on 16x16 maps — the op writes the keep bits (1/16 of the bytes) and ONE scaled copy of the B images
-    // instead; kept x 1/(1-p) rounded to fp16 and ANDed with the bits is what the MASK op itself stores, so the result is bit for
-    // bit the materialised one.  Decided per launch (run_op, run_conv): a consumer whose kernel does not take the launch makes the
-    // MASK op's own launch happen first ("mask_lazy" = 0: always).
-    for (size_t mi = 0; mi < e->suffix.size() && !e->f32; ++mi) {
-        const bmi_op_desc md = e->suffix[mi].d;
-        if (md.kind != BMI_OP_MASK || md.site.kind != BMI_SITE_ELEMENTWISE || md.site_pos == BMI_SITE_POS_INNER || md.site.p >= 1.f) continue;
-        const TensorInfo ti = e->tensors[md.in];
-        if (ti.stoch || ti.c % 32 != 0) continue;
-        // every reader must be able to apply the bits itself (else the tensor is written anyway and the bits are extra work):
-        //   conv3x3_s2 on 32x32 maps (also as a pair launch); conv3x3_patch for the input of a fused shortcut on 16x16 maps;
-        //   1x1 convs (conv1x1_stream clears the elements in LDS, conv_igemm while staging) and the 3x3 stride-2 convs that run in
-        //   conv_igemm anyway (ResNet-50's first site: 256 -> 128 k3s2, 256 -> 128 k1, 256 -> 512 k1s2).  A 3x3 stride-1 reader would
-        //   lose its patch kernel to the per-tap one: not lazy.
-        int readers = 0;
-        bool all = true, all_s2 = true;
-        for (const OpInfo& c : e->suffix) {
-            const bool reads = c.d.in == md.out || (c.d.kind == BMI_OP_CONV && (c.d.residual == md.out || c.d.in2 == md.out)) || c.bits_tensor == md.out;
-            if (!reads || &c == &e->suffix[mi]) continue;
-            ++readers;
-            bool ok = false;
-            // (round 6) conv3x3_patch's 64-channel tile — 3x3 stride-1 convs with Cout % 128 == 64 on 32-wide maps: the BasicBlocks behind the stem, which is
-            // where the first "layer" site sits — clears the dropped elements of its input patch in LDS and of a residual where it is added
-            auto p64 = [&](const OpInfo& q) {
-                const TensorInfo& qi = e->tensors[q.d.in];
-                return opt_conv_patch64() && q.d.kind == BMI_OP_CONV && !q.has_pair && q.d.in2 < 0 && q.d.ksize == 3 && q.d.stride == 1 && q.d.pad == 1 &&
-                       qi.c % 64 == 0 && q.cout % 64 == 0 && q.cout % 128 != 0 && q.wo == 32 && q.ho % 8 == 0 && q.bits_tensor < 0;
-            };
-            if (p64(c) && c.d.in2 != md.out) {
-                // as the input (any epilogue), and / or as the residual (the register-form epilogue: no site or the 2-bit elementwise one, outer)
-                const bool res_ok = c.d.residual != md.out ||
-                                    (c.d.site_pos != BMI_SITE_POS_INNER && (c.d.site.kind == BMI_SITE_NONE ||
-                                                                            (c.d.site.kind == BMI_SITE_ELEMENTWISE && bmi_site_log2_bits(c.d.site.p) == 1 && c.d.site.p < 1.f)));
-                if (res_ok) { all = all && true; all_s2 = false; continue; }
-            }
-            if (c.d.kind == BMI_OP_CONV && c.d.residual != md.out && c.bits_tensor < 0) {
-                if (c.d.in2 == md.out) { ok = c.d.in != md.out && c.ho == 16 && c.wo == 16; all_s2 = all_s2 && ti.h == 2 * c.ho && ti.w == 2 * c.wo; }
-                else if (c.d.in2 < 0) {
-                    const bool s2 = ti.h == 32 && ti.w == 32 && c.d.residual < 0 && c.d.site.kind == BMI_SITE_NONE &&
-                                    conv_takes_s2_kernel(c.d.ksize, c.d.stride, c.d.pad, ti.c, c.cout + (c.has_pair ? c.pair_cout : 0), ti.h, ti.w, c.ho, c.wo);
-                    const bool igemm = !c.has_pair && ti.c % 64 == 0 && c.cout % 64 == 0 &&
-                                       (c.d.ksize == 1 || (c.d.ksize == 3 && c.d.stride == 2));
-                    ok = s2 || igemm;
-                    all_s2 = all_s2 && s2;
-                }
-            }
-            all = all && ok;
-        }
-        if (!all || readers == 0) continue;
-        TensorInfo tb = ti, tsc = ti;
-        tb.stoch = true; tb.bits = true; tb.first = e->tensors[md.out].first; tb.last = e->tensors[md.out].last;
-        tsc.stoch = false; tsc.first = tsc.last = -1;
-        e->tensors.push_back(tb);
-        e->tensors.push_back(tsc);
-        e->tensors[md.out].lazy_bits = (int)e->tensors.size() - 2;
-        e->tensors[md.out].lazy_scaled = (int)e->tensors.size() - 1;
-        e->tensors[md.out].lazy_planar = all_s2 && ti.c % 64 == 0 && ti.w >= 2 && (ti.w & (ti.w - 1)) == 0 && ((ti.h * ti.w) & (ti.h * ti.w - 1)) == 0 &&
-                                         bmi_site_log2_bits(md.site.p) == 1;
-    }
-    *out = e;
+    const int rc = read_graph(e.get(), desc);
+    if (rc != BMI_OK) return rc;
+    rewrite_mask_bits(e.get());
+    fuse_pairs(e.get());            // after rewrite_mask_bits: a conv that reads keep bits is not "plain"
+    fuse_seams(e.get());            // after fuse_pairs: an op that has a pair takes no seam
+    mark_pooled_tails(e.get());     // after the fusions: reads has_pair / pair_d and counts the readers that are left
+    compute_live_ranges(e.get());   // over the suffix in its final order
+    plan_lazy_sites(e.get());       // last: copies first / last of the live ranges and must see the pair-fused consumers
+    *out = e.release();
     return BMI_OK;
 }
 
@@ -875,111 +1037,24 @@ int bmi_plan(bmi_handle h, int32_t max_batch, int32_t chunk_samples, size_t* wor
     if (!h || max_batch < 1 || chunk_samples < 1 || !workspace_bytes) return BMI_ERR_INVALID;
     BmiOptionScope opt_scope(&h->opts);
     const size_t B = (size_t)max_batch, NS = (size_t)max_batch * chunk_samples;
-    for (const TensorInfo& t : h->tensors)  // pixel indices (N * H * W) stay inside int32
+    for (const TensorInfo& t : h->tensors)  // pixel indices (N * H * W) stay inside int32 (checked before the handle is touched: a refused plan leaves the last one in force)
         if (NS * t.h * t.w >= 0x7fffffffull) return BMI_ERR_UNSUPPORTED;
-    size_t off = 0;
-    for (size_t i = 1; i < h->tensors.size(); ++i) {
-        TensorInfo& t = h->tensors[i];
-        if (t.stoch) continue;
-        t.offset = off;
-        off += align_up(B * t.h * t.w * t.c * (t.f32 ? 4 : 2), 256);
-    }
-    // first-fit packing of the suffix tensors by live range
-    struct Blk { size_t off, size; int last; };
-    std::vector<Blk> live;
-    std::vector<int> order;
-    for (size_t i = 1; i < h->tensors.size(); ++i)
-        if (h->tensors[i].stoch && h->tensors[i].first >= 0) order.push_back((int)i);
-    std::sort(order.begin(), order.end(), [&](int a, int b) { return h->tensors[a].first < h->tensors[b].first; });
-    const size_t st_base = off;
-    size_t st_peak = 0;
-    h->no_reuse = opt_ws_no_reuse() != 0;
-    for (int id : order) {
-        TensorInfo& t = h->tensors[id];
-        if (!h->no_reuse) live.erase(std::remove_if(live.begin(), live.end(), [&](const Blk& b) { return b.last < t.first; }), live.end());
-        std::sort(live.begin(), live.end(), [](const Blk& a, const Blk& b) { return a.off < b.off; });
-        const size_t size = align_up(t.bits ? NS * t.h * t.w * t.c / 8 : NS * t.h * t.w * t.c * (t.f32 ? 4 : 2), 256);
-        size_t pos = 0;
-        for (const Blk& b : live) {
-            if (pos + size <= b.off) break;
-            pos = std::max(pos, b.off + b.size);
-        }
-        t.offset = st_base + pos;
-        t.bytes = size;
-        live.push_back({pos, size, t.last});
-        st_peak = std::max(st_peak, pos + size);
-    }
-    off = st_base + st_peak;
+    size_t off = place_deterministic_tensors(h, B);
+    off = pack_suffix_tensors(h, NS, off);
     h->exit_off = off;
     off += align_up(ActiveImages::ints(max_batch, NS) * sizeof(int), 256);
-    // Split-K for the skinny deterministic 3x3 convs (VGG's 512 -> 512 convs on 2x2 maps: 250 images are 1000 pixels = 32 tiles
-    // of 128 x 128 on 256 CUs, 65 us at 73 TFLOP/s): one workgroup per (tile, tap), fp32 partial sums, a finishing pass.
-    // Decided here from the shape and the planned batch only.
     h->splitk_off = off;
-    size_t sk_bytes = 0;
-    for (OpInfo& op : h->prefix) {
-        op.nsplit = 0;
-        const bmi_op_desc& d = op.d;
-        if (d.kind != BMI_OP_CONV || (h->f32 && !h->split) || !opt_splitk() || d.ksize != 3 || d.residual >= 0 || d.in2 >= 0 || d.site.kind != BMI_SITE_NONE ||
-            op.has_pair || op.bits_tensor >= 0 || op.cout % 128 != 0)
-            continue;
-        const TensorInfo& ti = h->tensors[d.in];
-        const size_t M = B * op.ho * op.wo;
-        if (h->split) {
-            // the split engines (conv_split: 256-pixel tiles, 64-channel tiles on small grids): enough contiguous K ranges per tile for two
-            // workgroups per CU (256 CUs), nine at most, four at least (three ranges of a 252-workgroup launch measured slower: 85 -> 110 us);
-            // 72 K-steps (Cin = 256) or more
-            const size_t blocks = (M + 255) / 256 * (op.cout / 64);
-            const int ns = (int)std::min<size_t>(9, (512 + blocks - 1) / blocks);
-            if (ti.c < 256 || ns < 4) continue;
-            op.nsplit = ns;
-            sk_bytes = std::max(sk_bytes, align_up((size_t)op.nsplit * M * op.cout * sizeof(float), 256));
-            continue;
-        }
-        const size_t tiles = (M + 127) / 128 * (op.cout / 128);
-        if (ti.c % 64 != 0 || ti.c < 256 || tiles > (size_t)opt_splitk_tiles()) continue;      // stride 1 or 2 (VGG-19's 256 -> 512 exit convs: 37 -> 22 us); at
-                                                                       // Cin = 128 (18 K-steps) the split measured slower: 23 -> 28 us
-        op.nsplit = 9;
-        sk_bytes = std::max(sk_bytes, align_up((size_t)op.nsplit * M * op.cout * sizeof(float), 256));
-    }
-    off += sk_bytes;
+    off += plan_splitk(h, B);
     h->head_off = off;
     // [groups][3][B][C] moment partials + [groups][B] entropy partials (bmi_forward_mcd_entropy)
     h->head_part_bytes = align_up((size_t)((chunk_samples + 31) / 32) * max_batch * (3 * h->out_dim + 1) * sizeof(double), 256);
     off += h->head_part_bytes * (size_t)h->n_exits;      // one region per exit: the heads of a batched launch (launch_head_fused_multi) run concurrently
-    h->perm.clear();
-    for (const std::vector<OpInfo>* ops : {&h->prefix, &h->suffix})
-        for (const OpInfo& op : *ops) {
-            const bmi_site& st = op.d.site;
-            if (st.kind != BMI_SITE_MASKSEMBLE) continue;
-            bool seen = false;
-            for (const auto& pr : h->perm) seen = seen || pr.first == st.masks;
-            if (seen) continue;
-            const int width = op.d.kind == BMI_OP_HEAD ? h->tensors[op.d.in].c : op.cout;       // a site's table is [M][channels of its tensor]
-            h->perm.push_back({st.masks, off});
-            off += align_up((size_t)st.num_masks * width * sizeof(float), 256);
-        }
+    off = place_mask_tables(h, off);
     h->ws_bytes = off;
     h->max_batch = max_batch;
     h->chunk = chunk_samples;
-    // A lazy site keeps its PLANAR layout only while every stride-2 reader's launch passes conv3x3_s2's minimum-grid rule at the planned
-    // full chunk (n_ref = max_batch x chunk: what the launcher looks at; 256 CUs): a reader that declines makes run_conv materialise the
-    // tensor — correct either way, but the planar bits + copy would then have been written for nothing (and conv_igemm / conv1x1_stream
-    // refuse a planar operand).  Small engines (tests, T = 1 mirrors) therefore plan NHWC lazy sites.
-    for (TensorInfo& t : h->tensors) {
-        t.lazy_planar_plan = t.lazy_planar;
-        if (!t.lazy_planar) continue;
-        const int id = (int)(&t - h->tensors.data());
-        for (const OpInfo& c : h->suffix) {
-            if (c.d.kind != BMI_OP_CONV || c.d.in != id || c.d.in2 >= 0) continue;       // (the fused-shortcut reader is conv3x3_patch: no grid rule on the operand)
-            const int cout = c.cout + (c.has_pair ? c.pair_cout : 0);
-            const long imgs = std::max(1, 256 / (c.ho * c.wo));
-            const long tiles = ((long)NS + imgs - 1) / imgs * (cout / (cout % 256 ? 128 : 256));
-            if (opt_conv_s2() != 2 && tiles < 3 * 256 / 4) t.lazy_planar_plan = false;
-            if (opt_conv_s2() == 0) t.lazy_planar_plan = false;
-        }
-    }
-    plan_exit_stages(h);
+    plan_lazy_layout(h, NS);
+    plan_exit_stages(h);            // after pack_suffix_tensors: checks the staged orders against the offsets just given out
     *workspace_bytes = off;
     return BMI_OK;
 }
