@@ -20,6 +20,7 @@ STOP_RULES = {"sem": 0, "margin": 1}      # BMI_STOP_* of bmi_forward_mcd_adapti
 EXIT_RULES = {"confidence": 0, "margin": 1}      # BMI_EXIT_* of bmi_forward_mcd_exit_staged
 STOP_ON = {"exit": 0, "ensemble": 1}      # BMI_STOP_ON_* of bmi_forward_mcd_adaptive_ensemble
 NLL_VEC_SLAB, NLL_VEC_ROWS = 3456, 64       # bmi_nll_vector_scaling_grad stages min(NLL_VEC_ROWS, NLL_VEC_SLAB // (C | 1)) samples per chunk
+NLL_MAT_SLAB, NLL_MAT_ROWS = 3456, 64       # bmi_nll_matrix_scaling_grad stages min(NLL_MAT_ROWS, NLL_MAT_SLAB // (C | 1)) samples per chunk
 NLL_ENS_SLAB, NLL_ENS_ROWS = 9216, 192      # BMI_NLL_ENS_* of bmi_nll_ensemble_temperature_grid: floats / rows a workgroup stages per chunk
 
 
@@ -92,6 +93,10 @@ _PROTOS = {
     "bmi_ensemble_moments_vector": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 7),
     "bmi_nll_vector_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "bmi_nll_vector_scaling_grad": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 7 + [C.c_size_t, C.c_void_p]),
+    "bmi_engine_set_matrix_scaling": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
+    "bmi_ensemble_moments_matrix": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 7),
+    "bmi_nll_matrix_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "bmi_nll_matrix_scaling_grad": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 7 + [C.c_size_t, C.c_void_p]),
     "bmi_finalize_ensemble": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 10),
     "bmi_finalize_uncertainty": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 7),
     "bmi_forward_mcd_samples": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_int32, C.c_int32, C.c_void_p,

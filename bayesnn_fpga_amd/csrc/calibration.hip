@@ -389,3 +389,167 @@ int launch_nll_vector_scaling_grad(const float* logits, int T, int E, int B, int
     BMI_CHECK_LAUNCH();
     return BMI_OK;
 }
+
+// Value and gradient of a per-exit MATRIX-SCALING fit (bmi_nll_matrix_scaling_grad): nll_vec_terms_kernel with
+//     z_tc = ((0.0 + (double)l_t0 * M[c][0]) + (double)l_t1 * M[c][1] + ...) + b[c]       j ascending, every operation rounded
+// (M float64 [E][C][C] row-major, row = output class; b float64 [E][C]) in place of l * a + b, and the gradient of the matrix,
+//     d nll_b / d M[c][j] = sum_t r_t (p_tc - [c == y]) l_tj,
+// beside the bias's (train/calibration.py: nll_matrix_numpy).  float64 throughout, no fused multiply-adds, no floating-point atomics.
+//
+//   workgroup = one image x one exit, 256 threads; the samples go through LDS in chunks of TC rows, in sample order.
+//   z           a thread per (sample, class) of the chunk walks its row of M (through L1 / L2: 80 KB per exit at C = 100 do not fit in LDS
+//               beside the chunk) against the staged logits, j ascending, and leaves z in pe.
+//   pass 1      a group of L lanes per row, as in the vector kernel: max of z, the exponentials over z in place, their sum by shuffle
+//               butterfly, A_t (by the lane that met class y).
+//   join        one thread: the running (M, S) of the log-sum-exp over samples, the chunk's weights w_t — the vector kernel's.
+//   d           a thread per (sample, class): d_tc = w_t (p_tc - [c == y]) over the exponential in place.
+//   sums        a thread per entry k of [C * C + C] adds the chunk's samples in sample order onto ITS OWN running sum, which lives in the
+//               image's row of `terms` (read back by the thread that wrote it; rescaled by exp(M_old - M_new) from the second chunk on, divided
+//               by S in the last one): 10 100 running sums at C = 100 are neither 256 threads' registers nor this workgroup's LDS.
+//   terms       [E][B][1 + C * C + C] float64: the image's nll, the C * C entries of d / d M, the C of d / d b; nll_mat_sum_kernel adds
+//               them over the images in nll_sum_kernel's fixed order INTO the outputs.
+#define NLLM_SLAB 3456           // staged logits (floats, 13.5 KB) and z / exponentials / d (float64, 27 KB) per chunk
+#define NLLM_ROWS 64             // samples per staged chunk, at most: the kernel's staging limit is min(NLLM_ROWS, NLLM_SLAB / (C | 1))
+#define NLLM_MAX_C 128           // the head's own limit
+
+__global__ __launch_bounds__(NLL_THREADS) void nll_mat_terms_kernel(const float* __restrict__ logits, int T, int E, int B, int C, int CS, int TC,
+                                                                    int L, const int* __restrict__ labels, const double* __restrict__ matrix,
+                                                                    const double* __restrict__ bias, double* __restrict__ terms) {
+#pragma clang fp contract(off)
+    __shared__ float slab[NLLM_SLAB];                    // [tl][CS] raw logits
+    __shared__ double pe[NLLM_SLAB];                     // [tl][CS] z, then exp(z - m_t), then d
+    __shared__ double row_s[NLLM_ROWS], row_a[NLLM_ROWS], wt[NLLM_ROWS];
+    __shared__ double st[3];                             // running M, S and the chunk's rescale factor exp(M_old - M_new)
+    const int tid = threadIdx.x;
+    const int b = blockIdx.x, e = blockIdx.y;
+    const int lane = tid & (L - 1), grp = tid / L, ngrp = NLL_THREADS / L;
+    const int y = labels[b];
+    const bool y_ok = y >= 0 && y < C;                   // (the callers check their labels: never an out-of-range read)
+    const double* const mat = matrix + (size_t)e * C * C;
+    const double* const bi = bias + (size_t)e * C;
+    const int NK = C * C + C;
+    double* const out = terms + ((size_t)e * B + b) * (size_t)(NK + 1);
+    if (tid == 0) { st[0] = -INFINITY; st[1] = 0.0; st[2] = 0.0; }
+    for (int t0 = 0; t0 < T; t0 += TC) {
+        const int tcn = min(TC, T - t0);                 // <= NLLM_ROWS, tcn * CS <= NLLM_SLAB (the launcher's TC)
+        __syncthreads();                                 // the previous chunk's readers are done (first chunk: st is written)
+        for (int i = tid; i < tcn * C; i += NLL_THREADS) {
+            const int tl = i / C, c = i - tl * C;
+            slab[tl * CS + c] = logits[(((size_t)(t0 + tl) * E + e) * B + b) * C + c];
+        }
+        __syncthreads();
+        for (int i = tid; i < tcn * C; i += NLL_THREADS) {
+            const int tl = i / C, c = i - tl * C;
+            const float* row = slab + tl * CS;
+            const double* mrow = mat + (size_t)c * C;
+            double z = 0.0;
+            for (int j = 0; j < C; ++j) {
+                const double prod = (double)row[j] * mrow[j];
+                z = z + prod;
+            }
+            pe[tl * CS + c] = z + bi[c];
+        }
+        __syncthreads();
+        for (int r0 = 0; r0 < tcn; r0 += ngrp) {         // (every lane walks every step: the shuffles below need whole groups)
+            const int r = r0 + grp;
+            const bool live = r < tcn;
+            double* zrow = pe + (live ? r : 0) * CS;
+            double mx = -INFINITY;
+            if (live)
+                for (int c = lane; c < C; c += L) mx = fmax(mx, zrow[c]);
+            for (int m = L >> 1; m >= 1; m >>= 1) mx = fmax(mx, __shfl_xor(mx, m));
+            double s = 0.0, zy = 0.0;
+            bool mine = false;                           // this lane met class y
+            if (live)
+                for (int c = lane; c < C; c += L) {
+                    const double z = zrow[c];
+                    if (c == y) { zy = z; mine = true; }
+                    const double ex = exp(z - mx);
+                    zrow[c] = ex;
+                    s += ex;
+                }
+            for (int m = L >> 1; m >= 1; m >>= 1) s += __shfl_xor(s, m);
+            if (live && lane == 0) {
+                row_s[r] = s;
+                if (!y_ok) row_a[r] = (double)NAN;
+            }
+            if (live && mine) row_a[r] = (zy - mx) - log(s);
+        }
+        __syncthreads();
+        if (tid == 0) {
+            double cm = row_a[0];
+            for (int tl = 1; tl < tcn; ++tl) cm = fmax(cm, row_a[tl]);
+            const double m = st[0], nm = fmax(m, cm);
+            const double f = exp(m - nm);                // first chunk: exp(-inf) = 0 against sums that are 0
+            double s = st[1] * f;
+            for (int tl = 0; tl < tcn; ++tl) {
+                const double w = exp(row_a[tl] - nm);
+                wt[tl] = w;
+                s += w;
+            }
+            st[0] = nm; st[1] = s; st[2] = f;
+        }
+        __syncthreads();
+        for (int i = tid; i < tcn * C; i += NLL_THREADS) {
+            const int tl = i / C, c = i - tl * C;
+            const double hot = c == y ? 1.0 : 0.0;
+            pe[tl * CS + c] = wt[tl] * (pe[tl * CS + c] / row_s[tl] - hot);
+        }
+        __syncthreads();
+        const bool first = t0 == 0, last = t0 + TC >= T;
+        const double f = st[2], S = st[1];
+        for (int k = tid; k < NK; k += NLL_THREADS) {
+            double g = first ? 0.0 : out[1 + k] * f;     // (this thread's own store of the previous chunk)
+            if (k < C * C) {
+                const int c = k / C, j = k - c * C;
+                for (int tl = 0; tl < tcn; ++tl) {
+                    const double term = pe[tl * CS + c] * (double)slab[tl * CS + j];
+                    g = g + term;
+                }
+            } else {
+                const int c = k - C * C;
+                for (int tl = 0; tl < tcn; ++tl) g += pe[tl * CS + c];
+            }
+            out[1 + k] = last ? g / S : g;
+        }
+    }
+    __syncthreads();
+    if (tid == 0) out[0] = -((st[0] + log(st[1])) - log((double)T));
+}
+
+// nll[e] / grad_matrix[e][c][j] / grad_bias[e][c] += sum_b terms[e][b][k], one wavefront per (e, k), in nll_sum_kernel's fixed order
+__global__ __launch_bounds__(64) void nll_mat_sum_kernel(const double* __restrict__ terms, int B, int C, double* __restrict__ nll,
+                                                         double* __restrict__ grad_matrix, double* __restrict__ grad_bias) {
+    const int lane = threadIdx.x, k = blockIdx.x, e = blockIdx.y;
+    const int CC = C * C;
+    const size_t row = (size_t)(CC + C + 1);
+    const double* t = terms + (size_t)e * B * row + k;
+    double s = 0.0;
+    for (int b = lane; b < B; b += 64) s += t[(size_t)b * row];
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m);
+    if (lane == 0) {
+        if (k == 0) nll[e] += s;
+        else if (k <= CC) grad_matrix[(size_t)e * CC + k - 1] += s;
+        else grad_bias[(size_t)e * C + k - 1 - CC] += s;
+    }
+}
+
+bool nll_matrix_takes(int E, int B, int C) {
+    return E >= 1 && B >= 1 && C >= 1 && C <= NLLM_MAX_C && E <= 65535;
+}
+
+int launch_nll_matrix_scaling_grad(const float* logits, int T, int E, int B, int C, const int* labels, const double* matrix, const double* bias,
+                                   double* nll, double* grad_matrix, double* grad_bias, double* scratch, hipStream_t s) {
+    if (!nll_matrix_takes(E, B, C)) return BMI_ERR_UNSUPPORTED;
+    const int CS = C | 1;                                // odd row stride
+    const int TC = min(T, min(NLLM_ROWS, NLLM_SLAB / CS));           // >= 1: CS <= 129
+    int L = 1;
+    while (L < C && L < 64) L <<= 1;
+    hipLaunchKernelGGL(nll_mat_terms_kernel, dim3((unsigned)B, (unsigned)E), dim3(NLL_THREADS), 0, s, logits, T, E, B, C, CS, TC, L, labels, matrix,
+                       bias, scratch);
+    BMI_CHECK_LAUNCH();
+    hipLaunchKernelGGL(nll_mat_sum_kernel, dim3((unsigned)(C * C + C + 1), (unsigned)E), dim3(64), 0, s, scratch, B, C, nll, grad_matrix, grad_bias);
+    BMI_CHECK_LAUNCH();
+    return BMI_OK;
+}

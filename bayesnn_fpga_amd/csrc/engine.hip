@@ -100,7 +100,7 @@ struct bmi_engine_s {
     size_t head_off = 0, head_part_bytes = 0;   // float64 partial sums of a head launch's 32-sample groups (joined in group order), one region per exit
     std::vector<std::pair<const float*, size_t>> perm;   // (bmi_plan) Masksembles tables (device pointer of the site) -> workspace offset of the permuted copy
     std::vector<float> tau;              // bmi_engine_set_temperature: the temperatures as given ([n_exits]; empty: never set = ones)
-    Calibration cal;                     // the calibration map in force (kernels.h): written by the three setters below, read by make_head_args and ensemble_add
+    Calibration cal;                     // the calibration map in force (kernels.h): written by the four setters below, read by make_head_args and ensemble_add
     std::vector<char> staged_ok;        // (bmi_plan) per first_exit: the staged suffix order keeps every shared workspace range's live ranges apart
     // profiling
     bool profiling = false;
@@ -988,7 +988,7 @@ int bmi_engine_set_temperature(bmi_handle h, const float* tau, int32_t n_exits) 
         if (!(inv > 0.f) || !std::isfinite(inv)) return BMI_ERR_INVALID;      // 1 / tau leaves the float32 range
         ones = ones && tau[i] == 1.f;
     }
-    if (!ones && h->cal.vec_scale) return BMI_ERR_INVALID;     // one calibration map at a time: clear the vector scaling first
+    if (!ones && (h->cal.vec_scale || h->cal.mat)) return BMI_ERR_INVALID;     // one calibration map at a time: clear the vector / matrix scaling first
     h->tau.assign(tau, tau + n_exits);
     h->cal.inv_tau.clear();
     if (!ones)
@@ -1013,9 +1013,22 @@ int bmi_engine_set_vector_scaling(bmi_handle h, const float* scale_device, const
     if (!h) return BMI_ERR_INVALID;
     if (!scale_device) { h->cal.vec_scale = h->cal.vec_bias = nullptr; return BMI_OK; }
     if (!bias_device || n_exits != h->n_exits || out_dim != h->out_dim) return BMI_ERR_INVALID;
-    if (!h->cal.inv_tau.empty()) return BMI_ERR_INVALID;
+    if (!h->cal.inv_tau.empty() || h->cal.mat) return BMI_ERR_INVALID;
     h->cal.vec_scale = scale_device;
     h->cal.vec_bias = bias_device;
+    return BMI_OK;
+}
+
+// A full [C][C] matrix and a bias per exit (caller-owned device arrays, used as given), or matrix_device NULL: off — the heads and the
+// ensemble launches are then the instantiations they were and every output keeps its bits.  Read at launch time: captured graphs keep what
+// was set at capture.  Refused while a temperature other than all ones or a vector scaling is in force (and both refuse while this is set).
+int bmi_engine_set_matrix_scaling(bmi_handle h, const float* matrix_device, const float* bias_device, int32_t n_exits, int32_t out_dim) {
+    if (!h) return BMI_ERR_INVALID;
+    if (!matrix_device) { h->cal.mat = h->cal.mat_bias = nullptr; return BMI_OK; }
+    if (!bias_device || n_exits != h->n_exits || out_dim != h->out_dim) return BMI_ERR_INVALID;
+    if (!h->cal.inv_tau.empty() || h->cal.vec_scale) return BMI_ERR_INVALID;
+    h->cal.mat = matrix_device;
+    h->cal.mat_bias = bias_device;
     return BMI_OK;
 }
 
@@ -1222,6 +1235,10 @@ HeadArgs make_head_args(bmi_engine_s* e, const Pass& p, const OpInfo& op, int N,
     if (e->cal.vec_scale) {                                                 // this exit's [C] rows
         a.vec_scale = e->cal.vec_scale + (size_t)d.out * e->out_dim;
         a.vec_bias = e->cal.vec_bias + (size_t)d.out * e->out_dim;
+    }
+    if (e->cal.mat) {                                                       // this exit's [C][C] matrix and [C] bias
+        a.mat = e->cal.mat + (size_t)d.out * e->out_dim * e->out_dim;
+        a.mat_bias = e->cal.mat_bias + (size_t)d.out * e->out_dim;
     }
     if (p.S1) {
         const size_t eo = (size_t)d.out * B * e->out_dim;
@@ -2061,7 +2078,7 @@ int bmi_finalize_ensemble_per_image(int32_t n_exits, int32_t batch, int32_t out_
                                               mutual_info, nonfinite, (hipStream_t)stream);
 }
 
-// bmi_ensemble_moments, _weighted and _vector: cal holds what the entry point was given beside tau (the weights, the vector scaling)
+// bmi_ensemble_moments, _weighted, _vector and _matrix: cal holds what the entry point was given beside tau (the weights, the vector scaling)
 static int ensemble_moments_entry(const float* logits, int32_t T, int32_t E, int32_t B, int32_t C, const float* tau, Calibration cal, double* Q1,
                                   double* Q2, double* QH, bmi_stream stream) {
     if (!logits || !Q1 || !Q2 || !QH || T < 1 || E < 1 || B < 1 || C < 1) return BMI_ERR_INVALID;
@@ -2095,6 +2112,29 @@ int bmi_ensemble_moments_vector(const float* logits, int32_t T, int32_t E, int32
     Calibration cal;
     cal.vec_scale = scale_device; cal.vec_bias = bias_device; cal.ens_w = W_device;
     return ensemble_moments_entry(logits, T, E, B, C, nullptr, cal, Q1, Q2, QH, stream);
+}
+
+int bmi_ensemble_moments_matrix(const float* logits, int32_t T, int32_t E, int32_t B, int32_t C, const float* matrix_device, const float* bias_device,
+                                const double* W_device, double* Q1, double* Q2, double* QH, bmi_stream stream) {
+    if (!matrix_device || !bias_device) return BMI_ERR_INVALID;
+    Calibration cal;
+    cal.mat = matrix_device; cal.mat_bias = bias_device; cal.ens_w = W_device;
+    return ensemble_moments_entry(logits, T, E, B, C, nullptr, cal, Q1, Q2, QH, stream);
+}
+
+size_t bmi_nll_matrix_scratch_bytes(int32_t E, int32_t B, int32_t C) {
+    if (E < 1 || B < 1 || C < 1) return 0;
+    return (size_t)E * B * ((size_t)C * C + (size_t)C + 1) * sizeof(double);
+}
+
+int bmi_nll_matrix_scaling_grad(const float* logits, int32_t T, int32_t E, int32_t B, int32_t C, const int32_t* labels, const double* matrix,
+                                const double* bias, double* nll, double* grad_matrix, double* grad_bias, void* scratch, size_t scratch_bytes,
+                                bmi_stream stream) {
+    if (!logits || !labels || !matrix || !bias || !nll || !grad_matrix || !grad_bias || !scratch || T < 1 || E < 1 || B < 1 || C < 1)
+        return BMI_ERR_INVALID;
+    if (!nll_matrix_takes(E, B, C)) return BMI_ERR_UNSUPPORTED;
+    if (scratch_bytes < bmi_nll_matrix_scratch_bytes(E, B, C)) return BMI_ERR_NOMEM;
+    return launch_nll_matrix_scaling_grad(logits, T, E, B, C, labels, matrix, bias, nll, grad_matrix, grad_bias, (double*)scratch, (hipStream_t)stream);
 }
 
 size_t bmi_nll_vector_scratch_bytes(int32_t E, int32_t B, int32_t C) {

@@ -41,13 +41,18 @@ struct EnsTau { float inv[BMI_ENS_MAX_EXITS]; };
 // VEC (bmi_engine_set_vector_scaling, bmi_ensemble_moments_vector): z_te,c = (double) fl32(fl32(l * vs[e][c]) + vb[e][c]), the vector-scaled head's
 // own number (two rounded fp32 operations: plain operators under this body's `fp contract(off)`), in place of fl32(l * inv_e); vs / vb are device fp32 [E_all][C], read where they are used (the static LDS is full: 3.2 KB at
 // E = 4, C = 100 are cache hits after the first row).  Not VEC: the code as it was, vs / vb are never read.
-// The body of both kernels below: the vector form is a kernel of its own name and arguments, so that the four older ones keep theirs.
-template <bool ROWS, bool WEIGHTED, bool VEC>
+// MAP == 2 (bmi_engine_set_matrix_scaling, bmi_ensemble_moments_matrix): z_te,c = (double) fl32((..(fl32(M[e][c][0] * l_0) + fl32(M[e][c][1] * l_1))
+// + ..) + vb[e][c]), j ascending, every operation rounded — the matrix-scaled head's own number; vs = M, device fp32 [E_all][C][C].  Formed ONCE
+// per row, by the lane that owns class c, and parked (exactly, as a float64) in the row's slot of ql, which phase B overwrites later; the
+// row of M is read through L1, the logits straight from the caller's array (a row is C floats: cache hits after the first class).
+// The body of the kernels below: the vector and the matrix forms are kernels of their own name and arguments, so that the four older ones keep theirs.
+template <bool ROWS, bool WEIGHTED, int MAP>
 __device__ __forceinline__ void ensemble_moments_body(const float* __restrict__ logits, int T, int E_all, int B, int C, int CS, int TS, int L,
                                                       const EnsTau& tau, double* __restrict__ Q1, double* __restrict__ Q2, double* __restrict__ QH,
                                                       const int* __restrict__ list, const int* __restrict__ n_e, const double* __restrict__ W,
                                                       const float* __restrict__ vs, const float* __restrict__ vb) {
 #pragma clang fp contract(off)
+    constexpr bool VEC = MAP == 1;
     __shared__ double pq[ENS_SLAB];                      // [row][CS], row = tl * E + e: exp(z - max), then q
     __shared__ double ql[ENS_SLAB];                      // q log q
     __shared__ double row_sum[ENS_ROWS], row_h[ENS_ROWS];
@@ -57,7 +62,7 @@ __device__ __forceinline__ void ensemble_moments_body(const float* __restrict__ 
     const int E = (ROWS && n_e) ? min(n_e[b], E_all) : E_all;       // the exits of THIS image (rows of the chunk: [tl][E])
     if (ROWS && (E < 1 || (unsigned)b >= (unsigned)B)) return;       // (the whole workgroup)
     const int lane = tid & (L - 1), grp = tid / L, ngrp = ENS_THREADS / L;
-    if (!VEC && tid < E) inv_s[tid] = tau.inv[tid];
+    if (MAP == 0 && tid < E) inv_s[tid] = tau.inv[tid];
     for (int t0 = 0; t0 < T; t0 += TS) {
         const int tn = min(TS, T - t0);
         const int rows = tn * E;                         // <= ENS_ROWS, rows * CS <= ENS_SLAB (the launcher's TS)
@@ -67,6 +72,34 @@ __device__ __forceinline__ void ensemble_moments_body(const float* __restrict__ 
             const bool live = r < rows;
             const int tl = live ? r / E : 0, e = live ? r - tl * E : 0;
             const float* src = logits + (((size_t)(t0 + tl) * E_all + e) * B + b) * C;
+            if constexpr (MAP == 2) {
+                const float* const mat = vs + (size_t)e * C * C;
+                const float* const bi = vb + (size_t)e * C;
+                float mx = -INFINITY;
+                if (live)
+                    for (int c = lane; c < C; c += L) {
+                        const float* const mrow = mat + (size_t)c * C;
+                        float acc = mrow[0] * src[0];
+                        for (int j = 1; j < C; ++j) {
+                            const float prod = mrow[j] * src[j];
+                            acc = acc + prod;
+                        }
+                        const float z = acc + bi[c];
+                        ql[r * CS + c] = (double)z;
+                        mx = fmaxf(mx, z);
+                    }
+                for (int m = L >> 1; m >= 1; m >>= 1) mx = fmaxf(mx, __shfl_xor(mx, m));
+                double s = 0.0;
+                if (live)
+                    for (int c = lane; c < C; c += L) {
+                        const double ex = exp(ql[r * CS + c] - (double)mx);
+                        pq[r * CS + c] = ex;
+                        s += ex;
+                    }
+                for (int m = L >> 1; m >= 1; m >>= 1) s += __shfl_xor(s, m);
+                if (live && lane == 0) row_sum[r] = s;
+                continue;
+            }
             const float inv = VEC ? 1.f : inv_s[e];
             const float* const sc = VEC ? vs + (size_t)e * C : nullptr;
             const float* const bi = VEC ? vb + (size_t)e * C : nullptr;
@@ -144,7 +177,7 @@ __global__ __launch_bounds__(ENS_THREADS) void ensemble_moments_kernel(const flo
                                                                        double* __restrict__ Q2, double* __restrict__ QH,
                                                                        const int* __restrict__ list, const int* __restrict__ n_e,
                                                                        const double* __restrict__ W) {
-    ensemble_moments_body<ROWS, WEIGHTED, false>(logits, T, E_all, B, C, CS, TS, L, tau, Q1, Q2, QH, list, n_e, W, nullptr, nullptr);
+    ensemble_moments_body<ROWS, WEIGHTED, 0>(logits, T, E_all, B, C, CS, TS, L, tau, Q1, Q2, QH, list, n_e, W, nullptr, nullptr);
 }
 
 template <bool ROWS, bool WEIGHTED>
@@ -154,18 +187,32 @@ __global__ __launch_bounds__(ENS_THREADS) void ensemble_moments_vec_kernel(const
                                                                            double* __restrict__ Q2, double* __restrict__ QH,
                                                                            const int* __restrict__ list, const int* __restrict__ n_e,
                                                                            const double* __restrict__ W) {
-    ensemble_moments_body<ROWS, WEIGHTED, true>(logits, T, E_all, B, C, CS, TS, L, EnsTau{}, Q1, Q2, QH, list, n_e, W, vs, vb);
+    ensemble_moments_body<ROWS, WEIGHTED, 1>(logits, T, E_all, B, C, CS, TS, L, EnsTau{}, Q1, Q2, QH, list, n_e, W, vs, vb);
+}
+
+template <bool ROWS, bool WEIGHTED>
+__global__ __launch_bounds__(ENS_THREADS) void ensemble_moments_mat_kernel(const float* __restrict__ logits, int T, int E_all, int B, int C, int CS,
+                                                                           int TS, int L, const float* __restrict__ mat,
+                                                                           const float* __restrict__ mb, double* __restrict__ Q1,
+                                                                           double* __restrict__ Q2, double* __restrict__ QH,
+                                                                           const int* __restrict__ list, const int* __restrict__ n_e,
+                                                                           const double* __restrict__ W) {
+    ensemble_moments_body<ROWS, WEIGHTED, 2>(logits, T, E_all, B, C, CS, TS, L, EnsTau{}, Q1, Q2, QH, list, n_e, W, mat, mb);
 }
 
 bool ensemble_takes(int E, int C) {
     return E >= 1 && C >= 1 && E <= BMI_ENS_MAX_EXITS && C <= BMI_ENS_MAX_CLASSES && E * (C | 1) <= ENS_SLAB;
 }
 
-// One of the eight kernels: the vector form (VEC) takes the two coefficient arrays where the tempered form takes the table of inverses
-template <bool VEC, bool ROWS, bool WEIGHTED>
+// One of the twelve kernels: the vector form (MAP 1) and the matrix form (MAP 2) take their two coefficient arrays where the tempered form
+// (MAP 0) takes the table of inverses
+template <int MAP, bool ROWS, bool WEIGHTED>
 static void launch_ens(unsigned grid, hipStream_t s, const float* logits, int T, int E, int B, int C, int CS, int TS, int L, const Calibration& cal,
                        const EnsTau& tau, const EnsRows& rows, double* Q1, double* Q2, double* QH) {
-    if constexpr (VEC)
+    if constexpr (MAP == 2)
+        hipLaunchKernelGGL((ensemble_moments_mat_kernel<ROWS, WEIGHTED>), dim3(grid), dim3(ENS_THREADS), 0, s, logits, T, E, B, C, CS, TS, L,
+                           cal.mat, cal.mat_bias, Q1, Q2, QH, rows.list, rows.n_e, cal.ens_w);
+    else if constexpr (MAP == 1)
         hipLaunchKernelGGL((ensemble_moments_vec_kernel<ROWS, WEIGHTED>), dim3(grid), dim3(ENS_THREADS), 0, s, logits, T, E, B, C, CS, TS, L,
                            cal.vec_scale, cal.vec_bias, Q1, Q2, QH, rows.list, rows.n_e, cal.ens_w);
     else
@@ -174,18 +221,19 @@ static void launch_ens(unsigned grid, hipStream_t s, const float* logits, int T,
 }
 
 // The one dispatch over (ROWS, WEIGHTED), for either form
-template <bool VEC, class... Args>
+template <int MAP, class... Args>
 static void dispatch_ens(bool by_rows, bool weighted, const Args&... args) {
-    if (by_rows && weighted) launch_ens<VEC, true, true>(args...);
-    else if (by_rows) launch_ens<VEC, true, false>(args...);
-    else if (weighted) launch_ens<VEC, false, true>(args...);
-    else launch_ens<VEC, false, false>(args...);
+    if (by_rows && weighted) launch_ens<MAP, true, true>(args...);
+    else if (by_rows) launch_ens<MAP, true, false>(args...);
+    else if (weighted) launch_ens<MAP, false, true>(args...);
+    else launch_ens<MAP, false, false>(args...);
 }
 
 int launch_ensemble_moments(const float* logits, int T, int E, int B, int C, const Calibration& cal, const EnsRows& rows, double* Q1, double* Q2,
                             double* QH, hipStream_t s) {
     if (T < 1 || B < 1 || (rows.list && (rows.Bc < 1 || rows.Bc > B))) return BMI_ERR_INVALID;
     if ((cal.vec_scale != nullptr) != (cal.vec_bias != nullptr) || (cal.vec_scale && !cal.inv_tau.empty())) return BMI_ERR_INVALID;
+    if ((cal.mat != nullptr) != (cal.mat_bias != nullptr) || (cal.mat && (cal.vec_scale || !cal.inv_tau.empty()))) return BMI_ERR_INVALID;
     if (!ensemble_takes(E, C)) return BMI_ERR_UNSUPPORTED;
     const int CS = C | 1;                                // odd row stride
     const int TS = std::min(ENS_SLAB / (E * CS), ENS_ROWS / E);      // >= 1 (ensemble_takes)
@@ -195,8 +243,9 @@ int launch_ensemble_moments(const float* logits, int T, int E, int B, int C, con
     for (int e = 0; e < BMI_ENS_MAX_EXITS; ++e) tau.inv[e] = e < E && e < (int)cal.inv_tau.size() ? cal.inv_tau[e] : 1.f;
     const bool by_rows = rows.list || rows.n_e, weighted = cal.ens_w != nullptr;
     const unsigned grid = (unsigned)(rows.list ? rows.Bc : B);
-    if (cal.vec_scale) dispatch_ens<true>(by_rows, weighted, grid, s, logits, T, E, B, C, CS, TS, L, cal, tau, rows, Q1, Q2, QH);
-    else dispatch_ens<false>(by_rows, weighted, grid, s, logits, T, E, B, C, CS, TS, L, cal, tau, rows, Q1, Q2, QH);
+    if (cal.mat) dispatch_ens<2>(by_rows, weighted, grid, s, logits, T, E, B, C, CS, TS, L, cal, tau, rows, Q1, Q2, QH);
+    else if (cal.vec_scale) dispatch_ens<1>(by_rows, weighted, grid, s, logits, T, E, B, C, CS, TS, L, cal, tau, rows, Q1, Q2, QH);
+    else dispatch_ens<0>(by_rows, weighted, grid, s, logits, T, E, B, C, CS, TS, L, cal, tau, rows, Q1, Q2, QH);
     BMI_CHECK_LAUNCH();
     return BMI_OK;
 }

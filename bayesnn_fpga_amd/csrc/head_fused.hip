@@ -28,6 +28,9 @@ void launch_head_rt_multi_temp(const HeadArgsPack& p, int n, hipStream_t s);
 // the vector-scaling instantiations (HeadArgs::vec_scale != null): head_fused_vec.hip
 void launch_head_rt_vec(const HeadArgs& a, hipStream_t s);
 void launch_head_rt_multi_vec(const HeadArgsPack& p, int n, hipStream_t s);
+// the matrix-scaling instantiations (HeadArgs::mat != null): head_fused_mat.hip
+void launch_head_rt_mat(const HeadArgs& a, hipStream_t s);
+void launch_head_rt_multi_mat(const HeadArgsPack& p, int n, hipStream_t s);
 
 // Joins the per-group partial sums of an image in GROUP ORDER into the caller's accumulators: with hardware float64 atomics the
 // groups met in whatever order the workgroups finished, and the last bit of the sums of more than 64 samples changed from run to
@@ -91,6 +94,7 @@ static int head_prepare(HeadArgs& a) {
     if (a.imap && (a.Bc <= 0 || a.Bc > a.B)) return BMI_ERR_INVALID;
     if (!(a.inv_tau >= 0.f) || a.inv_tau > 3.0e38f) return BMI_ERR_INVALID;       // 0: off; else a finite positive 1 / tau
     if ((a.vec_scale != nullptr) != (a.vec_bias != nullptr) || (a.vec_scale && a.inv_tau != 0.f)) return BMI_ERR_INVALID;   // one calibration map at a time
+    if ((a.mat != nullptr) != (a.mat_bias != nullptr) || (a.mat && (a.inv_tau != 0.f || a.vec_scale))) return BMI_ERR_INVALID;
     if (a.K % 32 != 0 || a.C > 128) return BMI_ERR_UNSUPPORTED;
     if (a.site_logits.kind != BMI_SITE_NONE && a.site_logits.kind != BMI_SITE_ELEMENTWISE) return BMI_ERR_UNSUPPORTED;
     return BMI_OK;
@@ -101,7 +105,8 @@ int launch_head_fused(const HeadArgs& a_in, hipStream_t s) {
     const int groups = (a.tc + 31) / 32;
     const int rcp = head_prepare(a);
     if (rcp != BMI_OK) return rcp;
-    if (a.vec_scale) launch_head_rt_vec(a, s);
+    if (a.mat) launch_head_rt_mat(a, s);
+    else if (a.vec_scale) launch_head_rt_vec(a, s);
     else if (a.inv_tau != 0.f) launch_head_rt_temp(a, s);
     else
         switch ((a.C + 31) / 32) {
@@ -133,14 +138,15 @@ int launch_head_fused_multi(const HeadArgs* list, int n, hipStream_t s) {
         const HeadArgs &x = p.a[i], &y = p.a[0];
         if (x.imap || x.C != y.C || x.in_kind != y.in_kind || x.B != y.B || x.tc != y.tc || (x.part != nullptr) != (y.part != nullptr) ||
             (x.S1 != nullptr) != (y.S1 != nullptr) || (x.SH != nullptr) != (y.SH != nullptr) || (x.inv_tau != 0.f) != (y.inv_tau != 0.f) ||
-            (x.vec_scale != nullptr) != (y.vec_scale != nullptr))
+            (x.vec_scale != nullptr) != (y.vec_scale != nullptr) || (x.mat != nullptr) != (y.mat != nullptr))
             return BMI_ERR_UNSUPPORTED;
         for (int j = 0; j < i; ++j)
             if (x.part && x.part == p.a[j].part) return BMI_ERR_INVALID;
     }
     for (int i = n; i < BMI_HEAD_PACK_MAX; ++i) p.a[i] = p.a[0];
     const HeadArgs& a = p.a[0];
-    if (a.vec_scale) launch_head_rt_multi_vec(p, n, s);
+    if (a.mat) launch_head_rt_multi_mat(p, n, s);
+    else if (a.vec_scale) launch_head_rt_multi_vec(p, n, s);
     else if (a.inv_tau != 0.f) launch_head_rt_multi_temp(p, n, s);
     else
         switch ((a.C + 31) / 32) {

@@ -1,7 +1,7 @@
 // The exit head's kernel body, its two kernel templates and their launch switches (head_fused.hip has the description): shared by
 // head_fused.hip, which instantiates the untempered kernels (TEMP = false — the instantiations, registers and bits of an engine without a
 // temperature), head_fused_temp.hip, which instantiates the tempered ones in a translation unit of its own (they compile side by side), and
-// head_fused_vec.hip, which does the same for the vector-scaling kernels.
+// head_fused_vec.hip and head_fused_mat.hip, which do the same for the vector-scaling and the matrix-scaling kernels.
 #pragma once
 #include <cstdlib>
 
@@ -43,11 +43,28 @@ __device__ __forceinline__ float head_scale_bias(float l, float a, float b) {
     const float prod = l * a;
     return prod + b;
 }
+// one term of the matrix-scaled logit, acc = fl32(acc + fl32(m * l)): a rounded product and a rounded sum, for the same reason
+__device__ __forceinline__ float head_mat_step(float acc, float m, float l) {
+#pragma clang fp contract(off)
+    const float prod = m * l;
+    return acc + prod;
+}
+__device__ __forceinline__ float head_add(float acc, float b) {
+#pragma clang fp contract(off)
+    return acc + b;
+}
 
 // TEMP == 2: vector scaling (HeadArgs::vec_scale != null, bmi_engine_set_vector_scaling) — at the same place z_c = fl32(fl32(l_c * a_c) + b_c)
 // with this exit's per-class scale a and bias b, two rounded fp32 operations; everything behind it is the tempered code on z (the max is
 // taken over z: the map is not monotone across classes).  The coefficients are read through L1 where they are used: wave 0 only, once
 // per workgroup, 2 * 16 * RT loads that die at once (held across the K loop they would cost that many registers).
+// TEMP == 3: matrix scaling (HeadArgs::mat != null, bmi_engine_set_matrix_scaling) — at the same place
+//     z_c = fl32( (..(fl32(M[c][0] * l_0) + fl32(M[c][1] * l_1)) + .. + fl32(M[c][C-1] * l_{C-1})) + b[c] ),   j ascending, every operation rounded
+// with this exit's [C][C] matrix (row = output class) and [C] bias: the order a float32 numpy loop reproduces exactly, and under which a
+// diagonal matrix gives vector scaling's bits (the off-diagonal products are +-0).  No MFMA: its accumulation order is not this one.  Wave 0
+// writes the raw logits of sample r to pb_l (each lane its own classes), then both lanes of the sample read all C of them back, one per
+// step of a rolled loop over j, and add the step's term to the 16 * RT classes they own; M[c][j] is read through L1 (the same address for
+// the 32 lanes of a half).  Everything behind it is the tempered code on z.
 template <int RT, int KIND, bool CSPLIT, bool ENT, int TEMP>
 __device__ __forceinline__ void head_body(const HeadArgs& a) {
     static_assert(!CSPLIT || (RT >= 3 && RT <= 4), "class split: one wave per class tile");
@@ -305,6 +322,56 @@ __device__ __forceinline__ void head_body(const HeadArgs& a) {
                         }
                     }
             }
+            if constexpr (TEMP == 3) {
+                const float* const mm = a.mat;
+                const float* const mb = a.mat_bias;
+#pragma unroll
+                for (int i = 0; i < RT; ++i)
+#pragma unroll
+                    for (int e = 0; e < 16; ++e) {
+                        const int c = 32 * i + (e & 3) + 8 * (e >> 2) + 4 * hh;
+                        if (c < C) pb_l[c * 33 + r] = acc[i][e];
+                    }
+                // the other lane of sample r wrote half of column r: the LDS operations of one wave complete in order, the fences keep the
+                // compiler from moving the loads below above the stores above
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                // Row c = c0 + 4 * hh of M, c0 = 32 * i + (e & 3) + 8 * (e >> 2): a pointer that is the same for the whole wave plus one
+                // 32-bit offset per lane (the lane half's 4 rows, and j) — 64 addresses of their own per step would not fit the class-split
+                // kernels' 256 registers.  Only the LAST class tile can hold classes >= C: its lanes walk row min(c, C - 1) instead
+                // (loads inside the matrix, results that nothing below reads).
+                const unsigned half_off = (unsigned)(4 * hh * C);
+                const float l0 = pb_l[r];
+#pragma unroll
+                for (int i = 0; i < RT; ++i)
+#pragma unroll
+                    for (int e = 0; e < 16; ++e) {
+                        const int c0 = 32 * i + (e & 3) + 8 * (e >> 2);
+                        if (i < RT - 1) acc[i][e] = head_scale((mm + (size_t)c0 * C)[half_off], l0);
+                        else acc[i][e] = head_scale(mm[(unsigned)(min(c0 + 4 * hh, C - 1) * C)], l0);
+                    }
+#pragma unroll 1
+                for (int j = 1; j < C; ++j) {
+                    const float lj = pb_l[j * 33 + r];
+                    const unsigned off = half_off + (unsigned)j;
+#pragma unroll
+                    for (int i = 0; i < RT; ++i)
+#pragma unroll
+                        for (int e = 0; e < 16; ++e) {
+                            const int c0 = 32 * i + (e & 3) + 8 * (e >> 2);
+                            if (i < RT - 1) acc[i][e] = head_mat_step(acc[i][e], (mm + (size_t)c0 * C)[off], lj);
+                            else acc[i][e] = head_mat_step(acc[i][e], mm[(unsigned)(min(c0 + 4 * hh, C - 1) * C + j)], lj);
+                        }
+                }
+#pragma unroll
+                for (int i = 0; i < RT; ++i)
+#pragma unroll
+                    for (int e = 0; e < 16; ++e) {
+                        const int c = min(32 * i + (e & 3) + 8 * (e >> 2) + 4 * hh, C - 1);
+                        acc[i][e] = head_add(acc[i][e], mb[c]);
+                    }
+            }
             if constexpr (TEMP == 1) {
                 // the raw logits go to pb_l now (the pass below stores them otherwise); one rounded fp32 product per logit — never
                 // contracted into the subtraction of the max, so that z is the number a host restatement computes
@@ -427,6 +494,11 @@ template <int RT, int KIND, bool CSPLIT = false, bool ENT = false>
 __global__ __launch_bounds__(256, CSPLIT ? 2 : 1) void head_fused_vec_kernel(HeadArgs a) {
     head_body<RT, KIND, CSPLIT, ENT, 2>(a);
 }
+// the matrix-scaling twin (head_fused_mat.hip)
+template <int RT, int KIND, bool CSPLIT = false, bool ENT = false>
+__global__ __launch_bounds__(256, CSPLIT ? 2 : 1) void head_fused_mat_kernel(HeadArgs a) {
+    head_body<RT, KIND, CSPLIT, ENT, 3>(a);
+}
 
 // Several exit heads in ONE launch (round 6): with exit-only dropout — the configuration every run of the paper uses,
 // Software_Artifact/script_figs/journal_script.sh:10-63 — the whole network is the once-per-batch prefix and the sample-folded suffix is
@@ -442,16 +514,22 @@ template <int RT, int KIND, bool CSPLIT = false, bool ENT = false>
 __global__ __launch_bounds__(256, CSPLIT ? 2 : 1) void head_fused_multi_vec_kernel(HeadArgsPack p) {
     head_body<RT, KIND, CSPLIT, ENT, 2>(p.a[blockIdx.z]);     // every head of the pack carries its own exit's coefficient rows
 }
+template <int RT, int KIND, bool CSPLIT = false, bool ENT = false>
+__global__ __launch_bounds__(256, CSPLIT ? 2 : 1) void head_fused_multi_mat_kernel(HeadArgsPack p) {
+    head_body<RT, KIND, CSPLIT, ENT, 3>(p.a[blockIdx.z]);     // (its own exit's matrix and bias)
+}
 
-// TP: 0 untempered, 1 scalar temperature, 2 vector scaling — the kernel of one (class tiles, input kind, class split, entropy) form
+// TP: 0 untempered, 1 scalar temperature, 2 vector scaling, 3 matrix scaling — the kernel of one (class tiles, input kind, class split, entropy) form
 template <int RT, int KIND, bool CS, bool EN, int TP>
 static constexpr auto head_kernel_of() {
-    if constexpr (TP == 2) return &head_fused_vec_kernel<RT, KIND, CS, EN>;
+    if constexpr (TP == 3) return &head_fused_mat_kernel<RT, KIND, CS, EN>;
+    else if constexpr (TP == 2) return &head_fused_vec_kernel<RT, KIND, CS, EN>;
     else return &head_fused_kernel<RT, KIND, CS, EN, TP == 1>;
 }
 template <int RT, int KIND, bool CS, bool EN, int TP>
 static constexpr auto head_multi_kernel_of() {
-    if constexpr (TP == 2) return &head_fused_multi_vec_kernel<RT, KIND, CS, EN>;
+    if constexpr (TP == 3) return &head_fused_multi_mat_kernel<RT, KIND, CS, EN>;
+    else if constexpr (TP == 2) return &head_fused_multi_vec_kernel<RT, KIND, CS, EN>;
     else return &head_fused_multi_kernel<RT, KIND, CS, EN, TP == 1>;
 }
 

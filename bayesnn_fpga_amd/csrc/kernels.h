@@ -128,6 +128,9 @@ struct HeadArgs {   // fused exit head (head_fused.hip)
                           // z = logit * inv_tau, SL and `logits` stay the raw logit — or 0: off, the untempered instantiations (appended as SH was)
     const float* vec_scale; // vector scaling (bmi_engine_set_vector_scaling): this exit's device fp32 [C] rows — z_c = fl32(fl32(logit_c * vec_scale[c]) +
     const float* vec_bias;  // vec_bias[c]) in place of the tempered z — or null: off (both or neither; never with inv_tau != 0; appended as inv_tau was)
+    const float* mat;       // matrix scaling (bmi_engine_set_matrix_scaling): this exit's device fp32 [C][C] matrix (row = output class) and [C] bias —
+    const float* mat_bias;  // z_c = fl32((..(fl32(mat[c][0] * l_0) + fl32(mat[c][1] * l_1)) + ..) + mat_bias[c]), j ascending, every operation rounded — or
+                            // null: off (both or neither; never with inv_tau != 0 or vec_scale; appended as vec_scale was)
 };
 int launch_head_fused(const HeadArgs& a, hipStream_t s);
 #define BMI_HEAD_PACK_MAX 8
@@ -198,6 +201,12 @@ int launch_nll_ensemble_temperature_grid(const float* logits, int T, int E, int 
 bool nll_vector_takes(int E, int B, int C);
 int launch_nll_vector_scaling_grad(const float* logits, int T, int E, int B, int C, const int* labels, const double* scale, const double* bias,
                                    double* nll, double* grad_scale, double* grad_bias, double* scratch, hipStream_t s);
+// calibration.hip (bmi_nll_matrix_scaling_grad): nll [E], grad_matrix [E][C][C], grad_bias [E][C] += value and gradient of the per-exit NLL of the
+// T-mean softmax of z_c = ((0 + (double)l_0 * matrix[e][c][0]) + ...) + bias[e][c] (device float64); scratch: [E][B][C * C + C + 1] float64
+// per-image terms.  BMI_ERR_UNSUPPORTED (nothing launched) for the shapes nll_matrix_takes refuses (C > 128, E > 65535)
+bool nll_matrix_takes(int E, int B, int C);
+int launch_nll_matrix_scaling_grad(const float* logits, int T, int E, int B, int C, const int* labels, const double* matrix, const double* bias,
+                                   double* nll, double* grad_matrix, double* grad_bias, double* scratch, hipStream_t s);
 // ensemble.hip (bmi_ensemble_moments): Q1 / Q2 [E][B][C] and QH [E][B] += the moments and the entropy of the per-sample exit ensembles
 // q_te = mean_{i<=e} softmax(fl32(l_ti * inv_tau[i])) of logits [T][E][B][C], in sample order onto the running sums
 #define BMI_ENS_MAX_EXITS 32
@@ -209,11 +218,14 @@ bool ensemble_takes(int E, int C);
 //   inv_tau    host [E]: float32(1 / (double)tau[e]), what the heads and the ensemble members multiply by; EMPTY: off (never set, or all ones)
 //   vec_scale / vec_bias   the caller's DEVICE fp32 [E][C] (not owned; both or neither), null: off; never together with a non-empty inv_tau:
 //              z = fl32(fl32(l * vec_scale[e][c]) + vec_bias[e][c]) in place of the tempered product
+//   mat / mat_bias   the caller's DEVICE fp32 [E][C][C] and [E][C] (not owned; both or neither), null: off; never together with a non-empty inv_tau
+//              or a vec_scale: z_c = fl32((..(fl32(mat[e][c][0] * l_0) + fl32(mat[e][c][1] * l_1)) + ..) + mat_bias[e][c]), j ascending
 //   ens_w      the caller's DEVICE float64 [E][E] row-major (not owned), null: the equal-weight mean above; q_te = sum_{i<=e} W[e][i] p_ti in
 //              exit order, the weights as given; of image b only the rows e < n_e[b] are read
 struct Calibration {
     std::vector<float> inv_tau;
     const float *vec_scale = nullptr, *vec_bias = nullptr;
+    const float *mat = nullptr, *mat_bias = nullptr;
     const double* ens_w = nullptr;
 };
 // EnsRows (device int32, each null: not used): the launch covers the Bc images list[0 .. Bc-1] of the batch only, and of image b only its first

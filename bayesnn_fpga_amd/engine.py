@@ -383,6 +383,34 @@ def check_vector_scaling(scale, bias, n_exits, out_dim):
     return out[0], out[1]
 
 
+def check_matrix_scaling(matrix, bias, n_exits, out_dim):
+    """Matrix scaling as two C-contiguous float32 arrays (matrix [E, C, C] — row = output class —, bias [E, C]), or (None, None) when
+    ``matrix`` is None (off).  ``matrix``: [E, C, C], or [C, C] for every exit; ``bias``: [E, C], or [C] for every exit, None = zeros.
+    Raises ValueError for any other shape, for a bias without a matrix and for a value that is not finite (in float32, what the device
+    is given).  No sign constraint.  Host only."""
+    if matrix is None:
+        if bias is not None:
+            raise ValueError("matrix scaling: a bias needs a matrix")
+        return None, None
+    E, Cd = int(n_exits), int(out_dim)
+    out = []
+    for name, v, tail in (("matrix", matrix, (Cd, Cd)), ("bias", bias, (Cd,))):
+        if v is None:
+            out.append(np.zeros((E,) + tail, dtype=np.float32))
+            continue
+        raw = np.asarray(v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v, dtype=np.float64)
+        if raw.shape == tail:
+            raw = np.broadcast_to(raw, (E,) + tail)
+        elif raw.shape != (E,) + tail:
+            raise ValueError(f"matrix scaling: {name} must be {[E, *tail]} or {list(tail)} for {E} exits of {Cd} classes, got {list(raw.shape)}")
+        with np.errstate(over="ignore"):
+            f32 = np.ascontiguousarray(raw, dtype=np.float32)
+        if not (np.all(np.isfinite(raw)) and np.all(np.isfinite(f32))):
+            raise ValueError(f"matrix scaling: every {name} value must be finite (in float32 too)")
+        out.append(f32)
+    return out[0], out[1]
+
+
 def vary_mask(vary, n_exits):
     """``vary`` of ensemble_nll_grid (an exit index, an iterable of indices, or None) as the bit mask bmi_nll_ensemble_temperature_grid
     takes; raises ValueError for an index outside [0, n_exits)."""
@@ -594,15 +622,22 @@ class MCDEngine(CompiledGraph):
         vs = getattr(model, "exit_vector_scaling", None)
         if vs is not None:
             self.set_vector_scaling(*vs)
+        # matrix scaling (EngineModelMixin.set_exit_matrix_scaling, train/calibration.py: MatrixScaling): the third map, never with the other two
+        self._mat_keep = []
+        ms = getattr(model, "exit_matrix_scaling", None)
+        if ms is not None:
+            self.set_matrix_scaling(*ms)
 
     ensemble_weights = None       # float64 [E, E] on the host, or None: the equal-weight mean (set_ensemble_weights)
     _vector_scaling = None        # (scale, bias) float32 [E, C] on the host, or None: off (set_vector_scaling)
+    _matrix_scaling = None        # (matrix [E, C, C], bias [E, C]) float32 on the host, or None: off (set_matrix_scaling)
 
     def close(self):
         self.__dict__.pop("_ens_scratch", None)      # (accumulate_ensemble's chunk of per-sample logits)
         super().close()                              # (the handle goes first: nothing reads the weight buffers any more)
         self.__dict__.pop("_ens_w_keep", None)
         self.__dict__.pop("_vec_keep", None)
+        self.__dict__.pop("_mat_keep", None)
 
     def set_vector_scaling(self, scale, bias=None):
         """Per-class scale and bias of every exit's logits (bmi_engine_set_vector_scaling; Guo et al. 2017): ``scale`` / ``bias`` as
@@ -619,6 +654,8 @@ class MCDEngine(CompiledGraph):
         else:
             if any(t != 1.0 for t in self.temperature):
                 raise ValueError("vector scaling: a temperature is set on this engine (set_temperature(None) first: one calibration map at a time)")
+            if self._matrix_scaling is not None:
+                raise ValueError("vector scaling: a matrix scaling is set on this engine (set_matrix_scaling(None) first: one calibration map at a time)")
             bufs = (torch.from_numpy(a).to(self.device), torch.from_numpy(b).to(self.device))
             self._vec_keep.append(bufs)              # never freed before close(): a captured launch may still hold an earlier pointer
             rc = self.lib.bmi_engine_set_vector_scaling(self.handle, C.c_void_p(bufs[0].data_ptr()), C.c_void_p(bufs[1].data_ptr()), self.n_exits,
@@ -631,10 +668,42 @@ class MCDEngine(CompiledGraph):
         """The vector scaling in force: (scale, bias), float32 [E, C] host arrays, or None when off."""
         return self._vector_scaling
 
+    def set_matrix_scaling(self, matrix, bias=None):
+        """A full [C, C] matrix and a bias on every exit's logits (bmi_engine_set_matrix_scaling; Guo et al. 2017): ``matrix`` / ``bias`` as
+        ``check_matrix_scaling`` takes them — [E, C, C] or [C, C] for every exit, row = output class; ``bias`` [E, C], [C] or None = zeros — or
+        ``matrix`` None: off.  From the next launch on every path through the fused head and the exit-ensemble launches computes softmax,
+        mean, var, the entropies and the decisions of ``z = M l + b`` in the head's fp32 — per class the products in ascending j, each
+        rounded, added one by one, the bias last (``train.calibration.matrix_logits`` restates it exactly; a diagonal matrix gives
+        ``set_vector_scaling``'s bits).  ``logit_mean``, ``forward_once`` and ``forward_samples`` stay the raw logits.  Off, the engine launches
+        the kernels it did.  One calibration map at a time: ValueError while a temperature (other than all ones) or a vector scaling is set.
+        The arrays live in device buffers the engine keeps until ``close()``; a hipGraph captured earlier keeps what it was captured with
+        (``BatchesInFlight.set_matrix_scaling`` discards them)."""
+        m, b = check_matrix_scaling(matrix, bias, self.n_exits, self.out_dim)
+        if m is None:
+            rc = self.lib.bmi_engine_set_matrix_scaling(self.handle, None, None, 0, 0)
+        else:
+            if any(t != 1.0 for t in self.temperature):
+                raise ValueError("matrix scaling: a temperature is set on this engine (set_temperature(None) first: one calibration map at a time)")
+            if self._vector_scaling is not None:
+                raise ValueError("matrix scaling: a vector scaling is set on this engine (set_vector_scaling(None) first: one calibration map at a time)")
+            bufs = (torch.from_numpy(m).to(self.device), torch.from_numpy(b).to(self.device))
+            self._mat_keep.append(bufs)              # never freed before close(): a captured launch may still hold an earlier pointer
+            rc = self.lib.bmi_engine_set_matrix_scaling(self.handle, C.c_void_p(bufs[0].data_ptr()), C.c_void_p(bufs[1].data_ptr()), self.n_exits,
+                                                        self.out_dim)
+        _lib.check(rc, "bmi_engine_set_matrix_scaling")
+        self._matrix_scaling = None if m is None else (m, b)
+
+    @property
+    def matrix_scaling(self):
+        """The matrix scaling in force: (matrix [E, C, C], bias [E, C]), float32 host arrays, or None when off."""
+        return self._matrix_scaling
+
     def set_temperature(self, tau):
         tau = check_temperature(tau, self.n_exits)
         if self._vector_scaling is not None and tau is not None and any(t != 1.0 for t in tau):
             raise ValueError("temperature: a vector scaling is set on this engine (set_vector_scaling(None) first: one calibration map at a time)")
+        if self._matrix_scaling is not None and tau is not None and any(t != 1.0 for t in tau):
+            raise ValueError("temperature: a matrix scaling is set on this engine (set_matrix_scaling(None) first: one calibration map at a time)")
         super().set_temperature(tau)
     set_temperature.__doc__ = CompiledGraph.set_temperature.__doc__
 
@@ -863,19 +932,25 @@ class MCDEngine(CompiledGraph):
         self.accumulate_ensemble(x, S, H, Q, QH, t_begin, T, seed, cnt0)
         return self.finalize_ensemble(S, H, Q, QH, T)
 
-    def ensemble_moments(self, logits, tau=None, out=None, t_before=0, weights=None, scale=None, bias=None):
+    def ensemble_moments(self, logits, tau=None, out=None, t_before=0, weights=None, scale=None, bias=None, matrix=None):
         """The exit-ensemble read-out of per-sample logits the caller holds (bmi_ensemble_moments + bmi_finalize_ensemble): ``logits`` fp32
         [T, E, B, C] on the engine's device (``forward_samples``), ``tau`` None, a scalar or E temperatures (independent of the one set on
         this engine).  Returns the five ``ens_*`` entries of ``finalize_ensemble`` plus the sums ``Q`` [2, E, B, C] and ``QH`` [E, B];
         ``out=(Q, QH)`` ADDS into the sums of earlier calls that held ``t_before`` samples — the same bits as one call on all of them —
         and the results describe all ``t_before + T``.  ``weights`` (``check_ensemble_weights``: None, [E] or [E, E]; independent of the ones
         set on this engine): the weighted ensembles, bmi_ensemble_moments_weighted.  ``scale`` / ``bias`` (``check_vector_scaling``; not together
-        with ``tau``): the members under a vector scaling, bmi_ensemble_moments_vector, with or without ``weights``.
+        with ``tau``): the members under a vector scaling, bmi_ensemble_moments_vector, with or without ``weights``.  ``matrix`` / ``bias``
+        (``check_matrix_scaling``; not together with ``tau`` or ``scale``): the members under a matrix scaling, bmi_ensemble_moments_matrix.
         ``train.uncertainty.decompose_ensemble_logits`` is the host restatement."""
         T, E, B, Cd = check_buffer(logits, (None,) * 4, torch.float32, self.device, "logits [T, E, B, C]").shape
         tau = check_temperature(tau, E)
         W = check_ensemble_weights(weights, E)
-        va, vb = check_vector_scaling(scale, bias, E, Cd)
+        if matrix is not None:
+            if tau is not None or scale is not None:
+                raise ValueError("ensemble_moments: matrix and tau / scale are mutually exclusive")
+            va, vb = check_matrix_scaling(matrix, bias, E, Cd)
+        else:
+            va, vb = check_vector_scaling(scale, bias, E, Cd)
         if va is not None and tau is not None:
             raise ValueError("ensemble_moments: tau and scale / bias are mutually exclusive")
         if out is None:
@@ -891,7 +966,7 @@ class MCDEngine(CompiledGraph):
             a_dev, b_dev, w_dev = (None if a is None else torch.from_numpy(a).to(self.device) for a in (va, vb, W))
             ptr = lambda t: None if t is None else t.data_ptr()
             if va is not None:
-                name, cal = "bmi_ensemble_moments_vector", (ptr(a_dev), ptr(b_dev), ptr(w_dev))
+                name, cal = "bmi_ensemble_moments_matrix" if matrix is not None else "bmi_ensemble_moments_vector", (ptr(a_dev), ptr(b_dev), ptr(w_dev))
             elif W is not None:
                 name, cal = "bmi_ensemble_moments_weighted", (tau_c, ptr(w_dev))
             else:
@@ -1188,6 +1263,33 @@ class MCDEngine(CompiledGraph):
         _lib.check(rc, "bmi_nll_vector_scaling_grad")
         return out
 
+    def nll_matrix_grad(self, logits, labels, matrix, bias, out=None):
+        """Value and gradient of a matrix-scaling fit on the device (bmi_nll_matrix_scaling_grad): ``logits`` / ``labels`` as ``nll_grid``'s,
+        ``matrix`` float64 [E, C, C] (row = output class) and ``bias`` float64 [E, C] (arrays or tensors; taken as float64: the optimiser's
+        point, not the head's float32).  ADDS, per exit, sum_b -log mean_t softmax(M l_tb + bias)[y_b] and its gradients into ``out`` =
+        (nll [E], g_matrix [E, C, C], g_bias [E, C]), device float64 (zeros when None), and returns the triple: a walk over a loader
+        accumulates.  float64 throughout, the same bits on every run; ``train.calibration.nll_matrix_numpy`` is its host restatement.
+        Independent of what is set on this engine."""
+        T, E, B, Cd, labels = self._nll_args(logits, labels)
+        matrix = check_buffer(torch.as_tensor(matrix, dtype=torch.float64).to(self.device).contiguous(), (E, Cd, Cd), torch.float64, self.device,
+                              "matrix [E, C, C]")
+        bias = check_buffer(torch.as_tensor(bias, dtype=torch.float64).to(self.device).contiguous(), (E, Cd), torch.float64, self.device, "bias [E, C]")
+        shapes = ((E,), (E, Cd, Cd), (E, Cd))
+        if out is None:
+            out = tuple(torch.zeros(*shape, dtype=torch.float64, device=self.device) for shape in shapes)
+        elif len(out) != 3:
+            raise ValueError("out must be (nll [E], g_matrix [E, C, C], g_bias [E, C])")
+        else:
+            for o, shape, name in zip(out, shapes, ("out[0] (nll [E])", "out[1] (g_matrix [E, C, C])", "out[2] (g_bias [E, C])")):
+                check_buffer(o, shape, torch.float64, self.device, name)
+        scratch = self._scratch("_nll_scratch", int(self.lib.bmi_nll_matrix_scratch_bytes(E, B, Cd)))
+        with torch.cuda.device(self.device):
+            rc = self.lib.bmi_nll_matrix_scaling_grad(logits.data_ptr(), T, E, B, Cd, labels.data_ptr(), matrix.data_ptr(), bias.data_ptr(),
+                                                      out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), scratch.data_ptr(),
+                                                      scratch.numel(), self._stream())
+        _lib.check(rc, "bmi_nll_matrix_scaling_grad")
+        return out
+
     def ensemble_nll_grid(self, logits, labels, tau, vary, cand, out=None):
         """The objective of a joint temperature fit of the exit ensembles on the device (bmi_nll_ensemble_temperature_grid): ``logits`` /
         ``labels`` as ``nll_grid``'s, ``tau`` the current temperatures (one per exit, a scalar for all, None for ones), ``vary`` the exits
@@ -1380,6 +1482,16 @@ class BatchesInFlight:
         self.synchronize()
         for e in self.engines:
             e.set_vector_scaling(scale, bias)
+        for attr in ("_graphs", "_gstreams"):
+            if hasattr(self, attr):
+                delattr(self, attr)
+
+    def set_matrix_scaling(self, matrix, bias=None):
+        """``MCDEngine.set_matrix_scaling`` on every engine of the pipe; the captured hipGraphs are discarded (after a synchronize), like
+        ``set_vector_scaling``'s."""
+        self.synchronize()
+        for e in self.engines:
+            e.set_matrix_scaling(matrix, bias)
         for attr in ("_graphs", "_gstreams"):
             if hasattr(self, attr):
                 delattr(self, attr)

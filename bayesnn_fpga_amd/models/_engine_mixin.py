@@ -26,6 +26,7 @@ class EngineModelMixin:
     auto_tol = AUTO_TOL
     exit_temperature = None   # per-exit softmax temperatures (a plain list of floats: survives torch.save(model)), or None: off — set_exit_temperature
     exit_vector_scaling = None   # per-exit vector scaling (a pair of plain float32 arrays [E, C], scale and bias: survives torch.save(model)), or None: off — set_exit_vector_scaling; never together with exit_temperature
+    exit_matrix_scaling = None   # per-exit matrix scaling (a pair of plain float32 arrays, matrix [E, C, C] and bias [E, C]: survives torch.save(model)), or None: off — set_exit_matrix_scaling; never together with the two above
     exit_ensemble_weights = None   # the weights of the exit ensembles (a plain float64 array [E, E]: survives torch.save(model)), or None: the equal mean — set_exit_ensemble_weights
 
     def _init_engine_state(self):
@@ -72,6 +73,8 @@ class EngineModelMixin:
         tau = check_temperature(tau, model_exits(self))
         if tau is not None and self.exit_vector_scaling is not None:
             raise ValueError("set_exit_temperature: a vector scaling is set (set_exit_vector_scaling(None) first: one calibration map at a time)")
+        if tau is not None and self.exit_matrix_scaling is not None:
+            raise ValueError("set_exit_temperature: a matrix scaling is set (set_exit_matrix_scaling(None) first: one calibration map at a time)")
         self.exit_temperature = tau
         self._drop_engines()
 
@@ -86,7 +89,25 @@ class EngineModelMixin:
         a, b = check_vector_scaling(scale, bias, model_exits(self), int(self.out_dim))
         if a is not None and self.exit_temperature is not None:
             raise ValueError("set_exit_vector_scaling: a temperature is set (set_exit_temperature(None) first: one calibration map at a time)")
+        if a is not None and self.exit_matrix_scaling is not None:
+            raise ValueError("set_exit_vector_scaling: a matrix scaling is set (set_exit_matrix_scaling(None) first: one calibration map at a time)")
         self.exit_vector_scaling = None if a is None else (a, b)
+        self._drop_engines()
+
+    def set_exit_matrix_scaling(self, matrix, bias=None):
+        """Per-exit matrix scaling of everything the engines compute from this model's softmax (``MCDEngine.set_matrix_scaling``: z = M l + b
+        in the head's fp32, the one map that moves probability mass between classes; mean, var, the entropies, the exit ensembles and the
+        decisions; never the logits): ``matrix`` [E, C, C], or [C, C] for every exit, row = output class; ``bias`` [E, C], [C] or None =
+        zeros; every value finite; ``matrix`` None = off; ``train.calibration.MatrixScaling`` fits it on a validation split.  Stored on the
+        model as two plain float32 arrays and treated like ``set_exit_temperature``: compiled engines, pipes and the "auto" decision are
+        dropped.  One calibration map at a time: ValueError while ``exit_temperature`` or ``exit_vector_scaling`` is set — clear it first."""
+        from ..engine import check_matrix_scaling, model_exits
+        m, b = check_matrix_scaling(matrix, bias, model_exits(self), int(self.out_dim))
+        if m is not None and self.exit_temperature is not None:
+            raise ValueError("set_exit_matrix_scaling: a temperature is set (set_exit_temperature(None) first: one calibration map at a time)")
+        if m is not None and self.exit_vector_scaling is not None:
+            raise ValueError("set_exit_matrix_scaling: a vector scaling is set (set_exit_vector_scaling(None) first: one calibration map at a time)")
+        self.exit_matrix_scaling = None if m is None else (m, b)
         self._drop_engines()
 
     def set_exit_ensemble_weights(self, w):

@@ -52,7 +52,19 @@ whose value and gradient come from the device in one call for all exits (``MCDEn
 * ``lbfgs_minimize``   — a small deterministic L-BFGS with Armijo backtracking, the exits as independent problems in the same evaluations.
 * ``VectorScaling``    — the loader-level fit, on the same walk as ``TemperatureScaling``, started at the scalar fit.
 
-THE ORDER: fit the temperatures (``TemperatureScaling`` or ``EnsembleTemperatureScaling``) OR the vector scaling (``VectorScaling``) first,
+Neither map can move probability mass BETWEEN classes: a model that systematically confuses class i with class j — what the early exits
+of a multi-exit network do — needs MATRIX SCALING (Guo et al. 2017), z = M l + b with a full [C, C] matrix per exit
+(``MCDEngine.set_matrix_scaling``: inside the fused head, per class the products in ascending j, each rounded to fp32, added one by one;
+mutually exclusive with the other two maps, which are its special cases).  Its C^2 + C parameters per exit overfit a small split, so the
+fit carries the off-diagonal and bias regulariser of Kull et al. 2019 (ODIR); the same bias term is ``VectorScaling.fit``'s ``bias_l2``.
+
+* ``matrix_z`` / ``matrix_logits`` — the fp32 z of the matrix-scaled head, exactly, and mean / var of its softmax.
+* ``nll_matrix_numpy`` — float64 restatement of the device objective (``MCDEngine.nll_matrix_grad``, bmi_nll_matrix_scaling_grad).
+* ``odir_penalty``     — the regulariser, value and gradients, host float64.
+* ``MatrixScaling``    — the loader-level fit, started at the vector fit; ``select`` picks the regulariser on a hold-out loader.
+
+THE ORDER: fit the temperatures (``TemperatureScaling`` or ``EnsembleTemperatureScaling``) OR the vector scaling (``VectorScaling``) OR the
+matrix scaling (``MatrixScaling``) first,
 ``apply()``, then fit the weights AT those members — they are then fixed and the problem is convex (``EnsembleWeights`` reads ``predict``'s
 means, so it needs no change: weights fitted after ``VectorScaling.apply()`` are fitted at the scaled members).  The joint temperature
 fit's objective stays the equal-weight ensemble's; a joint fit of weights and temperatures, or of weights and a vector scaling, is not built.
@@ -210,6 +222,103 @@ def nll_vector_numpy(logits, labels, scale, bias):
         gb[e] = d.sum((0, 1))
         ga[e] = (d * l).sum((0, 1))
     return nll, ga, gb
+
+
+def matrix_z(logits, matrix, bias=None):
+    """float32 [T, E, B, C]: the logits of ``logits`` [T, E, B, C] under a matrix scaling, bit for bit what the exit head forms
+    (csrc/head_fused_body.h, TEMP == 3): per output class c, acc = fl32(M[c][0] * l_0), then acc = fl32(acc + fl32(M[c][j] * l_j)) for j
+    ascending, then fl32(acc + b[c]) — a loop over j on float32 arrays (numpy rounds every elementwise operation, nothing is fused), not
+    ``@``, whose summation order is not this one.  ``matrix`` / ``bias`` as ``engine.check_matrix_scaling`` takes them."""
+    from ..engine import check_matrix_scaling
+    l = np.asarray(logits, dtype=np.float32)
+    if l.ndim != 4:
+        raise ValueError("logits must be [T, E, B, C]")
+    E, C = l.shape[1], l.shape[3]
+    M, b = check_matrix_scaling(matrix, bias, E, C)
+    if M is None:
+        return l
+    z = np.empty_like(l)
+    for e in range(E):
+        le = l[:, e]                                             # [T, B, C]
+        acc = (M[e][:, 0] * le[..., 0:1]).astype(np.float32)     # [T, B, C]: entry c = M[c][0] * l_0
+        for j in range(1, C):
+            acc = (acc + (M[e][:, j] * le[..., j:j + 1]).astype(np.float32)).astype(np.float32)
+        z[:, e] = (acc + b[e]).astype(np.float32)
+    return z
+
+
+def matrix_logits(logits, matrix, bias=None):
+    """(mean, var), float64 [E, B, C]: over the T samples of ``logits`` [T, E, B, C], the mean and the variance (ddof = 0) of
+    softmax(``matrix_z``) — the head's fp32 z exactly, the softmax in float64 like ``scale_logits``.  A diagonal matrix gives
+    ``scale_logits``' result bit for bit."""
+    z = matrix_z(logits, matrix, bias).astype(np.float64)
+    z -= z.max(-1, keepdims=True)
+    p = np.exp(z)
+    p /= p.sum(-1, keepdims=True)
+    return p.mean(0), p.var(0)
+
+
+def nll_matrix_numpy(logits, labels, matrix, bias):
+    """(nll [E], g_matrix [E, C, C], g_bias [E, C]), float64: value and gradient of sum_b -log mean_t softmax(M_e l_tb + bias_e)[y_b] for
+    ``logits`` [T, E, B, C], ``labels`` [B], ``matrix`` [E, C, C] (row = output class) and ``bias`` [E, C] taken as float64.
+    bmi_nll_matrix_scaling_grad's arithmetic:  z_c = ((0.0 + float64(l_0) * M[c][0]) + float64(l_1) * M[c][1] + ...) + b[c], a loop over j
+    ascending (not ``@``), so z is the kernel's;  A_t, term_b, r_t and p_t as in ``nll_vector_numpy``;  d_tc = r_t (p_tc - [c == y]):
+    d term / d b_c = sum_t d_tc,  d term / d M[c][j] = sum_t d_tc l_tj.  On a diagonal matrix the value, g_bias and the diagonal of g_matrix
+    are ``nll_vector_numpy``'s, exactly.  sum_c g_bias = 0 and sum_c g_matrix[c][j] = 0 identically (the softmax gauge)."""
+    logits = np.asarray(logits)
+    T, E, B, C = logits.shape
+    labels = np.asarray(labels).astype(np.int64).reshape(B)
+    if labels.min() < 0 or labels.max() >= C:
+        raise ValueError(f"labels must lie in [0, {C})")
+    M = np.asarray(matrix, dtype=np.float64)
+    b = np.asarray(bias, dtype=np.float64)
+    if M.shape != (E, C, C) or b.shape != (E, C):
+        raise ValueError(f"matrix must be [E, C, C] = [{E}, {C}, {C}] and bias [E, C] = [{E}, {C}]")
+    idx = np.arange(B)
+    hot = np.zeros((B, C))
+    hot[idx, labels] = 1.0
+    nll, gM, gb = np.zeros(E), np.zeros((E, C, C)), np.zeros((E, C))
+    for e in range(E):
+        l = logits[:, e].astype(np.float64)                      # [T, B, C]
+        z = np.zeros((T, B, C))
+        for j in range(C):
+            z = z + l[..., j:j + 1] * M[e][:, j]
+        z = z + b[e]
+        zmax = z.max(-1)
+        ex = np.exp(z - zmax[..., None])
+        s = ex.sum(-1)
+        A = (z[:, idx, labels] - zmax) - np.log(s)               # [T, B]
+        am = A.max(0)
+        w = np.exp(A - am)
+        S = w.sum(0)
+        nll[e] = np.sum(-((am + np.log(S)) - np.log(float(T))))
+        d = (w / S)[..., None] * (ex / s[..., None] - hot)        # [T, B, C]
+        gb[e] = d.sum((0, 1))
+        for j in range(C):                                       # (column j: the reduction nll_vector_numpy runs for its g_scale)
+            gM[e][:, j] = (d * l[..., j:j + 1]).sum((0, 1))
+    return nll, gM, gb
+
+
+def odir_penalty(matrix, bias, n, off_diag_l2=0.0, bias_l2=0.0):
+    """(value [E], grad_matrix [E, C, C], grad_bias [E, C]), host float64: the off-diagonal and bias regulariser of Kull et al. 2019 (ODIR)
+    on the MEAN NLL, times ``n`` because the device objective is a sum over the n images,
+        value_e = n ( off_diag_l2 / (C (C - 1)) sum_{c != j} M[e][c][j]^2  +  bias_l2 / C sum_c b[e][c]^2 ).
+    It depends on the parameters only.  ``matrix`` None (``VectorScaling``'s bias term): no matrix term, grad_matrix None.  Zero on a
+    diagonal matrix with ``bias_l2 = 0``."""
+    b = np.asarray(bias, dtype=np.float64)
+    E, C = b.shape
+    n = float(n)
+    value = n * (float(bias_l2) / C) * np.sum(b * b, axis=1)
+    gb = (2.0 * n * float(bias_l2) / C) * b
+    if matrix is None:
+        return value, None, gb
+    M = np.asarray(matrix, dtype=np.float64)
+    if M.shape != (E, C, C):
+        raise ValueError(f"matrix must be [E, C, C] = [{E}, {C}, {C}]")
+    off = M * (1.0 - np.eye(C))
+    lam = float(off_diag_l2) / (C * (C - 1)) if C > 1 else 0.0
+    value = value + n * lam * np.sum(off * off, axis=(1, 2))
+    return value, (2.0 * n * lam) * off, gb
 
 
 def lbfgs_minimize(fun, x0, max_iter=100, gtol=1e-6, history=10, c1=1e-4, max_backtracks=30):
@@ -523,13 +632,20 @@ class VectorScaling(TemperatureScaling):
     start's value (a fit that did not move), the rounded start is returned.  sum_c of the bias gradient is 0, so the bias stays in the
     zero-sum gauge it starts in.  Raw logits depend on neither a temperature nor a vector scaling set on the model: a fit can be repeated."""
 
-    def fit(self, max_iter=50, gtol=1e-5, history=10, **search):
+    def fit(self, max_iter=50, gtol=1e-5, history=10, bias_l2=0.0, **search):
         """Walk + scalar search (keyword arguments ``search`` go to ``zoom_search``) + L-BFGS.  Returns — and keeps in ``self.result`` —
         dict(scale, bias float32 [E, C]; nll_start (the scalar fit's NLL), nll_after, grad_norm (|g|_inf at the optimiser's last point),
-        iterations, converged [E] each; tau [E] (the scalar fit); n)."""
+        iterations, converged [E] each; tau [E] (the scalar fit); n).  ``bias_l2`` > 0: the optimiser's objective gains ``odir_penalty``'s
+        bias term, n bias_l2 / C sum_c b_c^2, added on the host; ``nll_after`` stays the unpenalised NLL, the result gains ``penalty``
+        [E], and the rounded start is kept when rounding lost ground on the PENALISED objective.  0.0: the fit as it was, the penalty is
+        never evaluated."""
         from ..engine import model_exits
         batches = self.collect()
         eng, E, C = self._engine, model_exits(self.model), int(self.model.out_dim)
+        n = int(sum(y.numel() for _, y in batches))
+        bias_l2 = float(bias_l2)
+        if bias_l2 < 0 or not np.isfinite(bias_l2):
+            raise ValueError("bias_l2 must be finite and >= 0")
 
         def eval_tau(tau):
             out = None
@@ -546,20 +662,31 @@ class VectorScaling(TemperatureScaling):
                 out = eng.nll_vector_grad(logits, y, a, b, out=out)
             return out[0].cpu().numpy(), np.concatenate([out[1].cpu().numpy(), out[2].cpu().numpy()], axis=1)
 
+        def eval_pen(x):                                         # (bias_l2 > 0 only)
+            f, g = eval_vec(x)
+            pv, _, pg = odir_penalty(None, x[:, C:], n, 0.0, bias_l2)
+            g[:, C:] += pg
+            return f + pv, g
+
         z = zoom_search(eval_tau, E, **search)
         inv = 1.0 / np.asarray(z["tau"], dtype=np.float32).astype(np.float64)
         x0 = np.concatenate([np.repeat(inv[:, None], C, axis=1), np.zeros((E, C))], axis=1)
-        r = lbfgs_minimize(eval_vec, x0, max_iter=max_iter, gtol=gtol, history=history)
+        r = lbfgs_minimize(eval_pen if bias_l2 else eval_vec, x0, max_iter=max_iter, gtol=gtol, history=history)
         x32 = r["x"].astype(np.float32)
         x032 = x0.astype(np.float32)
         nll_after = eval_vec(x32.astype(np.float64))[0]
         nll_x0 = eval_vec(x032.astype(np.float64))[0]
-        keep = nll_after <= nll_x0                               # (a fit that moved: always)
+        if bias_l2:
+            pen, pen0 = (odir_penalty(None, v[:, C:].astype(np.float64), n, 0.0, bias_l2)[0] for v in (x32, x032))
+            keep = nll_after + pen <= nll_x0 + pen0
+        else:
+            keep = nll_after <= nll_x0                           # (a fit that moved: always)
         x32 = np.where(keep[:, None], x32, x032)
         nll_after = np.where(keep, nll_after, nll_x0)
-        self.result = dict(scale=np.ascontiguousarray(x32[:, :C]), bias=np.ascontiguousarray(x32[:, C:]), nll_start=z["nll_after"], nll_after=nll_after,
+        extra = dict(penalty=np.where(keep, pen, pen0)) if bias_l2 else {}
+        self.result = dict(**extra, scale=np.ascontiguousarray(x32[:, :C]), bias=np.ascontiguousarray(x32[:, C:]), nll_start=z["nll_after"], nll_after=nll_after,
                            grad_norm=np.max(np.abs(r["g"]), axis=1), iterations=r["iterations"], converged=r["converged"],
-                           tau=np.asarray(z["tau"]), n=int(sum(y.numel() for _, y in batches)))
+                           tau=np.asarray(z["tau"]), n=n)
         return self.result
 
     def apply(self):
@@ -567,6 +694,7 @@ class VectorScaling(TemperatureScaling):
         if self.result is None:
             raise RuntimeError("fit() first")
         self.model.set_exit_temperature(None)
+        self.model.set_exit_matrix_scaling(None)
         self.model.set_exit_vector_scaling(self.result["scale"], self.result["bias"])
         return self.model.exit_vector_scaling
 
@@ -575,6 +703,142 @@ class VectorScaling(TemperatureScaling):
         if self.result is None:
             raise RuntimeError("fit() first")
         name = f"vector_scaling_{experiment_id}.npz"
+        np.savez(name, **{k: np.asarray(v) for k, v in self.result.items()})
+        return name
+
+
+class MatrixScaling(VectorScaling):
+    """Fits a full [C, C] matrix and a bias per exit (matrix scaling) on a labelled (validation) loader.
+
+        ms = MatrixScaling(model, val_loader, gpu=0, mc_passes=10)
+        ms.fit(off_diag_l2=1.0)       # dict(matrix, bias, nll_start, nll_after, penalty, grad_norm, iterations, converged, scale0, bias0, tau, n)
+        ms.select(holdout_loader)     # ... or let a hold-out split choose off_diag_l2
+        ms.apply()                    # clears temperature and vector scaling; model.set_exit_matrix_scaling(matrix, bias)
+
+    AN UNREGULARISED MATRIX FIT ON A SMALL SPLIT OVERFITS.  It has C^2 + C parameters per exit (10 100 at C = 100) and will drive the
+    training NLL towards 0 with off-diagonal entries of any size.  A CPU trial — C = 10, 48 images, T = 10, teacher labels from a banded
+    confusion matrix, two exits: training NLL 97.1 / 38.2 under the vector fit; the unpenalised matrix fit took it to 39.0 / 0.32 with an
+    off-diagonal rms of 47 and 11; off_diag_l2 = 1.0 gives 54.9 / 5.7 with rms 0.30; off_diag_l2 = 100 gives 86.3 / 30.9 with rms 0.03.
+    Use ``off_diag_l2`` > 0 (``odir_penalty``: Kull et al. 2019) and choose it with ``select`` on data the fit has not seen.
+
+    The walk and the ``max_logit_bytes`` rule are ``TemperatureScaling``'s.  ``fit`` runs the vector fit first, unregularised, exactly as
+    ``VectorScaling.fit`` does, starts at M = diag(scale), b = bias and runs ``lbfgs_minimize`` on the C^2 + C parameters of every exit, all
+    exits in the same ``MCDEngine.nll_matrix_grad`` launches (one per batch and evaluation), in float64; the penalty is added on the host.
+    The result is rounded to float32 once, ``nll_after`` is the UNPENALISED NLL at the rounded parameters, and the rounded start is kept
+    where rounding lost ground on the penalised objective.  With ``bias_l2 = 0`` the start has zero penalty and every accepted step lowers
+    the penalised objective, so ``nll_after <= nll_start`` for every ``off_diag_l2 >= 0``."""
+
+    _held = None          # (select) the collected batches, kept across the candidates' fits
+    _held_vec = None      # (select) the vector fit of those batches
+
+    def collect(self):
+        return self._held if self._held is not None else super().collect()
+
+    def _eval_matrix(self, batches, x, C):
+        """Unpenalised (nll [E], grad [E, C * C + C]) of the point x [E, C * C + C] = (matrix rows, bias) over ``batches``, on the device."""
+        E = x.shape[0]
+        M = torch.from_numpy(np.ascontiguousarray(x[:, :C * C]).reshape(E, C, C)).to(self.device)
+        b = torch.from_numpy(np.ascontiguousarray(x[:, C * C:])).to(self.device)
+        out = None
+        for logits, y in batches:
+            out = self._engine.nll_matrix_grad(logits, y, M, b, out=out)
+        return out[0].cpu().numpy(), np.concatenate([out[1].cpu().numpy().reshape(E, C * C), out[2].cpu().numpy()], axis=1)
+
+    def fit(self, off_diag_l2=0.0, bias_l2=0.0, max_iter=50, gtol=1e-5, history=10, **search):
+        """Walk + vector fit (``VectorScaling.fit(max_iter, gtol, history, **search)``, unregularised) + L-BFGS on the matrix.  Returns — and
+        keeps in ``self.result`` — dict(matrix float32 [E, C, C], bias float32 [E, C]; nll_start (the vector fit's NLL), nll_after (unpenalised,
+        at the returned parameters), penalty, grad_norm (|g|_inf of the penalised objective at the optimiser's last point), iterations,
+        converged [E] each; scale0, bias0 (the vector fit), tau (the scalar fit); n)."""
+        from ..engine import model_exits
+        off_diag_l2, bias_l2 = float(off_diag_l2), float(bias_l2)
+        if not (np.isfinite(off_diag_l2) and np.isfinite(bias_l2)) or off_diag_l2 < 0 or bias_l2 < 0:
+            raise ValueError("off_diag_l2 and bias_l2 must be finite and >= 0")
+        own = self._held is None
+        if own:
+            self._held = TemperatureScaling.collect(self)
+        try:
+            batches = self._held
+            v = self._held_vec if self._held_vec is not None else VectorScaling.fit(self, max_iter=max_iter, gtol=gtol, history=history, **search)
+            if not own:
+                self._held_vec = v
+            E, C, n = model_exits(self.model), int(self.model.out_dim), int(v["n"])
+            penalised = off_diag_l2 != 0.0 or bias_l2 != 0.0
+
+            def pen_of(x):
+                return odir_penalty(x[:, :C * C].reshape(E, C, C), x[:, C * C:], n, off_diag_l2, bias_l2)
+
+            def objective(x):
+                f, g = self._eval_matrix(batches, x, C)
+                if penalised:
+                    pv, pm, pb = pen_of(x)
+                    f, g = f + pv, g + np.concatenate([pm.reshape(E, C * C), pb], axis=1)
+                return f, g
+
+            a0, b0 = v["scale"].astype(np.float64), v["bias"].astype(np.float64)
+            M0 = np.zeros((E, C, C))
+            M0[:, np.arange(C), np.arange(C)] = a0
+            x0 = np.concatenate([M0.reshape(E, C * C), b0], axis=1)          # (float32 values: the vector fit's rounded result)
+            r = lbfgs_minimize(objective, x0, max_iter=max_iter, gtol=gtol, history=history)
+            x32 = r["x"].astype(np.float32).astype(np.float64)
+            nll_after = self._eval_matrix(batches, x32, C)[0]
+            nll_x0 = self._eval_matrix(batches, x0, C)[0]
+            pen, pen0 = pen_of(x32)[0], pen_of(x0)[0]
+            keep = nll_after + pen <= nll_x0 + pen0                          # (a fit that moved: always)
+            x32 = np.where(keep[:, None], x32, x0).astype(np.float32)
+            self.result = dict(matrix=np.ascontiguousarray(x32[:, :C * C].reshape(E, C, C)), bias=np.ascontiguousarray(x32[:, C * C:]),
+                               nll_start=np.asarray(v["nll_after"]), nll_after=np.where(keep, nll_after, nll_x0), penalty=np.where(keep, pen, pen0),
+                               grad_norm=np.max(np.abs(r["g"]), axis=1), iterations=r["iterations"], converged=r["converged"],
+                               scale0=v["scale"], bias0=v["bias"], tau=np.asarray(v["tau"]), n=n)
+        finally:
+            if own:
+                self._held = None
+        return self.result
+
+    def select(self, holdout_loader, off_diag_l2=(0.01, 0.1, 1.0, 10.0), bias_l2=0.0, **fit):
+        """Chooses ``off_diag_l2`` on data the fit has not seen: one ``fit`` per candidate on the validation loader (walked once: the
+        collected logits and the vector fit are reused), the UNPENALISED NLL of each result on ``holdout_loader`` (walked once, the same
+        ``MCDEngine.nll_matrix_grad`` call), and the candidate with the lowest hold-out NLL summed over the exits is kept in ``self.result``
+        (ties: the first).  Returns the table: one dict per candidate, in order — off_diag_l2, bias_l2, nll_after [E] (validation),
+        nll_holdout [E], total_holdout, penalty [E], selected (bool)."""
+        cands = [float(c) for c in np.atleast_1d(np.asarray(off_diag_l2, dtype=np.float64))]
+        if not cands:
+            raise ValueError("select: no candidate")
+        C = int(self.model.out_dim)
+        self._held = TemperatureScaling.collect(self)
+        self._held_vec = None
+        try:
+            hold = TemperatureScaling(self.model, holdout_loader, self.gpu, self.mc_passes, self.seed, self.max_logit_bytes).collect()
+            table, results = [], []
+            for c in cands:
+                r = self.fit(off_diag_l2=c, bias_l2=bias_l2, **fit)
+                E = r["matrix"].shape[0]
+                x = np.concatenate([r["matrix"].reshape(E, C * C), r["bias"]], axis=1).astype(np.float64)
+                nll_h = self._eval_matrix(hold, x, C)[0]
+                results.append(r)
+                table.append(dict(off_diag_l2=c, bias_l2=float(bias_l2), nll_after=r["nll_after"], nll_holdout=nll_h,
+                                  total_holdout=float(np.sum(nll_h)), penalty=r["penalty"], selected=False))
+        finally:
+            self._held = self._held_vec = None
+        best = int(np.argmin([row["total_holdout"] for row in table]))       # (argmin: the first of equals)
+        table[best]["selected"] = True
+        self.result = results[best]
+        self.selected = best
+        return table
+
+    def apply(self):
+        """Clears the model's temperature and vector scaling and sets the fitted map: ``model.set_exit_matrix_scaling(matrix, bias)``."""
+        if self.result is None:
+            raise RuntimeError("fit() first")
+        self.model.set_exit_temperature(None)
+        self.model.set_exit_vector_scaling(None)
+        self.model.set_exit_matrix_scaling(self.result["matrix"], self.result["bias"])
+        return self.model.exit_matrix_scaling
+
+    def save(self, experiment_id):
+        """Writes ``matrix_scaling_<id>.npz`` (every entry of the result) and returns its name."""
+        if self.result is None:
+            raise RuntimeError("fit() first")
+        name = f"matrix_scaling_{experiment_id}.npz"
         np.savez(name, **{k: np.asarray(v) for k, v in self.result.items()})
         return name
 

@@ -50,7 +50,7 @@ def weighted_exit_ensembles(per_exit, W):
     return out
 
 
-def decompose_ensemble_logits(logits, tau=None, weights=None, scale=None, bias=None):
+def decompose_ensemble_logits(logits, tau=None, weights=None, scale=None, bias=None, matrix=None):
     """The exit ensembles as predictors, from per-pass logits [T, E, B, C] (``MCDEngine.forward_samples``), float64 on the host: the
     definition csrc/ensemble.hip implements on the device (``MCDEngine.predict_ensemble`` / ``ensemble_moments``).  Per pass t the members
     are p_te = softmax(z_te), z = the fp32 logit, or with ``tau`` (a scalar or E temperatures) the tempered head's ONE rounded fp32 product
@@ -61,7 +61,9 @@ def decompose_ensemble_logits(logits, tau=None, weights=None, scale=None, bias=N
     ``engine.check_ensemble_weights``): the weighted ensembles q_te = ((W[e][0] p_t0 + W[e][1] p_t1) + ...) + W[e][e] p_te — every product
     rounded, added in exit order from 0.0, no renormalisation — in place of the equal mean; everything behind q is the same.  ``scale`` /
     ``bias`` (``engine.check_vector_scaling``: [E, C] or [C], bias None = zeros; not together with ``tau``): the members under a vector
-    scaling, z = float32(float32(l * scale) + bias), the vector-scaled head's two rounded fp32 operations."""
+    scaling, z = float32(float32(l * scale) + bias), the vector-scaled head's two rounded fp32 operations.  ``matrix`` / ``bias``
+    (``engine.check_matrix_scaling``; not together with ``tau`` or ``scale``): the members under a matrix scaling, z = the fp32 number of
+    ``train.calibration.matrix_z``."""
     l = np.asarray(logits, dtype=np.float32)
     if l.ndim != 4:
         raise ValueError("logits must be [T, E, B, C]")
@@ -79,6 +81,11 @@ def decompose_ensemble_logits(logits, tau=None, weights=None, scale=None, bias=N
         from ..engine import check_vector_scaling
         va, vb = check_vector_scaling(scale, bias, E, l.shape[3])
         l = ((l * va[None, :, None, :]).astype(np.float32) + vb[None, :, None, :]).astype(np.float32)
+    if matrix is not None:
+        if tau is not None or scale is not None:
+            raise ValueError("matrix and tau / scale are mutually exclusive")
+        from .calibration import matrix_z
+        l = matrix_z(l, matrix, bias)
     W = None
     if weights is not None:
         from ..engine import check_ensemble_weights

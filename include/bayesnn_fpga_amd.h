@@ -662,6 +662,53 @@ int bmi_nll_vector_scaling_grad(const float* logits, int32_t T, int32_t E, int32
                                 const double* bias, double* nll, double* grad_scale, double* grad_bias, void* scratch, size_t scratch_bytes,
                                 bmi_stream stream);
 
+/* Matrix scaling (Guo et al. 2017): a full [out_dim][out_dim] matrix and a bias per exit, the one calibration map that moves probability
+ * mass between classes; temperature and vector scaling are its special cases.  matrix_device: DEVICE fp32 [n_exits][out_dim][out_dim],
+ * row-major, row = OUTPUT class; bias_device: DEVICE fp32 [n_exits][out_dim]; both owned by the caller and alive for as long as they are
+ * set, every value finite (used AS GIVEN: validating them is the caller's job, the Python layer does).  matrix_device NULL: off.  At the
+ * place the temperature acts — behind the classifier bias and a site on the logits, in front of the running max — every sample's logits
+ * become
+ *     acc = fl32(M[c][0] * l_0)
+ *     acc = fl32(acc + fl32(M[c][j] * l_j))          j = 1 .. C-1, ascending
+ *     z_c = fl32(acc + b[c])
+ * every product and every sum rounded to fp32, never a fused multiply-add, no matrix instruction (its accumulation order is not this
+ * one): a float32 numpy loop reproduces z exactly, and a diagonal matrix gives the bits of bmi_engine_set_vector_scaling (the off-diagonal
+ * products are +-0 for finite logits).  The max, the softmax, S1, S2 and the per-sample entropy (SH) are those of z.  SL and the
+ * per-sample logits of bmi_forward_mcd_samples stay the RAW l.  Every bmi_forward_mcd* entry point honours it, the ensemble launches of
+ * the *_ensemble entry points included; the decision kernels read the scaled sums; bmi_head_fused does not.  Off, the launches are the
+ * kernels they were and every output keeps its bits.  The pointers are read at launch: a captured hipGraph keeps what was set at capture.
+ * One calibration map at a time.  BMI_ERR_INVALID: a NULL handle, a NULL bias_device with a matrix, n_exits / out_dim other than the
+ * engine's, or a temperature other than all ones or a vector scaling in force; and bmi_engine_set_temperature (other than all ones) and
+ * bmi_engine_set_vector_scaling return BMI_ERR_INVALID while a matrix is set. */
+int bmi_engine_set_matrix_scaling(bmi_handle h, const float* matrix_device, const float* bias_device, int32_t n_exits, int32_t out_dim);
+
+/* bmi_ensemble_moments_vector with the two device arrays of bmi_engine_set_matrix_scaling (fp32 [E][C][C] and [E][C]):
+ *     z_te,c = (double) fl32( (..(fl32(M[e][c][0] * l_0) + fl32(M[e][c][1] * l_1)) + ..) + bias[e][c] )         the head's number above
+ * formed once per (sample, exit, image) row, and everything behind it unchanged.  W_device may be NULL (the equal-weight mean).
+ * BMI_ERR_INVALID: a null pointer otherwise, a count below 1; BMI_ERR_UNSUPPORTED as bmi_ensemble_moments. */
+int bmi_ensemble_moments_matrix(const float* logits, int32_t T, int32_t E, int32_t B, int32_t C, const float* matrix_device, const float* bias_device,
+                                const double* W_device, double* Q1, double* Q2, double* QH, bmi_stream stream);
+
+/* Value and gradient of a matrix-scaling fit on per-sample logits, all E exits in one call.  logits / labels as
+ * bmi_nll_temperature_grid's; matrix: device float64 [E][C][C] (row = output class), bias: device float64 [E][C]; nll: device float64
+ * [E], grad_matrix [E][C][C], grad_bias [E][C], all three ADDED TO (a walk over a loader accumulates in call order).  All in float64, no
+ * fused multiply-add, y = labels[b]:
+ *     z_tc = ((0.0 + (double)l_t0 * M[c][0]) + (double)l_t1 * M[c][1] + ...) + b[c]          j ascending, every operation rounded
+ *     A_t  = (z_ty - max_c z_tc) - log sum_c exp(z_tc - max_c z_tc),    nll[e] += sum_b -( logsumexp_t A_t - log T )
+ *     r_t  = exp(A_t) / sum_t' exp(A_t'),   d_tc = r_t (softmax_c(z_t) - [c == y])
+ *     grad_bias[e][c]      += sum_b sum_t d_tc
+ *     grad_matrix[e][c][j] += sum_b sum_t d_tc * (double)l_tj
+ * One workgroup per (image, exit) stages min(64, 3456 / (C | 1)) samples at a time; a larger T runs in chunks of samples with the running
+ * log-sum-exp state carried.  Bit-reproducible: per-image terms go to `scratch` ([E][B][C * C + C + 1] float64,
+ * bmi_nll_matrix_scratch_bytes — 80 MB at E = 4, B = 250, C = 100; 0 for a count below 1) and a second kernel sums them over the images
+ * in a fixed order; no floating-point atomics.  No allocation, no synchronisation.  BMI_ERR_INVALID (decided before any HIP call): a null
+ * pointer, a count below 1.  BMI_ERR_UNSUPPORTED: C > 128 (the head's own limit) or E > 65535.  BMI_ERR_NOMEM: scratch too small.  An
+ * error writes nothing. */
+size_t bmi_nll_matrix_scratch_bytes(int32_t E, int32_t B, int32_t C);
+int bmi_nll_matrix_scaling_grad(const float* logits, int32_t T, int32_t E, int32_t B, int32_t C, const int32_t* labels, const double* matrix,
+                                const double* bias, double* nll, double* grad_matrix, double* grad_bias, void* scratch, size_t scratch_bytes,
+                                bmi_stream stream);
+
 /* Per-op-kind HIP-event timing of bmi_forward_mcd (off by default; adds two event records per
  * launch).  bmi_profile_read synchronises the recorded events and resets the accumulators. */
 int bmi_profile_enable(bmi_handle h, int32_t enable);
