@@ -21,6 +21,7 @@ EXIT_RULES = {"confidence": 0, "margin": 1}      # BMI_EXIT_* of bmi_forward_mcd
 STOP_ON = {"exit": 0, "ensemble": 1}      # BMI_STOP_ON_* of bmi_forward_mcd_adaptive_ensemble
 NLL_VEC_SLAB, NLL_VEC_ROWS = 3456, 64       # bmi_nll_vector_scaling_grad stages min(NLL_VEC_ROWS, NLL_VEC_SLAB // (C | 1)) samples per chunk
 NLL_MAT_SLAB, NLL_MAT_ROWS = 3456, 64       # bmi_nll_matrix_scaling_grad stages min(NLL_MAT_ROWS, NLL_MAT_SLAB // (C | 1)) samples per chunk
+PASS_ACC_MAX_TOPS = 8                       # bmi_pass_accuracy: at most 8 top-k cut-offs per call (K), 128 classes, 32 exits
 NLL_ENS_SLAB, NLL_ENS_ROWS = 9216, 192      # BMI_NLL_ENS_* of bmi_nll_ensemble_temperature_grid: floats / rows a workgroup stages per chunk
 
 
@@ -132,6 +133,9 @@ _PROTOS = {
     "bmi_nll_ensemble_temperature_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "bmi_nll_ensemble_temperature_grid": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint32,
                                                     C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "bmi_pass_accuracy_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "bmi_pass_accuracy": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_int32), C.c_int32] +
+                          [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p]),
     "bmi_profile_enable": (C.c_int, [C.c_void_p, C.c_int32]),
     "bmi_profile_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "bmi_philox_mask": (C.c_int, [C.c_void_p, C.c_int64, C.c_uint64, C.c_int32, C.c_int32, C.c_float, C.c_void_p]),

@@ -2176,6 +2176,22 @@ int bmi_nll_ensemble_temperature_grid(const float* logits, int32_t T, int32_t E,
     return launch_nll_ensemble_temperature_grid(logits, T, E, B, C, labels, tau, vary_mask, tau_cand, G, nll, (double*)scratch, (hipStream_t)stream);
 }
 
+size_t bmi_pass_accuracy_scratch_bytes(int32_t T, int32_t E, int32_t B) {
+    if (T < 1 || E < 1 || B < 1) return 0;
+    const unsigned __int128 bytes = (unsigned __int128)T * E * B * (sizeof(double) + 2 * sizeof(int32_t));
+    return bytes > SIZE_MAX ? SIZE_MAX : (size_t)bytes;
+}
+
+int bmi_pass_accuracy(const float* logits, int32_t T, int32_t E, int32_t B, int32_t C, const int32_t* labels, const int32_t* tops, int32_t K,
+                      int32_t* hits, double* maxprob, int32_t* nonfinite, void* scratch, size_t scratch_bytes, bmi_stream stream) {
+    if (!logits || !labels || !tops || !hits || !maxprob || !scratch || T < 1 || E < 1 || B < 1 || C < 1 || K < 1) return BMI_ERR_INVALID;
+    if (!pass_accuracy_takes(T, E, B, C, K)) return BMI_ERR_UNSUPPORTED;
+    for (int i = 0; i < K; ++i)
+        if (tops[i] < 1) return BMI_ERR_INVALID;
+    if (scratch_bytes < bmi_pass_accuracy_scratch_bytes(T, E, B)) return BMI_ERR_NOMEM;
+    return launch_pass_accuracy(logits, T, E, B, C, labels, tops, K, hits, maxprob, nonfinite, scratch, (hipStream_t)stream);
+}
+
 int bmi_profile_enable(bmi_handle h, int32_t enable) {
     if (!h) return BMI_ERR_INVALID;
     h->profiling = enable != 0;

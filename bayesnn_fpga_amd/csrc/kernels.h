@@ -207,6 +207,13 @@ int launch_nll_vector_scaling_grad(const float* logits, int T, int E, int B, int
 bool nll_matrix_takes(int E, int B, int C);
 int launch_nll_matrix_scaling_grad(const float* logits, int T, int E, int B, int C, const int* labels, const double* matrix, const double* bias,
                                    double* nll, double* grad_matrix, double* grad_bias, double* scratch, hipStream_t s);
+// pass_accuracy.hip (bmi_pass_accuracy): hits [T][2][E][K] = the top-k hit counts of every exit (0) and every exit ensemble (1) of every pass,
+// maxprob [T][E] = the summed max-probabilities, both OVERWRITTEN; tops: HOST [K]; scratch: [T][E][B] float64 then [T][2][E][B] int32.
+// BMI_ERR_UNSUPPORTED (nothing launched) for the shapes pass_accuracy_takes refuses (C > 128, E > 32, K > 8, grid limits)
+#define BMI_PASS_ACC_MAX_TOPS 8
+bool pass_accuracy_takes(int T, int E, int B, int C, int K);
+int launch_pass_accuracy(const float* logits, int T, int E, int B, int C, const int* labels, const int* tops, int K, int* hits, double* maxprob,
+                         int* nonfinite, void* scratch, hipStream_t s);
 // ensemble.hip (bmi_ensemble_moments): Q1 / Q2 [E][B][C] and QH [E][B] += the moments and the entropy of the per-sample exit ensembles
 // q_te = mean_{i<=e} softmax(fl32(l_ti * inv_tau[i])) of logits [T][E][B][C], in sample order onto the running sums
 #define BMI_ENS_MAX_EXITS 32

@@ -1314,6 +1314,35 @@ class MCDEngine(CompiledGraph):
         _lib.check(rc, "bmi_nll_ensemble_temperature_grid")
         return out
 
+    def pass_accuracy(self, logits, labels, tops=(1, 5), out=None, nonfinite=None):
+        """Per-pass multi-exit accuracy on the device (bmi_pass_accuracy): ``logits`` fp32 [T, E, B, C] (``forward_samples``), ``labels`` int
+        [B], ``tops`` the top-k cut-offs (at most 8, each >= 1).  Returns ``(hits, maxprob)``, device tensors: ``hits`` int32 [T, 2, E, K] —
+        ``hits[t, 0, e, i]`` images of pass t whose label is among exit e's ``tops[i]`` highest logits, ``hits[t, 1, e, i]`` the same for the
+        summed softmax of exits 0..e (ties go to the lower class index) — and ``maxprob`` float64 [T, E], the exits' max-probabilities summed
+        over the images in image order.  Both are OVERWRITTEN (``out=(hits, maxprob)``: the caller's buffers, e.g. a row of its table).
+        ``nonfinite``: an int32 [1] device counter the number of (pass, exit, image) rows with a non-finite logit is ADDED to (such a row is
+        a miss and adds 0.0); a label outside [0, C) is a miss everywhere.  Exact counts, the same bits on every run;
+        ``train.evaluate.pass_accuracy_numpy`` is its host restatement.  Raw logits: independent of what is set on this engine."""
+        T, E, B, Cd, labels = self._nll_args(logits, labels)
+        tops = [int(k) for k in tops]
+        K = len(tops)
+        if out is None:
+            out = (torch.empty(T, 2, E, K, dtype=torch.int32, device=self.device), torch.empty(T, E, dtype=torch.float64, device=self.device))
+        elif len(out) != 2:
+            raise ValueError("out must be (hits [T, 2, E, K], maxprob [T, E])")
+        else:
+            check_buffer(out[0], (T, 2, E, K), torch.int32, self.device, "out[0] (hits [T, 2, E, K])")
+            check_buffer(out[1], (T, E), torch.float64, self.device, "out[1] (maxprob [T, E])")
+        if nonfinite is not None:
+            check_buffer(nonfinite, (1,), torch.int32, self.device, "nonfinite [1]")
+        scratch = self._scratch("_nll_scratch", int(self.lib.bmi_pass_accuracy_scratch_bytes(T, E, B)))
+        with torch.cuda.device(self.device):
+            rc = self.lib.bmi_pass_accuracy(logits.data_ptr(), T, E, B, Cd, labels.data_ptr(), (C.c_int32 * max(K, 1))(*tops), K, out[0].data_ptr(),
+                                            out[1].data_ptr(), None if nonfinite is None else nonfinite.data_ptr(), scratch.data_ptr(),
+                                            scratch.numel(), self._stream())
+        _lib.check(rc, "bmi_pass_accuracy")
+        return out
+
     def read_tensor(self, tensor_id, batch, samples=1):
         """A copy of graph tensor ``tensor_id`` as it sits in the workspace after a forward (bmi_tensor_info): fp32
         [samples * batch or batch, h, w, c].  For per-layer traces (tools/layer_trace.py): plan the engine under

@@ -709,6 +709,35 @@ int bmi_nll_matrix_scaling_grad(const float* logits, int32_t T, int32_t E, int32
                                 const double* bias, double* nll, double* grad_matrix, double* grad_bias, void* scratch, size_t scratch_bytes,
                                 bmi_stream stream);
 
+/* Per-pass multi-exit accuracy on per-sample logits: the top-k hit counts of every exit and of every exit ensemble of every stochastic
+ * pass, and every exit's summed max-probability, in two launches — the read-out of the reference's _MultiExitAccuracy._metrics
+ * (SA/train/loss/base_classes.py:39-66) for ALL 2 E rows, not only the two its row-0 overwrite keeps.  logits: device fp32 [T][E][B][C]
+ * (bmi_forward_mcd_samples' layout, the RAW logits: no calibration map acts here), labels: device int32 [B]; tops: HOST int32 [K], each
+ * >= 1, read during the call (a value > C always hits on a valid row).  For pass t and image b, y = labels[b], all in float64, no fused
+ * multiply-add:
+ *     rank(score) = #{c : score_c > score_y} + #{c < y : score_c == score_y}      the label loses ties to lower class indices: a stable
+ *                                                                                  descending sort, the project's "lowest index on ties"
+ *     rank_clf[e] = rank(l_te)                                                     comparisons of the fp32 logits as given
+ *     p_te = softmax_c((double)l_te)   (max-subtracted),   s_te = p_t0 + ... + p_te   in exit order from exit 0 (the reference's
+ *                                                                                  unnormalised `ensemble += softmax(logits)`)
+ *     rank_ens[e] = rank(s_te),        m_te = 1 / sum_c exp((double)l_tec - max_c)   (the row's max-probability)
+ *     hits[t][0][e][i] = #{b : rank_clf[e] < tops[i]},   hits[t][1][e][i] = #{b : rank_ens[e] < tops[i]}        int32 [T][2][E][K]
+ *     maxprob[t][e]    = sum_b m_te, added in image order b = 0, 1, ... from 0.0                                 float64 [T][E]
+ * Both outputs are OVERWRITTEN (the caller points at the row of its own table).  A row (t, e, b) with a non-finite logit is a miss for
+ * every k in clf[e] and in ens[e' >= e] of that (t, b), contributes 0.0 to maxprob[t][e] and adds 1 to *nonfinite (device int32, ADDED
+ * TO; NULL: not counted).  A label outside [0, C) makes the image a miss everywhere: nothing is read outside the row, and the row is not
+ * counted as non-finite.  No NaN reaches an output.  Exact and bit-reproducible: the counts are integers, the max-probability sum has one
+ * order whatever the launch geometry, no floating-point atomics; the per-(pass, exit, image) ranks and max-probabilities go through
+ * `scratch` (bmi_pass_accuracy_scratch_bytes = T * E * B * 16, 0 for a count below 1).  No allocation, no synchronisation: capturable.
+ * BMI_ERR_INVALID (decided before any HIP call): a null pointer other than nonfinite, a count below 1, a tops[i] < 1.
+ * BMI_ERR_UNSUPPORTED: C > 128 (the head's own limit), E > 32, K > 8, T * B >= 2^25 or T * E >= 2^31 (the launch grids).
+ * BMI_ERR_NOMEM: scratch too small.  An error writes nothing. */
+size_t bmi_pass_accuracy_scratch_bytes(int32_t T, int32_t E, int32_t B);
+int bmi_pass_accuracy(const float* logits, int32_t T, int32_t E, int32_t B, int32_t C, const int32_t* labels,
+                      const int32_t* tops /* host, [K], each >= 1; a value > C always hits on a valid row */, int32_t K, int32_t* hits,
+                      double* maxprob, int32_t* nonfinite /* device, ADDED to; NULL: not counted */, void* scratch, size_t scratch_bytes,
+                      bmi_stream stream);
+
 /* Per-op-kind HIP-event timing of bmi_forward_mcd (off by default; adds two event records per
  * launch).  bmi_profile_read synchronises the recorded events and resets the accumulators. */
 int bmi_profile_enable(bmi_handle h, int32_t enable);
