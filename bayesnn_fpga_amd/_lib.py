@@ -136,6 +136,10 @@ _PROTOS = {
     "bmi_pass_accuracy_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "bmi_pass_accuracy": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_int32), C.c_int32] +
                           [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p]),
+    "bmi_forward_mcd_votes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_int32] +
+                              [C.c_void_p] * 10 + [C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "bmi_vote_counts": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float)] + [C.c_void_p] * 7),
+    "bmi_finalize_votes": (C.c_int, [C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 5),
     "bmi_profile_enable": (C.c_int, [C.c_void_p, C.c_int32]),
     "bmi_profile_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "bmi_philox_mask": (C.c_int, [C.c_void_p, C.c_int64, C.c_uint64, C.c_int32, C.c_int32, C.c_float, C.c_void_p]),

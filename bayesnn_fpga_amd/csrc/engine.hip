@@ -1671,10 +1671,17 @@ int ensemble_add(const bmi_engine_s* e, const EnsembleSums& ens, int tc, int B, 
     return launch_ensemble_moments(ens.scratch, tc, e->n_exits, B, e->out_dim, e->cal, rows, ens.Q1, ens.Q2, ens.QH, s);
 }
 
+// bmi_forward_mcd_votes: the vote counts of the call (votes.hip), taken from the chunk of per-sample logits the ensemble launch reads
+struct VoteCounts {
+    int32_t* V;
+    int32_t* nonfinite;      // or null
+};
+
 // The folded path: the prefix once, then samples t_begin .. t_begin+t_count-1 through the suffix, `chunk` at a time.
 // ens: every chunk's heads also write their logits into ens->scratch (a runtime branch of the same kernels: S1 / S2 / SL / SH keep their
 // bits), and one launch of ensemble.hip behind them adds the chunk's samples, in sample order, to the ensemble sums.
-int forward_folded(bmi_engine_s* e, const Pass& p, int t_begin, int t_count, const EnsembleSums* ens = nullptr) {
+// votes (with ens only): one launch of votes.hip on the same scratch, under the same calibration, adds the chunk's votes.
+int forward_folded(bmi_engine_s* e, const Pass& p, int t_begin, int t_count, const EnsembleSums* ens = nullptr, const VoteCounts* votes = nullptr) {
     BmiOptionScope opt_scope(&e->opts);
     for (const OpInfo& op : e->prefix) {
         const int rc = run_op(e, p, op, p.B, 0);
@@ -1691,6 +1698,9 @@ int forward_folded(bmi_engine_s* e, const Pass& p, int t_begin, int t_count, con
         //  adding it is a change of what profile_launches() returns, not a refactoring)
         rc = ensemble_add(e, *ens, tc, p.B, p.stream);
         if (rc != BMI_OK) return rc;
+        if (!votes) continue;
+        rc = launch_vote_counts(ens->scratch, tc, e->n_exits, p.B, e->out_dim, e->cal, votes->V, votes->nonfinite, p.stream);
+        if (rc != BMI_OK) return rc;
     }
     return BMI_OK;
 }
@@ -1698,7 +1708,7 @@ int forward_folded(bmi_engine_s* e, const Pass& p, int t_begin, int t_count, con
 // bmi_forward_mcd, _images and _entropy (SH: null but for _entropy): their argument checks, then the folded path.
 int forward_moments(bmi_handle h, const float* x_nchw, int32_t batch, int32_t image_offset, int32_t t_begin, int32_t t_count, uint64_t seed,
                     int32_t mask_cnt0, double* S1, double* S2, double* SL, double* SH, void* workspace, size_t workspace_bytes, bmi_stream stream,
-                    const EnsembleSums* ens = nullptr) {
+                    const EnsembleSums* ens = nullptr, const VoteCounts* votes = nullptr) {
     const int rco = bmi_image_offset_ok(h, image_offset);      // (a null handle: BMI_ERR_INVALID; image 0 always passes)
     if (rco != BMI_OK) return rco;
     if (!x_nchw || !S1 || !S2 || !SL || !workspace) return BMI_ERR_INVALID;
@@ -1708,7 +1718,7 @@ int forward_moments(bmi_handle h, const float* x_nchw, int32_t batch, int32_t im
     Pass p{x_nchw, (char*)workspace, (hipStream_t)stream, batch, seed, mask_cnt0};
     p.b0 = image_offset;
     p.S1 = S1; p.S2 = S2; p.SL = SL; p.SH = SH;
-    return forward_folded(h, p, t_begin, t_count, ens);
+    return forward_folded(h, p, t_begin, t_count, ens, votes);
 }
 
 }  // namespace
@@ -1769,6 +1779,19 @@ int bmi_forward_mcd_ensemble(bmi_handle h, const float* x_nchw, int32_t batch, i
     const EnsembleSums ens{Q1, Q2, QH, (float*)scratch};
     return forward_moments(h, x_nchw, batch, image_offset, t_begin, t_count, seed, mask_cnt0, S1, S2, SL, SH, workspace, workspace_bytes, stream,
                            &ens);
+}
+
+int bmi_forward_mcd_votes(bmi_handle h, const float* x_nchw, int32_t batch, int32_t image_offset, int32_t t_begin, int32_t t_count, uint64_t seed,
+                          int32_t mask_cnt0, double* S1, double* S2, double* SL, double* SH, double* Q1, double* Q2, double* QH, int32_t* V,
+                          int32_t* nonfinite, void* scratch, size_t scratch_bytes, void* workspace, size_t workspace_bytes, bmi_stream stream) {
+    if (!h || !SH || !V) return BMI_ERR_INVALID;
+    const int rce = ensemble_args_ok(h, batch, Q1, Q2, QH, scratch, scratch_bytes);
+    if (rce != BMI_OK) return rce;
+    if (!vote_counts_takes(h->chunk, h->n_exits, batch, h->out_dim)) return BMI_ERR_UNSUPPORTED;
+    const EnsembleSums ens{Q1, Q2, QH, (float*)scratch};
+    const VoteCounts votes{V, nonfinite};
+    return forward_moments(h, x_nchw, batch, image_offset, t_begin, t_count, seed, mask_cnt0, S1, S2, SL, SH, workspace, workspace_bytes, stream,
+                           &ens, &votes);
 }
 
 int bmi_forward_mcd_samples(bmi_handle h, const float* x_nchw, int32_t batch, int32_t t_begin, int32_t t_count, uint64_t seed,
@@ -2120,6 +2143,33 @@ int bmi_ensemble_moments_matrix(const float* logits, int32_t T, int32_t E, int32
     Calibration cal;
     cal.mat = matrix_device; cal.mat_bias = bias_device; cal.ens_w = W_device;
     return ensemble_moments_entry(logits, T, E, B, C, nullptr, cal, Q1, Q2, QH, stream);
+}
+
+int bmi_vote_counts(const float* logits, int32_t T, int32_t E, int32_t B, int32_t C, const float* tau, const float* scale_device,
+                    const float* bias_device, const float* matrix_device, const double* W_device, int32_t* V, int32_t* nonfinite, bmi_stream stream) {
+    if (!logits || !V || T < 1 || E < 1 || B < 1 || C < 1) return BMI_ERR_INVALID;
+    if ((tau != nullptr) + (scale_device != nullptr) + (matrix_device != nullptr) > 1) return BMI_ERR_INVALID;       // one map at a time
+    if ((bias_device != nullptr) != (scale_device != nullptr || matrix_device != nullptr)) return BMI_ERR_INVALID;   // the bias belongs to a map
+    if (!vote_counts_takes(T, E, B, C)) return BMI_ERR_UNSUPPORTED;
+    Calibration cal;
+    if (tau)
+        for (int e = 0; e < E; ++e) {
+            if (!(tau[e] > 0.f) || !std::isfinite(tau[e])) return BMI_ERR_INVALID;
+            const float inv = (float)(1.0 / (double)tau[e]);       // (bmi_engine_set_temperature's rounding)
+            if (!(inv > 0.f) || !std::isfinite(inv)) return BMI_ERR_INVALID;
+            cal.inv_tau.push_back(inv);
+        }
+    if (scale_device) { cal.vec_scale = scale_device; cal.vec_bias = bias_device; }
+    if (matrix_device) { cal.mat = matrix_device; cal.mat_bias = bias_device; }
+    cal.ens_w = W_device;
+    return launch_vote_counts(logits, T, E, B, C, cal, V, nonfinite, (hipStream_t)stream);
+}
+
+int bmi_finalize_votes(int32_t n_exits, int32_t batch, int32_t out_dim, const int32_t* V, int32_t* vote_class, double* variation_ratio,
+                       double* vote_entropy, bmi_stream stream) {
+    if (!V || !vote_class || !variation_ratio || !vote_entropy || n_exits < 1 || batch < 1 || out_dim < 1) return BMI_ERR_INVALID;
+    if ((int64_t)2 * n_exits * batch > INT32_MAX / 64) return BMI_ERR_UNSUPPORTED;
+    return launch_finalize_votes(2 * n_exits * batch, out_dim, V, vote_class, variation_ratio, vote_entropy, (hipStream_t)stream);
 }
 
 size_t bmi_nll_matrix_scratch_bytes(int32_t E, int32_t B, int32_t C) {

@@ -251,6 +251,15 @@ int launch_finalize_ensemble(int n_rows, int C, int t_total, const double* Q1, c
 // the same with row (exit, image b) divided by t_used[b] (bmi_finalize_ensemble_per_image)
 int launch_finalize_ensemble_per_image(int n_exits, int batch, int C, const int* t_used, const double* Q1, const double* Q2, const double* QH,
                                        double* mean, double* var, double* pred, double* expd, double* mi, int* nonfinite, hipStream_t s);
+// votes.hip (bmi_vote_counts, bmi_forward_mcd_votes): V int32 [2][E][B][C] += the votes of the T passes of logits [T][E][B][C] — V[0]: the arg-max of
+// every exit's calibrated logits z (cal's map), V[1]: the arg-max of every exit ensemble q_te (cal.ens_w: the weighted ones), the lowest class
+// index on ties; a row with a non-finite z casts no vote, nor do the ensembles behind it, and adds 1 to *nonfinite (null: not counted).
+// Integer atomics: exact whatever the launch geometry.  BMI_ERR_UNSUPPORTED (nothing launched) for the shapes vote_counts_takes refuses
+// (C > 128, E > 32, T * B >= 2^25)
+bool vote_counts_takes(int T, int E, int B, int C);
+int launch_vote_counts(const float* logits, int T, int E, int B, int C, const Calibration& cal, int* V, int* nonfinite, hipStream_t s);
+// per (kind, exit, image) row of V: the lowest modal class (-1: no vote), 1 - modal count / votes (1.0), the entropy of the vote shares (0.0)
+int launch_finalize_votes(int n_rows, int C, const int* V, int* vote_class, double* ratio, double* entropy, hipStream_t s);
 int launch_philox_mask(uint8_t* keep, int64_t n, uint64_t seed, int site, int t, float p, hipStream_t s);
 // planar_w > 0: the bits in the lazy site's planar layout (rows of planar_w pixels; 2-bit sites, c % 64 == 0)
 int launch_mask_bits(uint8_t* bits, int n, int hw, int c, const SiteArgs& site, int batch, int t0, hipStream_t s, int planar_w = 0);

@@ -977,6 +977,88 @@ class MCDEngine(CompiledGraph):
         r.update(Q=Q, QH=QH)
         return r
 
+    # ---- vote counts: variation ratio and majority vote (bmi_forward_mcd_votes / bmi_vote_counts / bmi_finalize_votes) ----------------
+    def new_vote_counts(self, batch):
+        """Zeroed int32 vote counts V [2, E, B, C] of ``accumulate_votes``: V[0] the exits' votes, V[1] the exit ensembles'.  Integers:
+        additive over samples, chunks, calls and ranks."""
+        return torch.zeros(2, self.n_exits, batch, self.out_dim, dtype=torch.int32, device=self.device)
+
+    def accumulate_votes(self, x, S, H, Q, QH, V, t_begin, t_count, seed=0, cnt0=0, image_offset=0):
+        """``accumulate_ensemble`` (the same bits in S, H, Q and QH) that also adds every pass's votes into V [2, E, B, C] (``new_vote_counts``):
+        V[0, e, b, k] += 1 for k the arg-max of exit e's calibrated logits of that pass, V[1, e, b, k] += 1 for k the arg-max of the exit
+        ensemble q_e of that pass (the weighted one under ``set_ensemble_weights``), the lowest class index on ties.  One kernel
+        (csrc/votes.hip) behind every chunk's ensemble launch reads the same per-sample logits; a (pass, exit, image) row with a non-finite
+        calibrated logit casts no vote, nor do the ensembles behind it, and counts into the engine's counter (``check_finite``)."""
+        x = self._check_x(x)
+        B = x.shape[0]
+        self._check_sums(B, S, H, Q, QH, ensemble=True)
+        check_buffer(V, (2, self.n_exits, B, self.out_dim), torch.int32, self.device, "vote counts V")
+        scratch = self._ensemble_scratch()
+        with torch.cuda.device(self.device):
+            rc = self.lib.bmi_forward_mcd_votes(self.handle, x.data_ptr(), B, int(image_offset), int(t_begin), int(t_count),
+                                                int(seed) & 0xFFFFFFFFFFFFFFFF, int(cnt0), S[0].data_ptr(), S[1].data_ptr(), S[2].data_ptr(),
+                                                H.data_ptr(), Q[0].data_ptr(), Q[1].data_ptr(), QH.data_ptr(), V.data_ptr(),
+                                                self._nonfinite.data_ptr(), scratch.data_ptr(), scratch.numel(), self.workspace.data_ptr(),
+                                                self.workspace_bytes, self._stream())
+        _lib.check(rc, "bmi_forward_mcd_votes")
+        return S, H, Q, QH, V
+
+    def finalize_votes(self, V):
+        """The read-out of vote counts V [2, E, B, C] (bmi_finalize_votes), device tensors: ``votes`` int32 [E, B, C] (V[0] itself),
+        ``vote_class`` int32 [E, B] the majority vote (the lowest class with the modal count; -1 where no vote was cast),
+        ``variation_ratio`` float64 [E, B] = 1 - modal count / votes cast (1.0 where none), ``vote_entropy`` float64 [E, B] the entropy of
+        the vote shares in nats (0.0 where none) — and their ``ens_*`` twins for the exit ensembles (V[1]).
+        ``train.uncertainty.vote_readout_numpy`` is the host restatement."""
+        check_buffer(V, (2, None, None, None), torch.int32, self.device, "vote counts V")
+        _, E, B, Cd = V.shape
+        cls = torch.empty(2, E, B, dtype=torch.int32, device=self.device)
+        out = torch.empty(2, 2, E, B, dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = self.lib.bmi_finalize_votes(E, B, Cd, V.data_ptr(), cls.data_ptr(), out[0].data_ptr(), out[1].data_ptr(), self._stream())
+        _lib.check(rc, "bmi_finalize_votes")
+        return dict(votes=V[0], vote_class=cls[0], variation_ratio=out[0, 0], vote_entropy=out[1, 0],
+                    ens_votes=V[1], ens_vote_class=cls[1], ens_variation_ratio=out[0, 1], ens_vote_entropy=out[1, 1])
+
+    def predict_votes(self, x, T, seed=0, t_begin=0, cnt0=0):
+        """``predict_ensemble``'s dict plus the eight entries of ``finalize_votes``."""
+        S, H, Q, QH = self.new_ensemble_sums(x.shape[0])
+        V = self.new_vote_counts(x.shape[0])
+        self.accumulate_votes(x, S, H, Q, QH, V, t_begin, T, seed, cnt0)
+        r = self.finalize_ensemble(S, H, Q, QH, T)
+        r.update(self.finalize_votes(V))
+        return r
+
+    def vote_counts(self, logits, tau=None, weights=None, scale=None, bias=None, matrix=None, out=None):
+        """The vote counts of per-sample logits the caller holds (bmi_vote_counts): ``logits`` fp32 [T, E, B, C] on the engine's device
+        (``forward_samples``); ``tau``, ``weights``, ``scale`` / ``bias`` and ``matrix`` / ``bias`` as ``ensemble_moments`` takes them (at
+        most one map; all independent of what is set on this engine).  Returns V int32 [2, E, B, C]; ``out=V`` ADDS into the counts of
+        earlier calls.  ``train.uncertainty.vote_counts_numpy`` is the host restatement; ``finalize_votes`` reads V out."""
+        T, E, B, Cd = check_buffer(logits, (None,) * 4, torch.float32, self.device, "logits [T, E, B, C]").shape
+        tau = check_temperature(tau, E)
+        W = check_ensemble_weights(weights, E)
+        if matrix is not None:
+            if tau is not None or scale is not None:
+                raise ValueError("vote_counts: matrix and tau / scale are mutually exclusive")
+            va, vb = check_matrix_scaling(matrix, bias, E, Cd)
+        else:
+            va, vb = check_vector_scaling(scale, bias, E, Cd)
+        if va is not None and tau is not None:
+            raise ValueError("vote_counts: tau and scale / bias are mutually exclusive")
+        if out is None:
+            V = torch.zeros(2, E, B, Cd, dtype=torch.int32, device=self.device)
+        else:
+            V = check_buffer(out, (2, E, B, Cd), torch.int32, self.device, "out (V)")
+        tau_c = None if tau is None else (C.c_float * E)(*tau)
+        with torch.cuda.device(self.device):
+            # the device copies stay alive until the launch is queued, and are freed in stream order behind it
+            a_dev, b_dev, w_dev = (None if a is None else torch.from_numpy(a).to(self.device) for a in (va, vb, W))
+            ptr = lambda t: None if t is None else t.data_ptr()
+            vec, mat = (ptr(a_dev), None) if matrix is None else (None, ptr(a_dev))
+            rc = self.lib.bmi_vote_counts(logits.data_ptr(), T, E, B, Cd, tau_c, vec, ptr(b_dev), mat, ptr(w_dev), V.data_ptr(),
+                                          self._nonfinite.data_ptr(), self._stream())
+        _lib.check(rc, "bmi_vote_counts")
+        return V
+
     def predict_with_exit(self, x, T, threshold, seed=0, cnt0=0, first_exit=1):
         """Confidence-threshold early exiting on the device (bmi_forward_mcd_exit): an image leaves after the first exit
         e >= ``first_exit`` whose T-mean confidence exceeds ``threshold`` (the reference's ``confidence_exiting`` rule,

@@ -50,20 +50,9 @@ def weighted_exit_ensembles(per_exit, W):
     return out
 
 
-def decompose_ensemble_logits(logits, tau=None, weights=None, scale=None, bias=None, matrix=None):
-    """The exit ensembles as predictors, from per-pass logits [T, E, B, C] (``MCDEngine.forward_samples``), float64 on the host: the
-    definition csrc/ensemble.hip implements on the device (``MCDEngine.predict_ensemble`` / ``ensemble_moments``).  Per pass t the members
-    are p_te = softmax(z_te), z = the fp32 logit, or with ``tau`` (a scalar or E temperatures) the tempered head's ONE rounded fp32 product
-    float32(l) * float32(1 / tau_e); the ensemble of exits 0..e is q_te = (p_t0 + ... + p_te) / (e + 1) — the reference's per-pass
-    ``ensemble += softmax(logits)`` (train/loss/base_classes.py:41,54,58).  Returns dict(mean, var [E, B, C] — var with ddof 0, clamped at
-    0 —, pred_entropy H[mean], exp_entropy E_t H[q_t], mutual_info [E, B] — clamped at 0), entropies in nats.  Row 0 is exit 0 itself.
-    The exits of one pass share the trunk's draw: ``var`` is NOT sum_i var_i / (e + 1)^2.  ``weights`` (None, [E] or [E, E]:
-    ``engine.check_ensemble_weights``): the weighted ensembles q_te = ((W[e][0] p_t0 + W[e][1] p_t1) + ...) + W[e][e] p_te — every product
-    rounded, added in exit order from 0.0, no renormalisation — in place of the equal mean; everything behind q is the same.  ``scale`` /
-    ``bias`` (``engine.check_vector_scaling``: [E, C] or [C], bias None = zeros; not together with ``tau``): the members under a vector
-    scaling, z = float32(float32(l * scale) + bias), the vector-scaled head's two rounded fp32 operations.  ``matrix`` / ``bias``
-    (``engine.check_matrix_scaling``; not together with ``tau`` or ``scale``): the members under a matrix scaling, z = the fp32 number of
-    ``train.calibration.matrix_z``."""
+def calibrated_logits(logits, tau=None, weights=None, scale=None, bias=None, matrix=None):
+    """(z, W): the calibrated fp32 logits z [T, E, B, C] of per-pass logits under at most one map — the head's own numbers, as
+    ``decompose_ensemble_logits`` states them — and the checked ensemble weights float64 [E, E], or None."""
     l = np.asarray(logits, dtype=np.float32)
     if l.ndim != 4:
         raise ValueError("logits must be [T, E, B, C]")
@@ -90,6 +79,25 @@ def decompose_ensemble_logits(logits, tau=None, weights=None, scale=None, bias=N
     if weights is not None:
         from ..engine import check_ensemble_weights
         W = check_ensemble_weights(weights, E)
+    return l, W
+
+
+def decompose_ensemble_logits(logits, tau=None, weights=None, scale=None, bias=None, matrix=None):
+    """The exit ensembles as predictors, from per-pass logits [T, E, B, C] (``MCDEngine.forward_samples``), float64 on the host: the
+    definition csrc/ensemble.hip implements on the device (``MCDEngine.predict_ensemble`` / ``ensemble_moments``).  Per pass t the members
+    are p_te = softmax(z_te), z = the fp32 logit, or with ``tau`` (a scalar or E temperatures) the tempered head's ONE rounded fp32 product
+    float32(l) * float32(1 / tau_e); the ensemble of exits 0..e is q_te = (p_t0 + ... + p_te) / (e + 1) — the reference's per-pass
+    ``ensemble += softmax(logits)`` (train/loss/base_classes.py:41,54,58).  Returns dict(mean, var [E, B, C] — var with ddof 0, clamped at
+    0 —, pred_entropy H[mean], exp_entropy E_t H[q_t], mutual_info [E, B] — clamped at 0), entropies in nats.  Row 0 is exit 0 itself.
+    The exits of one pass share the trunk's draw: ``var`` is NOT sum_i var_i / (e + 1)^2.  ``weights`` (None, [E] or [E, E]:
+    ``engine.check_ensemble_weights``): the weighted ensembles q_te = ((W[e][0] p_t0 + W[e][1] p_t1) + ...) + W[e][e] p_te — every product
+    rounded, added in exit order from 0.0, no renormalisation — in place of the equal mean; everything behind q is the same.  ``scale`` /
+    ``bias`` (``engine.check_vector_scaling``: [E, C] or [C], bias None = zeros; not together with ``tau``): the members under a vector
+    scaling, z = float32(float32(l * scale) + bias), the vector-scaled head's two rounded fp32 operations.  ``matrix`` / ``bias``
+    (``engine.check_matrix_scaling``; not together with ``tau`` or ``scale``): the members under a matrix scaling, z = the fp32 number of
+    ``train.calibration.matrix_z``."""
+    l, W = calibrated_logits(logits, tau, weights, scale, bias, matrix)
+    T, E = l.shape[:2]
     z = l.astype(np.float64)
     z = z - z.max(axis=-1, keepdims=True)
     ex = np.exp(z)
@@ -114,6 +122,56 @@ def decompose_ensemble_logits(logits, tau=None, weights=None, scale=None, bias=N
                 mutual_info=np.maximum(pred_entropy - exp_entropy, 0.0))
 
 
+def vote_counts_numpy(logits, tau=None, weights=None, scale=None, bias=None, matrix=None):
+    """The vote counts of per-pass logits [T, E, B, C] on the host: the definition csrc/votes.hip implements on the device
+    (``MCDEngine.accumulate_votes`` / ``vote_counts``).  z = the calibrated fp32 logits of ``decompose_ensemble_logits`` (same arguments);
+    a row (t, e, b) with a non-finite z is bad.  V[0, e, b, k] counts the passes whose row is not bad and whose lowest arg-max of z (fp32
+    comparisons) is k; V[1, e, b, k] the passes with no bad row among exits 0..e whose lowest arg-max of the float64 exit ensemble q_te —
+    (p_t0 + ... + p_te) / (e + 1), or the weighted sum in exit order from 0.0 — is k.  Returns (V int32 [2, E, B, C], the number of bad
+    rows)."""
+    l, W = calibrated_logits(logits, tau, weights, scale, bias, matrix)
+    T, E, B, Cd = l.shape
+    bad = ~np.isfinite(l).all(axis=-1)                                   # [T, E, B]
+    ens_bad = np.cumsum(bad, axis=1) > 0
+    with np.errstate(invalid="ignore", over="ignore"):
+        z = np.where(bad[..., None], 0.0, l.astype(np.float64))          # (bad rows: a placeholder nobody counts)
+        z = z - z.max(axis=-1, keepdims=True)
+        ex = np.exp(z)
+        p = ex / ex.sum(axis=-1, keepdims=True)
+    V = np.zeros((2, E, B, Cd), dtype=np.int32)
+    rows = np.arange(B)
+    for t in range(T):
+        k = np.where(bad[t][..., None], -np.inf, l[t]).argmax(axis=-1)   # [E, B]: numpy's argmax is the first maximum
+        acc = np.zeros((B, Cd), dtype=np.float64)
+        qw = None if W is None else weighted_exit_ensembles(p[t], W)
+        for e in range(E):
+            acc = acc + p[t, e]
+            q = acc / (e + 1) if W is None else qw[e]
+            ok = ~bad[t, e]
+            np.add.at(V[0, e], (rows[ok], k[e][ok]), 1)
+            ok = ~ens_bad[t, e]
+            np.add.at(V[1, e], (rows[ok], q.argmax(axis=-1)[ok]), 1)
+    return V, int(bad.sum())
+
+
+def vote_readout_numpy(V):
+    """The read-out of vote counts V [..., C] (bmi_finalize_votes on the host): dict(vote_class int32 — the lowest class with the modal
+    count, -1 where no vote was cast —, variation_ratio = 1 - modal count / votes cast (1.0 where none), vote_entropy = -sum f log f over
+    the classes with votes, subtracted in class order from 0.0, in nats (0.0 where none)), each [...]."""
+    V = np.asarray(V)
+    n = V.sum(axis=-1, dtype=np.int64)
+    m = V.max(axis=-1)
+    some = n > 0
+    nn = np.where(some, n, 1).astype(np.float64)
+    h = np.zeros(n.shape, dtype=np.float64)
+    for c in range(V.shape[-1]):
+        x = V[..., c]
+        f = x.astype(np.float64) / nn
+        h = h - np.where(x > 0, f * np.log(np.where(x > 0, f, 1.0)), 0.0)
+    return dict(vote_class=np.where(some, V.argmax(axis=-1), -1).astype(np.int32),
+                variation_ratio=np.where(some, 1.0 - m.astype(np.float64) / nn, 1.0), vote_entropy=np.where(some, h, 0.0))
+
+
 class UncertaintyAnalysis:
     """One walk of ``loader`` (batches ``(x, y, ...)``) with ``mc_passes`` stochastic passes per batch.
 
@@ -133,10 +191,20 @@ class UncertaintyAnalysis:
     device's entropy of the float64 ensemble mean (within 1e-5 of the default walk's, whose members are the heads' fp32 softmax), so that
     ensemble_mutual_info = ensemble_pred_entropy - ensemble_exp_entropy; everything else keeps its numbers.  Not under a sharded walk (more than one rank): NotImplementedError.
     On a model that carries ensemble weights (``set_exit_ensemble_weights``) the ``ensemble=True`` walk describes the WEIGHTED ensembles —
-    the five device arrays through the engine, ``ensemble_ape`` from the weighted mean of ``mean``; the default walk keeps the equal mean."""
+    the five device arrays through the engine, ``ensemble_ape`` from the weighted mean of ``mean``; the default walk keeps the equal mean.
 
-    def __init__(self, model, loader, gpu=0, mc_passes=10, seed=0, group=None, ensemble=False):
-        self.ensemble = bool(ensemble)
+    ``votes=True`` (implies ``ensemble=True``; not under a sharded walk either): the walk also counts every pass's votes on the device
+    (``MCDEngine.predict_votes``) and fills ``votes`` int32 [E, N, C], ``vote_class`` int32 [E, N] (the majority vote), ``variation_ratio`` and
+    ``vote_entropy`` [E, N], their ``ensemble_*`` twins for the exit ensembles, ``mean_variation_ratio`` [E] and ``vote_agreement`` [E], the
+    share of images whose majority vote equals the arg-max of ``mean`` (``ensemble_mean_variation_ratio`` / ``ensemble_vote_agreement``:
+    the same against the device's ensemble mean); ``summary()`` and ``save()`` gain those keys.  Every attribute of the ``ensemble=True``
+    walk keeps its numbers."""
+
+    VOTE_KEYS = ("votes", "vote_class", "variation_ratio", "vote_entropy")
+
+    def __init__(self, model, loader, gpu=0, mc_passes=10, seed=0, group=None, ensemble=False, votes=False):
+        self.count_votes = bool(votes)               # (``votes`` itself becomes the array of counts)
+        self.ensemble = bool(ensemble) or self.count_votes
         self.model = model
         self.loader = loader
         self.device = get_device(gpu)
@@ -163,12 +231,17 @@ class UncertaintyAnalysis:
     def _run(self):
         from ..sharding import predict_sharded_uncertainty
         world = self._ranks()[1]
+        if self.count_votes and world > 1:
+            raise NotImplementedError("UncertaintyAnalysis(votes=True) under a sharded walk: the vote counts are not part of "
+                                      "sharding.accumulate_partitioned's all-reduce")
         if self.ensemble and world > 1:
             raise NotImplementedError("UncertaintyAnalysis(ensemble=True) under a sharded walk: the ensemble sums are not part of "
                                       "sharding.accumulate_partitioned's all-reduce")
         names = ("mean", "pred_entropy", "exp_entropy", "mutual_info")
         if self.ensemble:
             names += ("ens_var", "ens_pred_entropy", "ens_exp_entropy", "ens_mutual_info")
+        if self.count_votes:
+            names += ("ens_mean",) + self.VOTE_KEYS + tuple("ens_" + n for n in self.VOTE_KEYS)
         parts, labels, eng = [], [], None
         for k, batch in enumerate(self.loader):
             b_x = batch[0].to(self.device)
@@ -179,6 +252,8 @@ class UncertaintyAnalysis:
             self.model.advance(T)
             if world > 1:
                 r = predict_sharded_uncertainty(eng, b_x, T, seed, cnt0, group=self.group)
+            elif self.count_votes:
+                r = eng.predict_votes(b_x, T, seed, cnt0=cnt0)
             elif self.ensemble:
                 r = eng.predict_ensemble(b_x, T, seed, cnt0=cnt0)
             else:
@@ -207,14 +282,33 @@ class UncertaintyAnalysis:
             self.ensemble_exp_entropy = np.concatenate([p["ens_exp_entropy"] for p in parts], axis=1)
             self.ensemble_mutual_info = np.concatenate([p["ens_mutual_info"] for p in parts], axis=1)
             self.ensemble_mean_mi = self.ensemble_mutual_info.mean(axis=1)
+        if self.count_votes:
+            for n in self.VOTE_KEYS:
+                setattr(self, n, np.concatenate([p[n] for p in parts], axis=1))
+                setattr(self, "ensemble_" + n, np.concatenate([p["ens_" + n] for p in parts], axis=1))
+            ens_mean = np.concatenate([p["ens_mean"] for p in parts], axis=1)
+            self.mean_variation_ratio = self.variation_ratio.mean(axis=1)
+            self.ensemble_mean_variation_ratio = self.ensemble_variation_ratio.mean(axis=1)
+            self.vote_agreement = (self.vote_class == self.mean.argmax(axis=-1)).mean(axis=1)
+            self.ensemble_vote_agreement = (self.ensemble_vote_class == ens_mean.argmax(axis=-1)).mean(axis=1)
+
+    def _vote_arrays(self):
+        names = self.VOTE_KEYS + tuple("ensemble_" + n for n in self.VOTE_KEYS) + \
+            ("mean_variation_ratio", "ensemble_mean_variation_ratio", "vote_agreement", "ensemble_vote_agreement")
+        return {n: getattr(self, n) for n in names}
 
     def summary(self):
-        """Per exit: dict(ape, mean_mi, mean_exp_entropy, ensemble_ape), and ensemble_mean_mi of an ``ensemble=True`` walk."""
+        """Per exit: dict(ape, mean_mi, mean_exp_entropy, ensemble_ape), ensemble_mean_mi of an ``ensemble=True`` walk, and the mean
+        variation ratios and vote agreements of a ``votes=True`` walk."""
         out = [dict(ape=float(self.ape[e]), mean_mi=float(self.mean_mi[e]), mean_exp_entropy=float(self.mean_exp_entropy[e]),
                     ensemble_ape=float(self.ensemble_ape[e])) for e in range(len(self.ape))]
         if self.ensemble:
             for e, d in enumerate(out):
                 d["ensemble_mean_mi"] = float(self.ensemble_mean_mi[e])
+        if self.count_votes:
+            for e, d in enumerate(out):
+                for n in ("mean_variation_ratio", "ensemble_mean_variation_ratio", "vote_agreement", "ensemble_vote_agreement"):
+                    d[n] = float(getattr(self, n)[e])
         return out
 
     def save(self, experiment_id):
@@ -226,6 +320,8 @@ class UncertaintyAnalysis:
         if self.ensemble:
             extra = dict(ensemble_var=self.ensemble_var, ensemble_exp_entropy=self.ensemble_exp_entropy,
                          ensemble_mutual_info=self.ensemble_mutual_info, ensemble_mean_mi=self.ensemble_mean_mi)
+        if self.count_votes:
+            extra.update(self._vote_arrays())
         np.savez(name, mean=self.mean, pred_entropy=self.pred_entropy, exp_entropy=self.exp_entropy, mutual_info=self.mutual_info,
                  labels=self.labels, ape=self.ape, mean_mi=self.mean_mi, mean_exp_entropy=self.mean_exp_entropy,
                  ensemble_pred_entropy=self.ensemble_pred_entropy, ensemble_ape=self.ensemble_ape, **extra)

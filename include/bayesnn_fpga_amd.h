@@ -738,6 +738,56 @@ int bmi_pass_accuracy(const float* logits, int32_t T, int32_t E, int32_t B, int3
                       double* maxprob, int32_t* nonfinite /* device, ADDED to; NULL: not counted */, void* scratch, size_t scratch_bytes,
                       bmi_stream stream);
 
+/* Vote counts: the variation ratio and the majority-vote prediction, the third MC-dropout uncertainty measure beside the predictive
+ * entropy and the mutual information.  A vote is the arg-max of ONE stochastic pass, so it cannot be recovered from the sums over the
+ * passes (S1 / S2 / SL, Q1 / Q2 / QH): it is taken where the per-sample logits exist.  For pass t, image b and exit e, with the raw fp32
+ * logits l_te of length C and no fused multiply-add wherever a number is formed:
+ *     z_te  the calibrated fp32 logits, formed exactly as the fused head and the ensemble launches form them — no map: z = l;
+ *           temperature: fl32(l * inv_e), inv_e = float32(1 / tau_e); vector scaling: fl32(fl32(l * a_c) + b_c); matrix scaling: the number
+ *           of bmi_engine_set_matrix_scaling (products rounded one by one, added for j ascending, then the bias).  One map at a time.
+ *     bad   row (t, e, b) is bad if any z_tec, c < C, is not finite
+ *     classifier vote    k = min{c : z_c == max_c z} (fp32 comparisons, the lowest index on ties):  V[0][e][b][k] += 1; a bad row casts none
+ *     p_te = softmax_c((double) z_te), max-subtracted, float64 — the member of bmi_forward_mcd_ensemble
+ *     q_te = (p_t0 + ... + p_te) / (e + 1), summed in exit order and divided once; with weights (bmi_engine_set_ensemble_weights)
+ *            ((W[e][0] p_t0 + W[e][1] p_t1) + ...) + W[e][e] p_te, every product rounded, added from 0.0 — what bmi_forward_mcd_ensemble forms
+ *     ensemble vote      k = min{c : q_c == max_c q}:  V[1][e][b][k] += 1; none if any row i <= e of that (t, b) is bad
+ *     *nonfinite (device int32, ADDED to; NULL: not counted) gains 1 per bad row
+ * V is device int32 [2][E][B][C] and is ADDED to, like S1.  The counts are integers (integer atomic adds, no floating-point atomics):
+ * the same whatever the launch geometry and however the samples are split into chunks, launches, calls or ranks.
+ *
+ * bmi_forward_mcd_votes: bmi_forward_mcd_ensemble with the same arguments, the same bits in S1 / S2 / SL / SH / Q1 / Q2 / QH and the same
+ * scratch (bmi_ensemble_scratch_bytes); behind every chunk's ensemble launch one launch of votes.hip reads the same per-sample logits,
+ * under the handle's calibration map and ensemble weights.  V covers rows 0 .. batch-1 of a share (image_offset).  No allocation and no
+ * synchronisation: capturable.  BMI_ERR_INVALID: a null pointer other than nonfinite, what bmi_forward_mcd_ensemble refuses;
+ * BMI_ERR_UNSUPPORTED: more than 32 exits or 128 classes (and bmi_forward_mcd_ensemble's limits); BMI_ERR_NOMEM: scratch or workspace
+ * too small.  Decided before any HIP call; an error writes nothing. */
+int bmi_forward_mcd_votes(bmi_handle h, const float* x_nchw, int32_t batch, int32_t image_offset, int32_t t_begin, int32_t t_count,
+                          uint64_t seed, int32_t mask_cnt0, double* S1, double* S2, double* SL, double* SH, double* Q1, double* Q2, double* QH,
+                          int32_t* V, int32_t* nonfinite /* device, ADDED to; NULL: not counted */, void* scratch, size_t scratch_bytes,
+                          void* workspace, size_t workspace_bytes, bmi_stream stream);
+
+/* The same counts from a caller's per-sample logits: device fp32 [T][E][B][C] (bmi_forward_mcd_samples' layout).  Every map is optional
+ * and at most one may be given: tau HOST [E], every entry finite and > 0 (rounded like bmi_engine_set_temperature), or NULL; scale_device
+ * + bias_device device fp32 [E][C] (bmi_engine_set_vector_scaling's); matrix_device [E][C][C] + bias_device [E][C]
+ * (bmi_engine_set_matrix_scaling's).  bias_device belongs to the scale or to the matrix: it is given exactly when one of them is.
+ * W_device: device float64 [E][E] row-major, used as given, or NULL (the equal-weight mean).  V is ADDED to: two calls on the halves of T
+ * leave the counts of one call.  BMI_ERR_INVALID (decided before any HIP call): a null logits or V, a count below 1, more than one map,
+ * a bias without its map or a map without its bias, a tau entry that is not finite and > 0.  BMI_ERR_UNSUPPORTED (never a wrong
+ * number): C > 128, E > 32 or T * B >= 2^25 (the launch grid).  An error writes nothing. */
+int bmi_vote_counts(const float* logits, int32_t T, int32_t E, int32_t B, int32_t C, const float* tau /* host [E] or NULL */,
+                    const float* scale_device, const float* bias_device, const float* matrix_device, const double* W_device, int32_t* V,
+                    int32_t* nonfinite, bmi_stream stream);
+
+/* The read-out of V [2][E][batch][C], per kind, exit and image, all three outputs [2][E][batch] and OVERWRITTEN:
+ *     n = sum_c V_c (the votes cast),   m = max_c V_c
+ *     vote_class      = the lowest c with V_c == m                                    int32
+ *     variation_ratio = 1.0 - (double)m / (double)n                                   float64
+ *     vote_entropy    = -sum_{c : V_c > 0} f_c log f_c,  f_c = (double)V_c / (double)n, subtracted in class order from 0.0, in nats
+ *     n == 0:  vote_class = -1, variation_ratio = 1.0, vote_entropy = 0.0             no NaN reaches an output
+ * BMI_ERR_INVALID: a null pointer, a count below 1; BMI_ERR_UNSUPPORTED: 2 * n_exits * batch >= 2^25 (the launch grid). */
+int bmi_finalize_votes(int32_t n_exits, int32_t batch, int32_t out_dim, const int32_t* V, int32_t* vote_class, double* variation_ratio,
+                       double* vote_entropy, bmi_stream stream);
+
 /* Per-op-kind HIP-event timing of bmi_forward_mcd (off by default; adds two event records per
  * launch).  bmi_profile_read synchronises the recorded events and resets the accumulators. */
 int bmi_profile_enable(bmi_handle h, int32_t enable);
