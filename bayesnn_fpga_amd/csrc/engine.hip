@@ -981,18 +981,14 @@ int bmi_engine_set_temperature(bmi_handle h, const float* tau, int32_t n_exits) 
     if (!h) return BMI_ERR_INVALID;
     if (!tau) { h->tau.clear(); h->cal.inv_tau.clear(); return BMI_OK; }
     if (n_exits != h->n_exits) return BMI_ERR_INVALID;
+    Calibration next = h->cal;
+    if (!next.set_tau(tau, n_exits)) return BMI_ERR_INVALID;
     bool ones = true;
-    for (int i = 0; i < n_exits; ++i) {
-        if (!(tau[i] > 0.f) || !std::isfinite(tau[i])) return BMI_ERR_INVALID;
-        const float inv = (float)(1.0 / (double)tau[i]);
-        if (!(inv > 0.f) || !std::isfinite(inv)) return BMI_ERR_INVALID;      // 1 / tau leaves the float32 range
-        ones = ones && tau[i] == 1.f;
-    }
-    if (!ones && (h->cal.vec_scale || h->cal.mat)) return BMI_ERR_INVALID;     // one calibration map at a time: clear the vector / matrix scaling first
+    for (int i = 0; i < n_exits; ++i) ones = ones && tau[i] == 1.f;
+    if (ones) next.inv_tau.clear();
+    if (next.check() != BMI_OK) return BMI_ERR_INVALID;             // a vector / matrix scaling is in force: clear it first
     h->tau.assign(tau, tau + n_exits);
-    h->cal.inv_tau.clear();
-    if (!ones)
-        for (int i = 0; i < n_exits; ++i) h->cal.inv_tau.push_back((float)(1.0 / (double)tau[i]));
+    h->cal = next;
     return BMI_OK;
 }
 
@@ -1012,10 +1008,12 @@ int bmi_engine_set_ensemble_weights(bmi_handle h, const double* W_device, int32_
 int bmi_engine_set_vector_scaling(bmi_handle h, const float* scale_device, const float* bias_device, int32_t n_exits, int32_t out_dim) {
     if (!h) return BMI_ERR_INVALID;
     if (!scale_device) { h->cal.vec_scale = h->cal.vec_bias = nullptr; return BMI_OK; }
-    if (!bias_device || n_exits != h->n_exits || out_dim != h->out_dim) return BMI_ERR_INVALID;
-    if (!h->cal.inv_tau.empty() || h->cal.mat) return BMI_ERR_INVALID;
-    h->cal.vec_scale = scale_device;
-    h->cal.vec_bias = bias_device;
+    if (n_exits != h->n_exits || out_dim != h->out_dim) return BMI_ERR_INVALID;
+    Calibration next = h->cal;
+    next.vec_scale = scale_device;
+    next.vec_bias = bias_device;
+    if (next.check() != BMI_OK) return BMI_ERR_INVALID;             // no bias, or another map is in force
+    h->cal = next;
     return BMI_OK;
 }
 
@@ -1025,10 +1023,12 @@ int bmi_engine_set_vector_scaling(bmi_handle h, const float* scale_device, const
 int bmi_engine_set_matrix_scaling(bmi_handle h, const float* matrix_device, const float* bias_device, int32_t n_exits, int32_t out_dim) {
     if (!h) return BMI_ERR_INVALID;
     if (!matrix_device) { h->cal.mat = h->cal.mat_bias = nullptr; return BMI_OK; }
-    if (!bias_device || n_exits != h->n_exits || out_dim != h->out_dim) return BMI_ERR_INVALID;
-    if (!h->cal.inv_tau.empty() || h->cal.vec_scale) return BMI_ERR_INVALID;
-    h->cal.mat = matrix_device;
-    h->cal.mat_bias = bias_device;
+    if (n_exits != h->n_exits || out_dim != h->out_dim) return BMI_ERR_INVALID;
+    Calibration next = h->cal;
+    next.mat = matrix_device;
+    next.mat_bias = bias_device;
+    if (next.check() != BMI_OK) return BMI_ERR_INVALID;             // no bias, or another map is in force
+    h->cal = next;
     return BMI_OK;
 }
 
@@ -2106,13 +2106,7 @@ static int ensemble_moments_entry(const float* logits, int32_t T, int32_t E, int
                                   double* Q2, double* QH, bmi_stream stream) {
     if (!logits || !Q1 || !Q2 || !QH || T < 1 || E < 1 || B < 1 || C < 1) return BMI_ERR_INVALID;
     if (!ensemble_takes(E, C)) return BMI_ERR_UNSUPPORTED;
-    if (tau)
-        for (int e = 0; e < E; ++e) {
-            if (!(tau[e] > 0.f) || !std::isfinite(tau[e])) return BMI_ERR_INVALID;
-            const float inv = (float)(1.0 / (double)tau[e]);       // (bmi_engine_set_temperature's rounding)
-            if (!(inv > 0.f) || !std::isfinite(inv)) return BMI_ERR_INVALID;
-            cal.inv_tau.push_back(inv);
-        }
+    if (tau && !cal.set_tau(tau, E)) return BMI_ERR_INVALID;
     return launch_ensemble_moments(logits, T, E, B, C, cal, EnsRows(), Q1, Q2, QH, (hipStream_t)stream);
 }
 
@@ -2148,20 +2142,15 @@ int bmi_ensemble_moments_matrix(const float* logits, int32_t T, int32_t E, int32
 int bmi_vote_counts(const float* logits, int32_t T, int32_t E, int32_t B, int32_t C, const float* tau, const float* scale_device,
                     const float* bias_device, const float* matrix_device, const double* W_device, int32_t* V, int32_t* nonfinite, bmi_stream stream) {
     if (!logits || !V || T < 1 || E < 1 || B < 1 || C < 1) return BMI_ERR_INVALID;
-    if ((tau != nullptr) + (scale_device != nullptr) + (matrix_device != nullptr) > 1) return BMI_ERR_INVALID;       // one map at a time
-    if ((bias_device != nullptr) != (scale_device != nullptr || matrix_device != nullptr)) return BMI_ERR_INVALID;   // the bias belongs to a map
-    if (!vote_counts_takes(T, E, B, C)) return BMI_ERR_UNSUPPORTED;
     Calibration cal;
-    if (tau)
-        for (int e = 0; e < E; ++e) {
-            if (!(tau[e] > 0.f) || !std::isfinite(tau[e])) return BMI_ERR_INVALID;
-            const float inv = (float)(1.0 / (double)tau[e]);       // (bmi_engine_set_temperature's rounding)
-            if (!(inv > 0.f) || !std::isfinite(inv)) return BMI_ERR_INVALID;
-            cal.inv_tau.push_back(inv);
-        }
-    if (scale_device) { cal.vec_scale = scale_device; cal.vec_bias = bias_device; }
-    if (matrix_device) { cal.mat = matrix_device; cal.mat_bias = bias_device; }
+    cal.vec_scale = scale_device;
+    cal.mat = matrix_device;
+    (matrix_device ? cal.mat_bias : cal.vec_bias) = bias_device;       // the bias belongs to the map that is given: alone, it fails check()
     cal.ens_w = W_device;
+    if (tau) cal.inv_tau.assign(1, 1.f);                               // "a temperature is given", for check(); set_tau below replaces it
+    if (cal.check() != BMI_OK) return BMI_ERR_INVALID;
+    if (!vote_counts_takes(T, E, B, C)) return BMI_ERR_UNSUPPORTED;    // (E <= 32 before E entries of tau are read)
+    if (tau && !cal.set_tau(tau, E)) return BMI_ERR_INVALID;
     return launch_vote_counts(logits, T, E, B, C, cal, V, nonfinite, (hipStream_t)stream);
 }
 

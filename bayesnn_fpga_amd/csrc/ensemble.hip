@@ -232,8 +232,7 @@ static void dispatch_ens(bool by_rows, bool weighted, const Args&... args) {
 int launch_ensemble_moments(const float* logits, int T, int E, int B, int C, const Calibration& cal, const EnsRows& rows, double* Q1, double* Q2,
                             double* QH, hipStream_t s) {
     if (T < 1 || B < 1 || (rows.list && (rows.Bc < 1 || rows.Bc > B))) return BMI_ERR_INVALID;
-    if ((cal.vec_scale != nullptr) != (cal.vec_bias != nullptr) || (cal.vec_scale && !cal.inv_tau.empty())) return BMI_ERR_INVALID;
-    if ((cal.mat != nullptr) != (cal.mat_bias != nullptr) || (cal.mat && (cal.vec_scale || !cal.inv_tau.empty()))) return BMI_ERR_INVALID;
+    if (cal.check() != BMI_OK) return BMI_ERR_INVALID;
     if (!ensemble_takes(E, C)) return BMI_ERR_UNSUPPORTED;
     const int CS = C | 1;                                // odd row stride
     const int TS = std::min(ENS_SLAB / (E * CS), ENS_ROWS / E);      // >= 1 (ensemble_takes)

@@ -93,7 +93,7 @@ static int head_prepare(HeadArgs& a) {
     if (a.in_mod != a.B && a.in_mod != a.B * a.tc) return BMI_ERR_INVALID;
     if (a.imap && (a.Bc <= 0 || a.Bc > a.B)) return BMI_ERR_INVALID;
     if (!(a.inv_tau >= 0.f) || a.inv_tau > 3.0e38f) return BMI_ERR_INVALID;       // 0: off; else a finite positive 1 / tau
-    if ((a.vec_scale != nullptr) != (a.vec_bias != nullptr) || (a.vec_scale && a.inv_tau != 0.f)) return BMI_ERR_INVALID;   // one calibration map at a time
+    if ((a.vec_scale != nullptr) != (a.vec_bias != nullptr) || (a.vec_scale && a.inv_tau != 0.f)) return BMI_ERR_INVALID;   // at most one map (Calibration::check's rule, on the kernel's own arguments)
     if ((a.mat != nullptr) != (a.mat_bias != nullptr) || (a.mat && (a.inv_tau != 0.f || a.vec_scale))) return BMI_ERR_INVALID;
     if (a.K % 32 != 0 || a.C > 128) return BMI_ERR_UNSUPPORTED;
     if (a.site_logits.kind != BMI_SITE_NONE && a.site_logits.kind != BMI_SITE_ELEMENTWISE) return BMI_ERR_UNSUPPORTED;

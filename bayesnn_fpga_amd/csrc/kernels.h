@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <cmath>
 #include <vector>
 
 #include "../../include/bayesnn_fpga_amd.h"
@@ -229,11 +230,30 @@ bool ensemble_takes(int E, int C);
 //              or a vec_scale: z_c = fl32((..(fl32(mat[e][c][0] * l_0) + fl32(mat[e][c][1] * l_1)) + ..) + mat_bias[e][c]), j ascending
 //   ens_w      the caller's DEVICE float64 [E][E] row-major (not owned), null: the equal-weight mean above; q_te = sum_{i<=e} W[e][i] p_ti in
 //              exit order, the weights as given; of image b only the rows e < n_e[b] are read
+//   set_tau    the ONE place a temperature becomes inv_tau: E host values, each finite and > 0 with a float32 reciprocal that is too; false (and
+//              inv_tau as it was) otherwise.  All ones is stored like any other value: "all ones is off" is bmi_engine_set_temperature's rule only
+//   check      the ONE statement of the rules above (both or neither, one map at a time): BMI_OK or BMI_ERR_INVALID
 struct Calibration {
     std::vector<float> inv_tau;
     const float *vec_scale = nullptr, *vec_bias = nullptr;
     const float *mat = nullptr, *mat_bias = nullptr;
     const double* ens_w = nullptr;
+
+    bool set_tau(const float* tau, int E) {
+        std::vector<float> inv;
+        for (int e = 0; e < E; ++e) {
+            if (!(tau[e] > 0.f) || !std::isfinite(tau[e])) return false;
+            const float v = (float)(1.0 / (double)tau[e]);
+            if (!(v > 0.f) || !std::isfinite(v)) return false;                 // 1 / tau leaves the float32 range
+            inv.push_back(v);
+        }
+        inv_tau.swap(inv);
+        return true;
+    }
+    int check() const {
+        if ((vec_scale != nullptr) != (vec_bias != nullptr) || (mat != nullptr) != (mat_bias != nullptr)) return BMI_ERR_INVALID;
+        return (int)!inv_tau.empty() + (vec_scale != nullptr) + (mat != nullptr) > 1 ? BMI_ERR_INVALID : BMI_OK;
+    }
 };
 // EnsRows (device int32, each null: not used): the launch covers the Bc images list[0 .. Bc-1] of the batch only, and of image b only its first
 // n_e[b] exits; every row that is computed holds the plain launch's bits, the other rows are neither read nor written

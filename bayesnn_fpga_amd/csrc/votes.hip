@@ -200,8 +200,7 @@ static void launch_votes(unsigned grid, unsigned threads, size_t lds, hipStream_
 }
 
 int launch_vote_counts(const float* logits, int T, int E, int B, int C, const Calibration& cal, int* V, int* nonfinite, hipStream_t s) {
-    if ((cal.vec_scale != nullptr) != (cal.vec_bias != nullptr) || (cal.vec_scale && !cal.inv_tau.empty())) return BMI_ERR_INVALID;
-    if ((cal.mat != nullptr) != (cal.mat_bias != nullptr) || (cal.mat && (cal.vec_scale || !cal.inv_tau.empty()))) return BMI_ERR_INVALID;
+    if (cal.check() != BMI_OK) return BMI_ERR_INVALID;
     if (!vote_counts_takes(T, E, B, C)) return BMI_ERR_UNSUPPORTED;
     VoteTau tau;
     for (int e = 0; e < BMI_ENS_MAX_EXITS; ++e) tau.inv[e] = e < E && e < (int)cal.inv_tau.size() ? cal.inv_tau[e] : 1.f;

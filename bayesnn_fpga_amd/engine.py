@@ -14,6 +14,7 @@ path runs in ``libbayesnn_fpga_amd.so``.  What this replaces in the reference:
 """
 import ctypes as C
 import os
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -356,45 +357,17 @@ def check_ensemble_weights(w, n_exits):
     return W
 
 
-def check_vector_scaling(scale, bias, n_exits, out_dim):
-    """Vector scaling as two C-contiguous float32 arrays [E, C] (scale, bias), or (None, None) when ``scale`` is None (off).  ``scale`` / ``bias``:
-    [E, C], or [C] for every exit; ``bias`` None = zeros.  Raises ValueError for any other shape, for a bias without a scale and for a value
-    that is not finite (in float32, what the device is given).  No sign constraint.  Host only."""
-    if scale is None:
+def _check_affine_map(what, name, weight, bias, n_exits, out_dim, tail):
+    """The body of ``check_vector_scaling`` (``tail`` = (C,)) and ``check_matrix_scaling`` (``tail`` = (C, C)): ``weight`` as float32
+    [E, *tail] and ``bias`` as float32 [E, C], C-contiguous, each also taken without the leading E (every exit) and ``bias`` None = zeros;
+    (None, None) when ``weight`` is None.  ``what`` / ``name``: what the messages call the map and its first array."""
+    if weight is None:
         if bias is not None:
-            raise ValueError("vector scaling: a bias needs a scale")
+            raise ValueError(f"{what}: a bias needs a {name}")
         return None, None
     E, Cd = int(n_exits), int(out_dim)
     out = []
-    for name, v in (("scale", scale), ("bias", bias)):
-        if v is None:
-            out.append(np.zeros((E, Cd), dtype=np.float32))
-            continue
-        raw = np.asarray(v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v, dtype=np.float64)
-        if raw.shape == (Cd,):
-            raw = np.broadcast_to(raw, (E, Cd))
-        elif raw.shape != (E, Cd):
-            raise ValueError(f"vector scaling: {name} must be [{E}, {Cd}] or [{Cd}] for {E} exits of {Cd} classes, got {list(raw.shape)}")
-        with np.errstate(over="ignore"):
-            f32 = np.ascontiguousarray(raw, dtype=np.float32)
-        if not (np.all(np.isfinite(raw)) and np.all(np.isfinite(f32))):
-            raise ValueError(f"vector scaling: every {name} value must be finite (in float32 too)")
-        out.append(f32)
-    return out[0], out[1]
-
-
-def check_matrix_scaling(matrix, bias, n_exits, out_dim):
-    """Matrix scaling as two C-contiguous float32 arrays (matrix [E, C, C] — row = output class —, bias [E, C]), or (None, None) when
-    ``matrix`` is None (off).  ``matrix``: [E, C, C], or [C, C] for every exit; ``bias``: [E, C], or [C] for every exit, None = zeros.
-    Raises ValueError for any other shape, for a bias without a matrix and for a value that is not finite (in float32, what the device
-    is given).  No sign constraint.  Host only."""
-    if matrix is None:
-        if bias is not None:
-            raise ValueError("matrix scaling: a bias needs a matrix")
-        return None, None
-    E, Cd = int(n_exits), int(out_dim)
-    out = []
-    for name, v, tail in (("matrix", matrix, (Cd, Cd)), ("bias", bias, (Cd,))):
+    for name, v, tail in ((name, weight, tail), ("bias", bias, (Cd,))):
         if v is None:
             out.append(np.zeros((E,) + tail, dtype=np.float32))
             continue
@@ -402,13 +375,57 @@ def check_matrix_scaling(matrix, bias, n_exits, out_dim):
         if raw.shape == tail:
             raw = np.broadcast_to(raw, (E,) + tail)
         elif raw.shape != (E,) + tail:
-            raise ValueError(f"matrix scaling: {name} must be {[E, *tail]} or {list(tail)} for {E} exits of {Cd} classes, got {list(raw.shape)}")
+            raise ValueError(f"{what}: {name} must be {[E, *tail]} or {list(tail)} for {E} exits of {Cd} classes, got {list(raw.shape)}")
         with np.errstate(over="ignore"):
             f32 = np.ascontiguousarray(raw, dtype=np.float32)
         if not (np.all(np.isfinite(raw)) and np.all(np.isfinite(f32))):
-            raise ValueError(f"matrix scaling: every {name} value must be finite (in float32 too)")
+            raise ValueError(f"{what}: every {name} value must be finite (in float32 too)")
         out.append(f32)
     return out[0], out[1]
+
+
+def check_vector_scaling(scale, bias, n_exits, out_dim):
+    """Vector scaling as two C-contiguous float32 arrays [E, C] (scale, bias), or (None, None) when ``scale`` is None (off).  ``scale`` / ``bias``:
+    [E, C], or [C] for every exit; ``bias`` None = zeros.  Raises ValueError for any other shape, for a bias without a scale and for a value
+    that is not finite (in float32, what the device is given).  No sign constraint.  Host only."""
+    return _check_affine_map("vector scaling", "scale", scale, bias, n_exits, out_dim, (int(out_dim),))
+
+
+def check_matrix_scaling(matrix, bias, n_exits, out_dim):
+    """Matrix scaling as two C-contiguous float32 arrays (matrix [E, C, C] — row = output class —, bias [E, C]), or (None, None) when
+    ``matrix`` is None (off).  ``matrix``: [E, C, C], or [C, C] for every exit; ``bias``: [E, C], or [C] for every exit, None = zeros.
+    Raises ValueError for any other shape, for a bias without a matrix and for a value that is not finite (in float32, what the device
+    is given).  No sign constraint.  Host only."""
+    return _check_affine_map("matrix scaling", "matrix", matrix, bias, n_exits, out_dim, (int(out_dim),) * 2)
+
+
+class CalibrationMap(NamedTuple):
+    """What ``resolve_calibration_map`` returns: ``kind`` None (no map), "temperature", "vector" or "matrix", and the checked host values —
+    ``tau`` (``check_temperature``'s list) for a temperature; ``weight`` (the scale [E, C] or the matrix [E, C, C]) and ``bias`` [E, C],
+    float32, for the other two.  What a kind does not use is None."""
+    kind: Optional[str] = None
+    tau: Optional[list] = None
+    weight: Optional[np.ndarray] = None
+    bias: Optional[np.ndarray] = None
+
+
+def resolve_calibration_map(tau=None, scale=None, bias=None, matrix=None, *, n_exits, out_dim, who):
+    """THE rule of the calibration maps, for every caller that takes one (the engine and model setters, ``ensemble_moments``, ``vote_counts``,
+    ``train.uncertainty.calibrated_logits``): at most one of ``tau`` (``check_temperature``), ``scale`` (``check_vector_scaling``, with
+    ``bias``) and ``matrix`` (``check_matrix_scaling``, with ``bias``), checked by its own function and returned as a ``CalibrationMap``.
+    ValueError — ``who`` names the caller — when two are given together or a bias comes alone, and whatever the check of the one that is
+    given raises.  Host only."""
+    given = [name for name, v in (("tau", tau), ("scale", scale), ("matrix", matrix)) if v is not None]
+    if len(given) > 1:
+        raise ValueError(f"{who}: {' and '.join(given)} were given together (one calibration map at a time)")
+    if bias is not None and scale is None and matrix is None:
+        raise ValueError(f"{who}: a bias needs a scale or a matrix")
+    if matrix is not None:
+        return CalibrationMap("matrix", None, *check_matrix_scaling(matrix, bias, n_exits, out_dim))
+    if scale is not None:
+        return CalibrationMap("vector", None, *check_vector_scaling(scale, bias, n_exits, out_dim))
+    tau = check_temperature(tau, n_exits)
+    return CalibrationMap(None if tau is None else "temperature", tau)
 
 
 def vary_mask(vary, n_exits):
@@ -435,6 +452,11 @@ def check_buffer(t, shape, dtype, device, name):
     return t
 
 
+def _ptr(t):
+    """The device address of a tensor for the C ABI, None for None."""
+    return None if t is None else t.data_ptr()
+
+
 def build_graph(model, device, dtype="f16"):
     g = GraphBuilder(device, dtype)
     fam = getattr(model, "family", None)
@@ -448,6 +470,12 @@ def build_graph(model, device, dtype="f16"):
     else:
         raise TypeError(f"{type(model).__name__} is not a bayesnn_fpga_amd model")
     return g
+
+
+# the calibration maps of an engine, kind -> (what a message calls it, the MCDEngine setter that clears it, the C setter)
+_MAPS = {"temperature": ("temperature", "set_temperature", "bmi_engine_set_temperature"),
+         "vector": ("vector scaling", "set_vector_scaling", "bmi_engine_set_vector_scaling"),
+         "matrix": ("matrix scaling", "set_matrix_scaling", "bmi_engine_set_matrix_scaling")}
 
 
 class CompiledGraph:
@@ -612,61 +640,65 @@ class MCDEngine(CompiledGraph):
         # the non-finite counter of bmi_finalize_checked: allocated HERE, never lazily — a first finalize() inside a hipGraph capture
         # (BatchesInFlight.predict_graphed) would otherwise allocate it from the graph's private pool and re-zero it on every replay
         self._nonfinite = torch.zeros(1, dtype=torch.int32, device=device)
-        # weighted exit ensembles: like the temperature, a model that carries weights (EngineModelMixin.set_exit_ensemble_weights,
-        # train/calibration.py: EnsembleWeights) hands them to every engine built from it
-        self._ens_w_keep = []
+        # like the temperature (CompiledGraph.__init__), the ensemble weights and the vector or matrix scaling a model carries (EngineModelMixin's
+        # set_exit_* setters, train/calibration.py) go to every engine built from it; their device copies live in one list, freed by close()
+        self._cal_keep = []
         self.set_ensemble_weights(getattr(model, "exit_ensemble_weights", None))
-        # vector scaling: a model that carries one (EngineModelMixin.set_exit_vector_scaling, train/calibration.py: VectorScaling) — never
-        # together with a temperature — hands it to every engine built from it
-        self._vec_keep = []
-        vs = getattr(model, "exit_vector_scaling", None)
-        if vs is not None:
-            self.set_vector_scaling(*vs)
-        # matrix scaling (EngineModelMixin.set_exit_matrix_scaling, train/calibration.py: MatrixScaling): the third map, never with the other two
-        self._mat_keep = []
-        ms = getattr(model, "exit_matrix_scaling", None)
-        if ms is not None:
-            self.set_matrix_scaling(*ms)
+        for attr, setter in (("exit_vector_scaling", self.set_vector_scaling), ("exit_matrix_scaling", self.set_matrix_scaling)):
+            if getattr(model, attr, None) is not None:
+                setter(*getattr(model, attr))
 
     ensemble_weights = None       # float64 [E, E] on the host, or None: the equal-weight mean (set_ensemble_weights)
-    _vector_scaling = None        # (scale, bias) float32 [E, C] on the host, or None: off (set_vector_scaling)
-    _matrix_scaling = None        # (matrix [E, C, C], bias [E, C]) float32 on the host, or None: off (set_matrix_scaling)
+    _map = CalibrationMap()       # the map in force (set_temperature / set_vector_scaling / set_matrix_scaling through _set_map); all ones is no temperature
 
     def close(self):
         self.__dict__.pop("_ens_scratch", None)      # (accumulate_ensemble's chunk of per-sample logits)
         super().close()                              # (the handle goes first: nothing reads the weight buffers any more)
-        self.__dict__.pop("_ens_w_keep", None)
-        self.__dict__.pop("_vec_keep", None)
-        self.__dict__.pop("_mat_keep", None)
+        self.__dict__.pop("_cal_keep", None)
+
+    def _set_map(self, kind, m):
+        """What the three setters do with their resolved arguments ``m`` (``m.kind`` is ``kind``, or None: clear that kind — always allowed).
+        A map goes in only while no OTHER kind is in force; then bmi_engine_set_<kind> gets the temperatures, or fresh device copies of the
+        arrays.  A refused call leaves the engine as it was."""
+        on = m.kind is not None and not (kind == "temperature" and all(t == 1.0 for t in m.tau))      # (all ones: off)
+        if on and self._map.kind not in (None, kind):
+            what, clear = _MAPS[self._map.kind][:2]
+            raise ValueError(f"{_MAPS[kind][0]}: a {what} is set on this engine ({clear}(None) first: one calibration map at a time)")
+        if kind == "temperature":
+            super().set_temperature(m.tau)
+        else:
+            args = (None, None, 0, 0)
+            if on:
+                bufs = (torch.from_numpy(m.weight).to(self.device), torch.from_numpy(m.bias).to(self.device))
+                self._cal_keep.append(bufs)          # never freed before close(): a captured launch may still hold an earlier pointer
+                args = (C.c_void_p(bufs[0].data_ptr()), C.c_void_p(bufs[1].data_ptr()), self.n_exits, self.out_dim)
+            _lib.check(getattr(self.lib, _MAPS[kind][2])(self.handle, *args), _MAPS[kind][2])
+        if on:
+            self._map = m
+        elif self._map.kind == kind:
+            self._map = CalibrationMap()
+
+    def _resolve(self, who, **given):
+        return resolve_calibration_map(**given, n_exits=self.n_exits, out_dim=self.out_dim, who=who)
+
+    def _map_arrays(self, kind):
+        return (self._map.weight, self._map.bias) if self._map.kind == kind else None
 
     def set_vector_scaling(self, scale, bias=None):
         """Per-class scale and bias of every exit's logits (bmi_engine_set_vector_scaling; Guo et al. 2017): ``scale`` / ``bias`` as
         ``check_vector_scaling`` takes them — [E, C], or [C] for every exit, ``bias`` None = zeros — or ``scale`` None: off.  From the next
         launch on every path through the fused head and the exit-ensemble launches computes softmax, mean, var, the entropies and the decisions
         of ``z_c = float32(float32(logit_c * scale[e][c]) + bias[e][c])``; ``logit_mean``, ``forward_once`` and ``forward_samples`` stay the raw
-        logits, as under a temperature.  Off, the engine launches the kernels it did: the bits of an engine that never had one.  Mutually
-        exclusive with a temperature: ValueError while one (other than all ones) is set — ``set_temperature(None)`` first.  The arrays live
+        logits, as under a temperature.  Off, the engine launches the kernels it did: the bits of an engine that never had one.  One map
+        at a time: ValueError while a temperature (other than all ones) or a matrix scaling is set — clear it first.  The arrays live
         in device buffers the engine keeps; a hipGraph captured earlier keeps what it was captured with
         (``BatchesInFlight.set_vector_scaling`` discards them)."""
-        a, b = check_vector_scaling(scale, bias, self.n_exits, self.out_dim)
-        if a is None:
-            rc = self.lib.bmi_engine_set_vector_scaling(self.handle, None, None, 0, 0)
-        else:
-            if any(t != 1.0 for t in self.temperature):
-                raise ValueError("vector scaling: a temperature is set on this engine (set_temperature(None) first: one calibration map at a time)")
-            if self._matrix_scaling is not None:
-                raise ValueError("vector scaling: a matrix scaling is set on this engine (set_matrix_scaling(None) first: one calibration map at a time)")
-            bufs = (torch.from_numpy(a).to(self.device), torch.from_numpy(b).to(self.device))
-            self._vec_keep.append(bufs)              # never freed before close(): a captured launch may still hold an earlier pointer
-            rc = self.lib.bmi_engine_set_vector_scaling(self.handle, C.c_void_p(bufs[0].data_ptr()), C.c_void_p(bufs[1].data_ptr()), self.n_exits,
-                                                        self.out_dim)
-        _lib.check(rc, "bmi_engine_set_vector_scaling")
-        self._vector_scaling = None if a is None else (a, b)
+        self._set_map("vector", self._resolve("set_vector_scaling", scale=scale, bias=bias))
 
     @property
     def vector_scaling(self):
         """The vector scaling in force: (scale, bias), float32 [E, C] host arrays, or None when off."""
-        return self._vector_scaling
+        return self._map_arrays("vector")
 
     def set_matrix_scaling(self, matrix, bias=None):
         """A full [C, C] matrix and a bias on every exit's logits (bmi_engine_set_matrix_scaling; Guo et al. 2017): ``matrix`` / ``bias`` as
@@ -675,36 +707,18 @@ class MCDEngine(CompiledGraph):
         mean, var, the entropies and the decisions of ``z = M l + b`` in the head's fp32 — per class the products in ascending j, each
         rounded, added one by one, the bias last (``train.calibration.matrix_logits`` restates it exactly; a diagonal matrix gives
         ``set_vector_scaling``'s bits).  ``logit_mean``, ``forward_once`` and ``forward_samples`` stay the raw logits.  Off, the engine launches
-        the kernels it did.  One calibration map at a time: ValueError while a temperature (other than all ones) or a vector scaling is set.
+        the kernels it did.  One map at a time: ValueError while a temperature (other than all ones) or a vector scaling is set.
         The arrays live in device buffers the engine keeps until ``close()``; a hipGraph captured earlier keeps what it was captured with
         (``BatchesInFlight.set_matrix_scaling`` discards them)."""
-        m, b = check_matrix_scaling(matrix, bias, self.n_exits, self.out_dim)
-        if m is None:
-            rc = self.lib.bmi_engine_set_matrix_scaling(self.handle, None, None, 0, 0)
-        else:
-            if any(t != 1.0 for t in self.temperature):
-                raise ValueError("matrix scaling: a temperature is set on this engine (set_temperature(None) first: one calibration map at a time)")
-            if self._vector_scaling is not None:
-                raise ValueError("matrix scaling: a vector scaling is set on this engine (set_vector_scaling(None) first: one calibration map at a time)")
-            bufs = (torch.from_numpy(m).to(self.device), torch.from_numpy(b).to(self.device))
-            self._mat_keep.append(bufs)              # never freed before close(): a captured launch may still hold an earlier pointer
-            rc = self.lib.bmi_engine_set_matrix_scaling(self.handle, C.c_void_p(bufs[0].data_ptr()), C.c_void_p(bufs[1].data_ptr()), self.n_exits,
-                                                        self.out_dim)
-        _lib.check(rc, "bmi_engine_set_matrix_scaling")
-        self._matrix_scaling = None if m is None else (m, b)
+        self._set_map("matrix", self._resolve("set_matrix_scaling", matrix=matrix, bias=bias))
 
     @property
     def matrix_scaling(self):
         """The matrix scaling in force: (matrix [E, C, C], bias [E, C]), float32 host arrays, or None when off."""
-        return self._matrix_scaling
+        return self._map_arrays("matrix")
 
     def set_temperature(self, tau):
-        tau = check_temperature(tau, self.n_exits)
-        if self._vector_scaling is not None and tau is not None and any(t != 1.0 for t in tau):
-            raise ValueError("temperature: a vector scaling is set on this engine (set_vector_scaling(None) first: one calibration map at a time)")
-        if self._matrix_scaling is not None and tau is not None and any(t != 1.0 for t in tau):
-            raise ValueError("temperature: a matrix scaling is set on this engine (set_matrix_scaling(None) first: one calibration map at a time)")
-        super().set_temperature(tau)
+        self._set_map("temperature", self._resolve("set_temperature", tau=tau))
     set_temperature.__doc__ = CompiledGraph.set_temperature.__doc__
 
     def set_ensemble_weights(self, w):
@@ -720,7 +734,7 @@ class MCDEngine(CompiledGraph):
             rc = self.lib.bmi_engine_set_ensemble_weights(self.handle, None, 0)
         else:
             buf = torch.from_numpy(W).to(self.device)
-            self._ens_w_keep.append(buf)             # never freed before close(): a captured launch may still hold an earlier pointer
+            self._cal_keep.append(buf)               # never freed before close(): a captured launch may still hold an earlier pointer
             rc = self.lib.bmi_engine_set_ensemble_weights(self.handle, C.c_void_p(buf.data_ptr()), self.n_exits)
         _lib.check(rc, "bmi_engine_set_ensemble_weights")
         self.ensemble_weights = W
@@ -932,6 +946,19 @@ class MCDEngine(CompiledGraph):
         self.accumulate_ensemble(x, S, H, Q, QH, t_begin, T, seed, cnt0)
         return self.finalize_ensemble(S, H, Q, QH, T)
 
+    def _held_logits_map(self, who, logits, tau, weights, scale, bias, matrix):
+        """What ``ensemble_moments`` and ``vote_counts`` start from: the shape (T, E, B, C) of the checked ``logits``, the kind of the one map
+        among ``tau`` / ``scale`` / ``matrix`` (``resolve_calibration_map``), and the C arguments — the temperatures as a float array, the
+        map's two arrays and the checked ensemble weights as device tensors (``_ptr`` below) — each None where not given.  The caller holds the
+        device copies until its launch is queued; they are then freed in stream order behind it."""
+        shape = check_buffer(logits, (None,) * 4, torch.float32, self.device, "logits [T, E, B, C]").shape
+        m = resolve_calibration_map(tau, scale, bias, matrix, n_exits=shape[1], out_dim=shape[3], who=who)
+        W = check_ensemble_weights(weights, shape[1])
+        tau_c = None if m.tau is None else (C.c_float * shape[1])(*m.tau)
+        with torch.cuda.device(self.device):
+            dev = [None if h is None else torch.from_numpy(h).to(self.device) for h in (m.weight, m.bias, W)]
+        return (shape, m.kind, tau_c, *dev)
+
     def ensemble_moments(self, logits, tau=None, out=None, t_before=0, weights=None, scale=None, bias=None, matrix=None):
         """The exit-ensemble read-out of per-sample logits the caller holds (bmi_ensemble_moments + bmi_finalize_ensemble): ``logits`` fp32
         [T, E, B, C] on the engine's device (``forward_samples``), ``tau`` None, a scalar or E temperatures (independent of the one set on
@@ -942,17 +969,7 @@ class MCDEngine(CompiledGraph):
         with ``tau``): the members under a vector scaling, bmi_ensemble_moments_vector, with or without ``weights``.  ``matrix`` / ``bias``
         (``check_matrix_scaling``; not together with ``tau`` or ``scale``): the members under a matrix scaling, bmi_ensemble_moments_matrix.
         ``train.uncertainty.decompose_ensemble_logits`` is the host restatement."""
-        T, E, B, Cd = check_buffer(logits, (None,) * 4, torch.float32, self.device, "logits [T, E, B, C]").shape
-        tau = check_temperature(tau, E)
-        W = check_ensemble_weights(weights, E)
-        if matrix is not None:
-            if tau is not None or scale is not None:
-                raise ValueError("ensemble_moments: matrix and tau / scale are mutually exclusive")
-            va, vb = check_matrix_scaling(matrix, bias, E, Cd)
-        else:
-            va, vb = check_vector_scaling(scale, bias, E, Cd)
-        if va is not None and tau is not None:
-            raise ValueError("ensemble_moments: tau and scale / bias are mutually exclusive")
+        (T, E, B, Cd), kind, tau_c, a, b, w = self._held_logits_map("ensemble_moments", logits, tau, weights, scale, bias, matrix)
         if out is None:
             Q = torch.zeros(2, E, B, Cd, dtype=torch.float64, device=self.device)
             QH = torch.zeros(E, B, dtype=torch.float64, device=self.device)
@@ -960,17 +977,13 @@ class MCDEngine(CompiledGraph):
             Q, QH = out
             check_buffer(Q, (2, E, B, Cd), torch.float64, self.device, "out[0] (Q)")
             check_buffer(QH, (E, B), torch.float64, self.device, "out[1] (QH)")
-        tau_c = None if tau is None else (C.c_float * E)(*tau)
+        if kind in ("vector", "matrix"):
+            name, cal = f"bmi_ensemble_moments_{kind}", (_ptr(a), _ptr(b), _ptr(w))
+        elif w is not None:
+            name, cal = "bmi_ensemble_moments_weighted", (tau_c, _ptr(w))
+        else:
+            name, cal = "bmi_ensemble_moments", (tau_c,)
         with torch.cuda.device(self.device):
-            # the device copies stay alive until the launch is queued, and are freed in stream order behind it
-            a_dev, b_dev, w_dev = (None if a is None else torch.from_numpy(a).to(self.device) for a in (va, vb, W))
-            ptr = lambda t: None if t is None else t.data_ptr()
-            if va is not None:
-                name, cal = "bmi_ensemble_moments_matrix" if matrix is not None else "bmi_ensemble_moments_vector", (ptr(a_dev), ptr(b_dev), ptr(w_dev))
-            elif W is not None:
-                name, cal = "bmi_ensemble_moments_weighted", (tau_c, ptr(w_dev))
-            else:
-                name, cal = "bmi_ensemble_moments", (tau_c,)
             rc = getattr(self.lib, name)(logits.data_ptr(), T, E, B, Cd, *cal, Q[0].data_ptr(), Q[1].data_ptr(), QH.data_ptr(), self._stream())
         _lib.check(rc, name)
         r = self._finalize_ensemble_sums(Q, QH, int(t_before) + T)
@@ -1033,28 +1046,14 @@ class MCDEngine(CompiledGraph):
         (``forward_samples``); ``tau``, ``weights``, ``scale`` / ``bias`` and ``matrix`` / ``bias`` as ``ensemble_moments`` takes them (at
         most one map; all independent of what is set on this engine).  Returns V int32 [2, E, B, C]; ``out=V`` ADDS into the counts of
         earlier calls.  ``train.uncertainty.vote_counts_numpy`` is the host restatement; ``finalize_votes`` reads V out."""
-        T, E, B, Cd = check_buffer(logits, (None,) * 4, torch.float32, self.device, "logits [T, E, B, C]").shape
-        tau = check_temperature(tau, E)
-        W = check_ensemble_weights(weights, E)
-        if matrix is not None:
-            if tau is not None or scale is not None:
-                raise ValueError("vote_counts: matrix and tau / scale are mutually exclusive")
-            va, vb = check_matrix_scaling(matrix, bias, E, Cd)
-        else:
-            va, vb = check_vector_scaling(scale, bias, E, Cd)
-        if va is not None and tau is not None:
-            raise ValueError("vote_counts: tau and scale / bias are mutually exclusive")
+        (T, E, B, Cd), kind, tau_c, a, b, w = self._held_logits_map("vote_counts", logits, tau, weights, scale, bias, matrix)
         if out is None:
             V = torch.zeros(2, E, B, Cd, dtype=torch.int32, device=self.device)
         else:
             V = check_buffer(out, (2, E, B, Cd), torch.int32, self.device, "out (V)")
-        tau_c = None if tau is None else (C.c_float * E)(*tau)
+        vec, mat = (None, _ptr(a)) if kind == "matrix" else (_ptr(a), None)
         with torch.cuda.device(self.device):
-            # the device copies stay alive until the launch is queued, and are freed in stream order behind it
-            a_dev, b_dev, w_dev = (None if a is None else torch.from_numpy(a).to(self.device) for a in (va, vb, W))
-            ptr = lambda t: None if t is None else t.data_ptr()
-            vec, mat = (ptr(a_dev), None) if matrix is None else (None, ptr(a_dev))
-            rc = self.lib.bmi_vote_counts(logits.data_ptr(), T, E, B, Cd, tau_c, vec, ptr(b_dev), mat, ptr(w_dev), V.data_ptr(),
+            rc = self.lib.bmi_vote_counts(logits.data_ptr(), T, E, B, Cd, tau_c, vec, _ptr(b), mat, _ptr(w), V.data_ptr(),
                                           self._nonfinite.data_ptr(), self._stream())
         _lib.check(rc, "bmi_vote_counts")
         return V
@@ -1320,30 +1319,37 @@ class MCDEngine(CompiledGraph):
         _lib.check(rc, "bmi_nll_temperature_grid")
         return out
 
+    def _nll_map_grad(self, stem, name, rank, logits, labels, first, bias, out):
+        """``nll_vector_grad`` (``rank`` 1: ``first`` is the scale [E, C]) and ``nll_matrix_grad`` (``rank`` 2: the matrix [E, C, C]):
+        bmi_nll_<stem>_scaling_grad with bmi_nll_<stem>_scratch_bytes; ``name`` is what the messages call ``first``."""
+        T, E, B, Cd, labels = self._nll_args(logits, labels)
+        lead, dims = (E,) + (Cd,) * rank, "[E" + ", C" * rank + "]"
+        first = check_buffer(torch.as_tensor(first, dtype=torch.float64).to(self.device).contiguous(), lead, torch.float64, self.device, f"{name} {dims}")
+        bias = check_buffer(torch.as_tensor(bias, dtype=torch.float64).to(self.device).contiguous(), (E, Cd), torch.float64, self.device, "bias [E, C]")
+        shapes = ((E,), lead, (E, Cd))
+        names = ("nll [E]", f"g_{name} {dims}", "g_bias [E, C]")
+        if out is None:
+            out = tuple(torch.zeros(*shape, dtype=torch.float64, device=self.device) for shape in shapes)
+        elif len(out) != 3:
+            raise ValueError(f"out must be ({', '.join(names)})")
+        else:
+            for i, (o, shape) in enumerate(zip(out, shapes)):
+                check_buffer(o, shape, torch.float64, self.device, f"out[{i}] ({names[i]})")
+        scratch = self._scratch("_nll_scratch", int(getattr(self.lib, f"bmi_nll_{stem}_scratch_bytes")(E, B, Cd)))
+        entry = f"bmi_nll_{stem}_scaling_grad"
+        with torch.cuda.device(self.device):
+            rc = getattr(self.lib, entry)(logits.data_ptr(), T, E, B, Cd, labels.data_ptr(), first.data_ptr(), bias.data_ptr(), out[0].data_ptr(),
+                                          out[1].data_ptr(), out[2].data_ptr(), scratch.data_ptr(), scratch.numel(), self._stream())
+        _lib.check(rc, entry)
+        return out
+
     def nll_vector_grad(self, logits, labels, scale, bias, out=None):
         """Value and gradient of a vector-scaling fit on the device (bmi_nll_vector_scaling_grad): ``logits`` / ``labels`` as ``nll_grid``'s,
         ``scale`` / ``bias`` float64 [E, C] (arrays or tensors; taken as float64: the optimiser's point, not the head's float32).  ADDS, per
         exit, sum_b -log mean_t softmax(l_tb * scale + bias)[y_b] and its gradients into ``out`` = (nll [E], g_scale [E, C], g_bias [E, C]),
         device float64 (zeros when None), and returns the triple: a walk over a loader accumulates.  float64 throughout, the same bits on
         every run; ``train.calibration.nll_vector_numpy`` is its host restatement.  Independent of what is set on this engine."""
-        T, E, B, Cd, labels = self._nll_args(logits, labels)
-        scale = check_buffer(torch.as_tensor(scale, dtype=torch.float64).to(self.device).contiguous(), (E, Cd), torch.float64, self.device, "scale [E, C]")
-        bias = check_buffer(torch.as_tensor(bias, dtype=torch.float64).to(self.device).contiguous(), (E, Cd), torch.float64, self.device, "bias [E, C]")
-        shapes = ((E,), (E, Cd), (E, Cd))
-        if out is None:
-            out = tuple(torch.zeros(*shape, dtype=torch.float64, device=self.device) for shape in shapes)
-        elif len(out) != 3:
-            raise ValueError("out must be (nll [E], g_scale [E, C], g_bias [E, C])")
-        else:
-            for o, shape, name in zip(out, shapes, ("out[0] (nll [E])", "out[1] (g_scale [E, C])", "out[2] (g_bias [E, C])")):
-                check_buffer(o, shape, torch.float64, self.device, name)
-        scratch = self._scratch("_nll_scratch", int(self.lib.bmi_nll_vector_scratch_bytes(E, B, Cd)))
-        with torch.cuda.device(self.device):
-            rc = self.lib.bmi_nll_vector_scaling_grad(logits.data_ptr(), T, E, B, Cd, labels.data_ptr(), scale.data_ptr(), bias.data_ptr(),
-                                                      out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), scratch.data_ptr(),
-                                                      scratch.numel(), self._stream())
-        _lib.check(rc, "bmi_nll_vector_scaling_grad")
-        return out
+        return self._nll_map_grad("vector", "scale", 1, logits, labels, scale, bias, out)
 
     def nll_matrix_grad(self, logits, labels, matrix, bias, out=None):
         """Value and gradient of a matrix-scaling fit on the device (bmi_nll_matrix_scaling_grad): ``logits`` / ``labels`` as ``nll_grid``'s,
@@ -1352,25 +1358,7 @@ class MCDEngine(CompiledGraph):
         (nll [E], g_matrix [E, C, C], g_bias [E, C]), device float64 (zeros when None), and returns the triple: a walk over a loader
         accumulates.  float64 throughout, the same bits on every run; ``train.calibration.nll_matrix_numpy`` is its host restatement.
         Independent of what is set on this engine."""
-        T, E, B, Cd, labels = self._nll_args(logits, labels)
-        matrix = check_buffer(torch.as_tensor(matrix, dtype=torch.float64).to(self.device).contiguous(), (E, Cd, Cd), torch.float64, self.device,
-                              "matrix [E, C, C]")
-        bias = check_buffer(torch.as_tensor(bias, dtype=torch.float64).to(self.device).contiguous(), (E, Cd), torch.float64, self.device, "bias [E, C]")
-        shapes = ((E,), (E, Cd, Cd), (E, Cd))
-        if out is None:
-            out = tuple(torch.zeros(*shape, dtype=torch.float64, device=self.device) for shape in shapes)
-        elif len(out) != 3:
-            raise ValueError("out must be (nll [E], g_matrix [E, C, C], g_bias [E, C])")
-        else:
-            for o, shape, name in zip(out, shapes, ("out[0] (nll [E])", "out[1] (g_matrix [E, C, C])", "out[2] (g_bias [E, C])")):
-                check_buffer(o, shape, torch.float64, self.device, name)
-        scratch = self._scratch("_nll_scratch", int(self.lib.bmi_nll_matrix_scratch_bytes(E, B, Cd)))
-        with torch.cuda.device(self.device):
-            rc = self.lib.bmi_nll_matrix_scaling_grad(logits.data_ptr(), T, E, B, Cd, labels.data_ptr(), matrix.data_ptr(), bias.data_ptr(),
-                                                      out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), scratch.data_ptr(),
-                                                      scratch.numel(), self._stream())
-        _lib.check(rc, "bmi_nll_matrix_scaling_grad")
-        return out
+        return self._nll_map_grad("matrix", "matrix", 2, logits, labels, matrix, bias, out)
 
     def ensemble_nll_grid(self, logits, labels, tau, vary, cand, out=None):
         """The objective of a joint temperature fit of the exit ensembles on the device (bmi_nll_ensemble_temperature_grid): ``logits`` /
@@ -1511,9 +1499,7 @@ class BatchesInFlight:
         """Destroys the engines and drops their workspaces, captured graphs and static buffers (a pipe that is being replaced by a larger
         one, or whose model's weights changed)."""
         self.synchronize()
-        for attr in ("_graphs", "_gstreams"):
-            if hasattr(self, attr):
-                delattr(self, attr)
+        self._drop_graphs()
         for e in self.engines:
             e.close()
             e.workspace = None
@@ -1572,40 +1558,35 @@ class BatchesInFlight:
         kw = dict(max_batch=e0.max_batch, chunk_samples=e0.chunk_samples if e0.chunk_explicit else None, dtype=e0.dtype)
         self.engines += [MCDEngine(self._model, self.device, **kw) for _ in range(n - len(self.engines))]
         self.streams = [torch.cuda.Stream(self.device) for _ in range(n)] if n > 1 else [None]
+        self._drop_graphs()
+        return self
+
+    def _drop_graphs(self):
+        """Forgets the captured hipGraphs and their streams: a captured launch carries its kernel arguments and its instantiation."""
         for attr in ("_graphs", "_gstreams"):
             if hasattr(self, attr):
                 delattr(self, attr)
-        return self
+
+    def _set_on_engines(self, setter, *args):
+        self.synchronize()
+        for e in self.engines:
+            getattr(e, setter)(*args)
+        self._drop_graphs()
 
     def set_temperature(self, tau):
         """``MCDEngine.set_temperature`` on every engine of the pipe; the captured hipGraphs are discarded (after a synchronize): a captured
         launch carries its kernel arguments and its instantiation, so a replay would run under the temperature it was captured with."""
-        self.synchronize()
-        for e in self.engines:
-            e.set_temperature(tau)
-        for attr in ("_graphs", "_gstreams"):
-            if hasattr(self, attr):
-                delattr(self, attr)
+        self._set_on_engines("set_temperature", tau)
 
     def set_vector_scaling(self, scale, bias=None):
         """``MCDEngine.set_vector_scaling`` on every engine of the pipe; the captured hipGraphs are discarded (after a synchronize), like
         ``set_temperature``'s: a replay would run the instantiation and the pointers it was captured with."""
-        self.synchronize()
-        for e in self.engines:
-            e.set_vector_scaling(scale, bias)
-        for attr in ("_graphs", "_gstreams"):
-            if hasattr(self, attr):
-                delattr(self, attr)
+        self._set_on_engines("set_vector_scaling", scale, bias)
 
     def set_matrix_scaling(self, matrix, bias=None):
         """``MCDEngine.set_matrix_scaling`` on every engine of the pipe; the captured hipGraphs are discarded (after a synchronize), like
         ``set_vector_scaling``'s."""
-        self.synchronize()
-        for e in self.engines:
-            e.set_matrix_scaling(matrix, bias)
-        for attr in ("_graphs", "_gstreams"):
-            if hasattr(self, attr):
-                delattr(self, attr)
+        self._set_on_engines("set_matrix_scaling", matrix, bias)
 
     def step(self, x, T, seed=0, cnt0=0, group=None, kind=None, shard=False):
         """One batch step on the next slot — a hipGraph replay (``use_graph``) or eager — with the work partitioned over ``group`` when

@@ -20,6 +20,9 @@ AUTO_IMAGES = 256         # at most this many images of the first batch
 AUTO_CANDIDATES = ("f16", "f16x2")      # (fast, safe); a model may set ``auto_candidates = ("bf16", "bf16x3")`` for the bf16 pipe
 
 
+EXIT_MAPS = {"temperature": "exit_temperature", "vector": "exit_vector_scaling", "matrix": "exit_matrix_scaling"}      # kind -> the model's attribute
+
+
 class EngineModelMixin:
     engine_dtype = "auto"     # "auto" | "f16" | "bf16" | "f16x2" | "bf16x3" | "f32": the default of engine() / model(x) / FullAnalysis / evaluate
     auto_candidates = AUTO_CANDIDATES
@@ -63,36 +66,33 @@ class EngineModelMixin:
         do it themselves; ``train()`` does not — the converter's wrapper uses the training flag to mean "one pass" — so a training loop must)."""
         self._drop_engines()
 
+    def _set_exit_map(self, kind, **given):
+        """The three setters below: ``given`` goes through ``engine.resolve_calibration_map``; a map is stored only while the attributes of
+        the other two kinds are None (None — clearing this kind — is always stored), and the compiled engines are dropped."""
+        from ..engine import model_exits, resolve_calibration_map
+        m = resolve_calibration_map(**given, n_exits=model_exits(self), out_dim=int(self.out_dim), who=f"set_{EXIT_MAPS[kind]}")
+        held = [k for k, attr in EXIT_MAPS.items() if k != kind and getattr(self, attr) is not None]
+        if m.kind is not None and held:
+            raise ValueError(f"set_{EXIT_MAPS[kind]}: {EXIT_MAPS[held[0]]} is set on this model (set_{EXIT_MAPS[held[0]]}(None) first)")
+        setattr(self, EXIT_MAPS[kind], None if m.kind is None else m.tau if kind == "temperature" else (m.weight, m.bias))
+        self._drop_engines()
+
     def set_exit_temperature(self, tau):
         """Per-exit temperature scaling of everything the engines compute from this model's softmax (``MCDEngine.set_temperature``: mean, var,
         the entropies, the early-exit and adaptive-sampling decisions; never the logits): ``tau`` = one value per exit (or a scalar for all),
         finite and > 0, or None = off; ``train.calibration.TemperatureScaling`` fits it on a validation split.  Stored on the model as a plain
         list, and treated like a weight change: compiled engines, pipes with their captured graphs and the ``engine_dtype="auto"`` decision
         were all made under the other softmax and are dropped — the next use rebuilds them (and re-decides "auto") under this one."""
-        from ..engine import check_temperature, model_exits
-        tau = check_temperature(tau, model_exits(self))
-        if tau is not None and self.exit_vector_scaling is not None:
-            raise ValueError("set_exit_temperature: a vector scaling is set (set_exit_vector_scaling(None) first: one calibration map at a time)")
-        if tau is not None and self.exit_matrix_scaling is not None:
-            raise ValueError("set_exit_temperature: a matrix scaling is set (set_exit_matrix_scaling(None) first: one calibration map at a time)")
-        self.exit_temperature = tau
-        self._drop_engines()
+        self._set_exit_map("temperature", tau=tau)
 
     def set_exit_vector_scaling(self, scale, bias=None):
         """Per-exit vector scaling of everything the engines compute from this model's softmax (``MCDEngine.set_vector_scaling``: z_c = l_c *
         scale[e][c] + bias[e][c] in the head's fp32; mean, var, the entropies, the exit ensembles and the decisions; never the logits):
         ``scale`` / ``bias`` [E, C], or [C] for every exit, ``bias`` None = zeros, every value finite; ``scale`` None = off;
         ``train.calibration.VectorScaling`` fits it on a validation split.  Stored on the model as two plain float32 arrays and treated like
-        ``set_exit_temperature``: compiled engines, pipes and the "auto" decision are dropped.  Mutually exclusive with a temperature:
-        ValueError while ``exit_temperature`` is set — ``set_exit_temperature(None)`` first."""
-        from ..engine import check_vector_scaling, model_exits
-        a, b = check_vector_scaling(scale, bias, model_exits(self), int(self.out_dim))
-        if a is not None and self.exit_temperature is not None:
-            raise ValueError("set_exit_vector_scaling: a temperature is set (set_exit_temperature(None) first: one calibration map at a time)")
-        if a is not None and self.exit_matrix_scaling is not None:
-            raise ValueError("set_exit_vector_scaling: a matrix scaling is set (set_exit_matrix_scaling(None) first: one calibration map at a time)")
-        self.exit_vector_scaling = None if a is None else (a, b)
-        self._drop_engines()
+        ``set_exit_temperature``: compiled engines, pipes and the "auto" decision are dropped.  One map at a time: ValueError while
+        ``exit_temperature`` or ``exit_matrix_scaling`` is set — clear it first."""
+        self._set_exit_map("vector", scale=scale, bias=bias)
 
     def set_exit_matrix_scaling(self, matrix, bias=None):
         """Per-exit matrix scaling of everything the engines compute from this model's softmax (``MCDEngine.set_matrix_scaling``: z = M l + b
@@ -100,15 +100,8 @@ class EngineModelMixin:
         decisions; never the logits): ``matrix`` [E, C, C], or [C, C] for every exit, row = output class; ``bias`` [E, C], [C] or None =
         zeros; every value finite; ``matrix`` None = off; ``train.calibration.MatrixScaling`` fits it on a validation split.  Stored on the
         model as two plain float32 arrays and treated like ``set_exit_temperature``: compiled engines, pipes and the "auto" decision are
-        dropped.  One calibration map at a time: ValueError while ``exit_temperature`` or ``exit_vector_scaling`` is set — clear it first."""
-        from ..engine import check_matrix_scaling, model_exits
-        m, b = check_matrix_scaling(matrix, bias, model_exits(self), int(self.out_dim))
-        if m is not None and self.exit_temperature is not None:
-            raise ValueError("set_exit_matrix_scaling: a temperature is set (set_exit_temperature(None) first: one calibration map at a time)")
-        if m is not None and self.exit_vector_scaling is not None:
-            raise ValueError("set_exit_matrix_scaling: a vector scaling is set (set_exit_vector_scaling(None) first: one calibration map at a time)")
-        self.exit_matrix_scaling = None if m is None else (m, b)
-        self._drop_engines()
+        dropped.  One map at a time: ValueError while ``exit_temperature`` or ``exit_vector_scaling`` is set — clear it first."""
+        self._set_exit_map("matrix", matrix=matrix, bias=bias)
 
     def set_exit_ensemble_weights(self, w):
         """The weights of the exit ensembles of everything the engines compute from this model (``MCDEngine.set_ensemble_weights``: the

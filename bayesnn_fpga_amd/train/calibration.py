@@ -41,7 +41,7 @@ is convex in w: EM on the [E, N] table is exact and monotone, runs on the host, 
 
 One scalar per exit cannot correct class-wise miscalibration.  VECTOR SCALING (Guo et al. 2017) gives every exit a per-class scale and
 bias, z_c = a_c * l_c + b_c (``MCDEngine.set_vector_scaling``: two rounded fp32 operations inside the fused head, in place of the
-temperature's product; the two are mutually exclusive), fitted on the same objective with z in place of l / tau,
+temperature's product; never both), fitted on the same objective with z in place of l / tau,
 
     nll_e(a, b) = sum_n -log( (1/T) sum_t softmax(a * l_tn + b)[y_n] ),
 
@@ -55,7 +55,7 @@ whose value and gradient come from the device in one call for all exits (``MCDEn
 Neither map can move probability mass BETWEEN classes: a model that systematically confuses class i with class j — what the early exits
 of a multi-exit network do — needs MATRIX SCALING (Guo et al. 2017), z = M l + b with a full [C, C] matrix per exit
 (``MCDEngine.set_matrix_scaling``: inside the fused head, per class the products in ascending j, each rounded to fp32, added one by one;
-mutually exclusive with the other two maps, which are its special cases).  Its C^2 + C parameters per exit overfit a small split, so the
+never beside the other two maps, which are its special cases).  Its C^2 + C parameters per exit overfit a small split, so the
 fit carries the off-diagonal and bias regulariser of Kull et al. 2019 (ODIR); the same bias term is ``VectorScaling.fit``'s ``bias_l2``.
 
 * ``matrix_z`` / ``matrix_logits`` — the fp32 z of the matrix-scaled head, exactly, and mean / var of its softmax.
@@ -527,7 +527,49 @@ def coordinate_search(eval_fn, n_exits, target, init, mode="vector", sweep_rtol=
     return dict(tau=tau, nll_init=nll_init, nll_after=rows(tau), trace=np.array(trace), sweeps=sweeps, at_bound=at_bound, stopped_by_rule=stopped)
 
 
-class TemperatureScaling:
+# apply(): what a fit sets on the model, kind -> (the model's setter, the entries of the result it takes, the attribute it fills)
+_MODEL_SETTERS = {"temperature": ("set_exit_temperature", ("tau",), "exit_temperature"),
+                  "vector": ("set_exit_vector_scaling", ("scale", "bias"), "exit_vector_scaling"),
+                  "matrix": ("set_exit_matrix_scaling", ("matrix", "bias"), "exit_matrix_scaling"),
+                  "weights": ("set_exit_ensemble_weights", ("weights",), "exit_ensemble_weights")}
+
+
+class _Fit:
+    """What the loader-level fits below share: ``result`` (None before ``fit()``), ``apply()`` and ``save()``.  A subclass names its
+    ``_kind`` (a key of the table above), the kinds ``apply()`` clears first (``_clears``: one calibration map per model) and its file
+    prefix (``_file``)."""
+    result = None
+    _kind = _file = None
+    _clears = ()
+
+    def _require_fit(self):
+        if self.result is None:
+            raise RuntimeError("fit() first")
+        return self.result
+
+    def _save(self, prefix, experiment_id):
+        name = f"{prefix}_{experiment_id}.npz"
+        np.savez(name, **{k: np.asarray(v) for k, v in self._require_fit().items()})
+        return name
+
+    def apply(self):
+        """Sets the fitted values on the model — after clearing the maps they cannot stand beside (``VectorScaling`` and ``MatrixScaling``
+        clear the other two; a temperature clears nothing) — and returns the model's attribute: ``exit_temperature``, ``exit_vector_scaling``,
+        ``exit_matrix_scaling`` or ``exit_ensemble_weights``."""
+        r = self._require_fit()
+        for kind in self._clears:
+            getattr(self.model, _MODEL_SETTERS[kind][0])(None)
+        setter, keys, attr = _MODEL_SETTERS[self._kind]
+        getattr(self.model, setter)(*(r[k] for k in keys))
+        return getattr(self.model, attr)
+
+    def save(self, experiment_id):
+        """Writes ``<prefix>_<id>.npz`` — every entry of the result; the prefix is temperature, vector_scaling, matrix_scaling,
+        ensemble_temperature or ensemble_weights — and returns its name."""
+        return self._save(self._file, experiment_id)
+
+
+class TemperatureScaling(_Fit):
     """Fits one temperature per exit on a labelled (validation) loader.
 
         ts = TemperatureScaling(model, val_loader, gpu=0, mc_passes=10)
@@ -545,7 +587,8 @@ class TemperatureScaling:
         self.model, self.loader, self.gpu = model, val_loader, gpu
         self.mc_passes, self.seed, self.max_logit_bytes = int(mc_passes), int(seed), int(max_logit_bytes)
         self.device = get_device(gpu)
-        self.result = None
+
+    _kind, _file = "temperature", "temperature"
 
     def _n_images(self):
         loader = self.loader
@@ -588,34 +631,49 @@ class TemperatureScaling:
         at_bound [E] each, rounds, n)."""
         from ..engine import model_exits
         batches = self.collect()
-        eng, E = self._engine, model_exits(self.model)
-
-        def eval_fn(tau):
-            out = None
-            grid = torch.from_numpy(np.ascontiguousarray(tau, dtype=np.float32)).to(self.device)
-            for logits, y in batches:
-                out = eng.nll_grid(logits, y, grid, out=out)
-            return out.cpu().numpy()
-
-        r = zoom_search(eval_fn, E, **search)
+        r = zoom_search(lambda tau: self._eval_tau(batches, tau), model_exits(self.model), **search)
         r["n"] = int(sum(y.numel() for _, y in batches))
         self.result = r
         return r
 
-    def apply(self):
-        """``model.set_exit_temperature(tau)`` with the fitted temperatures."""
-        if self.result is None:
-            raise RuntimeError("fit() first")
-        self.model.set_exit_temperature([float(t) for t in self.result["tau"]])
-        return self.model.exit_temperature
+    def _eval_tau(self, batches, tau):
+        """nll [E, G] of the candidate temperatures ``tau`` [E, G] over ``batches``, on the device (``MCDEngine.nll_grid``)."""
+        out = None
+        grid = torch.from_numpy(np.ascontiguousarray(tau, dtype=np.float32)).to(self.device)
+        for logits, y in batches:
+            out = self._engine.nll_grid(logits, y, grid, out=out)
+        return out.cpu().numpy()
 
-    def save(self, experiment_id):
-        """Writes ``temperature_<id>.npz`` (tau, nll_before, nll_after, at_bound, rounds, n) and returns its name."""
-        if self.result is None:
-            raise RuntimeError("fit() first")
-        name = f"temperature_{experiment_id}.npz"
-        np.savez(name, **{k: np.asarray(v) for k, v in self.result.items()})
-        return name
+    def _eval_vector(self, batches, x, C):
+        """Unpenalised (nll [E], grad [E, 2 C]) of the point x [E, 2 C] = (scale, bias) over ``batches``, on the device."""
+        a = torch.from_numpy(np.ascontiguousarray(x[:, :C])).to(self.device)
+        b = torch.from_numpy(np.ascontiguousarray(x[:, C:])).to(self.device)
+        out = None
+        for logits, y in batches:
+            out = self._engine.nll_vector_grad(logits, y, a, b, out=out)
+        return out[0].cpu().numpy(), np.concatenate([out[1].cpu().numpy(), out[2].cpu().numpy()], axis=1)
+
+    def _eval_matrix(self, batches, x, C):
+        """Unpenalised (nll [E], grad [E, C * C + C]) of the point x [E, C * C + C] = (matrix rows, bias) over ``batches``, on the device."""
+        E = x.shape[0]
+        M = torch.from_numpy(np.ascontiguousarray(x[:, :C * C]).reshape(E, C, C)).to(self.device)
+        b = torch.from_numpy(np.ascontiguousarray(x[:, C * C:])).to(self.device)
+        out = None
+        for logits, y in batches:
+            out = self._engine.nll_matrix_grad(logits, y, M, b, out=out)
+        return out[0].cpu().numpy(), np.concatenate([out[1].cpu().numpy().reshape(E, C * C), out[2].cpu().numpy()], axis=1)
+
+    @staticmethod
+    def _round_and_keep(evaluate, penalty, x, x0):
+        """The tail of the vector and the matrix fit: the optimiser's point ``x`` and its start ``x0`` [E, D] rounded to float32 once — what
+        the head will run — and the objective (``evaluate(x)[0]``, plus ``penalty(x)`` [E] where one is given) evaluated once more at both;
+        per exit the rounded start is kept where rounding lost ground against it (a fit that moved: never).  Returns (x float32 [E, D],
+        the unpenalised nll [E], the penalty [E] — zeros without one)."""
+        x32, x032 = (v.astype(np.float32).astype(np.float64) for v in (x, x0))
+        nll, nll0 = evaluate(x32)[0], evaluate(x032)[0]
+        pen, pen0 = (penalty(x32), penalty(x032)) if penalty else (np.zeros_like(nll), np.zeros_like(nll0))
+        keep = nll + pen <= nll0 + pen0
+        return np.where(keep[:, None], x32, x032).astype(np.float32), np.where(keep, nll, nll0), np.where(keep, pen, pen0)
 
 
 class VectorScaling(TemperatureScaling):
@@ -641,70 +699,36 @@ class VectorScaling(TemperatureScaling):
         never evaluated."""
         from ..engine import model_exits
         batches = self.collect()
-        eng, E, C = self._engine, model_exits(self.model), int(self.model.out_dim)
+        E, C = model_exits(self.model), int(self.model.out_dim)
         n = int(sum(y.numel() for _, y in batches))
         bias_l2 = float(bias_l2)
         if bias_l2 < 0 or not np.isfinite(bias_l2):
             raise ValueError("bias_l2 must be finite and >= 0")
 
-        def eval_tau(tau):
-            out = None
-            grid = torch.from_numpy(np.ascontiguousarray(tau, dtype=np.float32)).to(self.device)
-            for logits, y in batches:
-                out = eng.nll_grid(logits, y, grid, out=out)
-            return out.cpu().numpy()
-
         def eval_vec(x):
-            a = torch.from_numpy(np.ascontiguousarray(x[:, :C])).to(self.device)
-            b = torch.from_numpy(np.ascontiguousarray(x[:, C:])).to(self.device)
-            out = None
-            for logits, y in batches:
-                out = eng.nll_vector_grad(logits, y, a, b, out=out)
-            return out[0].cpu().numpy(), np.concatenate([out[1].cpu().numpy(), out[2].cpu().numpy()], axis=1)
+            return self._eval_vector(batches, x, C)
 
-        def eval_pen(x):                                         # (bias_l2 > 0 only)
+        def pen_of(x):                                           # (bias_l2 > 0 only)
+            return odir_penalty(None, x[:, C:], n, 0.0, bias_l2)
+
+        def eval_pen(x):
             f, g = eval_vec(x)
-            pv, _, pg = odir_penalty(None, x[:, C:], n, 0.0, bias_l2)
+            pv, _, pg = pen_of(x)
             g[:, C:] += pg
             return f + pv, g
 
-        z = zoom_search(eval_tau, E, **search)
+        z = zoom_search(lambda tau: self._eval_tau(batches, tau), E, **search)
         inv = 1.0 / np.asarray(z["tau"], dtype=np.float32).astype(np.float64)
         x0 = np.concatenate([np.repeat(inv[:, None], C, axis=1), np.zeros((E, C))], axis=1)
         r = lbfgs_minimize(eval_pen if bias_l2 else eval_vec, x0, max_iter=max_iter, gtol=gtol, history=history)
-        x32 = r["x"].astype(np.float32)
-        x032 = x0.astype(np.float32)
-        nll_after = eval_vec(x32.astype(np.float64))[0]
-        nll_x0 = eval_vec(x032.astype(np.float64))[0]
-        if bias_l2:
-            pen, pen0 = (odir_penalty(None, v[:, C:].astype(np.float64), n, 0.0, bias_l2)[0] for v in (x32, x032))
-            keep = nll_after + pen <= nll_x0 + pen0
-        else:
-            keep = nll_after <= nll_x0                           # (a fit that moved: always)
-        x32 = np.where(keep[:, None], x32, x032)
-        nll_after = np.where(keep, nll_after, nll_x0)
-        extra = dict(penalty=np.where(keep, pen, pen0)) if bias_l2 else {}
+        x32, nll_after, pen = self._round_and_keep(eval_vec, (lambda x: pen_of(x)[0]) if bias_l2 else None, r["x"], x0)
+        extra = dict(penalty=pen) if bias_l2 else {}
         self.result = dict(**extra, scale=np.ascontiguousarray(x32[:, :C]), bias=np.ascontiguousarray(x32[:, C:]), nll_start=z["nll_after"], nll_after=nll_after,
                            grad_norm=np.max(np.abs(r["g"]), axis=1), iterations=r["iterations"], converged=r["converged"],
                            tau=np.asarray(z["tau"]), n=n)
         return self.result
 
-    def apply(self):
-        """Clears the model's temperature and sets the fitted scaling: ``model.set_exit_vector_scaling(scale, bias)``."""
-        if self.result is None:
-            raise RuntimeError("fit() first")
-        self.model.set_exit_temperature(None)
-        self.model.set_exit_matrix_scaling(None)
-        self.model.set_exit_vector_scaling(self.result["scale"], self.result["bias"])
-        return self.model.exit_vector_scaling
-
-    def save(self, experiment_id):
-        """Writes ``vector_scaling_<id>.npz`` (every entry of the result) and returns its name."""
-        if self.result is None:
-            raise RuntimeError("fit() first")
-        name = f"vector_scaling_{experiment_id}.npz"
-        np.savez(name, **{k: np.asarray(v) for k, v in self.result.items()})
-        return name
+    _kind, _file, _clears = "vector", "vector_scaling", ("temperature", "matrix")
 
 
 class MatrixScaling(VectorScaling):
@@ -733,16 +757,6 @@ class MatrixScaling(VectorScaling):
 
     def collect(self):
         return self._held if self._held is not None else super().collect()
-
-    def _eval_matrix(self, batches, x, C):
-        """Unpenalised (nll [E], grad [E, C * C + C]) of the point x [E, C * C + C] = (matrix rows, bias) over ``batches``, on the device."""
-        E = x.shape[0]
-        M = torch.from_numpy(np.ascontiguousarray(x[:, :C * C]).reshape(E, C, C)).to(self.device)
-        b = torch.from_numpy(np.ascontiguousarray(x[:, C * C:])).to(self.device)
-        out = None
-        for logits, y in batches:
-            out = self._engine.nll_matrix_grad(logits, y, M, b, out=out)
-        return out[0].cpu().numpy(), np.concatenate([out[1].cpu().numpy().reshape(E, C * C), out[2].cpu().numpy()], axis=1)
 
     def fit(self, off_diag_l2=0.0, bias_l2=0.0, max_iter=50, gtol=1e-5, history=10, **search):
         """Walk + vector fit (``VectorScaling.fit(max_iter, gtol, history, **search)``, unregularised) + L-BFGS on the matrix.  Returns — and
@@ -779,14 +793,9 @@ class MatrixScaling(VectorScaling):
             M0[:, np.arange(C), np.arange(C)] = a0
             x0 = np.concatenate([M0.reshape(E, C * C), b0], axis=1)          # (float32 values: the vector fit's rounded result)
             r = lbfgs_minimize(objective, x0, max_iter=max_iter, gtol=gtol, history=history)
-            x32 = r["x"].astype(np.float32).astype(np.float64)
-            nll_after = self._eval_matrix(batches, x32, C)[0]
-            nll_x0 = self._eval_matrix(batches, x0, C)[0]
-            pen, pen0 = pen_of(x32)[0], pen_of(x0)[0]
-            keep = nll_after + pen <= nll_x0 + pen0                          # (a fit that moved: always)
-            x32 = np.where(keep[:, None], x32, x0).astype(np.float32)
+            x32, nll_after, pen = self._round_and_keep(lambda x: self._eval_matrix(batches, x, C), lambda x: pen_of(x)[0], r["x"], x0)
             self.result = dict(matrix=np.ascontiguousarray(x32[:, :C * C].reshape(E, C, C)), bias=np.ascontiguousarray(x32[:, C * C:]),
-                               nll_start=np.asarray(v["nll_after"]), nll_after=np.where(keep, nll_after, nll_x0), penalty=np.where(keep, pen, pen0),
+                               nll_start=np.asarray(v["nll_after"]), nll_after=nll_after, penalty=pen,
                                grad_norm=np.max(np.abs(r["g"]), axis=1), iterations=r["iterations"], converged=r["converged"],
                                scale0=v["scale"], bias0=v["bias"], tau=np.asarray(v["tau"]), n=n)
         finally:
@@ -825,22 +834,7 @@ class MatrixScaling(VectorScaling):
         self.selected = best
         return table
 
-    def apply(self):
-        """Clears the model's temperature and vector scaling and sets the fitted map: ``model.set_exit_matrix_scaling(matrix, bias)``."""
-        if self.result is None:
-            raise RuntimeError("fit() first")
-        self.model.set_exit_temperature(None)
-        self.model.set_exit_vector_scaling(None)
-        self.model.set_exit_matrix_scaling(self.result["matrix"], self.result["bias"])
-        return self.model.exit_matrix_scaling
-
-    def save(self, experiment_id):
-        """Writes ``matrix_scaling_<id>.npz`` (every entry of the result) and returns its name."""
-        if self.result is None:
-            raise RuntimeError("fit() first")
-        name = f"matrix_scaling_{experiment_id}.npz"
-        np.savez(name, **{k: np.asarray(v) for k, v in self.result.items()})
-        return name
+    _kind, _file, _clears = "matrix", "matrix_scaling", ("temperature", "vector")
 
 
 class EnsembleTemperatureScaling(TemperatureScaling):
@@ -872,13 +866,7 @@ class EnsembleTemperatureScaling(TemperatureScaling):
         extra = {}
         if isinstance(init, str):
             if init == "per_exit":
-                def per_exit_fn(tau):
-                    out = None
-                    grid = torch.from_numpy(np.ascontiguousarray(tau, dtype=np.float32)).to(self.device)
-                    for logits, y in batches:
-                        out = eng.nll_grid(logits, y, grid, out=out)
-                    return out.cpu().numpy()
-                init = zoom_search(per_exit_fn, E)["tau"]
+                init = zoom_search(lambda tau: self._eval_tau(batches, tau), E)["tau"]
                 extra["nll_per_exit"] = eval_fn(init, None, np.ones(1))[:, 0]
             elif init == "ones":
                 init = np.ones(E)
@@ -892,13 +880,7 @@ class EnsembleTemperatureScaling(TemperatureScaling):
         self.result = r
         return r
 
-    def save(self, experiment_id):
-        """Writes ``ensemble_temperature_<id>.npz`` (the result dict) and returns its name."""
-        if self.result is None:
-            raise RuntimeError("fit() first")
-        name = f"ensemble_temperature_{experiment_id}.npz"
-        np.savez(name, **{k: np.asarray(v) for k, v in self.result.items()})
-        return name
+    _file = "ensemble_temperature"
 
 
 # ---- the weights of the exit ensembles -----------------------------------------------------------------------------------------------
@@ -950,7 +932,7 @@ def mixture_weights_em(A, rtol=1e-12, max_iter=100000):
     return dict(w=w, nll=nll, nll_uniform=trace[0], trace=np.array(trace), iterations=it, converged=converged)
 
 
-class EnsembleWeights:
+class EnsembleWeights(_Fit):
     """Fits the weights of the exit ensembles on a labelled (validation) loader, by maximum likelihood per row.
 
         ew = EnsembleWeights(model, val_loader, gpu=0, mc_passes=10)
@@ -967,7 +949,8 @@ class EnsembleWeights:
         self.model, self.loader, self.gpu = model, val_loader, gpu
         self.mc_passes, self.seed = int(mc_passes), int(seed)
         self.device = get_device(gpu)
-        self.result = None
+
+    _kind, _file = "weights", "ensemble_weights"
 
     def _engine_for(self, x):
         return self.model.engine(self.device, max_batch=x.shape[0], calib=x)
@@ -1009,18 +992,3 @@ class EnsembleWeights:
                            iterations=np.array([r["iterations"] for r in rows]), converged=np.array([r["converged"] for r in rows]),
                            n=int(A.shape[1]))
         return self.result
-
-    def apply(self):
-        """``model.set_exit_ensemble_weights(W)`` with the fitted matrix."""
-        if self.result is None:
-            raise RuntimeError("fit() first")
-        self.model.set_exit_ensemble_weights(self.result["weights"])
-        return self.model.exit_ensemble_weights
-
-    def save(self, experiment_id):
-        """Writes ``ensemble_weights_<id>.npz`` (the result dict) and returns its name."""
-        if self.result is None:
-            raise RuntimeError("fit() first")
-        name = f"ensemble_weights_{experiment_id}.npz"
-        np.savez(name, **{k: np.asarray(v) for k, v in self.result.items()})
-        return name

@@ -52,33 +52,23 @@ def weighted_exit_ensembles(per_exit, W):
 
 def calibrated_logits(logits, tau=None, weights=None, scale=None, bias=None, matrix=None):
     """(z, W): the calibrated fp32 logits z [T, E, B, C] of per-pass logits under at most one map — the head's own numbers, as
-    ``decompose_ensemble_logits`` states them — and the checked ensemble weights float64 [E, E], or None."""
+    ``decompose_ensemble_logits`` states them — and the checked ensemble weights float64 [E, E], or None.  The map is
+    ``engine.resolve_calibration_map``'s: a ``tau`` the engines refuse (not finite and > 0) is refused here too."""
     l = np.asarray(logits, dtype=np.float32)
     if l.ndim != 4:
         raise ValueError("logits must be [T, E, B, C]")
-    T, E = l.shape[:2]
-    if tau is not None:
-        t32 = np.asarray(tau, dtype=np.float64).astype(np.float32)
-        t32 = np.repeat(t32.reshape(-1), E) if t32.ndim == 0 else t32.reshape(-1)
-        if t32.size != E:
-            raise ValueError(f"tau: expected one value per exit ({E}), got {t32.size}")
-        inv = (1.0 / t32.astype(np.float64)).astype(np.float32)
+    from ..engine import check_ensemble_weights, resolve_calibration_map
+    E = l.shape[1]
+    m = resolve_calibration_map(tau, scale, bias, matrix, n_exits=E, out_dim=l.shape[3], who="calibrated_logits")
+    if m.kind == "temperature":
+        inv = (1.0 / np.asarray(m.tau, dtype=np.float64).astype(np.float32).astype(np.float64)).astype(np.float32)
         l = (l * inv[None, :, None, None]).astype(np.float32)
-    if scale is not None:
-        if tau is not None:
-            raise ValueError("tau and scale / bias are mutually exclusive")
-        from ..engine import check_vector_scaling
-        va, vb = check_vector_scaling(scale, bias, E, l.shape[3])
-        l = ((l * va[None, :, None, :]).astype(np.float32) + vb[None, :, None, :]).astype(np.float32)
-    if matrix is not None:
-        if tau is not None or scale is not None:
-            raise ValueError("matrix and tau / scale are mutually exclusive")
+    elif m.kind == "vector":
+        l = ((l * m.weight[None, :, None, :]).astype(np.float32) + m.bias[None, :, None, :]).astype(np.float32)
+    elif m.kind == "matrix":
         from .calibration import matrix_z
-        l = matrix_z(l, matrix, bias)
-    W = None
-    if weights is not None:
-        from ..engine import check_ensemble_weights
-        W = check_ensemble_weights(weights, E)
+        l = matrix_z(l, m.weight, m.bias)
+    W = check_ensemble_weights(weights, E)
     return l, W
 
 

@@ -14,6 +14,10 @@ Cases.  Inputs synthetic_images(B, seed=1234), weights synthetic_weights_(model,
      under a temperature, under a vector scaling with ensemble weights); the dynamic-exit and adaptive families of DYNAMIC.
   2. predict at the small plan max_batch = 37, chunk = 4, T = 9 (SMALL): no planar lazy layout, other split-K counts.
   3. resnet18_me f16 under BMI_MASK_BITS=1 and under BMI_CONV_PAIR=0 (read at bmi_create).
+  4. the calibration maps (``calibration_family``; ``--only calibration`` runs nothing else), resnet18_me f16 at max_batch = 37, chunk = 4,
+     T = 9: predict_ensemble under a matrix scaling; predict_votes under each of the three maps, with and without ensemble weights;
+     ensemble_moments and vote_counts on held forward_samples logits with each map passed as arguments; nll_grid, nll_vector_grad,
+     nll_matrix_grad and ensemble_nll_grid on those logits.
 The thresholds of the dynamic cases come from the engine's own predictions by the rules of ``exit_threshold`` / ``sem_threshold`` below, so
 that images leave at the first tested exit and others go on, and so that the adaptive walk runs its full-grid form first and its image-list
 form afterwards; they are printed with each line, as are active_after / active_after_step.
@@ -147,9 +151,44 @@ def dynamic_family(run, name, dtype):
     run.close(eng)
 
 
+def calibration_family(run, name="resnet18_me", dtype="f16", B=37, T=9):
+    tag = f"{name}/{dtype} B={B} T={T}"
+    eng, x = run.engine(name, dtype, max_batch=B, chunk=4), run.images(B)
+    E, Cd = eng.n_exits, eng.out_dim
+    rng = np.random.default_rng(7)
+    tau = [1.5, 1.25, 0.8, 2.0, 0.6][:E]
+    scale, vbias = np.linspace(0.5, 1.5, E * Cd).reshape(E, Cd), np.linspace(-0.25, 0.25, E * Cd).reshape(E, Cd)
+    matrix = np.eye(Cd)[None] * scale[:, :, None] + rng.uniform(-0.1, 0.1, (E, Cd, Cd))
+    weights = [float(i + 1) for i in range(E)]
+    maps = (("temperature", eng.set_temperature, (tau,), dict(tau=tau)), ("vector", eng.set_vector_scaling, (scale, vbias), dict(scale=scale, bias=vbias)),
+            ("matrix", eng.set_matrix_scaling, (matrix, vbias), dict(matrix=matrix, bias=vbias)))
+    eng.set_matrix_scaling(matrix, vbias)
+    run.case(f"predict_ensemble matrix {tag}", eng, lambda: eng.predict_ensemble(x, T, seed=SEED))
+    eng.set_matrix_scaling(None)
+    for kind, setter, args, _ in maps:
+        setter(*args)
+        for w in (None, weights):
+            eng.set_ensemble_weights(w)
+            run.case(f"predict_votes {kind} weights={int(w is not None)} {tag}", eng, lambda: eng.predict_votes(x, T, seed=SEED))
+        setter(None)
+    logits = eng.forward_samples(x, T, seed=SEED)
+    labels = torch.from_numpy(rng.integers(0, Cd, B)).to(run.dev)
+    for kind, _, _, kw in maps:
+        for w in (None, weights):
+            run.case(f"ensemble_moments {kind} weights={int(w is not None)} {tag}", eng, lambda: eng.ensemble_moments(logits, weights=w, **kw))
+            run.case(f"vote_counts {kind} weights={int(w is not None)} {tag}", eng, lambda: eng.vote_counts(logits, weights=w, **kw))
+    grid = np.exp(np.linspace(np.log(0.25), np.log(4.0), 7))[None].repeat(E, 0)
+    run.case(f"nll_grid {tag}", eng, lambda: eng.nll_grid(logits, labels, grid))
+    run.case(f"nll_vector_grad {tag}", eng, lambda: eng.nll_vector_grad(logits, labels, scale, vbias))
+    run.case(f"nll_matrix_grad {tag}", eng, lambda: eng.nll_matrix_grad(logits, labels, matrix, vbias))
+    run.case(f"ensemble_nll_grid {tag}", eng, lambda: eng.ensemble_nll_grid(logits, labels, tau, [0, E - 1], grid[0]))
+    run.close(eng)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default="", help="also write the lines to this file")
+    ap.add_argument("--only", default="", choices=("", "calibration"), help="run this family of cases alone")
     a = ap.parse_args()
     f = open(a.out, "w") if a.out else None
 
@@ -161,6 +200,12 @@ def main():
 
     run = Runner(out)
     out(f"# {torch.cuda.get_device_name(0)}; ABI {_lib.lib().bmi_version()}")
+    if a.only == "calibration":
+        calibration_family(run)
+        out(f"# done: {run.cases} cases")
+        if f:
+            f.close()
+        return
     x = run.images()
     for name, dtype in PREDICT:
         eng = run.engine(name, dtype)
@@ -203,6 +248,7 @@ def main():
             run.close(eng)
         finally:
             del os.environ[var]
+    calibration_family(run)
     out(f"# done: {run.cases} cases")
     if f:
         f.close()
