@@ -17,6 +17,7 @@ DTYPES = {"f16": DTYPE_F16, "bf16": DTYPE_BF16, "f32": DTYPE_F32, "f16x2": DTYPE
 FP32_ACT_DTYPES = ("f32", "f16x2", "bf16x3")      # engines that keep fp32 activations in the workspace
 OP_STEM, OP_CONV, OP_MASK, OP_HEAD, OP_MAXPOOL, OP_DENSE = 1, 2, 3, 4, 5, 6
 STOP_RULES = {"sem": 0, "margin": 1}      # BMI_STOP_* of bmi_forward_mcd_adaptive
+VOTE_STOP_RULES = {**STOP_RULES, "votes": 2}      # ... of bmi_forward_mcd_adaptive_votes, which alone takes BMI_STOP_VOTES
 EXIT_RULES = {"confidence": 0, "margin": 1}      # BMI_EXIT_* of bmi_forward_mcd_exit_staged
 STOP_ON = {"exit": 0, "ensemble": 1}      # BMI_STOP_ON_* of bmi_forward_mcd_adaptive_ensemble
 NLL_VEC_SLAB, NLL_VEC_ROWS = 3456, 64       # bmi_nll_vector_scaling_grad stages min(NLL_VEC_ROWS, NLL_VEC_SLAB // (C | 1)) samples per chunk
@@ -140,6 +141,15 @@ _PROTOS = {
                               [C.c_void_p] * 10 + [C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
     "bmi_vote_counts": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float)] + [C.c_void_p] * 7),
     "bmi_finalize_votes": (C.c_int, [C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 5),
+    "bmi_vote_counts_rows": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float)] + [C.c_void_p] * 5 +
+                             [C.c_int32] + [C.c_void_p] * 4),
+    "bmi_vote_decide": (C.c_int, [C.c_void_p] + [C.c_int32] * 8 + [C.c_void_p, C.c_int32] + [C.c_void_p] * 4),
+    "bmi_forward_mcd_adaptive_votes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_int32,
+                                                 C.c_int32, C.c_double, C.c_int32, C.c_int32] + [C.c_void_p] * 10 + [C.c_size_t] +
+                                       [C.c_void_p] * 2 + [C.POINTER(C.c_int32), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "bmi_forward_mcd_exit_staged_votes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_uint64, C.c_int32, C.POINTER(ExitRule)] +
+                                          [C.c_void_p] * 10 + [C.c_size_t, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p, C.c_size_t,
+                                                               C.c_void_p]),
     "bmi_profile_enable": (C.c_int, [C.c_void_p, C.c_int32]),
     "bmi_profile_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "bmi_philox_mask": (C.c_int, [C.c_void_p, C.c_int64, C.c_uint64, C.c_int32, C.c_int32, C.c_float, C.c_void_p]),

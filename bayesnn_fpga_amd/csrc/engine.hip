@@ -1879,10 +1879,11 @@ int bmi_forward_mcd_exit(bmi_handle h, const float* x_nchw, int32_t batch, int32
 
 // bmi_forward_mcd_exit_staged (ens null) and bmi_forward_mcd_exit_staged_ensemble: with ens every stage's heads also leave their logits in
 // the one [t_count][E][batch][C] scratch (active images only), and ONE launch of ensemble.hip behind the last stage that ran adds, for
-// every image, the exits it reached (n_e[b] = exit_of_image[b] + 1) to the ensemble sums
+// every image, the exits it reached (n_e[b] = exit_of_image[b] + 1) to the ensemble sums; votes (bmi_forward_mcd_exit_staged_votes, with ens
+// only): one launch of votes_rows.hip behind it, with the same n_e, adds their votes
 static int exit_staged(bmi_handle h, const float* x_nchw, int32_t batch, int32_t t_count, uint64_t seed, int32_t mask_cnt0,
                        const bmi_exit_rule* rule, double* S1, double* S2, double* SL, double* SH, int32_t* exit_of_image, int32_t* active_after,
-                       void* workspace, size_t workspace_bytes, bmi_stream stream, const EnsembleSums* ens) {
+                       void* workspace, size_t workspace_bytes, bmi_stream stream, const EnsembleSums* ens, const VoteCounts* votes = nullptr) {
     if (!h || !x_nchw || !rule || !S1 || !S2 || !SL || !workspace || !exit_of_image || !active_after) return BMI_ERR_INVALID;
     BmiOptionScope opt_scope(&h->opts);
     if (rule->criterion != BMI_EXIT_CONFIDENCE && rule->criterion != BMI_EXIT_MARGIN) return BMI_ERR_INVALID;
@@ -1912,7 +1913,11 @@ static int exit_staged(bmi_handle h, const float* x_nchw, int32_t batch, int32_t
         int* const n_e = on.lists[0];
         const int rce = launch_exit_counts(exit_of_image, batch, n_e, s);
         if (rce != BMI_OK) return rce;
-        return ensemble_add(h, *ens, t_count, batch, s, EnsRows{nullptr, 0, n_e});
+        const int rca = ensemble_add(h, *ens, t_count, batch, s, EnsRows{nullptr, 0, n_e});
+        if (rca != BMI_OK || !votes) return rca;
+        // (not recorded, as in forward_folded: the profile table has no slot for it)
+        return launch_vote_counts_rows(ens->scratch, t_count, h->n_exits, batch, h->out_dim, h->cal, EnsRows{nullptr, 0, n_e}, votes->V,
+                                       votes->nonfinite, s);
     };
     std::vector<const OpInfo*> stage_ops;
     for (int k = 0; fe + k <= last; ++k) {
@@ -1963,20 +1968,37 @@ int bmi_forward_mcd_exit_staged_ensemble(bmi_handle h, const float* x_nchw, int3
                        stream, &ens);
 }
 
+int bmi_forward_mcd_exit_staged_votes(bmi_handle h, const float* x_nchw, int32_t batch, int32_t t_count, uint64_t seed, int32_t mask_cnt0,
+                                      const bmi_exit_rule* rule, double* S1, double* S2, double* SL, double* SH, double* Q1, double* Q2,
+                                      double* QH, int32_t* V, int32_t* nonfinite, void* scratch, size_t scratch_bytes, int32_t* exit_of_image,
+                                      int32_t* active_after, void* workspace, size_t workspace_bytes, bmi_stream stream) {
+    if (!V) return BMI_ERR_INVALID;
+    const int rce = ensemble_args_ok(h, batch, Q1, Q2, QH, scratch, scratch_bytes);
+    if (rce != BMI_OK) return rce;
+    if (!vote_counts_takes(h->chunk, h->n_exits, batch, h->out_dim)) return BMI_ERR_UNSUPPORTED;
+    const EnsembleSums ens{Q1, Q2, QH, (float*)scratch};
+    const VoteCounts votes{V, nonfinite};
+    return exit_staged(h, x_nchw, batch, t_count, seed, mask_cnt0, rule, S1, S2, SL, SH, exit_of_image, active_after, workspace, workspace_bytes,
+                       stream, &ens, &votes);
+}
+
 // bmi_forward_mcd_adaptive (ens null) and bmi_forward_mcd_adaptive_ensemble: with ens every step's heads also leave their logits in the
 // scratch (one step of [t_step][E][batch][C]) and one launch of ensemble.hip behind them adds the step's samples of the images that ran it
 // to the ensemble sums — the full form while nobody has retired, the image-list form afterwards; stop_on = BMI_STOP_ON_ENSEMBLE: the rule
-// reads Q1 / Q2 at row test_exit in place of S1 / S2
+// reads Q1 / Q2 at row test_exit in place of S1 / S2.  votes (bmi_forward_mcd_adaptive_votes, with ens only): one launch of votes_rows.hip
+// behind the ensemble launch adds the step's votes of the same images; rule BMI_STOP_VOTES then decides on row test_exit of V[stop_on],
+// threshold = the slack.  rule_rc: the entry point's own verdict on rule and threshold (which rules it takes is its contract, not this
+// function's), returned where the rule was always checked
 static int adaptive(bmi_handle h, const float* x_nchw, int32_t batch, int32_t image_offset, int32_t t_max, int32_t t_step, uint64_t seed,
                     int32_t mask_cnt0, int32_t rule, double threshold, int32_t test_exit, double* S1, double* S2, double* SL, double* SH,
                     int32_t* t_used, uint8_t* converged, int32_t* active_after_step, void* workspace, size_t workspace_bytes, bmi_stream stream,
-                    const EnsembleSums* ens, int stop_on) {
+                    const EnsembleSums* ens, int stop_on, int rule_rc, const VoteCounts* votes = nullptr) {
     const int rco = bmi_image_offset_ok(h, image_offset);      // (a null handle: BMI_ERR_INVALID)
     if (rco != BMI_OK) return rco;
     BmiOptionScope opt_scope(&h->opts);
     if (!x_nchw || !S1 || !S2 || !SL || !t_used || !active_after_step || !workspace) return BMI_ERR_INVALID;
     if (batch < 1 || t_max < 1 || t_step < 1 || mask_cnt0 < 0) return BMI_ERR_INVALID;
-    if (rule != BMI_STOP_SEM && rule != BMI_STOP_MARGIN) return BMI_ERR_INVALID;
+    if (rule_rc != BMI_OK) return rule_rc;
     if (test_exit < 0 || test_exit >= h->n_exits) return BMI_ERR_INVALID;
     if (h->max_batch == 0 || batch > h->max_batch) return BMI_ERR_INVALID;
     if (t_step > h->chunk || (h->f32 && !h->split)) return BMI_ERR_UNSUPPORTED;     // (a step is one suffix chunk: the row table holds chunk x max_batch)
@@ -1991,6 +2013,10 @@ static int adaptive(bmi_handle h, const float* x_nchw, int32_t batch, int32_t im
     const size_t eo = (size_t)test_exit * batch * h->out_dim;
     const double* const R1 = (stop_on == BMI_STOP_ON_ENSEMBLE ? ens->Q1 : S1) + eo;      // the [batch][C] sums the rule reads
     const double* const R2 = (stop_on == BMI_STOP_ON_ENSEMBLE ? ens->Q2 : S2) + eo;
+    const bool by_votes = rule == BMI_STOP_VOTES;      // (only with votes: rule_rc)
+    // the [batch][C] counts the vote rule reads, and its slack
+    const int* const RV = votes ? votes->V + ((size_t)(stop_on == BMI_STOP_ON_ENSEMBLE ? 1 : 0) * h->n_exits + test_exit) * batch * h->out_dim : nullptr;
+    const int slack = by_votes ? (int)threshold : 0;
     const int n_steps = (t_max + t_step - 1) / t_step;
     for (int k = 0; k < n_steps; ++k) active_after_step[k] = 0;
     int rc;
@@ -2009,8 +2035,14 @@ static int adaptive(bmi_handle h, const float* x_nchw, int32_t batch, int32_t im
             rc = ensemble_add(h, *ens, tc, batch, s, EnsRows{on.act, on.bc, nullptr});
             if (rc != BMI_OK) return rc;
         }
+        if (votes) {        // (not recorded, as in forward_folded: the profile table has no slot for it)
+            rc = launch_vote_counts_rows(ens->scratch, tc, h->n_exits, batch, h->out_dim, h->cal, EnsRows{on.act, on.bc, nullptr}, votes->V,
+                                         votes->nonfinite, s);
+            if (rc != BMI_OK) return rc;
+        }
         // the stop rule over the still-active images, on the device; the host only learns how many go on
-        rc = launch_adaptive_decide(R1, R2, h->out_dim, t0 + tc, rule, threshold, on.act, on.bc, on.next(), on.count_dev, t_used, s);
+        rc = by_votes ? launch_vote_decide(RV, batch, h->out_dim, t0 + tc, t_max, slack, on.act, on.bc, on.next(), on.count_dev, t_used, s)
+                      : launch_adaptive_decide(R1, R2, h->out_dim, t0 + tc, rule, threshold, on.act, on.bc, on.next(), on.count_dev, t_used, s);
         if (rc != BMI_OK) return rc;
         int n_active = 0;
         rc = on.read_count(&n_active);
@@ -2021,8 +2053,13 @@ static int adaptive(bmi_handle h, const float* x_nchw, int32_t batch, int32_t im
         rc = on.take(n_active, std::min(t_step, t_max - t0 - t_step));
         if (rc != BMI_OK) return rc;
     }
-    return converged ? launch_adaptive_converged(R1, R2, h->out_dim, rule, threshold, batch, t_used, converged, s) : BMI_OK;
+    if (!converged) return BMI_OK;
+    return by_votes ? launch_vote_converged(RV, h->out_dim, t_max, slack, batch, t_used, converged, s)
+                    : launch_adaptive_converged(R1, R2, h->out_dim, rule, threshold, batch, t_used, converged, s);
 }
+
+// BMI_STOP_SEM / BMI_STOP_MARGIN: the rules every adaptive entry point takes
+static int moment_rule_rc(int32_t rule) { return rule == BMI_STOP_SEM || rule == BMI_STOP_MARGIN ? BMI_OK : BMI_ERR_INVALID; }
 
 int bmi_forward_mcd_adaptive(bmi_handle h, const float* x_nchw, int32_t batch, int32_t image_offset, int32_t t_max,
                              int32_t t_step, uint64_t seed, int32_t mask_cnt0, int32_t rule, double threshold,
@@ -2030,7 +2067,7 @@ int bmi_forward_mcd_adaptive(bmi_handle h, const float* x_nchw, int32_t batch, i
                              uint8_t* converged, int32_t* active_after_step, void* workspace, size_t workspace_bytes,
                              bmi_stream stream) {
     return adaptive(h, x_nchw, batch, image_offset, t_max, t_step, seed, mask_cnt0, rule, threshold, test_exit, S1, S2, SL, SH, t_used, converged,
-                    active_after_step, workspace, workspace_bytes, stream, nullptr, BMI_STOP_ON_EXIT);
+                    active_after_step, workspace, workspace_bytes, stream, nullptr, BMI_STOP_ON_EXIT, moment_rule_rc(rule));
 }
 
 int bmi_forward_mcd_adaptive_ensemble(bmi_handle h, const float* x_nchw, int32_t batch, int32_t image_offset, int32_t t_max, int32_t t_step,
@@ -2043,7 +2080,25 @@ int bmi_forward_mcd_adaptive_ensemble(bmi_handle h, const float* x_nchw, int32_t
     if (rce != BMI_OK) return rce;
     const EnsembleSums ens{Q1, Q2, QH, (float*)scratch};
     return adaptive(h, x_nchw, batch, image_offset, t_max, t_step, seed, mask_cnt0, rule, threshold, test_exit, S1, S2, SL, SH, t_used, converged,
-                    active_after_step, workspace, workspace_bytes, stream, &ens, stop_on);
+                    active_after_step, workspace, workspace_bytes, stream, &ens, stop_on, moment_rule_rc(rule));
+}
+
+int bmi_forward_mcd_adaptive_votes(bmi_handle h, const float* x_nchw, int32_t batch, int32_t image_offset, int32_t t_max, int32_t t_step,
+                                   uint64_t seed, int32_t mask_cnt0, int32_t rule, double threshold, int32_t test_exit, int32_t stop_on,
+                                   double* S1, double* S2, double* SL, double* SH, double* Q1, double* Q2, double* QH, int32_t* V,
+                                   int32_t* nonfinite, void* scratch, size_t scratch_bytes, int32_t* t_used, uint8_t* converged,
+                                   int32_t* active_after_step, void* workspace, size_t workspace_bytes, bmi_stream stream) {
+    if (!V || (stop_on != BMI_STOP_ON_EXIT && stop_on != BMI_STOP_ON_ENSEMBLE)) return BMI_ERR_INVALID;
+    const int rce = ensemble_args_ok(h, batch, Q1, Q2, QH, scratch, scratch_bytes);
+    if (rce != BMI_OK) return rce;
+    if (!vote_counts_takes(h->chunk, h->n_exits, batch, h->out_dim)) return BMI_ERR_UNSUPPORTED;
+    // the vote rule's threshold is its slack: a whole number of samples (a NaN fails the first comparison)
+    const bool slack_ok = threshold >= 0.0 && threshold <= (double)INT32_MAX && threshold == std::floor(threshold);
+    const int rule_rc = rule == BMI_STOP_VOTES ? (slack_ok ? BMI_OK : BMI_ERR_INVALID) : moment_rule_rc(rule);
+    const EnsembleSums ens{Q1, Q2, QH, (float*)scratch};
+    const VoteCounts votes{V, nonfinite};
+    return adaptive(h, x_nchw, batch, image_offset, t_max, t_step, seed, mask_cnt0, rule, threshold, test_exit, S1, S2, SL, SH, t_used, converged,
+                    active_after_step, workspace, workspace_bytes, stream, &ens, stop_on, rule_rc, &votes);
 }
 
 int bmi_finalize_per_image(int32_t n_exits, int32_t batch, int32_t out_dim, const int32_t* t_used, const double* S1,
@@ -2152,6 +2207,32 @@ int bmi_vote_counts(const float* logits, int32_t T, int32_t E, int32_t B, int32_
     if (!vote_counts_takes(T, E, B, C)) return BMI_ERR_UNSUPPORTED;    // (E <= 32 before E entries of tau are read)
     if (tau && !cal.set_tau(tau, E)) return BMI_ERR_INVALID;
     return launch_vote_counts(logits, T, E, B, C, cal, V, nonfinite, (hipStream_t)stream);
+}
+
+int bmi_vote_counts_rows(const float* logits, int32_t T, int32_t E, int32_t B, int32_t C, const float* tau, const float* scale_device,
+                         const float* bias_device, const float* matrix_device, const double* W_device, const int32_t* list, int32_t list_count,
+                         const int32_t* n_e, int32_t* V, int32_t* nonfinite, bmi_stream stream) {
+    if (!logits || !V || T < 1 || E < 1 || B < 1 || C < 1) return BMI_ERR_INVALID;
+    if (list && (list_count < 1 || list_count > B)) return BMI_ERR_INVALID;
+    Calibration cal;
+    cal.vec_scale = scale_device;
+    cal.mat = matrix_device;
+    (matrix_device ? cal.mat_bias : cal.vec_bias) = bias_device;       // (as in bmi_vote_counts)
+    cal.ens_w = W_device;
+    if (tau) cal.inv_tau.assign(1, 1.f);
+    if (cal.check() != BMI_OK) return BMI_ERR_INVALID;
+    if (!vote_counts_takes(T, E, B, C)) return BMI_ERR_UNSUPPORTED;
+    if (tau && !cal.set_tau(tau, E)) return BMI_ERR_INVALID;
+    return launch_vote_counts_rows(logits, T, E, B, C, cal, EnsRows{list, list ? list_count : 0, n_e}, V, nonfinite, (hipStream_t)stream);
+}
+
+int bmi_vote_decide(const int32_t* V, int32_t E, int32_t B, int32_t C, int32_t kind, int32_t test_exit, int32_t t, int32_t t_max, int32_t slack,
+                    const int32_t* in_list, int32_t in_count, int32_t* out_list, int32_t* count, int32_t* t_used, bmi_stream stream) {
+    if (!V || !out_list || !count || !t_used || E < 1 || B < 1 || C < 1) return BMI_ERR_INVALID;
+    if (kind < 0 || kind > 1 || test_exit < 0 || test_exit >= E || t < 1 || t_max < t || slack < 0) return BMI_ERR_INVALID;
+    if (in_count < 1 || in_count > B || in_list == out_list) return BMI_ERR_INVALID;
+    return launch_vote_decide(V + ((size_t)kind * E + test_exit) * B * C, B, C, t, t_max, slack, in_list, in_count, out_list, count, t_used,
+                              (hipStream_t)stream);
 }
 
 int bmi_finalize_votes(int32_t n_exits, int32_t batch, int32_t out_dim, const int32_t* V, int32_t* vote_class, double* variation_ratio,

@@ -280,6 +280,20 @@ bool vote_counts_takes(int T, int E, int B, int C);
 int launch_vote_counts(const float* logits, int T, int E, int B, int C, const Calibration& cal, int* V, int* nonfinite, hipStream_t s);
 // per (kind, exit, image) row of V: the lowest modal class (-1: no vote), 1 - modal count / votes (1.0), the entropy of the vote shares (0.0)
 int launch_finalize_votes(int n_rows, int C, const int* V, int* vote_class, double* ratio, double* entropy, hipStream_t s);
+// votes_rows.hip (bmi_vote_counts_rows, bmi_forward_mcd_adaptive_votes, bmi_forward_mcd_exit_staged_votes): launch_vote_counts over the images
+// rows.list[0 .. Bc-1] (null: all B) and of image b its first rows.n_e[b] exits (null: all E); logits and V keep the batch stride B and the
+// original image row.  Every count that is added is launch_vote_counts' for that row; the other rows are neither read nor written.
+// BMI_ERR_INVALID: a list with Bc outside [1, B]; BMI_ERR_UNSUPPORTED: what vote_counts_takes(T, E, B, C) refuses
+int launch_vote_counts_rows(const float* logits, int T, int E, int B, int C, const Calibration& cal, const EnsRows& rows, int* V, int* nonfinite,
+                            hipStream_t s);
+// The decided-vote stop rule (BMI_STOP_VOTES) on Vr = one [B][C] block of V (one kind, one exit), integers only: image b is decided at t of t_max
+// passes when lead >= max(0, t_max - t - slack), lead = min_{c != c1} (Vr[b][c1] - Vr[b][c] - (c < c1)), c1 = the lowest modal class.
+// launch_adaptive_decide's list discipline: every image of `in` (null: 0 .. bc-1) gets t_used[b] = t, the undecided go to `out` in order,
+// their number to *count
+int launch_vote_decide(const int* Vr, int B, int C, int t, int t_max, int slack, const int* in, int bc, int* out, int* count, int* t_used,
+                       hipStream_t s);
+// converged[b] = the rule at t_used[b], b < batch
+int launch_vote_converged(const int* Vr, int C, int t_max, int slack, int batch, const int* t_used, uint8_t* converged, hipStream_t s);
 int launch_philox_mask(uint8_t* keep, int64_t n, uint64_t seed, int site, int t, float p, hipStream_t s);
 // planar_w > 0: the bits in the lazy site's planar layout (rows of planar_w pixels; 2-bit sites, c % 64 == 0)
 int launch_mask_bits(uint8_t* bits, int n, int hw, int c, const SiteArgs& site, int batch, int t0, hipStream_t s, int planar_w = 0);

@@ -22,28 +22,12 @@
 //   finalize_votes_kernel  one wave per (kind, exit, image) row of V: n = the votes cast, m = the modal count, vote_class = the lowest class
 //                          that has it, variation_ratio = 1 - m / n, vote_entropy = -sum f log f in class order (f = V_c / n); n = 0:
 //                          -1, 1.0, 0.0.  Outputs overwritten.
-#include <algorithm>
 #include <climits>
 #include <cmath>
 #include <cstdint>
 
 #include "kernels.h"
-
-#define VOTE_THREADS 256
-#define VOTE_LDS_BYTES 65536      // what a launch may ask for without an attribute: the weighted form's waves per block follow from it
-
-enum { VOTE_MAP_NONE = 0, VOTE_MAP_TEMP = 1, VOTE_MAP_VEC = 2, VOTE_MAP_MAT = 3 };
-
-struct VoteTau { float inv[BMI_ENS_MAX_EXITS]; };
-
-// The lowest class of a row whose value equals the row's maximum `mx`: hit0 / hit1 = this lane's class c0 = lane / c1 = lane + 64 holds it.
-// -1: nobody does (a row of NaNs)
-__device__ __forceinline__ int vote_winner(bool hit0, bool hit1) {
-    const unsigned long long b0 = __ballot(hit0);
-    if (b0) return __ffsll(b0) - 1;
-    const unsigned long long b1 = __ballot(hit1);
-    return b1 ? 64 + __ffsll(b1) - 1 : -1;
-}
+#include "vote_walk.h"      // the exit walk of one (pass, image), shared with votes_rows.hip
 
 template <int MAP, bool WEIGHTED>
 __global__ __launch_bounds__(VOTE_THREADS) void vote_counts_kernel(const float* __restrict__ logits, int T, int E, int B, int C, VoteTau tau,
@@ -56,94 +40,7 @@ __global__ __launch_bounds__(VOTE_THREADS) void vote_counts_kernel(const float* 
     if (w >= (long long)T * B) return;
     const int lane = threadIdx.x & 63;
     const int t = (int)(w / B), b = (int)(w - (long long)t * B);
-    const int c0 = lane, c1 = lane + 64;
-    const bool in0 = c0 < C, in1 = c1 < C;
-    const bool two = C > 64;                              // (wave-uniform: the upper half exists)
-    double* const pw = vote_p + (size_t)wv * E * 128 + lane;
-    double s0 = 0.0, s1 = 0.0;                            // the running exit sum of the two owned classes
-    bool ens_ok = true;                                   // no bad row among the exits so far
-    int bad_rows = 0;
-    for (int e = 0; e < E; ++e) {
-        const float* row = logits + (((size_t)t * E + e) * B + b) * C;
-        float z0 = -INFINITY, z1 = -INFINITY;
-        if constexpr (MAP == VOTE_MAP_MAT) {
-            // (the rows of M of this lane's classes; an absent class reads row 0 of the exit and is dropped below)
-            const float* m0 = ma + ((size_t)e * C + (in0 ? c0 : 0)) * C;
-            const float* m1 = ma + ((size_t)e * C + (in1 ? c1 : 0)) * C;
-            const float l_0 = row[0];
-            float a0 = m0[0] * l_0, a1 = two ? m1[0] * l_0 : 0.f;
-            for (int j = 1; j < C; ++j) {
-                const float lj = row[j];
-                const float pr0 = m0[j] * lj;
-                a0 = a0 + pr0;
-                if (two) {
-                    const float pr1 = m1[j] * lj;
-                    a1 = a1 + pr1;
-                }
-            }
-            if (in0) z0 = a0 + mb[(size_t)e * C + c0];
-            if (in1) z1 = a1 + mb[(size_t)e * C + c1];
-        } else {
-            const float l0 = in0 ? row[c0] : 0.f, l1 = in1 ? row[c1] : 0.f;
-            if constexpr (MAP == VOTE_MAP_NONE) {
-                if (in0) z0 = l0;
-                if (in1) z1 = l1;
-            } else if constexpr (MAP == VOTE_MAP_TEMP) {
-                const float inv = tau.inv[e];
-                if (in0) z0 = l0 * inv;
-                if (in1) z1 = l1 * inv;
-            } else {
-                if (in0) { const float pr = l0 * ma[(size_t)e * C + c0]; z0 = pr + mb[(size_t)e * C + c0]; }
-                if (in1) { const float pr = l1 * ma[(size_t)e * C + c1]; z1 = pr + mb[(size_t)e * C + c1]; }
-            }
-        }
-        const bool bad = __ballot((in0 && !__builtin_isfinite(z0)) || (in1 && !__builtin_isfinite(z1))) != 0ull;
-        if (bad) {                                        // (wave-uniform)
-            ++bad_rows;
-            ens_ok = false;
-            continue;
-        }
-        float mx = fmaxf(z0, z1);
-#pragma unroll
-        for (int k = 32; k >= 1; k >>= 1) mx = fmaxf(mx, __shfl_xor(mx, k));
-        const int kc = vote_winner(in0 && z0 == mx, in1 && z1 == mx);
-        if (kc >= 0 && kc < C && lane == (kc & 63)) atomicAdd(V + (((size_t)0 * E + e) * B + b) * C + kc, 1);
-        if (!ens_ok) continue;                            // (wave-uniform: no ensemble vote behind a bad row, so no member either)
-        const double e0 = in0 ? exp((double)z0 - (double)mx) : 0.0;
-        double e1 = 0.0;
-        if (two) e1 = in1 ? exp((double)z1 - (double)mx) : 0.0;       // (C <= 64: the upper half costs no exponential and no division)
-        double s = e0 + e1;
-#pragma unroll
-        for (int k = 32; k >= 1; k >>= 1) s += __shfl_xor(s, k);
-        const double p0 = e0 / s;
-        double p1 = 0.0;
-        if (two) p1 = e1 / s;
-        double q0, q1;
-        if constexpr (WEIGHTED) {
-            pw[(e * 2 + 0) * 64] = p0;
-            pw[(e * 2 + 1) * 64] = p1;
-            const double* wr = W + (size_t)e * E;
-            q0 = 0.0;
-            q1 = 0.0;
-            for (int i = 0; i <= e; ++i) {
-                const double wi = wr[i];
-                const double t0 = wi * pw[(i * 2 + 0) * 64], t1 = wi * pw[(i * 2 + 1) * 64];
-                q0 = q0 + t0;
-                q1 = q1 + t1;
-            }
-        } else {
-            s0 += p0;
-            s1 += p1;
-            q0 = s0 / (double)(e + 1);
-            q1 = s1 / (double)(e + 1);
-        }
-        double qm = fmax(in0 ? q0 : -INFINITY, in1 ? q1 : -INFINITY);
-#pragma unroll
-        for (int k = 32; k >= 1; k >>= 1) qm = fmax(qm, __shfl_xor(qm, k));
-        const int kq = vote_winner(in0 && q0 == qm, in1 && q1 == qm);
-        if (kq >= 0 && kq < C && lane == (kq & 63)) atomicAdd(V + (((size_t)1 * E + e) * B + b) * C + kq, 1);
-    }
-    if (lane == 0 && nonfinite && bad_rows) atomicAdd(nonfinite, bad_rows);
+    vote_walk<MAP, WEIGHTED>(logits, t, b, lane, E, E, B, C, tau, ma, mb, W, V, nonfinite, vote_p + (size_t)wv * E * 128 + lane);
 }
 
 __global__ __launch_bounds__(VOTE_THREADS) void finalize_votes_kernel(int rows, int C, const int* __restrict__ V, int* __restrict__ vote_class,
@@ -202,23 +99,18 @@ static void launch_votes(unsigned grid, unsigned threads, size_t lds, hipStream_
 int launch_vote_counts(const float* logits, int T, int E, int B, int C, const Calibration& cal, int* V, int* nonfinite, hipStream_t s) {
     if (cal.check() != BMI_OK) return BMI_ERR_INVALID;
     if (!vote_counts_takes(T, E, B, C)) return BMI_ERR_UNSUPPORTED;
-    VoteTau tau;
-    for (int e = 0; e < BMI_ENS_MAX_EXITS; ++e) tau.inv[e] = e < E && e < (int)cal.inv_tau.size() ? cal.inv_tau[e] : 1.f;
-    const bool weighted = cal.ens_w != nullptr;
-    // the weighted form keeps E x 128 float64 per wave in LDS: as many waves per block as VOTE_LDS_BYTES holds (E = 32: 2), at most 4
-    const size_t wave_lds = weighted ? (size_t)E * 128 * sizeof(double) : 0;
-    const int waves = weighted ? (int)std::min<size_t>(VOTE_THREADS / 64, VOTE_LDS_BYTES / wave_lds) : VOTE_THREADS / 64;
-    const unsigned grid = (unsigned)(((int64_t)T * B + waves - 1) / waves), threads = (unsigned)waves * 64;
-    const size_t lds = wave_lds * waves;
-    const float* ma = cal.mat ? cal.mat : cal.vec_scale;
-    const float* mb = cal.mat ? cal.mat_bias : cal.vec_bias;
-    const int map = cal.mat ? VOTE_MAP_MAT : cal.vec_scale ? VOTE_MAP_VEC : !cal.inv_tau.empty() ? VOTE_MAP_TEMP : VOTE_MAP_NONE;
+    const VoteLaunch l = vote_launch_plan(cal, E, (int64_t)T * B);
+    const VoteTau& tau = l.tau;
+    const bool weighted = l.weighted;
+    const unsigned grid = l.grid, threads = l.threads;
+    const size_t lds = l.lds;
+    const float *ma = l.ma, *mb = l.mb;
 #define VOTE_CASE(M)                                                                                                              \
     case M:                                                                                                                       \
         if (weighted) launch_votes<M, true>(grid, threads, lds, s, logits, T, E, B, C, tau, ma, mb, cal.ens_w, V, nonfinite);    \
         else launch_votes<M, false>(grid, threads, lds, s, logits, T, E, B, C, tau, ma, mb, cal.ens_w, V, nonfinite);            \
         break;
-    switch (map) {
+    switch (l.map) {
         VOTE_CASE(VOTE_MAP_NONE)
         VOTE_CASE(VOTE_MAP_TEMP)
         VOTE_CASE(VOTE_MAP_VEC)

@@ -1041,22 +1041,60 @@ class MCDEngine(CompiledGraph):
         r.update(self.finalize_votes(V))
         return r
 
-    def vote_counts(self, logits, tau=None, weights=None, scale=None, bias=None, matrix=None, out=None):
+    def vote_counts(self, logits, tau=None, weights=None, scale=None, bias=None, matrix=None, out=None, rows=None, n_exits_of_image=None):
         """The vote counts of per-sample logits the caller holds (bmi_vote_counts): ``logits`` fp32 [T, E, B, C] on the engine's device
         (``forward_samples``); ``tau``, ``weights``, ``scale`` / ``bias`` and ``matrix`` / ``bias`` as ``ensemble_moments`` takes them (at
         most one map; all independent of what is set on this engine).  Returns V int32 [2, E, B, C]; ``out=V`` ADDS into the counts of
-        earlier calls.  ``train.uncertainty.vote_counts_numpy`` is the host restatement; ``finalize_votes`` reads V out."""
+        earlier calls.  ``train.uncertainty.vote_counts_numpy`` is the host restatement; ``finalize_votes`` reads V out.
+        ``rows`` (int32 [n], 1 <= n <= B, image indices, each at most once) and ``n_exits_of_image`` (int32 [B]), device tensors or
+        anything ``torch.as_tensor`` takes: the image-list form (bmi_vote_counts_rows) — only the listed images, and of image b only its
+        first ``n_exits_of_image[b]`` exits, are read and counted; everything else in V is left as it is."""
         (T, E, B, Cd), kind, tau_c, a, b, w = self._held_logits_map("vote_counts", logits, tau, weights, scale, bias, matrix)
         if out is None:
             V = torch.zeros(2, E, B, Cd, dtype=torch.int32, device=self.device)
         else:
             V = check_buffer(out, (2, E, B, Cd), torch.int32, self.device, "out (V)")
         vec, mat = (None, _ptr(a)) if kind == "matrix" else (_ptr(a), None)
+        if rows is not None or n_exits_of_image is not None:
+            lst = ne = None
+            if rows is not None:
+                lst = torch.as_tensor(rows, dtype=torch.int32, device=self.device).contiguous()
+                if lst.dim() != 1 or not 1 <= lst.numel() <= B:
+                    raise ValueError(f"rows must be a 1-d list of 1 .. {B} image indices, got shape {tuple(lst.shape)}")
+            if n_exits_of_image is not None:
+                ne = torch.as_tensor(n_exits_of_image, dtype=torch.int32, device=self.device).contiguous()
+                if tuple(ne.shape) != (B,):
+                    raise ValueError(f"n_exits_of_image must have shape ({B},), got {tuple(ne.shape)}")
+            with torch.cuda.device(self.device):
+                rc = self.lib.bmi_vote_counts_rows(logits.data_ptr(), T, E, B, Cd, tau_c, vec, _ptr(b), mat, _ptr(w), _ptr(lst),
+                                                   0 if lst is None else lst.numel(), _ptr(ne), V.data_ptr(), self._nonfinite.data_ptr(),
+                                                   self._stream())
+            _lib.check(rc, "bmi_vote_counts_rows")
+            return V
         with torch.cuda.device(self.device):
             rc = self.lib.bmi_vote_counts(logits.data_ptr(), T, E, B, Cd, tau_c, vec, _ptr(b), mat, _ptr(w), V.data_ptr(),
                                           self._nonfinite.data_ptr(), self._stream())
         _lib.check(rc, "bmi_vote_counts")
         return V
+
+    def vote_decide(self, V, t, T_max, slack=0, kind=0, test_exit=-1, active=None):
+        """The decided-vote stop rule on counts the caller holds (bmi_vote_decide; ``rule="votes"`` of ``accumulate_adaptive``): V int32
+        [2, E, B, C] after ``t`` of ``T_max`` passes, row ``V[kind, test_exit]`` (kind 0: the exit, 1: the exit ensemble), over the images
+        ``active`` (int32 list, default all).  Returns (still_active int32 [n] in order, t_used int32 [B]: ``t`` for every tested image,
+        -1 elsewhere).  ``train.uncertainty.vote_decided_numpy`` is the host restatement."""
+        check_buffer(V, (2, None, None, None), torch.int32, self.device, "vote counts V")
+        _, E, B, Cd = V.shape
+        test_exit = int(test_exit) + (E if int(test_exit) < 0 else 0)
+        lst = None if active is None else torch.as_tensor(active, dtype=torch.int32, device=self.device).contiguous()
+        n = B if lst is None else lst.numel()
+        out = torch.empty(max(n, 1), dtype=torch.int32, device=self.device)
+        count = torch.zeros(1, dtype=torch.int32, device=self.device)
+        t_used = torch.full((B,), -1, dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = self.lib.bmi_vote_decide(V.data_ptr(), E, B, Cd, int(kind), test_exit, int(t), int(T_max), int(slack), _ptr(lst), n,
+                                          out.data_ptr(), count.data_ptr(), t_used.data_ptr(), self._stream())
+        _lib.check(rc, "bmi_vote_decide")
+        return out[:int(count.item())], t_used
 
     def predict_with_exit(self, x, T, threshold, seed=0, cnt0=0, first_exit=1):
         """Confidence-threshold early exiting on the device (bmi_forward_mcd_exit): an image leaves after the first exit
@@ -1084,12 +1122,14 @@ class MCDEngine(CompiledGraph):
         return r
 
     def accumulate_early_exit(self, x, S, T, threshold, seed=0, cnt0=0, first_exit=1, rule="confidence", ensemble=False, H=None, Q=None,
-                              QH=None):
+                              QH=None, V=None):
         """The sampling half of ``predict_early_exit`` (bmi_forward_mcd_exit_staged) into the ZEROED sums S [3, E, B, C] (and H [E, B]:
         ``new_uncertainty_sums``): every row it computes equals ``accumulate``'s over samples 0 .. T-1 bit for bit, rows of exits an image
         never reached stay zero.  With ``Q`` and ``QH`` (and H; all ZEROED: ``new_ensemble_sums``) the exit-ensemble sums of the exits every
         image reached as well (bmi_forward_mcd_exit_staged_ensemble): rows e <= exit_layer[b] are ``accumulate_ensemble``'s bits, the others
-        stay zero; the rule is not changed.  Returns (exit_layer int32 [B] on the device, active_after host list [E])."""
+        stay zero; the rule is not changed.  With ``V`` (ZEROED: ``new_vote_counts``; needs Q / QH / H) the vote counts of the exits every
+        image reached as well (bmi_forward_mcd_exit_staged_votes): rows e <= exit_layer[b] of V[0] and V[1] are ``accumulate_votes``' counts,
+        the others stay zero.  Returns (exit_layer int32 [B] on the device, active_after host list [E])."""
         x = self._check_x(x)
         B = x.shape[0]
         if rule not in _lib.EXIT_RULES:
@@ -1101,13 +1141,18 @@ class MCDEngine(CompiledGraph):
             raise ValueError(f"first_exit must be in [0, {self.n_exits})")
         if (Q is None) != (QH is None):
             raise ValueError("the ensemble read-out needs both Q and QH (new_ensemble_sums)")
+        if V is not None and (Q is None or H is None):
+            raise ValueError("the vote counts V need the ensemble sums Q / QH and H (new_ensemble_sums)")
         self._check_sums(B, S, H, Q, QH, ensemble=Q is not None)
+        if V is not None:
+            check_buffer(V, (2, self.n_exits, B, self.out_dim), torch.int32, self.device, "vote counts V")
         exit_layer = torch.empty(B, dtype=torch.int32, device=self.device)
         active = (C.c_int32 * self.n_exits)()
         r_c = _lib.ExitRule(_lib.EXIT_RULES[rule], int(bool(ensemble)), float(threshold), first_exit)
-        name = "bmi_forward_mcd_exit_staged" if Q is None else "bmi_forward_mcd_exit_staged_ensemble"
+        name = "bmi_forward_mcd_exit_staged" if Q is None else "bmi_forward_mcd_exit_staged_ensemble" if V is None else "bmi_forward_mcd_exit_staged_votes"
         scratch = None if Q is None else self._ensemble_scratch()
-        ens = () if Q is None else (Q[0].data_ptr(), Q[1].data_ptr(), QH.data_ptr(), scratch.data_ptr(), scratch.numel())
+        votes = () if V is None else (V.data_ptr(), self._nonfinite.data_ptr())
+        ens = () if Q is None else (Q[0].data_ptr(), Q[1].data_ptr(), QH.data_ptr(), *votes, scratch.data_ptr(), scratch.numel())
         with torch.cuda.device(self.device):
             rc = getattr(self.lib, name)(self.handle, x.data_ptr(), B, T, int(seed) & 0xFFFFFFFFFFFFFFFF, int(cnt0), C.byref(r_c), S[0].data_ptr(),
                                          S[1].data_ptr(), S[2].data_ptr(), None if H is None else H.data_ptr(), *ens, exit_layer.data_ptr(), active,
@@ -1116,7 +1161,7 @@ class MCDEngine(CompiledGraph):
         return exit_layer, [int(v) for v in active]
 
     def predict_early_exit(self, x, T, threshold, seed=0, cnt0=0, first_exit=1, rule="confidence", ensemble=False, uncertainty=False,
-                           ensemble_readout=False):
+                           ensemble_readout=False, votes=False):
         """Early exiting by stages on the device (bmi_forward_mcd_exit_staged): unlike ``predict_with_exit`` the later stages skip the
         deterministic trunk too, so with exit-only dropout an image that leaves at exit 1 never runs layer3 / layer4.  After exit e >=
         ``first_exit`` an image leaves when its statistic exceeds ``threshold``: ``rule="confidence"`` max_c p_c (the reference's
@@ -1128,7 +1173,11 @@ class MCDEngine(CompiledGraph):
         ``finalize_uncertainty``.  With ``ensemble_readout`` (``ensemble`` keeps its meaning: it selects the rule), also the entropies
         above and the five ``ens_*`` entries of ``finalize_ensemble`` over ``T`` — the per-sample exit ensembles, from one kernel launch
         behind the last stage that ran; rows of exits an image never reached are meaningless — and ``best_ens``: dict(mean, var [B, C],
-        pred_entropy, exp_entropy, mutual_info [B]) of the ensemble of exits 0..exit_layer[b].  Synchronises once per decision."""
+        pred_entropy, exp_entropy, mutual_info [B]) of the ensemble of exits 0..exit_layer[b].  With ``votes`` (needs
+        ``ensemble_readout``) also the eight entries of ``finalize_votes`` and ``V``: rows e <= exit_layer[b] are ``predict_votes``', the
+        rows of exits an image never reached hold no votes (vote_class -1).  Synchronises once per decision."""
+        if votes and not ensemble_readout:
+            raise ValueError("votes=True needs ensemble_readout=True (the votes are taken from the logits the ensemble launch reads)")
         if rule not in _lib.EXIT_RULES:
             raise ValueError(f"rule must be one of {sorted(_lib.EXIT_RULES)}, got {rule!r}")
         if not 1 <= int(T) <= self.chunk_samples:
@@ -1140,7 +1189,8 @@ class MCDEngine(CompiledGraph):
             S, H, Q, QH = self.new_ensemble_sums(B)
         else:
             S, H = self.new_uncertainty_sums(B) if uncertainty else (self.new_moments(B), None)
-        exit_layer, active = self.accumulate_early_exit(x, S, T, threshold, seed, cnt0, first_exit, rule, ensemble, H, Q, QH)
+        V = self.new_vote_counts(B) if votes else None
+        exit_layer, active = self.accumulate_early_exit(x, S, T, threshold, seed, cnt0, first_exit, rule, ensemble, H, Q, QH, V)
         r = self.finalize(S, T) if H is None else self.finalize_uncertainty(S, H, T)
         r["exit_layer"] = exit_layer
         r["active_after"] = active
@@ -1149,6 +1199,9 @@ class MCDEngine(CompiledGraph):
             r.update(self._finalize_ensemble_sums(Q, QH, T))
             at = exit_layer.long()
             r["best_ens"] = {k: r["ens_" + k][at, idx] for k in ("mean", "var", "pred_entropy", "exp_entropy", "mutual_info")}
+        if votes:
+            r.update(self.finalize_votes(V))
+            r["V"] = V
         p = r["mean"]
         if ensemble and self.ensemble_weights is not None:      # the weighted mean of exits 0..e, in exit order (the rule's p)
             W, rows = self.ensemble_weights, []
@@ -1173,17 +1226,27 @@ class MCDEngine(CompiledGraph):
         return r
 
     def accumulate_adaptive(self, x, S, T_max, threshold, rule="sem", t_step=None, test_exit=-1, seed=0, cnt0=0, H=None, image_offset=0,
-                            ensemble=False, stop_on="exit", Q=None, QH=None):
+                            ensemble=False, stop_on="exit", Q=None, QH=None, V=None):
         """The sampling half of ``predict_adaptive`` (bmi_forward_mcd_adaptive) into the ZEROED sums S [3, E, B, C] (and H [E, B]:
         ``new_uncertainty_sums``): on return image b's rows hold exactly its first t_used[b] samples.  With ``ensemble`` also into the
         ZEROED exit-ensemble sums ``Q`` [2, E, B, C] and ``QH`` [E, B] (``new_ensemble_sums``; H is required then), truncated the same way
         (bmi_forward_mcd_adaptive_ensemble); ``stop_on="ensemble"`` makes the rule read the ensemble of exits 0..test_exit (Q) in place of
-        exit test_exit's own sums.  Returns (t_used int32 [B], converged uint8 [B], active_after_step host list)."""
+        exit test_exit's own sums.  With ``V`` (ZEROED: ``new_vote_counts``; needs ``ensemble``) also the vote counts, truncated the same
+        way: image b's rows are ``accumulate_votes``' over its first t_used[b] samples (bmi_forward_mcd_adaptive_votes).  Only then
+        ``rule="votes"`` is allowed: ``threshold`` is the integer slack >= 0, and an image retires after t samples when no class can reach
+        the leader of row test_exit of V[0] (``stop_on="exit"``) or V[1] (``"ensemble"``) in the T_max - t - slack samples still to come —
+        with slack 0 its majority vote there is the full T_max run's, exactly; converged is then all ones.
+        Returns (t_used int32 [B], converged uint8 [B], active_after_step host list)."""
         check_stop_on(stop_on, ensemble)
         x = self._check_x(x)
         B = x.shape[0]
-        if rule not in _lib.STOP_RULES:
-            raise ValueError(f"rule must be one of {sorted(_lib.STOP_RULES)}, got {rule!r}")
+        if V is not None and not ensemble:
+            raise ValueError("the vote counts V need ensemble=True (the votes are taken from the logits the ensemble launch reads)")
+        rules = _lib.STOP_RULES if V is None else _lib.VOTE_STOP_RULES
+        if rule not in rules:
+            raise ValueError(f"rule must be one of {sorted(rules)}, got {rule!r}" + (" (rule='votes' needs V)" if rule == "votes" else ""))
+        if rule == "votes" and not (float(threshold) >= 0 and float(threshold) == int(float(threshold))):
+            raise ValueError(f"rule='votes' takes a whole-number slack >= 0 as its threshold, got {threshold!r}")
         if t_step is None:
             t_step = min(DEFAULT_ADAPTIVE_T_STEP, self.chunk_samples)
         T_max, t_step, test_exit = int(T_max), int(t_step), int(test_exit)
@@ -1198,23 +1261,26 @@ class MCDEngine(CompiledGraph):
         if not ensemble and (Q is not None or QH is not None):
             raise ValueError("Q / QH are the sums of ensemble=True")
         self._check_sums(B, S, H, Q, QH, ensemble=ensemble)
+        if V is not None:
+            check_buffer(V, (2, self.n_exits, B, self.out_dim), torch.int32, self.device, "vote counts V")
         t_used = torch.empty(B, dtype=torch.int32, device=self.device)
         converged = torch.empty(B, dtype=torch.uint8, device=self.device)
         active = (C.c_int32 * (-(-T_max // t_step)))()
-        name = "bmi_forward_mcd_adaptive_ensemble" if ensemble else "bmi_forward_mcd_adaptive"
+        name = "bmi_forward_mcd_adaptive_votes" if V is not None else "bmi_forward_mcd_adaptive_ensemble" if ensemble else "bmi_forward_mcd_adaptive"
         scratch = self._ensemble_scratch() if ensemble else None
         stop = (_lib.STOP_ON[stop_on],) if ensemble else ()
-        ens = (Q[0].data_ptr(), Q[1].data_ptr(), QH.data_ptr(), scratch.data_ptr(), scratch.numel()) if ensemble else ()
+        votes = () if V is None else (V.data_ptr(), self._nonfinite.data_ptr())
+        ens = (Q[0].data_ptr(), Q[1].data_ptr(), QH.data_ptr(), *votes, scratch.data_ptr(), scratch.numel()) if ensemble else ()
         with torch.cuda.device(self.device):
             rc = getattr(self.lib, name)(self.handle, x.data_ptr(), B, int(image_offset), T_max, t_step, int(seed) & 0xFFFFFFFFFFFFFFFF, int(cnt0),
-                                         _lib.STOP_RULES[rule], float(threshold), test_exit, *stop, S[0].data_ptr(), S[1].data_ptr(), S[2].data_ptr(),
+                                         rules[rule], float(threshold), test_exit, *stop, S[0].data_ptr(), S[1].data_ptr(), S[2].data_ptr(),
                                          None if H is None else H.data_ptr(), *ens, t_used.data_ptr(), converged.data_ptr(), active,
                                          self.workspace.data_ptr(), self.workspace_bytes, self._stream())
         _lib.check(rc, name)
         return t_used, converged, [int(v) for v in active]
 
     def predict_adaptive(self, x, T_max, threshold, rule="sem", t_step=None, test_exit=-1, seed=0, cnt0=0, uncertainty=False,
-                         image_offset=0, ensemble=False, stop_on="exit"):
+                         image_offset=0, ensemble=False, stop_on="exit", votes=False):
         """Adaptive Monte-Carlo sampling on the device (bmi_forward_mcd_adaptive): samples run in steps of ``t_step`` (default
         DEFAULT_ADAPTIVE_T_STEP, at most the planned chunk) up to ``T_max``; after each step an image whose running estimate at exit
         ``test_exit`` passes the stop rule retires, and the later steps run on the images still active only.  Rules: ``"sem"`` — the
@@ -1226,20 +1292,29 @@ class MCDEngine(CompiledGraph):
         entropies and the exit-ensemble read-out as well: the five ``ens_*`` entries of ``finalize_ensemble``, each image's divided by its own
         t_used[b], plus the sums ``Q`` [2, E, B, C] and ``QH`` [E, B] — image b's are ``predict_ensemble(T=t_used[b])``'s; and
         ``stop_on="ensemble"`` (needs ``ensemble``) tests the rule on the ensemble of exits 0..test_exit, the predictor a caller of the
-        ensemble uses, instead of on exit test_exit alone.  Synchronises once per step."""
+        ensemble uses, instead of on exit test_exit alone.  With ``votes`` (needs ``ensemble``) also the eight entries of
+        ``finalize_votes`` (no t_used needed: they divide by the votes cast) and the counts ``V`` [2, E, B, C] — image b's are
+        ``predict_votes(T=t_used[b])``'s — and ``rule="votes"`` is allowed: ``threshold`` is then the integer slack (``accumulate_adaptive``).
+        Synchronises once per step."""
         check_stop_on(stop_on, ensemble)
+        if votes and not ensemble:
+            raise ValueError("votes=True needs ensemble=True (the votes are taken from the logits the ensemble launch reads)")
         B = x.shape[0]
         Q = QH = None
         if ensemble:
             S, H, Q, QH = self.new_ensemble_sums(B)
         else:
             S, H = self.new_uncertainty_sums(B) if uncertainty else (self.new_moments(B), None)
+        V = self.new_vote_counts(B) if votes else None
         t_used, converged, active = self.accumulate_adaptive(x, S, T_max, threshold, rule, t_step, test_exit, seed, cnt0, H, image_offset,
-                                                             ensemble, stop_on, Q, QH)
+                                                             ensemble, stop_on, Q, QH, V)
         r = self.finalize_per_image(S, t_used, H)
         if ensemble:
             r.update(self.finalize_ensemble_per_image(Q, QH, t_used))
             r.update(Q=Q, QH=QH)
+        if votes:
+            r.update(self.finalize_votes(V))
+            r["V"] = V
         r.update(t_used=t_used, converged=converged.bool(), active_after_step=active)
         return r
 

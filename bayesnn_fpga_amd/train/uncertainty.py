@@ -112,15 +112,24 @@ def decompose_ensemble_logits(logits, tau=None, weights=None, scale=None, bias=N
                 mutual_info=np.maximum(pred_entropy - exp_entropy, 0.0))
 
 
-def vote_counts_numpy(logits, tau=None, weights=None, scale=None, bias=None, matrix=None):
+def vote_counts_numpy(logits, tau=None, weights=None, scale=None, bias=None, matrix=None, rows=None, n_e=None):
     """The vote counts of per-pass logits [T, E, B, C] on the host: the definition csrc/votes.hip implements on the device
     (``MCDEngine.accumulate_votes`` / ``vote_counts``).  z = the calibrated fp32 logits of ``decompose_ensemble_logits`` (same arguments);
     a row (t, e, b) with a non-finite z is bad.  V[0, e, b, k] counts the passes whose row is not bad and whose lowest arg-max of z (fp32
     comparisons) is k; V[1, e, b, k] the passes with no bad row among exits 0..e whose lowest arg-max of the float64 exit ensemble q_te —
     (p_t0 + ... + p_te) / (e + 1), or the weighted sum in exit order from 0.0 — is k.  Returns (V int32 [2, E, B, C], the number of bad
-    rows)."""
+    rows).  ``rows`` (image indices) and ``n_e`` (int [B]): the image-list form of csrc/votes_rows.hip (``MCDEngine.vote_counts(rows=,
+    n_exits_of_image=)``) — only the listed images, and of image b only the exits e < n_e[b], are looked at: their counts are the full
+    form's (the running exit sum is cut, not changed), every other row of V is zero and a bad row there is not counted."""
     l, W = calibrated_logits(logits, tau, weights, scale, bias, matrix)
     T, E, B, Cd = l.shape
+    use = np.ones((E, B), dtype=bool)                                    # the (exit, image) rows the call looks at
+    if rows is not None:
+        use[:] = False
+        use[:, np.asarray(rows, dtype=np.int64)] = True
+    if n_e is not None:
+        use &= np.arange(E)[:, None] < np.asarray(n_e, dtype=np.int64)[None, :]
+    l = np.where(use[None, :, :, None], l, np.float32(0))                # (rows not looked at: a finite placeholder nobody counts)
     bad = ~np.isfinite(l).all(axis=-1)                                   # [T, E, B]
     ens_bad = np.cumsum(bad, axis=1) > 0
     with np.errstate(invalid="ignore", over="ignore"):
@@ -129,7 +138,7 @@ def vote_counts_numpy(logits, tau=None, weights=None, scale=None, bias=None, mat
         ex = np.exp(z)
         p = ex / ex.sum(axis=-1, keepdims=True)
     V = np.zeros((2, E, B, Cd), dtype=np.int32)
-    rows = np.arange(B)
+    imgs = np.arange(B)
     for t in range(T):
         k = np.where(bad[t][..., None], -np.inf, l[t]).argmax(axis=-1)   # [E, B]: numpy's argmax is the first maximum
         acc = np.zeros((B, Cd), dtype=np.float64)
@@ -137,11 +146,28 @@ def vote_counts_numpy(logits, tau=None, weights=None, scale=None, bias=None, mat
         for e in range(E):
             acc = acc + p[t, e]
             q = acc / (e + 1) if W is None else qw[e]
-            ok = ~bad[t, e]
-            np.add.at(V[0, e], (rows[ok], k[e][ok]), 1)
-            ok = ~ens_bad[t, e]
-            np.add.at(V[1, e], (rows[ok], q.argmax(axis=-1)[ok]), 1)
+            ok = ~bad[t, e] & use[e]
+            np.add.at(V[0, e], (imgs[ok], k[e][ok]), 1)
+            ok = ~ens_bad[t, e] & use[e]
+            np.add.at(V[1, e], (imgs[ok], q.argmax(axis=-1)[ok]), 1)
     return V, int(bad.sum())
+
+
+def vote_decided_numpy(V_row, t, T_max, slack=0):
+    """The decided-vote stop rule (BMI_STOP_VOTES; csrc/votes_rows.hip: vote_decide_kernel) on the host, integers only: ``V_row`` int
+    [..., C] = the counts of one row of V after ``t`` of ``T_max`` passes.  c1 = the lowest class with the largest count, lead = min over
+    c != c1 of V[c1] - V[c] - (1 if c < c1 else 0) — a class below c1 wins a tie — or INT32_MAX when C == 1; decided = lead >=
+    max(0, T_max - t - slack).  With slack 0 a decided row's lowest arg-max cannot change in the passes still to come, whatever they
+    vote.  Returns (decided bool [...], lead int64 [...])."""
+    V = np.asarray(V_row).astype(np.int64)
+    Cd = V.shape[-1]
+    c1 = V.argmax(axis=-1)                                               # numpy's argmax is the first maximum
+    top = np.take_along_axis(V, c1[..., None], axis=-1)
+    c = np.arange(Cd)
+    gap = top - V - (c < c1[..., None])
+    gap = np.where(c == c1[..., None], np.iinfo(np.int32).max, gap)
+    lead = gap.min(axis=-1)
+    return lead >= max(0, int(T_max) - int(t) - int(slack)), lead
 
 
 def vote_readout_numpy(V):

@@ -465,6 +465,33 @@ int bmi_forward_mcd_adaptive_ensemble(bmi_handle h, const float* x_nchw, int32_t
                                       size_t scratch_bytes, int32_t* t_used, uint8_t* converged, int32_t* active_after_step, void* workspace,
                                       size_t workspace_bytes, bmi_stream stream);
 
+/* Adaptive sampling that also keeps the vote counts (see bmi_vote_counts below), and can stop on them.  bmi_forward_mcd_adaptive_ensemble
+ * with the same arguments plus V (device int32 [2][E][batch][C], ZERO on entry) and nonfinite (device int32, ADDED to; NULL: not counted).
+ * Per step one launch of votes_rows.hip follows the ensemble launch on the same scratch, under the handle's calibration map and ensemble
+ * weights: over every image while none has retired, over the list of active images afterwards.  On return image b's rows of V hold exactly
+ * the votes of its first t_used[b] samples — bmi_forward_mcd_votes' counts truncated there — and S1 / S2 / SL / SH / Q1 / Q2 / QH hold
+ * bmi_forward_mcd_adaptive_ensemble's bits.  With BMI_STOP_SEM / BMI_STOP_MARGIN the decisions are bmi_forward_mcd_adaptive_ensemble's, bit
+ * for bit.  This entry point alone also takes
+ *   BMI_STOP_VOTES (2): integer arithmetic on row test_exit of V[0] (stop_on = BMI_STOP_ON_EXIT: the exit's votes) or of V[1]
+ *                       (BMI_STOP_ON_ENSEMBLE: the votes of the ensemble of exits 0..test_exit).  With t = samples so far,
+ *                           c1   = the lowest class with the largest count
+ *                           lead = min over c != c1 of (V[c1] - V[c] - (c < c1 ? 1 : 0)), INT32_MAX when C == 1
+ *                           r    = max(0, t_max - t - slack),  slack = threshold: a whole number >= 0 (at most INT32_MAX)
+ *                       stop when lead >= r.  A class below c1 wins a tie (the lowest index), hence the 1.  With slack = 0 no class can
+ *                       reach the leader in the t_max - t samples still to come, whatever they vote: vote_class at the tested row is
+ *                       EXACTLY that of the full t_max run (a pass casts at most one vote).  slack > 0 stops earlier and gives the
+ *                       guarantee up.  r = 0 at t_max, so converged is 1 for every image under this rule.
+ * The vote launches are not recorded in the profile table (it has no free slot; bmi_forward_mcd_votes' are not either).
+ * Errors: bmi_forward_mcd_adaptive_ensemble's, BMI_ERR_INVALID for a NULL V, a rule outside 0..2, BMI_STOP_VOTES with a threshold that is
+ * negative, fractional, not finite or above INT32_MAX; BMI_ERR_UNSUPPORTED for a shape votes.hip does not take (bmi_forward_mcd_votes'
+ * list); in every error case nothing is written.  Synchronises once per step. */
+#define BMI_STOP_VOTES 2
+int bmi_forward_mcd_adaptive_votes(bmi_handle h, const float* x_nchw, int32_t batch, int32_t image_offset, int32_t t_max, int32_t t_step,
+                                   uint64_t seed, int32_t mask_cnt0, int32_t rule, double threshold, int32_t test_exit, int32_t stop_on,
+                                   double* S1, double* S2, double* SL, double* SH, double* Q1, double* Q2, double* QH, int32_t* V,
+                                   int32_t* nonfinite, void* scratch, size_t scratch_bytes, int32_t* t_used, uint8_t* converged,
+                                   int32_t* active_after_step, void* workspace, size_t workspace_bytes, bmi_stream stream);
+
 /* Early exit by stages that also skips the deterministic trunk (the paper's exit-only dropout: every trunk and exit-branch conv is in
  * the once-per-batch prefix).  Every op, prefix and suffix, has a stage: the smallest exit index of any head downstream of its outputs
  * (a pair- or seam-fused op: the smaller of its two members'); stages <= rule->first_exit fold into stage 0.  Stage 0 runs on the whole
@@ -514,6 +541,18 @@ int bmi_forward_mcd_exit_staged_ensemble(bmi_handle h, const float* x_nchw, int3
                                          const bmi_exit_rule* rule, double* S1, double* S2, double* SL, double* SH, double* Q1, double* Q2,
                                          double* QH, void* scratch, size_t scratch_bytes, int32_t* exit_of_image, int32_t* active_after,
                                          void* workspace, size_t workspace_bytes, bmi_stream stream);
+
+/* Staged early exit that also keeps the vote counts of the exits every image reached.  bmi_forward_mcd_exit_staged_ensemble with the same
+ * arguments — the exit rule is NOT changed: there is no vote-based exit rule — plus V (device int32 [2][E][batch][C], ZERO on entry) and
+ * nonfinite (device int32, ADDED to; NULL: not counted).  Behind the one ensemble launch, one launch of votes_rows.hip walks all images
+ * with the same n_e[b] = exit_of_image[b] + 1 exits each: rows e <= exit_of_image[b] of V[0] and V[1] are bmi_forward_mcd_votes' counts
+ * (samples 0 .. t_count-1), rows of exits an image never reached stay zero.  Every other output holds
+ * bmi_forward_mcd_exit_staged_ensemble's bits.  Not recorded in the profile table.  Errors: bmi_forward_mcd_exit_staged_ensemble's,
+ * BMI_ERR_INVALID for a NULL V, BMI_ERR_UNSUPPORTED for a shape votes.hip does not take; in every error case nothing is written. */
+int bmi_forward_mcd_exit_staged_votes(bmi_handle h, const float* x_nchw, int32_t batch, int32_t t_count, uint64_t seed, int32_t mask_cnt0,
+                                      const bmi_exit_rule* rule, double* S1, double* S2, double* SL, double* SH, double* Q1, double* Q2,
+                                      double* QH, int32_t* V, int32_t* nonfinite, void* scratch, size_t scratch_bytes, int32_t* exit_of_image,
+                                      int32_t* active_after, void* workspace, size_t workspace_bytes, bmi_stream stream);
 
 /* The stage plan of bmi_forward_mcd_exit_staged for first_exit (host only; needs bmi_plan).  *n_stages = n_exits - first_exit; with
  * capacity 0 only that is written, else capacity must be >= it.  Per stage k (each array NULL: not written): prefix_macs[k] (MACs per
@@ -777,6 +816,27 @@ int bmi_forward_mcd_votes(bmi_handle h, const float* x_nchw, int32_t batch, int3
 int bmi_vote_counts(const float* logits, int32_t T, int32_t E, int32_t B, int32_t C, const float* tau /* host [E] or NULL */,
                     const float* scale_device, const float* bias_device, const float* matrix_device, const double* W_device, int32_t* V,
                     int32_t* nonfinite, bmi_stream stream);
+
+/* bmi_vote_counts over a list of images and a per-image number of exits (the kernel of bmi_forward_mcd_adaptive_votes and
+ * bmi_forward_mcd_exit_staged_votes).  list: device int32 [list_count], image indices in [0, B), each at most once, or NULL (every image;
+ * list_count is then ignored).  n_e: device int32 [B], or NULL (all E): of image b only the exits e < n_e[b] are read, and only those cast
+ * votes, exit or ensemble — the running exit sum is cut there.  logits and V keep the batch stride B: image b's rows sit at index b whether
+ * or not a list is given.  Every count that is added is the one bmi_vote_counts adds for that row; images not in the list and exits
+ * >= n_e[b] are neither read nor written (their logits may be stale or NaN, *nonfinite does not see them).  Errors: bmi_vote_counts', and
+ * BMI_ERR_INVALID for a list with list_count outside [1, B].  An error writes nothing. */
+int bmi_vote_counts_rows(const float* logits, int32_t T, int32_t E, int32_t B, int32_t C, const float* tau /* host [E] or NULL */,
+                         const float* scale_device, const float* bias_device, const float* matrix_device, const double* W_device,
+                         const int32_t* list, int32_t list_count, const int32_t* n_e, int32_t* V, int32_t* nonfinite, bmi_stream stream);
+
+/* The decided-vote stop rule (BMI_STOP_VOTES of bmi_forward_mcd_adaptive_votes) on counts the caller holds: V device int32 [2][E][B][C],
+ * non-negative; the rule reads row V[kind][test_exit][b] (kind 0: the exit, 1: the exit ensemble) of every image b of in_list (device
+ * int32 [in_count], or NULL: images 0 .. in_count-1) after t of t_max samples.  Every tested image gets t_used[b] = t (device int32 [B]);
+ * the images that are NOT decided go to out_list (device int32, room for in_count entries, not in_list itself) in their order, their
+ * number to *count (device int32).  Integer arithmetic only.  BMI_ERR_INVALID (decided before any HIP call): a NULL V / out_list / count
+ * / t_used, a count below 1, kind outside 0..1, test_exit outside [0, E), t < 1, t_max < t, slack < 0, in_count outside [1, B],
+ * out_list == in_list.  An error writes nothing. */
+int bmi_vote_decide(const int32_t* V, int32_t E, int32_t B, int32_t C, int32_t kind, int32_t test_exit, int32_t t, int32_t t_max, int32_t slack,
+                    const int32_t* in_list, int32_t in_count, int32_t* out_list, int32_t* count, int32_t* t_used, bmi_stream stream);
 
 /* The read-out of V [2][E][batch][C], per kind, exit and image, all three outputs [2][E][batch] and OVERWRITTEN:
  *     n = sum_c V_c (the votes cast),   m = max_c V_c

@@ -12,6 +12,11 @@ call: its wall time with ``stop_on="exit"`` (the same steps: what the read-out c
 ensemble of all exits at the SAME threshold), the mean t_used of both, and the device time of the ensemble.hip launches per step
 (bmi_profile_launches, full-grid steps and image-list steps apart).
 
+--votes: the decided-vote stop rule instead of the legs above (``predict_adaptive(ensemble=True, votes=True, rule="votes")``) against the
+fixed-T ``predict_votes(T)``, alternating, on the headline model and on the exit-only C = 100 model (synthetic weights and the trained-like
+twin of each), for slack 0, 1 and 2 and both ``stop_on``: mean t_used, wall time per batch, and the share of images whose ``vote_class`` at
+the tested row equals the fixed run's — 1.0 at slack 0 by construction of the rule, asserted here.
+
 The thresholds are the given quantiles of every image's SEM statistic after the first step (t = t_step) at the last exit, per model: a
 fixed threshold that suits one set of weights retires nobody on the other.
 """
@@ -109,6 +114,54 @@ def ensemble_leg(name, eng, x, a, t_step, thresholds):
                               active_after_step={k: r["active_after_step"] for k, r in res.items()})), flush=True)
 
 
+def votes_leg(name, model, dev, x, a):
+    """predict_votes(T) against predict_adaptive(rule="votes") at slack 0, 1, 2, stop_on "exit" and "ensemble", alternating."""
+    B, T = x.shape[0], a.T
+    eng = model.engine(dev, max_batch=B, dtype=a.dtype)
+    t_step = min(a.t_step, eng.chunk_samples)
+    calls = {"fixed": lambda: eng.predict_votes(x, T, seed=a.seed)}
+    for stop_on in ("exit", "ensemble"):
+        for slack in (0, 1, 2):
+            calls[stop_on, slack] = (lambda so=stop_on, sl=slack: eng.predict_adaptive(x, T, sl, rule="votes", t_step=t_step, seed=a.seed,
+                                                                                       ensemble=True, stop_on=so, votes=True))
+    for fn in calls.values():                                        # warm-up of every path (the scratch is allocated here)
+        fn()
+    times, res = {k: [] for k in calls}, {}
+    for _ in range(a.reps):                                          # alternating, same process
+        for k, fn in calls.items():
+            ms, res[k] = timed(fn)
+            times[k].append(ms)
+    fixed = float(np.median(times["fixed"]))
+    print(json.dumps(dict(model=name, what="fixed_votes", T=T, B=B, dtype=a.dtype, t_step=t_step, ms=round(fixed, 3),
+                          mean_variation_ratio_last_exit=round(float(res["fixed"]["variation_ratio"][-1].mean()), 4))), flush=True)
+    for k, r in res.items():
+        if k == "fixed":
+            continue
+        stop_on, slack = k
+        key = "vote_class" if stop_on == "exit" else "ens_vote_class"
+        same = float((r[key][-1] == res["fixed"][key][-1]).float().mean())
+        if slack == 0:
+            assert same == 1.0, f"slack 0 must keep the full run's majority vote ({name}, stop_on={stop_on}: {same})"
+        ms = float(np.median(times[k]))
+        steps = sum(1 for n in [B] + r["active_after_step"][:-1] if n)
+        print(json.dumps(dict(model=name, what="adaptive_votes", stop_on=stop_on, slack=slack, t_step=t_step, ms=round(ms, 3),
+                              vs_fixed=round(ms / fixed, 3), ms_per_step=round(ms / max(steps, 1), 3), steps_run=steps,
+                              mean_t_used=round(float(r["t_used"].float().mean()), 2),
+                              work_fraction=round(float(r["t_used"].float().mean()) / T, 3), active_after_step=r["active_after_step"],
+                              same_vote_class_as_fixed=same)), flush=True)
+    model.invalidate_engine()
+
+
+def twin_of(model):
+    """The trained-like twin: every classifier x 24, as bench.py's tolerance leg builds it"""
+    twin = copy.deepcopy(model)
+    with torch.no_grad():
+        for n in HEAD_NAMES:
+            getattr(twin, n).weight.mul_(24.0)
+    twin.invalidate_engine()
+    return twin
+
+
 def leg(name, model, dev, x, a):
     B, T = x.shape[0], a.T
     eng = model.engine(dev, max_batch=B, dtype=a.dtype)
@@ -165,16 +218,21 @@ def main():
     ap.add_argument("--seed", type=int, default=3)
     ap.add_argument("--dtype", default="f16")
     ap.add_argument("--ensemble", action="store_true", help="also measure predict_adaptive(ensemble=True) at the same thresholds")
+    ap.add_argument("--votes", action="store_true", help="measure the decided-vote stop rule against predict_votes, and nothing else")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
+    if a.votes:
+        x = synthetic_images(a.batch, seed=1234).to(dev)
+        for tag, kw in (("headline_c10", KW), ("exit_only_c100", dict(dropout_exit=True, dropout=None, dropout_p=0.25, out_dim=100))):
+            torch.manual_seed(0)
+            model = synthetic_weights_(ResNet18MCEarlyExit(**kw), 0).to(dev).eval()
+            votes_leg(tag + "/synthetic", model, dev, x, a)
+            votes_leg(tag + "/trained_like_twin", twin_of(model), dev, x, a)
+        return
     model = synthetic_weights_(ResNet18MCEarlyExit(**KW), 0).to(dev).eval()
     x = synthetic_images(a.batch, seed=1234).to(dev)
-    twin = copy.deepcopy(model)
-    with torch.no_grad():
-        for n in HEAD_NAMES:
-            getattr(twin, n).weight.mul_(24.0)
-    twin.invalidate_engine()
+    twin = twin_of(model)
     for name, m in (("synthetic", model), ("trained_like_twin", twin)):
         eng, t_step, thresholds = leg(name, m, dev, x, a)
         if a.ensemble:
