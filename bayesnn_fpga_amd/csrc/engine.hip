@@ -2312,6 +2312,31 @@ int bmi_pass_accuracy(const float* logits, int32_t T, int32_t E, int32_t B, int3
     return launch_pass_accuracy(logits, T, E, B, C, labels, tops, K, hits, maxprob, nonfinite, scratch, (hipStream_t)stream);
 }
 
+int bmi_reliability_record(const double* mean, int32_t E, int32_t B, int32_t C, const int32_t* labels, int32_t n0, int32_t N_cap, uint32_t* keys,
+                           uint8_t* hit, double* nll, double* brier, int32_t* counters, bmi_stream stream) {
+    if (!mean || !labels || !keys || !hit || !nll || !brier || E < 1 || B < 1 || C < 1 || N_cap < 1 || n0 < 0 || (int64_t)n0 + B > N_cap)
+        return BMI_ERR_INVALID;
+    if (!reliability_record_takes(E, B, C)) return BMI_ERR_UNSUPPORTED;
+    return launch_reliability_record(mean, E, B, C, labels, n0, N_cap, keys, hit, nll, brier, counters, (hipStream_t)stream);
+}
+
+size_t bmi_reliability_scratch_bytes(int32_t R, int32_t N, int32_t n_bins) { return reliability_scratch_bytes(R, N, n_bins); }
+
+int bmi_reliability_table(const uint32_t* keys, const uint8_t* hit, const double* nll, const double* brier, int32_t R, int32_t N, int32_t N_cap,
+                          int32_t n_bins, const float* edges_in, float* edges_out, int64_t* count, int64_t* hits, int64_t* conf_fix, double* sums,
+                          void* scratch, size_t scratch_bytes, bmi_stream stream) {
+    if (!keys || !hit || !nll || !brier || !edges_out || !count || !hits || !conf_fix || !sums || !scratch || R < 1 || N < 1 || N > N_cap ||
+        n_bins < 1 || n_bins > BMI_REL_MAX_BINS)
+        return BMI_ERR_INVALID;
+    if (edges_in)
+        for (int i = 0; i <= n_bins; ++i)
+            if (!std::isfinite(edges_in[i]) || (i && edges_in[i] < edges_in[i - 1])) return BMI_ERR_INVALID;
+    if (!reliability_table_takes(R, N, n_bins)) return BMI_ERR_UNSUPPORTED;
+    if (scratch_bytes < bmi_reliability_scratch_bytes(R, N, n_bins)) return BMI_ERR_NOMEM;
+    return launch_reliability_table(keys, hit, nll, brier, R, N, N_cap, n_bins, edges_in, edges_out, (long long*)count, (long long*)hits,
+                                    (long long*)conf_fix, sums, scratch, (hipStream_t)stream);
+}
+
 int bmi_profile_enable(bmi_handle h, int32_t enable) {
     if (!h) return BMI_ERR_INVALID;
     h->profiling = enable != 0;

@@ -215,6 +215,20 @@ int launch_nll_matrix_scaling_grad(const float* logits, int T, int E, int B, int
 bool pass_accuracy_takes(int T, int E, int B, int C, int K);
 int launch_pass_accuracy(const float* logits, int T, int E, int B, int C, const int* labels, const int* tops, int K, int* hits, double* maxprob,
                          int* nonfinite, void* scratch, hipStream_t s);
+// reliability.hip (bmi_reliability_record / bmi_reliability_table): the records [2 E][N_cap] of a batch of T-mean probabilities — keys uint32,
+// hit uint8, nll / brier float64 — at columns n0.., and from columns 0 .. N-1 the per-row table: edges [R][n_bins + 1], count / hits / conf_fix
+// int64 [R][n_bins], sums [R][2], all OVERWRITTEN; edges_in: HOST [n_bins + 1] or null (by mass); scratch: int64 [R][chunks][3][n_bins].
+// BMI_ERR_UNSUPPORTED (nothing launched) for the shapes the two takes refuse (C > 128, E > 32, R > 64, n_bins > 64, N >= 2^22, the grid)
+#define BMI_REL_MAX_BINS 64
+#define BMI_REL_MAX_IMAGES (1 << 22)
+bool reliability_record_takes(int E, int B, int C);
+bool reliability_table_takes(int R, int N, int n_bins);
+size_t reliability_scratch_bytes(int R, int N, int n_bins);
+int launch_reliability_record(const double* mean, int E, int B, int C, const int* labels, int n0, int N_cap, uint32_t* keys, uint8_t* hit,
+                              double* nll, double* brier, int* counters, hipStream_t s);
+int launch_reliability_table(const uint32_t* keys, const uint8_t* hit, const double* nll, const double* brier, int R, int N, int N_cap, int n_bins,
+                             const float* edges_in, float* edges_out, long long* count, long long* hits, long long* conf_fix, double* sums,
+                             void* scratch, hipStream_t s);
 // ensemble.hip (bmi_ensemble_moments): Q1 / Q2 [E][B][C] and QH [E][B] += the moments and the entropy of the per-sample exit ensembles
 // q_te = mean_{i<=e} softmax(fl32(l_ti * inv_tau[i])) of logits [T][E][B][C], in sample order onto the running sums
 #define BMI_ENS_MAX_EXITS 32

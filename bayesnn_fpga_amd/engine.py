@@ -1488,6 +1488,84 @@ class MCDEngine(CompiledGraph):
         _lib.check(rc, "bmi_pass_accuracy")
         return out
 
+    # ---- reliability tables (bmi_reliability_record / bmi_reliability_table) -----------------------------------------------------
+    def new_reliability_records(self, capacity, n_exits=None):
+        """The record buffers of ``capacity`` images for ``reliability_records``: dict(keys int32 [R, capacity] — the float32 bit patterns
+        of the confidences —, hit uint8, nll, brier float64 [R, capacity], counters int32 [2] = (non-finite rows, bad labels), zeroed),
+        R = 2 * n_exits rows: the exits, then the exit ensembles.  21 bytes per row and image."""
+        R, cap = 2 * int(self.n_exits if n_exits is None else n_exits), int(capacity)
+        if R < 2 or cap < 1:
+            raise ValueError("new_reliability_records needs n_exits >= 1 and capacity >= 1")
+        return dict(keys=torch.zeros(R, cap, dtype=torch.int32, device=self.device), hit=torch.zeros(R, cap, dtype=torch.uint8, device=self.device),
+                    nll=torch.zeros(R, cap, dtype=torch.float64, device=self.device), brier=torch.zeros(R, cap, dtype=torch.float64, device=self.device),
+                    counters=torch.zeros(2, dtype=torch.int32, device=self.device))
+
+    def _check_records(self, records):
+        R, cap = check_buffer(records["keys"], (None, None), torch.int32, self.device, "records['keys'] [R, capacity]").shape
+        check_buffer(records["hit"], (R, cap), torch.uint8, self.device, "records['hit'] [R, capacity]")
+        check_buffer(records["nll"], (R, cap), torch.float64, self.device, "records['nll'] [R, capacity]")
+        check_buffer(records["brier"], (R, cap), torch.float64, self.device, "records['brier'] [R, capacity]")
+        check_buffer(records["counters"], (2,), torch.int32, self.device, "records['counters'] [2]")
+        return R, cap
+
+    def reliability_records(self, mean, labels, records, offset):
+        """Writes the reliability records of one batch on the device (bmi_reliability_record): ``mean`` float64 [E, B, C] (``finalize``'s
+        T-mean probabilities), ``labels`` int [B], into columns ``offset .. offset + B - 1`` of ``records`` (``new_reliability_records``).
+        Per exit and per exit ensemble (the mean of exits 0..e) and image: the float32 confidence of the arg-max (lowest index on ties)
+        as its bit pattern, whether it hits the label, -log p_label and the Brier term.  A non-finite row or a label outside [0, C) leaves
+        zeros and counts in ``records['counters']``.  One launch, no synchronisation; returns ``offset + B``.
+        ``train.reliability.reliability_numpy`` is the host restatement."""
+        E, B, Cd = check_buffer(mean, (None,) * 3, torch.float64, self.device, "mean [E, B, C]").shape
+        labels = check_buffer(labels.to(device=self.device, dtype=torch.int32).contiguous(), (B,), torch.int32, self.device, "labels [B]")
+        R, cap = self._check_records(records)
+        offset = int(offset)
+        if R != 2 * E:
+            raise ValueError(f"records hold {R} rows, mean has {E} exits (2 * E rows)")
+        if offset < 0 or offset + B > cap:
+            raise ValueError(f"images {offset} .. {offset + B - 1} do not fit the records' capacity {cap}")
+        with torch.cuda.device(self.device):
+            rc = self.lib.bmi_reliability_record(mean.data_ptr(), E, B, Cd, labels.data_ptr(), offset, cap, records["keys"].data_ptr(),
+                                                 records["hit"].data_ptr(), records["nll"].data_ptr(), records["brier"].data_ptr(),
+                                                 records["counters"].data_ptr(), self._stream())
+        _lib.check(rc, "bmi_reliability_record")
+        return offset + B
+
+    def reliability_table(self, records, n, n_bins=15, binning="mass", check=True):
+        """The reliability table of the first ``n`` images of ``records`` on the device (bmi_reliability_table): a dict of device tensors —
+        ``edges`` float32 [R, n_bins + 1], ``count`` / ``hits`` / ``conf_fix`` int64 [R, n_bins] (images, correct images and the sum of
+        confidence * 2^40 per bin, bins ``edges[i] < conf <= edges[i + 1]``), ``sums`` float64 [R, 2] with its columns ``nll_sum`` and
+        ``brier_sum`` (added in image order) — and ``n``.  ``binning``: "mass" (the equal-mass edges of ``train.metrics.ece_hist_binary``:
+        order statistics of the confidences) or "width" (edges i / n_bins).  Exact integers, the same bits on every run and for every
+        cut of the images into ``reliability_records`` calls; ``train.reliability.table_metrics`` derives ECE, MCE, NLL, Brier and accuracy.
+        ``check`` (a host read: synchronises; pass False under a graph capture): FloatingPointError if a record was non-finite,
+        ValueError if a label was outside [0, C)."""
+        R, cap = self._check_records(records)
+        n, n_bins = int(n), int(n_bins)
+        if not 1 <= n <= cap:
+            raise ValueError(f"n = {n} outside [1, {cap}] (the records' capacity)")
+        if binning not in ("mass", "width"):
+            raise ValueError(f"binning must be 'mass' or 'width', got {binning!r}")
+        if not 1 <= n_bins <= _lib.REL_MAX_BINS:
+            raise ValueError(f"n_bins must be in [1, {_lib.REL_MAX_BINS}]")
+        edges_in = None if binning == "mass" else (C.c_float * (n_bins + 1))(*[float(np.float32(i) / np.float32(n_bins)) for i in range(n_bins + 1)])
+        edges = torch.empty(R, n_bins + 1, dtype=torch.float32, device=self.device)
+        ints = torch.empty(3, R, n_bins, dtype=torch.int64, device=self.device)
+        sums = torch.empty(R, 2, dtype=torch.float64, device=self.device)
+        scratch = self._scratch("_nll_scratch", max(1, int(self.lib.bmi_reliability_scratch_bytes(R, n, n_bins))))
+        with torch.cuda.device(self.device):
+            rc = self.lib.bmi_reliability_table(records["keys"].data_ptr(), records["hit"].data_ptr(), records["nll"].data_ptr(),
+                                                records["brier"].data_ptr(), R, n, cap, n_bins, edges_in, edges.data_ptr(), ints[0].data_ptr(),
+                                                ints[1].data_ptr(), ints[2].data_ptr(), sums.data_ptr(), scratch.data_ptr(), scratch.numel(),
+                                                self._stream())
+        _lib.check(rc, "bmi_reliability_table")
+        if check:
+            nonfinite, badlabel = (int(v) for v in records["counters"].tolist())
+            if nonfinite:
+                raise FloatingPointError(f"{nonfinite} reliability records with a non-finite probability on the {self.dtype!r} engine")
+            if badlabel:
+                raise ValueError(f"{badlabel} images with a label outside [0, C) in the reliability records")
+        return dict(edges=edges, count=ints[0], hits=ints[1], conf_fix=ints[2], sums=sums, nll_sum=sums[:, 0], brier_sum=sums[:, 1], n=n)
+
     def read_tensor(self, tensor_id, batch, samples=1):
         """A copy of graph tensor ``tensor_id`` as it sits in the workspace after a forward (bmi_tensor_info): fp32
         [samples * batch or batch, h, w, c].  For per-layer traces (tools/layer_trace.py): plan the engine under

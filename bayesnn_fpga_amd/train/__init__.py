@@ -1,4 +1,5 @@
 from .calibration import EnsembleTemperatureScaling, EnsembleWeights, TemperatureScaling  # noqa: F401
 from .evaluate import MultiExitAccuracy, evaluate, evaluate_exits  # noqa: F401
+from .reliability import ReliabilityAnalysis  # noqa: F401
 from .results_analyzer import FullAnalysis  # noqa: F401
 from .uncertainty import UncertaintyAnalysis, average_predictive_entropy  # noqa: F401

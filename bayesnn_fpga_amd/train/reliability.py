@@ -1,0 +1,204 @@
+"""Reliability tables over a loader: per exit and per exit ensemble the confidence histogram behind the top-label ECE (the equal-mass bins
+of ``train.metrics.ece_hist_binary``, SA/train/results_analyzer.py:446-495, or equal-width ones), the NLL and the Brier score (the
+reference's "MSE", :497-503) — the ``ECE, NLL, MSE`` columns of ``FullAnalysis.all_experiments``, formed on the device
+(csrc/reliability.hip: ``MCDEngine.reliability_records`` per batch, ONE ``MCDEngine.reliability_table`` at the end) from integer-exact tables.
+
+``reliability_numpy`` restates the device's arithmetic contract (the header comment of csrc/reliability.hip) on the host, loop by loop;
+``table_metrics`` derives the metrics from a table, the device's or the restatement's.
+"""
+import numpy as np
+
+from .results_analyzer import get_device
+
+FIX = 2.0 ** 40           # conf_fix counts confidences in units of 2^-40
+
+
+def _np(a):
+    return a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+
+
+def width_edges(n_bins):
+    """edges[i] = (float) i / n_bins, float32 [n_bins + 1]"""
+    return (np.arange(n_bins + 1, dtype=np.float32) / np.float32(n_bins)).astype(np.float32)
+
+
+def reliability_numpy(mean, labels, n_bins=15, binning="mass"):
+    """The host restatement of bmi_reliability_record + bmi_reliability_table: ``mean`` float64 [E, N, C] (T-mean probabilities), ``labels``
+    int [N].  Rows r = kind * E + e: the exits (kind 0), then the exit ensembles (p_0 + ... + p_e) / (e + 1), added in exit order and divided
+    once.  Returns dict(keys uint32, hit uint8, nll, brier float64 [R, N] — the records —, edges float32 [R, n_bins + 1], count, hits,
+    conf_fix int64 [R, n_bins], nll_sum, brier_sum float64 [R], nonfinite, badlabel, n).  Every sum is an explicit ascending loop: over
+    the classes for a row's probability sum and Brier term, over the images for the two float64 sums."""
+    mean = np.asarray(mean, dtype=np.float64)
+    if mean.ndim != 3:
+        raise ValueError("mean must be [E, N, C]")
+    E, N, Cd = mean.shape
+    y = np.asarray(labels).astype(np.int64).reshape(-1)
+    if y.shape[0] != N:
+        raise ValueError("labels must be [N]")
+    if binning not in ("mass", "width"):
+        raise ValueError(f"binning must be 'mass' or 'width', got {binning!r}")
+    R, n_bins = 2 * E, int(n_bins)
+    labelled = (y >= 0) & (y < Cd)
+    yy = np.where(labelled, y, 0)
+    rows = [None] * R
+    acc = np.zeros((N, Cd), dtype=np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for e in range(E):
+            acc = acc + mean[e]
+            rows[e], rows[E + e] = mean[e], acc / float(e + 1)
+    keys = np.zeros((R, N), dtype=np.uint32)
+    hit = np.zeros((R, N), dtype=np.uint8)
+    nll = np.zeros((R, N), dtype=np.float64)
+    brier = np.zeros((R, N), dtype=np.float64)
+    nonfinite = 0
+    idx = np.arange(N)
+    for r, v in enumerate(rows):
+        finite = np.isfinite(v).all(axis=1)
+        valid = labelled & finite
+        nonfinite += int((labelled & ~finite).sum())
+        v = np.where(valid[:, None], v, 1.0)                 # (invalid images: a finite placeholder whose results are dropped)
+        pc = np.maximum(v, 1e-256)
+        s = np.zeros(N, dtype=np.float64)
+        b = np.zeros(N, dtype=np.float64)
+        for c in range(Cd):                                  # ascending class order
+            s = s + pc[:, c]
+            d = v[:, c] - (yy == c)
+            b = b + d * d
+        pred = pc.argmax(axis=1)                             # numpy's argmax: the lowest index on ties
+        conf = (pc[idx, pred] / s).astype(np.float32)
+        keys[r] = np.where(valid, conf.view(np.uint32), 0)
+        hit[r] = valid & (pred == yy)
+        nll[r] = np.where(valid, -np.log(pc[idx, yy]), 0.0)
+        brier[r] = np.where(valid, b, 0.0)
+    edges = np.empty((R, n_bins + 1), dtype=np.float32)
+    if binning == "mass":
+        per = N // n_bins
+        for r in range(R):
+            srt = np.sort(keys[r]).view(np.float32)          # (the unsigned order of the keys is the float order)
+            edges[r, 0] = 0.0
+            for i in range(n_bins):
+                edges[r, i + 1] = srt[min((i + 1) * per, N - 1)]
+            edges[r, n_bins] = 1.0
+    else:
+        edges[:] = width_edges(n_bins)
+    count = np.zeros((R, n_bins), dtype=np.int64)
+    hits = np.zeros((R, n_bins), dtype=np.int64)
+    conf_fix = np.zeros((R, n_bins), dtype=np.int64)
+    nll_sum = np.zeros(R, dtype=np.float64)
+    brier_sum = np.zeros(R, dtype=np.float64)
+    for r in range(R):
+        conf = keys[r].view(np.float32)
+        for i in range(n_bins):
+            sel = (keys[r] != 0) & (conf > edges[r, i]) & (conf <= edges[r, i + 1])
+            count[r, i] = int(sel.sum())
+            hits[r, i] = int(hit[r][sel].sum())
+            conf_fix[r, i] = int((conf[sel].astype(np.float64) * FIX).astype(np.int64).sum())
+        s = t = 0.0
+        for a, b in zip(nll[r].tolist(), brier[r].tolist()):  # image order
+            s = s + a
+            t = t + b
+        nll_sum[r], brier_sum[r] = s, t
+    return dict(keys=keys, hit=hit, nll=nll, brier=brier, edges=edges, count=count, hits=hits, conf_fix=conf_fix, nll_sum=nll_sum,
+                brier_sum=brier_sum, nonfinite=nonfinite, badlabel=int((~labelled).sum()), n=N)
+
+
+def table_metrics(table, n=None):
+    """float64 on the host, from a table of ``MCDEngine.reliability_table`` or ``reliability_numpy`` (``n``: the number of images, default
+    ``table['n']``): dict(acc, ece, mce, nll, brier), each [R].  ece = sum_i |conf_fix_i / 2^40 / count_i - hits_i / count_i| * count_i / n
+    over the non-empty bins in bin order, mce the largest such gap, nll = nll_sum / n, brier = brier_sum / n, acc = sum_i hits_i / n."""
+    n = int(table["n"] if n is None else n)
+    count, hits, fix = (_np(table[k]).astype(np.int64) for k in ("count", "hits", "conf_fix"))
+    R, n_bins = count.shape
+    ece = np.zeros(R, dtype=np.float64)
+    mce = np.zeros(R, dtype=np.float64)
+    for r in range(R):
+        for i in range(n_bins):
+            k = int(count[r, i])
+            if k == 0:
+                continue
+            gap = abs(float(fix[r, i]) / FIX / k - float(hits[r, i]) / k)
+            ece[r] = ece[r] + gap * k / n
+            mce[r] = max(mce[r], gap)
+    return dict(acc=hits.sum(axis=1) / float(n), ece=ece, mce=mce, nll=_np(table["nll_sum"]).astype(np.float64) / n,
+                brier=_np(table["brier_sum"]).astype(np.float64) / n)
+
+
+def row_names(n_exits):
+    """The row labels of ``FullAnalysis.all_experiments``: the exits "0", "1", ..., then "Ensemble0", "Ensemble1", ..."""
+    return [str(e) for e in range(n_exits)] + [f"Ensemble{e}" for e in range(n_exits)]
+
+
+class ReliabilityAnalysis:
+    """One walk of ``loader`` (batches ``(x, y, ...)``) with ``mc_passes`` stochastic passes per batch, the calibration metrics formed on the
+    device.  The walk is ``UncertaintyAnalysis``'s: batch k runs under seed ``seed + k`` with the model's current Masksembles counter, the
+    counters advance by ``mc_passes`` afterwards (``model.advance``), the engine is the model's (``engine_dtype="auto"`` applies) — so the
+    T-mean probabilities are ``FullAnalysis(model, loader, mc_dropout=True, mc_passes=T, seed=seed).preds``.  Per batch only the records
+    (``MCDEngine.reliability_records``: 21 bytes per row and image) stay on the device; ONE ``MCDEngine.reliability_table`` call follows the
+    walk.  Not under a sharded walk (more than one rank): NotImplementedError.
+
+    ``table``: the device tensors of ``reliability_table``; ``metrics``: ``table_metrics`` of it; ``rows``: one ``(name, acc, ece, mce, nll,
+    brier)`` per exit and per exit ensemble, named like ``FullAnalysis.all_experiments``' rows; ``labels`` int64 [N]; ``n``."""
+
+    def __init__(self, model, loader, gpu=0, mc_passes=10, seed=0, n_bins=15, binning="mass"):
+        self.model = model
+        self.loader = loader
+        self.device = get_device(gpu)
+        self.mc_passes = int(mc_passes)
+        self.seed = seed
+        self.n_bins = int(n_bins)
+        self.binning = binning
+        self._run()
+
+    def _engine(self, b_x):
+        dtype = self.model.resolve_engine_dtype(self.device, None, calib=b_x, samples=self.mc_passes)
+        want = max(b_x.shape[0], int(getattr(self.loader, "batch_size", 0) or 0))
+        return self.model.engine(self.device, max_batch=want, dtype=dtype)
+
+    def _capacity(self):
+        """The images the loader announces (``FullAnalysis._collect``'s rule): the records' capacity"""
+        loader = self.loader
+        if getattr(loader, "sampler", None) is not None and hasattr(loader.sampler, "__len__"):
+            return len(loader.sampler)
+        if hasattr(loader, "dataset"):
+            return len(loader.dataset)
+        return sum(len(b[1]) for b in loader)
+
+    def _run(self):
+        import torch
+        from ..sharding import _rank_world
+        if _rank_world(None)[1] > 1:
+            raise NotImplementedError("ReliabilityAnalysis under a sharded walk: the records are not part of "
+                                      "sharding.accumulate_partitioned's all-reduce")
+        eng, records, labels, off = None, None, [], 0
+        for k, batch in enumerate(self.loader):
+            b_x = batch[0].to(self.device)
+            if eng is None:
+                eng = self._engine(b_x)
+                records = eng.new_reliability_records(max(1, self._capacity()))
+            ml = self.model.mask_layers()
+            T, seed, cnt0 = self.mc_passes, self.seed + k, (ml[0].cnt if ml else 0)
+            self.model.advance(T)
+            mean = eng.predict(b_x, T, seed, cnt0=cnt0)["mean"]
+            y = torch.as_tensor(np.asarray(batch[1]).astype(np.int64))
+            off = eng.reliability_records(mean, y, records, off)
+            labels.append(y.numpy())
+        if eng is None:
+            raise ValueError("empty loader")
+        self.n = off
+        self.labels = np.concatenate(labels)
+        self.records = records
+        self.table = eng.reliability_table(records, off, self.n_bins, self.binning)
+        eng.check_finite()
+        self.metrics = table_metrics(self.table, off)
+        m = self.metrics
+        self.rows = [(name, float(m["acc"][r]), float(m["ece"][r]), float(m["mce"][r]), float(m["nll"][r]), float(m["brier"][r]))
+                     for r, name in enumerate(row_names(eng.n_exits))]
+
+    def save(self, experiment_id):
+        """``test_reliability_<experiment_id>.csv``: a header line, then ``rows``; returns the file name."""
+        name = f"test_reliability_{experiment_id}.csv"
+        with open(name, "w") as f:
+            f.write("Layer,Accuracy,ECE,MCE,NLL,Brier\n")
+            for r in self.rows:
+                f.write(",".join(str(v) for v in r) + "\n")
+        return name

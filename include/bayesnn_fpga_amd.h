@@ -848,6 +848,44 @@ int bmi_vote_decide(const int32_t* V, int32_t E, int32_t B, int32_t C, int32_t k
 int bmi_finalize_votes(int32_t n_exits, int32_t batch, int32_t out_dim, const int32_t* V, int32_t* vote_class, double* variation_ratio,
                        double* vote_entropy, bmi_stream stream);
 
+/* Reliability tables: per exit and per exit ensemble the confidence histogram behind the top-label ECE (equal-mass bins as the reference's
+ * hist-ECE takes them, SA/train/results_analyzer.py:446-495, or fixed edges) and the NLL and Brier sums (:497-503), from the T-mean
+ * probabilities on the device.  R = 2 E rows r = kind * E + e: kind 0 is exit e's mean[e], kind 1 the exit ensemble
+ * q_e = (p_0 + ... + p_e) / (e + 1), added in exit order from exit 0 onto 0.0 and divided once.  Per row and image, v = the row's C values,
+ * y = labels[b], float64 and no fused multiply-add wherever a number is formed:
+ *     pc_c = max(v_c, 1e-256),   s = ((0.0 + pc_0) + pc_1) + ...  (ascending class order),   pred = the lowest c with pc_c = max_c pc
+ *     conf = (float)(pc_pred / s),   key = the float32 bit pattern of conf (uint32: for positive floats the unsigned order is the float order)
+ *     hit = (pred == y),   nll = -log(pc_y),   brier = ((0.0 + d_0^2) + d_1^2) + ...,   d_c = v_c - [c == y]  (the unclipped v)
+ * An image whose label is outside [0, C): key 0, hit 0, nll = brier = 0.0 in all R rows and counters[1] += 1 (nothing of it is read).
+ * Otherwise a (row, image) with a non-finite v_c: key 0, hit 0, nll = brier = 0.0 and counters[0] += 1.  No NaN reaches an output.
+ *
+ * The record call writes the records of the B images of one batch at columns n0 .. n0 + B - 1 of the caller's record buffers, each
+ * [R][N_cap]: keys uint32, hit uint8, nll and brier float64 (21 bytes per row and image).  mean: device float64 [E][B][C] (bmi_finalize's
+ * mean), labels: device int32 [B]; counters: device int32 [2], ADDED to, or NULL (not counted).  One launch; capturable.
+ * BMI_ERR_INVALID (decided before any HIP call): a null pointer other than counters, a count below 1, n0 < 0, n0 + B > N_cap.
+ * BMI_ERR_UNSUPPORTED: C > 128, E > 32, B >= 2^25 (the launch grid).  An error writes nothing. */
+int bmi_reliability_record(const double* mean, int32_t E, int32_t B, int32_t C, const int32_t* labels, int32_t n0, int32_t N_cap, uint32_t* keys,
+                           uint8_t* hit, double* nll, double* brier, int32_t* counters /* device [2], ADDED to; NULL: not counted */,
+                           bmi_stream stream);
+
+/* The table of columns 0 .. N-1 of the records, every output OVERWRITTEN:
+ *     edges    float32 [R][n_bins + 1].  edges_in NULL: by mass — per = N / n_bins (integer), edges[0] = 0, edges[i + 1] = the order statistic
+ *              of rank min((i + 1) * per, N - 1) (0-based, ascending) of the row's N keys (radix select: exact under duplicates), edges[n_bins]
+ *              = 1.  Otherwise edges_in: HOST float32 [n_bins + 1], finite and non-decreasing, read during the call, copied to every row.
+ *     count, hits, conf_fix   int64 [R][n_bins]: image n is in the one bin i with edges[i] < conf <= edges[i + 1] (a zero-width bin stays
+ *              empty, key 0 is in none); conf_fix = sum (int64)(conf * 2^40), exact for C <= 128, where conf >= 2^-8 is a multiple of 2^-40
+ *     sums     float64 [R][2]: the nll and the brier records, each added in image order n = 0, 1, ... from 0.0
+ * Integer (LDS) atomics only, no floating-point atomics: the same bits on every run, however the N images were cut into record calls.
+ * Four launches, no allocation, no synchronisation: capturable.  scratch: the per-chunk integer tables, bmi_reliability_scratch_bytes
+ * = R * ceil(N / 4096) * 3 * n_bins * 8 (0 for arguments the table call refuses).
+ * BMI_ERR_INVALID (decided before any HIP call): a null pointer other than edges_in, a count below 1, N > N_cap, n_bins outside [1, 64],
+ * an edges_in entry that is not finite or is below its predecessor.  BMI_ERR_UNSUPPORTED: R > 64, N >= 2^22.  BMI_ERR_NOMEM: scratch too
+ * small.  An error writes nothing. */
+size_t bmi_reliability_scratch_bytes(int32_t R, int32_t N, int32_t n_bins);
+int bmi_reliability_table(const uint32_t* keys, const uint8_t* hit, const double* nll, const double* brier, int32_t R, int32_t N, int32_t N_cap,
+                          int32_t n_bins, const float* edges_in /* host [n_bins + 1] or NULL */, float* edges_out, int64_t* count, int64_t* hits,
+                          int64_t* conf_fix, double* sums, void* scratch, size_t scratch_bytes, bmi_stream stream);
+
 /* Per-op-kind HIP-event timing of bmi_forward_mcd (off by default; adds two event records per
  * launch).  bmi_profile_read synchronises the recorded events and resets the accumulators. */
 int bmi_profile_enable(bmi_handle h, int32_t enable);

@@ -1,0 +1,131 @@
+#!/usr/bin/env python3
+"""Reliability tables on the device, measured.  One JSON line per measurement.
+
+  (r) no GPU: the resource lines of reliability.hip's kernels (tools/kernel_resources.py);
+  (t) the calibration rows of N images from T-mean probabilities that sit on the device, float64 [E, N, C], two routes alternating in one
+      process under a host clock that starts behind a synchronisation and ends behind the route's own last host read:
+        A  the host route of FullAnalysis.all_experiments(ece="hist"): preds.cpu(), exit_ensembles, then ece_hist_binary + nll_mse_acc
+           once per row, 2 E times;
+        B  the device route of ReliabilityAnalysis: MCDEngine.reliability_records per batch of --batch images, ONE reliability_table
+           (which reads the counters: the synchronisation), table_metrics on the host;
+      and the device time of B's two halves by HIP events.  The two routes' rows are compared.
+  Default size: N = 10000, E = 4, C = 100 (CIFAR-100's test set through resnet18's four exits).  Medians over --rounds timings.
+
+    python tools/reliability_bench.py [--rounds 9] [--launches 20] [--n 10000] [--classes 100] [--batch 250] [--parts t]
+    python tools/reliability_bench.py --parts r
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+from vector_scaling_bench import SIZES, event_ms, model_of, stats  # noqa: E402
+
+
+def part_r(a):
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"), "reliability.hip"], capture_output=True, text=True)
+    if out.returncode:
+        sys.exit(out.stderr[-2000:])
+    cols = ("sgpr", "vgpr", "agpr", "scratch", "occ", "s_spill", "v_spill", "lds")
+    for line in out.stdout.splitlines()[1:]:
+        print(json.dumps(dict(part="r", kernel=line[:90].strip().split("(")[0], **{c: int(x) for c, x in zip(cols, line[90:].split())})), flush=True)
+
+
+def problem(E, N, C, seed=0):
+    """Seeded probabilities of a network that is right 60 % of the time: float64 [E, N, C] and labels [N]"""
+    rng = np.random.default_rng(seed)
+    l = rng.standard_normal((E, N, C)) * 3.0
+    y = rng.integers(0, C, N)
+    l[:, np.arange(N), y] += (rng.random((E, N)) < 0.6) * 6.0
+    ex = np.exp(l - l.max(-1, keepdims=True))
+    return ex / ex.sum(-1, keepdims=True), y
+
+
+def part_t(a):
+    from bayesnn_fpga_amd.train.metrics import ece_hist_binary, nll_mse_acc
+    from bayesnn_fpga_amd.train.reliability import table_metrics
+    from bayesnn_fpga_amd.train.results_analyzer import exit_ensembles
+    dev = torch.device("cuda", 0)
+    eng = model_of(SIZES["paper"][0], dev).engine(dev, max_batch=8, dtype="f16x2")      # (the read-out's methods live on an engine; no forward runs)
+    E, N, C, B = eng.n_exits, a.n, a.classes, a.batch
+    p, y = problem(E, N, C)
+    preds, labels = torch.from_numpy(p).to(dev), torch.from_numpy(y).to(dev)
+    onehot = np.zeros((N, C))
+    onehot[np.arange(N), y] = 1
+    cuts = [(o, min(B, N - o)) for o in range(0, N, B)]
+    means = [preds[:, o:o + b].contiguous() for o, b in cuts]                    # what finalize() hands over, batch by batch
+    ys = [labels[o:o + b].to(torch.int32) for o, b in cuts]
+    rec = eng.new_reliability_records(N, n_exits=E)
+
+    def host():
+        pr = preds.cpu().numpy()
+        rows = []
+        for v in list(pr) + list(exit_ensembles(pr)):
+            nll, mse, acc = nll_mse_acc(v, onehot)
+            rows.append((acc, ece_hist_binary(v, onehot), nll, mse))
+        return np.array(rows)
+
+    def record():
+        for (o, _), m, yy in zip(cuts, means, ys):
+            eng.reliability_records(m, yy, rec, o)
+
+    def device():
+        record()
+        m = table_metrics(eng.reliability_table(rec, N), N)
+        return np.stack([m["acc"], m["ece"], m["nll"], m["brier"]], axis=1)
+
+    fns = {"A host: cpu() + 2E x (ece_hist_binary + nll_mse_acc)": host, "B device: records per batch + one table": device,
+           "A' host: cpu() + 2E x (ece_hist_binary + nll_mse_acc)": host}
+    arms, rows = list(fns), {}
+    times = {k: [] for k in arms}
+    for k in arms[:2]:
+        for _ in range(2):
+            fns[k]()                                                             # warm-up: code objects, buffers, numpy's scratch
+    for r in range(a.rounds):
+        for k in (arms if r % 2 == 0 else arms[::-1]):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            rows[k] = fns[k]()
+            times[k].append((time.perf_counter() - t0) * 1e3)
+    for k in arms:
+        s = stats(times[k])
+        print(json.dumps(dict(part="t", what="calibration rows from device-resident preds, host clock", arm=k, N=N, E=E, C=C, batch=B,
+                              timings=a.rounds, **s, ratio_to_A=round(s["median_ms"] / stats(times[arms[0]])["median_ms"], 4))), flush=True)
+    d = np.abs(rows[arms[0]] - rows[arms[1]])
+    print(json.dumps(dict(part="t", what="the two routes' rows", acc_equal=bool((d[:, 0] == 0).all()), max_ece_difference=float(d[:, 1].max()),
+                          max_rel_nll_difference=float((d[:, 2] / rows[arms[0]][:, 2]).max()),
+                          max_rel_brier_difference=float((d[:, 3] / rows[arms[0]][:, 3]).max()))), flush=True)
+    torch.cuda.synchronize()
+    for name, fn in (("records: one launch per batch", record), ("table: four launches", lambda: eng.reliability_table(rec, N, check=False))):
+        ts = [event_ms(fn, a.launches) for _ in range(a.rounds)]
+        print(json.dumps(dict(part="t", what="device time, HIP events", arm=name, N=N, E=E, C=C, batches=len(cuts),
+                              launches_per_timing=a.launches, timings=a.rounds, **stats(ts))), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=9)
+    ap.add_argument("--launches", type=int, default=20)
+    ap.add_argument("--n", type=int, default=10000)
+    ap.add_argument("--classes", type=int, default=100)
+    ap.add_argument("--batch", type=int, default=250)
+    ap.add_argument("--parts", default="t")
+    a = ap.parse_args()
+    parts = a.parts.split(",")
+    if set(parts) - {"r"} and not torch.cuda.is_available():
+        sys.exit("reliability_bench.py measures part t on the GPU: none visible (--parts r needs none)")
+    for p in parts:
+        {"r": part_r, "t": part_t}[p](a)
+
+
+if __name__ == "__main__":
+    main()
