@@ -24,6 +24,7 @@ NLL_VEC_SLAB, NLL_VEC_ROWS = 3456, 64       # bmi_nll_vector_scaling_grad stages
 NLL_MAT_SLAB, NLL_MAT_ROWS = 3456, 64       # bmi_nll_matrix_scaling_grad stages min(NLL_MAT_ROWS, NLL_MAT_SLAB // (C | 1)) samples per chunk
 PASS_ACC_MAX_TOPS = 8                       # bmi_pass_accuracy: at most 8 top-k cut-offs per call (K), 128 classes, 32 exits
 REL_MAX_BINS = 64                           # BMI_REL_MAX_BINS of bmi_reliability_table: n_bins in [1, 64], fewer than 2^22 images, 128 classes, 32 exits
+KDE_MIN_GRID, KDE_MAX_GRID = 16, 65536      # BMI_KDE_* of bmi_reliability_kde: grid points; bw_scale within [2^-100, 2^100]
 NLL_ENS_SLAB, NLL_ENS_ROWS = 9216, 192     # BMI_NLL_ENS_* of bmi_nll_ensemble_temperature_grid: floats / rows a workgroup stages per chunk
 
 
@@ -141,6 +142,7 @@ _PROTOS = {
     "bmi_reliability_record": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 6),
     "bmi_reliability_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "bmi_reliability_table": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 4 + [C.POINTER(C.c_float)] + [C.c_void_p] * 6 + [C.c_size_t, C.c_void_p]),
+    "bmi_reliability_kde": (C.c_int, [C.c_void_p] * 2 + [C.c_int32] * 5 + [C.c_double] + [C.c_void_p] * 8),
     "bmi_forward_mcd_votes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_int32] +
                               [C.c_void_p] * 10 + [C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
     "bmi_vote_counts": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float)] + [C.c_void_p] * 7),

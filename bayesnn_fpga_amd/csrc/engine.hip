@@ -2337,6 +2337,17 @@ int bmi_reliability_table(const uint32_t* keys, const uint8_t* hit, const double
                                     (long long*)conf_fix, sums, scratch, (hipStream_t)stream);
 }
 
+int bmi_reliability_kde(const uint32_t* keys, const uint8_t* hit, int32_t R, int32_t N, int32_t N_cap, int32_t G, int32_t order, double bw_scale,
+                        double* ece_kde, double* bw, double* sd, int64_t* n_data, int64_t* n_hit, int32_t* degenerate, double* density,
+                        bmi_stream stream) {
+    if (!keys || !hit || !ece_kde || !bw || !sd || !n_data || !n_hit || !degenerate || !density || R < 1 || N < 1 || N > N_cap ||
+        G < BMI_KDE_MIN_GRID || G > BMI_KDE_MAX_GRID || (order != 1 && order != 2) || !std::isfinite(bw_scale) || !(bw_scale > 0.0))
+        return BMI_ERR_INVALID;
+    if (!reliability_kde_takes(R, N, G, bw_scale)) return BMI_ERR_UNSUPPORTED;
+    return launch_reliability_kde(keys, hit, R, N, N_cap, G, order, bw_scale, ece_kde, bw, sd, (long long*)n_data, (long long*)n_hit, degenerate,
+                                  density, (hipStream_t)stream);
+}
+
 int bmi_profile_enable(bmi_handle h, int32_t enable) {
     if (!h) return BMI_ERR_INVALID;
     h->profiling = enable != 0;

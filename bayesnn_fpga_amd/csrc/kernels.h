@@ -229,6 +229,14 @@ int launch_reliability_record(const double* mean, int E, int B, int C, const int
 int launch_reliability_table(const uint32_t* keys, const uint8_t* hit, const double* nll, const double* brier, int R, int N, int N_cap, int n_bins,
                              const float* edges_in, float* edges_out, long long* count, long long* hits, long long* conf_fix, double* sums,
                              void* scratch, hipStream_t s);
+#define RL_TILE 1024        // records a workgroup stages in LDS per step of an ordered walk (reliability.hip, reliability_kde.hip)
+// reliability_kde.hip (bmi_reliability_kde): from columns 0 .. N-1 of the records' keys and hit bits, per row the KDE-ECE on a G-point grid —
+// ece_kde, bw, sd [R], n_data, n_hit int64 [R], degenerate int32 [R], density [R][2][G] = pp1, pp2 (the density sums in between) —, all
+// OVERWRITTEN; three launches.  BMI_ERR_UNSUPPORTED (nothing launched) for what reliability_kde_takes refuses (R > 64, N >= 2^22, G outside
+// [BMI_KDE_MIN_GRID, BMI_KDE_MAX_GRID], bw_scale outside [2^-100, 2^100])
+bool reliability_kde_takes(int R, int N, int G, double bw_scale);
+int launch_reliability_kde(const uint32_t* keys, const uint8_t* hit, int R, int N, int N_cap, int G, int order, double bw_scale, double* ece_kde,
+                           double* bw, double* sd, long long* n_data, long long* n_hit, int* degenerate, double* density, hipStream_t s);
 // ensemble.hip (bmi_ensemble_moments): Q1 / Q2 [E][B][C] and QH [E][B] += the moments and the entropy of the per-sample exit ensembles
 // q_te = mean_{i<=e} softmax(fl32(l_ti * inv_tau[i])) of logits [T][E][B][C], in sample order onto the running sums
 #define BMI_ENS_MAX_EXITS 32

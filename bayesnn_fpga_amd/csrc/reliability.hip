@@ -42,7 +42,6 @@
 
 #define RL_THREADS 256
 #define RL_CHUNK 4096
-#define RL_TILE 1024
 
 // lane `from`'s value in every lane; `from` is the same in every lane
 __device__ __forceinline__ double rl_broadcast(double v, int from) {

@@ -1566,6 +1566,46 @@ class MCDEngine(CompiledGraph):
                 raise ValueError(f"{badlabel} images with a label outside [0, C) in the reliability records")
         return dict(edges=edges, count=ints[0], hits=ints[1], conf_fix=ints[2], sums=sums, nll_sum=sums[:, 0], brier_sum=sums[:, 1], n=n)
 
+    def reliability_kde(self, records, n, grid_points=2 ** 14, order=1, bw_scale=None, check=True):
+        """The KDE-ECE of the first ``n`` images of ``records`` on the device (bmi_reliability_kde) — the reference's ``ECE`` column, the
+        top-label KDE calibration error of ``train.metrics.ece_kde_binary`` with the triweight densities evaluated exactly — from the
+        records' float32 confidences and hit bits: a dict of device tensors, ``ece_kde``, ``bw``, ``sd`` float64 [R], ``n_data``, ``n_hit``
+        int64 [R], ``degenerate`` int32 [R], ``density`` float64 [R, 2, grid_points] (the density of the correct predictions' confidences
+        and of all confidences on linspace(-0.6, 1.6, grid_points), zero outside (0, 1)).  ``order``: 1 or 2; ``bw_scale``: the bandwidth is
+        the standard deviation of the correct predictions' confidences times it, default the reference's ``(2 n) ** -0.2``.  A row without
+        data or with a zero denominator (no hit, one hit, equal hit confidences: the reference's NaN) has ``degenerate`` 1 and value 0.0.
+        Three launches, no allocation beyond the outputs; the same bits on every run and for every cut of the images into
+        ``reliability_records`` calls; ``train.reliability.reliability_kde_numpy`` is the host restatement.
+        ``check`` (a host read: synchronises; pass False under a graph capture): ValueError naming the degenerate rows."""
+        R, cap = self._check_records(records)
+        n, G, order = int(n), int(grid_points), int(order)
+        if not 1 <= n <= cap:
+            raise ValueError(f"n = {n} outside [1, {cap}] (the records' capacity)")
+        if not _lib.KDE_MIN_GRID <= G <= _lib.KDE_MAX_GRID:
+            raise ValueError(f"grid_points must be in [{_lib.KDE_MIN_GRID}, {_lib.KDE_MAX_GRID}]")
+        if order not in (1, 2):
+            raise ValueError(f"order must be 1 or 2, got {order}")
+        scale = float(2 * n) ** -0.2 if bw_scale is None else float(bw_scale)
+        if not (np.isfinite(scale) and scale > 0.0):
+            raise ValueError(f"bw_scale must be finite and positive, got {scale}")
+        f64 = torch.empty(3, R, dtype=torch.float64, device=self.device)
+        i64 = torch.empty(2, R, dtype=torch.int64, device=self.device)
+        degenerate = torch.empty(R, dtype=torch.int32, device=self.device)
+        density = torch.empty(R, 2, G, dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = self.lib.bmi_reliability_kde(records["keys"].data_ptr(), records["hit"].data_ptr(), R, n, cap, G, order, scale, f64[0].data_ptr(),
+                                              f64[1].data_ptr(), f64[2].data_ptr(), i64[0].data_ptr(), i64[1].data_ptr(), degenerate.data_ptr(),
+                                              density.data_ptr(), self._stream())
+        _lib.check(rc, "bmi_reliability_kde")
+        if check:
+            bad = [r for r, v in enumerate(degenerate.tolist()) if v]
+            if bad:
+                from .train.reliability import row_names
+                names = row_names(R // 2) if R % 2 == 0 else [str(r) for r in range(R)]
+                raise ValueError("degenerate KDE-ECE rows (no data, or fewer than two distinct correct confidences): " +
+                                 ", ".join(names[r] for r in bad))
+        return dict(ece_kde=f64[0], bw=f64[1], sd=f64[2], n_data=i64[0], n_hit=i64[1], degenerate=degenerate, density=density)
+
     def read_tensor(self, tensor_id, batch, samples=1):
         """A copy of graph tensor ``tensor_id`` as it sits in the workspace after a forward (bmi_tensor_info): fp32
         [samples * batch or batch, h, w, c].  For per-layer traces (tools/layer_trace.py): plan the engine under

@@ -123,6 +123,102 @@ def table_metrics(table, n=None):
                 brier=_np(table["brier_sum"]).astype(np.float64) / n)
 
 
+def kde_bw_scale(n):
+    """The reference's bandwidth factor (2 N)^-0.2 (SA/train/results_analyzer.py:386-391), formed on the host: what ``reliability_kde``
+    receives as ``bw_scale`` by default"""
+    return float(2 * int(n)) ** -0.2
+
+
+def reliability_kde_numpy(keys, hit, n, grid_points=2 ** 14, order=1, bw_scale=None):
+    """The host restatement of bmi_reliability_kde (the header comment of csrc/reliability_kde.hip): the top-label KDE-ECE of
+    ``train.metrics.ece_kde_binary`` — the reference's ``ECE`` — from the records' ``keys`` (uint32 or int32 [R, capacity]: the float32
+    confidences' bit patterns) and ``hit`` (uint8 [R, capacity]), columns ``0 .. n - 1``, with the exact (un-binned) triweight densities.
+    Float64 throughout; the sums over the images (mean, squared deviations, the density sums S1 and S2) are explicit loops in image order,
+    vectorised over the grid only; a centre adds to the grid points around it alone (the others would receive +0.0); the carry-forward and
+    the two trapezoids are explicit loops in index order.  ``bw_scale``: default ``kde_bw_scale(n)``.
+
+    Two differences from ``ece_kde_binary`` are on purpose: the records hold the FLOAT32 confidence, which is used for both densities (the
+    host function uses the unrounded float64 quotient for the density of all confidences), and the standard deviation is the float64
+    two-pass sum of the contract, not ``np.std`` of a float32 array.  A row with no data or a zero denominator (no hit, one hit, equal hit
+    confidences: the host function's NaN) is ``degenerate``: flag 1, value 0.0.
+
+    Returns dict(ece_kde, bw, sd float64 [R], n_data, n_hit int64 [R], degenerate int32 [R], density float64 [R, 2, G] = pp1, pp2 — the
+    device's outputs —, and the intermediates x [G], sums [R, 2, G] = S1, S2, h, perc, a, b [R], integrand [R, G], is_set [R, G] (the
+    integrand was formed there, not carried), mirror_high [R, n] (the datum's mirror is 2 - d))."""
+    import math
+    keys = np.ascontiguousarray(_np(keys))
+    if keys.dtype == np.int32:
+        keys = keys.view(np.uint32)
+    hit = np.asarray(_np(hit))
+    n, G, order = int(n), int(grid_points), int(order)
+    scale = kde_bw_scale(n) if bw_scale is None else float(bw_scale)
+    if keys.dtype != np.uint32 or keys.ndim != 2 or hit.shape != keys.shape or not 1 <= n <= keys.shape[1]:
+        raise ValueError("keys uint32 / int32 [R, capacity], hit [R, capacity], 1 <= n <= capacity")
+    if not 16 <= G <= 65536 or order not in (1, 2) or not 2.0 ** -100 <= scale <= 2.0 ** 100:
+        raise ValueError("grid_points in [16, 65536], order 1 or 2, bw_scale in [2^-100, 2^100]")
+    R = keys.shape[0]
+    step = 2.2 / float(G - 1)
+    x = np.arange(G, dtype=np.float64) * step + (-0.6)
+    inside = (x > 0.0) & (x < 1.0)
+    in_range = np.nonzero((x >= 0.0) & (x <= 1.0))[0]
+    out = dict(ece_kde=np.zeros(R), bw=np.zeros(R), sd=np.zeros(R), n_data=np.zeros(R, dtype=np.int64), n_hit=np.zeros(R, dtype=np.int64),
+               degenerate=np.zeros(R, dtype=np.int32), density=np.zeros((R, 2, G)), x=x, sums=np.zeros((R, 2, G)), h=np.zeros(R),
+               perc=np.zeros(R), a=np.zeros(R), b=np.zeros(R), integrand=np.zeros((R, G)), is_set=np.zeros((R, G), dtype=bool),
+               mirror_high=np.zeros((R, n), dtype=bool))
+    for r in range(R):
+        data = keys[r, :n] != 0
+        d_all = keys[r, :n].view(np.float32).astype(np.float64)
+        is_hit = data & (hit[r, :n] != 0)
+        nd, n1 = int(data.sum()), int(is_hit.sum())
+        s = q = sd = 0.0
+        if n1:
+            for d in d_all[is_hit].tolist():                 # image order
+                s = s + d
+            mu = s / float(n1)
+            for d in d_all[is_hit].tolist():
+                q = q + (d - mu) * (d - mu)
+            sd = math.sqrt(q / float(n1))
+        bw = (sd if sd != 0.0 else 1e-16) * scale
+        h = 3.0 * bw
+        S = out["sums"][r]
+        for d, hd in zip(d_all[data].tolist(), is_hit[data].tolist()):           # image order
+            for c in (d, -d if d < 0.5 else 2.0 - d):
+                # the grid points within h of the centre, one to spare on either side: every other term is nothing
+                lo = max(int(np.searchsorted(x, c - h)) - 1, 0)
+                hi = min(int(np.searchsorted(x, c + h)) + 1, G)
+                u = (x[lo:hi] - c) / h
+                t = 1.0 - u * u
+                term = np.where(t > 0.0, t * t * t, 0.0)
+                S[1, lo:hi] = S[1, lo:hi] + term
+                if hd:
+                    S[0, lo:hi] = S[0, lo:hi] + term
+        out["mirror_high"][r] = data & ~(d_all < 0.5)
+        pp1 = np.where(inside, S[0] * (35.0 / 32.0) / (h * float(2 * n1)) * 2.0, 0.0) if n1 else np.zeros(G)
+        pp2 = np.where(inside, S[1] * (35.0 / 32.0) / (h * float(2 * nd)) * 2.0, 0.0) if nd else np.zeros(G)
+        perc = float(n1) / float(nd) if nd else 0.0
+        is_set = np.maximum(pp1, pp2) > 1e-6
+        with np.errstate(divide="ignore", invalid="ignore"):
+            e = np.abs(x - np.minimum(perc * pp1 / pp2, 1.0))
+        formed = (e * e if order == 2 else e) * pp2
+        I = np.zeros(G)
+        for i in range(G):                                   # index order: the carry-forward is sequential
+            if is_set[i]:
+                I[i] = formed[i]
+            elif i >= 2:
+                I[i] = I[i - 1]
+        a = b = 0.0
+        for i in in_range[:-1].tolist():                     # (the indices in [0, 1] are consecutive)
+            a = a + (x[i + 1] - x[i]) * (I[i + 1] + I[i]) / 2.0
+            b = b + (x[i + 1] - x[i]) * (pp2[i + 1] + pp2[i]) / 2.0
+        deg = nd == 0 or b == 0.0
+        out["ece_kde"][r] = 0.0 if deg else a / b
+        for k, v in (("bw", bw), ("sd", sd), ("n_data", nd), ("n_hit", n1), ("degenerate", int(deg)), ("h", h), ("perc", perc), ("a", a), ("b", b)):
+            out[k][r] = v
+        out["density"][r, 0], out["density"][r, 1] = pp1, pp2
+        out["integrand"][r], out["is_set"][r] = I, is_set
+    return out
+
+
 def row_names(n_exits):
     """The row labels of ``FullAnalysis.all_experiments``: the exits "0", "1", ..., then "Ensemble0", "Ensemble1", ..."""
     return [str(e) for e in range(n_exits)] + [f"Ensemble{e}" for e in range(n_exits)]
@@ -137,9 +233,14 @@ class ReliabilityAnalysis:
     walk.  Not under a sharded walk (more than one rank): NotImplementedError.
 
     ``table``: the device tensors of ``reliability_table``; ``metrics``: ``table_metrics`` of it; ``rows``: one ``(name, acc, ece, mce, nll,
-    brier)`` per exit and per exit ensemble, named like ``FullAnalysis.all_experiments``' rows; ``labels`` int64 [N]; ``n``."""
+    brier)`` per exit and per exit ensemble, named like ``FullAnalysis.all_experiments``' rows; ``labels`` int64 [N]; ``n``.
 
-    def __init__(self, model, loader, gpu=0, mc_passes=10, seed=0, n_bins=15, binning="mass"):
+    ``kde=True``: one more device call after the table, ``MCDEngine.reliability_kde`` on ``grid_points`` grid points — the reference's own
+    ``ECE`` column (the KDE-ECE of ``train.metrics.ece_kde_binary``, exact densities).  ``kde``: its device tensors (False without it);
+    ``metrics["ece_kde"]`` float64 [R], NaN in a degenerate row (no hit, one hit, equal hit confidences: the reference's NaN); ``rows`` gains
+    the value as a seventh element and ``save`` an ``ECE_KDE`` column."""
+
+    def __init__(self, model, loader, gpu=0, mc_passes=10, seed=0, n_bins=15, binning="mass", kde=False, grid_points=2 ** 14):
         self.model = model
         self.loader = loader
         self.device = get_device(gpu)
@@ -147,6 +248,8 @@ class ReliabilityAnalysis:
         self.seed = seed
         self.n_bins = int(n_bins)
         self.binning = binning
+        self.kde = bool(kde)
+        self.grid_points = int(grid_points)
         self._run()
 
     def _engine(self, b_x):
@@ -193,12 +296,16 @@ class ReliabilityAnalysis:
         m = self.metrics
         self.rows = [(name, float(m["acc"][r]), float(m["ece"][r]), float(m["mce"][r]), float(m["nll"][r]), float(m["brier"][r]))
                      for r, name in enumerate(row_names(eng.n_exits))]
+        if self.kde:
+            self.kde = eng.reliability_kde(records, off, self.grid_points, check=False)
+            m["ece_kde"] = np.where(_np(self.kde["degenerate"]) != 0, np.nan, _np(self.kde["ece_kde"]))
+            self.rows = [row + (float(v),) for row, v in zip(self.rows, m["ece_kde"])]
 
     def save(self, experiment_id):
         """``test_reliability_<experiment_id>.csv``: a header line, then ``rows``; returns the file name."""
         name = f"test_reliability_{experiment_id}.csv"
         with open(name, "w") as f:
-            f.write("Layer,Accuracy,ECE,MCE,NLL,Brier\n")
+            f.write("Layer,Accuracy,ECE,MCE,NLL,Brier" + (",ECE_KDE" if self.kde else "") + "\n")
             for r in self.rows:
                 f.write(",".join(str(v) for v in r) + "\n")
         return name

@@ -886,6 +886,32 @@ int bmi_reliability_table(const uint32_t* keys, const uint8_t* hit, const double
                           int32_t n_bins, const float* edges_in /* host [n_bins + 1] or NULL */, float* edges_out, int64_t* count, int64_t* hits,
                           int64_t* conf_fix, double* sums, void* scratch, size_t scratch_bytes, bmi_stream stream);
 
+/* The KDE-ECE of columns 0 .. N-1 of the records — the one calibration error the reference prints (the `ECE` column of
+ * FullAnalysis.all_experiments: ece_eval_binary -> ece_kde_binary, SA/train/results_analyzer.py:351-443) —, per row, from the float32
+ * confidences (keys) and the hit bits alone, with the densities evaluated exactly (no binning).  Float64, no fused multiply-add, correctly
+ * rounded division and sqrt, no other library function; per row r, every sum from 0.0 in image order (the contract, operation by operation,
+ * is the header comment of csrc/reliability_kde.hip; train.reliability.reliability_kde_numpy restates it):
+ *     data     the images with keys[r][n] != 0, d = (double) conf;  n of them, n1 with the hit bit set
+ *     bw       sd = sqrt(sum (d - mu)^2 / n1) over the hit data, mu = sum d / n1 (two passes; n1 = 0: sd = 0);
+ *              bw = (sd != 0 ? sd : 1e-16) * bw_scale, h = 3 bw.  bw_scale: the reference's is (2 N)^-0.2, formed by the caller
+ *     grid     x_i = i * (2.2 / (G - 1)) + (-0.6), i < G
+ *     sums     S1 (hit data) and S2 (all data): per datum the centres d and its mirror (-d if d < 0.5, else 2 - d), per centre
+ *              u = (x_i - c) / h, t = 1 - u u, the term t t t where t > 0
+ *     density  [R][2][G] = pp1, pp2:  pp2_i = S2_i * (35 / 32) / (h * 2 n) * 2 where 0 < x_i < 1, else 0;  pp1 with S1 and n1
+ *     ece_kde  a / b, the trapezoids over 0 <= x_i <= 1 of I and of pp2:  where max(pp1_i, pp2_i) > 1e-6,
+ *              I_i = |x_i - min(n1 / n * pp1_i / pp2_i, 1)|^order * pp2_i, elsewhere the last such I below i (the reference's carry-forward), else 0
+ *     degenerate  1 where n = 0 or b == 0 (no hit, one hit or equal hit confidences: sd = 0, the reference's NaN), with ece_kde = 0.0
+ * Every output is OVERWRITTEN (density holds S1, S2 between the second and the third launch); no floating-point atomics: the same bits on every run and
+ * for every cut of the images into record calls.  Three launches, no allocation, no synchronisation: capturable.
+ * BMI_ERR_INVALID (decided before any HIP call): a null pointer, a count below 1, N > N_cap, G outside [BMI_KDE_MIN_GRID, BMI_KDE_MAX_GRID],
+ * order not 1 or 2, bw_scale not finite and positive.  BMI_ERR_UNSUPPORTED: R > 64, N >= 2^22, bw_scale outside [2^-100, 2^100] (inside,
+ * every quotient above is finite: no NaN reaches an output).  An error writes nothing. */
+#define BMI_KDE_MIN_GRID 16
+#define BMI_KDE_MAX_GRID 65536
+int bmi_reliability_kde(const uint32_t* keys, const uint8_t* hit, int32_t R, int32_t N, int32_t N_cap, int32_t G, int32_t order, double bw_scale,
+                        double* ece_kde /*[R]*/, double* bw /*[R]*/, double* sd /*[R]*/, int64_t* n_data /*[R]*/, int64_t* n_hit /*[R]*/,
+                        int32_t* degenerate /*[R]*/, double* density /*[R][2][G]*/, bmi_stream stream);
+
 /* Per-op-kind HIP-event timing of bmi_forward_mcd (off by default; adds two event records per
  * launch).  bmi_profile_read synchronises the recorded events and resets the accumulators. */
 int bmi_profile_enable(bmi_handle h, int32_t enable);

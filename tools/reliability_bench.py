@@ -9,9 +9,13 @@
         B  the device route of ReliabilityAnalysis: MCDEngine.reliability_records per batch of --batch images, ONE reliability_table
            (which reads the counters: the synchronisation), table_metrics on the host;
       and the device time of B's two halves by HIP events.  The two routes' rows are compared.
+  (k) the KDE-ECE of the R = 2 E rows on --grid grid points (default 2^14), from records that sit on the device: ONE
+      MCDEngine.reliability_kde call (three launches) by HIP events and under the host clock (with its host read of the degenerate flags),
+      next to the host route of FullAnalysis.all_experiments(ece="kde"): preds.cpu(), exit_ensembles, then ece_kde_binary(method="fft") once
+      per row, 2 E times.  The two routes' values are compared.
   Default size: N = 10000, E = 4, C = 100 (CIFAR-100's test set through resnet18's four exits).  Medians over --rounds timings.
 
-    python tools/reliability_bench.py [--rounds 9] [--launches 20] [--n 10000] [--classes 100] [--batch 250] [--parts t]
+    python tools/reliability_bench.py [--rounds 9] [--launches 20] [--n 10000] [--classes 100] [--batch 250] [--grid 16384] [--parts t,k]
     python tools/reliability_bench.py --parts r
 """
 import argparse
@@ -32,12 +36,14 @@ from vector_scaling_bench import SIZES, event_ms, model_of, stats  # noqa: E402
 
 
 def part_r(a):
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"), "reliability.hip"], capture_output=True, text=True)
-    if out.returncode:
-        sys.exit(out.stderr[-2000:])
     cols = ("sgpr", "vgpr", "agpr", "scratch", "occ", "s_spill", "v_spill", "lds")
-    for line in out.stdout.splitlines()[1:]:
-        print(json.dumps(dict(part="r", kernel=line[:90].strip().split("(")[0], **{c: int(x) for c, x in zip(cols, line[90:].split())})), flush=True)
+    for src in ("reliability.hip", "reliability_kde.hip"):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"), src], capture_output=True, text=True)
+        if out.returncode:
+            sys.exit(out.stderr[-2000:])
+        for line in out.stdout.splitlines()[1:]:
+            print(json.dumps(dict(part="r", kernel=line[:90].strip().split("(")[0], **{c: int(x) for c, x in zip(cols, line[90:].split())})),
+                  flush=True)
 
 
 def problem(E, N, C, seed=0):
@@ -111,6 +117,47 @@ def part_t(a):
                               launches_per_timing=a.launches, timings=a.rounds, **stats(ts))), flush=True)
 
 
+def part_k(a):
+    from bayesnn_fpga_amd.train.metrics import ece_kde_binary
+    from bayesnn_fpga_amd.train.results_analyzer import exit_ensembles
+    dev = torch.device("cuda", 0)
+    eng = model_of(SIZES["paper"][0], dev).engine(dev, max_batch=8, dtype="f16x2")      # (no forward runs)
+    E, N, C, B, G = eng.n_exits, a.n, a.classes, a.batch, a.grid
+    p, y = problem(E, N, C)
+    preds, labels = torch.from_numpy(p).to(dev), torch.from_numpy(y).to(dev)
+    onehot = np.zeros((N, C))
+    onehot[np.arange(N), y] = 1
+    rec = eng.new_reliability_records(N, n_exits=E)
+    for o in range(0, N, B):
+        eng.reliability_records(preds[:, o:o + B].contiguous(), labels[o:o + B].to(torch.int32), rec, o)
+
+    def host():
+        pr = preds.cpu().numpy()
+        return np.array([ece_kde_binary(v, onehot, grid_points=G, method="fft") for v in list(pr) + list(exit_ensembles(pr))])
+
+    def device():
+        return eng.reliability_kde(rec, N, G)["ece_kde"].cpu().numpy()
+
+    fns = {"A host: cpu() + 2E x ece_kde_binary(method='fft')": host, "B device: one reliability_kde on the records": device}
+    times, vals = {k: [] for k in fns}, {}
+    device()
+    for r in range(a.rounds):
+        for k in (list(fns) if r % 2 == 0 else list(fns)[::-1]):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            vals[k] = fns[k]()
+            times[k].append((time.perf_counter() - t0) * 1e3)
+    for k in fns:
+        print(json.dumps(dict(part="k", what="KDE-ECE rows, host clock", arm=k, N=N, R=2 * E, C=C, G=G, timings=a.rounds, **stats(times[k]))),
+              flush=True)
+    a_, b_ = (vals[k] for k in fns)
+    print(json.dumps(dict(part="k", what="the two routes' values", max_difference=float(np.abs(a_ - b_).max()), device=[float(v) for v in b_])),
+          flush=True)
+    ts = [event_ms(lambda: eng.reliability_kde(rec, N, G, check=False), a.launches) for _ in range(a.rounds)]
+    print(json.dumps(dict(part="k", what="device time, HIP events", arm="reliability_kde(check=False): three launches", N=N, R=2 * E, G=G,
+                          launches_per_timing=a.launches, timings=a.rounds, **stats(ts))), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=9)
@@ -118,13 +165,14 @@ def main():
     ap.add_argument("--n", type=int, default=10000)
     ap.add_argument("--classes", type=int, default=100)
     ap.add_argument("--batch", type=int, default=250)
+    ap.add_argument("--grid", type=int, default=2 ** 14)
     ap.add_argument("--parts", default="t")
     a = ap.parse_args()
     parts = a.parts.split(",")
     if set(parts) - {"r"} and not torch.cuda.is_available():
-        sys.exit("reliability_bench.py measures part t on the GPU: none visible (--parts r needs none)")
+        sys.exit("reliability_bench.py measures parts t and k on the GPU: none visible (--parts r needs none)")
     for p in parts:
-        {"r": part_r, "t": part_t}[p](a)
+        {"r": part_r, "t": part_t, "k": part_k}[p](a)
 
 
 if __name__ == "__main__":
