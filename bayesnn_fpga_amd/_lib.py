@@ -25,6 +25,9 @@ NLL_MAT_SLAB, NLL_MAT_ROWS = 3456, 64       # bmi_nll_matrix_scaling_grad stages
 PASS_ACC_MAX_TOPS = 8                       # bmi_pass_accuracy: at most 8 top-k cut-offs per call (K), 128 classes, 32 exits
 REL_MAX_BINS = 64                           # BMI_REL_MAX_BINS of bmi_reliability_table: n_bins in [1, 64], fewer than 2^22 images, 128 classes, 32 exits
 KDE_MIN_GRID, KDE_MAX_GRID = 16, 65536      # BMI_KDE_* of bmi_reliability_kde: grid points; bw_scale within [2^-100, 2^100]
+RANK_TILE_I, RANK_TILE_J = 512, 2048        # BMI_RANK_TILE_* of bmi_rank_quality: images a workgroup ranks / keys it stages in LDS per step
+RANK_MAX_IMAGES, RANK_MAX_ROWS = 1 << 17, 1024      # BMI_RANK_MAX_*: longer rows (a radix sort) are not built
+RANK_INVALID, RANK_MAX_KEY = 0xFFFFFFFF, 0x7F7FFFFF # the score key of an image that is in no count; the largest valid key (FLT_MAX's bits)
 NLL_ENS_SLAB, NLL_ENS_ROWS = 9216, 192     # BMI_NLL_ENS_* of bmi_nll_ensemble_temperature_grid: floats / rows a workgroup stages per chunk
 
 
@@ -143,6 +146,9 @@ _PROTOS = {
     "bmi_reliability_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "bmi_reliability_table": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 4 + [C.POINTER(C.c_float)] + [C.c_void_p] * 6 + [C.c_size_t, C.c_void_p]),
     "bmi_reliability_kde": (C.c_int, [C.c_void_p] * 2 + [C.c_int32] * 5 + [C.c_double] + [C.c_void_p] * 8),
+    "bmi_score_record": (C.c_int, [C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 3),
+    "bmi_rank_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "bmi_rank_quality": (C.c_int, [C.c_void_p] * 2 + [C.c_int32] * 3 + [C.c_void_p] * 6 + [C.c_size_t, C.c_void_p]),
     "bmi_forward_mcd_votes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_int32] +
                               [C.c_void_p] * 10 + [C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
     "bmi_vote_counts": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float)] + [C.c_void_p] * 7),

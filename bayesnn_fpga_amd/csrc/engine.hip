@@ -2348,6 +2348,25 @@ int bmi_reliability_kde(const uint32_t* keys, const uint8_t* hit, int32_t R, int
                                   density, (hipStream_t)stream);
 }
 
+int bmi_score_record(const double* score, int32_t R, int32_t B, int32_t direction, const uint32_t* valid_keys, int32_t n0, int32_t N_cap,
+                     uint32_t* ukeys, int32_t* counter, bmi_stream stream) {
+    if (!score || !ukeys || R < 1 || B < 1 || N_cap < 1 || n0 < 0 || (int64_t)n0 + B > N_cap || (direction != 1 && direction != -1))
+        return BMI_ERR_INVALID;
+    if (!score_record_takes(R, B)) return BMI_ERR_UNSUPPORTED;
+    return launch_score_record(score, R, B, direction, valid_keys, n0, N_cap, ukeys, counter, (hipStream_t)stream);
+}
+
+size_t bmi_rank_scratch_bytes(int32_t R, int32_t N) { return rank_scratch_bytes(R, N); }
+
+int bmi_rank_quality(const uint32_t* ukeys, const uint8_t* positive, int32_t R, int32_t N, int32_t N_cap, int32_t* rank, uint32_t* sorted_keys,
+                     int32_t* curve, int64_t* counts, double* aurc_sum, void* scratch, size_t scratch_bytes, bmi_stream stream) {
+    if (!ukeys || !positive || !rank || !sorted_keys || !curve || !counts || !aurc_sum || !scratch || R < 1 || N < 1 || N > N_cap)
+        return BMI_ERR_INVALID;
+    if (!rank_quality_takes(R, N)) return BMI_ERR_UNSUPPORTED;
+    if (scratch_bytes < bmi_rank_scratch_bytes(R, N)) return BMI_ERR_NOMEM;
+    return launch_rank_quality(ukeys, positive, R, N, N_cap, rank, sorted_keys, curve, (long long*)counts, aurc_sum, scratch, (hipStream_t)stream);
+}
+
 int bmi_profile_enable(bmi_handle h, int32_t enable) {
     if (!h) return BMI_ERR_INVALID;
     h->profiling = enable != 0;

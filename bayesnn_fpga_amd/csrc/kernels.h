@@ -237,6 +237,17 @@ int launch_reliability_table(const uint32_t* keys, const uint8_t* hit, const dou
 bool reliability_kde_takes(int R, int N, int G, double bw_scale);
 int launch_reliability_kde(const uint32_t* keys, const uint8_t* hit, int R, int N, int N_cap, int G, int order, double bw_scale, double* ece_kde,
                            double* bw, double* sd, long long* n_data, long long* n_hit, int* degenerate, double* density, hipStream_t s);
+// ranking.hip (bmi_score_record / bmi_rank_quality): the score keys [R][N_cap] of a batch at columns n0.. (counter: ADDED to, or null), and
+// from columns 0 .. N-1 of the keys and the positive bits per row the stable ranks, the sorted keys, the positives-so-far curve, counts
+// int64 [R][3] = m, n_pos, U2 and aurc_sum [R], all OVERWRITTEN; two launches; scratch: int64 [R][ceil(N / BMI_RANK_TILE_I)][3].
+// BMI_ERR_UNSUPPORTED (nothing launched) for what the two takes refuse (R > BMI_RANK_MAX_ROWS, B or N > BMI_RANK_MAX_IMAGES)
+bool score_record_takes(int R, int B);
+bool rank_quality_takes(int R, int N);
+size_t rank_scratch_bytes(int R, int N);
+int launch_score_record(const double* score, int R, int B, int direction, const uint32_t* valid_keys, int n0, int N_cap, uint32_t* ukeys,
+                        int* counter, hipStream_t s);
+int launch_rank_quality(const uint32_t* ukeys, const uint8_t* positive, int R, int N, int N_cap, int* rank, uint32_t* sorted_keys, int* curve,
+                        long long* counts, double* aurc_sum, void* scratch, hipStream_t s);
 // ensemble.hip (bmi_ensemble_moments): Q1 / Q2 [E][B][C] and QH [E][B] += the moments and the entropy of the per-sample exit ensembles
 // q_te = mean_{i<=e} softmax(fl32(l_ti * inv_tau[i])) of logits [T][E][B][C], in sample order onto the running sums
 #define BMI_ENS_MAX_EXITS 32

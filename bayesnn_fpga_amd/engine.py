@@ -1606,6 +1606,70 @@ class MCDEngine(CompiledGraph):
                                  ", ".join(names[r] for r in bad))
         return dict(ece_kde=f64[0], bw=f64[1], sd=f64[2], n_data=i64[0], n_hit=i64[1], degenerate=degenerate, density=density)
 
+    # ---- rank quality of the uncertainty scores (bmi_score_record / bmi_rank_quality) ---------------------------------------------
+    def new_score_records(self, capacity, rows):
+        """The key buffer of ``capacity`` images and ``rows`` rows for ``score_records``: dict(ukeys int32 [rows, capacity] — uint32 bit
+        patterns, filled with INVALID (all ones: -1) —, counter int32 [1] = the scores that were NaN, infinite or negative, zeroed)."""
+        R, cap = int(rows), int(capacity)
+        if R < 1 or cap < 1:
+            raise ValueError("new_score_records needs rows >= 1 and capacity >= 1")
+        return dict(ukeys=torch.full((R, cap), -1, dtype=torch.int32, device=self.device),
+                    counter=torch.zeros(1, dtype=torch.int32, device=self.device))
+
+    def score_records(self, score, records, offset, direction, valid=None):
+        """Writes the score keys of one batch on the device (bmi_score_record): ``score`` float64 [R, B], non-negative, into columns
+        ``offset .. offset + B - 1`` of ``records`` (``new_score_records``).  The key is the float32 bit pattern of the score for
+        ``direction=+1`` (an uncertainty: entropy, mutual information, variation ratio, vote entropy) and 0x7F7FFFFF minus it for
+        ``direction=-1`` (a confidence): ascending unsigned key order is "most certain first".  A NaN, infinite or negative score gives
+        INVALID (all ones) and counts in ``records['counter']``.  ``valid``: int32 [R, capacity], the reliability records' ``keys``; where it
+        is 0 (a bad label, a non-finite row) the image is INVALID in that row and not counted here.  One launch, no synchronisation;
+        returns ``offset + B``.  ``train.ranking.score_keys_numpy`` is the host restatement."""
+        R, B = check_buffer(score, (None, None), torch.float64, self.device, "score [R, B]").shape
+        cap = check_buffer(records["ukeys"], (R, None), torch.int32, self.device, "records['ukeys'] [R, capacity]").shape[1]
+        check_buffer(records["counter"], (1,), torch.int32, self.device, "records['counter'] [1]")
+        offset, direction = int(offset), int(direction)
+        if direction not in (1, -1):
+            raise ValueError(f"direction must be +1 (an uncertainty) or -1 (a confidence), got {direction}")
+        if B < 1 or offset < 0 or offset + B > cap:
+            raise ValueError(f"images {offset} .. {offset + B - 1} do not fit the records' capacity {cap}")
+        if not (R <= _lib.RANK_MAX_ROWS and B <= _lib.RANK_MAX_IMAGES):
+            raise ValueError(f"score_records takes at most {_lib.RANK_MAX_ROWS} rows and {_lib.RANK_MAX_IMAGES} images per call")
+        if valid is not None:
+            check_buffer(valid, (R, cap), torch.int32, self.device, "valid [R, capacity]")
+        with torch.cuda.device(self.device):
+            rc = self.lib.bmi_score_record(score.data_ptr(), R, B, direction, _ptr(valid), offset, cap, records["ukeys"].data_ptr(),
+                                           records["counter"].data_ptr(), self._stream())
+        _lib.check(rc, "bmi_score_record")
+        return offset + B
+
+    def rank_quality(self, ukeys, positive, n):
+        """The rank quality of the first ``n`` images of ``ukeys`` int32 [R, capacity] (``score_records``) against ``positive`` uint8
+        [R, capacity] — 1 where the image is what the score should flag: a wrong prediction, a noise image — on the device
+        (bmi_rank_quality).  The valid images of a row (key not INVALID), m of them, stand in the stable ascending key order, most certain
+        first, ties by image index.  A dict of device tensors: ``rank`` int32 [R, capacity] (the image's position, -1 for an invalid
+        image), ``sorted_keys`` int32 [R, capacity] (position k: the key of the image ranked k, all ones from m on), ``curve`` int32
+        [R, capacity] (position k: the positives at positions 0 .. k, n_pos from m on) — columns beyond ``n`` are zero —, ``counts`` int64
+        [R, 3] = (m, n_pos, U2) with AUROC = U2 / (2 n_pos n_neg), ``aurc_sum`` float64 [R] = sum_k curve[k] / (k + 1) in position order —
+        and ``n``.  Exact integers, O(n^2) compare steps per row and no sort; the same bits on every run and for every cut of the images
+        into ``score_records`` calls.  ``train.ranking.rank_metrics`` derives AUROC, AURC and E-AURC; ``rank_quality_numpy`` restates it."""
+        R, cap = check_buffer(ukeys, (None, None), torch.int32, self.device, "ukeys [R, capacity]").shape
+        check_buffer(positive, (R, cap), torch.uint8, self.device, "positive [R, capacity]")
+        n = int(n)
+        if not 1 <= n <= cap:
+            raise ValueError(f"n = {n} outside [1, {cap}] (the capacity)")
+        if n > _lib.RANK_MAX_IMAGES or R > _lib.RANK_MAX_ROWS:
+            raise ValueError(f"rank_quality takes at most {_lib.RANK_MAX_IMAGES} images and {_lib.RANK_MAX_ROWS} rows (n = {n}, R = {R})")
+        ints = torch.zeros(3, R, cap, dtype=torch.int32, device=self.device)
+        counts = torch.empty(R, 3, dtype=torch.int64, device=self.device)
+        aurc_sum = torch.empty(R, dtype=torch.float64, device=self.device)
+        scratch = self._scratch("_nll_scratch", max(1, int(self.lib.bmi_rank_scratch_bytes(R, n))))
+        with torch.cuda.device(self.device):
+            rc = self.lib.bmi_rank_quality(ukeys.data_ptr(), positive.data_ptr(), R, n, cap, ints[0].data_ptr(), ints[1].data_ptr(),
+                                           ints[2].data_ptr(), counts.data_ptr(), aurc_sum.data_ptr(), scratch.data_ptr(), scratch.numel(),
+                                           self._stream())
+        _lib.check(rc, "bmi_rank_quality")
+        return dict(rank=ints[0], sorted_keys=ints[1], curve=ints[2], counts=counts, aurc_sum=aurc_sum, n=n)
+
     def read_tensor(self, tensor_id, batch, samples=1):
         """A copy of graph tensor ``tensor_id`` as it sits in the workspace after a forward (bmi_tensor_info): fp32
         [samples * batch or batch, h, w, c].  For per-layer traces (tools/layer_trace.py): plan the engine under

@@ -912,6 +912,54 @@ int bmi_reliability_kde(const uint32_t* keys, const uint8_t* hit, int32_t R, int
                         double* ece_kde /*[R]*/, double* bw /*[R]*/, double* sd /*[R]*/, int64_t* n_data /*[R]*/, int64_t* n_hit /*[R]*/,
                         int32_t* degenerate /*[R]*/, double* density /*[R][2][G]*/, bmi_stream stream);
 
+/* Rank quality of the per-image uncertainty scores: do the wrong predictions — or out-of-distribution inputs — carry the high uncertainty?
+ * Per row the stable order of the images by a score key, the risk-coverage curve of selective prediction and the Mann-Whitney count of the
+ * AUROC, as exact integers on the device (csrc/ranking.hip; train.ranking.score_keys_numpy / rank_quality_numpy restate both calls).  The
+ * reference's hardware evaluation prints the mean predictive entropy of random-noise inputs (Hardware_Artifact/bayes_hw/data_utils.py:72-90,
+ * metric_utils.py:3-6); these two calls read the same data per image.
+ *
+ * bmi_score_record turns non-negative scores into 32-bit keys whose ascending unsigned order is "most certain first": score float64 [R][B]
+ * (device) -> columns n0 .. n0 + B - 1 of ukeys uint32 [R][N_cap].  Per (row, image):
+ *     f = (float) score (round to nearest)
+ *     valid_keys given (uint32 [R][N_cap], the same columns: the reliability records' keys) and valid_keys[r][n] == 0:
+ *                                   ukey = 0xFFFFFFFF (INVALID: the image is in no count), not counted
+ *     otherwise f NaN, infinite or below zero:   ukey = 0xFFFFFFFF and *counter += 1 (device int32, ADDED to, or NULL: not counted)
+ *     otherwise b = the bit pattern of f + 0.0f (-0.0 becomes +0.0; b <= 0x7F7FFFFF):
+ *                                   direction +1 (an uncertainty): ukey = b;   direction -1 (a confidence): ukey = 0x7F7FFFFF - b
+ * One launch; capturable.  BMI_ERR_INVALID (decided before any HIP call): a NULL score or ukeys, R / B / N_cap below 1, n0 < 0,
+ * n0 + B > N_cap, direction not +1 or -1.  BMI_ERR_UNSUPPORTED: R > BMI_RANK_MAX_ROWS, B > BMI_RANK_MAX_IMAGES.  An error writes nothing.
+ *
+ * bmi_rank_quality reads columns 0 .. N-1 of ukeys and of positive uint8 [R][N_cap] (1 where the image is what the score should flag: a
+ * wrong prediction, a noise image).  The valid images of row r are those with ukey != 0xFFFFFFFF (a ukey above 0x7F7FFFFF, which no
+ * record call writes, is read as INVALID), m of them, in the STABLE ascending order: by ukey, ties by image index.  Every output is
+ * OVERWRITTEN in columns 0 .. N-1; columns >= N are not touched:
+ *     rank         int32 [R][N_cap]    the image's position 0 .. m-1 in that order, -1 for an invalid image
+ *     sorted_keys  uint32 [R][N_cap]   position k: the ukey of the image ranked k; positions m .. N-1: 0xFFFFFFFF
+ *     curve        int32 [R][N_cap]    position k: the positive images at positions 0 .. k; positions m .. N-1: n_pos
+ *     counts       int64 [R][3]        m, n_pos (valid and positive), U2 = the sum over the pairs (positive i, negative j), both valid, of
+ *                                      2 [ukey_j < ukey_i] + [ukey_j == ukey_i]:  AUROC = U2 / (2 n_pos n_neg), ties counted half
+ *     aurc_sum     float64 [R]         ((0.0 + curve[0] / 1) + curve[1] / 2) + ... + curve[m-1] / m: ascending k from 0.0, each quotient the
+ *                                      correctly rounded float64 division of the two integers converted exactly, no fused multiply-add,
+ *                                      added by one wave in order; 0.0 when m = 0.  AURC = aurc_sum / m is formed on the host.
+ * Ranking by counting, O(N^2) compare steps per row and no sort: exact and stable by construction.  No floating-point atomics (integer
+ * LDS atomics only): the same bits on every run and for every cut of the images into record calls; no NaN reaches an output.  Two
+ * launches, no allocation, no synchronisation: capturable.  scratch: the per-tile integer partials, bmi_rank_scratch_bytes = R *
+ * ceil(N / BMI_RANK_TILE_I) * 3 * 8 (0 for arguments the call refuses).
+ * BMI_ERR_INVALID (decided before any HIP call): a null pointer, R / N below 1, N > N_cap.  BMI_ERR_UNSUPPORTED: N > BMI_RANK_MAX_IMAGES
+ * (2^17: a radix sort for longer rows is not built), R > BMI_RANK_MAX_ROWS (1024).  BMI_ERR_NOMEM: scratch too small.  An error writes
+ * nothing. */
+#define BMI_RANK_TILE_I 512         /* images whose keys one workgroup of the counting kernel keeps in registers */
+#define BMI_RANK_TILE_J 2048        /* images whose keys it stages in LDS per step */
+#define BMI_RANK_MAX_IMAGES 131072
+#define BMI_RANK_MAX_ROWS 1024
+int bmi_score_record(const double* score /*[R][B]*/, int32_t R, int32_t B, int32_t direction, const uint32_t* valid_keys /*[R][N_cap] or NULL*/,
+                     int32_t n0, int32_t N_cap, uint32_t* ukeys /*[R][N_cap]*/, int32_t* counter /* device [1], ADDED to; NULL: not counted */,
+                     bmi_stream stream);
+size_t bmi_rank_scratch_bytes(int32_t R, int32_t N);
+int bmi_rank_quality(const uint32_t* ukeys, const uint8_t* positive, int32_t R, int32_t N, int32_t N_cap, int32_t* rank, uint32_t* sorted_keys,
+                     int32_t* curve, int64_t* counts /*[R][3]*/, double* aurc_sum /*[R]*/, void* scratch, size_t scratch_bytes,
+                     bmi_stream stream);
+
 /* Per-op-kind HIP-event timing of bmi_forward_mcd (off by default; adds two event records per
  * launch).  bmi_profile_read synchronises the recorded events and resets the accumulators. */
 int bmi_profile_enable(bmi_handle h, int32_t enable);
