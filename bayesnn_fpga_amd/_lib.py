@@ -28,6 +28,7 @@ KDE_MIN_GRID, KDE_MAX_GRID = 16, 65536      # BMI_KDE_* of bmi_reliability_kde: 
 RANK_TILE_I, RANK_TILE_J = 512, 2048        # BMI_RANK_TILE_* of bmi_rank_quality: images a workgroup ranks / keys it stages in LDS per step
 RANK_MAX_IMAGES, RANK_MAX_ROWS = 1 << 17, 1024      # BMI_RANK_MAX_*: longer rows (a radix sort) are not built
 RANK_INVALID, RANK_MAX_KEY = 0xFFFFFFFF, 0x7F7FFFFF # the score key of an image that is in no count; the largest valid key (FLT_MAX's bits)
+POLICY_MAX_THRESHOLDS, POLICY_MAX_RECORD_ROWS = 1024, 64       # BMI_POLICY_MAX_* of bmi_exit_policy_sweep: thresholds per call / with selected records
 NLL_ENS_SLAB, NLL_ENS_ROWS = 9216, 192     # BMI_NLL_ENS_* of bmi_nll_ensemble_temperature_grid: floats / rows a workgroup stages per chunk
 
 
@@ -149,6 +150,9 @@ _PROTOS = {
     "bmi_score_record": (C.c_int, [C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 3),
     "bmi_rank_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "bmi_rank_quality": (C.c_int, [C.c_void_p] * 2 + [C.c_int32] * 3 + [C.c_void_p] * 6 + [C.c_size_t, C.c_void_p]),
+    "bmi_exit_stat_record": (C.c_int, [C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 2),
+    "bmi_exit_policy_scratch_bytes": (C.c_size_t, [C.c_int32] * 3),
+    "bmi_exit_policy_sweep": (C.c_int, [C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p, C.c_int32] + [C.c_void_p] * 13 + [C.c_size_t, C.c_void_p]),
     "bmi_forward_mcd_votes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_int32] +
                               [C.c_void_p] * 10 + [C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
     "bmi_vote_counts": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float)] + [C.c_void_p] * 7),

@@ -2367,6 +2367,31 @@ int bmi_rank_quality(const uint32_t* ukeys, const uint8_t* positive, int32_t R, 
     return launch_rank_quality(ukeys, positive, R, N, N_cap, rank, sorted_keys, curve, (long long*)counts, aurc_sum, scratch, (hipStream_t)stream);
 }
 
+int bmi_exit_stat_record(const double* S1, int32_t E, int32_t B, int32_t C, int32_t t_count, int32_t criterion, const double* weights, int32_t n0,
+                         int32_t N_cap, double* stat, bmi_stream stream) {
+    if (!S1 || !stat || E < 1 || B < 1 || C < 1 || t_count < 1 || N_cap < 1 || n0 < 0 || (int64_t)n0 + B > N_cap ||
+        (criterion != BMI_EXIT_CONFIDENCE && criterion != BMI_EXIT_MARGIN))
+        return BMI_ERR_INVALID;
+    if (!exit_stat_record_takes(E, B, C)) return BMI_ERR_UNSUPPORTED;
+    return launch_exit_stat_record(S1, E, B, C, t_count, criterion == BMI_EXIT_MARGIN, weights, n0, N_cap, stat, (hipStream_t)stream);
+}
+
+size_t bmi_exit_policy_scratch_bytes(int32_t E, int32_t N, int32_t G) { return exit_policy_scratch_bytes(E, N, G); }
+
+int bmi_exit_policy_sweep(const double* stat, int32_t E, int32_t N, int32_t N_cap, int32_t first_exit, const double* thresholds, int32_t G,
+                          const uint32_t* keys, const uint8_t* hit, const double* nll, const double* brier, int64_t* count, int64_t* hits,
+                          int64_t* invalid, uint8_t* exit_of, uint32_t* sel_keys, uint8_t* sel_hit, double* sel_nll, double* sel_brier,
+                          void* scratch, size_t scratch_bytes, bmi_stream stream) {
+    const int n_sel = (sel_keys != nullptr) + (sel_hit != nullptr) + (sel_nll != nullptr) + (sel_brier != nullptr);
+    if (!stat || !thresholds || !keys || !hit || !nll || !brier || !count || !hits || !invalid || !scratch || (n_sel != 0 && n_sel != 4) ||
+        E < 1 || N < 1 || G < 1 || N > N_cap || first_exit < 0 || first_exit >= E)
+        return BMI_ERR_INVALID;
+    if (!exit_policy_takes(E, N, G, n_sel == 4)) return BMI_ERR_UNSUPPORTED;
+    if (scratch_bytes < bmi_exit_policy_scratch_bytes(E, N, G)) return BMI_ERR_NOMEM;
+    return launch_exit_policy_sweep(stat, E, N, N_cap, first_exit, thresholds, G, keys, hit, nll, brier, (long long*)count, (long long*)hits,
+                                    (long long*)invalid, exit_of, sel_keys, sel_hit, sel_nll, sel_brier, scratch, (hipStream_t)stream);
+}
+
 int bmi_profile_enable(bmi_handle h, int32_t enable) {
     if (!h) return BMI_ERR_INVALID;
     h->profiling = enable != 0;

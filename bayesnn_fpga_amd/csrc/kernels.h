@@ -248,6 +248,20 @@ int launch_score_record(const double* score, int R, int B, int direction, const 
                         int* counter, hipStream_t s);
 int launch_rank_quality(const uint32_t* ukeys, const uint8_t* positive, int R, int N, int N_cap, int* rank, uint32_t* sorted_keys, int* curve,
                         long long* counts, double* aurc_sum, void* scratch, hipStream_t s);
+// exit_policy.hip (bmi_exit_stat_record / bmi_exit_policy_sweep): the decision statistics stat [2][E][N_cap] of a batch at columns n0..
+// (exit_rule_stat of exit_rule.h per (ens, exit, image); weights: device [E][E] or null; one launch), and from columns 0 .. N-1 of one
+// [E][N_cap] plane of them, G device thresholds and the outcome rows the per-threshold count / hits int64 [G][E] and invalid int64 [G],
+// OVERWRITTEN, and where given exit_of uint8 [G][N_cap] and the selected records [G][N_cap] (sel_keys null: none of the four); two
+// launches; scratch: uint32 [chunks][G][2 E + 1].  BMI_ERR_UNSUPPORTED (nothing launched) for what the two takes refuse
+bool exit_stat_record_takes(int E, int B, int C);
+bool exit_policy_takes(int E, int N, int G, bool select);
+size_t exit_policy_scratch_bytes(int E, int N, int G);
+int launch_exit_stat_record(const double* S1, int E, int B, int C, int t_count, int margin, const double* weights, int n0, int N_cap, double* stat,
+                            hipStream_t s);
+int launch_exit_policy_sweep(const double* stat, int E, int N, int N_cap, int first_exit, const double* thresholds, int G, const uint32_t* keys,
+                             const uint8_t* hit, const double* nll, const double* brier, long long* count, long long* hits, long long* invalid,
+                             uint8_t* exit_of, uint32_t* sel_keys, uint8_t* sel_hit, double* sel_nll, double* sel_brier, void* scratch,
+                             hipStream_t s);
 // ensemble.hip (bmi_ensemble_moments): Q1 / Q2 [E][B][C] and QH [E][B] += the moments and the entropy of the per-sample exit ensembles
 // q_te = mean_{i<=e} softmax(fl32(l_ti * inv_tau[i])) of logits [T][E][B][C], in sample order onto the running sums
 #define BMI_ENS_MAX_EXITS 32

@@ -730,10 +730,11 @@ class MCDEngine(CompiledGraph):
         unweighted kernels: the bits of an engine that never had weights.  The matrix lives in a small device buffer the engine keeps; a
         hipGraph captured earlier keeps the weights it was captured with (``model.set_exit_ensemble_weights`` drops the pipes that hold such graphs)."""
         W = check_ensemble_weights(w, self.n_exits)
+        self._ens_w_dev = None                       # (what exit_stat_records hands to bmi_exit_stat_record)
         if W is None:
             rc = self.lib.bmi_engine_set_ensemble_weights(self.handle, None, 0)
         else:
-            buf = torch.from_numpy(W).to(self.device)
+            buf = self._ens_w_dev = torch.from_numpy(W).to(self.device)
             self._cal_keep.append(buf)               # never freed before close(): a captured launch may still hold an earlier pointer
             rc = self.lib.bmi_engine_set_ensemble_weights(self.handle, C.c_void_p(buf.data_ptr()), self.n_exits)
         _lib.check(rc, "bmi_engine_set_ensemble_weights")
@@ -1669,6 +1670,112 @@ class MCDEngine(CompiledGraph):
                                            self._stream())
         _lib.check(rc, "bmi_rank_quality")
         return dict(rank=ints[0], sorted_keys=ints[1], curve=ints[2], counts=counts, aurc_sum=aurc_sum, n=n)
+
+    # ---- exit-policy sweep (bmi_exit_stat_record / bmi_exit_policy_sweep) ----------------------------------------------------------
+    def new_exit_stat_records(self, capacity, n_exits=None):
+        """The statistic buffer of ``capacity`` images for ``exit_stat_records``: dict(stat float64 [2, E, capacity], zeroed) — plane 0 the
+        exits' own statistics, plane 1 the exit ensembles'.  16 bytes per exit and image."""
+        E, cap = int(self.n_exits if n_exits is None else n_exits), int(capacity)
+        if E < 1 or cap < 1:
+            raise ValueError("new_exit_stat_records needs n_exits >= 1 and capacity >= 1")
+        return dict(stat=torch.zeros(2, E, cap, dtype=torch.float64, device=self.device))
+
+    def exit_stat_records(self, S, t_count, records, offset, rule="confidence"):
+        """Writes the decision statistics of one batch on the device (bmi_exit_stat_record): ``S`` [3, E, B, C], the sums ``accumulate``
+        filled over ``t_count`` samples (or S1 [E, B, C] alone), into columns ``offset .. offset + B - 1`` of ``records``
+        (``new_exit_stat_records``).  ``stat[ens, e, n]`` is the very number ``predict_early_exit(rule=, ensemble=ens)`` compares with its
+        threshold at exit e — S1 / t in the device rule's arithmetic, not ``finalize``'s mean S1 * (1 / t) —, under the engine's ensemble
+        weights if set.  A NaN is stored as it is.  One launch, no synchronisation; returns ``offset + B``.
+        ``train.exit_policy.exit_stat_numpy`` is the host restatement."""
+        if rule not in _lib.EXIT_RULES:
+            raise ValueError(f"rule must be one of {sorted(_lib.EXIT_RULES)}, got {rule!r}")
+        S1 = S[0] if S.dim() == 4 else S
+        E, B, Cd = check_buffer(S1, (None,) * 3, torch.float64, self.device, "S1 [E, B, C]").shape
+        cap = check_buffer(records["stat"], (2, E, None), torch.float64, self.device, "records['stat'] [2, E, capacity]").shape[2]
+        offset, t_count = int(offset), int(t_count)
+        if t_count < 1:
+            raise ValueError(f"t_count must be >= 1, got {t_count}")
+        if B < 1 or offset < 0 or offset + B > cap:
+            raise ValueError(f"images {offset} .. {offset + B - 1} do not fit the records' capacity {cap}")
+        if E > 32 or Cd > 128:
+            raise ValueError(f"exit_stat_records takes at most 32 exits and 128 classes (E = {E}, C = {Cd})")
+        w = self._ens_w_dev if E == self.n_exits else None
+        with torch.cuda.device(self.device):
+            rc = self.lib.bmi_exit_stat_record(S1.data_ptr(), E, B, Cd, t_count, _lib.EXIT_RULES[rule], _ptr(w), offset, cap,
+                                               records["stat"].data_ptr(), self._stream())
+        _lib.check(rc, "bmi_exit_stat_record")
+        return offset + B
+
+    def exit_policy_sweep(self, stat_records, reliability_records, n, thresholds, ensemble=False, first_exit=1, select=False, exit_of=False):
+        """The exit policy of every threshold over the first ``n`` images, on the device (bmi_exit_policy_sweep): ``stat_records`` from
+        ``exit_stat_records``, ``reliability_records`` from ``reliability_records`` (the outcome at every exit and exit ensemble),
+        ``thresholds`` a sequence or a float64 tensor [G], any order, G <= 1024.  Per threshold an image leaves at the lowest exit e in
+        [first_exit, E-2] whose statistic exceeds it (strictly), else at the last: the exit ``predict_early_exit`` assigns.  ``ensemble``:
+        the ensemble statistics decide and the equal-mean exit ensembles' outcome rows are read — ValueError while ensemble weights are
+        set, because those rows are not the weighted ensemble's.  A dict of device tensors: ``count`` / ``hits`` int64 [G, E] (images
+        leaving at each exit, the correct ones among them), ``invalid`` int64 [G] (images whose outcome record is empty: a bad label, a
+        non-finite row; in no count), ``thresholds`` float64 [G], with ``exit_of`` also ``exit_of`` uint8 [G, capacity], with ``select``
+        (G <= 64) also ``selected``: a record dict of G rows — the four records at the exit taken, zeros for an invalid image — that
+        ``reliability_table`` / ``reliability_kde`` / ``score_records(valid=)`` take as they take ``reliability_records``' — and ``n``.
+        Columns beyond ``n`` are zero.  Integers only; the same bits on every run and for every cut of the images into record calls.  A NaN
+        threshold lets nobody leave early.  Two launches, no synchronisation.  ``train.exit_policy.exit_policy_numpy`` restates it."""
+        R, cap = self._check_records(reliability_records)
+        E = R // 2
+        check_buffer(stat_records["stat"], (2, E, cap), torch.float64, self.device, "stat_records['stat'] [2, E, capacity]")
+        if R != 2 * E:
+            raise ValueError(f"reliability records of {R} rows are not 2 * E rows")
+        if not torch.is_tensor(thresholds):
+            thresholds = torch.as_tensor(np.asarray(thresholds, dtype=np.float64).reshape(-1))
+        thr = check_buffer(thresholds.to(device=self.device, dtype=torch.float64).contiguous(), (None,), torch.float64, self.device, "thresholds [G]")
+        G, n, first_exit, kind = thr.shape[0], int(n), int(first_exit), int(bool(ensemble))
+        if not 1 <= n <= cap:
+            raise ValueError(f"n = {n} outside [1, {cap}] (the records' capacity)")
+        if not 0 <= first_exit < E:
+            raise ValueError(f"first_exit must be in [0, {E})")
+        if not 1 <= G <= _lib.POLICY_MAX_THRESHOLDS:
+            raise ValueError(f"exit_policy_sweep takes 1 .. {_lib.POLICY_MAX_THRESHOLDS} thresholds, got {G}")
+        if select and G > _lib.POLICY_MAX_RECORD_ROWS:
+            raise ValueError(f"select=True takes at most {_lib.POLICY_MAX_RECORD_ROWS} thresholds (the rows a reliability table takes), got {G}")
+        if kind and self.ensemble_weights is not None:
+            raise ValueError("the ensemble policy under ensemble weights: the reliability records' ensemble rows are the equal-mean ensemble's")
+        ints = torch.empty(2, G, E, dtype=torch.int64, device=self.device)
+        invalid = torch.empty(G, dtype=torch.int64, device=self.device)
+        ex = torch.zeros(G, cap, dtype=torch.uint8, device=self.device) if exit_of else None
+        sel = None
+        if select:
+            sel = dict(keys=torch.zeros(G, cap, dtype=torch.int32, device=self.device), hit=torch.zeros(G, cap, dtype=torch.uint8, device=self.device),
+                       nll=torch.zeros(G, cap, dtype=torch.float64, device=self.device), brier=torch.zeros(G, cap, dtype=torch.float64, device=self.device),
+                       counters=torch.zeros(2, dtype=torch.int32, device=self.device))
+        rec = reliability_records
+        scratch = self._scratch("_nll_scratch", max(1, int(self.lib.bmi_exit_policy_scratch_bytes(E, n, G))))
+        with torch.cuda.device(self.device):
+            rc = self.lib.bmi_exit_policy_sweep(stat_records["stat"][kind].data_ptr(), E, n, cap, first_exit, thr.data_ptr(), G,
+                                                rec["keys"][kind * E:].data_ptr(), rec["hit"][kind * E:].data_ptr(), rec["nll"][kind * E:].data_ptr(),
+                                                rec["brier"][kind * E:].data_ptr(), ints[0].data_ptr(), ints[1].data_ptr(), invalid.data_ptr(),
+                                                _ptr(ex), *((_ptr(sel[k]) for k in ("keys", "hit", "nll", "brier")) if select else (None,) * 4),
+                                                scratch.data_ptr(), scratch.numel(), self._stream())
+        _lib.check(rc, "bmi_exit_policy_sweep")
+        out = dict(count=ints[0], hits=ints[1], invalid=invalid, thresholds=thr, n=n)
+        if exit_of:
+            out["exit_of"] = ex
+        if select:
+            out["selected"] = sel
+        return out
+
+    def exit_costs(self, T, first_exit=1):
+        """What an image costs when it leaves at each exit under ``predict_early_exit(T=, first_exit=)``, from ``exit_stages`` (host only):
+        dict(per_exit: a list of E Python ints, the cumulative MACs of the stages an image leaving at exit e ran — each stage's
+        prefix MACs without its whole-batch ops plus T x its suffix MACs; 0 for the exits before ``first_exit``, where nobody leaves —,
+        stage_macs / whole_batch_macs: the per-stage terms (whole-batch ops run over all B images whenever anybody reaches the stage),
+        macs_full: ``predict``'s MACs per image, T, first_exit).  ``train.exit_policy.policy_macs`` turns a count row into
+        ``predict_early_exit``'s ``macs_done``."""
+        T, first_exit = int(T), int(first_exit)
+        if T < 1:
+            raise ValueError(f"T must be >= 1, got {T}")
+        from .train.exit_policy import stage_costs
+        costs = stage_costs(self.exit_stages(first_exit), T, first_exit, self.n_exits)
+        costs["macs_full"] = int(self.prefix_macs + T * self.suffix_macs)
+        return costs
 
     def read_tensor(self, tensor_id, batch, samples=1):
         """A copy of graph tensor ``tensor_id`` as it sits in the workspace after a forward (bmi_tensor_info): fp32

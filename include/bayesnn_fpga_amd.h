@@ -960,6 +960,57 @@ int bmi_rank_quality(const uint32_t* ukeys, const uint8_t* positive, int32_t R, 
                      int32_t* curve, int64_t* counts /*[R][3]*/, double* aurc_sum /*[R]*/, void* scratch, size_t scratch_bytes,
                      bmi_stream stream);
 
+/* Exit-policy sweep: for many thresholds at once, where every image would leave under the staged engine's rule and what the predictions
+ * taken there are worth — the trade-off table of the reference's get_confidence_exiting_values (SA/train/results_analyzer.py:543-566:
+ * confidence_exiting, flop_saver, flop_saver_ensembled over eleven thresholds) from per-image records that stay on the device
+ * (csrc/exit_policy.hip; train.exit_policy.exit_stat_numpy / exit_policy_numpy restate both calls).
+ *
+ * bmi_exit_stat_record writes the decision statistics of a batch: S1 float64 [E][B][C] (device: the sums of t_count samples'
+ * probabilities, as every forward call leaves them) -> columns n0 .. n0 + B - 1 of stat float64 [2][E][N_cap].  stat[ens][e][n0 + b] is the
+ * number bmi_forward_mcd_exit_staged compares with its threshold at exit e under (criterion, ensemble = ens) — compiled from the same
+ * function (csrc/exit_rule.h), so the same bits: float64, no fused multiply-add,
+ *     p_c = S1[e][b][c] / t                                                 (ens 0)
+ *     p_c = (((0.0 + S1[0][b][c] / t) + S1[1][b][c] / t) + ... ) / (e + 1)   (ens 1, weights NULL)
+ *     p_c = ((0.0 + w[e][0] * (S1[0][b][c] / t)) + w[e][1] * (S1[1][b][c] / t)) + ...   up to exit e   (ens 1, weights device [E][E])
+ *     BMI_EXIT_CONFIDENCE: max_c p_c;   BMI_EXIT_MARGIN: top-1 minus top-2 (0 on a tie; top-1 alone when C = 1)
+ * A NaN statistic is stored as it is: the rule's stat > threshold is false for it, here as there.  One launch, no allocation, no
+ * synchronisation: capturable.  BMI_ERR_INVALID (decided before any HIP call): a NULL S1 or stat, E / B / C / t_count / N_cap below 1,
+ * n0 < 0, n0 + B > N_cap, an unknown criterion.  BMI_ERR_UNSUPPORTED: E > 32, C > 128.  An error writes nothing.
+ *
+ * bmi_exit_policy_sweep reads columns 0 .. N-1 of stat [E][N_cap] — ONE plane of the record (ens 0: the record's base; ens 1: base +
+ * E * N_cap) —, G thresholds (device float64, any order, repeats allowed) and the outcome rows keys / hit / nll / brier [E][N_cap] each: the
+ * reliability records (bmi_reliability_record) offset to row kind * E — kind 0 for the exits' own predictions, kind 1 for the equal-mean
+ * exit ensembles'.  Per threshold g and image n:
+ *     e* = the lowest e in [first_exit, E-2] with stat[e][n] > thresholds[g] (strict, float64), E-1 if there is none.  The statistic decides
+ *          alone: e* is the exit_of_image bmi_forward_mcd_exit_staged assigns under that threshold.  A NaN threshold lets nobody leave
+ *          early (it is on the device and cannot be refused before a HIP call).
+ *     exit_of[g][n] = e*                                     uint8 [G][N_cap], or NULL
+ *     keys[e*][n] == 0 (a bad label, a non-finite row):      invalid[g] += 1; the selected record is all zeros, which the table and KDE
+ *                                                            calls skip
+ *     otherwise  count[g][e*] += 1,  hits[g][e*] += hit[e*][n] != 0,  and the selected records sel_keys / sel_hit / sel_nll / sel_brier
+ *                [G][N_cap] (all four or none; G <= BMI_POLICY_MAX_RECORD_ROWS) are copies of the four records at (e*, n): a valid R = G
+ *                record set for bmi_reliability_table, bmi_reliability_kde and bmi_score_record(valid_keys =) — the ECE, KDE-ECE, NLL and
+ *                Brier of the exited predictions, with the bit contracts of those calls.
+ * count, hits int64 [G][E] and invalid int64 [G] are OVERWRITTEN; exit_of and the selected records in columns 0 .. N-1 only.  Integer
+ * LDS atomics and integer partial sums only, no floating-point atomics: the same bits on every run and for every cut of the images into
+ * record calls.  Two launches, no allocation, no synchronisation: capturable.  scratch: bmi_exit_policy_scratch_bytes = min(ceil(N / 128),
+ * 128) * G * (2 E + 1) * 4 (0 for arguments the call refuses).
+ * BMI_ERR_INVALID (decided before any HIP call): a NULL required pointer, some but not all of the four sel_ pointers, E / N / G below 1,
+ * N > N_cap, first_exit outside [0, E).  BMI_ERR_UNSUPPORTED: E > 32, G > BMI_POLICY_MAX_THRESHOLDS, N >= 2^22, selected records with
+ * G > BMI_POLICY_MAX_RECORD_ROWS.  BMI_ERR_NOMEM: scratch too small.  An error writes nothing. */
+#define BMI_POLICY_MAX_THRESHOLDS 1024
+#define BMI_POLICY_MAX_RECORD_ROWS 64      /* = what bmi_reliability_table takes as R */
+int bmi_exit_stat_record(const double* S1 /*[E][B][C]*/, int32_t E, int32_t B, int32_t C, int32_t t_count,
+                         int32_t criterion /*BMI_EXIT_CONFIDENCE | BMI_EXIT_MARGIN*/, const double* weights /*device [E][E] or NULL*/, int32_t n0,
+                         int32_t N_cap, double* stat /*[2][E][N_cap]*/, bmi_stream stream);
+size_t bmi_exit_policy_scratch_bytes(int32_t E, int32_t N, int32_t G);
+int bmi_exit_policy_sweep(const double* stat /*[E][N_cap]*/, int32_t E, int32_t N, int32_t N_cap, int32_t first_exit,
+                          const double* thresholds /*device [G]*/, int32_t G, const uint32_t* keys, const uint8_t* hit, const double* nll,
+                          const double* brier /*outcome rows: [E][N_cap] each*/, int64_t* count /*[G][E]*/, int64_t* hits /*[G][E]*/,
+                          int64_t* invalid /*[G]*/, uint8_t* exit_of /*[G][N_cap] or NULL*/, uint32_t* sel_keys, uint8_t* sel_hit,
+                          double* sel_nll, double* sel_brier /*[G][N_cap] each, all four or none*/, void* scratch, size_t scratch_bytes,
+                          bmi_stream stream);
+
 /* Per-op-kind HIP-event timing of bmi_forward_mcd (off by default; adds two event records per
  * launch).  bmi_profile_read synchronises the recorded events and resets the accumulators. */
 int bmi_profile_enable(bmi_handle h, int32_t enable);
