@@ -12,7 +12,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libbayesnn_fpga_amd.so")
-SOURCES = ["conv_igemm.hip", "conv_igemm_wide.hip", "conv3x3_patch.hip", "conv3x3_pw.hip", "conv3x3_s2.hip", "conv1x1_stream.hip", "conv1x1_seam.hip", "conv_exact.hip", "conv_split.hip", "misc_kernels.hip", "dense_f32.hip", "head_fused.hip", "head_fused_temp.hip", "head_fused_vec.hip", "head_fused_mat.hip", "calibration.hip", "ensemble.hip", "pass_accuracy.hip", "reliability.hip", "reliability_kde.hip", "ranking.hip", "exit_policy.hip", "votes.hip", "votes_rows.hip", "engine.hip"]
+SOURCES = ["conv_igemm.hip", "conv_igemm_wide.hip", "conv3x3_patch.hip", "conv3x3_pw.hip", "conv3x3_s2.hip", "conv1x1_stream.hip", "conv1x1_seam.hip", "conv_exact.hip", "conv_split.hip", "misc_kernels.hip", "dense_f32.hip", "head_fused.hip", "head_fused_temp.hip", "head_fused_vec.hip", "head_fused_mat.hip", "calibration.hip", "ensemble.hip", "pass_accuracy.hip", "reliability.hip", "reliability_kde.hip", "reliability_classwise.hip", "ranking.hip", "exit_policy.hip", "votes.hip", "votes_rows.hip", "engine.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 
 

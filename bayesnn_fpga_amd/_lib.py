@@ -147,6 +147,8 @@ _PROTOS = {
     "bmi_reliability_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "bmi_reliability_table": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 4 + [C.POINTER(C.c_float)] + [C.c_void_p] * 6 + [C.c_size_t, C.c_void_p]),
     "bmi_reliability_kde": (C.c_int, [C.c_void_p] * 2 + [C.c_int32] * 5 + [C.c_double] + [C.c_void_p] * 8),
+    "bmi_classwise_record": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 4),
+    "bmi_classwise_table": (C.c_int, [C.c_void_p] * 2 + [C.c_int32] * 5 + [C.POINTER(C.c_float)] + [C.c_void_p] * 6),
     "bmi_score_record": (C.c_int, [C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 3),
     "bmi_rank_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "bmi_rank_quality": (C.c_int, [C.c_void_p] * 2 + [C.c_int32] * 3 + [C.c_void_p] * 6 + [C.c_size_t, C.c_void_p]),

@@ -2348,6 +2348,28 @@ int bmi_reliability_kde(const uint32_t* keys, const uint8_t* hit, int32_t R, int
                                   density, (hipStream_t)stream);
 }
 
+int bmi_classwise_record(const double* mean, int32_t E, int32_t B, int32_t C, const int32_t* labels, int32_t n0, int32_t N_cap, uint32_t* pkeys,
+                         int32_t* labels_rec, int32_t* counters, bmi_stream stream) {
+    if (!mean || !labels || !pkeys || !labels_rec || E < 1 || B < 1 || C < 1 || N_cap < 1 || n0 < 0 || (int64_t)n0 + B > N_cap)
+        return BMI_ERR_INVALID;
+    if (!reliability_record_takes(E, B, C)) return BMI_ERR_UNSUPPORTED;
+    return launch_classwise_record(mean, E, B, C, labels, n0, N_cap, pkeys, labels_rec, counters, (hipStream_t)stream);
+}
+
+int bmi_classwise_table(const uint32_t* pkeys, const int32_t* labels_rec, int32_t R, int32_t C, int32_t N, int32_t N_cap, int32_t n_bins,
+                        const float* edges_in, float* edges_out, int64_t* count, int64_t* hits, int64_t* conf_fix, int64_t* valid,
+                        bmi_stream stream) {
+    if (!pkeys || !labels_rec || !edges_out || !count || !hits || !conf_fix || !valid || R < 1 || C < 1 || N < 1 || N > N_cap || n_bins < 1 ||
+        n_bins > BMI_REL_MAX_BINS)
+        return BMI_ERR_INVALID;
+    if (edges_in)
+        for (int i = 0; i <= n_bins; ++i)
+            if (!std::isfinite(edges_in[i]) || (i && edges_in[i] < edges_in[i - 1])) return BMI_ERR_INVALID;
+    if (!classwise_table_takes(R, C, N, n_bins)) return BMI_ERR_UNSUPPORTED;
+    return launch_classwise_table(pkeys, labels_rec, R, C, N, N_cap, n_bins, edges_in, edges_out, (long long*)count, (long long*)hits,
+                                  (long long*)conf_fix, (long long*)valid, (hipStream_t)stream);
+}
+
 int bmi_score_record(const double* score, int32_t R, int32_t B, int32_t direction, const uint32_t* valid_keys, int32_t n0, int32_t N_cap,
                      uint32_t* ukeys, int32_t* counter, bmi_stream stream) {
     if (!score || !ukeys || R < 1 || B < 1 || N_cap < 1 || n0 < 0 || (int64_t)n0 + B > N_cap || (direction != 1 && direction != -1))

@@ -1607,6 +1607,96 @@ class MCDEngine(CompiledGraph):
                                  ", ".join(names[r] for r in bad))
         return dict(ece_kde=f64[0], bw=f64[1], sd=f64[2], n_data=i64[0], n_hit=i64[1], degenerate=degenerate, density=density)
 
+    # ---- classwise reliability tables (bmi_classwise_record / bmi_classwise_table) -------------------------------------------------
+    def new_classwise_records(self, capacity, n_exits=None, out_dim=None):
+        """The record buffers of ``capacity`` images for ``classwise_records``: dict(pkeys int32 [R, C, capacity] — the float32 bit patterns
+        of EVERY class's confidence, filled with INVALID (all ones: -1) —, labels int32 [capacity], filled with -1, counters int32 [2] =
+        (non-finite rows, bad labels), zeroed), R = 2 * n_exits rows: the exits, then the exit ensembles; C = out_dim.
+        4 * R * C bytes per image (plus 4 for the label): 32 MB at 4 exits, 100 classes and 10 000 images."""
+        R, cap = 2 * int(self.n_exits if n_exits is None else n_exits), int(capacity)
+        Cd = int(self.out_dim if out_dim is None else out_dim)
+        if R < 2 or cap < 1 or Cd < 1:
+            raise ValueError("new_classwise_records needs n_exits >= 1, out_dim >= 1 and capacity >= 1")
+        return dict(pkeys=torch.full((R, Cd, cap), -1, dtype=torch.int32, device=self.device),
+                    labels=torch.full((cap,), -1, dtype=torch.int32, device=self.device),
+                    counters=torch.zeros(2, dtype=torch.int32, device=self.device))
+
+    def _check_classwise_records(self, records):
+        R, Cd, cap = check_buffer(records["pkeys"], (None,) * 3, torch.int32, self.device, "records['pkeys'] [R, C, capacity]").shape
+        check_buffer(records["labels"], (cap,), torch.int32, self.device, "records['labels'] [capacity]")
+        check_buffer(records["counters"], (2,), torch.int32, self.device, "records['counters'] [2]")
+        return R, Cd, cap
+
+    def classwise_records(self, mean, labels, records, offset):
+        """Writes the classwise records of one batch on the device (bmi_classwise_record): ``mean`` float64 [E, B, C] (``finalize``'s
+        T-mean probabilities), ``labels`` int [B], into columns ``offset .. offset + B - 1`` of ``records`` (``new_classwise_records``).
+        Per exit and per exit ensemble, image AND class: the float32 confidence p_c / sum p (zero below 2^-126) as its bit pattern — at
+        the arg-max class the key ``reliability_records`` writes —, and the image's label.  A non-finite row or a label outside [0, C)
+        leaves INVALID keys (a bad label: the label record -1) and counts in ``records['counters']``.  4 * R * C bytes per image.
+        One launch, no synchronisation; returns ``offset + B``.  ``train.reliability.classwise_numpy`` is the host restatement."""
+        E, B, Cd = check_buffer(mean, (None,) * 3, torch.float64, self.device, "mean [E, B, C]").shape
+        labels = check_buffer(labels.to(device=self.device, dtype=torch.int32).contiguous(), (B,), torch.int32, self.device, "labels [B]")
+        R, Cr, cap = self._check_classwise_records(records)
+        offset = int(offset)
+        if R != 2 * E:
+            raise ValueError(f"records hold {R} rows, mean has {E} exits (2 * E rows)")
+        if Cr != Cd:
+            raise ValueError(f"records hold {Cr} classes, mean has {Cd}")
+        if offset < 0 or offset + B > cap:
+            raise ValueError(f"images {offset} .. {offset + B - 1} do not fit the records' capacity {cap}")
+        with torch.cuda.device(self.device):
+            rc = self.lib.bmi_classwise_record(mean.data_ptr(), E, B, Cd, labels.data_ptr(), offset, cap, records["pkeys"].data_ptr(),
+                                               records["labels"].data_ptr(), records["counters"].data_ptr(), self._stream())
+        _lib.check(rc, "bmi_classwise_record")
+        return offset + B
+
+    def classwise_table(self, records, n, n_bins=15, binning="width", edges=None, check=True):
+        """The classwise reliability table of the first ``n`` images of ``records`` on the device (bmi_classwise_table): a dict of device
+        tensors — ``edges`` float32 [R, C, n_bins + 1], ``count`` / ``hits`` / ``conf_fix`` int64 [R, C, n_bins] (per class the pairs
+        (image, class), those whose label is the class, and the sum of the truncated confidence * 2^40 per bin; bin 0 is closed at its
+        lower edge, so confidence zero is counted), ``valid`` int64 [R] (the images of the row that are data) — and ``n``.  ``binning``:
+        "width" (edges i / n_bins: the published classwise ECE), "mass" (per (row, class) the order statistics of its confidences) or
+        "edges" with the caller's ``edges`` [n_bins + 1] (finite, non-decreasing; ``edges[0] > 0`` ignores the negligible probabilities),
+        which then sets ``n_bins``.  Exact integers, the same bits on every run and for every cut of the images into ``classwise_records``
+        calls; ``train.reliability.classwise_metrics`` derives the classwise ECE.  Two launches, no allocation beyond the outputs.
+        ``check`` (a host read: synchronises; pass False under a graph capture): FloatingPointError if a record was non-finite,
+        ValueError if a label was outside [0, C)."""
+        R, Cd, cap = self._check_classwise_records(records)
+        n = int(n)
+        if not 1 <= n <= cap:
+            raise ValueError(f"n = {n} outside [1, {cap}] (the records' capacity)")
+        if binning not in ("mass", "width", "edges"):
+            raise ValueError(f"binning must be 'mass', 'width' or 'edges', got {binning!r}")
+        if binning == "edges":
+            if edges is None:
+                raise ValueError("binning 'edges' needs edges [n_bins + 1]")
+            fixed = np.asarray(edges.detach().cpu() if torch.is_tensor(edges) else edges, dtype=np.float32).reshape(-1)
+            n_bins = fixed.shape[0] - 1
+            if n_bins >= 1 and (not np.isfinite(fixed).all() or (np.diff(fixed) < 0).any()):
+                raise ValueError("edges must be finite and non-decreasing")
+        else:
+            n_bins = int(n_bins)
+        if not 1 <= n_bins <= _lib.REL_MAX_BINS:
+            raise ValueError(f"n_bins must be in [1, {_lib.REL_MAX_BINS}]")
+        if binning == "width":
+            fixed = np.arange(n_bins + 1, dtype=np.float32) / np.float32(n_bins)
+        edges_in = None if binning == "mass" else (C.c_float * (n_bins + 1))(*[float(v) for v in fixed])
+        out_edges = torch.empty(R, Cd, n_bins + 1, dtype=torch.float32, device=self.device)
+        ints = torch.empty(3, R, Cd, n_bins, dtype=torch.int64, device=self.device)
+        valid = torch.empty(R, dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = self.lib.bmi_classwise_table(records["pkeys"].data_ptr(), records["labels"].data_ptr(), R, Cd, n, cap, n_bins, edges_in,
+                                              out_edges.data_ptr(), ints[0].data_ptr(), ints[1].data_ptr(), ints[2].data_ptr(), valid.data_ptr(),
+                                              self._stream())
+        _lib.check(rc, "bmi_classwise_table")
+        if check:
+            nonfinite, badlabel = (int(v) for v in records["counters"].tolist())
+            if nonfinite:
+                raise FloatingPointError(f"{nonfinite} classwise records with a non-finite probability on the {self.dtype!r} engine")
+            if badlabel:
+                raise ValueError(f"{badlabel} images with a label outside [0, C) in the classwise records")
+        return dict(edges=out_edges, count=ints[0], hits=ints[1], conf_fix=ints[2], valid=valid, n=n)
+
     # ---- rank quality of the uncertainty scores (bmi_score_record / bmi_rank_quality) ---------------------------------------------
     def new_score_records(self, capacity, rows):
         """The key buffer of ``capacity`` images and ``rows`` rows for ``score_records``: dict(ukeys int32 [rows, capacity] — uint32 bit

@@ -123,6 +123,121 @@ def table_metrics(table, n=None):
                 brier=_np(table["brier_sum"]).astype(np.float64) / n)
 
 
+INVALID = np.uint32(0xFFFFFFFF)   # a classwise key of a (row, image) that is not data (ranking.hip's convention)
+FLUSH = 2.0 ** -126               # a quotient below the least normal float32 is confidence zero
+
+
+def classwise_numpy(mean, labels, n_bins=15, binning="width", edges=None):
+    """The host restatement of bmi_classwise_record + bmi_classwise_table (the header comment of csrc/reliability_classwise.hip): ``mean``
+    float64 [E, N, C], ``labels`` int [N]; rows r = kind * E + e as in ``reliability_numpy``.  Per (row, image): pc = max(v, 1e-256), s the
+    ascending class sum, and for EVERY class conf_c = 0.0f if pc_c / s < 2^-126 else (float) (pc_c / s).  ``binning``: "width" (``width_edges(
+    n_bins)``: the published classwise ECE), "mass" (per (row, class) the order statistics of its N keys) or "edges" (the caller's ``edges``
+    float32 [n_bins + 1], which then sets ``n_bins``).  Bin 0 is closed at its lower edge: confidence zero is counted.
+
+    Returns dict(pkeys uint32 [R, C, N] — INVALID (all ones) where the label is outside [0, C) or the row non-finite —, labels int32 [N]
+    (-1 for a bad label), edges float32 [R, C, n_bins + 1], count, hits, conf_fix int64 [R, C, n_bins] (conf_fix = sum of the TRUNCATED
+    (int64) (conf * 2^40)), valid int64 [R], nonfinite, badlabel, n).  4 R C bytes per image on the device.  The class sum is an explicit
+    ascending loop; the rest loops over rows and bins and is vectorised over classes and images (integer sums: order-free)."""
+    mean = np.asarray(mean, dtype=np.float64)
+    if mean.ndim != 3:
+        raise ValueError("mean must be [E, N, C]")
+    E, N, Cd = mean.shape
+    y = np.asarray(labels).astype(np.int64).reshape(-1)
+    if y.shape[0] != N:
+        raise ValueError("labels must be [N]")
+    if binning not in ("mass", "width", "edges"):
+        raise ValueError(f"binning must be 'mass', 'width' or 'edges', got {binning!r}")
+    if binning == "edges":
+        if edges is None:
+            raise ValueError("binning 'edges' needs edges [n_bins + 1]")
+        fixed = np.asarray(edges, dtype=np.float32).reshape(-1)
+        n_bins = fixed.shape[0] - 1
+        if n_bins < 1 or not np.isfinite(fixed).all() or (np.diff(fixed) < 0).any():
+            raise ValueError("edges must be finite, non-decreasing and at least two")
+    else:
+        n_bins = int(n_bins)
+        fixed = width_edges(n_bins) if binning == "width" else None
+    R = 2 * E
+    labelled = (y >= 0) & (y < Cd)
+    rows = [None] * R
+    acc = np.zeros((N, Cd), dtype=np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for e in range(E):
+            acc = acc + mean[e]
+            rows[e], rows[E + e] = mean[e], acc / float(e + 1)
+    pkeys = np.empty((R, Cd, N), dtype=np.uint32)
+    valid = np.zeros(R, dtype=np.int64)
+    nonfinite = 0
+    for r, v in enumerate(rows):
+        finite = np.isfinite(v).all(axis=1)
+        ok = labelled & finite
+        nonfinite += int((labelled & ~finite).sum())
+        valid[r] = int(ok.sum())
+        v = np.where(ok[:, None], v, 1.0)                    # (invalid images: a finite placeholder whose results are dropped)
+        pc = np.maximum(v, 1e-256)
+        s = np.zeros(N, dtype=np.float64)
+        for c in range(Cd):                                  # ascending class order
+            s = s + pc[:, c]
+        for c in range(Cd):
+            q = pc[:, c] / s
+            conf = np.where(q < FLUSH, 0.0, q).astype(np.float32)
+            pkeys[r, c] = np.where(ok, conf.view(np.uint32), INVALID)
+    out_edges = np.empty((R, Cd, n_bins + 1), dtype=np.float32)
+    if fixed is None:
+        per = N // n_bins
+        for r in range(R):
+            for c in range(Cd):
+                srt = np.sort(pkeys[r, c])                   # unsigned order: INVALID keys last
+                out_edges[r, c, 0] = 0.0
+                for i in range(n_bins):
+                    k = srt[min((i + 1) * per, N - 1)]
+                    out_edges[r, c, i + 1] = 1.0 if k == INVALID else k.view(np.float32)
+                out_edges[r, c, n_bins] = 1.0
+    else:
+        out_edges[:] = fixed
+    count = np.zeros((R, Cd, n_bins), dtype=np.int64)
+    hits = np.zeros((R, Cd, n_bins), dtype=np.int64)
+    conf_fix = np.zeros((R, Cd, n_bins), dtype=np.int64)
+    is_label = (np.where(labelled, y, -1)[None, :] == np.arange(Cd)[:, None])               # [C, N]
+    for r in range(R):
+        data = pkeys[r] != INVALID
+        conf = np.where(data, pkeys[r], 0).astype(np.uint32).view(np.float32)               # [C, N]
+        fix = (conf.astype(np.float64) * FIX).astype(np.int64)                              # truncates
+        ed = out_edges[r]
+        for i in range(n_bins):
+            lower = conf >= ed[:, 0, None] if i == 0 else conf > ed[:, i, None]
+            sel = data & lower & (conf <= ed[:, i + 1, None])  # (the edges do not decrease: above edges[i] is at or above edges[0])
+            count[r, :, i] = sel.sum(axis=1)
+            hits[r, :, i] = (sel & is_label).sum(axis=1)
+            conf_fix[r, :, i] = np.where(sel, fix, 0).sum(axis=1)
+    return dict(pkeys=pkeys, labels=np.where(labelled, y, -1).astype(np.int32), edges=out_edges, count=count, hits=hits, conf_fix=conf_fix,
+                valid=valid, nonfinite=nonfinite, badlabel=int((~labelled).sum()), n=N)
+
+
+def classwise_metrics(table):
+    """float64 on the host, from a table of ``MCDEngine.classwise_table`` or ``classwise_numpy``: dict(cw_ece_per_class [R, C] =
+    sum_i |hits_i - conf_fix_i / 2^40| / valid[r] — class c's share of the classwise ECE: per bin |accuracy - mean confidence| weighted by
+    count / valid —, cw_ece [R] = its mean over the classes, cw_mce [R, C] = the largest |hits_i / count_i - conf_fix_i / 2^40 / count_i|
+    over the non-empty bins, class_count int64 [R, C] = sum_i hits_i (the valid images of label c that a bin holds)).  A row with
+    ``valid == 0`` gives NaN."""
+    count, hits, fix, valid = (_np(table[k]).astype(np.int64) for k in ("count", "hits", "conf_fix", "valid"))
+    R, Cd, n_bins = count.shape
+    per_class = np.full((R, Cd), np.nan, dtype=np.float64)
+    mce = np.full((R, Cd), np.nan, dtype=np.float64)
+    for r in range(R):
+        if valid[r] == 0:
+            continue
+        gap = np.abs(hits[r].astype(np.float64) - fix[r].astype(np.float64) / FIX)           # [C, n_bins]
+        tot = np.zeros(Cd, dtype=np.float64)
+        for i in range(n_bins):                              # bin order
+            tot = tot + gap[:, i]
+        per_class[r] = tot / float(valid[r])
+        filled = count[r] > 0
+        k = np.where(filled, count[r], 1).astype(np.float64)
+        mce[r] = np.where(filled, np.abs(hits[r] / k - fix[r].astype(np.float64) / FIX / k), 0.0).max(axis=1)
+    return dict(cw_ece=per_class.mean(axis=1), cw_ece_per_class=per_class, cw_mce=mce, class_count=hits.sum(axis=2))
+
+
 def kde_bw_scale(n):
     """The reference's bandwidth factor (2 N)^-0.2 (SA/train/results_analyzer.py:386-391), formed on the host: what ``reliability_kde``
     receives as ``bw_scale`` by default"""
@@ -238,9 +353,16 @@ class ReliabilityAnalysis:
     ``kde=True``: one more device call after the table, ``MCDEngine.reliability_kde`` on ``grid_points`` grid points — the reference's own
     ``ECE`` column (the KDE-ECE of ``train.metrics.ece_kde_binary``, exact densities).  ``kde``: its device tensors (False without it);
     ``metrics["ece_kde"]`` float64 [R], NaN in a degenerate row (no hit, one hit, equal hit confidences: the reference's NaN); ``rows`` gains
-    the value as a seventh element and ``save`` an ``ECE_KDE`` column."""
+    the value as a seventh element and ``save`` an ``ECE_KDE`` column.
 
-    def __init__(self, model, loader, gpu=0, mc_passes=10, seed=0, n_bins=15, binning="mass", kde=False, grid_points=2 ** 14):
+    ``classwise=True``: the walk also fills the classwise records per batch (``MCDEngine.classwise_records``: 4 R C bytes per image) and ONE
+    ``MCDEngine.classwise_table`` call (``classwise_bins`` bins, ``classwise_binning`` "width" or "mass") follows it.  ``classwise``: its
+    device tensors (False without it); ``metrics`` gains ``cw_ece`` [R] and ``cw_ece_per_class`` [R, C] (``classwise_metrics``); ``rows``
+    gains the classwise ECE as one more element, after the KDE value when both are asked for, and ``save`` a ``CW_ECE`` column.  Without
+    it nothing of this is allocated or launched."""
+
+    def __init__(self, model, loader, gpu=0, mc_passes=10, seed=0, n_bins=15, binning="mass", kde=False, grid_points=2 ** 14,
+                 classwise=False, classwise_bins=15, classwise_binning="width"):
         self.model = model
         self.loader = loader
         self.device = get_device(gpu)
@@ -250,6 +372,11 @@ class ReliabilityAnalysis:
         self.binning = binning
         self.kde = bool(kde)
         self.grid_points = int(grid_points)
+        self.classwise = bool(classwise)
+        self.classwise_bins = int(classwise_bins)
+        self.classwise_binning = classwise_binning
+        if self.classwise and classwise_binning not in ("width", "mass"):
+            raise ValueError(f"classwise_binning must be 'width' or 'mass', got {classwise_binning!r}")
         self._run()
 
     def _engine(self, b_x):
@@ -272,17 +399,21 @@ class ReliabilityAnalysis:
         if _rank_world(None)[1] > 1:
             raise NotImplementedError("ReliabilityAnalysis under a sharded walk: the records are not part of "
                                       "sharding.accumulate_partitioned's all-reduce")
-        eng, records, labels, off = None, None, [], 0
+        eng, records, cw_records, labels, off = None, None, None, [], 0
         for k, batch in enumerate(self.loader):
             b_x = batch[0].to(self.device)
             if eng is None:
                 eng = self._engine(b_x)
                 records = eng.new_reliability_records(max(1, self._capacity()))
+                if self.classwise:
+                    cw_records = eng.new_classwise_records(max(1, self._capacity()))
             ml = self.model.mask_layers()
             T, seed, cnt0 = self.mc_passes, self.seed + k, (ml[0].cnt if ml else 0)
             self.model.advance(T)
             mean = eng.predict(b_x, T, seed, cnt0=cnt0)["mean"]
             y = torch.as_tensor(np.asarray(batch[1]).astype(np.int64))
+            if self.classwise:
+                eng.classwise_records(mean, y, cw_records, off)
             off = eng.reliability_records(mean, y, records, off)
             labels.append(y.numpy())
         if eng is None:
@@ -300,12 +431,18 @@ class ReliabilityAnalysis:
             self.kde = eng.reliability_kde(records, off, self.grid_points, check=False)
             m["ece_kde"] = np.where(_np(self.kde["degenerate"]) != 0, np.nan, _np(self.kde["ece_kde"]))
             self.rows = [row + (float(v),) for row, v in zip(self.rows, m["ece_kde"])]
+        if self.classwise:
+            self.classwise_records = cw_records
+            self.classwise = eng.classwise_table(cw_records, off, self.classwise_bins, self.classwise_binning, check=False)
+            cw = classwise_metrics(self.classwise)
+            m["cw_ece"], m["cw_ece_per_class"] = cw["cw_ece"], cw["cw_ece_per_class"]
+            self.rows = [row + (float(v),) for row, v in zip(self.rows, m["cw_ece"])]
 
     def save(self, experiment_id):
         """``test_reliability_<experiment_id>.csv``: a header line, then ``rows``; returns the file name."""
         name = f"test_reliability_{experiment_id}.csv"
         with open(name, "w") as f:
-            f.write("Layer,Accuracy,ECE,MCE,NLL,Brier" + (",ECE_KDE" if self.kde else "") + "\n")
+            f.write("Layer,Accuracy,ECE,MCE,NLL,Brier" + (",ECE_KDE" if self.kde else "") + (",CW_ECE" if self.classwise else "") + "\n")
             for r in self.rows:
                 f.write(",".join(str(v) for v in r) + "\n")
         return name

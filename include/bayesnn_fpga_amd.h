@@ -912,6 +912,43 @@ int bmi_reliability_kde(const uint32_t* keys, const uint8_t* hit, int32_t R, int
                         double* ece_kde /*[R]*/, double* bw /*[R]*/, double* sd /*[R]*/, int64_t* n_data /*[R]*/, int64_t* n_hit /*[R]*/,
                         int32_t* degenerate /*[R]*/, double* density /*[R][2][G]*/, bmi_stream stream);
 
+/* Classwise reliability tables: the confidence histogram behind the classwise ECE (Kull et al. 2019) per exit, per exit ensemble AND PER
+ * CLASS — what the top-label calls above drop: the other C - 1 probabilities of every image.  Rows as above (R = 2 E, r = kind * E + e, the
+ * ensemble added in exit order from 0.0 and divided once).  Per row and image, v = the row's C values, float64 and no fused multiply-add
+ * (the contract, operation by operation, is the header comment of csrc/reliability_classwise.hip; train.reliability.classwise_numpy restates it):
+ *     pc_c = max(v_c, 1e-256),   s = ((0.0 + pc_0) + pc_1) + ...  (ascending class order: the s of bmi_reliability_record)
+ *     q_c = pc_c / s for EVERY class,   conf_c = 0.0f if q_c < 2^-126 (an explicit compare on the double), else (float) q_c;  conf_c <= 1.0f
+ *     key_c = the float32 bit pattern of conf_c;  at the arg-max class it is bit for bit the key bmi_reliability_record writes
+ * An image whose label is outside [0, C): all R C keys of it INVALID (0xFFFFFFFF), label record -1, counters[1] += 1.  Otherwise a (row,
+ * image) with a non-finite v_c: that row's C keys INVALID, counters[0] += 1.  Key 0 is a VALID key here (confidence zero).
+ *
+ * The record call writes the B images of one batch at columns n0 .. n0 + B - 1 of pkeys uint32 [R][C][N_cap] (the image index fastest) and
+ * labels_rec int32 [N_cap]: 4 R C bytes per image — 32 MB at E = 4, C = 100, N = 10 000.  mean: device float64 [E][B][C], labels: device
+ * int32 [B]; counters: device int32 [2], ADDED to, or NULL (not counted).  One launch, no allocation, no synchronisation: capturable.
+ * BMI_ERR_INVALID (decided before any HIP call): a null pointer other than counters, a count below 1, n0 < 0, n0 + B > N_cap.
+ * BMI_ERR_UNSUPPORTED: C > 128, E > 32, B >= 2^25 (the launch grid).  An error writes nothing. */
+int bmi_classwise_record(const double* mean, int32_t E, int32_t B, int32_t C, const int32_t* labels, int32_t n0, int32_t N_cap, uint32_t* pkeys,
+                         int32_t* labels_rec, int32_t* counters /* device [2], ADDED to; NULL: not counted */, bmi_stream stream);
+
+/* The classwise table of columns 0 .. N-1 of the records, every output OVERWRITTEN:
+ *     edges    float32 [R][C][n_bins + 1].  edges_in NULL: by mass, per (row, class) — per = N / n_bins (integer), edges[0] = 0, edges[i + 1]
+ *              = the order statistic of rank min((i + 1) * per, N - 1) (0-based) of that line's N keys in unsigned order (radix select: exact
+ *              under duplicates; INVALID keys sort last, a selected INVALID key gives 1.0f), edges[n_bins] = 1.  Otherwise edges_in: HOST
+ *              float32 [n_bins + 1], finite and non-decreasing, read during the call, copied to every (row, class).
+ *     count, hits, conf_fix   int64 [R][C][n_bins]: a valid pair (image n, class c) with conf >= edges[0] is in the lowest bin j with
+ *              conf <= edges[j + 1]; below edges[0] or above edges[n_bins] in none.  Bin 0 is CLOSED at its lower edge (confidence 0 is
+ *              counted: the other classes' confidences are data) — the top-label table's is open; edges_in[0] > 0 ignores the
+ *              negligible probabilities.  hits: the pairs with labels_rec[n] == c.  conf_fix = sum (int64)((double) conf * 2^40),
+ *              truncating: an exact integer definition within count * 2^-40 of the sum (a classwise conf can lie below 2^-8)
+ *     valid    int64 [R]: the images of the row whose keys are not INVALID
+ * Integer (LDS) atomics only and no floating-point sum: the same bits on every run, however the N images were cut into record calls.  Two
+ * launches, no scratch, no allocation, no synchronisation: capturable.
+ * BMI_ERR_INVALID (decided before any HIP call): a null pointer other than edges_in, a count below 1, N > N_cap, n_bins outside [1, 64], an
+ * edges_in entry that is not finite or is below its predecessor.  BMI_ERR_UNSUPPORTED: C > 128, R > 64, N >= 2^22.  An error writes nothing. */
+int bmi_classwise_table(const uint32_t* pkeys, const int32_t* labels_rec, int32_t R, int32_t C, int32_t N, int32_t N_cap, int32_t n_bins,
+                        const float* edges_in /* host [n_bins + 1] or NULL */, float* edges_out, int64_t* count, int64_t* hits,
+                        int64_t* conf_fix, int64_t* valid, bmi_stream stream);
+
 /* Rank quality of the per-image uncertainty scores: do the wrong predictions — or out-of-distribution inputs — carry the high uncertainty?
  * Per row the stable order of the images by a score key, the risk-coverage curve of selective prediction and the Mann-Whitney count of the
  * AUROC, as exact integers on the device (csrc/ranking.hip; train.ranking.score_keys_numpy / rank_quality_numpy restate both calls).  The
