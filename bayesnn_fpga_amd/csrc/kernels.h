@@ -229,6 +229,9 @@ int launch_reliability_record(const double* mean, int E, int B, int C, const int
 int launch_reliability_table(const uint32_t* keys, const uint8_t* hit, const double* nll, const double* brier, int R, int N, int N_cap, int n_bins,
                              const float* edges_in, float* edges_out, long long* count, long long* hits, long long* conf_fix, double* sums,
                              void* scratch, hipStream_t s);
+// the edges [L][n_bins + 1] of L lines of N_cap keys, by mass or the HOST edges_in copied to every line: one launch (reliability.hip), for
+// the top-label rows (L = R) and the classwise lines (L = R C) alike; the callers' takes have checked the shape
+int launch_line_edges(const uint32_t* keys, int L, int N, int N_cap, int n_bins, const float* edges_in, float* edges_out, hipStream_t s);
 // reliability_classwise.hip (bmi_classwise_record / bmi_classwise_table): the classwise records of a batch — pkeys uint32 [2 E][C][N_cap] (the
 // float32 confidence of EVERY class, INVALID = all ones) and labels_rec int32 [N_cap] — at columns n0.., and from columns 0 .. N-1 the per-
 // (row, class) table: edges [R][C][n_bins + 1], count / hits / conf_fix int64 [R][C][n_bins], valid int64 [R], all OVERWRITTEN; edges_in:
@@ -239,7 +242,6 @@ int launch_classwise_record(const double* mean, int E, int B, int C, const int* 
                             int* counters, hipStream_t s);
 int launch_classwise_table(const uint32_t* pkeys, const int* labels_rec, int R, int C, int N, int N_cap, int n_bins, const float* edges_in,
                            float* edges_out, long long* count, long long* hits, long long* conf_fix, long long* valid, hipStream_t s);
-#define RL_TILE 1024        // records a workgroup stages in LDS per step of an ordered walk (reliability.hip, reliability_kde.hip)
 // reliability_kde.hip (bmi_reliability_kde): from columns 0 .. N-1 of the records' keys and hit bits, per row the KDE-ECE on a G-point grid —
 // ece_kde, bw, sd [R], n_data, n_hit int64 [R], degenerate int32 [R], density [R][2][G] = pp1, pp2 (the density sums in between) —, all
 // OVERWRITTEN; three launches.  BMI_ERR_UNSUPPORTED (nothing launched) for what reliability_kde_takes refuses (R > 64, N >= 2^22, G outside

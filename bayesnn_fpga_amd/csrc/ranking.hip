@@ -40,15 +40,14 @@
 //                         workgroup's own images compares the indices as well; the tiles above it skip the two equal counts.  The
 //                         workgroup's m, n_pos and U2 partial go to the scratch (int64 [R][tiles][3]).
 //   rank_finish_kernel    one workgroup per row: the partials added up (integers, order-free), the tails m .. N-1 of sorted_keys and curve
-//                         filled, and aurc_sum added in position order by ONE wave from tiles of RL_TILE quotients the workgroup stages in
-//                         LDS (every lane adds the same values), as reliability_bins_kernel adds its two sums.
+//                         filled, and aurc_sum added in position order by record_common.h's ordered_sum<1> over the quotients.
 #include <cstdint>
 
-#include "kernels.h"
+#include "record_common.h"
 
 #pragma clang fp contract(off)
 
-#define RK_THREADS 256
+#define RK_THREADS RECORD_THREADS
 #define RK_IPT (BMI_RANK_TILE_I / RK_THREADS)
 #define RK_INVALID 0xFFFFFFFFu
 #define RK_MAX_KEY 0x7F7FFFFFu
@@ -194,7 +193,7 @@ __global__ __launch_bounds__(RK_THREADS) void rank_count_kernel(const uint32_t* 
 __global__ __launch_bounds__(RK_THREADS) void rank_finish_kernel(int N, size_t N_cap, int tiles, const long long* __restrict__ partial,
                                                                   uint32_t* __restrict__ sorted_keys, int* __restrict__ curve,
                                                                   long long* __restrict__ counts, double* __restrict__ aurc_sum) {
-    __shared__ double term[RL_TILE];
+    __shared__ double term[1][RL_TILE];
     __shared__ unsigned long long total[3];
     const int r = blockIdx.x, tid = threadIdx.x;
     uint32_t* sk = sorted_keys + (size_t)r * N_cap;
@@ -213,19 +212,10 @@ __global__ __launch_bounds__(RK_THREADS) void rank_finish_kernel(int N, size_t N
         sk[k] = RK_INVALID;
         cv[k] = n_pos;
     }
-    double acc = 0.0;                       // (wave 0's; every lane of it adds the same values)
-    for (int k0 = 0; k0 < m; k0 += RL_TILE) {
-        const int len = min(RL_TILE, m - k0);
-        for (int j = tid; j < len; j += RK_THREADS) term[j] = (double)cv[k0 + j] / (double)(k0 + j + 1);
-        __syncthreads();
-        if (tid < 64) {
-#pragma unroll 8
-            for (int j = 0; j < len; ++j) acc = acc + term[j];          // position order
-        }
-        __syncthreads();
-    }
+    double acc[1] = {0.0};                  // position order
+    ordered_sum<1>(m, term, acc, [&](int k, double (&t)[1]) { t[0] = (double)cv[k] / (double)(k + 1); });
     if (tid < 3) counts[(size_t)r * 3 + tid] = (long long)total[tid];
-    if (tid == 0) aurc_sum[r] = acc;
+    if (tid == 0) aurc_sum[r] = acc[0];
 }
 
 bool score_record_takes(int R, int B) { return R >= 1 && R <= BMI_RANK_MAX_ROWS && B >= 1 && B <= BMI_RANK_MAX_IMAGES; }

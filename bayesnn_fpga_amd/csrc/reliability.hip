@@ -24,31 +24,23 @@
 //          float64 nll_sum and brier_sum, each added in image order n = 0, 1, ... from 0.0.
 // Integer atomics only (LDS); every output is OVERWRITTEN; the same bits on every run, however the N images were cut into record calls.
 //
-//   reliability_records_kernel  one wave per image walks the exits and keeps the running exit sum; lane i owns classes i and i + 64.  The two
-//                               ascending sums are formed by every lane from the same broadcast values (v_readlane: the class index is
-//                               wave-uniform), the arg-max by a butterfly on (value, lower index).  Lane 0 writes the 2 E records of the
-//                               image at column n0 + b.
-//   reliability_edges_kernel    one workgroup per (row, edge): the order statistic by radix select over the uint32 keys, four passes of eight
-//                               bits, each a 256-bin LDS histogram (integer atomics) of the keys that match the digits chosen so far and a
-//                               one-wave scan for the digit that holds the rank.  Exact under any number of duplicate keys; no sort.
+// The shared pieces are record_common.h's: walk_exit_rows, class_sums, radix_select_u32, bin_of / conf_fix40, ordered_sum.
+//
+//   reliability_records_kernel  one wave per image walks its rows (walk_exit_rows); s and the Brier term are one pass of class_sums<2>, the
+//                               arg-max a butterfly on (value, lower index).  Lane 0 writes the 2 E records of the image at column n0 + b.
+//   line_edges_kernel           one workgroup per (edge, line of N_cap keys): the order statistic by radix_select_u32.  The lines are the R
+//                               rows here and the R C (row, class) lines of reliability_classwise.hip (launch_line_edges); a line is read
+//                               4 (n_bins - 1) times.
 //   reliability_partial_kernel  one workgroup per (chunk of RL_CHUNK images, row): the three integer bin sums of the chunk in LDS, written to
 //                               the scratch.
-//   reliability_bins_kernel     one workgroup per row: the chunks' integers added up (order-free); the two float64 sums added in image order
-//                               by ONE wave, from tiles of RL_TILE records the workgroup stages in LDS (every lane adds the same values).
+//   reliability_bins_kernel     one workgroup per row: the chunks' integers added up (order-free); the two float64 sums by ordered_sum<2>.
 #include <cmath>
 #include <cstdint>
 
-#include "kernels.h"
+#include "record_common.h"
 
-#define RL_THREADS 256
+#define RL_THREADS RECORD_THREADS
 #define RL_CHUNK 4096
-
-// lane `from`'s value in every lane; `from` is the same in every lane
-__device__ __forceinline__ double rl_broadcast(double v, int from) {
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), from), __builtin_amdgcn_readlane(__double2loint(v), from));
-}
-
-struct RlEdges { float v[BMI_REL_MAX_BINS + 1]; };
 
 __global__ __launch_bounds__(RL_THREADS) void reliability_records_kernel(const double* __restrict__ mean, int E, int B, int C,
                                                                          const int* __restrict__ labels, size_t n0, size_t N_cap,
@@ -72,124 +64,68 @@ __global__ __launch_bounds__(RL_THREADS) void reliability_records_kernel(const d
         return;
     }
     const int c0 = lane, c1 = lane + 64;
-    const bool in0 = c0 < C, in1 = c1 < C;
     const double t0 = c0 == y ? 1.0 : 0.0, t1 = c1 == y ? 1.0 : 0.0;
-    const int n_lo = min(C, 64);
-    double a0 = 0.0, a1 = 0.0;              // the running exit sum of the two owned classes
     int bad_rows = 0;
-    for (int e = 0; e < E; ++e) {
-        const double* row = mean + ((size_t)e * B + b) * C;
-        const double p0 = in0 ? row[c0] : 0.0, p1 = in1 ? row[c1] : 0.0;
-        a0 = a0 + p0;
-        a1 = a1 + p1;
-        const double div = (double)(e + 1);
-        for (int kind = 0; kind < 2; ++kind) {
-            const double v0 = kind ? a0 / div : p0, v1 = kind ? a1 / div : p1;
-            const bool bad = __ballot((in0 && !__builtin_isfinite(v0)) || (in1 && !__builtin_isfinite(v1))) != 0ull;
-            uint32_t key = 0u;
-            uint8_t h = 0;
-            double nl = 0.0, br = 0.0;
-            if (bad) {                      // (wave-uniform)
-                ++bad_rows;
-            } else {
-                // (a class beyond C: -1.0, below every clipped value)
-                const double pc0 = in0 ? (v0 < 1e-256 ? 1e-256 : v0) : -1.0, pc1 = in1 ? (v1 < 1e-256 ? 1e-256 : v1) : -1.0;
-                const double d0 = v0 - t0, d1 = v1 - t1;
-                const double q0 = d0 * d0, q1 = d1 * d1;
-                double s = 0.0;
-                for (int c = 0; c < n_lo; ++c) {           // ascending class order, the same values in every lane
-                    s = s + rl_broadcast(pc0, c);
-                    br = br + rl_broadcast(q0, c);
-                }
-                for (int c = 64; c < C; ++c) {
-                    s = s + rl_broadcast(pc1, c - 64);
-                    br = br + rl_broadcast(q1, c - 64);
-                }
-                double bv = pc0;
-                int bi = c0;
-                if (pc1 > bv) { bv = pc1; bi = c1; }
+    walk_exit_rows(mean, E, B, C, b, lane, [&](int r, bool bad, double v0, double v1, double pc0, double pc1) {
+        uint32_t key = 0u;
+        uint8_t h = 0;
+        double nl = 0.0, br = 0.0;
+        if (bad) {                          // (wave-uniform)
+            ++bad_rows;
+        } else {
+            const double d0 = v0 - t0, d1 = v1 - t1;
+            const double lo[2] = {pc0, d0 * d0}, hi[2] = {pc1, d1 * d1};
+            double sum[2];                  // s and the Brier term, in one pass over the classes
+            class_sums<2>(lo, hi, C, sum);
+            br = sum[1];
+            double bv = pc0;
+            int bi = c0;
+            if (pc1 > bv) { bv = pc1; bi = c1; }
 #pragma unroll
-                for (int k = 32; k >= 1; k >>= 1) {
-                    const double ov = __shfl_xor(bv, k);
-                    const int oi = __shfl_xor(bi, k);
-                    if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-                }
-                key = __float_as_uint((float)(bv / s));
-                h = bi == y;
-                nl = -log(__shfl(y < 64 ? pc0 : pc1, y & 63));
+            for (int k = 32; k >= 1; k >>= 1) {
+                const double ov = __shfl_xor(bv, k);
+                const int oi = __shfl_xor(bi, k);
+                if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
             }
-            if (lane == 0) {
-                const size_t at = (size_t)(kind * E + e) * N_cap + col;
-                keys[at] = key;
-                hit[at] = h;
-                nll[at] = nl;
-                brier[at] = br;
-            }
+            key = __float_as_uint((float)(bv / sum[0]));
+            h = bi == y;
+            nl = -log(__shfl(y < 64 ? pc0 : pc1, y & 63));
         }
-    }
+        if (lane == 0) {
+            const size_t at = (size_t)r * N_cap + col;
+            keys[at] = key;
+            hit[at] = h;
+            nll[at] = nl;
+            brier[at] = br;
+        }
+    });
     if (lane == 0 && counters && bad_rows) atomicAdd(counters, bad_rows);
 }
 
-// grid (n_bins, R): workgroup (i, r) writes edges[r][i + 1] for i < n_bins - 1; workgroup (n_bins - 1, r) writes edges[r][0] and [n_bins]
-__global__ __launch_bounds__(RL_THREADS) void reliability_edges_kernel(const uint32_t* __restrict__ keys, int N, size_t N_cap, int n_bins,
-                                                                       RlEdges fixed, int use_fixed, float* __restrict__ edges) {
+// grid (n_bins, L) by mass: workgroup (i, l) writes edges[l][i + 1] for i < n_bins - 1; workgroup (n_bins - 1, l) writes edges[l][0] and
+// [n_bins].  grid (1, L) with fixed edges: workgroup (0, l) copies them.  A selected INVALID key (all ones: classwise lines only) is the
+// edge 1.0f.
+__global__ __launch_bounds__(RL_THREADS) void line_edges_kernel(const uint32_t* __restrict__ keys, int N, size_t N_cap, int n_bins,
+                                                                BinEdges fixed, int use_fixed, float* __restrict__ edges) {
     __shared__ int hist[256];
-    __shared__ int chosen[2];               // the digit that holds the rank, the rank inside it
-    const int i = blockIdx.x, r = blockIdx.y, tid = threadIdx.x;
-    float* out = edges + (size_t)r * (n_bins + 1);
+    __shared__ int chosen[2];
+    const int i = blockIdx.x, tid = threadIdx.x;
+    const size_t l = blockIdx.y;
+    float* out = edges + l * (n_bins + 1);
+    if (use_fixed) {
+        if (tid <= n_bins) out[tid] = fixed.v[tid];
+        return;
+    }
     if (i == n_bins - 1) {
         if (tid == 0) {
-            out[0] = use_fixed ? fixed.v[0] : 0.f;
-            out[n_bins] = use_fixed ? fixed.v[n_bins] : 1.f;
+            out[0] = 0.f;
+            out[n_bins] = 1.f;
         }
         return;
     }
-    if (use_fixed) {
-        if (tid == 0) out[i + 1] = fixed.v[i + 1];
-        return;
-    }
-    const uint32_t* k = keys + (size_t)r * N_cap;
     const long long want = (long long)(i + 1) * (N / n_bins);
-    int rank = (int)(want < N - 1 ? want : N - 1);
-    uint32_t prefix = 0u, mask = 0u;
-    for (int shift = 24; shift >= 0; shift -= 8) {
-        hist[tid] = 0;
-        __syncthreads();
-        for (int n = tid; n < N; n += RL_THREADS) {
-            const uint32_t key = k[n];
-            if ((key & mask) == prefix) atomicAdd(&hist[(key >> shift) & 255u], 1);
-        }
-        __syncthreads();
-        if (tid < 64) {                     // lane l owns digits 4 l .. 4 l + 3; the keys that match the prefix number more than rank
-            const int h0 = hist[4 * tid], h1 = hist[4 * tid + 1], h2 = hist[4 * tid + 2], h3 = hist[4 * tid + 3];
-            const int tot = h0 + h1 + h2 + h3;
-            int incl = tot;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const int up = __shfl_up(incl, d);
-                if (tid >= d) incl += up;
-            }
-            const int excl = incl - tot;
-            if (excl <= rank && rank < incl) {       // exactly one lane
-                int digit = 4 * tid, left = rank - excl;
-                if (left >= h0) {
-                    left -= h0; ++digit;
-                    if (left >= h1) {
-                        left -= h1; ++digit;
-                        if (left >= h2) { left -= h2; ++digit; }
-                    }
-                }
-                chosen[0] = digit;
-                chosen[1] = left;
-            }
-        }
-        __syncthreads();
-        prefix |= (uint32_t)chosen[0] << shift;
-        mask |= 255u << shift;
-        rank = chosen[1];
-        __syncthreads();                    // (chosen and hist are rewritten by the next pass)
-    }
-    if (tid == 0) out[i + 1] = __uint_as_float(prefix);
+    const uint32_t key = radix_select_u32(keys + l * N_cap, N, (int)(want < N - 1 ? want : N - 1), hist, chosen);
+    if (tid == 0) out[i + 1] = key == 0xFFFFFFFFu ? 1.f : __uint_as_float(key);
 }
 
 // grid (chunks, R); part int64 [R][chunks][3][n_bins]: count, hits, conf_fix of the chunk's images
@@ -207,13 +143,11 @@ __global__ __launch_bounds__(RL_THREADS) void reliability_partial_kernel(const u
         const uint32_t key = keys[(size_t)r * N_cap + n];
         if (key == 0u) continue;
         const float conf = __uint_as_float(key);
-        if (!(conf > ed[0])) continue;
-        int j = 1;                          // the lowest edge conf does not exceed
-        while (j <= n_bins && conf > ed[j]) ++j;
-        if (j > n_bins) continue;
-        atomicAdd(&acc[0][j - 1], 1ull);
-        if (hit[(size_t)r * N_cap + n]) atomicAdd(&acc[1][j - 1], 1ull);
-        atomicAdd(&acc[2][j - 1], (unsigned long long)(long long)((double)conf * 1099511627776.0));
+        const int j = bin_of(conf, ed, n_bins, false);
+        if (j == n_bins) continue;
+        atomicAdd(&acc[0][j], 1ull);
+        if (hit[(size_t)r * N_cap + n]) atomicAdd(&acc[1][j], 1ull);
+        atomicAdd(&acc[2][j], conf_fix40(conf));
     }
     __syncthreads();
     if (tid < n_bins) {
@@ -245,26 +179,14 @@ __global__ __launch_bounds__(RL_THREADS) void reliability_bins_kernel(const doub
     }
     const double* nl = nll + (size_t)r * N_cap;
     const double* br = brier + (size_t)r * N_cap;
-    double s = 0.0, t = 0.0;                // (wave 0's; every lane of it adds the same values)
-    for (int n0 = 0; n0 < N; n0 += RL_TILE) {
-        const int len = min(RL_TILE, N - n0);
-        for (int j = tid; j < len; j += RL_THREADS) {
-            tile[0][j] = nl[n0 + j];
-            tile[1][j] = br[n0 + j];
-        }
-        __syncthreads();
-        if (tid < 64) {
-#pragma unroll 8
-            for (int j = 0; j < len; ++j) {  // image order
-                s = s + tile[0][j];
-                t = t + tile[1][j];
-            }
-        }
-        __syncthreads();
-    }
+    double sum[2] = {0.0, 0.0};             // image order
+    ordered_sum<2>(N, tile, sum, [&](int n, double (&t)[2]) {
+        t[0] = nl[n];
+        t[1] = br[n];
+    });
     if (tid == 0) {
-        sums[2 * r] = s;
-        sums[2 * r + 1] = t;
+        sums[2 * r] = sum[0];
+        sums[2 * r + 1] = sum[1];
     }
 }
 
@@ -291,18 +213,24 @@ int launch_reliability_record(const double* mean, int E, int B, int C, const int
     return BMI_OK;
 }
 
+int launch_line_edges(const uint32_t* keys, int L, int N, int N_cap, int n_bins, const float* edges_in, float* edges_out, hipStream_t s) {
+    BinEdges fixed = {};
+    if (edges_in)
+        for (int i = 0; i <= n_bins; ++i) fixed.v[i] = edges_in[i];
+    hipLaunchKernelGGL(line_edges_kernel, dim3(edges_in ? 1u : (unsigned)n_bins, (unsigned)L), dim3(RL_THREADS), 0, s, keys, N, (size_t)N_cap, n_bins,
+                       fixed, edges_in ? 1 : 0, edges_out);
+    BMI_CHECK_LAUNCH();
+    return BMI_OK;
+}
+
 int launch_reliability_table(const uint32_t* keys, const uint8_t* hit, const double* nll, const double* brier, int R, int N, int N_cap, int n_bins,
                              const float* edges_in, float* edges_out, long long* count, long long* hits, long long* conf_fix, double* sums,
                              void* scratch, hipStream_t s) {
     if (!reliability_table_takes(R, N, n_bins)) return BMI_ERR_UNSUPPORTED;
-    RlEdges fixed = {};
-    if (edges_in)
-        for (int i = 0; i <= n_bins; ++i) fixed.v[i] = edges_in[i];
     const int chunks = (N + RL_CHUNK - 1) / RL_CHUNK;
     long long* part = (long long*)scratch;
-    hipLaunchKernelGGL(reliability_edges_kernel, dim3((unsigned)n_bins, (unsigned)R), dim3(RL_THREADS), 0, s, keys, N, (size_t)N_cap, n_bins, fixed,
-                       edges_in ? 1 : 0, edges_out);
-    BMI_CHECK_LAUNCH();
+    const int rc = launch_line_edges(keys, R, N, N_cap, n_bins, edges_in, edges_out, s);
+    if (rc != BMI_OK) return rc;
     hipLaunchKernelGGL(reliability_partial_kernel, dim3((unsigned)chunks, (unsigned)R), dim3(RL_THREADS), 0, s, keys, hit, N, (size_t)N_cap, n_bins,
                        (const float*)edges_out, part);
     BMI_CHECK_LAUNCH();

@@ -35,31 +35,20 @@
 // Integer atomics only (LDS); no floating-point output but the edges; every output is OVERWRITTEN; the same bits on every run, however the
 // N images were cut into record calls.
 //
-//   classwise_records_kernel  one wave per image walks the exits and keeps the running exit sum; lane i owns classes i and i + 64.  The
-//                             ascending sum is formed by every lane from the same broadcast values (v_readlane: the class index is
-//                             wave-uniform), as reliability_records_kernel forms it.  Each lane writes the keys of its own classes for the
+// The shared pieces are record_common.h's: walk_exit_rows and class_sums (the very functions reliability_records_kernel runs: the same s,
+// the same key at the arg-max), radix_select_u32 (reliability.hip's line_edges_kernel, over the R C lines), bin_of / conf_fix40.
+//
+//   classwise_records_kernel  one wave per image walks its rows (walk_exit_rows).  Each lane writes the keys of its own classes for the
 //                             2 E rows at column n0 + b; lane 0 writes the label record.
-//   classwise_edges_kernel    one workgroup per (edge, line), line = (row, class): the order statistic by radix select over the uint32 keys,
-//                             four passes of eight bits, each a 256-bin LDS histogram (integer atomics) of the keys that match the digits
-//                             chosen so far and a one-wave scan for the digit that holds the rank.  Exact under any number of duplicate
-//                             keys; no sort.  A thread adds a run of equal digits with ONE atomic (near-zero probabilities share their top
-//                             digits: every lane would otherwise hit one address).  The simple form: a line is read 4 (n_bins - 1) times.
 //   classwise_bins_kernel     one workgroup per line: the three integer bin sums in LDS (a thread adds a run of pairs of one bin at once),
 //                             written straight to the outputs — no scratch —; the workgroups of class 0 count the row's valid images.
 #include <cmath>
 #include <cstdint>
 
-#include "kernels.h"
+#include "record_common.h"
 
-#define CW_THREADS 256
+#define CW_THREADS RECORD_THREADS
 #define CW_INVALID 0xFFFFFFFFu
-
-// lane `from`'s value in every lane; `from` is the same in every lane
-__device__ __forceinline__ double cw_broadcast(double v, int from) {
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), from), __builtin_amdgcn_readlane(__double2loint(v), from));
-}
-
-struct CwEdges { float v[BMI_REL_MAX_BINS + 1]; };
 
 __global__ __launch_bounds__(CW_THREADS) void classwise_records_kernel(const double* __restrict__ mean, int E, int B, int C,
                                                                        const int* __restrict__ labels, size_t n0, size_t N_cap,
@@ -87,112 +76,26 @@ __global__ __launch_bounds__(CW_THREADS) void classwise_records_kernel(const dou
         }
         return;
     }
-    const int n_lo = min(C, 64);
-    double a0 = 0.0, a1 = 0.0;              // the running exit sum of the two owned classes
     int bad_rows = 0;
-    for (int e = 0; e < E; ++e) {
-        const double* row = mean + ((size_t)e * B + b) * C;
-        const double p0 = in0 ? row[c0] : 0.0, p1 = in1 ? row[c1] : 0.0;
-        a0 = a0 + p0;
-        a1 = a1 + p1;
-        const double div = (double)(e + 1);
-        for (int kind = 0; kind < 2; ++kind) {
-            const double v0 = kind ? a0 / div : p0, v1 = kind ? a1 / div : p1;
-            const bool bad = __ballot((in0 && !__builtin_isfinite(v0)) || (in1 && !__builtin_isfinite(v1))) != 0ull;
-            uint32_t key0 = CW_INVALID, key1 = CW_INVALID;
-            if (bad) {                      // (wave-uniform)
-                ++bad_rows;
-            } else {
-                const double pc0 = v0 < 1e-256 ? 1e-256 : v0, pc1 = v1 < 1e-256 ? 1e-256 : v1;       // (a class beyond C: never read)
-                double s = 0.0;
-                for (int c = 0; c < n_lo; ++c) s = s + cw_broadcast(pc0, c);           // ascending class order, the same values in every lane
-                for (int c = 64; c < C; ++c) s = s + cw_broadcast(pc1, c - 64);
-                const double q0 = pc0 / s, q1 = pc1 / s;
-                key0 = q0 < 0x1p-126 ? 0u : __float_as_uint((float)q0);
-                key1 = q1 < 0x1p-126 ? 0u : __float_as_uint((float)q1);
-            }
-            const size_t at = (size_t)(kind * E + e) * plane;
-            if (in0) k0[at] = key0;
-            if (in1) k1[at] = key1;
+    walk_exit_rows(mean, E, B, C, b, lane, [&](int r, bool bad, double, double, double pc0, double pc1) {
+        uint32_t key0 = CW_INVALID, key1 = CW_INVALID;
+        if (bad) {                          // (wave-uniform)
+            ++bad_rows;
+        } else {                            // (the pc of a class beyond C is never read)
+            const double lo[1] = {pc0}, hi[1] = {pc1};
+            double s[1];
+            class_sums<1>(lo, hi, C, s);
+            const double q0 = pc0 / s[0], q1 = pc1 / s[0];
+            key0 = q0 < 0x1p-126 ? 0u : __float_as_uint((float)q0);
+            key1 = q1 < 0x1p-126 ? 0u : __float_as_uint((float)q1);
         }
-    }
+        if (in0) k0[r * plane] = key0;
+        if (in1) k1[r * plane] = key1;
+    });
     if (lane == 0) {
         labels_rec[col] = y;
         if (counters && bad_rows) atomicAdd(counters, bad_rows);
     }
-}
-
-// grid (n_bins, L) by mass: workgroup (i, l) writes edges[l][i + 1] for i < n_bins - 1; workgroup (n_bins - 1, l) writes edges[l][0] and
-// [n_bins].  grid (1, L) with fixed edges: workgroup (0, l) copies them.
-__global__ __launch_bounds__(CW_THREADS) void classwise_edges_kernel(const uint32_t* __restrict__ pkeys, int N, size_t N_cap, int n_bins,
-                                                                     CwEdges fixed, int use_fixed, float* __restrict__ edges) {
-    __shared__ int hist[256];
-    __shared__ int chosen[2];               // the digit that holds the rank, the rank inside it
-    const int i = blockIdx.x, tid = threadIdx.x;
-    const size_t l = blockIdx.y;
-    float* out = edges + l * (n_bins + 1);
-    if (use_fixed) {
-        if (tid <= n_bins) out[tid] = fixed.v[tid];
-        return;
-    }
-    if (i == n_bins - 1) {
-        if (tid == 0) {
-            out[0] = 0.f;
-            out[n_bins] = 1.f;
-        }
-        return;
-    }
-    const uint32_t* k = pkeys + l * N_cap;
-    const long long want = (long long)(i + 1) * (N / n_bins);
-    int rank = (int)(want < N - 1 ? want : N - 1);
-    uint32_t prefix = 0u, mask = 0u;
-    for (int shift = 24; shift >= 0; shift -= 8) {
-        hist[tid] = 0;
-        __syncthreads();
-        int cur = -1, run = 0;              // the thread's run of equal digits, added at once
-        for (int n = tid; n < N; n += CW_THREADS) {
-            const uint32_t key = k[n];
-            if ((key & mask) != prefix) continue;
-            const int d = (int)((key >> shift) & 255u);
-            if (d != cur) {
-                if (run) atomicAdd(&hist[cur], run);
-                cur = d;
-                run = 0;
-            }
-            ++run;
-        }
-        if (run) atomicAdd(&hist[cur], run);
-        __syncthreads();
-        if (tid < 64) {                     // lane l owns digits 4 l .. 4 l + 3; the keys that match the prefix number more than rank
-            const int h0 = hist[4 * tid], h1 = hist[4 * tid + 1], h2 = hist[4 * tid + 2], h3 = hist[4 * tid + 3];
-            const int tot = h0 + h1 + h2 + h3;
-            int incl = tot;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const int up = __shfl_up(incl, d);
-                if (tid >= d) incl += up;
-            }
-            const int excl = incl - tot;
-            if (excl <= rank && rank < incl) {       // exactly one lane
-                int digit = 4 * tid, left = rank - excl;
-                if (left >= h0) {
-                    left -= h0; ++digit;
-                    if (left >= h1) {
-                        left -= h1; ++digit;
-                        if (left >= h2) { left -= h2; ++digit; }
-                    }
-                }
-                chosen[0] = digit;
-                chosen[1] = left;
-            }
-        }
-        __syncthreads();
-        prefix |= (uint32_t)chosen[0] << shift;
-        mask |= 255u << shift;
-        rank = chosen[1];
-        __syncthreads();                    // (chosen and hist are rewritten by the next pass)
-    }
-    if (tid == 0) out[i + 1] = prefix == CW_INVALID ? 1.f : __uint_as_float(prefix);
 }
 
 // grid (L): workgroup l = r * C + c writes count / hits / conf_fix [l][n_bins]; the workgroups of class 0 write valid[r]
@@ -217,22 +120,20 @@ __global__ __launch_bounds__(CW_THREADS) void classwise_bins_kernel(const uint32
         if (key == CW_INVALID) continue;
         ++seen;
         const float conf = __uint_as_float(key);
-        if (!(conf >= ed[0])) continue;
-        int j = 1;                          // the lowest edge conf does not exceed
-        while (j <= n_bins && conf > ed[j]) ++j;
-        if (j > n_bins) continue;
-        if (j - 1 != cur) {
+        const int j = bin_of(conf, ed, n_bins, true);
+        if (j == n_bins) continue;
+        if (j != cur) {
             if (a) {
                 atomicAdd(&acc[0][cur], a);
                 atomicAdd(&acc[1][cur], h);
                 atomicAdd(&acc[2][cur], f);
             }
-            cur = j - 1;
+            cur = j;
             a = h = f = 0ull;
         }
         ++a;
         h += labels_rec[n] == c ? 1ull : 0ull;
-        f += (unsigned long long)(long long)((double)conf * 1099511627776.0);
+        f += conf_fix40(conf);
     }
     if (a) {
         atomicAdd(&acc[0][cur], a);
@@ -267,13 +168,9 @@ int launch_classwise_record(const double* mean, int E, int B, int C, const int* 
 int launch_classwise_table(const uint32_t* pkeys, const int* labels_rec, int R, int C, int N, int N_cap, int n_bins, const float* edges_in,
                            float* edges_out, long long* count, long long* hits, long long* conf_fix, long long* valid, hipStream_t s) {
     if (!classwise_table_takes(R, C, N, n_bins)) return BMI_ERR_UNSUPPORTED;
-    CwEdges fixed = {};
-    if (edges_in)
-        for (int i = 0; i <= n_bins; ++i) fixed.v[i] = edges_in[i];
     const unsigned L = (unsigned)(R * C);   // at most 64 * 128 lines
-    hipLaunchKernelGGL(classwise_edges_kernel, dim3(edges_in ? 1u : (unsigned)n_bins, L), dim3(CW_THREADS), 0, s, pkeys, N, (size_t)N_cap, n_bins,
-                       fixed, edges_in ? 1 : 0, edges_out);
-    BMI_CHECK_LAUNCH();
+    const int rc = launch_line_edges(pkeys, (int)L, N, N_cap, n_bins, edges_in, edges_out, s);
+    if (rc != BMI_OK) return rc;
     hipLaunchKernelGGL(classwise_bins_kernel, dim3(L), dim3(CW_THREADS), 0, s, pkeys, labels_rec, C, N, (size_t)N_cap, n_bins,
                        (const float*)edges_out, count, hits, conf_fix, valid);
     BMI_CHECK_LAUNCH();

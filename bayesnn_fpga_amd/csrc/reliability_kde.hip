@@ -29,9 +29,8 @@
 //            every quotient above finite.
 // No floating-point atomics; every output is OVERWRITTEN; the same bits on every run, however the N images were cut into record calls.
 //
-//   reliability_kde_moments_kernel    one workgroup per row: tiles of RL_TILE terms staged in LDS by every thread (the hit datum's d, then its
-//                                     squared deviation; +0.0 for every other record), added in image order by ONE wave (every lane adds the
-//                                     same values); n and n1 are integer counts (LDS integer atomics).
+//   reliability_kde_moments_kernel    one workgroup per row: two ordered sums (record_common.h's ordered_sum<1>) of the hit datum's d, then of
+//                                     its squared deviation, +0.0 for every other record; n and n1 are integer counts (LDS integer atomics).
 //   reliability_kde_density_kernel    grid (ceil(G / 256), R), one thread per grid point: walks the images in order from LDS tiles.  A centre
 //                                     is skipped when the lowest x is at least h above it or the highest x at least h below it: x, the
 //                                     difference and the quotient are monotone, so then |u| >= 1 at every point between and every term is
@@ -44,11 +43,11 @@
 #include <cmath>
 #include <cstdint>
 
-#include "kernels.h"
+#include "record_common.h"
 
 #pragma clang fp contract(off)
 
-#define RK_THREADS 256
+#define RK_THREADS RECORD_THREADS
 #define RK_ITILE (4 * RK_THREADS)
 
 __device__ __forceinline__ double rk_grid(int i, double step) { return (double)i * step + (-0.6); }
@@ -57,7 +56,7 @@ __global__ __launch_bounds__(RK_THREADS) void reliability_kde_moments_kernel(con
                                                                              int N, size_t N_cap, double bw_scale, long long* __restrict__ n_data,
                                                                              long long* __restrict__ n_hit, double* __restrict__ sd_out,
                                                                              double* __restrict__ bw_out) {
-    __shared__ double term[RL_TILE];        // per record what the ordered sum receives: +0.0 (the identity on these sums) from all but the hit data
+    __shared__ double term[1][RL_TILE];     // per record what the ordered sum receives: +0.0 (the identity on these sums) from all but the hit data
     __shared__ int count[2];                // n, n1 (integers: counted by every thread, in no order)
     __shared__ double mean;
     const int r = blockIdx.x, tid = threadIdx.x;
@@ -65,45 +64,29 @@ __global__ __launch_bounds__(RK_THREADS) void reliability_kde_moments_kernel(con
     const uint8_t* ht = hit + (size_t)r * N_cap;
     if (tid < 2) count[tid] = 0;
     int c0 = 0, c1 = 0;
-    double s = 0.0, q = 0.0, mu = 0.0;      // (s and q: wave 0's; every lane of it adds the same values)
+    double s[1] = {0.0}, q[1] = {0.0};      // (wave 0's), both in image order
     __syncthreads();
-    for (int pass = 0; pass < 2; ++pass) {
-        for (int n0 = 0; n0 < N; n0 += RL_TILE) {
-            const int len = min(RL_TILE, N - n0);
-            for (int j = tid; j < len; j += RK_THREADS) {
-                const uint32_t key = k[n0 + j];
-                const double d = (double)__uint_as_float(key);
-                const bool datum = key != 0u, hit_datum = datum && ht[n0 + j];
-                if (pass == 0) {
-                    c0 += datum;
-                    c1 += hit_datum;
-                    term[j] = hit_datum ? d : 0.0;
-                } else {
-                    const double e = d - mu;
-                    term[j] = hit_datum ? e * e : 0.0;
-                }
-            }
-            __syncthreads();
-            if (tid < 64) {
-                double acc = pass == 0 ? s : q;
-#pragma unroll 8
-                for (int j = 0; j < len; ++j) acc = acc + term[j];      // image order
-                if (pass == 0) s = acc; else q = acc;
-            }
-            __syncthreads();
-        }
-        if (pass == 0) {
-            if (c0) atomicAdd(&count[0], c0);
-            if (c1) atomicAdd(&count[1], c1);
-            __syncthreads();
-            if (tid == 0) mean = count[1] ? s / (double)count[1] : 0.0;
-            __syncthreads();
-            mu = mean;
-        }
-    }
+    ordered_sum<1>(N, term, s, [&](int n, double (&t)[1]) {
+        const uint32_t key = k[n];
+        const bool datum = key != 0u, hit_datum = datum && ht[n];
+        c0 += datum;
+        c1 += hit_datum;
+        t[0] = hit_datum ? (double)__uint_as_float(key) : 0.0;
+    });
+    if (c0) atomicAdd(&count[0], c0);
+    if (c1) atomicAdd(&count[1], c1);
+    __syncthreads();
+    if (tid == 0) mean = count[1] ? s[0] / (double)count[1] : 0.0;
+    __syncthreads();
+    const double mu = mean;
+    ordered_sum<1>(N, term, q, [&](int n, double (&t)[1]) {
+        const uint32_t key = k[n];
+        const double e = (double)__uint_as_float(key) - mu;
+        t[0] = key != 0u && ht[n] ? e * e : 0.0;
+    });
     if (tid == 0) {
         const int n1 = count[1];
-        const double sd = n1 ? sqrt(q / (double)n1) : 0.0;
+        const double sd = n1 ? sqrt(q[0] / (double)n1) : 0.0;
         n_data[r] = count[0];
         n_hit[r] = n1;
         sd_out[r] = sd;

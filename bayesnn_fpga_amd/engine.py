@@ -1497,9 +1497,69 @@ class MCDEngine(CompiledGraph):
         R, cap = 2 * int(self.n_exits if n_exits is None else n_exits), int(capacity)
         if R < 2 or cap < 1:
             raise ValueError("new_reliability_records needs n_exits >= 1 and capacity >= 1")
-        return dict(keys=torch.zeros(R, cap, dtype=torch.int32, device=self.device), hit=torch.zeros(R, cap, dtype=torch.uint8, device=self.device),
-                    nll=torch.zeros(R, cap, dtype=torch.float64, device=self.device), brier=torch.zeros(R, cap, dtype=torch.float64, device=self.device),
-                    counters=torch.zeros(2, dtype=torch.int32, device=self.device))
+        return self._reliability_record_dict(R, cap)
+
+    def _reliability_record_dict(self, R, cap):
+        z = lambda *shape, dtype: torch.zeros(*shape, dtype=dtype, device=self.device)
+        return dict(keys=z(R, cap, dtype=torch.int32), hit=z(R, cap, dtype=torch.uint8), nll=z(R, cap, dtype=torch.float64),
+                    brier=z(R, cap, dtype=torch.float64), counters=z(2, dtype=torch.int32))
+
+    # what the record and table calls of the read-outs check alike, the messages as their callers had them
+    def _mean_labels(self, mean, labels):
+        """(E, B, C, labels int32 [B] on the device) of a record call over ``mean`` [E, B, C]"""
+        E, B, Cd = check_buffer(mean, (None,) * 3, torch.float64, self.device, "mean [E, B, C]").shape
+        labels = check_buffer(labels.to(device=self.device, dtype=torch.int32).contiguous(), (B,), torch.int32, self.device, "labels [B]")
+        return E, B, Cd, labels
+
+    def _record_fit(self, R, cap, E, B, offset, Cr=None, Cd=None):
+        """The offset of a record call whose batch fits records of R rows (and Cr classes, against the mean's Cd) and capacity ``cap``"""
+        offset = int(offset)
+        if R != 2 * E:
+            raise ValueError(f"records hold {R} rows, mean has {E} exits (2 * E rows)")
+        if Cr != Cd:
+            raise ValueError(f"records hold {Cr} classes, mean has {Cd}")
+        return self._check_fits(offset, B, cap)
+
+    @staticmethod
+    def _check_fits(offset, B, cap, empty_ok=True):
+        offset = int(offset)
+        if (B < 1 and not empty_ok) or offset < 0 or offset + B > cap:
+            raise ValueError(f"images {offset} .. {offset + B - 1} do not fit the records' capacity {cap}")
+        return offset
+
+    @staticmethod
+    def _check_n(n, cap, what="the records' capacity"):
+        n = int(n)
+        if not 1 <= n <= cap:
+            raise ValueError(f"n = {n} outside [1, {cap}] ({what})")
+        return n
+
+    @staticmethod
+    def _bin_edges(binning, n_bins, edges=None, allowed=("mass", "width")):
+        """(n_bins, the host edges float32 [n_bins + 1] as a ctypes array, or None by mass) of a table call"""
+        if binning not in allowed:
+            raise ValueError("binning must be " + ", ".join(repr(b) for b in allowed[:-1]) + f" or {allowed[-1]!r}, got {binning!r}")
+        fixed = None
+        if binning == "edges":
+            if edges is None:
+                raise ValueError("binning 'edges' needs edges [n_bins + 1]")
+            fixed = np.asarray(edges.detach().cpu() if torch.is_tensor(edges) else edges, dtype=np.float32).reshape(-1)
+            n_bins = fixed.shape[0] - 1
+            if n_bins >= 1 and (not np.isfinite(fixed).all() or (np.diff(fixed) < 0).any()):
+                raise ValueError("edges must be finite and non-decreasing")
+        n_bins = int(n_bins)
+        if not 1 <= n_bins <= _lib.REL_MAX_BINS:
+            raise ValueError(f"n_bins must be in [1, {_lib.REL_MAX_BINS}]")
+        if binning == "width":
+            fixed = np.arange(n_bins + 1, dtype=np.float32) / np.float32(n_bins)
+        return n_bins, None if fixed is None else (C.c_float * (n_bins + 1))(*[float(v) for v in fixed])
+
+    def _raise_counters(self, records, noun):
+        nonfinite, badlabel = (int(v) for v in records["counters"].tolist())
+        if nonfinite:
+            raise FloatingPointError(f"{nonfinite} {noun} records with a non-finite probability on the {self.dtype!r} engine")
+        if badlabel:
+            raise ValueError(f"{badlabel} images with a label outside [0, C) in the {noun} records")
 
     def _check_records(self, records):
         R, cap = check_buffer(records["keys"], (None, None), torch.int32, self.device, "records['keys'] [R, capacity]").shape
@@ -1516,14 +1576,9 @@ class MCDEngine(CompiledGraph):
         as its bit pattern, whether it hits the label, -log p_label and the Brier term.  A non-finite row or a label outside [0, C) leaves
         zeros and counts in ``records['counters']``.  One launch, no synchronisation; returns ``offset + B``.
         ``train.reliability.reliability_numpy`` is the host restatement."""
-        E, B, Cd = check_buffer(mean, (None,) * 3, torch.float64, self.device, "mean [E, B, C]").shape
-        labels = check_buffer(labels.to(device=self.device, dtype=torch.int32).contiguous(), (B,), torch.int32, self.device, "labels [B]")
+        E, B, Cd, labels = self._mean_labels(mean, labels)
         R, cap = self._check_records(records)
-        offset = int(offset)
-        if R != 2 * E:
-            raise ValueError(f"records hold {R} rows, mean has {E} exits (2 * E rows)")
-        if offset < 0 or offset + B > cap:
-            raise ValueError(f"images {offset} .. {offset + B - 1} do not fit the records' capacity {cap}")
+        offset = self._record_fit(R, cap, E, B, offset)
         with torch.cuda.device(self.device):
             rc = self.lib.bmi_reliability_record(mean.data_ptr(), E, B, Cd, labels.data_ptr(), offset, cap, records["keys"].data_ptr(),
                                                  records["hit"].data_ptr(), records["nll"].data_ptr(), records["brier"].data_ptr(),
@@ -1541,14 +1596,8 @@ class MCDEngine(CompiledGraph):
         ``check`` (a host read: synchronises; pass False under a graph capture): FloatingPointError if a record was non-finite,
         ValueError if a label was outside [0, C)."""
         R, cap = self._check_records(records)
-        n, n_bins = int(n), int(n_bins)
-        if not 1 <= n <= cap:
-            raise ValueError(f"n = {n} outside [1, {cap}] (the records' capacity)")
-        if binning not in ("mass", "width"):
-            raise ValueError(f"binning must be 'mass' or 'width', got {binning!r}")
-        if not 1 <= n_bins <= _lib.REL_MAX_BINS:
-            raise ValueError(f"n_bins must be in [1, {_lib.REL_MAX_BINS}]")
-        edges_in = None if binning == "mass" else (C.c_float * (n_bins + 1))(*[float(np.float32(i) / np.float32(n_bins)) for i in range(n_bins + 1)])
+        n = self._check_n(n, cap)
+        n_bins, edges_in = self._bin_edges(binning, n_bins)
         edges = torch.empty(R, n_bins + 1, dtype=torch.float32, device=self.device)
         ints = torch.empty(3, R, n_bins, dtype=torch.int64, device=self.device)
         sums = torch.empty(R, 2, dtype=torch.float64, device=self.device)
@@ -1560,11 +1609,7 @@ class MCDEngine(CompiledGraph):
                                                 self._stream())
         _lib.check(rc, "bmi_reliability_table")
         if check:
-            nonfinite, badlabel = (int(v) for v in records["counters"].tolist())
-            if nonfinite:
-                raise FloatingPointError(f"{nonfinite} reliability records with a non-finite probability on the {self.dtype!r} engine")
-            if badlabel:
-                raise ValueError(f"{badlabel} images with a label outside [0, C) in the reliability records")
+            self._raise_counters(records, "reliability")
         return dict(edges=edges, count=ints[0], hits=ints[1], conf_fix=ints[2], sums=sums, nll_sum=sums[:, 0], brier_sum=sums[:, 1], n=n)
 
     def reliability_kde(self, records, n, grid_points=2 ** 14, order=1, bw_scale=None, check=True):
@@ -1579,9 +1624,7 @@ class MCDEngine(CompiledGraph):
         ``reliability_records`` calls; ``train.reliability.reliability_kde_numpy`` is the host restatement.
         ``check`` (a host read: synchronises; pass False under a graph capture): ValueError naming the degenerate rows."""
         R, cap = self._check_records(records)
-        n, G, order = int(n), int(grid_points), int(order)
-        if not 1 <= n <= cap:
-            raise ValueError(f"n = {n} outside [1, {cap}] (the records' capacity)")
+        n, G, order = self._check_n(n, cap), int(grid_points), int(order)
         if not _lib.KDE_MIN_GRID <= G <= _lib.KDE_MAX_GRID:
             raise ValueError(f"grid_points must be in [{_lib.KDE_MIN_GRID}, {_lib.KDE_MAX_GRID}]")
         if order not in (1, 2):
@@ -1634,16 +1677,9 @@ class MCDEngine(CompiledGraph):
         the arg-max class the key ``reliability_records`` writes —, and the image's label.  A non-finite row or a label outside [0, C)
         leaves INVALID keys (a bad label: the label record -1) and counts in ``records['counters']``.  4 * R * C bytes per image.
         One launch, no synchronisation; returns ``offset + B``.  ``train.reliability.classwise_numpy`` is the host restatement."""
-        E, B, Cd = check_buffer(mean, (None,) * 3, torch.float64, self.device, "mean [E, B, C]").shape
-        labels = check_buffer(labels.to(device=self.device, dtype=torch.int32).contiguous(), (B,), torch.int32, self.device, "labels [B]")
+        E, B, Cd, labels = self._mean_labels(mean, labels)
         R, Cr, cap = self._check_classwise_records(records)
-        offset = int(offset)
-        if R != 2 * E:
-            raise ValueError(f"records hold {R} rows, mean has {E} exits (2 * E rows)")
-        if Cr != Cd:
-            raise ValueError(f"records hold {Cr} classes, mean has {Cd}")
-        if offset < 0 or offset + B > cap:
-            raise ValueError(f"images {offset} .. {offset + B - 1} do not fit the records' capacity {cap}")
+        offset = self._record_fit(R, cap, E, B, offset, Cr, Cd)
         with torch.cuda.device(self.device):
             rc = self.lib.bmi_classwise_record(mean.data_ptr(), E, B, Cd, labels.data_ptr(), offset, cap, records["pkeys"].data_ptr(),
                                                records["labels"].data_ptr(), records["counters"].data_ptr(), self._stream())
@@ -1662,25 +1698,8 @@ class MCDEngine(CompiledGraph):
         ``check`` (a host read: synchronises; pass False under a graph capture): FloatingPointError if a record was non-finite,
         ValueError if a label was outside [0, C)."""
         R, Cd, cap = self._check_classwise_records(records)
-        n = int(n)
-        if not 1 <= n <= cap:
-            raise ValueError(f"n = {n} outside [1, {cap}] (the records' capacity)")
-        if binning not in ("mass", "width", "edges"):
-            raise ValueError(f"binning must be 'mass', 'width' or 'edges', got {binning!r}")
-        if binning == "edges":
-            if edges is None:
-                raise ValueError("binning 'edges' needs edges [n_bins + 1]")
-            fixed = np.asarray(edges.detach().cpu() if torch.is_tensor(edges) else edges, dtype=np.float32).reshape(-1)
-            n_bins = fixed.shape[0] - 1
-            if n_bins >= 1 and (not np.isfinite(fixed).all() or (np.diff(fixed) < 0).any()):
-                raise ValueError("edges must be finite and non-decreasing")
-        else:
-            n_bins = int(n_bins)
-        if not 1 <= n_bins <= _lib.REL_MAX_BINS:
-            raise ValueError(f"n_bins must be in [1, {_lib.REL_MAX_BINS}]")
-        if binning == "width":
-            fixed = np.arange(n_bins + 1, dtype=np.float32) / np.float32(n_bins)
-        edges_in = None if binning == "mass" else (C.c_float * (n_bins + 1))(*[float(v) for v in fixed])
+        n = self._check_n(n, cap)
+        n_bins, edges_in = self._bin_edges(binning, n_bins, edges, ("mass", "width", "edges"))
         out_edges = torch.empty(R, Cd, n_bins + 1, dtype=torch.float32, device=self.device)
         ints = torch.empty(3, R, Cd, n_bins, dtype=torch.int64, device=self.device)
         valid = torch.empty(R, dtype=torch.int64, device=self.device)
@@ -1690,11 +1709,7 @@ class MCDEngine(CompiledGraph):
                                               self._stream())
         _lib.check(rc, "bmi_classwise_table")
         if check:
-            nonfinite, badlabel = (int(v) for v in records["counters"].tolist())
-            if nonfinite:
-                raise FloatingPointError(f"{nonfinite} classwise records with a non-finite probability on the {self.dtype!r} engine")
-            if badlabel:
-                raise ValueError(f"{badlabel} images with a label outside [0, C) in the classwise records")
+            self._raise_counters(records, "classwise")
         return dict(edges=out_edges, count=ints[0], hits=ints[1], conf_fix=ints[2], valid=valid, n=n)
 
     # ---- rank quality of the uncertainty scores (bmi_score_record / bmi_rank_quality) ---------------------------------------------
@@ -1718,11 +1733,10 @@ class MCDEngine(CompiledGraph):
         R, B = check_buffer(score, (None, None), torch.float64, self.device, "score [R, B]").shape
         cap = check_buffer(records["ukeys"], (R, None), torch.int32, self.device, "records['ukeys'] [R, capacity]").shape[1]
         check_buffer(records["counter"], (1,), torch.int32, self.device, "records['counter'] [1]")
-        offset, direction = int(offset), int(direction)
+        direction = int(direction)
         if direction not in (1, -1):
             raise ValueError(f"direction must be +1 (an uncertainty) or -1 (a confidence), got {direction}")
-        if B < 1 or offset < 0 or offset + B > cap:
-            raise ValueError(f"images {offset} .. {offset + B - 1} do not fit the records' capacity {cap}")
+        offset = self._check_fits(offset, B, cap, empty_ok=False)
         if not (R <= _lib.RANK_MAX_ROWS and B <= _lib.RANK_MAX_IMAGES):
             raise ValueError(f"score_records takes at most {_lib.RANK_MAX_ROWS} rows and {_lib.RANK_MAX_IMAGES} images per call")
         if valid is not None:
@@ -1745,9 +1759,7 @@ class MCDEngine(CompiledGraph):
         into ``score_records`` calls.  ``train.ranking.rank_metrics`` derives AUROC, AURC and E-AURC; ``rank_quality_numpy`` restates it."""
         R, cap = check_buffer(ukeys, (None, None), torch.int32, self.device, "ukeys [R, capacity]").shape
         check_buffer(positive, (R, cap), torch.uint8, self.device, "positive [R, capacity]")
-        n = int(n)
-        if not 1 <= n <= cap:
-            raise ValueError(f"n = {n} outside [1, {cap}] (the capacity)")
+        n = self._check_n(n, cap, "the capacity")
         if n > _lib.RANK_MAX_IMAGES or R > _lib.RANK_MAX_ROWS:
             raise ValueError(f"rank_quality takes at most {_lib.RANK_MAX_IMAGES} images and {_lib.RANK_MAX_ROWS} rows (n = {n}, R = {R})")
         ints = torch.zeros(3, R, cap, dtype=torch.int32, device=self.device)
@@ -1782,11 +1794,10 @@ class MCDEngine(CompiledGraph):
         S1 = S[0] if S.dim() == 4 else S
         E, B, Cd = check_buffer(S1, (None,) * 3, torch.float64, self.device, "S1 [E, B, C]").shape
         cap = check_buffer(records["stat"], (2, E, None), torch.float64, self.device, "records['stat'] [2, E, capacity]").shape[2]
-        offset, t_count = int(offset), int(t_count)
+        t_count = int(t_count)
         if t_count < 1:
             raise ValueError(f"t_count must be >= 1, got {t_count}")
-        if B < 1 or offset < 0 or offset + B > cap:
-            raise ValueError(f"images {offset} .. {offset + B - 1} do not fit the records' capacity {cap}")
+        offset = self._check_fits(offset, B, cap, empty_ok=False)
         if E > 32 or Cd > 128:
             raise ValueError(f"exit_stat_records takes at most 32 exits and 128 classes (E = {E}, C = {Cd})")
         w = self._ens_w_dev if E == self.n_exits else None
@@ -1817,9 +1828,7 @@ class MCDEngine(CompiledGraph):
         if not torch.is_tensor(thresholds):
             thresholds = torch.as_tensor(np.asarray(thresholds, dtype=np.float64).reshape(-1))
         thr = check_buffer(thresholds.to(device=self.device, dtype=torch.float64).contiguous(), (None,), torch.float64, self.device, "thresholds [G]")
-        G, n, first_exit, kind = thr.shape[0], int(n), int(first_exit), int(bool(ensemble))
-        if not 1 <= n <= cap:
-            raise ValueError(f"n = {n} outside [1, {cap}] (the records' capacity)")
+        G, n, first_exit, kind = thr.shape[0], self._check_n(n, cap), int(first_exit), int(bool(ensemble))
         if not 0 <= first_exit < E:
             raise ValueError(f"first_exit must be in [0, {E})")
         if not 1 <= G <= _lib.POLICY_MAX_THRESHOLDS:
@@ -1831,11 +1840,7 @@ class MCDEngine(CompiledGraph):
         ints = torch.empty(2, G, E, dtype=torch.int64, device=self.device)
         invalid = torch.empty(G, dtype=torch.int64, device=self.device)
         ex = torch.zeros(G, cap, dtype=torch.uint8, device=self.device) if exit_of else None
-        sel = None
-        if select:
-            sel = dict(keys=torch.zeros(G, cap, dtype=torch.int32, device=self.device), hit=torch.zeros(G, cap, dtype=torch.uint8, device=self.device),
-                       nll=torch.zeros(G, cap, dtype=torch.float64, device=self.device), brier=torch.zeros(G, cap, dtype=torch.float64, device=self.device),
-                       counters=torch.zeros(2, dtype=torch.int32, device=self.device))
+        sel = self._reliability_record_dict(G, cap) if select else None
         rec = reliability_records
         scratch = self._scratch("_nll_scratch", max(1, int(self.lib.bmi_exit_policy_scratch_bytes(E, n, G))))
         with torch.cuda.device(self.device):

@@ -22,12 +22,15 @@ def width_edges(n_bins):
     return (np.arange(n_bins + 1, dtype=np.float32) / np.float32(n_bins)).astype(np.float32)
 
 
-def reliability_numpy(mean, labels, n_bins=15, binning="mass"):
-    """The host restatement of bmi_reliability_record + bmi_reliability_table: ``mean`` float64 [E, N, C] (T-mean probabilities), ``labels``
-    int [N].  Rows r = kind * E + e: the exits (kind 0), then the exit ensembles (p_0 + ... + p_e) / (e + 1), added in exit order and divided
-    once.  Returns dict(keys uint32, hit uint8, nll, brier float64 [R, N] — the records —, edges float32 [R, n_bins + 1], count, hits,
-    conf_fix int64 [R, n_bins], nll_sum, brier_sum float64 [R], nonfinite, badlabel, n).  Every sum is an explicit ascending loop: over
-    the classes for a row's probability sum and Brier term, over the images for the two float64 sums."""
+INVALID = np.uint32(0xFFFFFFFF)   # a classwise key of a (row, image) that is not data (ranking.hip's convention)
+FLUSH = 2.0 ** -126               # a quotient below the least normal float32 is confidence zero
+
+
+def _record_rows(mean, labels, binnings, binning):
+    """What both restatements do before they differ.  Checks the arguments; returns ((E, N, C), y int64 [N], labelled bool [N], rows): ``rows``
+    yields per row r = kind * E + e the tuple (valid bool [N] — labelled and every v_c finite —, the labelled images with a non-finite
+    v_c, v [N, C] — 1.0, a finite placeholder whose results are dropped, where not valid —, pc = max(v, 1e-256), s [N] = the class sum
+    as an explicit ascending loop)."""
     mean = np.asarray(mean, dtype=np.float64)
     if mean.ndim != 3:
         raise ValueError("mean must be [E, N, C]")
@@ -35,33 +38,64 @@ def reliability_numpy(mean, labels, n_bins=15, binning="mass"):
     y = np.asarray(labels).astype(np.int64).reshape(-1)
     if y.shape[0] != N:
         raise ValueError("labels must be [N]")
-    if binning not in ("mass", "width"):
-        raise ValueError(f"binning must be 'mass' or 'width', got {binning!r}")
-    R, n_bins = 2 * E, int(n_bins)
+    if binning not in binnings:
+        raise ValueError("binning must be " + ", ".join(repr(b) for b in binnings[:-1]) + f" or {binnings[-1]!r}, got {binning!r}")
     labelled = (y >= 0) & (y < Cd)
+
+    def rows():
+        acc = np.zeros((N, Cd), dtype=np.float64)
+        with np.errstate(invalid="ignore", over="ignore"):
+            per_exit = []
+            for e in range(E):
+                acc = acc + mean[e]
+                per_exit.append(acc / float(e + 1))
+        for v in list(mean) + per_exit:
+            finite = np.isfinite(v).all(axis=1)
+            valid = labelled & finite
+            v = np.where(valid[:, None], v, 1.0)
+            pc = np.maximum(v, 1e-256)
+            s = np.zeros(N, dtype=np.float64)
+            for c in range(Cd):                              # ascending class order
+                s = s + pc[:, c]
+            yield valid, int((labelled & ~finite).sum()), v, pc, s
+    return (E, N, Cd), y, labelled, rows()
+
+
+def _mass_edges(line, n_bins):
+    """float32 [n_bins + 1]: the equal-mass edges of one line of N uint32 keys — 0, the order statistics of rank min((i + 1) * per, N - 1),
+    per = N // n_bins, in unsigned key order (the float order of the confidences; INVALID keys last, a selected one is the edge 1.0), 1."""
+    N = line.shape[0]
+    per = N // n_bins
+    srt = np.sort(line)
+    out = np.empty(n_bins + 1, dtype=np.float32)
+    out[0] = 0.0
+    for i in range(n_bins):
+        k = srt[min((i + 1) * per, N - 1)]
+        out[i + 1] = 1.0 if k == INVALID else k.view(np.float32)
+    out[n_bins] = 1.0
+    return out
+
+
+def reliability_numpy(mean, labels, n_bins=15, binning="mass"):
+    """The host restatement of bmi_reliability_record + bmi_reliability_table: ``mean`` float64 [E, N, C] (T-mean probabilities), ``labels``
+    int [N].  Rows r = kind * E + e: the exits (kind 0), then the exit ensembles (p_0 + ... + p_e) / (e + 1), added in exit order and divided
+    once.  Returns dict(keys uint32, hit uint8, nll, brier float64 [R, N] — the records —, edges float32 [R, n_bins + 1], count, hits,
+    conf_fix int64 [R, n_bins], nll_sum, brier_sum float64 [R], nonfinite, badlabel, n).  Every sum is an explicit ascending loop: over
+    the classes for a row's probability sum and Brier term, over the images for the two float64 sums."""
+    (E, N, _), y, labelled, rows = _record_rows(mean, labels, ("mass", "width"), binning)
+    n_bins = int(n_bins)
+    R = 2 * E
     yy = np.where(labelled, y, 0)
-    rows = [None] * R
-    acc = np.zeros((N, Cd), dtype=np.float64)
-    with np.errstate(invalid="ignore", over="ignore"):
-        for e in range(E):
-            acc = acc + mean[e]
-            rows[e], rows[E + e] = mean[e], acc / float(e + 1)
     keys = np.zeros((R, N), dtype=np.uint32)
     hit = np.zeros((R, N), dtype=np.uint8)
     nll = np.zeros((R, N), dtype=np.float64)
     brier = np.zeros((R, N), dtype=np.float64)
     nonfinite = 0
     idx = np.arange(N)
-    for r, v in enumerate(rows):
-        finite = np.isfinite(v).all(axis=1)
-        valid = labelled & finite
-        nonfinite += int((labelled & ~finite).sum())
-        v = np.where(valid[:, None], v, 1.0)                 # (invalid images: a finite placeholder whose results are dropped)
-        pc = np.maximum(v, 1e-256)
-        s = np.zeros(N, dtype=np.float64)
+    for r, (valid, bad, v, pc, s) in enumerate(rows):
+        nonfinite += bad
         b = np.zeros(N, dtype=np.float64)
-        for c in range(Cd):                                  # ascending class order
-            s = s + pc[:, c]
+        for c in range(v.shape[1]):                          # ascending class order
             d = v[:, c] - (yy == c)
             b = b + d * d
         pred = pc.argmax(axis=1)                             # numpy's argmax: the lowest index on ties
@@ -71,16 +105,8 @@ def reliability_numpy(mean, labels, n_bins=15, binning="mass"):
         nll[r] = np.where(valid, -np.log(pc[idx, yy]), 0.0)
         brier[r] = np.where(valid, b, 0.0)
     edges = np.empty((R, n_bins + 1), dtype=np.float32)
-    if binning == "mass":
-        per = N // n_bins
-        for r in range(R):
-            srt = np.sort(keys[r]).view(np.float32)          # (the unsigned order of the keys is the float order)
-            edges[r, 0] = 0.0
-            for i in range(n_bins):
-                edges[r, i + 1] = srt[min((i + 1) * per, N - 1)]
-            edges[r, n_bins] = 1.0
-    else:
-        edges[:] = width_edges(n_bins)
+    for r in range(R):
+        edges[r] = _mass_edges(keys[r], n_bins) if binning == "mass" else width_edges(n_bins)
     count = np.zeros((R, n_bins), dtype=np.int64)
     hits = np.zeros((R, n_bins), dtype=np.int64)
     conf_fix = np.zeros((R, n_bins), dtype=np.int64)
@@ -123,10 +149,6 @@ def table_metrics(table, n=None):
                 brier=_np(table["brier_sum"]).astype(np.float64) / n)
 
 
-INVALID = np.uint32(0xFFFFFFFF)   # a classwise key of a (row, image) that is not data (ranking.hip's convention)
-FLUSH = 2.0 ** -126               # a quotient below the least normal float32 is confidence zero
-
-
 def classwise_numpy(mean, labels, n_bins=15, binning="width", edges=None):
     """The host restatement of bmi_classwise_record + bmi_classwise_table (the header comment of csrc/reliability_classwise.hip): ``mean``
     float64 [E, N, C], ``labels`` int [N]; rows r = kind * E + e as in ``reliability_numpy``.  Per (row, image): pc = max(v, 1e-256), s the
@@ -138,15 +160,7 @@ def classwise_numpy(mean, labels, n_bins=15, binning="width", edges=None):
     (-1 for a bad label), edges float32 [R, C, n_bins + 1], count, hits, conf_fix int64 [R, C, n_bins] (conf_fix = sum of the TRUNCATED
     (int64) (conf * 2^40)), valid int64 [R], nonfinite, badlabel, n).  4 R C bytes per image on the device.  The class sum is an explicit
     ascending loop; the rest loops over rows and bins and is vectorised over classes and images (integer sums: order-free)."""
-    mean = np.asarray(mean, dtype=np.float64)
-    if mean.ndim != 3:
-        raise ValueError("mean must be [E, N, C]")
-    E, N, Cd = mean.shape
-    y = np.asarray(labels).astype(np.int64).reshape(-1)
-    if y.shape[0] != N:
-        raise ValueError("labels must be [N]")
-    if binning not in ("mass", "width", "edges"):
-        raise ValueError(f"binning must be 'mass', 'width' or 'edges', got {binning!r}")
+    (E, N, Cd), y, labelled, rows = _record_rows(mean, labels, ("mass", "width", "edges"), binning)
     if binning == "edges":
         if edges is None:
             raise ValueError("binning 'edges' needs edges [n_bins + 1]")
@@ -158,43 +172,20 @@ def classwise_numpy(mean, labels, n_bins=15, binning="width", edges=None):
         n_bins = int(n_bins)
         fixed = width_edges(n_bins) if binning == "width" else None
     R = 2 * E
-    labelled = (y >= 0) & (y < Cd)
-    rows = [None] * R
-    acc = np.zeros((N, Cd), dtype=np.float64)
-    with np.errstate(invalid="ignore", over="ignore"):
-        for e in range(E):
-            acc = acc + mean[e]
-            rows[e], rows[E + e] = mean[e], acc / float(e + 1)
     pkeys = np.empty((R, Cd, N), dtype=np.uint32)
     valid = np.zeros(R, dtype=np.int64)
     nonfinite = 0
-    for r, v in enumerate(rows):
-        finite = np.isfinite(v).all(axis=1)
-        ok = labelled & finite
-        nonfinite += int((labelled & ~finite).sum())
+    for r, (ok, bad, _, pc, s) in enumerate(rows):
+        nonfinite += bad
         valid[r] = int(ok.sum())
-        v = np.where(ok[:, None], v, 1.0)                    # (invalid images: a finite placeholder whose results are dropped)
-        pc = np.maximum(v, 1e-256)
-        s = np.zeros(N, dtype=np.float64)
-        for c in range(Cd):                                  # ascending class order
-            s = s + pc[:, c]
         for c in range(Cd):
             q = pc[:, c] / s
             conf = np.where(q < FLUSH, 0.0, q).astype(np.float32)
             pkeys[r, c] = np.where(ok, conf.view(np.uint32), INVALID)
     out_edges = np.empty((R, Cd, n_bins + 1), dtype=np.float32)
-    if fixed is None:
-        per = N // n_bins
-        for r in range(R):
-            for c in range(Cd):
-                srt = np.sort(pkeys[r, c])                   # unsigned order: INVALID keys last
-                out_edges[r, c, 0] = 0.0
-                for i in range(n_bins):
-                    k = srt[min((i + 1) * per, N - 1)]
-                    out_edges[r, c, i + 1] = 1.0 if k == INVALID else k.view(np.float32)
-                out_edges[r, c, n_bins] = 1.0
-    else:
-        out_edges[:] = fixed
+    for r in range(R):
+        for c in range(Cd):
+            out_edges[r, c] = _mass_edges(pkeys[r, c], n_bins) if fixed is None else fixed
     count = np.zeros((R, Cd, n_bins), dtype=np.int64)
     hits = np.zeros((R, Cd, n_bins), dtype=np.int64)
     conf_fix = np.zeros((R, Cd, n_bins), dtype=np.int64)

@@ -20,9 +20,10 @@ def test_reliability_kernels_have_no_scratch_and_no_spills():
     assert r.returncode == 0, r.stderr[-2000:]
     # (the remarks of one kernel come in this order: name, ..., ScratchSize, Occupancy, SGPRs Spill, VGPRs Spill)
     kernels = re.findall(r"Function Name: (\S+).*?ScratchSize \[bytes/lane\]: (\d+).*?VGPRs Spill: (\d+)", r.stderr, flags=re.S)
-    # the per-image records kernel, the per-(row, edge) radix select, the per-(chunk, row) integer bins and the per-row finish
+    # the per-image records kernel, the per-(line, edge) radix select (shared with the classwise table: line_edges_kernel), the
+    # per-(chunk, row) integer bins and the per-row finish
     assert len(kernels) == 4, len(kernels)
-    names = ("records", "edges", "partial", "bins")
-    assert sorted(next((k for k in names if f"reliability_{k}_kernel" in n), n) for n, _, _ in kernels) == sorted(names)
+    names = ("reliability_records", "line_edges", "reliability_partial", "reliability_bins")
+    assert sorted(next((k for k in names if f"{k}_kernel" in n), n) for n, _, _ in kernels) == sorted(names)
     bad = [(n, sc, sp) for n, sc, sp in kernels if int(sc) or int(sp)]
     assert not bad, f"kernels with scratch / VGPR spills: {bad}"
