@@ -49,6 +49,17 @@ class Site(C.Structure):
                 ("masks", C.c_void_p)]
 
 
+class HeadEx(C.Structure):
+    """bmi_head_ex: one exit head of bmi_head_fused_ex (unit parity tests)."""
+    _fields_ = [("in_", C.c_void_p), ("in_is_f32", C.c_int32), ("in_mod", C.c_int32), ("hw", C.c_int32), ("k", C.c_int32),
+                ("weight_pad", C.c_void_p), ("bias", C.c_void_p), ("out_dim", C.c_int32), ("site", C.POINTER(Site)),
+                ("site_logits", C.POINTER(Site)), ("batch", C.c_int32), ("t0", C.c_int32), ("tc", C.c_int32), ("seed", C.c_uint64),
+                ("mask_cnt0", C.c_int32), ("S1", C.c_void_p), ("S2", C.c_void_p), ("SL", C.c_void_p), ("SH", C.c_void_p),
+                ("image_map", C.c_void_p), ("n_mapped", C.c_int32), ("image_offset", C.c_int32), ("logits", C.c_void_p),
+                ("logits_tstride", C.c_size_t), ("scratch", C.c_void_p), ("inv_tau", C.c_float), ("vec_scale", C.c_void_p),
+                ("vec_bias", C.c_void_p), ("mat", C.c_void_p), ("mat_bias", C.c_void_p)]
+
+
 class TensorDesc(C.Structure):
     _fields_ = [("h", C.c_int32), ("w", C.c_int32), ("c", C.c_int32)]
 
@@ -188,6 +199,7 @@ _PROTOS = {
     "bmi_head_fused": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
                                  C.POINTER(Site), C.POINTER(Site), C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_int32,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bmi_head_fused_ex": (C.c_int, [C.POINTER(HeadEx), C.c_int32, C.c_void_p]),
     "bmi_dense_f32": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 5 +
                       [C.POINTER(Site), C.c_int32, C.c_int32, C.c_uint64, C.c_int32, C.c_void_p]),
 }

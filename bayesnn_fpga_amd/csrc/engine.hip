@@ -2630,4 +2630,34 @@ int bmi_head_fused(const void* in, int32_t in_is_f32, int32_t in_mod, int32_t hw
     return launch_head_fused(a, (hipStream_t)stream);
 }
 
+// every field of HeadArgs from the caller's struct, as make_head_args fills it (b0 for the logits site, b0 * K as the feature site's offset)
+int bmi_head_fused_ex(const bmi_head_ex* heads, int32_t n_heads, bmi_stream stream) {
+    if (!heads || n_heads < 1 || n_heads > BMI_HEAD_PACK_MAX) return BMI_ERR_INVALID;
+    HeadArgs list[BMI_HEAD_PACK_MAX];
+    for (int i = 0; i < n_heads; ++i) {
+        const bmi_head_ex& h = heads[i];
+        if ((h.site && !site_ok(*h.site)) || (h.site_logits && !site_ok(*h.site_logits))) return BMI_ERR_INVALID;
+        if (h.image_offset < 0 || h.k < 0 || (h.image_map && h.n_mapped <= 0)) return BMI_ERR_INVALID;
+        if (h.logits && (h.batch <= 0 || h.out_dim <= 0 || h.logits_tstride < (size_t)h.batch * (size_t)h.out_dim)) return BMI_ERR_INVALID;   // rows would overlap
+        const uint64_t soff = (uint64_t)h.image_offset * (uint64_t)h.k;
+        if (h.site && (h.site->kind == BMI_SITE_ELEMENTWISE || h.site->kind == BMI_SITE_CHANNEL) && soff % 64 != 0) return BMI_ERR_UNSUPPORTED;
+        HeadArgs& a = list[i];
+        std::memset(&a, 0, sizeof(a));
+        a.in = h.in;
+        a.in_kind = h.in_is_f32 ? 1 : (unit_pair() ? 2 + unit_pair() : (opt_unit_dtype() == BMI_DTYPE_BF16 ? 2 : 0));
+        a.in_mod = h.in_mod; a.HW = h.hw; a.K = h.k; a.B = h.batch; a.t0 = h.t0; a.tc = h.tc;
+        a.w = h.weight_pad; a.bias = h.bias; a.C = h.out_dim;
+        a.imap = h.image_map; a.Bc = h.image_map ? h.n_mapped : 0;
+        a.site = resolve_site(h.site, h.seed, h.mask_cnt0, soff);
+        a.site_logits = resolve_site(h.site_logits, h.seed, h.mask_cnt0);
+        a.b0 = h.image_offset;
+        a.S1 = h.S1; a.S2 = h.S2; a.SL = h.SL; a.SH = h.SH;
+        a.logits = h.logits; a.logits_tstride = h.logits_tstride;
+        a.part = h.scratch;
+        a.inv_tau = h.inv_tau;
+        a.vec_scale = h.vec_scale; a.vec_bias = h.vec_bias; a.mat = h.mat; a.mat_bias = h.mat_bias;
+    }
+    return n_heads == 1 ? launch_head_fused(list[0], (hipStream_t)stream) : launch_head_fused_multi(list, n_heads, (hipStream_t)stream);
+}
+
 }  // extern "C"

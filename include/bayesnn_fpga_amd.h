@@ -1139,6 +1139,49 @@ int bmi_head_fused(const void* in, int32_t in_is_f32, int32_t in_mod, int32_t hw
                    const float* bias, int32_t out_dim, const bmi_site* site, const bmi_site* site_logits, int32_t batch, int32_t t0,
                    int32_t tc, uint64_t seed, int32_t mask_cnt0, double* S1, double* S2, double* SL, bmi_stream stream);
 
+/* One exit head with everything the fused kernel's launchers take (csrc/kernels.h, HeadArgs), and packs of them: bmi_head_fused reaches the
+ * plain form only.  Fields as bmi_head_fused's arguments, then:
+ *   SH              [batch] float64 accumulator of the per-sample softmax entropies in nats, or NULL (S1 / S2 / SL all NULL with `logits`
+ *                   given: logits only, no accumulator is touched)
+ *   image_map       device int32 [n_mapped]: the launch covers these images only (any order, no repeats), or NULL: all `batch` images
+ *   image_offset    batch index of this launch's image 0 in the sites' index space (bmi_forward_mcd_images): the logits site adds it to the
+ *                   image index, a stochastic feature site gets the element offset image_offset * k, which must be a multiple of 64
+ *                   (BMI_ERR_UNSUPPORTED otherwise, bmi_image_offset_ok's rule)
+ *   logits          per-sample raw logits out, sample tl of the launch, class c of image b -> logits[tl * logits_tstride + b * out_dim + c]
+ *                   (float32; logits_tstride in elements, >= batch * out_dim: BMI_ERR_INVALID otherwise), or NULL
+ *   scratch         float64 [ceil(tc / 32)][3][batch][out_dim], plus [ceil(tc / 32)][batch] behind it when SH is given: the partial sums
+ *                   of a launch with tc > 32, joined in group order (bit-reproducible); NULL: hardware float64 atomics for tc > 32.  Every
+ *                   head of a pack needs its own.
+ *   inv_tau         float32(1 / tau) of temperature scaling, or 0: off
+ *   vec_scale / vec_bias     device float32 [out_dim] of vector scaling (both or neither), or NULL
+ *   mat / mat_bias  device float32 [out_dim][out_dim] (row = output class) and [out_dim] of matrix scaling (both or neither), or NULL
+ * At most one of inv_tau, vec_*, mat* (BMI_ERR_INVALID).  S1 / S2 / SH are those of the mapped logits z, SL and `logits` stay raw. */
+typedef struct bmi_head_ex {
+    const void* in;
+    int32_t in_is_f32, in_mod, hw, k;
+    const float* weight_pad;
+    const float* bias;
+    int32_t out_dim;
+    const bmi_site* site;
+    const bmi_site* site_logits;
+    int32_t batch, t0, tc;
+    uint64_t seed;
+    int32_t mask_cnt0;
+    double *S1, *S2, *SL, *SH;
+    const int32_t* image_map;
+    int32_t n_mapped, image_offset;
+    float* logits;
+    size_t logits_tstride;
+    double* scratch;
+    float inv_tau;
+    const float *vec_scale, *vec_bias, *mat, *mat_bias;
+} bmi_head_ex;
+
+/* n_heads == 1: one launch of heads[0].  2 <= n_heads <= 8: the heads in ONE launch (the engine's pack, csrc/head_fused_body.h); they must
+ * agree in out_dim, input kind, batch, tc and in which of S1 / SH / scratch / the calibration maps they carry, and none may have an
+ * image_map (BMI_ERR_UNSUPPORTED; the engine launches such heads one by one).  Returns the launcher's code; nothing is written on an error. */
+int bmi_head_fused_ex(const bmi_head_ex* heads, int32_t n_heads, bmi_stream stream);
+
 /* Hidden dense layer in fp32 (BMI_OP_DENSE): out[n][c] = relu?(in[n % in_mod] . weight[c] + bias[c]) (site on the
  * [batch, cout] tensor, sample index n / batch + t0).  `in` is fp16 (in_is_f32 = 0) or fp32 [.][k]; weight fp32 [cout][k];
  * k % 32 == 0, cout % 64 == 0.  Replaces the Dense 512 layers of the VGG-11 classifier stack
