@@ -12,8 +12,10 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libbayesnn_fpga_amd.so")
-SOURCES = ["conv_igemm.hip", "conv_igemm_wide.hip", "conv3x3_patch.hip", "conv3x3_pw.hip", "conv3x3_s2.hip", "conv1x1_stream.hip", "conv1x1_seam.hip", "conv_exact.hip", "conv_split.hip", "misc_kernels.hip", "dense_f32.hip", "head_fused.hip", "head_fused_temp.hip", "head_fused_vec.hip", "head_fused_mat.hip", "calibration.hip", "ensemble.hip", "pass_accuracy.hip", "reliability.hip", "reliability_kde.hip", "reliability_classwise.hip", "ranking.hip", "exit_policy.hip", "votes.hip", "votes_rows.hip", "engine.hip"]
+SOURCES = ["conv_igemm.hip", "conv_igemm_wide.hip", "conv3x3_patch.hip", "conv3x3_pw.hip", "conv3x3_s2.hip", "conv1x1_stream.hip", "conv1x1_seam.hip", "conv_exact.hip", "conv_split.hip", "misc_kernels.hip", "dense_f32.hip", "head_fused.hip", "head_fused_temp.hip", "head_fused_vec.hip", "head_fused_mat.hip", "calibration.hip", "ensemble.hip", "pass_accuracy.hip", "reliability.hip", "reliability_kde.hip", "reliability_classwise.hip", "ranking.hip", "ranking_sort.hip", "exit_policy.hip", "votes.hip", "votes_rows.hip", "engine.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
+# per source, on top of FLAGS: new sources are compiled without the packed fp32 instructions (v_pk_*_f32); the earlier ones keep their code
+EXTRA_FLAGS = {"ranking_sort.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _hipcc():
@@ -39,7 +41,7 @@ def _headers():
 def _want(src, hdr_sha):
     """Content key of one object: its source, every header, the flags (NOT mtimes: a snapshot copied to the GPU box, or a checkout, gives
     every file a fresh timestamp in arbitrary order, and an object that was not recompiled could look newer than its edited source)."""
-    return _sha([os.path.join(CSRC, src)], hdr_sha + " ".join(FLAGS))
+    return _sha([os.path.join(CSRC, src)], hdr_sha + " ".join(FLAGS + EXTRA_FLAGS.get(src, [])))
 
 
 def _read(path):
@@ -82,7 +84,7 @@ def build(force=False, verbose=False):
         key = _want(src, hdr_sha)
         if not force and os.path.exists(obj) and _read(obj + ".sha256") == key:
             return obj, key
-        cmd = [hipcc, *FLAGS, "-c", path, "-o", obj]
+        cmd = [hipcc, *FLAGS, *EXTRA_FLAGS.get(src, []), "-c", path, "-o", obj]
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError(f"hipcc failed on {src}:\n{r.stderr}")

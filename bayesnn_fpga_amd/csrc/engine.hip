@@ -2389,6 +2389,29 @@ int bmi_rank_quality(const uint32_t* ukeys, const uint8_t* positive, int32_t R, 
     return launch_rank_quality(ukeys, positive, R, N, N_cap, rank, sorted_keys, curve, (long long*)counts, aurc_sum, scratch, (hipStream_t)stream);
 }
 
+size_t bmi_rank_sort_scratch_bytes(int32_t R, int32_t N) { return rank_sort_scratch_bytes(R, N); }
+
+int bmi_rank_quality_sorted(const uint32_t* ukeys, const uint8_t* positive, int32_t R, int32_t N, int32_t N_cap, int32_t* rank,
+                            uint32_t* sorted_keys, int32_t* curve, int64_t* counts, double* aurc_sum, void* scratch, size_t scratch_bytes,
+                            bmi_stream stream) {
+    if (!ukeys || !positive || !rank || !sorted_keys || !curve || !counts || !aurc_sum || !scratch || R < 1 || N < 1 || N > N_cap)
+        return BMI_ERR_INVALID;
+    if (!rank_sort_takes(R, N)) return BMI_ERR_UNSUPPORTED;
+    if (scratch_bytes < bmi_rank_sort_scratch_bytes(R, N)) return BMI_ERR_NOMEM;
+    return launch_rank_quality_sorted(ukeys, positive, R, N, N_cap, rank, sorted_keys, curve, (long long*)counts, aurc_sum, scratch,
+                                      (hipStream_t)stream);
+}
+
+int bmi_rank_detection(const uint32_t* sorted_keys, const int32_t* curve, const int64_t* counts, int32_t R, int32_t N, int32_t N_cap,
+                       const double* tpr, int32_t L, double* ap_sum, int64_t* det, bmi_stream stream) {
+    if (!sorted_keys || !curve || !counts || !tpr || !ap_sum || !det || R < 1 || N < 1 || N > N_cap || L < 1 || L > BMI_RANK_DET_MAX_LEVELS)
+        return BMI_ERR_INVALID;
+    for (int l = 0; l < L; ++l)
+        if (!(tpr[l] > 0.0 && tpr[l] <= 1.0)) return BMI_ERR_INVALID;
+    if (!rank_detection_takes(R, N, L)) return BMI_ERR_UNSUPPORTED;
+    return launch_rank_detection(sorted_keys, curve, (const long long*)counts, R, N, N_cap, tpr, L, ap_sum, (long long*)det, (hipStream_t)stream);
+}
+
 int bmi_exit_stat_record(const double* S1, int32_t E, int32_t B, int32_t C, int32_t t_count, int32_t criterion, const double* weights, int32_t n0,
                          int32_t N_cap, double* stat, bmi_stream stream) {
     if (!S1 || !stat || E < 1 || B < 1 || C < 1 || t_count < 1 || N_cap < 1 || n0 < 0 || (int64_t)n0 + B > N_cap ||

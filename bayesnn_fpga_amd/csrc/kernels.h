@@ -260,6 +260,17 @@ int launch_score_record(const double* score, int R, int B, int direction, const 
                         int* counter, hipStream_t s);
 int launch_rank_quality(const uint32_t* ukeys, const uint8_t* positive, int R, int N, int N_cap, int* rank, uint32_t* sorted_keys, int* curve,
                         long long* counts, double* aurc_sum, void* scratch, hipStream_t s);
+// ranking_sort.hip (bmi_rank_quality_sorted / bmi_rank_detection): launch_rank_quality's arguments and outputs by a stable LSD radix sort,
+// for N <= BMI_RANK_SORT_MAX_IMAGES; 17 launches; scratch: int32 [R][256][ceil(N / BMI_RANK_SORT_TILE)] and four uint32 [R][N].  And
+// from the sorted_keys, curve and counts of either rank call and L HOST levels tpr: ap_sum [R][2] and det int64 [R][L][2], OVERWRITTEN;
+// one launch.  BMI_ERR_UNSUPPORTED (nothing launched) for what the two takes refuse
+bool rank_sort_takes(int R, int N);
+bool rank_detection_takes(int R, int N, int L);
+size_t rank_sort_scratch_bytes(int R, int N);
+int launch_rank_quality_sorted(const uint32_t* ukeys, const uint8_t* positive, int R, int N, int N_cap, int* rank, uint32_t* sorted_keys,
+                               int* curve, long long* counts, double* aurc_sum, void* scratch, hipStream_t s);
+int launch_rank_detection(const uint32_t* sorted_keys, const int* curve, const long long* counts, int R, int N, int N_cap, const double* tpr,
+                          int L, double* ap_sum, long long* det, hipStream_t s);
 // exit_policy.hip (bmi_exit_stat_record / bmi_exit_policy_sweep): the decision statistics stat [2][E][N_cap] of a batch at columns n0..
 // (exit_rule_stat of exit_rule.h per (ens, exit, image); weights: device [E][E] or null; one launch), and from columns 0 .. N-1 of one
 // [E][N_cap] plane of them, G device thresholds and the outcome rows the per-threshold count / hits int64 [G][E] and invalid int64 [G],

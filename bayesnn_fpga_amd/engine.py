@@ -1747,7 +1747,7 @@ class MCDEngine(CompiledGraph):
         _lib.check(rc, "bmi_score_record")
         return offset + B
 
-    def rank_quality(self, ukeys, positive, n):
+    def rank_quality(self, ukeys, positive, n, method="auto"):
         """The rank quality of the first ``n`` images of ``ukeys`` int32 [R, capacity] (``score_records``) against ``positive`` uint8
         [R, capacity] — 1 where the image is what the score should flag: a wrong prediction, a noise image — on the device
         (bmi_rank_quality).  The valid images of a row (key not INVALID), m of them, stand in the stable ascending key order, most certain
@@ -1755,23 +1755,57 @@ class MCDEngine(CompiledGraph):
         image), ``sorted_keys`` int32 [R, capacity] (position k: the key of the image ranked k, all ones from m on), ``curve`` int32
         [R, capacity] (position k: the positives at positions 0 .. k, n_pos from m on) — columns beyond ``n`` are zero —, ``counts`` int64
         [R, 3] = (m, n_pos, U2) with AUROC = U2 / (2 n_pos n_neg), ``aurc_sum`` float64 [R] = sum_k curve[k] / (k + 1) in position order —
-        and ``n``.  Exact integers, O(n^2) compare steps per row and no sort; the same bits on every run and for every cut of the images
-        into ``score_records`` calls.  ``train.ranking.rank_metrics`` derives AUROC, AURC and E-AURC; ``rank_quality_numpy`` restates it."""
+        and ``n``.  Exact integers; the same bits on every run, for every cut of the images into ``score_records`` calls and for either
+        ``method``: "count" (bmi_rank_quality) ranks by O(n^2) compare steps per row without a sort, up to ``RANK_MAX_IMAGES`` = 2^17
+        images; "sort" (bmi_rank_quality_sorted) by a stable radix sort, up to ``RANK_SORT_MAX_IMAGES`` = 2^22 - 1, with 16 n + 1024
+        ceil(n / 4096) scratch bytes per row; "auto" counts up to 2^17 images and sorts above.  ``train.ranking.rank_metrics`` derives
+        AUROC, AURC and E-AURC, ``rank_detection`` the detection figures; ``rank_quality_numpy`` restates it."""
         R, cap = check_buffer(ukeys, (None, None), torch.int32, self.device, "ukeys [R, capacity]").shape
         check_buffer(positive, (R, cap), torch.uint8, self.device, "positive [R, capacity]")
         n = self._check_n(n, cap, "the capacity")
-        if n > _lib.RANK_MAX_IMAGES or R > _lib.RANK_MAX_ROWS:
-            raise ValueError(f"rank_quality takes at most {_lib.RANK_MAX_IMAGES} images and {_lib.RANK_MAX_ROWS} rows (n = {n}, R = {R})")
+        if method not in ("auto", "count", "sort"):
+            raise ValueError(f"method must be 'auto', 'count' or 'sort', got {method!r}")
+        sort = method == "sort" or (method == "auto" and n > _lib.RANK_MAX_IMAGES)
+        most, name = (_lib.RANK_SORT_MAX_IMAGES, "bmi_rank_quality_sorted") if sort else (_lib.RANK_MAX_IMAGES, "bmi_rank_quality")
+        if n > most or R > _lib.RANK_MAX_ROWS:
+            raise ValueError(f"rank_quality takes at most {most} images and {_lib.RANK_MAX_ROWS} rows (n = {n}, R = {R})")
         ints = torch.zeros(3, R, cap, dtype=torch.int32, device=self.device)
         counts = torch.empty(R, 3, dtype=torch.int64, device=self.device)
         aurc_sum = torch.empty(R, dtype=torch.float64, device=self.device)
-        scratch = self._scratch("_nll_scratch", max(1, int(self.lib.bmi_rank_scratch_bytes(R, n))))
+        need = self.lib.bmi_rank_sort_scratch_bytes(R, n) if sort else self.lib.bmi_rank_scratch_bytes(R, n)
+        scratch = self._scratch("_nll_scratch", max(1, int(need)))
         with torch.cuda.device(self.device):
-            rc = self.lib.bmi_rank_quality(ukeys.data_ptr(), positive.data_ptr(), R, n, cap, ints[0].data_ptr(), ints[1].data_ptr(),
-                                           ints[2].data_ptr(), counts.data_ptr(), aurc_sum.data_ptr(), scratch.data_ptr(), scratch.numel(),
-                                           self._stream())
-        _lib.check(rc, "bmi_rank_quality")
+            rc = getattr(self.lib, name)(ukeys.data_ptr(), positive.data_ptr(), R, n, cap, ints[0].data_ptr(), ints[1].data_ptr(),
+                                         ints[2].data_ptr(), counts.data_ptr(), aurc_sum.data_ptr(), scratch.data_ptr(), scratch.numel(),
+                                         self._stream())
+        _lib.check(rc, name)
         return dict(rank=ints[0], sorted_keys=ints[1], curve=ints[2], counts=counts, aurc_sum=aurc_sum, n=n)
+
+    def rank_detection(self, table, tpr=(0.95,)):
+        """The detection figures of a ``rank_quality`` table on the device (bmi_rank_detection): dict(``ap_sum`` float64 [R, 2] — [0] /
+        n_pos is the average precision of "a high score flags a positive", [1] / n_neg that of "a low score flags a negative", each a sum
+        over the tie groups in a fixed order —, ``det`` int64 [R, L, 2] = (TP, FP) at the lowest threshold, a tie-group boundary, whose
+        true-positive rate reaches ``tpr[l]`` — FPR at that TPR = FP / n_neg —, ``tpr``).  At most ``RANK_DET_MAX_LEVELS`` levels, each in
+        (0, 1].  One launch, no synchronisation.  ``train.ranking.detection_metrics`` forms AUPR and FPR; ``rank_detection_numpy``
+        restates it."""
+        n = int(table["n"])
+        R, cap = check_buffer(table["sorted_keys"], (None, None), torch.int32, self.device, "table['sorted_keys'] [R, capacity]").shape
+        check_buffer(table["curve"], (R, cap), torch.int32, self.device, "table['curve'] [R, capacity]")
+        check_buffer(table["counts"], (R, 3), torch.int64, self.device, "table['counts'] [R, 3]")
+        n = self._check_n(n, cap, "the capacity")
+        tpr = tuple(float(q) for q in tpr)
+        if not 1 <= len(tpr) <= _lib.RANK_DET_MAX_LEVELS or not all(0.0 < q <= 1.0 for q in tpr):
+            raise ValueError(f"tpr must be 1 to {_lib.RANK_DET_MAX_LEVELS} levels in (0, 1], got {tpr}")
+        if n > _lib.RANK_SORT_MAX_IMAGES or R > _lib.RANK_MAX_ROWS:
+            raise ValueError(f"rank_detection takes at most {_lib.RANK_SORT_MAX_IMAGES} images and {_lib.RANK_MAX_ROWS} rows")
+        L = len(tpr)
+        ap_sum = torch.empty(R, 2, dtype=torch.float64, device=self.device)
+        det = torch.empty(R, L, 2, dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = self.lib.bmi_rank_detection(table["sorted_keys"].data_ptr(), table["curve"].data_ptr(), table["counts"].data_ptr(), R, n, cap,
+                                             (C.c_double * L)(*tpr), L, ap_sum.data_ptr(), det.data_ptr(), self._stream())
+        _lib.check(rc, "bmi_rank_detection")
+        return dict(ap_sum=ap_sum, det=det, tpr=tpr)
 
     # ---- exit-policy sweep (bmi_exit_stat_record / bmi_exit_policy_sweep) ----------------------------------------------------------
     def new_exit_stat_records(self, capacity, n_exits=None):

@@ -7,7 +7,10 @@ prints the mean predictive entropy of random-noise inputs (Hardware_Artifact/bay
 image, the same data gives these measures.
 
 ``score_keys_numpy`` and ``rank_quality_numpy`` restate the device's arithmetic contract (the header comment of csrc/ranking.hip) on the
-host; ``rank_metrics``, ``risk_at_coverage`` and ``threshold_at_coverage`` read a table, the device's or the restatement's.
+host; ``rank_metrics``, ``risk_at_coverage`` and ``threshold_at_coverage`` read a table, the device's or the restatement's.  Rows above
+2^17 images are ranked by csrc/ranking_sort.hip's radix sort, to the same bits; ``rank_detection_numpy`` restates its detection read-out
+(``MCDEngine.rank_detection``: the average precision of both classes, the false-positive rate at a true-positive rate) and
+``detection_metrics`` reads it.
 """
 import math
 
@@ -118,6 +121,60 @@ def rank_metrics(table):
     return out
 
 
+def rank_detection_numpy(table, tpr=(0.95,)):
+    """The host restatement of bmi_rank_detection on a table of ``MCDEngine.rank_quality`` or ``rank_quality_numpy``: dict(ap_sum float64
+    [R, 2], det int64 [R, L, 2], tpr).  A threshold sits at a tie-group boundary: flagging every image from the group start s on has
+    TP(s) = n_pos - curve[s - 1] (curve[-1] = 0) and FP(s) = (m - s) - TP(s).  ``ap_sum[r, 0]``: over the positions s in DESCENDING order, a
+    group start adds pos_in_group * TP(s) / (m - s), every other position +0.0; ``ap_sum[r, 1]``: over the ends e (exclusive) in ASCENDING
+    order, a group end adds neg_in_group * (e - curve[e - 1]) / e — explicit loops of float64 divisions of exact integers.  ``det[r, l]`` =
+    (TP(s), FP(s)) at the largest group start s with TP(s) >= min(max(ceil(tpr[l] * n_pos), 1), n_pos); (0, 0) where n_pos is 0."""
+    tpr = tuple(float(q) for q in tpr)
+    if not tpr or not all(0.0 < q <= 1.0 for q in tpr):
+        raise ValueError(f"tpr levels must lie in (0, 1], got {tpr}")
+    counts, keys, curve = _np(table["counts"]).astype(np.int64), _u32(table["sorted_keys"]), _np(table["curve"])
+    R = counts.shape[0]
+    out = dict(ap_sum=np.zeros((R, 2), dtype=np.float64), det=np.zeros((R, len(tpr), 2), dtype=np.int64), tpr=tpr)
+    for r in range(R):
+        m, n_pos = int(counts[r, 0]), int(counts[r, 1])
+        sk, cv = keys[r, :m].tolist(), [0] + curve[r, :m].tolist()         # cv[k] = the positives at positions < k
+        start = [k for k in range(m) if k == 0 or sk[k - 1] != sk[k]]       # the tie groups [start[g], end[g])
+        end = start[1:] + [m]
+        begins = dict(zip(start, end))
+        ends = dict(zip(end, start))
+        a = b = 0.0
+        for i in range(m):
+            s, e = m - 1 - i, i + 1
+            a = a + (float((cv[begins[s]] - cv[s]) * (n_pos - cv[s])) / float(m - s) if s in begins else 0.0)
+            b = b + (float(((e - ends[e]) - (cv[e] - cv[ends[e]])) * (e - cv[e])) / float(e) if e in ends else 0.0)
+        out["ap_sum"][r] = (a, b)
+        for l, q in enumerate(tpr):
+            if n_pos:
+                need = min(max(int(math.ceil(q * float(n_pos))), 1), n_pos)
+                s = max(s for s in start if n_pos - cv[s] >= need)
+                out["det"][r, l] = (n_pos - cv[s], (m - s) - (n_pos - cv[s]))
+    return out
+
+
+def detection_metrics(det_table, table):
+    """float64 on the host, from ``MCDEngine.rank_detection`` / ``rank_detection_numpy`` and the rank table they read: dict(aupr_pos [R] =
+    ap_sum[:, 0] / n_pos, aupr_neg [R] = ap_sum[:, 1] / n_neg, fpr_at_tpr [R, L] = FP / n_neg), NaN where the class divided by is empty."""
+    counts = _np(table["counts"]).astype(np.int64)
+    ap_sum, det = _np(det_table["ap_sum"]).astype(np.float64), _np(det_table["det"]).astype(np.int64)
+    R, L = det.shape[:2]
+    out = dict(aupr_pos=np.full(R, np.nan), aupr_neg=np.full(R, np.nan), fpr_at_tpr=np.full((R, L), np.nan))
+    for r in range(R):
+        n_pos = int(counts[r, 1])
+        n_neg = int(counts[r, 0]) - n_pos
+        if n_pos:
+            out["aupr_pos"][r] = ap_sum[r, 0] / float(n_pos)
+        if n_neg:
+            out["aupr_neg"][r] = ap_sum[r, 1] / float(n_neg)
+        if n_pos and n_neg:
+            for l in range(L):
+                out["fpr_at_tpr"][r, l] = float(det[r, l, 1]) / float(n_neg)
+    return out
+
+
 def _position(m, c):
     """k = ceil(c m) clipped to [1, m]: the number of images kept at coverage ``c``"""
     return min(max(int(math.ceil(float(c) * m)), 1), m)
@@ -178,10 +235,15 @@ class RankingAnalysis:
     are ignored).  The walk goes on over them (seeds ``seed + k`` continue), their scores go into the columns behind the ``n``
     in-distribution ones, ``positive`` is 1 there and 0 in front, validity is by finiteness only, and a second ``rank_quality`` per score
     gives ``ood_tables`` / ``ood_metrics``; ``ood_rows``: one ``(name, score, auroc, ape_in, ape_noise)`` per row and score; ``ape``: the mean
-    predictive entropy per row, (in-distribution float64 [R], noise float64 [R]) — the pair the reference prints; ``n_ood``."""
+    predictive entropy per row, (in-distribution float64 [R], noise float64 [R]) — the pair the reference prints; ``n_ood``.
+
+    ``detection=True``: one ``MCDEngine.rank_detection`` per table at the levels ``tpr``; ``metrics[score]`` and ``ood_metrics[score]``
+    gain ``detection_metrics``' ``aupr_pos``, ``aupr_neg`` and ``fpr_at_tpr`` [R, L], and ``detection_rows`` / ``ood_detection_rows`` hold one
+    ``(name, score, aupr_pos, aupr_neg, fpr_at_tpr...)`` per row and score.  Both lists are empty without it; ``rows``, ``ood_rows`` and
+    ``save`` are the same either way.  A walk of more than 2^17 images is ranked by the radix sort (``rank_quality(method="auto")``)."""
 
     def __init__(self, model, loader, gpu=0, mc_passes=10, seed=0, scores=("confidence", "pred_entropy", "mutual_info", "variation_ratio"),
-                 ood_loader=None):
+                 ood_loader=None, detection=False, tpr=(0.95,)):
         self.model = model
         self.loader = loader
         self.ood_loader = ood_loader
@@ -189,6 +251,7 @@ class RankingAnalysis:
         self.mc_passes = int(mc_passes)
         self.seed = seed
         self.scores = tuple(scores)
+        self.detection, self.tpr = bool(detection), tuple(float(q) for q in tpr)
         unknown = [s for s in self.scores if s not in SCORES]
         if unknown or not self.scores:
             raise ValueError(f"scores must be among {sorted(SCORES)}, got {unknown or self.scores}")
@@ -208,6 +271,15 @@ class RankingAnalysis:
         if hasattr(loader, "dataset"):
             return len(loader.dataset)
         return sum(len(_images(b)) for b in loader)
+
+    def _detect(self, eng, tables, metrics, names):
+        """``detection=True``: the detection entries of ``metrics`` and the rows ``(name, score, aupr_pos, aupr_neg, fpr_at_tpr...)``"""
+        if not self.detection:
+            return []
+        for s in self.scores:
+            metrics[s].update(detection_metrics(eng.rank_detection(tables[s], self.tpr), tables[s]))
+        return [(name, s, float(metrics[s]["aupr_pos"][r]), float(metrics[s]["aupr_neg"][r])) +
+                tuple(float(v) for v in metrics[s]["fpr_at_tpr"][r]) for r, name in enumerate(names) for s in self.scores]
 
     def _run(self):
         import torch
@@ -260,7 +332,7 @@ class RankingAnalysis:
         self.labels = np.concatenate(labels)
         self.records = rel
         positive = 1 - rel["hit"]
-        self.tables = {s: eng.rank_quality(rec[s]["ukeys"], positive, self.n) for s in self.scores}
+        self.tables = {s: eng.rank_quality(rec[s]["ukeys"], positive, self.n, method="auto") for s in self.scores}
         eng.check_finite()
         self.metrics, self.rows = {}, []
         names = row_names(eng.n_exits)
@@ -271,18 +343,20 @@ class RankingAnalysis:
             for s in self.scores:
                 m = self.metrics[s]
                 self.rows.append((name, s, float(m["auroc"][r]), float(m["aurc"][r]), float(m["eaurc"][r]), float(m["risk80"][r])))
-        self.ood_tables, self.ood_metrics, self.ood_rows, self.ape = {}, {}, [], None
+        self.detection_rows = self._detect(eng, self.tables, self.metrics, names)
+        self.ood_tables, self.ood_metrics, self.ood_rows, self.ape, self.ood_detection_rows = {}, {}, [], None, []
         if self.n_ood:
             total = self.n + self.n_ood
             positive = torch.zeros(2 * eng.n_exits, n_in + n_out, dtype=torch.uint8, device=self.device)
             positive[:, self.n:total] = 1
             for s in self.scores:
-                self.ood_tables[s] = eng.rank_quality(ood_rec[s]["ukeys"], positive, total)
+                self.ood_tables[s] = eng.rank_quality(ood_rec[s]["ukeys"], positive, total, method="auto")
                 self.ood_metrics[s] = rank_metrics(self.ood_tables[s])
             ape = _np(ape_sum)
             self.ape = (ape[0] / float(self.n), ape[1] / float(self.n_ood))
             self.ood_rows = [(name, s, float(self.ood_metrics[s]["auroc"][r]), float(self.ape[0][r]), float(self.ape[1][r]))
                              for r, name in enumerate(names) for s in self.scores]
+            self.ood_detection_rows = self._detect(eng, self.ood_tables, self.ood_metrics, names)
 
     def save(self, experiment_id):
         """``test_ranking_<experiment_id>.csv``: a header line, then ``rows`` (with the out-of-distribution AUROC as a last column under

@@ -983,8 +983,42 @@ int bmi_classwise_table(const uint32_t* pkeys, const int32_t* labels_rec, int32_
  * launches, no allocation, no synchronisation: capturable.  scratch: the per-tile integer partials, bmi_rank_scratch_bytes = R *
  * ceil(N / BMI_RANK_TILE_I) * 3 * 8 (0 for arguments the call refuses).
  * BMI_ERR_INVALID (decided before any HIP call): a null pointer, R / N below 1, N > N_cap.  BMI_ERR_UNSUPPORTED: N > BMI_RANK_MAX_IMAGES
- * (2^17: a radix sort for longer rows is not built), R > BMI_RANK_MAX_ROWS (1024).  BMI_ERR_NOMEM: scratch too small.  An error writes
- * nothing. */
+ * (2^17: bmi_rank_quality_sorted takes longer rows), R > BMI_RANK_MAX_ROWS (1024).  BMI_ERR_NOMEM: scratch too small.  An error writes
+ * nothing.
+ *
+ * bmi_rank_quality_sorted is the same call by a sort (csrc/ranking_sort.hip): the same arguments, the same five outputs under the same
+ * contract BIT FOR BIT, for 1 <= N <= BMI_RANK_SORT_MAX_IMAGES (2^22 - 1).  A stable LSD radix sort for wave64 over the sort word (the
+ * ukey, one above 0x7F7FFFFF read as 0xFFFFFFFF: the invalid images land behind the m valid ones) with the payload (image index, the
+ * positive bit in bit 31): four passes of 8 bits over ping-pong buffers in the scratch, each pass three launches over all rows — a
+ * 256-bin LDS histogram per tile of BMI_RANK_SORT_TILE positions (integer LDS atomics), one exclusive scan per row in (digit, tile)
+ * order, and a stable scatter whose in-tile offsets come from wave ballots —, then the curve as a scan of the positive bits in position
+ * order, U2 from the tie groups (a binary search per group start) and aurc_sum added exactly as above.  No comparison sort, no per-key
+ * global atomic, no workgroup waits on another; integers only apart from aurc_sum, no floating-point atomics: the same bits on every run
+ * and for every cut of the images into record calls.  17 launches that depend on (R, N) only, no allocation, no synchronisation:
+ * capturable.  scratch: bmi_rank_sort_scratch_bytes = 4 * R * (256 * ceil(N / BMI_RANK_SORT_TILE) + 4 * N) (0 for arguments the call
+ * refuses).  BMI_ERR_INVALID as above.  BMI_ERR_UNSUPPORTED: N > BMI_RANK_SORT_MAX_IMAGES, R > BMI_RANK_MAX_ROWS.  BMI_ERR_NOMEM: scratch
+ * too small.  An error writes nothing.
+ *
+ * bmi_rank_detection reads columns 0 .. N-1 of the sorted_keys and curve and the counts of either rank call and gives the detection
+ * figures beside the AUROC: the average precision of both classes and the operating point at given true-positive rates (train.ranking.
+ * rank_detection_numpy restates it).  A threshold sits at a tie-group boundary: "flag every image whose key is at least the key of the
+ * group that starts at position s" has TP(s) = n_pos - curve[s-1] (curve[-1] = 0) and FP(s) = (m - s) - TP(s).  Both outputs OVERWRITTEN:
+ *     ap_sum  float64 [R][2]      [0] the positive class: over the group starts s in DESCENDING position the sum of
+ *                                     (double) (pos_in_group * TP(s)) / (double) (m - s); ap_sum[0] / n_pos is the average precision of
+ *                                     "a high score flags a positive".
+ *                                 [1] the negative class, swept from the certain end: over the group ends e (exclusive) in ASCENDING
+ *                                     position the sum of (double) (neg_in_group * (e - curve[e-1])) / (double) e; ap_sum[1] / n_neg is
+ *                                     the average precision of "a low score flags a negative".
+ *                                 Each product is formed in int64 and converted exactly, each quotient rounded once, no fused multiply-add;
+ *                                 the terms are added from 0.0 by one wave in that order, a position that is no boundary adding +0.0;
+ *                                 0.0 where m = 0.
+ *     det     int64 [R][L][2]     per level q = tpr[l] (HOST float64 [L], each in (0, 1], L <= BMI_RANK_DET_MAX_LEVELS):
+ *                                 need = min(max((long) ceil(q * (double) n_pos), 1), n_pos) — one rounded product, then the ceiling —,
+ *                                 s = the largest group start with TP(s) >= need: (TP(s), FP(s)); (0, 0) where n_pos = 0.  FPR at that
+ *                                 TPR = FP / n_neg is formed on the host.
+ * One launch, one workgroup per row, no scratch, no allocation, no synchronisation: capturable.  BMI_ERR_INVALID (decided before any HIP
+ * call): a null pointer, R / N / L below 1, N > N_cap, L > BMI_RANK_DET_MAX_LEVELS, a level outside (0, 1].  BMI_ERR_UNSUPPORTED: N >
+ * BMI_RANK_SORT_MAX_IMAGES, R > BMI_RANK_MAX_ROWS.  An error writes nothing. */
 #define BMI_RANK_TILE_I 512         /* images whose keys one workgroup of the counting kernel keeps in registers */
 #define BMI_RANK_TILE_J 2048        /* images whose keys it stages in LDS per step */
 #define BMI_RANK_MAX_IMAGES 131072
@@ -996,6 +1030,15 @@ size_t bmi_rank_scratch_bytes(int32_t R, int32_t N);
 int bmi_rank_quality(const uint32_t* ukeys, const uint8_t* positive, int32_t R, int32_t N, int32_t N_cap, int32_t* rank, uint32_t* sorted_keys,
                      int32_t* curve, int64_t* counts /*[R][3]*/, double* aurc_sum /*[R]*/, void* scratch, size_t scratch_bytes,
                      bmi_stream stream);
+#define BMI_RANK_SORT_TILE 4096     /* positions of one row a workgroup of the radix sort takes */
+#define BMI_RANK_SORT_MAX_IMAGES 4194303
+#define BMI_RANK_DET_MAX_LEVELS 8
+size_t bmi_rank_sort_scratch_bytes(int32_t R, int32_t N);
+int bmi_rank_quality_sorted(const uint32_t* ukeys, const uint8_t* positive, int32_t R, int32_t N, int32_t N_cap, int32_t* rank,
+                            uint32_t* sorted_keys, int32_t* curve, int64_t* counts /*[R][3]*/, double* aurc_sum /*[R]*/, void* scratch,
+                            size_t scratch_bytes, bmi_stream stream);
+int bmi_rank_detection(const uint32_t* sorted_keys, const int32_t* curve, const int64_t* counts /*[R][3]*/, int32_t R, int32_t N, int32_t N_cap,
+                       const double* tpr /* host [L] */, int32_t L, double* ap_sum /*[R][2]*/, int64_t* det /*[R][L][2]*/, bmi_stream stream);
 
 /* Exit-policy sweep: for many thresholds at once, where every image would leave under the staged engine's rule and what the predictions
  * taken there are worth — the trade-off table of the reference's get_confidence_exiting_values (SA/train/results_analyzer.py:543-566:

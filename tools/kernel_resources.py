@@ -12,7 +12,7 @@ from bayesnn_fpga_amd import _build  # noqa: E402
 
 src = sys.argv[1]
 path = src if os.path.exists(src) else os.path.join(_build.CSRC, src)
-r = subprocess.run([_build._hipcc(), *_build.FLAGS, *sys.argv[2:], "-Rpass-analysis=kernel-resource-usage", "-c", path, "-o", os.devnull],
+r = subprocess.run([_build._hipcc(), *_build.FLAGS, *_build.EXTRA_FLAGS.get(os.path.basename(src), []), *sys.argv[2:], "-Rpass-analysis=kernel-resource-usage", "-c", path, "-o", os.devnull],
                    capture_output=True, text=True)
 if r.returncode:
     sys.exit(r.stderr[-3000:])

@@ -11,10 +11,13 @@
         B  MCDEngine.score_records per batch of --batch images, ONE rank_quality, rank_metrics on the host (its reads of counts and
            aurc_sum: the synchronisation);
       and the device time of B's two halves, and of the rank call alone, by HIP events.  The two routes' numbers are compared.
+  (s) the counting rank call against the sorted one (rank_quality(method="count" / "sort")) on the same R = --rows rows of N keys, device
+      time by HIP events, the two alternating in one process; above the counting call's limit the sort alone.  Their outputs are compared.
   Sizes: --n 10000 (the reference's test sets; E = 4, R = 8) and --n 131072 (the largest row the rank call takes).  Medians over --rounds.
 
     python tools/ranking_bench.py [--rounds 9] [--launches 20] [--n 10000] [--batch 250] [--parts t]
     python tools/ranking_bench.py --parts r
+    python tools/ranking_bench.py --parts s --rows 35 --n 131072 [--rounds 5] [--launches 3]
 """
 import argparse
 import json
@@ -35,12 +38,13 @@ from vector_scaling_bench import SIZES, event_ms, model_of, stats  # noqa: E402
 
 def part_r(a):
     cols = ("sgpr", "vgpr", "agpr", "scratch", "occ", "s_spill", "v_spill", "lds")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"), "ranking.hip"], capture_output=True, text=True)
-    if out.returncode:
-        sys.exit(out.stderr[-2000:])
-    for line in out.stdout.splitlines()[1:]:
-        print(json.dumps(dict(part="r", kernel=line[:90].strip().split("(")[0], **{c: int(x) for c, x in zip(cols, line[90:].split())})),
-              flush=True)
+    for src in ("ranking.hip", "ranking_sort.hip"):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"), src], capture_output=True, text=True)
+        if out.returncode:
+            sys.exit(out.stderr[-2000:])
+        for line in out.stdout.splitlines()[1:]:
+            print(json.dumps(dict(part="r", kernel=line[:90].strip().split("(")[0], **{c: int(x) for c, x in zip(cols, line[90:].split())})),
+                  flush=True)
 
 
 def problem(R, N, seed=0):
@@ -124,19 +128,45 @@ def part_t(a):
                               if name.startswith("rank") else None)), flush=True)
 
 
+def part_s(a):
+    from bayesnn_fpga_amd import _lib
+    dev = torch.device("cuda", 0)
+    eng = model_of(SIZES["paper"][0], dev).engine(dev, max_batch=8, dtype="f16x2")
+    R, N = a.rows, a.n
+    score, hit = problem(R, N)
+    ukeys = torch.from_numpy(np.ascontiguousarray(score.astype(np.float32)).view(np.int32)).to(dev)       # direction +1: the float32 bits
+    positive = torch.from_numpy(1 - hit).to(dev)
+    methods = ["count", "sort"] if N <= _lib.RANK_MAX_IMAGES else ["sort"]
+    fns = {m: (lambda m=m: eng.rank_quality(ukeys, positive, N, method=m)) for m in methods}
+    tables = {m: fn() for m, fn in fns.items()}                                   # warm-up: code objects, the scratch buffer
+    torch.cuda.synchronize()
+    same = all(torch.equal(tables["count"][k], tables["sort"][k]) for k in ("rank", "sorted_keys", "curve", "counts", "aurc_sum")) \
+        if len(methods) == 2 else None
+    times = {m: [] for m in methods}
+    for r in range(a.rounds):
+        for m in (methods if r % 2 == 0 else methods[::-1]):
+            times[m].append(event_ms(fns[m], a.launches))
+    for m in methods:
+        st = stats(times[m])
+        print(json.dumps(dict(part="s", what="one rank_quality, device time, HIP events", method=m, N=N, R=R, launches_per_timing=a.launches,
+                              timings=a.rounds, **st, ratio_to_count=round(st["median_ms"] / stats(times[methods[0]])["median_ms"], 4)
+                              if len(methods) == 2 else None, outputs_equal=same)), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=9)
     ap.add_argument("--launches", type=int, default=20)
     ap.add_argument("--n", type=int, default=10000)
     ap.add_argument("--batch", type=int, default=250)
+    ap.add_argument("--rows", type=int, default=35)
     ap.add_argument("--parts", default="t")
     a = ap.parse_args()
     parts = a.parts.split(",")
     if set(parts) - {"r"} and not torch.cuda.is_available():
         sys.exit("ranking_bench.py measures part t on the GPU: none visible (--parts r needs none)")
     for p in parts:
-        {"r": part_r, "t": part_t}[p](a)
+        {"r": part_r, "t": part_t, "s": part_s}[p](a)
 
 
 if __name__ == "__main__":
