@@ -31,6 +31,8 @@ RANK_SORT_TILE, RANK_SORT_MAX_IMAGES = 4096, (1 << 22) - 1     # BMI_RANK_SORT_*
 RANK_DET_MAX_LEVELS = 8                     # BMI_RANK_DET_MAX_LEVELS of bmi_rank_detection: TPR levels per call
 RANK_INVALID, RANK_MAX_KEY = 0xFFFFFFFF, 0x7F7FFFFF # the score key of an image that is in no count; the largest valid key (FLT_MAX's bits)
 POLICY_MAX_THRESHOLDS, POLICY_MAX_RECORD_ROWS = 1024, 64       # BMI_POLICY_MAX_* of bmi_exit_policy_sweep: thresholds per call / with selected records
+CONFORMAL_METHODS = {"lac": 0, "aps": 1, "raps": 2}      # BMI_CONFORMAL_* of bmi_conformal_scores / bmi_conformal_sets
+CONFORMAL_MAX_LEVELS, CONFORMAL_MAX_KEY = 8, 0xFFFFFFFE   # BMI_CONFORMAL_MAX_LEVELS; the saturated score key: the quantile that admits every class
 NLL_ENS_SLAB, NLL_ENS_ROWS = 9216, 192     # BMI_NLL_ENS_* of bmi_nll_ensemble_temperature_grid: floats / rows a workgroup stages per chunk
 
 
@@ -162,6 +164,9 @@ _PROTOS = {
     "bmi_reliability_kde": (C.c_int, [C.c_void_p] * 2 + [C.c_int32] * 5 + [C.c_double] + [C.c_void_p] * 8),
     "bmi_classwise_record": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 4),
     "bmi_classwise_table": (C.c_int, [C.c_void_p] * 2 + [C.c_int32] * 5 + [C.POINTER(C.c_float)] + [C.c_void_p] * 6),
+    "bmi_conformal_scores": (C.c_int, [C.c_void_p] * 2 + [C.c_int32] * 6 + [C.c_uint32, C.c_void_p, C.c_void_p]),
+    "bmi_conformal_quantile": (C.c_int, [C.c_void_p] + [C.c_int32] * 3 + [C.POINTER(C.c_double), C.c_int32] + [C.c_void_p] * 3),
+    "bmi_conformal_sets": (C.c_int, [C.c_void_p] * 2 + [C.c_int32] * 6 + [C.c_uint32, C.c_void_p, C.c_int32] + [C.c_void_p] * 10),
     "bmi_score_record": (C.c_int, [C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 3),
     "bmi_rank_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "bmi_rank_quality": (C.c_int, [C.c_void_p] * 2 + [C.c_int32] * 3 + [C.c_void_p] * 6 + [C.c_size_t, C.c_void_p]),

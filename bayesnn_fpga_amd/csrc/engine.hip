@@ -2370,6 +2370,41 @@ int bmi_classwise_table(const uint32_t* pkeys, const int32_t* labels_rec, int32_
                                   (long long*)conf_fix, (long long*)valid, (hipStream_t)stream);
 }
 
+static bool conformal_method_ok(int32_t method, int32_t k_reg, uint32_t lam_fix) {
+    return method >= BMI_CONFORMAL_LAC && method <= BMI_CONFORMAL_RAPS && k_reg >= 0 && lam_fix <= (1u << 30);
+}
+
+int bmi_conformal_scores(const uint32_t* pkeys, const int32_t* labels_rec, int32_t R, int32_t C, int32_t N, int32_t N_cap, int32_t method,
+                         int32_t k_reg, uint32_t lam_fix, uint32_t* score_keys, bmi_stream stream) {
+    if (!pkeys || !labels_rec || !score_keys || R < 1 || C < 1 || N < 1 || N > N_cap || !conformal_method_ok(method, k_reg, lam_fix))
+        return BMI_ERR_INVALID;
+    if (!conformal_takes(R, C, N)) return BMI_ERR_UNSUPPORTED;
+    return launch_conformal_scores(pkeys, labels_rec, R, C, N, N_cap, method, k_reg, lam_fix, score_keys, (hipStream_t)stream);
+}
+
+int bmi_conformal_quantile(const uint32_t* score_keys, int32_t R, int32_t N, int32_t N_cap, const double* coverage, int32_t L, uint32_t* qhat,
+                           int64_t* n_valid, bmi_stream stream) {
+    if (!score_keys || !coverage || !qhat || !n_valid || R < 1 || N < 1 || N > N_cap || L < 1 || L > BMI_CONFORMAL_MAX_LEVELS)
+        return BMI_ERR_INVALID;
+    for (int l = 0; l < L; ++l)
+        if (!(coverage[l] > 0.0 && coverage[l] < 1.0)) return BMI_ERR_INVALID;
+    if (!conformal_takes(R, 1, N)) return BMI_ERR_UNSUPPORTED;
+    return launch_conformal_quantile(score_keys, R, N, N_cap, coverage, L, qhat, (long long*)n_valid, (hipStream_t)stream);
+}
+
+int bmi_conformal_sets(const uint32_t* pkeys, const int32_t* labels_rec, int32_t R, int32_t C, int32_t N, int32_t N_cap, int32_t method,
+                       int32_t k_reg, uint32_t lam_fix, const uint32_t* qhat, int32_t L, uint8_t* set_size, uint32_t* members, int64_t* valid,
+                       int64_t* covered, int64_t* size_sum, int64_t* size_hist, int64_t* cov_hist, int64_t* class_n, int64_t* class_cov,
+                       bmi_stream stream) {
+    if (!pkeys || !labels_rec || !qhat || !set_size || !valid || !covered || !size_sum || !size_hist || !cov_hist || !class_n || !class_cov ||
+        R < 1 || C < 1 || N < 1 || N > N_cap || L < 1 || L > BMI_CONFORMAL_MAX_LEVELS || !conformal_method_ok(method, k_reg, lam_fix))
+        return BMI_ERR_INVALID;
+    if (!conformal_takes(R, C, N)) return BMI_ERR_UNSUPPORTED;
+    const ConformalTables t = {(long long*)valid,     (long long*)covered, (long long*)size_sum, (long long*)size_hist,
+                               (long long*)cov_hist, (long long*)class_n, (long long*)class_cov};
+    return launch_conformal_sets(pkeys, labels_rec, R, C, N, N_cap, method, k_reg, lam_fix, qhat, L, set_size, members, t, (hipStream_t)stream);
+}
+
 int bmi_score_record(const double* score, int32_t R, int32_t B, int32_t direction, const uint32_t* valid_keys, int32_t n0, int32_t N_cap,
                      uint32_t* ukeys, int32_t* counter, bmi_stream stream) {
     if (!score || !ukeys || R < 1 || B < 1 || N_cap < 1 || n0 < 0 || (int64_t)n0 + B > N_cap || (direction != 1 && direction != -1))

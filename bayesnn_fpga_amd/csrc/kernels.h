@@ -242,6 +242,19 @@ int launch_classwise_record(const double* mean, int E, int B, int C, const int* 
                             int* counters, hipStream_t s);
 int launch_classwise_table(const uint32_t* pkeys, const int* labels_rec, int R, int C, int N, int N_cap, int n_bins, const float* edges_in,
                            float* edges_out, long long* count, long long* hits, long long* conf_fix, long long* valid, hipStream_t s);
+// conformal.hip (bmi_conformal_scores / bmi_conformal_quantile / bmi_conformal_sets): from columns 0 .. N-1 of the classwise records the
+// score key of the label's class per (row, image); from those keys and L HOST coverage levels qhat uint32 [R][L] and n_valid int64 [R]; and
+// from the records and DEVICE qhat the sets — set_size uint8 [R][L][N_cap], members uint32 [R][L][ceil(C / 32)][N_cap] or null — and the
+// seven int64 tables, all OVERWRITTEN; one, one and two launches, no scratch.  The callers have checked conformal_takes (C <= 128, R <= 64,
+// N < 2^22) and the arguments
+struct ConformalTables { long long *valid, *covered, *size_sum, *size_hist, *cov_hist, *class_n, *class_cov; };
+bool conformal_takes(int R, int C, int N);
+int launch_conformal_scores(const uint32_t* pkeys, const int* labels_rec, int R, int C, int N, int N_cap, int method, int k_reg, uint32_t lam_fix,
+                            uint32_t* score_keys, hipStream_t s);
+int launch_conformal_quantile(const uint32_t* score_keys, int R, int N, int N_cap, const double* coverage, int L, uint32_t* qhat,
+                              long long* n_valid, hipStream_t s);
+int launch_conformal_sets(const uint32_t* pkeys, const int* labels_rec, int R, int C, int N, int N_cap, int method, int k_reg, uint32_t lam_fix,
+                          const uint32_t* qhat, int L, uint8_t* set_size, uint32_t* members, ConformalTables t, hipStream_t s);
 // reliability_kde.hip (bmi_reliability_kde): from columns 0 .. N-1 of the records' keys and hit bits, per row the KDE-ECE on a G-point grid —
 // ece_kde, bw, sd [R], n_data, n_hit int64 [R], degenerate int32 [R], density [R][2][G] = pp1, pp2 (the density sums in between) —, all
 // OVERWRITTEN; three launches.  BMI_ERR_UNSUPPORTED (nothing launched) for what reliability_kde_takes refuses (R > 64, N >= 2^22, G outside

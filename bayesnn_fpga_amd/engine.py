@@ -1712,6 +1712,82 @@ class MCDEngine(CompiledGraph):
             self._raise_counters(records, "classwise")
         return dict(edges=out_edges, count=ints[0], hits=ints[1], conf_fix=ints[2], valid=valid, n=n)
 
+    # ---- conformal prediction sets (bmi_conformal_scores / bmi_conformal_quantile / bmi_conformal_sets) ----------------------------
+    def _conformal_args(self, records, n, method, k_reg, lam):
+        """(R, C, capacity, n, the method's code, k_reg, lam_fix = floor(lam * 2^30)) of a conformal call over classwise records"""
+        R, Cd, cap = self._check_classwise_records(records)
+        n = self._check_n(n, cap)
+        if method not in _lib.CONFORMAL_METHODS:
+            raise ValueError(f"method must be one of {sorted(_lib.CONFORMAL_METHODS)}, got {method!r}")
+        k_reg, lam = int(k_reg), float(lam)
+        if k_reg < 0 or not 0.0 <= lam <= 1.0:
+            raise ValueError(f"k_reg must be >= 0 and lam in [0, 1], got k_reg = {k_reg}, lam = {lam}")
+        if R > 64 or Cd > 128 or n >= _lib.RANK_SORT_MAX_IMAGES + 1:
+            raise ValueError(f"the conformal calls take at most 64 rows, 128 classes and fewer than 2^22 images (R = {R}, C = {Cd}, n = {n})")
+        return R, Cd, cap, n, _lib.CONFORMAL_METHODS[method], k_reg, int(lam * 2.0 ** 30)
+
+    def conformal_scores(self, records, n, method="aps", k_reg=0, lam=0.0):
+        """The calibration scores of the first ``n`` images of the classwise ``records`` on the device (bmi_conformal_scores): int32
+        [R, capacity], the uint32 score key of the LABEL's class per (row, image) — ``method`` "lac" (2^30 - u), "aps" (the cumulated
+        u of the classes down to the label's in the stable descending order, ties by class index) or "raps" (APS plus floor(``lam`` *
+        2^30) per rank beyond ``k_reg``), u = the truncated confidence * 2^30, saturating at 0xFFFFFFFE —, INVALID (all ones: -1) for
+        an image with an INVALID key or no label, and in the columns beyond ``n``.  Integers only: the same bits on every run.  One
+        launch, no synchronisation.  ``train.conformal.conformal_numpy`` is the host restatement."""
+        R, Cd, cap, n, code, k_reg, lam_fix = self._conformal_args(records, n, method, k_reg, lam)
+        scores = torch.full((R, cap), -1, dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = self.lib.bmi_conformal_scores(records["pkeys"].data_ptr(), records["labels"].data_ptr(), R, Cd, n, cap, code, k_reg, lam_fix,
+                                               scores.data_ptr(), self._stream())
+        _lib.check(rc, "bmi_conformal_scores")
+        return scores
+
+    def conformal_quantile(self, scores, n, coverage=(0.9,)):
+        """The conformal quantiles of the first ``n`` columns of ``scores`` int32 [R, capacity] (``conformal_scores``) on the device
+        (bmi_conformal_quantile): dict(``qhat`` int32 [R, L] — per row and level the order statistic of rank k - 1 of the valid keys,
+        k = ceil((n_valid + 1) * coverage), or 0xFFFFFFFE (-2: every class is in every set) where k > n_valid —, ``n_valid`` int64 [R],
+        ``coverage``).  At most ``CONFORMAL_MAX_LEVELS`` levels, each inside (0, 1).  A radix select: exact under ties.  One launch."""
+        R, cap = check_buffer(scores, (None, None), torch.int32, self.device, "scores [R, capacity]").shape
+        n = self._check_n(n, cap, "the capacity")
+        coverage = tuple(float(q) for q in coverage)
+        if not 1 <= len(coverage) <= _lib.CONFORMAL_MAX_LEVELS or not all(0.0 < q < 1.0 for q in coverage):
+            raise ValueError(f"coverage must be 1 to {_lib.CONFORMAL_MAX_LEVELS} levels inside (0, 1), got {coverage}")
+        if R > 64 or n > _lib.RANK_SORT_MAX_IMAGES:
+            raise ValueError(f"conformal_quantile takes at most 64 rows and fewer than 2^22 images (R = {R}, n = {n})")
+        L = len(coverage)
+        qhat = torch.empty(R, L, dtype=torch.int32, device=self.device)
+        n_valid = torch.empty(R, dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = self.lib.bmi_conformal_quantile(scores.data_ptr(), R, n, cap, (C.c_double * L)(*coverage), L, qhat.data_ptr(),
+                                                 n_valid.data_ptr(), self._stream())
+        _lib.check(rc, "bmi_conformal_quantile")
+        return dict(qhat=qhat, n_valid=n_valid, coverage=coverage)
+
+    def conformal_sets(self, records, n, qhat, method="aps", k_reg=0, lam=0.0, members=False):
+        """The prediction sets of the first ``n`` images of the classwise ``records`` under the quantiles ``qhat`` int32 [R, L]
+        (``conformal_quantile``'s, of scores formed with the same ``method``, ``k_reg`` and ``lam``) on the device (bmi_conformal_sets):
+        class c is in the set of (row, level, image) iff its score key does not exceed the quantile.  A dict of device tensors:
+        ``set_size`` uint8 [R, L, capacity] (255 for an invalid image and beyond ``n``), ``members`` int32 [R, L, ceil(C / 32), capacity]
+        (bit c % 32 of word c / 32) with ``members=True``, else None, and over the valid images the int64 tables ``valid`` [R],
+        ``covered`` and ``size_sum`` [R, L], ``size_hist`` and ``cov_hist`` [R, L, C + 1] (the images, and those whose label is in the
+        set, per set size), ``class_n`` [R, C] and ``class_cov`` [R, L, C] — and ``n``.  Exact integers, the same bits on every run and
+        for every cut of the images into ``classwise_records`` calls; ``train.conformal.conformal_metrics`` derives the coverage
+        figures.  Two launches, no synchronisation."""
+        R, Cd, cap, n, code, k_reg, lam_fix = self._conformal_args(records, n, method, k_reg, lam)
+        L = check_buffer(qhat, (R, None), torch.int32, self.device, "qhat [R, L]").shape[1]
+        if not 1 <= L <= _lib.CONFORMAL_MAX_LEVELS:
+            raise ValueError(f"qhat holds {L} levels, conformal_sets takes 1 to {_lib.CONFORMAL_MAX_LEVELS}")
+        set_size = torch.full((R, L, cap), 255, dtype=torch.uint8, device=self.device)
+        words = torch.zeros(R, L, (Cd + 31) // 32, cap, dtype=torch.int32, device=self.device) if members else None
+        t = dict(valid=(R,), covered=(R, L), size_sum=(R, L), size_hist=(R, L, Cd + 1), cov_hist=(R, L, Cd + 1), class_n=(R, Cd),
+                 class_cov=(R, L, Cd))
+        t = {k: torch.empty(shape, dtype=torch.int64, device=self.device) for k, shape in t.items()}
+        with torch.cuda.device(self.device):
+            rc = self.lib.bmi_conformal_sets(records["pkeys"].data_ptr(), records["labels"].data_ptr(), R, Cd, n, cap, code, k_reg, lam_fix,
+                                             qhat.data_ptr(), L, set_size.data_ptr(), _ptr(words), *(v.data_ptr() for v in t.values()),
+                                             self._stream())
+        _lib.check(rc, "bmi_conformal_sets")
+        return dict(set_size=set_size, members=words, n=n, **t)
+
     # ---- rank quality of the uncertainty scores (bmi_score_record / bmi_rank_quality) ---------------------------------------------
     def new_score_records(self, capacity, rows):
         """The key buffer of ``capacity`` images and ``rows`` rows for ``score_records``: dict(ukeys int32 [rows, capacity] — uint32 bit

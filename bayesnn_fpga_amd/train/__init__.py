@@ -1,4 +1,5 @@
 from .calibration import EnsembleTemperatureScaling, EnsembleWeights, TemperatureScaling  # noqa: F401
+from .conformal import ConformalAnalysis, conformal_metrics  # noqa: F401
 from .evaluate import MultiExitAccuracy, evaluate, evaluate_exits  # noqa: F401
 from .exit_policy import ExitPolicyAnalysis, policy_macs, policy_metrics, reference_costs  # noqa: F401
 from .ranking import RankingAnalysis, rank_metrics, risk_at_coverage, threshold_at_coverage  # noqa: F401

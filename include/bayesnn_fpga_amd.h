@@ -949,6 +949,62 @@ int bmi_classwise_table(const uint32_t* pkeys, const int32_t* labels_rec, int32_
                         const float* edges_in /* host [n_bins + 1] or NULL */, float* edges_out, int64_t* count, int64_t* hits,
                         int64_t* conf_fix, int64_t* valid, bmi_stream stream);
 
+/* Conformal prediction sets (split conformal prediction: LAC — Sadinle et al. 2019 —, APS — Romano et al. 2020, the deterministic form —,
+ * RAPS — Angelopoulos et al. 2021) from the classwise records above: the calibration score of every image, one quantile per row and
+ * coverage level, then per image the set of classes whose score does not exceed it, with the coverage tables.  Integers only
+ * (csrc/conformal.hip; train.conformal.conformal_numpy restates the three calls).  pkeys uint32 [R][C][N_cap] and labels_rec int32 [N_cap]
+ * are bmi_classwise_record's (every key at most 0x3F800000, the bits of 1.0f, or INVALID = 0xFFFFFFFF); columns 0 .. N-1 are read.
+ *
+ * A (row, image) is VALID when none of its C keys is INVALID and labels_rec[n] is in [0, C).  For a valid pair, conf_c the float32 behind
+ * key_c:
+ *     u_c     = (uint64) ((double) conf_c * 2^30), truncating (exact: at most 2^30)
+ *     order   class j PRECEDES class c when key_j > key_c, or key_j == key_c and j < c (total and stable: ties by class index)
+ *     rank_c  = the classes that precede c;   above_c = the sum of u_j over them
+ *     score_c (uint64) = BMI_CONFORMAL_LAC:   2^30 - u_c
+ *                        BMI_CONFORMAL_APS:   above_c + u_c                      (RAPS with lam_fix = 0)
+ *                        BMI_CONFORMAL_RAPS:  above_c + u_c + lam_fix * max(0, rank_c + 1 - k_reg);   lam_fix = floor(lambda * 2^30) <= 2^30
+ *     skey_c  = (uint32) min(score_c, 0xFFFFFFFE): saturating; an invalid pair has the one key INVALID, which sorts last
+ *
+ * bmi_conformal_scores writes score_keys[r][n] = skey of the LABEL's class (INVALID for an invalid pair) for n < N; columns >= N are not
+ * touched.  One launch.
+ *
+ * bmi_conformal_quantile reads columns 0 .. N-1 of score_keys.  Per row: n_valid[r] = n = the keys that are not INVALID; per level l,
+ * k = (int64) ceil((double) (n + 1) * coverage[l]) — one rounded product, then the ceiling —; qhat[r][l] = 0xFFFFFFFE when n == 0 or
+ * k > n (every class is then in every set: the calibration set is too small for the level), else the order statistic of rank k - 1
+ * (0-based, ascending unsigned order) of the row's keys, by a radix select: exact under duplicates, no sort.  coverage: HOST float64 [L],
+ * each in (0, 1), read during the call.  One launch, one workgroup per row.
+ *
+ * bmi_conformal_sets: class c is in the set of (r, l, n) iff skey_c <= qhat[r][l] (qhat: DEVICE uint32 [R][L]; an empty set is legal).
+ * Every output OVERWRITTEN (set_size and members in columns 0 .. N-1 only):
+ *     set_size   uint8 [R][L][N_cap]        the members; 255 for an invalid pair
+ *     members    uint32 [R][L][W][N_cap], W = ceil(C / 32), or NULL: bit c % 32 of word c / 32 is set for a member class c; the bits
+ *                beyond C and the words of an invalid pair are 0
+ *     valid      int64 [R]                  the valid images
+ *     covered    int64 [R][L]               the valid images whose label is in the set
+ *     size_sum   int64 [R][L]               the sum of the set sizes
+ *     size_hist  int64 [R][L][C + 1]        the valid images per set size (bin 0: the empty sets)
+ *     cov_hist   int64 [R][L][C + 1]        those of them whose label is in the set: the size-stratified coverage
+ *     class_n    int64 [R][C]               the valid images per label
+ *     class_cov  int64 [R][L][C]            those of them whose label is in the set: the class-conditional coverage
+ * Two launches (one clears the tables, no memset).  Integer atomics only (LDS per tile of 64 images, then global): the same bits on every
+ * run and for every cut of the images into record calls.
+ *
+ * All three: no allocation, no synchronisation: capturable.  BMI_ERR_INVALID (decided before any HIP call): a null pointer other than
+ * members, R / C / N below 1, N > N_cap, a method outside 0 .. 2, k_reg < 0 or lam_fix > 2^30 (checked for every method, used by RAPS alone), L outside [1, BMI_CONFORMAL_MAX_LEVELS], a
+ * coverage level that is not inside (0, 1).  BMI_ERR_UNSUPPORTED: C > 128, R > 64, N >= 2^22.  An error writes nothing. */
+#define BMI_CONFORMAL_LAC 0
+#define BMI_CONFORMAL_APS 1
+#define BMI_CONFORMAL_RAPS 2
+#define BMI_CONFORMAL_MAX_LEVELS 8
+int bmi_conformal_scores(const uint32_t* pkeys, const int32_t* labels_rec, int32_t R, int32_t C, int32_t N, int32_t N_cap, int32_t method,
+                         int32_t k_reg, uint32_t lam_fix, uint32_t* score_keys /*[R][N_cap]*/, bmi_stream stream);
+int bmi_conformal_quantile(const uint32_t* score_keys, int32_t R, int32_t N, int32_t N_cap, const double* coverage /* host [L] */, int32_t L,
+                           uint32_t* qhat /*[R][L]*/, int64_t* n_valid /*[R]*/, bmi_stream stream);
+int bmi_conformal_sets(const uint32_t* pkeys, const int32_t* labels_rec, int32_t R, int32_t C, int32_t N, int32_t N_cap, int32_t method,
+                       int32_t k_reg, uint32_t lam_fix, const uint32_t* qhat /* device [R][L] */, int32_t L, uint8_t* set_size,
+                       uint32_t* members /* or NULL */, int64_t* valid, int64_t* covered, int64_t* size_sum, int64_t* size_hist,
+                       int64_t* cov_hist, int64_t* class_n, int64_t* class_cov, bmi_stream stream);
+
 /* Rank quality of the per-image uncertainty scores: do the wrong predictions — or out-of-distribution inputs — carry the high uncertainty?
  * Per row the stable order of the images by a score key, the risk-coverage curve of selective prediction and the Mann-Whitney count of the
  * AUROC, as exact integers on the device (csrc/ranking.hip; train.ranking.score_keys_numpy / rank_quality_numpy restate both calls).  The
