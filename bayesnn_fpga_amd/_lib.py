@@ -80,6 +80,13 @@ class ModelDesc(C.Structure):
                 ("ops", C.POINTER(OpDesc)), ("n_exits", C.c_int32), ("out_dim", C.c_int32), ("dtype", C.c_int32)]
 
 
+class Lenet5Desc(C.Structure):
+    """bmi_lenet5_desc: the eight weight / bias buffers in the kernel's layouts, the classes, sites A, B, C and the chunk scratch."""
+    _fields_ = [("conv1_w", C.c_void_p), ("conv1_b", C.c_void_p), ("conv2_w_frag", C.c_void_p), ("conv2_b", C.c_void_p),
+                ("fc1_wt", C.c_void_p), ("fc1_b", C.c_void_p), ("fc2_wt", C.c_void_p), ("fc2_b", C.c_void_p), ("out_dim", C.c_int32),
+                ("sites", Site * 3), ("partials", C.c_void_p), ("partials_bytes", C.c_size_t)]
+
+
 class BmiError(RuntimeError):
     def __init__(self, code, what):
         self.code = code
@@ -212,6 +219,9 @@ _PROTOS = {
     "bmi_head_fused_ex": (C.c_int, [C.POINTER(HeadEx), C.c_int32, C.c_void_p]),
     "bmi_dense_f32": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 5 +
                       [C.POINTER(Site), C.c_int32, C.c_int32, C.c_uint64, C.c_int32, C.c_void_p]),
+    "bmi_lenet5_create": (C.c_int, [C.POINTER(Lenet5Desc), C.POINTER(C.c_void_p)]),
+    "bmi_lenet5_destroy": (C.c_int, [C.c_void_p]),
+    "bmi_lenet5_forward_mcd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_uint64] + [C.c_void_p] * 5),
 }
 
 EXPORTS = tuple(_PROTOS.keys())

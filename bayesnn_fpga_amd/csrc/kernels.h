@@ -443,6 +443,30 @@ int xcd_split_for(int n_ctiles, size_t weight_bytes);
 
 SiteArgs resolve_site(const bmi_site* site, uint64_t seed, int mask_cnt0, uint64_t elem_off = 0);
 
+// lenet5.hip: the whole MC-dropout LeNet-5 of one call in one launch (+ the ordered join of the sample chunks' float64 partials)
+struct Lenet5Args {
+    const float* x;          // fp32 [B][1][28][28]
+    const float* w1;         // conv1 fp32 [20][25]
+    const float* b1;
+    const _Float16* w2f;     // conv2 fp16 [76 K-groups][20 channels][8]: k = tap * 24 + channel, group 75 and channels 20..23 zero
+    const float* b2;
+    const float* fc1t;       // fc1 fp32 [80][100] (transposed)
+    const float* fb1;
+    const float* fc2t;       // fc2 fp32 [100][C] (transposed)
+    const float* fb2;
+    int B, C, b0;            // images of the call, classes, index of image 0 in the sites' element spaces
+    int t0, tc;              // first sample, samples
+    int n_chunks, per_chunk; // filled by launch_lenet5 from lenet5_chunks(B, tc)
+    SiteArgs site[3];        // A, B, C (kind BMI_SITE_NONE: off)
+    double* S1;              // float64 [B][C] sums, ADDED to; all three null: logits only
+    double* S2;
+    double* SL;
+    double* part;            // float64 [n_chunks][3][B][C] scratch, read only when n_chunks > 1
+    float* logits;           // fp32 [tc][B][C] or null
+};
+int lenet5_chunks(int batch, int t_count, int* per_chunk);
+int launch_lenet5(Lenet5Args a, hipStream_t s);
+
 #define BMI_CHECK_LAUNCH()                                  \
     do {                                                    \
         hipError_t e__ = hipGetLastError();                 \

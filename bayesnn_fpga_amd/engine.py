@@ -2032,6 +2032,105 @@ class MCDEngine(CompiledGraph):
                      ms=ms[i], flops=fl[i], bytes=by[i]) for i in range(n)]
 
 
+LENET5_CHUNK_IMAGES = 512       # csrc/lenet5.hip:lenet5_chunks — a call runs at most min(T, max(1, 512 // B)) sample chunks
+
+
+class LeNet5Engine:
+    """``models.extra.LeNet5MC`` compiled for one GPU: the whole Monte-Carlo loop of a batch is ONE launch of csrc/lenet5.hip (one
+    workgroup per image, the samples looped inside the kernel), so there are no engine dtypes and no workspace — only the float64
+    scratch of the sample chunks.  The interface is ``MCDEngine``'s where the two overlap: results are device tensors [1, B, C], every
+    call is asynchronous on the current torch stream; the chunk scratch belongs to the engine, so one engine serves ONE stream at a time (a
+    second stream takes a second engine).  Replaces ``FullAnalysis._get_output`` (SA/train/results_analyzer.py:236-248)
+    over the Keras LeNet of Hardware_Artifact/bayes_hw/models/models.py:34-73."""
+    n_exits = 1
+    dtype = "f16"          # (conv2's operands; everything else is fp32 — there is nothing to choose)
+    workspace = None
+
+    def __init__(self, model, device, max_batch=256):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("LeNet5Engine needs a HIP device (torch device type 'cuda' on ROCm); there is no CPU path")
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        self.lib, self.device, self.max_batch, self.out_dim = _lib.lib(), device, int(max_batch), int(model.out_dim)
+        dev = lambda t: t.detach().to(device=device, dtype=torch.float32).contiguous()
+        with torch.no_grad():
+            w2 = torch.zeros(608, 20)                                # [k = tap * 24 + channel][output channel], k >= 600 zero
+            w2[:600].view(25, 24, 20)[:, :20] = model.conv2.weight.detach().float().cpu().permute(2, 3, 1, 0).reshape(25, 20, 20)
+            frag = w2.view(76, 8, 20).permute(0, 2, 1).contiguous().to(device=device, dtype=torch.float16)
+            self._keep = [dev(model.conv1.weight), dev(model.conv1.bias), frag, dev(model.conv2.bias), dev(model.fc1.weight.t()),
+                          dev(model.fc1.bias), dev(model.fc2.weight.t()), dev(model.fc2.bias)]
+        self._partials = torch.empty(3 * max(self.max_batch, LENET5_CHUNK_IMAGES) * self.out_dim, dtype=torch.float64, device=device)
+        desc = _lib.Lenet5Desc(*[t.data_ptr() for t in self._keep], self.out_dim)
+        for i, s in enumerate(model.site_descs()):
+            desc.sites[i] = s
+        desc.partials, desc.partials_bytes = self._partials.data_ptr(), self._partials.numel() * 8
+        self.handle = C.c_void_p()
+        _lib.check(self.lib.bmi_lenet5_create(C.byref(desc), C.byref(self.handle)), "bmi_lenet5_create")
+
+    def close(self):
+        if getattr(self, "handle", None) is not None and self.handle.value:
+            self.lib.bmi_lenet5_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check_x(self, x):
+        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.device == self.device):
+            raise RuntimeError(f"input must live on {self.device}")
+        if x.dtype != torch.float32 or x.dim() != 4 or tuple(x.shape[1:]) != (1, 28, 28):
+            raise ValueError(f"expected float32 [B,1,28,28], got {x.dtype} {tuple(x.shape)}")
+        if not 1 <= x.shape[0] <= self.max_batch:
+            raise ValueError(f"batch {x.shape[0]} outside [1, max_batch = {self.max_batch}]")
+        return x.contiguous()
+
+    def new_moments(self, batch):
+        """Zeroed float64 accumulators S1 = sum p, S2 = sum p^2, SL = sum logit, each [1, B, C]."""
+        return torch.zeros(3, 1, batch, self.out_dim, dtype=torch.float64, device=self.device)
+
+    def _forward(self, x, S, logits, t_begin, t_count, seed):
+        x = self._check_x(x)
+        sums = (None, None, None) if S is None else tuple(S[i].data_ptr() for i in range(3))
+        with torch.cuda.device(self.device):
+            rc = self.lib.bmi_lenet5_forward_mcd(self.handle, x.data_ptr(), x.shape[0], int(t_begin), int(t_count), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                                 *sums, _ptr(logits), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+        _lib.check(rc, "bmi_lenet5_forward_mcd")
+
+    def accumulate(self, x, S, t_begin, t_count, seed=0):
+        """Adds samples t_begin .. t_begin+t_count-1 of batch ``x`` into the moment buffer ``S`` (``new_moments``)."""
+        check_buffer(S, (3, 1, x.shape[0], self.out_dim), torch.float64, self.device, "moment buffer S")
+        self._forward(x, S, None, t_begin, t_count, seed)
+        return S
+
+    def finalize(self, S, t_total):
+        """mean / var (ddof=0) / mean logit, float64 [1, B, C] each (bmi_finalize)."""
+        out = torch.empty_like(S)
+        with torch.cuda.device(self.device):
+            rc = self.lib.bmi_finalize(S[0].numel(), int(t_total), S[0].data_ptr(), S[1].data_ptr(), S[2].data_ptr(), out[0].data_ptr(),
+                                       out[1].data_ptr(), out[2].data_ptr(), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+        _lib.check(rc, "bmi_finalize")
+        return dict(mean=out[0], var=out[1], logit_mean=out[2])
+
+    def predict(self, x, T, seed=0, t_begin=0):
+        return self.finalize(self.accumulate(x, self.new_moments(x.shape[0]), t_begin, T, seed), T)
+
+    def forward_samples(self, x, T, seed=0, t_begin=0, out=None):
+        """Per-sample logits fp32 [T, 1, B, C]: what T calls of ``model(x)`` return, from one launch."""
+        shape = (int(T), 1, x.shape[0], self.out_dim)
+        out = torch.empty(shape, dtype=torch.float32, device=self.device) if out is None else \
+            check_buffer(out, shape, torch.float32, self.device, "out [T, 1, B, C]")
+        self._forward(x, None, out, t_begin, T, seed)
+        return out
+
+    def forward_once(self, x, seed=0, t=0, cnt0=0):
+        """One stochastic pass -> [fp32 logits [B, C]] (``cnt0``: the Masksembles counter of the other engines; there are no such sites here)."""
+        return [self.forward_samples(x, 1, seed=seed, t_begin=t)[0, 0]]
+
+
 class BatchesInFlight:
     """`n` independent engines of one model (own workspace, own device copy of the weights) on `n` streams: consecutive batches
     alternate between them, so the launch-bound once-per-batch prefix of batch k+1 (five ~50 us launches on B images) runs

@@ -9,7 +9,9 @@
   Bottleneck network fail in ``ex1conv1``).
 Parity for these is pinned against the fp32 CPU restatement in ``oracle/extra_models.py`` only.  Dense layers run
 as 1x1 convolutions on [N,1,1,C] tensors (same MFMA kernel, same fused dropout epilogue).
-LeNet-5 (config 1) is "CPU plumbing, no GPU" in BASELINE and is not on the accelerated path.
+* ``LeNet5MC``            — config 1, Hardware_Artifact/bayes_hw/models/models.py:34-73 (``lenet``; the counter rule over its 3 candidate
+  sites).  Its 5x5 convs on 1 and 20 channels, 7x7 pool and 80 -> 100 -> C dense layers lie outside the graph engine's kernels: it runs
+  as ONE fused kernel per call (csrc/lenet5.hip) behind ``engine.LeNet5Engine``, not through ``MCDEngine``.
 """
 import math
 
@@ -97,6 +99,47 @@ class VGG11MC(EngineModelMixin, nn.Module):
             else:                                                       # final classifier
                 g.head(x, m, 0, site=g.site(pending))
                 i += 1
+
+
+class LeNet5MC(EngineModelMixin, nn.Module):
+    """MC-dropout LeNet-5 on 28x28x1 inputs.  Candidate sites A (behind the first pool), B (behind flatten), C (behind fc1 + ReLU);
+    ``num_bayes_layer = k`` switches on the last k (models.py:36-68 with num_layers = 3); k = 1 is the oracle's ``LeNet5MC``.  Sites are
+    elementwise, numbered 0, 1, ... in call order over those that are on."""
+    family = "lenet5"
+    multi_exit = False
+    engine_dtype = "f16"
+
+    def __init__(self, num_bayes_layer=1, dropout_p=0.2, out_dim=10):
+        super().__init__()
+        if num_bayes_layer not in (0, 1, 2, 3):
+            raise ValueError("num_bayes_layer must be 0, 1, 2 or 3")
+        self.n_exits, self.out_dim, self.dropout_p, self.num_bayes_layer = 1, out_dim, dropout_p, num_bayes_layer
+        self.conv1 = nn.Conv2d(1, 20, 5, padding=2)
+        self.conv2 = nn.Conv2d(20, 20, 5, padding=2)
+        self.fc1 = nn.Linear(80, 100)
+        for loc, name in enumerate(("drop_a", "drop_b", "drop")):      # ("drop": the oracle's name for site C)
+            if loc >= 3 - num_bayes_layer:
+                setattr(self, name, MCDropout(dropout_p))
+        self.fc2 = nn.Linear(100, out_dim)
+        self._init_engine_state()
+
+    def site_descs(self):
+        """The three ``_lib.Site`` of bmi_lenet5_desc, A, B, C: off, or elementwise with the module's p and its call-order id."""
+        from .. import _lib
+        mods = [getattr(self, name, None) for name in ("drop_a", "drop_b", "drop")]
+        ids = iter(range(3))
+        return [_lib.make_site() if m is None else _lib.make_site(_lib.SITE_ELEMENTWISE, next(ids), m.p) for m in mods]
+
+    def engine(self, device, max_batch=None, **_):
+        """The compiled ``engine.LeNet5Engine`` for ``device`` (built on first use, rebuilt when it must grow)."""
+        from ..engine import LeNet5Engine
+        key, need = str(device), max_batch or 1
+        eng = self._engines.get(key)
+        if eng is None or eng.max_batch < need:
+            if eng is not None:
+                eng.close()
+            eng = self._engines[key] = LeNet5Engine(self, device, max_batch=max(need, eng.max_batch if eng else 0))
+        return eng
 
 
 class Bottleneck(nn.Module):

@@ -1289,6 +1289,58 @@ int bmi_dense_f32(const void* in, int32_t in_is_f32 /* 0: 16-bit (unit_entry_dty
                   int32_t in_mod, int32_t k, int32_t cout, int32_t relu, const bmi_site* site, int32_t batch, int32_t t0,
                   uint64_t seed, int32_t mask_cnt0, bmi_stream stream);
 
+/* MC-dropout LeNet-5 on 28x28x1 inputs (BASELINE config 1) as ONE fused kernel per call (csrc/lenet5.hip): one workgroup per image
+ * computes the deterministic part once into LDS and loops over its Monte-Carlo samples inside the kernel.  The network is the Keras
+ * model of the reference's hardware flow, Hardware_Artifact/bayes_hw/models/models.py:34-73 (`lenet`, model_num_layer 3): conv 5x5x20
+ * same + ReLU, max-pool 2, [site A], conv 5x5x20 same + ReLU, max-pool 7, flatten in NCHW order j = c * 4 + y * 2 + x, [site B],
+ * Dense 100 + ReLU, [site C], Dense C; its counter rule (:36-68) switches on the LAST num_bayes_layer of the three candidate sites.
+ * Its shapes (1 and 20 channels, 5x5 taps, a 7x7 pool, 80 -> 100 -> C dense layers) lie outside what bmi_create takes.
+ *
+ * The descriptor holds DEVICE pointers the caller owns and keeps alive, already in the kernel's layouts:
+ *   conv1_w       fp32 [20][5][5] (torch's [20][1][5][5]), conv1_b fp32 [20]
+ *   conv2_w_frag  fp16 [76][20][8]: element [g][n][i] = weight of output channel n at k = 8 g + i, k = (ky * 5 + kx) * 24 + c for input
+ *                 channel c < 20; zero for c >= 20 and for k >= 600 — an MFMA fragment is one 16-byte read.  conv2_b fp32 [20]
+ *   fc1_wt        fp32 [80][100], the TRANSPOSE of torch's fc1.weight; fc1_b fp32 [100]
+ *   fc2_wt        fp32 [100][out_dim], the transpose of fc2.weight; fc2_b fp32 [out_dim]
+ *   sites         A, B, C in this order; kind BMI_SITE_NONE = off, else BMI_SITE_ELEMENTWISE with p in [0, 1) and site_id = the call-order
+ *                 index among the sites that are on.  Element index over the call's whole batch: A ((b * 14 + y) * 14 + x) * 20 + c,
+ *                 B b * 80 + j, C b * 100 + j (csrc/philox.h)
+ *   partials      float64 scratch for the sample chunks of a call, partials_bytes >= 3 * max(batch, 512) * out_dim * 8 for the largest
+ *                 batch (a call splits its samples into AT MOST min(t_count, max(1, 512 / batch)) chunks — the samples per chunk are
+ *                 rounded up and the count follows from them, t_count = 10 with a bound of 6 runs five chunks of 2: a function of
+ *                 (batch, t_count) alone).  The scratch belongs to the handle: ONE stream per handle at a time — two calls on one handle
+ *                 from different streams race on it whenever a call has more than one chunk (one handle per stream instead)
+ * Create and destroy are host-only.  BMI_ERR_UNSUPPORTED: out_dim outside [2, 32], a channelwise or Masksembles site;
+ * BMI_ERR_INVALID: a NULL pointer, p outside [0, 1), an unknown site kind. */
+typedef struct bmi_lenet5_desc {
+    const float* conv1_w;
+    const float* conv1_b;
+    const void* conv2_w_frag;
+    const float* conv2_b;
+    const float* fc1_wt;
+    const float* fc1_b;
+    const float* fc2_wt;
+    const float* fc2_b;
+    int32_t out_dim;
+    bmi_site sites[3];
+    void* partials;
+    size_t partials_bytes;
+} bmi_lenet5_desc;
+typedef struct bmi_lenet5_s* bmi_lenet5_handle;
+
+int bmi_lenet5_create(const bmi_lenet5_desc* desc, bmi_lenet5_handle* out);
+int bmi_lenet5_destroy(bmi_lenet5_handle h);
+
+/* Samples t_begin .. t_begin+t_count-1 of x_nchw (device fp32 [batch][1][28][28]): the T-pass loop of FullAnalysis._get_output
+ * (SA/train/results_analyzer.py:236-248) over the model above.  ADDS into S1 / S2 / SL (device float64 [1][batch][out_dim], the contract
+ * of bmi_forward_mcd; bmi_finalize reads them out) the sums of softmax p, p * p and the logits, every image's samples in ascending t
+ * (chunk sums joined in chunk order, no floating-point atomics); `logits` (device fp32 [t_count][1][batch][out_dim], or NULL) receives
+ * every sample's logits.  S1 / S2 / SL may be NULL together when `logits` is given.  A sample's logits depend on (seed, t, image)
+ * alone.  Asynchronous on `stream`, no allocation: captures into a hipGraph.  Calls on one handle must be ordered on ONE stream (they
+ * share the descriptor's `partials`).  BMI_ERR_NOMEM: `partials` too small for this batch. */
+int bmi_lenet5_forward_mcd(bmi_lenet5_handle h, const float* x_nchw, int32_t batch, int32_t t_begin, int32_t t_count, uint64_t seed,
+                           double* S1, double* S2, double* SL, float* logits, bmi_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,69 @@
+"""BASELINE config 1 on the device: MC-dropout LeNet-5, T = 10, device-resident input to final mean and variance
+(``LeNet5Engine.predict``), beside the oracle's ``mcd_predict`` on the host CPU.  Prints one JSON line per (num_bayes_layer, batch).
+
+    python tools/lenet_bench.py [--iters 30] [--warmup 5] [--cpu-iters 3]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import torch  # noqa: E402
+
+from bayesnn_fpga_amd.models import extra as bx  # noqa: E402
+from bayesnn_fpga_amd.synthetic import synthetic_images, synthetic_weights_  # noqa: E402
+from oracle import extra_models as ox  # noqa: E402
+from oracle import mcd  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=30)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--cpu-iters", type=int, default=3)
+    ap.add_argument("--T", type=int, default=10)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("lenet_bench needs a GPU: there is no CPU path to time")
+    dev = torch.device("cuda:0")
+    for k in (1, 3):
+        for B in (250, 1024):
+            torch.manual_seed(0)
+            m = synthetic_weights_(bx.LeNet5MC(num_bayes_layer=k, dropout_p=0.25), 0).to(dev).eval()
+            x = synthetic_images(B, 1234, channels=1, size=28).to(dev)
+            eng = m.engine(dev, max_batch=B)
+            for _ in range(a.warmup):
+                eng.predict(x, a.T, seed=1)
+            torch.cuda.synchronize()
+            us = []
+            for _ in range(a.iters):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                eng.predict(x, a.T, seed=1)
+                e1.record()
+                e1.synchronize()
+                us.append(e0.elapsed_time(e1) * 1e3)
+            med = statistics.median(us)
+            row = dict(num_bayes_layer=k, batch=B, T=a.T, us_per_call=round(med, 1), us_min=round(min(us), 1), us_max=round(max(us), 1),
+                       mcd_samples_per_s=round(B * a.T / med * 1e6), iters=a.iters, device=torch.cuda.get_device_name(0))
+            if k == 1 and a.cpu_iters:      # the oracle has site C only
+                torch.manual_seed(0)
+                o = synthetic_weights_(ox.LeNet5MC(dropout_p=0.25), 0)
+                xc = x.cpu()
+                mcd.mcd_predict(o, xc, a.T, 1)
+                ts = []
+                for _ in range(a.cpu_iters):
+                    t0 = time.perf_counter()
+                    mcd.mcd_predict(o, xc, a.T, 1)
+                    ts.append(time.perf_counter() - t0)
+                row.update(cpu_oracle_us_per_call=round(statistics.median(ts) * 1e6), cpu_oracle_samples_per_s=round(B * a.T / statistics.median(ts)),
+                           cpu_threads=torch.get_num_threads(), cpu_cores=os.cpu_count())
+            print(json.dumps(row), flush=True)
+
+
+if __name__ == "__main__":
+    main()
