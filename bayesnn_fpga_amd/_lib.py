@@ -87,6 +87,13 @@ class Lenet5Desc(C.Structure):
                 ("sites", Site * 3), ("partials", C.c_void_p), ("partials_bytes", C.c_size_t)]
 
 
+class Lenet5MeDesc(C.Structure):
+    """bmi_lenet5_me_desc: the trunk's eight buffers, the early exit's six, the classes and the two exits' sites (early, main)."""
+    _fields_ = [(n, C.c_void_p) for n in ("conv1_w", "conv1_b", "conv2_w_frag", "conv2_b", "fc1_wt", "fc1_b", "fc2_wt", "fc2_b", "ex1conv1_w_frag",
+                                          "ex1conv1_b", "ex1fc1_wt", "ex1fc1_b", "ex1linear_wt", "ex1linear_b")] + \
+               [("out_dim", C.c_int32), ("sites", Site * 2)]
+
+
 class BmiError(RuntimeError):
     def __init__(self, code, what):
         self.code = code
@@ -222,6 +229,9 @@ _PROTOS = {
     "bmi_lenet5_create": (C.c_int, [C.POINTER(Lenet5Desc), C.POINTER(C.c_void_p)]),
     "bmi_lenet5_destroy": (C.c_int, [C.c_void_p]),
     "bmi_lenet5_forward_mcd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_uint64] + [C.c_void_p] * 5),
+    "bmi_lenet5_me_create": (C.c_int, [C.POINTER(Lenet5MeDesc), C.POINTER(C.c_void_p)]),
+    "bmi_lenet5_me_destroy": (C.c_int, [C.c_void_p]),
+    "bmi_lenet5_me_forward_mcd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_uint64] + [C.c_void_p] * 5),
 }
 
 EXPORTS = tuple(_PROTOS.keys())

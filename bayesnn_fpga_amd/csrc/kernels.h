@@ -467,6 +467,33 @@ struct Lenet5Args {
 int lenet5_chunks(int batch, int t_count, int* per_chunk);
 int launch_lenet5(Lenet5Args a, hipStream_t s);
 
+// lenet5_me.hip: the multi-exit MC-dropout LeNet-5 of one call in one launch, grid = images; exit 0 = the early exit, exit 1 = the main exit
+struct Lenet5MeArgs {
+    const float* x;          // fp32 [B][1][28][28]
+    const float* w1;         // trunk: as Lenet5Args
+    const float* b1;
+    const _Float16* w2f;
+    const float* b2;
+    const float* fc1t;
+    const float* fb1;
+    const float* fc2t;
+    const float* fb2;
+    const _Float16* ewf;     // ex1conv1 fp16 [76][20][8], conv2's fragment layout
+    const float* eb;         // ex1conv1 bias [20]
+    const float* efc1t;      // ex1fc1 fp32 [80][100] (transposed)
+    const float* efb1;
+    const float* elint;      // ex1linear fp32 [100][C] (transposed)
+    const float* elinb;
+    int B, C;
+    int t0, tc;              // first sample, samples
+    SiteArgs site[2];        // on the 100 hidden units in front of exit 0 / exit 1 (kind BMI_SITE_NONE: off)
+    double* S1;              // float64 [2][B][C] sums, ADDED to; all three null: logits only
+    double* S2;
+    double* SL;
+    float* logits;           // fp32 [tc][2][B][C] or null
+};
+int launch_lenet5_me(const Lenet5MeArgs& a, hipStream_t s);
+
 #define BMI_CHECK_LAUNCH()                                  \
     do {                                                    \
         hipError_t e__ = hipGetLastError();                 \

@@ -2036,14 +2036,15 @@ LENET5_CHUNK_IMAGES = 512       # csrc/lenet5.hip:lenet5_chunks — a call runs 
 
 
 class LeNet5Engine:
-    """``models.extra.LeNet5MC`` compiled for one GPU: the whole Monte-Carlo loop of a batch is ONE launch of csrc/lenet5.hip (one
-    workgroup per image, the samples looped inside the kernel), so there are no engine dtypes and no workspace — only the float64
-    scratch of the sample chunks.  The interface is ``MCDEngine``'s where the two overlap: results are device tensors [1, B, C], every
-    call is asynchronous on the current torch stream; the chunk scratch belongs to the engine, so one engine serves ONE stream at a time (a
-    second stream takes a second engine).  Replaces ``FullAnalysis._get_output`` (SA/train/results_analyzer.py:236-248)
-    over the Keras LeNet of Hardware_Artifact/bayes_hw/models/models.py:34-73."""
-    n_exits = 1
-    dtype = "f16"          # (conv2's operands; everything else is fp32 — there is nothing to choose)
+    """``models.extra.LeNet5MC`` or ``LeNet5MCEarlyExit`` compiled for one GPU: the whole Monte-Carlo loop of a batch is ONE launch of
+    csrc/lenet5.hip / csrc/lenet5_me.hip (one workgroup per image, the samples looped inside the kernel), so there are no engine dtypes and
+    no workspace.  The interface is ``MCDEngine``'s where the two overlap: results are device tensors [E, B, C] (E = 1, or 2 for the
+    multi-exit model: early exit, main exit), every call is asynchronous on the current torch stream.  The single-exit kernel splits small
+    batches into sample chunks whose float64 scratch belongs to the engine, so such an engine serves ONE stream at a time (a second stream
+    takes a second engine); the multi-exit kernel has no scratch.  Replaces ``FullAnalysis._get_output``
+    (SA/train/results_analyzer.py:236-248) over the Keras LeNet of Hardware_Artifact/bayes_hw/models/models.py:34-73 and over
+    T_Qlenet_bayes_me of Hardware_Artifact/bayes_hw/models/t_qmodels_bayes_me.py:41-147."""
+    dtype = "f16"          # (the convs' MFMA operands; everything else is fp32 — there is nothing to choose)
     workspace = None
 
     def __init__(self, model, device, max_batch=256):
@@ -2053,24 +2054,33 @@ class LeNet5Engine:
         if device.index is None:
             device = torch.device("cuda", torch.cuda.current_device())
         self.lib, self.device, self.max_batch, self.out_dim = _lib.lib(), device, int(max_batch), int(model.out_dim)
+        self.n_exits = int(model.n_exits)
+        self._abi = "bmi_lenet5_me" if self.n_exits == 2 else "bmi_lenet5"
         dev = lambda t: t.detach().to(device=device, dtype=torch.float32).contiguous()
+
+        def frag(conv):                                              # a 20 -> 20 5x5 conv as MFMA fragments fp16 [76][20][8]
+            w = torch.zeros(608, 20)                                 # [k = tap * 24 + channel][output channel], k >= 600 zero
+            w[:600].view(25, 24, 20)[:, :20] = conv.weight.detach().float().cpu().permute(2, 3, 1, 0).reshape(25, 20, 20)
+            return w.view(76, 8, 20).permute(0, 2, 1).contiguous().to(device=device, dtype=torch.float16)
+
         with torch.no_grad():
-            w2 = torch.zeros(608, 20)                                # [k = tap * 24 + channel][output channel], k >= 600 zero
-            w2[:600].view(25, 24, 20)[:, :20] = model.conv2.weight.detach().float().cpu().permute(2, 3, 1, 0).reshape(25, 20, 20)
-            frag = w2.view(76, 8, 20).permute(0, 2, 1).contiguous().to(device=device, dtype=torch.float16)
-            self._keep = [dev(model.conv1.weight), dev(model.conv1.bias), frag, dev(model.conv2.bias), dev(model.fc1.weight.t()),
+            self._keep = [dev(model.conv1.weight), dev(model.conv1.bias), frag(model.conv2), dev(model.conv2.bias), dev(model.fc1.weight.t()),
                           dev(model.fc1.bias), dev(model.fc2.weight.t()), dev(model.fc2.bias)]
-        self._partials = torch.empty(3 * max(self.max_batch, LENET5_CHUNK_IMAGES) * self.out_dim, dtype=torch.float64, device=device)
-        desc = _lib.Lenet5Desc(*[t.data_ptr() for t in self._keep], self.out_dim)
+            if self.n_exits == 2:
+                self._keep += [frag(model.ex1conv1), dev(model.ex1conv1.bias), dev(model.ex1fc1.weight.t()), dev(model.ex1fc1.bias),
+                               dev(model.ex1linear.weight.t()), dev(model.ex1linear.bias)]
+        desc = (_lib.Lenet5MeDesc if self.n_exits == 2 else _lib.Lenet5Desc)(*[t.data_ptr() for t in self._keep], self.out_dim)
         for i, s in enumerate(model.site_descs()):
             desc.sites[i] = s
-        desc.partials, desc.partials_bytes = self._partials.data_ptr(), self._partials.numel() * 8
+        if self.n_exits == 1:
+            self._partials = torch.empty(3 * max(self.max_batch, LENET5_CHUNK_IMAGES) * self.out_dim, dtype=torch.float64, device=device)
+            desc.partials, desc.partials_bytes = self._partials.data_ptr(), self._partials.numel() * 8
         self.handle = C.c_void_p()
-        _lib.check(self.lib.bmi_lenet5_create(C.byref(desc), C.byref(self.handle)), "bmi_lenet5_create")
+        _lib.check(getattr(self.lib, self._abi + "_create")(C.byref(desc), C.byref(self.handle)), self._abi + "_create")
 
     def close(self):
         if getattr(self, "handle", None) is not None and self.handle.value:
-            self.lib.bmi_lenet5_destroy(self.handle)
+            getattr(self.lib, self._abi + "_destroy")(self.handle)
             self.handle = C.c_void_p()
 
     def __del__(self):
@@ -2089,25 +2099,26 @@ class LeNet5Engine:
         return x.contiguous()
 
     def new_moments(self, batch):
-        """Zeroed float64 accumulators S1 = sum p, S2 = sum p^2, SL = sum logit, each [1, B, C]."""
-        return torch.zeros(3, 1, batch, self.out_dim, dtype=torch.float64, device=self.device)
+        """Zeroed float64 accumulators S1 = sum p, S2 = sum p^2, SL = sum logit, each [E, B, C]."""
+        return torch.zeros(3, self.n_exits, batch, self.out_dim, dtype=torch.float64, device=self.device)
 
     def _forward(self, x, S, logits, t_begin, t_count, seed):
         x = self._check_x(x)
         sums = (None, None, None) if S is None else tuple(S[i].data_ptr() for i in range(3))
         with torch.cuda.device(self.device):
-            rc = self.lib.bmi_lenet5_forward_mcd(self.handle, x.data_ptr(), x.shape[0], int(t_begin), int(t_count), int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                                 *sums, _ptr(logits), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
-        _lib.check(rc, "bmi_lenet5_forward_mcd")
+            rc = getattr(self.lib, self._abi + "_forward_mcd")(self.handle, x.data_ptr(), x.shape[0], int(t_begin), int(t_count),
+                                                               int(seed) & 0xFFFFFFFFFFFFFFFF, *sums, _ptr(logits),
+                                                               C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+        _lib.check(rc, self._abi + "_forward_mcd")
 
     def accumulate(self, x, S, t_begin, t_count, seed=0):
         """Adds samples t_begin .. t_begin+t_count-1 of batch ``x`` into the moment buffer ``S`` (``new_moments``)."""
-        check_buffer(S, (3, 1, x.shape[0], self.out_dim), torch.float64, self.device, "moment buffer S")
+        check_buffer(S, (3, self.n_exits, x.shape[0], self.out_dim), torch.float64, self.device, "moment buffer S")
         self._forward(x, S, None, t_begin, t_count, seed)
         return S
 
     def finalize(self, S, t_total):
-        """mean / var (ddof=0) / mean logit, float64 [1, B, C] each (bmi_finalize)."""
+        """mean / var (ddof=0) / mean logit, float64 [E, B, C] each (bmi_finalize)."""
         out = torch.empty_like(S)
         with torch.cuda.device(self.device):
             rc = self.lib.bmi_finalize(S[0].numel(), int(t_total), S[0].data_ptr(), S[1].data_ptr(), S[2].data_ptr(), out[0].data_ptr(),
@@ -2119,16 +2130,17 @@ class LeNet5Engine:
         return self.finalize(self.accumulate(x, self.new_moments(x.shape[0]), t_begin, T, seed), T)
 
     def forward_samples(self, x, T, seed=0, t_begin=0, out=None):
-        """Per-sample logits fp32 [T, 1, B, C]: what T calls of ``model(x)`` return, from one launch."""
-        shape = (int(T), 1, x.shape[0], self.out_dim)
+        """Per-sample logits fp32 [T, E, B, C]: what T calls of ``model(x)`` return, from one launch."""
+        shape = (int(T), self.n_exits, x.shape[0], self.out_dim)
         out = torch.empty(shape, dtype=torch.float32, device=self.device) if out is None else \
-            check_buffer(out, shape, torch.float32, self.device, "out [T, 1, B, C]")
+            check_buffer(out, shape, torch.float32, self.device, "out [T, E, B, C]")
         self._forward(x, None, out, t_begin, T, seed)
         return out
 
     def forward_once(self, x, seed=0, t=0, cnt0=0):
-        """One stochastic pass -> [fp32 logits [B, C]] (``cnt0``: the Masksembles counter of the other engines; there are no such sites here)."""
-        return [self.forward_samples(x, 1, seed=seed, t_begin=t)[0, 0]]
+        """One stochastic pass -> the E exits' fp32 logits [B, C], in depth order (``cnt0``: the Masksembles counter of the other engines; there
+        are no such sites here)."""
+        return list(self.forward_samples(x, 1, seed=seed, t_begin=t)[0])
 
 
 class BatchesInFlight:

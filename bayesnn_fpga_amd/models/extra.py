@@ -12,6 +12,9 @@ as 1x1 convolutions on [N,1,1,C] tensors (same MFMA kernel, same fused dropout e
 * ``LeNet5MC``            — config 1, Hardware_Artifact/bayes_hw/models/models.py:34-73 (``lenet``; the counter rule over its 3 candidate
   sites).  Its 5x5 convs on 1 and 20 channels, 7x7 pool and 80 -> 100 -> C dense layers lie outside the graph engine's kernels: it runs
   as ONE fused kernel per call (csrc/lenet5.hip) behind ``engine.LeNet5Engine``, not through ``MCDEngine``.
+* ``LeNet5MCEarlyExit``   — the multi-exit form of that LeNet, Hardware_Artifact/bayes_hw/models/t_qmodels_bayes_me.py:41-147
+  (``T_Qlenet_bayes_me``): an early exit on the pooled conv1 map and one MC-dropout layer in front of each exit's classifier; ONE fused
+  kernel per call as well (csrc/lenet5_me.hip), behind the same ``engine.LeNet5Engine``.
 """
 import math
 
@@ -140,6 +143,40 @@ class LeNet5MC(EngineModelMixin, nn.Module):
                 eng.close()
             eng = self._engines[key] = LeNet5Engine(self, device, max_batch=max(need, eng.max_batch if eng else 0))
         return eng
+
+
+class LeNet5MCEarlyExit(EngineModelMixin, nn.Module):
+    """Multi-exit MC-dropout LeNet-5 on 28x28x1 inputs: ``LeNet5MC``'s trunk under the same parameter names plus an early exit on the
+    pooled conv1 map [B, 20, 14, 14] — conv 5x5x20 with stride 7 (Keras "same" at stride 7 on a 14-wide map pads nothing: outputs 2x2),
+    ReLU, flatten, Linear 80 -> 100, ReLU, Linear 100 -> C.  ``dropout_exit`` puts one elementwise MC-dropout layer on the 100 hidden units
+    in front of each exit's classifier.  Exits in depth order: exit 0 is the early exit, exit 1 (the last) the main exit; site ids follow
+    that call order."""
+    family = "lenet5_me"
+    multi_exit = True
+    engine_dtype = "f16"
+
+    def __init__(self, dropout_exit=True, dropout_p=0.2, out_dim=10):
+        super().__init__()
+        self.n_exits, self.out_dim, self.dropout_p, self.dropout_exit = 2, out_dim, dropout_p, dropout_exit
+        self.conv1 = nn.Conv2d(1, 20, 5, padding=2)
+        self.conv2 = nn.Conv2d(20, 20, 5, padding=2)
+        self.fc1 = nn.Linear(80, 100)
+        self.fc2 = nn.Linear(100, out_dim)
+        self.ex1conv1 = nn.Conv2d(20, 20, 5, stride=7, padding=0)
+        self.ex1fc1 = nn.Linear(80, 100)
+        self.ex1linear = nn.Linear(100, out_dim)
+        if dropout_exit:
+            self.exit1_dropout = MCDropout(dropout_p)
+            self.exit_dropout = MCDropout(dropout_p)
+        self._init_engine_state()
+
+    def site_descs(self):
+        """The two ``_lib.Site`` of bmi_lenet5_me_desc, early exit then main exit: off, or elementwise with the module's p and its call-order id."""
+        from .. import _lib
+        mods = [getattr(self, name, None) for name in ("exit1_dropout", "exit_dropout")]
+        return [_lib.make_site() if m is None else _lib.make_site(_lib.SITE_ELEMENTWISE, i, m.p) for i, m in enumerate(mods)]
+
+    engine = LeNet5MC.engine
 
 
 class Bottleneck(nn.Module):

@@ -1341,6 +1341,52 @@ int bmi_lenet5_destroy(bmi_lenet5_handle h);
 int bmi_lenet5_forward_mcd(bmi_lenet5_handle h, const float* x_nchw, int32_t batch, int32_t t_begin, int32_t t_count, uint64_t seed,
                            double* S1, double* S2, double* SL, float* logits, bmi_stream stream);
 
+/* The multi-exit form of that LeNet as ONE fused kernel per call (csrc/lenet5_me.hip): T_Qlenet_bayes_me of the reference's hardware flow,
+ * Hardware_Artifact/bayes_hw/models/t_qmodels_bayes_me.py:41-147.  The trunk is the LeNet above without its sites A and B; an early exit
+ * reads the pooled conv1 map [20][14][14]: conv 5x5x20 stride 7 without padding (outputs 2x2) + ReLU, flatten j = c * 4 + y * 2 + x,
+ * Dense 100 + ReLU, [site 0], Dense C; the main exit keeps [site 1] in front of its Dense C.  Exits are numbered in depth order: exit 0 is
+ * the early exit, exit 1 the main exit.  One workgroup per image runs the deterministic part once and all t_count samples of the call: no
+ * sample chunks, no scratch, any number of streams per handle.
+ *
+ * The descriptor holds the trunk's eight DEVICE buffers in the layouts of bmi_lenet5_desc and the branch's six:
+ *   ex1conv1_w_frag  fp16 [76][20][8], conv2_w_frag's layout over ex1conv1's [20][20][5][5] weights; ex1conv1_b fp32 [20]
+ *   ex1fc1_wt        fp32 [80][100], the transpose of ex1fc1.weight; ex1fc1_b fp32 [100]
+ *   ex1linear_wt     fp32 [100][out_dim], the transpose of ex1linear.weight; ex1linear_b fp32 [out_dim]
+ *   sites            [0] in front of the early exit's classifier, [1] in front of the main exit's: BMI_SITE_NONE = off, else
+ *                    BMI_SITE_ELEMENTWISE with p in [0, 1) on the 100 hidden units, element b * 100 + j (csrc/philox.h)
+ * Create and destroy are host-only and refuse what bmi_lenet5_create refuses: BMI_ERR_UNSUPPORTED for out_dim outside [2, 32] and for a
+ * channelwise or Masksembles site; BMI_ERR_INVALID for a NULL pointer, p outside [0, 1), a negative site id, an unknown site kind. */
+typedef struct bmi_lenet5_me_desc {
+    const float* conv1_w;
+    const float* conv1_b;
+    const void* conv2_w_frag;
+    const float* conv2_b;
+    const float* fc1_wt;
+    const float* fc1_b;
+    const float* fc2_wt;
+    const float* fc2_b;
+    const void* ex1conv1_w_frag;
+    const float* ex1conv1_b;
+    const float* ex1fc1_wt;
+    const float* ex1fc1_b;
+    const float* ex1linear_wt;
+    const float* ex1linear_b;
+    int32_t out_dim;
+    bmi_site sites[2];
+} bmi_lenet5_me_desc;
+typedef struct bmi_lenet5_me_s* bmi_lenet5_me_handle;
+
+int bmi_lenet5_me_create(const bmi_lenet5_me_desc* desc, bmi_lenet5_me_handle* out);
+int bmi_lenet5_me_destroy(bmi_lenet5_me_handle h);
+
+/* Samples t_begin .. t_begin+t_count-1 of x_nchw (device fp32 [batch][1][28][28]).  ADDS into S1 / S2 / SL (device float64
+ * [2][batch][out_dim]) the sums of softmax p, p * p and the logits of both exits: per image and exit the samples of even index in the call
+ * in ascending t, the samples of odd index in ascending t, then the two sums (no floating-point atomics); `logits` (device fp32
+ * [t_count][2][batch][out_dim], or NULL) receives every sample's logits.  S1 / S2 / SL may be NULL together when `logits` is given.  A
+ * sample's logits depend on (seed, t, image) alone.  Asynchronous on `stream`, one launch, no allocation: captures into a hipGraph. */
+int bmi_lenet5_me_forward_mcd(bmi_lenet5_me_handle h, const float* x_nchw, int32_t batch, int32_t t_begin, int32_t t_count, uint64_t seed,
+                              double* S1, double* S2, double* SL, float* logits, bmi_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

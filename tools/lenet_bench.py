@@ -1,5 +1,6 @@
 """BASELINE config 1 on the device: MC-dropout LeNet-5, T = 10, device-resident input to final mean and variance
-(``LeNet5Engine.predict``), beside the oracle's ``mcd_predict`` on the host CPU.  Prints one JSON line per (num_bayes_layer, batch).
+(``LeNet5Engine.predict``), beside the oracle's ``mcd_predict`` on the host CPU.  Prints one JSON line per (num_bayes_layer, batch), then
+one per batch for the multi-exit model ``LeNet5MCEarlyExit`` (model = "lenet5_me": both exits' moments from one launch).
 
     python tools/lenet_bench.py [--iters 30] [--warmup 5] [--cpu-iters 3]
 """
@@ -30,10 +31,11 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("lenet_bench needs a GPU: there is no CPU path to time")
     dev = torch.device("cuda:0")
-    for k in (1, 3):
+    for k in (1, 3, "me"):
         for B in (250, 1024):
             torch.manual_seed(0)
-            m = synthetic_weights_(bx.LeNet5MC(num_bayes_layer=k, dropout_p=0.25), 0).to(dev).eval()
+            m = bx.LeNet5MCEarlyExit(dropout_p=0.25) if k == "me" else bx.LeNet5MC(num_bayes_layer=k, dropout_p=0.25)
+            m = synthetic_weights_(m, 0).to(dev).eval()
             x = synthetic_images(B, 1234, channels=1, size=28).to(dev)
             eng = m.engine(dev, max_batch=B)
             for _ in range(a.warmup):
@@ -48,7 +50,7 @@ def main():
                 e1.synchronize()
                 us.append(e0.elapsed_time(e1) * 1e3)
             med = statistics.median(us)
-            row = dict(num_bayes_layer=k, batch=B, T=a.T, us_per_call=round(med, 1), us_min=round(min(us), 1), us_max=round(max(us), 1),
+            row = dict(model=m.family, num_bayes_layer=2 if k == "me" else k, batch=B, T=a.T, us_per_call=round(med, 1), us_min=round(min(us), 1), us_max=round(max(us), 1),
                        mcd_samples_per_s=round(B * a.T / med * 1e6), iters=a.iters, device=torch.cuda.get_device_name(0))
             if k == 1 and a.cpu_iters:      # the oracle has site C only
                 torch.manual_seed(0)
