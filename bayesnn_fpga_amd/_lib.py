@@ -232,6 +232,7 @@ _PROTOS = {
     "bmi_lenet5_me_create": (C.c_int, [C.POINTER(Lenet5MeDesc), C.POINTER(C.c_void_p)]),
     "bmi_lenet5_me_destroy": (C.c_int, [C.c_void_p]),
     "bmi_lenet5_me_forward_mcd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_uint64] + [C.c_void_p] * 5),
+    "bmi_lenet5_me_forward_exit_staged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_uint64, C.POINTER(ExitRule)] + [C.c_void_p] * 5),
 }
 
 EXPORTS = tuple(_PROTOS.keys())

@@ -494,6 +494,16 @@ struct Lenet5MeArgs {
 };
 int launch_lenet5_me(const Lenet5MeArgs& a, hipStream_t s);
 
+// lenet5_me_exit.hip: that model with the staged early exit inside the launch; an image whose exit-0 statistic exceeds `threshold` never runs
+// conv2, fc1 or exit 1.  Samples 0 .. tc-1 (m.t0 = 0), m.S1 / S2 / SL all given and ZERO on entry, m.logits unused.
+struct Lenet5MeExitArgs {
+    Lenet5MeArgs m;
+    double threshold;        // the image leaves when stat > threshold (a NaN on either side: it stays)
+    int margin;              // 0: max_c p_c, 1: top-1 minus top-2 (exit_rule.h)
+    int* exit_of_image;      // int32 [B]: 0 left at the early exit, 1 ran the main exit
+};
+int launch_lenet5_me_exit(const Lenet5MeExitArgs& a, hipStream_t s);
+
 #define BMI_CHECK_LAUNCH()                                  \
     do {                                                    \
         hipError_t e__ = hipGetLastError();                 \

@@ -2033,6 +2033,10 @@ class MCDEngine(CompiledGraph):
 
 
 LENET5_CHUNK_IMAGES = 512       # csrc/lenet5.hip:lenet5_chunks — a call runs at most min(T, max(1, 512 // B)) sample chunks
+# multiply-adds per image of LeNet5MCEarlyExit's layers (BASELINE.md's host-side model; a sample adds hidden x C per exit it runs), and the
+# layers of the two stages of csrc/lenet5_me_exit.hip
+LENET5_ME_MACS = dict(conv1=28 * 28 * 20 * 25, ex1conv1=2 * 2 * 20 * 500, ex1fc1=80 * 100, conv2=14 * 14 * 20 * 500, fc1=80 * 100, hidden=100)
+LENET5_ME_STAGES = (("conv1", "ex1conv1", "ex1fc1"), ("conv2", "fc1"))
 
 
 class LeNet5Engine:
@@ -2136,6 +2140,46 @@ class LeNet5Engine:
             check_buffer(out, shape, torch.float32, self.device, "out [T, E, B, C]")
         self._forward(x, None, out, t_begin, T, seed)
         return out
+
+    def accumulate_early_exit(self, x, S, T, threshold, seed=0, rule="confidence"):
+        """The sampling half of ``predict_early_exit`` (bmi_lenet5_me_forward_exit_staged, ONE launch) into the ZEROED sums S [3, 2, B, C]:
+        exit 0's rows for every image, exit 1's for the images that stayed; each computed row equals ``accumulate(x, S, 0, T, seed)``'s bit
+        for bit, the others stay zero.  Returns exit_layer int32 [B] on the device (0: left at the early exit, 1: ran the main exit)."""
+        if self.n_exits != 2:
+            raise ValueError("early exiting needs the multi-exit model (LeNet5MCEarlyExit): this engine has one exit")
+        if rule not in _lib.EXIT_RULES:
+            raise ValueError(f"rule must be one of {sorted(_lib.EXIT_RULES)}, got {rule!r}")
+        x = self._check_x(x)
+        B = x.shape[0]
+        check_buffer(S, (3, 2, B, self.out_dim), torch.float64, self.device, "moment buffer S")
+        exit_layer = torch.empty(B, dtype=torch.int32, device=self.device)
+        r_c = _lib.ExitRule(_lib.EXIT_RULES[rule], 0, float(threshold), 0)
+        with torch.cuda.device(self.device):
+            rc = self.lib.bmi_lenet5_me_forward_exit_staged(self.handle, x.data_ptr(), B, int(T), int(seed) & 0xFFFFFFFFFFFFFFFF, C.byref(r_c),
+                                                            S[0].data_ptr(), S[1].data_ptr(), S[2].data_ptr(), exit_layer.data_ptr(),
+                                                            C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+        _lib.check(rc, "bmi_lenet5_me_forward_exit_staged")
+        return exit_layer
+
+    def predict_early_exit(self, x, T, threshold, seed=0, rule="confidence"):
+        """Early exiting inside the fused launch: after the T samples of the early exit an image leaves when its statistic exceeds
+        ``threshold`` (``rule="confidence"`` max_c p_c, ``"margin"`` top-1 minus top-2; p = the T-mean softmax of exit 0, strict comparison),
+        and its workgroup skips conv2, fc1 and the main exit.  Returns ``predict``'s dict (every computed row has ``predict``'s bits; rows of an
+        exit an image never reached are meaningless) plus exit_layer int32 [B], best_preds [B, C] = mean[exit_layer[b], b], active_after [2]
+        (host ints: the images that stayed after exit 0, then 0), and macs_done / macs_full by the per-image model of ``LENET5_ME_MACS``:
+        every image stage 0, the images that stayed stage 1.  Synchronises once, for the count."""
+        B, T = x.shape[0], int(T)
+        S = self.new_moments(B)
+        exit_layer = self.accumulate_early_exit(x, S, T, threshold, seed, rule)
+        r = self.finalize(S, T)
+        r["exit_layer"] = exit_layer
+        r["best_preds"] = r["mean"][exit_layer.long(), torch.arange(B, device=self.device)]
+        stayed = int(exit_layer.sum().item())
+        r["active_after"] = [stayed, 0]
+        stage = [sum(LENET5_ME_MACS[n] for n in names) + T * LENET5_ME_MACS["hidden"] * self.out_dim for names in LENET5_ME_STAGES]
+        r["macs_done"] = B * stage[0] + stayed * stage[1]
+        r["macs_full"] = B * (stage[0] + stage[1])
+        return r
 
     def forward_once(self, x, seed=0, t=0, cnt0=0):
         """One stochastic pass -> the E exits' fp32 logits [B, C], in depth order (``cnt0``: the Masksembles counter of the other engines; there

@@ -1387,6 +1387,20 @@ int bmi_lenet5_me_destroy(bmi_lenet5_me_handle h);
 int bmi_lenet5_me_forward_mcd(bmi_lenet5_me_handle h, const float* x_nchw, int32_t batch, int32_t t_begin, int32_t t_count, uint64_t seed,
                               double* S1, double* S2, double* SL, float* logits, bmi_stream stream);
 
+/* That model with the staged early exit INSIDE the launch (csrc/lenet5_me_exit.hip): samples 0 .. t_count-1 of exit 0 for every image, then
+ * the bmi_exit_rule statistic of exit 0 (float64 p_c = S1[0][b][c] / t_count; BMI_EXIT_CONFIDENCE max_c p_c, BMI_EXIT_MARGIN top-1 minus
+ * top-2, 0 on a tie: the function bmi_forward_mcd_exit_staged runs).  An image whose statistic is > rule->threshold (strict: a NaN threshold
+ * or statistic keeps it) leaves: exit_of_image[b] = 0, and its workgroup runs neither conv2 nor fc1 nor exit 1.  The others run the main
+ * exit's t_count samples as well: exit_of_image[b] = 1.  S1 / S2 / SL (device float64 [2][batch][out_dim]) must be ZERO on entry; every row
+ * the call computes has the bits bmi_lenet5_me_forward_mcd(t_begin = 0) gives, rows of an exit an image never reached stay zero.
+ * exit_of_image: device int32 [batch].  Asynchronous on `stream`, one launch, no allocation, no host read-back: captures into a hipGraph.
+ * Decided before any HIP call: BMI_ERR_INVALID for a NULL handle, x, rule, sum or exit_of_image, batch or t_count below 1, an unknown
+ * criterion, first_exit != 0; BMI_ERR_UNSUPPORTED for rule->ensemble != 0 (only exit 0 is ever tested, and the ensemble of exits 0..0 is
+ * exit 0 itself). */
+int bmi_lenet5_me_forward_exit_staged(bmi_lenet5_me_handle h, const float* x_nchw, int32_t batch, int32_t t_count, uint64_t seed,
+                                      const bmi_exit_rule* rule, double* S1, double* S2, double* SL, int32_t* exit_of_image,
+                                      bmi_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

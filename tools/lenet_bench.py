@@ -3,6 +3,12 @@
 one per batch for the multi-exit model ``LeNet5MCEarlyExit`` (model = "lenet5_me": both exits' moments from one launch).
 
     python tools/lenet_bench.py [--iters 30] [--warmup 5] [--cpu-iters 3]
+
+``--early-exit``: instead, the multi-exit model at B = 1024, T = 100: ``predict`` beside ``predict_early_exit`` (confidence rule) at three
+thresholds taken from that batch's own early-exit statistics, so that none, about half and all of the images leave.  The four calls
+alternate inside every iteration; one JSON line each.
+
+    python tools/lenet_bench.py --early-exit [--batch 1024] [--iters 30] [--warmup 5]
 """
 import argparse
 import json
@@ -21,16 +27,51 @@ from oracle import extra_models as ox  # noqa: E402
 from oracle import mcd  # noqa: E402
 
 
+def early_exit(a, dev, T=100):
+    B = a.batch
+    torch.manual_seed(0)
+    m = synthetic_weights_(bx.LeNet5MCEarlyExit(dropout_p=0.25), 0).to(dev).eval()
+    x = synthetic_images(B, 1234, channels=1, size=28).to(dev)
+    eng = m.engine(dev, max_batch=B)
+    stat = eng.predict(x, T, seed=1)["mean"][0].max(dim=1).values.cpu()
+    calls = [("predict", None)] + [(f"predict_early_exit, {name} leave", float(thr)) for name, thr in
+                                   (("none", stat.max()), ("half", stat.median()), ("all", stat.min() - 1e-6))]
+    run = lambda thr: eng.predict(x, T, seed=1) if thr is None else eng.predict_early_exit(x, T, thr, seed=1)
+    us, last = {name: [] for name, _ in calls}, {}
+    for it in range(a.warmup + a.iters):
+        for name, thr in calls:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            r = run(thr)
+            e1.record()
+            e1.synchronize()
+            if it >= a.warmup:
+                us[name].append(e0.elapsed_time(e1) * 1e3)
+            last[name] = r
+    for name, thr in calls:
+        med = statistics.median(us[name])
+        row = dict(model=m.family, call=name, batch=B, T=T, us_per_call=round(med, 1), us_min=round(min(us[name]), 1), us_max=round(max(us[name]), 1),
+                   iters=a.iters, device=torch.cuda.get_device_name(0))
+        if thr is not None:
+            r = last[name]
+            row.update(threshold=thr, images_left=B - r["active_after"][0], macs_done_over_full=round(r["macs_done"] / r["macs_full"], 4))
+        print(json.dumps(row), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--cpu-iters", type=int, default=3)
     ap.add_argument("--T", type=int, default=10)
+    ap.add_argument("--early-exit", action="store_true", help="T = 100: predict beside predict_early_exit at three thresholds")
+    ap.add_argument("--batch", type=int, default=1024, help="the batch of --early-exit")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("lenet_bench needs a GPU: there is no CPU path to time")
     dev = torch.device("cuda:0")
+    if a.early_exit:
+        return early_exit(a, dev)
     for k in (1, 3, "me"):
         for B in (250, 1024):
             torch.manual_seed(0)
