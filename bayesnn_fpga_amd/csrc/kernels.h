@@ -466,6 +466,9 @@ struct Lenet5Args {
 };
 int lenet5_chunks(int batch, int t_count, int* per_chunk);
 int launch_lenet5(Lenet5Args a, hipStream_t s);
+// lenet5_mask.hip: that LeNet with Masksembles sites (site[i].masks / num_masks; t0 = the mask index of sample 0): one pass per DISTINCT mask of the
+// call, n_chunks / per_chunk from lenet5_chunks(B, min(tc, M))
+int launch_lenet5_mask(Lenet5Args a, hipStream_t s);
 
 // lenet5_me.hip: the multi-exit MC-dropout LeNet-5 of one call in one launch, grid = images; exit 0 = the early exit, exit 1 = the main exit
 struct Lenet5MeArgs {

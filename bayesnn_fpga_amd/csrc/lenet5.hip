@@ -328,6 +328,7 @@ struct bmi_lenet5_s {
     Lenet5Args args;
     bmi_site sites[3];
     size_t partials_bytes;
+    int num_masks;      // > 0: the sites that are on are Masksembles sites of this many masks (lenet5_mask.hip)
 };
 
 extern "C" {
@@ -336,11 +337,20 @@ int bmi_lenet5_create(const bmi_lenet5_desc* d, bmi_lenet5_handle* out) {
     if (!d || !out) return BMI_ERR_INVALID;
     if (!d->conv1_w || !d->conv1_b || !d->conv2_w_frag || !d->conv2_b || !d->fc1_wt || !d->fc1_b || !d->fc2_wt || !d->fc2_b) return BMI_ERR_INVALID;
     if (d->out_dim < 2 || d->out_dim > 32) return BMI_ERR_UNSUPPORTED;
+    int n_mc = 0, num_masks = 0;
     for (const bmi_site& st : d->sites) {
         if (st.kind == BMI_SITE_NONE) continue;
-        if (st.kind != BMI_SITE_ELEMENTWISE) return (st.kind == BMI_SITE_CHANNEL || st.kind == BMI_SITE_MASKSEMBLE) ? BMI_ERR_UNSUPPORTED : BMI_ERR_INVALID;
+        if (st.kind == BMI_SITE_MASKSEMBLE) {      // (host-only: `masks` is never read here)
+            if (!st.masks || st.num_masks < 1) return BMI_ERR_INVALID;
+            if (st.num_masks > 32 || (num_masks && st.num_masks != num_masks)) return BMI_ERR_UNSUPPORTED;
+            num_masks = st.num_masks;
+            continue;
+        }
+        if (st.kind != BMI_SITE_ELEMENTWISE) return st.kind == BMI_SITE_CHANNEL ? BMI_ERR_UNSUPPORTED : BMI_ERR_INVALID;
         if (!(st.p >= 0.f && st.p < 1.f) || st.site_id < 0) return BMI_ERR_INVALID;      // (a NaN fails the comparison)
+        ++n_mc;
     }
+    if (n_mc && num_masks) return BMI_ERR_UNSUPPORTED;      // all MC dropout or all Masksembles, as the reference's global dropout_type
     if (d->partials_bytes && !d->partials) return BMI_ERR_INVALID;
     bmi_lenet5_s* h = new (std::nothrow) bmi_lenet5_s();
     if (!h) return BMI_ERR_NOMEM;
@@ -351,6 +361,7 @@ int bmi_lenet5_create(const bmi_lenet5_desc* d, bmi_lenet5_handle* out) {
     a.part = (double*)d->partials;
     for (int i = 0; i < 3; ++i) h->sites[i] = d->sites[i];
     h->partials_bytes = d->partials_bytes;
+    h->num_masks = num_masks;
     *out = h;
     return BMI_OK;
 }
@@ -366,12 +377,12 @@ int bmi_lenet5_forward_mcd(bmi_lenet5_handle h, const float* x_nchw, int32_t bat
     const bool sums = S1 || S2 || SL;
     if ((sums && !(S1 && S2 && SL)) || (!sums && !logits)) return BMI_ERR_INVALID;
     Lenet5Args a = h->args;
-    const int chunks = lenet5_chunks(batch, t_count, nullptr);
+    const int chunks = lenet5_chunks(batch, h->num_masks ? std::min(t_count, h->num_masks) : t_count, nullptr);      // Masksembles: one pass per distinct mask
     if (sums && chunks > 1 && (size_t)chunks * 3 * batch * a.C * sizeof(double) > h->partials_bytes) return BMI_ERR_NOMEM;
     a.x = x_nchw; a.B = batch; a.b0 = 0; a.t0 = t_begin; a.tc = t_count;
     a.S1 = S1; a.S2 = S2; a.SL = SL; a.logits = logits;
     for (int i = 0; i < 3; ++i) a.site[i] = resolve_site(h->sites[i].kind == BMI_SITE_NONE ? nullptr : &h->sites[i], seed, 0);
-    return launch_lenet5(a, (hipStream_t)stream);
+    return h->num_masks ? launch_lenet5_mask(a, (hipStream_t)stream) : launch_lenet5(a, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -2074,7 +2074,17 @@ class LeNet5Engine:
                 self._keep += [frag(model.ex1conv1), dev(model.ex1conv1.bias), dev(model.ex1fc1.weight.t()), dev(model.ex1fc1.bias),
                                dev(model.ex1linear.weight.t()), dev(model.ex1linear.bias)]
         desc = (_lib.Lenet5MeDesc if self.n_exits == 2 else _lib.Lenet5Desc)(*[t.data_ptr() for t in self._keep], self.out_dim)
-        for i, s in enumerate(model.site_descs()):
+        # Masksembles sites (csrc/lenet5_mask.hip): the masks as device fp32 [M][channels]; sample t of a call runs mask (cnt0 + t) mod M
+        self.num_masks, self._masks = 0, []
+        if getattr(model, "mask_type", "mc") == "mask":
+            for m in model.site_mods():
+                if m is not None:
+                    if not bool(((m.masks == 0) | (m.masks == 1)).all()):
+                        raise ValueError("Masksembles masks must hold nothing but 0 and 1")
+                    self.num_masks = int(m.n)
+                self._masks.append(None if m is None else dev(m.masks))
+        sites = model.site_descs([None if t is None else t.data_ptr() for t in self._masks]) if self.num_masks else model.site_descs()
+        for i, s in enumerate(sites):
             desc.sites[i] = s
         if self.n_exits == 1:
             self._partials = torch.empty(3 * max(self.max_batch, LENET5_CHUNK_IMAGES) * self.out_dim, dtype=torch.float64, device=device)
@@ -2106,8 +2116,10 @@ class LeNet5Engine:
         """Zeroed float64 accumulators S1 = sum p, S2 = sum p^2, SL = sum logit, each [E, B, C]."""
         return torch.zeros(3, self.n_exits, batch, self.out_dim, dtype=torch.float64, device=self.device)
 
-    def _forward(self, x, S, logits, t_begin, t_count, seed):
+    def _forward(self, x, S, logits, t_begin, t_count, seed, cnt0=0):
         x = self._check_x(x)
+        if self.num_masks:      # the entry point has no Masksembles counter of its own: it is folded into the first sample's mask index
+            t_begin = (int(cnt0) + int(t_begin)) % self.num_masks
         sums = (None, None, None) if S is None else tuple(S[i].data_ptr() for i in range(3))
         with torch.cuda.device(self.device):
             rc = getattr(self.lib, self._abi + "_forward_mcd")(self.handle, x.data_ptr(), x.shape[0], int(t_begin), int(t_count),
@@ -2115,10 +2127,11 @@ class LeNet5Engine:
                                                                C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
         _lib.check(rc, self._abi + "_forward_mcd")
 
-    def accumulate(self, x, S, t_begin, t_count, seed=0):
-        """Adds samples t_begin .. t_begin+t_count-1 of batch ``x`` into the moment buffer ``S`` (``new_moments``)."""
+    def accumulate(self, x, S, t_begin, t_count, seed=0, cnt0=0):
+        """Adds samples t_begin .. t_begin+t_count-1 of batch ``x`` into the moment buffer ``S`` (``new_moments``).  ``cnt0``: the Masksembles
+        counter at sample 0 (``model.mask_cnt0()``) — sample t runs mask (cnt0 + t) mod M; nothing else reads it."""
         check_buffer(S, (3, self.n_exits, x.shape[0], self.out_dim), torch.float64, self.device, "moment buffer S")
-        self._forward(x, S, None, t_begin, t_count, seed)
+        self._forward(x, S, None, t_begin, t_count, seed, cnt0)
         return S
 
     def finalize(self, S, t_total):
@@ -2130,15 +2143,15 @@ class LeNet5Engine:
         _lib.check(rc, "bmi_finalize")
         return dict(mean=out[0], var=out[1], logit_mean=out[2])
 
-    def predict(self, x, T, seed=0, t_begin=0):
-        return self.finalize(self.accumulate(x, self.new_moments(x.shape[0]), t_begin, T, seed), T)
+    def predict(self, x, T, seed=0, t_begin=0, cnt0=0):
+        return self.finalize(self.accumulate(x, self.new_moments(x.shape[0]), t_begin, T, seed, cnt0), T)
 
-    def forward_samples(self, x, T, seed=0, t_begin=0, out=None):
+    def forward_samples(self, x, T, seed=0, t_begin=0, out=None, cnt0=0):
         """Per-sample logits fp32 [T, E, B, C]: what T calls of ``model(x)`` return, from one launch."""
         shape = (int(T), self.n_exits, x.shape[0], self.out_dim)
         out = torch.empty(shape, dtype=torch.float32, device=self.device) if out is None else \
             check_buffer(out, shape, torch.float32, self.device, "out [T, E, B, C]")
-        self._forward(x, None, out, t_begin, T, seed)
+        self._forward(x, None, out, t_begin, T, seed, cnt0)
         return out
 
     def accumulate_early_exit(self, x, S, T, threshold, seed=0, rule="confidence"):
@@ -2182,9 +2195,9 @@ class LeNet5Engine:
         return r
 
     def forward_once(self, x, seed=0, t=0, cnt0=0):
-        """One stochastic pass -> the E exits' fp32 logits [B, C], in depth order (``cnt0``: the Masksembles counter of the other engines; there
-        are no such sites here)."""
-        return list(self.forward_samples(x, 1, seed=seed, t_begin=t)[0])
+        """One stochastic pass -> the E exits' fp32 logits [B, C], in depth order (``cnt0``: the Masksembles counter at sample 0: a
+        Masksembles model runs mask (cnt0 + t) mod M and reads neither the seed nor t otherwise)."""
+        return list(self.forward_samples(x, 1, seed=seed, t_begin=t, cnt0=cnt0)[0])
 
 
 class BatchesInFlight:

@@ -20,6 +20,7 @@ import math
 
 from torch import nn
 
+from ..utils import Masksembles1D, Masksembles2D
 from ._engine_mixin import EngineModelMixin
 from .resnet18.resnet18 import MCDropout, _no_cpu
 
@@ -107,31 +108,43 @@ class VGG11MC(EngineModelMixin, nn.Module):
 class LeNet5MC(EngineModelMixin, nn.Module):
     """MC-dropout LeNet-5 on 28x28x1 inputs.  Candidate sites A (behind the first pool), B (behind flatten), C (behind fc1 + ReLU);
     ``num_bayes_layer = k`` switches on the last k (models.py:36-68 with num_layers = 3); k = 1 is the oracle's ``LeNet5MC``.  Sites are
-    elementwise, numbered 0, 1, ... in call order over those that are on."""
+    elementwise, numbered 0, 1, ... in call order over those that are on.  ``mask_type="mask"`` (the hardware flow's ``dropout_type``,
+    model_utils.py:43-52) puts ``Masksembles2D(20)`` / ``Masksembles1D(80)`` / ``Masksembles1D(100)`` of ``num_masks`` masks in their places:
+    csrc/lenet5_mask.hip."""
     family = "lenet5"
     multi_exit = False
     engine_dtype = "f16"
 
-    def __init__(self, num_bayes_layer=1, dropout_p=0.2, out_dim=10):
+    def __init__(self, num_bayes_layer=1, dropout_p=0.2, out_dim=10, mask_type="mc", num_masks=4, mask_scale=2.0):
         super().__init__()
         if num_bayes_layer not in (0, 1, 2, 3):
             raise ValueError("num_bayes_layer must be 0, 1, 2 or 3")
+        if mask_type not in ("mc", "mask"):
+            raise ValueError("mask_type must be 'mc' or 'mask'")
         self.n_exits, self.out_dim, self.dropout_p, self.num_bayes_layer = 1, out_dim, dropout_p, num_bayes_layer
+        self.mask_type, self.num_masks, self.mask_scale = mask_type, num_masks, mask_scale
         self.conv1 = nn.Conv2d(1, 20, 5, padding=2)
         self.conv2 = nn.Conv2d(20, 20, 5, padding=2)
         self.fc1 = nn.Linear(80, 100)
-        for loc, name in enumerate(("drop_a", "drop_b", "drop")):      # ("drop": the oracle's name for site C)
-            if loc >= 3 - num_bayes_layer:
-                setattr(self, name, MCDropout(dropout_p))
+        for loc, (name, cls, channels) in enumerate((("drop_a", Masksembles2D, 20), ("drop_b", Masksembles1D, 80), ("drop", Masksembles1D, 100))):
+            if loc >= 3 - num_bayes_layer:      # ("drop": the oracle's name for site C)
+                setattr(self, name, MCDropout(dropout_p) if mask_type == "mc" else cls(channels, num_masks, mask_scale))
         self.fc2 = nn.Linear(100, out_dim)
         self._init_engine_state()
 
-    def site_descs(self):
-        """The three ``_lib.Site`` of bmi_lenet5_desc, A, B, C: off, or elementwise with the module's p and its call-order id."""
+    def site_mods(self):
+        """The modules of sites A, B, C (None: off)."""
+        return [getattr(self, name, None) for name in ("drop_a", "drop_b", "drop")]
+
+    def site_descs(self, mask_ptrs=None):
+        """The three ``_lib.Site`` of bmi_lenet5_desc, A, B, C: off, elementwise with the module's p and its call-order id, or Masksembles
+        with the module's n and ``mask_ptrs[i]``, the device address of its masks as fp32 [n][channels] (None: a null pointer)."""
         from .. import _lib
-        mods = [getattr(self, name, None) for name in ("drop_a", "drop_b", "drop")]
         ids = iter(range(3))
-        return [_lib.make_site() if m is None else _lib.make_site(_lib.SITE_ELEMENTWISE, next(ids), m.p) for m in mods]
+        return [_lib.make_site() if m is None else
+                _lib.make_site(_lib.SITE_ELEMENTWISE, next(ids), m.p) if isinstance(m, MCDropout) else
+                _lib.make_site(_lib.SITE_MASKSEMBLE, next(ids), 0.0, m.n, mask_ptrs[i] if mask_ptrs else None)
+                for i, m in enumerate(self.site_mods())]
 
     def engine(self, device, max_batch=None, **_):
         """The compiled ``engine.LeNet5Engine`` for ``device`` (built on first use, rebuilt when it must grow)."""

@@ -1304,14 +1304,20 @@ int bmi_dense_f32(const void* in, int32_t in_is_f32 /* 0: 16-bit (unit_entry_dty
  *   fc2_wt        fp32 [100][out_dim], the transpose of fc2.weight; fc2_b fp32 [out_dim]
  *   sites         A, B, C in this order; kind BMI_SITE_NONE = off, else BMI_SITE_ELEMENTWISE with p in [0, 1) and site_id = the call-order
  *                 index among the sites that are on.  Element index over the call's whole batch: A ((b * 14 + y) * 14 + x) * 20 + c,
- *                 B b * 80 + j, C b * 100 + j (csrc/philox.h)
+ *                 B b * 80 + j, C b * 100 + j (csrc/philox.h).  Or BMI_SITE_MASKSEMBLE (`dropout_type == "mask"` of
+ *                 Hardware_Artifact/bayes_hw/models/model_utils.py:43-52; csrc/lenet5_mask.hip) with num_masks = M in [1, 32] and masks =
+ *                 DEVICE fp32 [M][channels]: A [M][20] over the map's channels, B [M][80] over the features j = c * 4 + y * 2 + x,
+ *                 C [M][100]; any nonzero entry keeps, there is no rescale, p and site_id are ignored.  A model is all MC dropout or all
+ *                 Masksembles: the sites that are on share one kind and one M
  *   partials      float64 scratch for the sample chunks of a call, partials_bytes >= 3 * max(batch, 512) * out_dim * 8 for the largest
  *                 batch (a call splits its samples into AT MOST min(t_count, max(1, 512 / batch)) chunks — the samples per chunk are
  *                 rounded up and the count follows from them, t_count = 10 with a bound of 6 runs five chunks of 2: a function of
- *                 (batch, t_count) alone).  The scratch belongs to the handle: ONE stream per handle at a time — two calls on one handle
- *                 from different streams race on it whenever a call has more than one chunk (one handle per stream instead)
- * Create and destroy are host-only.  BMI_ERR_UNSUPPORTED: out_dim outside [2, 32], a channelwise or Masksembles site;
- * BMI_ERR_INVALID: a NULL pointer, p outside [0, 1), an unknown site kind. */
+ *                 (batch, t_count) alone; with Masksembles sites min(t_count, M) passes stand in t_count's place).  The scratch belongs
+ *                 to the handle: ONE stream per handle at a time — two calls on one handle from different streams race on it whenever a
+ *                 call has more than one chunk (one handle per stream instead)
+ * Create and destroy are host-only (`masks` is not read).  BMI_ERR_UNSUPPORTED: out_dim outside [2, 32], a channelwise site, elementwise
+ * and Masksembles sites in one model, unequal num_masks, num_masks > 32; BMI_ERR_INVALID: a NULL pointer (a Masksembles site's masks
+ * included), p outside [0, 1), num_masks < 1, an unknown site kind. */
 typedef struct bmi_lenet5_desc {
     const float* conv1_w;
     const float* conv1_b;
@@ -1336,8 +1342,10 @@ int bmi_lenet5_destroy(bmi_lenet5_handle h);
  * of bmi_forward_mcd; bmi_finalize reads them out) the sums of softmax p, p * p and the logits, every image's samples in ascending t
  * (chunk sums joined in chunk order, no floating-point atomics); `logits` (device fp32 [t_count][1][batch][out_dim], or NULL) receives
  * every sample's logits.  S1 / S2 / SL may be NULL together when `logits` is given.  A sample's logits depend on (seed, t, image)
- * alone.  Asynchronous on `stream`, no allocation: captures into a hipGraph.  Calls on one handle must be ordered on ONE stream (they
- * share the descriptor's `partials`).  BMI_ERR_NOMEM: `partials` too small for this batch. */
+ * alone.  With Masksembles sites sample i of the call uses mask (t_begin + i) mod M — the caller folds its counter into t_begin, there is
+ * no separate one — the seed is not read, and the kernel runs min(t_count, M) passes, each weighted by the samples it stands for (rows
+ * i and i + M of `logits` are equal bit for bit).  Asynchronous on `stream`, no allocation: captures into a hipGraph.  Calls on one
+ * handle must be ordered on ONE stream (they share the descriptor's `partials`).  BMI_ERR_NOMEM: `partials` too small for this batch. */
 int bmi_lenet5_forward_mcd(bmi_lenet5_handle h, const float* x_nchw, int32_t batch, int32_t t_begin, int32_t t_count, uint64_t seed,
                            double* S1, double* S2, double* SL, float* logits, bmi_stream stream);
 

@@ -9,6 +9,12 @@ thresholds taken from that batch's own early-exit statistics, so that none, abou
 alternate inside every iteration; one JSON line each.
 
     python tools/lenet_bench.py --early-exit [--batch 1024] [--iters 30] [--warmup 5]
+
+``--masks M``: instead, the Masksembles model (``mask_type="mask"``, M masks: csrc/lenet5_mask.hip) beside the MC-dropout model at the same
+(num_bayes_layer, B, T): k = 3 at B = 1024 and 250 with T = M and T = 100, k = 1 at B = 1024 with T = M.  The two calls alternate inside every
+iteration; one JSON line each.
+
+    python tools/lenet_bench.py --masks 4 [--iters 30] [--warmup 5]
 """
 import argparse
 import json
@@ -58,6 +64,32 @@ def early_exit(a, dev, T=100):
         print(json.dumps(row), flush=True)
 
 
+def masksembles(a, dev):
+    M = a.masks
+    for k, B, T in ((3, 1024, M), (3, 250, M), (3, 1024, 100), (3, 250, 100), (1, 1024, M)):
+        x = synthetic_images(B, 1234, channels=1, size=28).to(dev)
+        engines = {}
+        for name, kw in (("mc", {}), ("mask", dict(mask_type="mask", num_masks=M))):
+            torch.manual_seed(0)
+            m = synthetic_weights_(bx.LeNet5MC(num_bayes_layer=k, dropout_p=0.25, **kw), 0).to(dev).eval()
+            engines[name] = (m, m.engine(dev, max_batch=B))
+        us = {name: [] for name in engines}
+        for it in range(a.warmup + a.iters):
+            for name, (_, eng) in engines.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                eng.predict(x, T, seed=1)
+                e1.record()
+                e1.synchronize()
+                if it >= a.warmup:
+                    us[name].append(e0.elapsed_time(e1) * 1e3)
+        for name in engines:
+            med = statistics.median(us[name])
+            print(json.dumps(dict(model="lenet5", mask_type=name, num_masks=M if name == "mask" else None, num_bayes_layer=k, batch=B, T=T,
+                                  us_per_call=round(med, 1), us_min=round(min(us[name]), 1), us_max=round(max(us[name]), 1),
+                                  mcd_samples_per_s=round(B * T / med * 1e6), iters=a.iters, device=torch.cuda.get_device_name(0))), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=30)
@@ -66,12 +98,15 @@ def main():
     ap.add_argument("--T", type=int, default=10)
     ap.add_argument("--early-exit", action="store_true", help="T = 100: predict beside predict_early_exit at three thresholds")
     ap.add_argument("--batch", type=int, default=1024, help="the batch of --early-exit")
+    ap.add_argument("--masks", type=int, default=0, help="M > 0: the Masksembles model of M masks beside the MC-dropout model")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("lenet_bench needs a GPU: there is no CPU path to time")
     dev = torch.device("cuda:0")
     if a.early_exit:
         return early_exit(a, dev)
+    if a.masks:
+        return masksembles(a, dev)
     for k in (1, 3, "me"):
         for B in (250, 1024):
             torch.manual_seed(0)
