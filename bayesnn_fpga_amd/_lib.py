@@ -94,6 +94,13 @@ class Lenet5MeDesc(C.Structure):
                [("out_dim", C.c_int32), ("sites", Site * 2)]
 
 
+class QLenet5Desc(C.Structure):
+    """bmi_qlenet5_desc: the eight int8 code buffers in the kernel's layouts, the classes, quant_tbit, quant_ibit, sites A, B, C, the chunk scratch."""
+    _fields_ = [("conv1_q", C.c_void_p), ("conv1_bq", C.c_void_p), ("conv2_q_frag", C.c_void_p), ("conv2_bq", C.c_void_p),
+                ("fc1_q", C.c_void_p), ("fc1_bq", C.c_void_p), ("fc2_q", C.c_void_p), ("fc2_bq", C.c_void_p), ("out_dim", C.c_int32),
+                ("quant_tbit", C.c_int32), ("quant_ibit", C.c_int32), ("sites", Site * 3), ("partials", C.c_void_p), ("partials_bytes", C.c_size_t)]
+
+
 class BmiError(RuntimeError):
     def __init__(self, code, what):
         self.code = code
@@ -233,6 +240,9 @@ _PROTOS = {
     "bmi_lenet5_me_destroy": (C.c_int, [C.c_void_p]),
     "bmi_lenet5_me_forward_mcd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_uint64] + [C.c_void_p] * 5),
     "bmi_lenet5_me_forward_exit_staged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_uint64, C.POINTER(ExitRule)] + [C.c_void_p] * 5),
+    "bmi_qlenet5_create": (C.c_int, [C.POINTER(QLenet5Desc), C.POINTER(C.c_void_p)]),
+    "bmi_qlenet5_destroy": (C.c_int, [C.c_void_p]),
+    "bmi_qlenet5_forward_mcd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_uint64] + [C.c_void_p] * 5),
 }
 
 EXPORTS = tuple(_PROTOS.keys())

@@ -2059,8 +2059,12 @@ class LeNet5Engine:
             device = torch.device("cuda", torch.cuda.current_device())
         self.lib, self.device, self.max_batch, self.out_dim = _lib.lib(), device, int(max_batch), int(model.out_dim)
         self.n_exits = int(model.n_exits)
-        self._abi = "bmi_lenet5_me" if self.n_exits == 2 else "bmi_lenet5"
+        self.quant = None if getattr(model, "quant_tbit", None) is None else (int(model.quant_tbit), int(model.quant_ibit))
+        self._abi = "bmi_lenet5_me" if self.n_exits == 2 else ("bmi_qlenet5" if self.quant else "bmi_lenet5")
         dev = lambda t: t.detach().to(device=device, dtype=torch.float32).contiguous()
+        if self.quant:
+            self.dtype = "i8"      # (an instance attribute: every operand of csrc/qlenet5.hip is a fixed-point code of at most 8 bits)
+            return self._init_quant(model)
 
         def frag(conv):                                              # a 20 -> 20 5x5 conv as MFMA fragments fp16 [76][20][8]
             w = torch.zeros(608, 20)                                 # [k = tap * 24 + channel][output channel], k >= 600 zero
@@ -2091,6 +2095,29 @@ class LeNet5Engine:
             desc.partials, desc.partials_bytes = self._partials.data_ptr(), self._partials.numel() * 8
         self.handle = C.c_void_p()
         _lib.check(getattr(self.lib, self._abi + "_create")(C.byref(desc), C.byref(self.handle)), self._abi + "_create")
+
+    def _init_quant(self, model):
+        """The quantised model (csrc/qlenet5.hip): the fp32 parameters become int8 codes here (``quant.weight_codes``), conv2's in the 16 + 4
+        channel fragment layout of bmi_qlenet5_desc."""
+        from .quant import weight_codes
+        W, I = self.quant
+        q = lambda t: weight_codes(t.cpu(), W, I).to(torch.int8)
+        q2 = q(model.conv2.weight).permute(2, 3, 0, 1).reshape(25, 20, 20)      # [tap][output channel][input channel]
+        frag = torch.zeros(36, 20, 16, dtype=torch.int8)
+        frag[:25, :, :] = q2[:, :, :16]                                         # groups 0..27: tap g, channels 0..15
+        tail = torch.zeros(32, 20, 4, dtype=torch.int8)
+        tail[:25] = q2[:, :, 16:]                                               # groups 28..35: four taps x channels 16..19
+        frag[28:] = tail.view(8, 4, 20, 4).permute(0, 2, 1, 3).reshape(8, 20, 16)
+        self._keep = [t.contiguous().to(self.device) for t in (q(model.conv1.weight).reshape(20, 25), q(model.conv1.bias), frag, q(model.conv2.bias),
+                                                               q(model.fc1.weight), q(model.fc1.bias), q(model.fc2.weight), q(model.fc2.bias))]
+        desc = _lib.QLenet5Desc(*[t.data_ptr() for t in self._keep], self.out_dim, W, I)
+        self.num_masks, self._masks = 0, []
+        for i, s in enumerate(model.site_descs()):
+            desc.sites[i] = s
+        self._partials = torch.empty(3 * max(self.max_batch, LENET5_CHUNK_IMAGES) * self.out_dim, dtype=torch.float64, device=self.device)
+        desc.partials, desc.partials_bytes = self._partials.data_ptr(), self._partials.numel() * 8
+        self.handle = C.c_void_p()
+        _lib.check(self.lib.bmi_qlenet5_create(C.byref(desc), C.byref(self.handle)), "bmi_qlenet5_create")
 
     def close(self):
         if getattr(self, "handle", None) is not None and self.handle.value:

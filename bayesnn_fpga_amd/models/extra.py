@@ -110,17 +110,25 @@ class LeNet5MC(EngineModelMixin, nn.Module):
     ``num_bayes_layer = k`` switches on the last k (models.py:36-68 with num_layers = 3); k = 1 is the oracle's ``LeNet5MC``.  Sites are
     elementwise, numbered 0, 1, ... in call order over those that are on.  ``mask_type="mask"`` (the hardware flow's ``dropout_type``,
     model_utils.py:43-52) puts ``Masksembles2D(20)`` / ``Masksembles1D(80)`` / ``Masksembles1D(100)`` of ``num_masks`` masks in their places:
-    csrc/lenet5_mask.hip."""
+    csrc/lenet5_mask.hip.  ``quant_tbit = W`` (with ``quant_ibit = I``) makes it the hardware flow's QKeras model ``T_Qlenet_bayes``
+    (t_qmodels_bayes.py:38-96): the same fp32 parameters, quantised to W-bit codes when the engine is built (``quant.weight_codes``) and run in
+    fixed point by csrc/qlenet5.hip; MC dropout only."""
     family = "lenet5"
     multi_exit = False
     engine_dtype = "f16"
 
-    def __init__(self, num_bayes_layer=1, dropout_p=0.2, out_dim=10, mask_type="mc", num_masks=4, mask_scale=2.0):
+    def __init__(self, num_bayes_layer=1, dropout_p=0.2, out_dim=10, mask_type="mc", num_masks=4, mask_scale=2.0, quant_tbit=None, quant_ibit=0):
         super().__init__()
         if num_bayes_layer not in (0, 1, 2, 3):
             raise ValueError("num_bayes_layer must be 0, 1, 2 or 3")
         if mask_type not in ("mc", "mask"):
             raise ValueError("mask_type must be 'mc' or 'mask'")
+        if quant_tbit is not None:
+            if mask_type != "mc":
+                raise ValueError("the quantised LeNet-5 takes MC-dropout sites only: quant_tbit needs mask_type='mc'")
+            if not (isinstance(quant_tbit, int) and isinstance(quant_ibit, int) and 2 <= quant_tbit <= 8 and 0 <= quant_ibit < quant_tbit):
+                raise ValueError("quant_tbit must be an int in [2, 8] and quant_ibit one in [0, quant_tbit - 1]")
+        self.quant_tbit, self.quant_ibit = quant_tbit, quant_ibit
         self.n_exits, self.out_dim, self.dropout_p, self.num_bayes_layer = 1, out_dim, dropout_p, num_bayes_layer
         self.mask_type, self.num_masks, self.mask_scale = mask_type, num_masks, mask_scale
         self.conv1 = nn.Conv2d(1, 20, 5, padding=2)

@@ -1409,6 +1409,52 @@ int bmi_lenet5_me_forward_exit_staged(bmi_lenet5_me_handle h, const float* x_nch
                                       const bmi_exit_rule* rule, double* S1, double* S2, double* SL, int32_t* exit_of_image,
                                       bmi_stream stream);
 
+/* The QUANTISED LeNet-5 of the reference's hardware flow as ONE fused kernel per call (csrc/qlenet5.hip): T_Qlenet_bayes,
+ * Hardware_Artifact/bayes_hw/models/t_qmodels_bayes.py:38-96 — the LeNet of bmi_lenet5_desc with every kernel and bias through
+ * quantized_bits(W, I, alpha = 1) and every activation through quantized_relu(W); W = quant_tbit in [2, 8], I = quant_ibit in [0, W - 1],
+ * F = W - 1 - I.  The arithmetic is fixed point and is the contract (rne: round half to even):
+ *   weight / bias code  q = clip(rne(w * 2^F), -2^(W-1), 2^(W-1) - 1), value q * 2^-F;  activation code a = clip(rne(v * 2^W), 0, 2^W - 1),
+ *   value a * 2^-W;  input x8 = clip(rne(x * 2^8), 0, 255) from the fp32 image, value x8 * 2^-8 (eight fractional bits: this library's choice)
+ *   conv1      acc = sum x8 * q1 (int32), pre = acc + (b1 << 8), a1 = clip(rne(pre / 2^(7-I)), 0, 2^W - 1) on integers, 2x2 max on codes
+ *   conv2, fc1, fc2   acc = sum keep * a * q (int32, a dropped element adds 0), y = fadd_rn(fmul_rn(float(acc) * 2^-(W+F), d), b * 2^-F) in
+ *              fp32 — two rounded operations, never one FMA; d = fl32(1 / fl32(1 - p)) of the site in front of the layer, 1 where it is off.
+ *              conv2 and fc1 end in a = clip(rintf(y * 2^W), 0, 2^W - 1) (conv2: then the 7x7 max on codes); fc2's y is the fp32 logit
+ * Sites, their element numbering and keep bits, feature order, softmax, float64 sums, sample chunks and `partials` are bmi_lenet5_desc's.
+ *
+ * The descriptor holds DEVICE buffers of int8 CODES (the caller quantises):
+ *   conv1_q       [20][25], conv1_bq [20]
+ *   conv2_q_frag  [36][20][16]: 16-byte MFMA fragments, group g, output channel n, byte i.  g < 28: tap g (= ky * 5 + kx), input channel i;
+ *                 g >= 28: tap (g - 28) * 4 + i / 4, input channel 16 + i % 4; zero where the tap is >= 25.  conv2_bq [20]
+ *   fc1_q         [100][80] (torch's fc1.weight), fc1_bq [100];  fc2_q [out_dim][100] (torch's fc2.weight), fc2_bq [out_dim]
+ * Create and destroy are host-only.  BMI_ERR_UNSUPPORTED: quant_tbit outside [2, 8], quant_ibit outside [0, quant_tbit - 1], out_dim
+ * outside [2, 32], a Masksembles or channelwise site; BMI_ERR_INVALID: a NULL pointer, p outside [0, 1), a negative site id, an unknown
+ * site kind. */
+typedef struct bmi_qlenet5_desc {
+    const int8_t* conv1_q;
+    const int8_t* conv1_bq;
+    const int8_t* conv2_q_frag;
+    const int8_t* conv2_bq;
+    const int8_t* fc1_q;
+    const int8_t* fc1_bq;
+    const int8_t* fc2_q;
+    const int8_t* fc2_bq;
+    int32_t out_dim;
+    int32_t quant_tbit;
+    int32_t quant_ibit;
+    bmi_site sites[3];
+    void* partials;
+    size_t partials_bytes;
+} bmi_qlenet5_desc;
+typedef struct bmi_qlenet5_s* bmi_qlenet5_handle;
+
+int bmi_qlenet5_create(const bmi_qlenet5_desc* desc, bmi_qlenet5_handle* out);
+int bmi_qlenet5_destroy(bmi_qlenet5_handle h);
+
+/* bmi_lenet5_forward_mcd over the quantised model: the same arguments, sums, logits layout, chunk rule and stream contract.  The fp32
+ * logits are reproduced bit for bit by an integer loop on the host (tests/test_qlenet5.py). */
+int bmi_qlenet5_forward_mcd(bmi_qlenet5_handle h, const float* x_nchw, int32_t batch, int32_t t_begin, int32_t t_count, uint64_t seed,
+                            double* S1, double* S2, double* SL, float* logits, bmi_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,11 @@ alternate inside every iteration; one JSON line each.
 iteration; one JSON line each.
 
     python tools/lenet_bench.py --masks 4 [--iters 30] [--warmup 5]
+
+``--quant W,I``: instead, the quantised model (``quant_tbit=W, quant_ibit=I``: csrc/qlenet5.hip) beside the fp16 model at the same
+(num_bayes_layer, B, T): k = 1 and 3, B = 250 and 1024, T = 10 and 100.  The two calls alternate inside every iteration; one JSON line each.
+
+    python tools/lenet_bench.py --quant 6,0 [--iters 30] [--warmup 5]
 """
 import argparse
 import json
@@ -90,8 +95,38 @@ def masksembles(a, dev):
                                   mcd_samples_per_s=round(B * T / med * 1e6), iters=a.iters, device=torch.cuda.get_device_name(0))), flush=True)
 
 
+def quantised(a, dev):
+    W, I = (int(v) for v in a.quant.split(","))
+    for k in (1, 3):
+        for B in (250, 1024):
+            for T in (10, 100):
+                x = synthetic_images(B, 1234, channels=1, size=28).to(dev)
+                engines = {}
+                for name, kw in (("fp16", {}), ("quant", dict(quant_tbit=W, quant_ibit=I))):
+                    torch.manual_seed(0)
+                    m = synthetic_weights_(bx.LeNet5MC(num_bayes_layer=k, dropout_p=0.25, **kw), 0).to(dev).eval()
+                    engines[name] = (m, m.engine(dev, max_batch=B))
+                us = {name: [] for name in engines}
+                for it in range(a.warmup + a.iters):
+                    for name, (_, eng) in engines.items():
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        e0.record()
+                        eng.predict(x, T, seed=1)
+                        e1.record()
+                        e1.synchronize()
+                        if it >= a.warmup:
+                            us[name].append(e0.elapsed_time(e1) * 1e3)
+                for name in engines:
+                    med = statistics.median(us[name])
+                    print(json.dumps(dict(model="lenet5", kernel="qlenet5_kernel" if name == "quant" else "lenet5_kernel", quant=[W, I] if name == "quant" else None,
+                                          num_bayes_layer=k, batch=B, T=T, us_per_call=round(med, 1), us_min=round(min(us[name]), 1),
+                                          us_max=round(max(us[name]), 1), mcd_samples_per_s=round(B * T / med * 1e6), iters=a.iters,
+                                          device=torch.cuda.get_device_name(0))), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--quant", default="", help="W,I: the quantised model (csrc/qlenet5.hip) beside the fp16 model at equal (k, B, T)")
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--cpu-iters", type=int, default=3)
@@ -107,6 +142,8 @@ def main():
         return early_exit(a, dev)
     if a.masks:
         return masksembles(a, dev)
+    if a.quant:
+        return quantised(a, dev)
     for k in (1, 3, "me"):
         for B in (250, 1024):
             torch.manual_seed(0)
