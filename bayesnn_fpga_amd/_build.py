@@ -12,11 +12,11 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libbayesnn_fpga_amd.so")
-SOURCES = ["conv_igemm.hip", "conv_igemm_wide.hip", "conv3x3_patch.hip", "conv3x3_pw.hip", "conv3x3_s2.hip", "conv1x1_stream.hip", "conv1x1_seam.hip", "conv_exact.hip", "conv_split.hip", "misc_kernels.hip", "dense_f32.hip", "head_fused.hip", "head_fused_temp.hip", "head_fused_vec.hip", "head_fused_mat.hip", "calibration.hip", "ensemble.hip", "pass_accuracy.hip", "reliability.hip", "reliability_kde.hip", "reliability_classwise.hip", "conformal.hip", "ranking.hip", "ranking_sort.hip", "exit_policy.hip", "votes.hip", "votes_rows.hip", "lenet5.hip", "lenet5_me.hip", "lenet5_me_exit.hip", "lenet5_mask.hip", "qlenet5.hip", "engine.hip"]
+SOURCES = ["conv_igemm.hip", "conv_igemm_wide.hip", "conv3x3_patch.hip", "conv3x3_pw.hip", "conv3x3_s2.hip", "conv1x1_stream.hip", "conv1x1_seam.hip", "conv_exact.hip", "conv_split.hip", "misc_kernels.hip", "dense_f32.hip", "head_fused.hip", "head_fused_temp.hip", "head_fused_vec.hip", "head_fused_mat.hip", "calibration.hip", "ensemble.hip", "pass_accuracy.hip", "reliability.hip", "reliability_kde.hip", "reliability_classwise.hip", "conformal.hip", "ranking.hip", "ranking_sort.hip", "exit_policy.hip", "votes.hip", "votes_rows.hip", "lenet5.hip", "lenet5_me.hip", "lenet5_me_exit.hip", "lenet5_mask.hip", "qlenet5.hip", "qlenet5_me.hip", "engine.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 # per source, on top of FLAGS: new sources are compiled without the packed fp32 instructions (v_pk_*_f32); the earlier ones keep their code
 NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-EXTRA_FLAGS = {"ranking_sort.hip": NO_PK_F32, "conformal.hip": NO_PK_F32, "lenet5.hip": NO_PK_F32, "lenet5_me.hip": NO_PK_F32, "lenet5_me_exit.hip": NO_PK_F32, "lenet5_mask.hip": NO_PK_F32, "qlenet5.hip": NO_PK_F32}
+EXTRA_FLAGS = {"ranking_sort.hip": NO_PK_F32, "conformal.hip": NO_PK_F32, "lenet5.hip": NO_PK_F32, "lenet5_me.hip": NO_PK_F32, "lenet5_me_exit.hip": NO_PK_F32, "lenet5_mask.hip": NO_PK_F32, "qlenet5.hip": NO_PK_F32, "qlenet5_me.hip": NO_PK_F32}
 
 
 def _hipcc():

@@ -101,6 +101,13 @@ class QLenet5Desc(C.Structure):
                 ("quant_tbit", C.c_int32), ("quant_ibit", C.c_int32), ("sites", Site * 3), ("partials", C.c_void_p), ("partials_bytes", C.c_size_t)]
 
 
+class QLenet5MeDesc(C.Structure):
+    """bmi_qlenet5_me_desc: the trunk's eight int8 code buffers, the early exit's six, the classes, quant_tbit, quant_ibit, the two exits' sites."""
+    _fields_ = [(n, C.c_void_p) for n in ("conv1_q", "conv1_bq", "conv2_q_frag", "conv2_bq", "fc1_q", "fc1_bq", "fc2_q", "fc2_bq", "ex1conv1_q_frag",
+                                          "ex1conv1_bq", "ex1fc1_q", "ex1fc1_bq", "ex1linear_q", "ex1linear_bq")] + \
+               [("out_dim", C.c_int32), ("quant_tbit", C.c_int32), ("quant_ibit", C.c_int32), ("sites", Site * 2)]
+
+
 class BmiError(RuntimeError):
     def __init__(self, code, what):
         self.code = code
@@ -243,6 +250,9 @@ _PROTOS = {
     "bmi_qlenet5_create": (C.c_int, [C.POINTER(QLenet5Desc), C.POINTER(C.c_void_p)]),
     "bmi_qlenet5_destroy": (C.c_int, [C.c_void_p]),
     "bmi_qlenet5_forward_mcd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_uint64] + [C.c_void_p] * 5),
+    "bmi_qlenet5_me_create": (C.c_int, [C.POINTER(QLenet5MeDesc), C.POINTER(C.c_void_p)]),
+    "bmi_qlenet5_me_destroy": (C.c_int, [C.c_void_p]),
+    "bmi_qlenet5_me_forward_mcd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_uint64] + [C.c_void_p] * 5),
 }
 
 EXPORTS = tuple(_PROTOS.keys())

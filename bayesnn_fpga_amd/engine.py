@@ -2047,7 +2047,8 @@ class LeNet5Engine:
     batches into sample chunks whose float64 scratch belongs to the engine, so such an engine serves ONE stream at a time (a second stream
     takes a second engine); the multi-exit kernel has no scratch.  Replaces ``FullAnalysis._get_output``
     (SA/train/results_analyzer.py:236-248) over the Keras LeNet of Hardware_Artifact/bayes_hw/models/models.py:34-73 and over
-    T_Qlenet_bayes_me of Hardware_Artifact/bayes_hw/models/t_qmodels_bayes_me.py:41-147."""
+    T_Qlenet_bayes_me of Hardware_Artifact/bayes_hw/models/t_qmodels_bayes_me.py:41-147.  A model with ``quant_tbit`` set runs in fixed point
+    on int8 codes instead (csrc/qlenet5.hip / csrc/qlenet5_me.hip, ``dtype == "i8"``): the same interface, without the staged early exit."""
     dtype = "f16"          # (the convs' MFMA operands; everything else is fp32 — there is nothing to choose)
     workspace = None
 
@@ -2060,10 +2061,10 @@ class LeNet5Engine:
         self.lib, self.device, self.max_batch, self.out_dim = _lib.lib(), device, int(max_batch), int(model.out_dim)
         self.n_exits = int(model.n_exits)
         self.quant = None if getattr(model, "quant_tbit", None) is None else (int(model.quant_tbit), int(model.quant_ibit))
-        self._abi = "bmi_lenet5_me" if self.n_exits == 2 else ("bmi_qlenet5" if self.quant else "bmi_lenet5")
+        self._abi = ("bmi_qlenet5" if self.quant else "bmi_lenet5") + ("_me" if self.n_exits == 2 else "")
         dev = lambda t: t.detach().to(device=device, dtype=torch.float32).contiguous()
         if self.quant:
-            self.dtype = "i8"      # (an instance attribute: every operand of csrc/qlenet5.hip is a fixed-point code of at most 8 bits)
+            self.dtype = "i8"      # (an instance attribute: every operand of csrc/qlenet5.hip / qlenet5_me.hip is a fixed-point code of at most 8 bits)
             return self._init_quant(model)
 
         def frag(conv):                                              # a 20 -> 20 5x5 conv as MFMA fragments fp16 [76][20][8]
@@ -2097,27 +2098,36 @@ class LeNet5Engine:
         _lib.check(getattr(self.lib, self._abi + "_create")(C.byref(desc), C.byref(self.handle)), self._abi + "_create")
 
     def _init_quant(self, model):
-        """The quantised model (csrc/qlenet5.hip): the fp32 parameters become int8 codes here (``quant.weight_codes``), conv2's in the 16 + 4
-        channel fragment layout of bmi_qlenet5_desc."""
+        """The quantised models (csrc/qlenet5.hip, csrc/qlenet5_me.hip): the fp32 parameters become int8 codes here (``quant.weight_codes``),
+        the two 20 -> 20 convs' in the 16 + 4 channel fragment layout of bmi_qlenet5_desc.  The multi-exit kernel has no scratch."""
         from .quant import weight_codes
         W, I = self.quant
         q = lambda t: weight_codes(t.cpu(), W, I).to(torch.int8)
-        q2 = q(model.conv2.weight).permute(2, 3, 0, 1).reshape(25, 20, 20)      # [tap][output channel][input channel]
-        frag = torch.zeros(36, 20, 16, dtype=torch.int8)
-        frag[:25, :, :] = q2[:, :, :16]                                         # groups 0..27: tap g, channels 0..15
-        tail = torch.zeros(32, 20, 4, dtype=torch.int8)
-        tail[:25] = q2[:, :, 16:]                                               # groups 28..35: four taps x channels 16..19
-        frag[28:] = tail.view(8, 4, 20, 4).permute(0, 2, 1, 3).reshape(8, 20, 16)
-        self._keep = [t.contiguous().to(self.device) for t in (q(model.conv1.weight).reshape(20, 25), q(model.conv1.bias), frag, q(model.conv2.bias),
-                                                               q(model.fc1.weight), q(model.fc1.bias), q(model.fc2.weight), q(model.fc2.bias))]
-        desc = _lib.QLenet5Desc(*[t.data_ptr() for t in self._keep], self.out_dim, W, I)
+
+        def frag(conv):                                                         # a 20 -> 20 5x5 conv as MFMA fragments int8 [36][20][16]
+            q2 = q(conv.weight).permute(2, 3, 0, 1).reshape(25, 20, 20)         # [tap][output channel][input channel]
+            f = torch.zeros(36, 20, 16, dtype=torch.int8)
+            f[:25, :, :] = q2[:, :, :16]                                        # groups 0..27: tap g, channels 0..15
+            tail = torch.zeros(32, 20, 4, dtype=torch.int8)
+            tail[:25] = q2[:, :, 16:]                                           # groups 28..35: four taps x channels 16..19
+            f[28:] = tail.view(8, 4, 20, 4).permute(0, 2, 1, 3).reshape(8, 20, 16)
+            return f
+
+        keep = [q(model.conv1.weight).reshape(20, 25), q(model.conv1.bias), frag(model.conv2), q(model.conv2.bias),
+                q(model.fc1.weight), q(model.fc1.bias), q(model.fc2.weight), q(model.fc2.bias)]
+        if self.n_exits == 2:
+            keep += [frag(model.ex1conv1), q(model.ex1conv1.bias), q(model.ex1fc1.weight), q(model.ex1fc1.bias), q(model.ex1linear.weight),
+                     q(model.ex1linear.bias)]
+        self._keep = [t.contiguous().to(self.device) for t in keep]
+        desc = (_lib.QLenet5MeDesc if self.n_exits == 2 else _lib.QLenet5Desc)(*[t.data_ptr() for t in self._keep], self.out_dim, W, I)
         self.num_masks, self._masks = 0, []
         for i, s in enumerate(model.site_descs()):
             desc.sites[i] = s
-        self._partials = torch.empty(3 * max(self.max_batch, LENET5_CHUNK_IMAGES) * self.out_dim, dtype=torch.float64, device=self.device)
-        desc.partials, desc.partials_bytes = self._partials.data_ptr(), self._partials.numel() * 8
+        if self.n_exits == 1:
+            self._partials = torch.empty(3 * max(self.max_batch, LENET5_CHUNK_IMAGES) * self.out_dim, dtype=torch.float64, device=self.device)
+            desc.partials, desc.partials_bytes = self._partials.data_ptr(), self._partials.numel() * 8
         self.handle = C.c_void_p()
-        _lib.check(self.lib.bmi_qlenet5_create(C.byref(desc), C.byref(self.handle)), "bmi_qlenet5_create")
+        _lib.check(getattr(self.lib, self._abi + "_create")(C.byref(desc), C.byref(self.handle)), self._abi + "_create")
 
     def close(self):
         if getattr(self, "handle", None) is not None and self.handle.value:
@@ -2181,12 +2191,19 @@ class LeNet5Engine:
         self._forward(x, None, out, t_begin, T, seed, cnt0)
         return out
 
+    def _check_staged(self):
+        """What the staged early exit refuses, decided before any device call."""
+        if self.n_exits != 2:
+            raise ValueError("early exiting needs the multi-exit model (LeNet5MCEarlyExit): this engine has one exit")
+        if self.quant:
+            raise ValueError("the in-launch staged early exit exists for the fp16 model only (csrc/lenet5_me_exit.hip): this engine runs the "
+                             "quantised multi-exit model (quant_tbit is set)")
+
     def accumulate_early_exit(self, x, S, T, threshold, seed=0, rule="confidence"):
         """The sampling half of ``predict_early_exit`` (bmi_lenet5_me_forward_exit_staged, ONE launch) into the ZEROED sums S [3, 2, B, C]:
         exit 0's rows for every image, exit 1's for the images that stayed; each computed row equals ``accumulate(x, S, 0, T, seed)``'s bit
         for bit, the others stay zero.  Returns exit_layer int32 [B] on the device (0: left at the early exit, 1: ran the main exit)."""
-        if self.n_exits != 2:
-            raise ValueError("early exiting needs the multi-exit model (LeNet5MCEarlyExit): this engine has one exit")
+        self._check_staged()
         if rule not in _lib.EXIT_RULES:
             raise ValueError(f"rule must be one of {sorted(_lib.EXIT_RULES)}, got {rule!r}")
         x = self._check_x(x)
@@ -2208,6 +2225,7 @@ class LeNet5Engine:
         exit an image never reached are meaningless) plus exit_layer int32 [B], best_preds [B, C] = mean[exit_layer[b], b], active_after [2]
         (host ints: the images that stayed after exit 0, then 0), and macs_done / macs_full by the per-image model of ``LENET5_ME_MACS``:
         every image stage 0, the images that stayed stage 1.  Synchronises once, for the count."""
+        self._check_staged()
         B, T = x.shape[0], int(T)
         S = self.new_moments(B)
         exit_layer = self.accumulate_early_exit(x, S, T, threshold, seed, rule)

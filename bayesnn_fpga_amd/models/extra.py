@@ -14,7 +14,8 @@ as 1x1 convolutions on [N,1,1,C] tensors (same MFMA kernel, same fused dropout e
   as ONE fused kernel per call (csrc/lenet5.hip) behind ``engine.LeNet5Engine``, not through ``MCDEngine``.
 * ``LeNet5MCEarlyExit``   — the multi-exit form of that LeNet, Hardware_Artifact/bayes_hw/models/t_qmodels_bayes_me.py:41-147
   (``T_Qlenet_bayes_me``): an early exit on the pooled conv1 map and one MC-dropout layer in front of each exit's classifier; ONE fused
-  kernel per call as well (csrc/lenet5_me.hip), behind the same ``engine.LeNet5Engine``.
+  kernel per call as well (csrc/lenet5_me.hip), behind the same ``engine.LeNet5Engine``; with ``quant_tbit`` the QKeras model itself, in
+  fixed point (csrc/qlenet5_me.hip).
 """
 import math
 
@@ -171,13 +172,18 @@ class LeNet5MCEarlyExit(EngineModelMixin, nn.Module):
     pooled conv1 map [B, 20, 14, 14] — conv 5x5x20 with stride 7 (Keras "same" at stride 7 on a 14-wide map pads nothing: outputs 2x2),
     ReLU, flatten, Linear 80 -> 100, ReLU, Linear 100 -> C.  ``dropout_exit`` puts one elementwise MC-dropout layer on the 100 hidden units
     in front of each exit's classifier.  Exits in depth order: exit 0 is the early exit, exit 1 (the last) the main exit; site ids follow
-    that call order."""
+    that call order.  ``quant_tbit = W`` (with ``quant_ibit = I``) makes it the QKeras model ``T_Qlenet_bayes_me`` itself
+    (t_qmodels_bayes_me.py:41-147): the same modules and fp32 parameters, quantised to W-bit codes when the engine is built
+    (``quant.weight_codes``) and run in fixed point by csrc/qlenet5_me.hip."""
     family = "lenet5_me"
     multi_exit = True
     engine_dtype = "f16"
 
-    def __init__(self, dropout_exit=True, dropout_p=0.2, out_dim=10):
+    def __init__(self, dropout_exit=True, dropout_p=0.2, out_dim=10, quant_tbit=None, quant_ibit=0):
         super().__init__()
+        if quant_tbit is not None and not (isinstance(quant_tbit, int) and isinstance(quant_ibit, int) and 2 <= quant_tbit <= 8 and 0 <= quant_ibit < quant_tbit):
+            raise ValueError("quant_tbit must be an int in [2, 8] and quant_ibit one in [0, quant_tbit - 1]")
+        self.quant_tbit, self.quant_ibit = quant_tbit, quant_ibit
         self.n_exits, self.out_dim, self.dropout_p, self.dropout_exit = 2, out_dim, dropout_p, dropout_exit
         self.conv1 = nn.Conv2d(1, 20, 5, padding=2)
         self.conv2 = nn.Conv2d(20, 20, 5, padding=2)

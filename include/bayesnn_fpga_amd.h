@@ -1455,6 +1455,59 @@ int bmi_qlenet5_destroy(bmi_qlenet5_handle h);
 int bmi_qlenet5_forward_mcd(bmi_qlenet5_handle h, const float* x_nchw, int32_t batch, int32_t t_begin, int32_t t_count, uint64_t seed,
                             double* S1, double* S2, double* SL, float* logits, bmi_stream stream);
 
+/* The QUANTISED multi-exit LeNet-5 as ONE fused kernel per call (csrc/qlenet5_me.hip): T_Qlenet_bayes_me,
+ * Hardware_Artifact/bayes_hw/models/t_qmodels_bayes_me.py:41-147, as QKeras defines it — the network of bmi_lenet5_me_desc with every kernel
+ * and bias through quantized_bits(W, I, alpha = 1) and every activation through quantized_relu(W).  The arithmetic is bmi_qlenet5_desc's,
+ * layer for layer (W = quant_tbit in [2, 8], I = quant_ibit in [0, W - 1], F = W - 1 - I, rne: round half to even):
+ *   input and conv1   x8 = clip(rne(x * 2^8), 0, 255), acc = sum x8 * q1 (int32), pre = acc + (b1 << 8), a1 = clip(rne(pre / 2^(7-I)), 0,
+ *              2^W - 1) on integers, 2x2 max on codes
+ *   conv2, fc1, fc2, ex1conv1, ex1fc1, ex1linear   acc = sum keep * a * q (int32, a dropped unit adds 0; |acc| < 2^24), y =
+ *              fadd_rn(fmul_rn(float(acc) * 2^-(W+F), d), b * 2^-F) in fp32 — two rounded operations, never one FMA; d = fl32(1 / fl32(1 - p))
+ *              for fc2 and ex1linear when their site is on, 1 everywhere else.  The hidden layers end in a = clip(rintf(y * 2^W), 0, 2^W - 1)
+ *              (conv2: then the 7x7 max on codes); the two classifiers' y are the fp32 logits
+ * Geometry, feature orders (j = c * 4 + y * 2 + x), the sites' numbering, element indices (b * 100 + j) and keep bits, and the exits' order
+ * (exit 0 = the early exit) are bmi_lenet5_me_desc's.
+ *
+ * The descriptor holds DEVICE buffers of int8 CODES (the caller quantises): the trunk's eight in the layouts of bmi_qlenet5_desc and
+ *   ex1conv1_q_frag  [36][20][16], conv2_q_frag's layout over ex1conv1's [20][20][5][5] codes; ex1conv1_bq [20]
+ *   ex1fc1_q         [100][80] (torch's ex1fc1.weight), ex1fc1_bq [100]
+ *   ex1linear_q      [out_dim][100] (torch's ex1linear.weight), ex1linear_bq [out_dim]
+ *   sites            [0] in front of ex1linear, [1] in front of fc2: BMI_SITE_NONE = off, else BMI_SITE_ELEMENTWISE with p in [0, 1)
+ * Create and destroy are host-only.  BMI_ERR_UNSUPPORTED: quant_tbit outside [2, 8], quant_ibit outside [0, quant_tbit - 1], out_dim
+ * outside [2, 32], a Masksembles or channelwise site; BMI_ERR_INVALID: a NULL pointer, p outside [0, 1), a negative site id, an unknown
+ * site kind. */
+typedef struct bmi_qlenet5_me_desc {
+    const int8_t* conv1_q;
+    const int8_t* conv1_bq;
+    const int8_t* conv2_q_frag;
+    const int8_t* conv2_bq;
+    const int8_t* fc1_q;
+    const int8_t* fc1_bq;
+    const int8_t* fc2_q;
+    const int8_t* fc2_bq;
+    const int8_t* ex1conv1_q_frag;
+    const int8_t* ex1conv1_bq;
+    const int8_t* ex1fc1_q;
+    const int8_t* ex1fc1_bq;
+    const int8_t* ex1linear_q;
+    const int8_t* ex1linear_bq;
+    int32_t out_dim;
+    int32_t quant_tbit;
+    int32_t quant_ibit;
+    bmi_site sites[2];
+} bmi_qlenet5_me_desc;
+typedef struct bmi_qlenet5_me_s* bmi_qlenet5_me_handle;
+
+int bmi_qlenet5_me_create(const bmi_qlenet5_me_desc* desc, bmi_qlenet5_me_handle* out);
+int bmi_qlenet5_me_destroy(bmi_qlenet5_me_handle h);
+
+/* bmi_lenet5_me_forward_mcd over the quantised model: the same arguments, sums [2][batch][out_dim] and their order (even-indexed samples of
+ * the call, odd-indexed samples, then the two sums; no floating-point atomics), logits layout [t_count][2][batch][out_dim] and stream
+ * contract; one launch, no scratch.  NULL arguments are refused before any HIP call.  The fp32 logits of both exits are reproduced bit
+ * for bit by an integer loop on the host (tests/test_qlenet5_me.py). */
+int bmi_qlenet5_me_forward_mcd(bmi_qlenet5_me_handle h, const float* x_nchw, int32_t batch, int32_t t_begin, int32_t t_count, uint64_t seed,
+                               double* S1, double* S2, double* SL, float* logits, bmi_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,7 +17,9 @@ iteration; one JSON line each.
     python tools/lenet_bench.py --masks 4 [--iters 30] [--warmup 5]
 
 ``--quant W,I``: instead, the quantised model (``quant_tbit=W, quant_ibit=I``: csrc/qlenet5.hip) beside the fp16 model at the same
-(num_bayes_layer, B, T): k = 1 and 3, B = 250 and 1024, T = 10 and 100.  The two calls alternate inside every iteration; one JSON line each.
+(num_bayes_layer, B, T): k = 1 and 3, B = 250 and 1024, T = 10 and 100; then the multi-exit pair, quantised ``LeNet5MCEarlyExit``
+(csrc/qlenet5_me.hip) beside the fp16 one, at B = 250 and 1024, T = 3, 10 and 100.  The two calls alternate inside every iteration; one JSON
+line each.
 
     python tools/lenet_bench.py --quant 6,0 [--iters 30] [--warmup 5]
 """
@@ -97,14 +99,19 @@ def masksembles(a, dev):
 
 def quantised(a, dev):
     W, I = (int(v) for v in a.quant.split(","))
-    for k in (1, 3):
+    # (model, its kernels fp16 / quantised, num_bayes_layer, T): the single-exit pair, then the multi-exit pair (T = 3 and 10: the sample
+    # counts of the reference's hardware and software flows)
+    single = lambda k: (lambda **kw: bx.LeNet5MC(num_bayes_layer=k, dropout_p=0.25, **kw))
+    multi = lambda **kw: bx.LeNet5MCEarlyExit(dropout_p=0.25, **kw)
+    plans = [(single(k), ("lenet5_kernel", "qlenet5_kernel"), k, (10, 100)) for k in (1, 3)] + [(multi, ("lenet5_me_kernel", "qlenet5_me_kernel"), 2, (3, 10, 100))]
+    for make, kernels, k, samples in plans:
         for B in (250, 1024):
-            for T in (10, 100):
+            for T in samples:
                 x = synthetic_images(B, 1234, channels=1, size=28).to(dev)
                 engines = {}
                 for name, kw in (("fp16", {}), ("quant", dict(quant_tbit=W, quant_ibit=I))):
                     torch.manual_seed(0)
-                    m = synthetic_weights_(bx.LeNet5MC(num_bayes_layer=k, dropout_p=0.25, **kw), 0).to(dev).eval()
+                    m = synthetic_weights_(make(**kw), 0).to(dev).eval()
                     engines[name] = (m, m.engine(dev, max_batch=B))
                 us = {name: [] for name in engines}
                 for it in range(a.warmup + a.iters):
@@ -116,9 +123,9 @@ def quantised(a, dev):
                         e1.synchronize()
                         if it >= a.warmup:
                             us[name].append(e0.elapsed_time(e1) * 1e3)
-                for name in engines:
+                for name, (m, _) in engines.items():
                     med = statistics.median(us[name])
-                    print(json.dumps(dict(model="lenet5", kernel="qlenet5_kernel" if name == "quant" else "lenet5_kernel", quant=[W, I] if name == "quant" else None,
+                    print(json.dumps(dict(model=m.family, kernel=kernels[name == "quant"], quant=[W, I] if name == "quant" else None,
                                           num_bayes_layer=k, batch=B, T=T, us_per_call=round(med, 1), us_min=round(min(us[name]), 1),
                                           us_max=round(max(us[name]), 1), mcd_samples_per_s=round(B * T / med * 1e6), iters=a.iters,
                                           device=torch.cuda.get_device_name(0))), flush=True)
